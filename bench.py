@@ -2,15 +2,19 @@
 """Headline benchmark: images/sec of the part-detector + spatial-model forward (ending in
 argmax coordinates on the device) on 480x720x3 synthetic images, K=9, on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]      (N>1: launched by torch.distributed.run)
 
 A step = one pass of the whole path over one batch per GPU (BASELINE.json configs[1]: batch 64,
 fp32) with inputs already resident in HBM.  Ranks shard by batch (images are independent);
 the only collective is the all-gather of [B,2,9] int32 coordinates (main.py:573-574 -> RCCL).
+A plain run measures the headline configuration only: it sets up, runs one untimed first step (the library allocates its buffers) and W
+warm-up steps, times exactly K steps, writes the outputs of the last one (--dump-outputs DIR: DIR/<name>.npy) and prints the line.
+Everything else is measured with --full only: the second, profiled timed region of the same K steps (`ms_per_step_profiled`), the
+`roofline` object, the other configurations, the CPU baseline and bench_detail.json.
 Rank 0 prints ONE compact JSON line (<= 4 KB: it must survive the driver's 8 KB stdout tail) as its LAST line of stdout: the driver's
-contract keys, `roofline`, `cpu_baseline` and `configs` = {name: {value, ms_per_step, dtype, frac, bound}} for every other configuration
+contract keys and, with --full, `roofline`, `cpu_baseline` and `configs` = {name: {value, ms_per_step, dtype, frac, bound}} for every other configuration
 measured in the same run; the verbose record of every configuration goes to `bench_detail.json` (gpurun_out/ when that directory exists,
-else the working directory) and to stderr.  `roofline` (dominant
+else the working directory; --full only) and to stderr.  `roofline` (dominant
 kernel = the hand-written channel GEMM `cgemm_split_kernel` of the frequency-domain conv4_fullres /
 conv5 layers -- or, with the direct kernels selected, their MFMA implicit-GEMM launch -- timed live
 with HIP events on its stream) and `cpu_baseline` (the CPU restatement timed on the host cores;
@@ -202,17 +206,35 @@ def resident_inputs(B, rank, dev):
     return x, torso
 
 
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most this much in all
+PARAM_SAMPLE = 1 << 20            # --dump-outputs --train: elements of the fixed sample of the updated parameters
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (the int32 coordinates are exact in it)."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the limit of %d' % (total, DUMP_MAX_BYTES))
+    for k, a in host.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+
+
 def dist_on():
     """Is there a process group?  Every barrier / collective of this script runs when there is one -- also with ONE rank (torch.distributed.run
     --nproc-per-node 1, JCM_BENCH_FORCE_DIST=1: the nccl branch executed on a one-GPU box, tests/test_gpu_bench_ranks.py)."""
     return dist.is_available() and dist.is_initialized()
 
 
-def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32_conv=None, config_name=None, micro_batch=None, conv9_fft=None, fft_single=None, fft_t16=None, agree=False):
+def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32_conv=None, config_name=None, micro_batch=None, conv9_fft=None, fft_single=None, fft_t16=None, agree=False,
+               dump=None):
     """Time `args.steps` steps of one (dtype, batch) configuration; returns the result dict on
     rank 0 (None elsewhere).  Timed region: barrier + synchronize on both sides, max over ranks.
     f32_conv='split16': the fp32 path with its stride-1 layers on the direct fp16x3 split kernels (conv_split.hip).
-    B is the rank's batch per step; jcm_forward walks it in micro-batches (256 bf16 / 64 fp32 unless `micro_batch`)."""
+    B is the rank's batch per step; jcm_forward walks it in micro-batches (256 bf16 / 64 fp32 unless `micro_batch`).
+    Only with --full: the second, profiled timed region and the roofline object built from its per-launch events.
+    dump: directory that receives the arrays of the last timed step (--dump-outputs; rank 0)."""
     eng = Engine(device=local_rank, precision=dtype, f32_conv=f32_conv, micro_batch=micro_batch, conv9_fft=conv9_fft, fft_single=fft_single, fft_t16=fft_t16,
                  fft_fuse=args.fft_fuse).load_params(params)
     x, torso = resident_inputs(B, rank, dev)                                          # resident in HBM
@@ -220,19 +242,21 @@ def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32
 
     def step():
         r = eng.forward(x, torso if use_sm else None, use_sm=use_sm, want_prob=False)
-        return jdist.allgather_coords(r['sm_coords' if use_sm else 'pd_coords'])
+        return r, jdist.allgather_coords(r['sm_coords' if use_sm else 'pd_coords'])
 
-    # The per-launch HIP events of the roofline object come from a pool inside the library: one profiled step
-    # before the warm-up creates them, so that the profiled region below only records (2 hipEventRecord per conv
-    # launch, no event creation or destruction).
-    eng.set_profile(True)
+    # One step before the warm-up: the library allocates its buffers on the first call.  With --full it is profiled: the per-launch HIP
+    # events of the roofline object come from a pool inside the library, this step creates them, so that the profiled region below only
+    # records (2 hipEventRecord per conv launch, no event creation or destruction).
+    if args.full:
+        eng.set_profile(True)
     step()
-    eng.set_profile(False)
+    if args.full:
+        eng.set_profile(False)
     for _ in range(args.warmup):
         step()
 
     def timed_region(profile):
-        """EXACTLY args.steps steps between barrier + synchronize on both sides; returns (wall seconds, per-step HIP-event ms, coords)."""
+        """EXACTLY args.steps steps between barrier + synchronize on both sides; returns (wall seconds, per-step HIP-event ms, (result, coords) of the last step)."""
         torch.cuda.synchronize()
         if dist_on():
             dist.barrier()
@@ -244,7 +268,7 @@ def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32
         t0 = time.perf_counter()
         for i in range(args.steps):
             evs[i].record()
-            c = step()
+            last = step()
         evs[args.steps].record()
         torch.cuda.synchronize()
         if dist_on():
@@ -258,13 +282,14 @@ def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32
             t = torch.tensor([d], dtype=torch.float64, device=dev if dist.get_backend() == 'nccl' else 'cpu')
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             d = float(t.item())
-        return d, ms, c
+        return d, ms, last
 
     # Two timed regions of the same K steps (round 6): the first WITHOUT the library's per-launch events -- `value` / `ms_per_step`, what a
     # caller of jcm_forward gets --, the second WITH them (two hipEventRecord around every conv layer, its GEMM and the spatial model): the roofline object's
-    # launch durations, and `ms_per_step_profiled` beside the headline so that the cost of the instrumentation is on the line.
-    dt, step_ms, coords = timed_region(False)
-    dt_prof, step_ms_prof, _ = timed_region(True)
+    # launch durations, and `ms_per_step_profiled` beside the headline so that the cost of the instrumentation is on the line.  The second one: --full only.
+    dt, step_ms, (last_r, coords) = timed_region(False)
+    if args.full:
+        dt_prof, step_ms_prof, _ = timed_region(True)
     assert coords.shape == (world * B, 2, 9)
     out = None
     if rank == 0 and args.layer_times:
@@ -273,49 +298,12 @@ def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32
                 ms, n = eng.profile_read(scope)     # destructive read: the roofline object below then sees no launches
                 print('layer %-18s %8.3f ms/launch  (%d launches)' % (scope, ms / max(n, 1), n), file=sys.stderr)
     if rank == 0:
-        tot_ms, tot_n, tot_flops = 0.0, 0, 0.0
-        for scope, fl in FLOPS_DOMINANT.items():
-            ms, n = eng.profile_read(scope)
-            tot_ms, tot_n = tot_ms + ms, tot_n + n
-            tot_flops += fl / (16 if args.debug else 1) * B * args.steps if n else 0.0     # n = steps x micro-batches launches cover steps x B images
         kname = eng.conv_kernel_name('conv5', min(B, micro_batch or (256 if dtype == 'bf16' else 64)), 60, 90) if not args.debug else 'debug'
-        layer_ms = tot_ms / max(tot_n, 1)                      # average duration of a whole conv4_fullres / conv5 layer
         freq_domain = kname.startswith('conv_fft')
         mb = micro_batch or (256 if dtype == 'bf16' else 64)
-        gemm = None
-        if freq_domain:
-            # wide 9x9 layers in the frequency domain: the dominant kernel is the channel GEMM cgemm_split_kernel (one complex matrix
-            # product per frequency); its own executed bf16-MFMA FLOPs and algorithmic HBM bytes, its own HIP events
-            # 16-bit parts per operand and real products per multiply: fp32 handles two scaled fp16 parts / three products; bf16 handles ONE scaled fp16
-            # part / one product (default, "fft_single") or two bf16 parts / three products
-            single = dtype == 'bf16' and fft_single is not False
-            np_parts, nprod = (1, 1) if single else (2, 3)
-            mrows = min(B, mb)
-            mt = gemm_mtile(dtype, mrows)
-            rows_p = -(-mrows // mt) * mt
-            tot_ms, tot_n, tot_flops, tot_bytes, tot_flops32 = 0.0, 0, 0.0, 0.0, 0.0
-            for scope, (cin, cout) in GEMM_LAYERS.items():
-                ms, n = eng.profile_read(scope + '/gemm')
-                tot_ms, tot_n = tot_ms + ms, tot_n + n
-                tot_flops32 += 8.0 * cin * cout * FFT_FREQS * mrows * n              # complex multiply-adds as real FLOPs
-                tot_flops += nprod * 8.0 * cin * cout * FFT_FREQS * mrows * n        # executed on the bf16 matrix cores
-                # activation spectra and filter spectra (2 B x np parts x re|im per complex number), product spectra (complex fp32; complex fp16 on the
-                # default route of bf16 handles, whose intermediates are all 16-bit)
-                ybytes = 4 if single and fft_t16 is not False else 8
-                tot_bytes += FFT_FREQS * (rows_p * cin * 4 * np_parts + cin * cout * 4 * np_parts + mrows * cout * ybytes) * n
-            gemm = {'np_parts': np_parts, 'products': nprod, 'flops32_per_launch': tot_flops32 / max(tot_n, 1), 'bytes_per_launch': tot_bytes / max(tot_n, 1)}
-        launch_ms = tot_ms / max(tot_n, 1)                     # average launch duration (HIP events, launch stream)
-        flops_launch = tot_flops / max(tot_n, 1)               # average algorithmic (direct kernels) / executed (split GEMM) FLOPs per launch
-        achieved = flops_launch / (launch_ms * 1e-3) / 1e12 if tot_n else None
-        peak = PEAK_TFLOPS['bf16' if freq_domain else dtype]     # the channel GEMM runs on the bf16 matrix cores for both handle types
-        fp32_equiv = None
-        if f32_conv == 'split16' and achieved:      # the roofline of these kernels is the 16-bit matrix-core peak
-            fp32_equiv = achieved
-            achieved = achieved * 3
-            peak = PEAK_TFLOPS['bf16']
         value = world * B * args.steps / dt
         out = {
-            'value': value, 'ms_per_step': dt / args.steps * 1e3, 'ms_per_step_profiled': dt_prof / args.steps * 1e3,
+            'value': value, 'ms_per_step': dt / args.steps * 1e3,
             # the arithmetic the path computes in: exact fp32 MFMA chain, or fp32 operands carried as 16-bit parts
             # 'f32' alone = the exact fp32 MFMA accumulation chain; the default fp32 route carries every fp32 spectrum as two scaled fp16 parts (22 bits)
             'dtype': ((('bf16(fp16 spectra + fp16 row-transformed tensors, fft)' if fft_single is not False else 'bf16(bf16x2 spectra, fft)') if freq_domain else 'bf16') if dtype == 'bf16' else
@@ -329,66 +317,109 @@ def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32
                        'collective': 'all_gather coords int32 [B,2,9]'},
             'path_tflops': value * FLOPS_PD_SM / (16 if args.debug else 1) / 1e12,
             'scaling': 'weak',
-            'roofline': {'bound': 'mfma', 'kernel': ('cgemm_split_kernel: channel GEMM of the frequency-domain 9x9 layers (conv4_fullres + conv5; %s)' if freq_domain else
-                                                     'conv_igemm 9x9, 60x90 maps (conv4_fullres + conv5 launches; %s)')
-                                   % ('hand-written, v_mfma_f32_32x32x16_%s, operands split into %d %s parts (%d real products per multiply), one complex [B x Cin] x [Cin x Cout] '
-                                      'product per frequency of the 64 x 96 transform = 3136 per launch, LDS-DMA operand rings; achieved = executed bf16 MFMA FLOPs / GEMM time'
-                                      % ('bf16' if dtype == 'bf16' and gemm['np_parts'] == 2 else 'f16', gemm['np_parts'], 'bf16' if dtype == 'bf16' and gemm['np_parts'] == 2 else 'fp16 (scaled spectra)', gemm['products'])
-                                      if freq_domain else
-                                      'fp32 operands as 2 fp16 parts, 3 x fp16 MFMA 32x32x16 per k16 step, 12x32 patch x 256 ch; achieved = executed fp16 MFMA FLOPs (3 x algorithmic) against the fp16 peak'
-                                      if f32_conv == 'split16' else
-                                      'fp32 MFMA 32x32x2, 128-pixel strip tiles x 128 ch' if dtype == 'fp32' else
-                                      'bf16 MFMA 32x32x16, 384-pixel strips of the flattened batch x 256 ch, LDS-DMA halo + weight rings' if kname == 'conv_strip_bf16_kernel'
-                                      else 'bf16 MFMA 32x32x16, 12x32 patch x 256 ch'),
-                         'kernel_name': kname,
-                         'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': (achieved / peak) if achieved else None,
-                         'launch_ms': launch_ms, 'launches': tot_n, 'flops_per_launch': flops_launch},
         }
-        rf = out['roofline']
-        tkey = '%s_b%d_fft%s' % (dtype, min(B, mb), '_bf16x2' if dtype == 'bf16' and fft_single is False else '') if freq_domain else '%s%s_b%d' % (dtype, '_' + f32_conv if f32_conv == 'split16' else '', min(B, mb))
-        rf['traffic'], rf['traffic_source'] = pmc_traffic(tkey) if not args.debug else (None, None)
-        # SURVEY 8d's yardstick beside the executed-work one: images/s x 413.19 GFLOP (the direct-convolution FLOPs of the path) / MFMA peak of the handle's type
-        rf['algorithmic_frac'] = out['path_tflops'] / PEAK_TFLOPS[dtype]
         if freq_domain:
-            # the GEMM against both ceilings; `bound` names the one it sits closer to
-            gbs = gemm['bytes_per_launch'] / (launch_ms * 1e-3) / 1e9 if tot_n else None
-            useful = gemm['flops32_per_launch'] / (launch_ms * 1e-3) / 1e12 if tot_n else None      # complex-GEMM FLOPs without the split multiplier
-            rf['mfma'] = {'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': (achieved / peak) if achieved else None,
-                          'fp32_equivalent_tflops': useful, 'useful_frac': (useful / peak) if useful else None,
-                          'note': 'achieved counts the %d real products per multiply of the split operands as executed FLOPs; useful_frac does not' % gemm['products']}
-            rf['hbm'] = {'achieved': gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': (gbs / PEAK_HBM_GBS) if gbs else None,
-                         'algorithmic_bytes_per_launch': gemm['bytes_per_launch']}
-            if gbs and achieved and gbs / PEAK_HBM_GBS > achieved / peak:
-                rf.update({'bound': 'hbm', 'achieved': gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS})
-            rf['layer_ms'] = layer_ms  # the whole layer: four transform kernels + the GEMM
-            # the whole step against the HBM roof: bytes of every kernel of one step (2 x FETCH_SIZE + WRITE_SIZE summed over the committed counter pass of
-            # this configuration) / measured step time
-            sb, ssrc = step_traffic(tkey) if not args.debug else (None, None)
-            if sb:
-                imgs = min(B, mb)
-                gbs_step = sb * (B / imgs) / (dt / args.steps) / 1e9
-                rf['step'] = {'bytes_per_step': sb * (B / imgs), 'bytes_per_image': sb / imgs, 'achieved': gbs_step, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                              'frac': gbs_step / PEAK_HBM_GBS, 'traffic_source': ssrc,
-                              'note': 'SURVEY 8d prices the direct formulation at ~77 MB of activations per image; the five-pass frequency-domain route moves several times that'}
             out['path_tflops_note'] = 'images/s x direct-convolution FLOPs: the wide 9x9 layers execute 35x fewer in the frequency domain'
+        if args.full:
+            out['ms_per_step_profiled'] = dt_prof / args.steps * 1e3
+            tot_ms, tot_n, tot_flops = 0.0, 0, 0.0
+            for scope, fl in FLOPS_DOMINANT.items():
+                ms, n = eng.profile_read(scope)
+                tot_ms, tot_n = tot_ms + ms, tot_n + n
+                tot_flops += fl / (16 if args.debug else 1) * B * args.steps if n else 0.0     # n = steps x micro-batches launches cover steps x B images
+            layer_ms = tot_ms / max(tot_n, 1)                      # average duration of a whole conv4_fullres / conv5 layer
+            gemm = None
+            if freq_domain:
+                # wide 9x9 layers in the frequency domain: the dominant kernel is the channel GEMM cgemm_split_kernel (one complex matrix
+                # product per frequency); its own executed bf16-MFMA FLOPs and algorithmic HBM bytes, its own HIP events
+                # 16-bit parts per operand and real products per multiply: fp32 handles two scaled fp16 parts / three products; bf16 handles ONE scaled fp16
+                # part / one product (default, "fft_single") or two bf16 parts / three products
+                single = dtype == 'bf16' and fft_single is not False
+                np_parts, nprod = (1, 1) if single else (2, 3)
+                mrows = min(B, mb)
+                mt = gemm_mtile(dtype, mrows)
+                rows_p = -(-mrows // mt) * mt
+                tot_ms, tot_n, tot_flops, tot_bytes, tot_flops32 = 0.0, 0, 0.0, 0.0, 0.0
+                for scope, (cin, cout) in GEMM_LAYERS.items():
+                    ms, n = eng.profile_read(scope + '/gemm')
+                    tot_ms, tot_n = tot_ms + ms, tot_n + n
+                    tot_flops32 += 8.0 * cin * cout * FFT_FREQS * mrows * n              # complex multiply-adds as real FLOPs
+                    tot_flops += nprod * 8.0 * cin * cout * FFT_FREQS * mrows * n        # executed on the bf16 matrix cores
+                    # activation spectra and filter spectra (2 B x np parts x re|im per complex number), product spectra (complex fp32; complex fp16 on the
+                    # default route of bf16 handles, whose intermediates are all 16-bit)
+                    ybytes = 4 if single and fft_t16 is not False else 8
+                    tot_bytes += FFT_FREQS * (rows_p * cin * 4 * np_parts + cin * cout * 4 * np_parts + mrows * cout * ybytes) * n
+                gemm = {'np_parts': np_parts, 'products': nprod, 'flops32_per_launch': tot_flops32 / max(tot_n, 1), 'bytes_per_launch': tot_bytes / max(tot_n, 1)}
+            launch_ms = tot_ms / max(tot_n, 1)                     # average launch duration (HIP events, launch stream)
+            flops_launch = tot_flops / max(tot_n, 1)               # average algorithmic (direct kernels) / executed (split GEMM) FLOPs per launch
+            achieved = flops_launch / (launch_ms * 1e-3) / 1e12 if tot_n else None
+            peak = PEAK_TFLOPS['bf16' if freq_domain else dtype]     # the channel GEMM runs on the bf16 matrix cores for both handle types
+            fp32_equiv = None
+            if f32_conv == 'split16' and achieved:      # the roofline of these kernels is the 16-bit matrix-core peak
+                fp32_equiv = achieved
+                achieved = achieved * 3
+                peak = PEAK_TFLOPS['bf16']
+            out['roofline'] = {'bound': 'mfma', 'kernel': ('cgemm_split_kernel: channel GEMM of the frequency-domain 9x9 layers (conv4_fullres + conv5; %s)' if freq_domain else
+                                                         'conv_igemm 9x9, 60x90 maps (conv4_fullres + conv5 launches; %s)')
+                                       % ('hand-written, v_mfma_f32_32x32x16_%s, operands split into %d %s parts (%d real products per multiply), one complex [B x Cin] x [Cin x Cout] '
+                                          'product per frequency of the 64 x 96 transform = 3136 per launch, LDS-DMA operand rings; achieved = executed bf16 MFMA FLOPs / GEMM time'
+                                          % ('bf16' if dtype == 'bf16' and gemm['np_parts'] == 2 else 'f16', gemm['np_parts'], 'bf16' if dtype == 'bf16' and gemm['np_parts'] == 2 else 'fp16 (scaled spectra)', gemm['products'])
+                                          if freq_domain else
+                                          'fp32 operands as 2 fp16 parts, 3 x fp16 MFMA 32x32x16 per k16 step, 12x32 patch x 256 ch; achieved = executed fp16 MFMA FLOPs (3 x algorithmic) against the fp16 peak'
+                                          if f32_conv == 'split16' else
+                                          'fp32 MFMA 32x32x2, 128-pixel strip tiles x 128 ch' if dtype == 'fp32' else
+                                          'bf16 MFMA 32x32x16, 384-pixel strips of the flattened batch x 256 ch, LDS-DMA halo + weight rings' if kname == 'conv_strip_bf16_kernel'
+                                          else 'bf16 MFMA 32x32x16, 12x32 patch x 256 ch'),
+                             'kernel_name': kname,
+                             'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': (achieved / peak) if achieved else None,
+                             'launch_ms': launch_ms, 'launches': tot_n, 'flops_per_launch': flops_launch}
+            rf = out['roofline']
+            tkey = '%s_b%d_fft%s' % (dtype, min(B, mb), '_bf16x2' if dtype == 'bf16' and fft_single is False else '') if freq_domain else '%s%s_b%d' % (dtype, '_' + f32_conv if f32_conv == 'split16' else '', min(B, mb))
+            rf['traffic'], rf['traffic_source'] = pmc_traffic(tkey) if not args.debug else (None, None)
+            # SURVEY 8d's yardstick beside the executed-work one: images/s x 413.19 GFLOP (the direct-convolution FLOPs of the path) / MFMA peak of the handle's type
+            rf['algorithmic_frac'] = out['path_tflops'] / PEAK_TFLOPS[dtype]
+            if freq_domain:
+                # the GEMM against both ceilings; `bound` names the one it sits closer to
+                gbs = gemm['bytes_per_launch'] / (launch_ms * 1e-3) / 1e9 if tot_n else None
+                useful = gemm['flops32_per_launch'] / (launch_ms * 1e-3) / 1e12 if tot_n else None      # complex-GEMM FLOPs without the split multiplier
+                rf['mfma'] = {'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': (achieved / peak) if achieved else None,
+                              'fp32_equivalent_tflops': useful, 'useful_frac': (useful / peak) if useful else None,
+                              'note': 'achieved counts the %d real products per multiply of the split operands as executed FLOPs; useful_frac does not' % gemm['products']}
+                rf['hbm'] = {'achieved': gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': (gbs / PEAK_HBM_GBS) if gbs else None,
+                             'algorithmic_bytes_per_launch': gemm['bytes_per_launch']}
+                if gbs and achieved and gbs / PEAK_HBM_GBS > achieved / peak:
+                    rf.update({'bound': 'hbm', 'achieved': gbs, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS})
+                rf['layer_ms'] = layer_ms  # the whole layer: four transform kernels + the GEMM
+                # the whole step against the HBM roof: bytes of every kernel of one step (2 x FETCH_SIZE + WRITE_SIZE summed over the committed counter pass of
+                # this configuration) / measured step time
+                sb, ssrc = step_traffic(tkey) if not args.debug else (None, None)
+                if sb:
+                    imgs = min(B, mb)
+                    gbs_step = sb * (B / imgs) / (dt / args.steps) / 1e9
+                    rf['step'] = {'bytes_per_step': sb * (B / imgs), 'bytes_per_image': sb / imgs, 'achieved': gbs_step, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                                  'frac': gbs_step / PEAK_HBM_GBS, 'traffic_source': ssrc,
+                                  'note': 'SURVEY 8d prices the direct formulation at ~77 MB of activations per image; the five-pass frequency-domain route moves several times that'}
+            if use_sm:
+                # an FFT spatial model reports HBM GB/s beside the MFMA yardstick: ~14 MB of algorithmic traffic per image (10 forward + 81
+                # product + 81 inverse spectra / frames); the fused route (sm_fused.hip) keeps all but the 10 likelihood spectra on the CU -- measured
+                # bytes per image (2 x FETCH_SIZE + WRITE_SIZE of its two kernels) in profiles/pmc_traffic.json
+                ms, n = eng.profile_read('sm')
+                if n:
+                    imgs = B * args.steps / n                      # images per sm launch group (micro-batch)
+                    gbs = SM_ALGO_BYTES_PER_IMAGE * imgs / (ms / n * 1e-3) / 1e9
+                    smb, smsrc = sm_traffic(dtype)
+                    rf['sm'] = {'ms_per_call': ms / n, 'images_per_call': imgs, 'algorithmic_bytes_per_image': SM_ALGO_BYTES_PER_IMAGE, 'achieved': gbs,
+                                'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS, 'traffic_bytes_per_image': smb, 'traffic_source': smsrc,
+                                'mfma_yardstick_tflops': FLOPS_SM * imgs / (ms / n * 1e-3) / 1e12}
+            if fp32_equiv is not None:
+                out['roofline']['fp32_equivalent_tflops'] = fp32_equiv
+                out['roofline']['x_fp32_mfma_peak'] = fp32_equiv / PEAK_TFLOPS['fp32']
         free_b, total_b = torch.cuda.mem_get_info(dev)
         out['device_mem_used_gb'] = (total_b - free_b) / 1e9      # everything resident on this rank's GPU right after the timed steps (inputs, weights, filter spectra, workspace)
         med = float(np.median(step_ms))
         out['median_ms_per_step'] = med
         out['value_median'] = B / (med * 1e-3)      # this rank's images / median step (HIP events on the launch stream; no barrier inside)
         out['step_ms_min_max'] = [float(min(step_ms)), float(max(step_ms))]
-        if use_sm:
-            # an FFT spatial model reports HBM GB/s beside the MFMA yardstick: ~14 MB of algorithmic traffic per image (10 forward + 81
-            # product + 81 inverse spectra / frames); the fused route (sm_fused.hip) keeps all but the 10 likelihood spectra on the CU -- measured
-            # bytes per image (2 x FETCH_SIZE + WRITE_SIZE of its two kernels) in profiles/pmc_traffic.json
-            ms, n = eng.profile_read('sm')
-            if n:
-                imgs = B * args.steps / n                      # images per sm launch group (micro-batch)
-                gbs = SM_ALGO_BYTES_PER_IMAGE * imgs / (ms / n * 1e-3) / 1e9
-                smb, smsrc = sm_traffic(dtype)
-                rf['sm'] = {'ms_per_call': ms / n, 'images_per_call': imgs, 'algorithmic_bytes_per_image': SM_ALGO_BYTES_PER_IMAGE, 'achieved': gbs,
-                            'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS, 'traffic_bytes_per_image': smb, 'traffic_source': smsrc,
-                            'mfma_yardstick_tflops': FLOPS_SM * imgs / (ms / n * 1e-3) / 1e12}
         if agree_ref is not None:
             # north_star judges the bf16 configuration on arg-max agreement: this engine's coordinates against the fp32 default engine's on
             # the same resident images (evaluation.py:15-24, main.py:389-397)
@@ -403,9 +434,9 @@ def run_config(args, dtype, B, params, world, rank, local_rank, dev, use_sm, f32
                 a = argmax_agreement(agree_ref['pd_prob'], agree_ref['pd_coords'], r['pd_prob'], r['pd_coords'])
                 out['argmax_agreement']['pd'] = {'exact': a['exact'], 'within1': a['within1'], 'mean_dist': a['mean_dist'], 'safe': a['safe']}
             del r
-        if fp32_equiv is not None:
-            out['roofline']['fp32_equivalent_tflops'] = fp32_equiv
-            out['roofline']['x_fp32_mfma_peak'] = fp32_equiv / PEAK_TFLOPS['fp32']
+        if dump:
+            # what a caller of the timed path receives from its last step: rank 0's coordinates, and with N > 1 the all-gathered ones
+            dump_outputs(dump, dict(last_r, **({'coords_all_ranks': coords} if world > 1 else {})))
     eng.close()
     del x, torso
     torch.cuda.empty_cache()
@@ -418,9 +449,10 @@ FLOPS_CONV1 = 1_088_640_000 + 272_160_000 + 68_040_000          # conv1 full/hal
 FLOPS_TRAIN = 3 * FLOPS_PD_SM - FLOPS_CONV1
 
 
-def run_train(args, B, params, world, rank, local_rank, dev, use_sm, prec=None, f32_conv='args'):
+def run_train(args, B, params, world, rank, local_rank, dev, use_sm, prec=None, f32_conv='args', dump=None):
     """`--train`: time the joint training step (loss + gradients, gradient all-reduce, clip + Adam, table
-    refresh) on B images per GPU; data-parallel, one RCCL all-reduce of the flat gradient buffer per step."""
+    refresh) on B images per GPU; data-parallel, one RCCL all-reduce of the flat gradient buffer per step.
+    dump: directory that receives the losses of the last timed step and a fixed sample of the parameters it updated (--dump-outputs; rank 0)."""
     from joint_cnn_mrf_amd.train import Trainer
     prec = prec or args.dtype or 'fp32'
     f32_conv = args.f32_conv if f32_conv == 'args' else f32_conv
@@ -514,6 +546,10 @@ def run_train(args, B, params, world, rank, local_rank, dev, use_sm, prec=None, 
                                      'launch_ms': kern['wgrad:conv5']['launch_ms']} if 'wgrad:conv5' in kern else {}))),
                'conv5_passes': kern,
                'loss': [float(v) for v in losses.cpu().numpy()], 'workspace_gb': eng.workspace_bytes() / 1e9}
+        if dump:
+            flat = np.concatenate([v.ravel() for _k, v in sorted(tr.get_params(params).items())])
+            idx = np.sort(np.random.RandomState(0).randint(0, flat.size, PARAM_SAMPLE)) if flat.size > PARAM_SAMPLE else np.arange(flat.size)
+            dump_outputs(dump, {'losses': losses, 'params_sample': flat[idx]})
     eng.close()
     return out
 
@@ -541,9 +577,18 @@ def main():
                                                          'default 16 images per GPU (batch 128 over 8 GPUs)')
     ap.add_argument('--overlap', action='store_true', help='--train, N > 1, RCCL: start each layer\'s gradient all-reduce during the backward pass')
     ap.add_argument('--fft-fuse', type=int, default=None, help='fp32 engines: option "fft_fuse" (3 = default: pool and merge hand-overs fused; 0 = separate kernels, the A/B arm)')
-    ap.add_argument('--extras', type=int, default=1, help='0: the headline configuration only (no bf16 / chain / split16 / sustained / training lines)')
-    ap.add_argument('--layer-times', action='store_true', help='print the HIP-event time of every MFMA conv layer to stderr')
+    ap.add_argument('--full', action='store_true', help='measure everything beside the headline figure too: the profiled second timed region and the roofline '
+                                                        'object, the other configurations (--extras), the CPU baseline and bench_detail.json.  Without it a run '
+                                                        'sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--extras', type=int, default=1, help='with --full; 0: the headline configuration only (no bf16 / chain / split16 / sustained / training lines)')
+    ap.add_argument('--layer-times', action='store_true', help='with --full: print the HIP-event time of every MFMA conv layer to stderr')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the timed path returned in its last step as DIR/<name>.npy (float32, rank 0)')
     args = ap.parse_args()
+    if args.layer_times and not args.full:
+        ap.error('--layer-times needs --full (the per-launch events are recorded in the profiled timed region)')
+    if not args.full:
+        args.extras = 0
     if args.cpu_images == 0 or not args.extras:
         args.cpu_reps = 0
 
@@ -585,9 +630,9 @@ def main():
         params.update(synth.make_sm_params(synth.synthetic_priors(), kind='init'))   # main.py:477-487
 
     if args.train:
-        out = run_train(args, args.batch or 16, params, world, rank, local_rank, dev, use_sm)
+        out = run_train(args, args.batch or 16, params, world, rank, local_rank, dev, use_sm, dump=args.dump_outputs)
         if rank == 0:
-            emit(out)
+            emit(out, detail_file=args.full)
         if dist_on():
             dist.destroy_process_group()
         return
@@ -602,13 +647,13 @@ def main():
             raise SystemExit('--global-batch %d is smaller than the number of ranks %d' % (args.global_batch, world))
         scaling = 'strong'
         head = run_config(args, head_dtype, head_batch, params, world, rank, local_rank, dev, use_sm,
-                          f32_conv=args.f32_conv if head_dtype == 'fp32' else None, micro_batch=args.micro_batch,
+                          f32_conv=args.f32_conv if head_dtype == 'fp32' else None, micro_batch=args.micro_batch, dump=args.dump_outputs,
                           config_name='configs[3] (global batch %d sharded over %d rank%s)' % (args.global_batch, world, '' if world == 1 else 's'))
     else:
         head_dtype = args.dtype or 'fp32'
         head_batch = args.batch or (64 if head_dtype == 'fp32' else 256)
         head = run_config(args, head_dtype, head_batch, params, world, rank, local_rank, dev, use_sm,
-                          f32_conv=args.f32_conv if head_dtype == 'fp32' else None, micro_batch=args.micro_batch)
+                          f32_conv=args.f32_conv if head_dtype == 'fp32' else None, micro_batch=args.micro_batch, dump=args.dump_outputs)
     second = second_x2 = second_mfma = split16 = config3 = chain = sus = None
     if args.dtype is None and not args.debug and not args.global_batch and args.extras:
         # configs[2] (bf16, batch 256) with its arg-max agreement against the fp32 engine on the same images (single-rank runs: rank 0 alone
@@ -650,10 +695,13 @@ def main():
     if rank == 0:
         detail = {'metric': 'images/sec (720x480, K=9 joints) part-detector+spatial-model fwd',
                   'value': head['value'], 'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-                  'ms_per_step': head['ms_per_step'], 'ms_per_step_profiled': head.get('ms_per_step_profiled'), 'median_ms_per_step': head['median_ms_per_step'], 'value_median': head['value_median'] * world,
+                  'ms_per_step': head['ms_per_step'], 'median_ms_per_step': head['median_ms_per_step'], 'value_median': head['value_median'] * world,
                   'higher_is_better': True, 'scaling': scaling, 'vs_baseline': None,
                   'dtype': head['dtype'], 'data': 'synthetic', 'config': head['config'], 'path_tflops': head['path_tflops'],
-                  'roofline': head['roofline'], 'device_mem_used_gb': head.get('device_mem_used_gb')}
+                  'device_mem_used_gb': head.get('device_mem_used_gb')}
+        for key in ('ms_per_step_profiled', 'roofline'):      # --full
+            if key in head:
+                detail[key] = head[key]
         others = {'bf16_config2': second, 'bf16_config2_bf16x2': second_x2, 'bf16_config2_mfma': second_mfma, 'config3_gb2048': config3,
                   'f32_chain_config1': chain, 'f32_split16_config1': split16}
         for key, o in others.items():
@@ -667,7 +715,7 @@ def main():
                 detail[key] = {k: tr_out[k] for k in ('value', 'unit', 'ms_per_step', 'median_ms_per_step', 'dtype', 'config', 'train_tflops', 'frac_of_mfma_peak', 'roofline', 'conv5_passes', 'workspace_gb') if k in tr_out}
         if args.cpu_reps > 0 and world == 1 and not args.debug:      # the CPU baseline is a single-GPU-run item (rank 0, N = 1)
             detail['cpu_baseline'] = cpu_baseline(params, reps=args.cpu_reps, budget_s=args.cpu_budget)
-        emit(detail)
+        emit(detail, detail_file=args.full)
     if dist_on():
         dist.destroy_process_group()
 
@@ -698,21 +746,23 @@ def rnd(v, n=4):
     return v
 
 
-def emit(detail):
-    """Verbose record -> bench_detail.json (+ stderr); ONE compact line (<= 4 KB) -> stdout, last."""
+def emit(detail, detail_file=True):
+    """Verbose record -> bench_detail.json (when `detail_file`: --full) and stderr; ONE compact line (<= 4 KB) -> stdout, last."""
     ddir = os.path.join(ROOT, 'gpurun_out') if os.path.isdir(os.path.join(ROOT, 'gpurun_out')) else os.getcwd()
-    dpath = os.path.join(ddir, 'bench_detail.json')
-    try:
-        with open(dpath, 'w') as fh:
-            json.dump(detail, fh)
-    except OSError:
-        dpath = None
+    dpath = os.path.join(ddir, 'bench_detail.json') if detail_file else None
+    if dpath:
+        try:
+            with open(dpath, 'w') as fh:
+                json.dump(detail, fh)
+        except OSError:
+            dpath = None
     print(json.dumps(detail), file=sys.stderr)
     line = {k: detail[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'ms_per_step_profiled', 'median_ms_per_step', 'higher_is_better', 'scaling',
                                    'vs_baseline', 'dtype', 'data') if k in detail}
     cfg = detail['config']
     line['config'] = {'workload': cfg['workload'][:160], **{k: cfg[k] for k in ('batch_per_gpu', 'global_batch', 'micro_batch', 'use_sm', 'collective') if k in cfg}}
-    line['roofline'] = compact_roofline(detail['roofline'])
+    if 'roofline' in detail:
+        line['roofline'] = compact_roofline(detail['roofline'])
     if 'cpu_baseline' in detail:
         cb = detail['cpu_baseline']
         line['cpu_baseline'] = {'value': cb['value'], 'unit': cb['unit'], 'cores': cb['cores'], 'kind': cb['kind'], 'sample': cb['sample'][:200],

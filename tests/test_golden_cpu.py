@@ -1,9 +1,7 @@
 """The oracle against the committed golden vectors, on CPU.  The goldens were written by the
 NumPy formulation in float64; here the *other* formulation (torch/SciPy) must reproduce them,
 and the priors must reproduce what the reference's own prepare_pairwise_distribution.py emits
-(that check runs where /root/reference exists; elsewhere the recorded properties are checked)."""
-import os
-
+(its smoothing kernel is stored as tests/golden/prior_smooth_kernel.npy)."""
 import numpy as np
 import pytest
 import torch
@@ -31,12 +29,14 @@ def test_flic_priors_properties(pri):
     assert cells.shape == (3987, 10, 2) and cells[:, :, 0].max() <= 59 and cells[:, :, 1].max() <= 89
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/prepare_pairwise_distribution.py'), reason='reference tree absent')
 def test_prior_smoothing_kernel_matches_reference_source():
-    """The 9x9 binomial kernel is the one the reference builds (its lines 13-14)."""
-    src = open('/root/reference/prepare_pairwise_distribution.py').read()
-    assert 'np.array([[1, 8, 28, 56, 70, 56, 28, 8, 1]], dtype=np.uint16) / 256' in src
+    """The 9x9 binomial kernel is the one the reference builds (prepare_pairwise_distribution.py:13-14), bit for bit:
+    tests/golden/prior_smooth_kernel.npy is the float64 array those two lines evaluate to."""
     from joint_cnn_mrf_amd import priors
+    ref = load('prior_smooth_kernel')
+    assert ref.shape == (9, 9) and ref.dtype == np.float64
+    assert priors.SMOOTH_KERNEL.dtype == np.float64
+    np.testing.assert_array_equal(priors.SMOOTH_KERNEL, ref)
     assert priors.SMOOTH_KERNEL.shape == (9, 9) and abs(priors.SMOOTH_KERNEL.sum() - 1.0) < 1e-12
 
 

@@ -32,7 +32,7 @@ def _finite(v):
 
 
 def test_bench_two_ranks_weak_scaling_line():
-    d, _ = _bench('--gpus', '2', '--dtype', 'bf16', '--batch', '4', '--steps', '2', '--warmup', '1', '--cpu-reps', '0')
+    d, _ = _bench('--gpus', '2', '--full', '--dtype', 'bf16', '--batch', '4', '--steps', '2', '--warmup', '1', '--cpu-reps', '0')
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak' and d['steps'] == 2 and d['warmup'] == 1
     assert d['config']['batch_per_gpu'] == 4 and d['config']['global_batch'] == 8
     assert _finite(d['value']) and _finite(d['ms_per_step']) and _finite(d['median_ms_per_step'])
