@@ -211,6 +211,17 @@ int jcm_window_resize(jcm_handle h, const float* src, int nsrc, int H, int W, in
 /* np.average over the G scale copies of each image (main.py:413-414): in [n*G, M] -> out [n, M]. */
 int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float* out);
 
+/* -- training-time augmentation (augmentation.py:58-78; main.py:494-497) ----------------------------
+ * x [B,H,W,3], y [B,h,w,10] (= y_in, main.py:488), params [B,6] = (flip, delta, factor, angle, rh, rw):
+ * all device fp32; x_out / y_out same shapes, must not alias the inputs.  Enqueues, does not synchronise.
+ * Per image: flip (flip == 1; heat-map channels permuted), brightness + delta, contrast (mean of the brightened
+ * channel), clip to [0,1], rotation by `angle` (bilinear, fill 0), crop_and_resize of the box
+ * [rh, rw, rh + 0.95, rw + 0.95] back to the input size; heat maps then pow(., 1.6) + 1e-5, normalised per channel
+ * (DESIGN.md 4.7).  H, W, h, w >= 2; the handle must have n_joints == 9.  Uses the workspace arena: JCM_ERR_STATE
+ * from the gradient-ready callback of the same handle. */
+int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
+                      int hh, int hw, float* x_out, float* y_out);
+
 /* -- tower concat across processes (main.py:573-574: tf.concat of the per-tower maps; here one process per GPU) --------
  * The only collective of the inference path: every rank contributes its [B_local,2,K] int32 coordinates and receives
  * all ranks' in rank order, moved by RCCL (the ROCm build of the NCCL API) over xGMI.  RCCL is resolved with dlopen on

@@ -1,0 +1,229 @@
+// Training-time data augmentation (augmentation.py:58-78, applied at main.py:494-497): per image, in the reference's
+// order, flip (heat-map channels permuted), brightness, contrast, clip to [0, 1], rotation (ImageProjectiveTransform,
+// bilinear, fill 0), crop_and_resize back to the input size, and the heat maps' pow(., 1.6) + 1e-5 renormalisation.
+// The semantics are DESIGN.md 4.7 (a restatement of the TF-1.x ops, float32 in the order written; tests/augment_ref.py).
+// Three launches: the per-image channel sums of the brightened image (partials, no atomics), the image gather (crop taps ->
+// rotated samples -> source taps, the colour steps applied per source tap) and one work group per (image, heat-map channel).
+#include "kernels.h"
+
+namespace jcm {
+
+namespace {
+
+constexpr int kAugParts = 128;          // partial sums per image (aug_mean_kernel's grid.x)
+constexpr int kAugRed = 192;            // reduction width: a multiple of 3, so that slot t always holds channel t % 3
+constexpr int kAugImgThreads = 256;
+constexpr int kAugHmThreads = 512;
+constexpr float kCropSize = 0.95f;      // augmentation.py:40
+__constant__ int kHmFlipPerm[10] = {3, 4, 5, 0, 1, 2, 7, 6, 8, 9};     // augmentation.py:20
+
+// params[b] = (flip, delta, factor, angle, rh, rw)
+struct Rot {
+  float c, s, xo, yo;
+};
+
+// angles_to_projective_transforms for an h x w image; cos / sin in double, rounded (the host restatement uses the same values)
+__device__ Rot make_rot(float angle, int h, int w) {
+  Rot R;
+  R.c = (float)cos((double)angle);
+  R.s = (float)sin((double)angle);
+  const float wm = (float)(w - 1), hm = (float)(h - 1);
+  R.xo = (wm - (R.c * wm - R.s * hm)) / 2.f;
+  R.yo = (hm - (R.s * wm + R.c * hm)) / 2.f;
+  return R;
+}
+
+// one axis of crop_and_resize (crop extent == input extent n): taps lo / hi and weight l; ok = false -> the row / column is 0
+struct Axis {
+  int lo, hi;
+  float l;
+  bool ok;
+};
+__device__ __forceinline__ Axis crop_axis(float b1, int n, int i) {
+  const float b2 = b1 + kCropSize;
+  const float nm = (float)(n - 1);
+  const float scale = ((b2 - b1) * nm) / nm;
+  const float in = b1 * nm + (float)i * scale;
+  Axis a;
+  a.ok = in >= 0.f && in <= nm;            // false for NaN as well: no index is formed from it
+  const float t = a.ok ? floorf(in) : 0.f;
+  a.lo = (int)t;
+  a.hi = a.ok ? (int)ceilf(in) : 0;
+  a.l = a.ok ? in - t : 0.f;
+  return a;
+}
+
+// ImageProjectiveTransform (BILINEAR, fill 0) at output pixel (r, q) of an h x w map; at(yf, xf, v) writes the NC source values
+// at the integral float position (yf, xf), or zeros outside [0,h) x [0,w)
+template <int NC, class At>
+__device__ __forceinline__ void rot_sample(const Rot& R, int r, int q, At at, float* out) {
+  const float xi = (R.c * (float)q + (-R.s) * (float)r) + R.xo;
+  const float yi = (R.s * (float)q + R.c * (float)r) + R.yo;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) out[k] = 0.f;
+  if (!isfinite(xi) || !isfinite(yi)) return;
+  const float x0 = floorf(xi), y0 = floorf(yi), x1 = x0 + 1.f, y1 = y0 + 1.f;
+  float p00[NC], p01[NC], p10[NC], p11[NC];
+  at(y0, x0, p00);
+  at(y0, x1, p01);
+  at(y1, x0, p10);
+  at(y1, x1, p11);
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const float top = (x1 - xi) * p00[k] + (xi - x0) * p01[k];
+    const float bot = (x1 - xi) * p10[k] + (xi - x0) * p11[k];
+    out[k] = (y1 - yi) * top + (yi - y0) * bot;
+  }
+}
+
+// crop_and_resize of the rotated map at output pixel (r, q): four rotated samples, each from its four source taps
+template <int NC, class At>
+__device__ __forceinline__ void crop_rot_sample(const Rot& R, const Axis& Y, const Axis& X, At at, float* out) {
+#pragma unroll
+  for (int k = 0; k < NC; ++k) out[k] = 0.f;
+  if (!Y.ok || !X.ok) return;
+  float tl[NC], tr[NC], bl[NC], br[NC];
+  rot_sample<NC>(R, Y.lo, X.lo, at, tl);
+  rot_sample<NC>(R, Y.lo, X.hi, at, tr);
+  rot_sample<NC>(R, Y.hi, X.lo, at, bl);
+  rot_sample<NC>(R, Y.hi, X.hi, at, br);
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const float t = tl[k] + (tr[k] - tl[k]) * X.l;
+    const float b = bl[k] + (br[k] - bl[k]) * X.l;
+    out[k] = t + (b - t) * Y.l;
+  }
+}
+
+// fixed-order fold of red[0 .. kAugRed) into red[0..2] (slot t holds channel t % 3; every stride is a multiple of 3)
+__device__ __forceinline__ void fold3(double* red) {
+  for (int s = kAugRed / 2; s >= 3; s >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+  }
+  __syncthreads();
+}
+
+// partials[b][part][c] = sum over the part's pixels of double(float(x + delta)), channel c
+__global__ __launch_bounds__(kAugRed) void aug_mean_kernel(const float* __restrict__ x, const float* __restrict__ params, int HW,
+                                                           double* __restrict__ partials) {
+  __shared__ double red[kAugRed];
+  const int b = blockIdx.y;
+  const float delta = params[(size_t)b * 6 + 1];
+  const int n = HW * 3;
+  const int chunk = (n / 3 + kAugParts - 1) / kAugParts * 3;
+  const int lo = blockIdx.x * chunk;
+  const int hi = min(n, lo + chunk);
+  const float* xb = x + (size_t)b * n;
+  double s = 0.0;
+  for (int e = lo + (int)threadIdx.x; e < hi; e += kAugRed) s += (double)(xb[e] + delta);
+  red[threadIdx.x] = s;
+  fold3(red);
+  if (threadIdx.x < 3) partials[((size_t)b * kAugParts + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kAugImgThreads) void aug_image_kernel(const float* __restrict__ x, const float* __restrict__ params, int H, int W,
+                                                                   const double* __restrict__ partials, float* __restrict__ x_out) {
+  __shared__ double red[kAugRed];
+  __shared__ float s_mean[3];
+  __shared__ Rot s_rot;
+  const int b = blockIdx.y;
+  const float* p = params + (size_t)b * 6;
+  const bool flip = p[0] == 1.f;
+  const float delta = p[1], factor = p[2];
+  const int HW = H * W;
+  const int t = threadIdx.x;
+  if (t < kAugRed) {      // channel t % 3, parts t / 3 and t / 3 + 64
+    const double* pb = partials + (size_t)b * kAugParts * 3;
+    red[t] = pb[t] + pb[t + kAugRed];
+  }
+  if (t == kAugImgThreads - 1) s_rot = make_rot(p[3], H, W);
+  fold3(red);
+  if (t < 3) s_mean[t] = (float)(red[t] / (double)HW);
+  __syncthreads();
+  const int i = blockIdx.x * kAugImgThreads + t;
+  if (i >= HW) return;
+  const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
+  const Rot R = s_rot;
+  const float* xb = x + (size_t)b * HW * 3;
+  // a source pixel after flip, brightness, contrast and clip; zeros outside the image (the rotation's fill)
+  auto at = [&](float yf, float xf, float* v) {
+    if (yf >= 0.f && yf < (float)H && xf >= 0.f && xf < (float)W) {
+      const int xx = (int)xf;
+      const float* s = xb + ((size_t)(int)yf * W + (flip ? W - 1 - xx : xx)) * 3;
+      const float m[3] = {m0, m1, m2};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        float u = s[k] + delta;
+        u = (u - m[k]) * factor + m[k];
+        v[k] = fminf(fmaxf(u, 0.f), 1.f);
+      }
+    } else {
+      v[0] = v[1] = v[2] = 0.f;
+    }
+  };
+  const int r = i / W, q = i - r * W;
+  float o[3];
+  crop_rot_sample<3>(R, crop_axis(p[4], H, r), crop_axis(p[5], W, q), at, o);
+  float* dst = x_out + ((size_t)b * HW + i) * 3;
+  dst[0] = o[0];
+  dst[1] = o[1];
+  dst[2] = o[2];
+}
+
+// one work group per (heat-map channel k, image b): flip + channel permutation, rotation, crop, t = pow(v, 1.6) + 1e-5, t / sum(t)
+__global__ __launch_bounds__(kAugHmThreads) void aug_hm_kernel(const float* __restrict__ y, const float* __restrict__ params, int h, int w,
+                                                               float* __restrict__ y_out) {
+  __shared__ double red[kAugHmThreads];
+  __shared__ Rot s_rot;
+  const int k = blockIdx.x, b = blockIdx.y;
+  const float* p = params + (size_t)b * 6;
+  const bool flip = p[0] == 1.f;
+  const int hw = h * w;
+  const int t = threadIdx.x;
+  if (t == 0) s_rot = make_rot(p[3], h, w);
+  __syncthreads();
+  const Rot R = s_rot;
+  const float* yb = y + (size_t)b * hw * 10 + (flip ? kHmFlipPerm[k] : k);
+  float* ob = y_out + (size_t)b * hw * 10 + k;
+  auto at = [&](float yf, float xf, float* v) {
+    v[0] = 0.f;
+    if (yf >= 0.f && yf < (float)h && xf >= 0.f && xf < (float)w) {
+      const int xx = (int)xf;
+      v[0] = yb[((size_t)(int)yf * w + (flip ? w - 1 - xx : xx)) * 10];
+    }
+  };
+  double s = 0.0;
+  for (int i = t; i < hw; i += kAugHmThreads) {
+    const int r = i / w, q = i - r * w;
+    float v;
+    crop_rot_sample<1>(R, crop_axis(p[4], h, r), crop_axis(p[5], w, q), at, &v);
+    const float u = powf(v, 1.6f) + 1e-5f;
+    ob[(size_t)i * 10] = u;
+    s += (double)u;
+  }
+  red[t] = s;
+  for (int st = kAugHmThreads / 2; st > 0; st >>= 1) {
+    __syncthreads();
+    if (t < st) red[t] += red[t + st];
+  }
+  __syncthreads();
+  const float tot = (float)red[0];
+  for (int i = t; i < hw; i += kAugHmThreads) ob[(size_t)i * 10] = ob[(size_t)i * 10] / tot;     // this thread's own stores
+}
+
+}  // namespace
+
+size_t augment_scratch_doubles(int B) { return (size_t)B * kAugParts * 3; }
+
+hipError_t augment_train(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch,
+                         float* x_out, float* y_out, hipStream_t st) {
+  static_assert(kAugRed == 3 * (kAugParts / 2) && kAugImgThreads >= kAugRed, "aug_image_kernel folds two parts per reduction slot");
+  hipLaunchKernelGGL(aug_mean_kernel, dim3(kAugParts, B), dim3(kAugRed), 0, st, x, params, H * W, scratch);
+  hipLaunchKernelGGL(aug_image_kernel, dim3((H * W + kAugImgThreads - 1) / kAugImgThreads, B), dim3(kAugImgThreads), 0, st, x, params, H, W,
+                     scratch, x_out);
+  hipLaunchKernelGGL(aug_hm_kernel, dim3(10, B), dim3(kAugHmThreads), 0, st, y, params, hh, hw, y_out);
+  return hipGetLastError();
+}
+
+}  // namespace jcm

@@ -1214,6 +1214,32 @@ int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float
   return JCM_OK;
 }
 
+int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
+                      int hh, int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  if (!x || !y || !params || !x_out || !y_out) return fail(JCM_ERR_ARG, "augment_train: null pointer");
+  if (B < 1 || B > 65535 || H < 2 || W < 2 || hh < 2 || hw < 2 || (int64_t)H * W * 3 >= (int64_t)1 << 30 || (int64_t)hh * hw * 10 >= (int64_t)1 << 30)
+    return fail(JCM_ERR_ARG, "augment_train: bad sizes (B in [1, 65535], H, W, h, w >= 2)");
+  if (h->K != 9) return fail(JCM_ERR_ARG, "augment_train: the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
+  const size_t nx = (size_t)B * H * W * 3 * sizeof(float), ny = (size_t)B * hh * hw * 10 * sizeof(float), np = (size_t)B * 6 * sizeof(float);
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+    return pa < pb + nb && pb < pa + na;
+  };
+  if (overlap(x_out, nx, x, nx) || overlap(x_out, nx, y, ny) || overlap(x_out, nx, params, np) || overlap(y_out, ny, x, nx) ||
+      overlap(y_out, ny, y, ny) || overlap(y_out, ny, params, np) || overlap(x_out, nx, y_out, ny))
+    return fail(JCM_ERR_ARG, "augment_train: x_out / y_out alias an input or each other");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  return with_arena(c, [&] {
+    double* scratch = arena_alloc<double>(c, augment_scratch_doubles(B));
+    if (c->dry) return (int)JCM_OK;
+    HIP_TRY(augment_train(x, y, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
+    return (int)JCM_OK;
+  });
+}
+
 int jcm_profile_read(jcm_handle h, const char* scope, double* total_ms, int* launches) {
   JCM_TRY(check(h, false));
   if (!scope || !total_ms || !launches) return fail(JCM_ERR_ARG, "bad profile_read arguments");

@@ -302,6 +302,13 @@ hipError_t window_resize(const float* src, int H, int W, int C, const int* windo
                          int OH, int OW, float* out, hipStream_t st);
 hipError_t group_mean(const float* in, float* out, int n, int G, size_t M, hipStream_t st);
 
+// ---- augment.hip : training-time augmentation (augmentation.py:58-78) ---------------
+// x [B,H,W,3], y [B,hh,hw,10], params [B,6] = (flip, delta, factor, angle, rh, rw), all device fp32; three launches on `st`.
+// scratch: augment_scratch_doubles(B) doubles (the per-image channel sums of the brightened image)
+size_t augment_scratch_doubles(int B);
+hipError_t augment_train(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch,
+                         float* x_out, float* y_out, hipStream_t st);
+
 // ---- train_kernels.hip : training-step kernels other than convolutions (fp32 NHWC) ------------------
 size_t train_reduce_scratch_doubles(int C);      // scratch the per-channel reductions below need
 // batch mean / 1/sqrt(biased var + eps) of x [N,C]; moving stats (may be null) updated with `decay`

@@ -291,6 +291,30 @@ class Engine:
         _lib.check(self._lib.jcm_group_mean(self._h, self._p(x.contiguous()), n, group, m, self._p(out)), 'jcm_group_mean')
         return out
 
+    def augment_train(self, x, y, params, x_out=None, y_out=None):
+        """Training-time augmentation (augmentation.py:58-78): x [B,H,W,3], y [B,h,w,K+1] = y_in, params [B,6] device fp32
+        (augmentation.draw_params / check_params) -> (x_out, y_out), new tensors unless given.  Enqueued on the engine's stream."""
+        self._chk(x, 4, 'x')
+        self._chk(y, 4, 'y')
+        self._chk(params, 2, 'params')
+        B, H, W, C = x.shape
+        _, hh, hw, Ky = y.shape
+        if C != 3 or y.shape[0] != B or Ky != self.n_joints + 1 or tuple(params.shape) != (B, 6):
+            raise ValueError('augment_train expects x [B,H,W,3], y [B,h,w,%d], params [B,6]; got %s, %s, %s'
+                             % (self.n_joints + 1, tuple(x.shape), tuple(y.shape), tuple(params.shape)))
+        x_out = self._new(*x.shape) if x_out is None else self._chk(x_out, 4, 'x_out')
+        y_out = self._new(*y.shape) if y_out is None else self._chk(y_out, 4, 'y_out')
+        if x_out.shape != x.shape or y_out.shape != y.shape:
+            raise ValueError('x_out / y_out must have the shapes of x / y')
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self._stream:          # tensors made on torch's current stream: the engine's stream waits for them, and keeps them alive
+            self._stream.wait_stream(cur)
+            for t in (x, y, params, x_out, y_out):
+                t.record_stream(self._stream)
+        _lib.check(self._lib.jcm_augment_train(self._h, self._p(x), self._p(y), self._p(params), B, H, W, hh, hw,
+                                               self._p(x_out), self._p(y_out)), 'jcm_augment_train')
+        return x_out, y_out
+
     def set_option(self, key, value):
         """jcm_set_option(key, value) -- include/jcm.h lists the keys."""
         _lib.check(self._lib.jcm_set_option(self._h, key.encode(), int(value)), 'jcm_set_option(%s)' % key)

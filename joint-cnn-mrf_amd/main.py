@@ -273,20 +273,25 @@ class TowerTrainer:
     common start, so the composition is rebuilt from the per-replica results and written to every replica."""
     BN_DECAY = 0.9          # decay=0.9 of the reference's tf.contrib.layers.batch_norm calls (main.py:113,129)
 
-    def __init__(self, towers, params, **trainer_kw):
+    def __init__(self, towers, params, augment_rng=None, **trainer_kw):
         from .train import Trainer
         self.towers = towers
+        self.augment_rng = augment_rng      # numpy RandomState: augment every step (main.py:494-497), parameters drawn for the global batch
         self.trainers = [Trainer(e, **trainer_kw) for e in towers.engines]
         self.moving = {k: np.asarray(v, np.float32).reshape(-1).copy() for k, v in params.items()
                        if k.endswith('moving_mean') or k.endswith('moving_variance')}
 
     def train_step(self, x, y):
         tw = self.towers
+        aug = None
+        if self.augment_rng is not None:
+            from .augmentation import draw_params
+            aug = draw_params(self.augment_rng, x.shape[0])        # before the towers slice the batch: the same images for any tower count
         for tr, eng, (lo, hi) in zip(self.trainers, tw.engines, tw.slices(x.shape[0])):
             xs = torch.as_tensor(x[lo:hi]).to(eng.device, non_blocking=True).contiguous()
             ys = torch.as_tensor(y[lo:hi]).to(eng.device, non_blocking=True).contiguous()
             with torch.cuda.device(eng.device):
-                tr.loss_and_grads(xs, ys)
+                tr.loss_and_grads(xs, ys, augment=None if aug is None else aug[lo:hi])
         dev0 = tw.engines[0].device
         if tw.n > 1:
             total = self.trainers[0].grads

@@ -60,6 +60,7 @@ class Trainer:
         _lib.check(self._lib.jcm_train_set_grad_callback(engine._h, ctypes.cast(self._cb, ctypes.c_void_p), None),
                    'jcm_train_set_grad_callback')
         self.losses = torch.zeros(4, dtype=torch.float32, device=engine.device)
+        self._aug = None                                            # (x, y, params) buffers of the augmented batch (loss_and_grads(augment=))
 
     @property
     def n_iters(self):
@@ -67,15 +68,18 @@ class Trainer:
         _lib.check(self._lib.jcm_train_steps(self.eng._h, ctypes.byref(n)), 'jcm_train_steps')
         return n.value
 
-    def loss_and_grads(self, x, y):
+    def loss_and_grads(self, x, y, augment=None):
         """x [B,H,W,3], y [B,60,90,K+1] -> (losses[4] device tensor, flat grads device tensor).
-        losses = (loss_tower, loss_pd, loss_sm, weight_decay)."""
+        losses = (loss_tower, loss_pd, loss_sm, weight_decay).  `augment`: None, or a host [B,6] array of augmentation
+        parameters (augmentation.draw_params): the step trains on the augmented copy of (x, y) (main.py:494-497)."""
         e = self.eng
         e._chk(x, 4, 'x')
         e._chk(y, 4, 'y')
         B, H, W, C = x.shape
         if C != 3 or y.shape[0] != B or y.shape[3] != e.n_joints + 1:
             raise ValueError('x must be [B,H,W,3] and y [B,h,w,%d]; got %s, %s' % (e.n_joints + 1, tuple(x.shape), tuple(y.shape)))
+        if augment is not None:
+            x, y = self._augmented(x, y, augment)
         self._cb_error = None
         status = self._lib.jcm_train_loss_grads(e._h, e._p(x), e._p(y), B, H, W, int(self.use_sm), self.lmbd,
                                                 e._p(self.grads), e._p(self.losses))
@@ -85,6 +89,20 @@ class Trainer:
             raise err
         _lib.check(status, 'jcm_train_loss_grads')
         return self.losses, self.grads
+
+    def _augmented(self, x, y, augment):
+        """The augmented copy of (x, y) in buffers the trainer owns (kept across steps of the same shapes)."""
+        from .augmentation import check_params
+        e = self.eng
+        p = check_params(augment)
+        if p.shape[0] != x.shape[0]:
+            raise ValueError('augment has %d parameter rows for a batch of %d' % (p.shape[0], x.shape[0]))
+        if self._aug is None or self._aug[0].shape != x.shape or self._aug[1].shape != y.shape:
+            self._aug = (torch.empty_like(x), torch.empty_like(y), torch.empty(p.shape, dtype=torch.float32, device=e.device))
+        xa, ya, pd = self._aug
+        with torch.cuda.stream(e._stream):       # behind the previous step's reads of the parameter buffer; the host does not wait
+            pd.copy_(torch.from_numpy(p).pin_memory(), non_blocking=True)
+        return e.augment_train(x, y, pd, xa, ya)
 
     def layer_grads(self, scope, x, dz, want_dx=True):
         """The weight gradient (+ lmbd * w) and the data gradient of ONE stride-1 conv layer on given tensors, through the kernels the training
@@ -190,10 +208,11 @@ class Trainer:
             _lib.check(self._lib.jcm_update_tensor(self.eng._h, n.encode(), ctypes.c_void_p(buf.data_ptr() + 4 * o), c,
                                                    int(i == len(self._moving) - 1)), 'jcm_update_tensor(%s)' % n)
 
-    def train_step(self, x, y, want_norm=False, moving=None):
+    def train_step(self, x, y, want_norm=False, moving=None, augment=None):
         """One sess.run(train_step) (main.py:644).  Returns (losses tensor, grad norm or None).
-        `moving`: [(name, count)] of the BN moving statistics to keep in sync across ranks (N > 1)."""
-        self.loss_and_grads(x, y)
+        `moving`: [(name, count)] of the BN moving statistics to keep in sync across ranks (N > 1).
+        `augment`: host [B,6] augmentation parameters or None (loss_and_grads)."""
+        self.loss_and_grads(x, y, augment=augment)
         self.average_gradients()
         norm = self.apply(want_norm=want_norm)
         if moving:
