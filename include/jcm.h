@@ -222,6 +222,32 @@ int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float
 int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
                       int hh, int hw, float* x_out, float* y_out);
 
+/* -- TensorBoard summaries (tensorboard.py) -------------------------------------------------
+ * jcm_tensor_stats: per segment (offset, count) of a flat device fp32 buffer -- or, with data == NULL, of the handle's stored
+ *   trainable parameters in the layout of jcm_train_param_info (read in place; a segment must lie inside one tensor) -- the
+ *   statistics of tf.summary.histogram over u = fp32(f * v): f = scale, or with clip_norm > 0 the clip factor
+ *   clip_norm / max(norm, clip_norm) of the last jcm_train_apply of this handle, taken from device memory (tf.clip_by_global_norm
+ *   as the optimizer applied it).  segments: HOST int64 [n_segments][2].  Outputs (device):
+ *     stats  double [n_segments][4] = min, max, sum, sum_squares over the finite u (an empty segment: DBL_MAX, -DBL_MAX, 0, 0);
+ *     counts int64  [n_segments][3 + JCM_HIST_BUCKETS] = num (finite), n_pos (u > 0), n_nonfinite, then the counts of TF-1.x's
+ *            default buckets (histogram.cc: bucket b = upper_bound(limits, (double)u), limits from jcm_hist_bucket_limits).
+ *   Sums are fixed-order folds; results are bitwise reproducible.  Synchronises the stream (the segment table is host memory).
+ * jcm_hist_bucket_limits: the JCM_HIST_BUCKETS limits (-DBL_MAX ... -1e-12, 0, 1e-12 ... DBL_MAX); host only; returns the count
+ *   (out may be NULL), -1 when cap is too small.
+ * jcm_image_u8: NormalizeFloatImage of summary_image_op.cc for x [N,H,W,C] fp32, C = 1 or 3 -> out uint8 [N,H,W,C] (device):
+ *   per image min / max over the finite pixels, scale 127 / max(|min|, |max|) + 128 when min < 0, else 255 / max (0 when that
+ *   max < 1e-6), truncated; a pixel with a non-finite channel becomes (255, 0, 0) (gray: 255).
+ * jcm_hm_overlay: show_img_plus_hm (tensorboard.py:60-71) for images x [n,H,W,3] and heat maps hm [n,hh,hw,K] (K = 9, the
+ *   reference's joints): out uint8 [n,K+1,H,W,3] -- picture j < K = min(x + colorize(c_j), 1), picture K = the all-joints
+ *   picture, each quantised as jcm_image_u8; c_j = hm[..., j] resized (TF-1.x bilinear) times 1 / max(hm[..., j]).
+ * All three image calls enqueue without synchronising and use the workspace arena. */
+#define JCM_HIST_BUCKETS 1551
+int jcm_tensor_stats(jcm_handle h, const float* data, const int64_t* segments, int n_segments, float scale, float clip_norm, double* stats,
+                     int64_t* counts);
+int jcm_hist_bucket_limits(double* out, int cap);
+int jcm_image_u8(jcm_handle h, const float* x, int N, int H, int W, int C, uint8_t* out);
+int jcm_hm_overlay(jcm_handle h, const float* x, const float* hm, int n, int H, int W, int hh, int hw, int K, uint8_t* out);
+
 /* -- tower concat across processes (main.py:573-574: tf.concat of the per-tower maps; here one process per GPU) --------
  * The only collective of the inference path: every rank contributes its [B_local,2,K] int32 coordinates and receives
  * all ranks' in rank order, moved by RCCL (the ROCm build of the NCCL API) over xGMI.  RCCL is resolved with dlopen on

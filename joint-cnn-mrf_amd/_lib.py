@@ -10,6 +10,7 @@ JCM_PRECISION_F32 = 0
 JCM_PRECISION_BF16 = 1
 JCM_OPT_ADAM = 0
 JCM_OPT_MOMENTUM = 1
+JCM_HIST_BUCKETS = 1551      # include/jcm.h
 
 _c_float_p = ctypes.c_void_p      # device pointers travel as integers
 _c_i32_p = ctypes.c_void_p
@@ -47,6 +48,12 @@ SIGNATURES = {
     'jcm_group_mean': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_float_p]),
     'jcm_augment_train': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
+    'jcm_tensor_stats': (ctypes.c_int, [_handle, _c_float_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    'jcm_hist_bucket_limits': (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
+    'jcm_image_u8': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    'jcm_hm_overlay': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_void_p]),
     'jcm_profile_read': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
     'jcm_comm_unique_id': (ctypes.c_int, [ctypes.c_char_p]),
     'jcm_comm_create': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),

@@ -70,6 +70,11 @@ struct TrainState;   // jcm_train.hip
 struct jcm_ctx;
 namespace jcm {
 void train_destroy(jcm_ctx* c);
+// summary.hip's view of the training state (jcm_train.hip): the stored trainable tensor that holds [off, off + n) of the
+// jcm_train_param_info layout (nullptr if none does), and the device gradient sum of squares of the last jcm_train_apply
+// (nullptr before the first one)
+const float* train_param_range(jcm_ctx* c, int64_t off, int64_t n);
+const double* train_grad_sumsq(jcm_ctx* c);
 
 }  // namespace jcm
 
@@ -146,6 +151,7 @@ struct jcm_ctx {
   std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
   std::vector<hipEvent_t> event_pool;   // recycled by jcm_profile_read / "profile"=0, destroyed by jcm_destroy
   jcm::TrainState* train = nullptr;   // created by jcm_train_begin
+  double* hist_limits = nullptr;      // summary.hip: the positive half of TF's histogram bucket limits (uploaded on first use)
   std::mutex call_mu;                 // held by the thread whose outermost entry point of this handle is running (CallOrder)
   int call_depth = 0;                 // entry points of this handle on that thread's stack (> 1 only inside a gradient-ready callback)
   jcm::CallOrder* order = nullptr;    // the outermost running entry point's chain guard (notify_ready suspends it around the user callback)

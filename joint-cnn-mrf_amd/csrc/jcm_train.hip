@@ -51,6 +51,7 @@ struct TrainState {
   float* zs_tmax = nullptr;            // ... and the word of their fp16 scaling
   double* red = nullptr;               // per-channel reduction scratch
   double* sumsq = nullptr;             // [2]: grad sum of squares, weight sum of squares (l2)
+  bool grad_sumsq_valid = false;       // sumsq[0] holds the norm of a jcm_train_apply (summary.hip reads it)
   float* small = nullptr;              // [2*maxC + 64] misc
   // spatial model: per-pair parameter pointers / flat-gradient offsets, graph order
   const float** e_ptr = nullptr;
@@ -938,6 +939,7 @@ int jcm_train_apply(jcm_handle h, const float* grads, int optimizer, float lr, f
     HIP_TRY(optimizer_chunks(t->ck_w, t->ck_start, t->ck_off, t->ck_len, t->n_chunks, grads, t->opt_m, t->opt_v, clip ? t->sumsq : nullptr,
                              clip_norm, lr, 0.9f, 0.f, 0.f, 1, c->stream));
   t->step = step;
+  t->grad_sumsq_valid = true;
   if (grad_norm_out) {
     double ss = 0.0;
     HIP_TRY(hipMemcpyAsync(&ss, t->sumsq, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1036,6 +1038,15 @@ int jcm_update_tensor(jcm_handle h, const char* name, const float* data, int64_t
 }  // extern "C"
 
 namespace jcm {
+const float* train_param_range(jcm_ctx* c, int64_t off, int64_t n) {
+  if (!c->train || off < 0 || n < 0) return nullptr;
+  for (const Slot& s : c->train->slots)
+    if ((size_t)off >= s.off && (size_t)(off + n) <= s.off + s.n) return s.w + ((size_t)off - s.off);
+  return nullptr;
+}
+
+const double* train_grad_sumsq(jcm_ctx* c) { return c->train && c->train->grad_sumsq_valid ? c->train->sumsq : nullptr; }
+
 void train_destroy(jcm_ctx* c) {
   delete c->train;      // device buffers are in c->owned
   c->train = nullptr;

@@ -315,6 +315,57 @@ class Engine:
                                                self._p(x_out), self._p(y_out)), 'jcm_augment_train')
         return x_out, y_out
 
+    # ------------------------------------------------------------------ TensorBoard summaries (summary.py)
+    def _on_stream(self, *ts):
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self._stream:
+            self._stream.wait_stream(cur)
+            for t in ts:
+                t.record_stream(self._stream)
+
+    def tensor_stats(self, data, segments, scale=1.0, clip_norm=0.0):
+        """Histogram statistics per segment (offset, count) of the flat device tensor `data`, or of the stored trainable
+        parameters (jcm_train_param_info layout) when `data` is None.  Returns host (stats float64 [n,4] = min, max, sum,
+        sum_squares; counts int64 [n, 3 + JCM_HIST_BUCKETS] = num, n_pos, n_nonfinite, buckets).  clip_norm > 0: the values are
+        scaled by the clip factor of the last optimizer update (see jcm_tensor_stats)."""
+        seg = np.ascontiguousarray(np.asarray(segments, np.int64).reshape(-1, 2))
+        n = seg.shape[0]
+        if data is not None:
+            self._chk(data, 1, 'data')
+            if n and int((seg[:, 0] + seg[:, 1]).max()) > data.numel():
+                raise ValueError('tensor_stats: a segment reaches past the end of data (%d elements)' % data.numel())
+        stats = self._new(n, 4, dtype=torch.float64)
+        counts = self._new(n, 3 + _lib.JCM_HIST_BUCKETS, dtype=torch.int64)
+        if data is not None:
+            self._on_stream(data)
+        _lib.check(self._lib.jcm_tensor_stats(self._h, self._p(data), seg.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n, float(scale),
+                                              float(clip_norm), self._p(stats), self._p(counts)), 'jcm_tensor_stats')
+        return stats.cpu().numpy(), counts.cpu().numpy()
+
+    def image_u8(self, x, out=None):
+        """NormalizeFloatImage (TF-1.x summary_image_op.cc) per image: x [N,H,W,C] fp32, C in {1, 3} -> uint8 [N,H,W,C] device."""
+        self._chk(x, 4, 'x')
+        N, H, W, C = x.shape
+        out = self._new(N, H, W, C, dtype=torch.uint8) if out is None else self._chk(out, 4, 'out', torch.uint8)
+        self._on_stream(x, out)
+        _lib.check(self._lib.jcm_image_u8(self._h, self._p(x), N, H, W, C, self._p(out)), 'jcm_image_u8')
+        return out
+
+    def hm_overlay(self, x, hm, n=None):
+        """show_img_plus_hm (tensorboard.py:60-71) of the first n images: x [B,H,W,3], hm [B,h,w,9] -> uint8 [n,10,H,W,3] device
+        (pictures 0-8: one joint each, 9: all joints)."""
+        self._chk(x, 4, 'x')
+        self._chk(hm, 4, 'hm')
+        B, H, W, C = x.shape
+        n = B if n is None else int(n)
+        if C != 3 or hm.shape[0] != B or not 1 <= n <= B:
+            raise ValueError('hm_overlay expects x [B,H,W,3], hm [B,h,w,K], 1 <= n <= B; got %s, %s, n=%d' % (tuple(x.shape), tuple(hm.shape), n))
+        K = hm.shape[3]
+        out = self._new(n, K + 1, H, W, 3, dtype=torch.uint8)
+        self._on_stream(x, hm, out)
+        _lib.check(self._lib.jcm_hm_overlay(self._h, self._p(x), self._p(hm), n, H, W, hm.shape[1], hm.shape[2], K, self._p(out)), 'jcm_hm_overlay')
+        return out
+
     def set_option(self, key, value):
         """jcm_set_option(key, value) -- include/jcm.h lists the keys."""
         _lib.check(self._lib.jcm_set_option(self._h, key.encode(), int(value)), 'jcm_set_option(%s)' % key)

@@ -70,6 +70,9 @@ def build_parser():
     parser.add_argument('--multiscale', action='store_true', help='evaluation run: 8-scale test-time evaluation (get_predictions, main.py:382-425).')
     parser.add_argument('--predictions', default=None, help='evaluation run: write flic_pred_pd / flic_pred_sm to this .mat file (main.py:675).')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
+    parser.add_argument('--tb_dir', default=None, help='write TensorBoard summaries to DIR/<model_name>/{train,test} (main.py:448-450; off by default).')
+    parser.add_argument('--tb_log_iters', action='store_true', help='with --tb_dir: histograms and scalars after every step to DIR/<model_name>/train_iter '
+                        '(tb_log_iters, main.py:452,642-645).')
     return parser
 
 
@@ -317,6 +320,36 @@ class TowerTrainer:
         return self.trainers[0].losses
 
 
+TB_SCALARS = ['main/mse_pd', 'main/mse_sm', 'main/det_rate_pd', 'main/det_rate_sm']      # main.py:632-635
+IMG_TB_FROM = 450                                                                           # main.py:470
+
+
+def tb_batch(x, y, batch_size):
+    """The summary batch (main.py:470-471,621-626): batch_size images from image 450, or the first batch_size when the split is
+    shorter."""
+    lo = IMG_TB_FROM if x.shape[0] >= IMG_TB_FROM + batch_size else 0
+    return np.ascontiguousarray(x[lo:lo + batch_size], np.float32), np.ascontiguousarray(y[lo:lo + batch_size], np.float32)
+
+
+def tb_open(args, model_name):
+    """tf.summary.FileWriter(tb/<model_name>/{train,test,train_iter}, flush_secs=30) (main.py:448-450,599-601)."""
+    from . import summary
+    root = os.path.join(args.tb_dir, model_name)
+    w = {k: summary.FileWriter(os.path.join(root, k), flush_secs=30) for k in ('train', 'test')}
+    if getattr(args, 'tb_log_iters', False):
+        w['train_iter'] = summary.FileWriter(os.path.join(root, 'train_iter'), flush_secs=30)
+    return w
+
+
+def tb_summaries(writers, eng, layout, batches, use_sm, step, grads=None, params_flat=None):
+    """run_summary of the merged summary for the train and the test batch (main.py:621-626,650-653)."""
+    from . import summary
+    for split, (bx, by) in batches.items():
+        x = torch.as_tensor(bx).to(eng.device)
+        y = torch.as_tensor(by).to(eng.device)
+        summary.run_summary(writers[split], summary.merged_summary(eng, layout, x, y, use_sm, n_joints, grads=grads, params_flat=params_flat), step)
+
+
 def train_main(args):
     """`--train` (main.py:620-667): the reference's epoch loop -- shuffled whole batches (get_next_batch), eval_error on
     the first n_eval_ex train / test examples after every epoch, the reference's progress line, a checkpoint per epoch once
@@ -352,20 +385,37 @@ def train_main(args):
     eng = towers.engines[0]
     model_name = '{}_lr={}_lambda={}_bs={}'.format(time.strftime('%Y-%m-%d %H:%M:%S'), args.lr, args.lmbd, args.batch_size)     # main.py:447
     joints_to_eval, det_radius = [2], 10                                 # main.py:455-456
+    tb = tb_open(args, model_name) if args.tb_dir else None
+    tb_batches = {'train': tb_batch(x_train, y_train, args.batch_size), 'test': tb_batch(x_test, y_test, args.batch_size)} if tb else None
 
     def report(epoch):
+        if tb:      # gradients of the epoch's last update (none before the first)
+            tb_summaries(tb, eng, tt.trainers[0].layout, tb_batches, args.use_sm, epoch, grads=tt.trainers[0].grads if epoch > 0 else None)
         tr_e = evaluation.eval_error(x_train[:n_eval_ex], y_train[:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
         te_e = evaluation.eval_error(x_test[:n_eval_ex], y_test[:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
         print('Epoch {:d}  test_dr {:.3f} {:.3f}  train_dr {:.3f} {:.3f}  test_mse {:.5f} {:.5f}  train_mse {:.5f} {:.5f}'.format(
             epoch, te_e[2], te_e[3], tr_e[2], tr_e[3], te_e[0], te_e[1], tr_e[0], tr_e[1]), flush=True)      # main.py:628-631,656-657
+        if tb:
+            from . import summary
+            summary.write_summary(tb['test'], [float(v) for v in te_e[:4]], TB_SCALARS, epoch)
+            summary.write_summary(tb['train'], [float(v) for v in tr_e[:4]], TB_SCALARS, epoch)
 
     report(0)
+    global_iter = 0
     for epoch in range(1, args.n_epochs + 1):
         for bx, by in evaluation.get_next_batch(x_train, y_train, args.batch_size, shuffle=True, rng=rng):      # main.py:641
             tt.train_step(np.ascontiguousarray(bx, np.float32), np.ascontiguousarray(by, np.float32))
+            global_iter += 1
+            if tb and 'train_iter' in tb:       # main.py:642-645, without the images
+                from . import summary
+                tr0 = tt.trainers[0]
+                summary.run_summary(tb['train_iter'], summary.merged_summary(eng, tr0.layout, use_sm=args.use_sm, n_joints=n_joints,
+                                                                             grads=tr0.grads, images=False), global_iter)
         report(epoch)
         if epoch > args.n_epochs // 2:                                   # main.py:663-666
             tf_checkpoint.save_checkpoint('{}/{}-{}'.format(args.model_path, model_name, epoch), checkpoint.session_state(tt.trainers[0], params))
+    for w in (tb or {}).values():
+        w.close()
     print('Done in {:.2f} min\n\n'.format((time.time() - t_start) / 60))
     return tt
 
@@ -386,13 +436,25 @@ def main(argv=None):
     from . import checkpoint
     from .dist import Towers
     if args.synthetic:
-        _xt, _yt, x_test, y_test = _synthetic_dataset(args.batch_size, args.synthetic_size)
+        x_train, y_train, x_test, y_test = _synthetic_dataset(args.batch_size, args.synthetic_size)
         pairwise = synth.synthetic_priors()
     else:
-        _xt, _yt, x_test, y_test = get_dataset(args.data_dir)
+        x_train, y_train, x_test, y_test = get_dataset(args.data_dir)
         pairwise = get_pairwise_distr(args.data_dir)
     state = restore_params(args.restore_path, args) if args.restore else None
     params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)} if state else initial_params(args, pairwise)
+
+    def eval_tb(eng):      # main.py:668-673: the step-0 summaries, without the gradient parts
+        if not args.tb_dir:
+            return
+        from . import summary
+        model_name = '{}_lr={}_lambda={}_bs={}'.format(time.strftime('%Y-%m-%d %H:%M:%S'), args.lr, args.lmbd, args.batch_size)
+        tb = tb_open(args, model_name)
+        flat, layout = summary.flat_params(eng, params)
+        tb_summaries(tb, eng, layout, {'train': tb_batch(x_train, y_train, args.batch_size), 'test': tb_batch(x_test, y_test, args.batch_size)},
+                     args.use_sm, 0, params_flat=flat)
+        for w in tb.values():
+            w.close()
     # one set of engines only (each fp32 engine caches multi-GB filter spectra): the module engine for the multi-scale wrapper, which runs
     # on one device, or one tower per listed device for the single-scale run
     towers = None
@@ -401,10 +463,12 @@ def main(argv=None):
         if len(args.gpus) > 1:
             print('--multiscale evaluates on device %d only; the other --gpus entries are not used' % args.gpus[0], file=sys.stderr)
         configure(params, device=args.gpus[0], precision=args.precision, debug=args.debug)
+        eval_tb(engine())
         pred_pd, pred_sm = get_predictions(np.asarray(x_test), np.asarray(y_test))                     # main.py:674
     else:                                                                                              # single scale, sharded over the towers
         hps.debug = bool(args.debug)
         towers = Towers(params, args.gpus, precision=args.precision)
+        eval_tb(towers.engines[0])
         B = args.batch_size
         pd, sm = [], []
         for lo in range(0, (x_test.shape[0] // B) * B, B):
