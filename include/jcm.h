@@ -302,7 +302,8 @@ int64_t jcm_workspace_bytes(jcm_handle h);
 int jcm_train_begin(jcm_handle h);                       /* after jcm_finalize: allocates optimizer slots, n_iters = 0 */
 int jcm_train_param_count(jcm_handle h, int64_t* n_tensors, int64_t* n_elements);
 int jcm_train_param_info(jcm_handle h, int64_t index, char* name, int name_cap, int64_t* offset, int64_t* count);
-/* x [B,H,W,3], y = y_in [B,60,90,K+1] target heat maps (main.py:488); grads: device fp32 [n_elements];
+/* x [B,H,W,3], y = y_in [B,hh,ww,K+1] target heat maps (main.py:488) at the heat-map size of the image: hh = ceil(ceil(ceil(H/2)/2)/2),
+ * ww likewise (60x90 for 480x720; use_sm needs 60x90); grads: device fp32 [n_elements];
  * losses: device fp32 [4] = loss_tower, loss_pd, loss_sm, weight_decay('weights'). */
 int jcm_train_loss_grads(jcm_handle h, const float* x, const float* y, int B, int H, int W, int use_sm, float lmbd,
                          float* grads, float* losses);
@@ -310,9 +311,10 @@ int jcm_train_loss_grads(jcm_handle h, const float* x, const float* y, int B, in
  * opt.compute_gradients, main.py:560, evaluates for tf.nn.conv2d, main.py:135): x [B,H,W,Cin] the layer input, dz [B,H,W,Cout] the gradient
  * w.r.t. the convolution output;  grads[<scope>/weights] = sum over (b,y,x) of x (*) dz + lmbd * w  (flat buffer in the layout of
  * jcm_train_param_info, only this slice is written) and dx_out [B,H,W,Cin] (may be NULL) = conv_SAME(dz, flipped transposed w).  Used by the
- * tests to hold the gradient kernels to fp32-class error at full-size layer shapes; fp32 handles, after jcm_train_begin. */
-int jcm_train_layer_grads(jcm_handle h, const char* scope, const float* x, const float* dz, int B, int H, int W, float lmbd,
-                          float* grads, float* dx_out);
+ * tests to hold the gradient kernels to fp32-class error; after jcm_train_begin.  fp32 handles: x, dz, dx_out fp32.  bf16 handles: x, dz and
+ * dx_out bf16 (the tensors the mixed-precision step keeps between the layers), grads fp32. */
+int jcm_train_layer_grads(jcm_handle h, const char* scope, const void* x, const void* dz, int B, int H, int W, float lmbd,
+                          float* grads, void* dx_out);
 /* grads: the (tower-averaged) gradients, same layout; lr: the value of lr_tf for this update
  * (main.py:492); clip_norm <= 0 disables the clip; grad_norm_out (host, may be NULL) receives the
  * global norm before clipping and makes the call synchronise. */

@@ -45,6 +45,7 @@ struct TrainState {
   std::map<std::string, DgradW> dgrad;
   std::map<std::string, BnSave> bn;
   float* scratch_flip = nullptr;       // largest flipped HWIO weight
+  size_t scratch_flip_n = 0;           // ... its size in floats
   void* zs = nullptr;                  // split spectra of the dz the last conv_wgrad saw (frequency-domain route), for the conv_dgrad that follows
   const void* zs_of = nullptr;
   int zs_cin = 0;
@@ -172,9 +173,13 @@ static bool takes_windows(jcm_ctx* c, const ConvLayer* L, int B, int H, int W, i
   ConvArgs a{};
   a.B = B * *TY * *TX; a.H = kWin; a.W = kWin; a.Cin = L->cin; a.Cout = L->cout; a.circ = 1;
   if (!conv_fft_supported(a, L->ks)) return false;
-  // the data gradient runs the same windows through the flipped, transposed filter: a layer with Cin = this layer's Cout padded to 64
+  // the data gradient runs the same windows through the flipped, transposed filter: a layer with Cin = this layer's Cout.  dz reaches it with the
+  // stride of the packed data-gradient filter (Cout rounded up to 16), and the weight gradient takes the windows only for a stride that is a
+  // multiple of 64: a Cout of 80, 96, 160 ... stays on the whole map, where both gradients fall back to the direct kernels (such a layer on windows
+  // ran the data gradient's transform with 96 channels, which conv_fft_f32 refuses: the step failed)
+  if (L->cout % 64) return false;
   ConvArgs d = a;
-  d.Cin = (L->cout + 63) / 64 * 64; d.Cout = L->cin;
+  d.Cin = L->cout; d.Cout = L->cin;
   return conv_fft_supported(d, L->ks);
 }
 
@@ -417,6 +422,7 @@ int conv_dgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int B, void* dx, i
       // windows WITH their halo of real gradient pixels -> the flipped, transposed filter's layer on the 32 x 32 transform -> scatter
       const std::string key = "dgrad:" + f.scope;
       const int BW = B * f.TY * f.TX;
+      if ((size_t)f.L->ks * f.L->ks * cin_fft * f.L->cin > t->scratch_flip_n) return fail(JCM_ERR_STATE, "flipped filter of '" + f.scope + "' does not fit its buffer");
       if (!c->dry && !fft_spectra_valid(c, key, kWin, kWin, 1))
         HIP_TRY(flip_transpose_weights(f.L->w_raw, t->scratch_flip, f.L->ks, f.L->cin, f.L->cout, cin_fft, c->stream));
       t->zs = nullptr;
@@ -436,6 +442,7 @@ int conv_dgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int B, void* dx, i
     }
     if (takes_fft(c, &Ld, B, f.H, f.W)) {
       const std::string key = "dgrad:" + f.scope;
+      if ((size_t)f.L->ks * f.L->ks * cin_fft * f.L->cin > t->scratch_flip_n) return fail(JCM_ERR_STATE, "flipped filter of '" + f.scope + "' does not fit its buffer");
       if (!c->dry && !fft_spectra_valid(c, key, f.H, f.W))
         HIP_TRY(flip_transpose_weights(f.L->w_raw, t->scratch_flip, f.L->ks, f.L->cin, f.L->cout, cin_fft, c->stream));
       if (!c->dry && t->zs && t->zs_of == dz && t->zs_cin == cin_fft) { c->fft_xs = t->zs; c->fft_xs_ready = true; c->fft_tmax_in = t->zs_tmax; }      // the spectra of dz are there (conv_wgrad just made them)
@@ -758,12 +765,17 @@ int jcm_train_begin(jcm_handle h) {
       if (c->f32_conv == 2 && L.cin % 128 == 0)      // data gradient on the fp16x3 split kernel where its tile fits
         JCM_TRY(dev_alloc(c, &d.wd_split, conv_split_weight_bytes(L.ks, d.cinp, L.cin, 2)));
     }
-    const size_t nf = (size_t)L.ks * L.ks * (d.cinp_bf16 > d.cinp ? d.cinp_bf16 : d.cinp) * L.cin;
+    // the flipped filter's dz stride: cinp (direct kernels), cinp_bf16, or -- fp32 handles, frequency-domain data gradient -- a dz widened to 64
+    // channels (the logits path: Cout % 16 != 0, or conv6 with its 16-channel stride), which conv_dgrad flips for with CoP = 64
+    int cop = d.cinp_bf16 > d.cinp ? d.cinp_bf16 : d.cinp;
+    if (c->precision == JCM_PRECISION_F32 && cop < 64) cop = 64;
+    const size_t nf = (size_t)L.ks * L.ks * cop * L.cin;
     if (nf > max_w) max_w = nf;
     t->dgrad[kv.first] = d;
   }
   if (t->maxC < 16) t->maxC = 16;
   JCM_TRY(dev_alloc(c, reinterpret_cast<void**>(&t->scratch_flip), max_w * sizeof(float)));
+  t->scratch_flip_n = max_w;
   JCM_TRY(dev_alloc(c, reinterpret_cast<void**>(&t->opt_m), t->total * sizeof(float)));
   JCM_TRY(dev_alloc(c, reinterpret_cast<void**>(&t->opt_v), t->total * sizeof(float)));
   HIP_TRY(hipMemsetAsync(t->opt_m, 0, t->total * sizeof(float), c->stream));
@@ -883,10 +895,10 @@ int jcm_train_loss_grads(jcm_handle h, const float* x, const float* y, int B, in
 // The two gradient kernels of ONE stride-1 layer on caller-supplied tensors -- the route the training step takes on this handle (frequency
 // domain, direct fp32 MFMA chain, split operands), isolated from the rest of the step so that tests can hold the kernels themselves to a tight
 // bound (inside a full step a ReLU / max-pool decision that rounds the other way upstream moves a gradient by far more than kernel error).
-int jcm_train_layer_grads(jcm_handle h, const char* scope, const float* x, const float* dz, int B, int H, int W, float lmbd, float* grads, float* dx_out) {
+// On a bf16 handle x, dz and dx_out are bf16 (the step's tensors between the layers); grads stays fp32.
+int jcm_train_layer_grads(jcm_handle h, const char* scope, const void* x, const void* dz, int B, int H, int W, float lmbd, float* grads, void* dx_out) {
   JCM_TRY(need_train(h));
   if (!scope || !x || !dz || !grads || B < 1 || H < 1 || W < 1) return fail(JCM_ERR_ARG, "bad train_layer_grads arguments");
-  if (h->precision != JCM_PRECISION_F32) return fail(JCM_ERR_ARG, "train_layer_grads: fp32 handles only (bf16 handles keep bf16 tensors between the layers)");
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
@@ -897,14 +909,31 @@ int jcm_train_layer_grads(jcm_handle h, const char* scope, const float* x, const
   return with_arena(c, [&] {
     LayerFwd f;
     f.scope = scope;
-    JCM_TRY(conv_train_fwd_conv(c, f, 1, x, B, H, W, 1));      // (the frequency-domain weight gradient reads the input spectra the forward pass keeps)
     const size_t NPX = (size_t)B * H * W;
     const void* dl = dz;
     int ldl = L->cout, ldl_fft = 0;
+    if (bf(c)) {
+      // bf16 handles take no frequency-domain gradient route: no forward pass needed.  Both kernels read dz with the 32-channel stride of the
+      // packed data-gradient filter (the step's logits gradient: cast_pad_bf16 to 32 channels); a narrower dz is copied into zero padding
+      f.L = L; f.in = x; f.H = H; f.W = W;
+      const int ldb = t->dgrad[scope].cinp_bf16;
+      if (ldb != L->cout) {
+        void* dpad = act(c, NPX * ldb);
+        if (!c->dry) {
+          HIP_TRY(hipMemsetAsync(dpad, 0, NPX * ldb * 2, c->stream));
+          HIP_TRY(hipMemcpy2DAsync(dpad, (size_t)ldb * 2, dz, (size_t)L->cout * 2, (size_t)L->cout * 2, NPX, hipMemcpyDeviceToDevice, c->stream));
+        }
+        dl = dpad; ldl = ldb;
+      }
+      JCM_TRY(conv_wgrad(c, f, dl, ldl, B, lmbd, grads));
+      if (dx_out) JCM_TRY(conv_dgrad(c, f, dl, B, dx_out));
+      return (int)JCM_OK;
+    }
+    JCM_TRY(conv_train_fwd_conv(c, f, 1, x, B, H, W, 1));      // (the frequency-domain weight gradient reads the input spectra the forward pass keeps)
     if (L->cout % 16) {      // the logits layer: its gradient travels with a 16-channel stride, widened to 64 for the frequency-domain route (loss_grads_impl)
       constexpr int LDZ = 16, LDZF = 64;
       float* d16 = arena_alloc<float>(c, NPX * LDZ);
-      if (!c->dry) HIP_TRY(pad_channels_f32(dz, L->cout, d16, LDZ, NPX, c->stream));
+      if (!c->dry) HIP_TRY(pad_channels_f32(static_cast<const float*>(dz), L->cout, d16, LDZ, NPX, c->stream));
       dl = d16; ldl = LDZ;
       if (f.xs) {
         float* d64 = arena_alloc<float>(c, NPX * LDZF);

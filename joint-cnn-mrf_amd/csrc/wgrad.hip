@@ -197,7 +197,7 @@ __device__ __forceinline__ float4 w1_ld4(const __bf16* p) {
 template <class TZ>
 __global__ __launch_bounds__(256) void wgrad_conv1_kernel(const float* __restrict__ x, const TZ* __restrict__ dz,
                                                           float* __restrict__ partial, int B, int H0, int W0, int sub, int Ho, int Wo,
-                                                          int Cout, int nblk) {
+                                                          int pad_t, int pad_l, int Cout, int nblk) {
   constexpr int XN = 5 * W1_XW * 3, ZN = W1_PX * 64, RN = 96 * 64;
   constexpr int XNP = (XN + 3) / 4 * 4;      // dz behind the patch, 16-byte aligned
   __shared__ __attribute__((aligned(16))) float buf[(XNP + ZN > RN ? XNP + ZN : RN)];
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void wgrad_conv1_kernel(const float* __restric
       const int idx = tid + i * 256;
       const int ch = idx % 3, r = idx / 3;
       const int px = r % W1_XW, ry = r / W1_XW;
-      const int iy = 2 * oy + ry - 1, ix = 2 * ox0 + px - 1;
+      const int iy = 2 * oy + ry - pad_t, ix = 2 * ox0 + px - pad_l;
       xv[i] = 0.f;
       if (idx < XN && (unsigned)iy < (unsigned)Hs && (unsigned)ix < (unsigned)Ws) xv[i] = x[(((size_t)b * H0 + (size_t)iy * sub) * W0 + (size_t)ix * sub) * 3 + ch];
     }
@@ -301,11 +301,14 @@ hipError_t wgrad_conv1(const float* x, const void* dz, bool dz_bf16, float* part
   if (Cout > 64 || Cout % 4) return hipErrorInvalidValue;
   const int Hs = H0 / sub, Ws = W0 / sub;
   const int Ho = (Hs + 1) / 2, Wo = (Ws + 1) / 2;
+  // TF SAME, k = 5, s = 2 (conv1.hip): 1 before / 2 after on an even extent, 2 / 2 on an odd one (the sub-sampled branches of an image whose size
+  // is not a multiple of 8; the kernel used to assume 1 everywhere, which shifted every tap of such a branch by one pixel)
+  const int pad_t = ((Ho - 1) * 2 + 5 - Hs) / 2, pad_l = ((Wo - 1) * 2 + 5 - Ws) / 2;
   const int nblk = wgrad_conv1_blocks();
   if (dz_bf16)
-    hipLaunchKernelGGL(wgrad_conv1_kernel<__bf16>, dim3(nblk), dim3(256), 0, st, x, static_cast<const __bf16*>(dz), partial, B, H0, W0, sub, Ho, Wo, Cout, nblk);
+    hipLaunchKernelGGL(wgrad_conv1_kernel<__bf16>, dim3(nblk), dim3(256), 0, st, x, static_cast<const __bf16*>(dz), partial, B, H0, W0, sub, Ho, Wo, pad_t, pad_l, Cout, nblk);
   else
-    hipLaunchKernelGGL(wgrad_conv1_kernel<float>, dim3(nblk), dim3(256), 0, st, x, static_cast<const float*>(dz), partial, B, H0, W0, sub, Ho, Wo, Cout, nblk);
+    hipLaunchKernelGGL(wgrad_conv1_kernel<float>, dim3(nblk), dim3(256), 0, st, x, static_cast<const float*>(dz), partial, B, H0, W0, sub, Ho, Wo, pad_t, pad_l, Cout, nblk);
   return hipGetLastError();
 }
 

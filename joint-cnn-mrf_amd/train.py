@@ -68,16 +68,24 @@ class Trainer:
         _lib.check(self._lib.jcm_train_steps(self.eng._h, ctypes.byref(n)), 'jcm_train_steps')
         return n.value
 
+    @staticmethod
+    def heat_map_size(H, W):
+        """The heat-map size (hh, ww) of an H x W image: three SAME stride-2 stages (conv1 and the two pools), ceil(ceil(ceil(n/2)/2)/2)."""
+        c = lambda n: -(-n // 2)
+        return c(c(c(H))), c(c(c(W)))
+
     def loss_and_grads(self, x, y, augment=None):
-        """x [B,H,W,3], y [B,60,90,K+1] -> (losses[4] device tensor, flat grads device tensor).
+        """x [B,H,W,3], y [B,hh,ww,K+1] (hh x ww = heat_map_size(H, W): 60x90 for 480x720) -> (losses[4] device tensor, flat grads device tensor).
         losses = (loss_tower, loss_pd, loss_sm, weight_decay).  `augment`: None, or a host [B,6] array of augmentation
         parameters (augmentation.draw_params): the step trains on the augmented copy of (x, y) (main.py:494-497)."""
         e = self.eng
         e._chk(x, 4, 'x')
         e._chk(y, 4, 'y')
         B, H, W, C = x.shape
-        if C != 3 or y.shape[0] != B or y.shape[3] != e.n_joints + 1:
-            raise ValueError('x must be [B,H,W,3] and y [B,h,w,%d]; got %s, %s' % (e.n_joints + 1, tuple(x.shape), tuple(y.shape)))
+        hh, ww = self.heat_map_size(H, W)
+        if C != 3 or tuple(y.shape) != (B, hh, ww, e.n_joints + 1):      # the kernels read y as [B,hh,ww,K+1]: another size would be read past its end
+            raise ValueError('x must be [B,H,W,3] and y [B,%d,%d,%d] (the heat-map size of the image); got %s, %s'
+                             % (hh, ww, e.n_joints + 1, tuple(x.shape), tuple(y.shape)))
         if augment is not None:
             x, y = self._augmented(x, y, augment)
         self._cb_error = None
@@ -106,11 +114,15 @@ class Trainer:
 
     def layer_grads(self, scope, x, dz, want_dx=True):
         """The weight gradient (+ lmbd * w) and the data gradient of ONE stride-1 conv layer on given tensors, through the kernels the training
-        step uses on this engine: x [B,H,W,Cin], dz [B,H,W,Cout] -> (dw flat numpy [k*k*Cin*Cout] in HWIO order, dx [B,H,W,Cin] device or None)."""
+        step uses on this engine: x [B,H,W,Cin], dz [B,H,W,Cout] -> (dw flat numpy [k*k*Cin*Cout] in HWIO order, dx [B,H,W,Cin] device or None).
+        fp32 engines take fp32 x and dz; bf16 engines bf16 x and dz (the mixed-precision step's tensors) and return a bf16 dx."""
         e = self.eng
-        e._chk(x, 4, 'x')
-        e._chk(dz, 4, 'dz')
+        dt = torch.bfloat16 if e.precision == 'bf16' else torch.float32
+        e._chk(x, 4, 'x', dt)
+        e._chk(dz, 4, 'dz', dt)
         B, H, W, _ = x.shape
+        if tuple(dz.shape[:3]) != (B, H, W):
+            raise ValueError('dz must be [%d,%d,%d,Cout]; got %s' % (B, H, W, tuple(dz.shape)))
         dx = torch.empty_like(x) if want_dx else None
         _lib.check(self._lib.jcm_train_layer_grads(e._h, scope.encode(), e._p(x), e._p(dz), B, H, W, self.lmbd, e._p(self.grads), e._p(dx)),
                    'jcm_train_layer_grads(%s)' % scope)

@@ -109,3 +109,17 @@ def sampled_conv_grads(x, dz, w, lmbd, rs, n=40):
         xi.append((nb, y0, x0, ci))
         xv.append(v)
     return (np.array(wi), np.array(wv)), (xi, np.array(xv))
+
+
+def dense_conv_grads(x, dz, w, lmbd):
+    """float64 values of EVERY entry of the two gradients of z = conv2d_SAME(x, w) (stride 1; x [B,H,W,Cin], dz [B,H,W,Cout], w HWIO):
+    (dW + lmbd w [k,k,Cin,Cout], dX [B,H,W,Cin]), by autograd through the restated tf.nn.conv2d (oracle/jcm_oracle_torch.conv2d_same) on CPU
+    (pinned against sampled_conv_grads and a known answer: tests/test_oracle_kat.py::test_dense_conv_grads_*)."""
+    import torch
+    from oracle import jcm_oracle_torch as T
+    w64 = np.asarray(w, np.float64)
+    xt = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64).transpose(0, 3, 1, 2))).requires_grad_(True)
+    wt = torch.from_numpy(w64.copy()).requires_grad_(True)
+    zt = torch.from_numpy(np.ascontiguousarray(np.asarray(dz, np.float64).transpose(0, 3, 1, 2)))
+    gx, gw = torch.autograd.grad(T.conv2d_same(xt, wt, 1), [xt, wt], grad_outputs=zt)
+    return gw.numpy() + lmbd * w64, np.ascontiguousarray(gx.numpy().transpose(0, 2, 3, 1))

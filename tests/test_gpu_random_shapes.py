@@ -272,3 +272,229 @@ print('ok')
     env = dict(os.environ, JCM_FFT_CACHE_GB='0', PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(__file__)))] + sys.path))
     r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and 'ok' in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ---- the gradient kernels of one stride-1 layer (jcm_train_layer_grads) at shapes beyond the model's own, every entry against float64
+# (tests/test_gpu_train.py::test_gradient_kernels_at_full_size_layer_shapes holds them at the nine full-size layer shapes, sampled)
+def grad_cases():
+    """(i, B, H, W, Cin, Cout, ks, what the case is for).  Every case's float64 reference stays below ~40 GFLOP (4 B H W Cin Cout ks^2)."""
+    out = [(0, 2, 4, 37, 64, 64, 9, 'H < ks: weight-gradient rows with nvalid <= 0'),
+           (1, 3, 21, 3, 48, 16, 5, 'W < ks; Cin 48: direct kernels, last 64-channel tile of 48'),
+           (2, 1, 17, 61, 64, 128, 9, 'W % 30 == 1: a last strip of one pixel'),
+           (3, 2, 11, 59, 80, 96, 9, 'W % 30 == 29; Cin 80 / Cout 96: last channel tiles of 16 and 32'),
+           (4, 3, 19, 45, 16, 160, 5, 'Cin 16, Cout 160'),
+           (5, 1, 23, 31, 80, 160, 9, 'Cin 80, Cout 160, W % 30 == 1'),
+           (6, 2, 30, 44, 128, 16, 9, 'Cout 16: frequency-domain forward, gradients on the direct kernels (ldz % 64)'),
+           (7, 1, 26, 40, 64, 96, 5, 'Cout 96: frequency-domain forward, gradients on the direct kernels (ldz % 64)'),
+           (8, 2, 15, 23, 128, 9, 9, 'Cout 9: logits path, dz padded to 16 and widened to 64 (frequency domain; the flipped filter at 64 channels)'),
+           (9, 3, 13, 29, 48, 10, 9, 'Cout 10: logits path, dz padded to 16 (direct kernels)'),
+           (10, 1, 33, 50, 64, 9, 5, 'Cout 9, 5x5: logits path in the frequency domain'),
+           (11, 1, 49, 25, 128, 256, 9, 'windows 3 x 2, one valid row and one valid column in the last ones'),
+           (12, 1, 73, 25, 128, 256, 9, 'windows 4 x 2, one valid row / column in the last ones'),
+           (13, 1, 25, 97, 256, 128, 9, 'windows 2 x 5, one valid row / column in the last ones'),
+           (14, 1, 48, 72, 128, 256, 9, 'windows 2 x 3, the map fills its last window exactly'),
+           (15, 32, 5, 70, 128, 256, 5, '5x5 on windows, B = 32 (the largest batch on windows)'),
+           (16, 33, 5, 70, 128, 256, 5, 'B = 33: the same layer on the whole-map transform'),
+           (17, 1, 25, 49, 512, 96, 9, 'Cin Cout >= 128 x 256 with Cout % 64 != 0: whole map (the windows need a 64-channel dz stride)')]
+    rs = np.random.RandomState(2025)
+    for i in range(18, 26):
+        ks = int(rs.choice([5, 9]))
+        cin, cout = int(rs.choice([16, 32, 48, 64, 128])), int(rs.choice([9, 16, 32, 64, 96, 128]))
+        out.append((i, int(rs.choice([1, 2, 3])), int(rs.randint(3, 40)), int(rs.randint(3, 70)), cin, cout, ks, 'seeded'))
+    # the stride-1 layers of the debug-width step at 200 x 296 (test_pd_only_step_other_image_sizes), full-resolution branch, 2 images
+    out += [(26, 2, 50, 74, 16, 32, 5, 'debug conv2_fullres at 200x296'), (27, 2, 25, 37, 32, 64, 9, 'debug conv3_fullres at 200x296'),
+            (28, 2, 25, 37, 64, 128, 9, 'debug conv4_fullres at 200x296'), (29, 2, 25, 37, 128, 128, 9, 'debug conv5 at 200x296'),
+            (30, 2, 25, 37, 128, 9, 9, 'debug conv6 at 200x296')]
+    return out
+
+
+def _fft_len(n):
+    return next((v for v in (20, 24, 28, 32, 36, 40, 50, 60, 64, 72, 96, 100, 128, 192) if v >= n), None)
+
+
+def grad_routes(B, H, W, cin, cout, ks):
+    """Restates jcm_train.hip's route choice of the default fp32 handle: (frequency-domain forward, windows, weight-gradient route, data-gradient
+    route), routes 'win' / 'fft' / 'mfma'.  The forward is observable (conv_kernel_name), the windows are (their result differs bit-wise from
+    fft_windows = 0); the rest is asserted through the error bound of the route.  The window thresholds follow the library's environment overrides
+    (JCM_WIN_FREQ_RATIO, JCM_WIN_MIN_CC; defaults 1.5 and 128 x 256)."""
+    import os
+    ratio = float(os.environ.get('JCM_WIN_FREQ_RATIO', '1.5'))
+    min_cc = int(os.environ.get('JCM_WIN_MIN_CC', str(128 * 256)))
+    fft = cin % 64 == 0 and H + ks - 1 <= 192 and W + ks - 1 <= 192
+    win = (fft and cin * cout >= min_cc and B <= 32 and cout % 64 == 0 and
+           ratio * 32 * 17 <= _fft_len(H + 4) * (_fft_len(W + 4) // 2 + 1))
+    ldz = cout if cout % 16 == 0 else 64      # the logits path widens dz to 64 channels on the frequency-domain route
+    g = 'win' if win else ('fft' if fft and ldz % 64 == 0 else 'mfma')
+    return fft, win, g, g
+
+
+GRAD_BOUND = {'win': 1e-6, 'fft': 1e-6, 'mfma': 8e-6, 'split': 8e-6}
+
+
+def grad_layer_params(rs, cin, cout, ks):
+    """layer_params, without BatchNorm for a logits-style layer (Cout % 16 != 0, like conv6)."""
+    p = layer_params(rs, cin, cout, ks)
+    return p if cout % 16 == 0 else {k: v for k, v in p.items() if 'BatchNorm' not in k}
+
+
+def grad_tensors(rs, B, H, W, cin, cout):
+    """x = relu(N(0,1)); dz as BatchNorm's backward leaves it: zero mean per channel, scale ~1e-3 (test_gradient_kernels_at_full_size_layer_shapes)."""
+    x = np.maximum(rs.standard_normal((B, H, W, cin)), 0).astype(np.float32)
+    dz = rs.standard_normal((B, H, W, cout)) * 1e-3
+    return x, (dz - dz.mean(axis=(0, 1, 2), keepdims=True)).astype(np.float32)
+
+
+def layer_grads_checked(tr, x, dz, lmbd):
+    """jcm_train_layer_grads of scope 'c' through the C ABI on a gradient buffer and a dx filled with NaN: only the layer's weight slice is written
+    (every other element keeps its NaN, bit for bit), every dx entry is written, and a second identical call is bit-identical.  -> (dW, dx) numpy."""
+    from joint_cnn_mrf_amd import _lib
+    e = tr.eng
+    off, cnt = next((o, c) for n, o, c in tr.layout if n == 'c/weights')
+    res = []
+    for _ in range(2):
+        grads = torch.full((tr.n_elements,), float('nan'), dtype=torch.float32, device=e.device)
+        dx = torch.full(x.shape, float('nan'), dtype=x.dtype, device=e.device)
+        _lib.check(tr._lib.jcm_train_layer_grads(e._h, b'c', e._p(x), e._p(dz), x.shape[0], x.shape[1], x.shape[2], float(lmbd), e._p(grads), e._p(dx)),
+                   'jcm_train_layer_grads')
+        torch.cuda.synchronize()
+        g = grads.cpu()
+        assert torch.isfinite(g[off:off + cnt]).all(), "non-finite entries in the layer's weight-gradient slice"
+        rest = torch.cat([g[:off], g[off + cnt:]]).view(torch.int32)
+        assert (rest == torch.tensor(float('nan')).view(torch.int32)).all(), 'elements outside the layer slice were written'
+        assert not torch.isnan(dx).any(), 'dx entries left unwritten: %d' % int(torch.isnan(dx).sum())
+        res.append((g[off:off + cnt].numpy().copy(), dx.float().cpu().numpy()))
+    assert np.array_equal(res[0][0].view(np.int32), res[1][0].view(np.int32)) and np.array_equal(res[0][1].view(np.int32), res[1][1].view(np.int32)), \
+        'a second identical call is not bit-identical'
+    return res[0]
+
+
+def _rel(got, ref):
+    return float(np.abs(got.astype(np.float64).reshape(ref.shape) - ref).max() / max(np.abs(ref).max(), 1e-300))
+
+
+# one wide case per route for the scale edges (dz = 0, dz x 1e-9, dz x 3e7)
+SCALE_CASE = {'win': 11, 'fft': 2, 'mfma': 5, 'split': 11}
+
+
+@pytest.mark.parametrize('case', grad_cases(), ids=lambda c: 'B%d_%dx%d_%d-%d_k%d' % c[1:7])
+def test_gradient_kernels_random_shape(case):
+    """jcm_train_layer_grads of one stride-1 layer, EVERY entry of dW (+ lmbd w) and dX against dense_conv_grads (float64 autograd), on the
+    default fp32 handle ('exact': frequency domain, on 32 x 32 overlap-save windows where takes_windows allows), with the windows off
+    ('exact_nowin'), on the fp32 MFMA chain ('chain': conv9_fft off) and on the fp16x3 direct kernels ('split16').  Bounds relative to the tensor's
+    largest reference entry, those of test_gradient_kernels_at_full_size_layer_shapes: 1e-6 for the frequency-domain routes, 8e-6 for the
+    direct kernels.  Every call runs through layer_grads_checked (the entry point writes its slice and every dx entry, deterministically)."""
+    from joint_cnn_mrf_amd.engine import Engine
+    from joint_cnn_mrf_amd.train import Trainer
+    from golden_util import dense_conv_grads
+    i, B, H, W, cin, cout, ks, what = case
+    lmbd = 0.001
+    rs = np.random.RandomState(300 + i)
+    p = grad_layer_params(rs, cin, cout, ks)
+    w = p['c/weights']
+    x, dz = grad_tensors(rs, B, H, W, cin, cout)
+    ref_w, ref_x = dense_conv_grads(x, dz, w, lmbd)
+    xd, zd = torch.as_tensor(x, device='cuda:0'), torch.as_tensor(dz, device='cuda:0')
+    fft, win, wroute, droute = grad_routes(B, H, W, cin, cout, ks)
+    modes = [('exact', dict(f32_conv='exact'), (wroute, droute)), ('chain', dict(f32_conv='exact', conv9_fft=False), ('mfma', 'mfma')),
+             ('split16', dict(f32_conv='split16', split_min_wgs=0), ('split', 'split'))]
+    if fft:
+        modes.insert(1, ('exact_nowin', dict(f32_conv='exact'), (wroute if not win else 'fft', droute if not win else 'fft')))
+    got = {}
+    bad = []
+    for mode, kw, (rw, rx) in modes:
+        eng = Engine(device=0, **kw).load_params(p)
+        tr = Trainer(eng, use_sm=False, lmbd=lmbd)
+        if mode == 'exact_nowin':
+            eng.set_option('fft_windows', 0)
+        assert eng.conv_kernel_name('c', B, H, W).startswith('conv_fft') == (fft and mode in ('exact', 'exact_nowin')), mode
+        dw, dx = got[mode] = layer_grads_checked(tr, xd, zd, lmbd)
+        ew, ex = _rel(dw, ref_w), _rel(dx, ref_x)
+        print('  %-11s %-4s/%-4s dW err / max|dW| %.2e   dX err / max|dX| %.2e   (%s)' % (mode, rw, rx, ew, ex, what))
+        if not (ew <= GRAD_BOUND[rw] and ex <= GRAD_BOUND[rx]):
+            bad.append((mode, rw, ew, rx, ex))
+        route = {'exact': wroute, 'chain': 'mfma', 'split16': 'split'}.get(mode)
+        if route is not None and SCALE_CASE[route] == i:
+            check_grad_scale_edges(tr, x, dz, w, ref_w - lmbd * w.astype(np.float64), ref_x, GRAD_BOUND[rw], GRAD_BOUND[rx], mode)
+        eng.close()
+    assert not bad, bad
+    if fft:      # the windows are taken exactly where the route restatement says so
+        same = np.array_equal(got['exact'][0], got['exact_nowin'][0]) and np.array_equal(got['exact'][1], got['exact_nowin'][1])
+        assert same != win, 'windows taken: %s, expected %s' % (not same, win)
+
+
+def check_grad_scale_edges(tr, x, dz, w, dw_data, dx_ref, bound_w, bound_x, mode):
+    """dz = 0: dW = lmbd w to fp32 rounding and dx exactly 0; dz x 1e-9 and x 3e7 (lmbd = 0: the data term alone, the gains of
+    test_split16_is_range_free): the route's relative bound holds -- every operand is lifted by its own power-of-two scale."""
+    lmbd = 0.001
+    xd = torch.as_tensor(x, device='cuda:0')
+    dw, dx = layer_grads_checked(tr, xd, torch.zeros(dz.shape, dtype=torch.float32, device='cuda:0'), lmbd)
+    want = lmbd * w.astype(np.float64).reshape(-1)
+    assert (np.abs(dw.astype(np.float64) - want) <= 2.0 ** -23 * np.abs(want)).all(), '%s: dz = 0 does not give lmbd w' % mode
+    assert not dx.any() and not np.isnan(dx).any(), '%s: dz = 0 does not give dx = 0' % mode
+    for gain in (1e-9, 3e7):
+        dw, dx = layer_grads_checked(tr, xd, torch.as_tensor((dz * np.float32(gain)).astype(np.float32), device='cuda:0'), 0.0)
+        ew, ex = _rel(dw, gain * dw_data), _rel(dx, gain * dx_ref)
+        print('  %-11s dz x %.0e: dW %.2e  dX %.2e' % (mode, gain, ew, ex))
+        assert ew <= bound_w and ex <= bound_x, (mode, gain, ew, ex)
+
+
+# bf16 weight gradient (wgrad_split.hip, NP = 1: exact bf16 products, fp32 accumulation), relative to max|dW|: measured worst 1.2e-7 over the
+# sweep's bf16 cases (5x5 on windows, B = 32), the bound ~4x that
+BF16_DW_BOUND = 5e-7
+
+
+@pytest.mark.parametrize('case', [c for c in grad_cases() if c[4] % 32 == 0], ids=lambda c: 'B%d_%dx%d_%d-%d_k%d' % c[1:7])
+def test_bf16_gradient_kernels_random_shape(case):
+    """jcm_train_layer_grads on a bf16 handle (the mixed-precision step's kernels: wgrad_bf16 and the data gradient through conv_igemm_bf16 on
+    the flipped weights; bf16 x, dz, dx, fp32 grads) over the sweep's shapes with Cin % 32 == 0.  dW against dense_conv_grads on the bf16 values
+    of x and dz (+ lmbd times the fp32 master weights): the products are exact, so only fp32 accumulation separates them.  dX against the same on
+    bf16-rounded weights, rounded to bf16: check_bf16_layer (one bf16 ulp plus accumulation slack, <= 2 % of the entries rounded differently)."""
+    from joint_cnn_mrf_amd.engine import Engine
+    from joint_cnn_mrf_amd.train import Trainer
+    from golden_util import dense_conv_grads
+    i, B, H, W, cin, cout, ks, what = case
+    lmbd = 0.001
+    rs = np.random.RandomState(300 + i)
+    p = grad_layer_params(rs, cin, cout, ks)
+    w = p['c/weights']
+    x, dz = grad_tensors(rs, B, H, W, cin, cout)
+    xb, zb = torch.as_tensor(x).to(torch.bfloat16), torch.as_tensor(dz).to(torch.bfloat16)
+    x64, z64 = xb.double().numpy(), zb.double().numpy()
+    ref_w, _ = dense_conv_grads(x64, z64, w, lmbd)
+    _, ref_x = dense_conv_grads(x64, z64, O.bf16_round(w.astype(np.float64)), 0.0)
+    eng = Engine(device=0, precision='bf16').load_params(p)
+    tr = Trainer(eng, use_sm=False, lmbd=lmbd)
+    with pytest.raises(TypeError):
+        tr.layer_grads('c', torch.as_tensor(x, device='cuda:0'), torch.as_tensor(dz, device='cuda:0'))      # fp32 tensors on a bf16 handle
+    dw, dx = layer_grads_checked(tr, xb.cuda(), zb.cuda(), lmbd)
+    dw2, dx2 = tr.layer_grads('c', xb.cuda(), zb.cuda())
+    assert dx2.dtype == torch.bfloat16 and np.array_equal(dw2, dw) and np.array_equal(dx2.float().cpu().numpy(), dx)
+    eng.close()
+    ew = _rel(dw, ref_w)
+    refb = O.bf16_round(ref_x)
+    flips = float((dx.astype(np.float64) != refb).mean())
+    print('  bf16 dW err / max|dW| %.2e   dX entries off the rounded reference %.2f %%, worst %.2e of max   (%s)'
+          % (ew, 100 * flips, _rel(dx, refb), what))
+    assert ew <= BF16_DW_BOUND, ew
+    check_bf16_layer(dx.astype(np.float64), refb)
+
+
+def test_bf16_layer_grads_refusals():
+    """A bf16 handle refuses a layer the mixed-precision step cannot train (Cin % 32 != 0: the sweep's Cin 16 / 48 / 80 cases) before any
+    gradient kernel runs, and jcm_train_layer_grads refuses a layer that is not a stride-1 convolution, with messages that say so."""
+    from joint_cnn_mrf_amd.engine import Engine
+    from joint_cnn_mrf_amd.train import Trainer
+    rs = np.random.RandomState(9)
+    for cin in (16, 48, 80):
+        eng = Engine(device=0, precision='bf16')
+        with pytest.raises(RuntimeError, match=r'Cin % 32 == 0'):
+            eng.load_params(layer_params(rs, cin, 64, 9))
+            Trainer(eng, use_sm=False)
+        eng.close()
+    from joint_cnn_mrf_amd import synth
+    eng = Engine(device=0, precision='bf16').load_params(synth.make_pd_params(debug=False, bn='trained'))
+    tr = Trainer(eng, use_sm=False)
+    x = torch.zeros((1, 16, 16, 3), dtype=torch.bfloat16, device='cuda:0')
+    with pytest.raises(RuntimeError, match='is not a stride-1 conv layer'):
+        tr.layer_grads('conv1_fullres', x, torch.zeros((1, 16, 16, 8), dtype=torch.bfloat16, device='cuda:0'))
+    eng.close()

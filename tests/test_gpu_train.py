@@ -1,6 +1,8 @@
 """Joint training step on the GPU against oracle/train_oracle.py
 (float64 autograd restatement of main.py:511-577).  Gradients are compared per tensor,
 relative to that tensor's largest entry: 1e-4, the heat-map tolerance of the forward path."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -76,6 +78,68 @@ def test_pd_only_loss_and_grads(debug_case):
     for k in got:                                    # the loss does not reach the spatial model: exact zeros
         if k.startswith('energy_') or k.startswith('bias_') or k.startswith('bn_sm'):
             assert not got[k].any(), k
+
+
+OTHER_SIZES = [(244, 364, 3), (200, 296, 2), (484, 724, 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def other_size_case(size):
+    """(params, x, y, float64 step, float32 step, moving statistics after it) of the debug-width part detector at one OTHER_SIZES entry: the
+    restatements are computed once per size and shared by the three modes."""
+    from joint_cnn_mrf_amd.train import Trainer
+    H, W, B = size
+    hh, ww = Trainer.heat_map_size(H, W)
+    p = synth.make_pd_params(debug=True, bn='trained', seed=H)
+    x = synth.make_images(B, seed=H + 1, height=H, width=W)
+    y = synth.make_targets(B, seed=H + 2, hm_height=hh, hm_width=ww)
+    ref = T.loss_and_grads(x, y, p, use_sm=False, lmbd=0.001)
+    ref32 = T.loss_and_grads(x, y, p, use_sm=False, lmbd=0.001, dtype=torch.float32)
+    return p, x, y, ref, ref32, T.update_moving(p, ref['bn_stats'])
+
+
+@pytest.mark.parametrize('mode', ['exact', 'chain', 'split16'])
+@pytest.mark.parametrize('size', OTHER_SIZES, ids=lambda s: '%dx%d_B%d' % s)
+def test_pd_only_step_other_image_sizes(size, mode, request):
+    """The part-detector step at image sizes other than 480x720 (debug width, use_sm off): odd conv1 inputs on the sub-sampled branches (stride 2,
+    asymmetric SAME padding: wgrad_conv1_kernel), odd max pools at every level, and branch-merge resizes other than 30->60 / 23->90 (16x23 and
+    8x12 -> 31x46, 13x19 and 7x10 -> 25x37, 31x46 and 16x23 -> 61x91), in the three fp32 modes against the float64 restatement: losses to 2e-5,
+    every gradient tensor to GRAD_RTOL (+ the float32 run's own distance), the moving statistics as in test_moving_statistics_update."""
+    H, W, B = size
+    if (H, W, mode) == (200, 296, 'exact'):
+        # open finding: on the frequency-domain route the full-resolution branch of a 200x296 image (25x37 maps) is off by up to 1.4e-3 of
+        # max|g| (conv4_fullres/weights; the f32 slack is 4e-6), the chain and split16 routes are not.  jcm_train_layer_grads of the same layers
+        # at the same shapes (debug conv2..conv6 at 200x296, 2 images: cases 26-30 of test_gradient_kernels_random_shape) stays within 2.5e-7 on
+        # that route, so the cause lies in how the step hands tensors between those kernels, not in the kernels; not found yet
+        request.applymarker(pytest.mark.xfail(strict=True, reason='frequency-domain step at 25x37 maps: open finding'))
+    p, x, y, ref, ref32, want = other_size_case(size)
+    eng, tr = make_trainer(p, f32_conv='exact' if mode == 'chain' else mode, conv9_fft=False if mode == 'chain' else None, use_sm=False, lmbd=0.001)
+    losses, _ = tr.loss_and_grads(dev(x), dev(y))
+    got = tr.grads_dict()
+    l = losses.cpu().numpy()
+    moving = {k: tr.get_tensor(k, np.asarray(p[k]).shape) for k in want}
+    eng.close()
+    np.testing.assert_allclose(l, [ref['loss'], ref['loss_pd'], ref['loss_sm'], ref['l2']], rtol=2e-5)
+    check_grads(got, ref['grads'], ref32['grads'], verbose=True)
+    for k in want:
+        np.testing.assert_allclose(moving[k], want[k], rtol=2e-5, atol=1e-7, err_msg=k)
+
+
+def test_step_refuses_other_heat_map_sizes():
+    """The spatial model at a heat-map size other than 60x90 is refused by the library, and a y whose spatial size is not the image's heat-map
+    size raises ValueError before any kernel runs (the kernels read y as [B,hh,ww,K+1]: a smaller y was read past its end)."""
+    H, W, B = OTHER_SIZES[0]
+    p = synth.make_pd_params(debug=True, bn='trained')
+    p.update(synth.make_sm_params(synth.synthetic_priors(), kind='trained'))
+    eng, tr = make_trainer(p, use_sm=True, lmbd=0.001)
+    x = dev(synth.make_images(B, height=H, width=W))
+    with pytest.raises(RuntimeError, match='60x90 heat maps'):
+        tr.loss_and_grads(x, dev(synth.make_targets(B, hm_height=31, hm_width=46)))
+    with pytest.raises(ValueError, match='heat-map size'):
+        tr.loss_and_grads(x, dev(synth.make_targets(B)))                                # a 60x90 y for a 244x364 image
+    with pytest.raises(ValueError, match='heat-map size'):                              # ... and a y smaller than the 60x90 of a 480x720 image
+        tr.loss_and_grads(dev(synth.make_images(B)), dev(synth.make_targets(B, hm_height=30, hm_width=45)))
+    eng.close()
 
 
 def test_joint_loss_and_grads(debug_case, joint_ref):

@@ -191,3 +191,53 @@ def test_sampled_conv_grads_match_autograd(k):
     (wi, wv), (xi, xv) = sampled_conv_grads(x, dz, w, lmbd, np.random.RandomState(1), n=60)
     np.testing.assert_allclose(wv, gw[wi], rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(xv, [gx[i] for i in xi], rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize('shape', [(2, 7, 10, 3, 4, 5), (1, 4, 11, 16, 9, 9), (3, 12, 3, 8, 5, 5), (1, 1, 1, 2, 3, 9), (2, 13, 31, 5, 6, 9)],
+                         ids=lambda s: 'B%d_%dx%d_%d-%d_k%d' % s)
+def test_dense_conv_grads_match_sampled_sums(shape):
+    """tests/golden_util.dense_conv_grads (the dense float64 reference of the gradient-kernel sweeps) against the float64 sums taken straight from
+    the definition (sampled_conv_grads) at every sampled entry, corners included -- maps smaller than the kernel among them (H or W < ks)."""
+    from golden_util import dense_conv_grads, sampled_conv_grads
+    B, H, W, cin, cout, k = shape
+    rs = np.random.RandomState(B * 100 + H)
+    x = rs.standard_normal((B, H, W, cin)).astype(np.float32)
+    dz = rs.standard_normal((B, H, W, cout)).astype(np.float32)
+    w = rs.standard_normal((k, k, cin, cout)).astype(np.float32)
+    dw, dx = dense_conv_grads(x, dz, w, 0.01)
+    assert dw.shape == w.shape and dx.shape == x.shape and dw.dtype == np.float64 and dx.dtype == np.float64
+    (wi, wv), (xi, xv) = sampled_conv_grads(x, dz, w, 0.01, np.random.RandomState(2), n=60)
+    np.testing.assert_allclose(dw.reshape(-1)[wi], wv, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose([dx[i] for i in xi], xv, rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize('k', [5, 9])
+def test_dense_conv_grads_known_answer(k):
+    """One input pixel and one output-gradient pixel, both 1: dW is 1 at the single tap that connects them (the SAME padding puts input row
+    y + a - p under output row y, so the tap is (a, b) = (yi - yo + p, xi - xo + p)) and lmbd w elsewhere; dX is w's flipped tap column under
+    the output pixel.  A tap outside the kernel (pixels too far apart) gives dW = lmbd w exactly."""
+    from golden_util import dense_conv_grads
+    p = (k - 1) // 2
+    rs = np.random.RandomState(k)
+    w = rs.standard_normal((k, k, 2, 3))
+    x = np.zeros((1, 6, 8, 2))
+    dz = np.zeros((1, 6, 8, 3))
+    x[0, 4, 1, 1] = 1.0
+    dz[0, 3, 2, 2] = 1.0
+    dw, dx = dense_conv_grads(x, dz, w, 0.5)
+    want = 0.5 * w
+    want[4 - 3 + p, 1 - 2 + p, 1, 2] += 1.0
+    np.testing.assert_array_equal(dw, want)
+    wx = np.zeros((1, 6, 8, 2))
+    for a in range(k):
+        for b in range(k):
+            y, xx = 3 + a - p, 2 + b - p
+            if 0 <= y < 6 and 0 <= xx < 8:
+                wx[0, y, xx] = w[a, b, :, 2]
+    np.testing.assert_allclose(dx, wx, rtol=0, atol=1e-15)
+    x2 = np.zeros((1, 6, 30, 2))
+    dz2 = np.zeros((1, 6, 30, 3))
+    x2[0, 0, 0, 0] = 1.0
+    dz2[0, 5, 29, 1] = 1.0
+    dw2, _ = dense_conv_grads(x2, dz2, w, 0.5)
+    np.testing.assert_array_equal(dw2, 0.5 * w)
