@@ -99,6 +99,9 @@ int jcm_abi_version(void);
  *              spectra; and the product spectra between the channel GEMM and the inverse column pass as complex fp16 under a CONSTANT
  *              power-of-two shift (2^-(ceil(log2 Cin) + 14): the scaled operands bound every product, so nothing can overflow and typical
  *              entries sit fourteen binades above fp16's smallest normal number; round 5).  0 = complex fp32 for all three (round 3).
+ * "fft_tiles": any time, default 1 (fp32 handles, with "fft_fuse" bit 0): conv2 of a 120 x 180 map -> pool -> conv3 runs as 2 x 2 tiles of 60 x 90, each with its
+ *              2-pixel halo in the 64 x 96 transform of the 60 x 90 maps (a quarter of the filter spectra, register transform kernels).  0 = the whole map.
+ *              Environment JCM_FFT_TILES=0 (read once per process) turns the tiles off as well.
  * "fft_fuse" : any time, default 3 (jcm_pd_forward / jcm_forward on the frequency-domain route): hand-overs in row-transformed form, ONE kernel doing the
  *              inverse row transform + bias / ReLU / BatchNorm of the producing layer, the op between the layers and the forward row transform of the
  *              consuming layer.  bit 0 (fp32 handles) = conv2 -> 2x2 max pool -> conv3: a work group owns a row pair, takes the 2x2 maximum in LDS

@@ -217,6 +217,11 @@ static bool fft_reg_on() {
   static const bool on = [] { const char* e = std::getenv("JCM_FFT_REG"); return !e || std::atoi(e) != 0; }();
   return on;
 }
+// JCM_FFT_TILES=0 (environment, read once): conv2_fullres -> pool -> conv3 on the whole 120 x 180 map -- the A/B arm of the 2 x 2 tiles (ConvArgs::tiles)
+static bool fft_tiles_on() {
+  static const bool on = [] { const char* e = std::getenv("JCM_FFT_TILES"); return !e || std::atoi(e) != 0; }();
+  return on;
+}
 static int padn(int c, int n) { return (c + n - 1) / n * n; }
 
 int persistent_grid(const void* kernel, int ntiles, int threads, int dyn_lds) {
@@ -326,11 +331,18 @@ Plan3 plan_of(const ConvArgs& a, const Sizes& s, int np) {
   return p;
 }
 size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+// a tiled layer (ConvArgs::tiles) as the columns, the GEMM and the inverse column pass see it: 4 B images of an NY x NX transform whose NY rows are all real
+ConvArgs tile_view(const ConvArgs& a, const Sizes& s) {
+  ConvArgs t = a;
+  t.B = 4 * a.B; t.H = s.NY; t.W = a.W / 2;
+  t.tiles = 0;
+  return t;
+}
 }  // namespace
 size_t conv_fft_workspace_bytes(const ConvArgs& a, int ks, int np) {
   Sizes s;
-  if (!sizes_of(a.H, a.W, ks, &s, a.circ)) return 0;
-  const Plan3 p = plan_of(a, s, np);
+  if (!(a.tiles ? sizes_of(a.H / 2, a.W / 2, ks, &s) : sizes_of(a.H, a.W, ks, &s, a.circ))) return 0;
+  const Plan3 p = a.tiles ? plan_of(tile_view(a, s), s, np) : plan_of(a, s, np);
   return align256(p.t_bytes) + align256(p.xs_bytes) + align256(p.yf_bytes) + align256(p.sc_fwd_bytes) + align256(p.sc_inv_bytes);
 }
 // Can layer L (a, ks) hand its output to layer L+1 (kernel size ks_next, same map) in row-transformed form?  Same NX for both kernel
@@ -356,6 +368,12 @@ size_t conv_fft_pool_handover_bytes(const ConvArgs& a, int ks_next) {      // T[
   if (!sizes_of((a.H + 1) / 2, (a.W + 1) / 2, ks_next, &n)) return 0;
   return (size_t)a.B * (n.NX / 2 + 1) * ((a.H + 1) / 2) * a.Cout * sizeof(cf);
 }
+// 2 x 2 tiles: a 5x5 layer whose output goes through the pool hand-over into a 5x5 layer, on the model's 120 x 180 map (cfft_tiles_supported)
+bool conv_fft_tiles_supported(const ConvArgs& a, int ks, int ks_next) {
+  Sizes s;
+  return fft_reg_on() && fft_tiles_on() && ks == 5 && ks_next == 5 && !a.circ && !a.win_map && a.B >= 1 && conv_fft_pool_fusable(a, ks, ks_next) &&
+         a.H % 4 == 0 && a.W % 4 == 0 && sizes_of(a.H / 2, a.W / 2, ks, &s) && cfft_tiles_supported(s.NY, s.NX, a);
+}
 // h16: bf16 handles on the one-part route with 16-bit row-transformed tensors -- the register kernel only (the model's geometry)
 bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool h16) {
   Sizes s;
@@ -371,8 +389,44 @@ bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMer
 // xs (optional): where the split activation spectra of the layer's input live instead of the scratch -- the training step keeps them for the
 // weight gradient (wgrad_fft.hip); xs_ready: they are there already (the data gradient after the weight gradient of the same layer): the
 // forward transforms are skipped.
+// The tiled layer (a0.tiles): rows forward from the map into the 4 B tiles, columns, GEMM and inverse columns of the tiles' transform, then the pool
+// hand-over that stitches the tiles back together.  sc->tmax: 4 B words (one per tile: the GEMM row), sc->tmax_next: B words (one per image).
+static hipError_t conv_fft_tiles_f32(const ConvArgs& a0, int ks, int np, int in_layout, void* work, const void* t_in, void* t_next, const FftMerge* merge,
+                                     hipEvent_t g0, hipEvent_t g1, hipStream_t st, void* xs, bool xs_ready, const Fp16Scale* scp, const FftNext* nx) {
+  Sizes s;
+  if (np != 4 || in_layout != 0 || t_in || merge || xs || xs_ready || !t_next || !nx || !nx->pool || nx->merge || !scp || !scp->tmax || !scp->winv || !scp->tmax_next ||
+      !conv_fft_tiles_supported(a0, ks, nx->ks_next) || !sizes_of(a0.H / 2, a0.W / 2, ks, &s))
+    return hipErrorInvalidValue;
+  ConvArgs a = a0;
+  a.CoutP = pad64(a.Cout);
+  const ConvArgs at = tile_view(a, s);
+  const Plan3 p = plan_of(at, s, np);
+  Fp16Scale sc = *scp;
+  sc.hf = (float)s.NY;      // the column pass's bound: NY real rows per tile
+  sc.nb = at.B;
+  char* wk = static_cast<char*>(work);
+  cf* T = reinterpret_cast<cf*>(wk);
+  void* Xs = wk + align256(p.t_bytes);
+  cf* Yf = reinterpret_cast<cf*>(wk + align256(p.t_bytes) + align256(p.xs_bytes));
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  const cf* twb = twiddle_table(dev);
+  if (!twb) return hipErrorOutOfMemory;
+  if (!cfft_rows_fwd_tile_reg(s.NY, s.NX, a, T, sc.tmax, st)) return hipErrorInvalidValue;
+  if (hipError_t ce = cfft_cols_fwd(s.NY, at, np, T, Xs, twb + tw_offset(s.NY), p.NXH, p.MT, sc, st); ce != hipSuccess) return ce;
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (g0 && hipEventRecord(g0, st) != hipSuccess) return hipErrorUnknown;
+  if (hipError_t e = cgemm_split(Xs, a.wp, Yf, np, p.F, at.B, a.Cin, a.Cout, p.ldy, st, 0.f); e != hipSuccess) return e;
+  if (g1 && hipEventRecord(g1, st) != hipSuccess) return hipErrorUnknown;
+  ConvArgs ai = at;      // the inverse column pass keeps the Ht valid rows of each tile
+  ai.H = a.H / 2;
+  if (!cfft_cols_inv_reg(s.NY, ai, Yf, T, p.NXH, p.ldy, (ks - 1) / 2, st, nullptr, 0.f)) return hipErrorInvalidValue;
+  if (!cfft_rows_inv_pool_tile_reg(s.NY, s.NX, a, T, static_cast<cf*>(t_next), 1.0f / (float)(s.NY * s.NX), sc, st)) return hipErrorInvalidValue;
+  return hipGetLastError();
+}
 hipError_t conv_fft_f32(const ConvArgs& a0, int ks, int np, int in_layout, int out_layout, void* work, const void* t_in, void* t_next, const FftMerge* merge,
                         hipEvent_t g0, hipEvent_t g1, hipStream_t st, void* xs, bool xs_ready, const Fp16Scale* scp, const FftNext* nx) {
+  if (a0.tiles) return conv_fft_tiles_f32(a0, ks, np, in_layout, work, t_in, t_next, merge, g0, g1, st, xs, xs_ready, scp, nx);
   Sizes s;
   if (!conv_fft_supported(a0, ks) || !sizes_of(a0.H, a0.W, ks, &s, a0.circ) || (out_layout == 2 && a0.Cout % 8) || (np != 2 && np != 4 && np != 5) || (np == 5 && a0.Cin % 32)) return hipErrorInvalidValue;
   if (a0.circ && (t_in || t_next || merge || in_layout != 0 || out_layout != 0)) return hipErrorInvalidValue;      // windows: fp32 NHWC in and out, nothing fused

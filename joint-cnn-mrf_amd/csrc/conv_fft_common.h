@@ -316,6 +316,10 @@ bool cfft_rows_fwd_reg(int NX, const ConvArgs& a, int layout, cf* T, float* tmax
 // 32 x 32 overlap-save windows read straight from the map they are cut from (a.win_map, fp32 NHWC; Cin % 128 == 0): false = no such kernel
 bool cfft_rows_fwd_win_reg(int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st);
 bool cfft_rows_fwd_win_reg_supported(int NX, int Cin);
+// 2 x 2 tiles of a 5x5 layer's map (ConvArgs::tiles, conv_fft_rows_reg.hip): NY x NX = the tiles' transform; a = the layer on the whole map
+bool cfft_tiles_supported(int NY, int NX, const ConvArgs& a);
+bool cfft_rows_fwd_tile_reg(int NY, int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st);
+bool cfft_rows_inv_pool_tile_reg(int NY, int NX, const ConvArgs& a, const cf* T, cf* Tn, float norm, const Fp16Scale& sc, hipStream_t st);
 bool cfft_rows_fwd_merge_reg(int NX, const ConvArgs& a, const FftMerge& m, int in_layout, cf* T, float* tmax, hipStream_t st, float* t16);
 bool cfft_cols_inv_reg(int NY, const ConvArgs& a, const cf* Yf, cf* T, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv = 0.f);
 void cfft_rows_inv_fwd(int NX, const ConvArgs& a, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);

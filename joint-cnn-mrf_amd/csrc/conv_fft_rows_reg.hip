@@ -7,6 +7,8 @@
 // channel pair): it loads its half spectrum (one 8- or 16-byte load per kx; consecutive lanes are consecutive channel pairs, so every load or
 // store instruction of a wave is one contiguous run), transforms it in registers with compile-time indices and literal twiddles, and stores its
 // row.  No LDS, no barrier, no index arithmetic; all loads of a thread are in flight before the first butterfly.
+#include <type_traits>
+
 #include "conv_fft_common.h"
 #include "fft_reg.h"
 #include "resize_tf1.h"
@@ -603,14 +605,9 @@ bool cfft_rows_fwd_merge_reg(int NX, const ConvArgs& a, const FftMerge& m, int i
 // parity h (the kernel's pad is even).  The forward transform wants u_h[j] = (z[j] + (-1)^h z[j + M]) w^(j h), j < M = NX / 2: pixels j and j + M have the same
 // parity, so the thread of parity j % 2 forms s = z[j] + z[j + M] and d = z[j] - z[j + M] for ITS 24 values of j, keeps the one its own transform needs
 // (thread 0: s, thread 1: d) and swaps the other with its neighbour (DPP) -- 24 complex numbers cross lanes, nothing goes through LDS.
-template <int NX, int PAD, int I, class Act>
-__device__ __forceinline__ void fused_rows_mid(const cf (&x)[NX / 2], cf (&uu)[NX / 2], bool odd, int h, int W, Act&& act) {
-  constexpr int M = NX / 2, R1 = RPlan<M>::R1, R2 = RPlan<M>::R2, Q = M / 2;
-  // this thread's pixels n = 2 i + h, i < M:  the inverse's output X[2 (i + PAD / 2) + h], activated; zero behind the map (the next layer's padding)
-  constexpr int ma = I + PAD / 2, mb = I + Q + PAD / 2;      // sample indices of pixels 2 I + h and 2 (I + Q) + h
-  cf a = cf{0.f, 0.f}, bq = cf{0.f, 0.f};
-  if constexpr (ma < M) { if (2 * I + h < W) a = act(x[R2 * (ma % R1) + ma / R1]); }
-  if constexpr (mb < M) { if (2 * (I + Q) + h < W) bq = act(x[R2 * (mb % R1) + mb / R1]); }
+// u_h[2 I], u_h[2 I + 1] of the forward transform from this thread's pixels a = z[2 I + h] and bq = z[2 I + h + M]
+template <int NX, int I>
+__device__ __forceinline__ void fwd_rows_mid_pair(const cf a, const cf bq, cf (&uu)[NX / 2], bool odd) {
   const cf sm = a + bq, df = a - bq;                         // j = 2 I + h:  z[j] + z[j + M],  z[j] - z[j + M]
   const cf keep = cf{odd ? df.x : sm.x, odd ? df.y : sm.y}, send = cf{odd ? sm.x : df.x, odd ? sm.y : df.y};
   const cf recv = cf{__uint_as_float((unsigned)__builtin_amdgcn_mov_dpp((int)__float_as_uint(send.x), 0xB1, 0xF, 0xF, true)),
@@ -627,6 +624,16 @@ __device__ __forceinline__ void fused_rows_mid(const cf (&x)[NX / 2], cf (&uu)[N
   }
   uu[2 * I] = e;
   uu[2 * I + 1] = o;
+}
+template <int NX, int PAD, int I, class Act>
+__device__ __forceinline__ void fused_rows_mid(const cf (&x)[NX / 2], cf (&uu)[NX / 2], bool odd, int h, int W, Act&& act) {
+  constexpr int M = NX / 2, R1 = RPlan<M>::R1, R2 = RPlan<M>::R2, Q = M / 2;
+  // this thread's pixels n = 2 i + h, i < M:  the inverse's output X[2 (i + PAD / 2) + h], activated; zero behind the map (the next layer's padding)
+  constexpr int ma = I + PAD / 2, mb = I + Q + PAD / 2;      // sample indices of pixels 2 I + h and 2 (I + Q) + h
+  cf a = cf{0.f, 0.f}, bq = cf{0.f, 0.f};
+  if constexpr (ma < M) { if (2 * I + h < W) a = act(x[R2 * (ma % R1) + ma / R1]); }
+  if constexpr (mb < M) { if (2 * (I + Q) + h < W) bq = act(x[R2 * (mb % R1) + mb / R1]); }
+  fwd_rows_mid_pair<NX, I>(a, bq, uu, odd);
   if constexpr (I + 1 < Q) fused_rows_mid<NX, PAD, I + 1>(x, uu, odd, h, W, act);
 }
 template <int NX, int PAD>
@@ -971,6 +978,224 @@ bool cfft_rows_inv_reg(int NX, const ConvArgs& a, int layout, const cf* T, int p
   if (NX == 50) return launch_rows_inv_reg<50>(a, layout, T, pad, norm, sc, st);      // the half- and quarter-resolution branches (36 x 50, 20 x 28 transforms)
   if (NX == 28) return launch_rows_inv_reg<28>(a, layout, T, pad, norm, sc, st);
   return false;
+}
+
+// ---- a 5x5 layer on a map of 2 x 2 TILES (conv_fft.hip, ConvArgs::tiles): the Hm x Wm map is cut into tiles of Ht x Wt = Hm / 2 x Wm / 2, and tile
+// b' = (b 2 + ty) 2 + tx is a circular NY x NX transform whose zero padding is replaced by the neighbouring pixels (the halo of the 5x5 filter):
+// transform row t holds map row ty Ht + t for t < Ht + 2 and ty Ht + t - NY for t >= NY - 2 (the two rows above the tile), zero in between and
+// outside the map; the same along x.  A SAME output pixel of the tile reads transform rows y - 2 .. y + 2 mod NY: exactly those.  The filter spectra,
+// the GEMM and the inverse column pass are those of an Ht x Wt map of 4 B images; the forward row pass below gathers the tiles from the map, and
+// the pool hand-over below stitches the tiles' outputs back together.
+
+// ---- rows, forward, of the tiles of an NHWC fp32 map -> T[kx][c/16][b'][t][16] with NY rows per tile (all of them real: rows Ht .. NY - 1 carry
+// the halo).  Two threads per channel pair as in rows_fwd_reg_kernel: thread h loads pixels [h M, h M + M) of the transform row and swaps them with
+// the other thread of the pair (v_permlane32_swap); a pixel outside the map or in the unread gap is a buffer load past the descriptor's range: zero.
+template <int NX, int J>
+__device__ __forceinline__ void fwd_rows_in2_f32(cf (&u)[NX / 2], const cf (&raw)[NX / 2], float sg, bool odd) {
+  constexpr int M = NX / 2;
+  const cf a = raw[J], o = cf{__uint_as_float(pair_word(__float_as_uint(a.x), odd)), __uint_as_float(pair_word(__float_as_uint(a.y), odd))};
+  cf v = cf{fmaf(sg, a.x, o.x), fmaf(sg, a.y, o.y)};      // h = 0: z[J] + z[J + M];  h = 1: z[J] - z[J + M] (see fwd_rows_in2)
+  if constexpr (J > 0) {
+    const float wr = odd ? Tw<-J, NX>::re : 1.f, wi = odd ? Tw<-J, NX>::im : 0.f;
+    v = cf{fmaf(-v.y, wi, v.x * wr), fmaf(v.x, wi, v.y * wr)};
+  }
+  u[J] = v;
+  if constexpr (J + 1 < M) fwd_rows_in2_f32<NX, J + 1>(u, raw, sg, odd);
+}
+template <int NX>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void rows_fwd_tile_reg_kernel(const float* __restrict__ map, float4* __restrict__ T, int nrows, int NY,
+                                                                                                   int Hm, int Wm, int Ht, int Wt, int C, float* __restrict__ tmax) {
+  constexpr int M = NX / 2;
+  const int CP = C >> 1;
+  int h, p;
+  size_t by;
+  pair_coords(CP, h, p, by);
+  if (by >= (size_t)nrows) return;
+  const int bt = (int)(by / NY), t = (int)(by % NY);      // (tile, transform row): scalars
+  const int tx = bt & 1, ty = (bt >> 1) & 1, b = bt >> 2;
+  const int ym = t < Ht + 2 ? ty * Ht + t : (t >= NY - 2 ? ty * Ht + t - NY : -1);
+  const bool row_in = ym >= 0 && ym < Hm;
+  const auto d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(map) + ((size_t)b * Hm + (row_in ? ym : 0)) * Wm * C, 0, row_in ? Wm * C * 4 : 0, 0x00020000);
+  cf raw[M];
+  typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const int n = h * M + j;
+    const int xm = n < Wt + 2 ? tx * Wt + n : (n >= NX - 2 ? tx * Wt + n - NX : -1);
+    const int off = xm >= 0 && xm < Wm ? xm * C * 4 : Wm * C * 4;      // (past the range: the load returns zeros)
+    raw[j] = __builtin_bit_cast(cf, __builtin_amdgcn_raw_buffer_load_b64(d, p * 8 + off, 0, 0));
+  }
+  const bool odd = h != 0;
+  cf u[M];
+  fwd_rows_in2_f32<NX, 0>(u, raw, odd ? -1.f : 1.f, odd);
+  step1<M, -1>(u);
+  step2_inplace<M, -1, 0>(u);
+  const int cblk = p >> 5, v = p & 31, B4 = nrows / NY;
+  float4* dst = T + ((((size_t)cblk * 4 + (v >> 3)) * B4 + bt) * NY + t) * 8 + (v & 7);      // t_fwd_index(k = 0); per kx: + (C / 16) B' NY 8
+  const size_t kstride = (size_t)(C >> 4) * B4 * NY * 8;
+  float m = 0.f;
+  fwd_rows_visit<NX, 0>(u, odd, [&](int mi, const float4& o) __attribute__((always_inline)) {
+    const int k = 2 * mi + h;
+    if (k <= M) {
+      dst[(size_t)k * kstride] = o;
+      m = fmaxf(fmaxf(m, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    }
+  });
+  if (tmax) {      // the TILE's word of the spectra's scale: a tile is one row of the channel GEMM
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(reinterpret_cast<unsigned*>(tmax + bt), __float_as_uint(m));
+  }
+}
+
+// ---- conv2 -> 2x2/2 max pool -> conv3 from the tiles (the contract of rows_inv_pool_fwd_kernel<192, 96>: conv3's T[kx][c/16][b][r][16] of the pooled
+// Ht x Wt map and its per-IMAGE word of max |T|).  A wave = 32 channel pairs of ONE pooled row r; two threads per pair, adjacent lanes (the inverse
+// layout).  For each of the two x-tiles: the inverse rows of conv2 rows 2 r and 2 r + 1 (in tile ty = 2 r / Ht; Ht is even), each followed by the
+// epilogue under the tile's own scale and the horizontal maximum of pixels (2 i, 2 i + 1) -- one from each thread of the pair: a DPP swap --, then the
+// vertical maximum of the two rows.  Pooled pixel q = tx Wt / 2 + i; thread h keeps the pooled pixels of parity h, which is what the forward transform's
+// exchange (fwd_rows_mid_pair) starts from.  While the second tile runs, the first tile's pooled pixels wait in a per-wave LDS slice (each lane reads back
+// what it wrote: no barrier) -- in registers next to the second tile's transform they spilled (640 bytes per lane).
+// one output of the inverse row: pixel 2 I + h of the tile, activated, then the horizontal and (second row) vertical maximum into its pooled slot
+template <int NX, int TX, int I, int WT, class Act>
+__device__ __forceinline__ void pool_tile_px(const cf x, cf (&zp)[NX / 2], bool odd, bool first, Act&& act) {
+  const cf v = act(x);
+  const cf w = cf{__uint_as_float((unsigned)__builtin_amdgcn_mov_dpp((int)__float_as_uint(v.x), 0xB1, 0xF, 0xF, true)),
+                  __uint_as_float((unsigned)__builtin_amdgcn_mov_dpp((int)__float_as_uint(v.y), 0xB1, 0xF, 0xF, true))};
+  const cf pm = cf{fmaxf(v.x, w.x), fmaxf(v.y, w.y)};      // max of pixels 2 I, 2 I + 1 (the same in both threads)
+  constexpr int q = TX * (WT / 2) + I;                     // pooled pixel: its slot q / 2 in the thread of parity q % 2
+  if (((q & 1) != 0) == odd) zp[q >> 1] = first ? pm : cf{fmaxf(zp[q >> 1].x, pm.x), fmaxf(zp[q >> 1].y, pm.y)};
+}
+template <int NX, int TX, int K1, int K2, int WT, class Act>
+__device__ __forceinline__ void pool_tile_outs(const cf (&o)[RPlan<NX / 2>::R2], cf (&zp)[NX / 2], bool odd, bool first, Act&& act) {
+  constexpr int I = K1 + RPlan<NX / 2>::R1 * K2 - 1;      // X[2 m + h], m = K1 + R1 K2, is pixel 2 (m - 1) + h of the tile (pad 2)
+  if constexpr (I >= 0 && I < WT / 2) pool_tile_px<NX, TX, I, WT>(o[K2], zp, odd, first, act);
+  if constexpr (K2 + 1 < RPlan<NX / 2>::R2) pool_tile_outs<NX, TX, K1, K2 + 1, WT>(o, zp, odd, first, act);
+}
+// step 2 of the inverse row one output row at a time, each consumed at once (as inv_rows_out2: all of them at once spill)
+template <int NX, int TX, int K1, int WT, class Act>
+__device__ __forceinline__ void pool_tile_row(const cf (&u)[NX / 2], cf (&zp)[NX / 2], bool odd, bool first, Act&& act) {
+  constexpr int M = NX / 2;
+  cf o[RPlan<M>::R2];
+  step2_row<M, 1, K1>(u, o);
+  pool_tile_outs<NX, TX, K1, 0, WT>(o, zp, odd, first, act);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (K1 + 1 < RPlan<M>::R1) pool_tile_row<NX, TX, K1 + 1, WT>(u, zp, odd, first, act);
+}
+template <int NX, int I>
+__device__ __forceinline__ void pool_rows_mid(const cf (&zp)[NX / 2], cf (&uu)[NX / 2], bool odd) {
+  fwd_rows_mid_pair<NX, I>(zp[I], zp[I + NX / 4], uu, odd);      // pixels 2 I + h and 2 I + h + M
+  if constexpr (I + 1 < NX / 4) pool_rows_mid<NX, I + 1>(zp, uu, odd);
+}
+template <int NX, int WT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void rows_inv_pool_tile_reg_kernel(const float4* __restrict__ T, float4* __restrict__ Tn, const float* __restrict__ bias,
+                                                                                                        const float* __restrict__ scale, const float* __restrict__ shift, int relu_bn,
+                                                                                                        int nrows, int B, int Ht, int C, float norm0, Fp16Scale sc) {
+  constexpr int NXH = NX / 2 + 1, M = NX / 2;
+  static_assert(WT % 2 == 0 && WT + 4 <= NX, "even tile width with its halo inside the transform");
+  const int CP = C >> 1;
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int h = (int)(g & 1), lane = threadIdx.x & 63;
+  const int p = (int)((g >> 1) % CP);
+  const size_t by = (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)((g >> 1) / CP));      // pooled row b Ht + r: the same for the 64 lanes (C % 64 == 0)
+  if (by >= (size_t)nrows) return;
+  const int b = (int)(by / Ht), r = (int)(by % Ht), c = 2 * p;
+  constexpr int KS = (WT / 2 - 1) / 2;      // slots 0 .. KS - 1 hold pooled pixels of the first tile only, in both threads of a pair
+  __shared__ cf stash[4][KS][64];
+  const int ty = (2 * r) / Ht, yt = 2 * r - ty * Ht;      // conv2 rows 2 r, 2 r + 1 = rows yt, yt + 1 of tile row ty
+  const bool odd = h != 0;
+  const float b0v = bias[c], b1v = bias[c + 1];
+  float s0 = 1.f, s1 = 1.f, h0 = 0.f, h1 = 0.f;
+  if (relu_bn) { s0 = scale[c]; h0 = shift[c]; s1 = scale[c + 1]; h1 = shift[c + 1]; }
+  float tcommon = 0.f;
+  if (sc.tmax && sc.common) {      // one scale for the tensor: the largest of its nb (tile) words
+    for (int i = lane; i < sc.nb; i += 64) tcommon = fmaxf(tcommon, sc.tmax[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tcommon = fmaxf(tcommon, __shfl_xor(tcommon, o));
+  }
+  cf zp[M];
+#pragma unroll
+  for (int k = 0; k < M; ++k) zp[k] = cf{0.f, 0.f};      // (pooled pixels Wt .. NX - 1: the next layer's zero padding)
+  auto tile = [&](auto txc) __attribute__((always_inline)) {
+    constexpr int tx = decltype(txc)::value;
+    const int bt = (b * 2 + ty) * 2 + tx;
+    const float norm = sc.tmax ? norm0 * sc.winv[0] * fp16_unscale(sc.common ? tcommon : sc.tmax[bt], sc.hf) : norm0;      // the tile's scale
+    auto act = [&](cf z) __attribute__((always_inline)) {
+      float v0 = fmaf(z.x, norm, b0v), v1 = fmaf(z.y, norm, b1v);
+      if (relu_bn) { v0 = fmaf(fmaxf(v0, 0.f), s0, h0); v1 = fmaf(fmaxf(v1, 0.f), s1, h1); }
+      return cf{v0, v1};
+    };
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      __builtin_amdgcn_sched_barrier(0);      // one row at a time: the next row's loads do not go out over this one's transform
+      cf u[M];
+      // buffer loads: the row is the descriptor, the entry a scalar offset, the channel pair the only vector offset (with 64-bit addresses per entry
+      // the compiler keeps the 49 addresses for all four rows and spills them)
+      const auto d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(T) + (((size_t)bt * Ht + yt + rr) * NXH * C) / 2, 0, NXH * C * 8, 0x00020000);
+      const int vo = p * 16, ko = CP * 16;
+      auto load = [&](int k) __attribute__((always_inline)) {
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        const f4 q = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(d, vo, k * ko, 0));
+        return make_float4(q[0], q[1], q[2], q[3]);
+      };
+      // the row's own copy of the parity: the lane-selected twiddles of the four rows are the same values, and hoisted out of the rows they
+      // occupy ~100 registers for the whole kernel (spilled)
+      int hr = h;
+      asm volatile("" : "+v"(hr));
+      const bool odd_r = hr != 0;
+      inv_rows_load2<NX, false, 0>(u, odd_r ? -1.f : 1.f, odd_r, load);
+      step1<M, 1>(u);
+      pool_tile_row<NX, tx, 0, WT>(u, zp, odd, rr == 0, act);
+    }
+  };
+  cf(*const slice)[64] = stash[threadIdx.x >> 6];
+  tile(std::integral_constant<int, 0>{});
+#pragma unroll
+  for (int k = 0; k < KS; ++k) slice[k][lane] = zp[k];
+  tile(std::integral_constant<int, 1>{});
+#pragma unroll
+  for (int k = 0; k < KS; ++k) zp[k] = slice[k][lane];
+  cf uu[M];
+  pool_rows_mid<NX, 0>(zp, uu, odd);
+  step1<M, -1>(uu);
+  step2_inplace<M, -1, 0>(uu);
+  const int cblk = p >> 5, v = p & 31;
+  float4* dst = Tn + ((((size_t)cblk * 4 + (v >> 3)) * B + b) * Ht + r) * 8 + (v & 7);      // t_fwd_index(k = 0); per kx: + (C / 16) B Ht 8
+  const size_t kstride = (size_t)(C >> 4) * B * Ht * 8;
+  float m = 0.f;
+  fwd_rows_visit<NX, 0>(uu, odd, [&](int mi, const float4& o) __attribute__((always_inline)) {
+    const int k = 2 * mi + h;
+    if (k <= M) {
+      dst[(size_t)k * kstride] = o;
+      m = fmaxf(fmaxf(m, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    }
+  });
+  if (sc.tmax_next) {      // the next layer's per-IMAGE word
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (lane == 0 && m > 0.f) atomicMax(reinterpret_cast<unsigned*>(sc.tmax_next + b), __float_as_uint(m));
+  }
+}
+// a: the layer on the whole Hm x Wm map (a.B images); NY x NX: the tiles' transform.  Model geometry only: 90-column tiles, 96-point rows.
+bool cfft_tiles_supported(int NY, int NX, const ConvArgs& a) {
+  return NX == 96 && NY == 64 && a.W == 180 && a.H % 4 == 0 && a.H / 2 + 4 <= NY && a.Cin % 64 == 0 && a.Cout % 64 == 0 &&
+         (size_t)a.W * a.Cin * 4 < (size_t)1 << 31;
+}
+bool cfft_rows_fwd_tile_reg(int NY, int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st) {
+  if (!cfft_tiles_supported(NY, NX, a)) return false;
+  const int nrows = 4 * a.B * NY;
+  const size_t threads = (size_t)nrows * a.Cin;      // two threads per channel pair
+  hipLaunchKernelGGL(rows_fwd_tile_reg_kernel<96>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(a.x), reinterpret_cast<float4*>(T), nrows, NY,
+                     a.H, a.W, a.H / 2, a.W / 2, a.Cin, tmax);
+  return true;
+}
+// T: T'[b'][y][kx][c] of the 4 B tiles (Ht valid rows each, the inverse column pass); Tn: the next layer's T of the pooled Ht x Wt map of B images
+bool cfft_rows_inv_pool_tile_reg(int NY, int NX, const ConvArgs& a, const cf* T, cf* Tn, float norm, const Fp16Scale& sc, hipStream_t st) {
+  if (!cfft_tiles_supported(NY, NX, a)) return false;
+  const int Ht = a.H / 2, nrows = a.B * Ht;
+  const size_t threads = (size_t)nrows * a.Cout;
+  hipLaunchKernelGGL((rows_inv_pool_tile_reg_kernel<96, 90>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(T), reinterpret_cast<float4*>(Tn),
+                     a.bias, a.scale, a.shift, a.relu_bn, nrows, a.B, Ht, a.Cout, norm, sc);
+  return true;
 }
 
 }  // namespace cfft

@@ -109,6 +109,7 @@ struct jcm_ctx {
   bool fft_xs_ready = false;         // ... they are there already (data gradient after the weight gradient of the same layer): skip the forward transforms
   void* sm_scratch = nullptr;   // sm_fused.hip: partial sums + flags of sm_inv_finish_kernel's cuts (sm_fused_scratch_bytes(), zeroed once)
   unsigned sm_epoch = 0;        // ... the launch counter its flags carry
+  int fft_tiles = 1;            // fp32 handles, the pool hand-over of conv2_fullres: 2 x 2 tiles of the 120 x 180 map in the 60 x 90 maps' transform (ConvArgs::tiles)
   int fft_fuse = 3;             // fp32 handles, jcm_pd_forward: bit 0 = conv2 -> max pool -> conv3, bit 1 = conv4_fullres -> branch merge -> conv5 handed over in row-transformed form (conv_fft_rows_fused.hip)
   int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel
   int conv_hpool = 0;           // transient: the next direct bf16 convolution launch takes the half pool

@@ -294,18 +294,23 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   a.rows_mfma = c->fft_rows_mfma;
   const size_t mark = c->arena_off;
   const int np = fft_np(c);      // operand form of the channel GEMM (cgemm_split.hip)
+  // fp32 handles, the pool hand-over conv2 -> pool -> conv3 on the model's 120 x 180 map: the layer runs as 2 x 2 tiles in the 64 x 96 transform of the
+  // 60 x 90 maps (ConvArgs::tiles, conv_fft_rows_reg.hip) -- a quarter of the filter spectra, and the register row kernels
+  a.tiles = c->fft_tiles && c->fft_next_pool && !c->fft_t_in && !c->fft_xs && !c->fft_merge && !c->fft_win_map && !circ && in_layout == 0 &&
+            np == 4 && conv_fft_tiles_supported(a, L->ks, c->fft_next_ks) ? 1 : 0;
+  const int wH = a.tiles ? H / 2 : H, wW = a.tiles ? W / 2 : W;      // the map size the filter spectra are for
   void* work = arena_alloc<char>(c, conv_fft_workspace_bytes(a, L->ks, np));
   c->arena_off = mark;                                   // scratch of this layer only: later layers run behind it on the stream
   if (c->dry) { c->fft_t_in = nullptr; c->fft_t_next = nullptr; c->fft_merge = nullptr; c->fft_xs = nullptr; c->fft_xs_ready = false; c->fft_tmax_in = nullptr; c->fft_next_pool = 0; c->fft_next_ks = 0; c->fft_next_merge = nullptr; c->fft_t_in_16 = false; c->fft_win_map = nullptr; c->fft_win_scatter = false; return JCM_OK; }
   // Filter spectra are cached per (layer, map size).  The cache is bounded (JCM_FFT_CACHE_GB, default 64): a caller that walks many
   // image sizes (7.7 GB per size for conv5) makes it drop every spectrum that is not this layer's before it grows past the bound.
-  const std::string key = scope + (circ ? "@win" : "@") + std::to_string(H) + "x" + std::to_string(W);
+  const std::string key = scope + (circ ? "@win" : "@") + std::to_string(wH) + "x" + std::to_string(wW);
   // (A training handle keeps the spectra of BOTH geometries of a layer -- overlap-save windows for steps of <= 32 images, the whole map for evaluation
   // forwards and larger batches -- so that a loop that alternates training steps and evaluation does not re-pack gigabytes and stall the stream at
   // every flip (round 5 dropped the other geometry here); the cache bound below is what limits the footprint.)
   if (!c->fft_w.count(key)) {
     static const size_t cap = [] { const char* e = std::getenv("JCM_FFT_CACHE_GB"); return (size_t)(e ? std::atoi(e) : 64) << 30; }();
-    const size_t need = conv_fft_weight_bytes(H, W, L->ks, L->cin, L->cout, np, circ);
+    const size_t need = conv_fft_weight_bytes(wH, wW, L->ks, L->cin, L->cout, np, circ);
     size_t held = 0;
     for (auto& kv : c->fft_w) held += kv.second.bytes;
     if (held + need > cap && !c->fft_w.empty()) {
@@ -316,7 +321,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   }
   jcm_ctx::FftW& fw = c->fft_w[key];
   if (!fw.p) {
-    const size_t wb = (conv_fft_weight_bytes(H, W, L->ks, L->cin, L->cout, np, circ) + 255) & ~size_t(255);
+    const size_t wb = (conv_fft_weight_bytes(wH, wW, L->ks, L->cin, L->cout, np, circ) + 255) & ~size_t(255);
     fw.bytes = wb + 256;      // + the two words of the filter spectra's scale (np = 4)
     if (hipMalloc(&fw.p, fw.bytes) == hipSuccess) {
       fw.wscale = reinterpret_cast<float*>(static_cast<char*>(fw.p) + wb);
@@ -334,7 +339,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
       auto it = c->fft_w.find(key.substr(6));
       if (it != c->fft_w.end() && it->second.valid && it->second.wscale) bound_from = it->second.wscale;
     }
-    HIP_TRY(conv_fft_pack_weights(L->w_raw, fw.p, H, W, L->ks, L->cin, L->cout, np, c->precision == JCM_PRECISION_BF16, c->stream, fw.wscale, circ, bound_from));
+    HIP_TRY(conv_fft_pack_weights(L->w_raw, fw.p, wH, wW, L->ks, L->cin, L->cout, np, c->precision == JCM_PRECISION_BF16, c->stream, fw.wscale, circ, bound_from));
     fw.valid = true;
   }
   a.wp = fw.p;
@@ -364,7 +369,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
     // the word of this layer's input: handed over with t_in / ready spectra, or a fresh one for this layer's own row pass
     sc.tmax = c->fft_tmax_in;
     if ((t_in || xs_ready) && !sc.tmax) return fail(JCM_ERR_STATE, "conv_fft '" + scope + "': a handed-over tensor without its scale word");
-    if (!sc.tmax) JCM_TRY(fft_new_words(c, B, &sc.tmax));
+    if (!sc.tmax) JCM_TRY(fft_new_words(c, a.tiles ? 4 * B : B, &sc.tmax));      // (tiles: one word per tile, the row of the channel GEMM)
     if (t_next) JCM_TRY(fft_new_words(c, B, &sc.tmax_next));
     sc.winv = fw.wscale + 1;
     sc.common = c->train ? 1 : 0;      // a handle with training state: one scale per tensor (the weight gradient sums over the images)
@@ -857,6 +862,10 @@ int jcm_set_option(jcm_handle h, const char* key, int64_t value) {
   if (k == "fft_fuse") {   // allowed at any time (fp32 handles): bit 0 = conv2 -> pool -> conv3, bit 1 = conv4_fullres -> merge -> conv5 as fused hand-overs
     if (value < 0 || value > 3) return fail(JCM_ERR_ARG, "fft_fuse must be 0..3 (bit 0: pool hand-over, bit 1: merge hand-over)");
     h->fft_fuse = (int)value;
+    return JCM_OK;
+  }
+  if (k == "fft_tiles") {   // allowed at any time (fp32 handles): conv2_fullres -> pool -> conv3 as 2 x 2 tiles of the 120 x 180 map (fft_fuse bit 0)
+    h->fft_tiles = value != 0;
     return JCM_OK;
   }
   if (k == "bf16_hpool") {   // allowed at any time (bf16 handles)

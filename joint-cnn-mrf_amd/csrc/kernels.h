@@ -60,6 +60,9 @@ struct ConvArgs {
   // ... and the valid regions need not either: wout_TY > 0 -> `out` is the [win_B, wout_H, wout_W, Cout] MAP and the inverse row pass stores valid pixel (y, x)
   // of window (b, ty, tx) at map pixel (ty (H - 8) + y, tx (W - 8) + x) where that lies inside the map (conv_fft_win_scatter_supported())
   int wout_H = 0, wout_W = 0, wout_TY = 0, wout_TX = 0;
+  // conv_fft only, fp32 handles, a 5x5 layer followed by the 2x2 max pool (FftNext::pool): run the H x W map as 2 x 2 TILES of H / 2 x W / 2, each with its
+  // 2-pixel halo in the circular transform of an H / 2 x W / 2 map (conv_fft_tiles_supported(); the filter spectra are those of that map size)
+  int tiles = 0;
   // conv_fft, bf16 handles with 16-bit row-transformed tensors: the 96-point inverse row pass with planar bf16 output (conv5 of the model) as a matrix product
   // on the matrix cores (conv_fft_rows_mfma.hip).  1 = on where the kernel exists, 0 = the register kernel.
   int rows_mfma = 0;
@@ -142,6 +145,8 @@ hipError_t conv_fft_f32(const ConvArgs& a, int ks, int np, int in_layout, int ou
 bool conv_fft_win_gather_supported(int win, int Cin);
 bool conv_fft_win_scatter_supported(int win, int Cout);    // ... and its inverse row pass store the valid regions straight into the map?      // can the forward row pass of `win` x `win` overlap-save windows read them straight from the map?
 bool conv_fft_pool_fusable(const ConvArgs& a, int ks, int ks_next);
+// ... as 2 x 2 tiles of the map (ConvArgs::tiles; JCM_FFT_TILES=0 in the environment turns the route off), and the map size of their filter spectra
+bool conv_fft_tiles_supported(const ConvArgs& a, int ks, int ks_next);
 size_t conv_fft_pool_handover_bytes(const ConvArgs& a, int ks_next);
 bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool h16 = false);      // h16: bf16 handles (16-bit T / T', bf16 branches)
 size_t conv_fft_xs_bytes(const ConvArgs& a, int ks, int np);

@@ -1,0 +1,96 @@
+"""conv2_fullres -> max pool -> conv3 as 2x2 tiles of the 120x180 map (option "fft_tiles", ConvArgs::tiles in conv_fft.hip).
+
+Each 60x90 tile plus a 2-pixel halo fills the 64x96 circular transform of the 60x90 maps; the tiled route and the whole-map route compute the
+same SAME convolution through different transforms and per-tile (instead of per-image) fp16 scales, so they agree to rounding, and both hold
+the float64 goldens.  The logits map is 60x90: conv2's tile seams (map row 60, column 90) sit under logits row 30 and column 45."""
+import numpy as np
+import pytest
+import torch
+
+from golden_util import flic_priors, full_inputs, load, seeds
+from joint_cnn_mrf_amd import synth
+from oracle import jcm_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+SEAM_ROWS = slice(28, 33)
+SEAM_COLS = slice(43, 48)
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _logits(x, p, tiles, **kw):
+    from joint_cnn_mrf_amd.engine import Engine
+    eng = Engine(device=0, fft_tiles=tiles, **kw).load_params(p)
+    try:
+        return eng.model(dev(x)).cpu().numpy()
+    finally:
+        eng.close()
+
+
+def test_tiles_vs_whole_map_and_golden():
+    from joint_cnn_mrf_amd.engine import Engine
+    x, torso, p = full_inputs()
+    p.update(synth.make_sm_params(flic_priors(), kind='trained', seed=seeds()['sm']))
+    ref = load('full_pd_logits')
+    scale = max(1.0, float(np.abs(ref).max()))
+    got = {}
+    for tiles in (1, 0):
+        eng = Engine(device=0, fft_tiles=tiles).load_params(p)
+        got[tiles] = eng.model(dev(x)).cpu().numpy()
+        r = eng.forward(dev(x), dev(torso), use_sm=True)
+        eng.close()
+        err = np.abs(got[tiles] - ref)
+        assert err.max() <= 2e-4 * scale, (tiles, float(err.max()))
+        # the tile seams and the map border, where the halo is other tiles' pixels or the SAME padding
+        assert err[:, SEAM_ROWS].max() <= 2e-4 * scale and err[:, :, SEAM_COLS].max() <= 2e-4 * scale, tiles
+        assert max(err[:, :2].max(), err[:, -2:].max(), err[:, :, :2].max(), err[:, :, -2:].max()) <= 2e-4 * scale, tiles
+        np.testing.assert_array_equal(r['pd_coords'].cpu().numpy(), load('full_pd_coords'))
+        np.testing.assert_array_equal(r['sm_coords'].cpu().numpy(), load('full_sm_coords_trained'))
+    d = np.abs(got[1] - got[0])
+    assert d.max() <= 2e-5 * scale, float(d.max())
+    assert not np.array_equal(got[1], got[0])      # the route is taken at the model's geometry (other transforms, other rounding)
+
+
+def test_conv2_tiles_seams_vs_float64_oracle():
+    """Against the float64 oracle directly, on images whose content is concentrated on the seams (a bright cross through conv2's tile edges)."""
+    x, _, p = full_inputs()
+    x = x.copy()
+    x[:, 232:248, :, :] = 1.0      # image rows 232..247 -> conv2 map rows 58..61
+    x[:, :, 352:372, :] = 1.0      # image columns 352..371 -> conv2 map columns 88..92
+    ref = O.model(x, p)
+    scale = max(1.0, float(np.abs(ref).max()))
+    got = _logits(x, p, 1)
+    err = np.abs(got - ref)
+    assert err.max() <= 2e-4 * scale, float(err.max())
+    assert err[:, SEAM_ROWS].max() <= 2e-4 * scale and err[:, :, SEAM_COLS].max() <= 2e-4 * scale
+
+
+def test_tiles_per_tile_scale_and_batch_independence():
+    """A tile is one row of the channel GEMM with its own power-of-two scale: an image's result does not depend on its batch, not even next to an
+    image 1e4 times brighter, and a ragged batch of 5 (20 tiles) gives every image the bits it gets alone."""
+    _, _, p = full_inputs()
+    x = synth.make_images(5, seed=77)
+    xb = x.copy()
+    xb[2] *= 1e4
+    alone = _logits(x[:1], p, 1)
+    batch5 = _logits(x, p, 1)
+    bright = _logits(xb, p, 1)
+    assert np.array_equal(batch5[:1], alone)
+    assert np.array_equal(bright[[0, 1, 3, 4]], batch5[[0, 1, 3, 4]])
+    assert np.isfinite(bright).all()
+    whole = _logits(xb, p, 0)
+    for i in range(5):
+        s = max(1.0, float(np.abs(whole[i]).max()))
+        assert np.abs(bright[i] - whole[i]).max() <= 2e-5 * s, i
+
+
+@pytest.mark.parametrize('hw', [(240, 360), (256, 384)])
+def test_other_geometries_keep_the_whole_map_route(hw):
+    """Only the 120x180 map splits into tiles the register kernels take: elsewhere the option changes nothing, bit for bit."""
+    H, W = hw
+    p = synth.make_pd_params(debug=True, bn='trained', conv6_gain=8.0)
+    x = synth.make_images(2, seed=31, height=H, width=W)
+    assert np.array_equal(_logits(x, p, 1), _logits(x, p, 0))
