@@ -225,6 +225,21 @@ int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float
 int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
                       int hh, int hw, float* x_out, float* y_out);
 
+/* -- batches from a device-resident data set ----------------------------------------
+ * x_all [N,H,W,3], y_all [N,h,w,K+1]: device fp32, the whole data set; idx: HOST int32 [B], each in [0, N), repeats allowed.
+ * jcm_gather_batch: x_out[b] = x_all[idx[b]], y_out[b] = y_all[idx[b]], bit for bit (x_out [B,H,W,3], y_out [B,h,w,K+1]).
+ * jcm_augment_train_indexed: jcm_augment_train with image idx[b] of the data set as the source of output image b and
+ *   params[b] as its parameters; the results equal jcm_gather_batch followed by jcm_augment_train bit for bit.
+ * Every index is checked on the host before anything is launched: an index outside [0, N) is JCM_ERR_ARG with its position in
+ * the message, as are null pointers, bad sizes and outputs that overlap the data set, params or each other; nothing is written
+ * then.  idx is read before the call returns (the indices travel in the kernel arguments).  Both enqueue on the handle's
+ * stream and do not synchronise.  H, W, h, w >= 1 for the gather, >= 2 for the augmentation (which also needs n_joints == 9
+ * and uses the workspace arena, like jcm_augment_train). */
+int jcm_gather_batch(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W,
+                     int hh, int hw, float* x_out, float* y_out);
+int jcm_augment_train_indexed(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params,
+                              int B, int H, int W, int hh, int hw, float* x_out, float* y_out);
+
 /* -- TensorBoard summaries (tensorboard.py) -------------------------------------------------
  * jcm_tensor_stats: per segment (offset, count) of a flat device fp32 buffer -- or, with data == NULL, of the handle's stored
  *   trainable parameters in the layout of jcm_train_param_info (read in place; a segment must lie inside one tensor) -- the

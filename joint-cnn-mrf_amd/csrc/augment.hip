@@ -17,6 +17,16 @@ constexpr int kAugHmThreads = 512;
 constexpr float kCropSize = 0.95f;      // augmentation.py:40
 __constant__ int kHmFlipPerm[10] = {3, 4, 5, 0, 1, 2, 7, 6, 8, 9};     // augmentation.py:20
 
+// where image b of the batch comes from: image b of the array itself, or image idx[b] of a data set (jcm_augment_train_indexed; the
+// indices travel in the kernel arguments and were checked on the host)
+struct SrcDirect {
+  __device__ __forceinline__ size_t operator()(int b) const { return (size_t)b; }
+};
+struct SrcIndexed {
+  GatherIdx idx;
+  __device__ __forceinline__ size_t operator()(int b) const { return (size_t)idx.v[b]; }
+};
+
 // params[b] = (flip, delta, factor, angle, rh, rw)
 struct Rot {
   float c, s, xo, yo;
@@ -105,8 +115,9 @@ __device__ __forceinline__ void fold3(double* red) {
 }
 
 // partials[b][part][c] = sum over the part's pixels of double(float(x + delta)), channel c
+template <class Src>
 __global__ __launch_bounds__(kAugRed) void aug_mean_kernel(const float* __restrict__ x, const float* __restrict__ params, int HW,
-                                                           double* __restrict__ partials) {
+                                                           double* __restrict__ partials, Src src) {
   __shared__ double red[kAugRed];
   const int b = blockIdx.y;
   const float delta = params[(size_t)b * 6 + 1];
@@ -114,7 +125,7 @@ __global__ __launch_bounds__(kAugRed) void aug_mean_kernel(const float* __restri
   const int chunk = (n / 3 + kAugParts - 1) / kAugParts * 3;
   const int lo = blockIdx.x * chunk;
   const int hi = min(n, lo + chunk);
-  const float* xb = x + (size_t)b * n;
+  const float* xb = x + src(b) * n;
   double s = 0.0;
   for (int e = lo + (int)threadIdx.x; e < hi; e += kAugRed) s += (double)(xb[e] + delta);
   red[threadIdx.x] = s;
@@ -122,8 +133,9 @@ __global__ __launch_bounds__(kAugRed) void aug_mean_kernel(const float* __restri
   if (threadIdx.x < 3) partials[((size_t)b * kAugParts + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x];
 }
 
+template <class Src>
 __global__ __launch_bounds__(kAugImgThreads) void aug_image_kernel(const float* __restrict__ x, const float* __restrict__ params, int H, int W,
-                                                                   const double* __restrict__ partials, float* __restrict__ x_out) {
+                                                                   const double* __restrict__ partials, float* __restrict__ x_out, Src src) {
   __shared__ double red[kAugRed];
   __shared__ float s_mean[3];
   __shared__ Rot s_rot;
@@ -145,7 +157,7 @@ __global__ __launch_bounds__(kAugImgThreads) void aug_image_kernel(const float* 
   if (i >= HW) return;
   const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
   const Rot R = s_rot;
-  const float* xb = x + (size_t)b * HW * 3;
+  const float* xb = x + src(b) * HW * 3;
   // a source pixel after flip, brightness, contrast and clip; zeros outside the image (the rotation's fill)
   auto at = [&](float yf, float xf, float* v) {
     if (yf >= 0.f && yf < (float)H && xf >= 0.f && xf < (float)W) {
@@ -172,8 +184,9 @@ __global__ __launch_bounds__(kAugImgThreads) void aug_image_kernel(const float* 
 }
 
 // one work group per (heat-map channel k, image b): flip + channel permutation, rotation, crop, t = pow(v, 1.6) + 1e-5, t / sum(t)
+template <class Src>
 __global__ __launch_bounds__(kAugHmThreads) void aug_hm_kernel(const float* __restrict__ y, const float* __restrict__ params, int h, int w,
-                                                               float* __restrict__ y_out) {
+                                                               float* __restrict__ y_out, Src src) {
   __shared__ double red[kAugHmThreads];
   __shared__ Rot s_rot;
   const int k = blockIdx.x, b = blockIdx.y;
@@ -184,7 +197,7 @@ __global__ __launch_bounds__(kAugHmThreads) void aug_hm_kernel(const float* __re
   if (t == 0) s_rot = make_rot(p[3], h, w);
   __syncthreads();
   const Rot R = s_rot;
-  const float* yb = y + (size_t)b * hw * 10 + (flip ? kHmFlipPerm[k] : k);
+  const float* yb = y + src(b) * hw * 10 + (flip ? kHmFlipPerm[k] : k);
   float* ob = y_out + (size_t)b * hw * 10 + k;
   auto at = [&](float yf, float xf, float* v) {
     v[0] = 0.f;
@@ -216,13 +229,31 @@ __global__ __launch_bounds__(kAugHmThreads) void aug_hm_kernel(const float* __re
 
 size_t augment_scratch_doubles(int B) { return (size_t)B * kAugParts * 3; }
 
+template <class Src>
+void augment_launch(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch, float* x_out,
+                    float* y_out, const Src& src, hipStream_t st) {
+  static_assert(kAugRed == 3 * (kAugParts / 2) && kAugImgThreads >= kAugRed, "aug_image_kernel folds two parts per reduction slot");
+  hipLaunchKernelGGL(aug_mean_kernel<Src>, dim3(kAugParts, B), dim3(kAugRed), 0, st, x, params, H * W, scratch, src);
+  hipLaunchKernelGGL(aug_image_kernel<Src>, dim3((H * W + kAugImgThreads - 1) / kAugImgThreads, B), dim3(kAugImgThreads), 0, st, x, params, H, W,
+                     scratch, x_out, src);
+  hipLaunchKernelGGL(aug_hm_kernel<Src>, dim3(10, B), dim3(kAugHmThreads), 0, st, y, params, hh, hw, y_out, src);
+}
+
 hipError_t augment_train(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch,
                          float* x_out, float* y_out, hipStream_t st) {
-  static_assert(kAugRed == 3 * (kAugParts / 2) && kAugImgThreads >= kAugRed, "aug_image_kernel folds two parts per reduction slot");
-  hipLaunchKernelGGL(aug_mean_kernel, dim3(kAugParts, B), dim3(kAugRed), 0, st, x, params, H * W, scratch);
-  hipLaunchKernelGGL(aug_image_kernel, dim3((H * W + kAugImgThreads - 1) / kAugImgThreads, B), dim3(kAugImgThreads), 0, st, x, params, H, W,
-                     scratch, x_out);
-  hipLaunchKernelGGL(aug_hm_kernel, dim3(10, B), dim3(kAugHmThreads), 0, st, y, params, hh, hw, y_out);
+  augment_launch(x, y, params, B, H, W, hh, hw, scratch, x_out, y_out, SrcDirect{}, st);
+  return hipGetLastError();
+}
+
+hipError_t augment_train_indexed(const float* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
+                                 double* scratch, float* x_out, float* y_out, hipStream_t st) {
+  for (int b0 = 0; b0 < B; b0 += kGatherMax) {      // image b0 + i of the batch is image i of its launch: every per-image array starts at b0
+    const int nb = B - b0 < kGatherMax ? B - b0 : kGatherMax;
+    SrcIndexed src;
+    for (int i = 0; i < kGatherMax; ++i) src.idx.v[i] = i < nb ? idx[b0 + i] : 0;
+    augment_launch(x_all, y_all, params + (size_t)b0 * 6, nb, H, W, hh, hw, scratch + augment_scratch_doubles(b0), x_out + (size_t)b0 * H * W * 3,
+                   y_out + (size_t)b0 * hh * hw * 10, src, st);
+  }
   return hipGetLastError();
 }
 

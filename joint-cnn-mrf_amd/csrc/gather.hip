@@ -1,0 +1,74 @@
+// Batch gather from a device-resident data set: x_out[b] = x_all[idx[b]], y_out[b] = y_all[idx[b]], bit for bit.
+// A pure copy.  One launch covers both arrays of up to kGatherMax images: grid (kGatherXBlocks + kGatherYBlocks, images), the first
+// kGatherXBlocks columns sweep the image, the rest the heat maps, each work group striding over its image in 16-byte pieces (uint4) when
+// the image's byte count and both base addresses are multiples of 16 -- every image then starts 16-byte aligned -- and in 4-byte pieces
+// otherwise (chosen per array on the host).  The indices travel in the kernel arguments (GatherIdx): no staging buffer, no copy, nothing
+// for the host to wait for or to keep alive.  The entry point has checked every index against [0, N) before the launch.
+#include "kernels.h"
+
+namespace jcm {
+
+namespace {
+
+constexpr int kGatherThreads = 256;
+// 14 images x (120 + 8) work groups = 1 792 = 7 per CU: 259 200 uint4 per 480 x 720 x 3 image / (120 x 256 lanes) = 8.4 pieces per lane in the image columns,
+// 13 500 uint4 per 60 x 90 x 10 map / (8 x 256) = 6.6 in the heat-map columns
+constexpr int kGatherXBlocks = 120, kGatherYBlocks = 8;
+
+template <class T>
+__device__ __forceinline__ void copy_image(const T* __restrict__ src, T* __restrict__ dst, size_t n, int part, int parts) {
+  const size_t step = (size_t)parts * kGatherThreads;
+  size_t i = (size_t)part * kGatherThreads + threadIdx.x;
+  for (; i + 3 * step < n; i += 4 * step) {      // four independent loads in flight per lane
+    const T a = src[i], b = src[i + step], c = src[i + 2 * step], d = src[i + 3 * step];
+    dst[i] = a;
+    dst[i + step] = b;
+    dst[i + 2 * step] = c;
+    dst[i + 3 * step] = d;
+  }
+  for (; i < n; i += step) dst[i] = src[i];
+}
+
+// nx / ny: elements of TX / TY per image
+template <class TX, class TY>
+__global__ __launch_bounds__(kGatherThreads) void gather_batch_kernel(const TX* __restrict__ x_all, const TY* __restrict__ y_all, GatherIdx idx, size_t nx,
+                                                                      size_t ny, TX* __restrict__ x_out, TY* __restrict__ y_out) {
+  const int b = blockIdx.y;
+  const size_t src = (size_t)idx.v[b];
+  const int part = blockIdx.x;
+  if (part < kGatherXBlocks)
+    copy_image(x_all + src * nx, x_out + (size_t)b * nx, nx, part, kGatherXBlocks);
+  else
+    copy_image(y_all + src * ny, y_out + (size_t)b * ny, ny, part - kGatherXBlocks, kGatherYBlocks);
+}
+
+template <class TX, class TY>
+void launch(const float* x_all, const float* y_all, const GatherIdx& idx, int B, size_t nx, size_t ny, float* x_out, float* y_out, hipStream_t st) {
+  hipLaunchKernelGGL((gather_batch_kernel<TX, TY>), dim3(kGatherXBlocks + kGatherYBlocks, B), dim3(kGatherThreads), 0, st,
+                     reinterpret_cast<const TX*>(x_all), reinterpret_cast<const TY*>(y_all), idx, nx * sizeof(float) / sizeof(TX),
+                     ny * sizeof(float) / sizeof(TY), reinterpret_cast<TX*>(x_out), reinterpret_cast<TY*>(y_out));
+}
+
+bool wide(const void* a, const void* b, size_t floats_per_image) {
+  return (floats_per_image * sizeof(float)) % 16 == 0 && reinterpret_cast<uintptr_t>(a) % 16 == 0 && reinterpret_cast<uintptr_t>(b) % 16 == 0;
+}
+
+}  // namespace
+
+hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
+                        hipStream_t st) {
+  const bool wx = wide(x_all, x_out, nx), wy = wide(y_all, y_out, ny);
+  for (int b0 = 0; b0 < B; b0 += kGatherMax) {
+    const int nb = B - b0 < kGatherMax ? B - b0 : kGatherMax;
+    GatherIdx g;
+    for (int i = 0; i < kGatherMax; ++i) g.v[i] = i < nb ? idx[b0 + i] : 0;
+    float *xo = x_out + (size_t)b0 * nx, *yo = y_out + (size_t)b0 * ny;      // b0 * nx * 4 bytes keeps the 16-byte alignment when nx * 4 is a multiple of 16
+    if (wx && wy) launch<uint4, uint4>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+    else if (wx) launch<uint4, float>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+    else if (wy) launch<float, uint4>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+    else launch<float, float>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace jcm

@@ -1249,6 +1249,62 @@ int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float*
   });
 }
 
+namespace {
+
+// the argument checks jcm_gather_batch and jcm_augment_train_indexed share; Ky = heat-map channels; params may be null (gather)
+int check_indexed(const char* who, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B, int H, int W,
+                  int hh, int hw, int Ky, int min_side, const float* x_out, const float* y_out) {
+  const std::string w(who);
+  if (!x_all || !y_all || !idx || !x_out || !y_out) return fail(JCM_ERR_ARG, w + ": null pointer");
+  if (N < 1 || N > INT32_MAX || B < 1 || B > 65535 || H < min_side || W < min_side || hh < min_side || hw < min_side ||
+      (int64_t)H * W * 3 >= (int64_t)1 << 30 || (int64_t)hh * hw * Ky >= (int64_t)1 << 30)
+    return fail(JCM_ERR_ARG, w + ": bad sizes (N in [1, 2^31), B in [1, 65535], H, W, h, w >= " + std::to_string(min_side) + ")");
+  for (int b = 0; b < B; ++b)
+    if (idx[b] < 0 || (int64_t)idx[b] >= N)
+      return fail(JCM_ERR_ARG, w + ": idx[" + std::to_string(b) + "] = " + std::to_string(idx[b]) + " is outside [0, " + std::to_string(N) + ")");
+  const size_t ix = (size_t)H * W * 3 * sizeof(float), iy = (size_t)hh * hw * Ky * sizeof(float);
+  const size_t nxa = (size_t)N * ix, nya = (size_t)N * iy, nx = (size_t)B * ix, ny = (size_t)B * iy, np = (size_t)B * 6 * sizeof(float);
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+    return b != nullptr && pa < pb + nb && pb < pa + na;
+  };
+  if (overlap(x_out, nx, x_all, nxa) || overlap(x_out, nx, y_all, nya) || overlap(x_out, nx, params, np) || overlap(y_out, ny, x_all, nxa) ||
+      overlap(y_out, ny, y_all, nya) || overlap(y_out, ny, params, np) || overlap(x_out, nx, y_out, ny))
+    return fail(JCM_ERR_ARG, w + ": x_out / y_out overlap the data set, params or each other");
+  return JCM_OK;
+}
+
+}  // namespace
+
+int jcm_gather_batch(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W, int hh,
+                     int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  const int Ky = h->K + 1;
+  JCM_TRY(check_indexed("gather_batch", x_all, y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  HIP_TRY(gather_batch(x_all, y_all, idx, B, (size_t)H * W * 3, (size_t)hh * hw * Ky, x_out, y_out, h->stream));
+  return JCM_OK;
+}
+
+int jcm_augment_train_indexed(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
+                              int H, int W, int hh, int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  if (!params) return fail(JCM_ERR_ARG, "augment_train_indexed: null pointer");
+  if (h->K != 9)
+    return fail(JCM_ERR_ARG, "augment_train_indexed: the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
+  JCM_TRY(check_indexed("augment_train_indexed", x_all, y_all, N, idx, params, B, H, W, hh, hw, 10, 2, x_out, y_out));
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  return with_arena(c, [&] {
+    double* scratch = arena_alloc<double>(c, augment_scratch_doubles(B));
+    if (c->dry) return (int)JCM_OK;
+    HIP_TRY(augment_train_indexed(x_all, y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
+    return (int)JCM_OK;
+  });
+}
+
 int jcm_profile_read(jcm_handle h, const char* scope, double* total_ms, int* launches) {
   JCM_TRY(check(h, false));
   if (!scope || !total_ms || !launches) return fail(JCM_ERR_ARG, "bad profile_read arguments");

@@ -314,6 +314,19 @@ size_t augment_scratch_doubles(int B);
 hipError_t augment_train(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch,
                          float* x_out, float* y_out, hipStream_t st);
 
+// ---- gather.hip : batches by index from a device-resident data set -----------------
+// The indices of a launch travel by value in its kernel arguments; a batch of more than kGatherMax images takes several launches.
+constexpr int kGatherMax = 256;
+struct GatherIdx {
+  int v[kGatherMax];
+};
+// x_out[b] = x_all[idx[b]] (nx floats per image), y_out[b] = y_all[idx[b]] (ny floats); idx: HOST, B entries, every one checked by the caller
+hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
+                        hipStream_t st);
+// augment_train with image idx[b] of (x_all, y_all) as the source of output image b; same kernels, same arithmetic (augment.hip)
+hipError_t augment_train_indexed(const float* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
+                                 double* scratch, float* x_out, float* y_out, hipStream_t st);
+
 // ---- train_kernels.hip : training-step kernels other than convolutions (fp32 NHWC) ------------------
 size_t train_reduce_scratch_doubles(int C);      // scratch the per-channel reductions below need
 // batch mean / 1/sqrt(biased var + eps) of x [N,C]; moving stats (may be null) updated with `decay`

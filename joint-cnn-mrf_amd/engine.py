@@ -317,6 +317,58 @@ class Engine:
                                                self._p(x_out), self._p(y_out)), 'jcm_augment_train')
         return x_out, y_out
 
+    # ------------------------------------------------------------------ batches from a device-resident data set (dataset.py)
+    def _chk_indexed(self, who, x_all, y_all, idx, params, x_out, y_out):
+        """Shared checks of gather_batch / augment_train_indexed -> (host int32 indices, x_out, y_out).  The index RANGE is checked by the
+        entry point itself (on the host, before any launch)."""
+        self._chk(x_all, 4, 'x_all')
+        self._chk(y_all, 4, 'y_all')
+        N, H, W, C = x_all.shape
+        if C != 3 or y_all.shape[0] != N or y_all.shape[3] != self.n_joints + 1 or N < 1:
+            raise ValueError('%s expects x_all [N,H,W,3] and y_all [N,h,w,%d]; got %s, %s' % (who, self.n_joints + 1, tuple(x_all.shape), tuple(y_all.shape)))
+        if isinstance(idx, torch.Tensor):
+            if idx.device.type != 'cpu':
+                raise ValueError('%s: idx is a host array (it is checked on the host and travels in the kernel arguments), got a tensor on %s' % (who, idx.device))
+            idx = idx.numpy()
+        idx = np.asarray(idx)
+        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in 'iu':
+            raise ValueError('%s: idx must be a non-empty 1-D integer array, got shape %s dtype %s' % (who, idx.shape, idx.dtype))
+        if idx.dtype != np.int32:
+            if int(idx.min()) < -2 ** 31 or int(idx.max()) >= 2 ** 31:
+                raise ValueError('%s: idx does not fit int32' % who)
+            idx = idx.astype(np.int32)
+        idx = np.ascontiguousarray(idx)
+        B = idx.shape[0]
+        if params is not None:
+            self._chk(params, 2, 'params')
+            if tuple(params.shape) != (B, 6):
+                raise ValueError('%s expects params [%d,6] for %d indices; got %s' % (who, B, B, tuple(params.shape)))
+        x_out = self._new(B, H, W, 3) if x_out is None else self._chk(x_out, 4, 'x_out')
+        y_out = self._new(B, *y_all.shape[1:]) if y_out is None else self._chk(y_out, 4, 'y_out')
+        if tuple(x_out.shape) != (B, H, W, 3) or tuple(y_out.shape) != (B,) + tuple(y_all.shape[1:]):
+            raise ValueError('x_out / y_out must be [%d,...] with the image / map shapes of the data set; got %s, %s' % (B, tuple(x_out.shape), tuple(y_out.shape)))
+        self._on_stream(*[t for t in (x_all, y_all, params, x_out, y_out) if t is not None])
+        return idx, x_out, y_out
+
+    def gather_batch(self, x_all, y_all, idx, x_out=None, y_out=None):
+        """x_out[b] = x_all[idx[b]], y_out[b] = y_all[idx[b]] (bit for bit): x_all [N,H,W,3], y_all [N,h,w,K+1] device fp32, idx HOST integers
+        [B] in [0, N) (repeats allowed) -> (x_out, y_out), new tensors unless given.  Enqueued on the engine's stream; the host does not wait."""
+        idx, x_out, y_out = self._chk_indexed('gather_batch', x_all, y_all, idx, None, x_out, y_out)
+        N, H, W, _ = x_all.shape
+        _lib.check(self._lib.jcm_gather_batch(self._h, self._p(x_all), self._p(y_all), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.shape[0],
+                                              H, W, y_all.shape[1], y_all.shape[2], self._p(x_out), self._p(y_out)), 'jcm_gather_batch')
+        return x_out, y_out
+
+    def augment_train_indexed(self, x_all, y_all, idx, params, x_out=None, y_out=None):
+        """augment_train of the images idx[b] of the data set (x_all, y_all) with params[b], read through the index: the same bits as
+        gather_batch followed by augment_train, without the gathered copy."""
+        idx, x_out, y_out = self._chk_indexed('augment_train_indexed', x_all, y_all, idx, params, x_out, y_out)
+        N, H, W, _ = x_all.shape
+        _lib.check(self._lib.jcm_augment_train_indexed(self._h, self._p(x_all), self._p(y_all), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                       self._p(params), idx.shape[0], H, W, y_all.shape[1], y_all.shape[2], self._p(x_out), self._p(y_out)),
+                   'jcm_augment_train_indexed')
+        return x_out, y_out
+
     # ------------------------------------------------------------------ TensorBoard summaries (summary.py, DESIGN.md 4.8)
     def _on_stream(self, *ts):
         cur = torch.cuda.current_stream(self.device)

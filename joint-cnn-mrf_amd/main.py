@@ -70,6 +70,8 @@ def build_parser():
     parser.add_argument('--multiscale', action='store_true', help='evaluation run: 8-scale test-time evaluation (get_predictions, main.py:382-425).')
     parser.add_argument('--predictions', default=None, help='evaluation run: write flic_pred_pd / flic_pred_sm to this .mat file (main.py:675).')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
+    parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
+                        '(DESIGN.md 4.9); an error if they do not fit.')
     parser.add_argument('--tb_dir', default=None, help='write TensorBoard summaries to DIR/<model_name>/{train,test} (main.py:448-450; off by default).')
     parser.add_argument('--tb_log_iters', action='store_true', help='with --tb_dir: histograms and scalars after every step to DIR/<model_name>/train_iter '
                         '(tb_log_iters, main.py:452,642-645).')
@@ -295,6 +297,29 @@ class TowerTrainer:
             ys = torch.as_tensor(y[lo:hi]).to(eng.device, non_blocking=True).contiguous()
             with torch.cuda.device(eng.device):
                 tr.loss_and_grads(xs, ys, augment=None if aug is None else aug[lo:hi])
+        return self._average_and_apply()
+
+    def train_step_indexed(self, datasets, idx):
+        """train_step on the batch `idx` (host integers, one global batch) of device-resident data: `datasets` is a DeviceDataset or
+        {device: DeviceDataset} (DeviceDataset.for_towers: one copy per distinct device).  Every tower gathers its slice idx[lo:hi] on its
+        own device -- with augment_rng through the indexed augmentation, the parameters drawn for the global batch as in train_step."""
+        tw = self.towers
+        idx = np.asarray(idx).reshape(-1)
+        aug = None
+        if self.augment_rng is not None:
+            from .augmentation import draw_params
+            aug = draw_params(self.augment_rng, idx.shape[0])
+        for tr, eng, (lo, hi) in zip(self.trainers, tw.engines, tw.slices(idx.shape[0])):
+            ds = datasets[eng.device] if isinstance(datasets, dict) else datasets
+            if ds.device != eng.device:
+                raise ValueError('the data set is on %s, the tower on %s' % (ds.device, eng.device))
+            with torch.cuda.device(eng.device):
+                tr.loss_and_grads_indexed(ds, idx[lo:hi], augment=None if aug is None else aug[lo:hi])
+        return self._average_and_apply()
+
+    def _average_and_apply(self):
+        """The tower average, the clipped update on every replica and the composed moving statistics (the tail of a step)."""
+        tw = self.towers
         dev0 = tw.engines[0].device
         if tw.n > 1:
             total = self.trainers[0].grads
@@ -388,11 +413,21 @@ def train_main(args):
     tb = tb_open(args, model_name) if args.tb_dir else None
     tb_batches = {'train': tb_batch(x_train, y_train, args.batch_size), 'test': tb_batch(x_test, y_test, args.batch_size)} if tb else None
 
+    ds_train = ds_test = None
+    ev_train, ev_test = (x_train, y_train), (x_test, y_test)
+    if args.device_data:      # the (debug-subset) sets live on the towers' devices; eval_error reads the first tower's copy
+        from .dataset import DeviceDataset
+        # room the engines have not claimed yet: a full-width fp32 engine's filter-spectra cache and workspace grow to 64 GB on first use
+        reserve = len(towers.engines) * ((2 << 30) if args.debug else (64 << 30))
+        ds_test = DeviceDataset(x_test, y_test, device=eng.device, reserve_bytes=reserve)
+        ds_train = DeviceDataset.for_towers(towers, x_train, y_train, reserve_bytes=reserve)
+        ev_train, ev_test = (ds_train[eng.device].x, ds_train[eng.device].y), (ds_test.x, ds_test.y)
+
     def report(epoch):
         if tb:      # gradients of the epoch's last update (none before the first)
             tb_summaries(tb, eng, tt.trainers[0].layout, tb_batches, args.use_sm, epoch, grads=tt.trainers[0].grads if epoch > 0 else None)
-        tr_e = evaluation.eval_error(x_train[:n_eval_ex], y_train[:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
-        te_e = evaluation.eval_error(x_test[:n_eval_ex], y_test[:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
+        tr_e = evaluation.eval_error(ev_train[0][:n_eval_ex], ev_train[1][:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
+        te_e = evaluation.eval_error(ev_test[0][:n_eval_ex], ev_test[1][:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
         print('Epoch {:d}  test_dr {:.3f} {:.3f}  train_dr {:.3f} {:.3f}  test_mse {:.5f} {:.5f}  train_mse {:.5f} {:.5f}'.format(
             epoch, te_e[2], te_e[3], tr_e[2], tr_e[3], te_e[0], te_e[1], tr_e[0], tr_e[1]), flush=True)      # main.py:628-631,656-657
         if tb:
@@ -400,11 +435,18 @@ def train_main(args):
             summary.write_summary(tb['test'], [float(v) for v in te_e[:4]], TB_SCALARS, epoch)
             summary.write_summary(tb['train'], [float(v) for v in tr_e[:4]], TB_SCALARS, epoch)
 
+    def steps():      # one epoch of updates (main.py:641): the same permutation from `rng` on either route
+        if ds_train is not None:
+            for batch_idx in ds_train[eng.device].epoch_indices(rng, args.batch_size, shuffle=True):
+                yield tt.train_step_indexed(ds_train, batch_idx)
+        else:
+            for bx, by in evaluation.get_next_batch(x_train, y_train, args.batch_size, shuffle=True, rng=rng):
+                yield tt.train_step(np.ascontiguousarray(bx, np.float32), np.ascontiguousarray(by, np.float32))
+
     report(0)
     global_iter = 0
     for epoch in range(1, args.n_epochs + 1):
-        for bx, by in evaluation.get_next_batch(x_train, y_train, args.batch_size, shuffle=True, rng=rng):      # main.py:641
-            tt.train_step(np.ascontiguousarray(bx, np.float32), np.ascontiguousarray(by, np.float32))
+        for _ in steps():
             global_iter += 1
             if tb and 'train_iter' in tb:       # main.py:642-645, without the images
                 from . import summary

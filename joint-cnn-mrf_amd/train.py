@@ -61,6 +61,8 @@ class Trainer:
                    'jcm_train_set_grad_callback')
         self.losses = torch.zeros(4, dtype=torch.float32, device=engine.device)
         self._aug = None                                            # (x, y, params) buffers of the augmented batch (loss_and_grads(augment=))
+        self._gat = None                                            # (x, y) buffers of the gathered batch (loss_and_grads_indexed)
+        self.last_batch = None                                      # the device batch (x, y) the last step trained on
 
     @property
     def n_iters(self):
@@ -88,6 +90,13 @@ class Trainer:
                              % (hh, ww, e.n_joints + 1, tuple(x.shape), tuple(y.shape)))
         if augment is not None:
             x, y = self._augmented(x, y, augment)
+        return self._loss_and_grads(x, y)
+
+    def _loss_and_grads(self, x, y):
+        """jcm_train_loss_grads on the checked device batch (x, y) -- what loss_and_grads and loss_and_grads_indexed hand to the step."""
+        e = self.eng
+        B, H, W, _ = x.shape
+        self.last_batch = (x, y)
         self._cb_error = None
         status = self._lib.jcm_train_loss_grads(e._h, e._p(x), e._p(y), B, H, W, int(self.use_sm), self.lmbd,
                                                 e._p(self.grads), e._p(self.losses))
@@ -98,19 +107,46 @@ class Trainer:
         _lib.check(status, 'jcm_train_loss_grads')
         return self.losses, self.grads
 
-    def _augmented(self, x, y, augment):
-        """The augmented copy of (x, y) in buffers the trainer owns (kept across steps of the same shapes)."""
+    def _aug_buffers(self, shape_x, shape_y, augment):
+        """(x, y, params) buffers of the augmented batch, kept across steps of the same shapes, the parameters uploaded."""
         from .augmentation import check_params
         e = self.eng
         p = check_params(augment)
-        if p.shape[0] != x.shape[0]:
-            raise ValueError('augment has %d parameter rows for a batch of %d' % (p.shape[0], x.shape[0]))
-        if self._aug is None or self._aug[0].shape != x.shape or self._aug[1].shape != y.shape:
-            self._aug = (torch.empty_like(x), torch.empty_like(y), torch.empty(p.shape, dtype=torch.float32, device=e.device))
+        if p.shape[0] != shape_x[0]:
+            raise ValueError('augment has %d parameter rows for a batch of %d' % (p.shape[0], shape_x[0]))
+        if self._aug is None or tuple(self._aug[0].shape) != tuple(shape_x) or tuple(self._aug[1].shape) != tuple(shape_y):
+            self._aug = (torch.empty(tuple(shape_x), dtype=torch.float32, device=e.device), torch.empty(tuple(shape_y), dtype=torch.float32, device=e.device),
+                         torch.empty(p.shape, dtype=torch.float32, device=e.device))
         xa, ya, pd = self._aug
         with torch.cuda.stream(e._stream):       # behind the previous step's reads of the parameter buffer; the host does not wait
             pd.copy_(torch.from_numpy(p).pin_memory(), non_blocking=True)
-        return e.augment_train(x, y, pd, xa, ya)
+        return xa, ya, pd
+
+    def _augmented(self, x, y, augment):
+        """The augmented copy of (x, y) in buffers the trainer owns (kept across steps of the same shapes)."""
+        xa, ya, pd = self._aug_buffers(x.shape, y.shape, augment)
+        return self.eng.augment_train(x, y, pd, xa, ya)
+
+    def loss_and_grads_indexed(self, dataset, idx, augment=None):
+        """loss_and_grads on the batch (dataset.x[idx], dataset.y[idx]) of a DeviceDataset on this engine's device: gathered on the device
+        (Engine.gather_batch), or with `augment` read by the augmentation through the index (Engine.augment_train_indexed), into buffers
+        the trainer owns.  idx: host integers.  Nothing here makes the host wait."""
+        e = self.eng
+        idx = np.asarray(idx).reshape(-1)
+        B, (H, W) = idx.shape[0], dataset.x.shape[1:3]
+        hh, ww = self.heat_map_size(H, W)
+        if dataset.x.shape[3] != 3 or tuple(dataset.y.shape[1:]) != (hh, ww, e.n_joints + 1):
+            raise ValueError('the data set must hold x [N,H,W,3] and y [N,%d,%d,%d] (the heat-map size of the image); got %s, %s'
+                             % (hh, ww, e.n_joints + 1, tuple(dataset.x.shape), tuple(dataset.y.shape)))
+        shape_x, shape_y = (B, H, W, 3), (B, hh, ww, e.n_joints + 1)
+        if augment is not None:
+            xa, ya, pd = self._aug_buffers(shape_x, shape_y, augment)
+            x, y = e.augment_train_indexed(dataset.x, dataset.y, idx, pd, xa, ya)
+        else:
+            if self._gat is None or tuple(self._gat[0].shape) != shape_x:
+                self._gat = (torch.empty(shape_x, dtype=torch.float32, device=e.device), torch.empty(shape_y, dtype=torch.float32, device=e.device))
+            x, y = e.gather_batch(dataset.x, dataset.y, idx, *self._gat)
+        return self._loss_and_grads(x, y)
 
     def layer_grads(self, scope, x, dz, want_dx=True):
         """The weight gradient (+ lmbd * w) and the data gradient of ONE stride-1 conv layer on given tensors, through the kernels the training
@@ -225,6 +261,15 @@ class Trainer:
         `moving`: [(name, count)] of the BN moving statistics to keep in sync across ranks (N > 1).
         `augment`: host [B,6] augmentation parameters or None (loss_and_grads)."""
         self.loss_and_grads(x, y, augment=augment)
+        self.average_gradients()
+        norm = self.apply(want_norm=want_norm)
+        if moving:
+            self.sync_moving_statistics(moving)
+        return self.losses, norm
+
+    def train_step_indexed(self, dataset, idx, want_norm=False, moving=None, augment=None):
+        """train_step on the batch idx of a DeviceDataset (loss_and_grads_indexed)."""
+        self.loss_and_grads_indexed(dataset, idx, augment=augment)
         self.average_gradients()
         norm = self.apply(want_norm=want_norm)
         if moving:
