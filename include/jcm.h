@@ -203,6 +203,18 @@ int jcm_forward(jcm_handle h, const float* x, const float* torso, int B, int H, 
 int jcm_eval_forward(jcm_handle h, const float* x, const float* y, int B, int H, int W, int use_sm,
                      float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords, float* losses);
 
+/* -- byte images ----------------------------------------------------------------------
+ * jcm_pd_forward, jcm_forward and jcm_eval_forward on x [B,H,W,3] uint8 (device): byte k stands for float32(k) / float32(255), correctly
+ * rounded -- the value data.load_image makes of it -- and the results equal, bit for bit, those of the float entry on that float image.
+ * Only the conv1 kernels read the image; their byte-source variants convert at the load.  Every other argument, micro_batch, call_order,
+ * the profiling scopes and jcm_conv_kernel_name are those of the float entries.  (jcm_train_loss_grads stays float: training batches come
+ * out of the gather or the augmentation below, which write fp32.) */
+int jcm_pd_forward_u8(jcm_handle h, const uint8_t* x, int B, int H, int W, float* logits_out);
+int jcm_forward_u8(jcm_handle h, const uint8_t* x, const float* torso, int B, int H, int W, int use_sm,
+                   float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords);
+int jcm_eval_forward_u8(jcm_handle h, const uint8_t* x, const float* y, int B, int H, int W, int use_sm,
+                        float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords, float* losses);
+
 /* -- multi-scale test-time evaluation (the caller of the tower, main.py:326-425) ---------------------
  * One pad-or-crop window per output, then skimage.transform.resize(window, [OH,OW]) with the
  * 0.13.x defaults the reference relies on (bilinear, half-pixel centres, zeros outside, clip to
@@ -239,6 +251,13 @@ int jcm_gather_batch(jcm_handle h, const float* x_all, const float* y_all, int64
                      int hh, int hw, float* x_out, float* y_out);
 int jcm_augment_train_indexed(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params,
                               int B, int H, int W, int hh, int hw, float* x_out, float* y_out);
+/* The same two from a byte data set: x_all [N,H,W,3] uint8 (a quarter of the memory), y_all, x_out and y_out fp32 as above.  Every image value
+ * read is float32(k) / float32(255); the results equal those of the float entries on the float data set bit for bit.  Same checks, same
+ * error texts (under the _u8 names). */
+int jcm_gather_batch_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W,
+                        int hh, int hw, float* x_out, float* y_out);
+int jcm_augment_train_indexed_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params,
+                                 int B, int H, int W, int hh, int hw, float* x_out, float* y_out);
 
 /* -- TensorBoard summaries (tensorboard.py) -------------------------------------------------
  * jcm_tensor_stats: per segment (offset, count) of a flat device fp32 buffer -- or, with data == NULL, of the handle's stored

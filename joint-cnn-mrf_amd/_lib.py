@@ -43,6 +43,11 @@ SIGNATURES = {
                                    _c_float_p, _c_float_p, _c_i32_p, _c_i32_p]),
     'jcm_eval_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         _c_float_p, _c_float_p, _c_i32_p, _c_i32_p, _c_float_p]),
+    'jcm_pd_forward_u8': (ctypes.c_int, [_handle, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p]),
+    'jcm_forward_u8': (ctypes.c_int, [_handle, ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      _c_float_p, _c_float_p, _c_i32_p, _c_i32_p]),
+    'jcm_eval_forward_u8': (ctypes.c_int, [_handle, ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           _c_float_p, _c_float_p, _c_i32_p, _c_i32_p, _c_float_p]),
     'jcm_window_resize': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p]),
     'jcm_group_mean': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_float_p]),
@@ -52,6 +57,10 @@ SIGNATURES = {
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
     'jcm_augment_train_indexed': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), _c_float_p,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
+    'jcm_gather_batch_u8': (ctypes.c_int, [_handle, ctypes.c_void_p, _c_float_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
+    'jcm_augment_train_indexed_u8': (ctypes.c_int, [_handle, ctypes.c_void_p, _c_float_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), _c_float_p,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
     'jcm_tensor_stats': (ctypes.c_int, [_handle, _c_float_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_void_p, ctypes.c_void_p]),
     'jcm_hist_bucket_limits': (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int]),

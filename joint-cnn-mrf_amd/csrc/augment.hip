@@ -5,6 +5,7 @@
 // Three launches: the per-image channel sums of the brightened image (partials, no atomics), the image gather (crop taps ->
 // rotated samples -> source taps, the colour steps applied per source tap) and one work group per (image, heat-map channel).
 #include "kernels.h"
+#include "u8.h"
 
 namespace jcm {
 
@@ -115,8 +116,9 @@ __device__ __forceinline__ void fold3(double* red) {
 }
 
 // partials[b][part][c] = sum over the part's pixels of double(float(x + delta)), channel c
-template <class Src>
-__global__ __launch_bounds__(kAugRed) void aug_mean_kernel(const float* __restrict__ x, const float* __restrict__ params, int HW,
+// PixT (here and in aug_image_kernel): float, or uint8_t for a byte data set -- every value read goes through px_f32 (u8.h), the sums keep their order
+template <class Src, class PixT>
+__global__ __launch_bounds__(kAugRed) void aug_mean_kernel(const PixT* __restrict__ x, const float* __restrict__ params, int HW,
                                                            double* __restrict__ partials, Src src) {
   __shared__ double red[kAugRed];
   const int b = blockIdx.y;
@@ -125,16 +127,16 @@ __global__ __launch_bounds__(kAugRed) void aug_mean_kernel(const float* __restri
   const int chunk = (n / 3 + kAugParts - 1) / kAugParts * 3;
   const int lo = blockIdx.x * chunk;
   const int hi = min(n, lo + chunk);
-  const float* xb = x + src(b) * n;
+  const PixT* xb = x + src(b) * n;
   double s = 0.0;
-  for (int e = lo + (int)threadIdx.x; e < hi; e += kAugRed) s += (double)(xb[e] + delta);
+  for (int e = lo + (int)threadIdx.x; e < hi; e += kAugRed) s += (double)(px_f32(xb[e]) + delta);
   red[threadIdx.x] = s;
   fold3(red);
   if (threadIdx.x < 3) partials[((size_t)b * kAugParts + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x];
 }
 
-template <class Src>
-__global__ __launch_bounds__(kAugImgThreads) void aug_image_kernel(const float* __restrict__ x, const float* __restrict__ params, int H, int W,
+template <class Src, class PixT>
+__global__ __launch_bounds__(kAugImgThreads) void aug_image_kernel(const PixT* __restrict__ x, const float* __restrict__ params, int H, int W,
                                                                    const double* __restrict__ partials, float* __restrict__ x_out, Src src) {
   __shared__ double red[kAugRed];
   __shared__ float s_mean[3];
@@ -157,16 +159,16 @@ __global__ __launch_bounds__(kAugImgThreads) void aug_image_kernel(const float* 
   if (i >= HW) return;
   const float m0 = s_mean[0], m1 = s_mean[1], m2 = s_mean[2];
   const Rot R = s_rot;
-  const float* xb = x + src(b) * HW * 3;
+  const PixT* xb = x + src(b) * HW * 3;
   // a source pixel after flip, brightness, contrast and clip; zeros outside the image (the rotation's fill)
   auto at = [&](float yf, float xf, float* v) {
     if (yf >= 0.f && yf < (float)H && xf >= 0.f && xf < (float)W) {
       const int xx = (int)xf;
-      const float* s = xb + ((size_t)(int)yf * W + (flip ? W - 1 - xx : xx)) * 3;
+      const PixT* s = xb + ((size_t)(int)yf * W + (flip ? W - 1 - xx : xx)) * 3;
       const float m[3] = {m0, m1, m2};
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        float u = s[k] + delta;
+        float u = px_f32(s[k]) + delta;
         u = (u - m[k]) * factor + m[k];
         v[k] = fminf(fmaxf(u, 0.f), 1.f);
       }
@@ -229,12 +231,12 @@ __global__ __launch_bounds__(kAugHmThreads) void aug_hm_kernel(const float* __re
 
 size_t augment_scratch_doubles(int B) { return (size_t)B * kAugParts * 3; }
 
-template <class Src>
-void augment_launch(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch, float* x_out,
+template <class Src, class PixT>
+void augment_launch(const PixT* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch, float* x_out,
                     float* y_out, const Src& src, hipStream_t st) {
   static_assert(kAugRed == 3 * (kAugParts / 2) && kAugImgThreads >= kAugRed, "aug_image_kernel folds two parts per reduction slot");
-  hipLaunchKernelGGL(aug_mean_kernel<Src>, dim3(kAugParts, B), dim3(kAugRed), 0, st, x, params, H * W, scratch, src);
-  hipLaunchKernelGGL(aug_image_kernel<Src>, dim3((H * W + kAugImgThreads - 1) / kAugImgThreads, B), dim3(kAugImgThreads), 0, st, x, params, H, W,
+  hipLaunchKernelGGL((aug_mean_kernel<Src, PixT>), dim3(kAugParts, B), dim3(kAugRed), 0, st, x, params, H * W, scratch, src);
+  hipLaunchKernelGGL((aug_image_kernel<Src, PixT>), dim3((H * W + kAugImgThreads - 1) / kAugImgThreads, B), dim3(kAugImgThreads), 0, st, x, params, H, W,
                      scratch, x_out, src);
   hipLaunchKernelGGL(aug_hm_kernel<Src>, dim3(10, B), dim3(kAugHmThreads), 0, st, y, params, hh, hw, y_out, src);
 }
@@ -245,8 +247,10 @@ hipError_t augment_train(const float* x, const float* y, const float* params, in
   return hipGetLastError();
 }
 
-hipError_t augment_train_indexed(const float* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
-                                 double* scratch, float* x_out, float* y_out, hipStream_t st) {
+namespace {
+template <class PixT>
+hipError_t augment_indexed(const PixT* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
+                           double* scratch, float* x_out, float* y_out, hipStream_t st) {
   for (int b0 = 0; b0 < B; b0 += kGatherMax) {      // image b0 + i of the batch is image i of its launch: every per-image array starts at b0
     const int nb = B - b0 < kGatherMax ? B - b0 : kGatherMax;
     SrcIndexed src;
@@ -255,6 +259,16 @@ hipError_t augment_train_indexed(const float* x_all, const float* y_all, const i
                    y_out + (size_t)b0 * hh * hw * 10, src, st);
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t augment_train_indexed(const float* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
+                                 double* scratch, float* x_out, float* y_out, hipStream_t st) {
+  return augment_indexed(x_all, y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, st);
+}
+hipError_t augment_train_indexed_u8(const uint8_t* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
+                                    double* scratch, float* x_out, float* y_out, hipStream_t st) {
+  return augment_indexed(x_all, y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, st);
 }
 
 }  // namespace jcm

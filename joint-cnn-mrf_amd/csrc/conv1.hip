@@ -10,6 +10,7 @@
 // TF SAME with k=5, s=2 on an even extent pads 1 before / 2 after:
 // out = ceil(in/2), total = (out-1)*2+5-in, before = total/2.
 #include "kernels.h"
+#include "u8.h"
 
 namespace jcm {
 
@@ -18,17 +19,18 @@ constexpr int C1_IN = 2 * (C1_PT - 1) + 5;    // 19 input rows/cols per patch
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-template <class TO>
-__global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                    const float* __restrict__ bias, const float* __restrict__ scale,
-                                                    const float* __restrict__ shift, TO* __restrict__ out,
-                                                    int H0, int W0, int sub, int Hin, int Win, int Ho, int Wo,
-                                                    int pad_t, int pad_l, int Cout) {
+// PixT = float, or uint8_t (byte images, converted by u8_to_f32 at the load)
+template <class TO, class PixT>
+__device__ __forceinline__ void conv1_body(const PixT* __restrict__ x, const float* __restrict__ w,
+                                           const float* __restrict__ bias, const float* __restrict__ scale,
+                                           const float* __restrict__ shift, TO* __restrict__ out,
+                                           int H0, int W0, int sub, int Hin, int Win, int Ho, int Wo,
+                                           int pad_t, int pad_l, int Cout) {
   __shared__ float patch[C1_IN * C1_IN * 3];
   const int b = blockIdx.z;
   const int oy0 = blockIdx.y * C1_PT, ox0 = blockIdx.x * C1_PT;
   const int tid = threadIdx.x;
-  const float* xb = x + (size_t)b * H0 * W0 * 3;
+  const PixT* xb = x + (size_t)b * H0 * W0 * 3;
   for (int i = tid; i < C1_IN * C1_IN * 3; i += blockDim.x) {
     const int c = i % 3;
     const int p = i / 3;
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ x,
     const int gy = oy0 * 2 - pad_t + iy, gx = ox0 * 2 - pad_l + ix;   // coordinates in the sub-sampled image
     float v = 0.f;
     if ((unsigned)gy < (unsigned)Hin && (unsigned)gx < (unsigned)Win)
-      v = xb[((size_t)(gy * sub) * W0 + gx * sub) * 3 + c];
+      v = px_f32(xb[((size_t)(gy * sub) * W0 + gx * sub) * 3 + c]);
     patch[i] = v;
   }
   __syncthreads();
@@ -83,14 +85,42 @@ __global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ x,
   }
 }
 
-hipError_t conv1_5x5s2(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
-                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st) {
+template <class TO>
+__global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                    const float* __restrict__ bias, const float* __restrict__ scale,
+                                                    const float* __restrict__ shift, TO* __restrict__ out,
+                                                    int H0, int W0, int sub, int Hin, int Win, int Ho, int Wo,
+                                                    int pad_t, int pad_l, int Cout) {
+  conv1_body<TO, float>(x, w, bias, scale, shift, out, H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);
+}
+template <class TO>
+__global__ __launch_bounds__(256) void conv1_u8_kernel(const uint8_t* __restrict__ x, const float* __restrict__ w,
+                                                       const float* __restrict__ bias, const float* __restrict__ scale,
+                                                       const float* __restrict__ shift, TO* __restrict__ out,
+                                                       int H0, int W0, int sub, int Hin, int Win, int Ho, int Wo,
+                                                       int pad_t, int pad_l, int Cout) {
+  conv1_body<TO, uint8_t>(x, w, bias, scale, shift, out, H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);
+}
+
+hipError_t conv1_5x5s2(const void* xv, const float* w, const float* bias, const float* scale, const float* shift,
+                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st, bool x_u8) {
   if (Cout % 16 != 0 || Cout > 64 || H0 % sub != 0 || W0 % sub != 0) return hipErrorInvalidValue;
   const int Hin = H0 / sub, Win = W0 / sub;
   const int Ho = (Hin + 1) / 2, Wo = (Win + 1) / 2;
   const int tot_h = (Ho - 1) * 2 + 5 - Hin, tot_w = (Wo - 1) * 2 + 5 - Win;
   const int pad_t = (tot_h > 0 ? tot_h : 0) / 2, pad_l = (tot_w > 0 ? tot_w : 0) / 2;
   dim3 grid((Wo + C1_PT - 1) / C1_PT, (Ho + C1_PT - 1) / C1_PT, B);
+  if (x_u8) {
+    const uint8_t* x = static_cast<const uint8_t*>(xv);
+    if (out_bf16)
+      hipLaunchKernelGGL(conv1_u8_kernel<__bf16>, grid, dim3(64 * (Cout / 16)), 0, st, x, w, bias, scale, shift,
+                         static_cast<__bf16*>(out), H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);
+    else
+      hipLaunchKernelGGL(conv1_u8_kernel<float>, grid, dim3(64 * (Cout / 16)), 0, st, x, w, bias, scale, shift,
+                         static_cast<float*>(out), H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);
+    return hipGetLastError();
+  }
+  const float* x = static_cast<const float*>(xv);
   if (out_bf16)
     hipLaunchKernelGGL(conv1_kernel<__bf16>, grid, dim3(64 * (Cout / 16)), 0, st, x, w, bias, scale, shift,
                        static_cast<__bf16*>(out), H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);

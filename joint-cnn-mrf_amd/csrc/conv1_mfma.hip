@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "u8.h"
 
 namespace jcm {
 
@@ -36,8 +37,9 @@ namespace cfft { int persistent_grid(const void* kernel, int ntiles, int threads
 // anyway; fp32 output.  The window's scale is ITS OWN: the work group takes the largest |value| of the 35x35x3 window it has just loaded (one extra
 // barrier) and lifts it to [2^13, 2^14), the filter's scale comes with the packed filter -- so the kernel inherits fp32's range whatever the image holds,
 // without a pass over the image.  60 MFMAs 32x32x16 per wave (rounds 3-5: three bf16 parts, six products, 120).
-template <int NP, typename OutT>
-__device__ __forceinline__ void conv1_mfma_pool_body(const float* __restrict__ x, const f32x4* __restrict__ wq, const float* __restrict__ bias,
+// PixT = float, or uint8_t (byte images: three byte loads per pixel, converted by u8_to_f32 at the load; everything behind the load is the float kernel)
+template <int NP, typename OutT, typename PixT>
+__device__ __forceinline__ void conv1_mfma_pool_body(const PixT* __restrict__ x, const f32x4* __restrict__ wq, const float* __restrict__ bias,
                                                      const float* __restrict__ scale, const float* __restrict__ shift, OutT* __restrict__ out, int H0, int W0,
                                                      int sub, int Hin, int Win, int Hp, int Wp, int pad_t, int pad_l, int tiles_x, int tiles_img, int ntiles) {
   using ElT = std::conditional_t<NP == 1, __bf16, _Float16>;
@@ -62,20 +64,36 @@ __device__ __forceinline__ void conv1_mfma_pool_body(const float* __restrict__ x
 #pragma unroll
   for (int g = 0; g < 2; ++g) { bi[g] = bias[g * 32 + l31]; sc[g] = scale[g * 32 + l31]; sh[g] = shift[g * 32 + l31]; }
 
+  // Byte images: the prefetched window stays as loaded -- per pixel one 2-byte and one 1-byte load result, untouched -- until the top of the next
+  // iteration, so nothing waits for the loads in front of the MFMAs of the current tile; the bytes become floats (u8_to_f32) where the window is consumed.
+  // Float images are loaded into v directly, as before.
+  constexpr bool kU8 = std::is_same_v<PixT, uint8_t>;
+  typedef unsigned short __attribute__((aligned(1))) u16_unaligned;
   float v[PPT][3];
+  unsigned short raw01[kU8 ? PPT : 1];      // bytes 0 and 1 of the pixel
+  uint8_t raw2[kU8 ? PPT : 1];              // byte 2
   auto load_tile = [&](int t) __attribute__((always_inline)) {
     const int b = t / tiles_img, r = t - b * tiles_img;
     const int ty = r / tiles_x, tx = r - ty * tiles_x;
-    const float* xb = x + (size_t)b * H0 * W0 * 3;
+    const PixT* xb = x + (size_t)b * H0 * W0 * 3;
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       const int i = tid + 256 * k;
       const int iy = i / CM_IN, ix = i - iy * CM_IN;
       const int gy = ty * CM_T * 2 - pad_t + iy, gx = tx * CM_T * 2 - pad_l + ix;
-      v[k][0] = v[k][1] = v[k][2] = 0.f;
-      if (i < CM_IN * CM_IN && (unsigned)gy < (unsigned)Hin && (unsigned)gx < (unsigned)Win) {
-        const float* px3 = xb + ((size_t)(gy * sub) * W0 + gx * sub) * 3;
-        v[k][0] = px3[0]; v[k][1] = px3[1]; v[k][2] = px3[2];
+      const bool in = i < CM_IN * CM_IN && (unsigned)gy < (unsigned)Hin && (unsigned)gx < (unsigned)Win;
+      if constexpr (kU8) {
+        raw01[k] = 0; raw2[k] = 0;
+        if (in) {
+          const uint8_t* px3 = xb + ((size_t)(gy * sub) * W0 + gx * sub) * 3;
+          raw01[k] = *reinterpret_cast<const u16_unaligned*>(px3); raw2[k] = px3[2];
+        }
+      } else {
+        v[k][0] = v[k][1] = v[k][2] = 0.f;
+        if (in) {
+          const float* px3 = xb + ((size_t)(gy * sub) * W0 + gx * sub) * 3;
+          v[k][0] = px3[0]; v[k][1] = px3[1]; v[k][2] = px3[2];
+        }
       }
     }
   };
@@ -84,6 +102,12 @@ __device__ __forceinline__ void conv1_mfma_pool_body(const float* __restrict__ x
   for (; t < ntiles; t += gridDim.x) {
     // window -> LDS as 16-bit parts (round to nearest even; the remainders are exact)
     float xs = 1.f, xinv = 1.f;
+    if constexpr (kU8) {
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) {
+        v[k][0] = u8_to_f32(raw01[k] & 255u); v[k][1] = u8_to_f32(raw01[k] >> 8); v[k][2] = u8_to_f32(raw2[k]);
+      }
+    }
     if constexpr (NP == 2) {
       float m = 0.f;
 #pragma unroll
@@ -193,7 +217,7 @@ __global__ __launch_bounds__(256) void conv1_mfma_pool_kernel(const float* __res
                                                               const float* __restrict__ shift, __bf16* __restrict__ out,
                                                               int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
                                                               int pad_t, int pad_l, int tiles_x, int tiles_img, int ntiles) {
-  conv1_mfma_pool_body<1, __bf16>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x, tiles_img, ntiles);
+  conv1_mfma_pool_body<1, __bf16, float>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x, tiles_img, ntiles);
 }
 // fp32 handles on the default route: split operands (NP = 2: two scaled fp16 parts), fp32 in, fp32 out
 __global__ __launch_bounds__(256) void conv1_mfma_pool_split_kernel(const float* __restrict__ x, const f32x4* __restrict__ wq,
@@ -201,32 +225,49 @@ __global__ __launch_bounds__(256) void conv1_mfma_pool_split_kernel(const float*
                                                                     const float* __restrict__ shift, float* __restrict__ out,
                                                                     int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
                                                                     int pad_t, int pad_l, int tiles_x, int tiles_img, int ntiles) {
-  conv1_mfma_pool_body<2, float>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x, tiles_img, ntiles);
+  conv1_mfma_pool_body<2, float, float>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x, tiles_img, ntiles);
+}
+
+// the two kernels above on byte images
+__global__ __launch_bounds__(256) void conv1_mfma_pool_u8_kernel(const uint8_t* __restrict__ x, const f32x4* __restrict__ wq,
+                                                                 const float* __restrict__ bias, const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift, __bf16* __restrict__ out,
+                                                                 int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
+                                                                 int pad_t, int pad_l, int tiles_x, int tiles_img, int ntiles) {
+  conv1_mfma_pool_body<1, __bf16, uint8_t>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x, tiles_img, ntiles);
+}
+__global__ __launch_bounds__(256) void conv1_mfma_pool_split_u8_kernel(const uint8_t* __restrict__ x, const f32x4* __restrict__ wq,
+                                                                       const float* __restrict__ bias, const float* __restrict__ scale,
+                                                                       const float* __restrict__ shift, float* __restrict__ out,
+                                                                       int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
+                                                                       int pad_t, int pad_l, int tiles_x, int tiles_img, int ntiles) {
+  conv1_mfma_pool_body<2, float, uint8_t>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x, tiles_img, ntiles);
 }
 
 // ---- the same fusion on the exact fp32 path: v_mfma_f32_32x32x2_f32 (an exact k-ordered fma chain), fp32 window in LDS.
 // K = 5 kernel rows x 16 (15 values + a zero pad) = 40 MFMA k-steps of 2; lane (pixel, h) supplies window element 2s+h of its
 // row, lane (channel, h) the matching filter value (one ds_read_b32 each).  Same accumulator layout, same register-local pool.
 constexpr int CF_ROW = 35 * 3 + 3;              // fp32 row pitch of the LDS window (105 values + 3 zeros: element 15 of the last pixel's row window)
-__global__ __launch_bounds__(256) void conv1_mfma_pool_f32_kernel(const float* __restrict__ x, const float* __restrict__ wq,
-                                                                  const float* __restrict__ bias, const float* __restrict__ scale,
-                                                                  const float* __restrict__ shift, float* __restrict__ out,
-                                                                  int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
-                                                                  int pad_t, int pad_l, int tiles_x) {
+template <typename PixT>
+__device__ __forceinline__ void conv1_mfma_pool_f32_body(const PixT* __restrict__ x, const float* __restrict__ wq,
+                                                         const float* __restrict__ bias, const float* __restrict__ scale,
+                                                         const float* __restrict__ shift, float* __restrict__ out,
+                                                         int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
+                                                         int pad_t, int pad_l, int tiles_x) {
   __shared__ float win[CM_IN * CF_ROW];
   __shared__ float wl[5 * 16 * 64];            // [ky][k'][co]
   const int b = blockIdx.y;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int oy0 = ty * CM_T, ox0 = tx * CM_T;
   const int tid = threadIdx.x;
-  const float* xb = x + (size_t)b * H0 * W0 * 3;
+  const PixT* xb = x + (size_t)b * H0 * W0 * 3;
   for (int i = tid; i < CM_IN * CM_IN; i += 256) {
     const int iy = i / CM_IN, ix = i - iy * CM_IN;
     const int gy = oy0 * 2 - pad_t + iy, gx = ox0 * 2 - pad_l + ix;
     float v0 = 0.f, v1 = 0.f, v2 = 0.f;
     if ((unsigned)gy < (unsigned)Hin && (unsigned)gx < (unsigned)Win) {
-      const float* px3 = xb + ((size_t)(gy * sub) * W0 + gx * sub) * 3;
-      v0 = px3[0]; v1 = px3[1]; v2 = px3[2];
+      const PixT* px3 = xb + ((size_t)(gy * sub) * W0 + gx * sub) * 3;
+      v0 = px_f32(px3[0]); v1 = px_f32(px3[1]); v2 = px_f32(px3[2]);
     }
     float* w3 = win + iy * CF_ROW + ix * 3;
     w3[0] = v0; w3[1] = v1; w3[2] = v2;
@@ -284,6 +325,20 @@ __global__ __launch_bounds__(256) void conv1_mfma_pool_f32_kernel(const float* _
     }
   }
 }
+__global__ __launch_bounds__(256) void conv1_mfma_pool_f32_kernel(const float* __restrict__ x, const float* __restrict__ wq,
+                                                                  const float* __restrict__ bias, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, float* __restrict__ out,
+                                                                  int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
+                                                                  int pad_t, int pad_l, int tiles_x) {
+  conv1_mfma_pool_f32_body<float>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x);
+}
+__global__ __launch_bounds__(256) void conv1_mfma_pool_f32_u8_kernel(const uint8_t* __restrict__ x, const float* __restrict__ wq,
+                                                                     const float* __restrict__ bias, const float* __restrict__ scale,
+                                                                     const float* __restrict__ shift, float* __restrict__ out,
+                                                                     int H0, int W0, int sub, int Hin, int Win, int Hp, int Wp,
+                                                                     int pad_t, int pad_l, int tiles_x) {
+  conv1_mfma_pool_f32_body<uint8_t>(x, wq, bias, scale, shift, out, H0, W0, sub, Hin, Win, Hp, Wp, pad_t, pad_l, tiles_x);
+}
 
 constexpr int CS_NP = 2;
 // HWIO [5,5,3,64] fp32 -> [part][ky][h][co][8] fp16 (two parts of every weight times the power of two that lifts max|w| to [2^13, 2^14)), k' = 8h+i = 3*kx + c,
@@ -323,8 +378,8 @@ hipError_t pack_conv1_split(const float* w_hwio, void* wq, hipStream_t st) {
   hipLaunchKernelGGL(pack_conv1_split_kernel, dim3(1), dim3(256), 0, st, w_hwio, static_cast<_Float16*>(wq));
   return hipGetLastError();
 }
-hipError_t conv1_mfma_pool_split(const float* x, const void* wq, const float* bias, const float* scale, const float* shift, float* out,
-                                 int B, int H0, int W0, int sub, hipStream_t st) {
+hipError_t conv1_mfma_pool_split(const void* x, const void* wq, const float* bias, const float* scale, const float* shift, float* out,
+                                 int B, int H0, int W0, int sub, hipStream_t st, bool x_u8) {
   if (H0 % (4 * sub) != 0 || W0 % (4 * sub) != 0) return hipErrorInvalidValue;
   const int Hin = H0 / sub, Win = W0 / sub;
   const int Ho = Hin / 2, Wo = Win / 2;
@@ -332,8 +387,14 @@ hipError_t conv1_mfma_pool_split(const float* x, const void* wq, const float* bi
   const int pad_t = tot_h / 2, pad_l = tot_w / 2;
   const int tiles_x = (Wo + CM_T - 1) / CM_T, tiles_y = (Ho + CM_T - 1) / CM_T;
   const int ntiles = tiles_x * tiles_y * B;
+  if (x_u8) {
+    const int grid = cfft::persistent_grid(reinterpret_cast<const void*>(conv1_mfma_pool_split_u8_kernel), ntiles, 256);
+    hipLaunchKernelGGL(conv1_mfma_pool_split_u8_kernel, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t*>(x), static_cast<const f32x4*>(wq), bias,
+                       scale, shift, out, H0, W0, sub, Hin, Win, Ho / 2, Wo / 2, pad_t, pad_l, tiles_x, tiles_x * tiles_y, ntiles);
+    return hipGetLastError();
+  }
   const int grid = cfft::persistent_grid(reinterpret_cast<const void*>(conv1_mfma_pool_split_kernel), ntiles, 256);
-  hipLaunchKernelGGL(conv1_mfma_pool_split_kernel, dim3(grid), dim3(256), 0, st, x, static_cast<const f32x4*>(wq), bias, scale, shift, out,
+  hipLaunchKernelGGL(conv1_mfma_pool_split_kernel, dim3(grid), dim3(256), 0, st, static_cast<const float*>(x), static_cast<const f32x4*>(wq), bias, scale, shift, out,
                      H0, W0, sub, Hin, Win, Ho / 2, Wo / 2, pad_t, pad_l, tiles_x, tiles_x * tiles_y, ntiles);
   return hipGetLastError();
 }
@@ -350,16 +411,20 @@ hipError_t pack_conv1_f32(const float* w_hwio, float* wq, hipStream_t st) {
   return hipGetLastError();
 }
 // x [B,H0,W0,3] fp32 -> out [B,Hp,Wp,64] fp32 (conv s2 + bias/ReLU/BN + pool s2); H0/sub and W0/sub divisible by 4
-hipError_t conv1_mfma_pool_f32(const float* x, const float* wq, const float* bias, const float* scale, const float* shift, float* out,
-                               int B, int H0, int W0, int sub, hipStream_t st) {
+hipError_t conv1_mfma_pool_f32(const void* x, const float* wq, const float* bias, const float* scale, const float* shift, float* out,
+                               int B, int H0, int W0, int sub, hipStream_t st, bool x_u8) {
   if (H0 % (4 * sub) != 0 || W0 % (4 * sub) != 0) return hipErrorInvalidValue;
   const int Hin = H0 / sub, Win = W0 / sub;
   const int Ho = Hin / 2, Wo = Win / 2;
   const int tot_h = (Ho - 1) * 2 + 5 - Hin, tot_w = (Wo - 1) * 2 + 5 - Win;
   const int pad_t = tot_h / 2, pad_l = tot_w / 2;
   const int tiles_x = (Wo + CM_T - 1) / CM_T, tiles_y = (Ho + CM_T - 1) / CM_T;
-  hipLaunchKernelGGL(conv1_mfma_pool_f32_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, st, x, wq, bias, scale, shift, out, H0, W0, sub,
-                     Hin, Win, Ho / 2, Wo / 2, pad_t, pad_l, tiles_x);
+  if (x_u8)
+    hipLaunchKernelGGL(conv1_mfma_pool_f32_u8_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, st, static_cast<const uint8_t*>(x), wq, bias, scale, shift, out,
+                       H0, W0, sub, Hin, Win, Ho / 2, Wo / 2, pad_t, pad_l, tiles_x);
+  else
+    hipLaunchKernelGGL(conv1_mfma_pool_f32_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, st, static_cast<const float*>(x), wq, bias, scale, shift, out,
+                       H0, W0, sub, Hin, Win, Ho / 2, Wo / 2, pad_t, pad_l, tiles_x);
   return hipGetLastError();
 }
 
@@ -381,8 +446,8 @@ hipError_t pack_conv1_bf16(const float* w_hwio, void* wq, hipStream_t st) {
 
 // x [B,H0,W0,3] fp32 -> out [B,Hp,Wp,64] bf16 with Hp = (H0/sub)/4, Wp = (W0/sub)/4 (conv s2 then pool s2).
 // Requires H0/sub and W0/sub divisible by 4 (all three branches of the 480x720 model).
-hipError_t conv1_mfma_pool(const float* x, const void* wq, const float* bias, const float* scale, const float* shift,
-                           void* out, int B, int H0, int W0, int sub, hipStream_t st) {
+hipError_t conv1_mfma_pool(const void* x, const void* wq, const float* bias, const float* scale, const float* shift,
+                           void* out, int B, int H0, int W0, int sub, hipStream_t st, bool x_u8) {
   if (H0 % (4 * sub) != 0 || W0 % (4 * sub) != 0) return hipErrorInvalidValue;
   const int Hin = H0 / sub, Win = W0 / sub;
   const int Ho = Hin / 2, Wo = Win / 2;
@@ -390,8 +455,14 @@ hipError_t conv1_mfma_pool(const float* x, const void* wq, const float* bias, co
   const int pad_t = tot_h / 2, pad_l = tot_w / 2;
   const int tiles_x = (Wo + CM_T - 1) / CM_T, tiles_y = (Ho + CM_T - 1) / CM_T;
   const int ntiles = tiles_x * tiles_y * B;
+  if (x_u8) {
+    const int grid = cfft::persistent_grid(reinterpret_cast<const void*>(conv1_mfma_pool_u8_kernel), ntiles, 256);
+    hipLaunchKernelGGL(conv1_mfma_pool_u8_kernel, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t*>(x), static_cast<const f32x4*>(wq), bias,
+                       scale, shift, static_cast<__bf16*>(out), H0, W0, sub, Hin, Win, Ho / 2, Wo / 2, pad_t, pad_l, tiles_x, tiles_x * tiles_y, ntiles);
+    return hipGetLastError();
+  }
   const int grid = cfft::persistent_grid(reinterpret_cast<const void*>(conv1_mfma_pool_kernel), ntiles, 256);
-  hipLaunchKernelGGL(conv1_mfma_pool_kernel, dim3(grid), dim3(256), 0, st, x, static_cast<const f32x4*>(wq), bias,
+  hipLaunchKernelGGL(conv1_mfma_pool_kernel, dim3(grid), dim3(256), 0, st, static_cast<const float*>(x), static_cast<const f32x4*>(wq), bias,
                      scale, shift, static_cast<__bf16*>(out), H0, W0, sub, Hin, Win, Ho / 2, Wo / 2, pad_t, pad_l, tiles_x, tiles_x * tiles_y, ntiles);
   return hipGetLastError();
 }

@@ -4,7 +4,11 @@
 // the image's byte count and both base addresses are multiples of 16 -- every image then starts 16-byte aligned -- and in 4-byte pieces
 // otherwise (chosen per array on the host).  The indices travel in the kernel arguments (GatherIdx): no staging buffer, no copy, nothing
 // for the host to wait for or to keep alive.  The entry point has checked every index against [0, N) before the launch.
+// Byte data sets: the image columns convert instead of copying, x_out = u8_to_f32(x_all[idx]) -- a lane takes one aligned dword
+// of four image bytes and writes one float4, so a wave reads 256 contiguous bytes and writes 1 KB of whole lines per instruction (wide path:
+// image byte count and source base multiples of 4, destination base a multiple of 16); byte loads and dword stores otherwise.
 #include "kernels.h"
+#include "u8.h"
 
 namespace jcm {
 
@@ -27,6 +31,47 @@ __device__ __forceinline__ void copy_image(const T* __restrict__ src, T* __restr
     dst[i + 3 * step] = d;
   }
   for (; i < n; i += step) dst[i] = src[i];
+}
+
+// dst[i] = u8_to_f32(src[i]), n values.  WIDE: four values per piece (src 4-byte aligned, dst 16-byte aligned, n % 4 == 0)
+template <bool WIDE>
+__device__ __forceinline__ void convert_image(const uint8_t* __restrict__ src, float* __restrict__ dst, size_t n, int part, int parts) {
+  const size_t step = (size_t)parts * kGatherThreads;
+  size_t i = (size_t)part * kGatherThreads + threadIdx.x;
+  if constexpr (WIDE) {
+    const unsigned* s4 = reinterpret_cast<const unsigned*>(src);
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    const size_t n4 = n / 4;
+    auto cvt = [](unsigned w) { return make_float4(u8_to_f32(w & 255u), u8_to_f32((w >> 8) & 255u), u8_to_f32((w >> 16) & 255u), u8_to_f32(w >> 24)); };
+    for (; i + 3 * step < n4; i += 4 * step) {      // four independent loads in flight per lane
+      const unsigned a = s4[i], b = s4[i + step], c = s4[i + 2 * step], d = s4[i + 3 * step];
+      d4[i] = cvt(a);
+      d4[i + step] = cvt(b);
+      d4[i + 2 * step] = cvt(c);
+      d4[i + 3 * step] = cvt(d);
+    }
+    for (; i < n4; i += step) d4[i] = cvt(s4[i]);
+  } else {
+    for (; i < n; i += step) dst[i] = u8_to_f32(src[i]);
+  }
+}
+
+// image columns convert nx bytes -> nx floats, heat-map columns copy ny elements of TY
+template <bool WIDE, class TY>
+__global__ __launch_bounds__(kGatherThreads) void gather_batch_u8_kernel(const uint8_t* __restrict__ x_all, const TY* __restrict__ y_all, GatherIdx idx,
+                                                                         size_t nx, size_t ny, float* __restrict__ x_out, TY* __restrict__ y_out) {
+  const int b = blockIdx.y;
+  const size_t src = (size_t)idx.v[b];
+  const int part = blockIdx.x;
+  if (part < kGatherXBlocks)
+    convert_image<WIDE>(x_all + src * nx, x_out + (size_t)b * nx, nx, part, kGatherXBlocks);
+  else
+    copy_image(y_all + src * ny, y_out + (size_t)b * ny, ny, part - kGatherXBlocks, kGatherYBlocks);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(kGatherThreads) void u8_to_f32_kernel(const uint8_t* __restrict__ x, float* __restrict__ out, size_t n) {
+  convert_image<WIDE>(x, out, n, blockIdx.x, gridDim.x);
 }
 
 // nx / ny: elements of TX / TY per image
@@ -53,7 +98,42 @@ bool wide(const void* a, const void* b, size_t floats_per_image) {
   return (floats_per_image * sizeof(float)) % 16 == 0 && reinterpret_cast<uintptr_t>(a) % 16 == 0 && reinterpret_cast<uintptr_t>(b) % 16 == 0;
 }
 
+template <bool WIDE, class TY>
+void launch_u8(const uint8_t* x_all, const float* y_all, const GatherIdx& idx, int B, size_t nx, size_t ny, float* x_out, float* y_out, hipStream_t st) {
+  hipLaunchKernelGGL((gather_batch_u8_kernel<WIDE, TY>), dim3(kGatherXBlocks + kGatherYBlocks, B), dim3(kGatherThreads), 0, st, x_all,
+                     reinterpret_cast<const TY*>(y_all), idx, nx, ny * sizeof(float) / sizeof(TY), x_out, reinterpret_cast<TY*>(y_out));
+}
+
+// every image of a byte array starts 4-byte aligned and every converted image 16-byte aligned
+bool wide_u8(const void* src, const void* dst, size_t bytes_per_image) {
+  return bytes_per_image % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+}
+
 }  // namespace
+
+hipError_t gather_batch_u8(const uint8_t* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
+                           hipStream_t st) {
+  const bool wx = wide_u8(x_all, x_out, nx), wy = wide(y_all, y_out, ny);
+  for (int b0 = 0; b0 < B; b0 += kGatherMax) {
+    const int nb = B - b0 < kGatherMax ? B - b0 : kGatherMax;
+    GatherIdx g;
+    for (int i = 0; i < kGatherMax; ++i) g.v[i] = i < nb ? idx[b0 + i] : 0;
+    float *xo = x_out + (size_t)b0 * nx, *yo = y_out + (size_t)b0 * ny;
+    if (wx && wy) launch_u8<true, uint4>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+    else if (wx) launch_u8<true, float>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+    else if (wy) launch_u8<false, uint4>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+    else launch_u8<false, float>(x_all, y_all, g, nb, nx, ny, xo, yo, st);
+  }
+  return hipGetLastError();
+}
+
+hipError_t u8_to_f32_array(const uint8_t* x, float* x_out, size_t n, hipStream_t st) {
+  const size_t pieces = (n + 4 * kGatherThreads - 1) / (4 * kGatherThreads);
+  const int grid = (int)(pieces < 2048 ? (pieces ? pieces : 1) : 2048);
+  if (wide_u8(x, x_out, n)) hipLaunchKernelGGL(u8_to_f32_kernel<true>, dim3(grid), dim3(kGatherThreads), 0, st, x, x_out, n);
+  else hipLaunchKernelGGL(u8_to_f32_kernel<false>, dim3(grid), dim3(kGatherThreads), 0, st, x, x_out, n);
+  return hipGetLastError();
+}
 
 hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
                         hipStream_t st) {

@@ -391,13 +391,12 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
 // One conv layer.  Activations are fp32, or bf16 when the handle runs the bf16 path (`act_bf16`);
 // `out_f32` forces an fp32 result (the logits layer).
 int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub,
-                   void* out, bool act_bf16, bool out_f32, int in_planar, int out_planar) {
+                   void* out, bool act_bf16, bool out_f32, int in_planar, int out_planar, bool x_u8) {
   if (stride == 2) {
     if (c->dry) return JCM_OK;
     if (!(L->ks == 5 && L->cin == 3 && L->has_bn))
       return fail(JCM_ERR_ARG, "stride-2 kernel exists for 5x5, Cin=3, BN layers only (" + scope + ")");
-    HIP_TRY(conv1_5x5s2(static_cast<const float*>(x), L->w_raw, L->bias, L->scale, L->shift, out, act_bf16, B, H, W, sub,
-                        L->cout, c->stream));
+    HIP_TRY(conv1_5x5s2(x, L->w_raw, L->bias, L->scale, L->shift, out, act_bf16, B, H, W, sub, L->cout, c->stream, x_u8));
     return JCM_OK;
   }
   if (stride == 1 && takes_fft(c, L, B, H, W))
@@ -554,10 +553,11 @@ int refresh_derived(jcm_ctx* c, bool first) {
 namespace {
 
 int run_conv(jcm_ctx* c, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub, void* out,
-             bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0) {
+             bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false) {      // x_u8: the stride-2 layer reads a byte image
   const ConvLayer* L = conv_of(c, scope);
   if (!L) return fail(JCM_ERR_STATE, "no conv layer '" + scope + "' (set '" + scope + "/weights' and finalize)");
-  return run_conv_layer(c, L, scope, stride, x, B, H, W, sub, out, act_bf16, out_f32, in_planar, out_planar);
+  if (x_u8 && stride != 2) return fail(JCM_ERR_ARG, "byte images feed the stride-2 first layer only (" + scope + ")");
+  return run_conv_layer(c, L, scope, stride, x, B, H, W, sub, out, act_bf16, out_f32, in_planar, out_planar, x_u8);
 }
 
 // bf16 handles: does a [B,H,W,Cin] launch of this 9x9 layer take the flattened-strip kernel (which reads / writes the
@@ -603,9 +603,10 @@ static void* offer_pool_handover(jcm_ctx* c, const ConvLayer* La, const ConvLaye
   c->fft_next_ks = Lb->ks;
   return t;
 }
-// model(x, n_joints), main.py:29-74.  x fp32 NHWC; intermediate activations fp32 or bf16.
+// model(x, n_joints), main.py:29-74.  x fp32 NHWC, or (x_u8) a byte image whose values k stand for float32(k) / float32(255): only the conv1 kernels
+// read it, and their byte-source variants convert at the load (u8.h).  Intermediate activations fp32 or bf16.
 
-int pd_forward_impl(jcm_ctx* c, const float* x, int B, int H, int W, float* logits) {
+int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, float* logits) {
   static const char* const kRes[3] = {"fullres", "halfres", "quarterres"};
   const ConvLayer* L4 = conv_of(c, "conv4_fullres");
   const ConvLayer* L5 = conv_of(c, "conv5");
@@ -653,6 +654,14 @@ int pd_forward_impl(jcm_ctx* c, const float* x, int B, int H, int W, float* logi
   // tensor gives a lane only the 4 bytes of its channel pair inside a 16-byte unit (3.3 against 4.8 TB/s measured for the inverse row pass).
   // So with conv5 in the frequency domain the chain conv4 -> merge -> conv5 is NHWC; conv5's OUTPUT stays planar for the logits kernel.
   const int planar45 = planar && !takes_fft(c, L5, B, h4[0], w4[0]) ? 1 : 0;
+  // A branch whose scale is not an integer takes a real bilinear resize, and the resize kernel reads floats: a byte batch is widened ONCE, in front of the
+  // branches (the floats the float entry would have been given), and lives until the last branch has run.
+  const float* x_wide = nullptr;
+  if (x_u8 && (H % 4 || W % 4)) {
+    float* xw32 = arena_alloc<float>(c, (size_t)B * H * W * 3);
+    if (!c->dry) HIP_TRY(u8_to_f32_array(static_cast<const uint8_t*>(x), xw32, (size_t)B * H * W * 3, c->stream));
+    x_wide = xw32;
+  }
   static const int kOrder[3] = {1, 2, 0};
   for (int ri = 0; ri < 3; ++ri) {
     const int r = kOrder[ri];
@@ -664,12 +673,14 @@ int pd_forward_impl(jcm_ctx* c, const float* x, int B, int H, int W, float* logi
     const ConvLayer* L2 = conv_of(c, "conv2_" + res);
     const ConvLayer* L3 = conv_of(c, "conv3_" + res);
     if (!L1 || !L2 || !L3) return fail(JCM_ERR_STATE, "part-detector parameters incomplete (" + res + ")");
-    const float* xin = x;
+    const void* xin = x;
+    bool xin_u8 = x_u8;
     int xh = H, xw = W, xsub = sub;
     if (H % sub || W % sub) {   // non-integer scale: a real bilinear resize, not sub-sampling
+      const float* xf = x_u8 ? x_wide : static_cast<const float*>(x);
       float* xr = arena_alloc<float>(c, (size_t)B * hin * win * 3);
-      if (!c->dry) HIP_TRY(resize_bilinear(x, xr, B, H, W, 3, hin, win, c->stream));
-      xin = xr; xh = hin; xw = win; xsub = 1;
+      if (!c->dry) HIP_TRY(resize_bilinear(xf, xr, B, H, W, 3, hin, win, c->stream));
+      xin = xr; xin_u8 = false; xh = hin; xw = win; xsub = 1;
     }
     const int h1 = cdiv2(hin), w1 = cdiv2(win);
     const int h2 = cdiv2(h1), w2 = cdiv2(w1);
@@ -682,16 +693,16 @@ int pd_forward_impl(jcm_ctx* c, const float* x, int B, int H, int W, float* logi
       // default route (the stride-1 layers run on split operands on the bf16 matrix cores): conv1 too; the exact fp32 MFMA chain otherwise
       const bool split1 = c->conv9_fft && c->f32_conv == 0 && L1->wq1_split;
       if (!c->dry)
-        HIP_TRY(split1 ? conv1_mfma_pool_split(xin, L1->wq1_split, L1->bias, L1->scale, L1->shift, static_cast<float*>(p1), B, xh, xw, xsub, c->stream)
-                       : conv1_mfma_pool_f32(xin, L1->wq1_f32, L1->bias, L1->scale, L1->shift, static_cast<float*>(p1), B, xh, xw, xsub, c->stream));
+        HIP_TRY(split1 ? conv1_mfma_pool_split(xin, L1->wq1_split, L1->bias, L1->scale, L1->shift, static_cast<float*>(p1), B, xh, xw, xsub, c->stream, xin_u8)
+                       : conv1_mfma_pool_f32(xin, L1->wq1_f32, L1->bias, L1->scale, L1->shift, static_cast<float*>(p1), B, xh, xw, xsub, c->stream, xin_u8));
     } else if (bf && L1->wq1_bf16 && xh % (4 * xsub) == 0 && xw % (4 * xsub) == 0) {
       // bf16 path: conv1 + ReLU/BN + pool1 in one MFMA kernel; only the pooled map touches HBM
       p1 = act((size_t)B * h2 * w2 * L1->cout);
       if (!c->dry)
-        HIP_TRY(conv1_mfma_pool(xin, L1->wq1_bf16, L1->bias, L1->scale, L1->shift, p1, B, xh, xw, xsub, c->stream));  // :44-45,52-53,61-62
+        HIP_TRY(conv1_mfma_pool(xin, L1->wq1_bf16, L1->bias, L1->scale, L1->shift, p1, B, xh, xw, xsub, c->stream, xin_u8));  // :44-45,52-53,61-62
     } else {
       void* c1 = act((size_t)B * h1 * w1 * L1->cout);
-      JCM_TRY(run_conv(c, "conv1_" + res, 2, xin, B, xh, xw, xsub, c1, bf, false));       // main.py:44,52,61
+      JCM_TRY(run_conv(c, "conv1_" + res, 2, xin, B, xh, xw, xsub, c1, bf, false, 0, 0, xin_u8));       // main.py:44,52,61
       p1 = act((size_t)B * h2 * w2 * L1->cout);
       if (!c->dry) HIP_TRY(max_pool_2x2(c1, p1, bf, B, h1, w1, L1->cout, c->stream));       // :45,53,62
     }
@@ -1034,13 +1045,15 @@ int jcm_resize_bilinear(jcm_handle h, const float* x, int B, int H, int W, int C
   return JCM_OK;
 }
 
-int jcm_pd_forward(jcm_handle h, const float* x, int B, int H, int W, float* logits_out) {
+static int pd_forward_entry(jcm_handle h, const void* x, bool x_u8, int B, int H, int W, float* logits_out) {
   JCM_TRY(check(h, true));
   if (!x || !logits_out || B < 1 || H < 8 || W < 8) return fail(JCM_ERR_ARG, "bad pd_forward arguments");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  return with_arena(h, [&] { return pd_forward_impl(h, x, B, H, W, logits_out); });
+  return with_arena(h, [&] { return pd_forward_impl(h, x, x_u8, B, H, W, logits_out); });
 }
+int jcm_pd_forward(jcm_handle h, const float* x, int B, int H, int W, float* logits_out) { return pd_forward_entry(h, x, false, B, H, W, logits_out); }
+int jcm_pd_forward_u8(jcm_handle h, const uint8_t* x, int B, int H, int W, float* logits_out) { return pd_forward_entry(h, x, true, B, H, W, logits_out); }
 
 int jcm_spatial_softmax(jcm_handle h, const float* in, int B, int HW, int K, float* out) {
   JCM_TRY(check(h, false));
@@ -1113,7 +1126,7 @@ int jcm_argmax_coords(jcm_handle h, const float* hm, int B, int HH, int WW, int 
 
 // The tower of main.py:522-531, optionally with the two cross-entropy terms of main.py:538-539 in inference mode (what
 // eval_error runs, main.py:275-283).  The torso channel is `torso` [B,HW,1], or channel K of y [B,HW,K+1] when y is given.
-static int forward_impl(jcm_handle h, const float* x, const float* torso, const float* y, int B, int H, int W, int use_sm,
+static int forward_impl(jcm_handle h, const void* x, bool x_u8, const float* torso, const float* y, int B, int H, int W, int use_sm,
                         float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords, float* losses) {
   JCM_TRY(check(h, true));
   if (!x || B < 1 || H < 8 || W < 8) return fail(JCM_ERR_ARG, "bad forward arguments");
@@ -1140,7 +1153,8 @@ static int forward_impl(jcm_handle h, const float* x, const float* torso, const 
     float* logits = arena_alloc<float>(c, n);
     float* prob = pd_prob ? pd_prob + o : arena_alloc<float>(c, n);
     const size_t mark = c->arena_off;
-    JCM_TRY(pd_forward_impl(c, x + (size_t)b0 * H * W * 3, nb, H, W, logits));            // main.py:522
+    const void* xb = static_cast<const char*>(x) + (size_t)b0 * H * W * 3 * (x_u8 ? 1 : sizeof(float));
+    JCM_TRY(pd_forward_impl(c, xb, x_u8, nb, H, W, logits));            // main.py:522
     c->arena_off = mark;
     // spatial_softmax (main.py:523) and the argmax of evaluation.py:15-24 in one pass over the logits
     if (!c->dry) HIP_TRY(softmax_argmax(logits, prob, pd_coords ? pd_coords + (size_t)b0 * 2 * K : nullptr, nb, hh * ww, ww, K, c->stream));
@@ -1181,13 +1195,22 @@ static int forward_impl(jcm_handle h, const float* x, const float* torso, const 
 
 int jcm_forward(jcm_handle h, const float* x, const float* torso, int B, int H, int W, int use_sm,
                 float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords) {
-  return forward_impl(h, x, torso, nullptr, B, H, W, use_sm, pd_prob, sm_prob, pd_coords, sm_coords, nullptr);
+  return forward_impl(h, x, false, torso, nullptr, B, H, W, use_sm, pd_prob, sm_prob, pd_coords, sm_coords, nullptr);
+}
+int jcm_forward_u8(jcm_handle h, const uint8_t* x, const float* torso, int B, int H, int W, int use_sm,
+                   float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords) {
+  return forward_impl(h, x, true, torso, nullptr, B, H, W, use_sm, pd_prob, sm_prob, pd_coords, sm_coords, nullptr);
 }
 
 int jcm_eval_forward(jcm_handle h, const float* x, const float* y, int B, int H, int W, int use_sm,
                      float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords, float* losses) {
   if (!y || !losses) return fail(JCM_ERR_ARG, "eval_forward needs the target heat maps y [B,60,90,K+1] and a 2-float loss buffer");
-  return forward_impl(h, x, nullptr, y, B, H, W, use_sm, pd_prob, sm_prob, pd_coords, sm_coords, losses);
+  return forward_impl(h, x, false, nullptr, y, B, H, W, use_sm, pd_prob, sm_prob, pd_coords, sm_coords, losses);
+}
+int jcm_eval_forward_u8(jcm_handle h, const uint8_t* x, const float* y, int B, int H, int W, int use_sm,
+                        float* pd_prob, float* sm_prob, int32_t* pd_coords, int32_t* sm_coords, float* losses) {
+  if (!y || !losses) return fail(JCM_ERR_ARG, "eval_forward needs the target heat maps y [B,60,90,K+1] and a 2-float loss buffer");
+  return forward_impl(h, x, true, nullptr, y, B, H, W, use_sm, pd_prob, sm_prob, pd_coords, sm_coords, losses);
 }
 
 int jcm_window_resize(jcm_handle h, const float* src, int nsrc, int H, int W, int C, const int32_t* windows, int NW,
@@ -1252,7 +1275,8 @@ int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float*
 namespace {
 
 // the argument checks jcm_gather_batch and jcm_augment_train_indexed share; Ky = heat-map channels; params may be null (gather)
-int check_indexed(const char* who, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B, int H, int W,
+// xes: bytes per image value of the data set (4, or 1 for a byte data set; the outputs are fp32 either way)
+int check_indexed(const char* who, const void* x_all, size_t xes, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B, int H, int W,
                   int hh, int hw, int Ky, int min_side, const float* x_out, const float* y_out) {
   const std::string w(who);
   if (!x_all || !y_all || !idx || !x_out || !y_out) return fail(JCM_ERR_ARG, w + ": null pointer");
@@ -1263,7 +1287,7 @@ int check_indexed(const char* who, const float* x_all, const float* y_all, int64
     if (idx[b] < 0 || (int64_t)idx[b] >= N)
       return fail(JCM_ERR_ARG, w + ": idx[" + std::to_string(b) + "] = " + std::to_string(idx[b]) + " is outside [0, " + std::to_string(N) + ")");
   const size_t ix = (size_t)H * W * 3 * sizeof(float), iy = (size_t)hh * hw * Ky * sizeof(float);
-  const size_t nxa = (size_t)N * ix, nya = (size_t)N * iy, nx = (size_t)B * ix, ny = (size_t)B * iy, np = (size_t)B * 6 * sizeof(float);
+  const size_t nxa = (size_t)N * H * W * 3 * xes, nya = (size_t)N * iy, nx = (size_t)B * ix, ny = (size_t)B * iy, np = (size_t)B * 6 * sizeof(float);
   auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
     const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
     return b != nullptr && pa < pb + nb && pb < pa + na;
@@ -1280,29 +1304,50 @@ int jcm_gather_batch(jcm_handle h, const float* x_all, const float* y_all, int64
                      int hw, float* x_out, float* y_out) {
   JCM_TRY(check(h, false));
   const int Ky = h->K + 1;
-  JCM_TRY(check_indexed("gather_batch", x_all, y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
+  JCM_TRY(check_indexed("gather_batch", x_all, sizeof(float), y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
   DeviceGuard g(h->device);
   CallOrder order(h);
   HIP_TRY(gather_batch(x_all, y_all, idx, B, (size_t)H * W * 3, (size_t)hh * hw * Ky, x_out, y_out, h->stream));
   return JCM_OK;
 }
 
-int jcm_augment_train_indexed(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
-                              int H, int W, int hh, int hw, float* x_out, float* y_out) {
+int jcm_gather_batch_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W, int hh,
+                        int hw, float* x_out, float* y_out) {
   JCM_TRY(check(h, false));
-  if (!params) return fail(JCM_ERR_ARG, "augment_train_indexed: null pointer");
+  const int Ky = h->K + 1;
+  JCM_TRY(check_indexed("gather_batch_u8", x_all, 1, y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  HIP_TRY(gather_batch_u8(x_all, y_all, idx, B, (size_t)H * W * 3, (size_t)hh * hw * Ky, x_out, y_out, h->stream));
+  return JCM_OK;
+}
+
+static int augment_indexed_entry(jcm_handle h, const char* who, const void* x_all, bool x_u8, const float* y_all, int64_t N, const int32_t* idx,
+                                 const float* params, int B, int H, int W, int hh, int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  const std::string w(who);
+  if (!params) return fail(JCM_ERR_ARG, w + ": null pointer");
   if (h->K != 9)
-    return fail(JCM_ERR_ARG, "augment_train_indexed: the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
-  JCM_TRY(check_indexed("augment_train_indexed", x_all, y_all, N, idx, params, B, H, W, hh, hw, 10, 2, x_out, y_out));
+    return fail(JCM_ERR_ARG, w + ": the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
+  JCM_TRY(check_indexed(who, x_all, x_u8 ? 1 : sizeof(float), y_all, N, idx, params, B, H, W, hh, hw, 10, 2, x_out, y_out));
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
   return with_arena(c, [&] {
     double* scratch = arena_alloc<double>(c, augment_scratch_doubles(B));
     if (c->dry) return (int)JCM_OK;
-    HIP_TRY(augment_train_indexed(x_all, y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
+    if (x_u8) HIP_TRY(augment_train_indexed_u8(static_cast<const uint8_t*>(x_all), y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
+    else HIP_TRY(augment_train_indexed(static_cast<const float*>(x_all), y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
     return (int)JCM_OK;
   });
+}
+int jcm_augment_train_indexed(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
+                              int H, int W, int hh, int hw, float* x_out, float* y_out) {
+  return augment_indexed_entry(h, "augment_train_indexed", x_all, false, y_all, N, idx, params, B, H, W, hh, hw, x_out, y_out);
+}
+int jcm_augment_train_indexed_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
+                                 int H, int W, int hh, int hw, float* x_out, float* y_out) {
+  return augment_indexed_entry(h, "augment_train_indexed_u8", x_all, true, y_all, N, idx, params, B, H, W, hh, hw, x_out, y_out);
 }
 
 int jcm_profile_read(jcm_handle h, const char* scope, double* total_ms, int* launches) {

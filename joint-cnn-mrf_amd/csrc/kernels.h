@@ -213,24 +213,26 @@ hipError_t conv_strip_bf16(const ConvArgs& a, hipStream_t st);
 // ---- conv1.hip : 5x5 stride-2 SAME convolution of the (sub-sampled) RGB image ---------------
 // x [B,H0,W0,3] fp32; the branch input is x[:, ::sub, ::sub] (TF-1.x bilinear with an integer
 // scale is pure sub-sampling, main.py:51,60); w HWIO [5,5,3,Cout]; out [B,Ho,Wo,Cout] fp32 or bf16.
-hipError_t conv1_5x5s2(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
-                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st);
+// x_u8 (here and for the three conv1_mfma.hip launchers): x is a byte image [B,H0,W0,3], each value k standing for float32(k) / float32(255)
+// (u8.h); the byte-source kernels convert at the load and are the float kernels behind it.
+hipError_t conv1_5x5s2(const void* x, const float* w, const float* bias, const float* scale, const float* shift,
+                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st, bool x_u8 = false);
 
 // ---- conv1_mfma.hip : conv1 + bias/ReLU/BN + 2x2 max-pool fused, bf16 MFMA (bf16 path only) ----
 // x [B,H0,W0,3] fp32 (branch input = x[:, ::sub, ::sub]) -> out [B,(H0/sub)/4,(W0/sub)/4,64] bf16
 hipError_t pack_conv1_bf16(const float* w_hwio, void* wq, hipStream_t st);
-hipError_t conv1_mfma_pool(const float* x, const void* wq, const float* bias, const float* scale, const float* shift,
-                           void* out, int B, int H0, int W0, int sub, hipStream_t st);
+hipError_t conv1_mfma_pool(const void* x, const void* wq, const float* bias, const float* scale, const float* shift,
+                           void* out, int B, int H0, int W0, int sub, hipStream_t st, bool x_u8 = false);
 
 // the same fusion on the exact fp32 path (v_mfma_f32_32x32x2_f32): wq [5][16][64] fp32 from pack_conv1_f32, out fp32
 hipError_t pack_conv1_f32(const float* w_hwio, float* wq, hipStream_t st);
 // the same with fp32 operands as three bf16 parts on the bf16 matrix cores (fp32 handles on the default frequency-domain route)
 size_t conv1_split_weight_bytes();
 hipError_t pack_conv1_split(const float* w_hwio, void* wq, hipStream_t st);
-hipError_t conv1_mfma_pool_split(const float* x, const void* wq, const float* bias, const float* scale, const float* shift, float* out,
-                                 int B, int H0, int W0, int sub, hipStream_t st);
-hipError_t conv1_mfma_pool_f32(const float* x, const float* wq, const float* bias, const float* scale, const float* shift, float* out,
-                               int B, int H0, int W0, int sub, hipStream_t st);
+hipError_t conv1_mfma_pool_split(const void* x, const void* wq, const float* bias, const float* scale, const float* shift, float* out,
+                                 int B, int H0, int W0, int sub, hipStream_t st, bool x_u8 = false);
+hipError_t conv1_mfma_pool_f32(const void* x, const float* wq, const float* bias, const float* scale, const float* shift, float* out,
+                               int B, int H0, int W0, int sub, hipStream_t st, bool x_u8 = false);
 
 // ---- glue.hip ----------------------------------------------------------------------------------
 // `bf16`: activations are bf16 instead of fp32 (arithmetic stays fp32).
@@ -323,9 +325,17 @@ struct GatherIdx {
 // x_out[b] = x_all[idx[b]] (nx floats per image), y_out[b] = y_all[idx[b]] (ny floats); idx: HOST, B entries, every one checked by the caller
 hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
                         hipStream_t st);
+// the same from a byte image array: x_out[b][i] = u8_to_f32(x_all[idx[b]][i]) (u8.h), nx values per image; the heat maps are copied as above
+hipError_t gather_batch_u8(const uint8_t* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
+                           hipStream_t st);
+// x_out[i] = u8_to_f32(x[i]), n values (a byte batch whose branch inputs need a real resize: jcm_pd_forward_u8 at sizes not divisible by 4)
+hipError_t u8_to_f32_array(const uint8_t* x, float* x_out, size_t n, hipStream_t st);
 // augment_train with image idx[b] of (x_all, y_all) as the source of output image b; same kernels, same arithmetic (augment.hip)
 hipError_t augment_train_indexed(const float* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
                                  double* scratch, float* x_out, float* y_out, hipStream_t st);
+// the same with a byte image array as the source (every tap converted by u8_to_f32; sums in the same order: the same bits)
+hipError_t augment_train_indexed_u8(const uint8_t* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
+                                    double* scratch, float* x_out, float* y_out, hipStream_t st);
 
 // ---- train_kernels.hip : training-step kernels other than convolutions (fp32 NHWC) ------------------
 size_t train_reduce_scratch_doubles(int C);      // scratch the per-channel reductions below need

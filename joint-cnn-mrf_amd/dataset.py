@@ -6,6 +6,10 @@ gather by index on the device (`Engine.gather_batch`), or the source of the augm
 (`Engine.augment_train_indexed`).  `epoch_indices` draws the batches exactly as `evaluation.get_next_batch` does, so a run fed
 from the device sees the batches of a host-fed run with the same seed.  A set that does not fit raises
 `DeviceDataTooLarge`: there is no silent fall-back to the host path and no prefetching for larger sets.
+
+`image_dtype='uint8'` holds the images as the bytes they were made from: data.load_image computes every value as
+float32(k) / float32(255), so the byte image is the float image at a quarter of the memory (FLIC: 4.1 + 1.05 GB), of the upload and of the
+gather's reads.  Float input is converted by `to_u8_exact`, which proves the round trip and refuses data that is not on that grid.
 """
 import numpy as np
 import torch
@@ -15,6 +19,50 @@ DEFAULT_CHUNK_BYTES = 256 << 20      # per staging buffer
 
 class DeviceDataTooLarge(RuntimeError):
     """The data set does not fit into the device memory it may use."""
+
+
+class NotByteExact(ValueError):
+    """An image value is not float32(k) / float32(255) for a byte k: storing it as a byte would change it."""
+
+    def __init__(self, index, value):
+        self.index, self.value = tuple(int(i) for i in index), value
+        super().__init__('image value %r at index %s is not float32(k) / float32(255) for any byte k: it cannot be stored as uint8 without '
+                         'rounding (image_dtype=\'uint8\' holds byte images only)' % (value, self.index))
+
+
+_F255 = np.float32(255)
+
+
+CONVERT_ROWS_BYTES = 32 << 20      # to_u8_exact works on slices of this many source bytes: its temporaries stay a few times that, whatever the array
+
+
+def to_u8_exact(a):
+    """The byte image of a float image made as float32(k) / float32(255) (data.load_image): rint(a * 255) as uint8, VERIFIED -- the bytes
+    widened by that same division must give back `a` bit for bit, otherwise NotByteExact names the first offending index and value (NaN,
+    values outside [0, 1] and values off the grid all fail it).  A uint8 array is returned unchanged."""
+    a = np.asarray(a)
+    if a.dtype == np.uint8:
+        return a
+    if a.dtype != np.float32:
+        raise TypeError('to_u8_exact takes float32 or uint8 images, got %s' % a.dtype)
+    out = np.empty(a.shape, np.uint8)
+    if a.ndim == 0 or a.size == 0:
+        flat_a, flat_o, step = a.reshape(1, -1), out.reshape(1, -1), 1
+    else:                                  # slices along the first axis (views: a non-contiguous input is not copied as a whole)
+        flat_a, flat_o = a, out
+        step = max(1, CONVERT_ROWS_BYTES // max(1, 4 * (a.size // a.shape[0])))
+    for lo in range(0, flat_a.shape[0], step):
+        part = np.ascontiguousarray(flat_a[lo:lo + step])
+        with np.errstate(invalid='ignore'):
+            k = np.rint(part * _F255)
+            k = np.where((k >= 0) & (k <= 255), k, 0).astype(np.uint8)      # (NaN and out-of-range values: any byte, they fail the check below)
+        bad = (k.astype(np.float32) / _F255).view(np.uint32) != part.view(np.uint32)
+        if bad.any():
+            i = np.unravel_index(int(np.argmax(bad)), part.shape)
+            i = (i[0] + lo,) + tuple(i[1:]) if a.ndim else ()
+            raise NotByteExact(i, a[i].item())
+        flat_o[lo:lo + step] = k
+    return out
 
 
 def plan_chunks(n, chunk_rows):
@@ -38,14 +86,18 @@ def _open(a):
 
 
 class DeviceDataset:
-    """x [N,H,W,3], y [N,h,w,K+1] as fp32 device tensors `.x`, `.y` on `device`.
+    """x [N,H,W,3], y [N,h,w,K+1] as fp32 device tensors `.x`, `.y` on `device`; with image_dtype='uint8' `.x` is a uint8 tensor (x given as
+    uint8 is uploaded as is, x given as float32 goes through to_u8_exact chunk by chunk: NotByteExact if it is not a byte image).
 
     x, y: numpy arrays, np.memmap or paths of .npy files (opened memory-mapped).  rows: optional row subset (the --debug
     selection), taken in the order given.  chunk_rows: rows per staging buffer (default: DEFAULT_CHUNK_BYTES worth of images).
     budget_bytes: the device memory the set may take; default: what torch.cuda.mem_get_info reports free, less reserve_bytes
     (room the engines have not claimed yet: workspace, the filter-spectra cache)."""
 
-    def __init__(self, x, y, device=0, rows=None, chunk_rows=None, budget_bytes=None, reserve_bytes=0):
+    def __init__(self, x, y, device=0, rows=None, chunk_rows=None, budget_bytes=None, reserve_bytes=0, image_dtype='float32'):
+        if image_dtype not in ('float32', 'uint8'):
+            raise ValueError("image_dtype must be 'float32' or 'uint8', got %r" % (image_dtype,))
+        self.image_dtype = image_dtype
         x, y = _open(x), _open(y)
         if x.ndim != 4 or y.ndim != 4 or x.shape[3] != 3 or x.shape[0] != y.shape[0]:
             raise ValueError('DeviceDataset expects x [N,H,W,3] and y [N,h,w,K+1] with the same N; got %s, %s' % (x.shape, y.shape))
@@ -58,17 +110,19 @@ class DeviceDataset:
             raise ValueError('DeviceDataset needs at least one example')
         self.device = torch.device('cuda', device if isinstance(device, int) else torch.device(device).index or 0)
         shape_x, shape_y = (self.n,) + tuple(x.shape[1:]), (self.n,) + tuple(y.shape[1:])
-        self.nbytes = 4 * (int(np.prod(shape_x)) + int(np.prod(shape_y)))
+        xes = 1 if image_dtype == 'uint8' else 4                    # bytes per image value
+        self.nbytes = xes * int(np.prod(shape_x)) + 4 * int(np.prod(shape_y))
         if budget_bytes is None:
             free, total = torch.cuda.mem_get_info(self.device)
             budget_bytes, where = free - int(reserve_bytes), '%d bytes free of %d on %s, %d of them reserved for the engines' % (free, total, self.device, reserve_bytes)
         else:
             where = 'the budget given'
         if self.nbytes > budget_bytes:
-            raise DeviceDataTooLarge('the data set needs %d bytes (%d examples: x %s, y %s, fp32) and may use %d (%s); a set that does not fit '
-                                     'is not prefetched from the host: train without device data' % (self.nbytes, self.n, shape_x[1:], shape_y[1:], budget_bytes, where))
+            raise DeviceDataTooLarge('the data set needs %d bytes (%d examples: x %s, y %s, %s) and may use %d (%s); a set that does not fit '
+                                     'is not prefetched from the host: train without device data'
+                                     % (self.nbytes, self.n, shape_x[1:], shape_y[1:], 'fp32' if xes == 4 else 'x uint8, y fp32', budget_bytes, where))
         with torch.cuda.device(self.device):
-            self.x = torch.empty(shape_x, dtype=torch.float32, device=self.device)
+            self.x = torch.empty(shape_x, dtype=torch.uint8 if xes == 1 else torch.float32, device=self.device)
             self.y = torch.empty(shape_y, dtype=torch.float32, device=self.device)
             import time
             t0 = time.perf_counter()
@@ -82,18 +136,25 @@ class DeviceDataset:
     def _upload(src, dst, rows, chunk_rows, stream):
         n = dst.shape[0]
         row_elems = int(np.prod(dst.shape[1:]))
-        if chunk_rows is None:
-            chunk_rows = max(1, DEFAULT_CHUNK_BYTES // (4 * row_elems))
+        if chunk_rows is None:      # sized by the SOURCE: a float chunk that is converted to bytes is as large on the host as one that is uploaded as floats
+            chunk_rows = max(1, DEFAULT_CHUNK_BYTES // (max(dst.element_size(), np.dtype(src.dtype).itemsize) * row_elems))
         chunk_rows = min(int(chunk_rows), n)
         flat = dst.view(n, row_elems)
-        stage = [torch.empty((chunk_rows, row_elems), dtype=torch.float32).pin_memory() for _ in range(2)]
+        stage = [torch.empty((chunk_rows, row_elems), dtype=dst.dtype).pin_memory() for _ in range(2)]
         done = [None, None]
         for i, (lo, hi) in enumerate(plan_chunks(n, chunk_rows)):
             k = i % 2
             if done[k] is not None:
                 done[k].synchronize()        # the copy that last read this buffer; the other buffer's copy runs meanwhile
             part = src[lo:hi] if rows is None else src[rows[lo:hi]]
-            np.copyto(stage[k][:hi - lo].numpy(), np.asarray(part).reshape(hi - lo, row_elems), casting='same_kind')
+            part = np.asarray(part).reshape(hi - lo, row_elems)
+            if dst.dtype == torch.uint8:                   # a byte data set: bytes pass, floats are converted and the round trip checked
+                try:
+                    part = to_u8_exact(part)       # uint8 passes, float32 is converted with proof, anything else (float64, ...) is a TypeError
+                except NotByteExact as e:                  # the index in the caller's array: row of the upload order, then the position in the image
+                    r, c = e.index
+                    raise NotByteExact((lo + r,) + tuple(int(v) for v in np.unravel_index(c, dst.shape[1:])), e.value) from None
+            np.copyto(stage[k][:hi - lo].numpy(), part, casting='same_kind')
             with torch.cuda.stream(stream):
                 flat[lo:hi].copy_(stage[k][:hi - lo], non_blocking=True)
                 done[k] = torch.cuda.Event()

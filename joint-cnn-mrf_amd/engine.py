@@ -117,6 +117,13 @@ class Engine:
             raise ValueError('%s must be contiguous (NHWC)' % name)
         return t
 
+    def _chk_img(self, t, name):
+        """An image tensor [.,H,W,3]: float32, or uint8 (byte k is float32(k) / float32(255)) -> True for bytes.  Every other
+        dtype is refused as _chk refuses it."""
+        u8 = isinstance(t, torch.Tensor) and t.dtype == torch.uint8
+        self._chk(t, 4, name, torch.uint8 if u8 else torch.float32)
+        return u8
+
     def _new(self, *shape, dtype=torch.float32):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
@@ -166,13 +173,16 @@ class Engine:
         return out
 
     def model(self, x):
-        """main.py:29-74: [B,H,W,3] -> logits [B,H/8,W/8,K]."""
-        self._chk(x, 4, 'x')
+        """main.py:29-74: [B,H,W,3] (float32 or uint8) -> logits [B,H/8,W/8,K]."""
+        u8 = self._chk_img(x, 'x')
         B, H, W, C = x.shape
         if C != 3:
             raise ValueError('x must be [B,H,W,3], got %s' % (tuple(x.shape),))
         out = self._new(B, _hm_size(H), _hm_size(W), self.n_joints)
-        _lib.check(self._lib.jcm_pd_forward(self._h, self._p(x), B, H, W, self._p(out)), 'jcm_pd_forward')
+        if u8:
+            _lib.check(self._lib.jcm_pd_forward_u8(self._h, self._p(x), B, H, W, self._p(out)), 'jcm_pd_forward_u8')
+        else:
+            _lib.check(self._lib.jcm_pd_forward(self._h, self._p(x), B, H, W, self._p(out)), 'jcm_pd_forward')
         return out
 
     def spatial_softmax(self, hm):
@@ -223,8 +233,9 @@ class Engine:
 
     def forward(self, x, torso=None, use_sm=True, want_prob=True):
         """The tower of main.py:522-531 in one C call.  Returns a dict with 'pd_coords',
-        'sm_coords' (int32 [B,2,K]) and, if want_prob, 'pd_prob' / 'sm_prob' [B,60,90,K]."""
-        self._chk(x, 4, 'x')
+        'sm_coords' (int32 [B,2,K]) and, if want_prob, 'pd_prob' / 'sm_prob' [B,60,90,K].  x: float32, or uint8 (byte k standing for
+        float32(k) / float32(255): the same bits out as for that float image, a quarter of the bytes in)."""
+        u8 = self._chk_img(x, 'x')
         B, H, W, C = x.shape
         if C != 3:
             raise ValueError('x must be [B,H,W,3]')
@@ -242,16 +253,17 @@ class Engine:
             r['sm_coords'] = self._new(B, 2, K, dtype=torch.int32)
             if want_prob:
                 r['sm_prob'] = self._new(B, hh, ww, K)
-        _lib.check(self._lib.jcm_forward(self._h, self._p(x), self._p(torso if use_sm else None), B, H, W, int(bool(use_sm)),
-                                         self._p(r.get('pd_prob')), self._p(r.get('sm_prob')),
-                                         self._p(r['pd_coords']), self._p(r.get('sm_coords'))), 'jcm_forward')
+        fn, what = (self._lib.jcm_forward_u8, 'jcm_forward_u8') if u8 else (self._lib.jcm_forward, 'jcm_forward')
+        _lib.check(fn(self._h, self._p(x), self._p(torso if use_sm else None), B, H, W, int(bool(use_sm)),
+                      self._p(r.get('pd_prob')), self._p(r.get('sm_prob')),
+                      self._p(r['pd_coords']), self._p(r.get('sm_coords'))), what)
         return r
 
     def eval_forward(self, x, y, use_sm=True, want_prob=True):
         """The tower in inference mode plus the two cross-entropy losses of the graph (main.py:538-539), as eval_error
         runs it per batch (main.py:275-283).  y = y_in [B,60,90,K+1]: targets + torso channel.  Returns the dict of
-        forward() plus 'losses' (device fp32 [2]: loss_pd, loss_sm)."""
-        self._chk(x, 4, 'x')
+        forward() plus 'losses' (device fp32 [2]: loss_pd, loss_sm).  x: float32 or uint8, as for forward()."""
+        u8 = self._chk_img(x, 'x')
         self._chk(y, 4, 'y')
         B, H, W, C = x.shape
         hh, ww, K = _hm_size(H), _hm_size(W), self.n_joints
@@ -264,9 +276,10 @@ class Engine:
             r['sm_coords'] = self._new(B, 2, K, dtype=torch.int32)
             if want_prob:
                 r['sm_prob'] = self._new(B, hh, ww, K)
-        _lib.check(self._lib.jcm_eval_forward(self._h, self._p(x), self._p(y), B, H, W, int(bool(use_sm)),
-                                              self._p(r.get('pd_prob')), self._p(r.get('sm_prob')), self._p(r['pd_coords']),
-                                              self._p(r.get('sm_coords')), self._p(r['losses'])), 'jcm_eval_forward')
+        fn, what = (self._lib.jcm_eval_forward_u8, 'jcm_eval_forward_u8') if u8 else (self._lib.jcm_eval_forward, 'jcm_eval_forward')
+        _lib.check(fn(self._h, self._p(x), self._p(y), B, H, W, int(bool(use_sm)),
+                      self._p(r.get('pd_prob')), self._p(r.get('sm_prob')), self._p(r['pd_coords']),
+                      self._p(r.get('sm_coords')), self._p(r['losses'])), what)
         return r
 
     def window_resize(self, src, windows, oh, ow):
@@ -320,8 +333,8 @@ class Engine:
     # ------------------------------------------------------------------ batches from a device-resident data set (dataset.py)
     def _chk_indexed(self, who, x_all, y_all, idx, params, x_out, y_out):
         """Shared checks of gather_batch / augment_train_indexed -> (host int32 indices, x_out, y_out).  The index RANGE is checked by the
-        entry point itself (on the host, before any launch)."""
-        self._chk(x_all, 4, 'x_all')
+        entry point itself (on the host, before any launch).  x_all: float32, or uint8 (a byte data set; the outputs are float32 either way)."""
+        self._chk_img(x_all, 'x_all')
         self._chk(y_all, 4, 'y_all')
         N, H, W, C = x_all.shape
         if C != 3 or y_all.shape[0] != N or y_all.shape[3] != self.n_joints + 1 or N < 1:
@@ -352,21 +365,25 @@ class Engine:
 
     def gather_batch(self, x_all, y_all, idx, x_out=None, y_out=None):
         """x_out[b] = x_all[idx[b]], y_out[b] = y_all[idx[b]] (bit for bit): x_all [N,H,W,3], y_all [N,h,w,K+1] device fp32, idx HOST integers
-        [B] in [0, N) (repeats allowed) -> (x_out, y_out), new tensors unless given.  Enqueued on the engine's stream; the host does not wait."""
+        [B] in [0, N) (repeats allowed) -> (x_out, y_out), new tensors unless given.  Enqueued on the engine's stream; the host does not wait.
+        x_all may be uint8: x_out[b] = float32(x_all[idx[b]]) / float32(255), correctly rounded (fp32, as always)."""
         idx, x_out, y_out = self._chk_indexed('gather_batch', x_all, y_all, idx, None, x_out, y_out)
         N, H, W, _ = x_all.shape
-        _lib.check(self._lib.jcm_gather_batch(self._h, self._p(x_all), self._p(y_all), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.shape[0],
-                                              H, W, y_all.shape[1], y_all.shape[2], self._p(x_out), self._p(y_out)), 'jcm_gather_batch')
+        fn, what = (self._lib.jcm_gather_batch_u8, 'jcm_gather_batch_u8') if x_all.dtype == torch.uint8 else (self._lib.jcm_gather_batch, 'jcm_gather_batch')
+        _lib.check(fn(self._h, self._p(x_all), self._p(y_all), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.shape[0],
+                      H, W, y_all.shape[1], y_all.shape[2], self._p(x_out), self._p(y_out)), what)
         return x_out, y_out
 
     def augment_train_indexed(self, x_all, y_all, idx, params, x_out=None, y_out=None):
         """augment_train of the images idx[b] of the data set (x_all, y_all) with params[b], read through the index: the same bits as
-        gather_batch followed by augment_train, without the gathered copy."""
+        gather_batch followed by augment_train, without the gathered copy.  x_all may be uint8 (a byte data set): the same bits as from the
+        float data set float32(x_all) / float32(255)."""
         idx, x_out, y_out = self._chk_indexed('augment_train_indexed', x_all, y_all, idx, params, x_out, y_out)
         N, H, W, _ = x_all.shape
-        _lib.check(self._lib.jcm_augment_train_indexed(self._h, self._p(x_all), self._p(y_all), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                       self._p(params), idx.shape[0], H, W, y_all.shape[1], y_all.shape[2], self._p(x_out), self._p(y_out)),
-                   'jcm_augment_train_indexed')
+        fn, what = ((self._lib.jcm_augment_train_indexed_u8, 'jcm_augment_train_indexed_u8') if x_all.dtype == torch.uint8
+                    else (self._lib.jcm_augment_train_indexed, 'jcm_augment_train_indexed'))
+        _lib.check(fn(self._h, self._p(x_all), self._p(y_all), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                      self._p(params), idx.shape[0], H, W, y_all.shape[1], y_all.shape[2], self._p(x_out), self._p(y_out)), what)
         return x_out, y_out
 
     # ------------------------------------------------------------------ TensorBoard summaries (summary.py, DESIGN.md 4.8)

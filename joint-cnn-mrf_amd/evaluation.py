@@ -40,7 +40,7 @@ def get_next_batch(X, Y, batch_size, shuffle=False, rng=None):
 
 def eval_error(X_np, Y_np, engine, batch_size, use_sm=True, joints=(2,), det_radius=10):
     """main.py:275-283: run a data set through the tower in inference mode batch by batch and return the means over
-    batches of (loss_pd, loss_sm, det_rate_pd, det_rate_sm).  X_np [N,480,720,3], Y_np [N,60,90,10] (numpy or torch,
+    batches of (loss_pd, loss_sm, det_rate_pd, det_rate_sm).  X_np [N,480,720,3] (float, or uint8 byte images), Y_np [N,60,90,10] (numpy or torch,
     host or device); the remainder N % batch_size is dropped as in the reference (get_next_batch).  Everything stays on
     the device until the four means are read back."""
     n_batches = len(X_np) // batch_size
@@ -49,7 +49,9 @@ def eval_error(X_np, Y_np, engine, batch_size, use_sm=True, joints=(2,), det_rad
     K = engine.n_joints
     acc = torch.zeros(4, dtype=torch.float64, device=engine.device)
     for bx, by in get_next_batch(X_np, Y_np, batch_size):
-        x = torch.as_tensor(bx, dtype=torch.float32, device=engine.device).contiguous()
+        bx = torch.as_tensor(bx)
+        # byte images (a uint8 DeviceDataset, --u8_images) go to the byte entry as they are; everything else is widened to fp32 as before
+        x = bx.to(device=engine.device, dtype=torch.uint8 if bx.dtype == torch.uint8 else torch.float32).contiguous()
         y = torch.as_tensor(by, dtype=torch.float32, device=engine.device).contiguous()
         r = engine.eval_forward(x, y, use_sm=use_sm, want_prob=False)
         true = engine.argmax_coords(y[..., :K].contiguous())

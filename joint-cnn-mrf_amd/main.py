@@ -72,6 +72,9 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
+    parser.add_argument('--u8_images', action='store_true', help='hold and move the images as the bytes they were made from (DESIGN.md 4.10; same results bit for '
+                        'bit): the evaluation run streams byte batches from pinned memory (single scale; --multiscale is unchanged), --train needs '
+                        '--device_data and keeps the sets as uint8 on the device.')
     parser.add_argument('--tb_dir', default=None, help='write TensorBoard summaries to DIR/<model_name>/{train,test} (main.py:448-450; off by default).')
     parser.add_argument('--tb_log_iters', action='store_true', help='with --tb_dir: histograms and scalars after every step to DIR/<model_name>/train_iter '
                         '(tb_log_iters, main.py:452,642-645).')
@@ -247,6 +250,15 @@ def _synthetic_dataset(n_train, n_test):
             synth.make_images(n_test, seed=300), synth.make_targets(n_test, seed=400))
 
 
+def byte_grid(x):
+    """--synthetic --u8_images: generated float images put on the byte grid, byte k = floor(x * 256) (255 at x = 1) standing for k / 255."""
+    return np.minimum(np.floor(np.asarray(x, np.float32) * np.float32(256)), np.float32(255)).astype(np.uint8)
+
+
+U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
+                              'host-fed training steps take float batches')
+
+
 def initial_params(args, pairwise_distr):
     """tf.global_variables_initializer on the graph of main.py:474-487: He-initialised convolutions, identity BatchNorm,
     energies = the pairwise distributions, biases = 1e-5."""
@@ -353,7 +365,9 @@ def tb_batch(x, y, batch_size):
     """The summary batch (main.py:470-471,621-626): batch_size images from image 450, or the first batch_size when the split is
     shorter."""
     lo = IMG_TB_FROM if x.shape[0] >= IMG_TB_FROM + batch_size else 0
-    return np.ascontiguousarray(x[lo:lo + batch_size], np.float32), np.ascontiguousarray(y[lo:lo + batch_size], np.float32)
+    bx = np.asarray(x[lo:lo + batch_size])
+    bx = bx.astype(np.float32) / np.float32(255) if bx.dtype == np.uint8 else bx      # (byte images: the floats they stand for)
+    return np.ascontiguousarray(bx, np.float32), np.ascontiguousarray(y[lo:lo + batch_size], np.float32)
 
 
 def tb_open(args, model_name):
@@ -388,6 +402,8 @@ def train_main(args):
     t_start = time.time()
     if args.synthetic:
         x_train, y_train, x_test, y_test = _synthetic_dataset(args.synthetic_size, max(args.batch_size, args.synthetic_size // 2))
+        if args.u8_images:
+            x_train, x_test = byte_grid(x_train), byte_grid(x_test)
         pairwise = synth.synthetic_priors()
     else:
         x_train, y_train, x_test, y_test = get_dataset(args.data_dir)
@@ -419,8 +435,12 @@ def train_main(args):
         from .dataset import DeviceDataset
         # room the engines have not claimed yet: a full-width fp32 engine's filter-spectra cache and workspace grow to 64 GB on first use
         reserve = len(towers.engines) * ((2 << 30) if args.debug else (64 << 30))
-        ds_test = DeviceDataset(x_test, y_test, device=eng.device, reserve_bytes=reserve)
-        ds_train = DeviceDataset.for_towers(towers, x_train, y_train, reserve_bytes=reserve)
+        kind = 'uint8' if args.u8_images else 'float32'     # uint8: float files are converted chunk by chunk, the round trip checked (NotByteExact)
+        ds_test = DeviceDataset(x_test, y_test, device=eng.device, reserve_bytes=reserve, image_dtype=kind)
+        ds_train = DeviceDataset.for_towers(towers, x_train, y_train, reserve_bytes=reserve, image_dtype=kind)
+        if args.u8_images:
+            for name, d in [('test', ds_test)] + [('train', d) for d in ds_train.values()]:
+                print('device data (%s, images as uint8): %d bytes held on %s, uploaded in %.2f s' % (name, d.nbytes, d.device, d.upload_seconds), flush=True)
         ev_train, ev_test = (ds_train[eng.device].x, ds_train[eng.device].y), (ds_test.x, ds_test.y)
 
     def report(epoch):
@@ -468,6 +488,8 @@ def main(argv=None):
     hps = args
     if args.restore and not args.restore_path:
         raise SystemExit('--restore needs --restore_path <checkpoint prefix or .npz> (the reference hard-codes best_model_name, main.py:443)')
+    if args.train and args.u8_images and not args.device_data:
+        raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
     for g in args.gpus:
         if g < 0 or g >= torch.cuda.device_count():
             raise SystemExit('--gpus %s: device %d does not exist (%d visible)' % (args.gpus, g, torch.cuda.device_count()))
@@ -479,10 +501,13 @@ def main(argv=None):
     from .dist import Towers
     if args.synthetic:
         x_train, y_train, x_test, y_test = _synthetic_dataset(args.batch_size, args.synthetic_size)
+        if args.u8_images and not args.multiscale:
+            x_test = byte_grid(x_test)
         pairwise = synth.synthetic_priors()
     else:
         x_train, y_train, x_test, y_test = get_dataset(args.data_dir)
         pairwise = get_pairwise_distr(args.data_dir)
+    fed = None              # --u8_images: what the single-scale run moved to the devices
     state = restore_params(args.restore_path, args) if args.restore else None
     params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)} if state else initial_params(args, pairwise)
 
@@ -502,6 +527,8 @@ def main(argv=None):
     towers = None
     t0 = time.time()
     if args.multiscale:
+        if args.u8_images:
+            print('--u8_images: the multi-scale wrapper resizes float windows and is unchanged; the images stay float32', file=sys.stderr)
         if len(args.gpus) > 1:
             print('--multiscale evaluates on device %d only; the other --gpus entries are not used' % args.gpus[0], file=sys.stderr)
         configure(params, device=args.gpus[0], precision=args.precision, debug=args.debug)
@@ -513,11 +540,26 @@ def main(argv=None):
         eval_tb(towers.engines[0])
         B = args.batch_size
         pd, sm = [], []
-        for lo in range(0, (x_test.shape[0] // B) * B, B):
-            r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
-                               use_sm=args.use_sm)
-            pd.append(r['pd_coords'])
-            sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
+        if args.u8_images:      # the test images as bytes (converted once, the round trip checked), streamed from pinned memory
+            from .dataset import to_u8_exact
+            from .stream import ForwardStream
+            xb = to_u8_exact(x_test)      # (works through a memory-mapped file in slices; float64 or other data is refused)
+            tb = np.ascontiguousarray(y_test[:, :, :, n_joints:], np.float32)
+            fss = [ForwardStream(e, use_sm=args.use_sm) for e in towers.engines]
+
+            def feed(lo, hi):      # one tower's slice of every whole batch (Towers.slices: the remainder B % n_gpus is dropped)
+                for b0 in range(0, (xb.shape[0] // B) * B, B):
+                    yield xb[b0 + lo:b0 + hi], tb[b0 + lo:b0 + hi]
+            for parts in zip(*[fs.run(feed(lo, hi)) for fs, (lo, hi) in zip(fss, towers.slices(B))]):
+                pd.append(torch.from_numpy(np.concatenate([p['pd_coords'] for p in parts])))
+                sm.append(torch.from_numpy(np.concatenate([p['sm_coords' if args.use_sm else 'pd_coords'] for p in parts])))
+            fed = {'image_dtype': 'uint8', 'bytes_uploaded': int(sum(fs.bytes_uploaded for fs in fss))}
+        else:
+            for lo in range(0, (x_test.shape[0] // B) * B, B):
+                r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
+                                   use_sm=args.use_sm)
+                pd.append(r['pd_coords'])
+                sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
         to_ref = lambda c: torch.cat(c).permute(1, 2, 0).cpu().numpy()      # [2,K,N] (row, col) stacked on the last axis, main.py:425
         pred_pd, pred_sm = to_ref(pd), to_ref(sm)
     torch.cuda.synchronize()
@@ -526,9 +568,12 @@ def main(argv=None):
         import scipy.io
         os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
         scipy.io.savemat(args.predictions, {'flic_pred_pd': pred_pd, 'flic_pred_sm': pred_sm})         # main.py:675
-    print(json.dumps({'n_images': int(pred_pd.shape[2]), 'gpus': args.gpus, 'use_sm': bool(args.use_sm), 'debug': bool(args.debug),
-                      'multiscale': bool(args.multiscale), 'seconds': dt, 'images_per_sec': pred_pd.shape[2] / dt,
-                      'coords_image0_pd': pred_pd[:, :, 0].tolist()}))
+    line = {'n_images': int(pred_pd.shape[2]), 'gpus': args.gpus, 'use_sm': bool(args.use_sm), 'debug': bool(args.debug),
+            'multiscale': bool(args.multiscale), 'seconds': dt, 'images_per_sec': pred_pd.shape[2] / dt,
+            'coords_image0_pd': pred_pd[:, :, 0].tolist()}
+    if fed is not None:
+        line.update(fed)
+    print(json.dumps(line))
     if towers is not None:
         towers.close()
 
