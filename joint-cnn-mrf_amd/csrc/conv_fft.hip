@@ -384,15 +384,12 @@ bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMer
 // a.wp = the split filter spectra of THIS map size and kernel size; `work` = conv_fft_workspace_bytes(a, ks, np) bytes.  g0 / g1: optional
 // events recorded around the GEMM (the dominant kernel of the layer) for the roofline record.
 // in_layout / out_layout: 0 = fp32 NHWC, 1 = bf16 NHWC, 2 = bf16 planar
-// t_in (fp32 handles): the row-transformed input left by the previous layer's fused kernel -- the forward row pass is skipped;
-// t_next: write the NEXT layer's row-transformed input there instead of the spatial output (conv_fft_fusable() says when that is legal).
-// xs (optional): where the split activation spectra of the layer's input live instead of the scratch -- the training step keeps them for the
-// weight gradient (wgrad_fft.hip); xs_ready: they are there already (the data gradient after the weight gradient of the same layer): the
-// forward transforms are skipped.
+// link: what ties the layer to its neighbours (FftLink, kernels.h); the checks below say which combinations exist.
 // The tiled layer (a0.tiles): rows forward from the map into the 4 B tiles, columns, GEMM and inverse columns of the tiles' transform, then the pool
 // hand-over that stitches the tiles back together.  sc->tmax: 4 B words (one per tile: the GEMM row), sc->tmax_next: B words (one per image).
-static hipError_t conv_fft_tiles_f32(const ConvArgs& a0, int ks, int np, int in_layout, void* work, const void* t_in, void* t_next, const FftMerge* merge,
-                                     hipEvent_t g0, hipEvent_t g1, hipStream_t st, void* xs, bool xs_ready, const Fp16Scale* scp, const FftNext* nx) {
+static hipError_t conv_fft_tiles_f32(const ConvArgs& a0, int ks, int np, int in_layout, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
+                                     const Fp16Scale* scp) {
+  const void* t_in = link.t_in; void* t_next = link.t_next; const FftMerge* merge = link.merge; void* xs = link.xs; const bool xs_ready = link.xs_ready; const FftNext* nx = &link.next;
   Sizes s;
   if (np != 4 || in_layout != 0 || t_in || merge || xs || xs_ready || !t_next || !nx || !nx->pool || nx->merge || !scp || !scp->tmax || !scp->winv || !scp->tmax_next ||
       !conv_fft_tiles_supported(a0, ks, nx->ks_next) || !sizes_of(a0.H / 2, a0.W / 2, ks, &s))
@@ -424,9 +421,10 @@ static hipError_t conv_fft_tiles_f32(const ConvArgs& a0, int ks, int np, int in_
   if (!cfft_rows_inv_pool_tile_reg(s.NY, s.NX, a, T, static_cast<cf*>(t_next), 1.0f / (float)(s.NY * s.NX), sc, st)) return hipErrorInvalidValue;
   return hipGetLastError();
 }
-hipError_t conv_fft_f32(const ConvArgs& a0, int ks, int np, int in_layout, int out_layout, void* work, const void* t_in, void* t_next, const FftMerge* merge,
-                        hipEvent_t g0, hipEvent_t g1, hipStream_t st, void* xs, bool xs_ready, const Fp16Scale* scp, const FftNext* nx) {
-  if (a0.tiles) return conv_fft_tiles_f32(a0, ks, np, in_layout, work, t_in, t_next, merge, g0, g1, st, xs, xs_ready, scp, nx);
+hipError_t conv_fft_f32(const ConvArgs& a0, int ks, int np, int in_layout, int out_layout, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
+                        const Fp16Scale* scp) {
+  if (a0.tiles) return conv_fft_tiles_f32(a0, ks, np, in_layout, work, link, g0, g1, st, scp);
+  const void* t_in = link.t_in; void* t_next = link.t_next; const FftMerge* merge = link.merge; void* xs = link.xs; const bool xs_ready = link.xs_ready; const FftNext* nx = &link.next;
   Sizes s;
   if (!conv_fft_supported(a0, ks) || !sizes_of(a0.H, a0.W, ks, &s, a0.circ) || (out_layout == 2 && a0.Cout % 8) || (np != 2 && np != 4 && np != 5) || (np == 5 && a0.Cin % 32)) return hipErrorInvalidValue;
   if (a0.circ && (t_in || t_next || merge || in_layout != 0 || out_layout != 0)) return hipErrorInvalidValue;      // windows: fp32 NHWC in and out, nothing fused

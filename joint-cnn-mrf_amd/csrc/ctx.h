@@ -83,16 +83,29 @@ struct jcm_ctx {
   hipStream_t stream = nullptr;
   int precision = JCM_PRECISION_F32;
   int K = 9;
-  int f32_conv = 0;             // fp32 handles: 0 = default (frequency domain, or the exact fp32 MFMA chain with conv9_fft = 0), 2 = the direct fp16x3 split kernels (forward and gradients)
-  float* act_scale = nullptr;   // fp16x3: device {S, 1/S} of the current layer input (computed before every launch), + scratch
-  float* scale_scratch = nullptr;
-  int split_min_wgs = 128;      // grids smaller than this keep the exact kernel (option "split_min_wgs")
   bool finalized = false;
+  // ---- options (jcm_set_option) ----
+  int f32_conv = 0;             // fp32 handles: 0 = default (frequency domain, or the exact fp32 MFMA chain with conv9_fft = 0), 2 = the direct fp16x3 split kernels (forward and gradients)
+  int split_min_wgs = 128;      // grids smaller than this keep the exact kernel (option "split_min_wgs")
+  int sm_algo = 3;              // 3 = every transform in LDS (sm_fused.hip), 1 = direct sliding-window VALU kernel (the cross-check)
+  int conv9_fft = 1;            // fp32 handles: wide 9x9 layers in the frequency domain (conv_fft.hip) when the shape allows; 0 = fp32 MFMA chain
+  int fft_tiles = 1;            // fp32 handles, the pool hand-over of conv2_fullres: 2 x 2 tiles of the 120 x 180 map in the 60 x 90 maps' transform (ConvArgs::tiles)
+  int fft_fuse = 3;             // fp32 handles, jcm_pd_forward: bit 0 = conv2 -> max pool -> conv3, bit 1 = conv4_fullres -> branch merge -> conv5 handed over in row-transformed form (conv_fft_rows_fused.hip)
+  int fft_single = 1;           // bf16 handles: the channel GEMM on ONE scaled fp16 part per operand (np = 5; 0 = two bf16 parts, three products)
+  int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)
+  int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (ConvArgs::rows_mfma; conv_fft_rows_mfma.hip)
+  int fft_win = 1;              // training step of fp32 handles: frequency-domain layers on 32 x 32 overlap-save windows where that shrinks the filter-sized spectra (jcm_train.hip)
+  int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel
+  int sm_chunk = 32;            // training step: images per slice of the spatial model's backward pass (81 + 10 spectra per image live at once)
+  int micro_batch = 0;          // jcm_forward walks a batch in slices of this many images (0 = 256 bf16 / 64 fp32)
+  int call_order = 1;           // 0: this handle's calls are not ordered against other handles' (debugging only)
+  int debug_skip = 0;           // bisecting aid (jcm_pd_forward): bit 0 conv1(+pool1), 1 pool2, 2 conv2, 3 conv3, 4 conv4, 5 merge + conv5, 6 conv6 are NOT launched
+  // ---- parameters and what is derived from them (refresh_derived) ----
   std::map<std::string, jcm::Tensor> params;
   std::map<std::string, jcm::ConvLayer> convs;
   std::vector<void*> owned;   // device allocations made at finalize
-  // spatial model tables
-  bool has_sm = false;
+  size_t param_bytes = 0;
+  bool has_sm = false;          // spatial model tables
   float* sp_energy = nullptr;   // [P][120*180]
   float* sp_bias = nullptr;     // [P][5400]
   float* bn_sm_scale = nullptr; // [10]
@@ -101,31 +114,20 @@ struct jcm_ctx {
   const float** energy_ptrs = nullptr;   // [P] device table of the energy_* / bias_* parameter tensors, graph order
   const float** bias_ptrs = nullptr;
   int* cond0 = nullptr;         // single zero (jcm_conv_mrf)
-  int sm_algo = 3;              // 3 = every transform in LDS (sm_fused.hip), 1 = direct sliding-window VALU kernel (the cross-check)
-  // transient, set by jcm_pd_forward around two consecutive frequency-domain layers: the first writes the second's row-transformed input
-  void* fft_t_next = nullptr;
-  const void* fft_t_in = nullptr;
-  void* fft_xs = nullptr;            // transient: the next frequency-domain layer keeps its split input spectra here (training step: the weight gradient reads them)
-  bool fft_xs_ready = false;         // ... they are there already (data gradient after the weight gradient of the same layer): skip the forward transforms
+  float2* prior_spec_t = nullptr; // [P][91][120]: transposed half spectra of softplus5(energy) (sm_lds.hip)
+  struct FftW { void* p = nullptr; size_t bytes = 0; bool valid = false; float* wscale = nullptr; };      // wscale: two device floats behind the spectra (np = 4)
+  std::map<std::string, FftW> fft_w;   // filter spectra per "<scope>@HxW", computed on first use, invalidated by refresh_derived
+  double* hist_limits = nullptr;      // summary.hip: the positive half of TF's histogram bucket limits (uploaded on first use)
+  jcm::TrainState* train = nullptr;   // created by jcm_train_begin
+  // ---- workspace ----
+  // arena (stack allocator, grown on demand between forwards)
+  char* arena = nullptr;
+  size_t arena_cap = 0, arena_off = 0, arena_peak = 0;
+  bool dry = false;             // sizing pass: allocate offsets only, launch nothing
+  float* act_scale = nullptr;   // fp16x3: device {S, 1/S} of the current layer input (computed before every launch), + scratch
+  float* scale_scratch = nullptr;
   void* sm_scratch = nullptr;   // sm_fused.hip: partial sums + flags of sm_inv_finish_kernel's cuts (sm_fused_scratch_bytes(), zeroed once)
   unsigned sm_epoch = 0;        // ... the launch counter its flags carry
-  int fft_tiles = 1;            // fp32 handles, the pool hand-over of conv2_fullres: 2 x 2 tiles of the 120 x 180 map in the 60 x 90 maps' transform (ConvArgs::tiles)
-  int fft_fuse = 3;             // fp32 handles, jcm_pd_forward: bit 0 = conv2 -> max pool -> conv3, bit 1 = conv4_fullres -> branch merge -> conv5 handed over in row-transformed form (conv_fft_rows_fused.hip)
-  int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel
-  int conv_hpool = 0;           // transient: the next direct bf16 convolution launch takes the half pool
-  int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (ConvArgs::rows_mfma; conv_fft_rows_mfma.hip)
-  int fft_next_pool = 0, fft_next_ks = 0;      // transient, with fft_t_next: a 2x2 max pool lies between this layer and the one fft_t_next is for (kernel size fft_next_ks)
-  // transient: the next frequency-domain layer's input windows are cut from this map by its forward row pass (ConvArgs::win_map; jcm_train.hip)
-  const void* fft_win_map = nullptr;
-  int fft_win_B = 0, fft_win_H = 0, fft_win_W = 0, fft_win_TY = 0, fft_win_TX = 0;
-  bool fft_win_scatter = false;      // ... and its inverse row pass stores the valid regions into the map `out` (same geometry; ConvArgs::wout_*)
-  bool fft_t_in_16 = false;                     // transient, with fft_t_in (bf16 handles): the handed-over T is complex fp16 + its scale words (conv4_fullres -> conv5)
-  const void* fft_next_merge = nullptr;        // transient, with fft_t_next: const jcm::FftMerge* -- fft_t_next is the row-transformed MERGED map (this layer = the full-resolution branch)
-  const void* fft_merge = nullptr;   // const jcm::FftMerge*: the next frequency-domain layer forms the merged map itself (jcm_pd_forward, conv5)
-  int conv9_fft = 1;            // fp32 handles: wide 9x9 layers in the frequency domain (conv_fft.hip) when the shape allows; 0 = fp32 MFMA chain
-  int fft_single = 1;           // bf16 handles: the channel GEMM on ONE scaled fp16 part per operand (np = 5; 0 = two bf16 parts, three products)
-  int fft_win = 1;              // training step of fp32 handles: frequency-domain layers on 32 x 32 overlap-save windows where that shrinks the filter-sized spectra (jcm_train.hip)
-  int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)
   // device words of the fp16 scaling (kernels.h: Fp16Scale): zeroed floats, one per image of every row-transformed tensor of a call.  They come from
   // blocks of kFftWords floats; a call that needs more than a block holds (a forward of > 20 000 images in one piece) gets further blocks on demand,
   // and the blocks are re-zeroed and reused from the start BETWEEN calls (CallOrder), in stream order behind every kernel that read the old words.
@@ -133,27 +135,12 @@ struct jcm_ctx {
   struct WordBlock { float* p = nullptr; int cap = 0; };
   std::vector<WordBlock> fft_blocks;
   int fft_block_i = 0, fft_word_i = 0;      // next free word: fft_blocks[fft_block_i].p + fft_word_i
-  int call_order = 1;               // 0: this handle's calls are not ordered against other handles' (debugging only)
-  int debug_skip = 0;               // bisecting aid (jcm_pd_forward): bit 0 conv1(+pool1), 1 pool2, 2 conv2, 3 conv3, 4 conv4, 5 merge + conv5, 6 conv6 are NOT launched
-  float* fft_tmax_in = nullptr;     // transient: the word of the next frequency-domain layer's input (set with fft_t_in / fft_xs_ready by whoever produced that tensor)
-  float* fft_last_tmax = nullptr;   // the word the last frequency-domain layer's input used (the training step keeps it with the kept spectra)
-  struct FftW { void* p = nullptr; size_t bytes = 0; bool valid = false; float* wscale = nullptr; };      // wscale: two device floats behind the spectra (np = 4)
-  std::map<std::string, FftW> fft_w;   // filter spectra per "<scope>@HxW", computed on first use, invalidated by refresh_derived
-  int sm_chunk = 32;            // training step: images per slice of the spatial model's backward pass (81 + 10 spectra per image live at once)
-  int micro_batch = 0;          // jcm_forward walks a batch in slices of this many images (0 = 256 bf16 / 64 fp32)
-  float2* prior_spec_t = nullptr; // [P][91][120]: transposed half spectra of softplus5(energy) (sm_lds.hip)
-  // workspace arena (stack allocator, grown on demand between forwards)
-  char* arena = nullptr;
-  size_t arena_cap = 0, arena_off = 0, arena_peak = 0;
-  bool dry = false;             // sizing pass: allocate offsets only, launch nothing
-  size_t param_bytes = 0;
   // per-layer HIP-event timing on the launch stream (bench.py roofline object)
   bool profile = false;
   std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
   std::vector<hipEvent_t> event_pool;   // recycled by jcm_profile_read / "profile"=0, destroyed by jcm_destroy
-  jcm::TrainState* train = nullptr;   // created by jcm_train_begin
-  double* hist_limits = nullptr;      // summary.hip: the positive half of TF's histogram bucket limits (uploaded on first use)
-  std::mutex call_mu;                 // held by the thread whose outermost entry point of this handle is running (CallOrder)
+  // ---- call ordering (CallOrder) ----
+  std::mutex call_mu;                 // held by the thread whose outermost entry point of this handle is running
   int call_depth = 0;                 // entry points of this handle on that thread's stack (> 1 only inside a gradient-ready callback)
   jcm::CallOrder* order = nullptr;    // the outermost running entry point's chain guard (notify_ready suspends it around the user callback)
 };
@@ -181,10 +168,10 @@ struct DeviceGuard {
 // kernel then consumes -- found by tests/test_gpu_golden.py::test_two_engines_two_streams_soak.  The known over-reads are fixed at the
 // source; this ordering is the guarantee that does not depend on having found them all.  jcm_set_option("call_order", 0) takes a handle
 // out of the chain (it neither waits nor records; tools/determinism.py and the soak tests use it to look for what the chain would hide).
-// The constructor also clears the transient hand-over fields an aborted call may have left behind and laps the fp16 scale-word ring.
+// The outermost call's constructor also laps the fp16 scale-word ring (a nested call keeps handing out words behind the outer call's).
 // The lock is NOT held while the host blocks or while user code runs: release() (record the chain event, unlock) precedes every
 // host-side wait at the end of an entry point, and the gradient-ready callback of jcm_train_loss_grads runs between release() and acquire(),
-// so a callback may call jcm_* entry points (a nested call on the SAME handle keeps the outer call's transient state: `nested`).
+// so a callback may call jcm_* entry points (also of the SAME handle: `nested`).
 struct CallOrder {
   jcm_ctx* c;
   std::unique_lock<std::mutex> lk;       // the device's call chain
@@ -224,15 +211,17 @@ void prof_end(jcm_ctx* c, const std::string& scope, hipEvent_t e0, hipEvent_t e1
 void prof_release_all(jcm_ctx* c, bool destroy);
 // frequency-domain route (jcm_api.hip): takes_fft() says whether a layer / shape goes there; run_conv_fft() runs it (filter spectra cached in
 // c->fft_w under "<scope>@HxW", packed from L->w_raw when missing or invalidated); the training step uses both for its data gradient.
+// link (kernels.h: FftLink): what ties the call to the neighbouring frequency-domain layers -- requests read from it, the two scale-word results written to it;
+// null = the layer stands alone.  A non-empty link, or hpool (ConvArgs::hpool), for a layer that does not take the route it is meant for is JCM_ERR_STATE.
 bool takes_fft(jcm_ctx* c, const ConvLayer* L, int B, int H, int W);
 bool fft_spectra_valid(jcm_ctx* c, const std::string& scope, int H, int W, int circ = 0);
 // operand form of the channel GEMM on this handle (kernels.h): bf16 handles: 5 (one scaled fp16 part, default) or 2 (two bf16 parts); fp32 handles: 4 (two scaled fp16 parts)
 inline int fft_np(const jcm_ctx* c) { return c->precision == JCM_PRECISION_BF16 ? (c->fft_single ? 5 : 2) : 4; }
 int fft_new_words(jcm_ctx* c, int n, float** w);      // n zeroed device words of the scaling ring (one per image)
 // circ: x is a batch of overlap-save windows [B, H, W, Cin] that fill the transform, out their valid regions [B, H - 8, W - 8, Cout] (ConvArgs::circ)
-int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ = 0);
+int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ = 0, FftLink* link = nullptr);
 int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub,
-                   void* out, bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false);   // bf16 layouts: ConvArgs in kernels.h; x_u8: the stride-2 layer reads a byte image
+                   void* out, bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false, FftLink* link = nullptr, int hpool = 0);   // bf16 layouts: ConvArgs in kernels.h; x_u8: the stride-2 layer reads a byte image
 
 inline int cdiv2(int v) { return (v + 1) / 2; }
 

@@ -45,11 +45,8 @@ CallOrder::CallOrder(jcm_ctx* ctx) : c(ctx) {
   }
   ++c->call_depth;                   // (only ever touched by the thread that holds call_mu)
   acquire();
-  if (nested) return;                // the outer call's hand-over fields and scale words stay as they are
+  if (nested) return;                // the outer call's scale words stay as they are
   c->order = this;
-  // what an aborted call may have left behind
-  c->fft_t_in = nullptr; c->fft_t_next = nullptr; c->fft_merge = nullptr; c->fft_xs = nullptr; c->fft_xs_ready = false; c->fft_tmax_in = nullptr;
-  c->fft_next_pool = 0; c->fft_next_ks = 0; c->fft_next_merge = nullptr; c->fft_t_in_16 = false; c->fft_win_map = nullptr; c->fft_win_scatter = false;
   // the fp16-scale words are reused from the start only BETWEEN calls (a call keeps words of its early layers until its last ones: the training step)
   if (c->fft_block_i > 0 || c->fft_word_i > jcm_ctx::kFftWords - jcm_ctx::kFftWordsPerCall) {
     for (int i = 0; i <= c->fft_block_i && i < (int)c->fft_blocks.size(); ++i)
@@ -156,13 +153,12 @@ const ConvLayer* conv_of(jcm_ctx* c, const std::string& scope) {
 
 // The launch itself (kernel choice by precision / f32_conv); run_conv_layer brackets it with the timing events.
 static int launch_conv_layer(jcm_ctx* c, const ConvLayer* L, const void* wp, const void* x, int B, int H, int W, void* out, bool act_bf16,
-                             bool out_f32, int in_planar, int out_planar) {
+                             bool out_f32, int in_planar, int out_planar, int hpool) {
   ConvArgs a{};
   a.x = x; a.wp = wp; a.bias = L->bias; a.scale = L->scale; a.shift = L->shift; a.out = out;
   a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.relu_bn = L->has_bn ? 1 : 0;
   a.in_planar = in_planar; a.out_planar = out_planar;
-  a.hpool = c->conv_hpool;
-  c->conv_hpool = 0;
+  a.hpool = hpool;
   if ((in_planar || out_planar) && !act_bf16) return fail(JCM_ERR_ARG, "planar activations exist on the bf16 path only");
   if (a.hpool && !act_bf16) return fail(JCM_ERR_STATE, "half pool requested on an fp32 layer");
   if (act_bf16) {
@@ -286,7 +282,9 @@ int fft_new_words(jcm_ctx* c, int n, float** w) {
     c->fft_blocks.push_back(b);
   }
 }
-int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ) {
+int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ, FftLink* link) {
+  FftLink alone;
+  FftLink& k = link ? *link : alone;
   ConvArgs a{};
   a.x = x; a.bias = L->bias; a.scale = L->scale; a.shift = L->shift; a.out = out;
   a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.CoutP = L->cout; a.relu_bn = L->has_bn ? 1 : 0;
@@ -296,12 +294,12 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   const int np = fft_np(c);      // operand form of the channel GEMM (cgemm_split.hip)
   // fp32 handles, the pool hand-over conv2 -> pool -> conv3 on the model's 120 x 180 map: the layer runs as 2 x 2 tiles in the 64 x 96 transform of the
   // 60 x 90 maps (ConvArgs::tiles, conv_fft_rows_reg.hip) -- a quarter of the filter spectra, and the register row kernels
-  a.tiles = c->fft_tiles && c->fft_next_pool && !c->fft_t_in && !c->fft_xs && !c->fft_merge && !c->fft_win_map && !circ && in_layout == 0 &&
-            np == 4 && conv_fft_tiles_supported(a, L->ks, c->fft_next_ks) ? 1 : 0;
+  a.tiles = c->fft_tiles && k.next.pool && !k.t_in && !k.xs && !k.merge && !k.win_map && !circ && in_layout == 0 &&
+            np == 4 && conv_fft_tiles_supported(a, L->ks, k.next.ks_next) ? 1 : 0;
   const int wH = a.tiles ? H / 2 : H, wW = a.tiles ? W / 2 : W;      // the map size the filter spectra are for
   void* work = arena_alloc<char>(c, conv_fft_workspace_bytes(a, L->ks, np));
   c->arena_off = mark;                                   // scratch of this layer only: later layers run behind it on the stream
-  if (c->dry) { c->fft_t_in = nullptr; c->fft_t_next = nullptr; c->fft_merge = nullptr; c->fft_xs = nullptr; c->fft_xs_ready = false; c->fft_tmax_in = nullptr; c->fft_next_pool = 0; c->fft_next_ks = 0; c->fft_next_merge = nullptr; c->fft_t_in_16 = false; c->fft_win_map = nullptr; c->fft_win_scatter = false; return JCM_OK; }
+  if (c->dry) return JCM_OK;
   // Filter spectra are cached per (layer, map size).  The cache is bounded (JCM_FFT_CACHE_GB, default 64): a caller that walks many
   // image sizes (7.7 GB per size for conv5) makes it drop every spectrum that is not this layer's before it grows past the bound.
   const std::string key = scope + (circ ? "@win" : "@") + std::to_string(wH) + "x" + std::to_string(wW);
@@ -346,41 +344,28 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   hipEvent_t e0 = nullptr, e1 = nullptr, g0 = nullptr, g1 = nullptr;
   JCM_TRY(prof_begin(c, &e0, &e1));
   if (c->profile && (pool_get(c, &g0) != JCM_OK || pool_get(c, &g1) != JCM_OK)) { g0 = g1 = nullptr; }
-  const void* t_in = c->fft_t_in;
-  void* t_next = c->fft_t_next;
-  const FftMerge* mg = static_cast<const FftMerge*>(c->fft_merge);
-  void* xs = c->fft_xs;
-  const bool xs_ready = c->fft_xs_ready;
-  FftNext nx;
-  nx.pool = c->fft_next_pool; nx.ks_next = c->fft_next_ks; nx.merge = static_cast<const FftMerge*>(c->fft_next_merge);
-  c->fft_next_pool = 0; c->fft_next_ks = 0; c->fft_next_merge = nullptr;
-  const bool t_in_16 = c->fft_t_in_16;
-  c->fft_t_in_16 = false;
-  if (c->fft_win_map) {      // the windows are gathered by the forward row pass
-    a.win_map = c->fft_win_map; a.win_B = c->fft_win_B; a.win_H = c->fft_win_H; a.win_W = c->fft_win_W; a.win_TY = c->fft_win_TY; a.win_TX = c->fft_win_TX;
-    c->fft_win_map = nullptr;
+  if (k.win_map) {      // the windows are gathered by the forward row pass
+    a.win_map = k.win_map; a.win_B = k.win_B; a.win_H = k.win_H; a.win_W = k.win_W; a.win_TY = k.win_TY; a.win_TX = k.win_TX;
   }
-  if (c->fft_win_scatter) {      // ... and scattered by the inverse row pass (the geometry fields stay valid without a gather)
-    a.wout_H = c->fft_win_H; a.wout_W = c->fft_win_W; a.wout_TY = c->fft_win_TY; a.wout_TX = c->fft_win_TX;
-    c->fft_win_scatter = false;
+  if (k.win_scatter) {      // ... and scattered by the inverse row pass (same geometry, with or without a gather)
+    a.wout_H = k.win_H; a.wout_W = k.win_W; a.wout_TY = k.win_TY; a.wout_TX = k.win_TX;
   }
   Fp16Scale sc;
   if (np >= 4) {
     // the word of this layer's input: handed over with t_in / ready spectra, or a fresh one for this layer's own row pass
-    sc.tmax = c->fft_tmax_in;
-    if ((t_in || xs_ready) && !sc.tmax) return fail(JCM_ERR_STATE, "conv_fft '" + scope + "': a handed-over tensor without its scale word");
+    sc.tmax = k.tmax_in;
+    if ((k.t_in || k.xs_ready) && !sc.tmax) return fail(JCM_ERR_STATE, "conv_fft '" + scope + "': a handed-over tensor without its scale word");
     if (!sc.tmax) JCM_TRY(fft_new_words(c, a.tiles ? 4 * B : B, &sc.tmax));      // (tiles: one word per tile, the row of the channel GEMM)
-    if (t_next) JCM_TRY(fft_new_words(c, B, &sc.tmax_next));
+    if (k.t_next) JCM_TRY(fft_new_words(c, B, &sc.tmax_next));
     sc.winv = fw.wscale + 1;
     sc.common = c->train ? 1 : 0;      // a handle with training state: one scale per tensor (the weight gradient sums over the images)
     // 16-bit T / T' between the row and column passes: bf16 tensors on both sides of the layer, one-part spectra, nothing handed over or kept
     // ... except the merge hand-over conv4_fullres -> conv5 of jcm_pd_forward, which exists in 16-bit form (rows_inv_merge_fwd_reg_kernel<.., true>)
-    sc.t16 = (np == 5 && c->fft_t16 && in_layout != 0 && out_layout != 0 && !xs && (!t_in || t_in_16) && (!t_next || (nx.merge && !t_in))) ? 1 : 0;
+    sc.t16 = (np == 5 && c->fft_t16 && in_layout != 0 && out_layout != 0 && !k.xs && (!k.t_in || k.t_in_16) && (!k.t_next || (k.next.merge && !k.t_in))) ? 1 : 0;
   }
-  c->fft_t_in = nullptr; c->fft_t_next = nullptr; c->fft_merge = nullptr; c->fft_xs = nullptr; c->fft_xs_ready = false;
-  c->fft_tmax_in = sc.tmax_next;      // the next frequency-domain layer takes t_next (and its word)
-  c->fft_last_tmax = sc.tmax;
-  const hipError_t e = conv_fft_f32(a, L->ks, np, in_layout, out_layout, work, t_in, t_next, mg, g0, g1, c->stream, xs, xs_ready, np >= 4 ? &sc : nullptr, &nx);
+  k.tmax = sc.tmax;
+  k.tmax_next = sc.tmax_next;      // the layer that takes t_next takes its words too
+  const hipError_t e = conv_fft_f32(a, L->ks, np, in_layout, out_layout, work, k, g0, g1, c->stream, np >= 4 ? &sc : nullptr);
   if (g0 && g1 && e == hipSuccess) c->prof[scope + "/gemm"].emplace_back(g0, g1);
   else { if (g0) c->event_pool.push_back(g0); if (g1) c->event_pool.push_back(g1); }
   prof_end(c, scope, e0, e1, e == hipSuccess);
@@ -391,7 +376,11 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
 // One conv layer.  Activations are fp32, or bf16 when the handle runs the bf16 path (`act_bf16`);
 // `out_f32` forces an fp32 result (the logits layer).
 int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub,
-                   void* out, bool act_bf16, bool out_f32, int in_planar, int out_planar, bool x_u8) {
+                   void* out, bool act_bf16, bool out_f32, int in_planar, int out_planar, bool x_u8, FftLink* link, int hpool) {
+  const bool fft = stride == 1 && takes_fft(c, L, B, H, W);
+  // a request aimed at a route this layer does not take is an error of the caller, never dropped (nor left for the next layer)
+  if (!fft && link && !link->empty()) return fail(JCM_ERR_STATE, "layer '" + scope + "' was given a frequency-domain hand-over but does not run in the frequency domain");
+  if (hpool && (fft || stride != 1)) return fail(JCM_ERR_STATE, "half pool requested for layer '" + scope + "', which does not run on conv5_strip_bf16_kernel");
   if (stride == 2) {
     if (c->dry) return JCM_OK;
     if (!(L->ks == 5 && L->cin == 3 && L->has_bn))
@@ -399,8 +388,7 @@ int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int
     HIP_TRY(conv1_5x5s2(x, L->w_raw, L->bias, L->scale, L->shift, out, act_bf16, B, H, W, sub, L->cout, c->stream, x_u8));
     return JCM_OK;
   }
-  if (stride == 1 && takes_fft(c, L, B, H, W))
-    return run_conv_fft(c, L, scope, x, B, H, W, out, act_bf16 ? (in_planar ? 2 : 1) : 0, (act_bf16 && !out_f32) ? (out_planar ? 2 : 1) : 0);
+  if (fft) return run_conv_fft(c, L, scope, x, B, H, W, out, act_bf16 ? (in_planar ? 2 : 1) : 0, (act_bf16 && !out_f32) ? (out_planar ? 2 : 1) : 0, 0, link);
   if (c->dry) return JCM_OK;
   const void* wp = act_bf16 ? L->wp_bf16 : static_cast<const void*>(L->wp);
   if (stride != 1 || !wp) return fail(JCM_ERR_ARG, "no kernel for layer '" + scope + "' with stride " + std::to_string(stride));
@@ -410,7 +398,7 @@ int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   JCM_TRY(prof_begin(c, &e0, &e1));
-  const int r = launch_conv_layer(c, L, wp, x, B, H, W, out, act_bf16, out_f32, in_planar, out_planar);
+  const int r = launch_conv_layer(c, L, wp, x, B, H, W, out, act_bf16, out_f32, in_planar, out_planar, hpool);
   prof_end(c, scope, e0, e1, r == JCM_OK);
   return r;
 }
@@ -553,11 +541,11 @@ int refresh_derived(jcm_ctx* c, bool first) {
 namespace {
 
 int run_conv(jcm_ctx* c, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub, void* out,
-             bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false) {      // x_u8: the stride-2 layer reads a byte image
+             bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false, FftLink* link = nullptr, int hpool = 0) {      // x_u8: the stride-2 layer reads a byte image
   const ConvLayer* L = conv_of(c, scope);
   if (!L) return fail(JCM_ERR_STATE, "no conv layer '" + scope + "' (set '" + scope + "/weights' and finalize)");
   if (x_u8 && stride != 2) return fail(JCM_ERR_ARG, "byte images feed the stride-2 first layer only (" + scope + ")");
-  return run_conv_layer(c, L, scope, stride, x, B, H, W, sub, out, act_bf16, out_f32, in_planar, out_planar, x_u8);
+  return run_conv_layer(c, L, scope, stride, x, B, H, W, sub, out, act_bf16, out_f32, in_planar, out_planar, x_u8, link, hpool);
 }
 
 // bf16 handles: does a [B,H,W,Cin] launch of this 9x9 layer take the flattened-strip kernel (which reads / writes the
@@ -580,29 +568,27 @@ bool takes_c5strip(const ConvLayer* L, int B, int H, int W) {
 
 // fp32 handles: two consecutive frequency-domain layers on the same map -- the first one's fused inverse/forward row kernel writes the
 // second one's row-transformed input (from the arena) and the activation between them never reaches HBM.  Call right before
-// run_conv(first); returns the buffer to pass to expect_handover() before run_conv(second), or null.
-static void* offer_handover(jcm_ctx* c, const ConvLayer* La, const ConvLayer* Lb, int B, int H, int W) {
+// run_conv(first): fills the output side of its link and returns the buffer, or null; hand_over() then gives it to the second layer's link.
+static void* offer_handover(jcm_ctx* c, const ConvLayer* La, const ConvLayer* Lb, int B, int H, int W, FftLink& la) {
   if (c->precision != JCM_PRECISION_F32 || !takes_fft(c, La, B, H, W) || !takes_fft(c, Lb, B, H, W)) return nullptr;
   ConvArgs a{};
   a.B = B; a.H = H; a.W = W; a.Cin = La->cin; a.Cout = La->cout;
   if (La->cout != Lb->cin || !conv_fft_fusable(a, La->ks, Lb->ks)) return nullptr;
-  void* t = arena_alloc<char>(c, conv_fft_handover_bytes(a, La->ks));
-  c->fft_t_next = t;
-  return t;
+  return la.t_next = arena_alloc<char>(c, conv_fft_handover_bytes(a, La->ks));
 }
 // ... with the 2x2 max pool of main.py:47,55,64 between them: La runs on H x W, Lb on the pooled map; the fused kernel (conv_fft_rows_fused.hip) pools
 // a row pair in LDS and writes Lb's row-transformed input -- neither La's output nor the pooled map reaches HBM.
-static void* offer_pool_handover(jcm_ctx* c, const ConvLayer* La, const ConvLayer* Lb, int B, int H, int W) {
+static void* offer_pool_handover(jcm_ctx* c, const ConvLayer* La, const ConvLayer* Lb, int B, int H, int W, FftLink& la) {
   if (!(c->fft_fuse & 1) || c->precision != JCM_PRECISION_F32 || !takes_fft(c, La, B, H, W) || !takes_fft(c, Lb, B, (H + 1) / 2, (W + 1) / 2)) return nullptr;
   ConvArgs a{};
   a.B = B; a.H = H; a.W = W; a.Cin = La->cin; a.Cout = La->cout;
   if (La->cout != Lb->cin || !conv_fft_pool_fusable(a, La->ks, Lb->ks)) return nullptr;
-  void* t = arena_alloc<char>(c, conv_fft_pool_handover_bytes(a, Lb->ks));
-  c->fft_t_next = t;
-  c->fft_next_pool = 1;
-  c->fft_next_ks = Lb->ks;
-  return t;
+  la.next.pool = 1;
+  la.next.ks_next = Lb->ks;
+  return la.t_next = arena_alloc<char>(c, conv_fft_pool_handover_bytes(a, Lb->ks));
 }
+// the producer has run: its t_next and the words run_conv_fft gave it are the consumer's input
+static void hand_over(const FftLink& from, FftLink& to) { to.t_in = from.t_next; to.tmax_in = from.tmax_next; }
 // model(x, n_joints), main.py:29-74.  x fp32 NHWC, or (x_u8) a byte image whose values k stand for float32(k) / float32(255): only the conv1 kernels
 // read it, and their byte-source variants convert at the load (u8.h).  Intermediate activations fp32 or bf16.
 
@@ -636,6 +622,7 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
   }
   // branch outputs survive the per-branch scratch, so carve them first
   void* t45 = nullptr;
+  FftLink k5, k6;      // conv5 -> conv6
   for (int r = 0; r < 3; ++r) {
     if (r == 0 && fuse45) {
       ConvArgs a{};
@@ -708,7 +695,8 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
     }
     const int h3 = cdiv2(h2), w3 = cdiv2(w2);
     // fp32 handles: conv2 -> pool2 -> conv3 as one hand-over in row-transformed form (the pool inside the fused row kernel)
-    void* t23 = (bf || sk) ? nullptr : offer_pool_handover(c, L2, L3, B, h2, w2);
+    FftLink k2, k3, k4;      // conv2 -> (pool) -> conv3 -> conv4 of this branch
+    void* t23 = (bf || sk) ? nullptr : offer_pool_handover(c, L2, L3, B, h2, w2, k2);
     void* c2 = t23 ? nullptr : act((size_t)B * h2 * w2 * L2->cout);
     // bf16: conv2 -> pool2 -> conv3 on planar activations when both 5x5 layers take the strip kernel (its window rows are then 1-KB
     // contiguous LDS-DMA reads; from NHWC every 16-byte unit of a pixel is a separate cache line).  A planar [B][C/8][H][W][8] tensor IS an
@@ -716,9 +704,7 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
     const int pl23 = bf && takes_c5strip(L2, B, h2, w2) && takes_c5strip(L3, B, h3, w3) ? 1 : 0;
     // ... and the pool's horizontal half is taken in conv2's epilogue (even widths): c2 is then the [.., h2, w2 / 2, ..] map of pixel-pair maxima
     const int hp = pl23 && c->bf16_hpool && w2 % 2 == 0 && !(sk & 6) ? 1 : 0;
-    c->conv_hpool = hp;
-    if (!(sk & 4)) JCM_TRY(run_conv(c, "conv2_" + res, 1, p1, B, h2, w2, 1, c2, bf, false, 0, pl23));     // :46,54,63
-    c->conv_hpool = 0;
+    if (!(sk & 4)) JCM_TRY(run_conv(c, "conv2_" + res, 1, p1, B, h2, w2, 1, c2, bf, false, 0, pl23, false, &k2, hp));     // :46,54,63
     void* p2 = t23 ? nullptr : act((size_t)B * h3 * w3 * L2->cout);
     if (!c->dry && !(sk & 2) && !t23) {                                                     // :47,55,64
       if (hp) HIP_TRY(vpool_2x1_bf16(c2, p2, B * (L2->cout / 8), h2, w2 / 2, 8, c->stream));
@@ -728,13 +714,14 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
     const ConvLayer* L4r = conv_of(c, "conv4_" + res);
     if (!L4r) return fail(JCM_ERR_STATE, "part-detector parameters incomplete (conv4_" + res + ")");
     const int in4 = planar && L3->cout % 8 == 0 && takes_strip(L4r, B, h3, w3) && !takes_fft(c, L4r, B, h3, w3) ? 1 : 0;      // the patch kernels and the row pass read NHWC
-    void* t34 = (sk & 24) ? nullptr : offer_handover(c, L3, L4r, B, h3, w3);      // (no hand-over when either side is left out)
+    void* t34 = (sk & 24) ? nullptr : offer_handover(c, L3, L4r, B, h3, w3, k3);      // (no hand-over when either side is left out)
     void* c3 = t34 ? nullptr : act((size_t)B * h3 * w3 * L3->cout);
-    c->fft_t_in = t23;
-    if (!(sk & 8)) JCM_TRY(run_conv(c, "conv3_" + res, 1, p2, B, h3, w3, 1, c3, bf, false, pl23, in4));   // :48,56,65
-    c->fft_t_in = t34;
-    if (r == 0 && fuse45) { c->fft_t_next = t45; c->fft_next_merge = &mg; }      // conv4_fullres writes conv5's row-transformed (merged) input
-    if (!(sk & 16)) JCM_TRY(run_conv(c, "conv4_" + res, 1, c3, B, h3, w3, 1, x4[r], bf, false, in4, planar45));   // :49,57,66
+    hand_over(k2, k3);
+    if (!(sk & 8)) JCM_TRY(run_conv(c, "conv3_" + res, 1, p2, B, h3, w3, 1, c3, bf, false, pl23, in4, false, &k3));   // :48,56,65
+    hand_over(k3, k4);
+    if (r == 0 && fuse45) { k4.t_next = t45; k4.next.merge = &mg; }      // conv4_fullres writes conv5's row-transformed (merged) input
+    if (!(sk & 16)) JCM_TRY(run_conv(c, "conv4_" + res, 1, c3, B, h3, w3, 1, x4[r], bf, false, in4, planar45, false, &k4));   // :49,57,66
+    if (r == 0 && fuse45) { hand_over(k4, k5); k5.t_in_16 = h16; }
     c->arena_off = mark;
   }
   // conv5 in the frequency domain: its forward row kernel forms ((x1 + up(x2)) + up(x3)) / 3 while it loads the rows (NHWC inputs: fp32, or
@@ -750,13 +737,12 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
     else HIP_TRY(upsample_merge3(x4[0], x4[1], h4[1], w4[1], x4[2], h4[2], w4[2], merged, bf, B, hh, ww, L4->cout, c->stream));
   }
   const int sk = c->debug_skip;
-  void* t56 = (sk & 96) ? nullptr : offer_handover(c, L5, conv_of(c, "conv6"), B, hh, ww);
+  void* t56 = (sk & 96) ? nullptr : offer_handover(c, L5, conv_of(c, "conv6"), B, hh, ww, k5);
   void* c5 = t56 ? nullptr : act((size_t)B * hh * ww * L5->cout);
-  if (fuse_merge && !(sk & 32)) c->fft_merge = &mg;
-  if (fuse45) { c->fft_t_in = t45; c->fft_t_in_16 = h16; }
-  if (!(sk & 32)) JCM_TRY(run_conv(c, "conv5", 1, merged, B, hh, ww, 1, c5, bf, false, planar45, planar));   // :71
-  c->fft_t_in = t56;
-  if (!(sk & 64)) JCM_TRY(run_conv(c, "conv6", 1, c5, B, hh, ww, 1, logits, bf, true, planar, 0));         // :72
+  if (fuse_merge) k5.merge = &mg;
+  if (!(sk & 32)) JCM_TRY(run_conv(c, "conv5", 1, merged, B, hh, ww, 1, c5, bf, false, planar45, planar, false, &k5));   // :71
+  hand_over(k5, k6);
+  if (!(sk & 64)) JCM_TRY(run_conv(c, "conv6", 1, c5, B, hh, ww, 1, logits, bf, true, planar, 0, false, &k6));         // :72
   return JCM_OK;
 }
 
@@ -1014,14 +1000,15 @@ int jcm_conv_layer_merged(jcm_handle h, const char* scope, const float* x1, cons
     }
     FftMerge mg{a2, H2, W2, a3, H3, W3};
     const void* in = a1;
+    FftLink k;
     if (takes_fft(c, L, B, H, W)) {
-      c->fft_merge = &mg;
+      k.merge = &mg;
     } else {
       void* merged = arena_alloc<char>(c, n1 * (bf ? 2 : 4));
       if (!c->dry) HIP_TRY(upsample_merge3(a1, a2, H2, W2, a3, H3, W3, merged, bf, B, H, W, L->cin, c->stream));
       in = merged;
     }
-    JCM_TRY(run_conv(c, scope, 1, in, B, H, W, 1, ob, bf, false));
+    JCM_TRY(run_conv(c, scope, 1, in, B, H, W, 1, ob, bf, false, 0, 0, false, &k));
     if (bf && !c->dry) HIP_TRY(cast_bf16_f32(ob, out, nout, c->stream));
     return (int)JCM_OK;
   });

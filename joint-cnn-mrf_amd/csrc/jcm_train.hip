@@ -210,26 +210,28 @@ int conv_train_fwd_conv(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int 
     const bool sw = conv_fft_win_scatter_supported(kWin, L.cout);      // ... and where the inverse row pass can store into the map, neither do the valid regions
     float* rw = sw ? static_cast<float*>(f.r) : arena_alloc<float>(c, (size_t)BW * kWinValid * kWinValid * L.cout);
     if (!c->dry && !gw) HIP_TRY(window_gather_f32(static_cast<const float*>(x), xw, B, Hin, Win, L.cin, kWin, TY, TX, 0, c->stream));
-    c->fft_win_B = B; c->fft_win_H = Hin; c->fft_win_W = Win; c->fft_win_TY = TY; c->fft_win_TX = TX;
-    if (gw) c->fft_win_map = x;
-    c->fft_win_scatter = sw;
-    c->fft_xs = f.xs;
-    JCM_TRY(run_conv_fft(c, &L, f.scope, xw, BW, kWin, kWin, rw, 0, 0, 1));
+    FftLink k;
+    k.win_B = B; k.win_H = Hin; k.win_W = Win; k.win_TY = TY; k.win_TX = TX;
+    if (gw) k.win_map = x;
+    k.win_scatter = sw;
+    k.xs = f.xs;
+    JCM_TRY(run_conv_fft(c, &L, f.scope, xw, BW, kWin, kWin, rw, 0, 0, 1, &k));
     if (!c->dry) {
-      f.xs_tmax = c->fft_last_tmax;
+      f.xs_tmax = k.tmax;
       if (!sw) HIP_TRY(window_scatter_f32(rw, static_cast<float*>(f.r), B, f.H, f.W, L.cout, kWin, TY, TX, c->stream));
     }
     c->arena_off = mark;      // (later work runs behind the scatter on the stream)
     return JCM_OK;
   }
+  FftLink k;
   if (stride == 1 && !bf(c) && takes_fft(c, &L, B, Hin, Win)) {      // keep the input spectra: the weight gradient is taken in the frequency domain too
     ConvArgs ax{};
     ax.B = B; ax.H = Hin; ax.W = Win; ax.Cin = L.cin; ax.Cout = L.cout;
     f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(ax, L.ks, fft_np(c)));
-    c->fft_xs = f.xs;
+    k.xs = f.xs;
   }
-  JCM_TRY(run_conv_layer(c, &L, f.scope, stride, x, B, Hin, Win, sub, f.r, bf(c), !f.L->has_bn));
-  if (f.xs && !c->dry) f.xs_tmax = c->fft_last_tmax;
+  JCM_TRY(run_conv_layer(c, &L, f.scope, stride, x, B, Hin, Win, sub, f.r, bf(c), !f.L->has_bn, 0, 0, false, &k));
+  if (f.xs && !c->dry) f.xs_tmax = k.tmax;
   return JCM_OK;
 }
 
@@ -432,10 +434,11 @@ int conv_dgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int B, void* dx, i
       const bool sw = conv_fft_win_scatter_supported(kWin, f.L->cin);
       float* xw = sw ? static_cast<float*>(dx) : arena_alloc<float>(c, (size_t)BW * kWinValid * kWinValid * f.L->cin);
       if (!c->dry && !gw) HIP_TRY(window_gather_f32(static_cast<const float*>(dz), zw, B, f.H, f.W, cin_fft, kWin, f.TY, f.TX, 0, c->stream));
-      c->fft_win_B = B; c->fft_win_H = f.H; c->fft_win_W = f.W; c->fft_win_TY = f.TY; c->fft_win_TX = f.TX;
-      if (gw) c->fft_win_map = dz;
-      c->fft_win_scatter = sw;
-      JCM_TRY(run_conv_fft(c, &Ld, key, zw, BW, kWin, kWin, xw, 0, 0, 1));
+      FftLink k;
+      k.win_B = B; k.win_H = f.H; k.win_W = f.W; k.win_TY = f.TY; k.win_TX = f.TX;
+      if (gw) k.win_map = dz;
+      k.win_scatter = sw;
+      JCM_TRY(run_conv_fft(c, &Ld, key, zw, BW, kWin, kWin, xw, 0, 0, 1, &k));
       if (!c->dry && !sw) HIP_TRY(window_scatter_f32(xw, static_cast<float*>(dx), B, f.H, f.W, f.L->cin, kWin, f.TY, f.TX, c->stream));
       c->arena_off = mark;
       return JCM_OK;
@@ -445,9 +448,10 @@ int conv_dgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int B, void* dx, i
       if ((size_t)f.L->ks * f.L->ks * cin_fft * f.L->cin > t->scratch_flip_n) return fail(JCM_ERR_STATE, "flipped filter of '" + f.scope + "' does not fit its buffer");
       if (!c->dry && !fft_spectra_valid(c, key, f.H, f.W))
         HIP_TRY(flip_transpose_weights(f.L->w_raw, t->scratch_flip, f.L->ks, f.L->cin, f.L->cout, cin_fft, c->stream));
-      if (!c->dry && t->zs && t->zs_of == dz && t->zs_cin == cin_fft) { c->fft_xs = t->zs; c->fft_xs_ready = true; c->fft_tmax_in = t->zs_tmax; }      // the spectra of dz are there (conv_wgrad just made them)
+      FftLink k;
+      if (!c->dry && t->zs && t->zs_of == dz && t->zs_cin == cin_fft) { k.xs = t->zs; k.xs_ready = true; k.tmax_in = t->zs_tmax; }      // the spectra of dz are there (conv_wgrad just made them)
       t->zs = nullptr;
-      return run_conv_fft(c, &Ld, key, dz, B, f.H, f.W, dx, 0, 0);
+      return run_conv_fft(c, &Ld, key, dz, B, f.H, f.W, dx, 0, 0, 0, &k);
     }
     if (ldz_fft) return fail(JCM_ERR_STATE, "data gradient of '" + f.scope + "': widened dz without the frequency-domain route");
   }

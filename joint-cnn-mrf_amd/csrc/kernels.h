@@ -138,9 +138,29 @@ struct FftMerge { const void* x2; int H2, W2; const void* x3; int H3, W3; };    
 // row-transformed POOLED map, for a next layer of kernel size ks_next); merge = this layer is the full-resolution branch and t_next the row-transformed
 // merged map ((x1 + up(x2)) + up(x3)) / 3.  Neither: t_next is this layer's own output (same map).
 struct FftNext { int pool = 0; int ks_next = 0; const FftMerge* merge = nullptr; };
-// xs / xs_ready: keep the split activation spectra in a caller buffer (conv_fft_xs_bytes) / they are there already (skip the forward transforms)
-hipError_t conv_fft_f32(const ConvArgs& a, int ks, int np, int in_layout, int out_layout, void* work, const void* t_in, void* t_next, const FftMerge* merge,
-                        hipEvent_t g0, hipEvent_t g1, hipStream_t st, void* xs = nullptr, bool xs_ready = false, const Fp16Scale* sc = nullptr, const FftNext* nx = nullptr);
+// Everything that ties one frequency-domain layer call to its neighbours; default-constructed = the layer stands alone.  The caller fills the input and the output
+// side, run_conv_fft (jcm_api.hip) writes the two results, and a hand-over is the caller moving the producer's (t_next, tmax_next) into the consumer's (t_in, tmax_in).
+struct FftLink {
+  // input side
+  const void* t_in = nullptr;       // the row-transformed input left by the previous layer's fused kernel: the forward row pass is skipped
+  bool t_in_16 = false;             // ... as complex fp16 followed by its tile scale words (bf16 handles: conv4_fullres -> conv5)
+  float* tmax_in = nullptr;         // the scale words (Fp16Scale::tmax) that come with t_in / with ready spectra
+  const FftMerge* merge = nullptr;  // the layer forms the merged map itself while it loads the rows (conv5)
+  void* xs = nullptr;               // keep the split activation spectra in this caller buffer (conv_fft_xs_bytes; the training step's weight gradient reads them)
+  bool xs_ready = false;            // ... they are there already (the data gradient after the weight gradient of the same layer): skip the forward transforms
+  const void* win_map = nullptr;    // the overlap-save windows are cut from this map by the forward row pass (ConvArgs::win_map) ...
+  int win_B = 0, win_H = 0, win_W = 0, win_TY = 0, win_TX = 0;      // ... of this geometry, which win_scatter shares
+  // output side
+  void* t_next = nullptr;           // write the NEXT layer's row-transformed input there instead of the spatial output (conv_fft_fusable() says when that is legal)
+  FftNext next;                     // what lies between this layer and that one
+  bool win_scatter = false;         // the inverse row pass stores the valid regions into the map `out` (ConvArgs::wout_*)
+  // results (np >= 4), written by run_conv_fft
+  float* tmax = nullptr;            // the words this layer's input used
+  float* tmax_next = nullptr;       // the words of t_next
+  bool empty() const { return !t_in && !merge && !xs && !xs_ready && !win_map && !t_next && !next.pool && !next.merge && !win_scatter; }
+};
+hipError_t conv_fft_f32(const ConvArgs& a, int ks, int np, int in_layout, int out_layout, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
+                        const Fp16Scale* sc = nullptr);
 // the fused hand-overs of FftNext: is there a kernel for this pair of layers, and the size of the row-transformed tensor handed over
 bool conv_fft_win_gather_supported(int win, int Cin);
 bool conv_fft_win_scatter_supported(int win, int Cout);    // ... and its inverse row pass store the valid regions straight into the map?      // can the forward row pass of `win` x `win` overlap-save windows read them straight from the map?

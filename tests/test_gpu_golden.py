@@ -547,3 +547,38 @@ def test_bf16_half_pool_in_conv2_epilogue_is_bit_identical():
     eng.close()
     assert np.array_equal(got[0], got[1]) and np.array_equal(got[2], got[3])
     assert np.abs(got[1]).max() > 0 and np.abs(got[3]).max() > 0
+
+
+@pytest.mark.parametrize('precision', ['fp32', 'bf16'])
+def test_handle_carries_nothing_from_one_call_to_the_next(precision):
+    """What ties two frequency-domain layers together (hand-overs, scale words, the merge, the half pool) is passed from layer to layer inside ONE call
+    (csrc/kernels.h: FftLink) and never kept in the handle: a tower forward, a single conv5, a merged conv5 and forwards with "fft_fuse" switched off and on
+    again, run one after the other on one handle, each give the bits a fresh handle constructed with that option gives.  --debug width at 480 x 720: the
+    smallest input at which all five hand-overs and the tiles are taken.  (bf16 handles refuse the --debug width -- its 16-channel layers are below the
+    32 input channels of the bf16 kernels -- so that arm runs the first three calls at the goldens' full width.)"""
+    from joint_cnn_mrf_amd.engine import Engine
+    p = synth.make_pd_params(debug=True, bn='trained', conv6_gain=8.0) if precision == 'fp32' else full_inputs()[2]
+    cin, cout = p['conv5/weights'].shape[2:]
+    x = dev(synth.make_images(2))
+    rng = np.random.default_rng(77)
+    m1, m2, m3 = (dev(rng.standard_normal((2, h, w, cin))) for h, w in ((60, 90), (30, 45), (15, 23)))
+
+    def fresh(call, **opt):
+        eng = Engine(device=0, precision=precision, **opt).load_params(p)
+        out = call(eng).cpu().numpy()
+        eng.close()
+        return out
+
+    calls = [lambda e: e.model(x), lambda e: e.conv_layer(m1, 'conv5', 1, n_out=cout), lambda e: e.conv_layer_merged(m1, m2, m3, 'conv5', cout)]
+    eng = Engine(device=0, precision=precision).load_params(p)
+    got = [call(eng).cpu().numpy() for call in calls]
+    for i, call in enumerate(calls):
+        assert np.array_equal(got[i], fresh(call)), i
+    if precision == 'fp32':
+        first = got[0]
+        for fuse in (0, 3):
+            eng.set_option('fft_fuse', fuse)
+            got = eng.model(x).cpu().numpy()
+            assert np.array_equal(got, fresh(calls[0], fft_fuse=fuse)), fuse
+        assert np.array_equal(got, first)
+    eng.close()
