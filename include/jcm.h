@@ -102,6 +102,11 @@ int jcm_abi_version(void);
  * "fft_tiles": any time, default 1 (fp32 handles, with "fft_fuse" bit 0): conv2 of a 120 x 180 map -> pool -> conv3 runs as 2 x 2 tiles of 60 x 90, each with its
  *              2-pixel halo in the 64 x 96 transform of the 60 x 90 maps (a quarter of the filter spectra, register transform kernels).  0 = the whole map.
  *              Environment JCM_FFT_TILES=0 (read once per process) turns the tiles off as well.
+ * "fft_logits_rows": any time, default 1 (fp32 handles without training state): the logits layer conv6 behind conv5's row-transformed hand-over (60 x 90 maps:
+ *              96-point rows, at most 64 rows, at most 16 output channels) contracts the input channels and the nine vertical taps directly on the row
+ *              spectra -- one fp16 matrix product per kx with K = 9 x Cin, rows outside the map read as zeros -- and runs one inverse row pass: no column
+ *              passes, no padded filter spectra (58 MB of operand instead of 411 MB).  0 = conv6 as a whole frequency-domain layer.
+ *              Environment JCM_FFT_LOGITS_ROWS=0 (read once per process) turns the route off as well.
  * "fft_fuse" : any time, default 3 (jcm_pd_forward / jcm_forward on the frequency-domain route): hand-overs in row-transformed form, ONE kernel doing the
  *              inverse row transform + bias / ReLU / BatchNorm of the producing layer, the op between the layers and the forward row transform of the
  *              consuming layer.  bit 0 (fp32 handles) = conv2 -> 2x2 max pool -> conv3: a work group owns a row pair, takes the 2x2 maximum in LDS

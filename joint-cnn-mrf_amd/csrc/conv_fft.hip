@@ -222,6 +222,11 @@ static bool fft_tiles_on() {
   static const bool on = [] { const char* e = std::getenv("JCM_FFT_TILES"); return !e || std::atoi(e) != 0; }();
   return on;
 }
+// JCM_FFT_LOGITS_ROWS=0 (environment, read once): the logits layer as a whole frequency-domain layer -- the A/B arm of the contraction on the row spectra (conv_fft_logits.hip)
+static bool fft_logits_rows_on() {
+  static const bool on = [] { const char* e = std::getenv("JCM_FFT_LOGITS_ROWS"); return !e || std::atoi(e) != 0; }();
+  return on;
+}
 static int padn(int c, int n) { return (c + n - 1) / n * n; }
 
 int persistent_grid(const void* kernel, int ntiles, int threads, int dyn_lds) {
@@ -506,6 +511,53 @@ hipError_t conv_fft_f32(const ConvArgs& a0, int ks, int np, int in_layout, int o
     if (ai.wout_TX > 0) return hipErrorInvalidValue;      // (the scatter into the map exists in the register kernel only)
     cfft_rows_inv(s.NX, ai, out_layout, T, twx, opad, norm, sc, st);
   }
+  return hipGetLastError();
+}
+
+// ---- the logits layer on the row spectra of its input (conv_fft_logits.hip): a 9x9 layer with at most 16 output channels whose row-transformed input was
+// handed over at a 96-point row length.  No column pass, no filter spectra: the operand A (conv_fft_logits_pack) and one inverse row pass.
+bool conv_fft_logits_rows_supported(const ConvArgs& a, int ks) {
+  Sizes s;
+  return fft_logits_rows_on() && ks == 9 && !a.circ && !a.tiles && !a.win_map && conv_fft_supported(a, ks) && sizes_of(a.H, a.W, ks, &s) && cfft_logits_rows_supported(s.NX, a);
+}
+size_t conv_fft_logits_weight_bytes(int H, int W, int Cin) {
+  Sizes s;
+  return sizes_of(H, W, 9, &s) ? cfft_logits_rows_operand_bytes(s.NX, Cin) : 0;
+}
+size_t conv_fft_logits_workspace_bytes(const ConvArgs& a) {      // S = T'[b][y][kx][64]
+  Sizes s;
+  return sizes_of(a.H, a.W, 9, &s) ? align256((size_t)a.B * a.H * (s.NX / 2 + 1) * CB * sizeof(cf)) : 0;
+}
+hipError_t conv_fft_logits_pack(const float* w_hwio, void* aop, int H, int W, int Cin, int Cout, hipStream_t st, float* wscale) {
+  Sizes s;
+  if (!sizes_of(H, W, 9, &s) || Cin % 16 || Cout > 16 || !wscale) return hipErrorInvalidValue;
+  if (hipError_t e = hipMemsetAsync(wscale, 0, 2 * sizeof(float), st); e != hipSuccess) return e;
+  const size_t pairs = (size_t)Cin * Cout;
+  const dim3 bgrid((unsigned)((pairs + 255) / 256 > 1024 ? 1024 : (pairs + 255) / 256));
+  hipLaunchKernelGGL(weight_bound_kernel<81>, bgrid, dim3(256), 0, st, w_hwio, pairs, 0, wscale);
+  return cfft_logits_rows_pack(s.NX, w_hwio, aop, Cin, Cout, wscale, st);
+}
+// a.wp = the operand A; link.t_in = T[kx][c/16][b][y][16] with its words sc.tmax; work = conv_fft_logits_workspace_bytes(a).  The image's scale is
+// 2^k with tmax[b] 2^k < 2^15 (Fp16Scale::hf = 1: no column transform sums H rows), undone by the inverse row pass together with the operand's.
+hipError_t conv_fft_logits_f32(const ConvArgs& a0, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st, const Fp16Scale* scp) {
+  Sizes s;
+  if (!conv_fft_logits_rows_supported(a0, 9) || !sizes_of(a0.H, a0.W, 9, &s) || !link.t_in || link.t_in_16 || link.t_next || link.merge || link.xs || link.xs_ready || link.win_scatter ||
+      !scp || !scp->tmax || !scp->winv || scp->common)
+    return hipErrorInvalidValue;
+  ConvArgs a = a0;
+  a.CoutP = pad64(a.Cout);
+  Fp16Scale sc = *scp;
+  sc.hf = 1.f;
+  sc.nb = a.B;
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  const cf* twb = twiddle_table(dev);
+  if (!twb) return hipErrorOutOfMemory;
+  cf* S = static_cast<cf*>(work);
+  if (g0 && hipEventRecord(g0, st) != hipSuccess) return hipErrorUnknown;
+  if (hipError_t e = cfft_logits_rows(s.NX, a, static_cast<const cf*>(link.t_in), a.wp, sc.tmax, S, st); e != hipSuccess) return e;
+  if (g1 && hipEventRecord(g1, st) != hipSuccess) return hipErrorUnknown;
+  cfft_rows_inv(s.NX, a, 0, S, twb + tw_offset(s.NX), 4, 1.0f / (float)s.NX, sc, st);
   return hipGetLastError();
 }
 

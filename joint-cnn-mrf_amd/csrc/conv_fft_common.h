@@ -334,5 +334,11 @@ bool cfft_rows_inv_pool_fwd_supported(int NXI, int NXO, int Cout);
 // conv_fft_rows_mfma.hip: the 96-point inverse row pass of bf16 handles (16-bit T', planar bf16 output) as a matrix product on the matrix cores; false: no kernel for this case
 bool cfft_rows_inv_mfma(int NX, const ConvArgs& a, int layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
 bool cfft_rows_inv_merge_fwd_supported(int NX, const ConvArgs& a, const FftMerge& m);
+// conv_fft_logits.hip: the logits layer contracted on the row spectra of its input (fp32 handles, 96-point rows, H <= 64, Cout <= 16): the operand
+// A[kx][dy][ci][j] (two fp16 parts, wscale as conv_fft_pack_weights) and S = T'[b][y][kx][64] for the inverse row pass, scaled by fp16_scale(tmax[b], 1)
+bool cfft_logits_rows_supported(int NX, const ConvArgs& a);
+size_t cfft_logits_rows_operand_bytes(int NX, int Cin);
+hipError_t cfft_logits_rows_pack(int NX, const float* w_hwio, void* aop, int Cin, int Cout, float* wscale, hipStream_t st);
+hipError_t cfft_logits_rows(int NX, const ConvArgs& a, const cf* T, const void* aop, const float* tmax, cf* S, hipStream_t st);
 }  // namespace cfft
 }  // namespace jcm

@@ -90,6 +90,7 @@ struct jcm_ctx {
   int sm_algo = 3;              // 3 = every transform in LDS (sm_fused.hip), 1 = direct sliding-window VALU kernel (the cross-check)
   int conv9_fft = 1;            // fp32 handles: wide 9x9 layers in the frequency domain (conv_fft.hip) when the shape allows; 0 = fp32 MFMA chain
   int fft_tiles = 1;            // fp32 handles, the pool hand-over of conv2_fullres: 2 x 2 tiles of the 120 x 180 map in the 60 x 90 maps' transform (ConvArgs::tiles)
+  int fft_logits_rows = 1;      // fp32 handles without training state: the logits layer behind conv5's hand-over contracts the channels on the row spectra (conv_fft_logits.hip); 0 = a whole frequency-domain layer
   int fft_fuse = 3;             // fp32 handles, jcm_pd_forward: bit 0 = conv2 -> max pool -> conv3, bit 1 = conv4_fullres -> branch merge -> conv5 handed over in row-transformed form (conv_fft_rows_fused.hip)
   int fft_single = 1;           // bf16 handles: the channel GEMM on ONE scaled fp16 part per operand (np = 5; 0 = two bf16 parts, three products)
   int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)

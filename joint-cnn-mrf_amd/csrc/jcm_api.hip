@@ -297,18 +297,23 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   a.tiles = c->fft_tiles && k.next.pool && !k.t_in && !k.xs && !k.merge && !k.win_map && !circ && in_layout == 0 &&
             np == 4 && conv_fft_tiles_supported(a, L->ks, k.next.ks_next) ? 1 : 0;
   const int wH = a.tiles ? H / 2 : H, wW = a.tiles ? W / 2 : W;      // the map size the filter spectra are for
-  void* work = arena_alloc<char>(c, conv_fft_workspace_bytes(a, L->ks, np));
+  // fp32 handles, the last layer behind a hand-over (conv5 -> conv6 of jcm_pd_forward): 9 output channels do not pay for two column passes and a channel GEMM --
+  // the channels are contracted on the row spectra that arrive in t_in (conv_fft_logits.hip).  Not on a handle with training state (one scale per tensor there).
+  const bool lrows = c->fft_logits_rows && !c->train && np == 4 && k.t_in && !k.t_in_16 && !k.t_next && !k.next.pool && !k.next.merge && !k.xs && !k.xs_ready && !k.merge &&
+                     !k.win_map && !k.win_scatter && !circ && in_layout == 0 && out_layout == 0 && conv_fft_logits_rows_supported(a, L->ks);
+  void* work = arena_alloc<char>(c, lrows ? conv_fft_logits_workspace_bytes(a) : conv_fft_workspace_bytes(a, L->ks, np));
   c->arena_off = mark;                                   // scratch of this layer only: later layers run behind it on the stream
   if (c->dry) return JCM_OK;
   // Filter spectra are cached per (layer, map size).  The cache is bounded (JCM_FFT_CACHE_GB, default 64): a caller that walks many
   // image sizes (7.7 GB per size for conv5) makes it drop every spectrum that is not this layer's before it grows past the bound.
-  const std::string key = scope + (circ ? "@win" : "@") + std::to_string(wH) + "x" + std::to_string(wW);
+  const std::string key = scope + (circ ? "@win" : lrows ? "@rows" : "@") + std::to_string(wH) + "x" + std::to_string(wW);
+  const size_t wbytes = lrows ? conv_fft_logits_weight_bytes(wH, wW, L->cin) : conv_fft_weight_bytes(wH, wW, L->ks, L->cin, L->cout, np, circ);
   // (A training handle keeps the spectra of BOTH geometries of a layer -- overlap-save windows for steps of <= 32 images, the whole map for evaluation
   // forwards and larger batches -- so that a loop that alternates training steps and evaluation does not re-pack gigabytes and stall the stream at
   // every flip (round 5 dropped the other geometry here); the cache bound below is what limits the footprint.)
   if (!c->fft_w.count(key)) {
     static const size_t cap = [] { const char* e = std::getenv("JCM_FFT_CACHE_GB"); return (size_t)(e ? std::atoi(e) : 64) << 30; }();
-    const size_t need = conv_fft_weight_bytes(wH, wW, L->ks, L->cin, L->cout, np, circ);
+    const size_t need = wbytes;
     size_t held = 0;
     for (auto& kv : c->fft_w) held += kv.second.bytes;
     if (held + need > cap && !c->fft_w.empty()) {
@@ -319,7 +324,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   }
   jcm_ctx::FftW& fw = c->fft_w[key];
   if (!fw.p) {
-    const size_t wb = (conv_fft_weight_bytes(wH, wW, L->ks, L->cin, L->cout, np, circ) + 255) & ~size_t(255);
+    const size_t wb = (wbytes + 255) & ~size_t(255);
     fw.bytes = wb + 256;      // + the two words of the filter spectra's scale (np = 4)
     if (hipMalloc(&fw.p, fw.bytes) == hipSuccess) {
       fw.wscale = reinterpret_cast<float*>(static_cast<char*>(fw.p) + wb);
@@ -337,7 +342,8 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
       auto it = c->fft_w.find(key.substr(6));
       if (it != c->fft_w.end() && it->second.valid && it->second.wscale) bound_from = it->second.wscale;
     }
-    HIP_TRY(conv_fft_pack_weights(L->w_raw, fw.p, wH, wW, L->ks, L->cin, L->cout, np, c->precision == JCM_PRECISION_BF16, c->stream, fw.wscale, circ, bound_from));
+    if (lrows) HIP_TRY(conv_fft_logits_pack(L->w_raw, fw.p, wH, wW, L->cin, L->cout, c->stream, fw.wscale));
+    else HIP_TRY(conv_fft_pack_weights(L->w_raw, fw.p, wH, wW, L->ks, L->cin, L->cout, np, c->precision == JCM_PRECISION_BF16, c->stream, fw.wscale, circ, bound_from));
     fw.valid = true;
   }
   a.wp = fw.p;
@@ -365,7 +371,8 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   }
   k.tmax = sc.tmax;
   k.tmax_next = sc.tmax_next;      // the layer that takes t_next takes its words too
-  const hipError_t e = conv_fft_f32(a, L->ks, np, in_layout, out_layout, work, k, g0, g1, c->stream, np >= 4 ? &sc : nullptr);
+  const hipError_t e = lrows ? conv_fft_logits_f32(a, work, k, g0, g1, c->stream, &sc)
+                             : conv_fft_f32(a, L->ks, np, in_layout, out_layout, work, k, g0, g1, c->stream, np >= 4 ? &sc : nullptr);
   if (g0 && g1 && e == hipSuccess) c->prof[scope + "/gemm"].emplace_back(g0, g1);
   else { if (g0) c->event_pool.push_back(g0); if (g1) c->event_pool.push_back(g1); }
   prof_end(c, scope, e0, e1, e == hipSuccess);
@@ -863,6 +870,10 @@ int jcm_set_option(jcm_handle h, const char* key, int64_t value) {
   }
   if (k == "fft_tiles") {   // allowed at any time (fp32 handles): conv2_fullres -> pool -> conv3 as 2 x 2 tiles of the 120 x 180 map (fft_fuse bit 0)
     h->fft_tiles = value != 0;
+    return JCM_OK;
+  }
+  if (k == "fft_logits_rows") {   // allowed at any time (fp32 handles): the logits layer behind conv5's hand-over on the row spectra (conv_fft_logits.hip); 0 = a whole frequency-domain layer
+    h->fft_logits_rows = value != 0;
     return JCM_OK;
   }
   if (k == "bf16_hpool") {   // allowed at any time (bf16 handles)

@@ -161,6 +161,14 @@ struct FftLink {
 };
 hipError_t conv_fft_f32(const ConvArgs& a, int ks, int np, int in_layout, int out_layout, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
                         const Fp16Scale* sc = nullptr);
+// The logits layer contracted on the row spectra of its input (conv_fft_logits.hip; fp32 handles): a 9x9 layer with Cout <= 16 whose row-transformed input arrives
+// through link.t_in at a 96-point row length, H <= 64.  a.wp = the operand packed by conv_fft_logits_pack (conv_fft_logits_weight_bytes; wscale as above), work =
+// conv_fft_logits_workspace_bytes(a); out fp32 NHWC, bias epilogue.  JCM_FFT_LOGITS_ROWS=0 in the environment turns the route off.
+bool conv_fft_logits_rows_supported(const ConvArgs& a, int ks);
+size_t conv_fft_logits_weight_bytes(int H, int W, int Cin);
+size_t conv_fft_logits_workspace_bytes(const ConvArgs& a);
+hipError_t conv_fft_logits_pack(const float* w_hwio, void* aop, int H, int W, int Cin, int Cout, hipStream_t st, float* wscale);
+hipError_t conv_fft_logits_f32(const ConvArgs& a, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st, const Fp16Scale* sc);
 // the fused hand-overs of FftNext: is there a kernel for this pair of layers, and the size of the row-transformed tensor handed over
 bool conv_fft_win_gather_supported(int win, int Cin);
 bool conv_fft_win_scatter_supported(int win, int Cout);    // ... and its inverse row pass store the valid regions straight into the map?      // can the forward row pass of `win` x `win` overlap-save windows read them straight from the map?

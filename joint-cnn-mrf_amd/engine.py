@@ -19,7 +19,7 @@ def _hm_size(n):
 class Engine:
     """Owns a jcm_handle.  All tensor arguments are torch CUDA float32 NHWC, contiguous."""
 
-    def __init__(self, device=0, precision='fp32', n_joints=9, stream=None, f32_conv=None, split_min_wgs=None, micro_batch=None, conv9_fft=None, call_order=None, fft_single=None, fft_t16=None, fft_fuse=None, fft_tiles=None):
+    def __init__(self, device=0, precision='fp32', n_joints=9, stream=None, f32_conv=None, split_min_wgs=None, micro_batch=None, conv9_fft=None, call_order=None, fft_single=None, fft_t16=None, fft_fuse=None, fft_tiles=None, fft_logits_rows=None):
         if not torch.cuda.is_available():
             raise RuntimeError('joint-cnn-mrf_amd needs an MI355X (gfx950) GPU; torch.cuda.is_available() is False '
                                'and there is no CPU path')
@@ -52,6 +52,8 @@ class Engine:
             self.set_option('fft_fuse', int(fft_fuse))
         if fft_tiles is not None:     # fp32 engines: False = conv2_fullres -> pool -> conv3 on the whole 120x180 map (A/B arm of the 2x2 tiles; default on)
             self.set_option('fft_tiles', int(bool(fft_tiles)))
+        if fft_logits_rows is not None:     # fp32 engines: False = conv6 as a whole frequency-domain layer (A/B arm of the contraction on conv5's row spectra; default on)
+            self.set_option('fft_logits_rows', int(bool(fft_logits_rows)))
         if call_order is not None:    # False (debugging): this engine's calls are not ordered against other engines' on the device
             self.set_option('call_order', int(bool(call_order)))
         if split_min_wgs is not None: # 0 forces the split kernels even on grids too small to pay off (parity tests at small batch)
