@@ -49,37 +49,62 @@ const char* jcm_last_error(void);
 int jcm_abi_version(void);
 
 /* -- options ------------------------------------------------------------------------------
- * "precision": JCM_PRECISION_*  (the reference is fp32 throughout)
- * "n_joints" : K, default 9      (main.py:458)
+ * jcm_set_option stores a value, jcm_get_option reads it back.  An unknown key or a value outside the range is JCM_ERR_ARG (nothing is
+ * stored); a key marked "before" is JCM_ERR_STATE once jcm_finalize has run, every other key may be set at any time.
+ * Range: a..b inclusive (no b: up to INT_MAX); a|b = these two values only; bool = any non-zero value is stored as 1.
+ * Environment: the variable, read ONCE per handle by jcm_create (atoi), replaces the default; a later jcm_set_option wins over it.
+ * This table is the list of options (csrc/options.h is its counterpart in the library; tests/test_gpu_options.py compares the two).
+ *
+ *   key                default  range     settable  environment          meaning
+ *   "precision"        0        0..1      before    -                    JCM_PRECISION_* (the reference is fp32 throughout)
+ *   "n_joints"         9        1..9      before    -                    K, the joints of the model (main.py:458)
+ *   "f32_conv"         0        0|2       before    -                    fp32 handles: arithmetic of the direct convolution kernels (2 = fp16x3 split)
+ *   "split_min_wgs"    128      0..       any       -                    "f32_conv" = 2: grids smaller than this keep the exact kernel
+ *   "profile"          0        bool      any       -                    HIP events around every conv launch (jcm_profile_read)
+ *   "conv9_fft"        1        bool      any       -                    stride-1 convolutions in the frequency domain where the shape allows
+ *   "call_order"       1        bool      any       -                    calls of different handles on one device are ordered on the GPU
+ *   "fft_single"       1        bool      any       -                    bf16 handles: one fp16 part per operand of the channel product (0 = two bf16 parts)
+ *   "fft_t16"          1        bool      any       -                    bf16 handles, "fft_single" = 1: 16-bit row-transformed tensors and product spectra
+ *   "fft_rows_mfma"    1        bool      any       -                    bf16 handles, 16-bit tensors: conv5's inverse row pass on the matrix cores
+ *   "fft_windows"      1        bool      any       -                    fp32 training step: wide layers on 32 x 32 overlap-save windows
+ *   "fft_fuse"         3        0..3      any       -                    hand-overs in row-transformed form: bit 0 = across the max pool, bit 1 = across the branch merge
+ *   "fft_tiles"        1        bool      any       JCM_FFT_TILES        fp32 handles: conv2_fullres -> pool -> conv3 as 2 x 2 tiles of the 120 x 180 map
+ *   "fft_logits_rows"  1        bool      any       JCM_FFT_LOGITS_ROWS  fp32 handles: the logits layer contracts the channels on conv5's row spectra
+ *   "fft_reg"          1        bool      any       JCM_FFT_REG          register-resident transform kernels where they exist (0 = the LDS kernels: A/B arm)
+ *   "fft_cache_gb"     64       0..1048576  any     JCM_FFT_CACHE_GB     bound of the filter-spectra cache in GB
+ *   "bf16_hpool"       1        bool      any       -                    bf16 handles: horizontal half of pool2 in conv2's epilogue
+ *   "sm_algo"          3        1|3       any       -                    spatial model: 3 = every transform in LDS, 1 = direct sliding-window kernel
+ *   "sm_chunk"         32       1..       any       -                    training step: images per slice of the spatial model's backward pass
+ *   "micro_batch"      0        0..       any       -                    jcm_forward walks a batch in slices of this many images (0 = 256 bf16 / 64 fp32)
+ *   "debug_skip"       0        0..127    any       -                    bisecting aid (jcm_pd_forward): bit i leaves launch group i out; results are then garbage
+ *
+ * In more detail:
  * "f32_conv"  : fp32 handles only; arithmetic of the DIRECT (not frequency-domain) convolution kernels, i.e. of every layer when
  *              "conv9_fft" = 0 and of the shapes the frequency-domain route does not take otherwise: 0 (default) = the exact fp32 MFMA
  *              chain; 2 = the stride-1 layers with Cin % 16 == 0 and Cout % 128 == 0 as two-way fp16 operand splits with three
  *              products on the 16-bit matrix cores (fp32-class error; every operand tensor -- weights, layer inputs, gradients --
  *              is lifted into the fp16 range by its own power-of-two scale first), and the frequency-domain route off: the
  *              A/B arm of that route.  (1, three bf16 parts / six products, was retired in round 5: JCM_ERR_ARG.)
- * "split_min_wgs": any time; grids smaller than this keep the exact kernel (default 128, 0 = always split).
- * All three must be set before jcm_finalize.
- * "profile"  : 0/1, any time: bracket every MFMA conv launch with HIP events on the launch
+ * "split_min_wgs": grids smaller than this keep the exact kernel (0 = always split).
+ * "profile"  : bracket every MFMA conv launch with HIP events on the launch
  *              stream; read the totals back with jcm_profile_read.  Events come from a pool owned by the
  *              handle (created on first use, recycled by jcm_profile_read and by switching the option on,
  *              destroyed by jcm_destroy), so a profiled step only records.
- * "conv9_fft": any time, default 1: stride-1 convolutions in the frequency domain (conv_fft*.hip: in-LDS FFTs around one complex channel
+ * "conv9_fft": stride-1 convolutions in the frequency domain (conv_fft*.hip: in-LDS FFTs around one complex channel
  *              product per frequency on the bf16 matrix cores with split operands, cgemm_split.hip) -- every such layer of an fp32
  *              handle, the wide 9x9 layers of a bf16 handle -- whenever the shape allows (Cin % 64 == 0, map + kernel - 1 <= 192);
  *              0 = the direct MFMA kernels.  The training step of an fp32 handle takes the same route (forward, data and weight
  *              gradients); a bf16 handle trains on the direct bf16 kernels.  Filter spectra are built per (layer, map size) on
- *              first use (11.4 GB for the full-width model on 60x90 maps; cache bound: environment JCM_FFT_CACHE_GB, default 64).
- *              Environment JCM_FFT_REG=0 (read once per process): the LDS kernels instead of the register-resident transforms of
- *              csrc/conv_fft_rows_reg.hip (inverse column / row passes, the bf16 forward row pass, the fused inverse + forward row
- *              pass) -- the A/B arm; results agree to fp32 rounding.
+ *              first use (11.4 GB for the full-width model on 60x90 maps; "fft_cache_gb" bounds the cache: a layer that would grow it
+ *              past the bound drops every other layer's spectra first).
  *              An fp32 handle WITH TRAINING STATE holds more: a second 11.4 GB set of spectra of the flipped, transposed filters for
  *              the data gradient (both sets are repacked after every update) and up to 7.5 GB of weight-gradient scratch (the per-frequency
  *              products P and the column sums R of conv5) in the workspace arena -- about 31 GB beside the 6 GB of activations.
- * "call_order": any time, default 1: calls of different handles on one device are ordered one after the other on the GPU -- an entry
+ * "call_order": calls of different handles on one device are ordered one after the other on the GPU -- an entry
  *              point holds a per-device lock while it enqueues, makes its stream wait for the previous call of another stream and records
  *              an event behind its last kernel -- so they may come from different host threads and streams and results do not depend on
  *              the interleaving.  0 takes the handle out of that chain (debugging: tools/determinism.py).
- * "fft_single": any time, default 1 (bf16 handles): the channel product of the frequency-domain route on ONE fp16 part per operand -- spectra scaled
+ * "fft_single": (bf16 handles): the channel product of the frequency-domain route on ONE fp16 part per operand -- spectra scaled
  *              by one power of two per image (derived from a rigorous bound of the spectrum, so an image's result does not depend on its batch), rounded once to fp16's 11 significant bits, one real product per multiply,
  *              32 channels per GEMM stage.  The layer's input and output tensors are bf16 (8 bits): the spectra are eight times finer.
  *              0 = two bf16 parts per operand, three products (rounds 2-3).  Changing it drops the cached filter spectra.
@@ -89,25 +114,26 @@ int jcm_abi_version(void);
  *              97.6 % (part detector) / 96.3 % (spatial model), the same as the strict arm's 97.4 / 96.4 % and the direct bf16 MFMA
  *              kernels' 97.4 / 96.4 %, and 100 % / 99.9 % of the joints whose fp32 top-2 margin is clear of the bf16 noise
  *              (tests/test_gpu_argmax_agreement.py).
- * "fft_windows": any time, default 1 (fp32 handles with training state): the training step runs its wide 60x90 layers (conv4_fullres, conv5 -- every
+ * "fft_windows": (fp32 handles with training state): the training step runs its wide 60x90 layers (conv4_fullres, conv5 -- every
  *              layer with Cin * Cout >= 128 * 256 (round 6; 256 * 512 before) whose map has at least 1.5 x the frequencies of a window: conv3_fullres and the 30 x 45 maps of conv3_halfres / conv4_halfres too) on 32 x 32 overlap-save windows: forward, data
  *              gradient and weight gradient see 3 x 4 windows per image as a batch of 12 B images on a 32 x 32 circular transform, so the filter-sized
  *              spectra (what bounds the step at 16 images per GPU) shrink 5.8x.  0 = the 64 x 96 transform of the whole map (round 3).
- * "fft_t16"  : any time, default 1 (bf16 handles with "fft_single" = 1): the row-transformed tensors between the row and the column passes of
+ * "fft_t16"  : (bf16 handles with "fft_single" = 1): the row-transformed tensors between the row and the column passes of
  *              the frequency-domain route (half of the transform passes' HBM traffic) as complex fp16 in block floating point -- one power-of-two
  *              scale per (image, row, 64 channels) tile forward and per (image, kx, 64 channels) tile inverse, 11 significant bits like the
  *              spectra; and the product spectra between the channel GEMM and the inverse column pass as complex fp16 under a CONSTANT
  *              power-of-two shift (2^-(ceil(log2 Cin) + 14): the scaled operands bound every product, so nothing can overflow and typical
  *              entries sit fourteen binades above fp16's smallest normal number; round 5).  0 = complex fp32 for all three (round 3).
- * "fft_tiles": any time, default 1 (fp32 handles, with "fft_fuse" bit 0): conv2 of a 120 x 180 map -> pool -> conv3 runs as 2 x 2 tiles of 60 x 90, each with its
+ * "fft_tiles": (fp32 handles, with "fft_fuse" bit 0): conv2 of a 120 x 180 map -> pool -> conv3 runs as 2 x 2 tiles of 60 x 90, each with its
  *              2-pixel halo in the 64 x 96 transform of the 60 x 90 maps (a quarter of the filter spectra, register transform kernels).  0 = the whole map.
- *              Environment JCM_FFT_TILES=0 (read once per process) turns the tiles off as well.
- * "fft_logits_rows": any time, default 1 (fp32 handles without training state): the logits layer conv6 behind conv5's row-transformed hand-over (60 x 90 maps:
+ *              The tile kernels are register kernels: "fft_reg" = 0 turns the tiles off as well.
+ * "fft_logits_rows": (fp32 handles without training state): the logits layer conv6 behind conv5's row-transformed hand-over (60 x 90 maps:
  *              96-point rows, at most 64 rows, at most 16 output channels) contracts the input channels and the nine vertical taps directly on the row
  *              spectra -- one fp16 matrix product per kx with K = 9 x Cin, rows outside the map read as zeros -- and runs one inverse row pass: no column
  *              passes, no padded filter spectra (58 MB of operand instead of 411 MB).  0 = conv6 as a whole frequency-domain layer.
- *              Environment JCM_FFT_LOGITS_ROWS=0 (read once per process) turns the route off as well.
- * "fft_fuse" : any time, default 3 (jcm_pd_forward / jcm_forward on the frequency-domain route): hand-overs in row-transformed form, ONE kernel doing the
+ * "fft_reg"  : 0 = the LDS kernels instead of the register-resident transforms of csrc/conv_fft_rows_reg.hip (inverse column / row passes,
+ *              the bf16 forward row pass, the fused inverse + forward row pass) -- the A/B arm; results agree to fp32 rounding.
+ * "fft_fuse" : (jcm_pd_forward / jcm_forward on the frequency-domain route): hand-overs in row-transformed form, ONE kernel doing the
  *              inverse row transform + bias / ReLU / BatchNorm of the producing layer, the op between the layers and the forward row transform of the
  *              consuming layer.  bit 0 (fp32 handles) = conv2 -> 2x2 max pool -> conv3: a work group owns a row pair, takes the 2x2 maximum in LDS
  *              and transforms the pooled row; neither conv2's output nor the pooled map reaches HBM.  bit 1 = conv4_fullres -> branch merge ->
@@ -118,23 +144,24 @@ int jcm_abi_version(void);
  *              first: the last fp32 bit of the coarse terms, as the register merge of bf16 handles has done since round 5), third = correctly rounded
  *              x / 3 on fp32 handles, one multiplication by RN(1/3) on bf16 handles (against the quotient: the bf16 rounding of two merged values in a
  *              million).  0 = the separate kernels of round 5 (A/B arm; held by the same tests).
- * "fft_rows_mfma" : any time, default 1 (bf16 handles on the one-part route with 16-bit row-transformed tensors): conv5's 96-point inverse row pass as a MATRIX
+ * "fft_rows_mfma" : (bf16 handles on the one-part route with 16-bit row-transformed tensors): conv5's 96-point inverse row pass as a MATRIX
  *              PRODUCT on the matrix cores (rows_inv_mfma_kernel, conv_fft_rows_mfma.hip): T' (complex fp16) times the 96 x 98 real inverse-transform
  *              matrix held as two fp16 parts (22 significant bits: as exact as the fp32 butterflies), bias / ReLU / BatchNorm on the accumulators, planar
  *              bf16 out.  The register kernel it replaces is bound by vector-ALU issue (a 96-point transform is ~1000 scalar fp32 instructions per row
  *              and channel).  The two arms agree to fp32-level noise in front of the bf16 rounding (rms 1e-5 of the logit scale).  0 = the register kernel.
- * "bf16_hpool" : any time, default 1 (bf16 handles): the horizontal half of the 2x2 max pool behind conv2 is taken in conv2's epilogue (a lane pair of
+ * "bf16_hpool" : (bf16 handles): the horizontal half of the 2x2 max pool behind conv2 is taken in conv2's epilogue (a lane pair of
  *              conv5_strip_bf16_kernel is a pixel pair; even widths) and a two-row kernel finishes the pool: the full-width conv2 map is neither
  *              written nor re-read.  Bit-identical to the 2x2 pool kernel (rounding to bf16 is monotonic).  0 = the 2x2 pool kernel.
- * "sm_algo"  : any time; the pairwise convolutions of the spatial model (main.py:83-87): 3 (default) = every 120x180 transform in LDS,
+ * "sm_algo"  : the pairwise convolutions of the spatial model (main.py:83-87): 3 = every 120x180 transform in LDS,
  *              hand-written (sm_fused.hip; jcm_conv_mrf, the prior spectra and the training step's backward use the whole-frame
  *              kernels of sm_lds.hip); 1 = direct sliding-window kernel, the independent cross-check.  Both pass the same parity
  *              tests.  (Rounds 1-4 also had two rocFFT routes, 0 and 2; the library links no FFT library any more.)
- *              "sm_chunk": images per slice of the training step's spatial-model backward (default 32).
- * "micro_batch": any time; jcm_forward walks its batch in slices of this many images, so the workspace is
- *              sized for one slice (a rank's share of BASELINE configs[3]'s 2048 images fits).  0 (default)
+ *              "sm_chunk": images per slice of the training step's spatial-model backward.
+ * "micro_batch": jcm_forward walks its batch in slices of this many images, so the workspace is
+ *              sized for one slice (a rank's share of BASELINE configs[3]'s 2048 images fits).  0
  *              = 256 for bf16 handles, 64 for fp32 handles. */
 int jcm_set_option(jcm_handle h, const char* key, int64_t value);
+int jcm_get_option(jcm_handle h, const char* key, int64_t* value);
 
 /* -- parameters -----------------------------------------------------------------------------
  * Replaces tf.get_variable + Saver.restore (main.py:147,153,484,487,612).  `name` is the

@@ -24,6 +24,7 @@ SIGNATURES = {
     'jcm_last_error': (ctypes.c_char_p, []),
     'jcm_abi_version': (ctypes.c_int, []),
     'jcm_set_option': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.c_int64]),
+    'jcm_get_option': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     'jcm_set_tensor': (ctypes.c_int, [_handle, ctypes.c_char_p, _c_float_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),
     'jcm_finalize': (ctypes.c_int, [_handle]),
     'jcm_conv_layer': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _c_float_p,

@@ -22,7 +22,6 @@
 // (consecutive lanes = consecutive channels).  Twiddles come from one table per device, built on the host in double precision.
 // Reference semantics: conv2d SAME stride 1 + bias + ReLU + BatchNorm (main.py:133-135,156-169).
 #include <cmath>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -212,21 +211,6 @@ static bool sizes_of(int H, int W, int ks, Sizes* s, int circ = 0) {
   return (ks == 9 || ks == 5) && H + ks - 1 <= 192 && W + ks - 1 <= 192 && pick(H + 4, &s->NY) && pick(W + 4, &s->NX);
 }
 static int pad64(int c) { return (c + CB - 1) / CB * CB; }
-// JCM_FFT_REG=0 (environment, read once): the LDS kernels for every pass -- the A/B arm of the register kernels (conv_fft_rows_reg.hip)
-static bool fft_reg_on() {
-  static const bool on = [] { const char* e = std::getenv("JCM_FFT_REG"); return !e || std::atoi(e) != 0; }();
-  return on;
-}
-// JCM_FFT_TILES=0 (environment, read once): conv2_fullres -> pool -> conv3 on the whole 120 x 180 map -- the A/B arm of the 2 x 2 tiles (ConvArgs::tiles)
-static bool fft_tiles_on() {
-  static const bool on = [] { const char* e = std::getenv("JCM_FFT_TILES"); return !e || std::atoi(e) != 0; }();
-  return on;
-}
-// JCM_FFT_LOGITS_ROWS=0 (environment, read once): the logits layer as a whole frequency-domain layer -- the A/B arm of the contraction on the row spectra (conv_fft_logits.hip)
-static bool fft_logits_rows_on() {
-  static const bool on = [] { const char* e = std::getenv("JCM_FFT_LOGITS_ROWS"); return !e || std::atoi(e) != 0; }();
-  return on;
-}
 static int padn(int c, int n) { return (c + n - 1) / n * n; }
 
 int persistent_grid(const void* kernel, int ntiles, int threads, int dyn_lds) {
@@ -361,8 +345,8 @@ size_t conv_fft_handover_bytes(const ConvArgs& a, int ks) {      // T[kx][c/16][
   if (!sizes_of(a.H, a.W, ks, &s)) return 0;
   return (size_t)a.B * (s.NX / 2 + 1) * a.H * a.Cout * sizeof(cf);
 }
-bool conv_fft_win_gather_supported(int win, int Cin) { return fft_reg_on() && cfft_rows_fwd_win_reg_supported(win, Cin); }
-bool conv_fft_win_scatter_supported(int win, int Cout) { return fft_reg_on() && win == 32 && Cout % 64 == 0; }      // rows_inv_reg_kernel<32, 0, false>
+bool conv_fft_win_gather_supported(int win, int Cin, bool fft_reg) { return fft_reg && cfft_rows_fwd_win_reg_supported(win, Cin); }
+bool conv_fft_win_scatter_supported(int win, int Cout, bool fft_reg) { return fft_reg && win == 32 && Cout % 64 == 0; }      // rows_inv_reg_kernel<32, 0, false>
 // the fused hand-overs across a max pool / the branch merge (FftNext, conv_fft_rows_fused.hip)
 bool conv_fft_pool_fusable(const ConvArgs& a, int ks, int ks_next) {
   Sizes s, n;
@@ -376,14 +360,14 @@ size_t conv_fft_pool_handover_bytes(const ConvArgs& a, int ks_next) {      // T[
 // 2 x 2 tiles: a 5x5 layer whose output goes through the pool hand-over into a 5x5 layer, on the model's 120 x 180 map (cfft_tiles_supported)
 bool conv_fft_tiles_supported(const ConvArgs& a, int ks, int ks_next) {
   Sizes s;
-  return fft_reg_on() && fft_tiles_on() && ks == 5 && ks_next == 5 && !a.circ && !a.win_map && a.B >= 1 && conv_fft_pool_fusable(a, ks, ks_next) &&
+  return a.fft_reg && ks == 5 && ks_next == 5 && !a.circ && !a.win_map && a.B >= 1 && conv_fft_pool_fusable(a, ks, ks_next) &&
          a.H % 4 == 0 && a.W % 4 == 0 && sizes_of(a.H / 2, a.W / 2, ks, &s) && cfft_tiles_supported(s.NY, s.NX, a);
 }
 // h16: bf16 handles on the one-part route with 16-bit row-transformed tensors -- the register kernel only (the model's geometry)
-bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool h16) {
+bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool fft_reg, bool h16) {
   Sizes s;
   if (!conv_fft_fusable(a, ks, ks_next) || !sizes_of(a.H, a.W, ks, &s)) return false;
-  const bool reg = fft_reg_on() && cfft_rows_inv_merge_fwd_reg_supported(s.NX, a, m, (ks - 1) / 2);
+  const bool reg = fft_reg && cfft_rows_inv_merge_fwd_reg_supported(s.NX, a, m, (ks - 1) / 2);
   return h16 ? reg : (reg || cfft_rows_inv_merge_fwd_supported(s.NX, a, m));
 }
 // a.wp = the split filter spectra of THIS map size and kernel size; `work` = conv_fft_workspace_bytes(a, ks, np) bytes.  g0 / g1: optional
@@ -472,7 +456,7 @@ hipError_t conv_fft_f32(const ConvArgs& a0, int ks, int np, int in_layout, int o
   const cf* twy = twb + tw_offset(s.NY);
   const float norm = 1.0f / (float)(s.NY * s.NX);
   const cf* Tin = t_in ? static_cast<const cf*>(t_in) : T;
-  const bool fft_reg = fft_reg_on();
+  const bool fft_reg = a.fft_reg != 0;
   if (!xs_ready) {
     if (merge && !t_in) {
       if (!(fft_reg && cfft_rows_fwd_merge_reg(s.NX, a, *merge, in_layout, T, sc.tmax, st, sc.t16_fwd))) cfft_rows_fwd_merge(s.NX, a, *merge, in_layout, T, twx, sc.tmax, st, sc.t16_fwd);
@@ -518,7 +502,7 @@ hipError_t conv_fft_f32(const ConvArgs& a0, int ks, int np, int in_layout, int o
 // handed over at a 96-point row length.  No column pass, no filter spectra: the operand A (conv_fft_logits_pack) and one inverse row pass.
 bool conv_fft_logits_rows_supported(const ConvArgs& a, int ks) {
   Sizes s;
-  return fft_logits_rows_on() && ks == 9 && !a.circ && !a.tiles && !a.win_map && conv_fft_supported(a, ks) && sizes_of(a.H, a.W, ks, &s) && cfft_logits_rows_supported(s.NX, a);
+  return ks == 9 && !a.circ && !a.tiles && !a.win_map && conv_fft_supported(a, ks) && sizes_of(a.H, a.W, ks, &s) && cfft_logits_rows_supported(s.NX, a);
 }
 size_t conv_fft_logits_weight_bytes(int H, int W, int Cin) {
   Sizes s;

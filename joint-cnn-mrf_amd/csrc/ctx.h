@@ -84,7 +84,7 @@ struct jcm_ctx {
   int precision = JCM_PRECISION_F32;
   int K = 9;
   bool finalized = false;
-  // ---- options (jcm_set_option) ----
+  // ---- options (options.h holds the table of keys, ranges and environment defaults; these initialisers are the defaults) ----
   int f32_conv = 0;             // fp32 handles: 0 = default (frequency domain, or the exact fp32 MFMA chain with conv9_fft = 0), 2 = the direct fp16x3 split kernels (forward and gradients)
   int split_min_wgs = 128;      // grids smaller than this keep the exact kernel (option "split_min_wgs")
   int sm_algo = 3;              // 3 = every transform in LDS (sm_fused.hip), 1 = direct sliding-window VALU kernel (the cross-check)
@@ -95,6 +95,8 @@ struct jcm_ctx {
   int fft_single = 1;           // bf16 handles: the channel GEMM on ONE scaled fp16 part per operand (np = 5; 0 = two bf16 parts, three products)
   int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)
   int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (ConvArgs::rows_mfma; conv_fft_rows_mfma.hip)
+  int fft_reg = 1;              // the register-resident transform kernels of conv_fft_rows_reg.hip where they exist (ConvArgs::fft_reg); 0 = the LDS kernels for every pass
+  int fft_cache_gb = 64;        // bound of the filter-spectra cache fft_w (run_conv_fft drops the other layers' spectra before it grows past it)
   int fft_win = 1;              // training step of fp32 handles: frequency-domain layers on 32 x 32 overlap-save windows where that shrinks the filter-sized spectra (jcm_train.hip)
   int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel
   int sm_chunk = 32;            // training step: images per slice of the spatial model's backward pass (81 + 10 spectra per image live at once)
@@ -137,7 +139,7 @@ struct jcm_ctx {
   std::vector<WordBlock> fft_blocks;
   int fft_block_i = 0, fft_word_i = 0;      // next free word: fft_blocks[fft_block_i].p + fft_word_i
   // per-layer HIP-event timing on the launch stream (bench.py roofline object)
-  bool profile = false;
+  int profile = 0;              // option "profile"
   std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
   std::vector<hipEvent_t> event_pool;   // recycled by jcm_profile_read / "profile"=0, destroyed by jcm_destroy
   // ---- call ordering (CallOrder) ----

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "options.h"
 
 using namespace jcm;
 
@@ -290,6 +291,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.CoutP = L->cout; a.relu_bn = L->has_bn ? 1 : 0;
   a.circ = circ;
   a.rows_mfma = c->fft_rows_mfma;
+  a.fft_reg = c->fft_reg;
   const size_t mark = c->arena_off;
   const int np = fft_np(c);      // operand form of the channel GEMM (cgemm_split.hip)
   // fp32 handles, the pool hand-over conv2 -> pool -> conv3 on the model's 120 x 180 map: the layer runs as 2 x 2 tiles in the 64 x 96 transform of the
@@ -304,7 +306,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   void* work = arena_alloc<char>(c, lrows ? conv_fft_logits_workspace_bytes(a) : conv_fft_workspace_bytes(a, L->ks, np));
   c->arena_off = mark;                                   // scratch of this layer only: later layers run behind it on the stream
   if (c->dry) return JCM_OK;
-  // Filter spectra are cached per (layer, map size).  The cache is bounded (JCM_FFT_CACHE_GB, default 64): a caller that walks many
+  // Filter spectra are cached per (layer, map size).  The cache is bounded (option "fft_cache_gb", default 64): a caller that walks many
   // image sizes (7.7 GB per size for conv5) makes it drop every spectrum that is not this layer's before it grows past the bound.
   const std::string key = scope + (circ ? "@win" : lrows ? "@rows" : "@") + std::to_string(wH) + "x" + std::to_string(wW);
   const size_t wbytes = lrows ? conv_fft_logits_weight_bytes(wH, wW, L->cin) : conv_fft_weight_bytes(wH, wW, L->ks, L->cin, L->cout, np, circ);
@@ -312,7 +314,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   // forwards and larger batches -- so that a loop that alternates training steps and evaluation does not re-pack gigabytes and stall the stream at
   // every flip (round 5 dropped the other geometry here); the cache bound below is what limits the footprint.)
   if (!c->fft_w.count(key)) {
-    static const size_t cap = [] { const char* e = std::getenv("JCM_FFT_CACHE_GB"); return (size_t)(e ? std::atoi(e) : 64) << 30; }();
+    const size_t cap = (size_t)c->fft_cache_gb << 30;
     const size_t need = wbytes;
     size_t held = 0;
     for (auto& kv : c->fft_w) held += kv.second.bytes;
@@ -625,7 +627,7 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
   if ((!bf || h16) && !c->debug_skip && takes_fft(c, L4, B, hh, ww) && takes_fft(c, L5, B, hh, ww) && L4->cout == L5->cin) {
     ConvArgs a{};
     a.B = B; a.H = hh; a.W = ww; a.Cin = L4->cin; a.Cout = L4->cout;
-    fuse45 = (c->fft_fuse & 2) && conv_fft_merge_fusable(a, L4->ks, L5->ks, mg, h16);
+    fuse45 = (c->fft_fuse & 2) && conv_fft_merge_fusable(a, L4->ks, L5->ks, mg, c->fft_reg, h16);
   }
   // branch outputs survive the per-branch scratch, so carve them first
   void* t45 = nullptr;
@@ -782,7 +784,39 @@ int sm_forward_impl(jcm_ctx* c, const float* hm, int Ca, const float* extra, int
   return fail(JCM_ERR_STATE, "sm_algo must be 3 (transforms in LDS) or 1 (direct)");
 }
 
+const Option* find_option(const char* key) {
+  for (const Option& o : kOptions)
+    if (key && std::strcmp(key, o.name) == 0) return &o;
+  return nullptr;
+}
+// the value as the option stores it, or JCM_ERR_ARG
+int option_value(const Option& o, int64_t* value) {
+  if (o.kind == Option::BOOL) *value = *value != 0;
+  else if (o.kind == Option::RANGE ? (*value < o.lo || *value > o.hi) : (*value != o.lo && *value != o.hi))
+    return fail(JCM_ERR_ARG, std::string(o.name) + " must be " + std::to_string(o.lo) + (o.kind == Option::RANGE ? " .. " : " or ") + std::to_string(o.hi) + " (include/jcm.h)");
+  return JCM_OK;
+}
+
 }  // namespace
+
+namespace jcm {
+int option_profile(jcm_ctx* c, int64_t value) {
+  if (value && !c->profile) {
+    DeviceGuard g(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    prof_release_all(c, false);
+  }
+  return JCM_OK;
+}
+int option_fft_single(jcm_ctx* c, int64_t value) {
+  if (value != c->fft_single) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (auto& kv : c->fft_w) (void)hipFree(kv.second.p);
+    c->fft_w.clear();
+  }
+  return JCM_OK;
+}
+}  // namespace jcm
 
 extern "C" {
 
@@ -802,6 +836,12 @@ int jcm_create(int device, void* stream, jcm_handle* out) {
   jcm_ctx* c = new jcm_ctx();
   c->device = device;
   c->stream = static_cast<hipStream_t>(stream);
+  // the environment supplies defaults, read here and nowhere else (a value the option would refuse is ignored)
+  for (const Option& o : kOptions) {
+    const char* e = o.env ? std::getenv(o.env) : nullptr;
+    int64_t v = e ? std::atoi(e) : 0;
+    if (e && option_value(o, &v) == JCM_OK) c->*o.field = (int)v;
+  }
   *out = c;
   return JCM_OK;
 }
@@ -823,99 +863,20 @@ int jcm_destroy(jcm_handle h) {
 
 int jcm_set_option(jcm_handle h, const char* key, int64_t value) {
   JCM_TRY(check(h, false));
-  const std::string k = key ? key : "";
-  if (k == "profile") {   // allowed at any time; switching it on starts a fresh record (events go back to the pool)
-    if (value != 0 && !h->profile) {
-      DeviceGuard g(h->device);
-      (void)hipStreamSynchronize(h->stream);
-      prof_release_all(h, false);
-    }
-    h->profile = value != 0;
-    return JCM_OK;
-  }
-  if (k == "micro_batch") {   // allowed at any time
-    if (value < 0) return fail(JCM_ERR_ARG, "micro_batch must be >= 0 (0 = default: 256 bf16 / 64 fp32)");
-    h->micro_batch = (int)value;
-    return JCM_OK;
-  }
-  if (k == "debug_skip") {   // allowed at any time; bisecting aid: groups of launches of jcm_pd_forward that are left out (results are then garbage)
-    h->debug_skip = (int)value;
-    return JCM_OK;
-  }
-  if (k == "call_order") {   // allowed at any time; 0 = debugging: this handle's calls are not ordered against other handles' on the device
-    h->call_order = value != 0;
-    return JCM_OK;
-  }
-  if (k == "conv9_fft") {  // allowed at any time
-    h->conv9_fft = value != 0;
-    return JCM_OK;
-  }
-  if (k == "fft_single") {   // allowed at any time (bf16 handles); the filter spectra have another form: the cache is dropped
-    if ((value != 0) != (h->fft_single != 0)) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      for (auto& kv : h->fft_w) (void)hipFree(kv.second.p);
-      h->fft_w.clear();
-    }
-    h->fft_single = value != 0;
-    return JCM_OK;
-  }
-  if (k == "fft_windows") {   // allowed at any time (fp32 handles with training state)
-    h->fft_win = value != 0;
-    return JCM_OK;
-  }
-  if (k == "fft_fuse") {   // allowed at any time (fp32 handles): bit 0 = conv2 -> pool -> conv3, bit 1 = conv4_fullres -> merge -> conv5 as fused hand-overs
-    if (value < 0 || value > 3) return fail(JCM_ERR_ARG, "fft_fuse must be 0..3 (bit 0: pool hand-over, bit 1: merge hand-over)");
-    h->fft_fuse = (int)value;
-    return JCM_OK;
-  }
-  if (k == "fft_tiles") {   // allowed at any time (fp32 handles): conv2_fullres -> pool -> conv3 as 2 x 2 tiles of the 120 x 180 map (fft_fuse bit 0)
-    h->fft_tiles = value != 0;
-    return JCM_OK;
-  }
-  if (k == "fft_logits_rows") {   // allowed at any time (fp32 handles): the logits layer behind conv5's hand-over on the row spectra (conv_fft_logits.hip); 0 = a whole frequency-domain layer
-    h->fft_logits_rows = value != 0;
-    return JCM_OK;
-  }
-  if (k == "bf16_hpool") {   // allowed at any time (bf16 handles)
-    h->bf16_hpool = value != 0;
-    return JCM_OK;
-  }
-  if (k == "fft_rows_mfma") {   // allowed at any time (bf16 handles with 16-bit row-transformed tensors)
-    h->fft_rows_mfma = value != 0;
-    return JCM_OK;
-  }
-  if (k == "fft_t16") {   // allowed at any time (bf16 handles, fft_single = 1)
-    h->fft_t16 = value != 0;
-    return JCM_OK;
-  }
-  if (k == "sm_chunk") {  // allowed at any time
-    if (value < 1) return fail(JCM_ERR_ARG, "sm_chunk must be >= 1");
-    h->sm_chunk = (int)value;
-    return JCM_OK;
-  }
-  if (k == "split_min_wgs") {   // allowed at any time
-    if (value < 0) return fail(JCM_ERR_ARG, "split_min_wgs must be >= 0");
-    h->split_min_wgs = (int)value;
-    return JCM_OK;
-  }
-  if (k == "sm_algo") {   // allowed at any time
-    if (value != 1 && value != 3) return fail(JCM_ERR_ARG, "sm_algo must be 3 (every transform in LDS, default) or 1 (direct sliding-window kernel); the rocFFT routes 0 and 2 were removed in round 5");
-    h->sm_algo = (int)value;
-    return JCM_OK;
-  }
-  if (h->finalized) return fail(JCM_ERR_STATE, "options must be set before jcm_finalize");
-  if (k == "precision") {
-    if (value != JCM_PRECISION_F32 && value != JCM_PRECISION_BF16) return fail(JCM_ERR_ARG, "precision must be 0 (f32) or 1 (bf16)");
-    h->precision = (int)value;
-  } else if (k == "f32_conv") {
-    if (value != 0 && value != 2) return fail(JCM_ERR_ARG, "f32_conv must be 0 (default) or 2 (fp16x3 direct split kernels); 1 (bf16x6) was retired in round 5");
-    h->f32_conv = (int)value;
-  } else if (k == "n_joints") {
-    if (value < 1 || value > 9) return fail(JCM_ERR_ARG, "n_joints must be in [1,9]");
-    h->K = (int)value;
-  } else {
-    return fail(JCM_ERR_ARG, "unknown option '" + k + "'");
-  }
+  const Option* o = find_option(key);
+  if (!o) return fail(JCM_ERR_ARG, std::string("unknown option '") + (key ? key : "") + "'");
+  if (o->before_finalize && h->finalized) return fail(JCM_ERR_STATE, std::string("option '") + o->name + "' must be set before jcm_finalize");
+  JCM_TRY(option_value(*o, &value));
+  if (o->on_change) JCM_TRY(o->on_change(h, value));
+  h->*o->field = (int)value;
+  return JCM_OK;
+}
+
+int jcm_get_option(jcm_handle h, const char* key, int64_t* value) {
+  JCM_TRY(check(h, false));
+  const Option* o = find_option(key);
+  if (!o || !value) return fail(JCM_ERR_ARG, std::string("unknown option '") + (key ? key : "") + "' or null value pointer");
+  *value = h->*o->field;
   return JCM_OK;
 }
 

@@ -6,7 +6,6 @@
 #include <cmath>
 #include <cstring>
 
-#include <cstdlib>
 #include "ctx.h"
 
 using namespace jcm;
@@ -155,16 +154,18 @@ struct LayerFwd {
 // of 4, 3 x 4 windows per map) the same layer has 544 frequencies instead of 3136 and 192 "images" instead of 16: the filter-sized tensors shrink 5.8x, the
 // activation-sized ones (which were 3 % of the traffic) grow 2.1x.
 constexpr int kWin = 32, kWinValid = kWin - 8;
+// a layer takes the windows when its map has at least kWinFreqRatio x the frequencies of a window ...
+constexpr double kWinFreqRatio = 1.5;      // (round 6: 1.5 -- the 30 x 45 maps too, 936 frequencies against 544: 24.03 -> 23.87 ms; rounds 3-5: 2)
+// ... and Cin * Cout >= kWinMinCC
+constexpr long kWinMinCC = 128l * 256;      // (round 6: 128 x 256 = conv3_fullres too, now that the windows are gathered and scattered inside the row passes: 24.20 -> 24.03 ms; 64 x 128: 24.87)
 static bool takes_windows(jcm_ctx* c, const ConvLayer* L, int B, int H, int W, int* TY, int* TX) {
   if (bf(c) || !c->fft_win || !takes_fft(c, L, B, H, W)) return false;
   int NY = 0, NX = 0, MT = 0;
   if (!conv_fft_geometry(H, W, L->ks, B, L->cout, fft_np(c), &NY, &NX, &MT)) return false;
-  static const double fr = [] { const char* e = std::getenv("JCM_WIN_FREQ_RATIO"); return e ? std::atof(e) : 1.5; }();      // (round 6: 1.5 -- the 30 x 45 maps too, 936 frequencies against 544: 24.03 -> 23.87 ms; rounds 3-5: 2)
-  if (fr * kWin * (kWin / 2 + 1) > NY * (NX / 2 + 1)) return false;      // at least half the frequencies, or the larger activation spectra eat the gain (30 x 45 maps: 936 -> 544)
+  if (kWinFreqRatio * kWin * (kWin / 2 + 1) > NY * (NX / 2 + 1)) return false;      // at least half the frequencies, or the larger activation spectra eat the gain (30 x 45 maps: 936 -> 544)
   // ... and filters wide enough that their spectra dominate: the windows cost a gather, a scatter and 2.1x the transform work per channel (measured at 16 images:
   // with every 60 x 90 layer on windows the step stayed at 36 ms -- 9.7 ms saved on filter-sized tensors, as much spent on activation-sized ones)
-  static const long min_cc = [] { const char* e = std::getenv("JCM_WIN_MIN_CC"); return e ? std::atol(e) : 128l * 256; }();      // (round 6: 128 x 256 = conv3_fullres too, now that the windows are gathered and scattered inside the row passes: 24.20 -> 24.03 ms; 64 x 128: 24.87)
-  if ((long)L->cin * L->cout < min_cc) return false;
+  if ((long)L->cin * L->cout < kWinMinCC) return false;
   // ... and a batch small enough: what the windows save (filter-sized traffic, independent of the batch: 9.7 ms per step) is spent again on activation-sized work
   // that grows with it (4.4 ms at 16 images)
   if (B > 32) return false;
@@ -205,9 +206,9 @@ int conv_train_fwd_conv(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int 
     f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(ax, L.ks, fft_np(c)));
     const size_t mark = c->arena_off;
     // (round 6: where the forward row pass can cut the windows out of the map itself, the gathered tensor does not exist)
-    const bool gw = conv_fft_win_gather_supported(kWin, L.cin);
+    const bool gw = conv_fft_win_gather_supported(kWin, L.cin, c->fft_reg);
     float* xw = gw ? nullptr : arena_alloc<float>(c, (size_t)BW * kWin * kWin * L.cin);
-    const bool sw = conv_fft_win_scatter_supported(kWin, L.cout);      // ... and where the inverse row pass can store into the map, neither do the valid regions
+    const bool sw = conv_fft_win_scatter_supported(kWin, L.cout, c->fft_reg);      // ... and where the inverse row pass can store into the map, neither do the valid regions
     float* rw = sw ? static_cast<float*>(f.r) : arena_alloc<float>(c, (size_t)BW * kWinValid * kWinValid * L.cout);
     if (!c->dry && !gw) HIP_TRY(window_gather_f32(static_cast<const float*>(x), xw, B, Hin, Win, L.cin, kWin, TY, TX, 0, c->stream));
     FftLink k;
@@ -314,7 +315,7 @@ int conv_wgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int ldz, int B, fl
     if (!conv_fft_geometry(kWin, kWin, L->ks, BW, L->cout, np, &NY, &NX, &MTx, 1) || !conv_fft_geometry(kWin, kWin, L->ks, BW, L->cin, np, &ny2, &nx2, &MTz, 1))
       return fail(JCM_ERR_STATE, "window geometry of '" + f.scope + "'");
     const size_t mark = c->arena_off;
-    const bool gw = conv_fft_win_gather_supported(kWin, ldz);
+    const bool gw = conv_fft_win_gather_supported(kWin, ldz, c->fft_reg);
     float* zw = gw ? nullptr : arena_alloc<float>(c, (size_t)BW * kWin * kWin * ldz);
     ConvArgs az{};
     az.x = zw; az.B = BW; az.H = kWin; az.W = kWin; az.Cin = ldz; az.Cout = L->cin; az.circ = 1;
@@ -429,9 +430,9 @@ int conv_dgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int B, void* dx, i
         HIP_TRY(flip_transpose_weights(f.L->w_raw, t->scratch_flip, f.L->ks, f.L->cin, f.L->cout, cin_fft, c->stream));
       t->zs = nullptr;
       const size_t mark = c->arena_off;
-      const bool gw = conv_fft_win_gather_supported(kWin, cin_fft);
+      const bool gw = conv_fft_win_gather_supported(kWin, cin_fft, c->fft_reg);
       float* zw = gw ? nullptr : arena_alloc<float>(c, (size_t)BW * kWin * kWin * cin_fft);
-      const bool sw = conv_fft_win_scatter_supported(kWin, f.L->cin);
+      const bool sw = conv_fft_win_scatter_supported(kWin, f.L->cin, c->fft_reg);
       float* xw = sw ? static_cast<float*>(dx) : arena_alloc<float>(c, (size_t)BW * kWinValid * kWinValid * f.L->cin);
       if (!c->dry && !gw) HIP_TRY(window_gather_f32(static_cast<const float*>(dz), zw, B, f.H, f.W, cin_fft, kWin, f.TY, f.TX, 0, c->stream));
       FftLink k;

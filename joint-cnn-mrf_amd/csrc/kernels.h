@@ -66,6 +66,8 @@ struct ConvArgs {
   // conv_fft, bf16 handles with 16-bit row-transformed tensors: the 96-point inverse row pass with planar bf16 output (conv5 of the model) as a matrix product
   // on the matrix cores (conv_fft_rows_mfma.hip).  1 = on where the kernel exists, 0 = the register kernel.
   int rows_mfma = 0;
+  // conv_fft: the register-resident transform kernels (conv_fft_rows_reg.hip) where they exist; 0 = the LDS kernels for every pass, their A/B arm (option "fft_reg")
+  int fft_reg = 1;
   // conv5_strip_bf16 only: the LEFT HALF of the 2x2/2 max pool that follows the layer in its epilogue -- `out` is the [B, H, W / 2, Cout] map of
   // max(pixel 2 i, pixel 2 i + 1) (W even; either activation layout), half the bytes; vpool_2x1() finishes the pool.  The max of two bf16-rounded values is
   // the bf16 rounding of the max: bit-identical to pooling the stored map.
@@ -163,20 +165,21 @@ hipError_t conv_fft_f32(const ConvArgs& a, int ks, int np, int in_layout, int ou
                         const Fp16Scale* sc = nullptr);
 // The logits layer contracted on the row spectra of its input (conv_fft_logits.hip; fp32 handles): a 9x9 layer with Cout <= 16 whose row-transformed input arrives
 // through link.t_in at a 96-point row length, H <= 64.  a.wp = the operand packed by conv_fft_logits_pack (conv_fft_logits_weight_bytes; wscale as above), work =
-// conv_fft_logits_workspace_bytes(a); out fp32 NHWC, bias epilogue.  JCM_FFT_LOGITS_ROWS=0 in the environment turns the route off.
+// conv_fft_logits_workspace_bytes(a); out fp32 NHWC, bias epilogue.
 bool conv_fft_logits_rows_supported(const ConvArgs& a, int ks);
 size_t conv_fft_logits_weight_bytes(int H, int W, int Cin);
 size_t conv_fft_logits_workspace_bytes(const ConvArgs& a);
 hipError_t conv_fft_logits_pack(const float* w_hwio, void* aop, int H, int W, int Cin, int Cout, hipStream_t st, float* wscale);
 hipError_t conv_fft_logits_f32(const ConvArgs& a, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st, const Fp16Scale* sc);
 // the fused hand-overs of FftNext: is there a kernel for this pair of layers, and the size of the row-transformed tensor handed over
-bool conv_fft_win_gather_supported(int win, int Cin);
-bool conv_fft_win_scatter_supported(int win, int Cout);    // ... and its inverse row pass store the valid regions straight into the map?      // can the forward row pass of `win` x `win` overlap-save windows read them straight from the map?
+// (both kernels are register kernels: fft_reg = the handle's option)
+bool conv_fft_win_gather_supported(int win, int Cin, bool fft_reg);      // can the forward row pass of `win` x `win` overlap-save windows read them straight from the map?
+bool conv_fft_win_scatter_supported(int win, int Cout, bool fft_reg);    // ... and its inverse row pass store the valid regions straight into the map?
 bool conv_fft_pool_fusable(const ConvArgs& a, int ks, int ks_next);
-// ... as 2 x 2 tiles of the map (ConvArgs::tiles; JCM_FFT_TILES=0 in the environment turns the route off), and the map size of their filter spectra
+// ... as 2 x 2 tiles of the map (ConvArgs::tiles; register kernels only: needs a.fft_reg), and the map size of their filter spectra
 bool conv_fft_tiles_supported(const ConvArgs& a, int ks, int ks_next);
 size_t conv_fft_pool_handover_bytes(const ConvArgs& a, int ks_next);
-bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool h16 = false);      // h16: bf16 handles (16-bit T / T', bf16 branches)
+bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool fft_reg, bool h16 = false);      // h16: bf16 handles (16-bit T / T', bf16 branches)
 size_t conv_fft_xs_bytes(const ConvArgs& a, int ks, int np);
 // NHWC fp32 -> split spectra (the two forward passes); np = 4: tmax = the (zeroed) device word of this tensor
 hipError_t conv_fft_spectra(const ConvArgs& a, int ks, int np, void* work, void* xs, hipStream_t st, float* tmax = nullptr, int common = 0);

@@ -22,7 +22,6 @@
 // Unnormalised transforms, 1/(120*180) folded into the product;
 // the imaginary parts of the DC / Nyquist bins of a row are dropped as a C2R transform drops them.
 #include <atomic>
-#include <cstdlib>
 
 #include "sm_lds_fft.h"
 
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(NT) void sm_inv_finish_kernel(const float* __restri
                                                              const float2* __restrict__ lhat_t, const float2* __restrict__ phat_t,
                                                              const int* __restrict__ cond, const float* __restrict__ spb, float* __restrict__ logits, int K,
                                                              int C, float* __restrict__ tsave, int nunits, float* __restrict__ part, unsigned* __restrict__ flags,
-                                                             unsigned epoch, int perm) {
+                                                             unsigned epoch, bool per_item) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cf* lds = reinterpret_cast<cf*>(smem);
   cf* cb = lds + CB;
@@ -110,23 +109,20 @@ __global__ __launch_bounds__(NT) void sm_inv_finish_kernel(const float* __restri
   const int pk = tid % WC, pg = tid / WC;
 
   // this work group's units [u0, u1).  Work group i runs on XCD i % 8 (slot i / 8 of that XCD's in-order queue).
-  //   perm 2 -- one work group per item, items dealt so that an XCD owns WHOLE IMAGES: work group i takes joint n % K of image (i % 8) + 8 (n / K), n = i / 8.
+  //   per_item -- one work group per item, items dealt so that an XCD owns WHOLE IMAGES: work group i takes joint n % K of image (i % 8) + 8 (n / K), n = i / 8.
   //             The 32 work groups an XCD runs at a time are then the 9 joints of 3-4 images, walking their pairs in step: at a step they want 2 of an
   //             image's 10 likelihood spectra and one prior per joint -- ~16 distinct spectra for 64 loads, served by that XCD's L2 instead of the fabric.
-  //   perm 0 -- the balanced cut (G a multiple of 8): the ITEMS are split eight ways, one contiguous share per XCD, and an XCD's share of units is cut into
+  //   otherwise -- the balanced cut (G a multiple of 8): the ITEMS are split eight ways, one contiguous share per XCD, and an XCD's share of units is cut into
   //             equal ranges for its G / 8 slots.  A range's predecessor is therefore work group i - 8: the previous slot of the SAME XCD queue, placed on
   //             a CU before this one whatever else shares the GPU -- a work group never waits for one that has not been dispatched, so two handles'
   //             kernels (two streams, two processes) cannot hold each other's CUs in a cycle.  No range crosses an XCD's share: slot 0 has no tail, the
   //             last slot no head.
   const int G = gridDim.x, w = (int)blockIdx.x;
   int u0, u1;
-  if (perm == 2) {
+  if (per_item) {
     const int n = w / 8, b = w % 8 + 8 * (n / K);
     if (b * K >= nunits / PJ) return;      // (the last images of a batch that is not a multiple of 8)
     u0 = (b * K + n % K) * PJ;
-    u1 = u0 + PJ;
-  } else if (perm == 1) {      // one work group per item, in launch order (the A/B arm of 2)
-    u0 = w * PJ;
     u1 = u0 + PJ;
   } else {
     const int nitems = nunits / PJ, xcd = w % 8, slot = w / 8, S = G / 8;
@@ -298,16 +294,14 @@ hipError_t sm_fused_forward(const float* hm, int Ca, const float* extra, int ext
   const int items = B * K, rounds = (items + resident - 1) / resident;
   int G = items;
   if (items > resident && (double)rounds * resident > 1.15 * (double)items) G = resident;      // every range then holds >= C - 1 units (the kernel's cut rule)
-  if (const char* e = std::getenv("JCM_SM_G")) { const int g = std::atoi(e); if (g > 0 && g <= items && (items % g == 0 || g <= resident)) G = g; }      // (tools/sm_time.py sweeps)
   // the cut needs eight XCD shares of whole slots (G a multiple of 8, every range >= C - 1 units: items / 8 >= G / 8); otherwise one work group per item
   if (G != items && (G % 8 != 0 || items / 8 < G / 8)) G = items;
-  static const int perm_env = [] { const char* e = std::getenv("JCM_SM_PERM"); return e ? std::atoi(e) : 2; }();      // (1: items in launch order -- the A/B arm of 2)
-  const int perm = G == items ? (perm_env == 2 ? 2 : 1) : 0;
-  if (perm == 2) G = 8 * ((B + 7) / 8) * K;
+  const bool per_item = G == items;      // one work group per item, dealt so that an XCD owns whole images (round 6 decided the sweeps of G and of the dealing: profiles/r06_*)
+  if (per_item) G = 8 * ((B + 7) / 8) * K;
   float* part = static_cast<float*>(scratch);
   unsigned* flags = reinterpret_cast<unsigned*>(static_cast<char*>(scratch) + (size_t)resident * MHW * sizeof(float));
   hipLaunchKernelGGL(sm_inv_finish_kernel, dim3(G), dim3(NT), LDS_BYTES, st, hm, Ca, extra, extra_ld, sc, sh, lhat_t, phat_t, cond, spbias, logits, K, C, tsave, B * K * (C - 1),
-                     part, flags, epoch, perm);
+                     part, flags, epoch, per_item);
   return hipGetLastError();
 }
 

@@ -2,7 +2,6 @@
 // BatchNorm forward/backward, ReLU / max-pool / bilinear-merge backward, the soft-label spatial
 // cross-entropy and its gradient, global-norm, Adam / momentum updates.  All tensors fp32 NHWC;
 // per-channel reductions accumulate in double (products are formed in fp32, as the reference's fp32 graph forms them).
-#include <cstdlib>
 
 #include "kernels.h"
 
@@ -223,8 +222,7 @@ __global__ __launch_bounds__(256) void bn_apply_pool4_kernel(const float4* __res
 // false: not this case (bf16 / C % 4) -- the caller runs bn_apply and max_pool_2x2
 bool bn_apply_pool(const void* r, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y, void* p, bool bf16, int B, int H, int W, int C,
                    hipStream_t st) {
-  static const bool fused = [] { const char* e = std::getenv("JCM_BN_POOL"); return !e || std::atoi(e) != 0; }();      // JCM_BN_POOL=0: the two kernels (A/B arm)
-  if (!fused || bf16 || C % 4) return false;
+  if (bf16 || C % 4) return false;
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const size_t total = (size_t)B * Ho * Wo * (C / 4), g4 = (total + 255) / 256;
   hipLaunchKernelGGL(bn_apply_pool4_kernel, dim3((unsigned)(g4 > 16384 ? 16384 : g4)), dim3(256), 0, st, static_cast<const float4*>(r), reinterpret_cast<const float4*>(mean),
@@ -343,8 +341,7 @@ hipError_t col_sum(const void* x, bool bf16, size_t N, int C, float* out, double
 // bn_bwd_apply + col_sum of its output in one pass over the tensors (fp32, C % 4 == 0, 256 % (C / 4) == 0; otherwise the two calls)
 hipError_t bn_bwd_apply_colsum(const void* dy, float dy_scale, const void* r, bool bf16, const float* mean, const float* rstd, const float* gamma, const float* sums, size_t N,
                                int C, int relu, void* dz, float* colsum, double* scratch, hipStream_t st) {
-  static const bool fused = [] { const char* e = std::getenv("JCM_BN_COLSUM"); return !e || std::atoi(e) != 0; }();      // JCM_BN_COLSUM=0: the two passes (A/B arm)
-  if (!fused || bf16 || C % 4 || 256 % (C / 4)) {
+  if (bf16 || C % 4 || 256 % (C / 4)) {
     if (hipError_t e = bn_bwd_apply(dy, dy_scale, r, bf16, mean, rstd, gamma, sums, N, C, relu, dz, st); e != hipSuccess) return e;
     return col_sum(dz, bf16, N, C, colsum, scratch, st);
   }
@@ -546,9 +543,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pooled_kernel(const float4* 
 // false: not this case (bf16, C % 4, 256 % (C / 4)) -- nothing launched; the caller takes max_pool_bwd + the plain kernels
 bool bn_bwd_pooled(const void* dp, const void* y, const void* r, bool bf16, const float* mean, const float* rstd, const float* gamma, int B, int H, int W, int C, float* sums,
                    float* dgamma, float* dbeta, void* dz, float* colsum, double* scratch, hipStream_t st, hipError_t* err) {
-  static const bool fused = [] { const char* e = std::getenv("JCM_BN_POOLBWD"); return !e || std::atoi(e) != 0; }();      // JCM_BN_POOLBWD=0: max_pool_bwd + the plain kernels
   *err = hipSuccess;
-  if (!fused || bf16 || C % 4 || 256 % (C / 4)) return false;
+  if (bf16 || C % 4 || 256 % (C / 4)) return false;
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, C4 = C / 4;
   const size_t total = (size_t)B * Ho * Wo * C4, g4 = (total + 255) / 256, N = (size_t)B * H * W;
   const int blocks = (int)(g4 > RED_MAX_BLOCKS ? RED_MAX_BLOCKS : g4);

@@ -16,6 +16,25 @@ def _hm_size(n):
     return n
 
 
+def _precision(name):
+    return {'fp32': _lib.JCM_PRECISION_F32, 'f32': _lib.JCM_PRECISION_F32, 'bf16': _lib.JCM_PRECISION_BF16}[name]
+
+
+def _f32_conv(name):      # 'exact' = the default; 'split16' = the direct kernels on two fp16 parts per operand (fp16x3)
+    if name not in ('exact', 'split16'):
+        raise ValueError("f32_conv must be 'exact' or 'split16' (the bf16x6 arm 'split' was retired in round 5)")
+    return {'exact': 0, 'split16': 2}[name]
+
+
+def _flag(v):
+    return int(bool(v))
+
+
+# keyword of Engine.__init__ = key of jcm_set_option, and what turns the keyword's value into the option's
+_INIT_OPTIONS = (('precision', _precision), ('n_joints', int), ('f32_conv', _f32_conv), ('micro_batch', int), ('conv9_fft', _flag), ('fft_single', _flag),
+                 ('fft_t16', _flag), ('fft_fuse', int), ('fft_tiles', _flag), ('fft_logits_rows', _flag), ('call_order', _flag), ('split_min_wgs', int))
+
+
 class Engine:
     """Owns a jcm_handle.  All tensor arguments are torch CUDA float32 NHWC, contiguous."""
 
@@ -33,31 +52,11 @@ class Engine:
                    'jcm_create')
         self._h = h
         self._finalized = False
-        prec = {'fp32': _lib.JCM_PRECISION_F32, 'f32': _lib.JCM_PRECISION_F32, 'bf16': _lib.JCM_PRECISION_BF16}[precision]
-        _lib.check(self._lib.jcm_set_option(self._h, b'precision', prec), 'jcm_set_option(precision)')
-        _lib.check(self._lib.jcm_set_option(self._h, b'n_joints', self.n_joints), 'jcm_set_option(n_joints)')
-        if f32_conv is not None:      # 'exact' = the default; 'split16' = the direct kernels on two fp16 parts per operand (fp16x3: fp32-class accuracy on the 16-bit matrix cores)
-            if f32_conv not in ('exact', 'split16'):
-                raise ValueError("f32_conv must be 'exact' or 'split16' (the bf16x6 arm 'split' was retired in round 5)")
-            _lib.check(self._lib.jcm_set_option(self._h, b'f32_conv', {'exact': 0, 'split16': 2}[f32_conv]), 'jcm_set_option(f32_conv)')
-        if micro_batch is not None:   # forward() walks a batch in slices of this many images (default 256 bf16 / 64 fp32)
-            self.set_micro_batch(micro_batch)
-        if conv9_fft is not None:     # False: the wide 9x9 layers of an fp32 engine on the fp32 MFMA chain instead of the frequency domain
-            self.set_conv9_fft(conv9_fft)
-        if fft_single is not None:    # bf16 engines: False = two bf16 parts per operand of the channel GEMM (three products) instead of one scaled fp16 part
-            self.set_option('fft_single', int(bool(fft_single)))
-        if fft_t16 is not None:       # bf16 engines: False = the row-transformed tensors and the product spectra of the frequency-domain route stay complex fp32 (default: complex fp16)
-            self.set_option('fft_t16', int(bool(fft_t16)))
-        if fft_fuse is not None:      # fp32 engines: 0 = separate pool / merge kernels between the frequency-domain layers (A/B arm of the fused hand-overs; default 3)
-            self.set_option('fft_fuse', int(fft_fuse))
-        if fft_tiles is not None:     # fp32 engines: False = conv2_fullres -> pool -> conv3 on the whole 120x180 map (A/B arm of the 2x2 tiles; default on)
-            self.set_option('fft_tiles', int(bool(fft_tiles)))
-        if fft_logits_rows is not None:     # fp32 engines: False = conv6 as a whole frequency-domain layer (A/B arm of the contraction on conv5's row spectra; default on)
-            self.set_option('fft_logits_rows', int(bool(fft_logits_rows)))
-        if call_order is not None:    # False (debugging): this engine's calls are not ordered against other engines' on the device
-            self.set_option('call_order', int(bool(call_order)))
-        if split_min_wgs is not None: # 0 forces the split kernels even on grids too small to pay off (parity tests at small batch)
-            _lib.check(self._lib.jcm_set_option(self._h, b'split_min_wgs', int(split_min_wgs)), 'jcm_set_option(split_min_wgs)')
+        given = dict(precision=precision, n_joints=self.n_joints, f32_conv=f32_conv, micro_batch=micro_batch, conv9_fft=conv9_fft, fft_single=fft_single, fft_t16=fft_t16,
+                     fft_fuse=fft_fuse, fft_tiles=fft_tiles, fft_logits_rows=fft_logits_rows, call_order=call_order, split_min_wgs=split_min_wgs)
+        for key, convert in _INIT_OPTIONS:      # the option of the same name (include/jcm.h); None leaves the library's default
+            if given[key] is not None:
+                self.set_option(key, convert(given[key]))
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -443,24 +442,30 @@ class Engine:
         """jcm_set_option(key, value) -- include/jcm.h lists the keys."""
         _lib.check(self._lib.jcm_set_option(self._h, key.encode(), int(value)), 'jcm_set_option(%s)' % key)
 
+    def get_option(self, key):
+        """jcm_get_option(key): the value the handle holds."""
+        v = ctypes.c_int64(0)
+        _lib.check(self._lib.jcm_get_option(self._h, key.encode(), ctypes.byref(v)), 'jcm_get_option(%s)' % key)
+        return v.value
+
     def set_sm_algo(self, algo):
         """Pairwise-convolution algorithm of the spatial model: 'fft_fused' (default; every transform in LDS, sm_fused.hip / sm_lds.hip;
         'fft' is an alias) or 'direct' (LDS sliding-window VALU kernel, the independent cross-check).  Both are hand-written HIP paths; the
         rocFFT routes of rounds 1-4 ('fft', 'fft_split') were removed in round 5."""
-        _lib.check(self._lib.jcm_set_option(self._h, b'sm_algo', {'fft': 3, 'fft_fused': 3, 'direct': 1}[algo]), 'jcm_set_option(sm_algo)')
+        self.set_option('sm_algo', {'fft': 3, 'fft_fused': 3, 'direct': 1}[algo])
 
     def set_conv9_fft(self, on):
         """fp32 engines: run the wide 9x9 layers in the frequency domain (in-LDS FFTs + one complex channel GEMM per frequency;
         default) or on the fp32 MFMA accumulation chain.  Both pass the same parity tests."""
-        _lib.check(self._lib.jcm_set_option(self._h, b'conv9_fft', int(bool(on))), 'jcm_set_option(conv9_fft)')
+        self.set_option('conv9_fft', _flag(on))
 
     def set_micro_batch(self, n):
         """Images per internal slice of forward(): bounds the workspace when a rank holds a large share of a
         global batch (BASELINE configs[3]: 2048 images over the ranks).  0 = default (256 bf16 / 64 fp32)."""
-        _lib.check(self._lib.jcm_set_option(self._h, b'micro_batch', int(n)), 'jcm_set_option(micro_batch)')
+        self.set_option('micro_batch', int(n))
 
     def set_profile(self, on):
-        _lib.check(self._lib.jcm_set_option(self._h, b'profile', int(bool(on))), 'jcm_set_option(profile)')
+        self.set_option('profile', _flag(on))
 
     def profile_read(self, scope):
         """(total_ms, launches) of the HIP-event-bracketed launches of conv layer `scope`."""

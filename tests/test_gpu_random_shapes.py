@@ -315,11 +315,10 @@ def _fft_len(n):
 def grad_routes(B, H, W, cin, cout, ks):
     """Restates jcm_train.hip's route choice of the default fp32 handle: (frequency-domain forward, windows, weight-gradient route, data-gradient
     route), routes 'win' / 'fft' / 'mfma'.  The forward is observable (conv_kernel_name), the windows are (their result differs bit-wise from
-    fft_windows = 0); the rest is asserted through the error bound of the route.  The window thresholds follow the library's environment overrides
-    (JCM_WIN_FREQ_RATIO, JCM_WIN_MIN_CC; defaults 1.5 and 128 x 256)."""
-    import os
-    ratio = float(os.environ.get('JCM_WIN_FREQ_RATIO', '1.5'))
-    min_cc = int(os.environ.get('JCM_WIN_MIN_CC', str(128 * 256)))
+    fft_windows = 0); the rest is asserted through the error bound of the route.  The window thresholds are the library's constants
+    (jcm_train.hip: kWinFreqRatio = 1.5, kWinMinCC = 128 x 256)."""
+    ratio = 1.5
+    min_cc = 128 * 256
     fft = cin % 64 == 0 and H + ks - 1 <= 192 and W + ks - 1 <= 192
     win = (fft and cin * cout >= min_cc and B <= 32 and cout % 64 == 0 and
            ratio * 32 * 17 <= _fft_len(H + 4) * (_fft_len(W + 4) // 2 + 1))

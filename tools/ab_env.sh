@@ -1,5 +1,5 @@
 #!/bin/bash
-# same-box A/B of an environment switch: tools/ab_env.sh VAR "bench flags" [rounds]   (interleaved runs of VAR=0 and VAR=1)
+# same-box A/B of an option whose default comes from the environment (include/jcm.h lists them): tools/ab_env.sh VAR "bench flags" [rounds]   (interleaved runs of VAR=0 and VAR=1)
 VAR=$1; FLAGS=$2; N=${3:-3}
 for i in $(seq $N); do
   for v in 0 1; do

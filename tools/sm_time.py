@@ -1,4 +1,5 @@
-"""Times jcm_sm_forward (the spatial model alone) with HIP events: python tools/sm_time.py [B ...]"""
+"""Times jcm_sm_forward (the spatial model alone) with HIP events: python tools/sm_time.py [B ...]
+(The sweep of the grid size and of the item order that this tool was written for was decided in round 6 -- profiles/r06_* -- and its switches are gone.)"""
 import sys, numpy as np, torch
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 import joint_cnn_mrf_amd
