@@ -219,6 +219,21 @@ int jcm_argmax_coords(jcm_handle h, const float* hm, int B, int HH, int WW, int 
  * [B,2,K] may each be NULL (not both). */
 int jcm_softmax_argmax(jcm_handle h, const float* logits, int B, int HH, int WW, int K, float* prob, int32_t* coords);
 
+/* det_rate (evaluation.py:15-36) as detection-rate CURVES: every joint and every radius in one launch, one pass over the targets.
+ *   true[b,:,k] = first-occurrence flat arg-max of y[b,:,:,k] (the rules of jcm_argmax_coords: ties go to the lower index, a map of NaN or
+ *                 -inf only gives (0,0));
+ *   torso[b]    = sqrtf(dr*dr + dc*dc) between true[b,:,0] and true[b,:,7] (evaluation.py:26,29);
+ *   nd[b,k]     = sqrtf(er*er + ec*ec) * 100.0f / torso[b], er / ec the row / column differences of pred and true (evaluation.py:30);
+ *   hits[k*R+r] += number of images b with nd[b,k] <= radii[r] (evaluation.py:36 before the mean).
+ * fp32, one correctly rounded operation per step.  A zero torso length gives inf or NaN, stored as it is and never a hit (as in TensorFlow).
+ * pred_coords: device int32 [B,2,K] (row, col), as jcm_argmax_coords / jcm_forward write them; they are taken to be map coordinates and are not
+ * range-checked (the squared differences are summed in 64-bit integers, which arbitrary int32 values can overflow).  y: device [B,HH,WW,C], C >= K -- the targets y_in;
+ * channels >= K are ignored.  radii: HOST array of R floats, 1 <= R <= 32, passed to the kernel by value.  true_coords (device int32 [B,2,K]),
+ * norm_dist (device fp32 [B,K]) and hits (device int32 [K,R], ADDED to: zero it before the first batch) may each be NULL.
+ * JCM_ERR_ARG for K < 8, K > 16, C < K, C > 16, R outside 1..32 and B, HH or WW below 1; nothing is launched then. */
+int jcm_det_curve(jcm_handle h, const int32_t* pred_coords, const float* y, int B, int HH, int WW, int K, int C, const float* radii, int R,
+                  int32_t* true_coords, float* norm_dist, int32_t* hits);
+
 /* -- the whole tower ----------------------------------------------------------------------------
  * The graph of main.py:522-531: model -> spatial_softmax -> concat torso -> spatial_model ->
  * spatial_softmax -> argmax.  x [B,H,W,3]; torso [B,60,90,1] = y_in[...,K:] (main.py:528),

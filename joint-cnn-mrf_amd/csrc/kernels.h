@@ -282,6 +282,13 @@ hipError_t argmax_coords(const float* hm, int32_t* coords, int B, int HW, int WW
 // spatial_softmax followed by the first-occurrence argmax of the probabilities, one pass over the logits, one
 // workgroup per image: prob (may be null) [B,HW,K], coords (may be null) [B,2,K].  HW % 4 == 0, K <= 9.
 hipError_t softmax_argmax(const float* logits, float* prob, int32_t* coords, int B, int HW, int WW, int K, hipStream_t st);
+
+// ---- det_curve.hip -----------------------------------------------------------------------------
+// evaluation.py:15-36 for every joint and radius, one work group per image, y [B,HW,C] read once: the first-occurrence arg-max of the first K
+// channels (true_out [B,2,K], may be null), nd = |pred - true| * 100 / |true_0 - true_7| (nd_out [B,K], may be null) and hits[k*R+r] += (nd <= radii[r])
+// (int32 [K,R], may be null).  radii: R host floats, passed by value.  8 <= K <= C <= 16, 1 <= R <= 32.
+hipError_t det_curve(const int32_t* pred, const float* y, int B, int HW, int WW, int K, int C, const float* radii, int R, int32_t* true_out, float* nd_out,
+                     int32_t* hits, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

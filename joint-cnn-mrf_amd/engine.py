@@ -222,6 +222,34 @@ class Engine:
         _lib.check(self._lib.jcm_argmax_coords(self._h, self._p(hm), B, H, W, K, self._p(out)), 'jcm_argmax_coords')
         return out
 
+    def det_curve(self, pred_coords, y, radii, hits=None, want_dist=False, want_true=False):
+        """evaluation.py:15-36 for every joint and every radius in one launch and one pass over the targets.
+        pred_coords int32 [B,2,K] (row, col); y [B,H,W,C] with C >= K: the targets y_in, channels >= K ignored; radii: up to 32 numbers
+        (host).  hits: int32 [K,R] device tensor that is ADDED to (zeros when not given): hits[k,r] += #images whose joint k lies within
+        radii[r] % of the torso length.  Returns {'hits'} plus 'norm_dist' fp32 [B,K] (want_dist) and 'true_coords' int32 [B,2,K]
+        (want_true).  Nothing is read back.  K, C and the number of radii are checked by the library."""
+        self._chk(pred_coords, 3, 'pred_coords', torch.int32)
+        self._chk(y, 4, 'y')
+        B, H, W, C = y.shape
+        K = pred_coords.shape[2]
+        if tuple(pred_coords.shape) != (B, 2, K):
+            raise ValueError('pred_coords must be [B,2,K] with the batch size of y; got %s, y %s' % (tuple(pred_coords.shape), tuple(y.shape)))
+        rad = np.ascontiguousarray(np.asarray(radii if isinstance(radii, np.ndarray) else list(radii), dtype=np.float32).reshape(-1))
+        R = int(rad.size)
+        if hits is not None:
+            self._chk(hits, 2, 'hits', torch.int32)
+            if tuple(hits.shape) != (K, R):
+                raise ValueError('hits must be [K,R] = [%d,%d], got %s' % (K, R, tuple(hits.shape)))
+        out = {'hits': hits if hits is not None else torch.zeros((K, R), dtype=torch.int32, device=self.device)}
+        if want_dist:
+            out['norm_dist'] = self._new(B, K)
+        if want_true:
+            out['true_coords'] = self._new(B, 2, K, dtype=torch.int32)
+        self._on_stream(pred_coords, y, *out.values())      # the zeros and the caller's tensors were made on torch's current stream
+        _lib.check(self._lib.jcm_det_curve(self._h, self._p(pred_coords), self._p(y), B, H, W, K, C, rad.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), R,
+                                           self._p(out.get('true_coords')), self._p(out.get('norm_dist')), self._p(out['hits'])), 'jcm_det_curve')
+        return out
+
     def softmax_argmax(self, logits, want_prob=True):
         """spatial_softmax + arg-max of the probabilities in one kernel (the tail of forward()):
         [B,H,W,K] logits -> (prob [B,H,W,K] or None, coords int32 [B,2,K])."""

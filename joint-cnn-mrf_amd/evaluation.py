@@ -2,7 +2,11 @@
 batch loop that calls it, eval_error (main.py:275-283).
 
 The arg-max over the heat maps is libjcm's kernel (first occurrence); the remaining arithmetic of det_rate is a
-handful of [B,2,K] operations done with torch on the device."""
+handful of [B,2,K] operations done with torch on the device.
+
+DetCurve / eval_curves are the detection-rate CURVES the reference's report shows (one per joint, radii 1..20 % of the torso length): the
+same metric for every joint and every radius, counted by one kernel launch per batch (Engine.det_curve)."""
+import numpy as np
 import torch
 
 
@@ -38,11 +42,93 @@ def get_next_batch(X, Y, batch_size, shuffle=False, rng=None):
         yield X[batch_idx], Y[batch_idx]
 
 
-def eval_error(X_np, Y_np, engine, batch_size, use_sm=True, joints=(2,), det_radius=10):
+class DetCurve:
+    """Accumulator of detection-rate curves: counts[k, r] = number of images seen whose joint k lies within radii[r] % of the torso length
+    of its target (evaluation.py:26-36, the comparison before the mean).  update() adds a batch on the device without synchronising;
+    counts() / rates() read the [K,R] table back.  `engine` may be None for an accumulator that only merges or reports counts."""
+
+    def __init__(self, engine, radii=range(1, 21), n_joints=None):
+        self.engine = engine
+        self.radii = np.asarray(list(radii), dtype=np.float32)
+        if n_joints is None and engine is None:
+            raise ValueError('DetCurve without an engine needs n_joints')
+        self.n_joints = int(engine.n_joints if n_joints is None else n_joints)
+        self.n_images = 0
+        self._hits = None                                                 # device int32 [K,R], made by the first update
+        self._extra = np.zeros((self.n_joints, len(self.radii)), np.int64)   # counts merged in from other accumulators
+
+    def update(self, pred_coords, y):
+        """pred_coords int32 [B,2,K] on the engine's device, y [B,H,W,C >= K] the targets of the same images."""
+        if pred_coords.shape[2] != self.n_joints:
+            raise ValueError('pred_coords has %d joints, this curve %d' % (pred_coords.shape[2], self.n_joints))
+        self._hits = self.engine.det_curve(pred_coords, y, self.radii, hits=self._hits)['hits']
+        self.n_images += int(pred_coords.shape[0])
+        return self
+
+    def counts(self):
+        own = self._hits.cpu().numpy().astype(np.int64) if self._hits is not None else 0
+        return self._extra + own
+
+    def rates(self):
+        """Detection rates in percent [K,R]."""
+        if self.n_images == 0:
+            raise ValueError('DetCurve has seen no image')
+        return 100.0 * self.counts() / self.n_images
+
+    def merge(self, other):
+        """Add another accumulator's counts (a tower on another device, another shard of the set)."""
+        if self.n_joints != other.n_joints or not np.array_equal(self.radii, other.radii):
+            raise ValueError('merge needs the same joints and radii')
+        self._extra = self._extra + other.counts()
+        self.n_images += other.n_images
+        return self
+
+    def rate(self, joint, radius):
+        r = np.flatnonzero(self.radii == np.float32(radius))
+        if r.size == 0:
+            raise KeyError('radius %r is not one of %s' % (radius, self.radii.tolist()))
+        return float(self.rates()[joint, r[0]])
+
+    def as_dict(self, joint_names):
+        names = [str(n) for n in list(joint_names)[:self.n_joints]]
+        if len(names) != self.n_joints:
+            raise ValueError('%d joint names for %d joints' % (len(names), self.n_joints))
+        rates = self.rates()
+        d = {'radii': [float(r) for r in self.radii], 'n_images': int(self.n_images)}
+        for k, n in enumerate(names):
+            d[n] = [float(v) for v in rates[k]]
+        return d
+
+
+def _to_device_batch(bx, by, engine):
+    bx = torch.as_tensor(bx)
+    # byte images (a uint8 DeviceDataset, --u8_images) go to the byte entry as they are; everything else is widened to fp32
+    x = bx.to(device=engine.device, dtype=torch.uint8 if bx.dtype == torch.uint8 else torch.float32).contiguous()
+    y = torch.as_tensor(by, dtype=torch.float32, device=engine.device).contiguous()
+    return x, y
+
+
+def eval_curves(X, Y, engine, batch_size, use_sm=True, radii=range(1, 21)):
+    """Detection-rate curves of a whole set: every image goes through engine.forward once (the last batch may be partial -- unlike
+    eval_error, nothing is dropped) and its coordinates into two accumulators.  X [N,480,720,3] float or uint8, Y [N,60,90,K+1], numpy or
+    torch, host or device.  Returns (DetCurve of the part detector, DetCurve of the spatial model); without use_sm the second counts the part
+    detector's coordinates too (main.py:535)."""
+    K = engine.n_joints
+    pd, sm = DetCurve(engine, radii), DetCurve(engine, radii)
+    for lo in range(0, len(X), batch_size):
+        x, y = _to_device_batch(X[lo:lo + batch_size], Y[lo:lo + batch_size], engine)
+        r = engine.forward(x, y[..., K:].contiguous() if use_sm else None, use_sm=use_sm, want_prob=False)
+        pd.update(r['pd_coords'], y)
+        sm.update(r['sm_coords'] if use_sm else r['pd_coords'], y)
+    return pd, sm
+
+
+def eval_error(X_np, Y_np, engine, batch_size, use_sm=True, joints=(2,), det_radius=10, curves=None):
     """main.py:275-283: run a data set through the tower in inference mode batch by batch and return the means over
     batches of (loss_pd, loss_sm, det_rate_pd, det_rate_sm).  X_np [N,480,720,3] (float, or uint8 byte images), Y_np [N,60,90,10] (numpy or torch,
     host or device); the remainder N % batch_size is dropped as in the reference (get_next_batch).  Everything stays on
-    the device until the four means are read back."""
+    the device until the four means are read back.  curves: an optional pair of DetCurve (part detector, spatial model) that is fed the
+    coordinates of every batch on the way; the four numbers do not depend on it."""
     n_batches = len(X_np) // batch_size
     if n_batches == 0:
         raise ValueError('eval_error needs at least one whole batch (%d examples, batch size %d)' % (len(X_np), batch_size))
@@ -58,6 +144,9 @@ def eval_error(X_np, Y_np, engine, batch_size, use_sm=True, joints=(2,), det_rad
         dr_pd = det_rate_from_coords(r['pd_coords'], true, det_radius, 'all' if joints == 'all' else list(joints))
         dr_sm = det_rate_from_coords(r['sm_coords'], true, det_radius, 'all' if joints == 'all' else list(joints)) if use_sm else dr_pd
         acc += torch.stack([r['losses'][0].double(), r['losses'][1].double(), dr_pd.double(), dr_sm.double()])
+        if curves is not None:
+            curves[0].update(r['pd_coords'], y)
+            curves[1].update(r['sm_coords'] if use_sm else r['pd_coords'], y)
     return tuple(float(v) for v in (acc / n_batches).cpu())
 
 

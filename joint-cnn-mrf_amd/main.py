@@ -69,6 +69,9 @@ def build_parser():
     parser.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='arithmetic of the kernels.')
     parser.add_argument('--multiscale', action='store_true', help='evaluation run: 8-scale test-time evaluation (get_predictions, main.py:382-425).')
     parser.add_argument('--predictions', default=None, help='evaluation run: write flic_pred_pd / flic_pred_sm to this .mat file (main.py:675).')
+    parser.add_argument('--det_curve', default=None, metavar='PATH', help='evaluation run: write the detection-rate curves of the predictions (every joint, radii '
+                        '1..20 %% of the torso length, part detector and spatial model) to this JSON file and print the reference\'s test_dr line '
+                        '(main.py:424; DESIGN.md 4.11).')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -253,6 +256,42 @@ def _synthetic_dataset(n_train, n_test):
 def byte_grid(x):
     """--synthetic --u8_images: generated float images put on the byte grid, byte k = floor(x * 256) (255 at x = 1) standing for k / 255."""
     return np.minimum(np.floor(np.asarray(x, np.float32) * np.float32(256)), np.float32(255)).astype(np.uint8)
+
+
+DET_CURVE_IS_EVALUATION_ONLY = ('--det_curve belongs to the evaluation run (it measures the predictions of the test set that run assembles); '
+                                'it cannot be combined with --train')
+DET_CURVE_CHUNK = 256      # images per upload of det_curves_of_predictions
+
+
+def evaluated_indices(n_images, batch_size, n_towers, multiscale=False):
+    """Which test image each column of the assembled predictions belongs to.  The multi-scale run evaluates every image in order.  The single-scale
+    run walks whole batches only (the remainder n_images % batch_size is dropped) and gives tower i the slice [i * per, i * per + per) of every batch,
+    per = batch_size // n_towers (dist.shard_bounds, main.py:511,516): the remainder batch_size % n_towers of EVERY batch is dropped too, so with
+    --batch_size 14 on four towers column 12 is image 14, not image 12."""
+    if multiscale:
+        return np.arange(n_images, dtype=np.int64)
+    per = batch_size // n_towers
+    first = np.arange(0, (n_images // batch_size) * batch_size, batch_size, dtype=np.int64)
+    return (first[:, None] + np.arange(n_towers * per, dtype=np.int64)[None, :]).reshape(-1)
+
+
+def det_curves_of_predictions(eng, pred_pd, pred_sm, y, radii=range(1, 21), index=None):
+    """Detection-rate curves of assembled predictions: pred_* int [2,K,N] (row, col) as get_predictions returns them, y [.,60,90,>= K] targets;
+    column i is judged against y[index[i]] (index None: y[i]; evaluated_indices gives the index of an evaluation run).  Uploaded in chunks of
+    DET_CURVE_CHUNK images, counted on `eng`'s device, read back once.  Returns (DetCurve of the part detector, DetCurve of the spatial model)."""
+    from .evaluation import DetCurve
+    K, N = int(pred_pd.shape[1]), int(pred_pd.shape[2])
+    index = np.arange(N, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64)
+    if index.shape != (N,) or (N and (index.min() < 0 or index.max() >= len(y))):
+        raise ValueError('%d predictions need %d target indices inside [0, %d); got %s' % (N, N, len(y), index.shape))
+    curves = DetCurve(eng, radii, n_joints=K), DetCurve(eng, radii, n_joints=K)
+    for lo in range(0, N, DET_CURVE_CHUNK):
+        hi = min(N, lo + DET_CURVE_CHUNK)
+        yb = torch.as_tensor(np.ascontiguousarray(y[index[lo:hi]], dtype=np.float32), device=eng.device)
+        for curve, pred in zip(curves, (pred_pd, pred_sm)):
+            coords = np.ascontiguousarray(np.asarray(pred)[:, :, lo:hi].transpose(2, 0, 1), dtype=np.int32)      # [n,2,K]
+            curve.update(torch.as_tensor(coords, device=eng.device), yb)
+    return curves
 
 
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
@@ -488,6 +527,8 @@ def main(argv=None):
     hps = args
     if args.restore and not args.restore_path:
         raise SystemExit('--restore needs --restore_path <checkpoint prefix or .npz> (the reference hard-codes best_model_name, main.py:443)')
+    if args.train and args.det_curve:
+        raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
     if args.train and args.u8_images and not args.device_data:
         raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
     for g in args.gpus:
@@ -568,6 +609,17 @@ def main(argv=None):
         import scipy.io
         os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
         scipy.io.savemat(args.predictions, {'flic_pred_pd': pred_pd, 'flic_pred_sm': pred_sm})         # main.py:675
+    if args.det_curve:      # one place for every feed: the curves of the assembled predictions, counted on the first listed device
+        index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus), multiscale=args.multiscale)      # towers drop batch_size % n_gpus of every batch
+        c_pd, c_sm = det_curves_of_predictions(engine() if towers is None else towers.engines[0], pred_pd, pred_sm, y_test, index=index)
+        names = [str(n) for n in joint_names[:pred_pd.shape[1]]]
+        d_pd, d_sm = c_pd.as_dict(names), c_sm.as_dict(names)
+        doc = {'radii': d_pd['radii'], 'joint_names': names, 'n_images': d_pd['n_images'], 'multiscale': bool(args.multiscale), 'use_sm': bool(args.use_sm),
+               'pd': {n: d_pd[n] for n in names}, 'sm': {n: d_sm[n] for n in names}}
+        os.makedirs(os.path.dirname(args.det_curve) or '.', exist_ok=True)
+        with open(args.det_curve, 'w') as fh:
+            json.dump(doc, fh)
+        print('test_dr: {} {}'.format(c_pd.rate(2, 10), c_sm.rate(2, 10)))      # main.py:424: left wrist, radius 10
     line = {'n_images': int(pred_pd.shape[2]), 'gpus': args.gpus, 'use_sm': bool(args.use_sm), 'debug': bool(args.debug),
             'multiscale': bool(args.multiscale), 'seconds': dt, 'images_per_sec': pred_pd.shape[2] / dt,
             'coords_image0_pd': pred_pd[:, :, 0].tolist()}
