@@ -187,6 +187,13 @@ int jcm_finalize(jcm_handle h);
  * its bf16 result (fp32 for the last layer) is widened back. */
 int jcm_conv_layer(jcm_handle h, const char* scope, int stride, int last_layer, const float* x, int B, int H, int W,
                    float* out);
+/* pre_activ of conv_layer (main.py:160), the tensor tb.var_summary summarises: z = conv_SAME(x,w) + b in fp32, [B,ceil(H/s),ceil(W/s),Cout],
+ * for ANY stored layer, with or without BatchNorm (for the last layer it equals jcm_conv_layer(..., last_layer = 1)).  fp32 handles only: a
+ * bf16 handle returns JCM_ERR_ARG.  The layer takes the route jcm_conv_layer takes for it at this geometry, stand-alone, with the epilogue
+ * stopped at conv + bias -- not necessarily the arm the fused tower takes, so z need not equal the tower's pre-activation bit for bit
+ * (DESIGN.md 4.8).  Scope, stride (1 or 2) and sizes are checked before anything is launched; workspace arena, call order and
+ * gradient-callback rule as jcm_conv_layer. */
+int jcm_conv_layer_pre(jcm_handle h, const char* scope, int stride, const float* x, int B, int H, int W, float* z_out);
 /* conv_layer(((x1 + up(x2)) + up(x3)) / 3) (main.py:58,67,69-71: the three branches merged, then conv5), run as the tower runs it: where the
  * layer takes the frequency-domain route its forward row pass forms the merge while it loads the rows (the merged map never reaches memory),
  * otherwise the merge kernel runs in front of the layer.  x1 [B,H,W,Cin], x2 [B,H2,W2,Cin], x3 [B,H3,W3,Cin] -> out [B,H,W,Cout]; up() =
@@ -324,12 +331,28 @@ int jcm_augment_train_indexed_u8(jcm_handle h, const uint8_t* x_all, const float
  * jcm_hm_overlay: show_img_plus_hm (tensorboard.py:60-71) for images x [n,H,W,3] and heat maps hm [n,hh,hw,K] (K = 9, the
  *   reference's joints): out uint8 [n,K+1,H,W,3] -- picture j < K = min(x + colorize(c_j), 1), picture K = the all-joints
  *   picture, each quantised as jcm_image_u8; c_j = hm[..., j] resized (TF-1.x bilinear) times 1 / max(hm[..., j]).
- * All three image calls enqueue without synchronising and use the workspace arena. */
+ * All three image calls enqueue without synchronising and use the workspace arena.
+ * jcm_act_summary: tb.var_summary(pre_activ, name) + tf.summary.image('f_activ_' + name, activ[:, :, :, 7:8], 3) of conv_layer
+ *   (main.py:167-168) in one pass over z = the pre-activation [B,H,W,C] of layer `scope` (jcm_conv_layer_pre).  The images form n_groups
+ *   groups of B / n_groups consecutive images (the towers' slices; the B % n_groups trailing images are left out).  Outputs (device):
+ *     stats, counts: per group what jcm_tensor_stats returns per segment (double [n_groups][4], int64 [n_groups][3 + JCM_HIST_BUCKETS]);
+ *     activ_out [B,H,W,C] (may be NULL) = fp32(fp32(relu(z)) * scale[c]) + shift[c] with the folded inference-mode BatchNorm stored for
+ *            `scope`, two rounded operations; relu keeps a NaN (tf.nn.relu).  A layer without BatchNorm: activ = z.  The left-out
+ *            trailing images are not written;
+ *     pics_out fp32 [n_groups][n_pics][H][W] = channel pic_channel of the activation of the first n_pics images of every group
+ *            (n_pics <= B / n_groups; 0 with pics_out NULL: none); jcm_image_u8 (C = 1) quantises them as tf.summary.image does.
+ *   B < n_groups, pic_channel >= C, n_pics too large, an unknown scope and C != the layer's Cout are refused before any launch.
+ *   Results are bitwise reproducible; enqueues without synchronising; uses the workspace arena; timed under "<scope>/act_summary".
+ * jcm_bn_folded: the folded BatchNorm jcm_finalize (or the last refresh) stored for `scope`: scale = gamma / sqrt(var + 1e-3),
+ *   shift = beta - mean * scale, each step rounded to fp32; count = the layer's Cout; host or device pointers; synchronises. */
 #define JCM_HIST_BUCKETS 1551
 int jcm_tensor_stats(jcm_handle h, const float* data, const int64_t* segments, int n_segments, float scale, float clip_norm, double* stats,
                      int64_t* counts);
 int jcm_hist_bucket_limits(double* out, int cap);
 int jcm_image_u8(jcm_handle h, const float* x, int N, int H, int W, int C, uint8_t* out);
+int jcm_act_summary(jcm_handle h, const char* scope, const float* z, int B, int H, int W, int C, int n_groups, int pic_channel, int n_pics,
+                    float* activ_out, double* stats, int64_t* counts, float* pics_out);
+int jcm_bn_folded(jcm_handle h, const char* scope, float* scale_out, float* shift_out, int count);
 int jcm_hm_overlay(jcm_handle h, const float* x, const float* hm, int n, int H, int W, int hh, int hw, int K, uint8_t* out);
 
 /* -- tower concat across processes (main.py:573-574: tf.concat of the per-tower maps; here one process per GPU) --------
@@ -412,7 +435,7 @@ int jcm_train_apply(jcm_handle h, const float* grads, int optimizer, float lr, f
  * jcm_profile_read, jcm_last_error, another handle's calls).  It must not start a second training or forward call
  * on the SAME handle (that call would reuse the workspace the running step lives in): every entry point of the same handle
  * that uses the workspace arena or changes the training state or the parameters (jcm_forward, jcm_pd_forward, jcm_conv_layer*,
- * jcm_sm_forward, jcm_conv_mrf, jcm_train_*, jcm_update_tensor) returns JCM_ERR_STATE when called from the callback. */
+ * jcm_act_summary, jcm_sm_forward, jcm_conv_mrf, jcm_train_*, jcm_update_tensor) returns JCM_ERR_STATE when called from the callback. */
 typedef void (*jcm_grad_ready_fn)(void* user, int64_t offset, int64_t count);
 int jcm_train_set_grad_callback(jcm_handle h, jcm_grad_ready_fn fn, void* user);
 int jcm_train_steps(jcm_handle h, int64_t* n_iters);     /* n_iters_tf (main.py:491) */

@@ -29,6 +29,7 @@ SIGNATURES = {
     'jcm_finalize': (ctypes.c_int, [_handle]),
     'jcm_conv_layer': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _c_float_p,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p]),
+    'jcm_conv_layer_pre': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p]),
     'jcm_conv_layer_merged': (ctypes.c_int, [_handle, ctypes.c_char_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p]),
     'jcm_max_pool': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p]),
@@ -68,6 +69,9 @@ SIGNATURES = {
                                         ctypes.c_void_p, ctypes.c_void_p]),
     'jcm_hist_bucket_limits': (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
     'jcm_image_u8': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    'jcm_act_summary': (ctypes.c_int, [_handle, ctypes.c_char_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, _c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p]),
+    'jcm_bn_folded': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'jcm_hm_overlay': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_void_p]),
     'jcm_profile_read': (ctypes.c_int, [_handle, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),

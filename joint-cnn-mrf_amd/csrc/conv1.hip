@@ -19,8 +19,9 @@ constexpr int C1_IN = 2 * (C1_PT - 1) + 5;    // 19 input rows/cols per patch
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-// PixT = float, or uint8_t (byte images, converted by u8_to_f32 at the load)
-template <class TO, class PixT>
+// PixT = float, or uint8_t (byte images, converted by u8_to_f32 at the load).  LIN: the linear epilogue conv + bias (the pre-activation
+// jcm_conv_layer_pre returns); the accumulation is the same code, so z of the LIN instantiation is the value the other one rectifies.
+template <class TO, class PixT, bool LIN = false>
 __device__ __forceinline__ void conv1_body(const PixT* __restrict__ x, const float* __restrict__ w,
                                            const float* __restrict__ bias, const float* __restrict__ scale,
                                            const float* __restrict__ shift, TO* __restrict__ out,
@@ -72,7 +73,8 @@ __device__ __forceinline__ void conv1_body(const PixT* __restrict__ x, const flo
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int co = co0 + j + t;
-        vp[t] = fmaxf(acc[j + t] + bias[co], 0.f) * scale[co] + shift[co];
+        if constexpr (LIN) vp[t] = acc[j + t] + bias[co];
+        else vp[t] = fmaxf(acc[j + t] + bias[co], 0.f) * scale[co] + shift[co];
       }
       if constexpr (sizeof(TO) == 4) {
         *reinterpret_cast<float4*>(o + j) = make_float4(vp[0], vp[1], vp[2], vp[3]);
@@ -102,14 +104,28 @@ __global__ __launch_bounds__(256) void conv1_u8_kernel(const uint8_t* __restrict
   conv1_body<TO, uint8_t>(x, w, bias, scale, shift, out, H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);
 }
 
+// fp32 image -> fp32 pre-activation (jcm_conv_layer_pre); scale / shift are not read
+__global__ __launch_bounds__(256) void conv1_linear_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, float* __restrict__ out,
+                                                           int H0, int W0, int sub, int Hin, int Win, int Ho, int Wo,
+                                                           int pad_t, int pad_l, int Cout) {
+  conv1_body<float, float, true>(x, w, bias, nullptr, nullptr, out, H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);
+}
+
 hipError_t conv1_5x5s2(const void* xv, const float* w, const float* bias, const float* scale, const float* shift,
-                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st, bool x_u8) {
+                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st, bool x_u8, bool linear) {
   if (Cout % 16 != 0 || Cout > 64 || H0 % sub != 0 || W0 % sub != 0) return hipErrorInvalidValue;
+  if (linear && (out_bf16 || x_u8)) return hipErrorInvalidValue;      // the linear epilogue exists for fp32 in / fp32 out
   const int Hin = H0 / sub, Win = W0 / sub;
   const int Ho = (Hin + 1) / 2, Wo = (Win + 1) / 2;
   const int tot_h = (Ho - 1) * 2 + 5 - Hin, tot_w = (Wo - 1) * 2 + 5 - Win;
   const int pad_t = (tot_h > 0 ? tot_h : 0) / 2, pad_l = (tot_w > 0 ? tot_w : 0) / 2;
   dim3 grid((Wo + C1_PT - 1) / C1_PT, (Ho + C1_PT - 1) / C1_PT, B);
+  if (linear) {
+    hipLaunchKernelGGL(conv1_linear_kernel, grid, dim3(64 * (Cout / 16)), 0, st, static_cast<const float*>(xv), w, bias,
+                       static_cast<float*>(out), H0, W0, sub, Hin, Win, Ho, Wo, pad_t, pad_l, Cout);
+    return hipGetLastError();
+  }
   if (x_u8) {
     const uint8_t* x = static_cast<const uint8_t*>(xv);
     if (out_bf16)

@@ -222,9 +222,10 @@ bool fft_spectra_valid(jcm_ctx* c, const std::string& scope, int H, int W, int c
 inline int fft_np(const jcm_ctx* c) { return c->precision == JCM_PRECISION_BF16 ? (c->fft_single ? 5 : 2) : 4; }
 int fft_new_words(jcm_ctx* c, int n, float** w);      // n zeroed device words of the scaling ring (one per image)
 // circ: x is a batch of overlap-save windows [B, H, W, Cin] that fill the transform, out their valid regions [B, H - 8, W - 8, Cout] (ConvArgs::circ)
-int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ = 0, FftLink* link = nullptr);
+int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ = 0, FftLink* link = nullptr,
+                 int linear = 0);      // linear: the epilogue stops at conv + bias whatever the layer's BatchNorm (jcm_conv_layer_pre)
 int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub,
-                   void* out, bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false, FftLink* link = nullptr, int hpool = 0);   // bf16 layouts: ConvArgs in kernels.h; x_u8: the stride-2 layer reads a byte image
+                   void* out, bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false, FftLink* link = nullptr, int hpool = 0, int linear = 0);   // bf16 layouts: ConvArgs in kernels.h; x_u8: the stride-2 layer reads a byte image
 
 inline int cdiv2(int v) { return (v + 1) / 2; }
 

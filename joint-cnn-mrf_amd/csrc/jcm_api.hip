@@ -1,6 +1,7 @@
 // libjcm C ABI (include/jcm.h): context, parameter store, weight packing, workspace arena and
 // the forward graph of main.py:29-74,94-125,522-531 as a sequence of kernel launches on one
 // HIP stream.  No tensor library types cross this boundary -- plain pointers and sizes.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -154,10 +155,10 @@ const ConvLayer* conv_of(jcm_ctx* c, const std::string& scope) {
 
 // The launch itself (kernel choice by precision / f32_conv); run_conv_layer brackets it with the timing events.
 static int launch_conv_layer(jcm_ctx* c, const ConvLayer* L, const void* wp, const void* x, int B, int H, int W, void* out, bool act_bf16,
-                             bool out_f32, int in_planar, int out_planar, int hpool) {
+                             bool out_f32, int in_planar, int out_planar, int hpool, int linear) {
   ConvArgs a{};
   a.x = x; a.wp = wp; a.bias = L->bias; a.scale = L->scale; a.shift = L->shift; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.relu_bn = L->has_bn ? 1 : 0;
+  a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.relu_bn = L->has_bn && !linear ? 1 : 0;
   a.in_planar = in_planar; a.out_planar = out_planar;
   a.hpool = hpool;
   if ((in_planar || out_planar) && !act_bf16) return fail(JCM_ERR_ARG, "planar activations exist on the bf16 path only");
@@ -283,12 +284,12 @@ int fft_new_words(jcm_ctx* c, int n, float** w) {
     c->fft_blocks.push_back(b);
   }
 }
-int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ, FftLink* link) {
+int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ, FftLink* link, int linear) {
   FftLink alone;
   FftLink& k = link ? *link : alone;
   ConvArgs a{};
   a.x = x; a.bias = L->bias; a.scale = L->scale; a.shift = L->shift; a.out = out;
-  a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.CoutP = L->cout; a.relu_bn = L->has_bn ? 1 : 0;
+  a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.CoutP = L->cout; a.relu_bn = L->has_bn && !linear ? 1 : 0;
   a.circ = circ;
   a.rows_mfma = c->fft_rows_mfma;
   a.fft_reg = c->fft_reg;
@@ -385,8 +386,10 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
 // One conv layer.  Activations are fp32, or bf16 when the handle runs the bf16 path (`act_bf16`);
 // `out_f32` forces an fp32 result (the logits layer).
 int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub,
-                   void* out, bool act_bf16, bool out_f32, int in_planar, int out_planar, bool x_u8, FftLink* link, int hpool) {
+                   void* out, bool act_bf16, bool out_f32, int in_planar, int out_planar, bool x_u8, FftLink* link, int hpool, int linear) {
   const bool fft = stride == 1 && takes_fft(c, L, B, H, W);
+  // linear (jcm_conv_layer_pre): the epilogue of a BatchNorm layer stops at conv + bias; fp32 handles, a layer that stands alone
+  if (linear && (act_bf16 || x_u8 || hpool || (link && !link->empty()))) return fail(JCM_ERR_STATE, "the linear epilogue of layer '" + scope + "' exists for a stand-alone fp32 layer only");
   // a request aimed at a route this layer does not take is an error of the caller, never dropped (nor left for the next layer)
   if (!fft && link && !link->empty()) return fail(JCM_ERR_STATE, "layer '" + scope + "' was given a frequency-domain hand-over but does not run in the frequency domain");
   if (hpool && (fft || stride != 1)) return fail(JCM_ERR_STATE, "half pool requested for layer '" + scope + "', which does not run on conv5_strip_bf16_kernel");
@@ -394,10 +397,10 @@ int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int
     if (c->dry) return JCM_OK;
     if (!(L->ks == 5 && L->cin == 3 && L->has_bn))
       return fail(JCM_ERR_ARG, "stride-2 kernel exists for 5x5, Cin=3, BN layers only (" + scope + ")");
-    HIP_TRY(conv1_5x5s2(x, L->w_raw, L->bias, L->scale, L->shift, out, act_bf16, B, H, W, sub, L->cout, c->stream, x_u8));
+    HIP_TRY(conv1_5x5s2(x, L->w_raw, L->bias, L->scale, L->shift, out, act_bf16, B, H, W, sub, L->cout, c->stream, x_u8, linear != 0));
     return JCM_OK;
   }
-  if (fft) return run_conv_fft(c, L, scope, x, B, H, W, out, act_bf16 ? (in_planar ? 2 : 1) : 0, (act_bf16 && !out_f32) ? (out_planar ? 2 : 1) : 0, 0, link);
+  if (fft) return run_conv_fft(c, L, scope, x, B, H, W, out, act_bf16 ? (in_planar ? 2 : 1) : 0, (act_bf16 && !out_f32) ? (out_planar ? 2 : 1) : 0, 0, link, linear);
   if (c->dry) return JCM_OK;
   const void* wp = act_bf16 ? L->wp_bf16 : static_cast<const void*>(L->wp);
   if (stride != 1 || !wp) return fail(JCM_ERR_ARG, "no kernel for layer '" + scope + "' with stride " + std::to_string(stride));
@@ -407,7 +410,7 @@ int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   JCM_TRY(prof_begin(c, &e0, &e1));
-  const int r = launch_conv_layer(c, L, wp, x, B, H, W, out, act_bf16, out_f32, in_planar, out_planar, hpool);
+  const int r = launch_conv_layer(c, L, wp, x, B, H, W, out, act_bf16, out_f32, in_planar, out_planar, hpool, linear);
   prof_end(c, scope, e0, e1, r == JCM_OK);
   return r;
 }
@@ -550,11 +553,11 @@ int refresh_derived(jcm_ctx* c, bool first) {
 namespace {
 
 int run_conv(jcm_ctx* c, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub, void* out,
-             bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false, FftLink* link = nullptr, int hpool = 0) {      // x_u8: the stride-2 layer reads a byte image
+             bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false, FftLink* link = nullptr, int hpool = 0, int linear = 0) {      // x_u8: the stride-2 layer reads a byte image
   const ConvLayer* L = conv_of(c, scope);
   if (!L) return fail(JCM_ERR_STATE, "no conv layer '" + scope + "' (set '" + scope + "/weights' and finalize)");
   if (x_u8 && stride != 2) return fail(JCM_ERR_ARG, "byte images feed the stride-2 first layer only (" + scope + ")");
-  return run_conv_layer(c, L, scope, stride, x, B, H, W, sub, out, act_bf16, out_f32, in_planar, out_planar, x_u8, link, hpool);
+  return run_conv_layer(c, L, scope, stride, x, B, H, W, sub, out, act_bf16, out_f32, in_planar, out_planar, x_u8, link, hpool, linear);
 }
 
 // bf16 handles: does a [B,H,W,Cin] launch of this 9x9 layer take the flattened-strip kernel (which reads / writes the
@@ -938,6 +941,26 @@ int jcm_conv_layer(jcm_handle h, const char* scope, int stride, int last_layer, 
     if (!c->dry && !last_layer) HIP_TRY(cast_bf16_f32(ob, out, nout, c->stream));
     return (int)JCM_OK;
   });
+}
+
+// pre_activ of main.py:160 for any stored layer: the route jcm_conv_layer takes for this layer and geometry (stand-alone: nothing handed over), its
+// epilogue stopped at conv + bias (ConvArgs::relu_bn = 0; the stride-2 kernel's linear instantiation).  Everything is checked before the first launch.
+int jcm_conv_layer_pre(jcm_handle h, const char* scope, int stride, const float* x, int B, int H, int W, float* z_out) {
+  JCM_TRY(check(h, true));
+  if (!scope || !x || !z_out || B < 1 || H < 1 || W < 1) return fail(JCM_ERR_ARG, "bad conv_layer_pre arguments");
+  if (stride != 1 && stride != 2) return fail(JCM_ERR_ARG, "conv_layer_pre: stride must be 1 or 2, got " + std::to_string(stride));
+  if (h->precision != JCM_PRECISION_F32)
+    return fail(JCM_ERR_ARG, "conv_layer_pre: fp32 handles only (the pre-activation summaries are fp32; this is a bf16 handle)");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  const ConvLayer* L = conv_of(h, scope);
+  if (!L) return fail(JCM_ERR_STATE, std::string("no conv layer '") + scope + "'");
+  if ((int64_t)B * H * W * std::max(L->cin, L->cout) >= ((int64_t)1 << 40)) return fail(JCM_ERR_ARG, "conv_layer_pre: tensor too large");
+  if (stride == 2 && !(L->ks == 5 && L->cin == 3 && L->cout % 16 == 0 && L->cout <= 64))
+    return fail(JCM_ERR_ARG, std::string("conv_layer_pre: the stride-2 kernel exists for 5x5, Cin = 3, Cout % 16 == 0, Cout <= 64 ('") + scope + "')");
+  if (stride == 1 && !L->wp && !takes_fft(h, L, B, H, W))
+    return fail(JCM_ERR_ARG, std::string("conv_layer_pre: no stride-1 kernel for layer '") + scope + "' (size 5 or 9, Cin % 16 == 0)");
+  return with_arena(h, [&] { return run_conv(h, scope, stride, x, B, H, W, 1, z_out, false, false, 0, 0, false, nullptr, 0, 1); });
 }
 
 // conv_layer(((x1 + up(x2)) + up(x3)) / 3) (main.py:58,67,69-71) exactly as the tower runs it: on the frequency-domain route the merge is formed by the

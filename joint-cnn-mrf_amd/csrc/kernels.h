@@ -247,7 +247,8 @@ hipError_t conv_strip_bf16(const ConvArgs& a, hipStream_t st);
 // x_u8 (here and for the three conv1_mfma.hip launchers): x is a byte image [B,H0,W0,3], each value k standing for float32(k) / float32(255)
 // (u8.h); the byte-source kernels convert at the load and are the float kernels behind it.
 hipError_t conv1_5x5s2(const void* x, const float* w, const float* bias, const float* scale, const float* shift,
-                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st, bool x_u8 = false);
+                       void* out, bool out_bf16, int B, int H0, int W0, int sub, int Cout, hipStream_t st, bool x_u8 = false,
+                       bool linear = false);      // linear: out = conv + bias (fp32 in / out only; scale / shift unused)
 
 // ---- conv1_mfma.hip : conv1 + bias/ReLU/BN + 2x2 max-pool fused, bf16 MFMA (bf16 path only) ----
 // x [B,H0,W0,3] fp32 (branch input = x[:, ::sub, ::sub]) -> out [B,(H0/sub)/4,(W0/sub)/4,64] bf16

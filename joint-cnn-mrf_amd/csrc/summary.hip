@@ -9,64 +9,20 @@
 
 #include "ctx.h"
 #include "resize_tf1.h"
+#include "summary_stats.h"
 
 namespace jcm {
 
 namespace {
 
-constexpr int kPosLimits = JCM_HIST_BUCKETS / 2;     // 1e-12 * 1.1^k below 1e20, then DBL_MAX
-constexpr int kStatsThreads = 256;
-constexpr int kStatsWaves = kStatsThreads / 64;
 constexpr int kChunk = 32768;                       // elements per work group of the statistics pass
 constexpr int kImgThreads = 256;
-
-// histogram.cc InitDefaultBucketsInner: the positive half of the bucket limits (the table is mirrored around 0.0)
-struct PosLimits {
-  double v[kPosLimits];
-  int n = 0;
-  PosLimits() {
-    double x = 1.0e-12;
-    while (x < 1.0e20 && n < kPosLimits - 1) {
-      v[n++] = x;
-      x *= 1.1;
-    }
-    v[n++] = DBL_MAX;
-  }
-};
-const PosLimits& pos_limits() {
-  static const PosLimits L;
-  return L;
-}
 
 struct Chunk {
   const float* p;
   int n;
   int seg;
 };
-struct Part {
-  float mn, mx;
-  double s, ss;
-  unsigned num, npos, nnf, pad;
-};
-
-// index of the TF bucket of a finite nonzero-or-zero value d = (double)u: std::upper_bound over the full limit table
-// [-p[P-1], ..., -p[0], 0.0, p[0], ..., p[P-1]].  The first guess comes from log2 of the float; the loops correct it
-// against the double edges (they stop at the DBL_MAX edge, which every finite value lies below).
-__device__ __forceinline__ int bucket_of(float u, const double* __restrict__ lim) {
-  if (u == 0.f) return kPosLimits + 1;
-  const double a = fabs((double)u);
-  const float lg = log2f(fabsf(u));
-  int g = (int)floorf((lg + 39.863137f) * 7.2725409f) + 1;     // log2(1e12), 1 / log2(1.1)
-  g = min(max(g, 0), kPosLimits - 1);
-  if (u > 0.f) {               // first k with p[k] > a
-    while (g > 0 && lim[g - 1] > a) --g;
-    while (lim[g] <= a) ++g;
-    return kPosLimits + 1 + g;
-  }
-  while (g > 0 && lim[g - 1] >= a) --g;     // first k with p[k] >= a
-  while (lim[g] < a) ++g;
-  return kPosLimits - g;
-}
 
 __device__ __forceinline__ float stats_scale(float scale, float clip, const double* __restrict__ sumsq) {
   if (!sumsq) return scale;
@@ -75,133 +31,19 @@ __device__ __forceinline__ float stats_scale(float scale, float clip, const doub
 }
 
 // one work group per chunk: partial min / max / sums / counts and the chunk's histogram (one LDS sub-histogram per wave),
-// whose nonzero bins are added to the segment's int64 counts
+// whose nonzero bins are added to the segment's int64 counts (summary_stats.h)
 __global__ __launch_bounds__(kStatsThreads) void stats_chunk_kernel(const Chunk* __restrict__ chunks, const double* __restrict__ limits,
                                                                     float scale, float clip, const double* __restrict__ sumsq,
                                                                     Part* __restrict__ parts, unsigned long long* __restrict__ counts) {
-  __shared__ double lim[kPosLimits];
-  __shared__ unsigned hist[kStatsWaves][JCM_HIST_BUCKETS];
-  __shared__ float rmn[kStatsThreads], rmx[kStatsThreads];
-  __shared__ double rs[kStatsThreads], rss[kStatsThreads];
-  __shared__ unsigned rc[3][kStatsThreads];
-  const int t = threadIdx.x, wave = t / 64;
-  for (int i = t; i < kPosLimits; i += kStatsThreads) lim[i] = limits[i];
-  for (int i = t; i < kStatsWaves * JCM_HIST_BUCKETS; i += kStatsThreads) (&hist[0][0])[i] = 0u;
+  __shared__ StatsLds L;
+  const int t = threadIdx.x;
+  stats_lds_init(L, limits);
   const Chunk ck = chunks[blockIdx.x];
   const float f = stats_scale(scale, clip, sumsq);
   __syncthreads();
-  float mn = INFINITY, mx = -INFINITY;
-  double s = 0.0, ss = 0.0;
-  unsigned num = 0, npos = 0, nnf = 0;
-  for (int i = t; i < ck.n; i += kStatsThreads) {
-    const float u = ck.p[i] * f;
-    if (!isfinite(u)) {
-      ++nnf;
-      continue;
-    }
-    mn = fminf(mn, u);
-    mx = fmaxf(mx, u);
-    const double d = (double)u;
-    s += d;
-    ss += d * d;
-    ++num;
-    npos += u > 0.f;
-    atomicAdd(&hist[wave][bucket_of(u, lim)], 1u);
-  }
-  rmn[t] = mn;
-  rmx[t] = mx;
-  rs[t] = s;
-  rss[t] = ss;
-  rc[0][t] = num;
-  rc[1][t] = npos;
-  rc[2][t] = nnf;
-  for (int st = kStatsThreads / 2; st > 0; st >>= 1) {
-    __syncthreads();
-    if (t < st) {
-      rmn[t] = fminf(rmn[t], rmn[t + st]);
-      rmx[t] = fmaxf(rmx[t], rmx[t + st]);
-      rs[t] += rs[t + st];
-      rss[t] += rss[t + st];
-      rc[0][t] += rc[0][t + st];
-      rc[1][t] += rc[1][t + st];
-      rc[2][t] += rc[2][t + st];
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    Part P;
-    P.mn = rmn[0];
-    P.mx = rmx[0];
-    P.s = rs[0];
-    P.ss = rss[0];
-    P.num = rc[0][0];
-    P.npos = rc[1][0];
-    P.nnf = rc[2][0];
-    P.pad = 0;
-    parts[blockIdx.x] = P;
-  }
-  unsigned long long* cs = counts + (size_t)ck.seg * (3 + JCM_HIST_BUCKETS) + 3;
-  for (int b = t; b < JCM_HIST_BUCKETS; b += kStatsThreads) {
-    unsigned c = 0;
-#pragma unroll
-    for (int w = 0; w < kStatsWaves; ++w) c += hist[w][b];
-    if (c) atomicAdd(cs + b, (unsigned long long)c);
-  }
-}
-
-// one work group per segment: fixed-order fold of its chunks' partials -> stats [4] = (min, max, sum, sum_squares) and
-// counts [0..2] = (num, n_pos, n_nonfinite).  An empty histogram keeps TF's initial min / max (DBL_MAX, -DBL_MAX).
-__global__ __launch_bounds__(kStatsThreads) void stats_fold_kernel(const Part* __restrict__ parts, const int* __restrict__ first,
-                                                                   double* __restrict__ stats, unsigned long long* __restrict__ counts) {
-  __shared__ float rmn[kStatsThreads], rmx[kStatsThreads];
-  __shared__ double rs[kStatsThreads], rss[kStatsThreads];
-  __shared__ unsigned long long rc[3][kStatsThreads];
-  const int t = threadIdx.x, seg = blockIdx.x;
-  float mn = INFINITY, mx = -INFINITY;
-  double s = 0.0, ss = 0.0;
-  unsigned long long num = 0, npos = 0, nnf = 0;
-  for (int i = first[seg] + t; i < first[seg + 1]; i += kStatsThreads) {
-    const Part P = parts[i];
-    mn = fminf(mn, P.mn);
-    mx = fmaxf(mx, P.mx);
-    s += P.s;
-    ss += P.ss;
-    num += P.num;
-    npos += P.npos;
-    nnf += P.nnf;
-  }
-  rmn[t] = mn;
-  rmx[t] = mx;
-  rs[t] = s;
-  rss[t] = ss;
-  rc[0][t] = num;
-  rc[1][t] = npos;
-  rc[2][t] = nnf;
-  for (int st = kStatsThreads / 2; st > 0; st >>= 1) {
-    __syncthreads();
-    if (t < st) {
-      rmn[t] = fminf(rmn[t], rmn[t + st]);
-      rmx[t] = fmaxf(rmx[t], rmx[t + st]);
-      rs[t] += rs[t + st];
-      rss[t] += rss[t + st];
-      rc[0][t] += rc[0][t + st];
-      rc[1][t] += rc[1][t + st];
-      rc[2][t] += rc[2][t + st];
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    double* o = stats + (size_t)seg * 4;
-    const bool any = rc[0][0] > 0;
-    o[0] = any ? (double)rmn[0] : DBL_MAX;
-    o[1] = any ? (double)rmx[0] : -DBL_MAX;
-    o[2] = rs[0];
-    o[3] = rss[0];
-    unsigned long long* c = counts + (size_t)seg * (3 + JCM_HIST_BUCKETS);
-    c[0] = rc[0][0];
-    c[1] = rc[1][0];
-    c[2] = rc[2][0];
-  }
+  StatsAcc A;
+  for (int i = t; i < ck.n; i += kStatsThreads) A.add(ck.p[i] * f, L);
+  stats_block_finish(A, L, parts + blockIdx.x, counts + (size_t)ck.seg * (3 + JCM_HIST_BUCKETS) + 3);
 }
 
 // ---- images ---------------------------------------------------------------------------------------
@@ -432,7 +274,6 @@ int jcm_tensor_stats(jcm_handle h, const float* data, const int64_t* segments, i
                      int64_t* counts) {
   JCM_TRY(check(h, false));
   if (!segments || !stats || !counts || n_segments < 1 || n_segments > (1 << 20)) return fail(JCM_ERR_ARG, "tensor_stats: bad arguments");
-  if (pos_limits().n != kPosLimits) return fail(JCM_ERR_STATE, "tensor_stats: bucket table has the wrong size");
   if (!(scale == scale)) return fail(JCM_ERR_ARG, "tensor_stats: scale is NaN");
   jcm_ctx* c = h;
   const double* sumsq = nullptr;
@@ -460,10 +301,7 @@ int jcm_tensor_stats(jcm_handle h, const float* data, const int64_t* segments, i
   const int nck = (int)chunks.size();
   DeviceGuard g(h->device);
   CallOrder order(h);
-  if (!c->hist_limits) {
-    JCM_TRY(dev_alloc(c, reinterpret_cast<void**>(&c->hist_limits), kPosLimits * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(c->hist_limits, pos_limits().v, kPosLimits * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
+  JCM_TRY(hist_limits_dev(c));
   return with_arena(c, [&] {
     Chunk* dck = arena_alloc<Chunk>(c, std::max(nck, 1));
     int* dfirst = arena_alloc<int>(c, first.size());
@@ -474,7 +312,7 @@ int jcm_tensor_stats(jcm_handle h, const float* data, const int64_t* segments, i
     if (nck) HIP_TRY(hipMemcpyAsync(dck, chunks.data(), (size_t)nck * sizeof(Chunk), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dfirst, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (nck) hipLaunchKernelGGL(stats_chunk_kernel, dim3(nck), dim3(kStatsThreads), 0, c->stream, dck, c->hist_limits, scale, clip_norm, sumsq, parts, cnt);
-    hipLaunchKernelGGL(stats_fold_kernel, dim3(n_segments), dim3(kStatsThreads), 0, c->stream, parts, dfirst, stats, cnt);
+    hipLaunchKernelGGL(stats_fold_kernel, dim3(n_segments), dim3(kStatsThreads), 0, c->stream, parts, dfirst, 0, stats, cnt);
     HIP_TRY(hipGetLastError());
     order.release();
     HIP_TRY(hipStreamSynchronize(c->stream));     // the chunk table lives in host memory of this call

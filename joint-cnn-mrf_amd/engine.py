@@ -52,6 +52,7 @@ class Engine:
                    'jcm_create')
         self._h = h
         self._finalized = False
+        self._shapes = {}      # name -> shape of the parameters given so far (act_summary: does a layer have BatchNorm?)
         given = dict(precision=precision, n_joints=self.n_joints, f32_conv=f32_conv, micro_batch=micro_batch, conv9_fft=conv9_fft, fft_single=fft_single, fft_t16=fft_t16,
                      fft_fuse=fft_fuse, fft_tiles=fft_tiles, fft_logits_rows=fft_logits_rows, call_order=call_order, split_min_wgs=split_min_wgs)
         for key, convert in _INIT_OPTIONS:      # the option of the same name (include/jcm.h); None leaves the library's default
@@ -84,6 +85,7 @@ class Engine:
         arr = (ctypes.c_int64 * len(shape))(*shape)
         _lib.check(self._lib.jcm_set_tensor(self._h, name.encode(), ctypes.c_void_p(ptr), arr, len(shape)),
                    'jcm_set_tensor(%s)' % name)
+        self._shapes[name] = tuple(int(d) for d in shape)
         del keep
 
     def load_params(self, params, finalize=True):
@@ -142,6 +144,17 @@ class Engine:
         out = self._new(B, -(-H // stride), -(-W // stride), n_out)
         _lib.check(self._lib.jcm_conv_layer(self._h, name.encode(), stride, int(bool(last_layer)), self._p(x), B, H, W,
                                             self._p(out)), 'jcm_conv_layer(%s)' % name)
+        return out
+
+    def conv_layer_pre(self, x, name, stride, n_out):
+        """pre_activ of main.py:160: conv_SAME(x, w) + b of ANY stored layer, BatchNorm or not (fp32 engines only) -> [B,ceil(H/s),ceil(W/s),n_out]."""
+        self._chk(x, 4, 'x')
+        B, H, W, _ = x.shape
+        if stride not in (1, 2):
+            raise ValueError('stride must be 1 or 2, got %r' % (stride,))
+        out = self._new(B, -(-H // stride), -(-W // stride), int(n_out))
+        self._on_stream(x, out)
+        _lib.check(self._lib.jcm_conv_layer_pre(self._h, name.encode(), stride, self._p(x), B, H, W, self._p(out)), 'jcm_conv_layer_pre(%s)' % name)
         return out
 
     def conv_layer_merged(self, x1, x2, x3, name, n_out):
@@ -450,6 +463,32 @@ class Engine:
         self._on_stream(x, out)
         _lib.check(self._lib.jcm_image_u8(self._h, self._p(x), N, H, W, C, self._p(out)), 'jcm_image_u8')
         return out
+
+    def act_summary(self, z, name, n_groups=1, pic_channel=7, n_pics=3):
+        """main.py:167-168 in one pass over z = conv_layer_pre(., name) [B,H,W,C]: per group of B // n_groups consecutive images (a tower's slice;
+        the B % n_groups trailing images are left out) the statistics of tensor_stats, the activation BN(relu(z)) of layer `name`, and channel
+        pic_channel of the first n_pics activations of every group.  Returns {'activ' [B,H,W,C] (z itself for a layer without BatchNorm; the
+        left-out images are not written), 'stats' float64 [n_groups,4], 'counts' int64 [n_groups, 3 + JCM_HIST_BUCKETS] (host, as tensor_stats),
+        'pics' fp32 [n_groups,n_pics,H,W] (device)}.  The arguments are checked by the library."""
+        self._chk(z, 4, 'z')
+        B, H, W, C = z.shape
+        n_groups, n_pics = int(n_groups), int(n_pics)
+        has_bn = name + '/BatchNorm/gamma' in self._shapes
+        activ = torch.empty_like(z) if has_bn else None
+        stats = self._new(max(n_groups, 1), 4, dtype=torch.float64)
+        counts = self._new(max(n_groups, 1), 3 + _lib.JCM_HIST_BUCKETS, dtype=torch.int64)
+        pics = self._new(max(n_groups, 1), max(n_pics, 0), H, W)
+        self._on_stream(*[t for t in (z, activ, stats, counts, pics) if t is not None])
+        _lib.check(self._lib.jcm_act_summary(self._h, name.encode(), self._p(z), B, H, W, C, n_groups, int(pic_channel), n_pics, self._p(activ),
+                                             self._p(stats), self._p(counts), self._p(pics if n_pics > 0 else None)), 'jcm_act_summary(%s)' % name)
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)
+        return {'activ': activ if has_bn else z, 'stats': stats.cpu().numpy(), 'counts': counts.cpu().numpy(), 'pics': pics}
+
+    def bn_folded(self, name, n):
+        """The folded inference-mode BatchNorm stored for conv layer `name` -> host (scale, shift), float32 [n]."""
+        sc, sh = np.empty(int(n), np.float32), np.empty(int(n), np.float32)
+        _lib.check(self._lib.jcm_bn_folded(self._h, name.encode(), ctypes.c_void_p(sc.ctypes.data), ctypes.c_void_p(sh.ctypes.data), int(n)), 'jcm_bn_folded(%s)' % name)
+        return sc, sh
 
     def hm_overlay(self, x, hm, n=None):
         """show_img_plus_hm (tensorboard.py:60-71) of the first n images: x [B,H,W,3], hm [B,h,w,9] -> uint8 [n,10,H,W,3] device

@@ -81,6 +81,9 @@ def build_parser():
     parser.add_argument('--tb_dir', default=None, help='write TensorBoard summaries to DIR/<model_name>/{train,test} (main.py:448-450; off by default).')
     parser.add_argument('--tb_log_iters', action='store_true', help='with --tb_dir: histograms and scalars after every step to DIR/<model_name>/train_iter '
                         '(tb_log_iters, main.py:452,642-645).')
+    parser.add_argument('--tb_activations', action='store_true', help='with --tb_dir: add the per-layer activation summaries of conv_layer (main.py:167-168) to the '
+                        'epoch summaries of --train and the step-0 summaries of the evaluation run: tower_<i>/pre_activ_<layer>/{max,mean,min,std,n_pos,'
+                        'histogram} and tower_<i>/f_activ_<layer>/image/<k> for all 15 layers, one tower per --gpus entry (fp32 only; DESIGN.md 4.8).')
     return parser
 
 
@@ -419,13 +422,20 @@ def tb_open(args, model_name):
     return w
 
 
-def tb_summaries(writers, eng, layout, batches, use_sm, step, grads=None, params_flat=None):
-    """run_summary of the merged summary for the train and the test batch (main.py:621-626,650-653)."""
+TB_ACTIVATIONS_NEEDS_TB_DIR = '--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
+TB_ACTIVATIONS_IS_FP32 = ('--tb_activations: the pre-activation summaries are taken in fp32, as the reference takes them, and the bf16 kernels have no '
+                          'linear epilogue; run it with --precision fp32')
+
+
+def tb_summaries(writers, eng, layout, batches, use_sm, step, grads=None, params_flat=None, activations=False, n_towers=1):
+    """run_summary of the merged summary for the train and the test batch (main.py:621-626,650-653); activations: with the per-layer
+    activation summaries (--tb_activations), the batch cut into n_towers tower slices."""
     from . import summary
     for split, (bx, by) in batches.items():
         x = torch.as_tensor(bx).to(eng.device)
         y = torch.as_tensor(by).to(eng.device)
-        summary.run_summary(writers[split], summary.merged_summary(eng, layout, x, y, use_sm, n_joints, grads=grads, params_flat=params_flat), step)
+        summary.run_summary(writers[split], summary.merged_summary(eng, layout, x, y, use_sm, n_joints, grads=grads, params_flat=params_flat,
+                                                                       activations=activations, n_towers=n_towers), step)
 
 
 def train_main(args):
@@ -484,7 +494,8 @@ def train_main(args):
 
     def report(epoch):
         if tb:      # gradients of the epoch's last update (none before the first)
-            tb_summaries(tb, eng, tt.trainers[0].layout, tb_batches, args.use_sm, epoch, grads=tt.trainers[0].grads if epoch > 0 else None)
+            tb_summaries(tb, eng, tt.trainers[0].layout, tb_batches, args.use_sm, epoch, grads=tt.trainers[0].grads if epoch > 0 else None,
+                         activations=args.tb_activations, n_towers=len(args.gpus))
         tr_e = evaluation.eval_error(ev_train[0][:n_eval_ex], ev_train[1][:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
         te_e = evaluation.eval_error(ev_test[0][:n_eval_ex], ev_test[1][:n_eval_ex], eng, args.batch_size, args.use_sm, joints_to_eval, det_radius)
         print('Epoch {:d}  test_dr {:.3f} {:.3f}  train_dr {:.3f} {:.3f}  test_mse {:.5f} {:.5f}  train_mse {:.5f} {:.5f}'.format(
@@ -507,7 +518,7 @@ def train_main(args):
     for epoch in range(1, args.n_epochs + 1):
         for _ in steps():
             global_iter += 1
-            if tb and 'train_iter' in tb:       # main.py:642-645, without the images
+            if tb and 'train_iter' in tb:       # main.py:642-645, without the images and without the activation summaries
                 from . import summary
                 tr0 = tt.trainers[0]
                 summary.run_summary(tb['train_iter'], summary.merged_summary(eng, tr0.layout, use_sm=args.use_sm, n_joints=n_joints,
@@ -531,6 +542,10 @@ def main(argv=None):
         raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
     if args.train and args.u8_images and not args.device_data:
         raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
+    if args.tb_activations and not args.tb_dir:
+        raise SystemExit(TB_ACTIVATIONS_NEEDS_TB_DIR)
+    if args.tb_activations and args.precision != 'fp32':
+        raise SystemExit(TB_ACTIVATIONS_IS_FP32)
     for g in args.gpus:
         if g < 0 or g >= torch.cuda.device_count():
             raise SystemExit('--gpus %s: device %d does not exist (%d visible)' % (args.gpus, g, torch.cuda.device_count()))
@@ -560,7 +575,7 @@ def main(argv=None):
         tb = tb_open(args, model_name)
         flat, layout = summary.flat_params(eng, params)
         tb_summaries(tb, eng, layout, {'train': tb_batch(x_train, y_train, args.batch_size), 'test': tb_batch(x_test, y_test, args.batch_size)},
-                     args.use_sm, 0, params_flat=flat)
+                     args.use_sm, 0, params_flat=flat, activations=args.tb_activations, n_towers=len(args.gpus))
         for w in tb.values():
             w.close()
     # one set of engines only (each fp32 engine caches multi-GB filter spectra): the module engine for the multi-scale wrapper, which runs

@@ -328,10 +328,97 @@ def pairwise_summaries(eng, layout, params_flat=None, images=True):
     return out
 
 
-def merged_summary(eng, layout, x=None, y=None, use_sm=True, n_joints=9, grads=None, params_flat=None, clip_norm=4.0, images=True):
+# the order in which model (main.py:43-72) calls conv_layer
+ACTIV_SCOPES = tuple('conv%d_%s' % (i, r) for r in ('fullres', 'halfres', 'quarterres') for i in (1, 2, 3, 4)) + ('conv5', 'conv6')
+ACTIV_CHANNEL = 7           # main.py:168: activ[:, :, :, 7:8]
+N_ACTIV_TO_SHOW = 3         # ... max_outputs = 3
+
+
+def tower_slices(n_images, n_towers):
+    """(images per tower, images used): tower i takes images [i * per, (i + 1) * per) of the batch; the n_images % n_towers
+    trailing images are left out, as the reference's tower loop leaves them out (main.py:511,516)."""
+    if n_towers < 1 or n_images < n_towers:
+        raise ValueError('%d images do not fill %d towers' % (n_images, n_towers))
+    per = n_images // n_towers
+    return per, per * n_towers
+
+
+def activ_tags(n_towers, n_per_tower, scopes=ACTIV_SCOPES):
+    """Every tag activation_summaries emits, in its order: tower by tower, scope by scope, var_summary's six then the pictures."""
+    tags = []
+    for i in range(n_towers):
+        for s in scopes:
+            tags += ['tower_%d/pre_activ_%s/%s' % (i, s, k) for k in ('max', 'mean', 'min', 'std', 'n_pos', 'histogram')]
+            tags += ['tower_%d/f_activ_%s/image/%d' % (i, s, k) for k in range(min(N_ACTIV_TO_SHOW, n_per_tower))]
+    return tags
+
+
+def activation_summaries(eng, x, n_towers=1, taps=None):
+    """tb.var_summary(pre_activ, name) and tf.summary.image('f_activ_' + name, activ[:, :, :, 7:8], 3) of every conv_layer of model
+    (main.py:167-168) inside tf.name_scope('tower_%d') (main.py:519): x [B,H,W,3] float32, the summary batch (device); tower i is the
+    slice [i * per, (i + 1) * per) of it, per = B // n_towers.  The graph of model is composed line for line as main.model_layerwise
+    composes it, every conv_layer as Engine.conv_layer_pre followed by Engine.act_summary; one layer's tensors live at a time.
+    taps: a dict whose keys name scopes -- it receives those scopes' pre-activations (device).  Returns Summary.Value bytes and
+    futures (pictures), tower by tower, in the order in which model calls conv_layer."""
+    eng._chk(x, 4, 'x')
+    per, used = tower_slices(x.shape[0], n_towers)
+    n_pics = min(N_ACTIV_TO_SHOW, per)
+    x = x[:used]
+    found = {}
+
+    def conv_layer(t, stride, name):
+        n_out = _conv_out_channels(eng, name)
+        z = eng.conv_layer_pre(t, name, stride, n_out)
+        if taps is not None and name in taps:
+            taps[name] = z
+        r = eng.act_summary(z, name, n_groups=n_towers, pic_channel=ACTIV_CHANNEL, n_pics=n_pics)
+        u8 = _host(eng, eng.image_u8(r['pics'].view(n_towers * n_pics, z.shape[1], z.shape[2], 1)))
+        found[name] = (r['stats'], r['counts'], per * z.shape[1] * z.shape[2] * z.shape[3], u8)
+        return r['activ']
+
+    def branch(t, res):
+        t = conv_layer(t, 2, 'conv1_' + res)
+        t = eng.max_pool(t)
+        t = conv_layer(t, 1, 'conv2_' + res)
+        t = eng.max_pool(t)
+        t = conv_layer(t, 1, 'conv3_' + res)
+        return conv_layer(t, 1, 'conv4_' + res)
+
+    H, W = int(x.shape[1]), int(x.shape[2])
+    x1 = branch(x, 'fullres')
+    x2 = branch(eng.resize_bilinear(x, H // 2, W // 2), 'halfres')
+    x2 = eng.resize_bilinear(x2, int(x1.shape[1]), int(x1.shape[2]))
+    x3 = branch(eng.resize_bilinear(x, H // 4, W // 4), 'quarterres')
+    x3 = eng.resize_bilinear(x3, int(x1.shape[1]), int(x1.shape[2]))
+    with torch.cuda.stream(eng._stream):
+        t = x1 + x2 + x3
+        t /= 3
+    del x1, x2, x3
+    t = conv_layer(t, 1, 'conv5')
+    conv_layer(t, 1, 'conv6')
+    out = []
+    for i in range(n_towers):
+        for name in ACTIV_SCOPES:
+            st, cn, size, u8 = found[name]
+            out += var_summary(st[i], cn[i], size, name, baisc_name='tower_%d/pre_activ_' % i)
+            out += _image_values('tower_%d/f_activ_%s' % (i, name), u8[i * n_pics:(i + 1) * n_pics], N_ACTIV_TO_SHOW)
+    return out
+
+
+def _conv_out_channels(eng, name):
+    shape = eng._shapes.get(name + '/weights')
+    if shape is None or len(shape) != 4:
+        raise ValueError("no conv layer '%s' among the engine's parameters" % name)
+    return shape[3]
+
+
+def merged_summary(eng, layout, x=None, y=None, use_sm=True, n_joints=9, grads=None, params_flat=None, clip_norm=4.0, images=True,
+                   activations=False, n_towers=1):
     """tf.summary.merge_all() of the reference graph (main.py:586-597) -> Summary bytes.  x [B,H,W,3], y [B,h,w,K+1]: the
     summary batch (device); images=False leaves out every image (the per-iteration summaries).  The heat maps are the
-    inference-mode tower's (flag_train=False); without the spatial model its pictures repeat the part detector's."""
+    inference-mode tower's (flag_train=False); without the spatial model its pictures repeat the part detector's.
+    activations=True appends activation_summaries(eng, x, n_towers) -- the per-layer tags of main.py:167-168 -- behind the other
+    values; off (the default), the bytes are what they were without the switch."""
     vals = []
     if images:
         vals += _image_values('input', _host(eng, eng.image_u8(x)), N_INPUT_TO_SHOW)
@@ -344,6 +431,10 @@ def merged_summary(eng, layout, x=None, y=None, use_sm=True, n_joints=9, grads=N
         vals += show_img_plus_hm(eng, x, y[..., :n_joints], JOINT_NAMES, H, W, 'target')
         vals += show_img_plus_hm(eng, x, r['pd_prob'], JOINT_NAMES, H, W, 'pred_part_detector')
         vals += show_img_plus_hm(eng, x, r['sm_prob'] if use_sm else r['pd_prob'], JOINT_NAMES, H, W, 'pred_spatial_model')
+    if activations:
+        if x is None:
+            raise ValueError('activations=True needs the summary batch x')
+        vals += activation_summaries(eng, x, n_towers)
     return summary_proto([v.result() if hasattr(v, 'result') else v for v in vals])
 
 
