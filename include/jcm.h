@@ -241,6 +241,21 @@ int jcm_softmax_argmax(jcm_handle h, const float* logits, int B, int HH, int WW,
 int jcm_det_curve(jcm_handle h, const int32_t* pred_coords, const float* y, int B, int HH, int WW, int K, int C, const float* radii, int R,
                   int32_t* true_coords, float* norm_dist, int32_t* hits);
 
+/* Heat-map peaks: the top-P local maxima of every map, their sub-cell offsets and their scores, one launch, one pass over hm.
+ * hm: device fp32 [B,HH,WW,K], probabilities or logits.  Write v(r,c) for one map and i = r*WW + c; every comparison is an IEEE fp32 one.
+ *   local maximum p: v(p) > threshold, v(p) >= v(q) for every in-bounds 8-neighbour q, and v(p) > v(q) for those q whose index is below p's
+ *                    (a plateau yields its first pixel only; the first-occurrence global maximum is one whenever it exceeds threshold);
+ *   order:           value descending, then index ascending; the first min(P, n) are returned, so peak 0 is what jcm_argmax_coords gives
+ *                    whenever count > 0;
+ *   offset:          d_row = +0.25f if rows r-1 and r+1 both exist and v(r+1,c) > v(r-1,c), -0.25f if v(r+1,c) < v(r-1,c), else 0.f (border,
+ *                    equal neighbours); d_col likewise along the columns.  Comparisons, not differences: +-inf in logit maps make no NaN.
+ * cells: device int32 [B,K,P,2] (row, col); offsets: device fp32 [B,K,P,2] (d_row, d_col), may be NULL; scores: device fp32 [B,K,P], the bits
+ * of the input; count: device int32 [B,K].  Slots at or beyond count hold cells -1, offsets 0, score 0.  NaN inputs are outside the contract.
+ * JCM_ERR_ARG for P outside 1..8, B, HH, WW or K below 1 and HH * WW > 21600 (120 x 180): a larger map is refused, never truncated; nothing
+ * is launched and no output is touched then. */
+int jcm_hm_peaks(jcm_handle h, const float* hm, int B, int HH, int WW, int K, int P, float threshold,
+                 int32_t* cells, float* offsets, float* scores, int32_t* count);
+
 /* -- the whole tower ----------------------------------------------------------------------------
  * The graph of main.py:522-531: model -> spatial_softmax -> concat torso -> spatial_model ->
  * spatial_softmax -> argmax.  x [B,H,W,3]; torso [B,60,90,1] = y_in[...,K:] (main.py:528),

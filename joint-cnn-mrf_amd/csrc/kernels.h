@@ -290,6 +290,12 @@ hipError_t softmax_argmax(const float* logits, float* prob, int32_t* coords, int
 // (int32 [K,R], may be null).  radii: R host floats, passed by value.  8 <= K <= C <= 16, 1 <= R <= 32.
 hipError_t det_curve(const int32_t* pred, const float* y, int B, int HW, int WW, int K, int C, const float* radii, int R, int32_t* true_out, float* nd_out,
                      int32_t* hits, hipStream_t st);
+// ---- peaks.hip ---------------------------------------------------------------------------------
+// The top-P local maxima (3x3, first pixel of a plateau, value > threshold) of every map of hm [B,HH,WW,K] by (value descending, index
+// ascending): cells [B,K,P,2], offsets [B,K,P,2] (+-0.25 towards the higher neighbour; may be null), scores [B,K,P], count [B,K]; one launch,
+// one work group per (image, joint group), the maps staged in LDS.  1 <= P <= 8, HH * WW <= 21600.
+hipError_t hm_peaks(const float* hm, int B, int HH, int WW, int K, int P, float threshold, int32_t* cells, float* offsets, float* scores, int32_t* count,
+                    hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

@@ -263,6 +263,31 @@ class Engine:
                                            self._p(out.get('true_coords')), self._p(out.get('norm_dist')), self._p(out['hits'])), 'jcm_det_curve')
         return out
 
+    def hm_peaks(self, hm, max_peaks=4, threshold=0.0):
+        """The top max_peaks local maxima of every map of hm [B,H,W,K] (probabilities or logits) in one launch: a pixel above
+        `threshold` that no 8-neighbour exceeds (the first pixel of a plateau), ranked by value, then by index.  Returns {'cells' int32
+        [B,K,P,2] (row, col), 'offsets' fp32 [B,K,P,2] (+-0.25 of a cell towards the higher neighbour, 0 on the border and between equal
+        neighbours), 'scores' fp32 [B,K,P] (the map's value), 'count' int32 [B,K]}, device tensors; slots from count on hold -1 / 0 / 0.
+        Peak 0 is argmax_coords wherever count > 0.  Nothing is read back.  max_peaks (1..8) and the map size (H * W <= 21600) are checked by
+        the library."""
+        self._chk(hm, 4, 'hm')
+        B, H, W, K = hm.shape
+        P = int(max_peaks)
+        n = max(P, 0)
+        out = {'cells': self._new(B, K, n, 2, dtype=torch.int32), 'offsets': self._new(B, K, n, 2), 'scores': self._new(B, K, n),
+               'count': self._new(B, K, dtype=torch.int32)}
+        self._on_stream(hm, *out.values())
+        _lib.check(self._lib.jcm_hm_peaks(self._h, self._p(hm), B, H, W, K, P, float(threshold), self._p(out['cells']), self._p(out['offsets']),
+                                          self._p(out['scores']), self._p(out['count'])), 'jcm_hm_peaks')
+        return out
+
+    def _add_peaks(self, r, peaks, scratch):
+        """forward(peaks=P) / eval_forward(peaks=P): hm_peaks of the call's probabilities, which are in r (want_prob) or in scratch."""
+        for key in ('pd', 'sm'):
+            prob = r.get(key + '_prob', scratch.get(key + '_prob'))
+            if prob is not None:
+                r[key + '_peaks'] = self.hm_peaks(prob, max_peaks=peaks)
+
     def softmax_argmax(self, logits, want_prob=True):
         """spatial_softmax + arg-max of the probabilities in one kernel (the tail of forward()):
         [B,H,W,K] logits -> (prob [B,H,W,K] or None, coords int32 [B,2,K])."""
@@ -273,10 +298,12 @@ class Engine:
         _lib.check(self._lib.jcm_softmax_argmax(self._h, self._p(logits), B, H, W, K, self._p(prob), self._p(coords)), 'jcm_softmax_argmax')
         return prob, coords
 
-    def forward(self, x, torso=None, use_sm=True, want_prob=True):
+    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0):
         """The tower of main.py:522-531 in one C call.  Returns a dict with 'pd_coords',
         'sm_coords' (int32 [B,2,K]) and, if want_prob, 'pd_prob' / 'sm_prob' [B,60,90,K].  x: float32, or uint8 (byte k standing for
-        float32(k) / float32(255): the same bits out as for that float image, a quarter of the bytes in)."""
+        float32(k) / float32(255): the same bits out as for that float image, a quarter of the bytes in).  peaks = P > 0: also 'pd_peaks'
+        and, with use_sm, 'sm_peaks', the dict of hm_peaks(prob, P) of this call's probabilities (kept in a scratch tensor when
+        want_prob is False); every other entry is what the call without peaks returns."""
         u8 = self._chk_img(x, 'x')
         B, H, W, C = x.shape
         if C != 3:
@@ -295,16 +322,21 @@ class Engine:
             r['sm_coords'] = self._new(B, 2, K, dtype=torch.int32)
             if want_prob:
                 r['sm_prob'] = self._new(B, hh, ww, K)
+        scratch = {}
+        if peaks and not want_prob:
+            scratch = {k + '_prob': self._new(B, hh, ww, K) for k in (('pd', 'sm') if use_sm else ('pd',))}
         fn, what = (self._lib.jcm_forward_u8, 'jcm_forward_u8') if u8 else (self._lib.jcm_forward, 'jcm_forward')
         _lib.check(fn(self._h, self._p(x), self._p(torso if use_sm else None), B, H, W, int(bool(use_sm)),
-                      self._p(r.get('pd_prob')), self._p(r.get('sm_prob')),
+                      self._p(r.get('pd_prob', scratch.get('pd_prob'))), self._p(r.get('sm_prob', scratch.get('sm_prob'))),
                       self._p(r['pd_coords']), self._p(r.get('sm_coords'))), what)
+        if peaks:
+            self._add_peaks(r, peaks, scratch)
         return r
 
-    def eval_forward(self, x, y, use_sm=True, want_prob=True):
+    def eval_forward(self, x, y, use_sm=True, want_prob=True, peaks=0):
         """The tower in inference mode plus the two cross-entropy losses of the graph (main.py:538-539), as eval_error
         runs it per batch (main.py:275-283).  y = y_in [B,60,90,K+1]: targets + torso channel.  Returns the dict of
-        forward() plus 'losses' (device fp32 [2]: loss_pd, loss_sm).  x: float32 or uint8, as for forward()."""
+        forward() plus 'losses' (device fp32 [2]: loss_pd, loss_sm).  x: float32 or uint8, as for forward(); peaks as for forward()."""
         u8 = self._chk_img(x, 'x')
         self._chk(y, 4, 'y')
         B, H, W, C = x.shape
@@ -319,9 +351,14 @@ class Engine:
             if want_prob:
                 r['sm_prob'] = self._new(B, hh, ww, K)
         fn, what = (self._lib.jcm_eval_forward_u8, 'jcm_eval_forward_u8') if u8 else (self._lib.jcm_eval_forward, 'jcm_eval_forward')
+        scratch = {}
+        if peaks and not want_prob:
+            scratch = {k + '_prob': self._new(B, hh, ww, K) for k in (('pd', 'sm') if use_sm else ('pd',))}
         _lib.check(fn(self._h, self._p(x), self._p(y), B, H, W, int(bool(use_sm)),
-                      self._p(r.get('pd_prob')), self._p(r.get('sm_prob')), self._p(r['pd_coords']),
+                      self._p(r.get('pd_prob', scratch.get('pd_prob'))), self._p(r.get('sm_prob', scratch.get('sm_prob'))), self._p(r['pd_coords']),
                       self._p(r.get('sm_coords')), self._p(r['losses'])), what)
+        if peaks:
+            self._add_peaks(r, peaks, scratch)
         return r
 
     def window_resize(self, src, windows, oh, ow):

@@ -33,6 +33,24 @@ def det_rate(heat_map_pred, heat_map_target, normalized_radius=10, joints='all',
     return float(det_rate_from_coords(pred, true, normalized_radius, joints))
 
 
+def peaks_to_pixels(peaks, stride=8):
+    """The dict of Engine.hm_peaks (device tensors or host arrays: 'cells' [N,K,P,2], 'offsets' [N,K,P,2], 'scores' [N,K,P]; 'offsets' may be
+    absent) -> host fp32 [N,K,P,3] = ((row + d_row) * stride, (col + d_col) * stride, score): image pixels by the reference's `coords * 8`
+    (test.py), refined by the sub-cell offsets.  Filler slots (cells -1) give (-1, -1, 0)."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    cells = host(peaks['cells'])
+    scores = host(peaks['scores']).astype(np.float32)
+    offsets = host(peaks['offsets']).astype(np.float32) if peaks.get('offsets') is not None else np.zeros(cells.shape, np.float32)
+    if cells.ndim != 4 or cells.shape[3] != 2 or offsets.shape != cells.shape or scores.shape != cells.shape[:3]:
+        raise ValueError('peaks_to_pixels expects cells / offsets [N,K,P,2] and scores [N,K,P]; got %s, %s, %s' % (cells.shape, offsets.shape, scores.shape))
+    out = np.empty(cells.shape[:3] + (3,), np.float32)
+    out[..., :2] = (cells.astype(np.float32) + offsets) * np.float32(stride)
+    out[..., 2] = scores
+    filler = cells[..., 0] < 0
+    out[filler] = np.array([-1, -1, 0], np.float32)
+    return out
+
+
 def get_next_batch(X, Y, batch_size, shuffle=False, rng=None):
     """main.py:184-192: whole batches only -- the remainder len(X) % batch_size is dropped; `shuffle` draws a permutation."""
     import numpy as np

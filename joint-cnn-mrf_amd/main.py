@@ -72,6 +72,9 @@ def build_parser():
     parser.add_argument('--det_curve', default=None, metavar='PATH', help='evaluation run: write the detection-rate curves of the predictions (every joint, radii '
                         '1..20 %% of the torso length, part detector and spatial model) to this JSON file and print the reference\'s test_dr line '
                         '(main.py:424; DESIGN.md 4.11).')
+    parser.add_argument('--peaks', type=int, default=0, metavar='P', help='evaluation run with --predictions: also write flic_peaks_pd / flic_peaks_sm, [N,K,P,3] = '
+                        '(row, col, score) in image pixels of the P highest local maxima of every heat map, refined by a quarter cell towards the higher '
+                        'neighbour (evaluation.peaks_to_pixels; DESIGN.md 4.12).  1..8; 0 = off.')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -295,6 +298,13 @@ def det_curves_of_predictions(eng, pred_pd, pred_sm, y, radii=range(1, 21), inde
             coords = np.ascontiguousarray(np.asarray(pred)[:, :, lo:hi].transpose(2, 0, 1), dtype=np.int32)      # [n,2,K]
             curve.update(torch.as_tensor(coords, device=eng.device), yb)
     return curves
+
+
+PEAKS_IS_EVALUATION_ONLY = ('--peaks belongs to the evaluation run (it describes the heat maps of the test set that run predicts from); '
+                            'it cannot be combined with --train')
+PEAKS_NEEDS_PREDICTIONS = '--peaks writes flic_peaks_pd / flic_peaks_sm into the file of --predictions: give --predictions PATH as well'
+PEAKS_NOT_WITH_U8_IMAGES = ('--peaks cannot be combined with --u8_images: the streamed byte feed (stream.ForwardStream) returns coordinates only; '
+                            'run it on the float feed')
 
 
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
@@ -542,6 +552,15 @@ def main(argv=None):
         raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
     if args.train and args.u8_images and not args.device_data:
         raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
+    if args.peaks:
+        if args.train:
+            raise SystemExit(PEAKS_IS_EVALUATION_ONLY)
+        if not args.predictions:
+            raise SystemExit(PEAKS_NEEDS_PREDICTIONS)
+        if args.u8_images:
+            raise SystemExit(PEAKS_NOT_WITH_U8_IMAGES)
+        if not 1 <= args.peaks <= 8:
+            raise SystemExit('--peaks %d: 1 <= P <= 8' % args.peaks)
     if args.tb_activations and not args.tb_dir:
         raise SystemExit(TB_ACTIVATIONS_NEEDS_TB_DIR)
     if args.tb_activations and args.precision != 'fp32':
@@ -564,6 +583,7 @@ def main(argv=None):
         x_train, y_train, x_test, y_test = get_dataset(args.data_dir)
         pairwise = get_pairwise_distr(args.data_dir)
     fed = None              # --u8_images: what the single-scale run moved to the devices
+    peaks_pd = peaks_sm = None      # --peaks: the dicts of Engine.hm_peaks over the evaluated images, in the order of pred_pd / pred_sm
     state = restore_params(args.restore_path, args) if args.restore else None
     params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)} if state else initial_params(args, pairwise)
 
@@ -589,13 +609,18 @@ def main(argv=None):
             print('--multiscale evaluates on device %d only; the other --gpus entries are not used' % args.gpus[0], file=sys.stderr)
         configure(params, device=args.gpus[0], precision=args.precision, debug=args.debug)
         eval_tb(engine())
-        pred_pd, pred_sm = get_predictions(np.asarray(x_test), np.asarray(y_test))                     # main.py:674
+        if args.peaks:
+            from . import multiscale
+            pred_pd, pred_sm, peaks_pd, peaks_sm = multiscale.get_predictions(engine(), np.asarray(x_test), np.asarray(y_test), use_sm=hps.use_sm, peaks=args.peaks)
+        else:
+            pred_pd, pred_sm = get_predictions(np.asarray(x_test), np.asarray(y_test))                 # main.py:674
     else:                                                                                              # single scale, sharded over the towers
         hps.debug = bool(args.debug)
         towers = Towers(params, args.gpus, precision=args.precision)
         eval_tb(towers.engines[0])
         B = args.batch_size
         pd, sm = [], []
+        pk_pd, pk_sm = [], []
         if args.u8_images:      # the test images as bytes (converted once, the round trip checked), streamed from pinned memory
             from .dataset import to_u8_exact
             from .stream import ForwardStream
@@ -613,17 +638,27 @@ def main(argv=None):
         else:
             for lo in range(0, (x_test.shape[0] // B) * B, B):
                 r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
-                                   use_sm=args.use_sm)
+                                   use_sm=args.use_sm, peaks=args.peaks)
                 pd.append(r['pd_coords'])
                 sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
+                if args.peaks:
+                    pk_pd.append(r['pd_peaks'])
+                    pk_sm.append(r['sm_peaks'] if args.use_sm else r['pd_peaks'])
         to_ref = lambda c: torch.cat(c).permute(1, 2, 0).cpu().numpy()      # [2,K,N] (row, col) stacked on the last axis, main.py:425
         pred_pd, pred_sm = to_ref(pd), to_ref(sm)
+        if args.peaks:
+            collect = lambda parts: {f: torch.cat([p[f] for p in parts]) for f in parts[0]}
+            peaks_pd, peaks_sm = collect(pk_pd), collect(pk_sm)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.predictions:
         import scipy.io
         os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
-        scipy.io.savemat(args.predictions, {'flic_pred_pd': pred_pd, 'flic_pred_sm': pred_sm})         # main.py:675
+        mat = {'flic_pred_pd': pred_pd, 'flic_pred_sm': pred_sm}                                       # main.py:675
+        if args.peaks:
+            from .evaluation import peaks_to_pixels
+            mat.update(flic_peaks_pd=peaks_to_pixels(peaks_pd), flic_peaks_sm=peaks_to_pixels(peaks_sm))
+        scipy.io.savemat(args.predictions, mat)
     if args.det_curve:      # one place for every feed: the curves of the assembled predictions, counted on the first listed device
         index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus), multiscale=args.multiscale)      # towers drop batch_size % n_gpus of every batch
         c_pd, c_sm = det_curves_of_predictions(engine() if towers is None else towers.engines[0], pred_pd, pred_sm, y_test, index=index)
@@ -640,6 +675,8 @@ def main(argv=None):
             'coords_image0_pd': pred_pd[:, :, 0].tolist()}
     if fed is not None:
         line.update(fed)
+    if args.peaks:
+        line['peaks'] = int(args.peaks)
     print(json.dumps(line))
     if towers is not None:
         towers.close()

@@ -66,16 +66,19 @@ def scale_hm_back(engine, hms, pad_array, crop_array, orig_h, orig_w):
     return engine.window_resize(hms.contiguous(), windows, orig_h, orig_w)
 
 
-def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8):
+def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8, peaks=0):
     """main.py:382-425 without the det_rate bookkeeping: for every image the 8 rescaled copies go
     through the tower (with the UNSCALED target maps repeated, main.py:405), the heat maps are
     scaled back and averaged, and the arg-max coordinates are returned as the reference returns
-    them: int arrays [2, K, N] (row, col) for the part detector and the spatial model."""
+    them: int arrays [2, K, N] (row, col) for the part detector and the spatial model.
+    peaks = P > 0: returns (pd, sm, pd_peaks, sm_peaks), the last two the dicts of Engine.hm_peaks(., P) on the averaged maps the
+    coordinates are the arg-max of, collected over the image groups (device tensors [N,K,P,...]; sm_peaks is pd_peaks without use_sm)."""
     dev = engine.device
     K = engine.n_joints
     n = X.shape[0]
     in_h, in_w = int(X.shape[1]), int(X.shape[2])
     pd_all, sm_all = [], []
+    pd_pk, sm_pk = [], []
     for i0 in range(0, n, images_per_forward):
         x = torch.as_tensor(np.ascontiguousarray(X[i0:i0 + images_per_forward], dtype=np.float32), device=dev)
         y = torch.as_tensor(np.ascontiguousarray(Y[i0:i0 + images_per_forward], dtype=np.float32), device=dev)
@@ -85,10 +88,18 @@ def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8):
         r = engine.forward(xs, torso if use_sm else None, use_sm=use_sm, want_prob=True)
         hm_pd = engine.group_mean(scale_hm_back(engine, r['pd_prob'], PAD_ARRAY, CROP_ARRAY, 60, 90), 8)   # :407,413
         pd_all.append(engine.argmax_coords(hm_pd))                                                # :416
+        if peaks:
+            pd_pk.append(engine.hm_peaks(hm_pd, max_peaks=peaks))
         if use_sm:
             hm_sm = engine.group_mean(scale_hm_back(engine, r['sm_prob'], PAD_ARRAY, CROP_ARRAY, 60, 90), 8)
             sm_all.append(engine.argmax_coords(hm_sm))
+            if peaks:
+                sm_pk.append(engine.hm_peaks(hm_sm, max_peaks=peaks))
         assert m == hm_pd.shape[0]
     pd = torch.cat(pd_all).cpu().numpy().transpose(1, 2, 0)                                       # [2,K,N], :425
     sm = torch.cat(sm_all).cpu().numpy().transpose(1, 2, 0) if use_sm else pd
-    return pd, sm
+    if not peaks:
+        return pd, sm
+    collect = lambda parts: {f: torch.cat([p[f] for p in parts]) for f in parts[0]}
+    pd_peaks = collect(pd_pk)
+    return pd, sm, pd_peaks, collect(sm_pk) if use_sm else pd_peaks
