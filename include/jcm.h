@@ -207,6 +207,21 @@ int jcm_conv_layer_merged(jcm_handle h, const char* scope, const float* x1, cons
 int jcm_max_pool(jcm_handle h, const float* x, int B, int H, int W, int C, float* out);
 /* tf.image.resize_images(x, [OH,OW]) (main.py:51,58,60,67,89): TF-1.x legacy bilinear. */
 int jcm_resize_bilinear(jcm_handle h, const float* x, int B, int H, int W, int C, int OH, int OW, float* out);
+/* The front end of one branch of model(), run by the code the tower runs (one dispatch function serves both):
+ *   pool1(conv1_<res>(x[:, ::sub, ::sub])) (main.py:44-45, 52-53, 61-62).  x [B,H,W,3] device, fp32 or (x_u8 != 0) bytes standing for float32(k) / float32(255);
+ *   sub in {1, 2, 4}, H and W multiples of sub (the tower resizes other images instead of sub-sampling them).  out [B, ceil(ceil(H/sub/2)/2),
+ *   ceil(ceil(W/sub/2)/2), Cout]: fp32 on an fp32 handle, bf16 on a bf16 handle.  Where both sub-sampled extents are multiples of 4 and the layer has 64
+ *   filters this is ONE kernel of conv1_mfma.hip (conv1_mfma_pool_split_kernel on the default fp32 route, conv1_mfma_pool_f32_kernel with conv9_fft = 0 or
+ *   f32_conv = 2, conv1_mfma_pool_kernel on a bf16 handle; the _u8 twins for bytes); everywhere else conv1_5x5s2_kernel followed by the 2x2 pool.
+ *   jcm_conv_kernel_name(scope, B, H / sub, W / sub) names the kernel.  JCM_ERR_ARG before any launch for a bad sub, extents that sub does not divide,
+ *   B outside [1, 65535] or a layer that is not 5x5, Cin = 3 with BatchNorm. */
+int jcm_conv1_pool(jcm_handle h, const char* scope, const void* x, int x_u8, int B, int H, int W, int sub, void* out);
+/*   pool2(conv2_<res>(p1)) (main.py:46-47, 54-55, 63-64) on a bf16 handle.  p1 [B,H,W,Cin] bf16 NHWC -> out [B,ceil(H/2),ceil(W/2),Cout] bf16 NHWC.  scope is
+ *   "conv2_<res>"; "conv3_<res>" must be stored too, because the tower chooses the activation layout between the two (planar [B][C/8][H][W][8] when both run
+ *   on conv5_strip_bf16_kernel) and, with option "bf16_hpool" and an even W, takes the pool's horizontal half in conv2's epilogue.  The same expressions choose
+ *   here; a planar result is copied to NHWC at the end.  An fp32 handle returns JCM_ERR_STATE: there the pooled map is never materialised, conv2 hands conv3 its
+ *   row-transformed input. */
+int jcm_conv2_pool(jcm_handle h, const char* scope, const void* p1, int B, int H, int W, void* out);
 /* model(x, n_joints) (main.py:29-74): x [B,H,W,3] -> logits [B,H/8,W/8,K]. */
 int jcm_pd_forward(jcm_handle h, const float* x, int B, int H, int W, float* logits_out);
 
@@ -396,7 +411,10 @@ uint32_t jcm_crc32c(const void* data, size_t n, uint32_t crc);
 int jcm_profile_read(jcm_handle h, const char* scope, double* total_ms, int* launches);
 /* Name of the HIP kernel a launch of conv layer `scope` on a [B,H,W,Cin] input takes on this handle (the
  * dispatch depends on precision, options and shape); bench.py labels its roofline object with it and the
- * tests assert that the intended kernel is the one that runs. */
+ * tests assert that the intended kernel is the one that runs.  For the stride-2 first layers (Cin == 3) H and W are
+ * the layer's own input extents, i.e. those of the SUB-SAMPLED image: a fused conv1 + pool1 kernel of conv1_mfma.hip
+ * is named only where the tower takes it -- H % 4 == 0, W % 4 == 0 and the packed 64-filter image exists --
+ * and conv1_5x5s2_kernel everywhere else. */
 int jcm_conv_kernel_name(jcm_handle h, const char* scope, int B, int H, int W, char* name, int cap);
 /* Bytes currently held by the workspace arena + packed parameters. */
 int64_t jcm_workspace_bytes(jcm_handle h);

@@ -19,6 +19,8 @@ constexpr int C1_IN = 2 * (C1_PT - 1) + 5;    // 19 input rows/cols per patch
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
+// TO = __bf16 (bf16 handles): image and filter values are rounded to bf16 before they are multiplied, as conv1_mfma_pool_kernel rounds them -- the arithmetic
+// of a bf16 handle (bf16 operands, fp32 accumulation, bf16 result) does not depend on which of the two kernels the image size selects.
 // PixT = float, or uint8_t (byte images, converted by u8_to_f32 at the load).  LIN: the linear epilogue conv + bias (the pre-activation
 // jcm_conv_layer_pre returns); the accumulation is the same code, so z of the LIN instantiation is the value the other one rectifies.
 template <class TO, class PixT, bool LIN = false>
@@ -28,6 +30,7 @@ __device__ __forceinline__ void conv1_body(const PixT* __restrict__ x, const flo
                                            int H0, int W0, int sub, int Hin, int Win, int Ho, int Wo,
                                            int pad_t, int pad_l, int Cout) {
   __shared__ float patch[C1_IN * C1_IN * 3];
+  constexpr bool kBf = sizeof(TO) == 2;
   const int b = blockIdx.z;
   const int oy0 = blockIdx.y * C1_PT, ox0 = blockIdx.x * C1_PT;
   const int tid = threadIdx.x;
@@ -40,7 +43,7 @@ __device__ __forceinline__ void conv1_body(const PixT* __restrict__ x, const flo
     float v = 0.f;
     if ((unsigned)gy < (unsigned)Hin && (unsigned)gx < (unsigned)Win)
       v = px_f32(xb[((size_t)(gy * sub) * W0 + gx * sub) * 3 + c]);
-    patch[i] = v;
+    patch[i] = kBf ? (float)(__bf16)v : v;
   }
   __syncthreads();
   const int lane = tid & 63;
@@ -60,7 +63,7 @@ __device__ __forceinline__ void conv1_body(const PixT* __restrict__ x, const flo
         const float xv = patch[((py * 2 + ky) * C1_IN + px * 2 + kx) * 3 + c];
         const float* wk = wg + (size_t)((ky * 5 + kx) * 3 + c) * Cout;   // wave-uniform address
 #pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = fmaf(xv, wk[j], acc[j]);
+        for (int j = 0; j < 16; ++j) acc[j] = fmaf(xv, kBf ? (float)(__bf16)wk[j] : wk[j], acc[j]);
       }
     }
   }

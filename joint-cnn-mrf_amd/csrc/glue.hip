@@ -102,6 +102,21 @@ hipError_t vpool_2x1_bf16(const void* x, void* out, int B, int H, int W, int C, 
   return hipGetLastError();
 }
 
+// planar [B][C/8][HW][8] -> NHWC [B][HW][C] bf16: one 16-byte unit per thread, a copy (exact)
+__global__ void planar_to_nhwc_bf16_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, size_t HW, size_t C8, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t c8 = i % C8, r = i / C8;
+    const size_t p = r % HW, b = r / HW;
+    out[i] = x[(b * C8 + c8) * HW + p];
+  }
+}
+hipError_t planar_to_nhwc_bf16(const void* x, void* out, int B, int HW, int C, hipStream_t st) {
+  if (C % 8) return hipErrorInvalidValue;
+  const size_t total = (size_t)B * HW * (C / 8);
+  hipLaunchKernelGGL(planar_to_nhwc_bf16_kernel, dim3(grid_for(total)), dim3(256), 0, st, static_cast<const uint4*>(x), static_cast<uint4*>(out), (size_t)HW, (size_t)(C / 8), total);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------ bilinear
 // TF-1.x ResizeBilinear, align_corners=False: scale = in/float(out); src = i*scale (float32);
 // lo = floor(src); hi = min(lo+1, in-1); lerp = src-lo.  Lerp along x, then along y.

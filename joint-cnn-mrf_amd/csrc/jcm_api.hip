@@ -560,6 +560,14 @@ int run_conv(jcm_ctx* c, const std::string& scope, int stride, const void* x, in
   return run_conv_layer(c, L, scope, stride, x, B, H, W, sub, out, act_bf16, out_f32, in_planar, out_planar, x_u8, link, hpool, linear);
 }
 
+// does the stride-2 first layer L1 run fused with its pool (conv1_mfma.hip) on an image whose sub-sampled extents are H x W?  The fused kernels pool whole
+// 2x2 windows of whole conv-output pairs: both extents multiples of 4, and the packed 64-filter image of this handle's precision.
+bool conv1_pool_fused(const jcm_ctx* c, const ConvLayer* L1, int H, int W) {
+  return (c->precision == JCM_PRECISION_BF16 ? L1->wq1_bf16 != nullptr : L1->wq1_f32 != nullptr) && H % 4 == 0 && W % 4 == 0;
+}
+// ... fp32 handles: on split operands (conv1_mfma_pool_split_kernel) rather than the exact fp32 chain (conv1_mfma_pool_f32_kernel)?
+bool conv1_split_route(const jcm_ctx* c, const ConvLayer* L1) { return c->conv9_fft && c->f32_conv == 0 && L1->wq1_split; }
+
 // bf16 handles: does a [B,H,W,Cin] launch of this 9x9 layer take the flattened-strip kernel (which reads / writes the
 // planar activation layout at full speed)?
 bool takes_strip(const ConvLayer* L, int B, int H, int W) {
@@ -576,6 +584,64 @@ bool takes_c5strip(const ConvLayer* L, int B, int H, int W) {
   ConvArgs a{};
   a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.CoutP = L->coutp_bf16;
   return conv5_strip_bf16_supported(a, L->ks);
+}
+
+// conv1_<res> + pool1 (main.py:44-45, 52-53, 61-62) of a [B,xh,xw,3] image read at every xsub-th pixel of every xsub-th row (float, or bytes: x_u8), as
+// the tower runs them -- and as jcm_conv1_pool does, which calls this too.  Sub-sampled extents that are multiples of 4 with a 64-filter BatchNorm layer:
+// ONE MFMA kernel, only the pooled map reaches memory.  fp32 handles take it on split operands on the default route (the stride-1 layers run on split
+// operands there anyway), on the exact fp32 MFMA chain otherwise; bf16 handles on bf16 operands.  Every other geometry: the generic stride-2 kernel, then
+// the pool.  The pooled map [B, ceil(ceil(xh/xsub/2)/2), ceil(ceil(xw/xsub/2)/2), Cout] (fp32, bf16 on a bf16 handle) goes to `dst`, or to the arena when
+// dst is null; *p1 is where it is.
+int conv1_pool_stage(jcm_ctx* c, const std::string& scope, const ConvLayer* L1, const void* xin, bool xin_u8, int B, int xh, int xw, int xsub, void* dst, void** p1) {
+  const bool bf = c->precision == JCM_PRECISION_BF16;
+  const size_t es = bf ? 2 : 4;
+  auto act = [&](size_t elems) { return static_cast<void*>(arena_alloc<char>(c, elems * es)); };
+  const int h1 = cdiv2(xh / xsub), w1 = cdiv2(xw / xsub);
+  const int h2 = cdiv2(h1), w2 = cdiv2(w1);
+  if (conv1_pool_fused(c, L1, xh / xsub, xw / xsub)) {      // (xh, xw are multiples of xsub: the tower resizes otherwise, the entry refuses)
+    *p1 = dst ? dst : act((size_t)B * h2 * w2 * L1->cout);
+    if (c->dry) return JCM_OK;
+    if (bf) {
+      // bf16 path: conv1 + ReLU/BN + pool1 in one MFMA kernel; only the pooled map touches HBM
+      HIP_TRY(conv1_mfma_pool(xin, L1->wq1_bf16, L1->bias, L1->scale, L1->shift, *p1, B, xh, xw, xsub, c->stream, xin_u8));
+    } else {
+      // fp32 path: conv1 + ReLU/BN + pool1 in one fp32-MFMA kernel (the unpooled 240x360x64 map never reaches HBM)
+      // default route (the stride-1 layers run on split operands on the bf16 matrix cores): conv1 too; the exact fp32 MFMA chain otherwise
+      HIP_TRY(conv1_split_route(c, L1) ? conv1_mfma_pool_split(xin, L1->wq1_split, L1->bias, L1->scale, L1->shift, static_cast<float*>(*p1), B, xh, xw, xsub, c->stream, xin_u8)
+                                       : conv1_mfma_pool_f32(xin, L1->wq1_f32, L1->bias, L1->scale, L1->shift, static_cast<float*>(*p1), B, xh, xw, xsub, c->stream, xin_u8));
+    }
+    return JCM_OK;
+  }
+  void* c1 = act((size_t)B * h1 * w1 * L1->cout);
+  JCM_TRY(run_conv(c, scope, 2, xin, B, xh, xw, xsub, c1, bf, false, 0, 0, xin_u8));
+  *p1 = dst ? dst : act((size_t)B * h2 * w2 * L1->cout);
+  if (!c->dry) HIP_TRY(max_pool_2x2(c1, *p1, bf, B, h1, w1, L1->cout, c->stream));
+  return JCM_OK;
+}
+
+// conv2_<res> -> pool2 on a bf16 handle (main.py:46-47, 54-55, 63-64), a [B,h2,w2,C] map: the activation layout between conv2, the pool and conv3, and where
+// the pool's horizontal half is taken.  One place for the tower and jcm_conv2_pool.
+struct Pool2Layout {
+  // planar activations [B][C/8][H][W][8] when both 5x5 layers take the strip kernel (its window rows are then 1-KB contiguous LDS-DMA reads; from NHWC every
+  // 16-byte unit of a pixel is a separate cache line).  A planar tensor IS an NHWC tensor of B*C/8 images with 8 channels: the pooling kernel runs on it unchanged.
+  int pl23;
+  // ... and the pool's horizontal half is taken in conv2's epilogue (even widths): conv2 then writes the [.., h2, w2 / 2, ..] map of pixel-pair maxima
+  int hp;
+};
+Pool2Layout pool2_layout(jcm_ctx* c, const ConvLayer* L2, const ConvLayer* L3, int B, int h2, int w2) {
+  const bool bf = c->precision == JCM_PRECISION_BF16;
+  const int sk = c->debug_skip;
+  Pool2Layout l;
+  l.pl23 = bf && takes_c5strip(L2, B, h2, w2) && takes_c5strip(L3, B, cdiv2(h2), cdiv2(w2)) ? 1 : 0;
+  l.hp = l.pl23 && c->bf16_hpool && w2 % 2 == 0 && !(sk & 6) ? 1 : 0;
+  return l;
+}
+// the pool behind conv2: c2 as conv2 wrote it under `l` -> p2 [B,ceil(h2/2),ceil(w2/2),C] in the same layout
+hipError_t pool2_launch(jcm_ctx* c, const Pool2Layout& l, const void* c2, void* p2, int B, int h2, int w2, int C) {
+  const bool bf = c->precision == JCM_PRECISION_BF16;
+  if (l.hp) return vpool_2x1_bf16(c2, p2, B * (C / 8), h2, w2 / 2, 8, c->stream);
+  if (l.pl23) return max_pool_2x2(c2, p2, bf, B * (C / 8), h2, w2, 8, c->stream);
+  return max_pool_2x2(c2, p2, bf, B, h2, w2, C, c->stream);
 }
 
 // fp32 handles: two consecutive frequency-domain layers on the same map -- the first one's fused inverse/forward row kernel writes the
@@ -681,48 +747,21 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
       if (!c->dry) HIP_TRY(resize_bilinear(xf, xr, B, H, W, 3, hin, win, c->stream));
       xin = xr; xin_u8 = false; xh = hin; xw = win; xsub = 1;
     }
-    const int h1 = cdiv2(hin), w1 = cdiv2(win);
-    const int h2 = cdiv2(h1), w2 = cdiv2(w1);
-    void* p1;
+    const int h2 = cdiv2(cdiv2(hin)), w2 = cdiv2(cdiv2(win));
+    void* p1 = nullptr;
     const int sk = c->debug_skip;
-    if (sk & 1) { p1 = act((size_t)B * h2 * w2 * L1->cout); }
-    else if (!bf && L1->wq1_f32 && xh % (4 * xsub) == 0 && xw % (4 * xsub) == 0) {
-      // fp32 path: conv1 + ReLU/BN + pool1 in one fp32-MFMA kernel (the unpooled 240x360x64 map never reaches HBM)
-      p1 = act((size_t)B * h2 * w2 * L1->cout);
-      // default route (the stride-1 layers run on split operands on the bf16 matrix cores): conv1 too; the exact fp32 MFMA chain otherwise
-      const bool split1 = c->conv9_fft && c->f32_conv == 0 && L1->wq1_split;
-      if (!c->dry)
-        HIP_TRY(split1 ? conv1_mfma_pool_split(xin, L1->wq1_split, L1->bias, L1->scale, L1->shift, static_cast<float*>(p1), B, xh, xw, xsub, c->stream, xin_u8)
-                       : conv1_mfma_pool_f32(xin, L1->wq1_f32, L1->bias, L1->scale, L1->shift, static_cast<float*>(p1), B, xh, xw, xsub, c->stream, xin_u8));
-    } else if (bf && L1->wq1_bf16 && xh % (4 * xsub) == 0 && xw % (4 * xsub) == 0) {
-      // bf16 path: conv1 + ReLU/BN + pool1 in one MFMA kernel; only the pooled map touches HBM
-      p1 = act((size_t)B * h2 * w2 * L1->cout);
-      if (!c->dry)
-        HIP_TRY(conv1_mfma_pool(xin, L1->wq1_bf16, L1->bias, L1->scale, L1->shift, p1, B, xh, xw, xsub, c->stream, xin_u8));  // :44-45,52-53,61-62
-    } else {
-      void* c1 = act((size_t)B * h1 * w1 * L1->cout);
-      JCM_TRY(run_conv(c, "conv1_" + res, 2, xin, B, xh, xw, xsub, c1, bf, false, 0, 0, xin_u8));       // main.py:44,52,61
-      p1 = act((size_t)B * h2 * w2 * L1->cout);
-      if (!c->dry) HIP_TRY(max_pool_2x2(c1, p1, bf, B, h1, w1, L1->cout, c->stream));       // :45,53,62
-    }
+    if (sk & 1) p1 = act((size_t)B * h2 * w2 * L1->cout);
+    else JCM_TRY(conv1_pool_stage(c, "conv1_" + res, L1, xin, xin_u8, B, xh, xw, xsub, nullptr, &p1));      // main.py:44-45,52-53,61-62
     const int h3 = cdiv2(h2), w3 = cdiv2(w2);
     // fp32 handles: conv2 -> pool2 -> conv3 as one hand-over in row-transformed form (the pool inside the fused row kernel)
     FftLink k2, k3, k4;      // conv2 -> (pool) -> conv3 -> conv4 of this branch
     void* t23 = (bf || sk) ? nullptr : offer_pool_handover(c, L2, L3, B, h2, w2, k2);
     void* c2 = t23 ? nullptr : act((size_t)B * h2 * w2 * L2->cout);
-    // bf16: conv2 -> pool2 -> conv3 on planar activations when both 5x5 layers take the strip kernel (its window rows are then 1-KB
-    // contiguous LDS-DMA reads; from NHWC every 16-byte unit of a pixel is a separate cache line).  A planar [B][C/8][H][W][8] tensor IS an
-    // NHWC tensor of B*C/8 images with 8 channels: the pooling kernel runs on it unchanged.
-    const int pl23 = bf && takes_c5strip(L2, B, h2, w2) && takes_c5strip(L3, B, h3, w3) ? 1 : 0;
-    // ... and the pool's horizontal half is taken in conv2's epilogue (even widths): c2 is then the [.., h2, w2 / 2, ..] map of pixel-pair maxima
-    const int hp = pl23 && c->bf16_hpool && w2 % 2 == 0 && !(sk & 6) ? 1 : 0;
+    const Pool2Layout lay = pool2_layout(c, L2, L3, B, h2, w2);
+    const int pl23 = lay.pl23, hp = lay.hp;
     if (!(sk & 4)) JCM_TRY(run_conv(c, "conv2_" + res, 1, p1, B, h2, w2, 1, c2, bf, false, 0, pl23, false, &k2, hp));     // :46,54,63
     void* p2 = t23 ? nullptr : act((size_t)B * h3 * w3 * L2->cout);
-    if (!c->dry && !(sk & 2) && !t23) {                                                     // :47,55,64
-      if (hp) HIP_TRY(vpool_2x1_bf16(c2, p2, B * (L2->cout / 8), h2, w2 / 2, 8, c->stream));
-      else if (pl23) HIP_TRY(max_pool_2x2(c2, p2, bf, B * (L2->cout / 8), h2, w2, 8, c->stream));
-      else HIP_TRY(max_pool_2x2(c2, p2, bf, B, h2, w2, L2->cout, c->stream));
-    }
+    if (!c->dry && !(sk & 2) && !t23) HIP_TRY(pool2_launch(c, lay, c2, p2, B, h2, w2, L2->cout));      // :47,55,64
     const ConvLayer* L4r = conv_of(c, "conv4_" + res);
     if (!L4r) return fail(JCM_ERR_STATE, "part-detector parameters incomplete (conv4_" + res + ")");
     const int in4 = planar && L3->cout % 8 == 0 && takes_strip(L4r, B, h3, w3) && !takes_fft(c, L4r, B, h3, w3) ? 1 : 0;      // the patch kernels and the row pass read NHWC
@@ -1036,6 +1075,53 @@ static int pd_forward_entry(jcm_handle h, const void* x, bool x_u8, int B, int H
 }
 int jcm_pd_forward(jcm_handle h, const float* x, int B, int H, int W, float* logits_out) { return pd_forward_entry(h, x, false, B, H, W, logits_out); }
 int jcm_pd_forward_u8(jcm_handle h, const uint8_t* x, int B, int H, int W, float* logits_out) { return pd_forward_entry(h, x, true, B, H, W, logits_out); }
+
+// pool1(conv1_<res>(x[:, ::sub, ::sub])) through conv1_pool_stage, the function the tower calls.  Everything is checked before the first launch.
+int jcm_conv1_pool(jcm_handle h, const char* scope, const void* x, int x_u8, int B, int H, int W, int sub, void* out) {
+  JCM_TRY(check(h, true));
+  if (!scope || !x || !out || B < 1 || B > 65535 || H < 1 || W < 1) return fail(JCM_ERR_ARG, "bad conv1_pool arguments (B in [1, 65535], H, W >= 1)");
+  if (sub != 1 && sub != 2 && sub != 4) return fail(JCM_ERR_ARG, "conv1_pool: sub must be 1, 2 or 4, got " + std::to_string(sub));
+  if (H % sub || W % sub)
+    return fail(JCM_ERR_ARG, "conv1_pool: H and W must be multiples of sub (the tower resizes such an image instead of sub-sampling it), got " + std::to_string(H) + " x " + std::to_string(W));
+  if ((int64_t)B * H * W * 3 >= ((int64_t)1 << 40)) return fail(JCM_ERR_ARG, "conv1_pool: tensor too large");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  const ConvLayer* L = conv_of(h, scope);
+  if (!L) return fail(JCM_ERR_STATE, std::string("no conv layer '") + scope + "'");
+  if (!(L->ks == 5 && L->cin == 3 && L->has_bn && L->cout % 16 == 0 && L->cout <= 64))
+    return fail(JCM_ERR_ARG, std::string("conv1_pool: a 5x5, Cin = 3, BatchNorm layer with Cout % 16 == 0, Cout <= 64 is expected ('") + scope + "')");
+  void* p1 = nullptr;
+  return with_arena(h, [&] { return conv1_pool_stage(h, scope, L, x, x_u8 != 0, B, H, W, sub, out, &p1); });
+}
+
+// pool2(conv2_<res>(p1)) of a bf16 handle as the tower runs it (pool2_layout, pool2_launch), brought to NHWC at the end.
+int jcm_conv2_pool(jcm_handle h, const char* scope, const void* p1, int B, int H, int W, void* out) {
+  JCM_TRY(check(h, true));
+  if (!scope || !p1 || !out || B < 1 || H < 1 || W < 1) return fail(JCM_ERR_ARG, "bad conv2_pool arguments");
+  if (std::strncmp(scope, "conv2_", 6) != 0) return fail(JCM_ERR_ARG, std::string("conv2_pool: scope must be conv2_<res>, got '") + scope + "'");
+  if (h->precision != JCM_PRECISION_BF16)
+    return fail(JCM_ERR_STATE, "conv2_pool: bf16 handles only -- on an fp32 handle the pooled map is never materialised (conv2 hands conv3 its row-transformed input); this is an fp32 handle");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  const ConvLayer* L2 = conv_of(c, scope);
+  const ConvLayer* L3 = conv_of(c, std::string("conv3_") + (scope + 6));      // the tower's layout choice looks at the consumer too
+  if (!L2 || !L3) return fail(JCM_ERR_STATE, std::string("conv2_pool: no conv layer '") + (L2 ? std::string("conv3_") + (scope + 6) : std::string(scope)) + "'");
+  if (!(L2->ks == 5 && L2->has_bn && L2->wp_bf16 && L2->cout % 8 == 0))
+    return fail(JCM_ERR_ARG, std::string("conv2_pool: a 5x5 BatchNorm layer with Cout % 8 == 0 is expected ('") + scope + "')");
+  if ((int64_t)B * H * W * std::max(L2->cin, L2->cout) >= ((int64_t)1 << 40)) return fail(JCM_ERR_ARG, "conv2_pool: tensor too large");
+  return with_arena(c, [&] {
+    const int h3 = cdiv2(H), w3 = cdiv2(W);
+    const Pool2Layout lay = pool2_layout(c, L2, L3, B, H, W);
+    void* c2 = arena_alloc<char>(c, (size_t)B * H * W * L2->cout * 2);
+    JCM_TRY(run_conv(c, scope, 1, p1, B, H, W, 1, c2, true, false, 0, lay.pl23, false, nullptr, lay.hp));
+    void* p2 = lay.pl23 ? static_cast<void*>(arena_alloc<char>(c, (size_t)B * h3 * w3 * L2->cout * 2)) : out;
+    if (c->dry) return (int)JCM_OK;
+    HIP_TRY(pool2_launch(c, lay, c2, p2, B, H, W, L2->cout));
+    if (lay.pl23) HIP_TRY(planar_to_nhwc_bf16(p2, out, B, h3 * w3, L2->cout, c->stream));
+    return (int)JCM_OK;
+  });
+}
 
 int jcm_spatial_softmax(jcm_handle h, const float* in, int B, int HW, int K, float* out) {
   JCM_TRY(check(h, false));
@@ -1364,8 +1450,9 @@ int jcm_conv_kernel_name(jcm_handle h, const char* scope, int B, int H, int W, c
   ConvArgs a{};
   a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout; a.relu_bn = L->has_bn ? 1 : 0;
   const char* k;
-  if (L->cin == 3) {
-    k = h->precision == JCM_PRECISION_BF16 ? (L->wq1_bf16 ? "conv1_mfma_pool_kernel" : "conv1_5x5s2_kernel") : (L->wq1_f32 ? (h->conv9_fft && h->f32_conv == 0 && L->wq1_split ? "conv1_mfma_pool_split_kernel" : "conv1_mfma_pool_f32_kernel") : "conv1_5x5s2_kernel");
+  if (L->cin == 3) {      // H x W: the sub-sampled image; the fused kernels where the tower takes them (conv1_pool_stage), the generic one otherwise
+    k = !conv1_pool_fused(h, L, H, W) ? "conv1_5x5s2_kernel"
+        : h->precision == JCM_PRECISION_BF16 ? "conv1_mfma_pool_kernel" : conv1_split_route(h, L) ? "conv1_mfma_pool_split_kernel" : "conv1_mfma_pool_f32_kernel";
   } else if (h->precision == JCM_PRECISION_BF16) {
     a.CoutP = L->coutp_bf16;
     a.in_planar = 0;

@@ -271,6 +271,8 @@ hipError_t conv1_mfma_pool_f32(const void* x, const float* wq, const float* bias
 hipError_t max_pool_2x2(const void* x, void* out, bool bf16, int B, int H, int W, int C, hipStream_t st);
 // the lower half of the pool behind a conv5_strip_bf16 launch with hpool: out[b][y][x][c] = max(in[b][2 y][x][c], in[b][2 y + 1][x][c]) (bf16, C % 8 == 0)
 hipError_t vpool_2x1_bf16(const void* x, void* out, int B, int H, int W, int C, hipStream_t st);
+// bf16 planar [B][C/8][HW][8] -> NHWC [B][HW][C] (C % 8 == 0): a copy
+hipError_t planar_to_nhwc_bf16(const void* x, void* out, int B, int HW, int C, hipStream_t st);
 hipError_t resize_bilinear(const float* x, float* out, int B, int H, int W, int C, int OH, int OW, hipStream_t st);
 // out = (x1 + resize(x2) + resize(x3)) / 3   (main.py:58,67,69-70); x1 [B,H,W,C]
 hipError_t upsample_merge3(const void* x1, const void* x2, int H2, int W2, const void* x3, int H3, int W3,

@@ -186,6 +186,32 @@ class Engine:
         _lib.check(self._lib.jcm_resize_bilinear(self._h, self._p(x), B, H, W, C, oh, ow, self._p(out)), 'jcm_resize_bilinear')
         return out
 
+    def conv1_pool(self, x, scope, sub=1):
+        """pool1(conv1_<res>(x[:, ::sub, ::sub])) (main.py:44-45,52-53,61-62) by the dispatch the tower uses: x [B,H,W,3] float32 or uint8, sub in
+        {1, 2, 4} dividing H and W -> the pooled map, float32 (bfloat16 on a bf16 engine)."""
+        u8 = self._chk_img(x, 'x')
+        B, H, W, C = x.shape
+        if C != 3:
+            raise ValueError('x must be [B,H,W,3], got %s' % (tuple(x.shape),))
+        if sub not in (1, 2, 4) or H % sub or W % sub:
+            raise ValueError('sub must be 1, 2 or 4 and divide H and W, got sub = %r for %d x %d' % (sub, H, W))
+        n_out = self._shapes[scope + '/weights'][3]
+        out = self._new(B, (H // sub + 3) // 4, (W // sub + 3) // 4, n_out, dtype=torch.bfloat16 if self.precision == 'bf16' else torch.float32)      # ceil(ceil(n/2)/2) = ceil(n/4)
+        self._on_stream(x, out)
+        _lib.check(self._lib.jcm_conv1_pool(self._h, scope.encode(), self._p(x), int(u8), B, H, W, int(sub), self._p(out)), 'jcm_conv1_pool(%s)' % scope)
+        return out
+
+    def conv2_pool(self, p1, scope):
+        """pool2(conv2_<res>(p1)) (main.py:46-47,54-55,63-64) of a bf16 engine as the tower runs it: p1 [B,H,W,Cin] bfloat16 -> [B,ceil(H/2),ceil(W/2),Cout]
+        bfloat16.  An fp32 engine raises RuntimeError: its tower never materialises the pooled map."""
+        self._chk(p1, 4, 'p1', torch.bfloat16)
+        B, H, W, _ = p1.shape
+        n_out = self._shapes[scope + '/weights'][3]
+        out = self._new(B, (H + 1) // 2, (W + 1) // 2, n_out, dtype=torch.bfloat16)
+        self._on_stream(p1, out)
+        _lib.check(self._lib.jcm_conv2_pool(self._h, scope.encode(), self._p(p1), B, H, W, self._p(out)), 'jcm_conv2_pool(%s)' % scope)
+        return out
+
     def model(self, x):
         """main.py:29-74: [B,H,W,3] (float32 or uint8) -> logits [B,H/8,W/8,K]."""
         u8 = self._chk_img(x, 'x')
