@@ -1,5 +1,6 @@
 // Internal context of libjcm shared by the translation units behind include/jcm.h
-// (jcm_api.hip: inference graph; jcm_train.hip: training step).  Not part of the ABI.
+// (jcm_api.hip: entry points, call order, arena; conv_route.hip: how one conv layer runs; derived.hip: weight packings; pd_tower.hip: inference graph;
+// jcm_train.hip: training step).  Not part of the ABI.
 #pragma once
 #include "../../include/jcm.h"
 
@@ -96,7 +97,7 @@ struct jcm_ctx {
   int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)
   int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (ConvArgs::rows_mfma; conv_fft_rows_mfma.hip)
   int fft_reg = 1;              // the register-resident transform kernels of conv_fft_rows_reg.hip where they exist (ConvArgs::fft_reg); 0 = the LDS kernels for every pass
-  int fft_cache_gb = 64;        // bound of the filter-spectra cache fft_w (run_conv_fft drops the other layers' spectra before it grows past it)
+  int fft_cache_gb = 64;        // bound of the filter-spectra cache (conv_route.hip: a new entry that would grow it past the bound drops the others first)
   int fft_win = 1;              // training step of fp32 handles: frequency-domain layers on 32 x 32 overlap-save windows where that shrinks the filter-sized spectra (jcm_train.hip)
   int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel
   int sm_chunk = 32;            // training step: images per slice of the spatial model's backward pass (81 + 10 spectra per image live at once)
@@ -119,7 +120,7 @@ struct jcm_ctx {
   int* cond0 = nullptr;         // single zero (jcm_conv_mrf)
   float2* prior_spec_t = nullptr; // [P][91][120]: transposed half spectra of softplus5(energy) (sm_lds.hip)
   struct FftW { void* p = nullptr; size_t bytes = 0; bool valid = false; float* wscale = nullptr; };      // wscale: two device floats behind the spectra (np = 4)
-  std::map<std::string, FftW> fft_w;   // filter spectra per "<scope>@HxW", computed on first use, invalidated by refresh_derived
+  std::map<std::string, FftW> fft_w;   // the filter-spectra cache; touched by the fft_cache_* functions of conv_route.hip only
   double* hist_limits = nullptr;      // summary.hip: the positive half of TF's histogram bucket limits (uploaded on first use)
   jcm::TrainState* train = nullptr;   // created by jcm_train_begin
   // ---- workspace ----
@@ -203,46 +204,104 @@ int sm_scratch_next(jcm_ctx* c, void** scratch, unsigned* epoch);      // sm_fus
 const Tensor* find(jcm_ctx* c, const std::string& name);
 int check(jcm_handle h, bool need_final);
 const ConvLayer* conv_of(jcm_ctx* c, const std::string& scope);
+// ---- derived.hip ----
 int fold_bn(jcm_ctx* c, const std::string& scope, int n, float** scale, float** shift);
 // Rebuild every derived table (packed weights, folded BN, softplus'd priors and their spectra) from
 // the parameter store; called by jcm_finalize and after each optimizer update.
 int refresh_derived(jcm_ctx* c, bool first);
+// ---- jcm_api.hip ----
 // HIP-event pairs for the per-layer timing come from a pool: inside a timed region the only cost is two
 // hipEventRecord per launch (events are created on first use and recycled by jcm_profile_read).
+int prof_event(jcm_ctx* c, hipEvent_t* e);      // one event from the pool
 int prof_begin(jcm_ctx* c, hipEvent_t* e0, hipEvent_t* e1);
 void prof_end(jcm_ctx* c, const std::string& scope, hipEvent_t e0, hipEvent_t e1, bool ok);
 void prof_release_all(jcm_ctx* c, bool destroy);
-// frequency-domain route (jcm_api.hip): takes_fft() says whether a layer / shape goes there; run_conv_fft() runs it (filter spectra cached in
-// c->fft_w under "<scope>@HxW", packed from L->w_raw when missing or invalidated); the training step uses both for its data gradient.
-// link (kernels.h: FftLink): what ties the call to the neighbouring frequency-domain layers -- requests read from it, the two scale-word results written to it;
-// null = the layer stands alone.  A non-empty link, or hpool (ConvArgs::hpool), for a layer that does not take the route it is meant for is JCM_ERR_STATE.
+
+// ---- conv_route.hip: how one conv layer runs ----
+// the zero-initialised launch arguments of layer L on a [B,H,W,Cin] input; callers set further fields after the call
+inline ConvArgs conv_args(const ConvLayer* L, int B, int H, int W) {
+  ConvArgs a{};
+  a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout;
+  return a;
+}
+// One conv-layer request: what run_conv / run_conv_layer / run_conv_fft need beyond the layer.  Call sites name the fields they set.
+struct ConvCall {
+  const void* x = nullptr;      // [B,H,W,Cin] (stride 2: the image, read at every sub-th pixel of every sub-th row)
+  void* out = nullptr;
+  int B = 0, H = 0, W = 0;
+  int stride = 1, sub = 1;
+  bool act_bf16 = false;        // bf16 activations (the handle runs the bf16 path)
+  bool out_f32 = false;         // ... with an fp32 result all the same (the logits layer)
+  int in_planar = 0, out_planar = 0;      // bf16 layouts: ConvArgs in kernels.h
+  bool x_u8 = false;            // the stride-2 layer reads a byte image
+  // link (kernels.h: FftLink): what ties the call to the neighbouring frequency-domain layers -- requests read from it, the two scale-word results written to it;
+  // null = the layer stands alone.  A non-empty link, or hpool (ConvArgs::hpool), for a layer that does not take the route it is meant for is JCM_ERR_STATE.
+  FftLink* link = nullptr;
+  int hpool = 0;
+  int linear = 0;               // the epilogue stops at conv + bias whatever the layer's BatchNorm (jcm_conv_layer_pre)
+  int circ = 0;                 // run_conv_fft only: x is a batch of overlap-save windows [B, H, W, Cin] that fill the transform, out their valid regions [B, H - 8, W - 8, Cout] (ConvArgs::circ)
+};
+inline ConvCall conv_call(const void* x, void* out, int B, int H, int W) {
+  ConvCall q;
+  q.x = x; q.out = out; q.B = B; q.H = H; q.W = W;
+  return q;
+}
+// takes_fft() says whether a layer / shape goes to the frequency domain; run_conv_fft() runs it (filter spectra from the cache, packed from L->w_raw when
+// missing or invalidated); the training step uses both for its data gradient.
 bool takes_fft(jcm_ctx* c, const ConvLayer* L, int B, int H, int W);
-bool fft_spectra_valid(jcm_ctx* c, const std::string& scope, int H, int W, int circ = 0);
+bool takes_strip(const ConvLayer* L, int B, int H, int W);       // bf16: conv_strip_bf16_kernel
+bool takes_c5strip(const ConvLayer* L, int B, int H, int W);     // bf16: conv5_strip_bf16_kernel
+const char* conv_kernel_name(jcm_ctx* c, const ConvLayer* L, int B, int H, int W);
 // operand form of the channel GEMM on this handle (kernels.h): bf16 handles: 5 (one scaled fp16 part, default) or 2 (two bf16 parts); fp32 handles: 4 (two scaled fp16 parts)
 inline int fft_np(const jcm_ctx* c) { return c->precision == JCM_PRECISION_BF16 ? (c->fft_single ? 5 : 2) : 4; }
 int fft_new_words(jcm_ctx* c, int n, float** w);      // n zeroed device words of the scaling ring (one per image)
-// circ: x is a batch of overlap-save windows [B, H, W, Cin] that fill the transform, out their valid regions [B, H - 8, W - 8, Cout] (ConvArgs::circ)
-int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const void* x, int B, int H, int W, void* out, int in_layout, int out_layout, int circ = 0, FftLink* link = nullptr,
-                 int linear = 0);      // linear: the epilogue stops at conv + bias whatever the layer's BatchNorm (jcm_conv_layer_pre)
-int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, int stride, const void* x, int B, int H, int W, int sub,
-                   void* out, bool act_bf16, bool out_f32, int in_planar = 0, int out_planar = 0, bool x_u8 = false, FftLink* link = nullptr, int hpool = 0, int linear = 0);   // bf16 layouts: ConvArgs in kernels.h; x_u8: the stride-2 layer reads a byte image
+int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const ConvCall& q);      // reads x, out, B, H, W, the bf16 layout fields, link, linear, circ
+int run_conv_layer(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const ConvCall& q);
+int run_conv(jcm_ctx* c, const std::string& scope, const ConvCall& q);      // ... of the stored layer `scope`
+// the filter-spectra cache (jcm_ctx::fft_w)
+bool fft_spectra_valid(jcm_ctx* c, const std::string& scope, int H, int W, int circ = 0);
+void fft_cache_drop(jcm_ctx* c);            // free every entry (the caller has synchronised the stream)
+void fft_cache_invalidate(jcm_ctx* c);      // the weights changed: every entry is repacked on next use
 
 inline int cdiv2(int v) { return (v + 1) / 2; }
 
-// Sizing pass then the real pass, so the arena never reallocates mid-graph.
-template <class F>
-int with_arena(jcm_ctx* c, F&& body) {
+// Sizing pass then the real pass, so the arena never reallocates mid-graph.  `sizing` runs dry (offsets only, nothing launched) and leaves the peak;
+// `real` runs on the reserved arena.  The only place that writes c->dry.
+template <class S, class R>
+int with_arena(jcm_ctx* c, S&& sizing, R&& real) {
   // a call from inside the gradient-ready callback of this handle's running training step would overwrite that step's workspace
   if (c->call_depth > 1) return fail(JCM_ERR_STATE, "this entry point uses the handle's workspace and cannot be called from the gradient-ready callback of the same handle");
   c->dry = true;
   c->arena_off = 0;
   c->arena_peak = 0;
-  int r = body();
+  int r = sizing();
   c->dry = false;
   if (r != JCM_OK) return r;
   JCM_TRY(arena_reserve(c, c->arena_peak));
   c->arena_off = 0;
-  return body();
+  return real();
 }
+template <class F>
+int with_arena(jcm_ctx* c, F&& body) {
+  return with_arena(c, body, body);
+}
+
+// ---- pd_tower.hip: the tower and the stages its entry points share with it ----
+bool conv1_pool_fused(const jcm_ctx* c, const ConvLayer* L1, int H, int W);
+bool conv1_split_route(const jcm_ctx* c, const ConvLayer* L1);
+int conv1_pool_stage(jcm_ctx* c, const std::string& scope, const ConvLayer* L1, const void* xin, bool xin_u8, int B, int xh, int xw, int xsub, void* dst, void** p1);
+// conv2_<res> -> pool2 on a bf16 handle (main.py:46-47, 54-55, 63-64), a [B,h2,w2,C] map: the activation layout between conv2, the pool and conv3, and where
+// the pool's horizontal half is taken.  One place for the tower and jcm_conv2_pool.
+struct Pool2Layout {
+  // planar activations [B][C/8][H][W][8] when both 5x5 layers take the strip kernel (its window rows are then 1-KB contiguous LDS-DMA reads; from NHWC every
+  // 16-byte unit of a pixel is a separate cache line).  A planar tensor IS an NHWC tensor of B*C/8 images with 8 channels: the pooling kernel runs on it unchanged.
+  int pl23;
+  // ... and the pool's horizontal half is taken in conv2's epilogue (even widths): conv2 then writes the [.., h2, w2 / 2, ..] map of pixel-pair maxima
+  int hp;
+};
+Pool2Layout pool2_layout(jcm_ctx* c, const ConvLayer* L2, const ConvLayer* L3, int B, int h2, int w2);
+hipError_t pool2_launch(jcm_ctx* c, const Pool2Layout& l, const void* c2, void* p2, int B, int h2, int w2, int C);
+int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, float* logits);
+int sm_forward_impl(jcm_ctx* c, const float* hm, int Ca, const float* extra, int B, float* logits, int extra_ld = 0);
 
 }  // namespace jcm

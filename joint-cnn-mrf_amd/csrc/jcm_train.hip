@@ -171,8 +171,8 @@ static bool takes_windows(jcm_ctx* c, const ConvLayer* L, int B, int H, int W, i
   if (B > 32) return false;
   *TY = (H + kWinValid - 1) / kWinValid;
   *TX = (W + kWinValid - 1) / kWinValid;
-  ConvArgs a{};
-  a.B = B * *TY * *TX; a.H = kWin; a.W = kWin; a.Cin = L->cin; a.Cout = L->cout; a.circ = 1;
+  ConvArgs a = conv_args(L, B * *TY * *TX, kWin, kWin);
+  a.circ = 1;
   if (!conv_fft_supported(a, L->ks)) return false;
   // the data gradient runs the same windows through the flipped, transposed filter: a layer with Cin = this layer's Cout.  dz reaches it with the
   // stride of the packed data-gradient filter (Cout rounded up to 16), and the weight gradient takes the windows only for a stride that is a
@@ -201,8 +201,8 @@ int conv_train_fwd_conv(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int 
     // windows: gather -> frequency-domain layer on B TY TX windows (their spectra kept for the weight gradient) -> scatter of the valid regions
     f.win = 1; f.TY = TY; f.TX = TX;
     const int BW = B * TY * TX;
-    ConvArgs ax{};
-    ax.B = BW; ax.H = kWin; ax.W = kWin; ax.Cin = L.cin; ax.Cout = L.cout; ax.circ = 1;
+    ConvArgs ax = conv_args(&L, BW, kWin, kWin);
+    ax.circ = 1;
     f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(ax, L.ks, fft_np(c)));
     const size_t mark = c->arena_off;
     // (round 6: where the forward row pass can cut the windows out of the map itself, the gathered tensor does not exist)
@@ -216,7 +216,9 @@ int conv_train_fwd_conv(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int 
     if (gw) k.win_map = x;
     k.win_scatter = sw;
     k.xs = f.xs;
-    JCM_TRY(run_conv_fft(c, &L, f.scope, xw, BW, kWin, kWin, rw, 0, 0, 1, &k));
+    ConvCall q = conv_call(xw, rw, BW, kWin, kWin);
+    q.circ = 1; q.link = &k;
+    JCM_TRY(run_conv_fft(c, &L, f.scope, q));
     if (!c->dry) {
       f.xs_tmax = k.tmax;
       if (!sw) HIP_TRY(window_scatter_f32(rw, static_cast<float*>(f.r), B, f.H, f.W, L.cout, kWin, TY, TX, c->stream));
@@ -226,12 +228,12 @@ int conv_train_fwd_conv(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int 
   }
   FftLink k;
   if (stride == 1 && !bf(c) && takes_fft(c, &L, B, Hin, Win)) {      // keep the input spectra: the weight gradient is taken in the frequency domain too
-    ConvArgs ax{};
-    ax.B = B; ax.H = Hin; ax.W = Win; ax.Cin = L.cin; ax.Cout = L.cout;
-    f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(ax, L.ks, fft_np(c)));
+    f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(conv_args(&L, B, Hin, Win), L.ks, fft_np(c)));
     k.xs = f.xs;
   }
-  JCM_TRY(run_conv_layer(c, &L, f.scope, stride, x, B, Hin, Win, sub, f.r, bf(c), !f.L->has_bn, 0, 0, false, &k));
+  ConvCall q = conv_call(x, f.r, B, Hin, Win);
+  q.stride = stride; q.sub = sub; q.act_bf16 = bf(c); q.out_f32 = !f.L->has_bn; q.link = &k;
+  JCM_TRY(run_conv_layer(c, &L, f.scope, q));
   if (f.xs && !c->dry) f.xs_tmax = k.tmax;
   return JCM_OK;
 }
@@ -439,7 +441,9 @@ int conv_dgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int B, void* dx, i
       k.win_B = B; k.win_H = f.H; k.win_W = f.W; k.win_TY = f.TY; k.win_TX = f.TX;
       if (gw) k.win_map = dz;
       k.win_scatter = sw;
-      JCM_TRY(run_conv_fft(c, &Ld, key, zw, BW, kWin, kWin, xw, 0, 0, 1, &k));
+      ConvCall q = conv_call(zw, xw, BW, kWin, kWin);
+      q.circ = 1; q.link = &k;
+      JCM_TRY(run_conv_fft(c, &Ld, key, q));
       if (!c->dry && !sw) HIP_TRY(window_scatter_f32(xw, static_cast<float*>(dx), B, f.H, f.W, f.L->cin, kWin, f.TY, f.TX, c->stream));
       c->arena_off = mark;
       return JCM_OK;
@@ -452,7 +456,9 @@ int conv_dgrad(jcm_ctx* c, const LayerFwd& f, const void* dz, int B, void* dx, i
       FftLink k;
       if (!c->dry && t->zs && t->zs_of == dz && t->zs_cin == cin_fft) { k.xs = t->zs; k.xs_ready = true; k.tmax_in = t->zs_tmax; }      // the spectra of dz are there (conv_wgrad just made them)
       t->zs = nullptr;
-      return run_conv_fft(c, &Ld, key, dz, B, f.H, f.W, dx, 0, 0, 0, &k);
+      ConvCall q = conv_call(dz, dx, B, f.H, f.W);
+      q.link = &k;
+      return run_conv_fft(c, &Ld, key, q);
     }
     if (ldz_fft) return fail(JCM_ERR_STATE, "data gradient of '" + f.scope + "': widened dz without the frequency-domain route");
   }

@@ -141,7 +141,7 @@ struct FftMerge { const void* x2; int H2, W2; const void* x3; int H3, W3; };    
 // merged map ((x1 + up(x2)) + up(x3)) / 3.  Neither: t_next is this layer's own output (same map).
 struct FftNext { int pool = 0; int ks_next = 0; const FftMerge* merge = nullptr; };
 // Everything that ties one frequency-domain layer call to its neighbours; default-constructed = the layer stands alone.  The caller fills the input and the output
-// side, run_conv_fft (jcm_api.hip) writes the two results, and a hand-over is the caller moving the producer's (t_next, tmax_next) into the consumer's (t_in, tmax_in).
+// side, run_conv_fft (conv_route.hip) writes the two results, and a hand-over is the caller moving the producer's (t_next, tmax_next) into the consumer's (t_in, tmax_in).
 struct FftLink {
   // input side
   const void* t_in = nullptr;       // the row-transformed input left by the previous layer's fused kernel: the forward row pass is skipped

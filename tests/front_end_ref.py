@@ -1,5 +1,5 @@
 """Shapes and float64 references of the front-end tests (test_gpu_front_end.py, test_front_end_cpu.py): conv1_<res> + pool1 and, on bf16 handles,
-conv2_<res> + pool2, as the tower runs them (csrc/conv1_mfma.hip, csrc/jcm_api.hip: conv1_pool_stage, pool2_layout).  No GPU is needed here."""
+conv2_<res> + pool2, as the tower runs them (csrc/conv1_mfma.hip, csrc/pd_tower.hip: conv1_pool_stage, pool2_layout).  No GPU is needed here."""
 import functools
 
 import numpy as np
@@ -44,7 +44,7 @@ def fused_name_rule(H, W):
 
 
 def tower_takes_fused(H0, W0, sub):
-    """The tower's size condition on the image it reads at every sub-th pixel (jcm_api.hip, conv1_pool_stage)."""
+    """The tower's size condition on the image it reads at every sub-th pixel (pd_tower.hip, conv1_pool_stage)."""
     return H0 % sub == 0 and W0 % sub == 0 and (H0 // sub) % 4 == 0 and (W0 // sub) % 4 == 0
 
 

@@ -1,6 +1,6 @@
 """The first launches of every forward pass, kernel by kernel, against the float64 oracle: conv1_<res> + pool1 (at full width ONE fused MFMA kernel of
 csrc/conv1_mfma.hip per handle type, with a byte-source twin each) and, on bf16 handles, conv2_<res> + pool2 with the pool's horizontal half in conv2's
-epilogue.  Engine.conv1_pool / Engine.conv2_pool run the dispatch functions the tower itself calls (jcm_api.hip: conv1_pool_stage, pool2_layout,
+epilogue.  Engine.conv1_pool / Engine.conv2_pool run the dispatch functions the tower itself calls (pd_tower.hip: conv1_pool_stage, pool2_layout,
 pool2_launch), so what is measured here is what jcm_pd_forward launches.  Shapes and references: front_end_ref.py (checked by test_front_end_cpu.py).
 
 Bars and the worst values measured on an MI355X over every case of this file (printed by each test; relative to max|ref|):

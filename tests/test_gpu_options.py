@@ -172,3 +172,49 @@ def test_fft_reg_belongs_to_the_handle():
         print('fft_reg layer error: %.3e' % err)
         assert err <= 2e-5
     assert np.array_equal(got[0], got[2])
+
+
+def _tower_engine(precision, debug=True, **kw):
+    """A part-detector engine and one 64 x 96 image.  debug: the debug widths (16/32/64/128/128 filters), where conv4_*, conv5 and conv6 have
+    Cin % 64 == 0 and run in the frequency domain, so a forward fills the filter-spectra cache with entries of three map sizes."""
+    from joint_cnn_mrf_amd import synth
+    from joint_cnn_mrf_amd.engine import Engine
+    eng = Engine(device=0, precision=precision, **kw).load_params(synth.make_pd_params(debug=debug))
+    return eng, torch.as_tensor(synth.make_images(1, seed=31, height=64, width=96), device='cuda:0')
+
+
+def test_filter_spectra_cache_eviction_repacks_the_same_spectra():
+    """fft_cache_gb = 0: a key that is not cached drops all others (stream synchronise, free, clear) before it is packed.
+    On the engine that has run a forward with the default bound every key of this image is cached, so the bound of 0 set afterwards evicts nothing:
+    its two further forwards only hold that the option leaves cached spectra alone.  The eviction is crossed on a SECOND engine that gets the bound
+    before its first forward: the branches' layers have different map sizes, so every forward there drops, synchronises and re-packs several times
+    (after the first forward only the last key is held).  All five results are the logits under the default bound, bit for bit."""
+    eng, x = _tower_engine('fp32')
+    assert eng.conv_kernel_name('conv5', 1, 8, 12).startswith('conv_fft')
+    want = eng.model(x).clone()
+    eng.set_option('fft_cache_gb', 0)
+    for _ in range(2):
+        assert torch.equal(eng.model(x), want)
+    eng.close()
+    tight, _ = _tower_engine('fp32')
+    tight.set_option('fft_cache_gb', 0)
+    for _ in range(2):
+        assert torch.equal(tight.model(x), want)
+    tight.close()
+
+
+def test_fft_single_change_drops_the_filter_spectra():
+    """bf16 handle: the cached spectra are packed for one operand form.  set_option('fft_single', 0) behind a forward drops them, and the next forward
+    equals that of a fresh engine created with fft_single = False, bit for bit; back at 1 the first result comes again.  (The full-width tower: a
+    bf16 handle refuses the debug widths at jcm_finalize, "bf16 path needs Cin % 32 == 0" -- conv2 has Cin = 16 there.  Same image, same assertions.)"""
+    eng, x = _tower_engine('bf16', debug=False)
+    assert eng.conv_kernel_name('conv5', 1, 8, 12).startswith('conv_fft')
+    first = eng.model(x).clone()
+    eng.set_option('fft_single', 0)
+    two_parts = eng.model(x).clone()
+    fresh, _ = _tower_engine('bf16', debug=False, fft_single=False)
+    assert torch.equal(two_parts, fresh.model(x))
+    fresh.close()
+    eng.set_option('fft_single', 1)
+    assert torch.equal(eng.model(x), first)
+    eng.close()

@@ -573,6 +573,7 @@ def test_gradient_ready_callback_cannot_reenter_the_running_step(debug_case):
         for fn in (lambda: eng.model(dev(x)),
                    lambda: eng.spatial_model(torch.zeros((1, 60, 90, 10), device='cuda:0')),
                    lambda: tr.loss_and_grads(dev(x), dev(y)),
+                   lambda: eng.forward(dev(x), use_sm=False),
                    lambda: eng.update_tensor('conv6/biases', np.zeros(9, np.float32))):
             try:
                 fn()
@@ -583,7 +584,7 @@ def test_gradient_ready_callback_cannot_reenter_the_running_step(debug_case):
     tr.set_ready_hook(hook)
     tr.loss_and_grads(dev(x), dev(y))
     tr.set_ready_hook(None)
-    assert len(errors) == 4 and all(e is not None and 'gradient-ready callback' in e for e in errors), errors
+    assert len(errors) == 5 and all(e is not None and 'gradient-ready callback' in e for e in errors), errors
     assert torch.equal(tr.grads, want)
     eng.close()
 
