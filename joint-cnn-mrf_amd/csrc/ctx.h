@@ -1,6 +1,6 @@
 // Internal context of libjcm shared by the translation units behind include/jcm.h
-// (jcm_api.hip: entry points, call order, arena; conv_route.hip: how one conv layer runs; derived.hip: weight packings; pd_tower.hip: inference graph;
-// jcm_train.hip: training step).  Not part of the ABI.
+// (jcm_api.hip: entry points, parameter store, call order, arena; conv_route.hip: how one conv layer runs; derived.hip: weight packings; pd_tower.hip: inference graph;
+// jcm_train.hip: training step; train_state.hip: training state, optimizer and its entry points, both on train.h).  Not part of the ABI.
 #pragma once
 #include "../../include/jcm.h"
 
@@ -66,12 +66,14 @@ struct ConvLayer {
   float* shift = nullptr;
 };
 
-struct TrainState;   // jcm_train.hip
+struct TrainState;   // train.h
 }  // namespace jcm
 struct jcm_ctx;
 namespace jcm {
+// ---- train_state.hip: what the other files need of the training state ----
 void train_destroy(jcm_ctx* c);
-// summary.hip's view of the training state (jcm_train.hip): the stored trainable tensor that holds [off, off + n) of the
+void dgrad_filters_stale(jcm_ctx* c);      // the weights changed (jcm_train_apply, jcm_update_tensor): the packed data-gradient filters are repacked on next use
+// summary.hip's view: the stored trainable tensor that holds [off, off + n) of the
 // jcm_train_param_info layout (nullptr if none does), and the device gradient sum of squares of the last jcm_train_apply
 // (nullptr before the first one)
 const float* train_param_range(jcm_ctx* c, int64_t off, int64_t n);

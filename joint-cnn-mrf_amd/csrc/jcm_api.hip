@@ -311,6 +311,41 @@ int jcm_finalize(jcm_handle h) {
   return JCM_OK;
 }
 
+int jcm_get_tensor(jcm_handle h, const char* name, float* out, int64_t count) {
+  JCM_TRY(check(h, false));
+  if (!name || !out) return fail(JCM_ERR_ARG, "bad get_tensor arguments");
+  const Tensor* t = find(h, name);
+  if (!t) return fail(JCM_ERR_STATE, std::string("no parameter '") + name + "'");
+  if ((int64_t)t->n != count) return fail(JCM_ERR_ARG, std::string("'") + name + "' has " + std::to_string(t->n) + " elements");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  HIP_TRY(hipMemcpyAsync(out, t->d, t->n * sizeof(float), hipMemcpyDefault, h->stream));
+  order.release();
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return JCM_OK;
+}
+
+int jcm_update_tensor(jcm_handle h, const char* name, const float* data, int64_t count, int refresh) {
+  JCM_TRY(check(h, true));
+  if (!name || !data) return fail(JCM_ERR_ARG, "bad update_tensor arguments");
+  auto it = h->params.find(name);
+  if (it == h->params.end()) return fail(JCM_ERR_STATE, std::string("no parameter '") + name + "'");
+  if ((int64_t)it->second.n != count) return fail(JCM_ERR_ARG, std::string("'") + name + "' has " + std::to_string(it->second.n) + " elements");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  if (h->call_depth > 1) return fail(JCM_ERR_STATE, "jcm_update_tensor changes the handle's training state or parameters and cannot be called from the gradient-ready callback of the same handle");
+  HIP_TRY(hipMemcpyAsync(it->second.d, data, it->second.n * sizeof(float), hipMemcpyDefault, h->stream));
+  order.release();
+  const hipError_t se = hipStreamSynchronize(h->stream);   // the caller may free `data` on return
+  if (refresh) order.acquire();
+  HIP_TRY(se);
+  if (refresh) {
+    JCM_TRY(refresh_derived(h, false));
+    if (h->train) dgrad_filters_stale(h);
+  }
+  return JCM_OK;
+}
+
 int jcm_conv_layer(jcm_handle h, const char* scope, int stride, int last_layer, const float* x, int B, int H, int W, float* out) {
   JCM_TRY(check(h, true));
   if (!scope || !x || !out || B < 1 || H < 1 || W < 1) return fail(JCM_ERR_ARG, "bad conv_layer arguments");
