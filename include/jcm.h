@@ -131,7 +131,7 @@ int jcm_abi_version(void);
  *              96-point rows, at most 64 rows, at most 16 output channels) contracts the input channels and the nine vertical taps directly on the row
  *              spectra -- one fp16 matrix product per kx with K = 9 x Cin, rows outside the map read as zeros -- and runs one inverse row pass: no column
  *              passes, no padded filter spectra (58 MB of operand instead of 411 MB).  0 = conv6 as a whole frequency-domain layer.
- * "fft_reg"  : 0 = the LDS kernels instead of the register-resident transforms of csrc/conv_fft_rows_reg.hip (inverse column / row passes,
+ * "fft_reg"  : 0 = the LDS kernels instead of the register-resident transforms of csrc/conv_fft_reg_*.hip (inverse column / row passes,
  *              the bf16 forward row pass, the fused inverse + forward row pass) -- the A/B arm; results agree to fp32 rounding.
  * "fft_fuse" : (jcm_pd_forward / jcm_forward on the frequency-domain route): hand-overs in row-transformed form, ONE kernel doing the
  *              inverse row transform + bias / ReLU / BatchNorm of the producing layer, the op between the layers and the forward row transform of the

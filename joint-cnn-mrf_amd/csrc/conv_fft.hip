@@ -17,6 +17,9 @@
 //   cols_inv        (image, kx, 64 channels)         : inverse along ky, rows pad .. pad+H-1 kept -> T[b][y][kx][co]
 //   rows_inv        (image, row, 64 channels)        : Z = Y_c + i Y_{c+1} (Hermitian extension), inverse complex FFT along kx, columns
 //                                                      pad .. pad+W-1, 1/(NY NX), bias, ReLU, folded BatchNorm -> NHWC fp32 / bf16 / planar
+// Every transform pass is an LDS kernel for any size with a Plan (conv_fft_rows_fwd.hip, conv_fft_cols.hip, conv_fft_rows_inv.hip; the fused
+// hand-overs between two layers: conv_fft_rows_fused.hip) and, at the model's sizes, a kernel with the transform in registers, taken where it
+// exists (fft_reg_rows.h: conv_fft_reg_fwd.hip, conv_fft_reg_inv.hip -- rows and columns --, conv_fft_reg_fused.hip, conv_fft_reg_tiles.hip).
 // The filter spectra (flipped kernel: TF's conv2d is a correlation) are computed once per (layer, map size) at first use, split into the
 // same bf16 parts, in the GEMM's tile-major layout.  FFTs: the in-LDS decimation-in-frequency stages of sm_fused.hip, channel-vectorised
 // (consecutive lanes = consecutive channels).  Twiddles come from one table per device, built on the host in double precision.

@@ -1,5 +1,6 @@
 // Shared by the translation units of the frequency-domain convolution (conv_fft.hip: host side + filter spectra; conv_fft_rows_fwd.hip,
-// conv_fft_rows_inv.hip, conv_fft_cols.hip: the transform kernels, one file per pass so that they compile in parallel): radix plans,
+// conv_fft_rows_inv.hip, conv_fft_rows_fused.hip, conv_fft_cols.hip: the LDS transform kernels; conv_fft_reg_inv.hip, conv_fft_reg_fwd.hip,
+// conv_fft_reg_fused.hip, conv_fft_reg_tiles.hip: the register ones (fft_reg_rows.h) -- one file per pass so that they compile in parallel): radix plans,
 // the channel-vectorised in-LDS FFT stages, the bf16 operand split, and the size-dispatching launchers each file exports.
 #pragma once
 #include "fft_lds.h"
@@ -108,11 +109,15 @@ __device__ __forceinline__ cf unpack_h2_mix_v(unsigned u, float s) {
   asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r.y) : "v"(u), "v"(s));
   return r;
 }
+__device__ __forceinline__ float wave_max(float m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  return m;
+}
 // the work group's maximum, known to every thread (one barrier; red[] must not be in use by a stash of the same tile)
 template <int NTH>
 __device__ __forceinline__ float block_max_all(float m, float* red, int tid) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = wave_max(m);
   if ((tid & 63) == 0) red[tid >> 6] = m;
   __syncthreads();
   float r = red[0];
@@ -201,8 +206,7 @@ __device__ __forceinline__ float tmax_of(const float* __restrict__ tmax, int b, 
 // thread folds them and issues ONE atomic max on the image's device word (values are >= 0: their bit patterns order like unsigned integers).
 // The atomic returns nothing, so nobody waits for it; red[] is next written a whole tile (several barriers) later.
 __device__ __forceinline__ void wave_max_stash(float m, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
 }
 template <int NTH>
@@ -217,8 +221,7 @@ __device__ __forceinline__ void stash_to_word(const float* red, float* dst) {
 // the work group's maximum -> the device word
 template <int NTH>
 __device__ __forceinline__ void block_max_to(float m, float* dst, float* red, int tid) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = wave_max(m);
   if ((tid & 63) == 0) red[tid >> 6] = m;
   __syncthreads();
   if (tid == 0) {
@@ -309,14 +312,14 @@ hipError_t cfft_cols_fwd(int NY, const ConvArgs& a, int np, const cf* T, void* X
 // y16_inv (with t16 only): Yf holds complex fp16 products times a power of two (cgemm_split.hip); y16_inv = its inverse.  0: complex fp32
 void cfft_cols_inv(int NY, const ConvArgs& a, const cf* Yf, cf* T, const cf* tw, int NXH, int ldy, int pad, hipStream_t st, float* t16 = nullptr, float y16_inv = 0.f);
 void cfft_rows_inv(int NX, const ConvArgs& a, int layout, const cf* T, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
-// the same pass with the transform in the registers of two threads per channel pair (conv_fft_rows_reg.hip); false: no such kernel for this case
+// the same pass with the transform in the registers of two threads per channel pair (conv_fft_reg_*.hip, fft_reg_rows.h); false: no such kernel for this case
 bool cfft_rows_inv_reg(int NX, const ConvArgs& a, int layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
 bool cfft_rows_inv_fwd_reg(int NX, const ConvArgs& a, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
 bool cfft_rows_fwd_reg(int NX, const ConvArgs& a, int layout, cf* T, float* tmax, hipStream_t st, float* t16);
 // 32 x 32 overlap-save windows read straight from the map they are cut from (a.win_map, fp32 NHWC; Cin % 128 == 0): false = no such kernel
 bool cfft_rows_fwd_win_reg(int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st);
 bool cfft_rows_fwd_win_reg_supported(int NX, int Cin);
-// 2 x 2 tiles of a 5x5 layer's map (ConvArgs::tiles, conv_fft_rows_reg.hip): NY x NX = the tiles' transform; a = the layer on the whole map
+// 2 x 2 tiles of a 5x5 layer's map (ConvArgs::tiles, conv_fft_reg_tiles.hip): NY x NX = the tiles' transform; a = the layer on the whole map
 bool cfft_tiles_supported(int NY, int NX, const ConvArgs& a);
 bool cfft_rows_fwd_tile_reg(int NY, int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st);
 bool cfft_rows_inv_pool_tile_reg(int NY, int NX, const ConvArgs& a, const cf* T, cf* Tn, float norm, const Fp16Scale& sc, hipStream_t st);
@@ -327,7 +330,7 @@ void cfft_rows_inv_fwd(int NX, const ConvArgs& a, const cf* T, cf* Tn, const cf*
 // false: no kernel for this case
 bool cfft_rows_inv_pool_fwd(int NXI, int NXO, const ConvArgs& a, const cf* T, cf* Tn, const cf* twi, const cf* two, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
 bool cfft_rows_inv_merge_fwd(int NX, const ConvArgs& a, const FftMerge& m, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
-// conv_fft_rows_reg.hip: the model's geometry in registers; t16n != null: bf16 handles (16-bit T' in, 16-bit T + its scale words t16n out, bf16 coarse branches)
+// conv_fft_reg_fused.hip: the model's geometry in registers; t16n != null: bf16 handles (16-bit T' in, 16-bit T + its scale words t16n out, bf16 coarse branches)
 bool cfft_rows_inv_merge_fwd_reg(int NX, const ConvArgs& a, const FftMerge& m, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st, float* t16n = nullptr);
 bool cfft_rows_inv_merge_fwd_reg_supported(int NX, const ConvArgs& a, const FftMerge& m, int pad);
 bool cfft_rows_inv_pool_fwd_supported(int NXI, int NXO, int Cout);

@@ -1,7 +1,7 @@
 // Row passes of the frequency-domain convolution of a bf16 handle (16-bit row-transformed tensors, np = 5) with the 96-point transform as a
 // MATRIX PRODUCT on the matrix cores.
 //
-// The register kernels (conv_fft_rows_reg.hip) are bound by their vector-ALU issue slots on these handles (round 6, SQ_INSTS_VALU x 4 cycles = 85 % of the
+// The register kernels (conv_fft_reg_inv.hip) are bound by their vector-ALU issue slots on these handles (round 6, SQ_INSTS_VALU x 4 cycles = 85 % of the
 // kernel time at 2.3-3.6 TB/s; the library runs without packed fp32 arithmetic, fft_lds.h): a 96-point transform is ~1000 scalar fp32 instructions per
 // row and channel.  A real 96-point inverse transform of a Hermitian half spectrum is also the product of a constant 96 x 98 matrix with the row's 49
 // complex entries, and the data of these handles is 16-bit already: T' is complex fp16 (11 significant bits).  v_mfma_f32_32x32x16_f16 multiplies it by
@@ -143,8 +143,7 @@ __global__ __launch_bounds__(256, 2) void rows_inv_mfma_kernel(const unsigned* _
       if (sc.common) {
         tm = 0.f;
         for (int i = lane; i < sc.nb; i += 64) tm = fmaxf(tm, sc.tmax[i]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tm = fmaxf(tm, __shfl_xor(tm, o));
+        tm = wave_max(tm);
       } else {
         tm = sc.tmax[b];
       }

@@ -199,7 +199,7 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   const size_t mark = c->arena_off;
   const int np = fft_np(c);      // operand form of the channel GEMM (cgemm_split.hip)
   // fp32 handles, the pool hand-over conv2 -> pool -> conv3 on the model's 120 x 180 map: the layer runs as 2 x 2 tiles in the 64 x 96 transform of the
-  // 60 x 90 maps (ConvArgs::tiles, conv_fft_rows_reg.hip) -- a quarter of the filter spectra, and the register row kernels
+  // 60 x 90 maps (ConvArgs::tiles, conv_fft_reg_tiles.hip) -- a quarter of the filter spectra, and the register row kernels
   a.tiles = c->fft_tiles && k.next.pool && !k.t_in && !k.xs && !k.merge && !k.win_map && !circ && in_layout == 0 &&
             np == 4 && conv_fft_tiles_supported(a, L->ks, k.next.ks_next) ? 1 : 0;
   const int wH = a.tiles ? H / 2 : H, wW = a.tiles ? W / 2 : W;      // the map size the filter spectra are for

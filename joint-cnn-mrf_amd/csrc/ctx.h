@@ -98,7 +98,7 @@ struct jcm_ctx {
   int fft_single = 1;           // bf16 handles: the channel GEMM on ONE scaled fp16 part per operand (np = 5; 0 = two bf16 parts, three products)
   int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)
   int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (ConvArgs::rows_mfma; conv_fft_rows_mfma.hip)
-  int fft_reg = 1;              // the register-resident transform kernels of conv_fft_rows_reg.hip where they exist (ConvArgs::fft_reg); 0 = the LDS kernels for every pass
+  int fft_reg = 1;              // the register-resident transform kernels of conv_fft_reg_*.hip where they exist (ConvArgs::fft_reg); 0 = the LDS kernels for every pass
   int fft_cache_gb = 64;        // bound of the filter-spectra cache (conv_route.hip: a new entry that would grow it past the bound drops the others first)
   int fft_win = 1;              // training step of fp32 handles: frequency-domain layers on 32 x 32 overlap-save windows where that shrinks the filter-sized spectra (jcm_train.hip)
   int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel

@@ -1,4 +1,4 @@
-// FFTs held entirely in the registers of ONE thread (conv_fft_rows_reg.hip): every index is a compile-time constant, so there is no LDS
+// FFTs held entirely in the registers of ONE thread (the kernels of conv_fft_reg_*.hip, fft_reg_rows.h): every index is a compile-time constant, so there is no LDS
 // round trip, no barrier, no index arithmetic and no twiddle load -- the instruction stream of a transform is its butterflies.  (The LDS kernels
 // of conv_fft_common.h spend 70-80 % of their instructions around the butterflies and run at 2-3 work groups per CU)
 //   N = R1 * R2, n = R2 n1 + n2, k = k1 + R1 k2:   X[k] = sum_n2 w_N^(S n2 k1) [sum_n1 x[R2 n1 + n2] w_R1^(S n1 k1)] w_R2^(S n2 k2)

@@ -66,7 +66,7 @@ struct ConvArgs {
   // conv_fft, bf16 handles with 16-bit row-transformed tensors: the 96-point inverse row pass with planar bf16 output (conv5 of the model) as a matrix product
   // on the matrix cores (conv_fft_rows_mfma.hip).  1 = on where the kernel exists, 0 = the register kernel.
   int rows_mfma = 0;
-  // conv_fft: the register-resident transform kernels (conv_fft_rows_reg.hip) where they exist; 0 = the LDS kernels for every pass, their A/B arm (option "fft_reg")
+  // conv_fft: the register-resident transform kernels (conv_fft_reg_*.hip) where they exist; 0 = the LDS kernels for every pass, their A/B arm (option "fft_reg")
   int fft_reg = 1;
   // conv5_strip_bf16 only: the LEFT HALF of the 2x2/2 max pool that follows the layer in its epilogue -- `out` is the [B, H, W / 2, Cout] map of
   // max(pixel 2 i, pixel 2 i + 1) (W even; either activation layout), half the bytes; vpool_2x1() finishes the pool.  The max of two bf16-rounded values is

@@ -421,7 +421,7 @@ def test_two_processes_one_gpu_soak(precision):
 
 def test_lds_transform_kernels_arm():
     """JCM_FFT_REG=0 (read once per process) sends the inverse passes of the 64 x 96 transforms through the LDS kernels instead of the register-resident
-    transforms (csrc/conv_fft_rows_reg.hip).  Both arms compute the same transform up to the association order of the butterflies: the full-size fp32 tower
+    transforms (csrc/conv_fft_reg_*.hip).  Both arms compute the same transform up to the association order of the butterflies: the full-size fp32 tower
     against the float64 goldens and the bf16 tower against the bf16-operand oracle are run again in a process with the switch set."""
     import subprocess
     import sys
