@@ -67,7 +67,7 @@ int jcm_abi_version(void);
  *   "fft_t16"          1        bool      any       -                    bf16 handles, "fft_single" = 1: 16-bit row-transformed tensors and product spectra
  *   "fft_rows_mfma"    1        bool      any       -                    bf16 handles, 16-bit tensors: conv5's inverse row pass on the matrix cores
  *   "fft_windows"      1        bool      any       -                    fp32 training step: wide layers on 32 x 32 overlap-save windows
- *   "fft_fuse"         3        0..3      any       -                    hand-overs in row-transformed form: bit 0 = across the max pool, bit 1 = across the branch merge
+ *   "fft_fuse"         7        0..7      any       -                    bit 0 / 1 = hand-overs in row-transformed form across the max pool / the branch merge; bit 2 = coarse branches on a side stream
  *   "fft_tiles"        1        bool      any       JCM_FFT_TILES        fp32 handles: conv2_fullres -> pool -> conv3 as 2 x 2 tiles of the 120 x 180 map
  *   "fft_logits_rows"  1        bool      any       JCM_FFT_LOGITS_ROWS  fp32 handles: the logits layer contracts the channels on conv5's row spectra
  *   "fft_reg"          1        bool      any       JCM_FFT_REG          register-resident transform kernels where they exist (0 = the LDS kernels: A/B arm)
@@ -143,7 +143,15 @@ int jcm_abi_version(void);
  *              evaluates the separate kernels' expressions; the merge hand-over lerps the coarse branches along y first, then along x (TF lerps x
  *              first: the last fp32 bit of the coarse terms, as the register merge of bf16 handles has done since round 5), third = correctly rounded
  *              x / 3 on fp32 handles, one multiplication by RN(1/3) on bf16 handles (against the quotient: the bf16 rounding of two merged values in a
- *              million).  0 = the separate kernels of round 5 (A/B arm; held by the same tests).
+ *              million).  Bits 0 and 1 clear = the separate kernels of round 5 (A/B arm; held by the same tests).
+ *              bit 2 (both precisions) = the half- and quarter-resolution branches are enqueued on a second stream of the handle (non-blocking, created at
+ *              first use) and run BESIDE the full-resolution branch: the side stream waits for an event recorded at entry, and the handle's stream waits for the
+ *              side stream in front of the first kernel that reads x2 / x3 (conv4_fullres with bit 1, else the merge).  The coarse branches' workspace,
+ *              activations, scale words and x2 / x3 live in allocations of their own (counted by jcm_workspace_bytes), because two kernels that run at the same
+ *              time must not share cache lines.  Same kernels, same arguments: results are bit-identical to bit 2 clear (tests/test_gpu_branch_streams.py).
+ *              The per-layer times of "profile" then overlap and no longer add up to the step.  Same-box A/B at 64 images, three interleaved rounds: fp32 8.76-8.78 -> 8.20-8.39 ms per step (1.57 ms of
+ *              coarse kernels run inside the full-resolution branch's first 2.08 ms, which stretch to 3.23 ms: both sides draw on the same HBM), bf16 at
+ *              256 images 17.26-17.34 -> 17.15-17.22 ms (profiles/r10_ab_branch_streams.log, profiles/r10_branch_streams_timeline.md).
  * "fft_rows_mfma" : (bf16 handles on the one-part route with 16-bit row-transformed tensors): conv5's 96-point inverse row pass as a MATRIX
  *              PRODUCT on the matrix cores (rows_inv_mfma_kernel, conv_fft_rows_mfma.hip): T' (complex fp16) times the 96 x 98 real inverse-transform
  *              matrix held as two fp16 parts (22 significant bits: as exact as the fp32 butterflies), bias / ReLU / BatchNorm on the accumulators, planar

@@ -139,7 +139,7 @@ static int fft_cache_get(jcm_ctx* c, const std::string& scope, const std::string
     size_t held = 0;
     for (auto& kv : c->fft_w) held += kv.second.bytes;
     if (held + wbytes > cap && !c->fft_w.empty()) {
-      HIP_TRY(hipStreamSynchronize(c->stream));            // earlier layers of this forward may still read theirs
+      JCM_TRY(sync_streams(c));            // earlier layers of this forward may still read theirs, on either stream
       fft_cache_drop(c);
     }
   }

@@ -94,7 +94,7 @@ struct jcm_ctx {
   int conv9_fft = 1;            // fp32 handles: wide 9x9 layers in the frequency domain (conv_fft.hip) when the shape allows; 0 = fp32 MFMA chain
   int fft_tiles = 1;            // fp32 handles, the pool hand-over of conv2_fullres: 2 x 2 tiles of the 120 x 180 map in the 60 x 90 maps' transform (ConvArgs::tiles)
   int fft_logits_rows = 1;      // fp32 handles without training state: the logits layer behind conv5's hand-over contracts the channels on the row spectra (conv_fft_logits.hip); 0 = a whole frequency-domain layer
-  int fft_fuse = 3;             // fp32 handles, jcm_pd_forward: bit 0 = conv2 -> max pool -> conv3, bit 1 = conv4_fullres -> branch merge -> conv5 handed over in row-transformed form (conv_fft_rows_fused.hip)
+  int fft_fuse = 7;             // jcm_pd_forward: bit 0 = conv2 -> max pool -> conv3 (fp32 handles), bit 1 = conv4_fullres -> branch merge -> conv5 handed over in row-transformed form (conv_fft_rows_fused.hip); bit 2 = the coarse branches on the side stream (Side, SideBranches)
   int fft_single = 1;           // bf16 handles: the channel GEMM on ONE scaled fp16 part per operand (np = 5; 0 = two bf16 parts, three products)
   int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)
   int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (ConvArgs::rows_mfma; conv_fft_rows_mfma.hip)
@@ -141,6 +141,23 @@ struct jcm_ctx {
   struct WordBlock { float* p = nullptr; int cap = 0; };
   std::vector<WordBlock> fft_blocks;
   int fft_block_i = 0, fft_word_i = 0;      // next free word: fft_blocks[fft_block_i].p + fft_word_i
+  // ---- the side stream ("fft_fuse" bit 2; pd_tower.hip: SideBranches) ----
+  // jcm_pd_forward runs the half- and quarter-resolution branches beside the full-resolution one.  A kernel that touches lines another stream is producing
+  // leaves stale copies in its XCD's L2 (CallOrder, below), and arena alignment does not protect against a look-ahead read past the end of a buffer: so
+  // everything the side stream writes while the main stream runs -- workspace, activations, x2 / x3, scale words, the split kernels' input scale -- lives in
+  // allocations of its own.  Created at first use (side_init), freed by jcm_destroy.  SideBranches SWAPS these fields with their namesakes above for as long
+  // as it enqueues the coarse branches, so every launch site keeps reading c->stream and c->arena: outside of that scope this struct holds the side set,
+  // inside of it the main one.
+  struct Side {
+    hipStream_t stream = nullptr;             // hipStreamNonBlocking: the handle's own stream may be the legacy null stream, which blocking streams serialise against
+    hipEvent_t fork = nullptr, join = nullptr;      // hipEventDisableTiming
+    char* arena = nullptr;                    // sized by the dry pass that sizes the main arena (with_arena)
+    size_t arena_cap = 0, arena_off = 0, arena_peak = 0;
+    std::vector<WordBlock> fft_blocks;        // re-zeroed where the main ones are (CallOrder): on the main stream, in front of the fork
+    int fft_block_i = 0, fft_word_i = 0;
+    float* act_scale = nullptr;
+    float* scale_scratch = nullptr;
+  } side;
   // per-layer HIP-event timing on the launch stream (bench.py roofline object)
   int profile = 0;              // option "profile"
   std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
@@ -200,7 +217,9 @@ T* arena_alloc(jcm_ctx* c, size_t count) {
   return reinterpret_cast<T*>(c->arena + off);   // in a dry pass arena may be null: offsets only
 }
 
-int arena_reserve(jcm_ctx* c, size_t bytes);
+int arena_reserve(jcm_ctx* c, size_t bytes, size_t side_bytes);      // both arenas; growing either synchronises both streams first
+int side_init(jcm_ctx* c);                  // the side stream, its events and its scale buffer (first use)
+int sync_streams(jcm_ctx* c);               // the handle's stream and the side stream
 int dev_alloc(jcm_ctx* c, void** p, size_t bytes);
 int sm_scratch_next(jcm_ctx* c, void** scratch, unsigned* epoch);      // sm_fused_forward's scratch (allocated + zeroed at first use) and the next launch epoch
 const Tensor* find(jcm_ctx* c, const std::string& name);
@@ -276,10 +295,11 @@ int with_arena(jcm_ctx* c, S&& sizing, R&& real) {
   c->dry = true;
   c->arena_off = 0;
   c->arena_peak = 0;
+  c->side.arena_peak = 0;
   int r = sizing();
   c->dry = false;
   if (r != JCM_OK) return r;
-  JCM_TRY(arena_reserve(c, c->arena_peak));
+  JCM_TRY(arena_reserve(c, c->arena_peak, c->side.arena_peak));
   c->arena_off = 0;
   return real();
 }

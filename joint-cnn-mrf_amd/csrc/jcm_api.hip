@@ -50,12 +50,17 @@ CallOrder::CallOrder(jcm_ctx* ctx) : c(ctx) {
   if (nested) return;                // the outer call's scale words stay as they are
   c->order = this;
   // the fp16-scale words are reused from the start only BETWEEN calls (a call keeps words of its early layers until its last ones: the training step)
-  if (c->fft_block_i > 0 || c->fft_word_i > jcm_ctx::kFftWords - jcm_ctx::kFftWordsPerCall) {
-    for (int i = 0; i <= c->fft_block_i && i < (int)c->fft_blocks.size(); ++i)
-      (void)hipMemsetAsync(c->fft_blocks[i].p, 0, (size_t)c->fft_blocks[i].cap * sizeof(float), c->stream);
-    c->fft_block_i = 0;
-    c->fft_word_i = 0;
-  }
+  // (the side stream's words too, on THIS stream: every call has joined its side work before it ended, and the next fork is behind the memset)
+  auto lap = [&](std::vector<jcm_ctx::WordBlock>& blocks, int& block_i, int& word_i) {
+    if (block_i > 0 || word_i > jcm_ctx::kFftWords - jcm_ctx::kFftWordsPerCall) {
+      for (int i = 0; i <= block_i && i < (int)blocks.size(); ++i)
+        (void)hipMemsetAsync(blocks[i].p, 0, (size_t)blocks[i].cap * sizeof(float), c->stream);
+      block_i = 0;
+      word_i = 0;
+    }
+  };
+  lap(c->fft_blocks, c->fft_block_i, c->fft_word_i);
+  lap(c->side.fft_blocks, c->side.fft_block_i, c->side.fft_word_i);
 }
 void CallOrder::acquire() {
   if (!c || lk.owns_lock()) return;
@@ -86,14 +91,37 @@ CallOrder::~CallOrder() {
   }
 }
 
-int arena_reserve(jcm_ctx* c, size_t bytes) {
-  if (bytes <= c->arena_cap) return JCM_OK;
+int sync_streams(jcm_ctx* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->arena) HIP_TRY(hipFree(c->arena));
-  c->arena = nullptr;
-  c->arena_cap = 0;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->arena), bytes));
-  c->arena_cap = bytes;
+  if (c->side.stream) HIP_TRY(hipStreamSynchronize(c->side.stream));
+  return JCM_OK;
+}
+
+int arena_reserve(jcm_ctx* c, size_t bytes, size_t side_bytes) {
+  if (bytes <= c->arena_cap && side_bytes <= c->side.arena_cap) return JCM_OK;
+  JCM_TRY(sync_streams(c));
+  auto grow = [](char*& arena, size_t& cap, size_t want) {
+    if (want <= cap) return (int)JCM_OK;
+    if (arena) HIP_TRY(hipFree(arena));
+    arena = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&arena), want));
+    cap = want;
+    return (int)JCM_OK;
+  };
+  JCM_TRY(grow(c->arena, c->arena_cap, bytes));
+  return grow(c->side.arena, c->side.arena_cap, side_bytes);
+}
+
+int side_init(jcm_ctx* c) {
+  jcm_ctx::Side& s = c->side;
+  if (!s.stream) HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  if (!s.fork) HIP_TRY(hipEventCreateWithFlags(&s.fork, hipEventDisableTiming));
+  if (!s.join) HIP_TRY(hipEventCreateWithFlags(&s.join, hipEventDisableTiming));
+  if (!s.scale_scratch) {      // (the sizes of derived.hip's weight_scale, in one allocation)
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.scale_scratch), (1024 + 64) * sizeof(float)));
+    s.act_scale = s.scale_scratch + 1024;
+  }
   return JCM_OK;
 }
 
@@ -246,7 +274,7 @@ int jcm_create(int device, void* stream, jcm_handle* out) {
 int jcm_destroy(jcm_handle h) {
   if (!h) return JCM_OK;
   DeviceGuard g(h->device);
-  (void)hipStreamSynchronize(h->stream);
+  (void)sync_streams(h);
   prof_release_all(h, true);
   if (h->train) train_destroy(h);
   for (auto& kv : h->params) (void)hipFree(kv.second.d);
@@ -254,6 +282,12 @@ int jcm_destroy(jcm_handle h) {
   fft_cache_drop(h);
   for (auto& b : h->fft_blocks) (void)hipFree(b.p);
   if (h->arena) (void)hipFree(h->arena);
+  for (auto& b : h->side.fft_blocks) (void)hipFree(b.p);
+  if (h->side.arena) (void)hipFree(h->side.arena);
+  if (h->side.scale_scratch) (void)hipFree(h->side.scale_scratch);
+  if (h->side.fork) (void)hipEventDestroy(h->side.fork);
+  if (h->side.join) (void)hipEventDestroy(h->side.join);
+  if (h->side.stream) (void)hipStreamDestroy(h->side.stream);
   delete h;
   return JCM_OK;
 }
@@ -857,6 +891,6 @@ int jcm_conv_kernel_name(jcm_handle h, const char* scope, int B, int H, int W, c
   return JCM_OK;
 }
 
-int64_t jcm_workspace_bytes(jcm_handle h) { return h ? (int64_t)(h->arena_cap + h->param_bytes) : 0; }
+int64_t jcm_workspace_bytes(jcm_handle h) { return h ? (int64_t)(h->arena_cap + h->side.arena_cap + h->param_bytes) : 0; }
 
 }  // extern "C"

@@ -35,7 +35,7 @@ inline constexpr Option kOptions[] = {
     {"fft_t16",         &jcm_ctx::fft_t16,         Option::BOOL,   0,  1,       false, nullptr,               nullptr},
     {"fft_rows_mfma",   &jcm_ctx::fft_rows_mfma,   Option::BOOL,   0,  1,       false, nullptr,               nullptr},
     {"fft_windows",     &jcm_ctx::fft_win,         Option::BOOL,   0,  1,       false, nullptr,               nullptr},
-    {"fft_fuse",        &jcm_ctx::fft_fuse,        Option::RANGE,  0,  3,       false, nullptr,               nullptr},
+    {"fft_fuse",        &jcm_ctx::fft_fuse,        Option::RANGE,  0,  7,       false, nullptr,               nullptr},
     {"fft_tiles",       &jcm_ctx::fft_tiles,       Option::BOOL,   0,  1,       false, "JCM_FFT_TILES",       nullptr},
     {"fft_logits_rows", &jcm_ctx::fft_logits_rows, Option::BOOL,   0,  1,       false, "JCM_FFT_LOGITS_ROWS", nullptr},
     {"fft_reg",         &jcm_ctx::fft_reg,         Option::BOOL,   0,  1,       false, "JCM_FFT_REG",         nullptr},

@@ -1,6 +1,7 @@
 // The part-detector tower (main.py:29-74) and the spatial model (main.py:94-125) as sequences of launches on the handle's stream, and the
 // front-end stages the tower shares with jcm_conv1_pool / jcm_conv2_pool.  Host code only.
 #include <string>
+#include <utility>
 
 #include "ctx.h"
 
@@ -87,6 +88,64 @@ static void* offer_pool_handover(jcm_ctx* c, const ConvLayer* La, const ConvLaye
 }
 // the producer has run: its t_next and the words run_conv_fft gave it are the consumer's input
 static void hand_over(const FftLink& from, FftLink& to) { to.t_in = from.t_next; to.tmax_in = from.tmax_next; }
+// The half- and quarter-resolution branches on the handle's side stream ("fft_fuse" bit 2; jcm_ctx::Side says why everything they write has allocations of its
+// own).  fork(): the side stream waits for what the main stream holds so far.  enter() .. leave(): the handle's current stream, arena, scale words and input-scale
+// buffer ARE the side ones, so run_conv, conv1_pool_stage, the pool launches, the profiling events, fft_new_words and first-use filter-spectra packing go there
+// without knowing; leave() records the join event.  join(): the main stream waits for it -- in front of the first launch that reads x2 / x3.  The destructor
+// leaves and joins on every path out, error returns included: no caller buffer, arena region or CallOrder chain event is released while side work is in flight.
+// Off (bit 2 clear) or in a dry pass nothing is recorded; a dry pass still swaps, so that the side arena gets its own peak.
+struct SideBranches {
+  jcm_ctx* c;
+  bool on, inside = false, forked = false, fresh = true;
+  SideBranches(jcm_ctx* ctx, bool use) : c(ctx), on(use) {}
+  SideBranches(const SideBranches&) = delete;
+  SideBranches& operator=(const SideBranches&) = delete;
+  void swap() {
+    jcm_ctx::Side& s = c->side;
+    std::swap(c->stream, s.stream);
+    std::swap(c->arena, s.arena);
+    std::swap(c->arena_cap, s.arena_cap);
+    std::swap(c->arena_off, s.arena_off);
+    std::swap(c->arena_peak, s.arena_peak);
+    std::swap(c->fft_blocks, s.fft_blocks);
+    std::swap(c->fft_block_i, s.fft_block_i);
+    std::swap(c->fft_word_i, s.fft_word_i);
+    std::swap(c->act_scale, s.act_scale);
+    std::swap(c->scale_scratch, s.scale_scratch);
+  }
+  int fork() {
+    if (!on) return JCM_OK;
+    JCM_TRY(side_init(c));
+    if (c->dry) return JCM_OK;
+    HIP_TRY(hipEventRecord(c->side.fork, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->side.stream, c->side.fork, 0));
+    forked = true;
+    return JCM_OK;
+  }
+  void enter() {
+    if (!on || inside) return;
+    swap();
+    if (fresh) c->arena_off = 0;      // the side arena starts over with every pass (the previous pass's side work is in front of this pass's fork)
+    fresh = false;
+    inside = true;
+  }
+  hipError_t leave() {
+    if (!inside) return hipSuccess;
+    swap();
+    inside = false;
+    return forked ? hipEventRecord(c->side.join, c->side.stream) : hipSuccess;
+  }
+  int join() {
+    const hipError_t e = leave();
+    if (!forked) return JCM_OK;
+    forked = false;
+    // (a join event that could not be recorded: the host waits instead)
+    if (e != hipSuccess || hipStreamWaitEvent(c->stream, c->side.join, 0) != hipSuccess) HIP_TRY(hipStreamSynchronize(c->side.stream));
+    return JCM_OK;
+  }
+  ~SideBranches() { (void)join(); }
+};
+
 // model(x, n_joints), main.py:29-74.  x fp32 NHWC, or (x_u8) a byte image whose values k stand for float32(k) / float32(255): only the conv1 kernels
 // read it, and their byte-source variants convert at the load (u8.h).  Intermediate activations fp32 or bf16.
 
@@ -117,18 +176,21 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
     const ConvArgs a = conv_args(L4, B, hh, ww);
     fuse45 = (c->fft_fuse & 2) && conv_fft_merge_fusable(a, L4->ks, L5->ks, mg, c->fft_reg, h16);
   }
-  // branch outputs survive the per-branch scratch, so carve them first
+  // branch outputs survive the per-branch scratch, so carve them first: x1 (or conv5's row-transformed input) from the arena, x2 / x3 from the arena of the
+  // stream their branches run on
   void* t45 = nullptr;
   FftLink k5, k6;      // conv5 -> conv6
-  for (int r = 0; r < 3; ++r) {
-    if (r == 0 && fuse45) {
-      const ConvArgs a = conv_args(L4, B, hh, ww);
-      t45 = arena_alloc<char>(c, conv_fft_handover_bytes(a, L4->ks));
-      x4[0] = nullptr;
-    } else {
-      x4[r] = act((size_t)B * h4[r] * w4[r] * L4->cout);
-    }
+  if (fuse45) {
+    const ConvArgs a = conv_args(L4, B, hh, ww);
+    t45 = arena_alloc<char>(c, conv_fft_handover_bytes(a, L4->ks));
+    x4[0] = nullptr;
+  } else {
+    x4[0] = act((size_t)B * h4[0] * w4[0] * L4->cout);
   }
+  SideBranches side(c, (c->fft_fuse & 4) != 0);
+  side.enter();
+  for (int r = 1; r < 3; ++r) x4[r] = act((size_t)B * h4[r] * w4[r] * L4->cout);
+  (void)side.leave();      // (nothing is forked yet: only the arenas changed places)
   mg.x2 = x4[1]; mg.x3 = x4[2];
   // bf16: the 9x9 chain (conv3 out -> conv4 -> merge -> conv5 -> conv6 in) runs on planar activations [B][C/8][H*W][8]
   // when conv5 takes the strip kernel; every producer / consumer on that chain handles the layout.
@@ -145,9 +207,12 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
     if (!c->dry) HIP_TRY(u8_to_f32_array(static_cast<const uint8_t*>(x), xw32, (size_t)B * H * W * 3, c->stream));
     x_wide = xw32;
   }
+  JCM_TRY(side.fork());      // behind the widened byte batch, which both streams only read
   static const int kOrder[3] = {1, 2, 0};
   for (int ri = 0; ri < 3; ++ri) {
     const int r = kOrder[ri];
+    if (r == 0) HIP_TRY(side.leave());
+    else side.enter();
     const size_t mark = c->arena_off;
     const std::string res = kRes[r];
     const int sub = 1 << r;
@@ -195,6 +260,7 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
     if (r == 0 && fuse45) { k4.t_next = t45; k4.next.merge = &mg; }      // conv4_fullres writes conv5's row-transformed (merged) input
     ConvCall q4 = conv_call(c3, x4[r], B, h3, w3);
     q4.act_bf16 = bf; q4.in_planar = in4; q4.out_planar = planar45; q4.link = &k4;
+    if (r == 0 && fuse45) JCM_TRY(side.join());      // its fused inverse row kernel reads x2 / x3
     if (!(sk & 16)) JCM_TRY(run_conv(c, "conv4_" + res, q4));   // :49,57,66
     if (r == 0 && fuse45) { hand_over(k4, k5); k5.t_in_16 = h16; }
     c->arena_off = mark;
@@ -205,6 +271,7 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
   // (Round 5 measured the alternative for bf16 handles -- the merge as its own bandwidth-bound kernel + conv5's register row pass: 20.45 against
   // 20.11 ms per 256-image step with the fused kernel, three interleaved runs each: writing and re-reading the 1.4 GB merged tensor costs more
   // than the fused kernel's slower rows.)
+  JCM_TRY(side.join());      // the merge kernel, or conv5's forward row kernel, reads x2 / x3
   const bool fuse_merge = !fuse45 && takes_fft(c, L5, B, hh, ww) && !planar45;
   void* merged = fuse45 ? nullptr : fuse_merge ? x4[0] : act((size_t)B * hh * ww * L4->cout);
   if (!c->dry && !fuse45 && !fuse_merge && !(c->debug_skip & 32)) {                        // :58,67,69-70
