@@ -26,10 +26,12 @@ def cases():
     # rows per wave, three row parts (W > 128), one (W < 64); 15x23 is too narrow for its 64-entry window table -> patch kernel
     out += [(16, 2, 60, 90, 128, 128, 5), (17, 1, 120, 180, 64, 128, 5), (18, 3, 30, 45, 64, 128, 5), (19, 2, 15, 23, 128, 128, 5),
             (20, 5, 17, 29, 32, 128, 5), (21, 1, 9, 128, 96, 128, 5)]
-    # conv_fft (fp32, wide 9x9 layers in the frequency domain): the model's three map sizes (72x100, 40x60, 24x32 transforms) and a map
-    # that fills its 72x100 transform to the last row and column
+    # conv_fft (fp32; bf16: the wide 9x9 layers), transforms of (H + 4) x (W + 4) rounded up to a supported length: the model's three map sizes
+    # (22: 64x96, 23: 36x50, 24: 20x28 -- the lengths with register kernels); 25: 64x92 in 72x96, its last column the transform's last (92 + 4 = 96) and
+    # four rows of padding more than it needs; 26: 120x180 in 128x192, 27: 97x121 in 128x128 (32-channel blocks in the inverse column pass);
+    # 28: 60x92 fills its 64x96 transform to the last row AND column.  (Every length, filled on each axis: test_gpu_fft_lengths.py.)
     out += [(22, 2, 60, 90, 256, 512, 9), (23, 1, 30, 45, 128, 128, 9), (24, 3, 15, 23, 128, 256, 9), (25, 1, 64, 92, 128, 128, 9),
-            (26, 1, 120, 180, 64, 128, 5), (27, 2, 97, 121, 64, 64, 9)]      # 128 x 192 transforms (32-channel column blocks)
+            (26, 1, 120, 180, 64, 128, 5), (27, 2, 97, 121, 64, 64, 9), (28, 1, 60, 92, 128, 128, 9)]
     return out
 
 
@@ -305,6 +307,10 @@ def grad_cases():
     out += [(26, 2, 50, 74, 16, 32, 5, 'debug conv2_fullres at 200x296'), (27, 2, 25, 37, 32, 64, 9, 'debug conv3_fullres at 200x296'),
             (28, 2, 25, 37, 64, 128, 9, 'debug conv4_fullres at 200x296'), (29, 2, 25, 37, 128, 128, 9, 'debug conv5 at 200x296'),
             (30, 2, 25, 37, 128, 9, 9, 'debug conv6 at 200x296')]
+    # maps that FILL their transform (H + 4 = NY, W + 4 = NX: the wrap-around of the circular convolution ends in the first row / column nobody reads),
+    # at lengths the cases above do not reach: NY 64, 72, 100, 128, 192 and NX 24, 100, 192 (tests/fft_lengths_ref.py walks the whole table, forward)
+    out += [(31, 2, 60, 20, 64, 64, 9, 'fills 64 x 24'), (32, 1, 68, 96, 64, 64, 5, 'fills 72 x 100'), (33, 1, 124, 188, 64, 64, 5, 'fills 128 x 192'),
+            (34, 1, 96, 16, 128, 64, 9, 'fills 100 x 20'), (35, 1, 188, 20, 64, 64, 5, 'fills 192 x 24')]
     return out
 
 
