@@ -23,6 +23,9 @@
 // The filter spectra (flipped kernel: TF's conv2d is a correlation) are computed once per (layer, map size) at first use, split into the
 // same bf16 parts, in the GEMM's tile-major layout.  FFTs: the in-LDS decimation-in-frequency stages of sm_fused.hip, channel-vectorised
 // (consecutive lanes = consecutive channels).  Twiddles come from one table per device, built on the host in double precision.
+// This file: the filter-spectra kernels and their packers; then the host side -- sizes (kLens, sizes_of), the hand-over predicates, the FftPlan of a layer call
+// (conv_fft_plan.h: sizes, views, workspace regions, twiddles), the refusals that say which variant a call can take, the five pass functions that each choose
+// their kernel, and the runners (conv_fft_f32 with its tiled form, conv_fft_logits_f32, conv_fft_spectra), which are sequences of those passes.
 // Reference semantics: conv2d SAME stride 1 + bias + ReLU + BatchNorm (main.py:133-135,156-169).
 #include <cmath>
 #include <map>
@@ -31,6 +34,7 @@
 #include <vector>
 
 #include "conv_fft_common.h"
+#include "conv_fft_plan.h"
 
 namespace jcm {
 namespace cfft {
@@ -205,7 +209,7 @@ static int tw_offset(int n) {
 }
 // circular convolution of size >= (H + pad) x (W + pad); one size per map for every kernel size (pad of the 9x9 layers), so that two
 // consecutive layers can hand the row-transformed tensor over.  The old limit H + k - 1 <= 192 is kept.
-// circ (ConvArgs::circ): overlap-save windows -- the H x W input IS the transform (H, W must be transform lengths, at least one valid row / column)
+// circ (FftArgs::circ): overlap-save windows -- the H x W input IS the transform (H, W must be transform lengths, at least one valid row / column)
 static bool sizes_of(int H, int W, int ks, Sizes* s, int circ = 0) {
   if (circ) {
     s->NY = H; s->NX = W;
@@ -263,11 +267,13 @@ static const cf* twiddle_table(int dev) {
 
 using namespace cfft;
 
-bool conv_fft_supported(const ConvArgs& a, int ks) {
+// ---- sizes, filter spectra, hand-over predicates ----
+bool conv_fft_supported(const ConvArgs& a, int ks, int circ) {
   Sizes s;
-  return a.Cin % CB == 0 && a.Cin >= CB && a.Cout >= 1 && a.B >= 1 && sizes_of(a.H, a.W, ks, &s, a.circ);
+  return a.Cin % CB == 0 && a.Cin >= CB && a.Cout >= 1 && a.B >= 1 && sizes_of(a.H, a.W, ks, &s, circ);
 }
-// np: operand form of the channel GEMM (cgemm_split.hip): 4 = fp32 handles, 5 / 2 = bf16 handles
+// np: operand form of the channel GEMM (FftOperand; cgemm_split.hip): 4 = fp32 handles, 5 / 2 = bf16 handles
+static bool operand_form(int np) { return np == kFftBf16x2 || np == kFftFp16x2 || np == kFftFp16x1; }
 size_t conv_fft_weight_bytes(int H, int W, int ks, int Cin, int Cout, int np, int circ) {
   Sizes s;
   if (!sizes_of(H, W, ks, &s, circ)) return 0;
@@ -276,7 +282,7 @@ size_t conv_fft_weight_bytes(int H, int W, int ks, int Cin, int Cout, int np, in
 hipError_t conv_fft_pack_weights(const float* w_hwio, void* wf, int H, int W, int ks, int Cin, int Cout, int np, bool round_bf16, hipStream_t st, float* wscale, int circ,
                                  const float* bound_from) {
   Sizes s;
-  if (!sizes_of(H, W, ks, &s, circ) || Cin % 16 || (np != 2 && np != 4 && np != 5) || (np >= 4 && !wscale) || (np == 5 && Cin % 32)) return hipErrorInvalidValue;
+  if (!sizes_of(H, W, ks, &s, circ) || Cin % 16 || !operand_form(np) || (np >= 4 && !wscale) || (np == kFftFp16x1 && Cin % 32)) return hipErrorInvalidValue;
   const int ntl = cgemm_split_ntile(np, Cout), CoutP = padn(Cout, ntl);
   const size_t cpt = 8;      // thread = (8 input channels: one 16-byte unit, output channel); one kx per block
   const dim3 grid((unsigned)(((size_t)Cin / cpt * CoutP + 255) / 256), (unsigned)(s.NX / 2 + 1));
@@ -301,52 +307,29 @@ hipError_t conv_fft_pack_weights(const float* w_hwio, void* wf, int H, int W, in
 #undef WS_LAUNCH
   return hipGetLastError();
 }
-// scratch: T (the larger of the two row-transformed tensors) + the split activation spectra Xs + the product spectra Yf
-namespace {
-struct Plan3 { size_t t_bytes, xs_bytes, yf_bytes, sc_fwd_bytes, sc_inv_bytes; int MT, NXH, F, ldy, inv_cb; };
-Plan3 plan_of(const ConvArgs& a, const Sizes& s, int np) {
-  Plan3 p;
-  p.NXH = s.NX / 2 + 1;
-  p.F = s.NY * p.NXH;
-  p.ldy = padn(a.Cout, cgemm_split_ntile(np, a.Cout));      // complex numbers per row of the product spectra: whole N tiles, and whole
-  if (p.ldy < pad64(a.Cout)) p.ldy = pad64(a.Cout);          // 64-channel blocks of the inverse passes (columns no tile writes are never stored)
-  p.MT = cgemm_split_mtile(np, a.B, a.Cout);
-  const size_t cop = pad64(a.Cout), cmax = (size_t)a.Cin > cop ? a.Cin : cop;
-  const size_t bp = (size_t)(a.B + p.MT - 1) / p.MT * p.MT;
-  p.t_bytes = (size_t)a.B * p.NXH * a.H * cmax * sizeof(cf);
-  p.xs_bytes = (size_t)p.F * bp * a.Cin * 4 * cgemm_split_parts(np);
-  p.yf_bytes = (size_t)p.F * a.B * p.ldy * sizeof(cf);
-  // tile scale words of the 16-bit T / T' (np = 5, Fp16Scale::t16): one per (image, row, 64 input channels) / (image, kx, inv_cb output channels)
-  p.inv_cb = s.NY > 100 ? 32 : 64;      // colblk<NY>() of the inverse column pass
-  p.sc_fwd_bytes = (size_t)a.B * a.H * (a.Cin / CB) * sizeof(float);
-  p.sc_inv_bytes = (size_t)a.B * p.NXH * (cop / p.inv_cb) * sizeof(float);
-  return p;
-}
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-// a tiled layer (ConvArgs::tiles) as the columns, the GEMM and the inverse column pass see it: 4 B images of an NY x NX transform whose NY rows are all real
-ConvArgs tile_view(const ConvArgs& a, const Sizes& s) {
-  ConvArgs t = a;
-  t.B = 4 * a.B; t.H = s.NY; t.W = a.W / 2;
-  t.tiles = 0;
-  return t;
-}
-}  // namespace
-size_t conv_fft_workspace_bytes(const ConvArgs& a, int ks, int np) {
-  Sizes s;
-  if (!(a.tiles ? sizes_of(a.H / 2, a.W / 2, ks, &s) : sizes_of(a.H, a.W, ks, &s, a.circ))) return 0;
-  const Plan3 p = a.tiles ? plan_of(tile_view(a, s), s, np) : plan_of(a, s, np);
-  return align256(p.t_bytes) + align256(p.xs_bytes) + align256(p.yf_bytes) + align256(p.sc_fwd_bytes) + align256(p.sc_inv_bytes);
-}
 // Can layer L (a, ks) hand its output to layer L+1 (kernel size ks_next, same map) in row-transformed form?  Same NX for both kernel
 // sizes (always: the size depends on the map only), unpadded channel count, two row buffers in LDS.
 bool conv_fft_fusable(const ConvArgs& a, int ks, int ks_next) {
   Sizes s, n;
   return sizes_of(a.H, a.W, ks, &s) && sizes_of(a.H, a.W, ks_next, &n) && s.NX == n.NX && a.Cout % CB == 0;
 }
-size_t conv_fft_handover_bytes(const ConvArgs& a, int ks) {      // T[kx][c/16][b][y][16] of the next layer
+static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+FftHandover16 conv_fft_handover16(int B, int NXH, int H, int C) {
+  FftHandover16 h;
+  h.words_off = align256((size_t)B * NXH * H * C * 4);
+  h.bytes = h.words_off + (size_t)B * H * (C / CB) * sizeof(float);
+  return h;
+}
+// T[kx][c/16][b][y][16] of the next layer, complex fp32.  h16: the 16-bit form (conv_fft_handover16) lives in a buffer of the same size -- 4 instead of 8 bytes per
+// complex number leave 4 B NXH H C bytes for at most 255 bytes of alignment and B H C / 16 bytes of scale words, and NXH >= 11, C >= 64: the maximum below is the
+// fp32 size for every shape the route takes, and says so in code.
+size_t conv_fft_handover_bytes(const ConvArgs& a, int ks, bool h16) {
   Sizes s;
   if (!sizes_of(a.H, a.W, ks, &s)) return 0;
-  return (size_t)a.B * (s.NX / 2 + 1) * a.H * a.Cout * sizeof(cf);
+  const int NXH = s.NX / 2 + 1;
+  const size_t f32 = (size_t)a.B * NXH * a.H * a.Cout * sizeof(cf);
+  const size_t b16 = h16 ? conv_fft_handover16(a.B, NXH, a.H, a.Cout).bytes : 0;
+  return f32 > b16 ? f32 : b16;
 }
 bool conv_fft_win_gather_supported(int win, int Cin, bool fft_reg) { return fft_reg && cfft_rows_fwd_win_reg_supported(win, Cin); }
 bool conv_fft_win_scatter_supported(int win, int Cout, bool fft_reg) { return fft_reg && win == 32 && Cout % 64 == 0; }      // rows_inv_reg_kernel<32, 0, false>
@@ -360,12 +343,6 @@ size_t conv_fft_pool_handover_bytes(const ConvArgs& a, int ks_next) {      // T[
   if (!sizes_of((a.H + 1) / 2, (a.W + 1) / 2, ks_next, &n)) return 0;
   return (size_t)a.B * (n.NX / 2 + 1) * ((a.H + 1) / 2) * a.Cout * sizeof(cf);
 }
-// 2 x 2 tiles: a 5x5 layer whose output goes through the pool hand-over into a 5x5 layer, on the model's 120 x 180 map (cfft_tiles_supported)
-bool conv_fft_tiles_supported(const ConvArgs& a, int ks, int ks_next) {
-  Sizes s;
-  return a.fft_reg && ks == 5 && ks_next == 5 && !a.circ && !a.win_map && a.B >= 1 && conv_fft_pool_fusable(a, ks, ks_next) &&
-         a.H % 4 == 0 && a.W % 4 == 0 && sizes_of(a.H / 2, a.W / 2, ks, &s) && cfft_tiles_supported(s.NY, s.NX, a);
-}
 // h16: bf16 handles on the one-part route with 16-bit row-transformed tensors -- the register kernel only (the model's geometry)
 bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool fft_reg, bool h16) {
   Sizes s;
@@ -373,147 +350,16 @@ bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMer
   const bool reg = fft_reg && cfft_rows_inv_merge_fwd_reg_supported(s.NX, a, m, (ks - 1) / 2);
   return h16 ? reg : (reg || cfft_rows_inv_merge_fwd_supported(s.NX, a, m));
 }
-// a.wp = the split filter spectra of THIS map size and kernel size; `work` = conv_fft_workspace_bytes(a, ks, np) bytes.  g0 / g1: optional
-// events recorded around the GEMM (the dominant kernel of the layer) for the roofline record.
-// in_layout / out_layout: 0 = fp32 NHWC, 1 = bf16 NHWC, 2 = bf16 planar
-// link: what ties the layer to its neighbours (FftLink, kernels.h); the checks below say which combinations exist.
-// The tiled layer (a0.tiles): rows forward from the map into the 4 B tiles, columns, GEMM and inverse columns of the tiles' transform, then the pool
-// hand-over that stitches the tiles back together.  sc->tmax: 4 B words (one per tile: the GEMM row), sc->tmax_next: B words (one per image).
-static hipError_t conv_fft_tiles_f32(const ConvArgs& a0, int ks, int np, int in_layout, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
-                                     const Fp16Scale* scp) {
-  const void* t_in = link.t_in; void* t_next = link.t_next; const FftMerge* merge = link.merge; void* xs = link.xs; const bool xs_ready = link.xs_ready; const FftNext* nx = &link.next;
+// geometry of the spectra for the weight-gradient kernels
+bool conv_fft_geometry(int H, int W, int ks, int B, int Cout, int np, int* NY, int* NX, int* MT, int circ) {
   Sizes s;
-  if (np != 4 || in_layout != 0 || t_in || merge || xs || xs_ready || !t_next || !nx || !nx->pool || nx->merge || !scp || !scp->tmax || !scp->winv || !scp->tmax_next ||
-      !conv_fft_tiles_supported(a0, ks, nx->ks_next) || !sizes_of(a0.H / 2, a0.W / 2, ks, &s))
-    return hipErrorInvalidValue;
-  ConvArgs a = a0;
-  a.CoutP = pad64(a.Cout);
-  const ConvArgs at = tile_view(a, s);
-  const Plan3 p = plan_of(at, s, np);
-  Fp16Scale sc = *scp;
-  sc.hf = (float)s.NY;      // the column pass's bound: NY real rows per tile
-  sc.nb = at.B;
-  char* wk = static_cast<char*>(work);
-  cf* T = reinterpret_cast<cf*>(wk);
-  void* Xs = wk + align256(p.t_bytes);
-  cf* Yf = reinterpret_cast<cf*>(wk + align256(p.t_bytes) + align256(p.xs_bytes));
-  int dev = 0;
-  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-  const cf* twb = twiddle_table(dev);
-  if (!twb) return hipErrorOutOfMemory;
-  if (!cfft_rows_fwd_tile_reg(s.NY, s.NX, a, T, sc.tmax, st)) return hipErrorInvalidValue;
-  if (hipError_t ce = cfft_cols_fwd(s.NY, at, np, T, Xs, twb + tw_offset(s.NY), p.NXH, p.MT, sc, st); ce != hipSuccess) return ce;
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (g0 && hipEventRecord(g0, st) != hipSuccess) return hipErrorUnknown;
-  if (hipError_t e = cgemm_split(Xs, a.wp, Yf, np, p.F, at.B, a.Cin, a.Cout, p.ldy, st, 0.f); e != hipSuccess) return e;
-  if (g1 && hipEventRecord(g1, st) != hipSuccess) return hipErrorUnknown;
-  ConvArgs ai = at;      // the inverse column pass keeps the Ht valid rows of each tile
-  ai.H = a.H / 2;
-  if (!cfft_cols_inv_reg(s.NY, ai, Yf, T, p.NXH, p.ldy, (ks - 1) / 2, st, nullptr, 0.f)) return hipErrorInvalidValue;
-  if (!cfft_rows_inv_pool_tile_reg(s.NY, s.NX, a, T, static_cast<cf*>(t_next), 1.0f / (float)(s.NY * s.NX), sc, st)) return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-hipError_t conv_fft_f32(const ConvArgs& a0, int ks, int np, int in_layout, int out_layout, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
-                        const Fp16Scale* scp) {
-  if (a0.tiles) return conv_fft_tiles_f32(a0, ks, np, in_layout, work, link, g0, g1, st, scp);
-  const void* t_in = link.t_in; void* t_next = link.t_next; const FftMerge* merge = link.merge; void* xs = link.xs; const bool xs_ready = link.xs_ready; const FftNext* nx = &link.next;
-  Sizes s;
-  if (!conv_fft_supported(a0, ks) || !sizes_of(a0.H, a0.W, ks, &s, a0.circ) || (out_layout == 2 && a0.Cout % 8) || (np != 2 && np != 4 && np != 5) || (np == 5 && a0.Cin % 32)) return hipErrorInvalidValue;
-  if (a0.circ && (t_in || t_next || merge || in_layout != 0 || out_layout != 0)) return hipErrorInvalidValue;      // windows: fp32 NHWC in and out, nothing fused
-  if (nx && (nx->pool || nx->merge) && (!t_next || (nx->pool && nx->merge))) return hipErrorInvalidValue;
-  Fp16Scale sc;
-  if (np >= 4) {
-    if (!scp || !scp->tmax || !scp->winv || (t_next && !scp->tmax_next)) return hipErrorInvalidValue;
-    sc = *scp;
-    sc.hf = (float)a0.H;
-    sc.nb = a0.B;
-  }
-  // bf16 handles: the merge hand-over (conv4_fullres -> conv5) in 16-bit form -- t_next / t_in is a complex-fp16 T followed by its tile scale words
-  const bool h16 = sc.t16 && ((t_next && nx && nx->merge && !t_in) || (t_in && !t_next));
-  if ((t_in || t_next) && !h16 && (in_layout != 0 || out_layout != 0)) return hipErrorInvalidValue;
-  if (t_next && a0.Cout % CB) return hipErrorInvalidValue;
-  if (sc.t16 && (np != 5 || in_layout == 0 || out_layout == 0 || xs || ((t_in || t_next) && !h16))) return hipErrorInvalidValue;      // 16-bit T / T': bf16 tensors either side, one-part route
-  if (merge && in_layout == 2) return hipErrorInvalidValue;      // the merge reads NHWC (fp32 or bf16)
-  ConvArgs a = a0;
-  a.CoutP = pad64(a.Cout);
-  // output row y = row y + pad of the circular convolution (whose size is H + 4 for both kernel sizes); windows: the valid region starts 4 rows into the window
-  const int opad = (ks - 1) / 2 + (a0.circ ? 4 : 0);
-  const Plan3 p = plan_of(a, s, np);
-  char* wk = static_cast<char*>(work);
-  cf* T = reinterpret_cast<cf*>(wk);
-  void* Xs = xs ? xs : wk + align256(p.t_bytes);
-  cf* Yf = reinterpret_cast<cf*>(wk + align256(p.t_bytes) + align256(p.xs_bytes));
-  if (sc.t16) {
-    sc.t16_fwd = reinterpret_cast<float*>(wk + align256(p.t_bytes) + align256(p.xs_bytes) + align256(p.yf_bytes));
-    sc.t16_inv = reinterpret_cast<float*>(wk + align256(p.t_bytes) + align256(p.xs_bytes) + align256(p.yf_bytes) + align256(p.sc_fwd_bytes));
-    sc.t16_cb = p.inv_cb;
-    // a handed-over 16-bit T carries its scale words behind it (written by the producing layer's fused row kernel)
-    if (t_in) sc.t16_fwd = reinterpret_cast<float*>(const_cast<char*>(static_cast<const char*>(t_in)) + align256((size_t)a.B * p.NXH * a.H * a.Cin * 4));
-  }
-  if (xs_ready && !xs) return hipErrorInvalidValue;
-  int dev = 0;
-  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-  const cf* twb = twiddle_table(dev);
-  if (!twb) return hipErrorOutOfMemory;
-  const cf* twx = twb + tw_offset(s.NX);
-  const cf* twy = twb + tw_offset(s.NY);
-  const float norm = 1.0f / (float)(s.NY * s.NX);
-  const cf* Tin = t_in ? static_cast<const cf*>(t_in) : T;
-  const bool fft_reg = a.fft_reg != 0;
-  if (!xs_ready) {
-    if (merge && !t_in) {
-      if (!(fft_reg && cfft_rows_fwd_merge_reg(s.NX, a, *merge, in_layout, T, sc.tmax, st, sc.t16_fwd))) cfft_rows_fwd_merge(s.NX, a, *merge, in_layout, T, twx, sc.tmax, st, sc.t16_fwd);
-    } else if (!t_in) {
-      if (a.win_map) { if (!cfft_rows_fwd_win_reg(s.NX, a, T, sc.tmax, st)) return hipErrorInvalidValue; }
-      else if (!(fft_reg && cfft_rows_fwd_reg(s.NX, a, in_layout, T, sc.tmax, st, sc.t16_fwd))) cfft_rows_fwd(s.NX, a, in_layout, T, twx, sc.tmax, st, sc.t16_fwd);
-    }
-    if (hipError_t ce = cfft_cols_fwd(s.NY, a, np, Tin, Xs, twy, p.NXH, p.MT, sc, st); ce != hipSuccess) return ce;
-  }
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (g0 && hipEventRecord(g0, st) != hipSuccess) return hipErrorUnknown;
-  // 16-bit intermediates (bf16 handles, one-part route): the product spectra travel as complex fp16 too, under the constant shift of cgemm_split.hip
-  // (same-box A/B at 256 images: 19.1 -> 18.0 ms per step, profiles/r05_ab_y16.log)
-  const float yshift = sc.t16 ? cgemm_split_y16_shift(a.Cin) : 0.f, yinv = yshift != 0.f ? 1.0f / yshift : 0.f;
-  if (hipError_t e = cgemm_split(Xs, a.wp, Yf, np, p.F, a.B, a.Cin, a.Cout, p.ldy, st, yshift); e != hipSuccess) return e;
-  if (g1 && hipEventRecord(g1, st) != hipSuccess) return hipErrorUnknown;
-  ConvArgs ai = a;      // the inverse passes' view: windows keep their valid region only
-  if (a0.circ) { ai.H = a0.H - 8; ai.W = a0.W - 8; }
-  if (!(fft_reg && p.inv_cb == 64 && cfft_cols_inv_reg(s.NY, ai, Yf, T, p.NXH, p.ldy, opad, st, sc.t16_inv, yinv))) cfft_cols_inv(s.NY, ai, Yf, T, twy, p.NXH, p.ldy, opad, st, sc.t16_inv, yinv);
-  if (t_next && nx && nx->pool) {
-    Sizes sn;
-    if (!sizes_of((a.H + 1) / 2, (a.W + 1) / 2, nx->ks_next, &sn) ||
-        !cfft_rows_inv_pool_fwd(s.NX, sn.NX, a, T, static_cast<cf*>(t_next), twx, twb + tw_offset(sn.NX), opad, norm, sc, st))
-      return hipErrorInvalidValue;
-  } else if (t_next && nx && nx->merge) {
-    if (sc.t16) {
-      float* t16n = reinterpret_cast<float*>(static_cast<char*>(t_next) + align256((size_t)a.B * p.NXH * a.H * a.Cout * 4));
-      if (!(fft_reg && cfft_rows_inv_merge_fwd_reg(s.NX, a, *nx->merge, T, static_cast<cf*>(t_next), opad, norm, sc, st, t16n))) return hipErrorInvalidValue;
-    } else if (!(fft_reg && cfft_rows_inv_merge_fwd_reg(s.NX, a, *nx->merge, T, static_cast<cf*>(t_next), opad, norm, sc, st)) &&
-               !cfft_rows_inv_merge_fwd(s.NX, a, *nx->merge, T, static_cast<cf*>(t_next), twx, opad, norm, sc, st)) {
-      return hipErrorInvalidValue;
-    }
-  } else if (t_next) {
-    if (!(fft_reg && cfft_rows_inv_fwd_reg(s.NX, a, T, static_cast<cf*>(t_next), opad, norm, sc, st))) cfft_rows_inv_fwd(s.NX, a, T, static_cast<cf*>(t_next), twx, opad, norm, sc, st);
-  } else if (!((ai.rows_mfma & 1) && cfft_rows_inv_mfma(s.NX, ai, out_layout, T, opad, norm, sc, st)) && !(fft_reg && cfft_rows_inv_reg(s.NX, ai, out_layout, T, opad, norm, sc, st))) {
-    if (ai.wout_TX > 0) return hipErrorInvalidValue;      // (the scatter into the map exists in the register kernel only)
-    cfft_rows_inv(s.NX, ai, out_layout, T, twx, opad, norm, sc, st);
-  }
-  return hipGetLastError();
-}
-
-// ---- the logits layer on the row spectra of its input (conv_fft_logits.hip): a 9x9 layer with at most 16 output channels whose row-transformed input was
-// handed over at a 96-point row length.  No column pass, no filter spectra: the operand A (conv_fft_logits_pack) and one inverse row pass.
-bool conv_fft_logits_rows_supported(const ConvArgs& a, int ks) {
-  Sizes s;
-  return ks == 9 && !a.circ && !a.tiles && !a.win_map && conv_fft_supported(a, ks) && sizes_of(a.H, a.W, ks, &s) && cfft_logits_rows_supported(s.NX, a);
+  if (!sizes_of(H, W, ks, &s, circ)) return false;
+  *NY = s.NY; *NX = s.NX; *MT = cgemm_split_mtile(np, B, Cout);
+  return true;
 }
 size_t conv_fft_logits_weight_bytes(int H, int W, int Cin) {
   Sizes s;
   return sizes_of(H, W, 9, &s) ? cfft_logits_rows_operand_bytes(s.NX, Cin) : 0;
-}
-size_t conv_fft_logits_workspace_bytes(const ConvArgs& a) {      // S = T'[b][y][kx][64]
-  Sizes s;
-  return sizes_of(a.H, a.W, 9, &s) ? align256((size_t)a.B * a.H * (s.NX / 2 + 1) * CB * sizeof(cf)) : 0;
 }
 hipError_t conv_fft_logits_pack(const float* w_hwio, void* aop, int H, int W, int Cin, int Cout, hipStream_t st, float* wscale) {
   Sizes s;
@@ -522,62 +368,284 @@ hipError_t conv_fft_logits_pack(const float* w_hwio, void* aop, int H, int W, in
   const size_t pairs = (size_t)Cin * Cout;
   const dim3 bgrid((unsigned)((pairs + 255) / 256 > 1024 ? 1024 : (pairs + 255) / 256));
   hipLaunchKernelGGL(weight_bound_kernel<81>, bgrid, dim3(256), 0, st, w_hwio, pairs, 0, wscale);
-  return cfft_logits_rows_pack(s.NX, w_hwio, aop, Cin, Cout, wscale, st);
-}
-// a.wp = the operand A; link.t_in = T[kx][c/16][b][y][16] with its words sc.tmax; work = conv_fft_logits_workspace_bytes(a).  The image's scale is
-// 2^k with tmax[b] 2^k < 2^15 (Fp16Scale::hf = 1: no column transform sums H rows), undone by the inverse row pass together with the operand's.
-hipError_t conv_fft_logits_f32(const ConvArgs& a0, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st, const Fp16Scale* scp) {
-  Sizes s;
-  if (!conv_fft_logits_rows_supported(a0, 9) || !sizes_of(a0.H, a0.W, 9, &s) || !link.t_in || link.t_in_16 || link.t_next || link.merge || link.xs || link.xs_ready || link.win_scatter ||
-      !scp || !scp->tmax || !scp->winv || scp->common)
-    return hipErrorInvalidValue;
-  ConvArgs a = a0;
-  a.CoutP = pad64(a.Cout);
-  Fp16Scale sc = *scp;
-  sc.hf = 1.f;
-  sc.nb = a.B;
-  int dev = 0;
-  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-  const cf* twb = twiddle_table(dev);
-  if (!twb) return hipErrorOutOfMemory;
-  cf* S = static_cast<cf*>(work);
-  if (g0 && hipEventRecord(g0, st) != hipSuccess) return hipErrorUnknown;
-  if (hipError_t e = cfft_logits_rows(s.NX, a, static_cast<const cf*>(link.t_in), a.wp, sc.tmax, S, st); e != hipSuccess) return e;
-  if (g1 && hipEventRecord(g1, st) != hipSuccess) return hipErrorUnknown;
-  cfft_rows_inv(s.NX, a, 0, S, twb + tw_offset(s.NX), 4, 1.0f / (float)s.NX, sc, st);
+  if (!cfft_logits_rows_pack(s.NX, w_hwio, aop, Cin, Cout, wscale, st)) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-// the split spectra of an NHWC fp32 tensor alone (rows + columns forward): xs = conv_fft_xs_bytes() bytes, work = conv_fft_workspace_bytes()
-size_t conv_fft_xs_bytes(const ConvArgs& a, int ks, int np) {
-  Sizes s;
-  if (!sizes_of(a.H, a.W, ks, &s, a.circ)) return 0;
-  return align256(plan_of(a, s, np).xs_bytes);
+// ---- the plan (conv_fft_plan.h) ----
+// the one place that lays the workspace out: the regions in this order, each at the next multiple of 256 bytes
+static void carve(FftPlan* p, size_t t, size_t xs, size_t yf, size_t sc_fwd, size_t sc_inv) {
+  FftRegion* const regions[] = {&p->T, &p->Xs, &p->Yf, &p->t16_fwd, &p->t16_inv};
+  const size_t bytes[] = {t, xs, yf, sc_fwd, sc_inv};
+  size_t off = 0;
+  for (int i = 0; i < 5; ++i) {
+    regions[i]->off = off;
+    regions[i]->bytes = bytes[i];
+    off += align256(bytes[i]);
+  }
+  p->total = off;
 }
-hipError_t conv_fft_spectra(const ConvArgs& a0, int ks, int np, void* work, void* xs, hipStream_t st, float* tmax, int common) {
+FftPlan conv_fft_plan(const FftArgs& a, int ks, int np, int pool_ks_next) {
+  FftPlan p;
+  Sizes s, n;
+  p.ok = a.tiles ? sizes_of(a.H / 2, a.W / 2, ks, &s) : sizes_of(a.H, a.W, ks, &s, a.circ);
+  if (!p.ok) return p;
+  p.ks = ks; p.np = np;
+  p.NY = s.NY; p.NX = s.NX; p.NXH = s.NX / 2 + 1; p.F = s.NY * p.NXH;
+  if (pool_ks_next && sizes_of((a.H + 1) / 2, (a.W + 1) / 2, pool_ks_next, &n)) p.NX_next = n.NX;
+  p.opad = (ks - 1) / 2 + (a.circ ? 4 : 0);      // windows: the valid region starts 4 rows into the window
+  p.norm = 1.0f / (float)(s.NY * s.NX);
+  p.map = a;
+  p.map.CoutP = pad64(a.Cout);
+  p.col = p.map;
+  if (a.tiles) { p.col.B = 4 * a.B; p.col.H = s.NY; p.col.W = a.W / 2; p.col.tiles = 0; }
+  p.inv = p.col;
+  if (a.tiles) p.inv.H = a.H / 2;
+  if (a.circ) { p.inv.H = a.H - 8; p.inv.W = a.W - 8; }
+  const FftArgs& c = p.col;
+  p.ldy = padn(c.Cout, cgemm_split_ntile(np, c.Cout));      // complex numbers per row of the product spectra: whole N tiles, and whole
+  if (p.ldy < pad64(c.Cout)) p.ldy = pad64(c.Cout);          // 64-channel blocks of the inverse passes (columns no tile writes are never stored)
+  p.MT = cgemm_split_mtile(np, c.B, c.Cout);
+  p.inv_cb = s.NY > 100 ? 32 : 64;      // colblk<NY>() of the inverse column pass
+  const size_t cop = pad64(c.Cout), cmax = (size_t)c.Cin > cop ? c.Cin : cop;
+  const size_t bp = (size_t)(c.B + p.MT - 1) / p.MT * p.MT;
+  carve(&p, (size_t)c.B * p.NXH * c.H * cmax * sizeof(cf), (size_t)p.F * bp * c.Cin * 4 * cgemm_split_parts(np), (size_t)p.F * c.B * p.ldy * sizeof(cf),
+        (size_t)c.B * c.H * (c.Cin / CB) * sizeof(float), (size_t)c.B * p.NXH * (cop / p.inv_cb) * sizeof(float));
+  return p;
+}
+FftPlan conv_fft_logits_plan(const FftArgs& a) {
+  FftPlan p;
   Sizes s;
-  if (!conv_fft_supported(a0, ks) || !sizes_of(a0.H, a0.W, ks, &s, a0.circ) || !xs || (np >= 4 && !tmax)) return hipErrorInvalidValue;
-  Fp16Scale sc;
-  if (np >= 4) { sc.tmax = tmax; sc.hf = (float)a0.H; sc.nb = a0.B; sc.common = common; }
-  ConvArgs a = a0;
-  a.CoutP = pad64(a.Cout);
-  const Plan3 p = plan_of(a, s, np);
+  p.ok = sizes_of(a.H, a.W, 9, &s);
+  if (!p.ok) return p;
+  p.ks = 9; p.np = kFftFp16x2;
+  p.NY = s.NY; p.NX = s.NX; p.NXH = s.NX / 2 + 1; p.F = s.NY * p.NXH;
+  p.opad = 4;
+  p.norm = 1.0f / (float)s.NX;      // no column transform
+  p.map = a;
+  p.map.CoutP = pad64(a.Cout);
+  p.col = p.inv = p.map;
+  carve(&p, (size_t)a.B * a.H * p.NXH * CB * sizeof(cf), 0, 0, 0, 0);      // S = T'[b][y][kx][64]
+  return p;
+}
+hipError_t conv_fft_plan_twiddles(FftPlan* p) {
   int dev = 0;
   if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
   const cf* twb = twiddle_table(dev);
   if (!twb) return hipErrorOutOfMemory;
-  cf* T = static_cast<cf*>(work);
-  if (a.win_map) { if (!cfft_rows_fwd_win_reg(s.NX, a, T, sc.tmax, st)) return hipErrorInvalidValue; }
-  else cfft_rows_fwd(s.NX, a, 0, T, twb + tw_offset(s.NX), sc.tmax, st);
-  if (hipError_t ce = cfft_cols_fwd(s.NY, a, np, T, xs, twb + tw_offset(s.NY), p.NXH, p.MT, sc, st); ce != hipSuccess) return ce;
+  p->twx = twb + tw_offset(p->NX);
+  p->twy = twb + tw_offset(p->NY);
+  p->twx_next = p->NX_next ? twb + tw_offset(p->NX_next) : nullptr;
+  return hipSuccess;
+}
+size_t conv_fft_workspace_bytes(const FftArgs& a, int ks, int np) {
+  const FftPlan p = conv_fft_plan(a, ks, np);
+  return p.ok ? p.total : 0;
+}
+// the split spectra of an NHWC fp32 tensor alone (conv_fft_spectra): xs = conv_fft_xs_bytes() bytes, work = conv_fft_workspace_bytes()
+size_t conv_fft_xs_bytes(const FftArgs& a0, int ks, int np) {
+  FftArgs a = a0;
+  a.tiles = 0;
+  const FftPlan p = conv_fft_plan(a, ks, np);
+  return p.ok ? align256(p.Xs.bytes) : 0;
+}
+
+// ---- what each variant takes: null, or the first condition the call violates ----
+const char* conv_fft_refusal(const FftPlan& p, FftLayout in, FftLayout out, const FftLink& k, int t16) {
+  const FftArgs& a = p.map;
+  if (!p.ok) return "no transform size for this map and kernel size";
+  if (a.Cin % CB || a.Cin < CB || a.Cout < 1 || a.B < 1) return "input channels in whole blocks of 64, at least one output channel and one image";
+  if (out == kFftBf16Planar && a.Cout % 8) return "planar bf16 output needs whole units of 8 channels";
+  if (!operand_form(p.np)) return "operand forms of the channel GEMM: 2, 4, 5";
+  if (p.np == kFftFp16x1 && a.Cin % 32) return "the one-part operand stages 32 input channels at a time";
+  if (a.circ && (k.t_in || k.t_next || k.merge || in != kFftF32Nhwc || out != kFftF32Nhwc)) return "windows take fp32 NHWC on both sides and no hand-over";
+  if ((k.next.pool || k.next.merge) && (!k.t_next || (k.next.pool && k.next.merge))) return "a pool or merge hand-over needs t_next, and only one of the two";
+  // bf16 handles: the merge hand-over (conv4_fullres -> conv5) in 16-bit form -- t_next / t_in is a complex-fp16 T followed by its tile scale words
+  const bool h16 = t16 && ((k.t_next && k.next.merge && !k.t_in) || (k.t_in && !k.t_next));
+  if ((k.t_in || k.t_next) && !h16 && (in != kFftF32Nhwc || out != kFftF32Nhwc)) return "a 32-bit hand-over takes fp32 NHWC tensors on both sides";
+  if (k.t_next && a.Cout % CB) return "a hand-over needs output channels in whole blocks of 64";
+  if (t16 && p.np != kFftFp16x1) return "16-bit T needs the one-part operand form";
+  if (t16 && (in == kFftF32Nhwc || out == kFftF32Nhwc)) return "16-bit T needs bf16 tensors on both sides";
+  if (t16 && (k.xs || ((k.t_in || k.t_next) && !h16))) return "16-bit T keeps no spectra and hands over only across the merge";
+  if (k.merge && in == kFftBf16Planar) return "the merge reads NHWC";
+  if (k.xs_ready && !k.xs) return "ready spectra without their buffer";
+  if (k.t_next && k.next.pool && !p.NX_next) return "no transform size for the pooled map";
+  return nullptr;
+}
+// 2 x 2 tiles: a 5x5 layer whose output goes through the pool hand-over into a 5x5 layer, on the model's 120 x 180 map (cfft_tiles_supported)
+const char* conv_fft_tiles_refusal(const FftPlan& p, FftLayout in, FftLayout, const FftLink& k) {
+  const FftArgs& a = p.map;
+  if (!a.tiles) return "not planned as tiles";
+  if (p.np != kFftFp16x2 || in != kFftF32Nhwc) return "tiles exist on fp32 handles (operand form 4, fp32 NHWC input)";
+  if (k.t_in || k.merge || k.xs || k.xs_ready || k.win_map) return "tiles read their own map: no hand-over in, no merge, no kept spectra, no windows";
+  if (!k.t_next || !k.next.pool || k.next.merge) return "tiles feed the pool hand-over and nothing else";
+  if (!a.fft_reg) return "tiles exist as register kernels only";
+  if (p.ks != 5 || k.next.ks_next != 5) return "tiles exist for a 5x5 layer in front of a 5x5 layer";
+  if (a.circ || a.win_map || a.B < 1) return "tiles of whole maps, at least one image";
+  if (!conv_fft_pool_fusable(a, p.ks, k.next.ks_next)) return "no pool hand-over for this pair of layers";
+  if (a.H % 4 || a.W % 4 || !p.ok || !cfft_tiles_supported(p.NY, p.NX, a)) return "tiles exist for the model's 120 x 180 map geometry";
+  return nullptr;
+}
+// the logits layer on the row spectra of its input: a 9x9 layer with at most 16 output channels whose row-transformed input was handed over at a 96-point row length
+const char* conv_fft_logits_refusal(const FftPlan& p, int ks, int np, FftLayout in, FftLayout out, const FftLink& k, int common) {
+  const FftArgs& a = p.map;
+  if (ks != 9 || np != kFftFp16x2 || in != kFftF32Nhwc || out != kFftF32Nhwc) return "logits rows: a 9x9 layer of an fp32 handle, fp32 NHWC on both sides";
+  if (a.circ || a.tiles || a.win_map || k.win_map || k.win_scatter) return "logits rows: whole maps, no windows, no tiles";
+  if (!p.ok || !conv_fft_supported(a, 9) || !cfft_logits_rows_supported(p.NX, a)) return "logits rows: 96-point rows, at most 64 rows and 16 output channels";
+  if (!k.t_in || k.t_in_16) return "logits rows read a 32-bit row-transformed input";
+  if (k.t_next || k.next.pool || k.next.merge || k.merge || k.xs || k.xs_ready) return "logits rows hand nothing over and keep no spectra";
+  if (common) return "logits rows scale each image by its own word";
+  return nullptr;
+}
+
+// ---- the five passes.  Each picks its kernel here, in order of preference; true: launched.  false: no kernel took the case (or a HIP call in front of the launch
+// failed, which hipGetLastError() then reports).
+namespace {
+struct Run {      // one call: the plan bound to its workspace, its scale and its stream
+  const FftPlan& p;
+  cf* T;
+  void* Xs;
+  cf* Yf;
+  Fp16Scale sc;
+  float yshift, yinv;      // 16-bit product spectra (below)
+  hipStream_t st;
+  bool reg() const { return p.map.fft_reg != 0; }
+};
+// what the kernels take of the caller's scale: np >= 4 only; hf = the rows a column transform sums; the words of a 16-bit T / T' from the plan's regions
+Fp16Scale device_scale(const FftPlan& p, const FftScale* in, float hf, void* work) {
+  Fp16Scale sc;
+  if (p.np < 4 || !in) return sc;
+  sc.tmax = in->tmax; sc.tmax_next = in->tmax_next; sc.winv = in->winv; sc.common = in->common; sc.t16 = in->t16;
+  sc.hf = hf;
+  sc.nb = p.col.B;
+  if (sc.t16) {
+    sc.t16_fwd = p.at<float>(work, p.t16_fwd);
+    sc.t16_inv = p.at<float>(work, p.t16_inv);
+    sc.t16_cb = p.inv_cb;
+  }
+  return sc;
+}
+hipError_t refuse(const char** why, const char* reason) {
+  if (why) *why = reason;
+  return hipErrorInvalidValue;
+}
+hipError_t not_launched(const char** why, const char* reason) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : refuse(why, reason);
+}
+
+// 1. rows, forward: the layer's input -> T.  Tiles: their register kernel.  Merged input: register, else LDS.  Windows cut from their map: the register kernel
+// (the only one; conv_fft_win_gather_supported said so).  Plain: register, else LDS.  (The register kernels take bf16 NHWC into a 16-bit T: fp32 input --
+// conv_fft_spectra always -- ends on the LDS kernel by this same rule.)
+bool pass_rows_fwd(const Run& r, FftLayout in, const FftMerge* merge) {
+  const FftPlan& p = r.p;
+  const FftArgs& a = p.map;
+  if (a.tiles) return cfft_rows_fwd_tile_reg(p.NY, p.NX, a, r.T, r.sc.tmax, r.st);
+  if (merge) return (r.reg() && cfft_rows_fwd_merge_reg(p.NX, a, *merge, in, r.T, r.sc.tmax, r.st, r.sc.t16_fwd)) || cfft_rows_fwd_merge(p.NX, a, *merge, in, r.T, p.twx, r.sc.tmax, r.st, r.sc.t16_fwd);
+  if (a.win_map) return cfft_rows_fwd_win_reg(p.NX, a, r.T, r.sc.tmax, r.st);
+  return (r.reg() && cfft_rows_fwd_reg(p.NX, a, in, r.T, r.sc.tmax, r.st, r.sc.t16_fwd)) || cfft_rows_fwd(p.NX, a, in, r.T, p.twx, r.sc.tmax, r.st, r.sc.t16_fwd);
+}
+// 2. columns, forward, with the operand split: T (or the handed-over one) -> Xs.  One kernel family (LDS).
+bool pass_cols_fwd(const Run& r, const cf* Tin) { return cfft_cols_fwd(r.p.NY, r.p.col, r.p.np, Tin, r.Xs, r.p.twy, r.p.NXH, r.p.MT, r.sc, r.st); }
+// 3. the channel GEMM: Xs x filter spectra -> Yf, between the two optional events
+hipError_t pass_gemm(const Run& r, hipEvent_t g0, hipEvent_t g1) {
+  const FftArgs& c = r.p.col;
+  if (g0 && hipEventRecord(g0, r.st) != hipSuccess) return hipErrorUnknown;
+  if (hipError_t e = cgemm_split(r.Xs, c.wp, r.Yf, r.p.np, r.p.F, c.B, c.Cin, c.Cout, r.p.ldy, r.st, r.yshift); e != hipSuccess) return e;
+  if (g1 && hipEventRecord(g1, r.st) != hipSuccess) return hipErrorUnknown;
+  return hipSuccess;
+}
+// 4. columns, inverse: Yf -> T' (the valid rows).  Register (64-channel work groups only), else LDS; tiles have the register kernel alone.
+bool pass_cols_inv(const Run& r) {
+  const FftPlan& p = r.p;
+  if (r.reg() && p.inv_cb == 64 && cfft_cols_inv_reg(p.NY, p.inv, r.Yf, r.T, p.NXH, p.ldy, p.opad, r.st, r.sc.t16_inv, r.yinv)) return true;
+  if (p.map.tiles) return false;
+  return cfft_cols_inv(p.NY, p.inv, r.Yf, r.T, p.twy, p.NXH, p.ldy, p.opad, r.st, r.sc.t16_inv, r.yinv);
+}
+// 5. rows, inverse, with the epilogue: T' -> the layer's output, or -- fused with the next layer's forward rows -- its hand-over t_next.
+//    tiles: their pool hand-over.  Pool: the one LDS kernel.  Merge: register, else (32-bit only) LDS.  Same map: register, else LDS.
+//    Output: matrix cores (rows_mfma), register, LDS -- the scatter into the map exists in the register kernel only.  lds_only: the logits rows (their S has the
+//    64-channel layout of the LDS kernel's T' and an odd channel count).
+bool pass_rows_inv(const Run& r, FftLayout out, const FftLink& k, bool lds_only = false) {
+  const FftPlan& p = r.p;
+  const FftArgs& a = p.map;
+  cf* Tn = static_cast<cf*>(k.t_next);
+  if (lds_only) return cfft_rows_inv(p.NX, p.inv, out, r.T, p.twx, p.opad, p.norm, r.sc, r.st);
+  if (a.tiles) return cfft_rows_inv_pool_tile_reg(p.NY, p.NX, a, r.T, Tn, p.norm, r.sc, r.st);
+  if (Tn && k.next.pool) return cfft_rows_inv_pool_fwd(p.NX, p.NX_next, a, r.T, Tn, p.twx, p.twx_next, p.opad, p.norm, r.sc, r.st);
+  if (Tn && k.next.merge) {
+    if (r.sc.t16) return r.reg() && cfft_rows_inv_merge_fwd_reg(p.NX, a, *k.next.merge, r.T, Tn, p.opad, p.norm, r.sc, r.st, conv_fft_handover16(a.B, p.NXH, a.H, a.Cout).words(Tn));
+    return (r.reg() && cfft_rows_inv_merge_fwd_reg(p.NX, a, *k.next.merge, r.T, Tn, p.opad, p.norm, r.sc, r.st)) || cfft_rows_inv_merge_fwd(p.NX, a, *k.next.merge, r.T, Tn, p.twx, p.opad, p.norm, r.sc, r.st);
+  }
+  if (Tn) return (r.reg() && cfft_rows_inv_fwd_reg(p.NX, a, r.T, Tn, p.opad, p.norm, r.sc, r.st)) || cfft_rows_inv_fwd(p.NX, a, r.T, Tn, p.twx, p.opad, p.norm, r.sc, r.st);
+  if ((p.inv.rows_mfma & 1) && cfft_rows_inv_mfma(p.NX, p.inv, out, r.T, p.opad, p.norm, r.sc, r.st)) return true;
+  if (r.reg() && cfft_rows_inv_reg(p.NX, p.inv, out, r.T, p.opad, p.norm, r.sc, r.st)) return true;
+  if (p.inv.win_scatter) return false;
+  return cfft_rows_inv(p.NX, p.inv, out, r.T, p.twx, p.opad, p.norm, r.sc, r.st);
+}
+const char* scale_refusal(const FftPlan& p, const FftScale* sc, const FftLink& k) {
+  if (p.np < 4) return nullptr;
+  if (!sc || !sc->tmax || !sc->winv) return "scaled operand forms need the scale words of the input and of the filter spectra";
+  if (k.t_next && !sc->tmax_next) return "a hand-over needs the scale words of the next layer";
+  return nullptr;
+}
+}  // namespace
+
+// The five passes on the map, on windows or on tiles (the refusals above say which combinations of link, layouts and operand form exist).
+hipError_t conv_fft_f32(FftPlan p, FftLayout in, FftLayout out, void* work, const FftLink& k, hipEvent_t g0, hipEvent_t g1, hipStream_t st, const FftScale* scp, const char** why) {
+  const int t16 = p.np >= 4 && scp ? scp->t16 : 0;
+  if (const char* no = p.map.tiles ? conv_fft_tiles_refusal(p, in, out, k) : conv_fft_refusal(p, in, out, k, t16)) return refuse(why, no);
+  if (const char* no = scale_refusal(p, scp, k)) return refuse(why, no);
+  if (hipError_t e = conv_fft_plan_twiddles(&p); e != hipSuccess) return e;
+  Run r{p, p.at<cf>(work, p.T), k.xs ? k.xs : p.at<void>(work, p.Xs), p.at<cf>(work, p.Yf), device_scale(p, scp, (float)p.col.H, work), 0.f, 0.f, st};
+  // a handed-over 16-bit T carries its scale words behind it (written by the producing layer's fused row kernel)
+  if (r.sc.t16 && k.t_in) r.sc.t16_fwd = conv_fft_handover16(p.col.B, p.NXH, p.col.H, p.col.Cin).words(k.t_in);
+  // 16-bit intermediates (bf16 handles, one-part route): the product spectra travel as complex fp16 too, under the constant shift of cgemm_split.hip
+  // (same-box A/B at 256 images: 19.1 -> 18.0 ms per step, profiles/r05_ab_y16.log)
+  r.yshift = r.sc.t16 ? cgemm_split_y16_shift(p.col.Cin) : 0.f;
+  r.yinv = r.yshift != 0.f ? 1.0f / r.yshift : 0.f;
+  if (!k.xs_ready) {
+    if (!k.t_in && !pass_rows_fwd(r, in, k.merge)) return not_launched(why, "no forward row kernel for this case");
+    if (!pass_cols_fwd(r, k.t_in ? static_cast<const cf*>(k.t_in) : r.T)) return not_launched(why, "no forward column kernel for this operand form and scale");
+  }
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (hipError_t e = pass_gemm(r, g0, g1); e != hipSuccess) return e;
+  if (!pass_cols_inv(r)) return not_launched(why, "no inverse column kernel for this case");
+  if (!pass_rows_inv(r, out, k)) return not_launched(why, p.inv.win_scatter ? "the scatter into the map exists in the register kernel only" : "no kernel for this hand-over");
   return hipGetLastError();
 }
-// geometry of the spectra for the weight-gradient kernels
-bool conv_fft_geometry(int H, int W, int ks, int B, int Cout, int np, int* NY, int* NX, int* MT, int circ) {
-  Sizes s;
-  if (!sizes_of(H, W, ks, &s, circ)) return false;
-  *NY = s.NY; *NX = s.NX; *MT = cgemm_split_mtile(np, B, Cout);
-  return true;
+
+// ---- the logits layer on the row spectra of its input (conv_fft_logits.hip).  No column pass, no filter spectra: the operand A (conv_fft_logits_pack), the
+// contraction and one inverse row pass.  p.map.wp = the operand A; link.t_in = T[kx][c/16][b][y][16] with its words sc.tmax.  The image's scale is 2^k with
+// tmax[b] 2^k < 2^15 (Fp16Scale::hf = 1: no column transform sums H rows), undone by the inverse row pass together with the operand's.
+hipError_t conv_fft_logits_f32(FftPlan p, int ks, int np, FftLayout in, FftLayout out, void* work, const FftLink& k, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
+                               const FftScale* scp, const char** why) {
+  if (const char* no = conv_fft_logits_refusal(p, ks, np, in, out, k, scp ? scp->common : 0)) return refuse(why, no);
+  if (const char* no = scale_refusal(p, scp, k)) return refuse(why, no);
+  if (hipError_t e = conv_fft_plan_twiddles(&p); e != hipSuccess) return e;
+  const Run r{p, p.at<cf>(work, p.T), nullptr, nullptr, device_scale(p, scp, 1.f, work), 0.f, 0.f, st};
+  if (g0 && hipEventRecord(g0, st) != hipSuccess) return hipErrorUnknown;
+  if (!cfft_logits_rows(p.NX, p.map, static_cast<const cf*>(k.t_in), p.map.wp, r.sc.tmax, r.T, st)) return not_launched(why, "no logits-rows kernel for this case");
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (g1 && hipEventRecord(g1, st) != hipSuccess) return hipErrorUnknown;
+  if (!pass_rows_inv(r, out, k, true)) return not_launched(why, "no inverse row kernel for this case");
+  return hipGetLastError();
+}
+
+// the split spectra of an NHWC fp32 tensor alone: passes 1 and 2
+hipError_t conv_fft_spectra(const FftArgs& a0, int ks, int np, void* work, void* xs, hipStream_t st, float* tmax, int common, const char** why) {
+  FftArgs a = a0;
+  a.tiles = 0;
+  FftPlan p = conv_fft_plan(a, ks, np);
+  if (!p.ok || !conv_fft_supported(a, ks, a.circ)) return refuse(why, "no transform size for this map and kernel size, or channels not in whole blocks of 64");
+  if (!xs || (np >= 4 && !tmax)) return refuse(why, "spectra need their buffer and, in the scaled operand forms, the scale word");
+  if (hipError_t e = conv_fft_plan_twiddles(&p); e != hipSuccess) return e;
+  FftScale in;
+  in.tmax = tmax; in.common = common;
+  const Run r{p, p.at<cf>(work, p.T), xs, nullptr, device_scale(p, &in, (float)a.H, work), 0.f, 0.f, st};
+  if (!pass_rows_fwd(r, kFftF32Nhwc, nullptr)) return not_launched(why, "no forward row kernel for this case");
+  if (!pass_cols_fwd(r, r.T)) return not_launched(why, "no forward column kernel for this operand form and scale");
+  return hipGetLastError();
 }
 
 }  // namespace jcm

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(colinv_threads<NY>()) void cols_inv_kernel(const cf
 }
 
 
-template <int NY> static hipError_t launch_cols_fwd(const ConvArgs& a, int np, const cf* T, void* Xs, const cf* tw, int NXH, int MT, const Fp16Scale& sc, hipStream_t st) {
+template <int NY> static bool launch_cols_fwd(const FftArgs& a, int np, const cf* T, void* Xs, const cf* tw, int NXH, int MT, const Fp16Scale& sc, hipStream_t st) {
   constexpr int IMG = colimg<NY>();
   constexpr int lds = (NY * IMG * 16 + NY) * (int)sizeof(cf);
   const int KC = a.Cin / 16, mtiles = (a.B + MT - 1) / MT;
@@ -174,44 +174,45 @@ template <int NY> static hipError_t launch_cols_fwd(const ConvArgs& a, int np, c
   const dim3 blk(colfwd_threads<NY>());
 #define COLS_FWD(KERNEL, ATTR, ...)                                                                              \
   do {                                                                                                           \
-    if (hipError_t e = ATTR.ensure(reinterpret_cast<const void*>(KERNEL), lds); e != hipSuccess) return e;        \
+    if (ATTR.ensure(reinterpret_cast<const void*>(KERNEL), lds) != hipSuccess) return false;                      \
     const dim3 grid((unsigned)persistent_grid(reinterpret_cast<const void*>(KERNEL), ntiles, (int)blk.x, lds));  \
     hipLaunchKernelGGL(KERNEL, grid, blk, lds, st, T, static_cast<uint4*>(Xs), tw, a.B, a.H, KC, MT, mtiles, __VA_ARGS__, ntiles); \
   } while (0)
   if (np == 5 && sc.t16_fwd) {
-    if (!sc.tmax || (KC & 3)) return hipErrorInvalidValue;
+    if (!sc.tmax || (KC & 3)) return false;
     COLS_FWD((cols_fwd_split_kernel<NY, 5, true>), attr5h, sc.tmax, sc.common, sc.t16_fwd);
   } else if (np == 5) {
-    if (!sc.tmax || (KC & 1)) return hipErrorInvalidValue;
+    if (!sc.tmax || (KC & 1)) return false;
     COLS_FWD((cols_fwd_split_kernel<NY, 5>), attr5, sc.tmax, sc.common, (const float*)nullptr);
   } else if (np == 2) {
     COLS_FWD((cols_fwd_split_kernel<NY, 2>), attr2, (const float*)nullptr, 0, (const float*)nullptr);
   } else if (np == 4) {
-    if (!sc.tmax) return hipErrorInvalidValue;
+    if (!sc.tmax) return false;
     COLS_FWD((cols_fwd_split_kernel<NY, 4>), attr4, sc.tmax, sc.common, (const float*)nullptr);
   } else {
-    return hipErrorInvalidValue;
+    return false;
   }
 #undef COLS_FWD
-  return hipSuccess;
+  return true;
 }
 // a.CoutP = output channels the inverse passes transform (Cout padded to 64); ldy = channel stride of Yf (Cout padded to the GEMM's N tile)
-template <int NY> static void launch_cols_inv(const ConvArgs& a, const cf* Yf, cf* T, const cf* tw, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv) {
+template <int NY> static void launch_cols_inv(const FftArgs& a, const cf* Yf, cf* T, const cf* tw, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv) {
   const dim3 grid(a.B * NXH * (a.CoutP / colblk<NY>())), blk(colinv_threads<NY>());
   if (t16) hipLaunchKernelGGL((cols_inv_kernel<NY, true>), grid, blk, 0, st, Yf, T, tw, a.B, a.H, NXH, a.CoutP, ldy, pad, t16, y16_inv);      // (y16_inv != 0: conv_fft.hip)
   else hipLaunchKernelGGL((cols_inv_kernel<NY, false>), grid, blk, 0, st, Yf, T, tw, a.B, a.H, NXH, a.CoutP, ldy, pad, nullptr, 0.f);
 }
-hipError_t cfft_cols_fwd(int NY, const ConvArgs& a, int np, const cf* T, void* Xs, const cf* tw, int NXH, int MT, const Fp16Scale& sc, hipStream_t st) {
-  hipError_t e = hipSuccess;
+bool cfft_cols_fwd(int NY, const FftArgs& a, int np, const cf* T, void* Xs, const cf* tw, int NXH, int MT, const Fp16Scale& sc, hipStream_t st) {
+  bool e = false;
 #define CALL(N) e = launch_cols_fwd<N>(a, np, T, Xs, tw, NXH, MT, sc, st)
   CFFT_BY_SIZE(NY, CALL)
 #undef CALL
   return e;
 }
-void cfft_cols_inv(int NY, const ConvArgs& a, const cf* Yf, cf* T, const cf* tw, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv) {
+bool cfft_cols_inv(int NY, const FftArgs& a, const cf* Yf, cf* T, const cf* tw, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv) {
 #define CALL(N) launch_cols_inv<N>(a, Yf, T, tw, NXH, ldy, pad, st, t16, y16_inv)
   CFFT_BY_SIZE(NY, CALL)
 #undef CALL
+  return true;
 }
 
 }  // namespace cfft

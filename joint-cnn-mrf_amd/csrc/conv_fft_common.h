@@ -1,4 +1,5 @@
-// Shared by the translation units of the frequency-domain convolution (conv_fft.hip: host side + filter spectra; conv_fft_rows_fwd.hip,
+// Shared by the translation units of the frequency-domain convolution (conv_fft.hip: filter spectra + host side -- the plan of conv_fft_plan.h, the refusals, the
+// five pass functions and the runners; conv_fft_rows_fwd.hip,
 // conv_fft_rows_inv.hip, conv_fft_rows_fused.hip, conv_fft_cols.hip: the LDS transform kernels; conv_fft_reg_inv.hip, conv_fft_reg_fwd.hip,
 // conv_fft_reg_fused.hip, conv_fft_reg_tiles.hip: the register ones (fft_reg_rows.h) -- one file per pass so that they compile in parallel): radix plans,
 // the channel-vectorised in-LDS FFT stages, the bf16 operand split, and the size-dispatching launchers each file exports.
@@ -303,45 +304,47 @@ __device__ __forceinline__ void split8(const float (&x)[8], uint4 (&out)[NP]) {
 int persistent_grid(const void* kernel, int ntiles, int threads, int dyn_lds = 0);      // dyn_lds: the launch's dynamic LDS bytes
 
 // ---- launchers (N = transform length, one of the lengths with a Plan); a.CoutP = output channels the inverse passes transform (Cout
-// padded to 64), ldy = channel stride of the product spectra (Cout padded to the GEMM's N tile)
-// sc: the fp16 scaling of np = 4 (tmax written by the forward row passes, read by the column pass and the inverse row passes); all null otherwise
+// padded to 64), ldy = channel stride of the product spectra (Cout padded to the GEMM's N tile).  The pass functions of conv_fft.hip choose among them.
+// Every launcher answers the same way: true = launched; false = nothing launched -- no kernel of this family for the case, or a HIP call in front of the launch
+// failed (hipGetLastError() then says which).  The caller asks hipGetLastError() behind the launches either way.
+// sc: the fp16 scaling of np = 4 / 5 (tmax written by the forward row passes, read by the column pass and the inverse row passes); all null otherwise
 // t16 (every launcher): the tile scale words of a 16-bit T / T' (null: complex fp32)
-void cfft_rows_fwd(int NX, const ConvArgs& a, int layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16 = nullptr);
-void cfft_rows_fwd_merge(int NX, const ConvArgs& a, const FftMerge& m, int in_layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16 = nullptr);      // in_layout 0 / 1: NHWC fp32 / bf16
-hipError_t cfft_cols_fwd(int NY, const ConvArgs& a, int np, const cf* T, void* Xs, const cf* tw, int NXH, int MT, const Fp16Scale& sc, hipStream_t st);
+// -- the LDS kernels: every length, every layout
+bool cfft_rows_fwd(int NX, const FftArgs& a, FftLayout layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16 = nullptr);
+bool cfft_rows_fwd_merge(int NX, const FftArgs& a, const FftMerge& m, FftLayout in_layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16 = nullptr);      // NHWC fp32 / bf16
+bool cfft_cols_fwd(int NY, const FftArgs& a, int np, const cf* T, void* Xs, const cf* tw, int NXH, int MT, const Fp16Scale& sc, hipStream_t st);
 // y16_inv (with t16 only): Yf holds complex fp16 products times a power of two (cgemm_split.hip); y16_inv = its inverse.  0: complex fp32
-void cfft_cols_inv(int NY, const ConvArgs& a, const cf* Yf, cf* T, const cf* tw, int NXH, int ldy, int pad, hipStream_t st, float* t16 = nullptr, float y16_inv = 0.f);
-void cfft_rows_inv(int NX, const ConvArgs& a, int layout, const cf* T, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
-// the same pass with the transform in the registers of two threads per channel pair (conv_fft_reg_*.hip, fft_reg_rows.h); false: no such kernel for this case
-bool cfft_rows_inv_reg(int NX, const ConvArgs& a, int layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
-bool cfft_rows_inv_fwd_reg(int NX, const ConvArgs& a, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
-bool cfft_rows_fwd_reg(int NX, const ConvArgs& a, int layout, cf* T, float* tmax, hipStream_t st, float* t16);
-// 32 x 32 overlap-save windows read straight from the map they are cut from (a.win_map, fp32 NHWC; Cin % 128 == 0): false = no such kernel
-bool cfft_rows_fwd_win_reg(int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st);
+bool cfft_cols_inv(int NY, const FftArgs& a, const cf* Yf, cf* T, const cf* tw, int NXH, int ldy, int pad, hipStream_t st, float* t16 = nullptr, float y16_inv = 0.f);
+bool cfft_rows_inv(int NX, const FftArgs& a, FftLayout layout, const cf* T, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
+bool cfft_rows_inv_fwd(int NX, const FftArgs& a, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
+// -- the same passes with the transform in the registers of two threads per channel pair (conv_fft_reg_*.hip, fft_reg_rows.h), at the model's sizes
+bool cfft_rows_inv_reg(int NX, const FftArgs& a, FftLayout layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
+bool cfft_rows_inv_fwd_reg(int NX, const FftArgs& a, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
+bool cfft_rows_fwd_reg(int NX, const FftArgs& a, FftLayout layout, cf* T, float* tmax, hipStream_t st, float* t16);
+// 32 x 32 overlap-save windows read straight from the map they are cut from (a.win_map, fp32 NHWC; Cin % 128 == 0)
+bool cfft_rows_fwd_win_reg(int NX, const FftArgs& a, cf* T, float* tmax, hipStream_t st);
 bool cfft_rows_fwd_win_reg_supported(int NX, int Cin);
-// 2 x 2 tiles of a 5x5 layer's map (ConvArgs::tiles, conv_fft_reg_tiles.hip): NY x NX = the tiles' transform; a = the layer on the whole map
-bool cfft_tiles_supported(int NY, int NX, const ConvArgs& a);
-bool cfft_rows_fwd_tile_reg(int NY, int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st);
-bool cfft_rows_inv_pool_tile_reg(int NY, int NX, const ConvArgs& a, const cf* T, cf* Tn, float norm, const Fp16Scale& sc, hipStream_t st);
-bool cfft_rows_fwd_merge_reg(int NX, const ConvArgs& a, const FftMerge& m, int in_layout, cf* T, float* tmax, hipStream_t st, float* t16);
-bool cfft_cols_inv_reg(int NY, const ConvArgs& a, const cf* Yf, cf* T, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv = 0.f);
-void cfft_rows_inv_fwd(int NX, const ConvArgs& a, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
-// conv_fft_rows_fused.hip: inverse rows + epilogue + 2x2 max pool + forward rows of the pooled map (NXO points, twiddles two) / + branch merge + forward rows.
-// false: no kernel for this case
-bool cfft_rows_inv_pool_fwd(int NXI, int NXO, const ConvArgs& a, const cf* T, cf* Tn, const cf* twi, const cf* two, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
-bool cfft_rows_inv_merge_fwd(int NX, const ConvArgs& a, const FftMerge& m, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
+// 2 x 2 tiles of a 5x5 layer's map (FftArgs::tiles, conv_fft_reg_tiles.hip): NY x NX = the tiles' transform; a = the layer on the whole map
+bool cfft_tiles_supported(int NY, int NX, const FftArgs& a);
+bool cfft_rows_fwd_tile_reg(int NY, int NX, const FftArgs& a, cf* T, float* tmax, hipStream_t st);
+bool cfft_rows_inv_pool_tile_reg(int NY, int NX, const FftArgs& a, const cf* T, cf* Tn, float norm, const Fp16Scale& sc, hipStream_t st);
+bool cfft_rows_fwd_merge_reg(int NX, const FftArgs& a, const FftMerge& m, FftLayout in_layout, cf* T, float* tmax, hipStream_t st, float* t16);
+bool cfft_cols_inv_reg(int NY, const FftArgs& a, const cf* Yf, cf* T, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv = 0.f);
+// -- conv_fft_rows_fused.hip: inverse rows + epilogue + 2x2 max pool + forward rows of the pooled map (NXO points, twiddles two) / + branch merge + forward rows
+bool cfft_rows_inv_pool_fwd(int NXI, int NXO, const FftArgs& a, const cf* T, cf* Tn, const cf* twi, const cf* two, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
+bool cfft_rows_inv_merge_fwd(int NX, const FftArgs& a, const FftMerge& m, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
 // conv_fft_reg_fused.hip: the model's geometry in registers; t16n != null: bf16 handles (16-bit T' in, 16-bit T + its scale words t16n out, bf16 coarse branches)
-bool cfft_rows_inv_merge_fwd_reg(int NX, const ConvArgs& a, const FftMerge& m, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st, float* t16n = nullptr);
+bool cfft_rows_inv_merge_fwd_reg(int NX, const FftArgs& a, const FftMerge& m, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st, float* t16n = nullptr);
 bool cfft_rows_inv_merge_fwd_reg_supported(int NX, const ConvArgs& a, const FftMerge& m, int pad);
 bool cfft_rows_inv_pool_fwd_supported(int NXI, int NXO, int Cout);
-// conv_fft_rows_mfma.hip: the 96-point inverse row pass of bf16 handles (16-bit T', planar bf16 output) as a matrix product on the matrix cores; false: no kernel for this case
-bool cfft_rows_inv_mfma(int NX, const ConvArgs& a, int layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
+// conv_fft_rows_mfma.hip: the 96-point inverse row pass of bf16 handles (16-bit T', planar bf16 output) as a matrix product on the matrix cores
+bool cfft_rows_inv_mfma(int NX, const FftArgs& a, FftLayout layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st);
 bool cfft_rows_inv_merge_fwd_supported(int NX, const ConvArgs& a, const FftMerge& m);
 // conv_fft_logits.hip: the logits layer contracted on the row spectra of its input (fp32 handles, 96-point rows, H <= 64, Cout <= 16): the operand
 // A[kx][dy][ci][j] (two fp16 parts, wscale as conv_fft_pack_weights) and S = T'[b][y][kx][64] for the inverse row pass, scaled by fp16_scale(tmax[b], 1)
-bool cfft_logits_rows_supported(int NX, const ConvArgs& a);
+bool cfft_logits_rows_supported(int NX, const FftArgs& a);
 size_t cfft_logits_rows_operand_bytes(int NX, int Cin);
-hipError_t cfft_logits_rows_pack(int NX, const float* w_hwio, void* aop, int Cin, int Cout, float* wscale, hipStream_t st);
-hipError_t cfft_logits_rows(int NX, const ConvArgs& a, const cf* T, const void* aop, const float* tmax, cf* S, hipStream_t st);
+bool cfft_logits_rows_pack(int NX, const float* w_hwio, void* aop, int Cin, int Cout, float* wscale, hipStream_t st);
+bool cfft_logits_rows(int NX, const FftArgs& a, const cf* T, const void* aop, const float* tmax, cf* S, hipStream_t st);
 }  // namespace cfft
 }  // namespace jcm

@@ -183,21 +183,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
 }
 
-bool cfft_logits_rows_supported(int NX, const ConvArgs& a) { return NX == 96 && a.H >= 1 && a.H <= 64 && a.Cin % 16 == 0 && a.Cout >= 1 && a.Cout <= 16 && a.B >= 1; }
+bool cfft_logits_rows_supported(int NX, const FftArgs& a) { return NX == 96 && a.H >= 1 && a.H <= 64 && a.Cin % 16 == 0 && a.Cout >= 1 && a.Cout <= 16 && a.B >= 1; }
 size_t cfft_logits_rows_operand_bytes(int NX, int Cin) { return (size_t)(NX / 2 + 1) * 9 * (Cin / 16) * 4 * 64 * sizeof(uint4); }
-hipError_t cfft_logits_rows_pack(int NX, const float* w_hwio, void* aop, int Cin, int Cout, float* wscale, hipStream_t st) {
+bool cfft_logits_rows_pack(int NX, const float* w_hwio, void* aop, int Cin, int Cout, float* wscale, hipStream_t st) {
   const dim3 grid((unsigned)((9 * (Cin / 16) * 64 + 255) / 256), (unsigned)(NX / 2 + 1));
   hipLaunchKernelGGL(logits_rows_operand_kernel, grid, dim3(256), 0, st, w_hwio, static_cast<uint4*>(aop), Cin, Cout, NX, wscale);
-  return hipGetLastError();
+  return true;
 }
-hipError_t cfft_logits_rows(int NX, const ConvArgs& a, const cf* T, const void* aop, const float* tmax, cf* S, hipStream_t st) {
-  if (!cfft_logits_rows_supported(NX, a)) return hipErrorInvalidValue;
+bool cfft_logits_rows(int NX, const FftArgs& a, const cf* T, const void* aop, const float* tmax, cf* S, hipStream_t st) {
+  if (!cfft_logits_rows_supported(NX, a)) return false;
   static LdsAttr attr;
-  if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(logits_rows_kernel), kLrLds); e != hipSuccess) return e;
+  if (attr.ensure(reinterpret_cast<const void*>(logits_rows_kernel), kLrLds) != hipSuccess) return false;
   const int NXH = NX / 2 + 1, items = NXH * a.B, per = (items + 7) / 8;
   hipLaunchKernelGGL(logits_rows_kernel, dim3((unsigned)(per * 8)), dim3(512), kLrLds, st, reinterpret_cast<const float4*>(T), static_cast<const uint4*>(aop), tmax, S, a.B, a.H,
                      a.Cin / 16, NXH, per);
-  return hipGetLastError();
+  return true;
 }
 
 }  // namespace cfft

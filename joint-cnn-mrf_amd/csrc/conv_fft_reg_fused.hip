@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   fwd_rows_store_f32<NX>(uu, h, Tn, TRowDst(p, b, y, B, H, C), sc.tmax_next, b);      // + the next layer's per-image word (max |T|) of its spectra's scale
 }
 // true: launched (96-point rows, pad 2 or 4, whole 64-channel blocks)
-bool cfft_rows_inv_fwd_reg(int NX, const ConvArgs& a, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv_fwd_reg(int NX, const FftArgs& a, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   if (NX != 96 || (pad != 2 && pad != 4) || a.Cout % 64 || a.W > NX) return false;
   const int nrows = a.B * a.H;
   const size_t threads = (size_t)nrows * a.Cout;
@@ -198,7 +198,7 @@ bool cfft_rows_inv_merge_fwd_reg_supported(int NX, const ConvArgs& a, const FftM
   return (size_t)m.H2 * m.W2 * a.Cout * 4 < (size_t)1 << 31;      // one buffer descriptor per coarse image
 }
 // t16n: null = fp32 handles (T', T complex fp32; x2, x3 fp32 NHWC); else the scale words of the 16-bit T written here (bf16 handles: T' 16-bit with sc.t16_inv, x2 / x3 bf16 NHWC)
-bool cfft_rows_inv_merge_fwd_reg(int NX, const ConvArgs& a, const FftMerge& m, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st, float* t16n) {
+bool cfft_rows_inv_merge_fwd_reg(int NX, const FftArgs& a, const FftMerge& m, const cf* T, cf* Tn, int pad, float norm, const Fp16Scale& sc, hipStream_t st, float* t16n) {
   if (!cfft_rows_inv_merge_fwd_reg_supported(NX, a, m, pad) || ((t16n != nullptr) != (sc.t16_inv != nullptr))) return false;
   const int nrows = a.B * a.H;
   const size_t threads = a.Cout == 512 ? (size_t)((nrows + 3) / 4) * 8 * 256 : (size_t)nrows * a.Cout;      // (512 channels: eight work groups per four rows)

@@ -31,8 +31,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NX >= 96 ? 
   fwd_rows_finish<NX>(raw, T, h, p, b, y, B, H, C, tmax, t16);
 }
 // true: launched (96- / 50- / 28-point rows of a bf16 NHWC tensor -- the 60 x 90, 30 x 45 and 15 x 23 maps --, 16-bit T; W <= NX)
-bool cfft_rows_fwd_reg(int NX, const ConvArgs& a, int layout, cf* T, float* tmax, hipStream_t st, float* t16) {
-  if ((NX != 96 && NX != 50 && NX != 28) || layout != 1 || !t16 || a.Cin % 64 || a.W > NX) return false;
+bool cfft_rows_fwd_reg(int NX, const FftArgs& a, FftLayout layout, cf* T, float* tmax, hipStream_t st, float* t16) {
+  if ((NX != 96 && NX != 50 && NX != 28) || layout != kFftBf16Nhwc || !t16 || a.Cin % 64 || a.W > NX) return false;
   const int nrows = a.B * a.H;
   const size_t threads = (size_t)nrows * a.Cin;      // two threads per channel pair
   const dim3 grid((unsigned)((threads + 255) / 256)), blk(256);
@@ -92,13 +92,13 @@ __global__ __launch_bounds__(256) void rows_fwd_win_reg_kernel(const float* __re
   wave_max_to_word(m, tmax, bw);      // the window's word of the spectra's scale
 }
 bool cfft_rows_fwd_win_reg_supported(int NX, int Cin) { return NX == 32 && Cin % 128 == 0; }
-bool cfft_rows_fwd_win_reg(int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st) {
-  if (!a.win_map || !cfft_rows_fwd_win_reg_supported(NX, a.Cin) || a.H != NX || a.W != NX || a.B != a.win_B * a.win_TY * a.win_TX) return false;
-  if ((size_t)a.win_W * a.Cin * 4 >= (size_t)1 << 31) return false;
+bool cfft_rows_fwd_win_reg(int NX, const FftArgs& a, cf* T, float* tmax, hipStream_t st) {
+  if (!a.win_map || !cfft_rows_fwd_win_reg_supported(NX, a.Cin) || a.H != NX || a.W != NX || a.B != a.win.BW()) return false;
+  if ((size_t)a.win.W * a.Cin * 4 >= (size_t)1 << 31) return false;
   const int nrows = a.B * NX;
   const size_t threads = (size_t)nrows * (a.Cin / 2);
   hipLaunchKernelGGL(rows_fwd_win_reg_kernel<32>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(a.win_map), reinterpret_cast<float4*>(T), nrows, a.B,
-                     a.win_H, a.win_W, a.Cin, a.win_TY, a.win_TX, a.win_valid_only, tmax);
+                     a.win.H, a.win.W, a.Cin, a.win.TY, a.win.TX, a.win_valid_only, tmax);
   return true;
 }
 
@@ -195,8 +195,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   fwd_rows_finish<NX>(raw, T, h, p, b, y, B, H, C, tmax, t16);
 }
 // true: launched (the model's merge on a bf16 handle with 16-bit T: 90-column maps, x2 at half and x3 at a quarter of the width)
-bool cfft_rows_fwd_merge_reg(int NX, const ConvArgs& a, const FftMerge& m, int in_layout, cf* T, float* tmax, hipStream_t st, float* t16) {
-  if (NX != 96 || in_layout != 1 || !t16 || a.Cin % 64 || a.W != 90 || m.W2 != 45 || m.W3 != 23 || m.H2 < 1 || m.H3 < 1) return false;
+bool cfft_rows_fwd_merge_reg(int NX, const FftArgs& a, const FftMerge& m, FftLayout in_layout, cf* T, float* tmax, hipStream_t st, float* t16) {
+  if (NX != 96 || in_layout != kFftBf16Nhwc || !t16 || a.Cin % 64 || a.W != 90 || m.W2 != 45 || m.W3 != 23 || m.H2 < 1 || m.H3 < 1) return false;
   const int nrows = a.B * a.H;
   const size_t threads = a.Cin == 512 ? (size_t)((nrows + 3) / 4) * 8 * 256 : (size_t)nrows * a.Cin;      // (512 channels: eight work groups per four rows)
   hipLaunchKernelGGL((rows_fwd_merge_reg_kernel<96, 90, 23>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, static_cast<const unsigned*>(a.x), static_cast<const unsigned*>(m.x2), m.H2,

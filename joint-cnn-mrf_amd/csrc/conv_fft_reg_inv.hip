@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NY >= 64 ? 
   }
 }
 // true: launched (64-point columns, 64-channel tiles)
-bool cfft_cols_inv_reg(int NY, const ConvArgs& a, const cf* Yf, cf* T, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv) {
+bool cfft_cols_inv_reg(int NY, const FftArgs& a, const cf* Yf, cf* T, int NXH, int ldy, int pad, hipStream_t st, float* t16, float y16_inv) {
   if (a.CoutP % 64 || ((y16_inv != 0.f) != (t16 != nullptr)) || (t16 && ldy % 2)) return false;      // 16-bit T' comes with fp16 product spectra
   const size_t threads = (size_t)a.B * NXH * a.CoutP;
   const dim3 grid((unsigned)((threads + 255) / 256)), blk(256);
@@ -168,27 +168,28 @@ bool cfft_cols_inv_reg(int NY, const ConvArgs& a, const cf* Yf, cf* T, int NXH, 
   return true;
 }
 
-template <int NX> static bool launch_rows_inv_reg(const ConvArgs& a, int layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+template <int NX> static bool launch_rows_inv_reg(const FftArgs& a, FftLayout layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   const int nrows = a.B * a.H;
-  if (a.wout_TX > 0 && (layout != 0 || sc.t16_inv)) return false;      // the scatter of overlap-save windows exists for fp32 outputs
+  if (a.win_scatter && (layout != kFftF32Nhwc || sc.t16_inv)) return false;      // the scatter of overlap-save windows exists for fp32 outputs
   if ((a.Cout & 1) || a.CoutP % 64) return false;      // channel pairs are stored as one word; a wave = 32 pairs of ONE row (the kernel keeps the row in scalar registers)
   const size_t threads = (size_t)nrows * a.CoutP;      // two threads per channel pair
   const dim3 grid((unsigned)((threads + 255) / 256)), blk(256);
   const bool h16 = sc.t16_inv != nullptr;
-#define RR_LAUNCH(L, H16) hipLaunchKernelGGL((rows_inv_reg_kernel<NX, L, H16>), grid, blk, 0, st, T, a.out, a.bias, a.scale, a.shift, a.relu_bn, nrows, a.H, a.W, a.CoutP, a.Cout, pad, norm, sc, a.wout_H, a.wout_W, a.wout_TY, a.wout_TX)
-  if (layout == 0 && !h16) RR_LAUNCH(0, false);
-  else if (layout == 1 && h16 && a.Cout % 8 == 0) RR_LAUNCH(1, true);
-  else if (layout == 1 && a.Cout % 8 == 0) RR_LAUNCH(1, false);
-  else if (layout == 2 && h16 && a.Cout % 8 == 0) RR_LAUNCH(2, true);
-  else if (layout == 2 && a.Cout % 8 == 0) RR_LAUNCH(2, false);
+  const WinGeom wout = a.win_scatter ? a.win : WinGeom{};      // TY = 0: the kernel stores the batch of valid regions
+#define RR_LAUNCH(L, H16) hipLaunchKernelGGL((rows_inv_reg_kernel<NX, L, H16>), grid, blk, 0, st, T, a.out, a.bias, a.scale, a.shift, a.relu_bn, nrows, a.H, a.W, a.CoutP, a.Cout, pad, norm, sc, wout.H, wout.W, wout.TY, wout.TX)
+  if (layout == kFftF32Nhwc && !h16) RR_LAUNCH(0, false);
+  else if (layout == kFftBf16Nhwc && h16 && a.Cout % 8 == 0) RR_LAUNCH(1, true);
+  else if (layout == kFftBf16Nhwc && a.Cout % 8 == 0) RR_LAUNCH(1, false);
+  else if (layout == kFftBf16Planar && h16 && a.Cout % 8 == 0) RR_LAUNCH(2, true);
+  else if (layout == kFftBf16Planar && a.Cout % 8 == 0) RR_LAUNCH(2, false);
   else return false;
 #undef RR_LAUNCH
   return true;
 }
 // true: launched.  false: no register kernel for this (length, layout) -- the caller takes the LDS kernel.
-bool cfft_rows_inv_reg(int NX, const ConvArgs& a, int layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv_reg(int NX, const FftArgs& a, FftLayout layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   if (NX == 96) return launch_rows_inv_reg<96>(a, layout, T, pad, norm, sc, st);
-  if (NX == 32 && layout == 0) return launch_rows_inv_reg<32>(a, layout, T, pad, norm, sc, st);      // the training step's overlap-save windows (fp32)
+  if (NX == 32 && layout == kFftF32Nhwc) return launch_rows_inv_reg<32>(a, layout, T, pad, norm, sc, st);      // the training step's overlap-save windows (fp32)
   if (NX == 50) return launch_rows_inv_reg<50>(a, layout, T, pad, norm, sc, st);      // the half- and quarter-resolution branches (36 x 50, 20 x 28 transforms)
   if (NX == 28) return launch_rows_inv_reg<28>(a, layout, T, pad, norm, sc, st);
   return false;

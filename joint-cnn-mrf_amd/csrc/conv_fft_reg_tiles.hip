@@ -137,11 +137,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   fwd_rows_store_f32<NX>(uu, h, Tn, TRowDst(p, b, r, B, Ht, C), sc.tmax_next, b);      // + the next layer's per-IMAGE word
 }
 // a: the layer on the whole Hm x Wm map (a.B images); NY x NX: the tiles' transform.  Model geometry only: 90-column tiles, 96-point rows.
-bool cfft_tiles_supported(int NY, int NX, const ConvArgs& a) {
+bool cfft_tiles_supported(int NY, int NX, const FftArgs& a) {
   return NX == 96 && NY == 64 && a.W == 180 && a.H % 4 == 0 && a.H / 2 + 4 <= NY && a.Cin % 64 == 0 && a.Cout % 64 == 0 &&
          (size_t)a.W * a.Cin * 4 < (size_t)1 << 31;
 }
-bool cfft_rows_fwd_tile_reg(int NY, int NX, const ConvArgs& a, cf* T, float* tmax, hipStream_t st) {
+bool cfft_rows_fwd_tile_reg(int NY, int NX, const FftArgs& a, cf* T, float* tmax, hipStream_t st) {
   if (!cfft_tiles_supported(NY, NX, a)) return false;
   const int nrows = 4 * a.B * NY;
   const size_t threads = (size_t)nrows * a.Cin;      // two threads per channel pair
@@ -150,7 +150,7 @@ bool cfft_rows_fwd_tile_reg(int NY, int NX, const ConvArgs& a, cf* T, float* tma
   return true;
 }
 // T: T'[b'][y][kx][c] of the 4 B tiles (Ht valid rows each, the inverse column pass); Tn: the next layer's T of the pooled Ht x Wt map of B images
-bool cfft_rows_inv_pool_tile_reg(int NY, int NX, const ConvArgs& a, const cf* T, cf* Tn, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv_pool_tile_reg(int NY, int NX, const FftArgs& a, const cf* T, cf* Tn, float norm, const Fp16Scale& sc, hipStream_t st) {
   if (!cfft_tiles_supported(NY, NX, a)) return false;
   const int Ht = a.H / 2, nrows = a.B * Ht;
   const size_t threads = (size_t)nrows * a.Cout;

@@ -291,7 +291,7 @@ bool cfft_rows_inv_merge_fwd_supported(int NX, const ConvArgs& a, const FftMerge
   return m.W2 <= (kMergeKC / 3) * XP && m.W3 <= (kMergeKC / 6) * XP && (size_t)m.H2 * m.W2 * a.Cout * 4 < (size_t)1 << 31;
 }
 // true: launched.  a: the producing layer (conv2) on its H x W map; NXO: row length of the pooled map's transform; two: twiddles of that length
-bool cfft_rows_inv_pool_fwd(int NXI, int NXO, const ConvArgs& a, const cf* T, cf* Tn, const cf* twi, const cf* two, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv_pool_fwd(int NXI, int NXO, const FftArgs& a, const cf* T, cf* Tn, const cf* twi, const cf* two, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   if (!cfft_rows_inv_pool_fwd_supported(NXI, NXO, a.Cout)) return false;
   const int Ho = (a.H + 1) / 2;
   const int ntiles = a.B * Ho * (a.Cout / CB);
@@ -311,7 +311,7 @@ bool cfft_rows_inv_pool_fwd(int NXI, int NXO, const ConvArgs& a, const cf* T, cf
 }
 
 // true: launched.  a: the producing layer (conv4_fullres); m: the coarse branches (fp32 NHWC)
-bool cfft_rows_inv_merge_fwd(int NX, const ConvArgs& a, const FftMerge& m, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv_merge_fwd(int NX, const FftArgs& a, const FftMerge& m, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   if (!cfft_rows_inv_merge_fwd_supported(NX, a, m)) return false;
   constexpr int KC = kMergeKC;
   const int dyn = kMergeKC * rows_threads<96>() * (int)sizeof(cf);

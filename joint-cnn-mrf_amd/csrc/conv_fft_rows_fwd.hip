@@ -168,7 +168,7 @@ __global__ __launch_bounds__(rows_threads<NX>()) void rows_fwd_merge_kernel(cons
 }
 
 
-template <int NX> static void launch_rows_fwd(const ConvArgs& a, int layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
+template <int NX> static void launch_rows_fwd(const FftArgs& a, FftLayout layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
   const int ntiles = a.B * a.H * (a.Cin / CB);
   const dim3 blk(rows_threads<NX>());
 #define RF_LAUNCH(L, H16)                                                                                                              \
@@ -176,30 +176,32 @@ template <int NX> static void launch_rows_fwd(const ConvArgs& a, int layout, cf*
     const dim3 grid(persistent_grid(reinterpret_cast<const void*>(rows_fwd_kernel<NX, L, H16>), ntiles, rows_threads<NX>()));          \
     hipLaunchKernelGGL((rows_fwd_kernel<NX, L, H16>), grid, blk, 0, st, a.x, T, tw, a.B, a.H, a.W, a.Cin, ntiles, tmax, t16);          \
   } while (0)
-  if (layout == 0) RF_LAUNCH(0, false);      // (fp32 handles keep T in fp32)
-  else if (layout == 1) { if (t16) RF_LAUNCH(1, true); else RF_LAUNCH(1, false); }
+  if (layout == kFftF32Nhwc) RF_LAUNCH(0, false);      // (fp32 handles keep T in fp32)
+  else if (layout == kFftBf16Nhwc) { if (t16) RF_LAUNCH(1, true); else RF_LAUNCH(1, false); }
   else { if (t16) RF_LAUNCH(2, true); else RF_LAUNCH(2, false); }
 #undef RF_LAUNCH
 }
-template <int NX> static void launch_rows_fwd_merge(const ConvArgs& a, const FftMerge& m, int in_layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
+template <int NX> static void launch_rows_fwd_merge(const FftArgs& a, const FftMerge& m, FftLayout in_layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
   const dim3 grid(a.B * a.H * (a.Cin / CB)), blk(rows_threads<NX>());
   const float sy2 = (float)m.H2 / (float)a.H, sx2 = (float)m.W2 / (float)a.W, sy3 = (float)m.H3 / (float)a.H, sx3 = (float)m.W3 / (float)a.W;
-  if (in_layout == 1 && t16)
+  if (in_layout == kFftBf16Nhwc && t16)
     hipLaunchKernelGGL((rows_fwd_merge_kernel<NX, true, true>), grid, blk, 0, st, a.x, m.x2, m.H2, m.W2, m.x3, m.H3, m.W3, T, tw, a.B, a.H, a.W, a.Cin, sy2, sx2, sy3, sx3, tmax, t16);
-  else if (in_layout == 1)
+  else if (in_layout == kFftBf16Nhwc)
     hipLaunchKernelGGL((rows_fwd_merge_kernel<NX, true>), grid, blk, 0, st, a.x, m.x2, m.H2, m.W2, m.x3, m.H3, m.W3, T, tw, a.B, a.H, a.W, a.Cin, sy2, sx2, sy3, sx3, tmax, nullptr);
   else
     hipLaunchKernelGGL((rows_fwd_merge_kernel<NX, false>), grid, blk, 0, st, a.x, m.x2, m.H2, m.W2, m.x3, m.H3, m.W3, T, tw, a.B, a.H, a.W, a.Cin, sy2, sx2, sy3, sx3, tmax, nullptr);
 }
-void cfft_rows_fwd(int NX, const ConvArgs& a, int layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
+bool cfft_rows_fwd(int NX, const FftArgs& a, FftLayout layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
 #define CALL(N) launch_rows_fwd<N>(a, layout, T, tw, tmax, st, t16)
   CFFT_BY_SIZE(NX, CALL)
 #undef CALL
+  return true;
 }
-void cfft_rows_fwd_merge(int NX, const ConvArgs& a, const FftMerge& m, int in_layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
+bool cfft_rows_fwd_merge(int NX, const FftArgs& a, const FftMerge& m, FftLayout in_layout, cf* T, const cf* tw, float* tmax, hipStream_t st, float* t16) {
 #define CALL(N) launch_rows_fwd_merge<N>(a, m, in_layout, T, tw, tmax, st, t16)
   CFFT_BY_SIZE(NX, CALL)
 #undef CALL
+  return true;
 }
 
 }  // namespace cfft

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(rows_threads<NX>()) void rows_inv_fwd_kernel(const 
   }
 }
 
-template <int NX> static void launch_rows_inv(const ConvArgs& a, int layout, const cf* T, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+template <int NX> static void launch_rows_inv(const FftArgs& a, FftLayout layout, const cf* T, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   const int ntiles = a.B * a.H * (a.CoutP / CB);
   const dim3 blk(rows_threads<NX>());
 #define RI_LAUNCH(L, H16)                                                                                                                                           \
@@ -248,25 +248,27 @@ template <int NX> static void launch_rows_inv(const ConvArgs& a, int layout, con
     hipLaunchKernelGGL((rows_inv_kernel<NX, L, H16>), grid, blk, 0, st, T, a.out, tw, a.bias, a.scale, a.shift, a.relu_bn, a.H, a.W, a.CoutP, a.Cout, pad, norm, ntiles, sc); \
   } while (0)
   const bool h16 = sc.t16_inv != nullptr;
-  if (layout == 0) RI_LAUNCH(0, false);      // (fp32 handles keep T' in fp32)
-  else if (layout == 1) { if (h16) RI_LAUNCH(1, true); else RI_LAUNCH(1, false); }
+  if (layout == kFftF32Nhwc) RI_LAUNCH(0, false);      // (fp32 handles keep T' in fp32)
+  else if (layout == kFftBf16Nhwc) { if (h16) RI_LAUNCH(1, true); else RI_LAUNCH(1, false); }
   else { if (h16) RI_LAUNCH(2, true); else RI_LAUNCH(2, false); }
 #undef RI_LAUNCH
 }
-template <int NX> static void launch_rows_inv_fwd(const ConvArgs& a, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+template <int NX> static void launch_rows_inv_fwd(const FftArgs& a, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   const int ntiles = a.B * a.H * (a.Cout / CB);
   const dim3 grid(persistent_grid(reinterpret_cast<const void*>(rows_inv_fwd_kernel<NX>), ntiles, rows_threads<NX>()));
   hipLaunchKernelGGL(rows_inv_fwd_kernel<NX>, grid, dim3(rows_threads<NX>()), 0, st, T, Tn, tw, a.bias, a.scale, a.shift, a.relu_bn, a.B, a.H, a.W, a.Cout, pad, norm, ntiles, sc);
 }
-void cfft_rows_inv(int NX, const ConvArgs& a, int layout, const cf* T, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv(int NX, const FftArgs& a, FftLayout layout, const cf* T, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
 #define CALL(N) launch_rows_inv<N>(a, layout, T, tw, pad, norm, sc, st)
   CFFT_BY_SIZE(NX, CALL)
 #undef CALL
+  return true;
 }
-void cfft_rows_inv_fwd(int NX, const ConvArgs& a, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv_fwd(int NX, const FftArgs& a, const cf* T, cf* Tn, const cf* tw, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
 #define CALL(N) launch_rows_inv_fwd<N>(a, T, Tn, tw, pad, norm, sc, st)
   CFFT_BY_SIZE(NX, CALL)
 #undef CALL
+  return true;
 }
 
 }  // namespace cfft

@@ -222,12 +222,12 @@ __global__ __launch_bounds__(256, 2) void rows_inv_mfma_kernel(const unsigned* _
 }
 
 
-bool cfft_rows_inv_mfma_supported(int NX, const ConvArgs& a, int layout, int pad, const Fp16Scale& sc) {
-  return NX == rm::NX && layout == 2 && sc.t16_inv && sc.t16_cb == 64 && a.CoutP % 64 == 0 && a.CoutP <= kParMax && a.Cout % 8 == 0 && a.W + pad <= rm::NX && pad >= 0 &&
-         a.wout_TX == 0 && (size_t)rm::NXH * a.CoutP * 4 < rm::kZeroOff;
+bool cfft_rows_inv_mfma_supported(int NX, const FftArgs& a, FftLayout layout, int pad, const Fp16Scale& sc) {
+  return NX == rm::NX && layout == kFftBf16Planar && sc.t16_inv && sc.t16_cb == 64 && a.CoutP % 64 == 0 && a.CoutP <= kParMax && a.Cout % 8 == 0 && a.W + pad <= rm::NX && pad >= 0 &&
+         !a.win_scatter && (size_t)rm::NXH * a.CoutP * 4 < rm::kZeroOff;
 }
 // true: launched
-bool cfft_rows_inv_mfma(int NX, const ConvArgs& a, int layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
+bool cfft_rows_inv_mfma(int NX, const FftArgs& a, FftLayout layout, const cf* T, int pad, float norm, const Fp16Scale& sc, hipStream_t st) {
   if (!cfft_rows_inv_mfma_supported(NX, a, layout, pad, sc)) return false;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return false;

@@ -2,6 +2,7 @@
 // frequency-domain route.  Host code only.
 #include <string>
 
+#include "conv_fft_plan.h"
 #include "ctx.h"
 
 namespace jcm {
@@ -188,26 +189,38 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
   FftLink alone;
   FftLink& k = q.link ? *q.link : alone;
   const int B = q.B, H = q.H, W = q.W, circ = q.circ;
-  // tensor layouts of the row passes: 0 fp32 NHWC, 1 bf16 NHWC, 2 bf16 planar
-  const int in_layout = q.act_bf16 ? (q.in_planar ? 2 : 1) : 0, out_layout = (q.act_bf16 && !q.out_f32) ? (q.out_planar ? 2 : 1) : 0;
-  ConvArgs a = conv_args(L, B, H, W);
+  const FftLayout in_layout = q.act_bf16 ? (q.in_planar ? kFftBf16Planar : kFftBf16Nhwc) : kFftF32Nhwc;
+  const FftLayout out_layout = (q.act_bf16 && !q.out_f32) ? (q.out_planar ? kFftBf16Planar : kFftBf16Nhwc) : kFftF32Nhwc;
+  FftArgs a = fft_args(L, B, H, W);
   a.x = q.x; a.bias = L->bias; a.scale = L->scale; a.shift = L->shift; a.out = q.out;
   a.CoutP = L->cout; a.relu_bn = L->has_bn && !q.linear ? 1 : 0;
   a.circ = circ;
   a.rows_mfma = c->fft_rows_mfma;
   a.fft_reg = c->fft_reg;
+  // the windows are gathered by the forward row pass (win_map) and / or scattered by the inverse row pass (win_scatter): one geometry
+  a.win_map = k.win_map; a.win_scatter = k.win_scatter; a.win = k.win;
   const size_t mark = c->arena_off;
-  const int np = fft_np(c);      // operand form of the channel GEMM (cgemm_split.hip)
+  const int np = fft_np(c);      // operand form of the channel GEMM (kernels.h: FftOperand)
+  const int pool_ks = k.next.pool ? k.next.ks_next : 0;
   // fp32 handles, the pool hand-over conv2 -> pool -> conv3 on the model's 120 x 180 map: the layer runs as 2 x 2 tiles in the 64 x 96 transform of the
-  // 60 x 90 maps (ConvArgs::tiles, conv_fft_reg_tiles.hip) -- a quarter of the filter spectra, and the register row kernels
-  a.tiles = c->fft_tiles && k.next.pool && !k.t_in && !k.xs && !k.merge && !k.win_map && !circ && in_layout == 0 &&
-            np == 4 && conv_fft_tiles_supported(a, L->ks, k.next.ks_next) ? 1 : 0;
+  // 60 x 90 maps (FftArgs::tiles, conv_fft_reg_tiles.hip) -- a quarter of the filter spectra, and the register row kernels
+  a.tiles = c->fft_tiles && k.next.pool ? 1 : 0;
+  FftPlan plan = conv_fft_plan(a, L->ks, np, pool_ks);
+  if (a.tiles && conv_fft_tiles_refusal(plan, in_layout, out_layout, k)) {
+    a.tiles = 0;
+    plan = conv_fft_plan(a, L->ks, np, pool_ks);
+  }
   const int wH = a.tiles ? H / 2 : H, wW = a.tiles ? W / 2 : W;      // the map size the filter spectra are for
   // fp32 handles, the last layer behind a hand-over (conv5 -> conv6 of jcm_pd_forward): 9 output channels do not pay for two column passes and a channel GEMM --
   // the channels are contracted on the row spectra that arrive in t_in (conv_fft_logits.hip).  Not on a handle with training state (one scale per tensor there).
-  const bool lrows = c->fft_logits_rows && !c->train && np == 4 && k.t_in && !k.t_in_16 && !k.t_next && !k.next.pool && !k.next.merge && !k.xs && !k.xs_ready && !k.merge &&
-                     !k.win_map && !k.win_scatter && !circ && in_layout == 0 && out_layout == 0 && conv_fft_logits_rows_supported(a, L->ks);
-  void* work = arena_alloc<char>(c, lrows ? conv_fft_logits_workspace_bytes(a) : conv_fft_workspace_bytes(a, L->ks, np));
+  const int common = c->train ? 1 : 0;
+  bool lrows = false;
+  if (c->fft_logits_rows && k.t_in && !a.tiles) {
+    const FftPlan lp = conv_fft_logits_plan(a);
+    lrows = !conv_fft_logits_refusal(lp, L->ks, np, in_layout, out_layout, k, common);
+    if (lrows) plan = lp;
+  }
+  void* work = arena_alloc<char>(c, plan.ok ? plan.total : 0);
   c->arena_off = mark;                                   // scratch of this layer only: later layers run behind it on the stream
   if (c->dry) return JCM_OK;
   const FftForm form = circ ? FftForm::Win : lrows ? FftForm::Rows : FftForm::Map;
@@ -221,17 +234,11 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
                                        np >= 4 ? fft_forward_wscale(c, scope, form, wH, wW) : nullptr));
     fw.valid = true;
   }
-  a.wp = fw.p;
+  plan.map.wp = plan.col.wp = plan.inv.wp = fw.p;
   hipEvent_t e0 = nullptr, e1 = nullptr, g0 = nullptr, g1 = nullptr;
   JCM_TRY(prof_begin(c, &e0, &e1));
   if (c->profile && (prof_event(c, &g0) != JCM_OK || prof_event(c, &g1) != JCM_OK)) { g0 = g1 = nullptr; }
-  if (k.win_map) {      // the windows are gathered by the forward row pass
-    a.win_map = k.win_map; a.win_B = k.win_B; a.win_H = k.win_H; a.win_W = k.win_W; a.win_TY = k.win_TY; a.win_TX = k.win_TX;
-  }
-  if (k.win_scatter) {      // ... and scattered by the inverse row pass (same geometry, with or without a gather)
-    a.wout_H = k.win_H; a.wout_W = k.win_W; a.wout_TY = k.win_TY; a.wout_TX = k.win_TX;
-  }
-  Fp16Scale sc;
+  FftScale sc;
   if (np >= 4) {
     // the word of this layer's input: handed over with t_in / ready spectra, or a fresh one for this layer's own row pass
     sc.tmax = k.tmax_in;
@@ -239,19 +246,20 @@ int run_conv_fft(jcm_ctx* c, const ConvLayer* L, const std::string& scope, const
     if (!sc.tmax) JCM_TRY(fft_new_words(c, a.tiles ? 4 * B : B, &sc.tmax));      // (tiles: one word per tile, the row of the channel GEMM)
     if (k.t_next) JCM_TRY(fft_new_words(c, B, &sc.tmax_next));
     sc.winv = fw.wscale + 1;
-    sc.common = c->train ? 1 : 0;      // a handle with training state: one scale per tensor (the weight gradient sums over the images)
+    sc.common = common;      // a handle with training state: one scale per tensor (the weight gradient sums over the images)
     // 16-bit T / T' between the row and column passes: bf16 tensors on both sides of the layer, one-part spectra, nothing handed over or kept
     // ... except the merge hand-over conv4_fullres -> conv5 of jcm_pd_forward, which exists in 16-bit form (rows_inv_merge_fwd_reg_kernel<.., true>)
-    sc.t16 = (np == 5 && c->fft_t16 && in_layout != 0 && out_layout != 0 && !k.xs && (!k.t_in || k.t_in_16) && (!k.t_next || (k.next.merge && !k.t_in))) ? 1 : 0;
+    sc.t16 = (np == kFftFp16x1 && c->fft_t16 && in_layout != kFftF32Nhwc && out_layout != kFftF32Nhwc && !k.xs && (!k.t_in || k.t_in_16) && (!k.t_next || (k.next.merge && !k.t_in))) ? 1 : 0;
   }
   k.tmax = sc.tmax;
   k.tmax_next = sc.tmax_next;      // the layer that takes t_next takes its words too
-  const hipError_t e = lrows ? conv_fft_logits_f32(a, work, k, g0, g1, c->stream, &sc)
-                             : conv_fft_f32(a, L->ks, np, in_layout, out_layout, work, k, g0, g1, c->stream, np >= 4 ? &sc : nullptr);
+  const char* why = nullptr;
+  const hipError_t e = lrows ? conv_fft_logits_f32(plan, L->ks, np, in_layout, out_layout, work, k, g0, g1, c->stream, &sc, &why)
+                             : conv_fft_f32(plan, in_layout, out_layout, work, k, g0, g1, c->stream, np >= 4 ? &sc : nullptr, &why);
   if (g0 && g1 && e == hipSuccess) c->prof[scope + "/gemm"].emplace_back(g0, g1);
   else { if (g0) c->event_pool.push_back(g0); if (g1) c->event_pool.push_back(g1); }
   prof_end(c, scope, e0, e1, e == hipSuccess);
-  if (e != hipSuccess) return fail(JCM_ERR_HIP, std::string("conv_fft_f32: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(JCM_ERR_HIP, why ? "conv_fft '" + scope + "': " + why : std::string("conv_fft_f32: ") + hipGetErrorString(e));
   return JCM_OK;
 }
 

@@ -92,13 +92,13 @@ struct jcm_ctx {
   int split_min_wgs = 128;      // grids smaller than this keep the exact kernel (option "split_min_wgs")
   int sm_algo = 3;              // 3 = every transform in LDS (sm_fused.hip), 1 = direct sliding-window VALU kernel (the cross-check)
   int conv9_fft = 1;            // fp32 handles: wide 9x9 layers in the frequency domain (conv_fft.hip) when the shape allows; 0 = fp32 MFMA chain
-  int fft_tiles = 1;            // fp32 handles, the pool hand-over of conv2_fullres: 2 x 2 tiles of the 120 x 180 map in the 60 x 90 maps' transform (ConvArgs::tiles)
+  int fft_tiles = 1;            // fp32 handles, the pool hand-over of conv2_fullres: 2 x 2 tiles of the 120 x 180 map in the 60 x 90 maps' transform (FftArgs::tiles)
   int fft_logits_rows = 1;      // fp32 handles without training state: the logits layer behind conv5's hand-over contracts the channels on the row spectra (conv_fft_logits.hip); 0 = a whole frequency-domain layer
   int fft_fuse = 7;             // jcm_pd_forward: bit 0 = conv2 -> max pool -> conv3 (fp32 handles), bit 1 = conv4_fullres -> branch merge -> conv5 handed over in row-transformed form (conv_fft_rows_fused.hip); bit 2 = the coarse branches on the side stream (Side, SideBranches)
   int fft_single = 1;           // bf16 handles: the channel GEMM on ONE scaled fp16 part per operand (np = 5; 0 = two bf16 parts, three products)
   int fft_t16 = 1;              // bf16 handles on the one-part route (fft_single): the row-transformed tensors T / T' as complex fp16 in block floating point (Fp16Scale::t16)
-  int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (ConvArgs::rows_mfma; conv_fft_rows_mfma.hip)
-  int fft_reg = 1;              // the register-resident transform kernels of conv_fft_reg_*.hip where they exist (ConvArgs::fft_reg); 0 = the LDS kernels for every pass
+  int fft_rows_mfma = 1;        // bf16 handles with 16-bit row-transformed tensors: conv5's inverse row pass on the matrix cores (FftArgs::rows_mfma; conv_fft_rows_mfma.hip)
+  int fft_reg = 1;              // the register-resident transform kernels of conv_fft_reg_*.hip where they exist (FftArgs::fft_reg); 0 = the LDS kernels for every pass
   int fft_cache_gb = 64;        // bound of the filter-spectra cache (conv_route.hip: a new entry that would grow it past the bound drops the others first)
   int fft_win = 1;              // training step of fp32 handles: frequency-domain layers on 32 x 32 overlap-save windows where that shrinks the filter-sized spectra (jcm_train.hip)
   int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel
@@ -245,6 +245,12 @@ inline ConvArgs conv_args(const ConvLayer* L, int B, int H, int W) {
   a.B = B; a.H = H; a.W = W; a.Cin = L->cin; a.Cout = L->cout;
   return a;
 }
+// ... of the frequency-domain route (kernels.h: FftArgs)
+inline FftArgs fft_args(const ConvLayer* L, int B, int H, int W) {
+  FftArgs a{};
+  static_cast<ConvArgs&>(a) = conv_args(L, B, H, W);
+  return a;
+}
 // One conv-layer request: what run_conv / run_conv_layer / run_conv_fft need beyond the layer.  Call sites name the fields they set.
 struct ConvCall {
   const void* x = nullptr;      // [B,H,W,Cin] (stride 2: the image, read at every sub-th pixel of every sub-th row)
@@ -260,7 +266,7 @@ struct ConvCall {
   FftLink* link = nullptr;
   int hpool = 0;
   int linear = 0;               // the epilogue stops at conv + bias whatever the layer's BatchNorm (jcm_conv_layer_pre)
-  int circ = 0;                 // run_conv_fft only: x is a batch of overlap-save windows [B, H, W, Cin] that fill the transform, out their valid regions [B, H - 8, W - 8, Cout] (ConvArgs::circ)
+  int circ = 0;                 // run_conv_fft only: x is a batch of overlap-save windows [B, H, W, Cin] that fill the transform, out their valid regions [B, H - 8, W - 8, Cout] (FftArgs::circ)
 };
 inline ConvCall conv_call(const void* x, void* out, int B, int H, int W) {
   ConvCall q;

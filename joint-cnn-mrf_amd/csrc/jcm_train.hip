@@ -51,7 +51,7 @@ float* grad_of(TrainState* t, float* grads, const std::string& name) {
 inline bool bf(const jcm_ctx* c) { return c->precision == JCM_PRECISION_BF16; }
 inline void* act(jcm_ctx* c, size_t elems) { return arena_alloc<char>(c, elems * (bf(c) ? 2 : 4)); }
 
-// ---- overlap-save windows (fp32 handles; ConvArgs::circ).  At 16 images per GPU every pass of a wide layer is bound by filter-sized
+// ---- overlap-save windows (fp32 handles; FftArgs::circ).  At 16 images per GPU every pass of a wide layer is bound by filter-sized
 // spectra -- F Cin Cout complex numbers written by the packers, read by the forward and the data-gradient GEMM, written and read as the weight gradient's
 // per-frequency products: 6 x 6.6 GB per step for conv5 on the 64 x 96 transform of its 60 x 90 map.  Cut into 32 x 32 windows (24 x 24 valid pixels + a halo
 // of 4, 3 x 4 windows per map) the same layer has 544 frequencies instead of 3136 and 192 "images" instead of 16: the filter-sized tensors shrink 5.8x, the
@@ -75,8 +75,7 @@ static bool takes_windows(jcm_ctx* c, const ConvLayer* L, int B, int H, int W, i
   *TY = (H + kWinValid - 1) / kWinValid;
   *TX = (W + kWinValid - 1) / kWinValid;
   ConvArgs a = conv_args(L, B * *TY * *TX, kWin, kWin);
-  a.circ = 1;
-  if (!conv_fft_supported(a, L->ks)) return false;
+  if (!conv_fft_supported(a, L->ks, 1)) return false;
   // the data gradient runs the same windows through the flipped, transposed filter: a layer with Cin = this layer's Cout.  dz reaches it with the
   // stride of the packed data-gradient filter (Cout rounded up to 16), and the weight gradient takes the windows only for a stride that is a
   // multiple of 64: a Cout of 80, 96, 160 ... stays on the whole map, where both gradients fall back to the direct kernels (such a layer on windows
@@ -84,7 +83,7 @@ static bool takes_windows(jcm_ctx* c, const ConvLayer* L, int B, int H, int W, i
   if (L->cout % 64) return false;
   ConvArgs d = a;
   d.Cin = L->cout; d.Cout = L->cin;
-  return conv_fft_supported(d, L->ks);
+  return conv_fft_supported(d, L->ks, 1);
 }
 
 
@@ -109,7 +108,7 @@ int run_conv_windows(jcm_ctx* c, const ConvLayer* L, const std::string& key, con
   float* rw = sw ? static_cast<float*>(out) : arena_alloc<float>(c, (size_t)g.BW() * kWinValid * kWinValid * L->cout);
   if (!c->dry && !gw) HIP_TRY(win_gather(c, g, in, xw, L->cin, 0));
   FftLink k;
-  k.win_B = g.B; k.win_H = g.H; k.win_W = g.W; k.win_TY = g.TY; k.win_TX = g.TX;
+  k.win = g;
   if (gw) k.win_map = in;
   k.win_scatter = sw;
   k.xs = xs;
@@ -139,14 +138,14 @@ int conv_train_fwd_conv(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int 
   L.shift = t->zeros;
   if (int TY = 0, TX = 0; stride == 1 && takes_windows(c, &L, B, Hin, Win, &TY, &TX)) {      // the windows' spectra are kept for the weight gradient
     f.win = WinGeom{B, Hin, Win, TY, TX};
-    ConvArgs ax = conv_args(&L, f.win.BW(), kWin, kWin);
+    FftArgs ax = fft_args(&L, f.win.BW(), kWin, kWin);
     ax.circ = 1;
     f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(ax, L.ks, fft_np(c)));
     return run_conv_windows(c, &L, f.scope, f.win, x, f.r, f.xs, &f.xs_tmax);
   }
   FftLink k;
   if (stride == 1 && !bf(c) && takes_fft(c, &L, B, Hin, Win)) {      // keep the input spectra: the weight gradient is taken in the frequency domain too
-    f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(conv_args(&L, B, Hin, Win), L.ks, fft_np(c)));
+    f.xs = arena_alloc<char>(c, conv_fft_xs_bytes(fft_args(&L, B, Hin, Win), L.ks, fft_np(c)));
     k.xs = f.xs;
   }
   ConvCall q = conv_call(x, f.r, B, Hin, Win);
@@ -237,14 +236,14 @@ int wgrad_freq(jcm_ctx* c, const LayerFwd& f, const void* dz, int ldz, int n, in
   *taken = conv_fft_geometry(th, tw, L->ks, n, L->cout, np, &NY, &NX, &MTx, circ) && conv_fft_geometry(th, tw, L->ks, n, L->cin, np, &ny2, &nx2, &MTz, circ);
   if (!*taken) return JCM_OK;
   size_t mark = c->arena_off;
-  ConvArgs az{};
+  FftArgs az{};
   az.x = dz; az.B = n; az.H = th; az.W = tw; az.Cin = ldz; az.Cout = L->cin; az.circ = circ;
   bool gw = true;
   float* zw = nullptr;
   if (win) {
     zw = win_buffer(c, *win, ldz, &gw);
     az.x = zw;
-    if (gw) { az.win_map = dz; az.win_B = win->B; az.win_H = win->H; az.win_W = win->W; az.win_TY = win->TY; az.win_TX = win->TX; az.win_valid_only = 1; }
+    if (gw) { az.win_map = dz; az.win = *win; az.win_valid_only = 1; }
   }
   char* zs = arena_alloc<char>(c, conv_fft_xs_bytes(az, L->ks, np));
   if (!win) mark = c->arena_off;      // zs stays allocated
@@ -256,12 +255,13 @@ int wgrad_freq(jcm_ctx* c, const LayerFwd& f, const void* dz, int ldz, int n, in
     float* ztmax = nullptr;
     if (np == 4) JCM_TRY(fft_new_words(c, n, &ztmax));
     hipError_t le = gw ? hipSuccess : win_gather(c, *win, dz, zw, ldz, 1);
-    if (le == hipSuccess) le = conv_fft_spectra(az, L->ks, np, work, zs, c->stream, ztmax, 1);
+    const char* why = nullptr;
+    if (le == hipSuccess) le = conv_fft_spectra(az, L->ks, np, work, zs, c->stream, ztmax, 1, &why);
     if (le == hipSuccess)
       le = wgrad_fft(f.xs, zs, P, L->w_raw, lmbd, grad_of(c->train, grads, f.scope + "/weights"), L->ks, NY, NX, n, MTx, MTz, L->cin, ldz, L->cout, c->stream,
                      np, f.xs_tmax, ztmax, th);
     prof_end(c, "wgrad:" + f.scope, e0, e1, le == hipSuccess);
-    if (le != hipSuccess) return fail(JCM_ERR_HIP, std::string("frequency-domain weight gradient ") + (win ? "(windows) " : "") + "of '" + f.scope + "': " + hipGetErrorString(le));
+    if (le != hipSuccess) return fail(JCM_ERR_HIP, std::string("frequency-domain weight gradient ") + (win ? "(windows) " : "") + "of '" + f.scope + "': " + (why ? why : hipGetErrorString(le)));
     if (!win) { ho->zs = zs; ho->zs_tmax = ztmax; ho->zs_ld = ldz; }
   }
   c->arena_off = mark;

@@ -47,27 +47,6 @@ struct ConvArgs {
   // so a halo row of one unit is contiguous in HBM (a 64-pixel LDS-DMA reads 1 KB instead of 64 separate 128-byte
   // lines).  The 9x9 chain conv3 -> conv4 -> merge -> conv5 -> conv6 of the bf16 path runs planar.
   int in_planar = 0, out_planar = 0;
-  // conv_fft only -- OVERLAP-SAVE windows (the training step, jcm_train.hip): the input is a batch of H x W windows that FILL the circular transform
-  // (H, W are transform lengths; each window carries a halo of 4 real pixels around its (H - 8) x (W - 8) valid region), the output is the batch of valid
-  // regions [B, H - 8, W - 8, Cout]: row j of it is row j + 4 + (k - 1) / 2 of the circular convolution.  The filter spectra shrink with the window
-  // (32 x 32: 544 frequencies instead of the 3136 of a 60 x 90 map), which is what pays when the batch is small.
-  int circ = 0;
-  // ... whose windows need not exist as a tensor (round 6): win_map = the [win_B, win_H, win_W, Cin] fp32 map they are cut from (x is then unused) -- window
-  // (b, ty, tx) of the win_TY x win_TX grid covers map rows ty (H - 8) - 4 .. + H, columns tx (W - 8) - 4 .. + W, zeros outside the map (and in the halo of 4
-  // when win_valid_only: the weight gradient's dZ).  The forward row pass gathers while it loads (conv_fft_win_gather_supported()).
-  const void* win_map = nullptr;
-  int win_B = 0, win_H = 0, win_W = 0, win_TY = 0, win_TX = 0, win_valid_only = 0;
-  // ... and the valid regions need not either: wout_TY > 0 -> `out` is the [win_B, wout_H, wout_W, Cout] MAP and the inverse row pass stores valid pixel (y, x)
-  // of window (b, ty, tx) at map pixel (ty (H - 8) + y, tx (W - 8) + x) where that lies inside the map (conv_fft_win_scatter_supported())
-  int wout_H = 0, wout_W = 0, wout_TY = 0, wout_TX = 0;
-  // conv_fft only, fp32 handles, a 5x5 layer followed by the 2x2 max pool (FftNext::pool): run the H x W map as 2 x 2 TILES of H / 2 x W / 2, each with its
-  // 2-pixel halo in the circular transform of an H / 2 x W / 2 map (conv_fft_tiles_supported(); the filter spectra are those of that map size)
-  int tiles = 0;
-  // conv_fft, bf16 handles with 16-bit row-transformed tensors: the 96-point inverse row pass with planar bf16 output (conv5 of the model) as a matrix product
-  // on the matrix cores (conv_fft_rows_mfma.hip).  1 = on where the kernel exists, 0 = the register kernel.
-  int rows_mfma = 0;
-  // conv_fft: the register-resident transform kernels (conv_fft_reg_*.hip) where they exist; 0 = the LDS kernels for every pass, their A/B arm (option "fft_reg")
-  int fft_reg = 1;
   // conv5_strip_bf16 only: the LEFT HALF of the 2x2/2 max pool that follows the layer in its epilogue -- `out` is the [B, H, W / 2, Cout] map of
   // max(pixel 2 i, pixel 2 i + 1) (W even; either activation layout), half the bytes; vpool_2x1() finishes the pool.  The max of two bf16-rounded values is
   // the bf16 rounding of the max: bit-identical to pooling the stored map.
@@ -98,10 +77,14 @@ hipError_t conv_thin_bf16(const ConvArgs& a, hipStream_t st);
 
 // ---- conv_fft.hip : stride-1 SAME convolution (9x9, 5x5) in the frequency domain: in-LDS FFTs (rows, then columns with the operand split
 // fused in) around the channel GEMM of cgemm_split.hip, one complex matrix product per frequency.  a.wp = split filter spectra of this map
-// and kernel size (conv_fft_pack_weights).  np = operand form of the channel GEMM: 5 = ONE fp16 part of spectra scaled by powers of two, one product, 32 channels per
-// stage (bf16 handles, default: the tensors on either side of the layer are bf16, an 11-bit spectrum is 8x finer); 2 = two bf16 parts (bf16 handles), 3 = three bf16 parts / six
-// products, 4 = two FP16 parts / three products of spectra scaled by powers of two (fp32 handles; both fp32-class, 4 is the default).
+// and kernel size (conv_fft_pack_weights).  np = operand form of the channel GEMM (FftOperand below): 5 = ONE fp16 part of spectra scaled by powers of two, one product,
+// 32 channels per stage (bf16 handles, default: the tensors on either side of the layer are bf16, an 11-bit spectrum is 8x finer); 2 = two bf16 parts (bf16 handles with
+// "fft_single" off); 4 = two FP16 parts / three products of spectra scaled by powers of two (fp32 handles).  Nothing else: the three-part form np = 3 of earlier rounds
+// survives only as the spectra layout wgrad_fft.hip names, and conv_fft_f32 refuses it.
 // Shapes: Cin % 64 == 0, H + k - 1 <= 192, W + k - 1 <= 192.
+enum FftOperand : int { kFftBf16x2 = 2, kFftFp16x2 = 4, kFftFp16x1 = 5 };
+// tensor layouts of the row passes (the values are the kernels' template arguments)
+enum FftLayout : int { kFftF32Nhwc = 0, kFftBf16Nhwc = 1, kFftBf16Planar = 2 };
 //
 // np = 4 / 5 scaling (fp16 carries 11 bits over 2^-24 .. 2^16): device words, all written and read on the stream --
 //   tmax[b]      : max |T| of image b of the layer's row-transformed input (atomic max by the row pass, or by the previous layer's fused kernel:
@@ -111,28 +94,65 @@ hipError_t conv_thin_bf16(const ConvArgs& a, hipStream_t st);
 //                  sums over the images and needs one scale);
 //   tmax_next[b] : the words of the NEXT layer when t_next is given;
 //   winv         : 1 / (scale of the filter spectra), written by conv_fft_pack_weights into wscale[1] (wscale[0] is its scratch).
+// FftScale is what the caller of a layer supplies; Fp16Scale is what the kernels take (by value: its layout is theirs), derived from it and the layer's
+// FftPlan by the runners of conv_fft.hip -- no caller fills it.
+struct FftScale {
+  float* tmax = nullptr;
+  float* tmax_next = nullptr;
+  const float* winv = nullptr;
+  int common = 0;
+  // np = 5: ask for 16-bit row-transformed tensors (T between the forward row and column pass, T' between the inverse column and row pass: complex fp16 in block
+  // floating point, conv_fft_common.h).  bf16 in / out layouts only.
+  int t16 = 0;
+};
 struct Fp16Scale {
   float* tmax = nullptr;
   float* tmax_next = nullptr;
   const float* winv = nullptr;
-  float hf = 0.f;      // H (set by conv_fft_f32)
-  int nb = 0;          // B (set by conv_fft_f32)
+  float hf = 0.f;      // rows the column transform sums: H (1 for the logits layer's row spectra)
+  int nb = 0;          // images = rows of the channel GEMM
   int common = 0;
-  // np = 5 with 16-bit row-transformed tensors: t16 = 1 asks conv_fft_f32 for them; it carves the tile scale words out of its workspace and fills the
-  // pointers below for its kernels (T between the forward row and column pass, T' between the inverse column and row pass: complex fp16 in block
-  // floating point, conv_fft_common.h; t16_cb = channels per tile of the inverse column pass).  bf16 in / out layouts only.
   int t16 = 0;
-  float* t16_fwd = nullptr;
+  float* t16_fwd = nullptr;      // the tile scale words of the 16-bit T / T': regions of the plan's workspace (or behind a handed-over T)
   float* t16_inv = nullptr;
-  int t16_cb = 64;
+  int t16_cb = 64;               // channels per tile of the inverse column pass
 };
-bool conv_fft_supported(const ConvArgs& a, int ks);
-size_t conv_fft_weight_bytes(int H, int W, int ks, int Cin, int Cout, int np, int circ = 0);      // circ: H x W is the window = the transform (ConvArgs::circ)
+// window geometry of a layer pass: every [H, W] map of the batch cut into TY x TX overlap-save windows; TY = 0: the layer runs on the whole map
+struct WinGeom {
+  int B = 0, H = 0, W = 0, TY = 0, TX = 0;
+  int BW() const { return B * TY * TX; }      // windows = "images" of the transform
+};
+// The arguments of a frequency-domain layer: ConvArgs + what only this route reads (the cfft_* launchers of conv_fft_common.h take it).
+struct FftArgs : ConvArgs {
+  // OVERLAP-SAVE windows (the training step, jcm_train.hip): the input is a batch of H x W windows that FILL the circular transform (H, W are transform lengths;
+  // each window carries a halo of 4 real pixels around its (H - 8) x (W - 8) valid region), the output is the batch of valid regions [B, H - 8, W - 8, Cout]:
+  // row j of it is row j + 4 + (k - 1) / 2 of the circular convolution.  The filter spectra shrink with the window (32 x 32: 544 frequencies instead of the
+  // 3136 of a 60 x 90 map), which is what pays when the batch is small.
+  int circ = 0;
+  // ... whose windows need not exist as a tensor: win_map = the [win.B, win.H, win.W, Cin] fp32 map they are cut from (x is then unused) -- window (b, ty, tx) of the
+  // win.TY x win.TX grid covers map rows ty (H - 8) - 4 .. + H, columns tx (W - 8) - 4 .. + W, zeros outside the map (and in the halo of 4 when win_valid_only: the
+  // weight gradient's dZ).  The forward row pass gathers while it loads (conv_fft_win_gather_supported()).
+  const void* win_map = nullptr;
+  int win_valid_only = 0;
+  // ... and the valid regions need not either: win_scatter -> `out` is the [win.B, win.H, win.W, Cout] MAP and the inverse row pass stores valid pixel (y, x) of
+  // window (b, ty, tx) at map pixel (ty (H - 8) + y, tx (W - 8) + x) where that lies inside the map (conv_fft_win_scatter_supported())
+  bool win_scatter = false;
+  WinGeom win;      // the one geometry both share
+  // fp32 handles, a 5x5 layer followed by the 2x2 max pool (FftNext::pool): run the H x W map as 2 x 2 TILES of H / 2 x W / 2, each with its 2-pixel halo in the
+  // circular transform of an H / 2 x W / 2 map (conv_fft_tiles_refusal(); the filter spectra are those of that map size)
+  int tiles = 0;
+  // bf16 handles with 16-bit row-transformed tensors: the 96-point inverse row pass with planar bf16 output (conv5 of the model) as a matrix product on the matrix
+  // cores (conv_fft_rows_mfma.hip).  1 = on where the kernel exists, 0 = the register kernel.
+  int rows_mfma = 0;
+  // the register-resident transform kernels (conv_fft_reg_*.hip) where they exist; 0 = the LDS kernels for every pass, their A/B arm (option "fft_reg")
+  int fft_reg = 1;
+};
+bool conv_fft_supported(const ConvArgs& a, int ks, int circ = 0);      // circ: FftArgs::circ
+size_t conv_fft_weight_bytes(int H, int W, int ks, int Cin, int Cout, int np, int circ = 0);      // circ: H x W is the window = the transform
 hipError_t conv_fft_pack_weights(const float* w_hwio, void* wf, int H, int W, int ks, int Cin, int Cout, int np, bool round_bf16, hipStream_t st,
                                  float* wscale = nullptr, int circ = 0,
                                  const float* bound_from = nullptr);      // bound_from: device word holding the filter's bound already (wscale[0] of the same filter's other spectra)
-size_t conv_fft_workspace_bytes(const ConvArgs& a, int ks, int np);
-// in / out layout: 0 = fp32 NHWC, 1 = bf16 NHWC, 2 = bf16 planar (bf16 handles: operands are bf16 values, the arithmetic is fp32-class); g0/g1: optional events around the GEMM
+size_t conv_fft_workspace_bytes(const FftArgs& a, int ks, int np);      // = conv_fft_plan(a, ks, np).total (conv_fft_plan.h)
 // t_in / t_next: the row-transformed tensor handed from one frequency-domain layer to the next (fp32 NHWC handles; conv_fft_fusable).
 // merge: a.x is the full-resolution branch x1 and the layer's input is ((x1 + up(x2)) + up(x3)) / 3, formed while the rows are loaded.
 struct FftMerge { const void* x2; int H2, W2; const void* x3; int H3, W3; };      // x1 (a.x), x2, x3: NHWC in the layer's input type
@@ -146,43 +166,34 @@ struct FftLink {
   // input side
   const void* t_in = nullptr;       // the row-transformed input left by the previous layer's fused kernel: the forward row pass is skipped
   bool t_in_16 = false;             // ... as complex fp16 followed by its tile scale words (bf16 handles: conv4_fullres -> conv5)
-  float* tmax_in = nullptr;         // the scale words (Fp16Scale::tmax) that come with t_in / with ready spectra
+  float* tmax_in = nullptr;         // the scale words (FftScale::tmax) that come with t_in / with ready spectra
   const FftMerge* merge = nullptr;  // the layer forms the merged map itself while it loads the rows (conv5)
   void* xs = nullptr;               // keep the split activation spectra in this caller buffer (conv_fft_xs_bytes; the training step's weight gradient reads them)
   bool xs_ready = false;            // ... they are there already (the data gradient after the weight gradient of the same layer): skip the forward transforms
-  const void* win_map = nullptr;    // the overlap-save windows are cut from this map by the forward row pass (ConvArgs::win_map) ...
-  int win_B = 0, win_H = 0, win_W = 0, win_TY = 0, win_TX = 0;      // ... of this geometry, which win_scatter shares
+  const void* win_map = nullptr;    // the overlap-save windows are cut from this map by the forward row pass (FftArgs::win_map) ...
+  WinGeom win;                      // ... of this geometry, which win_scatter shares
   // output side
   void* t_next = nullptr;           // write the NEXT layer's row-transformed input there instead of the spatial output (conv_fft_fusable() says when that is legal)
   FftNext next;                     // what lies between this layer and that one
-  bool win_scatter = false;         // the inverse row pass stores the valid regions into the map `out` (ConvArgs::wout_*)
+  bool win_scatter = false;         // the inverse row pass stores the valid regions into the map `out` (FftArgs::win_scatter)
   // results (np >= 4), written by run_conv_fft
   float* tmax = nullptr;            // the words this layer's input used
   float* tmax_next = nullptr;       // the words of t_next
   bool empty() const { return !t_in && !merge && !xs && !xs_ready && !win_map && !t_next && !next.pool && !next.merge && !win_scatter; }
 };
-hipError_t conv_fft_f32(const ConvArgs& a, int ks, int np, int in_layout, int out_layout, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st,
-                        const Fp16Scale* sc = nullptr);
-// The logits layer contracted on the row spectra of its input (conv_fft_logits.hip; fp32 handles): a 9x9 layer with Cout <= 16 whose row-transformed input arrives
-// through link.t_in at a 96-point row length, H <= 64.  a.wp = the operand packed by conv_fft_logits_pack (conv_fft_logits_weight_bytes; wscale as above), work =
-// conv_fft_logits_workspace_bytes(a); out fp32 NHWC, bias epilogue.
-bool conv_fft_logits_rows_supported(const ConvArgs& a, int ks);
+// The runners (conv_fft_f32, conv_fft_logits_f32: conv_fft_plan.h) take the layer's FftPlan.
 size_t conv_fft_logits_weight_bytes(int H, int W, int Cin);
-size_t conv_fft_logits_workspace_bytes(const ConvArgs& a);
 hipError_t conv_fft_logits_pack(const float* w_hwio, void* aop, int H, int W, int Cin, int Cout, hipStream_t st, float* wscale);
-hipError_t conv_fft_logits_f32(const ConvArgs& a, void* work, const FftLink& link, hipEvent_t g0, hipEvent_t g1, hipStream_t st, const Fp16Scale* sc);
 // the fused hand-overs of FftNext: is there a kernel for this pair of layers, and the size of the row-transformed tensor handed over
 // (both kernels are register kernels: fft_reg = the handle's option)
 bool conv_fft_win_gather_supported(int win, int Cin, bool fft_reg);      // can the forward row pass of `win` x `win` overlap-save windows read them straight from the map?
 bool conv_fft_win_scatter_supported(int win, int Cout, bool fft_reg);    // ... and its inverse row pass store the valid regions straight into the map?
 bool conv_fft_pool_fusable(const ConvArgs& a, int ks, int ks_next);
-// ... as 2 x 2 tiles of the map (ConvArgs::tiles; register kernels only: needs a.fft_reg), and the map size of their filter spectra
-bool conv_fft_tiles_supported(const ConvArgs& a, int ks, int ks_next);
 size_t conv_fft_pool_handover_bytes(const ConvArgs& a, int ks_next);
 bool conv_fft_merge_fusable(const ConvArgs& a, int ks, int ks_next, const FftMerge& m, bool fft_reg, bool h16 = false);      // h16: bf16 handles (16-bit T / T', bf16 branches)
-size_t conv_fft_xs_bytes(const ConvArgs& a, int ks, int np);
-// NHWC fp32 -> split spectra (the two forward passes); np = 4: tmax = the (zeroed) device word of this tensor
-hipError_t conv_fft_spectra(const ConvArgs& a, int ks, int np, void* work, void* xs, hipStream_t st, float* tmax = nullptr, int common = 0);
+size_t conv_fft_xs_bytes(const FftArgs& a, int ks, int np);      // = the plan's Xs region, rounded up to 256 bytes
+// NHWC fp32 -> split spectra (the two forward passes); np = 4: tmax = the (zeroed) device word of this tensor.  *why (optional): the reason of a refusal
+hipError_t conv_fft_spectra(const FftArgs& a, int ks, int np, void* work, void* xs, hipStream_t st, float* tmax = nullptr, int common = 0, const char** why = nullptr);
 bool conv_fft_geometry(int H, int W, int ks, int B, int Cout, int np, int* NY, int* NX, int* MT, int circ = 0);
 
 // ---- wgrad_fft.hip : weight gradient of a stride-1 layer in the frequency domain (fp32 handles, training step): per frequency
@@ -200,7 +211,8 @@ hipError_t pad_channels_f32(const float* in, int ldi, float* out, int ldo, size_
 hipError_t window_gather_f32(const float* map, float* win, int B, int H, int W, int C, int WS, int TY, int TX, int valid_only, hipStream_t st);
 hipError_t window_scatter_f32(const float* val, float* map, int B, int H, int W, int C, int WS, int TY, int TX, hipStream_t st);
 bool conv_fft_fusable(const ConvArgs& a, int ks, int ks_next);
-size_t conv_fft_handover_bytes(const ConvArgs& a, int ks);
+// h16: the hand-over in 16-bit form (data, then tile scale words: conv_fft_plan.h); the same byte count, see the definition
+size_t conv_fft_handover_bytes(const ConvArgs& a, int ks, bool h16 = false);
 
 // ---- cgemm_split.hip : Y[f][b][co] = sum_ci X[f][b][ci] W[f][ci][co] (complex) for F frequencies on v_mfma_f32_32x32x16_bf16, operands
 // as np bf16 parts in tile-major LDS-image layout:

@@ -182,7 +182,7 @@ int pd_forward_impl(jcm_ctx* c, const void* x, bool x_u8, int B, int H, int W, f
   FftLink k5, k6;      // conv5 -> conv6
   if (fuse45) {
     const ConvArgs a = conv_args(L4, B, hh, ww);
-    t45 = arena_alloc<char>(c, conv_fft_handover_bytes(a, L4->ks));
+    t45 = arena_alloc<char>(c, conv_fft_handover_bytes(a, L4->ks, h16));
     x4[0] = nullptr;
   } else {
     x4[0] = act((size_t)B * h4[0] * w4[0] * L4->cout);

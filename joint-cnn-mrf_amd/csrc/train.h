@@ -64,12 +64,6 @@ struct TrainState {
   long step = 0;                       // optimizer updates applied (n_iters, main.py:491)
 };
 
-// window geometry of a layer pass: every [H, W] map of the batch cut into TY x TX overlap-save windows (jcm_train.hip: kWin); TY = 0: the layer runs on the whole map
-struct WinGeom {
-  int B = 0, H = 0, W = 0, TY = 0, TX = 0;
-  int BW() const { return B * TY * TX; }      // windows = "images" of the transform
-};
-
 // ---- one conv layer in training mode: r = relu(conv + b) [or conv + b], batch stats, y = BN(r)
 struct LayerFwd {
   std::string scope;
@@ -80,7 +74,7 @@ struct LayerFwd {
   void* y = nullptr;
   void* xs = nullptr;          // fp32 handles, frequency-domain layers: the split spectra of the input, kept for the weight gradient (wgrad_fft.hip)
   float* xs_tmax = nullptr;    // ... and the device word of their fp16 scaling (np = 4)
-  WinGeom win;                 // the layer ran on overlap-save windows: xs are the WINDOWS' spectra
+  WinGeom win;                 // (kernels.h) the layer ran on overlap-save windows of kWin x kWin (jcm_train.hip): xs are the WINDOWS' spectra
 };
 
 inline int need_train(jcm_handle h) {

@@ -1,4 +1,4 @@
-"""conv2_fullres -> max pool -> conv3 as 2x2 tiles of the 120x180 map (option "fft_tiles", ConvArgs::tiles in conv_fft.hip).
+"""conv2_fullres -> max pool -> conv3 as 2x2 tiles of the 120x180 map (option "fft_tiles", FftArgs::tiles in conv_fft.hip).
 
 Each 60x90 tile plus a 2-pixel halo fills the 64x96 circular transform of the 60x90 maps; the tiled route and the whole-map route compute the
 same SAME convolution through different transforms and per-tile (instead of per-image) fp16 scales, so they agree to rounding, and both hold

@@ -4,7 +4,7 @@ lands in the first row / column nobody reads, so an off-by-one in padding, wrap,
 map one short of it (the row pass packs two real rows into one complex transform: the last row is unpaired), and the first map that needs the
 length (the most zero padding).  The cases come from tests/fft_lengths_ref.py; tests/test_fft_lengths_cpu.py holds them to the source.
 
-Which kernel family runs each pass, read from the launchers (conv_fft.hip: conv_fft_f32; conv_fft_reg_fwd.hip, conv_fft_reg_inv.hip,
+Which kernel family runs each pass, read from the launchers (conv_fft.hip: the five pass functions pass_rows_fwd .. pass_rows_inv; conv_fft_reg_fwd.hip, conv_fft_reg_inv.hip,
 conv_fft_rows_*.hip, conv_fft_cols.hip).  'LDS' = the kernels CFFT_BY_SIZE instantiates for all 14 lengths, 'reg' = register-resident transforms.
 
   pass            | fp32 handle                    | fp32, fft_reg = 0 | bf16 handle (one fp16 part, 16-bit T) | bf16, fft_single = 0 (fp32 T)
