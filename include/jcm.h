@@ -279,6 +279,33 @@ int jcm_det_curve(jcm_handle h, const int32_t* pred_coords, const float* y, int 
 int jcm_hm_peaks(jcm_handle h, const float* hm, int B, int HH, int WW, int K, int P, float threshold,
                  int32_t* cells, float* offsets, float* scores, int32_t* count);
 
+/* Pose decoding: of the P candidate cells per joint, the ONE combination with the highest spatial-model energy -- a joint MAP over P^9 poses in
+ * place of nine independent arg-maxes.  Fixed geometry: 60x90 maps, 120x180 priors, 9 joints plus the torso channel, 1 <= P <= 4.
+ * hm10:  device fp32 [B,60,90,10], what jcm_sm_forward takes: nine part-detector probabilities and the torso map.
+ * cells: device int32 [B,9,P,2] (row, col), count: device int32 [B,9], as jcm_hm_peaks writes them (count is read clamped to 0..P; a cell of a
+ *        slot below count lies in the map).
+ * Write u_c(q) = softplus5(bn_sm(hm10[b,q,c])), the likelihood of the spatial-model forward (the same device expression), d = 1e-6,
+ * e_{j|c} / b_{j|c} the handle's softplus'd prior [120,180] / bias [60,90] of pair <j>_<c>, (yj,xj) = cell of joint j's candidate pj, and
+ * t = (yt,xt) the torso cell: the first-occurrence flat arg-max of channel 9 by the rules of jcm_argmax_coords.
+ * Tables, fp32, one correctly rounded operation per step, log and softplus as the spatial model's kernels evaluate them:
+ *   T[j,c,pj,pc] = log( e_{j|c}[59 + (yj - yc), 89 + (xj - xc)] * u_c(cell_c,pc) + b_{j|c}[yj,xj] + d )        j != c, both < 9
+ *   V[j,p]       = log( u_j(cell_j,p) + d ) + log( e_{j|torso}[59 + (yj - yt), 89 + (xj - xt)] * u_9(t) + b_{j|torso}[yj,xj] + d )
+ *   M[a,b,pa,pb] = T[a,b,pa,pb] + T[b,a,pb,pa]                                                                   a < b
+ * which is the marginal energy of main.py:117-123 with every conditioning map collapsed onto its candidate cell ([59 + dy, 89 + dx] is where
+ * conv_mrf reads the prior for that displacement; the 61x91 -> 60x90 resize of main.py:89 is left out: a delta has no neighbourhood to blend).
+ * Entries of a slot at or beyond count are 0.
+ * Search: a pose is s = (p_0 .. p_8), p_j < count[b,j]; its score is the fixed-order fp32 sum
+ *   S_0 = V[0,p_0];  inc_k = (((V[k,p_k] + M[0,k,p_0,p_k]) + M[1,k,p_1,p_k]) + ..) + M[k-1,k,p_{k-1},p_k];  S_k = S_{k-1} + inc_k;  score = S_8.
+ * The result is the pose of the highest score; ties go to the lexicographically smallest (p_0 .. p_8), p_0 most significant.  An image with some
+ * count[b,j] == 0 has no pose: index -1, coords -1, score and score0 -inf.  NaN inputs are outside the contract.
+ * Outputs (device; each may be NULL except index): index int32 [B,9], the chosen candidate per joint; coords int32 [B,2,9], its cell in the layout
+ * of jcm_argmax_coords; score fp32 [B]; score0 fp32 [B], the score of the all-candidate-0 pose, i.e. of the independent arg-maxes; V fp32 [B,9,P]
+ * and M fp32 [B,36,P,P], pairs (a < b) in lexicographic order.
+ * JCM_ERR_ARG for P outside 1..4, B < 1 or a required pointer that is NULL, JCM_ERR_STATE before jcm_finalize or on a handle without
+ * spatial-model parameters; nothing is launched and no output is touched then.  Uses the handle's workspace, like jcm_sm_forward. */
+int jcm_pose_decode(jcm_handle h, const float* hm10, int B, const int32_t* cells, const int32_t* count, int P,
+                    int32_t* index, int32_t* coords, float* score, float* score0, float* V, float* M);
+
 /* -- the whole tower ----------------------------------------------------------------------------
  * The graph of main.py:522-531: model -> spatial_softmax -> concat torso -> spatial_model ->
  * spatial_softmax -> argmax.  x [B,H,W,3]; torso [B,60,90,1] = y_in[...,K:] (main.py:528),

@@ -47,6 +47,8 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_float), ctypes.c_int, _c_i32_p, _c_float_p, _c_i32_p]),
     'jcm_hm_peaks': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                     _c_i32_p, _c_float_p, _c_float_p, _c_i32_p]),
+    'jcm_pose_decode': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, _c_i32_p, _c_i32_p, ctypes.c_int, _c_i32_p, _c_i32_p, _c_float_p, _c_float_p,
+                                       _c_float_p, _c_float_p]),
     'jcm_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    _c_float_p, _c_float_p, _c_i32_p, _c_i32_p]),
     'jcm_eval_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,

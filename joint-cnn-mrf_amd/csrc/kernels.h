@@ -310,6 +310,14 @@ hipError_t det_curve(const int32_t* pred, const float* y, int B, int HW, int WW,
 // one work group per (image, joint group), the maps staged in LDS.  1 <= P <= 8, HH * WW <= 21600.
 hipError_t hm_peaks(const float* hm, int B, int HH, int WW, int K, int P, float threshold, int32_t* cells, float* offsets, float* scores, int32_t* count,
                     hipStream_t st);
+// ---- pose_decode.hip ---------------------------------------------------------------------------
+// Of the P <= 4 candidate cells per joint (cells [B,9,P,2], count [B,9], as hm_peaks writes them) the combination with the highest spatial-model energy on
+// hm10 [B,60,90,10] (jcm.h: jcm_pose_decode): V [B,9,P] and M [B,36,P,P] (required here), the 16 partial winners per image (pscore, ppose [B,16]), then
+// index [B,9], coords [B,2,9], score [B], score0 [B] (the last three may be null).  Three launches; 1 <= P <= 4, B <= kPoseMaxB.
+constexpr int kPoseMaxB = 1 << 20;
+hipError_t pose_decode(const float* hm10, int B, const int32_t* cells, const int32_t* count, int P, const float* sp_energy, const float* sp_bias,
+                       const float* bn_scale, const float* bn_shift, float* V, float* M, float* pscore, int32_t* ppose, int32_t* index, int32_t* coords,
+                       float* score, float* score0, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

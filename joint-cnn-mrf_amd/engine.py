@@ -314,6 +314,41 @@ class Engine:
             if prob is not None:
                 r[key + '_peaks'] = self.hm_peaks(prob, max_peaks=peaks)
 
+    def pose_decode(self, hm10, peaks, want_tables=False):
+        """Of the candidate cells per joint in `peaks` (the dict of hm_peaks on nine joint maps, P <= 4: 'cells' int32 [B,9,P,2], 'count' int32
+        [B,9]) the ONE combination with the highest spatial-model energy on hm10 [B,60,90,10] (what spatial_model takes: nine part-detector
+        probabilities and the torso map) -- a joint MAP over P^9 poses (include/jcm.h: jcm_pose_decode).  Returns {'index' int32
+        [B,9] (the chosen peak per joint), 'coords' int32 [B,2,9] (its cell, the layout of argmax_coords), 'score' fp32 [B], 'score0' fp32 [B]
+        (the all-peak-0 pose: the independent arg-maxes)} plus, with want_tables, 'V' fp32 [B,9,P] and 'M' fp32 [B,36,P,P].  An image with an
+        empty candidate list has no pose: -1 / -1 / -inf / -inf.  Device tensors; nothing is read back.  P is checked by the library."""
+        self._chk(hm10, 4, 'hm10')
+        cells, count = peaks['cells'], peaks['count']
+        self._chk(cells, 4, "peaks['cells']", torch.int32)
+        self._chk(count, 2, "peaks['count']", torch.int32)
+        B, P = hm10.shape[0], cells.shape[2]
+        if tuple(hm10.shape[1:]) != (60, 90, 10) or tuple(cells.shape) != (B, 9, P, 2) or tuple(count.shape) != (B, 9):
+            raise ValueError("pose_decode expects hm10 [B,60,90,10], peaks['cells'] [B,9,P,2] and peaks['count'] [B,9]; got %s, %s, %s"
+                             % (tuple(hm10.shape), tuple(cells.shape), tuple(count.shape)))
+        out = {'index': self._new(B, 9, dtype=torch.int32), 'coords': self._new(B, 2, 9, dtype=torch.int32), 'score': self._new(B), 'score0': self._new(B)}
+        if want_tables:
+            out['V'] = self._new(B, 9, P)
+            out['M'] = self._new(B, 36, P, P)
+        self._on_stream(hm10, cells, count, *out.values())
+        _lib.check(self._lib.jcm_pose_decode(self._h, self._p(hm10), B, self._p(cells), self._p(count), P, self._p(out['index']), self._p(out['coords']),
+                                             self._p(out['score']), self._p(out['score0']), self._p(out.get('V')), self._p(out.get('M'))), 'jcm_pose_decode')
+        return out
+
+    @staticmethod
+    def _chk_decode(decode, use_sm, peaks):
+        if decode and not (use_sm and 1 <= peaks <= 4):
+            raise ValueError('decode=True needs use_sm=True and 1 <= peaks <= 4 (the candidates are pd_peaks); got use_sm=%s, peaks=%s' % (bool(use_sm), peaks))
+
+    def _add_pose(self, r, scratch, torso):
+        """forward(decode=True) / eval_forward(decode=True): pose_decode of the call's pd_peaks on its part-detector probabilities and torso map."""
+        with torch.cuda.stream(self._stream):      # the probabilities were written on the engine's stream
+            hm10 = torch.cat([r.get('pd_prob', scratch.get('pd_prob')), torso], dim=3)
+        r['pose'] = self.pose_decode(hm10, r['pd_peaks'])
+
     def softmax_argmax(self, logits, want_prob=True):
         """spatial_softmax + arg-max of the probabilities in one kernel (the tail of forward()):
         [B,H,W,K] logits -> (prob [B,H,W,K] or None, coords int32 [B,2,K])."""
@@ -324,12 +359,15 @@ class Engine:
         _lib.check(self._lib.jcm_softmax_argmax(self._h, self._p(logits), B, H, W, K, self._p(prob), self._p(coords)), 'jcm_softmax_argmax')
         return prob, coords
 
-    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0):
+    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0, decode=False):
         """The tower of main.py:522-531 in one C call.  Returns a dict with 'pd_coords',
         'sm_coords' (int32 [B,2,K]) and, if want_prob, 'pd_prob' / 'sm_prob' [B,60,90,K].  x: float32, or uint8 (byte k standing for
         float32(k) / float32(255): the same bits out as for that float image, a quarter of the bytes in).  peaks = P > 0: also 'pd_peaks'
         and, with use_sm, 'sm_peaks', the dict of hm_peaks(prob, P) of this call's probabilities (kept in a scratch tensor when
-        want_prob is False); every other entry is what the call without peaks returns."""
+        want_prob is False); every other entry is what the call without peaks returns.  decode=True (needs use_sm and 1 <= peaks <= 4): also
+        'pose', the dict of pose_decode with pd_peaks as candidates on this call's part-detector probabilities and torso map; every other
+        entry is what the call without it returns."""
+        self._chk_decode(decode, use_sm, peaks)
         u8 = self._chk_img(x, 'x')
         B, H, W, C = x.shape
         if C != 3:
@@ -357,12 +395,16 @@ class Engine:
                       self._p(r['pd_coords']), self._p(r.get('sm_coords'))), what)
         if peaks:
             self._add_peaks(r, peaks, scratch)
+        if decode:
+            self._add_pose(r, scratch, torso)
         return r
 
-    def eval_forward(self, x, y, use_sm=True, want_prob=True, peaks=0):
+    def eval_forward(self, x, y, use_sm=True, want_prob=True, peaks=0, decode=False):
         """The tower in inference mode plus the two cross-entropy losses of the graph (main.py:538-539), as eval_error
         runs it per batch (main.py:275-283).  y = y_in [B,60,90,K+1]: targets + torso channel.  Returns the dict of
-        forward() plus 'losses' (device fp32 [2]: loss_pd, loss_sm).  x: float32 or uint8, as for forward(); peaks as for forward()."""
+        forward() plus 'losses' (device fp32 [2]: loss_pd, loss_sm).  x: float32 or uint8, as for forward(); peaks and decode as for forward()
+        (the torso map is channel K of y)."""
+        self._chk_decode(decode, use_sm, peaks)
         u8 = self._chk_img(x, 'x')
         self._chk(y, 4, 'y')
         B, H, W, C = x.shape
@@ -385,6 +427,8 @@ class Engine:
                       self._p(r.get('sm_coords')), self._p(r['losses'])), what)
         if peaks:
             self._add_peaks(r, peaks, scratch)
+        if decode:
+            self._add_pose(r, scratch, y[..., K:])
         return r
 
     def window_resize(self, src, windows, oh, ow):

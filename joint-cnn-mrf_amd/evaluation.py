@@ -51,6 +51,27 @@ def peaks_to_pixels(peaks, stride=8):
     return out
 
 
+def pose_to_pixels(pose, peaks, stride=8):
+    """The dict of Engine.pose_decode ('index' [N,K], 'coords' [N,2,K], 'score' [N]) and the dict of Engine.hm_peaks it chose from ('offsets'
+    [N,K,P,2]; may be absent), device tensors or host arrays -> host fp32 [N,K,3] = ((row + d_row) * stride, (col + d_col) * stride, score):
+    the chosen cell in image pixels as peaks_to_pixels gives it, refined by the chosen peak's sub-cell offset, and the score of the pose.
+    An image without a pose (index -1) gives (-1, -1, -inf)."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    index, coords, score = host(pose['index']), host(pose['coords']), host(pose['score']).astype(np.float32)
+    if index.ndim != 2 or coords.shape != (index.shape[0], 2, index.shape[1]) or score.shape != index.shape[:1]:
+        raise ValueError('pose_to_pixels expects index [N,K], coords [N,2,K] and score [N]; got %s, %s, %s' % (index.shape, coords.shape, score.shape))
+    pick = np.maximum(index, 0).astype(np.int64)
+    if peaks.get('offsets') is not None:
+        offsets = np.take_along_axis(host(peaks['offsets']).astype(np.float32), pick[:, :, None, None], axis=2)[:, :, 0, :]      # [N,K,2]
+    else:
+        offsets = np.zeros(index.shape + (2,), np.float32)
+    out = np.empty(index.shape + (3,), np.float32)
+    out[..., :2] = (coords.transpose(0, 2, 1).astype(np.float32) + offsets) * np.float32(stride)
+    out[..., 2] = score[:, None]
+    out[index < 0] = np.array([-1, -1, -np.inf], np.float32)
+    return out
+
+
 def get_next_batch(X, Y, batch_size, shuffle=False, rng=None):
     """main.py:184-192: whole batches only -- the remainder len(X) % batch_size is dropped; `shuffle` draws a permutation."""
     import numpy as np

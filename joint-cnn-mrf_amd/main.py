@@ -75,6 +75,9 @@ def build_parser():
     parser.add_argument('--peaks', type=int, default=0, metavar='P', help='evaluation run with --predictions: also write flic_peaks_pd / flic_peaks_sm, [N,K,P,3] = '
                         '(row, col, score) in image pixels of the P highest local maxima of every heat map, refined by a quarter cell towards the higher '
                         'neighbour (evaluation.peaks_to_pixels; DESIGN.md 4.12).  1..8; 0 = off.')
+    parser.add_argument('--decode_pose', action='store_true', help='evaluation run with --use_sm, --predictions and --peaks P <= 4: of the P peaks per joint of the '
+                        'part detector, choose the ONE combination with the highest spatial-model energy (Engine.pose_decode; DESIGN.md 4.13); writes flic_pred_pose '
+                        '/ flic_pose_score and prints test_dr_pose.')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -305,6 +308,32 @@ PEAKS_IS_EVALUATION_ONLY = ('--peaks belongs to the evaluation run (it describes
 PEAKS_NEEDS_PREDICTIONS = '--peaks writes flic_peaks_pd / flic_peaks_sm into the file of --predictions: give --predictions PATH as well'
 PEAKS_NOT_WITH_U8_IMAGES = ('--peaks cannot be combined with --u8_images: the streamed byte feed (stream.ForwardStream) returns coordinates only; '
                             'run it on the float feed')
+
+
+DECODE_POSE_IS_EVALUATION_ONLY = ('--decode_pose belongs to the evaluation run (it chooses among the peaks of the test set that run predicts from); '
+                                  'it cannot be combined with --train')
+DECODE_POSE_NEEDS_USE_SM = '--decode_pose scores poses with the spatial model: give --use_sm as well'
+DECODE_POSE_NEEDS_PREDICTIONS = '--decode_pose writes flic_pred_pose / flic_pose_score into the file of --predictions: give --predictions PATH as well'
+DECODE_POSE_NEEDS_PEAKS = '--decode_pose chooses among the peaks of --peaks P: give --peaks P with 1 <= P <= 4 as well'
+DECODE_POSE_NOT_WITH_U8_IMAGES = ('--decode_pose cannot be combined with --u8_images: the streamed byte feed (stream.ForwardStream) returns coordinates only; '
+                                  'run it on the float feed')
+DECODE_POSE_NOT_WITH_MULTISCALE = ('--decode_pose cannot be combined with --multiscale: the multi-scale average has no per-scale candidates; '
+                                   'run it on the single-scale path')
+
+
+def pose_det_rate(eng, pred_pose, y, index, joints=(2,), det_radius=10):
+    """The reference's test_dr figure (evaluation.py:26-37: left wrist, radius 10) of decoded poses: pred_pose int [2,K,N] (row, col), column i judged
+    against y[index[i]], through evaluation.det_rate_from_coords in chunks of DET_CURVE_CHUNK images on `eng`'s device.  An image without a pose
+    (coordinates -1) is a miss wherever -1 is far from the target."""
+    from .evaluation import det_rate_from_coords
+    K, N = int(pred_pose.shape[1]), int(pred_pose.shape[2])
+    acc = 0.0
+    for lo in range(0, N, DET_CURVE_CHUNK):
+        hi = min(N, lo + DET_CURVE_CHUNK)
+        yb = torch.as_tensor(np.ascontiguousarray(y[index[lo:hi]][..., :K], dtype=np.float32), device=eng.device)
+        coords = torch.as_tensor(np.ascontiguousarray(np.asarray(pred_pose)[:, :, lo:hi].transpose(2, 0, 1), dtype=np.int32), device=eng.device)
+        acc += float(det_rate_from_coords(coords, eng.argmax_coords(yb), det_radius, list(joints))) * (hi - lo)
+    return acc / N
 
 
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
@@ -552,6 +581,19 @@ def main(argv=None):
         raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
     if args.train and args.u8_images and not args.device_data:
         raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
+    if args.decode_pose:
+        if args.train:
+            raise SystemExit(DECODE_POSE_IS_EVALUATION_ONLY)
+        if not args.use_sm:
+            raise SystemExit(DECODE_POSE_NEEDS_USE_SM)
+        if not args.predictions:
+            raise SystemExit(DECODE_POSE_NEEDS_PREDICTIONS)
+        if not 1 <= args.peaks <= 4:
+            raise SystemExit(DECODE_POSE_NEEDS_PEAKS)
+        if args.u8_images:
+            raise SystemExit(DECODE_POSE_NOT_WITH_U8_IMAGES)
+        if args.multiscale:
+            raise SystemExit(DECODE_POSE_NOT_WITH_MULTISCALE)
     if args.peaks:
         if args.train:
             raise SystemExit(PEAKS_IS_EVALUATION_ONLY)
@@ -583,6 +625,7 @@ def main(argv=None):
         x_train, y_train, x_test, y_test = get_dataset(args.data_dir)
         pairwise = get_pairwise_distr(args.data_dir)
     fed = None              # --u8_images: what the single-scale run moved to the devices
+    pose = None             # --decode_pose: the dict of Engine.pose_decode over the evaluated images
     peaks_pd = peaks_sm = None      # --peaks: the dicts of Engine.hm_peaks over the evaluated images, in the order of pred_pd / pred_sm
     state = restore_params(args.restore_path, args) if args.restore else None
     params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)} if state else initial_params(args, pairwise)
@@ -620,7 +663,7 @@ def main(argv=None):
         eval_tb(towers.engines[0])
         B = args.batch_size
         pd, sm = [], []
-        pk_pd, pk_sm = [], []
+        pk_pd, pk_sm, poses = [], [], []
         if args.u8_images:      # the test images as bytes (converted once, the round trip checked), streamed from pinned memory
             from .dataset import to_u8_exact
             from .stream import ForwardStream
@@ -638,17 +681,21 @@ def main(argv=None):
         else:
             for lo in range(0, (x_test.shape[0] // B) * B, B):
                 r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
-                                   use_sm=args.use_sm, peaks=args.peaks)
+                                   use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose)
                 pd.append(r['pd_coords'])
                 sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
                 if args.peaks:
                     pk_pd.append(r['pd_peaks'])
                     pk_sm.append(r['sm_peaks'] if args.use_sm else r['pd_peaks'])
+                if args.decode_pose:
+                    poses.append(r['pose'])
         to_ref = lambda c: torch.cat(c).permute(1, 2, 0).cpu().numpy()      # [2,K,N] (row, col) stacked on the last axis, main.py:425
         pred_pd, pred_sm = to_ref(pd), to_ref(sm)
         if args.peaks:
             collect = lambda parts: {f: torch.cat([p[f] for p in parts]) for f in parts[0]}
             peaks_pd, peaks_sm = collect(pk_pd), collect(pk_sm)
+            if args.decode_pose:
+                pose = {f: v.cpu().numpy() for f, v in collect(poses).items()}
     torch.cuda.synchronize()
     dt = time.time() - t0
     if args.predictions:
@@ -658,6 +705,8 @@ def main(argv=None):
         if args.peaks:
             from .evaluation import peaks_to_pixels
             mat.update(flic_peaks_pd=peaks_to_pixels(peaks_pd), flic_peaks_sm=peaks_to_pixels(peaks_sm))
+        if pose is not None:
+            mat.update(flic_pred_pose=pose['coords'].transpose(1, 2, 0), flic_pose_score=np.stack([pose['score'], pose['score0']], axis=1))
         scipy.io.savemat(args.predictions, mat)
     if args.det_curve:      # one place for every feed: the curves of the assembled predictions, counted on the first listed device
         index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus), multiscale=args.multiscale)      # towers drop batch_size % n_gpus of every batch
@@ -670,6 +719,9 @@ def main(argv=None):
         with open(args.det_curve, 'w') as fh:
             json.dump(doc, fh)
         print('test_dr: {} {}'.format(c_pd.rate(2, 10), c_sm.rate(2, 10)))      # main.py:424: left wrist, radius 10
+    if pose is not None:
+        index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus))
+        print('test_dr_pose: {}'.format(pose_det_rate(towers.engines[0], pose['coords'].transpose(1, 2, 0), y_test, index)))
     line = {'n_images': int(pred_pd.shape[2]), 'gpus': args.gpus, 'use_sm': bool(args.use_sm), 'debug': bool(args.debug),
             'multiscale': bool(args.multiscale), 'seconds': dt, 'images_per_sec': pred_pd.shape[2] / dt,
             'coords_image0_pd': pred_pd[:, :, 0].tolist()}
@@ -677,6 +729,8 @@ def main(argv=None):
         line.update(fed)
     if args.peaks:
         line['peaks'] = int(args.peaks)
+    if pose is not None:      # the share of images whose decoded pose is not the all-peak-0 pose (the independent arg-maxes)
+        line['pose_changed'] = float((pose['index'] != 0).any(axis=1).mean())
     print(json.dumps(line))
     if towers is not None:
         towers.close()
