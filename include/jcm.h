@@ -490,6 +490,30 @@ int jcm_train_loss_grads(jcm_handle h, const float* x, const float* y, int B, in
  * dx_out bf16 (the tensors the mixed-precision step keeps between the layers), grads fp32. */
 int jcm_train_layer_grads(jcm_handle h, const char* scope, const void* x, const void* dz, int B, int H, int W, float lmbd,
                           float* grads, void* dx_out);
+/* The stages of the step BETWEEN its convolutions, each on caller tensors through the host function the step itself calls, so that the tests can hold
+ * every kernel variant to float64 at channel counts and map sizes no whole step reaches (DESIGN.md 4.5a lists the variants).  After jcm_train_begin.
+ * Activation tensors (r, y, pool, dy, dz, dx) are fp32 on an fp32 handle and bf16 on a bf16 handle; statistics, losses and grads are fp32.
+ * `scope` names a conv layer with BatchNorm: it supplies gamma / beta / the moving statistics and the channel count C.
+ *   jcm_train_bn_fwd   : r [B,H,W,C] (the layer's relu(conv + b)) -> y_out = BN(r) with batch statistics (main.py:129), pool_out (may be NULL)
+ *       [B,ceil(H/2),ceil(W/2),C] = the 2x2/2 SAME max pool of y, mean_out / rstd_out [C] (may be NULL; rstd = 1/sqrt(biased var + 1e-3)); the handle keeps
+ *       the statistics for the backward pass and advances moving_mean / moving_variance (decay 0.9, Bessel-corrected variance; main.py:557).
+ *   jcm_train_bn_bwd   : dy [B,H,W,C] times dy_scale -- or, pooled != 0, the gradient of the POOLED map [B,ceil(H/2),ceil(W/2),C], which goes to the first maximum
+ *       of y in each window (dy_scale must be 1) -- with r and y (pooled only; otherwise may be NULL) of the forward pass and its statistics
+ *       (mean / rstd [C]; NULL = what the handle kept) -> dz_out [B,H,W,C] = the gradient w.r.t. conv + b (through BatchNorm and the ReLU, r > 0) and
+ *       grads[<scope>/BatchNorm/gamma, /beta, <scope>/biases] in the flat layout of jcm_train_param_info (only these slices are written).
+ *   A pool request (pool_out, pooled) on a layer with C % 4 != 0 returns JCM_ERR_ARG: the pool kernels take four channels per thread.
+ *   jcm_train_resize_bwd : the adjoint of jcm_resize_bilinear, times scale: dy [B,H,W,C] -> dx_out [B,sh,sw,C]  (the branch merge, main.py:58,67,69-70).
+ *   jcm_train_softmax_ce : main.py:220-240 per (image, joint) map of HW pixels: logits [B,HW,K], target [B,HW,Kt] (first K channels), loss [B*K];
+ *       dz (may be NULL) [B,HW,ldz]: columns < K (+)= gscale * (softmax - target) -- TF's backprop, also where a target map does not sum to one --
+ *       accumulate != 0 adds to what dz holds; columns >= K are not touched.
+ *   jcm_train_softmax_bwd: dz [B,HW,ldz] += p * (g - sum over the map's pixels of p * g), p [B,HW,K] probabilities, g [B,HW,ldg] (first K channels). */
+int jcm_train_bn_fwd(jcm_handle h, const char* scope, const void* r, int B, int H, int W, void* y_out, void* pool_out, float* mean_out, float* rstd_out);
+int jcm_train_bn_bwd(jcm_handle h, const char* scope, const void* dy, float dy_scale, int pooled, const void* r, const void* y, const float* mean,
+                     const float* rstd, int B, int H, int W, float* grads, void* dz_out);
+int jcm_train_resize_bwd(jcm_handle h, const void* dy, int B, int sh, int sw, int H, int W, int C, float scale, void* dx_out);
+int jcm_train_softmax_ce(jcm_handle h, const float* logits, const float* target, int B, int HW, int K, int Kt, float gscale, float* loss, float* dz,
+                         int ldz, int accumulate);
+int jcm_train_softmax_bwd(jcm_handle h, const float* p, const float* g, int B, int HW, int K, int ldg, float* dz, int ldz);
 /* grads: the (tower-averaged) gradients, same layout; lr: the value of lr_tf for this update
  * (main.py:492); clip_norm <= 0 disables the clip; grad_norm_out (host, may be NULL) receives the
  * global norm before clipping and makes the call synchronise. */

@@ -155,17 +155,18 @@ int conv_train_fwd_conv(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int 
   return JCM_OK;
 }
 
+// the BatchNorm half, on f.r of a layer whose L / H / W are set: batch statistics into BnSave and the moving averages, y = BN(r) (a layer without BatchNorm: y is r)
 // pool_out (optional): the 2x2/2 max pool of the layer's output goes there -- taken by the BatchNorm kernel while it writes y where that form exists
-int conv_train_fwd(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int B, int Hin, int Win, int sub, void* pool_out = nullptr) {
+// y_dst (optional): y is written there instead of the arena (jcm_train_bn_fwd: the caller's tensor)
+int conv_train_fwd_bn(jcm_ctx* c, LayerFwd& f, int B, void* pool_out, void* y_dst = nullptr) {
   TrainState* t = c->train;
-  JCM_TRY(conv_train_fwd_conv(c, f, stride, x, B, Hin, Win, sub));
   const size_t N = (size_t)B * f.H * f.W;
   if (!f.L->has_bn) {
     f.y = f.r;
     if (pool_out && !c->dry) HIP_TRY(max_pool_2x2(f.y, pool_out, bf(c), B, f.H, f.W, f.L->cout, c->stream));
     return JCM_OK;
   }
-  f.y = act(c, N * f.L->cout);
+  f.y = y_dst ? y_dst : act(c, N * f.L->cout);
   if (c->dry) return JCM_OK;
   BnSave& s = t->bn[f.scope];
   Tensor& mm = c->params[f.scope + "/BatchNorm/moving_mean"];
@@ -178,16 +179,23 @@ int conv_train_fwd(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int B, in
   return JCM_OK;
 }
 
+// one layer of the step's forward pass: the two halves
+int conv_train_fwd(jcm_ctx* c, LayerFwd& f, int stride, const void* x, int B, int Hin, int Win, int sub, void* pool_out = nullptr) {
+  JCM_TRY(conv_train_fwd_conv(c, f, stride, x, B, Hin, Win, sub));
+  return conv_train_fwd_bn(c, f, B, pool_out);
+}
+
 // ---- backward of one BN(relu(conv+b)) layer given dy (scaled by dy_scale): fills the parameter
 // gradients, returns dz (arena) for the caller to push through wgrad / dgrad.
 // pooled: the layer's output y went through the 2x2/2 max pool and dy is the POOLED gradient: the pool's backward pass is formed inside the BatchNorm backward
 // kernels where that form exists (bn_bwd_pooled); otherwise max_pool_bwd writes it to a [B, H, W, C] tensor and the plain kernels run
-int conv_train_bwd_pre(jcm_ctx* c, const LayerFwd& f, const void* dy, float dy_scale, bool pooled, int B, float* grads, void** dz_out) {
+// dz_dst (optional): dz is written there instead of the arena (jcm_train_bn_bwd: the caller's tensor)
+int conv_train_bwd_pre(jcm_ctx* c, const LayerFwd& f, const void* dy, float dy_scale, bool pooled, int B, float* grads, void** dz_out, void* dz_dst = nullptr) {
   TrainState* t = c->train;
   const size_t N = (size_t)B * f.H * f.W;
   const int C = f.L->cout;
   void* dy_full = pooled ? act(c, N * C) : nullptr;
-  void* dz = act(c, N * C);
+  void* dz = dz_dst ? dz_dst : act(c, N * C);
   *dz_out = dz;
   if (c->dry) return JCM_OK;
   const BnSave& s = t->bn[f.scope];
@@ -657,6 +665,86 @@ int jcm_train_layer_grads(jcm_handle h, const char* scope, const void* x, const 
     }
     return layer_grads(c, f, z, B, lmbd, grads, dx_out ? &dx : nullptr);
   });
+}
+
+// ---- the stages between the convolutions on caller-supplied tensors: each entry runs the host function the step runs (conv_train_fwd_bn,
+// conv_train_bwd_pre, resize_bilinear_bwd, softmax_ce, softmax_bwd), so that tests can hold every kernel variant behind it to float64 at channel
+// counts and map sizes the step itself never sees.  A stage that has no kernel for the request is refused here, with the reason.
+static int bn_stage_layer(jcm_ctx* c, const char* who, const char* scope, int B, int H, int W, bool pool, LayerFwd* f) {
+  const ConvLayer* L = scope ? conv_of(c, scope) : nullptr;
+  if (!L || !L->has_bn) return fail(JCM_ERR_ARG, std::string(who) + ": '" + (scope ? scope : "") + "' is not a conv layer with BatchNorm");
+  if (B < 1 || H < 1 || W < 1) return fail(JCM_ERR_ARG, std::string(who) + ": B, H and W must be positive");
+  if (pool && L->cout % 4)
+    return fail(JCM_ERR_ARG, std::string(who) + ": no 2x2 pool kernel for " + std::to_string(L->cout) + " channels (the pool kernels take four channels per thread: C % 4 == 0)");
+  f->scope = scope; f->L = L; f->H = H; f->W = W;
+  return JCM_OK;
+}
+
+int jcm_train_bn_fwd(jcm_handle h, const char* scope, const void* r, int B, int H, int W, void* y_out, void* pool_out, float* mean_out, float* rstd_out) {
+  JCM_TRY(need_train(h));
+  if (!r || !y_out) return fail(JCM_ERR_ARG, "bad train_bn_fwd arguments");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  if (h->call_depth > 1) return fail(JCM_ERR_STATE, "jcm_train_bn_fwd changes the handle's training state or parameters and cannot be called from the gradient-ready callback of the same handle");
+  jcm_ctx* c = h;
+  LayerFwd f;
+  JCM_TRY(bn_stage_layer(c, "train_bn_fwd", scope, B, H, W, pool_out != nullptr, &f));
+  f.r = const_cast<void*>(r);
+  JCM_TRY(with_arena(c, [&] { return conv_train_fwd_bn(c, f, B, pool_out, y_out); }));
+  const BnSave& s = c->train->bn[f.scope];
+  const size_t nb = (size_t)f.L->cout * sizeof(float);
+  if (mean_out) HIP_TRY(hipMemcpyAsync(mean_out, s.mean, nb, hipMemcpyDeviceToDevice, c->stream));
+  if (rstd_out) HIP_TRY(hipMemcpyAsync(rstd_out, s.rstd, nb, hipMemcpyDeviceToDevice, c->stream));
+  return JCM_OK;
+}
+
+int jcm_train_bn_bwd(jcm_handle h, const char* scope, const void* dy, float dy_scale, int pooled, const void* r, const void* y, const float* mean, const float* rstd,
+                     int B, int H, int W, float* grads, void* dz_out) {
+  JCM_TRY(need_train(h));
+  if (!dy || !r || !grads || !dz_out || (pooled && !y)) return fail(JCM_ERR_ARG, "bad train_bn_bwd arguments (the pooled form reads y)");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  if (h->call_depth > 1) return fail(JCM_ERR_STATE, "jcm_train_bn_bwd changes the handle's training state or parameters and cannot be called from the gradient-ready callback of the same handle");
+  jcm_ctx* c = h;
+  LayerFwd f;
+  JCM_TRY(bn_stage_layer(c, "train_bn_bwd", scope, B, H, W, pooled != 0, &f));
+  if (pooled && dy_scale != 1.0f) return fail(JCM_ERR_ARG, "train_bn_bwd: the pooled form takes dy_scale = 1 (bn_bwd_pooled has no scale)");
+  f.r = const_cast<void*>(r);
+  f.y = const_cast<void*>(y);
+  const BnSave& s = c->train->bn[f.scope];
+  const size_t nb = (size_t)f.L->cout * sizeof(float);
+  if (mean) HIP_TRY(hipMemcpyAsync(s.mean, mean, nb, hipMemcpyDeviceToDevice, c->stream));
+  if (rstd) HIP_TRY(hipMemcpyAsync(s.rstd, rstd, nb, hipMemcpyDeviceToDevice, c->stream));
+  void* dz = nullptr;
+  return with_arena(c, [&] { return conv_train_bwd_pre(c, f, dy, dy_scale, pooled != 0, B, grads, &dz, dz_out); });
+}
+
+int jcm_train_resize_bwd(jcm_handle h, const void* dy, int B, int sh, int sw, int H, int W, int C, float scale, void* dx_out) {
+  JCM_TRY(need_train(h));
+  if (!dy || !dx_out || B < 1 || sh < 1 || sw < 1 || H < 1 || W < 1 || C < 1) return fail(JCM_ERR_ARG, "bad train_resize_bwd arguments");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  HIP_TRY(resize_bilinear_bwd(dy, dx_out, bf(h), B, sh, sw, H, W, C, scale, h->stream));
+  return JCM_OK;
+}
+
+int jcm_train_softmax_ce(jcm_handle h, const float* logits, const float* target, int B, int HW, int K, int Kt, float gscale, float* loss, float* dz, int ldz,
+                         int accumulate) {
+  JCM_TRY(need_train(h));
+  if (!logits || !target || !loss || B < 1 || HW < 1 || K < 1 || Kt < K || (dz && ldz < K)) return fail(JCM_ERR_ARG, "bad train_softmax_ce arguments (Kt >= K, ldz >= K)");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  HIP_TRY(softmax_ce(logits, target, B, HW, K, Kt, gscale, loss, dz, ldz, accumulate, h->stream));
+  return JCM_OK;
+}
+
+int jcm_train_softmax_bwd(jcm_handle h, const float* p, const float* g, int B, int HW, int K, int ldg, float* dz, int ldz) {
+  JCM_TRY(need_train(h));
+  if (!p || !g || !dz || B < 1 || HW < 1 || K < 1 || ldg < K || ldz < K) return fail(JCM_ERR_ARG, "bad train_softmax_bwd arguments (ldg >= K, ldz >= K)");
+  DeviceGuard guard(h->device);
+  CallOrder order(h);
+  HIP_TRY(softmax_bwd(p, g, B, HW, K, ldg, dz, ldz, h->stream));
+  return JCM_OK;
 }
 
 }  // extern "C"

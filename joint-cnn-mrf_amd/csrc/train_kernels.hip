@@ -123,7 +123,7 @@ __global__ void bn_stats_finish_kernel(const double* __restrict__ partial, int b
   const double s = fold_partials(partial, blocks, 2, C, 0, c), ss = fold_partials(partial, blocks, 2, C, 1, c);
   if (threadIdx.x != 0) return;
   const double m = s / N;
-  double var = ss / N - m * m;
+  double var = N > 1.0 ? ss / N - m * m : 0.0;      // one sample has variance 0; ss - m^2 would be the rounding of its fp32 square, up to 2^-24 x^2 against eps
   if (var < 0.0) var = 0.0;
   mean[c] = (float)m;
   rstd[c] = (float)(1.0 / sqrt(var + (double)eps));

@@ -165,6 +165,83 @@ class Trainer:
         off, cnt = next((o, c) for n, o, c in self.layout if n == scope + '/weights')
         return self.grads[off:off + cnt].cpu().numpy(), dx
 
+    # ------------------------------------------------------------------ the stages between the convolutions, one at a time (include/jcm.h)
+    def _act_dtype(self):
+        return torch.bfloat16 if self.eng.precision == 'bf16' else torch.float32
+
+    def _slice(self, name):
+        off, cnt = next((o, c) for n, o, c in self.layout if n == name)
+        return self.grads[off:off + cnt]
+
+    def bn_forward(self, scope, r, pool=False):
+        """Training-mode BatchNorm of layer `scope` on r [B,H,W,C] (jcm_train_bn_fwd): -> (y, pooled y or None, mean [C], rstd [C]); the handle's
+        moving statistics advance.  Tensors of the engine's activation type (bf16 engines: bfloat16); the statistics are float32."""
+        e = self.eng
+        e._chk(r, 4, 'r', self._act_dtype())
+        B, H, W, C = r.shape
+        y = torch.empty_like(r)
+        p = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=r.dtype, device=e.device) if pool else None
+        mean, rstd = e._new(C), e._new(C)
+        _lib.check(self._lib.jcm_train_bn_fwd(e._h, scope.encode(), e._p(r), B, H, W, e._p(y), e._p(p), e._p(mean), e._p(rstd)), 'jcm_train_bn_fwd(%s)' % scope)
+        return y, p, mean, rstd
+
+    def bn_backward(self, scope, dy, r, y=None, mean=None, rstd=None, dy_scale=1.0, pooled=False):
+        """Backward of BN(relu(.)) of layer `scope` (jcm_train_bn_bwd): dy [B,H,W,C], or with pooled=True the gradient of the 2x2-pooled map (y required)
+        -> (dz [B,H,W,C], dgamma, dbeta, dbias: views of self.grads).  mean / rstd: the forward pass's (None: what the handle kept)."""
+        e = self.eng
+        dt = self._act_dtype()
+        e._chk(r, 4, 'r', dt)
+        e._chk(dy, 4, 'dy', dt)
+        B, H, W, C = r.shape
+        if tuple(dy.shape) != ((B, (H + 1) // 2, (W + 1) // 2, C) if pooled else (B, H, W, C)):
+            raise ValueError('dy has shape %s for r %s (pooled=%s)' % (tuple(dy.shape), tuple(r.shape), bool(pooled)))
+        if y is not None and (e._chk(y, 4, 'y', dt).shape != r.shape):
+            raise ValueError('y must have the shape of r')
+        for t, n in ((mean, 'mean'), (rstd, 'rstd')):
+            if t is not None and (e._chk(t, 1, n).shape[0] != C):
+                raise ValueError('%s must be [%d]' % (n, C))
+        dz = torch.empty_like(r)
+        _lib.check(self._lib.jcm_train_bn_bwd(e._h, scope.encode(), e._p(dy), float(dy_scale), int(bool(pooled)), e._p(r), e._p(y), e._p(mean), e._p(rstd),
+                                              B, H, W, e._p(self.grads), e._p(dz)), 'jcm_train_bn_bwd(%s)' % scope)
+        return dz, self._slice(scope + '/BatchNorm/gamma'), self._slice(scope + '/BatchNorm/beta'), self._slice(scope + '/biases')
+
+    def resize_backward(self, dy, h, w, scale=1.0):
+        """The adjoint of Engine.resize_bilinear from [B,h,w,C], times scale (jcm_train_resize_bwd): dy [B,H,W,C] -> dx [B,h,w,C]."""
+        e = self.eng
+        e._chk(dy, 4, 'dy', self._act_dtype())
+        B, H, W, C = dy.shape
+        dx = torch.empty((B, h, w, C), dtype=dy.dtype, device=e.device)
+        _lib.check(self._lib.jcm_train_resize_bwd(e._h, e._p(dy), B, h, w, H, W, C, float(scale), e._p(dx)), 'jcm_train_resize_bwd')
+        return dx
+
+    def softmax_ce(self, logits, target, gscale=1.0, dz=None, accumulate=False):
+        """main.py:220-240 per map (jcm_train_softmax_ce): logits [B,HW,K], target [B,HW,Kt >= K] -> loss [B,K]; dz [B,HW,ldz >= K] (optional, written
+        in place): columns < K (+)= gscale * (softmax - target)."""
+        e = self.eng
+        e._chk(logits, 3, 'logits')
+        e._chk(target, 3, 'target')
+        B, HW, K = logits.shape
+        if tuple(target.shape[:2]) != (B, HW) or target.shape[2] < K:
+            raise ValueError('target must be [%d,%d,>=%d]; got %s' % (B, HW, K, tuple(target.shape)))
+        if dz is not None and (tuple(e._chk(dz, 3, 'dz').shape[:2]) != (B, HW) or dz.shape[2] < K):
+            raise ValueError('dz must be [%d,%d,>=%d]; got %s' % (B, HW, K, tuple(dz.shape)))
+        loss = e._new(B, K)
+        _lib.check(self._lib.jcm_train_softmax_ce(e._h, e._p(logits), e._p(target), B, HW, K, target.shape[2], float(gscale), e._p(loss), e._p(dz),
+                                                  dz.shape[2] if dz is not None else 0, int(bool(accumulate))), 'jcm_train_softmax_ce')
+        return loss
+
+    def softmax_backward(self, p, g, dz):
+        """dz [B,HW,ldz] += p * (g - sum_px p g) per map (jcm_train_softmax_bwd): p [B,HW,K], g [B,HW,ldg >= K]; dz in place."""
+        e = self.eng
+        e._chk(p, 3, 'p')
+        e._chk(g, 3, 'g')
+        e._chk(dz, 3, 'dz')
+        B, HW, K = p.shape
+        if tuple(g.shape[:2]) != (B, HW) or tuple(dz.shape[:2]) != (B, HW) or g.shape[2] < K or dz.shape[2] < K:
+            raise ValueError('g and dz must be [%d,%d,>=%d]; got %s, %s' % (B, HW, K, tuple(g.shape), tuple(dz.shape)))
+        _lib.check(self._lib.jcm_train_softmax_bwd(e._h, e._p(p), e._p(g), B, HW, K, g.shape[2], e._p(dz), dz.shape[2]), 'jcm_train_softmax_bwd')
+        return dz
+
     def grads_dict(self):
         """The flat gradient buffer as {TF variable name: numpy array} (reference shapes unknown here: flat)."""
         g = self.grads.cpu().numpy()
