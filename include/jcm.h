@@ -345,6 +345,26 @@ int jcm_window_resize(jcm_handle h, const float* src, int nsrc, int H, int W, in
 /* np.average over the G scale copies of each image (main.py:413-414): in [n*G, M] -> out [n, M]. */
 int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float* out);
 
+/* -- mirrored test-time evaluation -----------------------------------------------------
+ * The maps of an image averaged with the un-mirrored maps of its mirror image: jcm_mirror_pairs makes the batch the tower sees,
+ * jcm_mirror_merge folds the tower's maps back.  Both enqueue one launch on the handle's stream and do not synchronise.
+ * jcm_mirror_pairs: x [B,H,W,C] device, float32 (x_u8 == 0) or uint8 (x_u8 == 1); out [2B,H,W,C] device, the same type, not overlapping x:
+ *   out[2b]              = x[b]
+ *   out[2b+1][y][xx][c]  = x[b][y][W-1-xx][c]
+ * Pure bit copies, any C >= 1 (images C = 3, the torso map C = 1).  JCM_ERR_ARG for a null pointer, B, H, W or C below 1, H * W * C >= 2^31 and a
+ * row of more than 65536 bytes (W * C * sizeof(value); a row is staged in LDS); nothing is launched then. */
+int jcm_mirror_pairs(jcm_handle h, const void* x, int x_u8, int B, int H, int W, int C, void* out);
+/* jcm_mirror_merge: hm [n*G,HH,WW,K] device fp32, copy g of group i is entry i*G+g, G even; the odd g are maps of mirrored inputs.
+ * out [n,HH,WW,K] device fp32, not overlapping hm:
+ *   out[i,y,x,k] = (float)( (v_0 + v_1 + .. + v_{G-1}) / (double)G ),  the sum in double, g = 0 .. G-1 in this order,
+ *   v_g = hm[i*G+g, y, x, k]              for even g,
+ *   v_g = hm[i*G+g, y, WW-1-x, perm[k]]   for odd g
+ * -- the arithmetic of jcm_group_mean, so G = 2 is exact and every G is reproduced bit for bit by a sequential float64 loop.
+ * perm: HOST array of K entries, a permutation of 0..K-1; NULL = the first K entries of the FLIC left/right table {3,4,5,0,1,2,7,6,8,9}
+ * (augmentation.py:20; needs K <= 10 and, as a permutation, K in {6, 8, 9, 10}).  JCM_ERR_ARG for odd G, G < 2, n, HH, WW or K below 1, K > 64,
+ * HH * WW * K >= 2^31, a perm that is not a permutation of 0..K-1 and a null hm or out; nothing is launched then. */
+int jcm_mirror_merge(jcm_handle h, const float* hm, int n, int G, int HH, int WW, int K, const int32_t* perm, float* out);
+
 /* -- training-time augmentation (augmentation.py:58-78; main.py:494-497) ----------------------------
  * x [B,H,W,3], y [B,h,w,10] (= y_in, main.py:488), params [B,6] = (flip, delta, factor, angle, rh, rw):
  * all device fp32; x_out / y_out same shapes, must not alias the inputs.  Enqueues, does not synchronise.

@@ -4,6 +4,7 @@
 // The semantics are DESIGN.md 4.7 (a restatement of the TF-1.x ops, float32 in the order written; tests/augment_ref.py).
 // Three launches: the per-image channel sums of the brightened image (partials, no atomics), the image gather (crop taps ->
 // rotated samples -> source taps, the colour steps applied per source tap) and one work group per (image, heat-map channel).
+#include "hm_flip.h"
 #include "kernels.h"
 #include "u8.h"
 
@@ -16,7 +17,7 @@ constexpr int kAugRed = 192;            // reduction width: a multiple of 3, so 
 constexpr int kAugImgThreads = 256;
 constexpr int kAugHmThreads = 512;
 constexpr float kCropSize = 0.95f;      // augmentation.py:40
-__constant__ int kHmFlipPerm[10] = {3, 4, 5, 0, 1, 2, 7, 6, 8, 9};     // augmentation.py:20
+static_assert(kHmFlipChannels == 10, "aug_hm_kernel permutes the 10 heat-map channels by kHmFlipPerm (hm_flip.h)");
 
 // where image b of the batch comes from: image b of the array itself, or image idx[b] of a data set (jcm_augment_train_indexed; the
 // indices travel in the kernel arguments and were checked on the host)

@@ -318,6 +318,13 @@ constexpr int kPoseMaxB = 1 << 20;
 hipError_t pose_decode(const float* hm10, int B, const int32_t* cells, const int32_t* count, int P, const float* sp_energy, const float* sp_bias,
                        const float* bn_scale, const float* bn_shift, float* V, float* M, float* pscore, int32_t* ppose, int32_t* index, int32_t* coords,
                        float* score, float* score0, hipStream_t st);
+// ---- mirror.hip : mirrored test-time evaluation ----------------------------------
+// out[2b] = x[b], out[2b+1][y][xx][c] = x[b][y][W-1-xx][c]: bit copies of float (x_u8 false) or uint8 values, x [B,H,W,C] -> out [2B,H,W,C]; one launch.
+// W * C * sizeof(value) <= 65536.
+hipError_t mirror_pairs(const void* x, bool x_u8, int B, int H, int W, int C, void* out, hipStream_t st);
+// out[i,y,x,k] = float(sum over g < G, in order, in double, of v_g / double(G)), v_g = hm[i*G+g,y,x,k] (g even) or hm[i*G+g,y,WW-1-x,perm[k]] (g odd);
+// hm [n*G,HH,WW,K], G even, perm: K HOST entries, a permutation of 0..K-1 (the caller checks it), K <= 64; one launch.
+hipError_t mirror_merge(const float* hm, int n, int G, int HH, int WW, int K, const int* perm, float* out, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

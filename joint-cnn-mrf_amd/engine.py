@@ -359,14 +359,17 @@ class Engine:
         _lib.check(self._lib.jcm_softmax_argmax(self._h, self._p(logits), B, H, W, K, self._p(prob), self._p(coords)), 'jcm_softmax_argmax')
         return prob, coords
 
-    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0, decode=False):
+    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0, decode=False, flip_test=False):
         """The tower of main.py:522-531 in one C call.  Returns a dict with 'pd_coords',
         'sm_coords' (int32 [B,2,K]) and, if want_prob, 'pd_prob' / 'sm_prob' [B,60,90,K].  x: float32, or uint8 (byte k standing for
         float32(k) / float32(255): the same bits out as for that float image, a quarter of the bytes in).  peaks = P > 0: also 'pd_peaks'
         and, with use_sm, 'sm_peaks', the dict of hm_peaks(prob, P) of this call's probabilities (kept in a scratch tensor when
         want_prob is False); every other entry is what the call without peaks returns.  decode=True (needs use_sm and 1 <= peaks <= 4): also
         'pose', the dict of pose_decode with pd_peaks as candidates on this call's part-detector probabilities and torso map; every other
-        entry is what the call without it returns."""
+        entry is what the call without it returns.  flip_test=True: mirrored test-time evaluation -- ONE forward on
+        mirror_pairs(x) (2B images; with use_sm on mirror_pairs(torso)), 'pd_prob' / 'sm_prob' the mirror_merge of its probabilities, [B,...],
+        the coords argmax_coords of the merged maps; peaks and decode work on the merged maps (kept in scratch when want_prob is False) and the
+        unmirrored torso map.  False changes nothing."""
         self._chk_decode(decode, use_sm, peaks)
         u8 = self._chk_img(x, 'x')
         B, H, W, C = x.shape
@@ -378,6 +381,8 @@ class Engine:
             self._chk(torso, 4, 'torso')
             if tuple(torso.shape) != (B, 60, 90, 1):
                 raise ValueError('torso must be [B,60,90,1], got %s' % (tuple(torso.shape),))
+        if flip_test:
+            return self._forward_flip(x, torso, use_sm, want_prob, peaks, decode)
         hh, ww, K = _hm_size(H), _hm_size(W), self.n_joints
         r = {'pd_coords': self._new(B, 2, K, dtype=torch.int32)}
         if want_prob:
@@ -393,6 +398,21 @@ class Engine:
         _lib.check(fn(self._h, self._p(x), self._p(torso if use_sm else None), B, H, W, int(bool(use_sm)),
                       self._p(r.get('pd_prob', scratch.get('pd_prob'))), self._p(r.get('sm_prob', scratch.get('sm_prob'))),
                       self._p(r['pd_coords']), self._p(r.get('sm_coords'))), what)
+        if peaks:
+            self._add_peaks(r, peaks, scratch)
+        if decode:
+            self._add_pose(r, scratch, torso)
+        return r
+
+    def _forward_flip(self, x, torso, use_sm, want_prob, peaks, decode):
+        """forward(flip_test=True): the existing forward on the 2B interleaved images, its maps merged pair by pair."""
+        r2 = self.forward(self.mirror_pairs(x), self.mirror_pairs(torso) if use_sm else None, use_sm=use_sm, want_prob=True)
+        r, scratch = {}, {}
+        for key in (('pd', 'sm') if use_sm else ('pd',)):
+            self._on_stream(r2[key + '_prob'])
+            prob = self.mirror_merge(r2[key + '_prob'])
+            r[key + '_coords'] = self.argmax_coords(prob)
+            (r if want_prob else scratch)[key + '_prob'] = prob
         if peaks:
             self._add_peaks(r, peaks, scratch)
         if decode:
@@ -453,6 +473,51 @@ class Engine:
         for d in x.shape[1:]:
             m *= int(d)
         _lib.check(self._lib.jcm_group_mean(self._h, self._p(x.contiguous()), n, group, m, self._p(out)), 'jcm_group_mean')
+        return out
+
+    def mirror_pairs(self, x):
+        """x [B,H,W,C] float32 or uint8 -> [2B,H,W,C] of the same type: out[2b] = x[b], out[2b+1] = x[b] mirrored left/right (out[2b+1,y,xx,c] =
+        x[b,y,W-1-xx,c]); bit copies, one launch (include/jcm.h: jcm_mirror_pairs)."""
+        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError('mirror_pairs: x must be a float32 or uint8 torch tensor, got %s' % (getattr(x, 'dtype', type(x)),))
+        if x.dim() != 4:
+            raise ValueError('mirror_pairs: x must have 4 dims (NHWC), got shape %s' % (tuple(x.shape),))
+        self._chk(x, 4, 'x', x.dtype)
+        B, H, W, C = x.shape
+        if min(B, H, W, C) < 1:
+            raise ValueError('mirror_pairs: x must not be empty, got shape %s' % (tuple(x.shape),))
+        out = self._new(2 * B, H, W, C, dtype=x.dtype)
+        self._on_stream(x, out)
+        _lib.check(self._lib.jcm_mirror_pairs(self._h, self._p(x), int(x.dtype == torch.uint8), B, H, W, C, self._p(out)), 'jcm_mirror_pairs')
+        return out
+
+    def mirror_merge(self, hm, group=2, perm=None):
+        """hm [n*group,HH,WW,K] float32, copy g of group i at i*group+g, the odd g maps of mirrored inputs -> [n,HH,WW,K]: the mean over the group
+        (float64, g in order, as group_mean) with the odd copies read mirrored back, out[i,y,x,k] from hm[i*group+g,y,WW-1-x,perm[k]].  perm: K host
+        integers, a permutation of 0..K-1; None = the FLIC left/right table [3,4,5,0,1,2,7,6,8,9] cut to K (include/jcm.h: jcm_mirror_merge)."""
+        if not isinstance(hm, torch.Tensor) or hm.dtype != torch.float32:
+            raise ValueError('mirror_merge: hm must be a float32 torch tensor, got %s' % (getattr(hm, 'dtype', type(hm)),))
+        if hm.dim() != 4:
+            raise ValueError('mirror_merge: hm must have 4 dims [n*group,HH,WW,K], got shape %s' % (tuple(hm.shape),))
+        self._chk(hm, 4, 'hm')
+        group = int(group)
+        N, HH, WW, K = hm.shape
+        if group < 2 or group % 2:
+            raise ValueError('mirror_merge: group = %d; the copies come in (plain, mirrored) pairs, so it is even and >= 2' % group)
+        if N < group or N % group or min(HH, WW, K) < 1:
+            raise ValueError('mirror_merge: hm %s is not a whole number of groups of %d non-empty maps' % (tuple(hm.shape), group))
+        table = None
+        if perm is not None:
+            table = np.asarray(perm).reshape(-1)
+            if table.dtype.kind not in 'iu' or table.shape[0] != K or sorted(table.tolist()) != list(range(K)):
+                raise ValueError('mirror_merge: perm must be a permutation of 0..%d, got %s' % (K - 1, list(np.asarray(perm).reshape(-1).tolist())))
+            table = np.ascontiguousarray(table, dtype=np.int32)
+        elif K > 10 or sorted(_lib.HM_FLIP_PERM[:K]) != list(range(K)):
+            raise ValueError('mirror_merge: the FLIC left/right table cut to K = %d channels is not a permutation; give perm' % K)
+        out = self._new(N // group, HH, WW, K)
+        self._on_stream(hm, out)
+        _lib.check(self._lib.jcm_mirror_merge(self._h, self._p(hm), N // group, group, HH, WW, K,
+                                              table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if table is not None else None, self._p(out)), 'jcm_mirror_merge')
         return out
 
     def augment_train(self, x, y, params, x_out=None, y_out=None):

@@ -147,16 +147,17 @@ def _to_device_batch(bx, by, engine):
     return x, y
 
 
-def eval_curves(X, Y, engine, batch_size, use_sm=True, radii=range(1, 21)):
+def eval_curves(X, Y, engine, batch_size, use_sm=True, radii=range(1, 21), flip_test=False):
     """Detection-rate curves of a whole set: every image goes through engine.forward once (the last batch may be partial -- unlike
     eval_error, nothing is dropped) and its coordinates into two accumulators.  X [N,480,720,3] float or uint8, Y [N,60,90,K+1], numpy or
     torch, host or device.  Returns (DetCurve of the part detector, DetCurve of the spatial model); without use_sm the second counts the part
-    detector's coordinates too (main.py:535)."""
+    detector's coordinates too (main.py:535).  flip_test=True: the coordinates of the mirrored test-time evaluation (Engine.forward(flip_test=True))
+    are judged, against the same targets."""
     K = engine.n_joints
     pd, sm = DetCurve(engine, radii), DetCurve(engine, radii)
     for lo in range(0, len(X), batch_size):
         x, y = _to_device_batch(X[lo:lo + batch_size], Y[lo:lo + batch_size], engine)
-        r = engine.forward(x, y[..., K:].contiguous() if use_sm else None, use_sm=use_sm, want_prob=False)
+        r = engine.forward(x, y[..., K:].contiguous() if use_sm else None, use_sm=use_sm, want_prob=False, flip_test=flip_test)
         pd.update(r['pd_coords'], y)
         sm.update(r['sm_coords'] if use_sm else r['pd_coords'], y)
     return pd, sm

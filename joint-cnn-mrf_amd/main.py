@@ -78,6 +78,9 @@ def build_parser():
     parser.add_argument('--decode_pose', action='store_true', help='evaluation run with --use_sm, --predictions and --peaks P <= 4: of the P peaks per joint of the '
                         'part detector, choose the ONE combination with the highest spatial-model energy (Engine.pose_decode; DESIGN.md 4.13); writes flic_pred_pose '
                         '/ flic_pose_score and prints test_dr_pose.')
+    parser.add_argument('--flip_test', action='store_true', help='evaluation run: mirrored test-time evaluation -- every image goes through the tower in both '
+                        'orientations and the maps of the mirror image, read back with the left/right joints exchanged, are averaged with the plain ones '
+                        '(Engine.forward(flip_test=True); with --multiscale on top of the 8 scales, 16 copies per image; DESIGN.md 4.14).')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -233,7 +236,7 @@ def get_predictions(X_np, Y_np, sess=None):
     """main.py:382-425 (multi-scale test-time evaluation) -> (pred_coords_pd, pred_coords_sm), each
     [2, n_joints, N]; `sess` is accepted for signature compatibility and ignored."""
     from . import multiscale
-    return multiscale.get_predictions(engine(), X_np, Y_np, use_sm=hps.use_sm)
+    return multiscale.get_predictions(engine(), X_np, Y_np, use_sm=hps.use_sm, flip_test=bool(getattr(hps, 'flip_test', False)))
 
 
 # ------------------------------------------------------------------ data set, session files (main.py:286-299,604-612,666)
@@ -334,6 +337,10 @@ def pose_det_rate(eng, pred_pose, y, index, joints=(2,), det_radius=10):
         coords = torch.as_tensor(np.ascontiguousarray(np.asarray(pred_pose)[:, :, lo:hi].transpose(2, 0, 1), dtype=np.int32), device=eng.device)
         acc += float(det_rate_from_coords(coords, eng.argmax_coords(yb), det_radius, list(joints))) * (hi - lo)
     return acc / N
+
+
+FLIP_TEST_IS_EVALUATION_ONLY = ('--flip_test belongs to the evaluation run (it averages the heat maps of a test image and of its mirror image); '
+                                'it cannot be combined with --train')
 
 
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
@@ -579,6 +586,8 @@ def main(argv=None):
         raise SystemExit('--restore needs --restore_path <checkpoint prefix or .npz> (the reference hard-codes best_model_name, main.py:443)')
     if args.train and args.det_curve:
         raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
+    if args.train and args.flip_test:
+        raise SystemExit(FLIP_TEST_IS_EVALUATION_ONLY)
     if args.train and args.u8_images and not args.device_data:
         raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
     if args.decode_pose:
@@ -654,7 +663,8 @@ def main(argv=None):
         eval_tb(engine())
         if args.peaks:
             from . import multiscale
-            pred_pd, pred_sm, peaks_pd, peaks_sm = multiscale.get_predictions(engine(), np.asarray(x_test), np.asarray(y_test), use_sm=hps.use_sm, peaks=args.peaks)
+            pred_pd, pred_sm, peaks_pd, peaks_sm = multiscale.get_predictions(engine(), np.asarray(x_test), np.asarray(y_test), use_sm=hps.use_sm, peaks=args.peaks,
+                                                                              flip_test=args.flip_test)
         else:
             pred_pd, pred_sm = get_predictions(np.asarray(x_test), np.asarray(y_test))                 # main.py:674
     else:                                                                                              # single scale, sharded over the towers
@@ -664,7 +674,19 @@ def main(argv=None):
         B = args.batch_size
         pd, sm = [], []
         pk_pd, pk_sm, poses = [], [], []
-        if args.u8_images:      # the test images as bytes (converted once, the round trip checked), streamed from pinned memory
+        if args.u8_images and args.flip_test:      # byte batches through the towers' byte forward (the streamed feed has no mirrored evaluation)
+            from .dataset import to_u8_exact
+            xb = to_u8_exact(x_test)
+            n_moved = 0
+            for lo in range(0, (xb.shape[0] // B) * B, B):
+                bx, bt = np.ascontiguousarray(xb[lo:lo + B]), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32)
+                r = towers.forward(bx, bt, use_sm=args.use_sm, flip_test=True)
+                pd.append(r['pd_coords'])
+                sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
+                for a, b in towers.slices(B):      # what the towers took of the batch
+                    n_moved += bx[a:b].nbytes + (bt[a:b].nbytes if args.use_sm else 0)
+            fed = {'image_dtype': 'uint8', 'bytes_uploaded': int(n_moved)}
+        elif args.u8_images:      # the test images as bytes (converted once, the round trip checked), streamed from pinned memory
             from .dataset import to_u8_exact
             from .stream import ForwardStream
             xb = to_u8_exact(x_test)      # (works through a memory-mapped file in slices; float64 or other data is refused)
@@ -681,7 +703,7 @@ def main(argv=None):
         else:
             for lo in range(0, (x_test.shape[0] // B) * B, B):
                 r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
-                                   use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose)
+                                   use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, flip_test=args.flip_test)
                 pd.append(r['pd_coords'])
                 sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
                 if args.peaks:
@@ -727,6 +749,8 @@ def main(argv=None):
             'coords_image0_pd': pred_pd[:, :, 0].tolist()}
     if fed is not None:
         line.update(fed)
+    if args.flip_test:
+        line['flip_test'] = True
     if args.peaks:
         line['peaks'] = int(args.peaks)
     if pose is not None:      # the share of images whose decoded pose is not the all-peak-0 pose (the independent arg-maxes)

@@ -56,23 +56,33 @@ def get_different_scales(engine, x, pad_array, crop_array, orig_h, orig_w):
     return engine.window_resize(x.contiguous(), windows, orig_h, orig_w)
 
 
-def scale_hm_back(engine, hms, pad_array, crop_array, orig_h, orig_w):
-    """main.py:351-379.  hms [N*8, 60, 90, K] (copy s of image i at i*8+s) -> same shape."""
+def scale_hm_back(engine, hms, pad_array, crop_array, orig_h, orig_w, copies_per_scale=1):
+    """main.py:351-379.  hms [N*8, 60, 90, K] (copy s of image i at i*8+s) -> same shape.  copies_per_scale = c > 1: every scale holds c
+    consecutive maps (hms [N*8*c, ...], map j of scale s of image i at i*8*c + s*c + j) and the back-window of scale s is applied to all c of them."""
     wins = _back_windows(pad_array, crop_array, orig_h, orig_w)
     ns = len(wins)
-    if hms.shape[0] % ns:
-        raise ValueError('expected a multiple of %d heat maps' % ns)
-    windows = [(i,) + wins[i % ns] for i in range(hms.shape[0])]
+    cps = int(copies_per_scale)
+    if cps < 1:
+        raise ValueError('copies_per_scale must be >= 1, got %r' % (copies_per_scale,))
+    if hms.shape[0] % (ns * cps):
+        raise ValueError('expected a multiple of %d heat maps' % (ns * cps))
+    windows = [(i,) + wins[(i // cps) % ns] for i in range(hms.shape[0])]
     return engine.window_resize(hms.contiguous(), windows, orig_h, orig_w)
 
 
-def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8, peaks=0):
+def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8, peaks=0, flip_test=False):
     """main.py:382-425 without the det_rate bookkeeping: for every image the 8 rescaled copies go
     through the tower (with the UNSCALED target maps repeated, main.py:405), the heat maps are
     scaled back and averaged, and the arg-max coordinates are returned as the reference returns
     them: int arrays [2, K, N] (row, col) for the part detector and the spatial model.
     peaks = P > 0: returns (pd, sm, pd_peaks, sm_peaks), the last two the dicts of Engine.hm_peaks(., P) on the averaged maps the
-    coordinates are the arg-max of, collected over the image groups (device tensors [N,K,P,...]; sm_peaks is pd_peaks without use_sm)."""
+    coordinates are the arg-max of, collected over the image groups (device tensors [N,K,P,...]; sm_peaks is pd_peaks without use_sm).
+    flip_test=True: mirrored test-time evaluation on top of the scales, DEFINED by this order of steps: (1) scale first, exactly
+    as without it: get_different_scales gives the 8m copies; (2) Engine.mirror_pairs makes them 16m, copy 2s+j of image i at i*16+2s+j (j = 1 the
+    mirror image of scale s); (3) the same for the repeated torso maps; (4) one forward; (5) scale back, the back-window of scale s applied to both
+    members of its pair (scale_hm_back(copies_per_scale=2)); (6) Engine.mirror_merge(group=16), which reads the odd copies mirrored back; (7) arg-max
+    and peaks as before.  "Mirror the image, then scale it" would be a different function: several back-windows are not symmetric (the 90-wide map
+    at 1/1.3 is cut as 10 | 69 | 11), so the window of scale s applied to a mirrored map covers other columns than its mirror image would."""
     dev = engine.device
     K = engine.n_joints
     n = X.shape[0]
@@ -85,13 +95,19 @@ def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8, peaks=0):
         m = x.shape[0]
         xs = get_different_scales(engine, x, PAD_ARRAY, CROP_ARRAY, in_h, in_w)                 # [m*8,480,720,3]
         torso = y[:, :, :, K:].repeat_interleave(8, dim=0).contiguous()                           # main.py:405,528
+        if flip_test:
+            xs = engine.mirror_pairs(xs)                                                          # [m*16,480,720,3]
+            torso = engine.mirror_pairs(torso) if use_sm else torso
+            mean = lambda prob: engine.mirror_merge(scale_hm_back(engine, prob, PAD_ARRAY, CROP_ARRAY, 60, 90, copies_per_scale=2), group=16)
+        else:
+            mean = lambda prob: engine.group_mean(scale_hm_back(engine, prob, PAD_ARRAY, CROP_ARRAY, 60, 90), 8)   # :407,413
         r = engine.forward(xs, torso if use_sm else None, use_sm=use_sm, want_prob=True)
-        hm_pd = engine.group_mean(scale_hm_back(engine, r['pd_prob'], PAD_ARRAY, CROP_ARRAY, 60, 90), 8)   # :407,413
+        hm_pd = mean(r['pd_prob'])
         pd_all.append(engine.argmax_coords(hm_pd))                                                # :416
         if peaks:
             pd_pk.append(engine.hm_peaks(hm_pd, max_peaks=peaks))
         if use_sm:
-            hm_sm = engine.group_mean(scale_hm_back(engine, r['sm_prob'], PAD_ARRAY, CROP_ARRAY, 60, 90), 8)
+            hm_sm = mean(r['sm_prob'])
             sm_all.append(engine.argmax_coords(hm_sm))
             if peaks:
                 sm_pk.append(engine.hm_peaks(hm_sm, max_peaks=peaks))
