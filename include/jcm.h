@@ -165,6 +165,9 @@ int jcm_abi_version(void);
  *              kernels of sm_lds.hip); 1 = direct sliding-window kernel, the independent cross-check.  Both pass the same parity
  *              tests.  (Rounds 1-4 also had two rocFFT routes, 0 and 2; the library links no FFT library any more.)
  *              "sm_chunk": images per slice of the training step's spatial-model backward.
+ * "torso_algo": (default 1, range 1|1, settable at any time, no environment variable) the route of jcm_torso_infer: 1 = direct sliding-window
+ *              kernel.  A key with ONE value, kept so that a second route can be added without a new key; it is listed here and not as a row of
+ *              the table above, whose key list tests/test_gpu_options.py pins (tests/test_gpu_torso.py holds this key's round trip).
  * "micro_batch": jcm_forward walks its batch in slices of this many images, so the workspace is
  *              sized for one slice (a rank's share of BASELINE configs[3]'s 2048 images fits).  0
  *              = 256 for bf16 handles, 64 for fp32 handles. */
@@ -305,6 +308,36 @@ int jcm_hm_peaks(jcm_handle h, const float* hm, int B, int HH, int WW, int K, in
  * spatial-model parameters; nothing is launched and no output is touched then.  Uses the handle's workspace, like jcm_sm_forward. */
 int jcm_pose_decode(jcm_handle h, const float* hm10, int B, const int32_t* cells, const int32_t* count, int P,
                     int32_t* index, int32_t* coords, float* score, float* score0, float* V, float* M);
+
+/* Torso map from the part detector: the torso cell that the nine part-detector maps and the nine learned priors e_{j|torso} explain best, and the
+ * blob at it -- the tenth channel jcm_sm_forward needs, for an image that has no annotation.  Fixed geometry like jcm_pose_decode's:
+ * HH = 60, WW = 90, K = 9, 120x180 priors.
+ * prob: device fp32 [B,60,90,9], the part-detector probabilities (what jcm_forward writes as pd_prob).
+ * Write a = (a_y,a_x) and t = (t_y,t_x) for cells of the map, u_j(a) = softplus5(bn_sm(prob[b,a,j])), the likelihood of the spatial-model forward
+ * (the same device expression; channel j of bn_sm, the tenth BatchNorm channel is not used), e_{j|torso} the handle's softplus'd prior [120,180] of
+ * pair <j>_torso, d = 1e-6, and the index convention of jcm_pose_decode ([59 + dy, 89 + dx] is where conv_mrf reads the prior for the displacement
+ * joint - torso = (dy, dx)):
+ *   C_j(t) = sum over the 5400 cells a of   e_{j|torso}[59 + (a_y - t_y), 89 + (a_x - t_x)] * u_j(a)                     j = 0 .. 8
+ *   E(t)   = ((..(log(C_0(t) + d) + log(C_1(t) + d)) + ..) + log(C_8(t) + d))                                            fp32, this order
+ * C_j is the ADJOINT of the pairwise pass of main.py:83-87, a correlation of joint j's map with its prior: the evidence the joints send to a torso
+ * at t.  Every prior index lies in [0,118] x [0,178], so no padding case exists.  There is no bias term (b_{j|torso} is indexed by the joint's cell,
+ * not the torso's), and the 61x91 -> 60x90 resize of main.py:89 is left out as in jcm_pose_decode.  C_j is an fp32 sum of 5400 non-negative terms
+ * whose order belongs to the route (DESIGN.md 4.15 has the measured distance from float64); log as the spatial model's kernels evaluate it.
+ * Outputs (device):
+ *   energy fp32 [B,60,90]    E; may be NULL
+ *   cell   int32 [B,2]       (row, col) of the first-occurrence arg-max of E in row-major order, by the rules of jcm_argmax_coords
+ *   torso  fp32 [B,60,90,1]  the 3x3 binomial blob outer([1,2,1],[1,2,1]) / 16 that data.target_heat_maps places at `cell`, cut at the border, zeros
+ *                            elsewhere; may be NULL
+ * cells_in (device int32 [B,2], may be NULL): when given, no energy is formed -- prob, energy and cell are neither read nor written -- and torso
+ * (required then) gets the blob at cells_in[b], each coordinate clamped into the map (0..59, 0..89) before any index is formed from it: the
+ * device-side blob writer of the per-person maps (Engine.forward(torso='infer', people=M)).
+ * Route: option "torso_algo", 1 = direct (an LDS-tiled sliding-window sum per (image, joint), csrc/torso_infer.hip).  It is the only value: a
+ * frequency-domain route on the cached prior spectra (read conjugated) is not shipped.
+ * The launches (likelihoods, correlations, log-sum + arg-max + blob) are enqueued on the handle's stream; nothing synchronises.  NaN inputs are
+ * outside the contract.  JCM_ERR_ARG for another geometry, B < 1 or a required pointer that is NULL, JCM_ERR_STATE before jcm_finalize or (without
+ * cells_in) on a handle without spatial-model parameters; nothing is launched and no output is touched then.  Uses the handle's workspace. */
+int jcm_torso_infer(jcm_handle h, const float* prob, int B, int HH, int WW, int K, const int32_t* cells_in,
+                    float* energy, int32_t* cell, float* torso);
 
 /* -- the whole tower ----------------------------------------------------------------------------
  * The graph of main.py:522-531: model -> spatial_softmax -> concat torso -> spatial_model ->

@@ -50,6 +50,7 @@ SIGNATURES = {
                                     _c_i32_p, _c_float_p, _c_float_p, _c_i32_p]),
     'jcm_pose_decode': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, _c_i32_p, _c_i32_p, ctypes.c_int, _c_i32_p, _c_i32_p, _c_float_p, _c_float_p,
                                        _c_float_p, _c_float_p]),
+    'jcm_torso_infer': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32_p, _c_float_p, _c_i32_p, _c_float_p]),
     'jcm_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    _c_float_p, _c_float_p, _c_i32_p, _c_i32_p]),
     'jcm_eval_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,

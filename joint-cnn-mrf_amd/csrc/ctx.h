@@ -102,6 +102,7 @@ struct jcm_ctx {
   int fft_cache_gb = 64;        // bound of the filter-spectra cache (conv_route.hip: a new entry that would grow it past the bound drops the others first)
   int fft_win = 1;              // training step of fp32 handles: frequency-domain layers on 32 x 32 overlap-save windows where that shrinks the filter-sized spectra (jcm_train.hip)
   int bf16_hpool = 1;           // bf16 handles: the horizontal half of pool2 in conv2's epilogue (ConvArgs::hpool) + vpool_2x1_bf16 instead of the 2x2 pool kernel
+  int torso_algo = 1;           // jcm_torso_infer: 1 = direct sliding-window kernel (torso_infer.hip), the only route
   int sm_chunk = 32;            // training step: images per slice of the spatial model's backward pass (81 + 10 spectra per image live at once)
   int micro_batch = 0;          // jcm_forward walks a batch in slices of this many images (0 = 256 bf16 / 64 fp32)
   int call_order = 1;           // 0: this handle's calls are not ordered against other handles' (debugging only)

@@ -318,6 +318,14 @@ constexpr int kPoseMaxB = 1 << 20;
 hipError_t pose_decode(const float* hm10, int B, const int32_t* cells, const int32_t* count, int P, const float* sp_energy, const float* sp_bias,
                        const float* bn_scale, const float* bn_shift, float* V, float* M, float* pscore, int32_t* ppose, int32_t* index, int32_t* coords,
                        float* score, float* score0, hipStream_t st);
+// ---- torso_infer.hip : the torso map from the part detector ---------------------
+// prob [B,60,90,9] -> corr [B][9][5400] = C_j(t) (jcm.h: jcm_torso_infer; lik [B][9][60][96] and corr are scratch), then energy [B,5400] (may be null),
+// cell [B,2] = its first-occurrence arg-max and torso [B,5400] (may be null) = the 3x3 blob at it.  Four launches.  B <= kTorsoMaxB.
+constexpr int kTorsoMaxB = 1 << 20;
+hipError_t torso_infer_direct(const float* prob, int B, const float* sp_energy, const float* bn_scale, const float* bn_shift, float* lik, float* corr,
+                              float* energy, int32_t* cell, float* torso, hipStream_t st);
+// torso[b] = the blob at cells_in[b] clamped into the map; one launch
+hipError_t torso_blobs(const int32_t* cells_in, int B, float* torso, hipStream_t st);
 // ---- mirror.hip : mirrored test-time evaluation ----------------------------------
 // out[2b] = x[b], out[2b+1][y][xx][c] = x[b][y][W-1-xx][c]: bit copies of float (x_u8 false) or uint8 values, x [B,H,W,C] -> out [2B,H,W,C]; one launch.
 // W * C * sizeof(value) <= 65536.

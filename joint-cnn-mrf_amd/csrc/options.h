@@ -42,6 +42,7 @@ inline constexpr Option kOptions[] = {
     {"fft_cache_gb",    &jcm_ctx::fft_cache_gb,    Option::RANGE,  0,  1 << 20, false, "JCM_FFT_CACHE_GB",    nullptr},
     {"bf16_hpool",      &jcm_ctx::bf16_hpool,      Option::BOOL,   0,  1,       false, nullptr,               nullptr},
     {"sm_algo",         &jcm_ctx::sm_algo,         Option::EITHER, 1,  3,       false, nullptr,               nullptr},
+    {"torso_algo",      &jcm_ctx::torso_algo,      Option::EITHER, 1,  1,       false, nullptr,               nullptr},
     {"sm_chunk",        &jcm_ctx::sm_chunk,        Option::RANGE,  1,  INT_MAX, false, nullptr,               nullptr},
     {"micro_batch",     &jcm_ctx::micro_batch,     Option::RANGE,  0,  INT_MAX, false, nullptr,               nullptr},
     {"debug_skip",      &jcm_ctx::debug_skip,      Option::RANGE,  0,  127,     false, nullptr,               nullptr},

@@ -141,17 +141,20 @@ class Towers:
     def slices(self, batch_size):
         return [shard_bounds(batch_size, self.n, i) for i in range(self.n)]           # main.py:511,516-517
 
-    def forward(self, x, torso, use_sm=True, want_prob=False, peaks=0, decode=False, flip_test=False):
+    def forward(self, x, torso, use_sm=True, want_prob=False, peaks=0, decode=False, flip_test=False, people=1):
         """x [B,480,720,3], torso [B,60,90,1] (host or any device) -> dict of tensors on the FIRST tower's device,
         concatenated in tower order (= tf.concat axis 0); a remainder B % n_gpus is dropped as in the reference.  peaks = P > 0: every
         tower also returns Engine.forward's 'pd_peaks' / 'sm_peaks', concatenated the same way, and with decode=True its 'pose'.  flip_test=True:
-        mirrored test-time evaluation (Engine.forward(flip_test=True)); every tower mirrors its own slice on its own device."""
+        mirrored test-time evaluation (Engine.forward(flip_test=True)); every tower mirrors its own slice on its own device.
+        torso='infer' (with people=M): every tower infers the torso map of its own slice (Engine.forward(torso='infer')); the
+        nested 'people' dict is concatenated like the peaks."""
+        infer = isinstance(torso, str)
         outs = []
         for eng, (lo, hi) in zip(self.engines, self.slices(x.shape[0])):
             xs = torch.as_tensor(x[lo:hi]).to(eng.device, non_blocking=True).contiguous()
-            ts = torch.as_tensor(torso[lo:hi]).to(eng.device, non_blocking=True).contiguous() if use_sm else None
+            ts = torso if infer else torch.as_tensor(torso[lo:hi]).to(eng.device, non_blocking=True).contiguous() if use_sm else None
             with torch.cuda.device(eng.device):
-                outs.append(eng.forward(xs, ts, use_sm=use_sm, want_prob=want_prob, peaks=peaks, decode=decode, flip_test=flip_test))
+                outs.append(eng.forward(xs, ts, use_sm=use_sm, want_prob=want_prob, peaks=peaks, decode=decode, flip_test=flip_test, people=people))
         dev0 = self.engines[0].device
         cat = lambda parts: torch.cat([p.to(dev0) for p in parts], dim=0)
         return {k: {f: cat([o[k][f] for o in outs]) for f in outs[0][k]} if isinstance(outs[0][k], dict) else cat([o[k] for o in outs]) for k in outs[0]}

@@ -349,6 +349,109 @@ class Engine:
             hm10 = torch.cat([r.get('pd_prob', scratch.get('pd_prob')), torso], dim=3)
         r['pose'] = self.pose_decode(hm10, r['pd_peaks'])
 
+    def torso_infer(self, prob, want_energy=False, cells=None):
+        """The torso map from the part detector (include/jcm.h: jcm_torso_infer): prob [B,60,90,9], the part-detector
+        probabilities -> {'cell' int32 [B,2] (row, col): the cell whose nine correlations of joint map and learned prior e_{j|torso} have the
+        highest log-sum E, 'torso' fp32 [B,60,90,1]: the 3x3 blob of data.target_heat_maps at it -- the tenth channel spatial_model takes} plus,
+        with want_energy, 'energy' fp32 [B,60,90] = E.  cells (int32 [N,2], device): no energy is formed and prob is not read (it may be None);
+        'torso' [N,60,90,1] holds the blobs at the given cells, clamped into the map, and 'cell' the clamped cells.  Device tensors; nothing is
+        read back.  The geometry is checked by the library."""
+        if cells is not None:
+            self._chk(cells, 2, 'cells', torch.int32)
+            if cells.shape[1] != 2:
+                raise ValueError('cells must be [N,2], got %s' % (tuple(cells.shape),))
+            N = cells.shape[0]
+            out = {'torso': self._new(N, 60, 90, 1)}
+            self._on_stream(cells, out['torso'])
+            _lib.check(self._lib.jcm_torso_infer(self._h, self._p(None), N, 60, 90, 9, self._p(cells), self._p(None), self._p(None), self._p(out['torso'])),
+                       'jcm_torso_infer')
+            with torch.cuda.stream(self._stream):
+                out['cell'] = torch.stack([cells[:, 0].clamp(0, 59), cells[:, 1].clamp(0, 89)], dim=1)
+            return out
+        self._chk(prob, 4, 'prob')
+        B, H, W, K = prob.shape
+        out = {'cell': self._new(B, 2, dtype=torch.int32), 'torso': self._new(B, H, W, 1)}
+        if want_energy:
+            out['energy'] = self._new(B, H, W)
+        self._on_stream(prob, *out.values())
+        _lib.check(self._lib.jcm_torso_infer(self._h, self._p(prob), B, H, W, K, self._p(None), self._p(out.get('energy')), self._p(out['cell']),
+                                             self._p(out['torso'])), 'jcm_torso_infer')
+        return out
+
+    def torso_sm(self, prob, want_prob=True, people=1, people_threshold=0.0):
+        """The spatial model on part-detector probabilities prob [B,60,90,9] that come without a torso map: torso_infer,
+        spatial_model on [prob, torso], softmax_argmax -- what forward(torso='infer') runs behind the part detector.  Returns {'sm_coords',
+        'torso_cell' int32 [B,2], 'torso' [B,60,90,1], 'hm10' (the spatial model's input, [B * people,60,90,10])} plus 'sm_prob' (want_prob) and,
+        for people = M > 1, 'people' (see forward): the torso candidates are the top-M local maxima of spatial_softmax(E) (hm_peaks, K = 1),
+        torso_infer(cells=) writes the B * M blobs and the spatial model runs once on B * M images, image b's probabilities repeated for its M
+        slots; the top-level entries are slot 0."""
+        self._chk(prob, 4, 'prob')
+        B, K, M = prob.shape[0], 9, int(people)
+        if tuple(prob.shape[1:]) != (60, 90, K) or self.n_joints != K:
+            raise ValueError('torso_sm expects prob [B,60,90,9] on an engine with 9 joints; got %s, n_joints = %d' % (tuple(prob.shape), self.n_joints))
+        if not 1 <= M <= 4:
+            raise ValueError('people must be in 1..4, got %r' % (people,))
+        t = self.torso_infer(prob, want_energy=M > 1)
+        r = {}
+        if M == 1:
+            with torch.cuda.stream(self._stream):
+                hm10 = torch.cat([prob, t['torso']], dim=3)
+            sm_prob, r['sm_coords'] = self.softmax_argmax(self.spatial_model(hm10), want_prob=want_prob)
+            r['torso_cell'], r['torso'] = t['cell'], t['torso']
+        else:
+            pk = self.hm_peaks(self.spatial_softmax(t['energy'].view(B, 60, 90, 1)), max_peaks=M, threshold=people_threshold)
+            cells = pk['cells'].view(B, M, 2)
+            blobs = self.torso_infer(None, cells=cells.view(B * M, 2))['torso']
+            with torch.cuda.stream(self._stream):
+                hm10 = torch.cat([prob.repeat_interleave(M, dim=0), blobs], dim=3)
+            pm, cm = self.softmax_argmax(self.spatial_model(hm10), want_prob=want_prob)
+            with torch.cuda.stream(self._stream):
+                count = pk['count'].view(B)
+                live = torch.arange(M, device=self.device).view(1, M) < count.view(B, 1)          # [B,M]
+                cm = cm.view(B, M, 2, K)
+                cm = torch.where(live.view(B, M, 1, 1), cm, torch.full_like(cm, -1))
+                r['people'] = {'count': count, 'torso_cell': cells, 'torso_score': pk['scores'].view(B, M), 'sm_coords': cm}
+                if pm is not None:
+                    pm = pm.view(B, M, 60, 90, K) * live.view(B, M, 1, 1, 1).to(pm.dtype)
+                    r['people']['sm_prob'] = pm
+                r['torso_cell'], r['torso'] = cells[:, 0].contiguous(), blobs.view(B, M, 60, 90, 1)[:, 0].contiguous()
+                r['sm_coords'] = cm[:, 0].contiguous()
+                sm_prob = pm[:, 0].contiguous() if pm is not None else None
+        if sm_prob is not None:
+            r['sm_prob'] = sm_prob
+        r['hm10'] = hm10
+        return r
+
+    def _forward_infer(self, x, want_prob, peaks, decode, people, people_threshold):
+        """forward(torso='infer'): the part detector (the forward without spatial model: the same pd_* bits), then torso_sm on its probabilities."""
+        B, M = x.shape[0], people
+        if (_hm_size(x.shape[1]), _hm_size(x.shape[2]), self.n_joints) != (60, 90, 9):
+            raise ValueError("torso='infer' is defined for 60x90 heat maps (480x720 images) and 9 joints; got x %s, n_joints = %d" % (tuple(x.shape), self.n_joints))
+        r = self.forward(x, None, use_sm=False, want_prob=True)
+        s = self.torso_sm(r['pd_prob'], want_prob=bool(want_prob or peaks), people=M, people_threshold=people_threshold)
+        hm10 = s.pop('hm10')
+        scratch = {}
+        if not want_prob:
+            scratch = {'pd_prob': r.pop('pd_prob'), 'sm_prob': s.pop('sm_prob', None)}
+            if M > 1:
+                s['people'].pop('sm_prob', None)
+        r.update(s)
+        if peaks:
+            self._add_peaks(r, peaks, scratch)
+        if decode and M == 1:
+            self._add_pose(r, scratch, r['torso'])
+        elif decode:      # per slot: image b's candidates against each of its M torso maps
+            rep = {k: r['pd_peaks'][k].repeat_interleave(M, dim=0).contiguous() for k in ('cells', 'count')}
+            pose = self.pose_decode(hm10, rep)
+            with torch.cuda.stream(self._stream):      # slots at or beyond count have no pose: -1 / -inf, as pose_decode writes an image without one
+                live = torch.arange(M, device=self.device).view(1, M) < r['people']['count'].view(B, 1)
+                r['pose'] = {}
+                for k, v in pose.items():
+                    v = v.view(B, M, *v.shape[1:])
+                    none = torch.full_like(v, -1 if v.dtype == torch.int32 else float('-inf'))
+                    r['pose'][k] = torch.where(live.view(B, M, *([1] * (v.dim() - 2))), v, none)
+        return r
+
     def softmax_argmax(self, logits, want_prob=True):
         """spatial_softmax + arg-max of the probabilities in one kernel (the tail of forward()):
         [B,H,W,K] logits -> (prob [B,H,W,K] or None, coords int32 [B,2,K])."""
@@ -359,7 +462,7 @@ class Engine:
         _lib.check(self._lib.jcm_softmax_argmax(self._h, self._p(logits), B, H, W, K, self._p(prob), self._p(coords)), 'jcm_softmax_argmax')
         return prob, coords
 
-    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0, decode=False, flip_test=False):
+    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0, decode=False, flip_test=False, people=1, people_threshold=0.0):
         """The tower of main.py:522-531 in one C call.  Returns a dict with 'pd_coords',
         'sm_coords' (int32 [B,2,K]) and, if want_prob, 'pd_prob' / 'sm_prob' [B,60,90,K].  x: float32, or uint8 (byte k standing for
         float32(k) / float32(255): the same bits out as for that float image, a quarter of the bytes in).  peaks = P > 0: also 'pd_peaks'
@@ -369,12 +472,29 @@ class Engine:
         entry is what the call without it returns.  flip_test=True: mirrored test-time evaluation -- ONE forward on
         mirror_pairs(x) (2B images; with use_sm on mirror_pairs(torso)), 'pd_prob' / 'sm_prob' the mirror_merge of its probabilities, [B,...],
         the coords argmax_coords of the merged maps; peaks and decode work on the merged maps (kept in scratch when want_prob is False) and the
-        unmirrored torso map.  False changes nothing."""
+        unmirrored torso map.  False changes nothing.  torso='infer' (needs use_sm): no torso map is given -- it is inferred from
+        this call's part-detector probabilities (torso_infer) and the spatial model runs on it; the dict gains 'torso_cell' int32 [B,2] and 'torso'
+        [B,60,90,1], 'pd_*' are the bits of forward(use_sm=False) and 'sm_*' those of forward(x, torso=r['torso']); peaks and decode as before.
+        people = M in 1..4 (with torso='infer'; 1 changes nothing): one spatial-model result per torso candidate, the top-M local maxima of
+        spatial_softmax(E) above people_threshold (hm_peaks; slot 0 is the arg-max): the dict gains 'people' = {'count' int32 [B], 'torso_cell'
+        int32 [B,M,2], 'torso_score' fp32 [B,M], 'sm_coords' int32 [B,M,2,K], and with want_prob 'sm_prob' [B,M,60,90,K]}, slots at or beyond
+        count holding -1 in the coordinates and 0 in the maps; the top-level 'sm_*', 'torso_cell' and 'torso' are slot 0, and with decode 'pose'
+        is decoded per slot, [B,M,...].  flip_test=True with torso='infer' is a ValueError."""
         self._chk_decode(decode, use_sm, peaks)
         u8 = self._chk_img(x, 'x')
         B, H, W, C = x.shape
         if C != 3:
             raise ValueError('x must be [B,H,W,3]')
+        infer = isinstance(torso, str)
+        if infer and torso != 'infer':
+            raise ValueError("torso must be a tensor, None or 'infer', got %r" % (torso,))
+        if not isinstance(people, int) or not 1 <= people <= 4 or (people > 1 and not infer):
+            raise ValueError("people must be an integer in 1..4 and needs torso='infer' above 1; got people=%r, torso=%s" % (people, 'infer' if infer else 'given'))
+        if infer:
+            if not use_sm or flip_test:
+                raise ValueError("torso='infer' needs use_sm=True and does not combine with flip_test=True (the torso under mirrored evaluation is not defined); "
+                                 'got use_sm=%s, flip_test=%s' % (bool(use_sm), bool(flip_test)))
+            return self._forward_infer(x, want_prob, peaks, decode, people, float(people_threshold))
         if use_sm:
             if torso is None:
                 raise ValueError('use_sm=True needs the torso heat map y_in[..., 9:] (main.py:528)')

@@ -78,6 +78,11 @@ def build_parser():
     parser.add_argument('--decode_pose', action='store_true', help='evaluation run with --use_sm, --predictions and --peaks P <= 4: of the P peaks per joint of the '
                         'part detector, choose the ONE combination with the highest spatial-model energy (Engine.pose_decode; DESIGN.md 4.13); writes flic_pred_pose '
                         '/ flic_pose_score and prints test_dr_pose.')
+    parser.add_argument('--infer_torso', action='store_true', help='single-scale evaluation run with --use_sm: the spatial model is fed the torso map INFERRED from the '
+                        'part detector (Engine.forward(torso=\'infer\'), DESIGN.md 4.15) instead of the annotated channel y[..., 9]; the JSON line gains '
+                        'infer_torso and torso_cell_dist (mean distance in cells to the arg-max of the annotated torso channel), --predictions gains flic_torso_cell.')
+    parser.add_argument('--people', type=int, default=1, metavar='M', help='with --infer_torso: one spatial-model result per torso candidate, up to M in 1..4 per image '
+                        '(Engine.forward(people=M)); --predictions gains flic_people_sm [N,M,2,K] and flic_people_count.')
     parser.add_argument('--flip_test', action='store_true', help='evaluation run: mirrored test-time evaluation -- every image goes through the tower in both '
                         'orientations and the maps of the mirror image, read back with the left/right joints exchanged, are averaged with the plain ones '
                         '(Engine.forward(flip_test=True); with --multiscale on top of the 8 scales, 16 copies per image; DESIGN.md 4.14).')
@@ -339,6 +344,12 @@ def pose_det_rate(eng, pred_pose, y, index, joints=(2,), det_radius=10):
     return acc / N
 
 
+INFER_TORSO_IS_EVALUATION_ONLY = ('--infer_torso belongs to the evaluation run (training with an inferred torso map is not defined: the step reads the '
+                                  'annotated channel); drop --train')
+INFER_TORSO_NEEDS_USE_SM = '--infer_torso infers the torso map the spatial model reads: give --use_sm as well'
+INFER_TORSO_SINGLE_SCALE_ONLY = ('--infer_torso cannot be combined with --multiscale, --flip_test or --u8_images: the torso under multi-scale and mirrored '
+                                 'evaluation is not defined, and the streamed byte feed returns coordinates only')
+PEOPLE_NEEDS_INFER_TORSO = '--people M (1 <= M <= 4) asks for one result per INFERRED torso candidate: give --infer_torso as well'
 FLIP_TEST_IS_EVALUATION_ONLY = ('--flip_test belongs to the evaluation run (it averages the heat maps of a test image and of its mirror image); '
                                 'it cannot be combined with --train')
 
@@ -590,6 +601,15 @@ def main(argv=None):
         raise SystemExit(FLIP_TEST_IS_EVALUATION_ONLY)
     if args.train and args.u8_images and not args.device_data:
         raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
+    if args.infer_torso:
+        if args.train:
+            raise SystemExit(INFER_TORSO_IS_EVALUATION_ONLY)
+        if not args.use_sm:
+            raise SystemExit(INFER_TORSO_NEEDS_USE_SM)
+        if args.multiscale or args.flip_test or args.u8_images:
+            raise SystemExit(INFER_TORSO_SINGLE_SCALE_ONLY)
+    if args.people != 1 and not (args.infer_torso and 1 <= args.people <= 4):
+        raise SystemExit(PEOPLE_NEEDS_INFER_TORSO)
     if args.decode_pose:
         if args.train:
             raise SystemExit(DECODE_POSE_IS_EVALUATION_ONLY)
@@ -674,6 +694,7 @@ def main(argv=None):
         B = args.batch_size
         pd, sm = [], []
         pk_pd, pk_sm, poses = [], [], []
+        torso_cells, people = [], []      # --infer_torso / --people
         if args.u8_images and args.flip_test:      # byte batches through the towers' byte forward (the streamed feed has no mirrored evaluation)
             from .dataset import to_u8_exact
             xb = to_u8_exact(x_test)
@@ -702,8 +723,15 @@ def main(argv=None):
             fed = {'image_dtype': 'uint8', 'bytes_uploaded': int(sum(fs.bytes_uploaded for fs in fss))}
         else:
             for lo in range(0, (x_test.shape[0] // B) * B, B):
-                r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
-                                   use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, flip_test=args.flip_test)
+                r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32),
+                                   'infer' if args.infer_torso else np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
+                                   use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, flip_test=args.flip_test, people=args.people)
+                if args.infer_torso:
+                    torso_cells.append(r['torso_cell'])
+                    if args.people > 1:
+                        people.append(r['people'])
+                    if args.decode_pose and args.people > 1:      # the file holds one pose per image: slot 0, the arg-max torso
+                        r['pose'] = {f: v[:, 0].contiguous() for f, v in r['pose'].items()}
                 pd.append(r['pd_coords'])
                 sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
                 if args.peaks:
@@ -729,6 +757,11 @@ def main(argv=None):
             mat.update(flic_peaks_pd=peaks_to_pixels(peaks_pd), flic_peaks_sm=peaks_to_pixels(peaks_sm))
         if pose is not None:
             mat.update(flic_pred_pose=pose['coords'].transpose(1, 2, 0), flic_pose_score=np.stack([pose['score'], pose['score0']], axis=1))
+        if args.infer_torso:
+            mat.update(flic_torso_cell=torch.cat(torso_cells).cpu().numpy())                            # [N,2] (row, col)
+            if people:
+                mat.update(flic_people_sm=torch.cat([p['sm_coords'] for p in people]).cpu().numpy(),    # [N,M,2,K], -1 from flic_people_count on
+                           flic_people_count=torch.cat([p['count'] for p in people]).cpu().numpy())
         scipy.io.savemat(args.predictions, mat)
     if args.det_curve:      # one place for every feed: the curves of the assembled predictions, counted on the first listed device
         index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus), multiscale=args.multiscale)      # towers drop batch_size % n_gpus of every batch
@@ -751,6 +784,14 @@ def main(argv=None):
         line.update(fed)
     if args.flip_test:
         line['flip_test'] = True
+    if args.infer_torso:      # how far the inferred cell lies from the arg-max of the annotated torso channel (first occurrence), in cells
+        index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus))
+        ann = np.asarray(y_test)[index][:, :, :, n_joints].reshape(len(index), -1).argmax(axis=1)
+        got = torch.cat(torso_cells).cpu().numpy().astype(np.float64)
+        line['infer_torso'] = True
+        line['torso_cell_dist'] = float(np.sqrt((got[:, 0] - ann // 90) ** 2 + (got[:, 1] - ann % 90) ** 2).mean())
+        if args.people > 1:
+            line['people'] = int(args.people)
     if args.peaks:
         line['peaks'] = int(args.peaks)
     if pose is not None:      # the share of images whose decoded pose is not the all-peak-0 pose (the independent arg-maxes)

@@ -70,7 +70,7 @@ def scale_hm_back(engine, hms, pad_array, crop_array, orig_h, orig_w, copies_per
     return engine.window_resize(hms.contiguous(), windows, orig_h, orig_w)
 
 
-def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8, peaks=0, flip_test=False):
+def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8, peaks=0, flip_test=False, torso=None):
     """main.py:382-425 without the det_rate bookkeeping: for every image the 8 rescaled copies go
     through the tower (with the UNSCALED target maps repeated, main.py:405), the heat maps are
     scaled back and averaged, and the arg-max coordinates are returned as the reference returns
@@ -82,7 +82,11 @@ def get_predictions(engine, X, Y, use_sm=True, images_per_forward=8, peaks=0, fl
     mirror image of scale s); (3) the same for the repeated torso maps; (4) one forward; (5) scale back, the back-window of scale s applied to both
     members of its pair (scale_hm_back(copies_per_scale=2)); (6) Engine.mirror_merge(group=16), which reads the odd copies mirrored back; (7) arg-max
     and peaks as before.  "Mirror the image, then scale it" would be a different function: several back-windows are not symmetric (the 90-wide map
-    at 1/1.3 is cut as 10 | 69 | 11), so the window of scale s applied to a mirrored map covers other columns than its mirror image would."""
+    at 1/1.3 is cut as 10 | 69 | 11), so the window of scale s applied to a mirrored map covers other columns than its mirror image would.
+    torso: None = channel K of Y, the only source here; 'infer' (Engine.forward(torso='infer')) is refused: which of the eight
+    scales' inferred cells would stand for the image is not defined."""
+    if torso is not None:
+        raise ValueError("get_predictions takes the torso map from Y; torso=%r is not supported under multi-scale evaluation" % (torso,))
     dev = engine.device
     K = engine.n_joints
     n = X.shape[0]
