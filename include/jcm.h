@@ -378,6 +378,29 @@ int jcm_window_resize(jcm_handle h, const float* src, int nsrc, int H, int W, in
 /* np.average over the G scale copies of each image (main.py:413-414): in [n*G, M] -> out [n, M]. */
 int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float* out);
 
+/* -- images of any size: the letterbox fit ------------------------------------------------
+ * A ragged batch of byte images resampled, aspect preserved and antialiased, into the frame the tower reads: image b lands in the content
+ * rectangle of out[b], everything else of out[b] is the byte `pad`.
+ * src: ONE device buffer of src_bytes bytes holding the B images, image b = [h_b, w_b, C] uint8 in HWC order at any byte offset (no alignment
+ * is assumed); desc: HOST int64 [B][3] = (byte offset, h_b, w_b), read before the call returns (it travels in the kernel arguments);
+ * out: device [B,OH,OW,C], not overlapping src: uint8 (out_f32 == 0) or float32 (out_f32 != 0), each value float32(byte) / float32(255), the
+ * value the byte stands for at the byte entries above; geom: HOST int32 [B][4] = (y0, x0, ch, cw), written by the call, may be NULL.
+ * Geometry (integers, / is floor division), h x w into OH x OW:
+ *   OH * w <= OW * h:  ch = OH,  cw = max(1, (2 * w * OH + h) / (2 * h));      otherwise:  cw = OW,  ch = max(1, (2 * h * OW + w) / (2 * w))
+ *   y0 = (OH - ch) / 2,  x0 = (OW - cw) / 2;   the content rectangle is [y0, y0 + ch) x [x0, x0 + cw).
+ * Resampling: a separable triangle filter whose support widens with the reduction ("bilinear with antialiasing"; plain edge-clamped bilinear
+ * when enlarging), in float64, evaluated as written.  Per axis, n source samples onto m content samples:
+ *   f = (double)n / (double)m,  sup = max(f, 1.0);   output o:  c = (o + 0.5) * f,  lo = max(0, (int)floor(c - sup)),  hi = min(n, (int)ceil(c + sup))
+ *   t_i = max(0.0, 1.0 - fabs((i + 0.5 - c) / sup))  for i = lo .. hi - 1,   T = t_lo + .. + t_{hi-1} in ascending i,   weight_i = t_i / T.
+ * A content value is acc = sum_j wy_j * (sum_i wx_i * (double)p[lo_y + j][lo_x + i][channel]): the inner sum first, ascending i from 0.0, then the
+ * outer, ascending j from 0.0; the byte is min(255, max(0, (int)floor(acc + 0.5))).  A source of exactly OH x OW comes out as a bit copy.
+ * JCM_ERR_ARG -- nothing is launched, out and geom are untouched -- for a null src, desc or out, B < 1, C outside 1..4, OH or OW outside 1..4096,
+ * pad outside 0..255, an h_b or w_b outside 1..16384, an image whose bytes do not lie inside [0, src_bytes), a reduction above 32 on either axis
+ * (h > 32 * ch or w > 32 * cw: at most 66 taps per axis), B * OH * OW * C >= 2^31, and an out that overlaps src.
+ * One launch per 64 images on the handle's stream; nothing synchronises.  Uses no workspace. */
+int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C,
+                   int OH, int OW, int pad, int out_f32, void* out, int32_t* geom);
+
 /* -- mirrored test-time evaluation -----------------------------------------------------
  * The maps of an image averaged with the un-mirrored maps of its mirror image: jcm_mirror_pairs makes the batch the tower sees,
  * jcm_mirror_merge folds the tower's maps back.  Both enqueue one launch on the handle's stream and do not synchronise.

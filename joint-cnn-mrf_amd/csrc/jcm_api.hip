@@ -747,6 +747,50 @@ int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float
   return JCM_OK;
 }
 
+int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, int out_f32,
+                   void* out, int32_t* geom) {
+  JCM_TRY(check(h, false));
+  if (!src || !desc || !out) return fail(JCM_ERR_ARG, "fit_images: null pointer (src, desc and out are required, geom may be NULL)");
+  if (B < 1 || C < 1 || C > 4 || OH < 1 || OH > 4096 || OW < 1 || OW > 4096 || pad < 0 || pad > 255 || src_bytes < 1)
+    return fail(JCM_ERR_ARG, "fit_images: bad sizes (B >= 1, C in 1..4, OH and OW in 1..4096, pad in 0..255)");
+  if ((int64_t)B * OH * OW * C >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, "fit_images: B * OH * OW * C >= 2^31");
+  for (int b = 0; b < B; ++b) {
+    const int64_t off = desc[b * (int64_t)3], hb = desc[b * (int64_t)3 + 1], wb = desc[b * (int64_t)3 + 2];
+    const std::string who = "fit_images: image " + std::to_string(b);
+    if (hb < 1 || hb > 16384 || wb < 1 || wb > 16384)
+      return fail(JCM_ERR_ARG, who + " is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..16384");
+    if (off < 0 || off > src_bytes || hb * wb * C > src_bytes - off)
+      return fail(JCM_ERR_ARG, who + " (" + std::to_string(hb * wb * C) + " bytes at offset " + std::to_string(off) + ") does not lie inside the " +
+                                   std::to_string(src_bytes) + " bytes of src");
+    const FitGeom g = fit_geometry((int)hb, (int)wb, OH, OW);
+    if (hb > 32 * (int64_t)g.ch || wb > 32 * (int64_t)g.cw)
+      return fail(JCM_ERR_ARG, who + ", " + std::to_string(hb) + " x " + std::to_string(wb) + " into " + std::to_string(g.ch) + " x " + std::to_string(g.cw) +
+                                   ": a reduction above 32 (at most 66 taps per axis)");
+  }
+  const size_t no = (size_t)B * OH * OW * C * (out_f32 ? sizeof(float) : 1);
+  {
+    const char *pa = reinterpret_cast<const char*>(src), *pb = static_cast<const char*>(out);
+    if (pa < pb + no && pb < pa + src_bytes) return fail(JCM_ERR_ARG, "fit_images: out overlaps src");
+  }
+  if (geom)
+    for (int b = 0; b < B; ++b) {
+      const FitGeom g = fit_geometry((int)desc[b * (int64_t)3 + 1], (int)desc[b * (int64_t)3 + 2], OH, OW);
+      geom[b * (int64_t)4] = g.y0;
+      geom[b * (int64_t)4 + 1] = g.x0;
+      geom[b * (int64_t)4 + 2] = g.ch;
+      geom[b * (int64_t)4 + 3] = g.cw;
+    }
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  hipEvent_t e0, e1;
+  JCM_TRY(prof_begin(c, &e0, &e1));
+  const hipError_t launch = fit_images(src, src_bytes, desc, B, C, OH, OW, pad, out_f32 != 0, out, c->stream);
+  prof_end(c, "fit_images", e0, e1, launch == hipSuccess);
+  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("fit_images: ") + hipGetErrorString(launch));
+  return JCM_OK;
+}
+
 int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
                       int hh, int hw, float* x_out, float* y_out) {
   JCM_TRY(check(h, false));

@@ -333,6 +333,39 @@ hipError_t mirror_pairs(const void* x, bool x_u8, int B, int H, int W, int C, vo
 // out[i,y,x,k] = float(sum over g < G, in order, in double, of v_g / double(G)), v_g = hm[i*G+g,y,x,k] (g even) or hm[i*G+g,y,WW-1-x,perm[k]] (g odd);
 // hm [n*G,HH,WW,K], G even, perm: K HOST entries, a permutation of 0..K-1 (the caller checks it), K <= 64; one launch.
 hipError_t mirror_merge(const float* hm, int n, int G, int HH, int WW, int K, const int* perm, float* out, hipStream_t st);
+// ---- fit.hip : letterbox fit of a ragged batch of byte images ---------------------
+// The images of a launch travel by value in its kernel arguments; a batch of more than kFitMax images takes several launches.
+constexpr int kFitMax = 64;
+constexpr int kFitTW = 32;      // content columns per work group
+struct FitBatch {
+  int64_t off[kFitMax];         // byte offset of image i in src
+  int h[kFitMax], w[kFitMax];
+  int first[kFitMax + 1];       // work groups [first[i], first[i + 1]) are the strips of image i
+};
+// the content rectangle of an h x w source in an OH x OW frame (jcm.h: jcm_fit_images; integers, floor division)
+struct FitGeom {
+  int y0, x0, ch, cw;
+};
+__host__ __device__ inline FitGeom fit_geometry(int h, int w, int OH, int OW) {
+  FitGeom g;
+  if ((int64_t)OH * w <= (int64_t)OW * h) {
+    g.ch = OH;
+    const int64_t cw = (2 * (int64_t)w * OH + h) / (2 * (int64_t)h);
+    g.cw = cw < 1 ? 1 : (int)cw;
+  } else {
+    g.cw = OW;
+    const int64_t ch = (2 * (int64_t)h * OW + w) / (2 * (int64_t)w);
+    g.ch = ch < 1 ? 1 : (int)ch;
+  }
+  g.y0 = (OH - g.ch) / 2;
+  g.x0 = (OW - g.cw) / 2;
+  return g;
+}
+// src: B byte images [h_b, w_b, C] at desc[b] = (byte offset, h_b, w_b) (HOST int64 [B][3], read before the call returns; every entry checked by the
+// caller: 1 <= C <= 4, sizes, bounds, a reduction of at most 32 per axis) -> out [B,OH,OW,C] uint8 or (out_f32) float32 = u8_to_f32(byte); the
+// separable triangle filter of jcm.h in float64, `pad` outside the content rectangle.  One launch per kFitMax images.
+hipError_t fit_images(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
+                      hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

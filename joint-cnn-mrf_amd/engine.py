@@ -595,6 +595,62 @@ class Engine:
         _lib.check(self._lib.jcm_group_mean(self._h, self._p(x.contiguous()), n, group, m, self._p(out)), 'jcm_group_mean')
         return out
 
+    def fit_images(self, images, out_hw=(480, 720), pad=0, dtype=torch.uint8, out=None):
+        """Images of any size into the frame the tower reads (include/jcm.h: jcm_fit_images): `images` is a list of uint8 [h,w,3]
+        torch tensors or numpy arrays, on the host or on the engine's device, of mixed sizes.  Each is resampled, aspect preserved and
+        antialiased, into the centred content rectangle of an out_hw frame; the rest of the frame is the byte `pad`.  One packed device buffer,
+        one launch per 64 images.  Returns (x [B,OH,OW,3] of `dtype` -- torch.uint8, or torch.float32 = byte / 255 -- and geom, host int32 [B,6] =
+        (y0, x0, ch, cw, h, w): the content rectangle and the source size, what evaluation.fit_to_source takes).  out: a tensor to write into
+        instead of a new one.  Sizes, pad and the reduction limit (32 per axis) are checked by the library."""
+        if not isinstance(images, (list, tuple)) or len(images) == 0:
+            raise ValueError('images must be a non-empty list of uint8 [h,w,3] images')
+        if dtype not in (torch.uint8, torch.float32):
+            raise TypeError('dtype must be torch.uint8 or torch.float32, got %s' % (dtype,))
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        B, C = len(images), 3
+        ts = []
+        for i, im in enumerate(images):
+            name = 'images[%d]' % i
+            if isinstance(im, np.ndarray):
+                if im.dtype != np.uint8:
+                    raise TypeError('%s must be uint8, got %s' % (name, im.dtype))
+                im = torch.from_numpy(np.ascontiguousarray(im))
+            elif not isinstance(im, torch.Tensor):
+                raise TypeError('%s must be a torch tensor or a numpy array' % name)
+            if im.dtype != torch.uint8:
+                raise TypeError('%s must be %s, got %s' % (name, torch.uint8, im.dtype))
+            if im.dim() != 3 or im.shape[2] != C or im.shape[0] < 1 or im.shape[1] < 1:
+                raise ValueError('%s must be [h,w,3] (HWC), got shape %s' % (name, tuple(im.shape)))
+            if im.device.type != 'cpu' and im.device != self.device:
+                raise ValueError('%s is on %s, engine is on %s' % (name, im.device, self.device))
+            ts.append(im)
+        desc = np.empty((B, 3), np.int64)
+        off = 0
+        for i, im in enumerate(ts):
+            desc[i] = (off, im.shape[0], im.shape[1])
+            off += im.numel()
+        if out is None:
+            out = self._new(B, OH, OW, C, dtype=dtype)
+        else:
+            self._chk(out, 4, 'out', dtype)
+            if tuple(out.shape) != (B, OH, OW, C):
+                raise ValueError('out must be [%d,%d,%d,%d], got %s' % (B, OH, OW, C, tuple(out.shape)))
+        src = self._new(off, dtype=torch.uint8)
+        host = [i for i, im in enumerate(ts) if im.device.type == 'cpu']
+        if len(host) == B:      # one packed host buffer, one copy
+            src.copy_(torch.cat([im.reshape(-1) for im in ts]))
+        else:
+            for i, im in enumerate(ts):
+                src[int(desc[i, 0]):int(desc[i, 0]) + im.numel()].copy_(im.reshape(-1))
+        geom = np.empty((B, 6), np.int32)
+        g4 = np.empty((B, 4), np.int32)
+        self._on_stream(src, out)
+        _lib.check(self._lib.jcm_fit_images(self._h, self._p(src), off, desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B, C, OH, OW, int(pad),
+                                            int(dtype == torch.float32), self._p(out), g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), 'jcm_fit_images')
+        geom[:, :4] = g4
+        geom[:, 4:] = desc[:, 1:]
+        return out, geom
+
     def mirror_pairs(self, x):
         """x [B,H,W,C] float32 or uint8 -> [2B,H,W,C] of the same type: out[2b] = x[b], out[2b+1] = x[b] mirrored left/right (out[2b+1,y,xx,c] =
         x[b,y,W-1-xx,c]); bit copies, one launch (include/jcm.h: jcm_mirror_pairs)."""

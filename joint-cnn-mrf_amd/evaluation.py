@@ -72,6 +72,27 @@ def pose_to_pixels(pose, peaks, stride=8):
     return out
 
 
+def fit_to_source(points, geom):
+    """Points of the fitted frame back into their source images.  points: host array [N,...,2+] = (row, col, ...) in pixels of
+    the frame Engine.fit_images made, as peaks_to_pixels / pose_to_pixels and `coords * 8` give them; geom: the [N,6] (or [N,4] + sizes) int
+    array fit_images returned, (y0, x0, ch, cw, h, w) per image.  Returns (the same array as float64 with
+        row_s = (row - y0 + 0.5) * h / ch - 0.5,   col_s = (col - x0 + 0.5) * w / cw - 0.5
+    -- the inverse of the fit's pixel-centre mapping; trailing entries (scores) pass through, filler rows (row, col < 0) stay as they are -- and
+    `inside`, bool [N,...]: whether the fitted point lay in the content rectangle [y0, y0 + ch) x [x0, x0 + cw); filler rows are outside)."""
+    pts = np.array(points, dtype=np.float64)
+    geom = np.asarray(geom)
+    if pts.ndim < 2 or pts.shape[-1] < 2 or geom.ndim != 2 or geom.shape != (pts.shape[0], 6):
+        raise ValueError('fit_to_source expects points [N,...,2+] and geom [N,6]; got %s, %s' % (pts.shape, geom.shape))
+    g = geom.astype(np.float64).reshape((geom.shape[0],) + (1,) * (pts.ndim - 2) + (6,))
+    row, col = pts[..., 0], pts[..., 1]
+    filler = (row < 0) & (col < 0)
+    inside = ~filler & (row >= g[..., 0]) & (row < g[..., 0] + g[..., 2]) & (col >= g[..., 1]) & (col < g[..., 1] + g[..., 3])
+    out = pts.copy()
+    out[..., 0] = np.where(filler, row, (row - g[..., 0] + 0.5) * g[..., 4] / g[..., 2] - 0.5)
+    out[..., 1] = np.where(filler, col, (col - g[..., 1] + 0.5) * g[..., 5] / g[..., 3] - 0.5)
+    return out, inside
+
+
 def get_next_batch(X, Y, batch_size, shuffle=False, rng=None):
     """main.py:184-192: whole batches only -- the remainder len(X) % batch_size is dropped; `shuffle` draws a permutation."""
     import numpy as np

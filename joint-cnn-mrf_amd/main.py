@@ -86,6 +86,10 @@ def build_parser():
     parser.add_argument('--flip_test', action='store_true', help='evaluation run: mirrored test-time evaluation -- every image goes through the tower in both '
                         'orientations and the maps of the mirror image, read back with the left/right joints exchanged, are averaged with the plain ones '
                         '(Engine.forward(flip_test=True); with --multiscale on top of the 8 scales, 16 copies per image; DESIGN.md 4.14).')
+    parser.add_argument('--predict', nargs='+', default=None, metavar='PATH', help='instead of the evaluation run: image files of ANY size (or directories, expanded in '
+                        'sorted order) -> the nine joints in each image\'s own pixels, written as JSON to the file of --predictions (predict.predict_images, DESIGN.md '
+                        '4.16): the images are letterboxed into 480x720 on the device, with --use_sm the torso is inferred; --peaks, --decode_pose, --people and '
+                        '--batch_size apply.  .npy files holding uint8 [h,w,3] are always read; other formats need PIL.  Runs on the first device of --gpus.')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -354,6 +358,43 @@ FLIP_TEST_IS_EVALUATION_ONLY = ('--flip_test belongs to the evaluation run (it a
                                 'it cannot be combined with --train')
 
 
+PREDICT_NEEDS_PREDICTIONS = '--predict writes its JSON document to the file of --predictions: give --predictions OUT.json as well'
+PREDICT_NOT_WITH_TRAIN = '--predict runs the tower on the named images and is no training run: drop --train'
+PREDICT_NOT_WITH_MULTISCALE = ('--predict cannot be combined with --multiscale: with --use_sm the torso is inferred, and the inferred torso under multi-scale '
+                               'evaluation is not defined')
+PREDICT_NOT_WITH_FLIP_TEST = ('--predict cannot be combined with --flip_test: with --use_sm the torso is inferred, and the inferred torso under mirrored '
+                              'evaluation is not defined')
+PREDICT_NOT_WITH_DET_CURVE = '--predict cannot be combined with --det_curve: the named images have no annotation to measure a detection rate against'
+PREDICT_NOT_WITH_DEVICE_DATA = '--predict cannot be combined with --device_data: that flag places the training sets of --train'
+
+
+def predict_main(args):
+    """--predict PATH [PATH ...]: the named images through predict.predict_images on the first listed device; the JSON document goes to
+    --predictions, one JSON line with the image count and the device times of the fit and of the forwards to stdout."""
+    from . import checkpoint, predict
+    files = predict.expand_paths(args.predict)
+    images = [predict.load_image(f) for f in files]
+    if args.restore:
+        state = restore_params(args.restore_path, args)
+        params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)}
+    else:
+        pairwise = synth.synthetic_priors() if args.synthetic else (get_pairwise_distr(args.data_dir) if args.use_sm else None)
+        params = initial_params(args, pairwise)
+    hps.debug = bool(args.debug)
+    eng = Engine(device=args.gpus[0], precision=args.precision, n_joints=n_joints).load_params(params)
+    try:
+        timing = {}
+        results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
+                                         batch_size=args.batch_size, timing=timing)
+    finally:
+        eng.close()
+    os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
+    with open(args.predictions, 'w') as fh:
+        json.dump(predict.predictions_document(files, results), fh)
+    print(json.dumps({'predict': True, 'n_images': len(files), 'fit_ms': timing['fit_ms'], 'forward_ms': timing['forward_ms'], 'gpu': args.gpus[0],
+                      'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}))
+
+
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
 
@@ -595,6 +636,12 @@ def main(argv=None):
     hps = args
     if args.restore and not args.restore_path:
         raise SystemExit('--restore needs --restore_path <checkpoint prefix or .npz> (the reference hard-codes best_model_name, main.py:443)')
+    if args.predict:
+        for given, message in ((args.train, PREDICT_NOT_WITH_TRAIN), (args.multiscale, PREDICT_NOT_WITH_MULTISCALE), (args.flip_test, PREDICT_NOT_WITH_FLIP_TEST),
+                               (args.det_curve, PREDICT_NOT_WITH_DET_CURVE), (args.device_data, PREDICT_NOT_WITH_DEVICE_DATA),
+                               (not args.predictions, PREDICT_NEEDS_PREDICTIONS)):
+            if given:
+                raise SystemExit(message)
     if args.train and args.det_curve:
         raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
     if args.train and args.flip_test:
@@ -608,7 +655,7 @@ def main(argv=None):
             raise SystemExit(INFER_TORSO_NEEDS_USE_SM)
         if args.multiscale or args.flip_test or args.u8_images:
             raise SystemExit(INFER_TORSO_SINGLE_SCALE_ONLY)
-    if args.people != 1 and not (args.infer_torso and 1 <= args.people <= 4):
+    if args.people != 1 and not ((args.infer_torso or (args.predict and args.use_sm)) and 1 <= args.people <= 4):
         raise SystemExit(PEOPLE_NEEDS_INFER_TORSO)
     if args.decode_pose:
         if args.train:
@@ -639,6 +686,9 @@ def main(argv=None):
     for g in args.gpus:
         if g < 0 or g >= torch.cuda.device_count():
             raise SystemExit('--gpus %s: device %d does not exist (%d visible)' % (args.gpus, g, torch.cuda.device_count()))
+    if args.predict:
+        predict_main(args)
+        return
     if args.train:
         train_main(args)
         return
