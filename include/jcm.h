@@ -401,6 +401,23 @@ int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float
 int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C,
                    int OH, int OW, int pad, int out_f32, void* out, int32_t* geom);
 
+/* -- windows of images of any size ----------------------------------------------------------
+ * jcm_fit_images applied to rectangles of the images: what a second pass over the people of a photo cuts out (predict.py: zoom).
+ * src, src_bytes, C, OH, OW, pad, out_f32 are those of jcm_fit_images; desc: HOST int64 [NW][7] = (byte offset, h, w, wy0, wx0, wh, ww), read before
+ * the call returns: the image [h, w, C] sits at the byte offset exactly as for jcm_fit_images, the window is its rows [wy0, wy0 + wh) and
+ * columns [wx0, wx0 + ww).  wy0 and wx0 may be negative and the window may reach past any edge; several windows may name one image.
+ * Let V be the [wh, ww, C] byte image with V[y][x] = image[wy0 + y][wx0 + x] where that sample exists and the byte `pad` elsewhere (np.pad, then a
+ * crop).  out[i] [OH,OW,C] and geom[i] = (y0, x0, ch, cw) are exactly what jcm_fit_images gives for V: the geometry of wh x ww into OH x OW, the
+ * float64 triangle filter, its summation order and its rounding, as stated above.  The pad samples of V take part in the filter like any other
+ * sample.  A window (0, 0, h, w) therefore gives the bits of jcm_fit_images for that image.
+ * JCM_ERR_ARG -- nothing is launched, out and geom are untouched -- for everything jcm_fit_images refuses, the size limit (1..16384) and the
+ * reduction limit (32 per axis) read on wh x ww; for an image side outside 1..2^24 or image bytes outside [0, src_bytes); and for a window that
+ * shares no pixel with its image (wy0 >= h, wy0 + wh <= 0, wx0 >= w or wx0 + ww <= 0).
+ * One launch per 64 windows on the handle's stream (a window is 36 bytes of kernel arguments); nothing synchronises.  Uses no workspace.  The
+ * work is the window's: only the rows and columns of the image that the window's filter reads are loaded, whatever the image's size. */
+int jcm_fit_windows(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C,
+                    int OH, int OW, int pad, int out_f32, void* out, int32_t* geom);
+
 /* -- mirrored test-time evaluation -----------------------------------------------------
  * The maps of an image averaged with the un-mirrored maps of its mirror image: jcm_mirror_pairs makes the batch the tower sees,
  * jcm_mirror_merge folds the tower's maps back.  Both enqueue one launch on the handle's stream and do not synchronise.

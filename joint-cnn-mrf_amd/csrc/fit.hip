@@ -12,6 +12,14 @@
 //     item -- at 1080 x 1920 -> 405 x 720 the first version of this kernel spent more instructions on index arithmetic than on the filter.
 // The images of a launch travel in its kernel arguments (FitBatch, as gather.hip's indices do): nothing is uploaded, nothing for the host to
 // wait for.  The grid is the number of strips of the launch's images, not B times the strips of the widest.
+//
+// Windows (jcm.h: jcm_fit_windows) are the same kernel instantiated on FitWinBatch: the filter runs over the virtual wh x ww image
+// -- its rows and columns are the window's -- and only the staging step knows that a staged sample is image[wy0 + row][wx0 + col] where the image
+// has one and `pad` elsewhere.  A staged row outside the image is filled with `pad` before any offset is formed from it; the in-image part of a
+// staged row is [vb_lo, vb_hi) of its segment bytes and offsets are formed from its first in-image column only.  The strips, the ring and the
+// groups of rows are the window's, so the work is the window's whatever the image's size.  The FitBatch instantiation is the code it was.
+#include <type_traits>
+
 #include "kernels.h"
 #include "u8.h"
 
@@ -92,9 +100,15 @@ struct FitWalk {
   }
 };
 
+// the size the filter sees: the image's, or the window's
+__device__ __forceinline__ int fit_rows(const FitBatch& fb, int i) { return fb.h[i]; }
+__device__ __forceinline__ int fit_cols(const FitBatch& fb, int i) { return fb.w[i]; }
+__device__ __forceinline__ int fit_rows(const FitWinBatch& fb, int i) { return fb.wh[i]; }
+__device__ __forceinline__ int fit_cols(const FitWinBatch& fb, int i) { return fb.ww[i]; }
+
 // R ring rows, TX / TY: leading dimensions of the horizontal / vertical weight tables (>= the taps of any output of the launch's images)
-template <bool F32>
-__global__ __launch_bounds__(kFitThreads) void fit_images_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, FitBatch fb, int nimg, int b0, int C,
+template <bool F32, class Batch>
+__global__ __launch_bounds__(kFitThreads) void fit_images_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, Batch fb, int nimg, int b0, int C,
                                                                  int OH, int OW, unsigned pad, int R, int TX, int TY, void* __restrict__ out) {
   extern __shared__ __align__(16) double fit_lds[];
   const int TWC = kFitTW * C;
@@ -116,7 +130,8 @@ __global__ __launch_bounds__(kFitThreads) void fit_images_kernel(const uint8_t* 
   int bi = 0;
   while (bi + 1 < nimg && (int)blockIdx.x >= fb.first[bi + 1]) ++bi;
   const int s = blockIdx.x - fb.first[bi], nS = fb.first[bi + 1] - fb.first[bi];
-  const int h = fb.h[bi], w = fb.w[bi];
+  constexpr bool kWin = std::is_same<Batch, FitWinBatch>::value;
+  const int h = fit_rows(fb, bi), w = fit_cols(fb, bi);
   const int64_t off = fb.off[bi];
   const FitGeom g = fit_geometry(h, w, OH, OW);
   const size_t obase = (size_t)(b0 + bi) * OH * OW * C;
@@ -162,9 +177,35 @@ __global__ __launch_bounds__(kFitThreads) void fit_images_kernel(const uint8_t* 
   __syncthreads();
 
   unsigned* stage32 = reinterpret_cast<unsigned*>(stage);
+  // a whole image: every staged sample exists
   const int rowb = w * C;                                                                           // bytes of a source row
   const unsigned base_lo = (unsigned)reinterpret_cast<uintptr_t>(src) + (unsigned)off + (unsigned)seg_lo * C;      // mod 4: the alignment of a segment
   const int64_t seg_off = off + (int64_t)seg_lo * C;                                                // byte offset in src of row 0's segment
+  // a window: staged row `row` is image row wy0 + row, staged column 0 image column c0; [vb_lo, vb_hi) of the segment's bytes lie in the image
+  int ih = 0, wy0 = 0, vb_lo = 0, vb_hi = 0;
+  int64_t irowb = 0, in_off = 0;       // bytes of an image row; byte offset in src of image row 0's first in-image staged sample (segment byte vb_lo)
+  unsigned in_lo = 0;                  // mod 4: the alignment of segment byte 0 of image row 0
+  if constexpr (kWin) {
+    ih = fb.h[bi];
+    wy0 = fb.wy0[bi];
+    const int iw = fb.w[bi], c0 = fb.wx0[bi] + seg_lo;
+    vb_lo = max(0, -c0) * C;
+    vb_hi = min(segb / C, iw - c0) * C;
+    irowb = (int64_t)iw * C;
+    in_off = off + (int64_t)max(c0, 0) * C;
+    in_lo = (unsigned)reinterpret_cast<uintptr_t>(src) + (unsigned)in_off - (unsigned)vb_lo;
+  }
+  // the offset of a staged row's segment in its aligned words
+  auto shift_of = [&](int row) -> int {
+    if constexpr (kWin) {
+      const int ir = wy0 + row;
+      if (ir < 0 || ir >= ih || vb_hi <= vb_lo) return 0;      // a row of `pad`: no offset is formed
+      return (int)((in_lo + (unsigned)ir * (unsigned)irowb) & 3u);
+    } else {
+      return (int)((base_lo + (unsigned)row * (unsigned)rowb) & 3u);
+    }
+  };
+  const unsigned pad4 = pad * 0x01010101u;
 
   int nf = 0;      // source rows below nf have been filtered (or will never be read again)
   for (int o0 = 0; o0 < g.ch;) {
@@ -185,8 +226,22 @@ __global__ __launch_bounds__(kFitThreads) void fit_images_kernel(const uint8_t* 
       const int nr = min(hiG - r, rows_per_pass);
       for (FitWalk it(wpr); it.k < nr; it.next()) {
         const int row = r + it.k, wi = it.e;
-        const int shift = (int)((base_lo + (unsigned)row * (unsigned)rowb) & 3u);
-        if (wi * 4 < shift + segb) {
+        const int shift = shift_of(row);
+        if constexpr (kWin) {
+          const int ir = wy0 + row;
+          unsigned v = pad4;
+          if (ir >= 0 && ir < ih && vb_lo < vb_hi) {
+            const int sb = wi * 4 - shift;                                     // segment byte of the word's first byte
+            const int64_t ra = in_off + (int64_t)ir * irowb;                   // offset in src of segment byte vb_lo, a sample of the image
+            if (sb >= vb_lo && sb + 4 <= vb_hi) {
+              v = *reinterpret_cast<const unsigned*>(src + ra + (sb - vb_lo));    // a 4-byte aligned address, all four bytes in the image
+            } else if (sb + 4 > vb_lo && sb < vb_hi) {
+              v = 0;
+              for (int q = 0; q < 4; ++q) v |= (sb + q >= vb_lo && sb + q < vb_hi ? (unsigned)src[ra + (sb + q - vb_lo)] : pad) << (8 * q);
+            }
+          }
+          stage32[it.k * wpr + wi] = v;
+        } else if (wi * 4 < shift + segb) {
           const int64_t wa = seg_off + (int64_t)row * rowb - shift + wi * 4;      // a 4-byte aligned address
           unsigned v;
           if (wa >= 0 && wa + 4 <= src_bytes) {
@@ -203,7 +258,7 @@ __global__ __launch_bounds__(kFitThreads) void fit_images_kernel(const uint8_t* 
       const int slot0 = r % R;
       for (FitWalk it(twc); it.k < nr; it.next()) {
         const int row = r + it.k, e = it.e, x = ecol[e];
-        const int shift = (int)((base_lo + (unsigned)row * (unsigned)rowb) & 3u);
+        const int shift = shift_of(row);
         const uint8_t* p = stage + it.k * stride + shift + ebyte[e];
         const double* wgt = wx + x * TX;
         const int n = nx[x];
@@ -254,44 +309,65 @@ int fit_lds_bytes(int R, int C, int TX) {
   return (R * kFitTW * C + kFitTW * TX + kFitWyCap + raw) * (int)sizeof(double) + kFitStage + (2 * kFitTW + 4 * kFitGMax + 8 * kFitTW) * (int)sizeof(int);
 }
 
-}  // namespace
-
-hipError_t fit_images(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
+// one launch per Batch-ful of desc rows: (offset, h, w) of an image, or (offset, h, w, wy0, wx0, wh, ww) of a window
+template <class Batch>
+hipError_t fit_launch(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
                       hipStream_t st) {
+  constexpr bool kWin = std::is_same<Batch, FitWinBatch>::value;
+  constexpr int kMax = kWin ? kFitWinMax : kFitMax, kDesc = kWin ? 7 : 3;
   static LdsAttr attr_u8, attr_f32;
   const int lds_max = fit_lds_bytes(kFitRingCap, 4, kFitRingCap - 1);
-  const void* fn = out_f32 ? reinterpret_cast<const void*>(fit_images_kernel<true>) : reinterpret_cast<const void*>(fit_images_kernel<false>);
+  const void* fn = out_f32 ? reinterpret_cast<const void*>(fit_images_kernel<true, Batch>) : reinterpret_cast<const void*>(fit_images_kernel<false, Batch>);
   if (hipError_t e = (out_f32 ? attr_f32 : attr_u8).ensure(fn, lds_max); e != hipSuccess) return e;
-  for (int b0 = 0; b0 < B; b0 += kFitMax) {
-    const int nb = B - b0 < kFitMax ? B - b0 : kFitMax;
-    FitBatch fb{};
+  for (int b0 = 0; b0 < B; b0 += kMax) {
+    const int nb = B - b0 < kMax ? B - b0 : kMax;
+    Batch fb{};
     int TX = 0, TY = 0, R = 0;
     for (int i = 0; i < nb; ++i) {
-      const int64_t* d = desc + (size_t)(b0 + i) * 3;
+      const int64_t* d = desc + (size_t)(b0 + i) * kDesc;
       fb.off[i] = d[0];
       fb.h[i] = (int)d[1];
       fb.w[i] = (int)d[2];
-      const FitGeom g = fit_geometry(fb.h[i], fb.w[i], OH, OW);
+      int fh = fb.h[i], fw = fb.w[i];      // the size the filter sees
+      if constexpr (kWin) {
+        fb.wy0[i] = (int)d[3];
+        fb.wx0[i] = (int)d[4];
+        fb.wh[i] = fh = (int)d[5];
+        fb.ww[i] = fw = (int)d[6];
+      }
+      const FitGeom g = fit_geometry(fh, fw, OH, OW);
       fb.first[i + 1] = fb.first[i] + (g.cw + kFitTW - 1) / kFitTW;
-      const int tx = fit_taps_bound(fb.w[i], g.cw), ty = fit_taps_bound(fb.h[i], g.ch);
+      const int tx = fit_taps_bound(fw, g.cw), ty = fit_taps_bound(fh, g.ch);
       TX = tx > TX ? tx : TX;
       TY = ty > TY ? ty : TY;
       // a ring of the vertical support plus about twelve further output rows, so that a group of rows shares one pass over the source
-      const int r = ty + (int)std::ceil(12.0 * (double)fb.h[i] / (double)g.ch);
+      const int r = ty + (int)std::ceil(12.0 * (double)fh / (double)g.ch);
       R = r > R ? r : R;
     }
-    for (int i = nb; i < kFitMax; ++i) fb.first[i + 1] = fb.first[nb];
+    for (int i = nb; i < kMax; ++i) fb.first[i + 1] = fb.first[nb];
     if (TX > kFitRingCap - 1 || TY > kFitRingCap - 1) return hipErrorInvalidValue;      // a reduction above 32: the entry point refuses it
     R = R > kFitRingCap ? kFitRingCap : R;
     const int lds = fit_lds_bytes(R, C, TX);
     if (out_f32)
-      hipLaunchKernelGGL(fit_images_kernel<true>, dim3(fb.first[nb]), dim3(kFitThreads), lds, st, src, src_bytes, fb, nb, b0, C, OH, OW, (unsigned)pad, R,
-                         TX, TY, out);
+      hipLaunchKernelGGL((fit_images_kernel<true, Batch>), dim3(fb.first[nb]), dim3(kFitThreads), lds, st, src, src_bytes, fb, nb, b0, C, OH, OW,
+                         (unsigned)pad, R, TX, TY, out);
     else
-      hipLaunchKernelGGL(fit_images_kernel<false>, dim3(fb.first[nb]), dim3(kFitThreads), lds, st, src, src_bytes, fb, nb, b0, C, OH, OW, (unsigned)pad, R,
-                         TX, TY, out);
+      hipLaunchKernelGGL((fit_images_kernel<false, Batch>), dim3(fb.first[nb]), dim3(kFitThreads), lds, st, src, src_bytes, fb, nb, b0, C, OH, OW,
+                         (unsigned)pad, R, TX, TY, out);
   }
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t fit_images(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
+                      hipStream_t st) {
+  return fit_launch<FitBatch>(src, src_bytes, desc, B, C, OH, OW, pad, out_f32, out, st);
+}
+
+hipError_t fit_windows(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, bool out_f32, void* out,
+                       hipStream_t st) {
+  return fit_launch<FitWinBatch>(src, src_bytes, desc, NW, C, OH, OW, pad, out_f32, out, st);
 }
 
 }  // namespace jcm

@@ -747,13 +747,49 @@ int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float
   return JCM_OK;
 }
 
+namespace {
+
+// what jcm_fit_images and jcm_fit_windows check alike (`who` names the entry point in the message): pointers, the frame, the size of out
+int fit_check_frame(const std::string& who, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad,
+                    const void* out) {
+  if (!src || !desc || !out) return fail(JCM_ERR_ARG, who + ": null pointer (src, desc and out are required, geom may be NULL)");
+  if (B < 1 || C < 1 || C > 4 || OH < 1 || OH > 4096 || OW < 1 || OW > 4096 || pad < 0 || pad > 255 || src_bytes < 1)
+    return fail(JCM_ERR_ARG, who + ": bad sizes (B >= 1, C in 1..4, OH and OW in 1..4096, pad in 0..255)");
+  if ((int64_t)B * OH * OW * C >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, who + ": B * OH * OW * C >= 2^31");
+  return JCM_OK;
+}
+// fh x fw, the size the filter sees (an image, or a window), against the size and reduction limits
+int fit_check_size(const std::string& who, int64_t fh, int64_t fw, int OH, int OW) {
+  if (fh < 1 || fh > 16384 || fw < 1 || fw > 16384)
+    return fail(JCM_ERR_ARG, who + " is " + std::to_string(fh) + " x " + std::to_string(fw) + "; both sides lie in 1..16384");
+  const FitGeom g = fit_geometry((int)fh, (int)fw, OH, OW);
+  if (fh > 32 * (int64_t)g.ch || fw > 32 * (int64_t)g.cw)
+    return fail(JCM_ERR_ARG, who + ", " + std::to_string(fh) + " x " + std::to_string(fw) + " into " + std::to_string(g.ch) + " x " + std::to_string(g.cw) +
+                                 ": a reduction above 32 (at most 66 taps per axis)");
+  return JCM_OK;
+}
+int fit_check_overlap(const std::string& who, const uint8_t* src, int64_t src_bytes, const void* out, size_t no) {
+  const char *pa = reinterpret_cast<const char*>(src), *pb = static_cast<const char*>(out);
+  if (pa < pb + no && pb < pa + src_bytes) return fail(JCM_ERR_ARG, who + ": out overlaps src");
+  return JCM_OK;
+}
+// geom[i] = the content rectangle of desc row i (`stride` entries a row, the filter's size at entries at, at + 1)
+void fit_write_geom(const int64_t* desc, int B, int stride, int at, int OH, int OW, int32_t* geom) {
+  for (int b = 0; b < B; ++b) {
+    const FitGeom g = fit_geometry((int)desc[b * (int64_t)stride + at], (int)desc[b * (int64_t)stride + at + 1], OH, OW);
+    geom[b * (int64_t)4] = g.y0;
+    geom[b * (int64_t)4 + 1] = g.x0;
+    geom[b * (int64_t)4 + 2] = g.ch;
+    geom[b * (int64_t)4 + 3] = g.cw;
+  }
+}
+
+}  // namespace
+
 int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, int out_f32,
                    void* out, int32_t* geom) {
   JCM_TRY(check(h, false));
-  if (!src || !desc || !out) return fail(JCM_ERR_ARG, "fit_images: null pointer (src, desc and out are required, geom may be NULL)");
-  if (B < 1 || C < 1 || C > 4 || OH < 1 || OH > 4096 || OW < 1 || OW > 4096 || pad < 0 || pad > 255 || src_bytes < 1)
-    return fail(JCM_ERR_ARG, "fit_images: bad sizes (B >= 1, C in 1..4, OH and OW in 1..4096, pad in 0..255)");
-  if ((int64_t)B * OH * OW * C >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, "fit_images: B * OH * OW * C >= 2^31");
+  JCM_TRY(fit_check_frame("fit_images", src, src_bytes, desc, B, C, OH, OW, pad, out));
   for (int b = 0; b < B; ++b) {
     const int64_t off = desc[b * (int64_t)3], hb = desc[b * (int64_t)3 + 1], wb = desc[b * (int64_t)3 + 2];
     const std::string who = "fit_images: image " + std::to_string(b);
@@ -762,24 +798,10 @@ int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const in
     if (off < 0 || off > src_bytes || hb * wb * C > src_bytes - off)
       return fail(JCM_ERR_ARG, who + " (" + std::to_string(hb * wb * C) + " bytes at offset " + std::to_string(off) + ") does not lie inside the " +
                                    std::to_string(src_bytes) + " bytes of src");
-    const FitGeom g = fit_geometry((int)hb, (int)wb, OH, OW);
-    if (hb > 32 * (int64_t)g.ch || wb > 32 * (int64_t)g.cw)
-      return fail(JCM_ERR_ARG, who + ", " + std::to_string(hb) + " x " + std::to_string(wb) + " into " + std::to_string(g.ch) + " x " + std::to_string(g.cw) +
-                                   ": a reduction above 32 (at most 66 taps per axis)");
+    JCM_TRY(fit_check_size(who, hb, wb, OH, OW));
   }
-  const size_t no = (size_t)B * OH * OW * C * (out_f32 ? sizeof(float) : 1);
-  {
-    const char *pa = reinterpret_cast<const char*>(src), *pb = static_cast<const char*>(out);
-    if (pa < pb + no && pb < pa + src_bytes) return fail(JCM_ERR_ARG, "fit_images: out overlaps src");
-  }
-  if (geom)
-    for (int b = 0; b < B; ++b) {
-      const FitGeom g = fit_geometry((int)desc[b * (int64_t)3 + 1], (int)desc[b * (int64_t)3 + 2], OH, OW);
-      geom[b * (int64_t)4] = g.y0;
-      geom[b * (int64_t)4 + 1] = g.x0;
-      geom[b * (int64_t)4 + 2] = g.ch;
-      geom[b * (int64_t)4 + 3] = g.cw;
-    }
+  JCM_TRY(fit_check_overlap("fit_images", src, src_bytes, out, (size_t)B * OH * OW * C * (out_f32 ? sizeof(float) : 1)));
+  if (geom) fit_write_geom(desc, B, 3, 1, OH, OW, geom);
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
@@ -788,6 +810,38 @@ int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const in
   const hipError_t launch = fit_images(src, src_bytes, desc, B, C, OH, OW, pad, out_f32 != 0, out, c->stream);
   prof_end(c, "fit_images", e0, e1, launch == hipSuccess);
   if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("fit_images: ") + hipGetErrorString(launch));
+  return JCM_OK;
+}
+
+int jcm_fit_windows(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, int out_f32,
+                    void* out, int32_t* geom) {
+  JCM_TRY(check(h, false));
+  JCM_TRY(fit_check_frame("fit_windows", src, src_bytes, desc, NW, C, OH, OW, pad, out));
+  constexpr int64_t kSide = (int64_t)1 << 24;      // image sides: rows, columns and their sums with a window's stay far inside int
+  for (int i = 0; i < NW; ++i) {
+    const int64_t* d = desc + i * (int64_t)7;
+    const int64_t off = d[0], hb = d[1], wb = d[2], wy0 = d[3], wx0 = d[4], wh = d[5], ww = d[6];
+    const std::string who = "fit_windows: window " + std::to_string(i);
+    if (hb < 1 || hb > kSide || wb < 1 || wb > kSide)
+      return fail(JCM_ERR_ARG, who + ": its image is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..2^24");
+    if (off < 0 || off > src_bytes || hb * wb * C > src_bytes - off)
+      return fail(JCM_ERR_ARG, who + ": its image (" + std::to_string(hb * wb * C) + " bytes at offset " + std::to_string(off) +
+                                   ") does not lie inside the " + std::to_string(src_bytes) + " bytes of src");
+    JCM_TRY(fit_check_size(who, wh, ww, OH, OW));
+    if (wy0 >= hb || wy0 + wh <= 0 || wx0 >= wb || wx0 + ww <= 0)      // wh, ww <= 16384: the sums cannot overflow unless the window is disjoint anyway
+      return fail(JCM_ERR_ARG, who + ", rows " + std::to_string(wy0) + ".. and columns " + std::to_string(wx0) + ".., " + std::to_string(wh) + " x " +
+                                   std::to_string(ww) + ", shares no pixel with its " + std::to_string(hb) + " x " + std::to_string(wb) + " image");
+  }
+  JCM_TRY(fit_check_overlap("fit_windows", src, src_bytes, out, (size_t)NW * OH * OW * C * (out_f32 ? sizeof(float) : 1)));
+  if (geom) fit_write_geom(desc, NW, 7, 5, OH, OW, geom);
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  hipEvent_t e0, e1;
+  JCM_TRY(prof_begin(c, &e0, &e1));
+  const hipError_t launch = fit_windows(src, src_bytes, desc, NW, C, OH, OW, pad, out_f32 != 0, out, c->stream);
+  prof_end(c, "fit_windows", e0, e1, launch == hipSuccess);
+  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("fit_windows: ") + hipGetErrorString(launch));
   return JCM_OK;
 }
 

@@ -366,6 +366,20 @@ __host__ __device__ inline FitGeom fit_geometry(int h, int w, int OH, int OW) {
 // separable triangle filter of jcm.h in float64, `pad` outside the content rectangle.  One launch per kFitMax images.
 hipError_t fit_images(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
                       hipStream_t st);
+// The windows of a launch (jcm.h: jcm_fit_windows): window i is rows [wy0, wy0 + wh) x columns [wx0, wx0 + ww) of the h x w image
+// at off, `pad` where the image has no sample.  36 bytes a window: 64 of them are 2308 bytes of kernel arguments (FitBatch: 1284; the limit is 4096).
+constexpr int kFitWinMax = 64;
+struct FitWinBatch {
+  int64_t off[kFitWinMax];      // byte offset in src of the IMAGE window i is cut from
+  int h[kFitWinMax], w[kFitWinMax];
+  int wy0[kFitWinMax], wx0[kFitWinMax], wh[kFitWinMax], ww[kFitWinMax];
+  int first[kFitWinMax + 1];    // work groups [first[i], first[i + 1]) are the strips of window i
+};
+// desc: HOST int64 [NW][7] = (byte offset, h, w, wy0, wx0, wh, ww), every entry checked by the caller (as for fit_images, the size and reduction
+// limits on wh x ww; image sides <= 2^24; every window shares a pixel with its image) -> out [NW,OH,OW,C]: fit_images of the padded window, bit
+// for bit.  One launch per kFitWinMax windows; the source rows and columns a work group stages are those of its window's support only.
+hipError_t fit_windows(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, bool out_f32, void* out,
+                       hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

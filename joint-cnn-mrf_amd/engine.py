@@ -602,12 +602,28 @@ class Engine:
         one launch per 64 images.  Returns (x [B,OH,OW,3] of `dtype` -- torch.uint8, or torch.float32 = byte / 255 -- and geom, host int32 [B,6] =
         (y0, x0, ch, cw, h, w): the content rectangle and the source size, what evaluation.fit_to_source takes).  out: a tensor to write into
         instead of a new one.  Sizes, pad and the reduction limit (32 per axis) are checked by the library."""
+        ts, desc, off, dtype = self._fit_check(images, dtype)
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        B, C = len(ts), 3
+        out = self._fit_out(out, B, OH, OW, C, dtype)
+        src = self._fit_pack(ts, desc, off)
+        geom = np.empty((B, 6), np.int32)
+        g4 = np.empty((B, 4), np.int32)
+        self._on_stream(src, out)
+        _lib.check(self._lib.jcm_fit_images(self._h, self._p(src), off, desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B, C, OH, OW, int(pad),
+                                            int(dtype == torch.float32), self._p(out), g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), 'jcm_fit_images')
+        geom[:, :4] = g4
+        geom[:, 4:] = desc[:, 1:]
+        return out, geom
+
+    def _fit_check(self, images, dtype):
+        """The input checks fit_images and fit_windows share -> (the images as uint8 torch tensors, desc int64 [B,3] = (byte offset in the packed
+        buffer, h, w), the buffer's bytes, dtype)."""
         if not isinstance(images, (list, tuple)) or len(images) == 0:
             raise ValueError('images must be a non-empty list of uint8 [h,w,3] images')
         if dtype not in (torch.uint8, torch.float32):
             raise TypeError('dtype must be torch.uint8 or torch.float32, got %s' % (dtype,))
-        OH, OW = int(out_hw[0]), int(out_hw[1])
-        B, C = len(images), 3
+        C = 3
         ts = []
         for i, im in enumerate(images):
             name = 'images[%d]' % i
@@ -624,31 +640,58 @@ class Engine:
             if im.device.type != 'cpu' and im.device != self.device:
                 raise ValueError('%s is on %s, engine is on %s' % (name, im.device, self.device))
             ts.append(im)
-        desc = np.empty((B, 3), np.int64)
+        desc = np.empty((len(ts), 3), np.int64)
         off = 0
         for i, im in enumerate(ts):
             desc[i] = (off, im.shape[0], im.shape[1])
             off += im.numel()
+        return ts, desc, off, dtype
+
+    def _fit_out(self, out, B, OH, OW, C, dtype):
         if out is None:
-            out = self._new(B, OH, OW, C, dtype=dtype)
-        else:
-            self._chk(out, 4, 'out', dtype)
-            if tuple(out.shape) != (B, OH, OW, C):
-                raise ValueError('out must be [%d,%d,%d,%d], got %s' % (B, OH, OW, C, tuple(out.shape)))
+            return self._new(B, OH, OW, C, dtype=dtype)
+        self._chk(out, 4, 'out', dtype)
+        if tuple(out.shape) != (B, OH, OW, C):
+            raise ValueError('out must be [%d,%d,%d,%d], got %s' % (B, OH, OW, C, tuple(out.shape)))
+        return out
+
+    def _fit_pack(self, ts, desc, off):
+        """The images back to back in one device buffer of `off` bytes."""
         src = self._new(off, dtype=torch.uint8)
-        host = [i for i, im in enumerate(ts) if im.device.type == 'cpu']
-        if len(host) == B:      # one packed host buffer, one copy
+        if all(im.device.type == 'cpu' for im in ts):      # one packed host buffer, one copy
             src.copy_(torch.cat([im.reshape(-1) for im in ts]))
         else:
             for i, im in enumerate(ts):
                 src[int(desc[i, 0]):int(desc[i, 0]) + im.numel()].copy_(im.reshape(-1))
-        geom = np.empty((B, 6), np.int32)
-        g4 = np.empty((B, 4), np.int32)
+        return src
+
+    def fit_windows(self, images, windows, out_hw=(480, 720), pad=0, dtype=torch.uint8, out=None):
+        """Rectangles of images of any size into the frame the tower reads (include/jcm.h: jcm_fit_windows): `images` as for
+        fit_images; `windows` int [NW,5] = (image index, y0, x0, h, w), the convention of window_resize: rows [y0, y0 + h) and columns
+        [x0, x0 + w) of that image, which may reach past any edge (the byte `pad` stands where the image has no sample, and takes part in the
+        filter) and may name an image more than once.  Each window is fitted exactly as fit_images would fit the padded crop.  One packed
+        device buffer, one launch per 64 windows.  Returns (x [NW,OH,OW,3] of `dtype`, geom host int32 [NW,6] = (y0, x0, ch, cw, h, w) with the
+        WINDOW's size: what evaluation.window_to_source takes together with `windows`).  A window that shares no pixel with its image, and the
+        size and reduction limits, are refused by the library."""
+        ts, desc, off, dtype = self._fit_check(images, dtype)
+        wins = np.asarray(windows)
+        if wins.dtype.kind not in 'iu' or wins.ndim != 2 or wins.shape[1] != 5 or wins.shape[0] < 1:
+            raise ValueError('windows must be an integer array [NW,5] = (image index, y0, x0, h, w), got %s %s' % (wins.dtype, wins.shape))
+        wins = wins.astype(np.int64)
+        if wins[:, 0].min() < 0 or wins[:, 0].max() >= len(ts):
+            raise ValueError('windows name images %d..%d; there are %d' % (wins[:, 0].min(), wins[:, 0].max(), len(ts)))
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        NW, C = wins.shape[0], 3
+        out = self._fit_out(out, NW, OH, OW, C, dtype)
+        src = self._fit_pack(ts, desc, off)
+        d7 = np.ascontiguousarray(np.concatenate([desc[wins[:, 0]], wins[:, 1:]], axis=1))
+        geom = np.empty((NW, 6), np.int32)
+        g4 = np.empty((NW, 4), np.int32)
         self._on_stream(src, out)
-        _lib.check(self._lib.jcm_fit_images(self._h, self._p(src), off, desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B, C, OH, OW, int(pad),
-                                            int(dtype == torch.float32), self._p(out), g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), 'jcm_fit_images')
+        _lib.check(self._lib.jcm_fit_windows(self._h, self._p(src), off, d7.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), NW, C, OH, OW, int(pad),
+                                             int(dtype == torch.float32), self._p(out), g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), 'jcm_fit_windows')
         geom[:, :4] = g4
-        geom[:, 4:] = desc[:, 1:]
+        geom[:, 4:] = wins[:, 3:]
         return out, geom
 
     def mirror_pairs(self, x):

@@ -93,6 +93,43 @@ def fit_to_source(points, geom):
     return out, inside
 
 
+def fit_geometry(h, w, OH, OW):
+    """(y0, x0, ch, cw): the content rectangle of an h x w source in an OH x OW frame, the integer arithmetic include/jcm.h states for
+    jcm_fit_images (and, on a window's size, jcm_fit_windows)."""
+    h, w, OH, OW = int(h), int(w), int(OH), int(OW)
+    if OH * w <= OW * h:
+        ch, cw = OH, max(1, (2 * w * OH + h) // (2 * h))
+    else:
+        cw, ch = OW, max(1, (2 * h * OW + w) // (2 * w))
+    return (OH - ch) // 2, (OW - cw) // 2, ch, cw
+
+
+def window_to_source(points, geom, windows, sizes):
+    """Points of fitted windows back into the images the windows were cut from.  points [N,...,2+] and geom [N,6] as for
+    fit_to_source, geom being what Engine.fit_windows returned -- (y0, x0, ch, cw, wh, ww), the WINDOW's size --; windows: the int [N,5] =
+    (image index, wy0, wx0, wh, ww) that call was given; sizes: int [n_images,2] = (h, w) of the images the windows index.  Returns
+    fit_to_source(points, geom) with (wy0, wx0) added to the row and column entries, and `inside`: fit_to_source's (the fitted point lay in the
+    content rectangle) and the mapped point lies in [-0.5, h - 0.5) x [-0.5, w - 0.5) of its image -- not in the part of the window that the
+    image does not cover.  Filler rows pass through as in fit_to_source."""
+    windows, sizes = np.asarray(windows), np.asarray(sizes)
+    if windows.ndim != 2 or windows.shape[1] != 5 or sizes.ndim != 2 or sizes.shape[1] != 2:
+        raise ValueError('window_to_source expects windows [N,5] and sizes [n_images,2]; got %s, %s' % (windows.shape, sizes.shape))
+    out, inside = fit_to_source(points, geom)
+    if windows.shape[0] != out.shape[0] or windows[:, 0].min() < 0 or windows[:, 0].max() >= sizes.shape[0]:
+        raise ValueError('window_to_source: %d windows naming images %d..%d for %d points and %d sizes' %
+                         (windows.shape[0], windows[:, 0].min(), windows[:, 0].max(), out.shape[0], sizes.shape[0]))
+    lead = (windows.shape[0],) + (1,) * (out.ndim - 2)
+    hw = sizes[windows[:, 0]].astype(np.float64)
+    pts = np.asarray(points, dtype=np.float64)
+    filler = (pts[..., 0] < 0) & (pts[..., 1] < 0)      # fit_to_source left these rows as they were
+    row = out[..., 0] + windows[:, 1].astype(np.float64).reshape(lead)
+    col = out[..., 1] + windows[:, 2].astype(np.float64).reshape(lead)
+    inside = inside & (row >= -0.5) & (row < hw[:, 0].reshape(lead) - 0.5) & (col >= -0.5) & (col < hw[:, 1].reshape(lead) - 0.5)
+    out[..., 0] = np.where(filler, out[..., 0], row)
+    out[..., 1] = np.where(filler, out[..., 1], col)
+    return out, inside
+
+
 def get_next_batch(X, Y, batch_size, shuffle=False, rng=None):
     """main.py:184-192: whole batches only -- the remainder len(X) % batch_size is dropped; `shuffle` draws a permutation."""
     import numpy as np

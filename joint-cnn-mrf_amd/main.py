@@ -90,6 +90,9 @@ def build_parser():
                         'sorted order) -> the nine joints in each image\'s own pixels, written as JSON to the file of --predictions (predict.predict_images, DESIGN.md '
                         '4.16): the images are letterboxed into 480x720 on the device, with --use_sm the torso is inferred; --peaks, --decode_pose, --people and '
                         '--batch_size apply.  .npy files holding uint8 [h,w,3] are always read; other formats need PIL.  Runs on the first device of --gpus.')
+    parser.add_argument('--zoom', action='store_true', help='with --predict and --use_sm: a second pass -- a window around every person of the first pass, sized so '
+                        'that the torso has the length FLIC torsos have in a 480-row frame, is fitted and run through the tower again (DESIGN.md 4.17); every '
+                        'image of the document gains "zoom", one entry per person.  What it buys with FLIC-trained weights has not been measured.')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -366,6 +369,9 @@ PREDICT_NOT_WITH_FLIP_TEST = ('--predict cannot be combined with --flip_test: wi
                               'evaluation is not defined')
 PREDICT_NOT_WITH_DET_CURVE = '--predict cannot be combined with --det_curve: the named images have no annotation to measure a detection rate against'
 PREDICT_NOT_WITH_DEVICE_DATA = '--predict cannot be combined with --device_data: that flag places the training sets of --train'
+ZOOM_NEEDS_PREDICT = '--zoom is the second pass of --predict (a window around every person the first pass found): give --predict PATH as well'
+ZOOM_NEEDS_USE_SM = ('--zoom needs --use_sm: the windows are placed at the inferred torso and sized by the shoulders and hips of the spatial model, '
+                     'and the second pass runs the spatial model at the torso cell it is given')
 
 
 def predict_main(args):
@@ -385,14 +391,17 @@ def predict_main(args):
     try:
         timing = {}
         results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
-                                         batch_size=args.batch_size, timing=timing)
+                                         batch_size=args.batch_size, timing=timing, zoom=args.zoom)
     finally:
         eng.close()
     os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
     with open(args.predictions, 'w') as fh:
         json.dump(predict.predictions_document(files, results), fh)
-    print(json.dumps({'predict': True, 'n_images': len(files), 'fit_ms': timing['fit_ms'], 'forward_ms': timing['forward_ms'], 'gpu': args.gpus[0],
-                      'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}))
+    line = {'predict': True, 'n_images': len(files), 'fit_ms': timing['fit_ms'], 'forward_ms': timing['forward_ms'], 'gpu': args.gpus[0],
+            'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}
+    if args.zoom:
+        line.update(zoom=True, zoom_fit_ms=timing['zoom_fit_ms'], zoom_forward_ms=timing['zoom_forward_ms'])
+    print(json.dumps(line))
 
 
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
@@ -642,6 +651,11 @@ def main(argv=None):
                                (not args.predictions, PREDICT_NEEDS_PREDICTIONS)):
             if given:
                 raise SystemExit(message)
+    if args.zoom:
+        if not args.predict:
+            raise SystemExit(ZOOM_NEEDS_PREDICT)
+        if not args.use_sm:
+            raise SystemExit(ZOOM_NEEDS_USE_SM)
     if args.train and args.det_curve:
         raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
     if args.train and args.flip_test:
