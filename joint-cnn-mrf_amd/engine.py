@@ -307,12 +307,18 @@ class Engine:
                                           self._p(out['scores']), self._p(out['count'])), 'jcm_hm_peaks')
         return out
 
-    def _add_peaks(self, r, peaks, scratch):
-        """forward(peaks=P) / eval_forward(peaks=P): hm_peaks of the call's probabilities, which are in r (want_prob) or in scratch."""
-        for key in ('pd', 'sm'):
+    def _add_peaks_pose(self, r, scratch, peaks, decode, torso):
+        """The tail of the forward family.  peaks = P: hm_peaks of the call's probabilities, which are in r (want_prob) or in scratch; decode:
+        pose_decode of the call's pd_peaks on its part-detector probabilities and torso map.  Returns r."""
+        for key in ('pd', 'sm') if peaks else ():
             prob = r.get(key + '_prob', scratch.get(key + '_prob'))
             if prob is not None:
                 r[key + '_peaks'] = self.hm_peaks(prob, max_peaks=peaks)
+        if decode:
+            with torch.cuda.stream(self._stream):      # the probabilities were written on the engine's stream
+                hm10 = torch.cat([r.get('pd_prob', scratch.get('pd_prob')), torso], dim=3)
+            r['pose'] = self.pose_decode(hm10, r['pd_peaks'])
+        return r
 
     def pose_decode(self, hm10, peaks, want_tables=False):
         """Of the candidate cells per joint in `peaks` (the dict of hm_peaks on nine joint maps, P <= 4: 'cells' int32 [B,9,P,2], 'count' int32
@@ -343,11 +349,14 @@ class Engine:
         if decode and not (use_sm and 1 <= peaks <= 4):
             raise ValueError('decode=True needs use_sm=True and 1 <= peaks <= 4 (the candidates are pd_peaks); got use_sm=%s, peaks=%s' % (bool(use_sm), peaks))
 
-    def _add_pose(self, r, scratch, torso):
-        """forward(decode=True) / eval_forward(decode=True): pose_decode of the call's pd_peaks on its part-detector probabilities and torso map."""
-        with torch.cuda.stream(self._stream):      # the probabilities were written on the engine's stream
-            hm10 = torch.cat([r.get('pd_prob', scratch.get('pd_prob')), torso], dim=3)
-        r['pose'] = self.pose_decode(hm10, r['pd_peaks'])
+    def _dead_slots(self, count, vs, float_fill):
+        """The tensors vs, each [B,M,...], with the slots at or beyond count [B] emptied: int32 entries become -1, float entries float_fill --
+        -inf through torch.where, 0 by multiplying with the live mask.  A list, made inside the caller's `with torch.cuda.stream(self._stream)`."""
+        B, M = vs[0].shape[:2]
+        live = torch.arange(M, device=self.device).view(1, M) < count.view(B, 1)          # [B,M]
+        lives = [live.view(B, M, *([1] * (v.dim() - 2))) for v in vs]
+        return [v * lv.to(v.dtype) if v.dtype != torch.int32 and float_fill == 0
+                else torch.where(lv, v, torch.full_like(v, -1 if v.dtype == torch.int32 else float_fill)) for v, lv in zip(vs, lives)]
 
     def torso_infer(self, prob, want_energy=False, cells=None):
         """The torso map from the part detector (include/jcm.h: jcm_torso_infer): prob [B,60,90,9], the part-detector
@@ -407,12 +416,10 @@ class Engine:
             pm, cm = self.softmax_argmax(self.spatial_model(hm10), want_prob=want_prob)
             with torch.cuda.stream(self._stream):
                 count = pk['count'].view(B)
-                live = torch.arange(M, device=self.device).view(1, M) < count.view(B, 1)          # [B,M]
-                cm = cm.view(B, M, 2, K)
-                cm = torch.where(live.view(B, M, 1, 1), cm, torch.full_like(cm, -1))
+                cm, *pm = self._dead_slots(count, [cm.view(B, M, 2, K)] + ([pm.view(B, M, 60, 90, K)] if pm is not None else []), 0)
+                pm = pm[0] if pm else None
                 r['people'] = {'count': count, 'torso_cell': cells, 'torso_score': pk['scores'].view(B, M), 'sm_coords': cm}
                 if pm is not None:
-                    pm = pm.view(B, M, 60, 90, K) * live.view(B, M, 1, 1, 1).to(pm.dtype)
                     r['people']['sm_prob'] = pm
                 r['torso_cell'], r['torso'] = cells[:, 0].contiguous(), blobs.view(B, M, 60, 90, 1)[:, 0].contiguous()
                 r['sm_coords'] = cm[:, 0].contiguous()
@@ -436,20 +443,12 @@ class Engine:
             if M > 1:
                 s['people'].pop('sm_prob', None)
         r.update(s)
-        if peaks:
-            self._add_peaks(r, peaks, scratch)
-        if decode and M == 1:
-            self._add_pose(r, scratch, r['torso'])
-        elif decode:      # per slot: image b's candidates against each of its M torso maps
+        self._add_peaks_pose(r, scratch, peaks, decode and M == 1, r['torso'])
+        if decode and M > 1:      # per slot: image b's candidates against each of its M torso maps
             rep = {k: r['pd_peaks'][k].repeat_interleave(M, dim=0).contiguous() for k in ('cells', 'count')}
             pose = self.pose_decode(hm10, rep)
             with torch.cuda.stream(self._stream):      # slots at or beyond count have no pose: -1 / -inf, as pose_decode writes an image without one
-                live = torch.arange(M, device=self.device).view(1, M) < r['people']['count'].view(B, 1)
-                r['pose'] = {}
-                for k, v in pose.items():
-                    v = v.view(B, M, *v.shape[1:])
-                    none = torch.full_like(v, -1 if v.dtype == torch.int32 else float('-inf'))
-                    r['pose'][k] = torch.where(live.view(B, M, *([1] * (v.dim() - 2))), v, none)
+                r['pose'] = dict(zip(pose, self._dead_slots(r['people']['count'], [v.view(B, M, *v.shape[1:]) for v in pose.values()], float('-inf'))))
         return r
 
     def softmax_argmax(self, logits, want_prob=True):
@@ -481,7 +480,7 @@ class Engine:
         count holding -1 in the coordinates and 0 in the maps; the top-level 'sm_*', 'torso_cell' and 'torso' are slot 0, and with decode 'pose'
         is decoded per slot, [B,M,...].  flip_test=True with torso='infer' is a ValueError."""
         self._chk_decode(decode, use_sm, peaks)
-        u8 = self._chk_img(x, 'x')
+        self._chk_img(x, 'x')
         B, H, W, C = x.shape
         if C != 3:
             raise ValueError('x must be [B,H,W,3]')
@@ -503,26 +502,26 @@ class Engine:
                 raise ValueError('torso must be [B,60,90,1], got %s' % (tuple(torso.shape),))
         if flip_test:
             return self._forward_flip(x, torso, use_sm, want_prob, peaks, decode)
+        return self._tower_call('jcm_forward', x, torso if use_sm else None, use_sm, want_prob, peaks, decode, torso)
+
+    def _tower_call(self, entry, x, maps, use_sm, want_prob, peaks, decode, torso, losses=False):
+        """The library call forward and eval_forward share: `entry` (its _u8 twin for byte images) on x and `maps` (forward's torso map, eval_forward's
+        y) into a new result dict -- 'pd_coords', with use_sm 'sm_coords', with want_prob the '*_prob' maps (with peaks and without want_prob they go
+        to a scratch dict instead), with `losses` 'losses' fp32 [2], the entry's last argument -- then the peaks and pose tail."""
+        B, H, W, _ = x.shape
         hh, ww, K = _hm_size(H), _hm_size(W), self.n_joints
-        r = {'pd_coords': self._new(B, 2, K, dtype=torch.int32)}
-        if want_prob:
-            r['pd_prob'] = self._new(B, hh, ww, K)
-        if use_sm:
-            r['sm_coords'] = self._new(B, 2, K, dtype=torch.int32)
-            if want_prob:
-                r['sm_prob'] = self._new(B, hh, ww, K)
-        scratch = {}
-        if peaks and not want_prob:
-            scratch = {k + '_prob': self._new(B, hh, ww, K) for k in (('pd', 'sm') if use_sm else ('pd',))}
-        fn, what = (self._lib.jcm_forward_u8, 'jcm_forward_u8') if u8 else (self._lib.jcm_forward, 'jcm_forward')
-        _lib.check(fn(self._h, self._p(x), self._p(torso if use_sm else None), B, H, W, int(bool(use_sm)),
-                      self._p(r.get('pd_prob', scratch.get('pd_prob'))), self._p(r.get('sm_prob', scratch.get('sm_prob'))),
-                      self._p(r['pd_coords']), self._p(r.get('sm_coords'))), what)
-        if peaks:
-            self._add_peaks(r, peaks, scratch)
-        if decode:
-            self._add_pose(r, scratch, torso)
-        return r
+        r, scratch = {}, {}
+        for key in ('pd', 'sm') if use_sm else ('pd',):
+            r[key + '_coords'] = self._new(B, 2, K, dtype=torch.int32)
+            if want_prob or peaks:
+                (r if want_prob else scratch)[key + '_prob'] = self._new(B, hh, ww, K)
+        if losses:
+            r['losses'] = self._new(2)
+        what = entry + ('_u8' if x.dtype == torch.uint8 else '')
+        _lib.check(getattr(self._lib, what)(self._h, self._p(x), self._p(maps), B, H, W, int(bool(use_sm)),
+                                            self._p(r.get('pd_prob', scratch.get('pd_prob'))), self._p(r.get('sm_prob', scratch.get('sm_prob'))),
+                                            self._p(r['pd_coords']), self._p(r.get('sm_coords')), *([self._p(r['losses'])] if losses else [])), what)
+        return self._add_peaks_pose(r, scratch, peaks, decode, torso)
 
     def _forward_flip(self, x, torso, use_sm, want_prob, peaks, decode):
         """forward(flip_test=True): the existing forward on the 2B interleaved images, its maps merged pair by pair."""
@@ -533,11 +532,7 @@ class Engine:
             prob = self.mirror_merge(r2[key + '_prob'])
             r[key + '_coords'] = self.argmax_coords(prob)
             (r if want_prob else scratch)[key + '_prob'] = prob
-        if peaks:
-            self._add_peaks(r, peaks, scratch)
-        if decode:
-            self._add_pose(r, scratch, torso)
-        return r
+        return self._add_peaks_pose(r, scratch, peaks, decode, torso)
 
     def eval_forward(self, x, y, use_sm=True, want_prob=True, peaks=0, decode=False):
         """The tower in inference mode plus the two cross-entropy losses of the graph (main.py:538-539), as eval_error
@@ -545,31 +540,13 @@ class Engine:
         forward() plus 'losses' (device fp32 [2]: loss_pd, loss_sm).  x: float32 or uint8, as for forward(); peaks and decode as for forward()
         (the torso map is channel K of y)."""
         self._chk_decode(decode, use_sm, peaks)
-        u8 = self._chk_img(x, 'x')
+        self._chk_img(x, 'x')
         self._chk(y, 4, 'y')
         B, H, W, C = x.shape
         hh, ww, K = _hm_size(H), _hm_size(W), self.n_joints
         if C != 3 or tuple(y.shape) != (B, hh, ww, K + 1):
             raise ValueError('x must be [B,H,W,3] and y [B,%d,%d,%d]; got %s, %s' % (hh, ww, K + 1, tuple(x.shape), tuple(y.shape)))
-        r = {'pd_coords': self._new(B, 2, K, dtype=torch.int32), 'losses': self._new(2)}
-        if want_prob:
-            r['pd_prob'] = self._new(B, hh, ww, K)
-        if use_sm:
-            r['sm_coords'] = self._new(B, 2, K, dtype=torch.int32)
-            if want_prob:
-                r['sm_prob'] = self._new(B, hh, ww, K)
-        fn, what = (self._lib.jcm_eval_forward_u8, 'jcm_eval_forward_u8') if u8 else (self._lib.jcm_eval_forward, 'jcm_eval_forward')
-        scratch = {}
-        if peaks and not want_prob:
-            scratch = {k + '_prob': self._new(B, hh, ww, K) for k in (('pd', 'sm') if use_sm else ('pd',))}
-        _lib.check(fn(self._h, self._p(x), self._p(y), B, H, W, int(bool(use_sm)),
-                      self._p(r.get('pd_prob', scratch.get('pd_prob'))), self._p(r.get('sm_prob', scratch.get('sm_prob'))), self._p(r['pd_coords']),
-                      self._p(r.get('sm_coords')), self._p(r['losses'])), what)
-        if peaks:
-            self._add_peaks(r, peaks, scratch)
-        if decode:
-            self._add_pose(r, scratch, y[..., K:])
-        return r
+        return self._tower_call('jcm_eval_forward', x, y, use_sm, want_prob, peaks, decode, y[..., K:], losses=True)
 
     def window_resize(self, src, windows, oh, ow):
         """Pad-or-crop `windows` [(src_index, y0, x0, h, w), ...] of src [N,H,W,C], each resized to
@@ -603,18 +580,7 @@ class Engine:
         (y0, x0, ch, cw, h, w): the content rectangle and the source size, what evaluation.fit_to_source takes).  out: a tensor to write into
         instead of a new one.  Sizes, pad and the reduction limit (32 per axis) are checked by the library."""
         ts, desc, off, dtype = self._fit_check(images, dtype)
-        OH, OW = int(out_hw[0]), int(out_hw[1])
-        B, C = len(ts), 3
-        out = self._fit_out(out, B, OH, OW, C, dtype)
-        src = self._fit_pack(ts, desc, off)
-        geom = np.empty((B, 6), np.int32)
-        g4 = np.empty((B, 4), np.int32)
-        self._on_stream(src, out)
-        _lib.check(self._lib.jcm_fit_images(self._h, self._p(src), off, desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B, C, OH, OW, int(pad),
-                                            int(dtype == torch.float32), self._p(out), g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), 'jcm_fit_images')
-        geom[:, :4] = g4
-        geom[:, 4:] = desc[:, 1:]
-        return out, geom
+        return self._fit_run('jcm_fit_images', ts, desc, off, desc, desc[:, 1:], out_hw, pad, dtype, out)
 
     def _fit_check(self, images, dtype):
         """The input checks fit_images and fit_windows share -> (the images as uint8 torch tensors, desc int64 [B,3] = (byte offset in the packed
@@ -647,23 +613,32 @@ class Engine:
             off += im.numel()
         return ts, desc, off, dtype
 
-    def _fit_out(self, out, B, OH, OW, C, dtype):
+    def _fit_run(self, entry, ts, desc, off, rows, sizes, out_hw, pad, dtype, out):
+        """What fit_images and fit_windows share once the descriptor array is built: the output frame (`out` checked, or a new one), the images
+        ts back to back in one device buffer of `off` bytes (desc[:, 0] their offsets), the library's `entry` on the int64 descriptor `rows`
+        [n, 3 or 7], and geom [n,6] = the content rectangles it returns + `sizes` [n,2]."""
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        n, C = rows.shape[0], 3
         if out is None:
-            return self._new(B, OH, OW, C, dtype=dtype)
-        self._chk(out, 4, 'out', dtype)
-        if tuple(out.shape) != (B, OH, OW, C):
-            raise ValueError('out must be [%d,%d,%d,%d], got %s' % (B, OH, OW, C, tuple(out.shape)))
-        return out
-
-    def _fit_pack(self, ts, desc, off):
-        """The images back to back in one device buffer of `off` bytes."""
+            out = self._new(n, OH, OW, C, dtype=dtype)
+        else:
+            self._chk(out, 4, 'out', dtype)
+            if tuple(out.shape) != (n, OH, OW, C):
+                raise ValueError('out must be [%d,%d,%d,%d], got %s' % (n, OH, OW, C, tuple(out.shape)))
         src = self._new(off, dtype=torch.uint8)
         if all(im.device.type == 'cpu' for im in ts):      # one packed host buffer, one copy
             src.copy_(torch.cat([im.reshape(-1) for im in ts]))
         else:
             for i, im in enumerate(ts):
                 src[int(desc[i, 0]):int(desc[i, 0]) + im.numel()].copy_(im.reshape(-1))
-        return src
+        geom = np.empty((n, 6), np.int32)
+        g4 = np.empty((n, 4), np.int32)
+        self._on_stream(src, out)
+        _lib.check(getattr(self._lib, entry)(self._h, self._p(src), off, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n, C, OH, OW, int(pad),
+                                             int(dtype == torch.float32), self._p(out), g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), entry)
+        geom[:, :4] = g4
+        geom[:, 4:] = sizes
+        return out, geom
 
     def fit_windows(self, images, windows, out_hw=(480, 720), pad=0, dtype=torch.uint8, out=None):
         """Rectangles of images of any size into the frame the tower reads (include/jcm.h: jcm_fit_windows): `images` as for
@@ -680,19 +655,8 @@ class Engine:
         wins = wins.astype(np.int64)
         if wins[:, 0].min() < 0 or wins[:, 0].max() >= len(ts):
             raise ValueError('windows name images %d..%d; there are %d' % (wins[:, 0].min(), wins[:, 0].max(), len(ts)))
-        OH, OW = int(out_hw[0]), int(out_hw[1])
-        NW, C = wins.shape[0], 3
-        out = self._fit_out(out, NW, OH, OW, C, dtype)
-        src = self._fit_pack(ts, desc, off)
         d7 = np.ascontiguousarray(np.concatenate([desc[wins[:, 0]], wins[:, 1:]], axis=1))
-        geom = np.empty((NW, 6), np.int32)
-        g4 = np.empty((NW, 4), np.int32)
-        self._on_stream(src, out)
-        _lib.check(self._lib.jcm_fit_windows(self._h, self._p(src), off, d7.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), NW, C, OH, OW, int(pad),
-                                             int(dtype == torch.float32), self._p(out), g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), 'jcm_fit_windows')
-        geom[:, :4] = g4
-        geom[:, 4:] = wins[:, 3:]
-        return out, geom
+        return self._fit_run('jcm_fit_windows', ts, desc, off, d7, wins[:, 3:], out_hw, pad, dtype, out)
 
     def mirror_pairs(self, x):
         """x [B,H,W,C] float32 or uint8 -> [2B,H,W,C] of the same type: out[2b] = x[b], out[2b+1] = x[b] mirrored left/right (out[2b+1,y,xx,c] =
@@ -754,11 +718,7 @@ class Engine:
         y_out = self._new(*y.shape) if y_out is None else self._chk(y_out, 4, 'y_out')
         if x_out.shape != x.shape or y_out.shape != y.shape:
             raise ValueError('x_out / y_out must have the shapes of x / y')
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:          # tensors made on torch's current stream: the engine's stream waits for them, and keeps them alive
-            self._stream.wait_stream(cur)
-            for t in (x, y, params, x_out, y_out):
-                t.record_stream(self._stream)
+        self._on_stream(x, y, params, x_out, y_out)      # tensors made on torch's current stream: the engine's stream waits for them, and keeps them alive
         _lib.check(self._lib.jcm_augment_train(self._h, self._p(x), self._p(y), self._p(params), B, H, W, hh, hw,
                                                self._p(x_out), self._p(y_out)), 'jcm_augment_train')
         return x_out, y_out

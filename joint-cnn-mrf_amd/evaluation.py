@@ -233,10 +233,7 @@ def eval_error(X_np, Y_np, engine, batch_size, use_sm=True, joints=(2,), det_rad
     K = engine.n_joints
     acc = torch.zeros(4, dtype=torch.float64, device=engine.device)
     for bx, by in get_next_batch(X_np, Y_np, batch_size):
-        bx = torch.as_tensor(bx)
-        # byte images (a uint8 DeviceDataset, --u8_images) go to the byte entry as they are; everything else is widened to fp32 as before
-        x = bx.to(device=engine.device, dtype=torch.uint8 if bx.dtype == torch.uint8 else torch.float32).contiguous()
-        y = torch.as_tensor(by, dtype=torch.float32, device=engine.device).contiguous()
+        x, y = _to_device_batch(bx, by, engine)
         r = engine.eval_forward(x, y, use_sm=use_sm, want_prob=False)
         true = engine.argmax_coords(y[..., :K].contiguous())
         dr_pd = det_rate_from_coords(r['pd_coords'], true, det_radius, 'all' if joints == 'all' else list(joints))

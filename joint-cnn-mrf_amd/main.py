@@ -18,14 +18,15 @@ checkpoints; `--restore --restore_path P` resumes from one.  Data: the .npy file
 import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-from . import synth
+from . import eval_run, multiscale, synth
 from .engine import Engine
+from .eval_run import (_synthetic_dataset, byte_grid, det_curves_of_predictions, evaluated_indices, get_dataset, get_pairwise_distr,  # noqa: F401
+                       initial_params, load_data, model_name, run_params)
 
 # main.py:18-26
 joint_names = np.array(['lsho', 'lelb', 'lwri', 'rsho', 'relb', 'rwri', 'lhip', 'rhip', 'nose', 'torso'])
@@ -234,97 +235,32 @@ def tower(x, hm_target, use_sm=None):
 
 def get_different_scales(x, pad_array, crop_array, orig_h, orig_w):
     """main.py:326-348: the 4 padded + 4 cropped copies of an image, resized back to orig_h x orig_w."""
-    from . import multiscale
     return multiscale.get_different_scales(engine(), x, pad_array, crop_array, orig_h, orig_w)
 
 
 def scale_hm_back(hms, pad_array, crop_array, orig_h, orig_w):
     """main.py:351-379: undo the pad / crop on the 8 heat maps of an image."""
-    from . import multiscale
     return multiscale.scale_hm_back(engine(), hms, pad_array, crop_array, orig_h, orig_w)
 
 
 def get_predictions(X_np, Y_np, sess=None):
     """main.py:382-425 (multi-scale test-time evaluation) -> (pred_coords_pd, pred_coords_sm), each
     [2, n_joints, N]; `sess` is accepted for signature compatibility and ignored."""
-    from . import multiscale
     return multiscale.get_predictions(engine(), X_np, Y_np, use_sm=hps.use_sm, flip_test=bool(getattr(hps, 'flip_test', False)))
 
 
-# ------------------------------------------------------------------ data set, session files (main.py:286-299,604-612,666)
-DATASET_FILES = ('x_train_flic.npy', 'y_train_flic.npy', 'x_test_flic.npy', 'y_test_flic.npy')     # main.py:290-293, written by data.py
 model_path = 'models_ex'                                                                            # main.py:444
 
 
-def get_dataset(data_dir='.'):
-    """main.py:286-294: the four arrays data.py prepares (x [N,480,720,3] fp32 in [0,1], y [N,60,90,10])."""
-    missing = [f for f in DATASET_FILES if not os.path.exists(os.path.join(data_dir, f))]
-    if missing:
-        raise FileNotFoundError('%s not found in %r: run `python -m joint_cnn_mrf_amd.data` on the FLIC frames first (the reference\'s '
-                                'data.py step), or pass --synthetic for generated data' % (', '.join(missing), data_dir))
-    return tuple(np.load(os.path.join(data_dir, f), mmap_mode='r') for f in DATASET_FILES)
-
-
-def get_pairwise_distr(data_dir='.'):
-    """main.py:297-299: the pickle prepare_pairwise_distribution.py writes ({'<j>_<c>': [120,180] float64})."""
-    import pickle
-    with open(os.path.join(data_dir, 'pairwise_distribution.pickle'), 'rb') as handle:
-        return pickle.load(handle)
-
-
-def _synthetic_dataset(n_train, n_test):
-    return (synth.make_images(n_train, seed=100), synth.make_targets(n_train, seed=200),
-            synth.make_images(n_test, seed=300), synth.make_targets(n_test, seed=400))
-
-
-def byte_grid(x):
-    """--synthetic --u8_images: generated float images put on the byte grid, byte k = floor(x * 256) (255 at x = 1) standing for k / 255."""
-    return np.minimum(np.floor(np.asarray(x, np.float32) * np.float32(256)), np.float32(255)).astype(np.uint8)
-
-
+# ------------------------------------------------------------------ what main() refuses, and why (FLAG_RULES, above main(), has the order)
+RESTORE_NEEDS_RESTORE_PATH = '--restore needs --restore_path <checkpoint prefix or .npz> (the reference hard-codes best_model_name, main.py:443)'
 DET_CURVE_IS_EVALUATION_ONLY = ('--det_curve belongs to the evaluation run (it measures the predictions of the test set that run assembles); '
                                 'it cannot be combined with --train')
-DET_CURVE_CHUNK = 256      # images per upload of det_curves_of_predictions
-
-
-def evaluated_indices(n_images, batch_size, n_towers, multiscale=False):
-    """Which test image each column of the assembled predictions belongs to.  The multi-scale run evaluates every image in order.  The single-scale
-    run walks whole batches only (the remainder n_images % batch_size is dropped) and gives tower i the slice [i * per, i * per + per) of every batch,
-    per = batch_size // n_towers (dist.shard_bounds, main.py:511,516): the remainder batch_size % n_towers of EVERY batch is dropped too, so with
-    --batch_size 14 on four towers column 12 is image 14, not image 12."""
-    if multiscale:
-        return np.arange(n_images, dtype=np.int64)
-    per = batch_size // n_towers
-    first = np.arange(0, (n_images // batch_size) * batch_size, batch_size, dtype=np.int64)
-    return (first[:, None] + np.arange(n_towers * per, dtype=np.int64)[None, :]).reshape(-1)
-
-
-def det_curves_of_predictions(eng, pred_pd, pred_sm, y, radii=range(1, 21), index=None):
-    """Detection-rate curves of assembled predictions: pred_* int [2,K,N] (row, col) as get_predictions returns them, y [.,60,90,>= K] targets;
-    column i is judged against y[index[i]] (index None: y[i]; evaluated_indices gives the index of an evaluation run).  Uploaded in chunks of
-    DET_CURVE_CHUNK images, counted on `eng`'s device, read back once.  Returns (DetCurve of the part detector, DetCurve of the spatial model)."""
-    from .evaluation import DetCurve
-    K, N = int(pred_pd.shape[1]), int(pred_pd.shape[2])
-    index = np.arange(N, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64)
-    if index.shape != (N,) or (N and (index.min() < 0 or index.max() >= len(y))):
-        raise ValueError('%d predictions need %d target indices inside [0, %d); got %s' % (N, N, len(y), index.shape))
-    curves = DetCurve(eng, radii, n_joints=K), DetCurve(eng, radii, n_joints=K)
-    for lo in range(0, N, DET_CURVE_CHUNK):
-        hi = min(N, lo + DET_CURVE_CHUNK)
-        yb = torch.as_tensor(np.ascontiguousarray(y[index[lo:hi]], dtype=np.float32), device=eng.device)
-        for curve, pred in zip(curves, (pred_pd, pred_sm)):
-            coords = np.ascontiguousarray(np.asarray(pred)[:, :, lo:hi].transpose(2, 0, 1), dtype=np.int32)      # [n,2,K]
-            curve.update(torch.as_tensor(coords, device=eng.device), yb)
-    return curves
-
-
 PEAKS_IS_EVALUATION_ONLY = ('--peaks belongs to the evaluation run (it describes the heat maps of the test set that run predicts from); '
                             'it cannot be combined with --train')
 PEAKS_NEEDS_PREDICTIONS = '--peaks writes flic_peaks_pd / flic_peaks_sm into the file of --predictions: give --predictions PATH as well'
 PEAKS_NOT_WITH_U8_IMAGES = ('--peaks cannot be combined with --u8_images: the streamed byte feed (stream.ForwardStream) returns coordinates only; '
                             'run it on the float feed')
-
-
 DECODE_POSE_IS_EVALUATION_ONLY = ('--decode_pose belongs to the evaluation run (it chooses among the peaks of the test set that run predicts from); '
                                   'it cannot be combined with --train')
 DECODE_POSE_NEEDS_USE_SM = '--decode_pose scores poses with the spatial model: give --use_sm as well'
@@ -334,23 +270,6 @@ DECODE_POSE_NOT_WITH_U8_IMAGES = ('--decode_pose cannot be combined with --u8_im
                                   'run it on the float feed')
 DECODE_POSE_NOT_WITH_MULTISCALE = ('--decode_pose cannot be combined with --multiscale: the multi-scale average has no per-scale candidates; '
                                    'run it on the single-scale path')
-
-
-def pose_det_rate(eng, pred_pose, y, index, joints=(2,), det_radius=10):
-    """The reference's test_dr figure (evaluation.py:26-37: left wrist, radius 10) of decoded poses: pred_pose int [2,K,N] (row, col), column i judged
-    against y[index[i]], through evaluation.det_rate_from_coords in chunks of DET_CURVE_CHUNK images on `eng`'s device.  An image without a pose
-    (coordinates -1) is a miss wherever -1 is far from the target."""
-    from .evaluation import det_rate_from_coords
-    K, N = int(pred_pose.shape[1]), int(pred_pose.shape[2])
-    acc = 0.0
-    for lo in range(0, N, DET_CURVE_CHUNK):
-        hi = min(N, lo + DET_CURVE_CHUNK)
-        yb = torch.as_tensor(np.ascontiguousarray(y[index[lo:hi]][..., :K], dtype=np.float32), device=eng.device)
-        coords = torch.as_tensor(np.ascontiguousarray(np.asarray(pred_pose)[:, :, lo:hi].transpose(2, 0, 1), dtype=np.int32), device=eng.device)
-        acc += float(det_rate_from_coords(coords, eng.argmax_coords(yb), det_radius, list(joints))) * (hi - lo)
-    return acc / N
-
-
 INFER_TORSO_IS_EVALUATION_ONLY = ('--infer_torso belongs to the evaluation run (training with an inferred torso map is not defined: the step reads the '
                                   'annotated channel); drop --train')
 INFER_TORSO_NEEDS_USE_SM = '--infer_torso infers the torso map the spatial model reads: give --use_sm as well'
@@ -359,8 +278,6 @@ INFER_TORSO_SINGLE_SCALE_ONLY = ('--infer_torso cannot be combined with --multis
 PEOPLE_NEEDS_INFER_TORSO = '--people M (1 <= M <= 4) asks for one result per INFERRED torso candidate: give --infer_torso as well'
 FLIP_TEST_IS_EVALUATION_ONLY = ('--flip_test belongs to the evaluation run (it averages the heat maps of a test image and of its mirror image); '
                                 'it cannot be combined with --train')
-
-
 PREDICT_NEEDS_PREDICTIONS = '--predict writes its JSON document to the file of --predictions: give --predictions OUT.json as well'
 PREDICT_NOT_WITH_TRAIN = '--predict runs the tower on the named images and is no training run: drop --train'
 PREDICT_NOT_WITH_MULTISCALE = ('--predict cannot be combined with --multiscale: with --use_sm the torso is inferred, and the inferred torso under multi-scale '
@@ -372,20 +289,21 @@ PREDICT_NOT_WITH_DEVICE_DATA = '--predict cannot be combined with --device_data:
 ZOOM_NEEDS_PREDICT = '--zoom is the second pass of --predict (a window around every person the first pass found): give --predict PATH as well'
 ZOOM_NEEDS_USE_SM = ('--zoom needs --use_sm: the windows are placed at the inferred torso and sized by the shoulders and hips of the spatial model, '
                      'and the second pass runs the spatial model at the torso cell it is given')
+U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
+                              'host-fed training steps take float batches')
+TB_ACTIVATIONS_NEEDS_TB_DIR = '--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
+TB_ACTIVATIONS_IS_FP32 = ('--tb_activations: the pre-activation summaries are taken in fp32, as the reference takes them, and the bf16 kernels have no '
+                          'linear epilogue; run it with --precision fp32')
 
 
 def predict_main(args):
     """--predict PATH [PATH ...]: the named images through predict.predict_images on the first listed device; the JSON document goes to
     --predictions, one JSON line with the image count and the device times of the fit and of the forwards to stdout."""
-    from . import checkpoint, predict
+    from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
-    if args.restore:
-        state = restore_params(args.restore_path, args)
-        params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)}
-    else:
-        pairwise = synth.synthetic_priors() if args.synthetic else (get_pairwise_distr(args.data_dir) if args.use_sm else None)
-        params = initial_params(args, pairwise)
+    pairwise = None if args.restore else synth.synthetic_priors() if args.synthetic else get_pairwise_distr(args.data_dir) if args.use_sm else None
+    params, _ = run_params(args, pairwise)
     hps.debug = bool(args.debug)
     eng = Engine(device=args.gpus[0], precision=args.precision, n_joints=n_joints).load_params(params)
     try:
@@ -402,32 +320,6 @@ def predict_main(args):
     if args.zoom:
         line.update(zoom=True, zoom_fit_ms=timing['zoom_fit_ms'], zoom_forward_ms=timing['zoom_forward_ms'])
     print(json.dumps(line))
-
-
-U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
-                              'host-fed training steps take float batches')
-
-
-def initial_params(args, pairwise_distr):
-    """tf.global_variables_initializer on the graph of main.py:474-487: He-initialised convolutions, identity BatchNorm,
-    energies = the pairwise distributions, biases = 1e-5."""
-    params = synth.make_pd_params(debug=args.debug)
-    if args.use_sm:
-        params.update(synth.make_sm_params(pairwise_distr, kind='init'))
-    return params
-
-
-def restore_params(path, args):
-    """saver.restore (main.py:612): `path` is a tf.train.Saver checkpoint prefix (P.index + P.data-00000-of-00001, read by
-    tf_checkpoint.py) or an .npz keyed by the same variable names.  Returns every saved variable, optimizer slots included."""
-    from . import checkpoint, tf_checkpoint
-    if path.endswith('.npz'):
-        with np.load(path) as z:
-            state = {k: z[k] for k in z.files}
-    else:
-        state = tf_checkpoint.load_checkpoint(path)
-    checkpoint.validate({k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)}, args.debug, args.use_sm)
-    return state
 
 
 class TowerTrainer:
@@ -529,11 +421,6 @@ def tb_open(args, model_name):
     return w
 
 
-TB_ACTIVATIONS_NEEDS_TB_DIR = '--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
-TB_ACTIVATIONS_IS_FP32 = ('--tb_activations: the pre-activation summaries are taken in fp32, as the reference takes them, and the bf16 kernels have no '
-                          'linear epilogue; run it with --precision fp32')
-
-
 def tb_summaries(writers, eng, layout, batches, use_sm, step, grads=None, params_flat=None, activations=False, n_towers=1):
     """run_summary of the merged summary for the train and the test batch (main.py:621-626,650-653); activations: with the per-layer
     activation summaries (--tb_activations), the batch cut into n_towers tower slices."""
@@ -556,14 +443,9 @@ def train_main(args):
         raise NotImplementedError('--data_augm: the augmentation pipeline (augmentation.py: flips, rotations, crops on the TF input '
                                   'queue) is outside the hot path this build covers; train without it')
     t_start = time.time()
-    if args.synthetic:
-        x_train, y_train, x_test, y_test = _synthetic_dataset(args.synthetic_size, max(args.batch_size, args.synthetic_size // 2))
-        if args.u8_images:
-            x_train, x_test = byte_grid(x_train), byte_grid(x_test)
-        pairwise = synth.synthetic_priors()
-    else:
-        x_train, y_train, x_test, y_test = get_dataset(args.data_dir)
-        pairwise = get_pairwise_distr(args.data_dir)
+    x_train, y_train, x_test, y_test, pairwise = load_data(args)
+    if args.synthetic and args.u8_images:
+        x_train, x_test = byte_grid(x_train), byte_grid(x_test)
     n_train, n_test = x_train.shape[0], x_test.shape[0]
     rng = np.random.RandomState(args.seed)
     n_eval_ex = 512 if args.debug else 1100                              # main.py:453
@@ -572,17 +454,16 @@ def train_main(args):
         tr_idx, te_idx = np.sort(rng.permutation(x_train.shape[0])[:n_train]), np.sort(rng.permutation(x_test.shape[0])[:n_test])
         x_train, y_train, x_test, y_test = x_train[tr_idx], y_train[tr_idx], x_test[te_idx], y_test[te_idx]
     n_updates_total = args.n_epochs * n_train // args.batch_size        # main.py:466
-    state = restore_params(args.restore_path, args) if args.restore else None
-    params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)} if state else initial_params(args, pairwise)
+    params, state = run_params(args, pairwise)
     towers = Towers(params, args.gpus, precision=args.precision)
     tt = TowerTrainer(towers, params, optimizer=args.optimizer, lr=args.lr, lmbd=args.lmbd, use_sm=args.use_sm, n_updates_total=n_updates_total)
     if state:
         for tr in tt.trainers:
             checkpoint.restore_session_state(tr, state)
     eng = towers.engines[0]
-    model_name = '{}_lr={}_lambda={}_bs={}'.format(time.strftime('%Y-%m-%d %H:%M:%S'), args.lr, args.lmbd, args.batch_size)     # main.py:447
+    run_name = model_name(args)
     joints_to_eval, det_radius = [2], 10                                 # main.py:455-456
-    tb = tb_open(args, model_name) if args.tb_dir else None
+    tb = tb_open(args, run_name) if args.tb_dir else None
     tb_batches = {'train': tb_batch(x_train, y_train, args.batch_size), 'test': tb_batch(x_test, y_test, args.batch_size)} if tb else None
 
     ds_train = ds_test = None
@@ -632,237 +513,63 @@ def train_main(args):
                                                                              grads=tr0.grads, images=False), global_iter)
         report(epoch)
         if epoch > args.n_epochs // 2:                                   # main.py:663-666
-            tf_checkpoint.save_checkpoint('{}/{}-{}'.format(args.model_path, model_name, epoch), checkpoint.session_state(tt.trainers[0], params))
+            tf_checkpoint.save_checkpoint('{}/{}-{}'.format(args.model_path, run_name, epoch), checkpoint.session_state(tt.trainers[0], params))
     for w in (tb or {}).values():
         w.close()
     print('Done in {:.2f} min\n\n'.format((time.time() - t_start) / 60))
     return tt
 
 
+# What main() refuses: (holds for these flags, message or function of the flags giving it), in the order of precedence -- the first rule
+# that holds ends the run with its message, so a rule may rely on every rule above it having passed.
+FLAG_RULES = (
+    (lambda a: a.restore and not a.restore_path, RESTORE_NEEDS_RESTORE_PATH),
+    (lambda a: a.predict and a.train, PREDICT_NOT_WITH_TRAIN),
+    (lambda a: a.predict and a.multiscale, PREDICT_NOT_WITH_MULTISCALE),
+    (lambda a: a.predict and a.flip_test, PREDICT_NOT_WITH_FLIP_TEST),
+    (lambda a: a.predict and a.det_curve, PREDICT_NOT_WITH_DET_CURVE),
+    (lambda a: a.predict and a.device_data, PREDICT_NOT_WITH_DEVICE_DATA),
+    (lambda a: a.predict and not a.predictions, PREDICT_NEEDS_PREDICTIONS),
+    (lambda a: a.zoom and not a.predict, ZOOM_NEEDS_PREDICT),
+    (lambda a: a.zoom and not a.use_sm, ZOOM_NEEDS_USE_SM),
+    (lambda a: a.train and a.det_curve, DET_CURVE_IS_EVALUATION_ONLY),
+    (lambda a: a.train and a.flip_test, FLIP_TEST_IS_EVALUATION_ONLY),
+    (lambda a: a.train and a.u8_images and not a.device_data, U8_TRAIN_NEEDS_DEVICE_DATA),
+    (lambda a: a.infer_torso and a.train, INFER_TORSO_IS_EVALUATION_ONLY),
+    (lambda a: a.infer_torso and not a.use_sm, INFER_TORSO_NEEDS_USE_SM),
+    (lambda a: a.infer_torso and (a.multiscale or a.flip_test or a.u8_images), INFER_TORSO_SINGLE_SCALE_ONLY),
+    (lambda a: a.people != 1 and not ((a.infer_torso or (a.predict and a.use_sm)) and 1 <= a.people <= 4), PEOPLE_NEEDS_INFER_TORSO),
+    (lambda a: a.decode_pose and a.train, DECODE_POSE_IS_EVALUATION_ONLY),
+    (lambda a: a.decode_pose and not a.use_sm, DECODE_POSE_NEEDS_USE_SM),
+    (lambda a: a.decode_pose and not a.predictions, DECODE_POSE_NEEDS_PREDICTIONS),
+    (lambda a: a.decode_pose and not 1 <= a.peaks <= 4, DECODE_POSE_NEEDS_PEAKS),
+    (lambda a: a.decode_pose and a.u8_images, DECODE_POSE_NOT_WITH_U8_IMAGES),
+    (lambda a: a.decode_pose and a.multiscale, DECODE_POSE_NOT_WITH_MULTISCALE),
+    (lambda a: a.peaks and a.train, PEAKS_IS_EVALUATION_ONLY),
+    (lambda a: a.peaks and not a.predictions, PEAKS_NEEDS_PREDICTIONS),
+    (lambda a: a.peaks and a.u8_images, PEAKS_NOT_WITH_U8_IMAGES),
+    (lambda a: a.peaks and not 1 <= a.peaks <= 8, lambda a: '--peaks %d: 1 <= P <= 8' % a.peaks),
+    (lambda a: a.tb_activations and not a.tb_dir, TB_ACTIVATIONS_NEEDS_TB_DIR),
+    (lambda a: a.tb_activations and a.precision != 'fp32', TB_ACTIVATIONS_IS_FP32),
+)
+
+
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    if args.restore and not args.restore_path:
-        raise SystemExit('--restore needs --restore_path <checkpoint prefix or .npz> (the reference hard-codes best_model_name, main.py:443)')
-    if args.predict:
-        for given, message in ((args.train, PREDICT_NOT_WITH_TRAIN), (args.multiscale, PREDICT_NOT_WITH_MULTISCALE), (args.flip_test, PREDICT_NOT_WITH_FLIP_TEST),
-                               (args.det_curve, PREDICT_NOT_WITH_DET_CURVE), (args.device_data, PREDICT_NOT_WITH_DEVICE_DATA),
-                               (not args.predictions, PREDICT_NEEDS_PREDICTIONS)):
-            if given:
-                raise SystemExit(message)
-    if args.zoom:
-        if not args.predict:
-            raise SystemExit(ZOOM_NEEDS_PREDICT)
-        if not args.use_sm:
-            raise SystemExit(ZOOM_NEEDS_USE_SM)
-    if args.train and args.det_curve:
-        raise SystemExit(DET_CURVE_IS_EVALUATION_ONLY)
-    if args.train and args.flip_test:
-        raise SystemExit(FLIP_TEST_IS_EVALUATION_ONLY)
-    if args.train and args.u8_images and not args.device_data:
-        raise SystemExit(U8_TRAIN_NEEDS_DEVICE_DATA)
-    if args.infer_torso:
-        if args.train:
-            raise SystemExit(INFER_TORSO_IS_EVALUATION_ONLY)
-        if not args.use_sm:
-            raise SystemExit(INFER_TORSO_NEEDS_USE_SM)
-        if args.multiscale or args.flip_test or args.u8_images:
-            raise SystemExit(INFER_TORSO_SINGLE_SCALE_ONLY)
-    if args.people != 1 and not ((args.infer_torso or (args.predict and args.use_sm)) and 1 <= args.people <= 4):
-        raise SystemExit(PEOPLE_NEEDS_INFER_TORSO)
-    if args.decode_pose:
-        if args.train:
-            raise SystemExit(DECODE_POSE_IS_EVALUATION_ONLY)
-        if not args.use_sm:
-            raise SystemExit(DECODE_POSE_NEEDS_USE_SM)
-        if not args.predictions:
-            raise SystemExit(DECODE_POSE_NEEDS_PREDICTIONS)
-        if not 1 <= args.peaks <= 4:
-            raise SystemExit(DECODE_POSE_NEEDS_PEAKS)
-        if args.u8_images:
-            raise SystemExit(DECODE_POSE_NOT_WITH_U8_IMAGES)
-        if args.multiscale:
-            raise SystemExit(DECODE_POSE_NOT_WITH_MULTISCALE)
-    if args.peaks:
-        if args.train:
-            raise SystemExit(PEAKS_IS_EVALUATION_ONLY)
-        if not args.predictions:
-            raise SystemExit(PEAKS_NEEDS_PREDICTIONS)
-        if args.u8_images:
-            raise SystemExit(PEAKS_NOT_WITH_U8_IMAGES)
-        if not 1 <= args.peaks <= 8:
-            raise SystemExit('--peaks %d: 1 <= P <= 8' % args.peaks)
-    if args.tb_activations and not args.tb_dir:
-        raise SystemExit(TB_ACTIVATIONS_NEEDS_TB_DIR)
-    if args.tb_activations and args.precision != 'fp32':
-        raise SystemExit(TB_ACTIVATIONS_IS_FP32)
-    for g in args.gpus:
+    for holds, message in FLAG_RULES:
+        if holds(args):
+            raise SystemExit(message(args) if callable(message) else message)
+    for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too
         if g < 0 or g >= torch.cuda.device_count():
             raise SystemExit('--gpus %s: device %d does not exist (%d visible)' % (args.gpus, g, torch.cuda.device_count()))
     if args.predict:
         predict_main(args)
-        return
-    if args.train:
+    elif args.train:
         train_main(args)
-        return
-    # evaluation run (main.py:668-675): multi-scale predictions of the test set -> matlab/predictions.mat
-    from . import checkpoint
-    from .dist import Towers
-    if args.synthetic:
-        x_train, y_train, x_test, y_test = _synthetic_dataset(args.batch_size, args.synthetic_size)
-        if args.u8_images and not args.multiscale:
-            x_test = byte_grid(x_test)
-        pairwise = synth.synthetic_priors()
     else:
-        x_train, y_train, x_test, y_test = get_dataset(args.data_dir)
-        pairwise = get_pairwise_distr(args.data_dir)
-    fed = None              # --u8_images: what the single-scale run moved to the devices
-    pose = None             # --decode_pose: the dict of Engine.pose_decode over the evaluated images
-    peaks_pd = peaks_sm = None      # --peaks: the dicts of Engine.hm_peaks over the evaluated images, in the order of pred_pd / pred_sm
-    state = restore_params(args.restore_path, args) if args.restore else None
-    params = {k: v for k, v in state.items() if k in checkpoint.expected_shapes(args.debug, args.use_sm)} if state else initial_params(args, pairwise)
-
-    def eval_tb(eng):      # main.py:668-673: the step-0 summaries, without the gradient parts
-        if not args.tb_dir:
-            return
-        from . import summary
-        model_name = '{}_lr={}_lambda={}_bs={}'.format(time.strftime('%Y-%m-%d %H:%M:%S'), args.lr, args.lmbd, args.batch_size)
-        tb = tb_open(args, model_name)
-        flat, layout = summary.flat_params(eng, params)
-        tb_summaries(tb, eng, layout, {'train': tb_batch(x_train, y_train, args.batch_size), 'test': tb_batch(x_test, y_test, args.batch_size)},
-                     args.use_sm, 0, params_flat=flat, activations=args.tb_activations, n_towers=len(args.gpus))
-        for w in tb.values():
-            w.close()
-    # one set of engines only (each fp32 engine caches multi-GB filter spectra): the module engine for the multi-scale wrapper, which runs
-    # on one device, or one tower per listed device for the single-scale run
-    towers = None
-    t0 = time.time()
-    if args.multiscale:
-        if args.u8_images:
-            print('--u8_images: the multi-scale wrapper resizes float windows and is unchanged; the images stay float32', file=sys.stderr)
-        if len(args.gpus) > 1:
-            print('--multiscale evaluates on device %d only; the other --gpus entries are not used' % args.gpus[0], file=sys.stderr)
-        configure(params, device=args.gpus[0], precision=args.precision, debug=args.debug)
-        eval_tb(engine())
-        if args.peaks:
-            from . import multiscale
-            pred_pd, pred_sm, peaks_pd, peaks_sm = multiscale.get_predictions(engine(), np.asarray(x_test), np.asarray(y_test), use_sm=hps.use_sm, peaks=args.peaks,
-                                                                              flip_test=args.flip_test)
-        else:
-            pred_pd, pred_sm = get_predictions(np.asarray(x_test), np.asarray(y_test))                 # main.py:674
-    else:                                                                                              # single scale, sharded over the towers
-        hps.debug = bool(args.debug)
-        towers = Towers(params, args.gpus, precision=args.precision)
-        eval_tb(towers.engines[0])
-        B = args.batch_size
-        pd, sm = [], []
-        pk_pd, pk_sm, poses = [], [], []
-        torso_cells, people = [], []      # --infer_torso / --people
-        if args.u8_images and args.flip_test:      # byte batches through the towers' byte forward (the streamed feed has no mirrored evaluation)
-            from .dataset import to_u8_exact
-            xb = to_u8_exact(x_test)
-            n_moved = 0
-            for lo in range(0, (xb.shape[0] // B) * B, B):
-                bx, bt = np.ascontiguousarray(xb[lo:lo + B]), np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32)
-                r = towers.forward(bx, bt, use_sm=args.use_sm, flip_test=True)
-                pd.append(r['pd_coords'])
-                sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
-                for a, b in towers.slices(B):      # what the towers took of the batch
-                    n_moved += bx[a:b].nbytes + (bt[a:b].nbytes if args.use_sm else 0)
-            fed = {'image_dtype': 'uint8', 'bytes_uploaded': int(n_moved)}
-        elif args.u8_images:      # the test images as bytes (converted once, the round trip checked), streamed from pinned memory
-            from .dataset import to_u8_exact
-            from .stream import ForwardStream
-            xb = to_u8_exact(x_test)      # (works through a memory-mapped file in slices; float64 or other data is refused)
-            tb = np.ascontiguousarray(y_test[:, :, :, n_joints:], np.float32)
-            fss = [ForwardStream(e, use_sm=args.use_sm) for e in towers.engines]
-
-            def feed(lo, hi):      # one tower's slice of every whole batch (Towers.slices: the remainder B % n_gpus is dropped)
-                for b0 in range(0, (xb.shape[0] // B) * B, B):
-                    yield xb[b0 + lo:b0 + hi], tb[b0 + lo:b0 + hi]
-            for parts in zip(*[fs.run(feed(lo, hi)) for fs, (lo, hi) in zip(fss, towers.slices(B))]):
-                pd.append(torch.from_numpy(np.concatenate([p['pd_coords'] for p in parts])))
-                sm.append(torch.from_numpy(np.concatenate([p['sm_coords' if args.use_sm else 'pd_coords'] for p in parts])))
-            fed = {'image_dtype': 'uint8', 'bytes_uploaded': int(sum(fs.bytes_uploaded for fs in fss))}
-        else:
-            for lo in range(0, (x_test.shape[0] // B) * B, B):
-                r = towers.forward(np.ascontiguousarray(x_test[lo:lo + B], np.float32),
-                                   'infer' if args.infer_torso else np.ascontiguousarray(y_test[lo:lo + B, :, :, n_joints:], np.float32),
-                                   use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, flip_test=args.flip_test, people=args.people)
-                if args.infer_torso:
-                    torso_cells.append(r['torso_cell'])
-                    if args.people > 1:
-                        people.append(r['people'])
-                    if args.decode_pose and args.people > 1:      # the file holds one pose per image: slot 0, the arg-max torso
-                        r['pose'] = {f: v[:, 0].contiguous() for f, v in r['pose'].items()}
-                pd.append(r['pd_coords'])
-                sm.append(r['sm_coords'] if args.use_sm else r['pd_coords'])
-                if args.peaks:
-                    pk_pd.append(r['pd_peaks'])
-                    pk_sm.append(r['sm_peaks'] if args.use_sm else r['pd_peaks'])
-                if args.decode_pose:
-                    poses.append(r['pose'])
-        to_ref = lambda c: torch.cat(c).permute(1, 2, 0).cpu().numpy()      # [2,K,N] (row, col) stacked on the last axis, main.py:425
-        pred_pd, pred_sm = to_ref(pd), to_ref(sm)
-        if args.peaks:
-            collect = lambda parts: {f: torch.cat([p[f] for p in parts]) for f in parts[0]}
-            peaks_pd, peaks_sm = collect(pk_pd), collect(pk_sm)
-            if args.decode_pose:
-                pose = {f: v.cpu().numpy() for f, v in collect(poses).items()}
-    torch.cuda.synchronize()
-    dt = time.time() - t0
-    if args.predictions:
-        import scipy.io
-        os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
-        mat = {'flic_pred_pd': pred_pd, 'flic_pred_sm': pred_sm}                                       # main.py:675
-        if args.peaks:
-            from .evaluation import peaks_to_pixels
-            mat.update(flic_peaks_pd=peaks_to_pixels(peaks_pd), flic_peaks_sm=peaks_to_pixels(peaks_sm))
-        if pose is not None:
-            mat.update(flic_pred_pose=pose['coords'].transpose(1, 2, 0), flic_pose_score=np.stack([pose['score'], pose['score0']], axis=1))
-        if args.infer_torso:
-            mat.update(flic_torso_cell=torch.cat(torso_cells).cpu().numpy())                            # [N,2] (row, col)
-            if people:
-                mat.update(flic_people_sm=torch.cat([p['sm_coords'] for p in people]).cpu().numpy(),    # [N,M,2,K], -1 from flic_people_count on
-                           flic_people_count=torch.cat([p['count'] for p in people]).cpu().numpy())
-        scipy.io.savemat(args.predictions, mat)
-    if args.det_curve:      # one place for every feed: the curves of the assembled predictions, counted on the first listed device
-        index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus), multiscale=args.multiscale)      # towers drop batch_size % n_gpus of every batch
-        c_pd, c_sm = det_curves_of_predictions(engine() if towers is None else towers.engines[0], pred_pd, pred_sm, y_test, index=index)
-        names = [str(n) for n in joint_names[:pred_pd.shape[1]]]
-        d_pd, d_sm = c_pd.as_dict(names), c_sm.as_dict(names)
-        doc = {'radii': d_pd['radii'], 'joint_names': names, 'n_images': d_pd['n_images'], 'multiscale': bool(args.multiscale), 'use_sm': bool(args.use_sm),
-               'pd': {n: d_pd[n] for n in names}, 'sm': {n: d_sm[n] for n in names}}
-        os.makedirs(os.path.dirname(args.det_curve) or '.', exist_ok=True)
-        with open(args.det_curve, 'w') as fh:
-            json.dump(doc, fh)
-        print('test_dr: {} {}'.format(c_pd.rate(2, 10), c_sm.rate(2, 10)))      # main.py:424: left wrist, radius 10
-    if pose is not None:
-        index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus))
-        print('test_dr_pose: {}'.format(pose_det_rate(towers.engines[0], pose['coords'].transpose(1, 2, 0), y_test, index)))
-    line = {'n_images': int(pred_pd.shape[2]), 'gpus': args.gpus, 'use_sm': bool(args.use_sm), 'debug': bool(args.debug),
-            'multiscale': bool(args.multiscale), 'seconds': dt, 'images_per_sec': pred_pd.shape[2] / dt,
-            'coords_image0_pd': pred_pd[:, :, 0].tolist()}
-    if fed is not None:
-        line.update(fed)
-    if args.flip_test:
-        line['flip_test'] = True
-    if args.infer_torso:      # how far the inferred cell lies from the arg-max of the annotated torso channel (first occurrence), in cells
-        index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus))
-        ann = np.asarray(y_test)[index][:, :, :, n_joints].reshape(len(index), -1).argmax(axis=1)
-        got = torch.cat(torso_cells).cpu().numpy().astype(np.float64)
-        line['infer_torso'] = True
-        line['torso_cell_dist'] = float(np.sqrt((got[:, 0] - ann // 90) ** 2 + (got[:, 1] - ann % 90) ** 2).mean())
-        if args.people > 1:
-            line['people'] = int(args.people)
-    if args.peaks:
-        line['peaks'] = int(args.peaks)
-    if pose is not None:      # the share of images whose decoded pose is not the all-peak-0 pose (the independent arg-maxes)
-        line['pose_changed'] = float((pose['index'] != 0).any(axis=1).mean())
-    print(json.dumps(line))
-    if towers is not None:
-        towers.close()
+        eval_run.run(args)
 
 
 if __name__ == '__main__':

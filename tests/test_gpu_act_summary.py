@@ -4,7 +4,6 @@ float64 oracle, the whole chain against the fused forward, and the command line 
 import ctypes
 import io
 import os
-import subprocess
 import sys
 import zlib
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import _lib, synth
 from oracle import jcm_oracle as O
@@ -291,9 +291,8 @@ def test_whole_chain(debug_setup):
 
 
 # ------------------------------------------------------------------ the command line
-def _cli(args, cwd, ok=True, timeout=900):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=timeout)
+def _run(args, cwd, ok=True, timeout=900):
+    r = run_cli(args, cwd, timeout=timeout)
     assert (r.returncode == 0) == ok, r.stdout[-2000:] + r.stderr[-2000:]
     return r
 
@@ -326,7 +325,7 @@ def test_cli_train_writes_activation_summaries(tmp_path):
     common = ['--train', '--debug', '--use_sm', '--synthetic', '--synthetic_size', '8', '--batch_size', '4', '--gpus', '0', '0', '--n_epochs', '1',
               '--model_path', str(tmp_path / 'models_ex')]
     D = tmp_path / 'tb'
-    _cli(common + ['--tb_dir', str(D), '--tb_activations'], str(tmp_path))
+    _run(common + ['--tb_dir', str(D), '--tb_activations'], str(tmp_path))
     (run,) = os.listdir(str(D))
     for split in ('train', 'test'):
         ev = _events(str(D / run / split))
@@ -335,7 +334,7 @@ def test_cli_train_writes_activation_summaries(tmp_path):
             _check_activation_tags(ev[step])
             assert 'input/image/0' in ev[step] and 'grads/conv5/weights' in ev[step]      # behind the tags that were there before
     D2 = tmp_path / 'tb_plain'
-    _cli(common + ['--tb_dir', str(D2)], str(tmp_path))
+    _run(common + ['--tb_dir', str(D2)], str(tmp_path))
     (run,) = os.listdir(str(D2))
     for split in ('train', 'test'):
         for tags in _events(str(D2 / run / split)).values():
@@ -345,13 +344,13 @@ def test_cli_train_writes_activation_summaries(tmp_path):
 def test_cli_eval_and_refusals(tmp_path):
     D = tmp_path / 'tb'
     common = ['--debug', '--use_sm', '--synthetic', '--synthetic_size', '4', '--batch_size', '4', '--gpus', '0', '0']
-    _cli(common + ['--tb_dir', str(D), '--tb_activations'], str(tmp_path))
+    _run(common + ['--tb_dir', str(D), '--tb_activations'], str(tmp_path))
     (run,) = os.listdir(str(D))
     for split in ('train', 'test'):
         ev = _events(str(D / run / split))
         assert sorted(ev) == [0]
         _check_activation_tags(ev[0])
-    r = _cli(common + ['--tb_activations'], str(tmp_path), ok=False)
+    r = _run(common + ['--tb_activations'], str(tmp_path), ok=False)
     assert '--tb_dir' in r.stderr
-    r = _cli(common + ['--tb_dir', str(tmp_path / 'no'), '--tb_activations', '--precision', 'bf16'], str(tmp_path), ok=False)
+    r = _run(common + ['--tb_dir', str(tmp_path / 'no'), '--tb_activations', '--precision', 'bf16'], str(tmp_path), ok=False)
     assert 'fp32' in r.stderr and not os.path.exists(str(tmp_path / 'no'))

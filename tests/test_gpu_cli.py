@@ -3,13 +3,12 @@
 and the command line end to end (train on generated data, save a tf.train.Saver checkpoint, restore it, evaluate)."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import synth
 from oracle import jcm_oracle as O
@@ -134,9 +133,8 @@ def test_rccl_communicator_c_abi_one_rank():
     eng.close()
 
 
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=900)
+def _run_ok(args, cwd):
+    r = run_cli(args, cwd, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -147,7 +145,7 @@ def test_cli_train_save_restore_evaluate(tmp_path):
     evaluation run writes predictions.mat.  `--data_augm` and unknown devices are refused, not ignored."""
     from joint_cnn_mrf_amd import tf_checkpoint
     common = ['--debug', '--use_sm', '--synthetic', '--synthetic_size', '8', '--batch_size', '4', '--model_path', str(tmp_path / 'models_ex')]
-    out = _cli(['--train', '--gpus', '0', '0', '--n_epochs', '2'] + common, str(tmp_path))
+    out = _run_ok(['--train', '--gpus', '0', '0', '--n_epochs', '2'] + common, str(tmp_path))
     lines = [l for l in out.splitlines() if l.startswith('Epoch ')]
     assert [l.split()[1] for l in lines] == ['0', '1', '2'] and 'test_dr' in lines[0] and 'train_mse' in lines[0]
     ckpts = sorted(f for f in os.listdir(tmp_path / 'models_ex') if f.endswith('.index'))
@@ -155,15 +153,14 @@ def test_cli_train_save_restore_evaluate(tmp_path):
     prefix = str(tmp_path / 'models_ex' / ckpts[0][:-len('.index')])
     state = tf_checkpoint.load_checkpoint(prefix)
     assert int(state['n_iters']) == 2 * (8 // 4) and 'conv5/weights/Adam_1' in state and 'energy_lsho_lelb' in state
-    out2 = _cli(['--train', '--restore', '--restore_path', prefix, '--gpus', '0', '--n_epochs', '1'] + common, str(tmp_path))
+    out2 = _run_ok(['--train', '--restore', '--restore_path', prefix, '--gpus', '0', '--n_epochs', '1'] + common, str(tmp_path))
     assert len([l for l in out2.splitlines() if l.startswith('Epoch ')]) == 2
     pred = str(tmp_path / 'matlab' / 'predictions.mat')
-    out3 = _cli(['--restore', '--restore_path', prefix, '--gpus', '0', '0', '--predictions', pred] + common, str(tmp_path))
+    out3 = _run_ok(['--restore', '--restore_path', prefix, '--gpus', '0', '0', '--predictions', pred] + common, str(tmp_path))
     rec = json.loads(out3.strip().splitlines()[-1])
     import scipy.io
     m = scipy.io.loadmat(pred)
     assert m['flic_pred_pd'].shape == (2, 9, rec['n_images']) and m['flic_pred_sm'].shape == (2, 9, rec['n_images'])
-    env = dict(os.environ, PYTHONPATH=ROOT)
     for bad in (['--train', '--data_augm', '--gpus', '0'] + common, ['--gpus', '99'] + common):
-        r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + bad, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
+        r = run_cli(bad, str(tmp_path), timeout=300)
         assert r.returncode != 0

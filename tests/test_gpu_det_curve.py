@@ -4,14 +4,13 @@ exactly representable integers, so any difference is a kernel fault, not a toler
 eval_curves on a --debug engine, the error paths and the command line."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import det_curve_ref as R
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import evaluation, synth
 from joint_cnn_mrf_amd import main as M
@@ -238,9 +237,8 @@ def test_error_paths_launch_nothing(eng):
     assert int((hits != 7).sum()) == 0
 
 
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
+def _run_ok(args, cwd):
+    r = run_cli(args, cwd)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -253,7 +251,7 @@ def test_cli_writes_the_curves_of_its_predictions(tmp_path, multiscale):
     P, Mat = str(tmp_path / 'curves' / 'det.json'), str(tmp_path / 'pred.mat')
     n = 2 if multiscale else 5                                # 5 images in batches of 2: 4 are evaluated (whole batches)
     args = ['--synthetic', '--debug', '--use_sm', '--synthetic_size', str(n), '--batch_size', '2', '--det_curve', P, '--predictions', Mat]
-    out = _cli(args + (['--multiscale'] if multiscale else []), str(tmp_path))
+    out = _run_ok(args + (['--multiscale'] if multiscale else []), str(tmp_path))
     doc = json.load(open(P))
     m = scipy.io.loadmat(Mat)
     N = 2 if multiscale else 4

@@ -5,13 +5,12 @@ and with augmentation), and `--device_data` on the command line.  Everything com
 where two runs of the HOST-fed loop differ from each other (then twice their largest difference is allowed, and said)."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import _lib, evaluation, synth
 from joint_cnn_mrf_amd.dataset import DeviceDataset, DeviceDataTooLarge
@@ -223,9 +222,8 @@ def test_indexed_training_run_equals_the_host_fed_run(train_case, gpus, augment)
 
 
 # ------------------------------------------------------------------ command line
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=900)
+def _run_ok(args, cwd):
+    r = run_cli(args, cwd, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return [l for l in r.stdout.splitlines() if l.startswith('Epoch ')]
 
@@ -234,7 +232,7 @@ def test_cli_device_data_prints_the_epoch_lines_of_the_host_fed_run(tmp_path):
     common = ['--train', '--debug', '--use_sm', '--synthetic', '--synthetic_size', '8', '--batch_size', '4', '--n_epochs', '2']
     runs = {}
     for name, extra in (('host', []), ('host_again', []), ('device', ['--device_data'])):
-        runs[name] = _cli(common + extra + ['--model_path', str(tmp_path / name)], str(tmp_path))
+        runs[name] = _run_ok(common + extra + ['--model_path', str(tmp_path / name)], str(tmp_path))
         assert [l.split()[1] for l in runs[name]] == ['0', '1', '2'] and 'test_dr' in runs[name][0] and 'train_mse' in runs[name][0]
         ckpts = sorted(f for f in os.listdir(tmp_path / name) if f.endswith('.index'))
         assert len(ckpts) == 1 and ckpts[0].endswith('-2.index')

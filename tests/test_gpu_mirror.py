@@ -6,8 +6,6 @@ import ctypes
 import functools
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ import torch
 from numpy.testing import assert_array_equal
 
 import mirror_ref as R
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import multiscale as MS
 from joint_cnn_mrf_amd import synth
@@ -362,11 +361,6 @@ def test_get_predictions_flip_test(tower, per_forward):
 
 
 # ------------------------------------------------------------------ the command line
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    return subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
-
-
 CLI_CASES = {
     'single_scale': (['--batch_size', '2', '--synthetic_size', '4', '--peaks', '2', '--decode_pose'], 4),
     'multiscale': (['--multiscale', '--batch_size', '2', '--synthetic_size', '2', '--peaks', '2'], 2),
@@ -379,7 +373,7 @@ def test_cli_flip_test(tmp_path, case):
     import scipy.io
     extra, n = CLI_CASES[case]
     mat, curve = str(tmp_path / 'P.mat'), str(tmp_path / 'C.json')
-    r = _cli(['--debug', '--synthetic', '--use_sm', '--gpus', '0', '--flip_test', '--predictions', mat, '--det_curve', curve] + extra, str(tmp_path))
+    r = run_cli(['--debug', '--synthetic', '--use_sm', '--gpus', '0', '--flip_test', '--predictions', mat, '--det_curve', curve] + extra, str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['flip_test'] is True and line['n_images'] == n and line['multiscale'] == (case == 'multiscale')
@@ -396,5 +390,5 @@ def test_cli_flip_test(tmp_path, case):
 
 
 def test_cli_refuses_flip_test_with_train(tmp_path):
-    r = _cli(['--train', '--flip_test', '--debug', '--synthetic', '--gpus', '0'], str(tmp_path))
+    r = run_cli(['--train', '--flip_test', '--debug', '--synthetic', '--gpus', '0'], str(tmp_path))
     assert r.returncode != 0 and '--flip_test' in r.stderr

@@ -3,8 +3,6 @@ tests/test_peaks_cpu.py) with assert_array_equal on all four outputs -- the kern
 no tolerance -- then forward(peaks=), the multi-scale wrapper and the command line."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,6 +10,7 @@ import torch
 from numpy.testing import assert_array_equal
 
 import peaks_ref as R
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import multiscale, synth
 
@@ -273,9 +272,8 @@ def test_multiscale_with_peaks(tower):
     assert_array_equal(one[2]['cells'][:, :, 0].cpu().numpy().transpose(2, 1, 0), one[0])
 
 
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
+def _run_ok(args, cwd):
+    r = run_cli(args, cwd)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -284,7 +282,7 @@ def test_cli_writes_the_peaks_of_its_predictions(tmp_path):
     import scipy.io
     args = ['--debug', '--synthetic', '--use_sm', '--batch_size', '4', '--synthetic_size', '8', '--gpus', '0']
     with_pk, without = str(tmp_path / 'P.mat'), str(tmp_path / 'Q.mat')
-    out = _cli(args + ['--predictions', with_pk, '--peaks', '3'], str(tmp_path))
+    out = _run_ok(args + ['--predictions', with_pk, '--peaks', '3'], str(tmp_path))
     m = scipy.io.loadmat(with_pk)
     line = json.loads(out.strip().splitlines()[-1])
     assert line['peaks'] == 3 and line['n_images'] == 8
@@ -295,7 +293,7 @@ def test_cli_writes_the_peaks_of_its_predictions(tmp_path):
         assert (pk[:, :, 0, 2] > 0).all()
         filler = pk[..., 2] == 0
         assert (pk[filler][:, :2] == -1).all()
-    out = _cli(args + ['--predictions', without], str(tmp_path))
+    out = _run_ok(args + ['--predictions', without], str(tmp_path))
     q = scipy.io.loadmat(without)
     assert 'flic_peaks_pd' not in q and 'flic_peaks_sm' not in q
     assert 'peaks' not in json.loads(out.strip().splitlines()[-1])

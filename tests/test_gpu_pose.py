@@ -5,8 +5,6 @@ it, forward(decode=), the argument contract and the command line."""
 import ctypes
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import torch
 from numpy.testing import assert_array_equal
 
 import pose_ref as R
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import main as M
 from joint_cnn_mrf_amd import synth
@@ -288,16 +287,11 @@ def test_argument_contract(engines):
         fresh.close()
 
 
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    return subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
-
-
 def test_cli_decodes_the_poses_of_its_predictions(tmp_path):
     import scipy.io
     args = ['--debug', '--synthetic', '--use_sm', '--batch_size', '4', '--synthetic_size', '8', '--gpus', '0']
     mat = str(tmp_path / 'P.mat')
-    r = _cli(args + ['--predictions', mat, '--peaks', '3', '--decode_pose'], str(tmp_path))
+    r = run_cli(args + ['--predictions', mat, '--peaks', '3', '--decode_pose'], str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     m = scipy.io.loadmat(mat)
     lines = r.stdout.strip().splitlines()

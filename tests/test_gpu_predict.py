@@ -4,14 +4,13 @@ narrow parameters and generated priors of --synthetic --debug."""
 import argparse
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 from numpy.testing import assert_array_equal
 
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import evaluation as EV
 from joint_cnn_mrf_amd import predict as P
@@ -115,11 +114,6 @@ def test_without_spatial_model_and_with_people(world):
 
 
 # ------------------------------------------------------------------ the command line
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    return subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
-
-
 def test_cli_predict(world, tmp_path):
     """Three .npy files in a directory (expanded in sorted order) -> the JSON document holds predict_images' values; one JSON line on stdout."""
     eng, images, x, geom, r = world
@@ -129,7 +123,7 @@ def test_cli_predict(world, tmp_path):
         np.save(str(d / ('img%d.npy' % i)), im)
     (d / 'notes.txt').write_text('not an image')
     out = str(tmp_path / 'out' / 'pred.json')
-    res = _cli(['--synthetic', '--debug', '--use_sm', '--gpus', '0', '--batch_size', '2', '--peaks', '2', '--predict', str(d), '--predictions', out], str(tmp_path))
+    res = run_cli(['--synthetic', '--debug', '--use_sm', '--gpus', '0', '--batch_size', '2', '--peaks', '2', '--predict', str(d), '--predictions', out], str(tmp_path))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
     assert line['predict'] is True and line['n_images'] == 3 and line['fit_ms'] > 0 and line['forward_ms'] > 0
@@ -161,6 +155,6 @@ def test_cli_refusals(tmp_path):
         assert str(ei.value) == M.PREDICT_NEEDS_PREDICTIONS
     finally:
         M.hps = keep
-    res = _cli(base + ['--predictions', str(tmp_path / 'o.json'), '--flip_test'], str(tmp_path))      # and once through the real entry point
+    res = run_cli(base + ['--predictions', str(tmp_path / 'o.json'), '--flip_test'], str(tmp_path))      # and once through the real entry point
     assert res.returncode != 0 and '--flip_test' in res.stderr
     assert not (tmp_path / 'o.json').exists()

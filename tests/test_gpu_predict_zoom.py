@@ -4,14 +4,13 @@ Engine.fit_windows, Engine.torso_infer(cells=), Engine.forward, evaluation.windo
 people=2 gives an entry per counted slot, and the command line writes the entries."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 from numpy.testing import assert_array_equal
 
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import evaluation as EV
 from joint_cnn_mrf_amd import predict as P
@@ -171,9 +170,8 @@ def test_cli_predict_zoom(world, tmp_path):
     for i, im in enumerate(images):
         np.save(str(d / ('img%d.npy' % i)), im)
     out = str(tmp_path / 'pred.json')
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    res = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main', '--synthetic', '--debug', '--use_sm', '--gpus', '0', '--batch_size', '2', '--peaks', '2',
-                          '--predict', str(d), '--predictions', out, '--zoom'], cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+    res = run_cli(['--synthetic', '--debug', '--use_sm', '--gpus', '0', '--batch_size', '2', '--peaks', '2',
+                   '--predict', str(d), '--predictions', out, '--zoom'], str(tmp_path))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
     assert line['predict'] is True and line['zoom'] is True and line['zoom_fit_ms'] >= 0 and line['zoom_forward_ms'] >= 0

@@ -4,13 +4,13 @@ command line end to end through the independent event-file decoder."""
 import io
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import synth
 
@@ -161,9 +161,8 @@ def test_overlays_against_restatement():
     eng.close()
 
 
-def _cli(args, cwd, timeout=900):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=timeout)
+def _run_ok(args, cwd, timeout=900):
+    r = run_cli(args, cwd, timeout=timeout)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -190,7 +189,7 @@ def _sizes(use_sm=True):
 def test_cli_train_writes_summaries(tmp_path):
     from PIL import Image
     D = tmp_path / 'tb'
-    out = _cli(['--train', '--debug', '--use_sm', '--synthetic', '--synthetic_size', '8', '--batch_size', '4', '--gpus', '0', '0', '--n_epochs', '2',
+    out = _run_ok(['--train', '--debug', '--use_sm', '--synthetic', '--synthetic_size', '8', '--batch_size', '4', '--gpus', '0', '0', '--n_epochs', '2',
                 '--tb_dir', str(D), '--model_path', str(tmp_path / 'models_ex')], str(tmp_path))
     runs = os.listdir(str(D))
     assert len(runs) == 1 and sorted(os.listdir(str(D / runs[0]))) == ['test', 'train']
@@ -242,7 +241,7 @@ def test_cli_eval_summaries_and_default_off(tmp_path):
     """The evaluation run with --tb_dir writes the step-0 summaries without the gradient parts; without --tb_dir nothing is written."""
     common = ['--debug', '--use_sm', '--synthetic', '--synthetic_size', '4', '--batch_size', '2', '--gpus', '0']
     D = tmp_path / 'tb'
-    _cli(common + ['--tb_dir', str(D)], str(tmp_path))
+    _run_ok(common + ['--tb_dir', str(D)], str(tmp_path))
     run = os.listdir(str(D))[0]
     for split in ('train', 'test'):
         ev = _events(str(D / run / split))
@@ -252,7 +251,7 @@ def test_cli_eval_summaries_and_default_off(tmp_path):
         assert not any(t.endswith('/gradients') or t.endswith('/gradients_1') for t in tags)
     plain = tmp_path / 'plain'
     plain.mkdir()
-    _cli(common, str(plain))
+    _run_ok(common, str(plain))
     for dirpath, _, files in os.walk(str(plain)):
         assert not any(f.startswith('events.out.tfevents') for f in files), dirpath
     assert not os.path.exists(str(plain / 'tb'))

@@ -6,8 +6,6 @@ One route exists, "torso_algo" = 1 (direct); the frequency-domain route of the i
 import ctypes
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ import torch
 from numpy.testing import assert_array_equal
 
 import torso_ref as T
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import synth
 
@@ -309,15 +308,10 @@ def test_towers_infer(world):
 
 
 # ------------------------------------------------------------------ the command line
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    return subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
-
-
 def test_cli_infer_torso(tmp_path):
     import scipy.io
     mat = str(tmp_path / 'P.mat')
-    r = _cli(['--synthetic', '--debug', '--use_sm', '--infer_torso', '--people', '2', '--gpus', '0', '--batch_size', '2', '--synthetic_size', '4',
+    r = run_cli(['--synthetic', '--debug', '--use_sm', '--infer_torso', '--people', '2', '--gpus', '0', '--batch_size', '2', '--synthetic_size', '4',
               '--predictions', mat], str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -333,5 +327,5 @@ def test_cli_infer_torso(tmp_path):
 def test_cli_refusals(tmp_path):
     for extra, word in ((['--train', '--infer_torso', '--use_sm'], '--infer_torso'), (['--infer_torso', '--use_sm', '--multiscale'], '--multiscale'),
                         (['--use_sm', '--people', '2'], '--infer_torso')):
-        r = _cli(['--debug', '--synthetic', '--gpus', '0'] + extra, str(tmp_path))
+        r = run_cli(['--debug', '--synthetic', '--gpus', '0'] + extra, str(tmp_path))
         assert r.returncode != 0 and word in r.stderr, extra

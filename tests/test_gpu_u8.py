@@ -3,13 +3,12 @@ result on byte images must equal the result on that float image BIT FOR BIT: the
 references are always made on the host with numpy (`as_float`) and uploaded, never by a division on the device under test."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from cli_util import run_cli
 import joint_cnn_mrf_amd  # noqa: F401
 from joint_cnn_mrf_amd import synth
 from joint_cnn_mrf_amd import main as M
@@ -286,9 +285,8 @@ def test_forward_stream_equals_forward_per_batch_in_order(kind, use_sm):
 
 
 # ------------------------------------------------------------------ command line
-def _cli(args, cwd):
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, '-m', 'joint_cnn_mrf_amd.main'] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=900)
+def _run_ok(args, cwd):
+    r = run_cli(args, cwd, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout.splitlines()
 
@@ -298,7 +296,7 @@ def test_cli_evaluation_on_bytes_writes_the_predictions_of_a_direct_forward(tmp_
     from joint_cnn_mrf_amd.dist import Towers
     B, n = 4, 10
     mat = str(tmp_path / 'predictions.mat')
-    out = _cli(['--synthetic', '--debug', '--use_sm', '--u8_images', '--batch_size', str(B), '--synthetic_size', str(n), '--predictions', mat], str(tmp_path))
+    out = _run_ok(['--synthetic', '--debug', '--use_sm', '--u8_images', '--batch_size', str(B), '--synthetic_size', str(n), '--predictions', mat], str(tmp_path))
     line = json.loads([l for l in out if l.startswith('{')][-1])
     assert line['image_dtype'] == 'uint8' and line['n_images'] == 8
     assert line['bytes_uploaded'] == 8 * (480 * 720 * 3 + 60 * 90 * 4)
@@ -321,7 +319,7 @@ def test_cli_evaluation_on_bytes_writes_the_predictions_of_a_direct_forward(tmp_
 
 def test_cli_training_on_bytes_prints_finite_epoch_lines_and_saves_a_checkpoint(tmp_path):
     from joint_cnn_mrf_amd import tf_checkpoint
-    out = _cli(['--train', '--device_data', '--u8_images', '--synthetic', '--debug', '--use_sm', '--synthetic_size', '8', '--batch_size', '4',
+    out = _run_ok(['--train', '--device_data', '--u8_images', '--synthetic', '--debug', '--use_sm', '--synthetic_size', '8', '--batch_size', '4',
                 '--n_epochs', '2', '--model_path', str(tmp_path / 'm')], str(tmp_path))
     epochs = [l for l in out if l.startswith('Epoch ')]
     assert [l.split()[1] for l in epochs] == ['0', '1', '2']
