@@ -418,6 +418,38 @@ int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const in
 int jcm_fit_windows(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C,
                     int OH, int OW, int pad, int out_f32, void* out, int32_t* geom);
 
+/* -- poses drawn onto the source images ------------------------------------------------------
+ * The ragged byte batch of jcm_fit_images with C = 3 (src, src_bytes, desc HOST int64 [B][3] = (byte offset, h, w), any byte offsets) comes out
+ * in `out`, a device buffer of src_bytes bytes, image b at the same offset, with two layers drawn on it.  Bytes of out that belong to no image
+ * are not written.  out == src (in place) is allowed: a pixel depends on its own source pixel only; any other overlap is refused.
+ * Layer 1, the heat tint (hm == NULL: off).  hm: device float32 [B,hh,hw,K], K in 1..16, finite; geom: HOST int32 [B][4] = (y0, x0, ch, cw), the fit
+ * of image b into the (hh * stride) x (hw * stride) frame the maps belong to (what jcm_fit_images returns); heat_mask: HOST uint8 [K], bits 0, 1, 2
+ * of entry j say that joint j tints R, G, B; heat_gain in 0..255.  M(b, j) is the maximum of map j of image b; a joint with M <= 0 adds nothing.
+ * For source pixel (y, x) of an h x w image, in float64, evaluated as written:
+ *   fy = ((double)y + 0.5) * (double)ch / (double)h - 0.5 + (double)y0;   cy = min(max(fy / (double)stride, 0.0), (double)(hh - 1))
+ *   iy = (int)floor(cy),  iy1 = min(iy + 1, hh - 1),  ty = cy - iy;   the columns alike from x, cw, w, x0, hw
+ *   s = (1 - ty) * ((1 - tx) * v00 + tx * v01) + ty * ((1 - tx) * v10 + tx * v11),   v.. = hm[b][iy | iy1][ix | ix1][j]
+ *   q = min(255, max(0, floor(s * 255.0 / (double)M + 0.5))),   add = (q * heat_gain + 127) / 255 (integers)
+ * and for j ascending and every channel c of heat_mask[j]: v_c = min(255, v_c + add).
+ * Layer 2, capsules, on top of the tint.  prims: HOST int32 [NP][8] = (image, ay, ax, by, bx, r, rgb = 0xRRGGBB, alpha), sorted by image
+ * (non-decreasing), applied within an image in listing order.  Coordinates and r are in sixteenths of a pixel; integer pixel coordinates are
+ * pixel centres, so pixel (y, x) has its centre at (16 y, 16 x).  A disc is a capsule with a == b.  The coverage c of a pixel, 0..16, counts its
+ * sub-samples (offsets -6, -2, +2, +6 sixteenths on each axis) inside the capsule; sample (sy, sx), in float64 from the exact integers:
+ *   ey = sy - ay, ex = sx - ax, dy = by - ay, dx = bx - ax;   ee = ey*ey + ex*ex;  t = ey*dy + ex*dx;  L2 = dy*dy + dx*dx;  rr = (double)r * r
+ *   L2 == 0 or t <= 0:  inside iff ee <= rr;    t >= L2:  inside iff (sy-by)*(sy-by) + (sx-bx)*(sx-bx) <= rr;    else:  inside iff ee * L2 - t * t <= rr * L2
+ * and per channel, in integers, v = (v * (4080 - c * alpha) + colour * c * alpha + 2040) / 4080.  No square root, no division by a computed
+ * value: a restatement in the same order gives the same bytes.
+ * JCM_ERR_ARG -- nothing is launched, out is untouched -- for a null src, desc or out; B < 1; a side outside 1..16384; image bytes outside
+ * [0, src_bytes); out partly overlapping src; NP < 0, or NP > 0 with null prims; an image index outside 0..B-1 or out of order; more than 256
+ * primitives for one image; a coordinate outside +-2^20; r outside 0..2^16; alpha outside 0..255; rgb outside 0..0xFFFFFF; hm with a null geom or
+ * heat_mask, K outside 1..16, hh, hw or stride < 1, heat_gain outside 0..255, a geom row with ch or cw < 1, or B * hh * hw * K >= 2^31.
+ * desc, prims, geom and heat_mask are read before the call returns: they travel in kernel arguments (the primitives by ceil(NP / 120) small launches
+ * into the handle's workspace; the map maxima by one more launch).  One launch per 64 images on the handle's stream.  The call does NOT
+ * synchronise (growing the handle's workspace, first call or a larger NP, does, as for every entry point that uses it). */
+int jcm_render_poses(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, uint8_t* out,
+                     const int32_t* prims, int NP,
+                     const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain);
+
 /* -- mirrored test-time evaluation -----------------------------------------------------
  * The maps of an image averaged with the un-mirrored maps of its mirror image: jcm_mirror_pairs makes the batch the tower sees,
  * jcm_mirror_merge folds the tower's maps back.  Both enqueue one launch on the handle's stream and do not synchronise.

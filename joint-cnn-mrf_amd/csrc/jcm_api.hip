@@ -845,6 +845,65 @@ int jcm_fit_windows(jcm_handle h, const uint8_t* src, int64_t src_bytes, const i
   return JCM_OK;
 }
 
+int jcm_render_poses(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP,
+                     const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain) {
+  JCM_TRY(check(h, false));
+  const std::string who = "render_poses";
+  if (!src || !desc || !out) return fail(JCM_ERR_ARG, who + ": null pointer (src, desc and out are required)");
+  if (B < 1 || src_bytes < 1) return fail(JCM_ERR_ARG, who + ": B >= 1 images in src_bytes >= 1 bytes are expected");
+  for (int b = 0; b < B; ++b) {
+    const int64_t off = desc[b * (int64_t)3], hb = desc[b * (int64_t)3 + 1], wb = desc[b * (int64_t)3 + 2];
+    const std::string img = who + ": image " + std::to_string(b);
+    if (hb < 1 || hb > 16384 || wb < 1 || wb > 16384)
+      return fail(JCM_ERR_ARG, img + " is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..16384");
+    if (off < 0 || off > src_bytes || hb * wb * 3 > src_bytes - off)
+      return fail(JCM_ERR_ARG, img + " (" + std::to_string(hb * wb * 3) + " bytes at offset " + std::to_string(off) + ") does not lie inside the " +
+                                   std::to_string(src_bytes) + " bytes of src");
+  }
+  if (out != src) {
+    const char *pa = reinterpret_cast<const char*>(src), *pb = reinterpret_cast<const char*>(out);
+    if (pa < pb + src_bytes && pb < pa + src_bytes) return fail(JCM_ERR_ARG, who + ": out overlaps src in part (out == src, in place, is allowed)");
+  }
+  if (NP < 0 || (NP > 0 && !prims)) return fail(JCM_ERR_ARG, who + ": NP >= 0 primitives are expected, and prims with NP > 0");
+  constexpr int32_t kCoord = 1 << 20;
+  for (int i = 0, run = 0; i < NP; ++i) {
+    const int32_t* p = prims + i * (int64_t)8;
+    const std::string prim = who + ": primitive " + std::to_string(i);
+    if (p[0] < 0 || p[0] >= B || (i > 0 && p[0] < p[-8]))
+      return fail(JCM_ERR_ARG, prim + " names image " + std::to_string(p[0]) + "; the images are 0.." + std::to_string(B - 1) + " and the list is sorted by image");
+    run = i > 0 && p[0] == p[-8] ? run + 1 : 1;
+    if (run > kRenderPrimMax) return fail(JCM_ERR_ARG, who + ": image " + std::to_string(p[0]) + " has more than " + std::to_string(kRenderPrimMax) + " primitives");
+    for (int k = 1; k <= 4; ++k)
+      if (p[k] < -kCoord || p[k] > kCoord) return fail(JCM_ERR_ARG, prim + ": coordinate " + std::to_string(p[k]) + " outside +-2^20 sixteenths of a pixel");
+    if (p[5] < 0 || p[5] > (1 << 16)) return fail(JCM_ERR_ARG, prim + ": r = " + std::to_string(p[5]) + " outside 0..2^16");
+    if (p[6] < 0 || p[6] > 0xFFFFFF) return fail(JCM_ERR_ARG, prim + ": rgb outside 0..0xFFFFFF");
+    if (p[7] < 0 || p[7] > 255) return fail(JCM_ERR_ARG, prim + ": alpha = " + std::to_string(p[7]) + " outside 0..255");
+  }
+  if (hm) {
+    if (!geom || !heat_mask) return fail(JCM_ERR_ARG, who + ": hm needs geom and heat_mask");
+    if (K < 1 || K > 16 || hh < 1 || hw < 1 || stride < 1 || heat_gain < 0 || heat_gain > 255)
+      return fail(JCM_ERR_ARG, who + ": hm needs K in 1..16, hh, hw and stride >= 1 and heat_gain in 0..255");
+    if ((int64_t)B * hh * hw * K >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, who + ": B * hh * hw * K >= 2^31");
+    for (int b = 0; b < B; ++b)
+      if (geom[b * (int64_t)4 + 2] < 1 || geom[b * (int64_t)4 + 3] < 1)
+        return fail(JCM_ERR_ARG, who + ": geom row " + std::to_string(b) + " has a content rectangle without a pixel");
+  }
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  return with_arena(c, [&] {
+    int32_t* prims_dev = arena_alloc<int32_t>(c, render_prim_ints(NP));
+    float* maxima = hm ? arena_alloc<float>(c, (size_t)B * K) : nullptr;
+    if (c->dry) return (int)JCM_OK;
+    hipEvent_t e0, e1;
+    JCM_TRY(prof_begin(c, &e0, &e1));
+    const hipError_t launch = render_poses(src, desc, B, out, prims, NP, prims_dev, hm, hh, hw, K, stride, geom, heat_mask, heat_gain, maxima, c->stream);
+    prof_end(c, "render_poses", e0, e1, launch == hipSuccess);
+    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("render_poses: ") + hipGetErrorString(launch));
+    return (int)JCM_OK;
+  });
+}
+
 int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
                       int hh, int hw, float* x_out, float* y_out) {
   JCM_TRY(check(h, false));

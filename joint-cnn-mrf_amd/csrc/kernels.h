@@ -380,6 +380,32 @@ struct FitWinBatch {
 // for bit.  One launch per kFitWinMax windows; the source rows and columns a work group stages are those of its window's support only.
 hipError_t fit_windows(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, bool out_f32, void* out,
                        hipStream_t st);
+// ---- render.hip : poses drawn onto the ragged byte batch --------------------------
+// The images of a launch travel by value in its kernel arguments, as FitBatch does; a batch of more than kRenderMax images takes several launches.
+constexpr int kRenderMax = 64;
+constexpr int kRenderTile = 8192;        // consecutive pixels (row-major) per work group: 24 KB of LDS
+constexpr int kRenderPrimMax = 256;      // primitives per image: one thread of a work group culls one
+struct RenderBatch {
+  int64_t off[kRenderMax];               // byte offset of image i in src and in out
+  int h[kRenderMax], w[kRenderMax];
+  int first[kRenderMax + 1];             // work groups [first[i], first[i + 1]) are the tiles of image i
+  int pfirst[kRenderMax + 1];            // primitives [pfirst[i], pfirst[i + 1]) of the device list are image i's
+  int gy0[kRenderMax], gx0[kRenderMax], gch[kRenderMax], gcw[kRenderMax];      // the image's fit into the heat maps' frame (the tint only)
+};                                       // 2568 bytes of the 4096 a launch may carry
+struct RenderHeat {
+  const float* hm;                       // [B,hh,hw,K]
+  const float* maxima;                   // [B,K], written by the launch before
+  int hh, hw, K, stride, gain;
+  uint8_t mask[16];
+};
+// workspace the caller provides: prims_dev = render_prim_ints(NP) ints (256-byte aligned), maxima = B * K floats (hm only)
+size_t render_prim_ints(int NP);
+// src / out: the packed buffers; desc HOST int64 [B][3]; prims HOST int32 [NP][8] sorted by image; geom HOST int32 [B][4], heat_mask HOST [K] (hm only).
+// Every entry has been checked by the caller (jcm.h: jcm_render_poses).  The host arrays are read before the call returns; ceil(NP / 120) upload
+// launches, one launch for the maxima (hm), one launch per kRenderMax images.  out == src is allowed.
+hipError_t render_poses(const uint8_t* src, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP, int32_t* prims_dev,
+                        const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain,
+                        float* maxima, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

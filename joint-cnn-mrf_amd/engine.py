@@ -613,6 +613,61 @@ class Engine:
             off += im.numel()
         return ts, desc, off, dtype
 
+    def _fit_pack(self, ts, desc, off):
+        """The images ts back to back in one new device buffer of `off` bytes, image i at byte desc[i, 0]."""
+        src = self._new(off, dtype=torch.uint8)
+        if all(im.device.type == 'cpu' for im in ts):      # one packed host buffer, one copy
+            src.copy_(torch.cat([im.reshape(-1) for im in ts]))
+        else:
+            for i, im in enumerate(ts):
+                src[int(desc[i, 0]):int(desc[i, 0]) + im.numel()].copy_(im.reshape(-1))
+        return src
+
+    def render_poses(self, images, prims, hm=None, geom=None, heat_mask=None, heat_gain=255, stride=8):
+        """Poses drawn onto images of any size (include/jcm.h: jcm_render_poses): `images` as for fit_images; `prims` int [NP,8] =
+        (image, ay, ax, by, bx, r, rgb = 0xRRGGBB, alpha), capsules in sixteenths of a pixel, sorted by image and applied in listing order (what
+        predict.skeleton_primitives makes; NP = 0 draws none).  hm: the heat tint under them -- a device float32 [B,hh,hw,K] tensor, or a list of B
+        [hh,hw,K] device tensors, the maps of the frame the images were fitted into; then geom int [B,4 or 6], the fit of every image ((y0, x0, ch,
+        cw, ..), what fit_images returns), heat_mask uint8 [K] (bits 0, 1, 2: joint j tints R, G, B), heat_gain 0..255 and stride, frame pixels per
+        map cell.  The images are packed as fit_images packs them and drawn on in place there: returns a list of uint8 [h,w,3] device tensors,
+        views into that one buffer.  Nothing synchronises; every range is checked by the library."""
+        ts, desc, off, _ = self._fit_check(images, torch.uint8)
+        B = len(ts)
+        pr = np.asarray(prims)
+        if pr.size == 0:
+            pr = np.zeros((0, 8), np.int32)
+        if pr.dtype.kind not in 'iu' or pr.ndim != 2 or pr.shape[1] != 8:
+            raise ValueError('prims must be an integer array [NP,8] = (image, ay, ax, by, bx, r, rgb, alpha), got %s %s' % (pr.dtype, pr.shape))
+        if pr.shape[0] and (pr.min() < -2 ** 31 or pr.max() >= 2 ** 31):
+            raise ValueError('prims holds a value outside int32')
+        pr = np.ascontiguousarray(pr, dtype=np.int32)
+        hh = hw = K = 0
+        g4 = mask = None
+        if hm is not None:
+            if isinstance(hm, (list, tuple)):
+                hm = torch.stack(list(hm))
+            self._chk(hm, 4, 'hm')
+            hh, hw, K = int(hm.shape[1]), int(hm.shape[2]), int(hm.shape[3])
+            if hm.shape[0] != B:
+                raise ValueError('hm holds %d images, images %d' % (hm.shape[0], B))
+            if geom is None or heat_mask is None:
+                raise ValueError('hm needs geom (the fit of every image) and heat_mask (the channels every joint tints)')
+            g4 = np.asarray(geom)
+            if g4.dtype.kind not in 'iu' or g4.ndim != 2 or g4.shape[0] != B or g4.shape[1] < 4:
+                raise ValueError('geom must be an integer array [%d, 4 or 6] = (y0, x0, ch, cw, ..), got %s %s' % (B, g4.dtype, g4.shape))
+            g4 = np.ascontiguousarray(g4[:, :4], dtype=np.int32)
+            mask = np.ascontiguousarray(np.asarray(heat_mask), dtype=np.uint8).reshape(-1)
+            if mask.shape[0] != K:
+                raise ValueError('heat_mask has %d entries, hm %d joints' % (mask.shape[0], K))
+        buf = self._fit_pack(ts, desc, off)
+        self._on_stream(buf, *([hm] if hm is not None else []))
+        _lib.check(self._lib.jcm_render_poses(
+            self._h, self._p(buf), off, desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B, self._p(buf),
+            pr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if pr.shape[0] else None, pr.shape[0], self._p(hm), hh, hw, K, int(stride),
+            g4.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if g4 is not None else None,
+            mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None, int(heat_gain)), 'jcm_render_poses')
+        return [buf[int(d[0]):int(d[0]) + int(d[1] * d[2] * 3)].view(int(d[1]), int(d[2]), 3) for d in desc]
+
     def _fit_run(self, entry, ts, desc, off, rows, sizes, out_hw, pad, dtype, out):
         """What fit_images and fit_windows share once the descriptor array is built: the output frame (`out` checked, or a new one), the images
         ts back to back in one device buffer of `off` bytes (desc[:, 0] their offsets), the library's `entry` on the int64 descriptor `rows`
@@ -625,12 +680,7 @@ class Engine:
             self._chk(out, 4, 'out', dtype)
             if tuple(out.shape) != (n, OH, OW, C):
                 raise ValueError('out must be [%d,%d,%d,%d], got %s' % (n, OH, OW, C, tuple(out.shape)))
-        src = self._new(off, dtype=torch.uint8)
-        if all(im.device.type == 'cpu' for im in ts):      # one packed host buffer, one copy
-            src.copy_(torch.cat([im.reshape(-1) for im in ts]))
-        else:
-            for i, im in enumerate(ts):
-                src[int(desc[i, 0]):int(desc[i, 0]) + im.numel()].copy_(im.reshape(-1))
+        src = self._fit_pack(ts, desc, off)
         geom = np.empty((n, 6), np.int32)
         g4 = np.empty((n, 4), np.int32)
         self._on_stream(src, out)

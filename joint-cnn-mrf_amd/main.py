@@ -40,7 +40,8 @@ hm_height, hm_width = 60, 90      # data.py:180
 flag_train = False                # inference only: BatchNorm uses moving statistics (main.py:406)
 
 hps = argparse.Namespace(debug=False, train=False, gpus=[0], restore=False, use_sm=True, data_augm=False,
-                         batch_size=14)            # defaults of main.py:428-439
+                         batch_size=14,            # defaults of main.py:428-439
+                         render=None, render_heat=None)
 pairwise_energies, pairwise_biases = {}, {}        # '<j>_<c>' -> tensor, main.py:478-487
 _engine = None
 
@@ -94,6 +95,11 @@ def build_parser():
     parser.add_argument('--zoom', action='store_true', help='with --predict and --use_sm: a second pass -- a window around every person of the first pass, sized so '
                         'that the torso has the length FLIC torsos have in a 480-row frame, is fitted and run through the tower again (DESIGN.md 4.17); every '
                         'image of the document gains "zoom", one entry per person.  What it buys with FLIC-trained weights has not been measured.')
+    parser.add_argument('--render', default=None, metavar='DIR', help='with --predict: draw the predicted skeleton on every input, on the device at the input\'s '
+                        'own size (Engine.render_poses, DESIGN.md 4.18), and write DIR/<index:05d>_<basename>.png, one per input; the spatial model\'s '
+                        'joints with --use_sm (a zoomed person\'s from the second pass), the part detector\'s otherwise.  The JSON line gains render_ms.')
+    parser.add_argument('--render_heat', default=None, choices=['pd', 'sm'], help='with --render: tint the images with the heat maps of the part detector (pd) or '
+                        'of the spatial model (sm, needs --use_sm) under the skeleton, every joint in the colour the reference\'s overlays give it.')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -289,6 +295,9 @@ PREDICT_NOT_WITH_DEVICE_DATA = '--predict cannot be combined with --device_data:
 ZOOM_NEEDS_PREDICT = '--zoom is the second pass of --predict (a window around every person the first pass found): give --predict PATH as well'
 ZOOM_NEEDS_USE_SM = ('--zoom needs --use_sm: the windows are placed at the inferred torso and sized by the shoulders and hips of the spatial model, '
                      'and the second pass runs the spatial model at the torso cell it is given')
+RENDER_NEEDS_PREDICT = '--render draws the result of --predict onto its input images: give --predict PATH as well'
+RENDER_HEAT_NEEDS_RENDER = '--render_heat tints the pictures --render writes: give --render DIR as well'
+RENDER_HEAT_SM_NEEDS_USE_SM = '--render_heat sm tints with the maps of the spatial model: give --use_sm as well, or ask for --render_heat pd'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
 TB_ACTIVATIONS_NEEDS_TB_DIR = '--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
@@ -298,7 +307,8 @@ TB_ACTIVATIONS_IS_FP32 = ('--tb_activations: the pre-activation summaries are ta
 
 def predict_main(args):
     """--predict PATH [PATH ...]: the named images through predict.predict_images on the first listed device; the JSON document goes to
-    --predictions, one JSON line with the image count and the device times of the fit and of the forwards to stdout."""
+    --predictions, one JSON line with the image count and the device times of the fit and of the forwards to stdout.  With --render DIR the
+    images come back with the result drawn on them (predict.render_images) and go to DIR as PNG files; the line gains render_ms."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -309,7 +319,9 @@ def predict_main(args):
     try:
         timing = {}
         results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
-                                         batch_size=args.batch_size, timing=timing, zoom=args.zoom)
+                                         batch_size=args.batch_size, timing=timing, zoom=args.zoom, keep_maps=bool(args.render_heat))
+        if args.render:
+            pictures = predict.render_images(eng, images, results, heat=args.render_heat, batch_size=args.batch_size, timing=timing)
     finally:
         eng.close()
     os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
@@ -319,6 +331,13 @@ def predict_main(args):
             'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}
     if args.zoom:
         line.update(zoom=True, zoom_fit_ms=timing['zoom_fit_ms'], zoom_forward_ms=timing['zoom_forward_ms'])
+    if args.render:
+        from .summary import encode_png
+        os.makedirs(args.render, exist_ok=True)
+        for i, (f, picture) in enumerate(zip(files, pictures)):
+            with open(os.path.join(args.render, '%05d_%s.png' % (i, os.path.splitext(os.path.basename(f))[0])), 'wb') as fh:
+                fh.write(encode_png(picture))
+        line.update(render_ms=timing['render_ms'])
     print(json.dumps(line))
 
 
@@ -551,6 +570,9 @@ FLAG_RULES = (
     (lambda a: a.peaks and not 1 <= a.peaks <= 8, lambda a: '--peaks %d: 1 <= P <= 8' % a.peaks),
     (lambda a: a.tb_activations and not a.tb_dir, TB_ACTIVATIONS_NEEDS_TB_DIR),
     (lambda a: a.tb_activations and a.precision != 'fp32', TB_ACTIVATIONS_IS_FP32),
+    (lambda a: a.render and not a.predict, RENDER_NEEDS_PREDICT),
+    (lambda a: a.render_heat and not a.render, RENDER_HEAT_NEEDS_RENDER),
+    (lambda a: a.render_heat == 'sm' and not a.use_sm, RENDER_HEAT_SM_NEEDS_USE_SM),
 )
 
 

@@ -8,7 +8,10 @@ measured.  Multi-scale and mirrored evaluation are not offered here: the inferre
 The zoom pass (predict_images(zoom=True)) answers the changed scale: a window around every person the first pass found, sized
 so that the person's torso gets the length FLIC torsos have in a 480-row frame, is fitted by Engine.fit_windows and run through the tower
 again, with the torso blob at the window's centre; evaluation.window_to_source maps the joints back.  What this buys with FLIC-trained weights
-has not been measured either."""
+has not been measured either.
+
+Pictures: skeleton_primitives turns results into capsules, render_images draws them -- and, with keep_maps, the heat maps
+under them -- onto the images at their own size through Engine.render_poses."""
 import os
 
 import numpy as np
@@ -35,7 +38,7 @@ def _coords_to_points(coords):
     return np.where(c < 0, -1.0, c * STRIDE)
 
 
-def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1, batch_size=16, pad=0, timing=None, zoom=False):
+def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1, batch_size=16, pad=0, timing=None, zoom=False, keep_maps=False):
     """images: a list of uint8 [h,w,3] arrays or tensors of mixed sizes (what Engine.fit_images takes).  They are fitted and run through
     engine.forward(x_u8, torso='infer' if use_sm else None, use_sm=use_sm, peaks=peaks, decode=decode, people=people) batch_size at a time.
     Returns one dict per image, everything in the image's own pixels (row, col), host numpy:
@@ -50,6 +53,8 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
         evaluation.window_to_source): {'zoomed' bool, 'window' (y0, x0, h, w) in the image's pixels, 'torso_len' (the person's pass-1
         shoulder-to-hip distance in the image's pixels), 'pd', 'pd_inside', 'sm', 'sm_inside'}; a person zoom_windows skips has zoomed False
         and the pass-1 values.
+      with keep_maps (every key above keeps its value): 'maps' = {'pd': device float32 [60,90,K]} and with use_sm also 'sm' (people > 1: slot 0),
+        views of the first pass's probability maps of the image's batch -- what render_images(heat=...) tints with.
     timing: a dict that receives 'fit_ms' and 'forward_ms', device-event times summed over the batches (the upload of host images is part of
     neither), and with zoom 'zoom_fit_ms' and 'zoom_forward_ms', those of the second pass."""
     if not isinstance(images, (list, tuple)) or len(images) == 0:
@@ -70,12 +75,15 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
             ev[0].record(engine._stream)
             x, geom = engine.fit_images(batch, out_hw=FRAME, pad=pad)
             ev[1].record(engine._stream)
-            r = engine.forward(x, 'infer' if use_sm else None, use_sm=use_sm, want_prob=False, peaks=peaks, decode=decode, people=people)
+            r = engine.forward(x, 'infer' if use_sm else None, use_sm=use_sm, want_prob=bool(keep_maps), peaks=peaks, decode=decode, people=people)
             ev[2].record(engine._stream)
             ev[2].synchronize()
             fit_ms += ev[0].elapsed_time(ev[1])
             fwd_ms += ev[1].elapsed_time(ev[2])
             res = _to_source(r, geom, names, use_sm, peaks, decode, people)
+            if keep_maps:
+                for b, e in enumerate(res):
+                    e['maps'] = {key: r[key + '_prob'][b] for key in (('pd', 'sm') if use_sm else ('pd',))}
             if zoom:
                 _zoom_pass(engine, batch, res, people, int(batch_size), pad, zoom_ms)
             out.extend(res)
@@ -227,6 +235,101 @@ def _to_source(r, geom, names, use_sm, peaks, decode, people):
     return res
 
 
+# ------------------------------------------------------------------ pictures of the result
+NECK = -1      # no joint of the network: the midpoint of the shoulders, the floor-halved sum of their fixed-point coordinates
+# limbs as (first joint, second joint); a limb takes the colour of its second joint
+SKELETON = ((0, 1), (1, 2), (3, 4), (4, 5), (0, 3), (0, 6), (3, 7), (6, 7), (NECK, 8))
+# colorize's table (tensorboard.py:6-18), 0xRRGGBB per joint of JOINT_NAMES: shoulders green, elbows blue, wrists yellow, hips magenta, nose red
+JOINT_RGB = (0x00FF00, 0x0000FF, 0xFFFF00, 0x00FF00, 0x0000FF, 0xFFFF00, 0xFF00FF, 0xFF00FF, 0xFF0000)
+# bits 0, 1, 2: the joint's map tints R, G, B (jcm_render_poses)
+HEAT_MASK = tuple((1 if c >> 16 & 255 else 0) | (2 if c >> 8 & 255 else 0) | (4 if c & 255 else 0) for c in JOINT_RGB)
+LIMB_ALPHA, JOINT_ALPHA = 192, 255
+
+
+def _fixed(v):
+    """Pixels (integer coordinates are pixel centres) -> sixteenths of a pixel."""
+    return int(np.floor(16.0 * float(v) + 0.5))
+
+
+def _skeletons(r, which, zoom):
+    """The (joints [K,2], inside [K]) pairs one image's result draws: one per entry of 'zoom' (a person the second pass skipped carries the
+    first pass's values), else one per counted slot of 'people' (spatial model only), else the image's one set of joints."""
+    if zoom and 'zoom' in r:
+        return [(e[which], e[which + '_inside']) for e in r['zoom']]
+    if which == 'sm' and 'people' in r:
+        p = r['people']
+        return [(p['sm'][m], p['sm_inside'][m]) for m in range(int(p['count']))]
+    return [(r[which], r[which + '_inside'])]
+
+
+def skeleton_primitives(results, which='sm', zoom=True):
+    """The capsules Engine.render_poses draws for `results` (dicts of predict_images; image i of the list is image i of the primitives) ->
+    int32 [NP,8] = (image, ay, ax, by, bx, r, rgb, alpha), coordinates and radii in sixteenths of a pixel (floor(16 v + 0.5)).  Per image
+    rl = max(16, 2 * (h + w) // 75), 2 px at 480 x 720.  Per skeleton, first the limbs of SKELETON whose two ends are inside (radius rl, the
+    colour of the second joint, alpha 192; the neck exists when both shoulders do), then a disc per inside joint (radius 2 rl, alpha 255).
+    which: 'sm' or 'pd', whose joints are drawn; with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
+    in a result, one skeleton per entry of it, a zoomed person's from the second pass."""
+    if which not in ('sm', 'pd'):
+        raise ValueError("which must be 'sm' or 'pd', got %r" % (which,))
+    rows = []
+    for i, r in enumerate(results):
+        if which not in r:
+            raise ValueError("results[%d] has no %r joints (predict_images(use_sm=%s) makes them)" % (i, which, which == 'sm'))
+        rl = max(16, 2 * (int(r['size'][0]) + int(r['size'][1])) // 75)
+        for joints, inside in _skeletons(r, which, zoom):
+            K = len(inside)
+            pts = [(_fixed(joints[j][0]), _fixed(joints[j][1])) if inside[j] else None for j in range(K)]
+            neck = None
+            if K > 3 and pts[0] is not None and pts[3] is not None:
+                neck = ((pts[0][0] + pts[3][0]) // 2, (pts[0][1] + pts[3][1]) // 2)
+            for ja, jb in SKELETON:
+                if jb >= K or ja >= K:
+                    continue
+                a, b = neck if ja == NECK else pts[ja], pts[jb]
+                if a is not None and b is not None:
+                    rows.append((i, a[0], a[1], b[0], b[1], rl, JOINT_RGB[jb], LIMB_ALPHA))
+            for j in range(min(K, len(JOINT_RGB))):
+                if pts[j] is not None:
+                    rows.append((i, pts[j][0], pts[j][1], pts[j][0], pts[j][1], 2 * rl, JOINT_RGB[j], JOINT_ALPHA))
+    return np.array(rows, np.int32).reshape(-1, 8)
+
+
+def render_images(engine, images, results, heat=None, which=None, zoom=True, heat_gain=255, batch_size=16, timing=None):
+    """`images` (what predict_images took) with `results` (what it returned) drawn on them by Engine.render_poses, batch_size at a time -> a list
+    of host uint8 [h,w,3] arrays.  which: 'sm' or 'pd' (default: 'sm' where the results have it); zoom as for skeleton_primitives.  heat:
+    None, or 'pd' / 'sm': the maps of that stage tinted under the skeleton (JOINT_RGB's colours; needs predict_images(keep_maps=True)).
+    timing: a dict that receives 'render_ms', the device-event time of the render calls summed over the batches (uploads and the read-back
+    are not part of it)."""
+    if not isinstance(images, (list, tuple)) or len(images) != len(results) or len(images) == 0:
+        raise ValueError('images and results must be non-empty lists of the same length')
+    if heat not in (None, 'pd', 'sm'):
+        raise ValueError("heat must be None, 'pd' or 'sm', got %r" % (heat,))
+    if which is None:
+        which = 'sm' if 'sm' in results[0] else 'pd'
+    out, ms = [], 0.0
+    with torch.cuda.stream(engine._stream):
+        for lo in range(0, len(images), int(batch_size)):
+            batch = [_upload(im, engine.device) for im in images[lo:lo + int(batch_size)]]
+            res = results[lo:lo + int(batch_size)]
+            kw = {}
+            if heat is not None:
+                if any('maps' not in r or heat not in r['maps'] for r in res):
+                    raise ValueError('heat=%r needs the maps of that stage: run predict_images(keep_maps=True%s)' % (heat, ', use_sm=True' if heat == 'sm' else ''))
+                maps = [r['maps'][heat] for r in res]
+                kw = dict(hm=maps, geom=np.array([r['geom'][:4] for r in res], np.int32), heat_mask=HEAT_MASK[:maps[0].shape[-1]],
+                          heat_gain=heat_gain, stride=STRIDE)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record(engine._stream)
+            drawn = engine.render_poses(batch, skeleton_primitives(res, which, zoom), **kw)
+            ev[1].record(engine._stream)
+            host = [d.cpu().numpy() for d in drawn]
+            ms += ev[0].elapsed_time(ev[1])
+            out.extend(host)
+    if timing is not None:
+        timing.update(render_ms=ms)
+    return out
+
+
 # ------------------------------------------------------------------ the command line (main.py --predict)
 def expand_paths(paths):
     """Files as given, directories expanded to their image files in sorted order."""
@@ -273,4 +376,4 @@ def _listed(v):
 
 def predictions_document(files, results):
     return {'joint_names': results[0]['joint_names'], 'frame': list(FRAME), 'stride': STRIDE,
-            'images': [dict({'path': f}, **{k: _listed(v) for k, v in r.items() if k != 'joint_names'}) for f, r in zip(files, results)]}
+            'images': [dict({'path': f}, **{k: _listed(v) for k, v in r.items() if k not in ('joint_names', 'maps')}) for f, r in zip(files, results)]}
