@@ -639,6 +639,14 @@ int jcm_train_resize_bwd(jcm_handle h, const void* dy, int B, int sh, int sw, in
 int jcm_train_softmax_ce(jcm_handle h, const float* logits, const float* target, int B, int HW, int K, int Kt, float gscale, float* loss, float* dz,
                          int ldz, int accumulate);
 int jcm_train_softmax_bwd(jcm_handle h, const float* p, const float* g, int B, int HW, int K, int ldg, float* dz, int ldz);
+/* The spatial model's training stage on caller tensors, through the host function the step calls behind its spatial softmax (main.py:528-531,539 and
+ * their backward pass; fp32 on every handle; 9 joints, spatial-model parameters set).  pd_prob [B,5400,K] = hm_pred_pd, y [B,5400,K+1] the targets:
+ *   ce_out [B*K]     = the cross-entropy of every (image, joint) map of the spatial model's logits, unscaled;
+ *   dlog [B,5400,16] : channels < K += d (gscale * sum ce) / d pd_logits, through pd_prob = softmax over the map; channels >= K are not touched;
+ *   grads            : the energy_*, bias_* and bn_sm/BatchNorm/{gamma,beta} slices of the flat layout of jcm_train_param_info = the gradients of
+ *                      gscale * sum ce; nothing else is written;
+ * and bn_sm's moving_mean / moving_variance advance as in the step.  The backward pass runs in slices of "sm_chunk" images. */
+int jcm_train_sm_grads(jcm_handle h, const float* pd_prob, const float* y, int B, float gscale, float* ce_out, float* dlog, float* grads);
 /* grads: the (tower-averaged) gradients, same layout; lr: the value of lr_tf for this update
  * (main.py:492); clip_norm <= 0 disables the clip; grad_norm_out (host, may be NULL) receives the
  * global norm before clipping and makes the call synchronise. */

@@ -747,4 +747,19 @@ int jcm_train_softmax_bwd(jcm_handle h, const float* p, const float* g, int B, i
   return JCM_OK;
 }
 
+// The spatial model's training stage on caller tensors: sm_train_impl, the host function the step calls behind spatial_softmax -- forward in training
+// mode (bn_sm's batch statistics, its moving statistics advance), the cross-entropies, and the backward pass in slices of "sm_chunk" images -- so that
+// tests can hold it to float64 by itself, at batches and slice widths no whole step of the suite reaches.
+int jcm_train_sm_grads(jcm_handle h, const float* pd_prob, const float* y, int B, float gscale, float* ce_out, float* dlog, float* grads) {
+  JCM_TRY(need_train(h));
+  if (!pd_prob || !y || !ce_out || !dlog || !grads || B < 1) return fail(JCM_ERR_ARG, "bad train_sm_grads arguments (no null pointers, B >= 1)");
+  if (!h->has_sm) return fail(JCM_ERR_STATE, "train_sm_grads needs the spatial-model parameters (bn_sm, energy_*, bias_*)");
+  if (h->K + 1 != kC) return fail(JCM_ERR_ARG, "train_sm_grads: the spatial model's training stage is defined for 9 joints (n_joints = " + std::to_string(h->K) + ")");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  if (h->call_depth > 1) return fail(JCM_ERR_STATE, "jcm_train_sm_grads changes the handle's training state or parameters and cannot be called from the gradient-ready callback of the same handle");
+  jcm_ctx* c = h;
+  return with_arena(c, [&] { return sm_train_impl(c, pd_prob, y, B, gscale, ce_out, dlog, grads); });
+}
+
 }  // extern "C"

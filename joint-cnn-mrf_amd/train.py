@@ -242,6 +242,26 @@ class Trainer:
         _lib.check(self._lib.jcm_train_softmax_bwd(e._h, e._p(p), e._p(g), B, HW, K, g.shape[2], e._p(dz), dz.shape[2]), 'jcm_train_softmax_bwd')
         return dz
 
+    def sm_grads(self, pd_prob, y, gscale=None, dlog=None):
+        """The spatial model's training stage by itself (jcm_train_sm_grads): pd_prob [B,5400,K] probabilities, y [B,5400,K+1] targets ->
+        (ce [B,K] unscaled, dlog [B,5400,16]); the energy_* / bias_* / bn_sm slices of self.grads take the gradients of gscale * sum(ce) (default
+        gscale: 1 / (B K), the step's mean), dlog's channels < K gain the gradient w.r.t. the part detector's logits (dlog=None: added to zeros),
+        bn_sm's moving statistics advance.  Nothing else of self.grads is written."""
+        e = self.eng
+        e._chk(pd_prob, 3, 'pd_prob')
+        e._chk(y, 3, 'y')
+        B, HW, K = pd_prob.shape
+        if (HW, K) != (5400, e.n_joints) or tuple(y.shape) != (B, HW, K + 1):
+            raise ValueError('pd_prob must be [B,5400,%d] and y [B,5400,%d]; got %s, %s' % (e.n_joints, e.n_joints + 1, tuple(pd_prob.shape), tuple(y.shape)))
+        if dlog is None:
+            dlog = torch.zeros((B, HW, 16), dtype=torch.float32, device=e.device)
+        elif tuple(e._chk(dlog, 3, 'dlog').shape) != (B, HW, 16):
+            raise ValueError('dlog must be [%d,%d,16]; got %s' % (B, HW, tuple(dlog.shape)))
+        ce = e._new(B, K)
+        _lib.check(self._lib.jcm_train_sm_grads(e._h, e._p(pd_prob), e._p(y), B, float(1.0 / (B * K) if gscale is None else gscale), e._p(ce), e._p(dlog),
+                                                e._p(self.grads)), 'jcm_train_sm_grads')
+        return ce, dlog
+
     def grads_dict(self):
         """The flat gradient buffer as {TF variable name: numpy array} (reference shapes unknown here: flat)."""
         g = self.grads.cpu().numpy()
