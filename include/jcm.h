@@ -309,6 +309,53 @@ int jcm_hm_peaks(jcm_handle h, const float* hm, int B, int HH, int WW, int K, in
 int jcm_pose_decode(jcm_handle h, const float* hm10, int B, const int32_t* cells, const int32_t* count, int P,
                     int32_t* index, int32_t* coords, float* score, float* score0, float* V, float* M);
 
+/* -- frame sequences: a temporal edge on the heat maps of a clip -------------------------------
+ * One hidden position per (sequence s, joint k), independent of every other (s, k), observed through the maps of T consecutive frames:
+ * jcm_seq_filter is the causal forward filter (what an online caller runs, frame by frame or in pieces), jcm_seq_viterbi the offline most
+ * probable track.  hm: device fp32 [S,T,HH,WW,K], the layout the forward writes with the frames as its batch; p_t = hm[s,t,:,:,k] widened to
+ * float64.  Negative values and NaN are outside the contract.  HW = HH * WW.
+ * Motion model: a separable truncated kernel with 1-D taps w_k[0 .. 2R], float64, taps: HOST [K][2R+1], one row per joint, read before the call
+ * returns (it travels in kernel arguments); a uniform "anywhere" term of mass rho for misses and scene cuts: om = 1 - rho, u = rho / HW, formed
+ * in float64 on the host.  Cells outside the map contribute nothing.  All arithmetic is float64, one correctly rounded operation per step,
+ * evaluated as written (the library is built without contraction); there is no transcendental on the device.
+ * Filter, a_{t-1} the previous belief:
+ *   c(y,x) = sum over dy = -R .. R, ascending from 0.0, of w[dy+R] * a_{t-1}(y-dy, x)      terms outside the map skipped
+ *   m(y,x) = sum over dx = -R .. R, ascending from 0.0, of w[dx+R] * c(y, x-dx)
+ *   pred = om * m + u;   b = p_t * pred;   Z = sum of b;   a_t = b / Z
+ *   Z == 0 or not finite: b = p_t, Z = sum of p_t, reset = 1; that Z == 0 as well: a_t = 1 / HW everywhere, reset = 2.
+ *   Frame 0 without state_in takes the b = p_t branch with reset 0 (2 when the map is all zero); with state_in it is an ordinary frame.
+ *   The order of the sum Z is the kernel's own and fixed: it depends on neither S nor T, so a clip split over several calls with the state
+ *   carried gives the bits of one call.
+ *   state_in / state_out: device float64 [S,K,HH,WW], the belief before frame 0 / after frame T-1 (either may be NULL; two distinct buffers).
+ *   filtered: fp32 [S,T,HH,WW,K] = (float)a_t, may be NULL;  coords: int32 [S,T,2,K], the first-occurrence flat arg-max of the float64 a_t as
+ *   (row, col) in the layout of jcm_argmax_coords, required;  norm: float64 [S,T,K] = the Z that a_t was divided by (0 with reset 2), may be
+ *   NULL;  reset: int32 [S,T,K], may be NULL.
+ * Viterbi, max-product in the probability domain (no logarithm; max is exact and order-free).  d_0 = p_0 / max p_0; for t >= 1:
+ *   c(y,x) = max over dy of w[dy+R] * d_{t-1}(y-dy, x)      scanning dy ascending over the terms inside the map, a strictly greater value
+ *                                                           replaces (the lowest dy wins a tie); dy*(y,x) is the winner
+ *   m(y,x) = max over dx of w[dx+R] * c(y, x-dx)            likewise, dx*;   source cell = (y - dy*(y, x-dx*), x - dx*)
+ *   e = max(om * m, u * D),  D = max d_{t-1}                the jump wins only when strictly greater; its source is the first-occurrence
+ *                                                           flat arg-max of d_{t-1}
+ *   b = p_t * e;   M = max b;   d_t = b / M
+ *   M == 0 is a break: b = p_t, M = max p_t, every cell of the frame has no source, breaks = 1; that M == 0 as well: d_t = 1 everywhere,
+ *   breaks = 2.  Frame 0 is handled the same way without a flag, unless its map is all zero (breaks 2).
+ *   Backtrace: the end cell is the first-occurrence flat arg-max of d_{T-1}; then along the source cells; across a break the earlier segment
+ *   ends at the first-occurrence arg-max of its last d.
+ *   path: int32 [S,T,2,K] (row, col), required;  maxes: float64 [S,T,K] = the M that d_t was divided by (0 with breaks 2), may be NULL;
+ *   breaks: int32 [S,T,K], may be NULL.
+ * One work group per (s, k); the belief plane, the scratch plane and (Viterbi) the byte plane of dy* live in LDS for the whole launch, so a
+ * frame costs one read of its map and no launch.  Viterbi keeps the source cell of every cell, int16 [S*K][T][HW], and one int32 per (s, k, t)
+ * in the handle's workspace and walks them back in a second launch; jcm_seq_filter uses the workspace for the taps only.
+ * JCM_ERR_ARG -- nothing is launched and no output is touched -- for S, T, HH, WW or K below 1, K > 16, R outside 0..16, rho outside [0,1], a
+ * required pointer that is NULL, S * T * K >= 2^31, and HH * WW > 8192: two float64 planes and a byte plane must fit the 160 KB of LDS, and a
+ * larger map is refused, never truncated.  jcm_seq_viterbi returns JCM_ERR_STATE, with the bytes it needs in the message, when the
+ * back-pointers do not fit the workspace the device can still give; split the clip then.  Both enqueue on the handle's stream and do not
+ * synchronise (growing the workspace does, as for every entry point that uses it). */
+int jcm_seq_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                   const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out);
+int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                    int32_t* path, double* maxes, int32_t* breaks);
+
 /* Torso map from the part detector: the torso cell that the nine part-detector maps and the nine learned priors e_{j|torso} explain best, and the
  * blob at it -- the tenth channel jcm_sm_forward needs, for an image that has no annotation.  Fixed geometry like jcm_pose_decode's:
  * HH = 60, WW = 90, K = 9, 120x180 priors.

@@ -406,6 +406,20 @@ size_t render_prim_ints(int NP);
 hipError_t render_poses(const uint8_t* src, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP, int32_t* prims_dev,
                         const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain,
                         float* maxima, hipStream_t st);
+// ---- sequence.hip : the temporal edge, a scan over the T frames of a clip ----------
+// hm [S,T,HH,WW,K]; one work group per (sequence, joint), whose belief plane stays in LDS for all T frames of the launch.  HH * WW <= kSeqMaxHW,
+// K <= kSeqMaxK, 0 <= R <= kSeqMaxR; taps: DEVICE [K][2R+1] (seq_put_taps uploads a host table through kernel arguments, ceil(n / 480) launches).
+constexpr int kSeqMaxHW = 8192;
+constexpr int kSeqMaxK = 16;
+constexpr int kSeqMaxR = 16;
+hipError_t seq_put_taps(const double* taps_host, int n, double* taps_dev, hipStream_t st);
+// the forward filter (jcm.h: jcm_seq_filter); state_in, filtered, norm, reset and state_out may be null
+hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const double* state_in,
+                      float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st);
+// the most probable track (jcm.h: jcm_seq_viterbi); workspace the caller provides: bp int16 [S*K][T][HH*WW] (the source cell of every cell, -1 = none),
+// amax int32 [S*K][T] (the arg-max of every frame's d).  Two launches: the scan, then the backtrace (one lane per (sequence, joint)).
+hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, int16_t* bp, int32_t* amax,
+                       int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

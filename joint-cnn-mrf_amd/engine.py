@@ -344,6 +344,54 @@ class Engine:
                                              self._p(out['score']), self._p(out['score0']), self._p(out.get('V')), self._p(out.get('M'))), 'jcm_pose_decode')
         return out
 
+    def _seq_args(self, hm, sigma, radius):
+        """hm [T,HH,WW,K] or [S,T,HH,WW,K] -> (hm as [S,T,HH,WW,K], whether a sequence axis was added, host taps [K,2R+1], R)."""
+        from .predict import seq_radius, seq_taps
+        if not isinstance(hm, torch.Tensor) or hm.dim() not in (4, 5):
+            raise ValueError('hm must be a device tensor [T,HH,WW,K] or [S,T,HH,WW,K]')
+        single = hm.dim() == 4
+        hm5 = self._chk(hm.unsqueeze(0) if single else hm, 5, 'hm')
+        K = hm5.shape[4]
+        R = seq_radius(sigma) if radius is None else int(radius)
+        if not 0 <= R <= 16:      # before the taps are built; the library checks it again
+            raise ValueError('radius must be in 0..16, got %r' % (radius,))
+        return hm5, single, seq_taps(sigma, R, K), R
+
+    def seq_filter(self, hm, sigma, rho, radius=None, state=None):
+        """The causal forward filter of a clip's heat maps (include/jcm.h: jcm_seq_filter): hm [T,HH,WW,K] or [S,T,HH,WW,K],
+        frame after frame of what forward returns as pd_prob / sm_prob; sigma: a scalar or K values, the motion per frame in heat-map cells
+        (predict.seq_taps builds the taps); rho in [0,1]: the mass of the uniform "anywhere" term; radius: default min(16, ceil(3 max sigma));
+        state: float64 [S,K,HH,WW] ([K,HH,WW] for a 4-d hm), the 'state' of the call that ended just before frame 0, or None at a clip's start.
+        Returns {'filtered' fp32 like hm, 'coords' int32 [S,T,2,K] (row, col), 'norm' float64 [S,T,K], 'reset' int32 [S,T,K], 'state' float64
+        [S,K,HH,WW]}, device tensors without the S axis for a 4-d hm; nothing is read back.  HH * WW <= 8192 and K <= 16 are checked by the
+        library."""
+        hm5, single, taps, R = self._seq_args(hm, sigma, radius)
+        S, T, HH, WW, K = hm5.shape
+        if state is not None:
+            state = self._chk(state.unsqueeze(0) if single and isinstance(state, torch.Tensor) and state.dim() == 3 else state, 4, 'state', torch.float64)
+            if tuple(state.shape) != (S, K, HH, WW):
+                raise ValueError('state must be [S,K,HH,WW] = %s, got %s' % ((S, K, HH, WW), tuple(state.shape)))
+        out = {'filtered': self._new(S, T, HH, WW, K), 'coords': self._new(S, T, 2, K, dtype=torch.int32), 'norm': self._new(S, T, K, dtype=torch.float64),
+               'reset': self._new(S, T, K, dtype=torch.int32), 'state': self._new(S, K, HH, WW, dtype=torch.float64)}
+        self._on_stream(hm5, *([state] if state is not None else []), *out.values())
+        _lib.check(self._lib.jcm_seq_filter(self._h, self._p(hm5), S, T, HH, WW, K, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R, float(rho),
+                                            self._p(state), self._p(out['filtered']), self._p(out['coords']), self._p(out['norm']), self._p(out['reset']),
+                                            self._p(out['state'])), 'jcm_seq_filter')
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def seq_viterbi(self, hm, sigma, rho, radius=None):
+        """The most probable track through a clip's heat maps (include/jcm.h: jcm_seq_viterbi); hm, sigma, rho and radius as for
+        seq_filter.  Returns {'path' int32 [S,T,2,K] (row, col), 'maxes' float64 [S,T,K], 'breaks' int32 [S,T,K]}, device tensors without the S
+        axis for a 4-d hm; nothing is read back.  The back-pointers (2 bytes per cell, frame, joint and sequence) live in the engine's
+        workspace; a clip they do not fit in is a RuntimeError that names the bytes."""
+        hm5, single, taps, R = self._seq_args(hm, sigma, radius)
+        S, T, HH, WW, K = hm5.shape
+        out = {'path': self._new(S, T, 2, K, dtype=torch.int32), 'maxes': self._new(S, T, K, dtype=torch.float64), 'breaks': self._new(S, T, K, dtype=torch.int32)}
+        self._on_stream(hm5, *out.values())
+        _lib.check(self._lib.jcm_seq_viterbi(self._h, self._p(hm5), S, T, HH, WW, K, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R, float(rho),
+                                             self._p(out['path']), self._p(out['maxes']), self._p(out['breaks'])), 'jcm_seq_viterbi')
+        return {k: v[0] for k, v in out.items()} if single else out
+
     @staticmethod
     def _chk_decode(decode, use_sm, peaks):
         if decode and not (use_sm and 1 <= peaks <= 4):

@@ -100,6 +100,14 @@ def build_parser():
                         'joints with --use_sm (a zoomed person\'s from the second pass), the part detector\'s otherwise.  The JSON line gains render_ms.')
     parser.add_argument('--render_heat', default=None, choices=['pd', 'sm'], help='with --render: tint the images with the heat maps of the part detector (pd) or '
                         'of the spatial model (sm, needs --use_sm) under the skeleton, every joint in the colour the reference\'s overlays give it.')
+    parser.add_argument('--sequence', default=None, choices=['filter', 'viterbi'], help='with --predict: the expanded paths, in their sorted order, are the frames '
+                        'of ONE clip (all of one size); every image of the document gains "track", one position per joint that is consistent over the clip '
+                        '(predict.predict_sequence, DESIGN.md 4.19): filter = the causal forward filter, viterbi = the most probable track.  With --render the '
+                        'tracked skeleton is drawn.  What tracking buys with trained weights has not been measured.')
+    parser.add_argument('--seq_sigma', type=float, nargs='+', default=None, metavar='CELLS', help='with --sequence: the standard deviation of a joint\'s motion per '
+                        'frame in heat-map cells, one value or one per joint (default 1.5, an untuned placeholder).')
+    parser.add_argument('--seq_rho', type=float, default=None, metavar='RHO', help='with --sequence: the mass in [0,1] of the uniform "anywhere" term that absorbs '
+                        'misses and scene cuts (default 0.05, an untuned placeholder).')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -298,6 +306,10 @@ ZOOM_NEEDS_USE_SM = ('--zoom needs --use_sm: the windows are placed at the infer
 RENDER_NEEDS_PREDICT = '--render draws the result of --predict onto its input images: give --predict PATH as well'
 RENDER_HEAT_NEEDS_RENDER = '--render_heat tints the pictures --render writes: give --render DIR as well'
 RENDER_HEAT_SM_NEEDS_USE_SM = '--render_heat sm tints with the maps of the spatial model: give --use_sm as well, or ask for --render_heat pd'
+SEQUENCE_NEEDS_PREDICT = '--sequence tracks the joints over the frames --predict names: give --predict PATH as well'
+SEQUENCE_NO_ZOOM = '--sequence cannot be combined with --zoom: the windows of the second pass would move from frame to frame, which is out of scope'
+SEQUENCE_ONE_PERSON = '--sequence tracks one person: --people M > 1 would need an association of people across frames, which is out of scope'
+SEQ_OPTION_NEEDS_SEQUENCE = '--seq_sigma and --seq_rho set the motion model of --sequence: give --sequence filter or --sequence viterbi as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
 TB_ACTIVATIONS_NEEDS_TB_DIR = '--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
@@ -308,7 +320,8 @@ TB_ACTIVATIONS_IS_FP32 = ('--tb_activations: the pre-activation summaries are ta
 def predict_main(args):
     """--predict PATH [PATH ...]: the named images through predict.predict_images on the first listed device; the JSON document goes to
     --predictions, one JSON line with the image count and the device times of the fit and of the forwards to stdout.  With --render DIR the
-    images come back with the result drawn on them (predict.render_images) and go to DIR as PNG files; the line gains render_ms."""
+    images come back with the result drawn on them (predict.render_images) and go to DIR as PNG files; the line gains render_ms.  With --sequence
+    the images are the frames of one clip (predict.predict_sequence): the document gains "track" per file, the pictures show the tracked skeleton."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -318,10 +331,17 @@ def predict_main(args):
     eng = Engine(device=args.gpus[0], precision=args.precision, n_joints=n_joints).load_params(params)
     try:
         timing = {}
-        results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
-                                         batch_size=args.batch_size, timing=timing, zoom=args.zoom, keep_maps=bool(args.render_heat))
+        if args.sequence:
+            sigma = predict.SEQ_SIGMA if args.seq_sigma is None else args.seq_sigma
+            results = predict.predict_sequence(eng, images, mode=args.sequence, sigma=sigma[0] if isinstance(sigma, list) and len(sigma) == 1 else sigma,
+                                               rho=predict.SEQ_RHO if args.seq_rho is None else args.seq_rho, use_sm=args.use_sm, batch_size=args.batch_size,
+                                               keep_maps=bool(args.render_heat), peaks=args.peaks, decode=args.decode_pose, timing=timing)
+        else:
+            results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
+                                             batch_size=args.batch_size, timing=timing, zoom=args.zoom, keep_maps=bool(args.render_heat))
         if args.render:
-            pictures = predict.render_images(eng, images, results, heat=args.render_heat, batch_size=args.batch_size, timing=timing)
+            pictures = predict.render_images(eng, images, results, heat=args.render_heat, which='track' if args.sequence else None,
+                                             batch_size=args.batch_size, timing=timing)
     finally:
         eng.close()
     os.makedirs(os.path.dirname(args.predictions) or '.', exist_ok=True)
@@ -329,6 +349,8 @@ def predict_main(args):
         json.dump(predict.predictions_document(files, results), fh)
     line = {'predict': True, 'n_images': len(files), 'fit_ms': timing['fit_ms'], 'forward_ms': timing['forward_ms'], 'gpu': args.gpus[0],
             'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}
+    if args.sequence:
+        line.update(sequence=args.sequence)
     if args.zoom:
         line.update(zoom=True, zoom_fit_ms=timing['zoom_fit_ms'], zoom_forward_ms=timing['zoom_forward_ms'])
     if args.render:
@@ -574,13 +596,20 @@ FLAG_RULES = (
     (lambda a: a.render_heat and not a.render, RENDER_HEAT_NEEDS_RENDER),
     (lambda a: a.render_heat == 'sm' and not a.use_sm, RENDER_HEAT_SM_NEEDS_USE_SM),
 )
+# The rules of --sequence, walked behind FLAG_RULES: a table of their own, so that the table above ends where the tests of earlier flags expect it to.
+SEQUENCE_RULES = (
+    (lambda a: a.sequence and not a.predict, SEQUENCE_NEEDS_PREDICT),
+    (lambda a: a.sequence and a.zoom, SEQUENCE_NO_ZOOM),
+    (lambda a: a.sequence and a.people != 1, SEQUENCE_ONE_PERSON),
+    (lambda a: (a.seq_sigma is not None or a.seq_rho is not None) and not a.sequence, SEQ_OPTION_NEEDS_SEQUENCE),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

@@ -11,7 +11,12 @@ again, with the torso blob at the window's centre; evaluation.window_to_source m
 has not been measured either.
 
 Pictures: skeleton_primitives turns results into capsules, render_images draws them -- and, with keep_maps, the heat maps
-under them -- onto the images at their own size through Engine.render_poses."""
+under them -- onto the images at their own size through Engine.render_poses.
+
+Frame sequences: predict_sequence takes the frames of a clip, all of one size, and adds to every frame's result a 'track': one
+position per joint that is consistent over the clip, from Engine.seq_filter (causal) or Engine.seq_viterbi (the most probable track) on the
+stacked heat maps.  SequenceTracker is the online form of the filter.  SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what tracking buys
+with trained weights has not been measured."""
 import os
 
 import numpy as np
@@ -29,6 +34,11 @@ FRAME = (480, 720)
 ZOOM_TORSO_PIXELS = 130.63038126031898
 ZOOM_TORSO_JOINTS = ((0, 3), (6, 7))      # (lsho, rsho), (lhip, rhip)
 FIT_SIDE_MAX = 16384                      # include/jcm.h: the sides of what jcm_fit_images / jcm_fit_windows fit
+# The motion model of the sequence stages: the standard deviation of a joint's motion per frame in heat-map cells, and the mass of the uniform
+# "anywhere" term.  Untuned placeholders: no consecutive-frame data is at hand to derive them from.
+SEQ_SIGMA = 1.5
+SEQ_RHO = 0.05
+SEQ_RADIUS_MAX = 16                       # include/jcm.h: R of jcm_seq_filter / jcm_seq_viterbi
 IMAGE_EXTENSIONS = ('.npy', '.png', '.jpg', '.jpeg', '.bmp', '.gif', '.tif', '.tiff', '.webp', '.ppm')
 
 
@@ -235,6 +245,118 @@ def _to_source(r, geom, names, use_sm, peaks, decode, people):
     return res
 
 
+# ------------------------------------------------------------------ frame sequences
+def _seq_sigma(sigma, K=None):
+    sg = np.asarray(sigma, np.float64).reshape(-1)
+    if sg.size == 0 or not np.all(np.isfinite(sg)) or np.any(sg <= 0):
+        raise ValueError('sigma must be positive and finite, got %r' % (sigma,))
+    if K is not None:
+        if sg.size not in (1, K):
+            raise ValueError('sigma must be a scalar or %d values (one per joint), got %d' % (K, sg.size))
+        sg = np.broadcast_to(sg, (K,))
+    return sg
+
+
+def seq_radius(sigma):
+    """The default tap radius of the sequence stages: min(16, ceil(3 * max sigma))."""
+    return int(min(SEQ_RADIUS_MAX, np.ceil(3.0 * _seq_sigma(sigma).max())))
+
+
+def seq_taps(sigma, radius, K):
+    """The 1-D taps of the motion kernel jcm_seq_filter / jcm_seq_viterbi take: float64 [K, 2 * radius + 1], row k = exp(-d^2 / (2 sigma_k^2)) for
+    d = -radius .. radius, divided by its sum.  sigma: a scalar or K values, in heat-map cells per frame.  The one builder: Engine.seq_* and the
+    restatement of the tests share it."""
+    R = int(radius)
+    if R < 0:
+        raise ValueError('radius must be >= 0, got %r' % (radius,))
+    sg = _seq_sigma(sigma, int(K))
+    d = np.arange(-R, R + 1, dtype=np.float64)
+    w = np.exp(-(d[None, :] * d[None, :]) / (2.0 * sg[:, None] * sg[:, None]))
+    return np.ascontiguousarray(w / w.sum(axis=1, keepdims=True))
+
+
+def _one_size(frames):
+    if not isinstance(frames, (list, tuple)) or len(frames) == 0:
+        raise ValueError('frames must be a non-empty list of uint8 [h,w,3] images of one size')
+    shapes = {tuple(f.shape) for f in frames}
+    if len(shapes) != 1:
+        raise ValueError('the frames of a clip have one size (one letterbox geometry); got %s' % sorted(shapes))
+
+
+def _track_entries(seq, geom, mode):
+    """The dict of Engine.seq_filter / seq_viterbi on [T,HH,WW,K] maps and the frames' fit -> one 'track' dict per frame."""
+    cells = seq['coords' if mode == 'filter' else 'path']
+    pts, inside = fit_to_source(_coords_to_points(cells), geom)
+    value, flag = ('norm', 'reset') if mode == 'filter' else ('maxes', 'breaks')
+    v, f = seq[value].cpu().numpy(), seq[flag].cpu().numpy()
+    return [{'mode': mode, 'points': pts[t], 'inside': inside[t], value: v[t], flag: f[t]} for t in range(pts.shape[0])]
+
+
+def _seq_maps(results, use_sm):
+    return torch.stack([r['maps']['sm' if use_sm else 'pd'] for r in results]).contiguous()
+
+
+def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
+                     keep_maps=False, **kw):
+    """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
+    geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
+    [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal) or Engine.seq_viterbi (mode 'viterbi', the most probable
+    track); evaluation.fit_to_source maps the cells back.  Returns predict_images' dicts, every key with the value it has there, plus
+      'track': {'mode', 'points' float64 [K,2] (row, col) in the frame's own pixels, 'inside' bool [K], 'norm' or 'maxes' float64 [K], 'reset' or
+                'breaks' int [K]}  (the library's Z / M and its flags, include/jcm.h).
+    'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
+    the defaults SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what the track buys with trained weights has not been measured.
+    One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
+    frame, are out of scope."""
+    if mode not in ('filter', 'viterbi'):
+        raise ValueError("mode must be 'filter' or 'viterbi', got %r" % (mode,))
+    if people != 1:
+        raise ValueError('predict_sequence tracks one person: people=%r would need an association of people across frames, which is out of scope' % (people,))
+    if zoom:
+        raise ValueError('predict_sequence has no zoom pass: its windows would move from frame to frame, which is out of scope')
+    _one_size(frames)
+    results = predict_images(engine, frames, use_sm=use_sm, batch_size=batch_size, keep_maps=True, **kw)
+    with torch.cuda.stream(engine._stream):
+        hm = _seq_maps(results, use_sm)
+        seq = (engine.seq_filter if mode == 'filter' else engine.seq_viterbi)(hm, sigma, rho, radius=radius)
+        geom = np.array([r['geom'] for r in results], np.int64)
+        for r, track in zip(results, _track_entries(seq, geom, mode)):
+            r['track'] = track
+            if not keep_maps:
+                del r['maps']
+    return results
+
+
+class SequenceTracker:
+    """The online form of predict_sequence(mode='filter'): push(frames) takes the next frames of the clip, a few or one at a time, and returns
+    their dicts with 'track'; the filter's float64 belief is carried from call to call, so any split of a clip gives the values of one
+    predict_sequence over all of it.  Every push must bring frames of the first push's size.  reset() starts a new clip."""
+
+    def __init__(self, engine, sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, **kw):
+        self.engine, self.sigma, self.rho, self.radius, self.use_sm, self.batch_size, self.kw = engine, sigma, rho, radius, use_sm, batch_size, kw
+        self.reset()
+
+    def reset(self):
+        self.state, self.shape = None, None
+
+    def push(self, frames, keep_maps=False):
+        _one_size(frames)
+        shape = tuple(frames[0].shape)
+        if self.shape is not None and shape != self.shape:
+            raise ValueError('the frames of a clip have one size: this clip began with %s, got %s' % (self.shape, shape))
+        self.shape = shape
+        results = predict_images(self.engine, frames, use_sm=self.use_sm, batch_size=self.batch_size, keep_maps=True, **self.kw)
+        with torch.cuda.stream(self.engine._stream):
+            seq = self.engine.seq_filter(_seq_maps(results, self.use_sm), self.sigma, self.rho, radius=self.radius, state=self.state)
+            self.state = seq['state']
+            geom = np.array([r['geom'] for r in results], np.int64)
+            for r, track in zip(results, _track_entries(seq, geom, 'filter')):
+                r['track'] = track
+                if not keep_maps:
+                    del r['maps']
+        return results
+
+
 # ------------------------------------------------------------------ pictures of the result (DESIGN.md 4.18)
 NECK = -1      # no joint of the network: the midpoint of the shoulders, the floor-halved sum of their fixed-point coordinates
 # limbs as (first joint, second joint); a limb takes the colour of its second joint
@@ -252,8 +374,10 @@ def _fixed(v):
 
 
 def _skeletons(r, which, zoom):
-    """The (joints [K,2], inside [K]) pairs one image's result draws: one per entry of 'zoom' (a person the second pass skipped carries the
+    """The (joints [K,2], inside [K]) pairs one image's result draws: the tracked joints for 'track'; else one per entry of 'zoom' (a person the second pass skipped carries the
     first pass's values), else one per counted slot of 'people' (spatial model only), else the image's one set of joints."""
+    if which == 'track':
+        return [(r['track']['points'], r['track']['inside'])]
     if zoom and 'zoom' in r:
         return [(e[which], e[which + '_inside']) for e in r['zoom']]
     if which == 'sm' and 'people' in r:
@@ -267,14 +391,14 @@ def skeleton_primitives(results, which='sm', zoom=True):
     int32 [NP,8] = (image, ay, ax, by, bx, r, rgb, alpha), coordinates and radii in sixteenths of a pixel (floor(16 v + 0.5)).  Per image
     rl = max(16, 2 * (h + w) // 75), 2 px at 480 x 720.  Per skeleton, first the limbs of SKELETON whose two ends are inside (radius rl, the
     colour of the second joint, alpha 192; the neck exists when both shoulders do), then a disc per inside joint (radius 2 rl, alpha 255).
-    which: 'sm' or 'pd', whose joints are drawn; with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
+    which: 'sm' or 'pd', whose joints are drawn, or 'track', the tracked joints of predict_sequence; with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
     in a result, one skeleton per entry of it, a zoomed person's from the second pass."""
-    if which not in ('sm', 'pd'):
-        raise ValueError("which must be 'sm' or 'pd', got %r" % (which,))
+    if which not in ('sm', 'pd', 'track'):
+        raise ValueError("which must be 'sm', 'pd' or 'track', got %r" % (which,))
     rows = []
     for i, r in enumerate(results):
         if which not in r:
-            raise ValueError("results[%d] has no %r joints (predict_images(use_sm=%s) makes them)" % (i, which, which == 'sm'))
+            raise ValueError("results[%d] has no %r joints (%s makes them)" % (i, which, 'predict_sequence' if which == 'track' else 'predict_images(use_sm=%s)' % (which == 'sm')))
         rl = max(16, 2 * (int(r['size'][0]) + int(r['size'][1])) // 75)
         for joints, inside in _skeletons(r, which, zoom):
             K = len(inside)
@@ -296,7 +420,7 @@ def skeleton_primitives(results, which='sm', zoom=True):
 
 def render_images(engine, images, results, heat=None, which=None, zoom=True, heat_gain=255, batch_size=16, timing=None):
     """`images` (what predict_images took) with `results` (what it returned) drawn on them by Engine.render_poses, batch_size at a time -> a list
-    of host uint8 [h,w,3] arrays.  which: 'sm' or 'pd' (default: 'sm' where the results have it); zoom as for skeleton_primitives.  heat:
+    of host uint8 [h,w,3] arrays.  which: 'sm', 'pd' or 'track' (default: 'sm' where the results have it); zoom as for skeleton_primitives.  heat:
     None, or 'pd' / 'sm': the maps of that stage tinted under the skeleton (JOINT_RGB's colours; needs predict_images(keep_maps=True)).
     timing: a dict that receives 'render_ms', the device-event time of the render calls summed over the batches (uploads and the read-back
     are not part of it)."""
