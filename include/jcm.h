@@ -634,7 +634,9 @@ int64_t jcm_workspace_bytes(jcm_handle h);
  *   jcm_train_loss_grads : forward with batch-statistics BatchNorm (is_training=True, main.py:113,129;
  *       the moving_mean / moving_variance update ops of main.py:557 run here, decay 0.9), loss_tower =
  *       CE(pd) + CE(sm) + lmbd * weight_decay('weights') (main.py:538-540), and opt.compute_gradients
- *       (main.py:560) into one flat caller-owned buffer laid out by jcm_train_param_info.
+ *       (main.py:560) into one flat caller-owned buffer laid out by jcm_train_param_info.  The advanced moving statistics are in the
+ *       parameter store at once (jcm_get_tensor), but the folded BatchNorm tables the inference entry points read are rebuilt only by
+ *       jcm_train_apply / jcm_update_tensor(refresh != 0): until then inference on the handle is bit-identical to inference before the call.
  *   jcm_train_apply      : grad_renorm(., clip_norm) = tf.clip_by_global_norm (main.py:302-309,576) and
  *       opt.apply_gradients (main.py:577) with tf.train.AdamOptimizer (beta 0.9/0.999, eps 1e-8) or
  *       MomentumOptimizer(0.9) (main.py:501-504); then every derived table (packed weights, folded BN,
