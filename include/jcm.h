@@ -550,6 +550,32 @@ int jcm_gather_batch_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, 
 int jcm_augment_train_indexed_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params,
                                  int B, int H, int W, int hh, int hw, float* x_out, float* y_out);
 
+/* -- affine training augmentation: one composed sample of the image, target maps redrawn at the transformed joint cells --------
+ * x [B,H,W,3] device fp32; cells: device int32 [B,10,2], the (row, col) heat-map cell of each channel's joint (data.joint_cells); x_out [B,H,W,3],
+ * y_out [B,h,w,10] device fp32.  colour: HOST fp32 [B,3] = (flip in {0, 1}, delta, factor); geom: HOST float64 [B,12] = the inverse map (a, b, c0, d, e, f0)
+ * followed by the forward map (A, B, C0, D, E, F0) (augmentation.affine_geometry: all trigonometry is done there, none on the device).  Both are read
+ * before the call returns and travel in the kernel arguments, 16 images per launch; the call enqueues on the handle's stream and does not synchronise.
+ * Image: output pixel (q, r) reads the source at xs = (a q + b r) + c0, ys = (d q + e r) + f0, float64, one rounded operation per step as written; x0 =
+ *   floor(xs), fx = xs - x0 (y alike); the four taps (y0 | y0 + 1, x0 | x0 + 1); a tap outside [0, W-1] x [0, H-1] is `pad` itself, a tap inside is
+ *   v = clip(((src + delta) - m_c) * factor + m_c, 0, 1) in float32, m_c the contrast mean of jcm_augment_train (the fixed-order double sum of src + delta
+ *   over the source image, / (H W), rounded to float32); top = (1 - fx) v00 + fx v01, bot alike, out = float32((1 - fy) top + fy bot).  A position that is
+ *   not finite gives `pad`.  Bilinear, not antialiased: a scale below 1 aliases.
+ * Maps: output channel k takes source channel ks = flip ? {3,4,5,0,1,2,7,6,8,9}[k] : k; its cell (r, c) stands for the point (8 c + 3.5, 8 r + 3.5); qx =
+ *   (A x + B y) + C0, qy = (D x + E y) + F0, clamped to [0, W] / [0, H] (NaN -> 0), cell' = (int(qy / 8), int(qx / 8)) -- the rule of data.joint_cells;
+ *   y_out[b, :, :, k] is the 3x3 blob [1,2,1] x [1,2,1] / 16 around cell' cut by the border (row h / column w are possible centres) and 0 elsewhere: bit for
+ *   bit data.target_heat_maps of cell'.  No pow, no renormalisation.
+ * The _indexed entries read image idx[b] of a data set (x_all [N,H,W,3], cells_all [N,10,2]; idx HOST int32 [B] in [0, N), repeats allowed) and equal
+ * jcm_gather_batch followed by jcm_augment_affine bit for bit; _u8 reads a byte data set, every value as float32(k) / float32(255): the bits of the float
+ * entry on the widened data.  JCM_ERR_ARG, with nothing launched or written: null pointers, H != 8 h or W != 8 w, B outside [1, 65535], n_joints != 9, an
+ * index outside [0, N) (its position in the message), a flip that is not 0 or 1, a colour, geom or pad value that is not finite, outputs that overlap an
+ * input or each other.  Uses the workspace arena: JCM_ERR_STATE from the gradient-ready callback of the same handle. */
+int jcm_augment_affine(jcm_handle h, const float* x, const int32_t* cells, const float* colour, const double* geom, int B, int H, int W,
+                       int hh, int hw, float pad, float* x_out, float* y_out);
+int jcm_augment_affine_indexed(jcm_handle h, const float* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
+                               const double* geom, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out);
+int jcm_augment_affine_indexed_u8(jcm_handle h, const uint8_t* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
+                                  const double* geom, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out);
+
 /* -- TensorBoard summaries (tensorboard.py) -------------------------------------------------
  * jcm_tensor_stats: per segment (offset, count) of a flat device fp32 buffer -- or, with data == NULL, of the handle's stored
  *   trainable parameters in the layout of jcm_train_param_info (read in place; a segment must lie inside one tensor) -- the

@@ -50,6 +50,117 @@ def augment_train(engine, x, y, params):
     return engine.augment_train(x, y, pd)
 
 
+# ------------------------------------------------------------------ the affine augmentation (DESIGN.md 4.20; csrc/augment_affine.hip)
+# One composed affine sample of the image (flip, rotation, scale, shift; `pad` outside) and target maps redrawn as the data set's 3x3 blobs at the
+# transformed joint cells.  Not in the reference: its docstring promises "scale [0.5, 1.5]" (augmentation.py:60-61) but its code has the fixed 0.95 crop.
+N_AFFINE_PARAMS = 7                          # (flip, delta, factor, angle, scale, tx, ty)
+# The default ranges are those of the reference's docstring.  They are UNTUNED PLACEHOLDERS: no trained weights and no FLIC images were available to
+# measure what any range buys in detection rate.
+AFFINE_SCALE = (0.5, 1.5)
+AFFINE_SHIFT = 0.0
+
+
+def draw_affine_params(rng, B, scale=AFFINE_SCALE, max_angle=MAX_ROTATE_ANGLE, shift=AFFINE_SHIFT):
+    """[B, 7] float64 = (flip, delta, factor, angle, scale, tx, ty) from one rng.random_sample((B, 7)) draw: flip, delta and factor in the ranges of
+    draw_params, angle uniform in +-max_angle, scale uniform in [lo, hi], tx / ty uniform in +-shift as fractions of the frame width / height."""
+    lo, hi = float(scale[0]), float(scale[1])
+    max_angle, shift = float(max_angle), float(shift)
+    if not (0 < lo <= hi) or not np.isfinite(hi):
+        raise ValueError('scale must be (lo, hi) with 0 < lo <= hi, got %r' % (scale,))
+    if not (0 <= shift < 0.5):
+        raise ValueError('shift must be in [0, 0.5), got %r' % (shift,))
+    if not (0 <= max_angle <= np.pi):
+        raise ValueError('max_angle must be in [0, pi], got %r' % (max_angle,))
+    u = rng.random_sample((int(B), N_AFFINE_PARAMS))
+    p = np.empty_like(u)
+    p[:, 0] = u[:, 0] > 0.5
+    p[:, 1] = -MAX_BRIGHTNESS_DELTA + u[:, 1] * (2 * MAX_BRIGHTNESS_DELTA)
+    p[:, 2] = CONTRAST_LOWER + (CONTRAST_UPPER - CONTRAST_LOWER) * u[:, 2]
+    p[:, 3] = -max_angle + u[:, 3] * (2 * max_angle)
+    p[:, 4] = lo + u[:, 4] * (hi - lo)
+    p[:, 5] = -shift + u[:, 5] * (2 * shift)
+    p[:, 6] = -shift + u[:, 6] * (2 * shift)
+    return p
+
+
+def affine_geometry(params, H, W):
+    """params [B, 7] (draw_affine_params) for H x W images -> (colour float32 [B, 3] = (flip, delta, factor), geom float64 [B, 12]).
+
+    geom[:, :6] = (a, b, c0, d, e, f0), the inverse map: output pixel (q, r) reads the source at xs = a q + b r + c0, ys = d q + e r + f0, which is
+        u = q - cx - tx W,  v = r - cy - ty H,  xs = cx + (c u + s v) / scale,  ys = cy + (-s u + c v) / scale,  with flip xs <- (W - 1) - xs
+    (cx, cy = (W - 1) / 2, (H - 1) / 2; c, s = cos, sin of the angle) folded into six numbers.
+    geom[:, 6:] = (A, B, C0, D, E, F0), the forward map of a source point (x, y) to its output position qx = A x + B y + C0, qy = D x + E y + F0: the same
+    steps undone in reverse order, in closed form -- not a numerical matrix inversion.  All trigonometry of the augmentation happens here, in float64."""
+    p = np.asarray(params, np.float64)
+    if p.ndim != 2 or p.shape[1] != N_AFFINE_PARAMS or p.shape[0] < 1:
+        raise ValueError('affine parameters must be [B, %d], got shape %s' % (N_AFFINE_PARAMS, p.shape))
+    H, W = int(H), int(W)
+    flip, ang, sc, tx, ty = p[:, 0] == 1.0, p[:, 3], p[:, 4], p[:, 5], p[:, 6]
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    c, s = np.cos(ang), np.sin(ang)
+    ox, oy = cx + tx * W, cy + ty * H                 # where the source's centre lands in the output
+    g = np.empty((p.shape[0], 12), np.float64)
+    a, b, c0 = c / sc, s / sc, cx - (c * ox + s * oy) / sc
+    g[:, 0] = np.where(flip, -a, a)
+    g[:, 1] = np.where(flip, -b, b)
+    g[:, 2] = np.where(flip, (W - 1) - c0, c0)
+    g[:, 3] = (-s) / sc
+    g[:, 4] = c / sc
+    g[:, 5] = cy - ((-s) * ox + c * oy) / sc
+    A, D = sc * c, sc * s
+    C0, F0 = ox - sc * (c * cx - s * cy), oy - sc * (s * cx + c * cy)
+    g[:, 6] = np.where(flip, -A, A)
+    g[:, 7] = -(sc * s)
+    g[:, 8] = np.where(flip, C0 + A * (W - 1), C0)
+    g[:, 9] = np.where(flip, -D, D)
+    g[:, 10] = sc * c
+    g[:, 11] = np.where(flip, F0 + D * (W - 1), F0)
+    return np.ascontiguousarray(p[:, :3], np.float32), g
+
+
+def check_affine(colour, geom):
+    """Host-side check of (colour [B, 3], geom [B, 12]): shapes, finite, flip 0 or 1, both maps non-singular.  Returns them as contiguous float32 / float64
+    arrays; raises ValueError."""
+    col, g = np.asarray(colour, dtype=np.float32), np.asarray(geom, dtype=np.float64)
+    if col.ndim != 2 or col.shape[1] != 3 or col.shape[0] < 1:
+        raise ValueError('affine colour parameters must be [B, 3], got shape %s' % (col.shape,))
+    if g.ndim != 2 or g.shape[1] != 12 or g.shape[0] != col.shape[0]:
+        raise ValueError('affine geometry must be [%d, 12] for %d colour rows, got shape %s' % (col.shape[0], col.shape[0], g.shape))
+    if not np.isfinite(col).all() or not np.isfinite(g).all():
+        raise ValueError('affine parameters must be finite')
+    if not np.isin(col[:, 0], (0.0, 1.0)).all():
+        raise ValueError('affine parameter flip (colour column 0) must be 0 or 1')
+    det_inv, det_fwd = g[:, 0] * g[:, 4] - g[:, 1] * g[:, 3], g[:, 6] * g[:, 10] - g[:, 7] * g[:, 9]
+    with np.errstate(over='ignore', invalid='ignore'):
+        if not (np.isfinite(det_inv) & (det_inv != 0) & np.isfinite(det_fwd) & (det_fwd != 0)).all():
+            raise ValueError('affine geometry is singular (a map with determinant 0)')
+    return np.ascontiguousarray(col), np.ascontiguousarray(g)
+
+
+class AffineDraw:
+    """One batch's draw of the affine augmentation: colour [B, 3], geom [B, 12] (affine_geometry) and the pad value -- what Trainer.train_step(augment=)
+    takes besides the [B, 6] array of the reference's augmentation.  draw[lo:hi] is the draw of a tower's slice of the batch."""
+
+    def __init__(self, colour, geom, pad=0.0):
+        self.colour, self.geom = check_affine(colour, geom)
+        self.pad = float(pad)
+        if not np.isfinite(self.pad):
+            raise ValueError('pad must be finite, got %r' % (pad,))
+
+    def __len__(self):
+        return self.colour.shape[0]
+
+    def __getitem__(self, s):
+        if not isinstance(s, slice):
+            raise TypeError('an AffineDraw is sliced by image ranges, got %r' % (s,))
+        return AffineDraw(self.colour[s], self.geom[s], self.pad)
+
+
+def draw_affine(rng, B, H, W, pad=0.0, **ranges):
+    """AffineDraw for B images of H x W: draw_affine_params(rng, B, **ranges) through affine_geometry."""
+    return AffineDraw(*affine_geometry(draw_affine_params(rng, B, **ranges), H, W), pad=pad)
+
+
 def augment_test(x, y):
     """augmentation.py:81-90: the identity."""
     return x, y

@@ -52,20 +52,21 @@ def joint_cells(xy):
     return cells
 
 
-def target_heat_maps(cells):
+def target_heat_maps(cells, hm_h=HM_H, hm_w=HM_W):
     """cells [n,10,2] -> y [n,60,90,10] float32: the 3x3 binomial blob centred on each joint's cell,
-    clipped at the map border (the reference pastes into a 5-cell padded map and crops, data.py:176-183)."""
+    clipped at the map border (the reference pastes into a 5-cell padded map and crops, data.py:176-183).
+    hm_h, hm_w: another map size (the affine augmentation redraws these maps at any image size)."""
     cells = np.asarray(cells)
     n = cells.shape[0]
     m = 2                                                 # margin: a centre may sit on row 60 / column 90 (clamp to 480 / 720)
-    y = np.zeros((n, HM_H + 2 * m, HM_W + 2 * m, cells.shape[1]), np.float32)
+    y = np.zeros((n, hm_h + 2 * m, hm_w + 2 * m, cells.shape[1]), np.float32)
     for i in range(n):
         for k in range(cells.shape[1]):
             r, c = int(cells[i, k, 0]), int(cells[i, k, 1])
-            if not (0 <= r <= HM_H and 0 <= c <= HM_W):
+            if not (0 <= r <= hm_h and 0 <= c <= hm_w):
                 raise ValueError('cell (%d, %d) outside the clamped range' % (r, c))
             y[i, r - 1 + m:r + 2 + m, c - 1 + m:c + 2 + m, k] = BLOB
-    return np.ascontiguousarray(y[:, m:HM_H + m, m:HM_W + m])
+    return np.ascontiguousarray(y[:, m:hm_h + m, m:hm_w + m])
 
 
 def load_flic(mat_path):

@@ -92,9 +92,13 @@ class DeviceDataset:
     x, y: numpy arrays, np.memmap or paths of .npy files (opened memory-mapped).  rows: optional row subset (the --debug
     selection), taken in the order given.  chunk_rows: rows per staging buffer (default: DEFAULT_CHUNK_BYTES worth of images).
     budget_bytes: the device memory the set may take; default: what torch.cuda.mem_get_info reports free, less reserve_bytes
-    (room the engines have not claimed yet: workspace, the filter-spectra cache)."""
+    (room the engines have not claimed yet: workspace, the filter-spectra cache).
+    cells: optional integers [N,K+1,2], the (row, col) heat-map cell of every channel's joint (data.joint_cells), indexed like x and y (`rows` selects from
+    them too) -> `.cells`, int32 on the device, read by the affine augmentation (Engine.augment_affine_indexed).  Without it `.cells` is derived once at
+    upload as the arg-max cell of each map (the first maximum): exact for a whole blob, but a blob cut by the border -- a joint clamped to row h or
+    column w -- has lost its true centre, and only passing `cells` keeps it."""
 
-    def __init__(self, x, y, device=0, rows=None, chunk_rows=None, budget_bytes=None, reserve_bytes=0, image_dtype='float32'):
+    def __init__(self, x, y, device=0, rows=None, chunk_rows=None, budget_bytes=None, reserve_bytes=0, image_dtype='float32', cells=None):
         if image_dtype not in ('float32', 'uint8'):
             raise ValueError("image_dtype must be 'float32' or 'uint8', got %r" % (image_dtype,))
         self.image_dtype = image_dtype
@@ -105,6 +109,13 @@ class DeviceDataset:
             rows = np.asarray(rows, np.int64).reshape(-1)
             if rows.size and (rows.min() < 0 or rows.max() >= x.shape[0]):
                 raise IndexError('rows outside [0, %d)' % x.shape[0])
+        if cells is not None:
+            cells = np.asarray(cells)
+            if cells.shape != (x.shape[0], y.shape[3], 2) or cells.dtype.kind not in 'iu':
+                raise ValueError('cells must be integers [N,%d,2] = (row, col) per example of x and channel of y; got %s %s' % (y.shape[3], cells.shape, cells.dtype))
+            if cells.size and (cells.min() < 0 or cells[..., 0].max() > y.shape[1] or cells[..., 1].max() > y.shape[2]):
+                raise ValueError('cells outside [0, %d] x [0, %d] (data.joint_cells clamps to the image, so row h / column w are the last)' % (y.shape[1], y.shape[2]))
+            cells = np.ascontiguousarray(cells if rows is None else cells[rows], np.int32)
         self.n = int(x.shape[0] if rows is None else rows.size)
         if self.n < 1:
             raise ValueError('DeviceDataset needs at least one example')
@@ -131,6 +142,24 @@ class DeviceDataset:
                 self._upload(src, dst, rows, chunk_rows, stream)
             stream.synchronize()         # one-off: afterwards the tensors are safe to read from any stream
             self.upload_seconds = time.perf_counter() - t0
+            # .cells int32 [N,K+1,2]: the (row, col) heat-map cell of every channel's joint, which the affine augmentation transforms (8 bytes
+            # per map, not counted in nbytes).  Given as `cells` (data.joint_cells) they are exact.  Derived, they are the arg-max cell of each map, the first
+            # maximum as in jcm_argmax_coords -- which for a blob cut by the border (a centre on row h or column w) is a neighbour of the true centre.
+            self.cells = torch.as_tensor(cells, device=self.device) if cells is not None else self._argmax_cells(self.y)
+
+    @staticmethod
+    def _argmax_cells(y, chunk_bytes=64 << 20):
+        """int32 [N,C,2] = (row, col) of the first maximum of every map of y [N,h,w,C], in slices of chunk_bytes of y."""
+        n, h, w, ch = y.shape
+        out = torch.empty((n, ch, 2), dtype=torch.int32, device=y.device)
+        pos = torch.arange(h * w, dtype=torch.int32, device=y.device).view(1, h * w, 1)
+        step = max(1, chunk_bytes // (4 * h * w * ch))
+        for lo in range(0, n, step):
+            part = y[lo:lo + step].reshape(-1, h * w, ch)
+            first = torch.where(part == part.amax(dim=1, keepdim=True), pos, h * w).amin(dim=1)      # [n', C]: the lowest index that holds the maximum
+            out[lo:lo + step, :, 0] = torch.div(first, w, rounding_mode='floor')
+            out[lo:lo + step, :, 1] = first % w
+        return out
 
     @staticmethod
     def _upload(src, dst, rows, chunk_rows, stream):

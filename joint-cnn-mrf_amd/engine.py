@@ -877,6 +877,76 @@ class Engine:
                       self._p(params), idx.shape[0], H, W, y_all.shape[1], y_all.shape[2], self._p(x_out), self._p(y_out)), what)
         return x_out, y_out
 
+    # ------------------------------------------------------------------ the affine augmentation (augmentation.py)
+    def _affine_call(self, who, x, cells, idx, colour, geom, pad, x_out, y_out):
+        """The checks and the call the two affine entries share; idx None: image b of x / cells itself."""
+        from .augmentation import check_affine
+        u8 = self._chk_img(x, 'x_all' if idx is not None else 'x')
+        self._chk(cells, 3, 'cells', torch.int32)
+        N, H, W, C = x.shape
+        if u8 and idx is None:
+            raise TypeError('%s: x must be float32 (byte images are read through an index: augment_affine_indexed)' % who)
+        if C != 3 or tuple(cells.shape) != (N, 10, 2) or N < 1 or self.n_joints != 9:
+            raise ValueError('%s expects x [N,H,W,3] and cells [N,10,2] on an engine with n_joints == 9; got %s, %s, n_joints = %d'
+                             % (who, tuple(x.shape), tuple(cells.shape), self.n_joints))
+        if H % 8 or W % 8:
+            raise ValueError('%s: images of %d x %d; a heat-map cell is 8 x 8 pixels, H and W must be multiples of 8' % (who, H, W))
+        if idx is not None:
+            if isinstance(idx, torch.Tensor):
+                if idx.device.type != 'cpu':
+                    raise ValueError('%s: idx is a host array (it is checked on the host and travels in the kernel arguments), got a tensor on %s' % (who, idx.device))
+                idx = idx.numpy()
+            idx = np.asarray(idx)
+            if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in 'iu':
+                raise ValueError('%s: idx must be a non-empty 1-D integer array, got shape %s dtype %s' % (who, idx.shape, idx.dtype))
+            if idx.dtype != np.int32:
+                if int(idx.min()) < -2 ** 31 or int(idx.max()) >= 2 ** 31:
+                    raise ValueError('%s: idx does not fit int32' % who)
+                idx = idx.astype(np.int32)
+            idx = np.ascontiguousarray(idx)
+        B = N if idx is None else idx.shape[0]
+        colour, geom = check_affine(colour, geom)
+        if colour.shape[0] != B:
+            raise ValueError('%s: %d parameter rows for a batch of %d' % (who, colour.shape[0], B))
+        hh, hw = H // 8, W // 8
+        x_out = self._new(B, H, W, 3) if x_out is None else self._chk(x_out, 4, 'x_out')
+        y_out = self._new(B, hh, hw, 10) if y_out is None else self._chk(y_out, 4, 'y_out')
+        if tuple(x_out.shape) != (B, H, W, 3) or tuple(y_out.shape) != (B, hh, hw, 10):
+            raise ValueError('x_out / y_out must be [%d,%d,%d,3] and [%d,%d,%d,10]; got %s, %s' % (B, H, W, B, hh, hw, tuple(x_out.shape), tuple(y_out.shape)))
+        self._on_stream(x, cells, x_out, y_out)
+        cp, gp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        if idx is None:
+            status, what = self._lib.jcm_augment_affine(self._h, self._p(x), self._p(cells), cp, gp, B, H, W, hh, hw, float(pad),
+                                                        self._p(x_out), self._p(y_out)), 'jcm_augment_affine'
+        else:
+            fn, what = ((self._lib.jcm_augment_affine_indexed_u8, 'jcm_augment_affine_indexed_u8') if u8
+                        else (self._lib.jcm_augment_affine_indexed, 'jcm_augment_affine_indexed'))
+            status = fn(self._h, self._p(x), self._p(cells), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, gp, B, H, W, hh, hw, float(pad),
+                        self._p(x_out), self._p(y_out))
+        _lib.check(status, what)
+        return x_out, y_out
+
+    def augment_affine(self, x, cells, colour, geom, pad=0.0, x_out=None, y_out=None):
+        """The affine augmentation: x [B,H,W,3] device fp32, cells [B,10,2] device int32 = the (row, col) heat-map cell of every channel's
+        joint, colour [B,3] / geom [B,12] HOST arrays (augmentation.affine_geometry), pad the value outside the source -> (x_out [B,H,W,3], y_out
+        [B,H/8,W/8,10]), new tensors unless given: one bilinear sample of the image through the inverse map, the targets redrawn as 3x3 blobs at the cells
+        the forward map sends the joints to.  Enqueued on the engine's stream; the host does not wait."""
+        return self._affine_call('augment_affine', x, cells, None, colour, geom, pad, x_out, y_out)
+
+    def augment_affine_indexed(self, x_all, cells_all, idx, colour, geom, pad=0.0, x_out=None, y_out=None):
+        """augment_affine of the images idx[b] of the data set (x_all [N,H,W,3], cells_all [N,10,2]) read through the index: the same bits as gather_batch
+        followed by augment_affine, without the gathered copy.  x_all may be uint8 (a byte data set): the same bits as from the float data set
+        float32(x_all) / float32(255)."""
+        return self._affine_call('augment_affine_indexed', x_all, cells_all, idx, colour, geom, pad, x_out, y_out)
+
+    def joint_cells(self, y):
+        """y [B,h,w,K+1] target maps -> int32 [B,K+1,2], the (row, col) of every channel's arg-max cell (the first maximum, as jcm_argmax_coords picks it): the
+        cells the affine augmentation transforms when the data set did not keep them.  A blob cut by the border loses its true centre this way."""
+        self._chk(y, 4, 'y')
+        self._on_stream(y)
+        with torch.cuda.stream(self._stream):      # the coordinates are written on the engine's stream
+            return self.argmax_coords(y).permute(0, 2, 1).contiguous()
+
     # ------------------------------------------------------------------ TensorBoard summaries (summary.py, DESIGN.md 4.8)
     def _on_stream(self, *ts):
         cur = torch.cuda.current_stream(self.device)

@@ -108,6 +108,16 @@ def build_parser():
                         'frame in heat-map cells, one value or one per joint (default 1.5, an untuned placeholder).')
     parser.add_argument('--seq_rho', type=float, default=None, metavar='RHO', help='with --sequence: the mass in [0,1] of the uniform "anywhere" term that absorbs '
                         'misses and scene cuts (default 0.05, an untuned placeholder).')
+    parser.add_argument('--augm_affine', action='store_true', help='--train: augment every batch on the device with one composed affine sample of the image -- '
+                        'flip, brightness, contrast, a rotation of up to 20 degrees, scale and shift -- and targets redrawn as 3x3 blobs at the transformed joint '
+                        'cells (Engine.augment_affine, DESIGN.md 4.20; drawn from --seed + 1).  Not the reference\'s --data_augm.  What it buys in detection rate '
+                        'has not been measured.')
+    parser.add_argument('--augm_scale', type=float, nargs=2, default=None, metavar=('LO', 'HI'), help='with --augm_affine: the scale is uniform in [LO, HI], '
+                        '0 < LO <= HI (default 0.5 1.5, the range of the reference\'s docstring: an untuned placeholder).')
+    parser.add_argument('--augm_shift', type=float, default=None, metavar='F', help='with --augm_affine: the shift is uniform in +-F of the frame width and height, '
+                        '0 <= F < 0.5 (default 0, an untuned placeholder).')
+    parser.add_argument('--augm_pad', type=float, default=None, metavar='V', help='with --augm_affine: the value of the pixels outside the source image, 0 <= V <= 1 '
+                        '(default 0).')
     parser.add_argument('--seed', type=int, default=0, help='shuffling seed.')
     parser.add_argument('--device_data', action='store_true', help='--train: upload the train and test sets to device memory once and gather the batches there '
                         '(DESIGN.md 4.9); an error if they do not fit.')
@@ -312,7 +322,9 @@ SEQUENCE_ONE_PERSON = '--sequence tracks one person: --people M > 1 would need a
 SEQ_OPTION_NEEDS_SEQUENCE = '--seq_sigma and --seq_rho set the motion model of --sequence: give --sequence filter or --sequence viterbi as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
-TB_ACTIVATIONS_NEEDS_TB_DIR = '--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
+AUGM_AFFINE_NEEDS_TRAIN = '--augm_affine augments the batches of a training run: give --train as well'
+AUGM_OPTION_NEEDS_AUGM_AFFINE = '--augm_scale, --augm_shift and --augm_pad set the ranges of --augm_affine: give --augm_affine as well'
+TB_ACTIVATIONS_NEEDS_TB_DIR ='--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
 TB_ACTIVATIONS_IS_FP32 = ('--tb_activations: the pre-activation summaries are taken in fp32, as the reference takes them, and the bf16 kernels have no '
                           'linear epilogue; run it with --precision fp32')
 
@@ -372,20 +384,30 @@ class TowerTrainer:
     common start, so the composition is rebuilt from the per-replica results and written to every replica."""
     BN_DECAY = 0.9          # decay=0.9 of the reference's tf.contrib.layers.batch_norm calls (main.py:113,129)
 
-    def __init__(self, towers, params, augment_rng=None, **trainer_kw):
+    def __init__(self, towers, params, augment_rng=None, augment_kind='reference', affine_kw=None, **trainer_kw):
         from .train import Trainer
+        if augment_kind not in ('reference', 'affine'):
+            raise ValueError("augment_kind must be 'reference' or 'affine', got %r" % (augment_kind,))
+        if affine_kw and augment_kind != 'affine':
+            raise ValueError("affine_kw belongs to augment_kind='affine'")
         self.towers = towers
         self.augment_rng = augment_rng      # numpy RandomState: augment every step (main.py:494-497), parameters drawn for the global batch
+        self.augment_kind = augment_kind    # 'reference': augmentation.draw_params (DESIGN.md 4.7); 'affine': augmentation.draw_affine (DESIGN.md 4.20)
+        self.affine_kw = dict(affine_kw or {})      # pad, scale, max_angle, shift of augmentation.draw_affine
         self.trainers = [Trainer(e, **trainer_kw) for e in towers.engines]
         self.moving = {k: np.asarray(v, np.float32).reshape(-1).copy() for k, v in params.items()
                        if k.endswith('moving_mean') or k.endswith('moving_variance')}
 
+    def _draw(self, B, H, W):
+        """The augmentation draw of one global batch, or None: made before the towers slice the batch, so the images are the same for any tower count."""
+        if self.augment_rng is None:
+            return None
+        from .augmentation import draw_affine, draw_params
+        return draw_affine(self.augment_rng, B, H, W, **self.affine_kw) if self.augment_kind == 'affine' else draw_params(self.augment_rng, B)
+
     def train_step(self, x, y):
         tw = self.towers
-        aug = None
-        if self.augment_rng is not None:
-            from .augmentation import draw_params
-            aug = draw_params(self.augment_rng, x.shape[0])        # before the towers slice the batch: the same images for any tower count
+        aug = self._draw(x.shape[0], x.shape[1], x.shape[2])
         for tr, eng, (lo, hi) in zip(self.trainers, tw.engines, tw.slices(x.shape[0])):
             xs = torch.as_tensor(x[lo:hi]).to(eng.device, non_blocking=True).contiguous()
             ys = torch.as_tensor(y[lo:hi]).to(eng.device, non_blocking=True).contiguous()
@@ -399,10 +421,8 @@ class TowerTrainer:
         own device -- with augment_rng through the indexed augmentation, the parameters drawn for the global batch as in train_step."""
         tw = self.towers
         idx = np.asarray(idx).reshape(-1)
-        aug = None
-        if self.augment_rng is not None:
-            from .augmentation import draw_params
-            aug = draw_params(self.augment_rng, idx.shape[0])
+        ds0 = next(iter(datasets.values())) if isinstance(datasets, dict) else datasets
+        aug = self._draw(idx.shape[0], ds0.x.shape[1], ds0.x.shape[2])
         for tr, eng, (lo, hi) in zip(self.trainers, tw.engines, tw.slices(idx.shape[0])):
             ds = datasets[eng.device] if isinstance(datasets, dict) else datasets
             if ds.device != eng.device:
@@ -497,7 +517,11 @@ def train_main(args):
     n_updates_total = args.n_epochs * n_train // args.batch_size        # main.py:466
     params, state = run_params(args, pairwise)
     towers = Towers(params, args.gpus, precision=args.precision)
-    tt = TowerTrainer(towers, params, optimizer=args.optimizer, lr=args.lr, lmbd=args.lmbd, use_sm=args.use_sm, n_updates_total=n_updates_total)
+    augm = {}
+    if args.augm_affine:      # drawn from a generator of its own: the batches are those of the run without it
+        kw = {'scale': args.augm_scale, 'shift': args.augm_shift, 'pad': args.augm_pad}
+        augm = dict(augment_rng=np.random.RandomState(args.seed + 1), augment_kind='affine', affine_kw={k: v for k, v in kw.items() if v is not None})
+    tt = TowerTrainer(towers, params, optimizer=args.optimizer, lr=args.lr, lmbd=args.lmbd, use_sm=args.use_sm, n_updates_total=n_updates_total, **augm)
     if state:
         for tr in tt.trainers:
             checkpoint.restore_session_state(tr, state)
@@ -603,13 +627,22 @@ SEQUENCE_RULES = (
     (lambda a: a.sequence and a.people != 1, SEQUENCE_ONE_PERSON),
     (lambda a: (a.seq_sigma is not None or a.seq_rho is not None) and not a.sequence, SEQ_OPTION_NEEDS_SEQUENCE),
 )
+# The rules of --augm_affine, walked behind SEQUENCE_RULES (a table of their own for the same reason).  --data_augm stays refused where it always was, in train_main.
+AUGM_RULES = (
+    (lambda a: a.augm_affine and not a.train, AUGM_AFFINE_NEEDS_TRAIN),
+    (lambda a: (a.augm_scale is not None or a.augm_shift is not None or a.augm_pad is not None) and not a.augm_affine, AUGM_OPTION_NEEDS_AUGM_AFFINE),
+    (lambda a: a.augm_scale is not None and not 0 < a.augm_scale[0] <= a.augm_scale[1] < float('inf'),
+     lambda a: '--augm_scale %g %g: 0 < LO <= HI' % tuple(a.augm_scale)),
+    (lambda a: a.augm_shift is not None and not 0 <= a.augm_shift < 0.5, lambda a: '--augm_shift %g: 0 <= F < 0.5' % a.augm_shift),
+    (lambda a: a.augm_pad is not None and not 0 <= a.augm_pad <= 1, lambda a: '--augm_pad %g: 0 <= V <= 1' % a.augm_pad),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .augmentation import AffineDraw
 
 CLIP_NORM = 4.0      # main.py:576
 
@@ -61,6 +62,7 @@ class Trainer:
                    'jcm_train_set_grad_callback')
         self.losses = torch.zeros(4, dtype=torch.float32, device=engine.device)
         self._aug = None                                            # (x, y, params) buffers of the augmented batch (loss_and_grads(augment=))
+        self._aff = None                                            # (x, y) buffers of the affinely augmented batch (augment=AffineDraw)
         self._gat = None                                            # (x, y) buffers of the gathered batch (loss_and_grads_indexed)
         self.last_batch = None                                      # the device batch (x, y) the last step trained on
 
@@ -79,7 +81,9 @@ class Trainer:
     def loss_and_grads(self, x, y, augment=None):
         """x [B,H,W,3], y [B,hh,ww,K+1] (hh x ww = heat_map_size(H, W): 60x90 for 480x720) -> (losses[4] device tensor, flat grads device tensor).
         losses = (loss_tower, loss_pd, loss_sm, weight_decay).  `augment`: None, or a host [B,6] array of augmentation
-        parameters (augmentation.draw_params): the step trains on the augmented copy of (x, y) (main.py:494-497)."""
+        parameters (augmentation.draw_params): the step trains on the augmented copy of (x, y) (main.py:494-497); or an
+        augmentation.AffineDraw: the step trains on the affine sample of x and on targets redrawn at the transformed arg-max cells of y
+        (DESIGN.md 4.20)."""
         e = self.eng
         e._chk(x, 4, 'x')
         e._chk(y, 4, 'y')
@@ -88,7 +92,10 @@ class Trainer:
         if C != 3 or tuple(y.shape) != (B, hh, ww, e.n_joints + 1):      # the kernels read y as [B,hh,ww,K+1]: another size would be read past its end
             raise ValueError('x must be [B,H,W,3] and y [B,%d,%d,%d] (the heat-map size of the image); got %s, %s'
                              % (hh, ww, e.n_joints + 1, tuple(x.shape), tuple(y.shape)))
-        if augment is not None:
+        if isinstance(augment, AffineDraw):
+            xa, ya = self._aff_buffers(x.shape, y.shape, augment)
+            x, y = e.augment_affine(x, e.joint_cells(y), augment.colour, augment.geom, augment.pad, xa, ya)
+        elif augment is not None:
             x, y = self._augmented(x, y, augment)
         return self._loss_and_grads(x, y)
 
@@ -122,6 +129,15 @@ class Trainer:
             pd.copy_(torch.from_numpy(p).pin_memory(), non_blocking=True)
         return xa, ya, pd
 
+    def _aff_buffers(self, shape_x, shape_y, draw):
+        """(x, y) buffers of the affinely augmented batch, kept across steps of the same shapes (the draw itself travels in the kernel arguments)."""
+        if len(draw) != shape_x[0]:
+            raise ValueError('augment has %d parameter rows for a batch of %d' % (len(draw), shape_x[0]))
+        if self._aff is None or tuple(self._aff[0].shape) != tuple(shape_x) or tuple(self._aff[1].shape) != tuple(shape_y):
+            dev = self.eng.device
+            self._aff = (torch.empty(tuple(shape_x), dtype=torch.float32, device=dev), torch.empty(tuple(shape_y), dtype=torch.float32, device=dev))
+        return self._aff
+
     def _augmented(self, x, y, augment):
         """The augmented copy of (x, y) in buffers the trainer owns (kept across steps of the same shapes)."""
         xa, ya, pd = self._aug_buffers(x.shape, y.shape, augment)
@@ -139,7 +155,12 @@ class Trainer:
             raise ValueError('the data set must hold x [N,H,W,3] and y [N,%d,%d,%d] (the heat-map size of the image); got %s, %s'
                              % (hh, ww, e.n_joints + 1, tuple(dataset.x.shape), tuple(dataset.y.shape)))
         shape_x, shape_y = (B, H, W, 3), (B, hh, ww, e.n_joints + 1)
-        if augment is not None:
+        if isinstance(augment, AffineDraw):
+            if getattr(dataset, 'cells', None) is None:
+                raise ValueError('the affine augmentation reads the joint cells of the data set: it must have .cells [N,10,2] (dataset.DeviceDataset)')
+            xa, ya = self._aff_buffers(shape_x, shape_y, augment)
+            x, y = e.augment_affine_indexed(dataset.x, dataset.cells, idx, augment.colour, augment.geom, augment.pad, xa, ya)
+        elif augment is not None:
             xa, ya, pd = self._aug_buffers(shape_x, shape_y, augment)
             x, y = e.augment_train_indexed(dataset.x, dataset.y, idx, pd, xa, ya)
         else:
@@ -356,7 +377,7 @@ class Trainer:
     def train_step(self, x, y, want_norm=False, moving=None, augment=None):
         """One sess.run(train_step) (main.py:644).  Returns (losses tensor, grad norm or None).
         `moving`: [(name, count)] of the BN moving statistics to keep in sync across ranks (N > 1).
-        `augment`: host [B,6] augmentation parameters or None (loss_and_grads)."""
+        `augment`: host [B,6] augmentation parameters, an augmentation.AffineDraw or None (loss_and_grads)."""
         self.loss_and_grads(x, y, augment=augment)
         self.average_gradients()
         norm = self.apply(want_norm=want_norm)
