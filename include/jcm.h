@@ -356,6 +356,33 @@ int jcm_seq_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, 
 int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
                     int32_t* path, double* maxes, int32_t* breaks);
 
+/* -- several tracks through single-channel maps: one torso track per person of a clip ----------
+ * hm: device fp32 [S,T,HH,WW], one non-negative channel (the torso probabilities of the frames); M in 1..4 tracks; taps HOST [2R+1], R and rho as for
+ * jcm_seq_* with one tap row; D in 0..64, the exclusion half-width in cells.
+ * For track n = 0 .. M-1, in this order, per clip s:
+ *   observation of pass n:  p(n)_t(y,x) = 0 if, for some earlier track m < n with value[s,m,t] > 0, max(|y - y_{m,t}|, |x - x_{m,t}|) <= D,
+ *                           where (y_{m,t}, x_{m,t}) is track m's cell of frame t;  otherwise p(n)_t(y,x) = hm[s,t,y,x].
+ *   On p(n) runs EXACTLY the recurrence of jcm_seq_viterbi (resp. jcm_seq_filter) at K = 1 as stated above: its arithmetic, tie rules,
+ *   breaks / resets and backtrace (the library has one copy of it).  The track's cell of frame t is the path's (resp. the filter's arg-max).
+ *   value[s,n,t] = p(n)_t at the track's cell of frame t -- so an earlier track excludes nothing in a frame where it has no support itself.
+ * For n = 0 nothing is excluded: track 0 is, bit for bit, jcm_seq_viterbi / jcm_seq_filter on hm viewed as [S,T,HH,WW,1].  Identity is stable by
+ * construction (a track is one run of the temporal model), and a torso that fades for a few frames is bridged by the motion model and rho.
+ * Viterbi outputs (device): path int32 [S,M,T,2] (row, col), required;  maxes float64 [S,M,T], breaks int32 [S,M,T], may be NULL;  value fp32
+ *   [S,M,T], required.
+ * Filter outputs (device): coords int32 [S,M,T,2], required (pass n reads the cells of the passes < n of the same frames);  norm float64 [S,M,T],
+ *   reset int32 [S,M,T], may be NULL;  value fp32 [S,M,T], required;  state_in / state_out float64 [S,M,HH*WW], the beliefs before frame 0 /
+ *   after frame T-1, either may be NULL, two distinct buffers: a clip fed in pieces gives the bits of one call;  filtered fp32 [S,M,T,HH,WW],
+ *   may be NULL.
+ * The exclusion is applied while a frame is staged into LDS; no masked copy of the maps is written.  One work group per clip and pass; the
+ * launches of a call follow each other on the handle's stream without a host synchronisation.  Viterbi's workspace is that of ONE pass (int16
+ * per clip, frame and cell), reused by the next; JCM_ERR_STATE with the bytes it needs in the message when it does not fit.
+ * JCM_ERR_ARG -- nothing is launched and no output is touched -- for what jcm_seq_* refuse (sizes below 1, R outside 0..16, rho outside [0,1],
+ * HH * WW > 8192, S * T * 4 >= 2^31), M outside 1..4, D outside 0..64, and a required pointer that is NULL. */
+int jcm_seq_tracks_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double rho, int D,
+                           int32_t* path, double* maxes, int32_t* breaks, float* value);
+int jcm_seq_tracks_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double rho, int D,
+                          const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, float* value);
+
 /* Torso map from the part detector: the torso cell that the nine part-detector maps and the nine learned priors e_{j|torso} explain best, and the
  * blob at it -- the tenth channel jcm_sm_forward needs, for an image that has no annotation.  Fixed geometry like jcm_pose_decode's:
  * HH = 60, WW = 90, K = 9, 120x180 priors.

@@ -54,6 +54,12 @@ SIGNATURES = {
                                       ctypes.c_int, ctypes.c_double, ctypes.c_void_p, _c_float_p, _c_i32_p, ctypes.c_void_p, _c_i32_p, ctypes.c_void_p]),
     'jcm_seq_viterbi': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                        ctypes.c_int, ctypes.c_double, _c_i32_p, ctypes.c_void_p, _c_i32_p]),
+    'jcm_seq_tracks_viterbi': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_i32_p, ctypes.c_void_p, _c_i32_p,
+                                              _c_float_p]),
+    'jcm_seq_tracks_filter': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, _c_float_p, _c_i32_p,
+                                             ctypes.c_void_p, _c_i32_p, ctypes.c_void_p, _c_float_p]),
     'jcm_torso_infer': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32_p, _c_float_p, _c_i32_p, _c_float_p]),
     'jcm_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    _c_float_p, _c_float_p, _c_i32_p, _c_i32_p]),

@@ -420,6 +420,15 @@ hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, cons
 // amax int32 [S*K][T] (the arg-max of every frame's d).  Two launches: the scan, then the backtrace (one lane per (sequence, joint)).
 hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, int16_t* bp, int32_t* amax,
                        int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
+// ---- seq_tracks.hip : several torso tracks through single-channel maps -------------
+// hm [S,T,HH,WW]; M in 1..4 passes of the scan above at K = 1 (seq_scan.h), pass n with the cells within D of the tracks m < n zeroed while the frame is
+// staged; one work group per clip and pass, the passes in stream order.  taps: DEVICE [2R+1].  Outputs [S,M,..] in the layouts of jcm.h.
+hipError_t seq_tracks_filter(const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double om, double u, int D,
+                             const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, float* value,
+                             hipStream_t st);
+// workspace of ONE pass, reused by the next: bp int16 [S][T][HH*WW], amax int32 [S][T]
+hipError_t seq_tracks_viterbi(const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double om, double u, int D, int16_t* bp,
+                              int32_t* amax, int32_t* path, double* maxes, int32_t* breaks, float* value, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

@@ -8,6 +8,9 @@ import torch
 
 from . import _lib
 
+# The exclusion half-width of seq_tracks in heat-map cells.  An untuned placeholder: no consecutive-frame data is at hand to derive it from.
+SEQ_EXCLUDE = 4
+
 
 def _hm_size(n):
     """Three SAME stride-2 stages (conv1 + two max-pools): ceil(ceil(ceil(n/2)/2)/2)."""
@@ -392,6 +395,54 @@ class Engine:
                                              self._p(out['path']), self._p(out['maxes']), self._p(out['breaks'])), 'jcm_seq_viterbi')
         return {k: v[0] for k, v in out.items()} if single else out
 
+    def seq_tracks(self, hm, people, sigma, rho, radius=None, exclude=SEQ_EXCLUDE, mode='viterbi', state=None, want_filtered=False):
+        """Several consistent tracks through single-channel maps -- one torso per person of a clip (include/jcm.h:
+        jcm_seq_tracks_viterbi / jcm_seq_tracks_filter).  hm [T,HH,WW] or [S,T,HH,WW], non-negative (spatial_softmax of the torso energy);
+        people = M in 1..4; sigma (a scalar), rho and radius as for seq_filter (predict.seq_taps builds the one tap row); exclude = D in 0..64:
+        pass n sees the map with the cells within D (Chebyshev) of every earlier track's cell zeroed, frame by frame, where that track has a
+        positive value -- SEQ_EXCLUDE is an untuned placeholder.  Track 0 is seq_viterbi / seq_filter on the map, bit for bit.
+        mode 'viterbi' returns {'path' int32 [S,M,T,2] (row, col), 'maxes' float64 [S,M,T], 'breaks' int32 [S,M,T], 'value' fp32 [S,M,T]};
+        mode 'filter' takes state (float64 [S,M,HH*WW] or None at a clip's start) and returns {'coords', 'norm', 'reset', 'value' in the same
+        shapes, 'state' float64 [S,M,HH*WW]} and, with want_filtered, 'filtered' fp32 [S,M,T,HH,WW], the beliefs.  Device tensors, without the S axis for a 3-d hm; nothing is read back.  M, D and the map size
+        (HH * WW <= 8192) are checked by the library."""
+        from .predict import seq_radius, seq_taps
+        if mode not in ('filter', 'viterbi'):
+            raise ValueError("mode must be 'filter' or 'viterbi', got %r" % (mode,))
+        if state is not None and mode != 'filter':
+            raise ValueError("state belongs to mode='filter'")
+        if not isinstance(hm, torch.Tensor) or hm.dim() not in (3, 4):
+            raise ValueError('hm must be a device tensor [T,HH,WW] or [S,T,HH,WW]')
+        single = hm.dim() == 3
+        hm4 = self._chk(hm.unsqueeze(0) if single else hm, 4, 'hm')
+        S, T, HH, WW = hm4.shape
+        M, D = int(people), int(exclude)
+        R = seq_radius(sigma) if radius is None else int(radius)
+        if not 0 <= R <= 16:      # before the taps are built; the library checks it again
+            raise ValueError('radius must be in 0..16, got %r' % (radius,))
+        tap_row = seq_taps(sigma, R, 1)
+        taps = tap_row.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        n = max(M, 0)
+        cells, v, f = ('coords', 'norm', 'reset') if mode == 'filter' else ('path', 'maxes', 'breaks')
+        out = {cells: self._new(S, n, T, 2, dtype=torch.int32), v: self._new(S, n, T, dtype=torch.float64), f: self._new(S, n, T, dtype=torch.int32),
+               'value': self._new(S, n, T)}
+        if mode == 'filter':
+            if state is not None:
+                state = self._chk(state.unsqueeze(0) if single and isinstance(state, torch.Tensor) and state.dim() == 2 else state, 3, 'state', torch.float64)
+                if tuple(state.shape) != (S, n, HH * WW):
+                    raise ValueError('state must be [S,M,HH*WW] = %s, got %s' % ((S, n, HH * WW), tuple(state.shape)))
+            out['state'] = self._new(S, n, HH * WW, dtype=torch.float64)
+            if want_filtered:
+                out['filtered'] = self._new(S, n, T, HH, WW)
+            self._on_stream(hm4, *([state] if state is not None else []), *out.values())
+            _lib.check(self._lib.jcm_seq_tracks_filter(self._h, self._p(hm4), S, T, HH, WW, M, taps, R, float(rho), D, self._p(state), self._p(out.get('filtered')),
+                                                       self._p(out['coords']), self._p(out['norm']), self._p(out['reset']), self._p(out['state']),
+                                                       self._p(out['value'])), 'jcm_seq_tracks_filter')
+        else:
+            self._on_stream(hm4, *out.values())
+            _lib.check(self._lib.jcm_seq_tracks_viterbi(self._h, self._p(hm4), S, T, HH, WW, M, taps, R, float(rho), D, self._p(out['path']),
+                                                        self._p(out['maxes']), self._p(out['breaks']), self._p(out['value'])), 'jcm_seq_tracks_viterbi')
+        return {k: t[0] for k, t in out.items()} if single else out
+
     @staticmethod
     def _chk_decode(decode, use_sm, peaks):
         if decode and not (use_sm and 1 <= peaks <= 4):
@@ -435,21 +486,24 @@ class Engine:
                                              self._p(out['torso'])), 'jcm_torso_infer')
         return out
 
-    def torso_sm(self, prob, want_prob=True, people=1, people_threshold=0.0):
+    def torso_sm(self, prob, want_prob=True, people=1, people_threshold=0.0, want_torso_prob=False):
         """The spatial model on part-detector probabilities prob [B,60,90,9] that come without a torso map: torso_infer,
         spatial_model on [prob, torso], softmax_argmax -- what forward(torso='infer') runs behind the part detector.  Returns {'sm_coords',
         'torso_cell' int32 [B,2], 'torso' [B,60,90,1], 'hm10' (the spatial model's input, [B * people,60,90,10])} plus 'sm_prob' (want_prob) and,
         for people = M > 1, 'people' (see forward): the torso candidates are the top-M local maxima of spatial_softmax(E) (hm_peaks, K = 1),
         torso_infer(cells=) writes the B * M blobs and the spatial model runs once on B * M images, image b's probabilities repeated for its M
-        slots; the top-level entries are slot 0."""
+        slots; the top-level entries are slot 0.  want_torso_prob: also 'torso_prob' [B,60,90] = spatial_softmax(E), the map the people's candidates
+        are the maxima of and Engine.seq_tracks tracks; every other entry is what the call without it returns."""
         self._chk(prob, 4, 'prob')
         B, K, M = prob.shape[0], 9, int(people)
         if tuple(prob.shape[1:]) != (60, 90, K) or self.n_joints != K:
             raise ValueError('torso_sm expects prob [B,60,90,9] on an engine with 9 joints; got %s, n_joints = %d' % (tuple(prob.shape), self.n_joints))
         if not 1 <= M <= 4:
             raise ValueError('people must be in 1..4, got %r' % (people,))
-        t = self.torso_infer(prob, want_energy=M > 1)
+        t = self.torso_infer(prob, want_energy=M > 1 or bool(want_torso_prob))
         r = {}
+        if want_torso_prob:
+            r['torso_prob'] = self.spatial_softmax(t['energy'].view(B, 60, 90, 1)).view(B, 60, 90)
         if M == 1:
             with torch.cuda.stream(self._stream):
                 hm10 = torch.cat([prob, t['torso']], dim=3)
@@ -477,13 +531,13 @@ class Engine:
         r['hm10'] = hm10
         return r
 
-    def _forward_infer(self, x, want_prob, peaks, decode, people, people_threshold):
+    def _forward_infer(self, x, want_prob, peaks, decode, people, people_threshold, want_torso_prob=False):
         """forward(torso='infer'): the part detector (the forward without spatial model: the same pd_* bits), then torso_sm on its probabilities."""
         B, M = x.shape[0], people
         if (_hm_size(x.shape[1]), _hm_size(x.shape[2]), self.n_joints) != (60, 90, 9):
             raise ValueError("torso='infer' is defined for 60x90 heat maps (480x720 images) and 9 joints; got x %s, n_joints = %d" % (tuple(x.shape), self.n_joints))
         r = self.forward(x, None, use_sm=False, want_prob=True)
-        s = self.torso_sm(r['pd_prob'], want_prob=bool(want_prob or peaks), people=M, people_threshold=people_threshold)
+        s = self.torso_sm(r['pd_prob'], want_prob=bool(want_prob or peaks), people=M, people_threshold=people_threshold, want_torso_prob=want_torso_prob)
         hm10 = s.pop('hm10')
         scratch = {}
         if not want_prob:
@@ -509,7 +563,8 @@ class Engine:
         _lib.check(self._lib.jcm_softmax_argmax(self._h, self._p(logits), B, H, W, K, self._p(prob), self._p(coords)), 'jcm_softmax_argmax')
         return prob, coords
 
-    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0, decode=False, flip_test=False, people=1, people_threshold=0.0):
+    def forward(self, x, torso=None, use_sm=True, want_prob=True, peaks=0, decode=False, flip_test=False, people=1, people_threshold=0.0,
+                want_torso_prob=False):
         """The tower of main.py:522-531 in one C call.  Returns a dict with 'pd_coords',
         'sm_coords' (int32 [B,2,K]) and, if want_prob, 'pd_prob' / 'sm_prob' [B,60,90,K].  x: float32, or uint8 (byte k standing for
         float32(k) / float32(255): the same bits out as for that float image, a quarter of the bytes in).  peaks = P > 0: also 'pd_peaks'
@@ -526,7 +581,8 @@ class Engine:
         spatial_softmax(E) above people_threshold (hm_peaks; slot 0 is the arg-max): the dict gains 'people' = {'count' int32 [B], 'torso_cell'
         int32 [B,M,2], 'torso_score' fp32 [B,M], 'sm_coords' int32 [B,M,2,K], and with want_prob 'sm_prob' [B,M,60,90,K]}, slots at or beyond
         count holding -1 in the coordinates and 0 in the maps; the top-level 'sm_*', 'torso_cell' and 'torso' are slot 0, and with decode 'pose'
-        is decoded per slot, [B,M,...].  flip_test=True with torso='infer' is a ValueError."""
+        is decoded per slot, [B,M,...].  flip_test=True with torso='infer' is a ValueError.  want_torso_prob (with torso='infer'; False changes
+        nothing): the dict gains 'torso_prob' [B,60,90] = spatial_softmax of the torso energy E."""
         self._chk_decode(decode, use_sm, peaks)
         self._chk_img(x, 'x')
         B, H, W, C = x.shape
@@ -537,11 +593,13 @@ class Engine:
             raise ValueError("torso must be a tensor, None or 'infer', got %r" % (torso,))
         if not isinstance(people, int) or not 1 <= people <= 4 or (people > 1 and not infer):
             raise ValueError("people must be an integer in 1..4 and needs torso='infer' above 1; got people=%r, torso=%s" % (people, 'infer' if infer else 'given'))
+        if want_torso_prob and not infer:
+            raise ValueError("want_torso_prob needs torso='infer': a given torso map has no energy")
         if infer:
             if not use_sm or flip_test:
                 raise ValueError("torso='infer' needs use_sm=True and does not combine with flip_test=True (the torso under mirrored evaluation is not defined); "
                                  'got use_sm=%s, flip_test=%s' % (bool(use_sm), bool(flip_test)))
-            return self._forward_infer(x, want_prob, peaks, decode, people, float(people_threshold))
+            return self._forward_infer(x, want_prob, peaks, decode, people, float(people_threshold), bool(want_torso_prob))
         if use_sm:
             if torso is None:
                 raise ValueError('use_sm=True needs the torso heat map y_in[..., 9:] (main.py:528)')

@@ -108,6 +108,14 @@ def build_parser():
                         'frame in heat-map cells, one value or one per joint (default 1.5, an untuned placeholder).')
     parser.add_argument('--seq_rho', type=float, default=None, metavar='RHO', help='with --sequence: the mass in [0,1] of the uniform "anywhere" term that absorbs '
                         'misses and scene cuts (default 0.05, an untuned placeholder).')
+    parser.add_argument('--seq_people', type=int, default=None, metavar='M', help='with --sequence, --predict and --use_sm: a clip with up to M (1..4) people in it '
+                        '(predict.predict_sequence_people, DESIGN.md 4.21): M consistent torso tracks are pulled out of the frames\' torso maps, the spatial model '
+                        'runs once per frame and track, and every person\'s joints are tracked; every image of the document gains "tracks" ("track" is track 0) '
+                        'and --render draws one skeleton per track present in the frame.  What this buys with trained weights has not been measured.')
+    parser.add_argument('--seq_torso_sigma', type=float, default=None, metavar='CELLS', help='with --seq_people: the standard deviation of a torso\'s motion per '
+                        'frame in heat-map cells (default 1.5, an untuned placeholder).')
+    parser.add_argument('--seq_exclude', type=int, default=None, metavar='CELLS', help='with --seq_people: the half-width in 0..64 heat-map cells of the square '
+                        'around an earlier track\'s torso cell that a later track may not use in that frame (default 4, an untuned placeholder).')
     parser.add_argument('--augm_affine', action='store_true', help='--train: augment every batch on the device with one composed affine sample of the image -- '
                         'flip, brightness, contrast, a rotation of up to 20 degrees, scale and shift -- and targets redrawn as 3x3 blobs at the transformed joint '
                         'cells (Engine.augment_affine, DESIGN.md 4.20; drawn from --seed + 1).  Not the reference\'s --data_augm.  What it buys in detection rate '
@@ -320,6 +328,9 @@ SEQUENCE_NEEDS_PREDICT = '--sequence tracks the joints over the frames --predict
 SEQUENCE_NO_ZOOM = '--sequence cannot be combined with --zoom: the windows of the second pass would move from frame to frame, which is out of scope'
 SEQUENCE_ONE_PERSON = '--sequence tracks one person: --people M > 1 would need an association of people across frames, which is out of scope'
 SEQ_OPTION_NEEDS_SEQUENCE = '--seq_sigma and --seq_rho set the motion model of --sequence: give --sequence filter or --sequence viterbi as well'
+SEQ_PEOPLE_NEEDS_SEQUENCE = '--seq_people tracks the people of the clip --sequence names: give --sequence filter or --sequence viterbi as well'
+SEQ_PEOPLE_NEEDS_USE_SM = '--seq_people needs --use_sm: the torso tracks come from the inferred torso map and every person is one run of the spatial model'
+SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
 AUGM_AFFINE_NEEDS_TRAIN = '--augm_affine augments the batches of a training run: give --train as well'
@@ -333,7 +344,8 @@ def predict_main(args):
     """--predict PATH [PATH ...]: the named images through predict.predict_images on the first listed device; the JSON document goes to
     --predictions, one JSON line with the image count and the device times of the fit and of the forwards to stdout.  With --render DIR the
     images come back with the result drawn on them (predict.render_images) and go to DIR as PNG files; the line gains render_ms.  With --sequence
-    the images are the frames of one clip (predict.predict_sequence): the document gains "track" per file, the pictures show the tracked skeleton."""
+    the images are the frames of one clip (predict.predict_sequence): the document gains "track" per file, the pictures show the tracked skeleton; with --seq_people M
+    (predict.predict_sequence_people) also "tracks", one skeleton per person, and the line gains seq_people, seq_torso_ms and seq_people_sm_ms."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -345,9 +357,14 @@ def predict_main(args):
         timing = {}
         if args.sequence:
             sigma = predict.SEQ_SIGMA if args.seq_sigma is None else args.seq_sigma
-            results = predict.predict_sequence(eng, images, mode=args.sequence, sigma=sigma[0] if isinstance(sigma, list) and len(sigma) == 1 else sigma,
-                                               rho=predict.SEQ_RHO if args.seq_rho is None else args.seq_rho, use_sm=args.use_sm, batch_size=args.batch_size,
-                                               keep_maps=bool(args.render_heat), peaks=args.peaks, decode=args.decode_pose, timing=timing)
+            seq = dict(mode=args.sequence, sigma=sigma[0] if isinstance(sigma, list) and len(sigma) == 1 else sigma,
+                       rho=predict.SEQ_RHO if args.seq_rho is None else args.seq_rho, batch_size=args.batch_size, keep_maps=bool(args.render_heat),
+                       peaks=args.peaks, decode=args.decode_pose, timing=timing)
+            if args.seq_people is not None:
+                results = predict.predict_sequence_people(eng, images, args.seq_people, exclude=predict.SEQ_EXCLUDE if args.seq_exclude is None else args.seq_exclude,
+                                                          torso_sigma=predict.SEQ_TORSO_SIGMA if args.seq_torso_sigma is None else args.seq_torso_sigma, **seq)
+            else:
+                results = predict.predict_sequence(eng, images, use_sm=args.use_sm, **seq)
         else:
             results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
                                              batch_size=args.batch_size, timing=timing, zoom=args.zoom, keep_maps=bool(args.render_heat))
@@ -363,6 +380,8 @@ def predict_main(args):
             'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}
     if args.sequence:
         line.update(sequence=args.sequence)
+    if args.seq_people is not None:
+        line.update(seq_people=args.seq_people, seq_torso_ms=timing['seq_torso_ms'], seq_people_sm_ms=timing['seq_people_sm_ms'])
     if args.zoom:
         line.update(zoom=True, zoom_fit_ms=timing['zoom_fit_ms'], zoom_forward_ms=timing['zoom_forward_ms'])
     if args.render:
@@ -636,13 +655,22 @@ AUGM_RULES = (
     (lambda a: a.augm_shift is not None and not 0 <= a.augm_shift < 0.5, lambda a: '--augm_shift %g: 0 <= F < 0.5' % a.augm_shift),
     (lambda a: a.augm_pad is not None and not 0 <= a.augm_pad <= 1, lambda a: '--augm_pad %g: 0 <= V <= 1' % a.augm_pad),
 )
+# The rules of --seq_people, walked behind AUGM_RULES (a table of their own for the same reason).  --people with --sequence stays refused above.
+SEQ_PEOPLE_RULES = (
+    (lambda a: a.seq_people is not None and not a.sequence, SEQ_PEOPLE_NEEDS_SEQUENCE),
+    (lambda a: a.seq_people is not None and not a.use_sm, SEQ_PEOPLE_NEEDS_USE_SM),
+    (lambda a: a.seq_people is not None and not 1 <= a.seq_people <= 4, lambda a: '--seq_people %d: 1 <= M <= 4' % a.seq_people),
+    (lambda a: (a.seq_torso_sigma is not None or a.seq_exclude is not None) and a.seq_people is None, SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE),
+    (lambda a: a.seq_torso_sigma is not None and not 0 < a.seq_torso_sigma < float('inf'), lambda a: '--seq_torso_sigma %g: CELLS > 0' % a.seq_torso_sigma),
+    (lambda a: a.seq_exclude is not None and not 0 <= a.seq_exclude <= 64, lambda a: '--seq_exclude %d: 0 <= CELLS <= 64' % a.seq_exclude),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

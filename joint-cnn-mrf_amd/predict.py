@@ -16,12 +16,18 @@ under them -- onto the images at their own size through Engine.render_poses.
 Frame sequences: predict_sequence takes the frames of a clip, all of one size, and adds to every frame's result a 'track': one
 position per joint that is consistent over the clip, from Engine.seq_filter (causal) or Engine.seq_viterbi (the most probable track) on the
 stacked heat maps.  SequenceTracker is the online form of the filter.  SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what tracking buys
-with trained weights has not been measured."""
+with trained weights has not been measured.
+
+Clips with several people: predict_sequence_people pulls up to four consistent torso tracks out of the frames' torso maps
+(Engine.seq_tracks: successive passes of the temporal model, each with the earlier tracks' neighbourhoods excluded), runs the spatial model
+once per (frame, track) with the blob at the track's cell and tracks every person's joints; PeopleTracker is its online form.  SEQ_EXCLUDE and
+SEQ_TORSO_SIGMA are untuned placeholders too."""
 import os
 
 import numpy as np
 import torch
 
+from .engine import SEQ_EXCLUDE      # the exclusion half-width of Engine.seq_tracks, cells: an untuned placeholder
 from .evaluation import fit_geometry, fit_to_source, peaks_to_pixels, pose_to_pixels, window_to_source
 
 JOINT_NAMES = ('lsho', 'lelb', 'lwri', 'rsho', 'relb', 'rwri', 'lhip', 'rhip', 'nose')      # main.py:18, without the torso channel
@@ -38,6 +44,7 @@ FIT_SIDE_MAX = 16384                      # include/jcm.h: the sides of what jcm
 # "anywhere" term.  Untuned placeholders: no consecutive-frame data is at hand to derive them from.
 SEQ_SIGMA = 1.5
 SEQ_RHO = 0.05
+SEQ_TORSO_SIGMA = 1.5                     # a torso's motion per frame in cells (predict_sequence_people): an untuned placeholder
 SEQ_RADIUS_MAX = 16                       # include/jcm.h: R of jcm_seq_filter / jcm_seq_viterbi
 IMAGE_EXTENSIONS = ('.npy', '.png', '.jpg', '.jpeg', '.bmp', '.gif', '.tif', '.tiff', '.webp', '.ppm')
 
@@ -48,7 +55,8 @@ def _coords_to_points(coords):
     return np.where(c < 0, -1.0, c * STRIDE)
 
 
-def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1, batch_size=16, pad=0, timing=None, zoom=False, keep_maps=False):
+def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1, batch_size=16, pad=0, timing=None, zoom=False, keep_maps=False,
+                   torso_prob=False):
     """images: a list of uint8 [h,w,3] arrays or tensors of mixed sizes (what Engine.fit_images takes).  They are fitted and run through
     engine.forward(x_u8, torso='infer' if use_sm else None, use_sm=use_sm, peaks=peaks, decode=decode, people=people) batch_size at a time.
     Returns one dict per image, everything in the image's own pixels (row, col), host numpy:
@@ -65,6 +73,8 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
         and the pass-1 values.
       with keep_maps (every key above keeps its value): 'maps' = {'pd': device float32 [60,90,K]} and with use_sm also 'sm' (people > 1: slot 0),
         views of the first pass's probability maps of the image's batch -- what render_images(heat=...) tints with.
+      with torso_prob (needs keep_maps and use_sm; every key above keeps its value): 'maps' also holds 'torso_prob', device float32 [60,90] =
+        spatial_softmax of the torso energy E -- the map predict_sequence_people tracks torsos through.
     timing: a dict that receives 'fit_ms' and 'forward_ms', device-event times summed over the batches (the upload of host images is part of
     neither), and with zoom 'zoom_fit_ms' and 'zoom_forward_ms', those of the second pass."""
     if not isinstance(images, (list, tuple)) or len(images) == 0:
@@ -73,6 +83,8 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
         raise ValueError('zoom=True needs use_sm=True: the windows are placed at the inferred torso and sized by the spatial model\'s shoulders and hips')
     if int(batch_size) < 1:
         raise ValueError('batch_size must be >= 1, got %r' % (batch_size,))
+    if torso_prob and not (keep_maps and use_sm):
+        raise ValueError('torso_prob=True needs keep_maps=True and use_sm=True: the map is kept in \'maps\' and comes from the inferred torso')
     names = list(JOINT_NAMES[:engine.n_joints])
     out = []
     fit_ms = fwd_ms = 0.0
@@ -85,7 +97,8 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
             ev[0].record(engine._stream)
             x, geom = engine.fit_images(batch, out_hw=FRAME, pad=pad)
             ev[1].record(engine._stream)
-            r = engine.forward(x, 'infer' if use_sm else None, use_sm=use_sm, want_prob=bool(keep_maps), peaks=peaks, decode=decode, people=people)
+            r = engine.forward(x, 'infer' if use_sm else None, use_sm=use_sm, want_prob=bool(keep_maps), peaks=peaks, decode=decode, people=people,
+                               **({'want_torso_prob': True} if torso_prob else {}))
             ev[2].record(engine._stream)
             ev[2].synchronize()
             fit_ms += ev[0].elapsed_time(ev[1])
@@ -94,6 +107,8 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
             if keep_maps:
                 for b, e in enumerate(res):
                     e['maps'] = {key: r[key + '_prob'][b] for key in (('pd', 'sm') if use_sm else ('pd',))}
+                    if torso_prob:
+                        e['maps']['torso_prob'] = r['torso_prob'][b]
             if zoom:
                 _zoom_pass(engine, batch, res, people, int(batch_size), pad, zoom_ms)
             out.extend(res)
@@ -357,6 +372,141 @@ class SequenceTracker:
         return results
 
 
+# ------------------------------------------------------------------ clips with several people
+def _people_joint_maps(engine, pd, cells, batch_size):
+    """pd [T,60,90,9], the frames' part-detector probabilities, and cells int32 [M,T,2], every track's torso cell -> [M,T,60,90,9]: per (frame,
+    track) the spatial model on [pd of the frame, the torso blob at the track's cell], as probabilities; batch_size frames at a time."""
+    M, T = cells.shape[:2]
+    out = []
+    for lo in range(0, T, batch_size):
+        hi = min(T, lo + batch_size)
+        at = cells[:, lo:hi].permute(1, 0, 2).reshape(-1, 2).contiguous()                      # (frame, track) order
+        blob = engine.torso_infer(None, cells=at)['torso']
+        hm10 = torch.cat([pd[lo:hi].repeat_interleave(M, dim=0), blob], dim=3)
+        prob, _ = engine.softmax_argmax(engine.spatial_model(hm10), want_prob=True)
+        out.append(prob.view(hi - lo, M, *prob.shape[1:]))
+    return torch.cat(out).permute(1, 0, 2, 3, 4).contiguous()
+
+
+def _people_entries(torso, seq, geom, mode, people_threshold):
+    """The dicts of Engine.seq_tracks on [T,60,90] and of Engine.seq_filter / seq_viterbi on [M,T,60,90,K], and the frames' fit -> per frame
+    ('tracks', 'track'); `count` is filled in by the caller."""
+    cells_key, value, flag = ('coords', 'norm', 'reset') if mode == 'filter' else ('path', 'maxes', 'breaks')
+    tc = torso[cells_key].cpu().numpy()                                                       # [M,T,2]
+    tv, tf = torso['value'].cpu().numpy(), torso[flag].cpu().numpy()                          # [M,T]
+    M, T = tv.shape
+    tpts, _ = fit_to_source(np.where(tc < 0, -1.0, tc.astype(np.float64) * STRIDE).transpose(1, 0, 2), geom)      # [T,M,2]
+    jc = seq[cells_key]                                                                       # [M,T,2,K]
+    K = jc.shape[3]
+    pts, inside = fit_to_source(_coords_to_points(jc.permute(1, 0, 2, 3).reshape(T * M, 2, K)).reshape(T, M, K, 2), geom)
+    v, f = seq[value].cpu().numpy(), seq[flag].cpu().numpy()                                  # [M,T,K]
+    present = (tv > people_threshold) & (tf != 2)
+    out = []
+    for t in range(T):
+        tracks = {'mode': mode, 'count': 0, 'torso': tpts[t], 'torso_value': tv[:, t], 'present': present[:, t], 'points': pts[t], 'inside': inside[t],
+                  value: v[:, t], flag: f[:, t]}
+        track = {'mode': mode, 'points': pts[t, 0], 'inside': inside[t, 0], value: v[0, t], flag: f[0, t]}
+        out.append((tracks, track))
+    return out, present
+
+
+def _people_pass(engine, results, people, mode, sigma, torso_sigma, rho, radius, exclude, people_threshold, batch_size, states, timing):
+    """Steps 2 to 5 of predict_sequence_people on the dicts of predict_images(keep_maps=True, torso_prob=True); states: (torso state, joint
+    state) of the filter or (None, None).  Returns the new states and the [M,T] presence."""
+    M = int(people)
+    with torch.cuda.stream(engine._stream):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record(engine._stream)
+        torso_maps = torch.stack([r['maps']['torso_prob'] for r in results]).contiguous()
+        torso = engine.seq_tracks(torso_maps, M, torso_sigma, rho, exclude=exclude, mode=mode, state=states[0])
+        ev[1].record(engine._stream)
+        pd = torch.stack([r['maps']['pd'] for r in results]).contiguous()
+        hm = _people_joint_maps(engine, pd, torso['coords' if mode == 'filter' else 'path'], int(batch_size))
+        ev[2].record(engine._stream)
+        seq = engine.seq_filter(hm, sigma, rho, radius=radius, state=states[1]) if mode == 'filter' else engine.seq_viterbi(hm, sigma, rho, radius=radius)
+        geom = np.array([r['geom'] for r in results], np.int64)
+        entries, present = _people_entries(torso, seq, geom, mode, people_threshold)
+        for r, (tracks, track) in zip(results, entries):
+            r['tracks'], r['track'] = tracks, track
+        if timing is not None:
+            ev[2].synchronize()
+            timing['seq_torso_ms'] = timing.get('seq_torso_ms', 0.0) + ev[0].elapsed_time(ev[1])
+            timing['seq_people_sm_ms'] = timing.get('seq_people_sm_ms', 0.0) + ev[1].elapsed_time(ev[2])
+    return (torso.get('state'), seq.get('state')), present
+
+
+def _check_people(people, zoom):
+    if not isinstance(people, int) or not 1 <= people <= 4:
+        raise ValueError('people must be an integer in 1..4, got %r' % (people,))
+    if zoom:
+        raise ValueError('predict_sequence_people has no zoom pass: a zoom pass per track is out of scope')
+
+
+def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, exclude=SEQ_EXCLUDE,
+                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, **kw):
+    """The frames of ONE clip with up to people = M (1..4) persons in it; frames as for predict_sequence.  On the device:
+      1. predict_images(frames, use_sm=True, people=1, keep_maps=True, torso_prob=True, **kw): per frame the part-detector maps and the torso map
+         spatial_softmax(E);
+      2. Engine.seq_tracks on the stacked torso maps [T,60,90]: M torso tracks -- track 0 the most probable torso track (mode 'viterbi') or the
+         causal filter's (mode 'filter'), track n the same through what is left once the cells within `exclude` of the tracks before it are
+         taken out of every frame; identity is stable by construction, tracks are reported in pass order and never re-sorted;
+      3. per (frame, track) the spatial model on [the frame's pd maps, the blob at the track's cell], batch_size frames at a time;
+      4. the existing Engine.seq_filter / seq_viterbi on the [M,T,60,90,K] maps, the persons as its sequences;
+      5. evaluation.fit_to_source.
+    Returns predict_images' dicts, every key with its value, plus
+      'tracks': {'mode', 'count' (the tracks present in at least one frame of the call), 'torso' float64 [M,2] (row, col) in the frame's pixels,
+                 'torso_value' float32 [M] (the torso map at the track's cell, 0 where an earlier track excludes it), 'present' bool [M]
+                 (torso_value > people_threshold and the torso pass did not meet an all-zero map there, flag 2), 'points' float64 [M,K,2],
+                 'inside' bool [M,K], 'maxes' / 'breaks' or 'norm' / 'reset' [M,K]}
+      'track': track 0 in the layout of predict_sequence, so that what reads 'track' works unchanged.
+    timing also receives 'seq_torso_ms' and 'seq_people_sm_ms', the device times of steps 2 and 3.  'maps' is kept only with keep_maps.
+    exclude (SEQ_EXCLUDE = 4 cells), torso_sigma (SEQ_TORSO_SIGMA = 1.5), sigma, rho and people_threshold are untuned placeholders -- no
+    consecutive-frame data and no trained weights are at hand -- and what this buys with trained weights has not been measured.  zoom=True
+    raises ValueError."""
+    if mode not in ('filter', 'viterbi'):
+        raise ValueError("mode must be 'filter' or 'viterbi', got %r" % (mode,))
+    _check_people(people, zoom)
+    _one_size(frames)
+    results = predict_images(engine, frames, use_sm=True, people=1, batch_size=batch_size, keep_maps=True, torso_prob=True, timing=timing, **kw)
+    _, present = _people_pass(engine, results, people, mode, sigma, torso_sigma, rho, radius, exclude, people_threshold, batch_size, (None, None), timing)
+    for r in results:
+        r['tracks']['count'] = int(present.any(axis=1).sum())
+        if not keep_maps:
+            del r['maps']
+    return results
+
+
+class PeopleTracker:
+    """The online form of predict_sequence_people(mode='filter'): push(frames) takes the next frames of the clip and returns their dicts with
+    'tracks' and 'track'; the float64 beliefs of the torso passes and of the persons' joints are both carried from call to call, so any split of
+    a clip gives the values of one predict_sequence_people over all of it -- except 'count', which counts over the frames of its own push.
+    Every push must bring frames of the first push's size.  reset() starts a new clip."""
+
+    def __init__(self, engine, people, sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, exclude=SEQ_EXCLUDE, people_threshold=0.0, radius=None,
+                 batch_size=16, **kw):
+        _check_people(people, False)
+        self.engine, self.people, self.kw = engine, people, kw
+        self.args = (sigma, torso_sigma, rho, radius, exclude, people_threshold, batch_size)
+        self.reset()
+
+    def reset(self):
+        self.states, self.shape = (None, None), None
+
+    def push(self, frames, keep_maps=False):
+        _one_size(frames)
+        shape = tuple(frames[0].shape)
+        if self.shape is not None and shape != self.shape:
+            raise ValueError('the frames of a clip have one size: this clip began with %s, got %s' % (self.shape, shape))
+        self.shape = shape
+        results = predict_images(self.engine, frames, use_sm=True, people=1, batch_size=self.args[-1], keep_maps=True, torso_prob=True, **self.kw)
+        self.states, present = _people_pass(self.engine, results, self.people, 'filter', *self.args, self.states, None)
+        for r in results:
+            r['tracks']['count'] = int(present.any(axis=1).sum())
+            if not keep_maps:
+                del r['maps']
+        return results
+
+
 # ------------------------------------------------------------------ pictures of the result (DESIGN.md 4.18)
 NECK = -1      # no joint of the network: the midpoint of the shoulders, the floor-halved sum of their fixed-point coordinates
 # limbs as (first joint, second joint); a limb takes the colour of its second joint
@@ -374,8 +524,11 @@ def _fixed(v):
 
 
 def _skeletons(r, which, zoom):
-    """The (joints [K,2], inside [K]) pairs one image's result draws: the tracked joints for 'track'; else one per entry of 'zoom' (a person the second pass skipped carries the
+    """The (joints [K,2], inside [K]) pairs one image's result draws: the tracked joints for 'track' (with 'tracks' in the result one per track present in the frame); else one per entry of 'zoom' (a person the second pass skipped carries the
     first pass's values), else one per counted slot of 'people' (spatial model only), else the image's one set of joints."""
+    if which == 'track' and 'tracks' in r:
+        p = r['tracks']
+        return [(p['points'][m], p['inside'][m]) for m in range(len(p['present'])) if p['present'][m]]
     if which == 'track':
         return [(r['track']['points'], r['track']['inside'])]
     if zoom and 'zoom' in r:
@@ -391,7 +544,7 @@ def skeleton_primitives(results, which='sm', zoom=True):
     int32 [NP,8] = (image, ay, ax, by, bx, r, rgb, alpha), coordinates and radii in sixteenths of a pixel (floor(16 v + 0.5)).  Per image
     rl = max(16, 2 * (h + w) // 75), 2 px at 480 x 720.  Per skeleton, first the limbs of SKELETON whose two ends are inside (radius rl, the
     colour of the second joint, alpha 192; the neck exists when both shoulders do), then a disc per inside joint (radius 2 rl, alpha 255).
-    which: 'sm' or 'pd', whose joints are drawn, or 'track', the tracked joints of predict_sequence; with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
+    which: 'sm' or 'pd', whose joints are drawn, or 'track', the tracked joints of predict_sequence (one skeleton per present track of predict_sequence_people); with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
     in a result, one skeleton per entry of it, a zoomed person's from the second pass."""
     if which not in ('sm', 'pd', 'track'):
         raise ValueError("which must be 'sm', 'pd' or 'track', got %r" % (which,))
