@@ -524,6 +524,42 @@ int jcm_render_poses(jcm_handle h, const uint8_t* src, int64_t src_bytes, const 
                      const int32_t* prims, int NP,
                      const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain);
 
+/* -- rendered people: a data set drawn on the device ------------------------------------------
+ * out [B,H,W,3] from one scene record and one list of primitives per image: a vertical gradient with four octaves of value noise, capsules and
+ * convex quadrilaterals over it in painter's order, sensor noise on top.  Everything is integer arithmetic (the capsule test: float64 products of
+ * integers, exact); "floor(a / b)" is floor division, also for a negative a; ">>" on a negative value is the arithmetic shift (floor).
+ * records: HOST int32 [B][JCM_SYNTH_REC_INTS = 20]:
+ *   [0] seed   [1..3] c0 (R, G, B of row 0)   [4..6] c1 (of row H - 1)   [7..10] amp[o], o = 0..3   [11..14] s[o], the octave's shift: lattice cells
+ *   of 1 << s[o] pixels (synth.py uses 6, 4, 2, 0)   [15] a, the sensor-noise amplitude   [16] n, the image's primitive count   [17] first, the
+ *   index of its first primitive in prims   [18], [19] reserved, 0
+ * prims: HOST int32 [NP][JCM_SYNTH_PRIM_INTS = 16]:
+ *   [0] kind: 0 capsule, 1 quadrilateral   [1..8] geometry in sixteenths of a pixel -- capsule: ay, ax, by, bx, r, 0, 0, 0; quadrilateral: y0, x0,
+ *   y1, x1, y2, x2, y3, x3, the vertices in order (either winding)   [9..11] col (R, G, B)   [12] tamp   [13] ts   [14] tseed   [15] reserved, 0
+ * hash32(seed, i, j), on uint32 with wrap-around (a negative seed is its two's complement):
+ *   h = (seed * 0x9E3779B1) ^ (i * 0x85EBCA77) ^ (j * 0xC2B2AE3D);  h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16
+ * vnoise(seed, s, y, x) in 0..255: cell = 1 << s, i = y >> s, j = x >> s, fy = y & (cell - 1), fx = x & (cell - 1), L(i, j) = hash32(seed, i, j) >> 24,
+ *   ((cell - fy) * ((cell - fx) * L(i, j) + fx * L(i, j + 1)) + fy * ((cell - fx) * L(i + 1, j) + fx * L(i + 1, j + 1))) >> (2 * s)
+ * Pixel (y, x), channel k, in this order:
+ *   1. g = c0[k] + floor((c1[k] - c0[k]) * y / max(H - 1, 1));   v = clamp(g + sum over o of floor(amp[o] * (vnoise(seed + o, s[o], y, x) - 128) / 256), 0, 255)
+ *      (the noise is the same for the three channels).
+ *   2. For primitive first, first + 1, .., first + n - 1: c = the count of the pixel's 16 sub-samples inside it (sample positions and the capsule
+ *      test: jcm_render_poses above; the quadrilateral: the four cross products (v[i+1] - v[i]) x (sample - v[i]) = (y[i+1] - y[i]) * (sx - x[i])
+ *      - (x[i+1] - x[i]) * (sy - y[i]), in 64-bit integers, are all >= 0 or all <= 0).  Where c > 0:
+ *        t = clamp(col[k] + floor(tamp * (vnoise(tseed, ts, y, x) - 128) / 256), 0, 255);   v = (c * t + (16 - c) * v + 8) >> 4
+ *   3. v = clamp(v + (int)(hash32(seed ^ JCM_SYNTH_NOISE_KEY, y * W + x, k) mod (2 * a + 1)) - a, 0, 255)
+ * out: device, uint8 [B,H,W,3] (out_f32 == 0) at ANY byte address, or float32 (out_f32 == 1, 4-byte aligned) = float32(v) / float32(255), the byte
+ * grid of the image entry points.  Every element of out is written.
+ * JCM_ERR_ARG -- nothing is launched, out is untouched -- for a null records or out, or NP > 0 with null prims; B outside 1..65535; H or W < 1 or
+ * H * W > 2^31 - 1; NP < 0; a colour, an amplitude (amp, a, tamp) outside 0..255; a shift (s[o], ts) outside 0..8; n outside 0..64; first < 0 or
+ * first + n > NP; a kind other than 0 and 1; a coordinate outside +-2^20; a capsule with r < 0 or r > 2^16.
+ * records and prims are read before the call returns: they travel in kernel arguments (ceil(B / 48) + ceil(NP / 60) small launches into the
+ * handle's workspace); then ONE launch on the handle's stream.  The call does NOT synchronise (growing the handle's workspace does, as for every
+ * entry point that uses it). */
+#define JCM_SYNTH_REC_INTS 20
+#define JCM_SYNTH_PRIM_INTS 16
+#define JCM_SYNTH_NOISE_KEY 0x5BD1E995u
+int jcm_synth_people(jcm_handle h, const int32_t* records, int B, const int32_t* prims, int NP, int H, int W, int out_f32, void* out);
+
 /* -- mirrored test-time evaluation -----------------------------------------------------
  * The maps of an image averaged with the un-mirrored maps of its mirror image: jcm_mirror_pairs makes the batch the tower sees,
  * jcm_mirror_merge folds the tower's maps back.  Both enqueue one launch on the handle's stream and do not synchronise.

@@ -11,6 +11,7 @@ JCM_PRECISION_BF16 = 1
 JCM_OPT_ADAM = 0
 JCM_OPT_MOMENTUM = 1
 JCM_HIST_BUCKETS = 1551      # include/jcm.h
+SYNTH_REC_INTS, SYNTH_PRIM_INTS = 20, 16      # include/jcm.h: a scene record and a primitive record of jcm_synth_people
 HM_FLIP_PERM = (3, 4, 5, 0, 1, 2, 7, 6, 8, 9)      # csrc/hm_flip.h: where channel k of a mirrored FLIC heat map reads from (augmentation.py:20)
 
 _c_float_p = ctypes.c_void_p      # device pointers travel as integers
@@ -79,6 +80,8 @@ SIGNATURES = {
     'jcm_render_poses': (ctypes.c_int, [_handle, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_void_p,
                                         ctypes.POINTER(ctypes.c_int32), ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8), ctypes.c_int]),
+    'jcm_synth_people': (ctypes.c_int, [_handle, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'jcm_group_mean': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_float_p]),
     'jcm_mirror_pairs': (ctypes.c_int, [_handle, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'jcm_mirror_merge': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),

@@ -406,6 +406,16 @@ size_t render_prim_ints(int NP);
 hipError_t render_poses(const uint8_t* src, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP, int32_t* prims_dev,
                         const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain,
                         float* maxima, hipStream_t st);
+// ---- synth_people.hip : rendered people, a data set drawn on the device ------------
+constexpr int kSynthRecInts = 20;        // a scene record (jcm.h: JCM_SYNTH_REC_INTS)
+constexpr int kSynthPrimInts = 16;       // a primitive record (jcm.h: JCM_SYNTH_PRIM_INTS)
+constexpr int kSynthPrimMax = 64;        // primitives per image: one lane of a wave culls one
+constexpr int kSynthTile = 8192;         // consecutive pixels (row-major) per work group: 24 KB of LDS
+// records HOST int32 [B][20], prims HOST int32 [NP][16], every entry checked by the caller (jcm.h: jcm_synth_people); both are read before the call
+// returns: they go into records_dev (B * 20 ints) and prims_dev (max(NP, 1) * 16 ints), workspace the caller provides (256-byte aligned), by
+// ceil(n / 960) small launches that carry them in their arguments.  out: uint8 [B,H,W,3], or float32 (out_f32) = byte / 255.  One more launch.
+hipError_t synth_people(const int32_t* records, int B, const int32_t* prims, int NP, int H, int W, bool out_f32, void* out, int32_t* records_dev,
+                        int32_t* prims_dev, hipStream_t st);
 // ---- sequence.hip : the temporal edge, a scan over the T frames of a clip ----------
 // hm [S,T,HH,WW,K]; one work group per (sequence, joint), whose belief plane stays in LDS for all T frames of the launch.  HH * WW <= kSeqMaxHW,
 // K <= kSeqMaxK, 0 <= R <= kSeqMaxR; taps: DEVICE [K][2R+1] (seq_put_taps uploads a host table through kernel arguments, ceil(n / 480) launches).

@@ -16,6 +16,7 @@
 //     bytes an image) and are put into workspace by small launches that carry kRenderPut of them each in THEIR arguments: nothing is copied
 //     from caller-owned host memory asynchronously, so nothing has to be waited for.
 //   * the per-map maxima the tint normalises by come from a launch of their own (one work group per map) into workspace.
+#include "coverage.h"      // render_coverage: the capsule test, shared with synth_people.hip
 #include "kernels.h"
 
 namespace jcm {
@@ -72,31 +73,6 @@ __device__ __forceinline__ void render_copy(const uint8_t* src, uint8_t* dst, in
         if (lo + q >= 0 && lo + q < n) dst[lo + q] = src[lo + q];
     }
   }
-}
-
-// the count of the pixel's 16 sub-samples inside capsule (ay, ax) - (by, bx), radius r, all in sixteenths of a pixel (jcm.h has the test)
-__device__ __forceinline__ int render_coverage(int y, int x, int ay, int ax, int by, int bx, int r) {
-  const double dy = (double)(by - ay), dx = (double)(bx - ax);
-  const double L2 = dy * dy + dx * dx, rr = (double)r * (double)r, rrL2 = rr * L2;
-  int c = 0;
-#pragma unroll
-  for (int iy = 0; iy < 4; ++iy) {
-    const int sy = 16 * y - 6 + 4 * iy;
-    const double ey = (double)(sy - ay), fy = (double)(sy - by);
-    const double eyy = ey * ey, eydy = ey * dy, fyy = fy * fy;
-#pragma unroll
-    for (int ix = 0; ix < 4; ++ix) {
-      const int sx = 16 * x - 6 + 4 * ix;
-      const double ex = (double)(sx - ax), fx = (double)(sx - bx);
-      const double ee = eyy + ex * ex, t = eydy + ex * dx;
-      bool in;
-      if (L2 == 0.0 || t <= 0.0) in = ee <= rr;
-      else if (t >= L2) in = fyy + fx * fx <= rr;
-      else in = ee * L2 - t * t <= rrL2;
-      c += in ? 1 : 0;
-    }
-  }
-  return c;
 }
 
 // one axis of the tint's sampling position: source pixel centre -> the fitted frame -> heat-map cells, clamped

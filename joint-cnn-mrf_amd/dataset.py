@@ -207,3 +207,56 @@ class DeviceDataset:
             if eng.device not in out:
                 out[eng.device] = cls(x, y, device=eng.device, **kw)
         return out
+
+    def rerender_people(self, engine, poses, indices, seed, batch=64, **ranges):
+        """A byte set of rendered people (render_people) drawn again in place: example i becomes a new scene of the pose
+        poses[indices[i]] -- new draws from RandomState(seed), the same poses -- written by Engine.synth_people straight into `.x`; `.y` and `.cells`
+        are replaced with the new scenes' targets and cells.  Everything -- the launches and the copies into `.y` and `.cells` -- is enqueued batch by batch
+        on the ENGINE's stream, behind whatever that stream still reads of the set (a gather in flight); the host does not wait.  Work on another
+        stream that reads the set has to wait for the engine's stream, as for every call of the engine."""
+        indices = np.asarray(indices).reshape(-1)
+        if self.image_dtype != 'uint8':
+            raise ValueError('rerender_people draws bytes: the set must be held with image_dtype=\'uint8\'')
+        if indices.shape[0] != self.n:
+            raise ValueError('rerender_people: %d indices for a set of %d examples' % (indices.shape[0], self.n))
+        if engine.device != self.device:
+            raise ValueError('the data set is on %s, the engine on %s' % (self.device, engine.device))
+        engine._on_stream(self.x, self.y, self.cells)      # (the engine's stream waits for the current one, as in every call of the engine)
+        for lo, _x, y, cells in _people_batches(engine, poses, indices, seed, batch, ranges, into=self.x):
+            with torch.cuda.stream(engine._stream):
+                self.y[lo:lo + y.shape[0]].copy_(torch.as_tensor(y))
+                self.cells[lo:lo + y.shape[0]].copy_(torch.as_tensor(np.ascontiguousarray(cells, np.int32)))
+        return self
+
+
+def _people_batches(engine, poses, indices, seed, batch, ranges, into=None, dtype=torch.uint8):
+    """The scenes of poses[indices] from RandomState(seed), `batch` at a time in index order: yields (lo, x device [n,H,W,3], y host, cells host).
+    into: a device tensor [N,H,W,3] whose rows [lo, lo + n) receive the images (its height and width are the scenes'); otherwise 480x720."""
+    from . import synth
+    indices = np.asarray(indices).reshape(-1)
+    rng = np.random.RandomState(seed)
+    H, W = (int(into.shape[1]), int(into.shape[2])) if into is not None else (480, 720)
+    for lo in range(0, indices.shape[0], int(batch)):
+        recs, prims, _xy, cells, y = synth.people_batch(rng, poses, indices[lo:lo + int(batch)], H, W, **ranges)
+        x = engine.synth_people(recs, prims, H, W, out=None if into is None else into[lo:lo + recs.shape[0]], dtype=dtype)
+        yield lo, x, y, cells
+
+
+def render_people(engine, poses, indices, seed, image_dtype='uint8', batch=64, **ranges):
+    """A data set of rendered people: one scene per entry of `indices` into poses [N,2,9] (data.py's xy), drawn from
+    RandomState(seed) by synth.people_batch, rendered `batch` at a time on the engine's device and downloaded -> (x [n,480,720,3] uint8, or float32
+    = byte / 255 with image_dtype='float32'; y float32 [n,60,90,10]; cells int64 [n,10,2]): host arrays of the shapes and dtypes get_dataset returns,
+    and the cells DeviceDataset(cells=...) and the affine augmentation take."""
+    if image_dtype not in ('float32', 'uint8'):
+        raise ValueError("image_dtype must be 'float32' or 'uint8', got %r" % (image_dtype,))
+    indices = np.asarray(indices).reshape(-1)
+    n = indices.shape[0]
+    if n < 1:
+        raise ValueError('render_people needs at least one index')
+    x = np.empty((n, 480, 720, 3), np.uint8 if image_dtype == 'uint8' else np.float32)
+    ys, cs = [], []
+    for lo, xb, y, cells in _people_batches(engine, poses, indices, seed, batch, ranges, dtype=torch.uint8 if image_dtype == 'uint8' else torch.float32):
+        x[lo:lo + y.shape[0]] = xb.cpu().numpy()
+        ys.append(y)
+        cs.append(cells)
+    return x, np.concatenate(ys), np.concatenate(cs)

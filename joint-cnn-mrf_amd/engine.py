@@ -774,6 +774,39 @@ class Engine:
             mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if mask is not None else None, int(heat_gain)), 'jcm_render_poses')
         return [buf[int(d[0]):int(d[0]) + int(d[1] * d[2] * 3)].view(int(d[1]), int(d[2]), 3) for d in desc]
 
+    def synth_people(self, records, prims, H, W, out=None, dtype=torch.uint8):
+        """Rendered people (include/jcm.h: jcm_synth_people): `records` int [B,20], one scene record per image, and `prims` int
+        [NP,16], the primitives the records name (what synth.people_batch makes; NP = 0: backgrounds only), both host arrays -> [B,H,W,3] on the
+        device, torch.uint8 or torch.float32 (= byte / 255).  out: a contiguous device tensor of that shape and dtype to write into instead of
+        a new one (a view at any byte offset for uint8).  One launch; nothing synchronises; every range is checked by the library."""
+        rec, pr = np.asarray(records), np.asarray(prims)
+        if pr.size == 0:
+            pr = np.zeros((0, _lib.SYNTH_PRIM_INTS), np.int32)
+        for a, n, name in ((rec, _lib.SYNTH_REC_INTS, 'records'), (pr, _lib.SYNTH_PRIM_INTS, 'prims')):
+            if a.dtype.kind not in 'iu' or a.ndim != 2 or a.shape[1] != n:
+                raise ValueError('%s must be an integer array [.,%d], got %s %s' % (name, n, a.dtype, a.shape))
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError('%s holds a value outside int32' % name)
+        if rec.shape[0] < 1:
+            raise ValueError('records must hold at least one image')
+        if dtype not in (torch.uint8, torch.float32):
+            raise TypeError('dtype must be torch.uint8 or torch.float32, got %s' % (dtype,))
+        rec, pr = np.ascontiguousarray(rec, dtype=np.int32), np.ascontiguousarray(pr, dtype=np.int32)
+        B, H, W = rec.shape[0], int(H), int(W)
+        if out is None:
+            if H < 1 or W < 1 or B * H * W * 3 >= 2 ** 40:
+                raise ValueError('synth_people: H and W >= 1 and an output below 2^40 elements are expected, got %d x %d x %d' % (B, H, W))
+            out = self._new(B, H, W, 3, dtype=dtype)
+        else:
+            self._chk(out, 4, 'out', dtype)
+            if tuple(out.shape) != (B, H, W, 3):
+                raise ValueError('out must be [%d,%d,%d,3], got %s' % (B, H, W, tuple(out.shape)))
+        self._on_stream(out)
+        _lib.check(self._lib.jcm_synth_people(
+            self._h, rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), B, pr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if pr.shape[0] else None,
+            pr.shape[0], H, W, int(dtype == torch.float32), self._p(out)), 'jcm_synth_people')
+        return out
+
     def _fit_run(self, entry, ts, desc, off, rows, sizes, out_hw, pad, dtype, out):
         """What fit_images and fit_windows share once the descriptor array is built: the output frame (`out` checked, or a new one), the images
         ts back to back in one device buffer of `off` bytes (desc[:, 0] their offsets), the library's `entry` on the int64 descriptor `rows`

@@ -4,6 +4,7 @@ three runs of main.py share: the data set, the parameters a run starts from, the
 run(args) loads the data, builds ONE set of engines, sends the test set through one of four feeds -- each returns a Result -- and hands that
 record to the writers: the .mat file of --predictions, the JSON document of --det_curve, the JSON line on stdout.  main.py parses and refuses
 flag combinations before anything here runs; nothing in this module looks at a combination main() refuses."""
+import functools
 import json
 import os
 import sys
@@ -46,9 +47,75 @@ def byte_grid(x):
     return np.minimum(np.floor(np.asarray(x, np.float32) * np.float32(256)), np.float32(255)).astype(np.uint8)
 
 
-def load_data(args):
+def people_split(n):
+    """--synth_people: the first 80 % of n poses, in file order, are the training poses and the last 20 % the test poses -> (train, test) indices."""
+    return np.arange(n * 4 // 5), np.arange(n * 4 // 5, n)
+
+
+@functools.lru_cache(maxsize=8)
+def poses_problem(path):
+    """None if `path` holds what --synth_people takes (an [N,2,9] float64 array with at least five poses, finite), else what is wrong with it."""
+    try:
+        a = np.load(path, mmap_mode='r')
+    except Exception as e:      # a missing or unreadable file is refused like a wrong one
+        return 'cannot be read (%s)' % e
+    if a.ndim != 3 or a.shape[1:] != (2, 9) or a.dtype != np.float64 or a.shape[0] < 5:
+        return 'holds %s %s' % (a.dtype, tuple(a.shape))
+    return None if np.isfinite(a).all() else 'holds values that are not finite'
+
+
+def people_seed(args, epoch):
+    """The generator seed of a rendered set: the test set is epoch 0, the training set of epoch e (the first one: 1) is seed + 2 + e."""
+    return int(args.seed) + 2 + int(epoch)
+
+
+def _people_dataset(args, extra):
+    """--synth_people: rendered people in the poses of the file, the sets rendered on the first device of --gpus and downloaded."""
+    from . import dataset, priors
+    from .engine import Engine
+    poses = np.asarray(np.load(args.synth_people), np.float64)
+    tr, te = people_split(poses.shape[0])
+    cap = args.synthetic_size if getattr(args, 'synthetic_size_given', False) else None      # not given: every training pose
+    if args.train:
+        tr = tr[:cap] if cap is not None else tr
+    else:      # an evaluation run reads a batch of the training set, for the summaries
+        tr = tr[:args.batch_size]
+    kind = 'uint8' if args.u8_images and not (args.multiscale and not args.train) else 'float32'
+    eng = Engine(device=args.gpus[0])
+    try:
+        x_train, y_train, c_train = dataset.render_people(eng, poses, tr, people_seed(args, 1), image_dtype=kind)
+        x_test, y_test, c_test = dataset.render_people(eng, poses, te, people_seed(args, 0), image_dtype=kind)
+        if getattr(args, 'synth_dump', None):      # the scenes are drawn one after the other: the first 16 of the set are the first 16 of its generator
+            xy = synth.people_batch(np.random.RandomState(people_seed(args, 0)), poses, te[:16])[2]
+            dump_people(eng, x_test[:16], xy, args.synth_dump)
+    finally:
+        eng.close()
+    if extra is not None:
+        extra.update(poses=poses, train_idx=tr, test_idx=te, cells_train=c_train, cells_test=c_test)
+    return x_train, y_train, x_test, y_test, priors.build_pairwise_distributions(c_train)
+
+
+def dump_people(eng, x, xy, out_dir):
+    """--synth_dump: the images x (uint8, or float32 on the byte grid) as DIR/<index:05d>.png with a white disc of 3 pixels on every annotated joint
+    xy [n,2,9] (x, y), to the sixteenth of a pixel, drawn by Engine.render_poses.  A way to look, not a measurement."""
+    from .summary import encode_png
+    x = np.asarray(x)
+    x = x if x.dtype == np.uint8 else np.rint(x * np.float32(255)).astype(np.uint8)
+    at = np.rint(np.asarray(xy, np.float64) * 16).astype(np.int64)
+    prims = [(i, at[i, 1, k], at[i, 0, k], at[i, 1, k], at[i, 0, k], 16 * 3, 0xFFFFFF, 255) for i in range(x.shape[0]) for k in range(N_JOINTS)]
+    pictures = eng.render_poses([im for im in x], np.array(prims, np.int32).reshape(-1, 8))
+    os.makedirs(out_dir, exist_ok=True)
+    for i, pic in enumerate(pictures):
+        with open(os.path.join(out_dir, '%05d.png' % i), 'wb') as fh:
+            fh.write(encode_png(pic.cpu().numpy()))
+
+
+def load_data(args, extra=None):
     """x_train, y_train, x_test, y_test, pairwise: the FLIC files of --data_dir, or with --synthetic generated priors and sets (--train: --synthetic_size
-    examples to train on and half as many, at least a batch, to test; an evaluation run: that many to test and a batch for the summaries)."""
+    examples to train on and half as many, at least a batch, to test; an evaluation run: that many to test and a batch for the summaries), or with
+    --synth_people rendered people (extra: a dict that receives the poses, the two index sets and the joint cells of the two sets)."""
+    if getattr(args, 'synth_people', None):
+        return _people_dataset(args, extra)
     if not args.synthetic:
         return get_dataset(args.data_dir) + (get_pairwise_distr(args.data_dir),)
     sizes = (args.synthetic_size, max(args.batch_size, args.synthetic_size // 2)) if args.train else (args.batch_size, args.synthetic_size)

@@ -25,7 +25,7 @@ import torch
 
 from . import eval_run, multiscale, synth
 from .engine import Engine
-from .eval_run import (_synthetic_dataset, byte_grid, det_curves_of_predictions, evaluated_indices, get_dataset, get_pairwise_distr,  # noqa: F401
+from .eval_run import (_synthetic_dataset, byte_grid, people_seed, poses_problem, det_curves_of_predictions, evaluated_indices, get_dataset, get_pairwise_distr,  # noqa: F401
                        initial_params, load_data, model_name, run_params)
 
 # main.py:18-26
@@ -44,6 +44,14 @@ hps = argparse.Namespace(debug=False, train=False, gpus=[0], restore=False, use_
                          render=None, render_heat=None)
 pairwise_energies, pairwise_biases = {}, {}        # '<j>_<c>' -> tensor, main.py:478-487
 _engine = None
+
+
+class _StoreGiven(argparse.Action):
+    """store, and note in <dest>_given that the flag was on the command line (its default stays what it was)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + '_given', True)
 
 
 def build_parser():
@@ -65,7 +73,18 @@ def build_parser():
     # not in the reference (module globals / hard-coded paths there)
     parser.add_argument('--data_dir', default='.', help='directory of x_*_flic.npy, y_*_flic.npy, pairwise_distribution.pickle (main.py:290-298).')
     parser.add_argument('--synthetic', action='store_true', help='generated images / targets / priors instead of the FLIC files.')
-    parser.add_argument('--synthetic_size', type=int, default=56, help='number of generated training examples with --synthetic.')
+    parser.add_argument('--synthetic_size', type=int, default=56, action=_StoreGiven, help='number of generated training examples with --synthetic; with '
+                        '--synth_people the most training poses that are rendered (there the default is all of them: synthetic_size_given tells).')
+    parser.set_defaults(synthetic_size_given=False)
+    parser.add_argument('--synth_people', default=None, metavar='POSES.npy', help='instead of the FLIC files: rendered people (DESIGN.md 4.22) in the poses of '
+                        'this [N,2,9] float64 annotation array (data.py\'s xy), drawn on the device by Engine.synth_people -- the first 80 %% of the poses, in file '
+                        'order, are the training set and the last 20 %% the test set; bytes under --u8_images, floats otherwise; the priors are those of the '
+                        'training cells.  Figures, not photographs: nothing measured on them is a FLIC number.')
+    parser.add_argument('--synth_fresh', action='store_true', help='with --train --device_data --u8_images --synth_people: draw the training set again, in place on '
+                        'the device, at the start of every epoch after the first (DeviceDataset.rerender_people, RandomState(seed + 2 + epoch)): the same poses, '
+                        'new scenes.  The batches are those of a run without it.')
+    parser.add_argument('--synth_dump', default=None, metavar='DIR', help='with --synth_people: write the first 16 test images to DIR as PNG files with the annotated '
+                        'joints marked at their annotated positions (Engine.render_poses).  A way to look, not a measurement.')
     parser.add_argument('--model_path', default=model_path, help='checkpoint directory (main.py:444).')
     parser.add_argument('--restore_path', default=None, help='checkpoint prefix (tf.train.Saver files) or .npz for --restore (main.py:443,612).')
     parser.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help='arithmetic of the kernels.')
@@ -335,6 +354,11 @@ U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte ima
                               'host-fed training steps take float batches')
 AUGM_AFFINE_NEEDS_TRAIN = '--augm_affine augments the batches of a training run: give --train as well'
 AUGM_OPTION_NEEDS_AUGM_AFFINE = '--augm_scale, --augm_shift and --augm_pad set the ranges of --augm_affine: give --augm_affine as well'
+SYNTH_PEOPLE_NOT_WITH_SYNTHETIC = '--synth_people and --synthetic both replace the data set: give one of them'
+SYNTH_PEOPLE_NOT_WITH_PREDICT = '--synth_people replaces the data of --train and of the evaluation run; --predict reads the images it names: drop one of them'
+SYNTH_FRESH_NEEDS_COMPANIONS = ('--synth_fresh draws the device-resident byte training set of rendered people again every epoch: give --train, --device_data, '
+                                '--u8_images and --synth_people POSES.npy as well')
+SYNTH_DUMP_NEEDS_SYNTH_PEOPLE = '--synth_dump writes pictures of the test set --synth_people renders: give --synth_people POSES.npy as well'
 TB_ACTIVATIONS_NEEDS_TB_DIR ='--tb_activations adds tags to the summaries --tb_dir writes: give --tb_dir DIR as well'
 TB_ACTIVATIONS_IS_FP32 = ('--tb_activations: the pre-activation summaries are taken in fp32, as the reference takes them, and the bf16 kernels have no '
                           'linear epilogue; run it with --precision fp32')
@@ -523,13 +547,14 @@ def train_main(args):
         raise NotImplementedError('--data_augm: the augmentation pipeline (augmentation.py: flips, rotations, crops on the TF input '
                                   'queue) is outside the hot path this build covers; train without it')
     t_start = time.time()
-    x_train, y_train, x_test, y_test, pairwise = load_data(args)
+    people = {}      # --synth_people: the poses, the index sets and the joint cells of the rendered sets
+    x_train, y_train, x_test, y_test, pairwise = load_data(args, people)
     if args.synthetic and args.u8_images:
         x_train, x_test = byte_grid(x_train), byte_grid(x_test)
     n_train, n_test = x_train.shape[0], x_test.shape[0]
     rng = np.random.RandomState(args.seed)
     n_eval_ex = 512 if args.debug else 1100                              # main.py:453
-    if args.debug and not args.synthetic:                                # main.py:459-462
+    if args.debug and not args.synthetic and not args.synth_people:      # main.py:459-462 (a rendered set is sized by --synthetic_size)
         n_train, n_test = min(1024, n_train), min(512, n_test)
         tr_idx, te_idx = np.sort(rng.permutation(x_train.shape[0])[:n_train]), np.sort(rng.permutation(x_test.shape[0])[:n_test])
         x_train, y_train, x_test, y_test = x_train[tr_idx], y_train[tr_idx], x_test[te_idx], y_test[te_idx]
@@ -557,8 +582,8 @@ def train_main(args):
         # room the engines have not claimed yet: a full-width fp32 engine's filter-spectra cache and workspace grow to 64 GB on first use
         reserve = len(towers.engines) * ((2 << 30) if args.debug else (64 << 30))
         kind = 'uint8' if args.u8_images else 'float32'     # uint8: float files are converted chunk by chunk, the round trip checked (NotByteExact)
-        ds_test = DeviceDataset(x_test, y_test, device=eng.device, reserve_bytes=reserve, image_dtype=kind)
-        ds_train = DeviceDataset.for_towers(towers, x_train, y_train, reserve_bytes=reserve, image_dtype=kind)
+        ds_test = DeviceDataset(x_test, y_test, device=eng.device, reserve_bytes=reserve, image_dtype=kind, cells=people.get('cells_test'))
+        ds_train = DeviceDataset.for_towers(towers, x_train, y_train, reserve_bytes=reserve, image_dtype=kind, cells=people.get('cells_train'))
         if args.u8_images:
             for name, d in [('test', ds_test)] + [('train', d) for d in ds_train.values()]:
                 print('device data (%s, images as uint8): %d bytes held on %s, uploaded in %.2f s' % (name, d.nbytes, d.device, d.upload_seconds), flush=True)
@@ -577,7 +602,10 @@ def train_main(args):
             summary.write_summary(tb['test'], [float(v) for v in te_e[:4]], TB_SCALARS, epoch)
             summary.write_summary(tb['train'], [float(v) for v in tr_e[:4]], TB_SCALARS, epoch)
 
-    def steps():      # one epoch of updates (main.py:641): the same permutation from `rng` on either route
+    def steps(epoch):      # one epoch of updates (main.py:641): the same permutation from `rng` on either route
+        if args.synth_fresh and epoch > 1:      # new scenes of the same poses, from a generator of their own: `rng` draws the batches of a run without it
+            for e in towers.engines:
+                ds_train[e.device].rerender_people(e, people['poses'], people['train_idx'], people_seed(args, epoch))
         if ds_train is not None:
             for batch_idx in ds_train[eng.device].epoch_indices(rng, args.batch_size, shuffle=True):
                 yield tt.train_step_indexed(ds_train, batch_idx)
@@ -588,7 +616,7 @@ def train_main(args):
     report(0)
     global_iter = 0
     for epoch in range(1, args.n_epochs + 1):
-        for _ in steps():
+        for _ in steps(epoch):
             global_iter += 1
             if tb and 'train_iter' in tb:       # main.py:642-645, without the images and without the activation summaries
                 from . import summary
@@ -664,13 +692,22 @@ SEQ_PEOPLE_RULES = (
     (lambda a: a.seq_torso_sigma is not None and not 0 < a.seq_torso_sigma < float('inf'), lambda a: '--seq_torso_sigma %g: CELLS > 0' % a.seq_torso_sigma),
     (lambda a: a.seq_exclude is not None and not 0 <= a.seq_exclude <= 64, lambda a: '--seq_exclude %d: 0 <= CELLS <= 64' % a.seq_exclude),
 )
+# The rules of --synth_people, walked behind SEQ_PEOPLE_RULES (a table of their own for the same reason).
+SYNTH_PEOPLE_RULES = (
+    (lambda a: a.synth_people and a.synthetic, SYNTH_PEOPLE_NOT_WITH_SYNTHETIC),
+    (lambda a: a.synth_people and a.predict, SYNTH_PEOPLE_NOT_WITH_PREDICT),
+    (lambda a: a.synth_fresh and not (a.train and a.device_data and a.u8_images and a.synth_people), SYNTH_FRESH_NEEDS_COMPANIONS),
+    (lambda a: a.synth_dump and not a.synth_people, SYNTH_DUMP_NEEDS_SYNTH_PEOPLE),
+    (lambda a: a.synth_people and poses_problem(a.synth_people) is not None,      # (poses_problem remembers its answer per path)
+     lambda a: '--synth_people %s: an [N,2,9] float64 array of at least five poses (data.py\'s xy) is expected; the file %s' % (a.synth_people, poses_problem(a.synth_people))),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too
