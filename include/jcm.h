@@ -356,6 +356,39 @@ int jcm_seq_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, 
 int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
                     int32_t* path, double* maxes, int32_t* breaks);
 
+/* -- frame sequences, offline: smoothed marginals and expected transition statistics -----------
+ * The third inference of the model above: gamma_t = P(x_t | all T frames) per (s, k), and from the same backward pass the posterior mass of
+ * "moved" and of "jumped" and the expected squared displacement of every transition, from which sigma (per joint) and rho are re-estimated on
+ * the host (Baum-Welch).  hm, taps, R, rho, om and u exactly as for jcm_seq_filter; there is no state_in: smoothing is offline.  All arithmetic
+ * is float64, one correctly rounded operation per step, evaluated as written; "sum" below is the sum Z of the filter, in its order.
+ * Forward: the recurrence of jcm_seq_filter, bit for bit (the library has one copy of it); norm and reset are what the filter writes, and every
+ * a_t is kept as float64 [S*K][T][HW] in the handle's workspace.
+ * Backward, beta_{T-1} = 1; for t = T-1 .. 0:
+ *   g = a_t * beta_t;   G = sum of g;   gamma_t = g / G
+ *   G == 0 or not finite: gamma_t = a_t, cut = 1, and beta_t is taken as 1 from here on back (the future is dropped)
+ *   t >= 1 and reset[t] == 0, an ordinary transition, with w2[j] = (double)((j-R)*(j-R)) * w[j] and Z_t = norm[t]:
+ *     q = p_t * beta_t;   Q = sum of q
+ *     c(y,x)  = sum over dy = -R .. R, ascending from 0.0, of w[dy+R]  * q(y+dy, x)      terms outside the map skipped; the ADJOINT index of
+ *     c2(y,x) = sum over dy = -R .. R, ascending from 0.0, of w2[dy+R] * q(y+dy, x)      the filter's, so that asymmetric taps are right
+ *     m(y,x)  = sum over dx = -R .. R, ascending from 0.0, of w[dx+R]  * c(y, x+dx)
+ *     sx(y,x) = sum over dx of w2[dx+R] * c(y, x+dx);   sy(y,x) = sum over dx of w[dx+R] * c2(y, x+dx);   sq = sx + sy
+ *     uQ = u * Q;   beta_{t-1} = (om * m + uQ) / Z_t
+ *     trans[s,t,k,:] = ( (om * sum of a_{t-1} * m) / Z_t,  uQ / Z_t,  (om * sum of a_{t-1} * sq) / Z_t ):  the posterior mass of "moved", of
+ *     "jumped", and the expected squared displacement in cells^2 over the moves
+ *   t >= 1 and reset[t] != 0 (frame t never saw frame t-1): beta_{t-1} = 1, trans[s,t,k,:] = 0.  trans[s,0,k,:] = 0.
+ * Outputs (device):  smoothed fp32 [S,T,HH,WW,K] = (float)gamma_t, may be NULL;  coords int32 [S,T,2,K], the first-occurrence flat arg-max of
+ *   the float64 gamma_t as (row, col) in the layout of jcm_argmax_coords, required;  conf fp32 [S,T,K] = (float)gamma_t at that cell;  norm
+ *   float64 [S,T,K] and reset int32 [S,T,K] as jcm_seq_filter writes them;  mass float64 [S,T,K] = G, a diagnostic that is 1 in exact
+ *   arithmetic;  cut int32 [S,T,K];  trans float64 [S,T,K,3], per frame -- the caller adds them up, so nothing on the device depends on T's
+ *   summation order.  All but coords may be NULL.
+ * One work group per (s, k) in both launches; the backward launch keeps three float64 planes in LDS for all T frames, so HH * WW <= 6144 here
+ * (144 KB plus the reduction scratch of the 160 KB; 60 x 90 fits): a larger map is JCM_ERR_ARG, never truncated.  Every other refusal is that
+ * of jcm_seq_filter.  JCM_ERR_STATE, with the bytes it needs in the message, when the beliefs (8 bytes per sequence, joint, frame and cell) do
+ * not fit the workspace the device can still give; split the clip then.  Enqueues on the handle's stream and does not synchronise (growing the
+ * workspace does). */
+int jcm_seq_smooth(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                   float* smoothed, int32_t* coords, float* conf, double* norm, int32_t* reset, double* mass, int32_t* cut, double* trans);
+
 /* -- several tracks through single-channel maps: one torso track per person of a clip ----------
  * hm: device fp32 [S,T,HH,WW], one non-negative channel (the torso probabilities of the frames); M in 1..4 tracks; taps HOST [2R+1], R and rho as for
  * jcm_seq_* with one tap row; D in 0..64, the exclusion half-width in cells.

@@ -430,6 +430,13 @@ hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, cons
 // amax int32 [S*K][T] (the arg-max of every frame's d).  Two launches: the scan, then the backtrace (one lane per (sequence, joint)).
 hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, int16_t* bp, int32_t* amax,
                        int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
+// ---- seq_smooth.hip : the smoothed marginals and the expected transition statistics --
+// Two launches, one work group per (sequence, joint) each: the filter's scan (seq_scan.h) that also writes every a_t to belief float64 [S*K][T][HH*WW],
+// then the backward scan with three float64 planes in LDS for all T frames, so HH * WW <= kSeqSmoothMaxHW (3 * 48 KB + the reduction scratch of 160 KB).
+// norm and reset are required here (the backward launch reads them); smoothed, conf, mass, cut and trans may be null.
+constexpr int kSeqSmoothMaxHW = 6144;
+hipError_t seq_smooth(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, double* belief, float* smoothed,
+                      int32_t* coords, float* conf, double* norm, int32_t* reset, double* mass, int32_t* cut, double* trans, hipStream_t st);
 // ---- seq_tracks.hip : several torso tracks through single-channel maps -------------
 // hm [S,T,HH,WW]; M in 1..4 passes of the scan above at K = 1 (seq_scan.h), pass n with the cells within D of the tracks m < n zeroed while the frame is
 // staged; one work group per clip and pass, the passes in stream order.  taps: DEVICE [2R+1].  Outputs [S,M,..] in the layouts of jcm.h.

@@ -103,12 +103,13 @@ __device__ __forceinline__ void sq_block_argmax(double& bv, int& bi, double* rd,
 }
 
 // The filter of one group: it reads sequence s_in of hm, channel k, and writes as sequence s_out of the outputs (the two differ only for the tracks).
-// sq_planes: A [HW], C [HW] of dynamic LDS.
+// sq_planes: A [HW], C [HW] of dynamic LDS.  belief: the group's own float64 [T][HW], every a_t as it is divided (what the smoother's backward launch
+// reads, seq_smooth.hip), or null.
 template <class Tr>
 __device__ __forceinline__ void sq_filter_scan(double* sq_planes, const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
                                                int R, double om, double u, const double* __restrict__ state_in, float* __restrict__ filtered,
                                                int32_t* coords, double* __restrict__ norm, int32_t* __restrict__ reset, double* __restrict__ state_out,
-                                               int vec, int s_in, int s_out, int k, const Tr& tr) {
+                                               int vec, int s_in, int s_out, int k, const Tr& tr, double* __restrict__ belief = nullptr) {
   __shared__ double w[kSqTaps];
   __shared__ double rd[kSqWaves];
   __shared__ int ri[kSqWaves];
@@ -170,6 +171,7 @@ __device__ __forceinline__ void sq_filter_scan(double* sq_planes, const float* _
       A[i] = a;
       if (a > bv) { bv = a; bi = i; }
       if (filtered) filtered[(ft * HW + i) * K + k] = (float)a;
+      if (belief) belief[(size_t)t * HW + i] = a;
     }
     sq_block_argmax(bv, bi, rd, ri, tid);      // its barriers also order this frame's A against the next vertical pass
     if (tid == 0) {

@@ -1,0 +1,231 @@
+// Frame sequences, offline: the smoothed posterior P(x_t | all T frames) of the hidden position of every (sequence, joint) and the
+// expected transition statistics that re-estimate sigma and rho (Baum-Welch; the M-step is host code, predict.seq_fit).  All arithmetic is float64, one
+// correctly rounded operation per step, in the order include/jcm.h states; no atomics.
+// Two launches, one work group per (sequence, joint) each.  The forward launch is the filter's scan itself (seq_scan.h: sq_filter_scan), which here also
+// writes every a_t as float64 [S*K][T][HW] to the workspace.  The backward launch keeps three float64 planes in LDS for all T frames:
+//   B   beta_t, then q = p_t * beta_t (staged in place, the staging of the filter with a functor), then beta_{t-1}
+//   C   g = a_t * beta_t until gamma_t is out; then the vertical pass of q with the taps w
+//   C2  the vertical pass of q with w2[j] = (j - R)^2 w[j]
+// The passes use the ADJOINT index of the filter's (q(y + dy, x), c(y, x + dx)): beta_{t-1}(x') sums over where the position goes, not where it came
+// from.  Consecutive lanes read consecutive cells of a row dy away, as in the filter's vertical pass: conflict-free ds_read_b64.  A cell i belongs to
+// thread i % 1024 in every pass that writes it, so a plane is only read across threads between barriers; every sum is sq_block_sum's.
+#include <string>
+
+#include "seq_scan.h"
+
+namespace jcm {
+
+namespace {
+
+constexpr int kSmLdsMax = 3 * kSeqSmoothMaxHW * 8;
+
+// The staging functor of q = p_t * beta_t: the plane holds beta_t where the widened p_t arrives.  It reads the very plane sq_stage writes through its
+// `__restrict__ plane`, which holds only because of how sq_stage visits a plane: every cell is read exactly once, by the thread that then stores it, as an
+// operand of that store, and no cell is read or written a second time within the call.  A change to sq_stage that touches a cell twice (a prefetch of
+// plane values, a second pass) must drop the in-place use here.
+struct SqTimes {
+  const double* plane;
+  __device__ __forceinline__ double operator()(int p, double v) const { return v * plane[p]; }
+};
+
+__global__ __launch_bounds__(kSqThreads) void seq_smooth_fwd_kernel(const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
+                                                                    int R, double om, double u, int32_t* __restrict__ coords, double* __restrict__ norm,
+                                                                    int32_t* __restrict__ reset, double* __restrict__ belief, int vec) {
+  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // A [HW], C [HW]
+  const int s = blockIdx.x / K, k = blockIdx.x - s * K;
+  // the scan needs a coords buffer: the caller's holds the FILTER's arg-max until the backward launch, next on the stream, overwrites every entry
+  sq_filter_scan(sq_planes, hm, T, HH, WW, K, taps, R, om, u, nullptr, nullptr, coords, norm, reset, nullptr, vec, s, s, k, SqPlain(),
+                 belief + (size_t)blockIdx.x * T * HH * WW);
+}
+
+__global__ __launch_bounds__(kSqThreads) void seq_smooth_bwd_kernel(const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
+                                                                    int R, double om, double u, const double* __restrict__ belief,
+                                                                    const double* __restrict__ norm, const int32_t* __restrict__ reset,
+                                                                    float* __restrict__ smoothed, int32_t* __restrict__ coords, float* __restrict__ conf,
+                                                                    double* __restrict__ mass, int32_t* __restrict__ cut, double* __restrict__ trans, int vec) {
+  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // B [HW], C [HW], C2 [HW]
+  __shared__ double w[kSqTaps];
+  __shared__ double w2[kSqTaps];
+  __shared__ double rd[kSqWaves];
+  __shared__ int ri[kSqWaves];
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x / K, k = blockIdx.x - s * K;
+  const int HW = HH * WW, n = HW * K;
+  double* B = sq_planes;
+  double* C = sq_planes + HW;
+  double* C2 = sq_planes + 2 * (size_t)HW;
+  if (tid < 2 * R + 1) {
+    const double wv = taps[k * (2 * R + 1) + tid];
+    w[tid] = wv;
+    w2[tid] = (double)((tid - R) * (tid - R)) * wv;
+  }
+  for (int i = tid; i < HW; i += kSqThreads) B[i] = 1.0;
+  __syncthreads();
+  const double* ag = belief + (size_t)blockIdx.x * T * HW;
+
+  for (int t = T - 1; t >= 0; --t) {
+    const size_t ft = (size_t)s * T + t;
+    const double* at = ag + (size_t)t * HW;
+    double gp = 0.0;
+    for (int i = tid; i < HW; i += kSqThreads) {
+      const double g = at[i] * B[i];
+      C[i] = g;
+      gp = gp + g;
+    }
+    const double G = sq_block_sum(gp, rd, tid);
+    const bool bad = !(G > 0.0 && G <= 1.79769313486231570815e308);      // 0 or not finite: the future is dropped (thread-uniform: G is)
+    double bv = -1.0;
+    int bi = kSqNone;
+    for (int i = tid; i < HW; i += kSqThreads) {
+      const double gam = bad ? at[i] : C[i] / G;
+      if (bad) B[i] = 1.0;
+      if (gam > bv) { bv = gam; bi = i; }
+      if (smoothed) smoothed[(ft * HW + i) * K + k] = (float)gam;
+    }
+    sq_block_argmax(bv, bi, rd, ri, tid);      // its barriers also order B against the staging below
+    if (tid == 0) {
+      bi = min(max(bi, 0), HW - 1);
+      const int r = bi / WW;
+      coords[(ft * 2 + 0) * K + k] = r;
+      coords[(ft * 2 + 1) * K + k] = bi - r * WW;
+      if (conf) conf[ft * K + k] = (float)bv;
+      if (mass) mass[ft * K + k] = G;
+      if (cut) cut[ft * K + k] = bad ? 1 : 0;
+    }
+    double tm = 0.0, tj = 0.0, ts = 0.0;
+    if (t >= 1) {
+      if (reset[ft * K + k] != 0) {      // frame t never saw frame t-1 (thread-uniform)
+        for (int i = tid; i < HW; i += kSqThreads) B[i] = 1.0;
+      } else {
+        const double Z = norm[ft * K + k];
+        sq_stage(hm + ft * n, n, K, k, vec != 0, B, tid, SqTimes{B});
+        __syncthreads();
+        double qp = 0.0;
+        for (int i = tid; i < HW; i += kSqThreads) qp = qp + B[i];
+        const double Q = sq_block_sum(qp, rd, tid);
+        for (int i = tid; i < HW; i += kSqThreads) {
+          const int y = i / WW;
+          const int lo = max(-R, -y), hi = min(R, HH - 1 - y);
+          double acc = 0.0, acc2 = 0.0;
+          for (int dy = lo; dy <= hi; ++dy) {
+            const double q = B[i + dy * WW];
+            acc = acc + w[dy + R] * q;
+            acc2 = acc2 + w2[dy + R] * q;
+          }
+          C[i] = acc;
+          C2[i] = acc2;
+        }
+        __syncthreads();
+        const double uQ = u * Q;
+        const double* am = ag + (size_t)(t - 1) * HW;
+        double mp = 0.0, sp = 0.0;
+        for (int i = tid; i < HW; i += kSqThreads) {
+          const int y = i / WW, x = i - y * WW;
+          const int lo = max(-R, -x), hi = min(R, WW - 1 - x);
+          double m = 0.0, sx = 0.0, sy = 0.0;
+          for (int dx = lo; dx <= hi; ++dx) {
+            const double c = C[i + dx], c2 = C2[i + dx];
+            m = m + w[dx + R] * c;
+            sx = sx + w2[dx + R] * c;
+            sy = sy + w[dx + R] * c2;
+          }
+          const double sq = sx + sy;
+          const double a = am[i];
+          mp = mp + a * m;
+          sp = sp + a * sq;
+          B[i] = (om * m + uQ) / Z;
+        }
+        const double M1 = sq_block_sum(mp, rd, tid);
+        const double M2 = sq_block_sum(sp, rd, tid);      // the barriers of the two sums also order B, C and C2 against the next frame
+        tm = (om * M1) / Z;
+        tj = uQ / Z;
+        ts = (om * M2) / Z;
+      }
+    }
+    if (trans && tid == 0) {
+      trans[(ft * K + k) * 3 + 0] = tm;
+      trans[(ft * K + k) * 3 + 1] = tj;
+      trans[(ft * K + k) * 3 + 2] = ts;
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t seq_smooth(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, double* belief, float* smoothed,
+                      int32_t* coords, float* conf, double* norm, int32_t* reset, double* mass, int32_t* cut, double* trans, hipStream_t st) {
+  if (!sq_sizes_ok(S, T, HH, WW, K, R) || (int64_t)HH * WW > kSeqSmoothMaxHW || !belief || !coords || !norm || !reset) return hipErrorInvalidValue;
+  const int HW = HH * WW;
+  const int vec = sq_vec(hm, HW, K) ? 1 : 0;
+  static LdsAttr fwd_attr, bwd_attr;
+  if (hipError_t e = fwd_attr.ensure(reinterpret_cast<const void*>(seq_smooth_fwd_kernel), kSqLdsMax); e != hipSuccess) return e;
+  if (hipError_t e = bwd_attr.ensure(reinterpret_cast<const void*>(seq_smooth_bwd_kernel), kSmLdsMax); e != hipSuccess) return e;
+  hipLaunchKernelGGL(seq_smooth_fwd_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8, st, hm, T, HH, WW, K, taps, R, om, u, coords, norm, reset, belief, vec);
+  hipLaunchKernelGGL(seq_smooth_bwd_kernel, dim3(S * K), dim3(kSqThreads), 3 * HW * 8, st, hm, T, HH, WW, K, taps, R, om, u, belief, norm, reset, smoothed,
+                     coords, conf, mass, cut, trans, vec);
+  return hipGetLastError();
+}
+
+}  // namespace jcm
+
+using namespace jcm;
+
+namespace {
+
+// the argument rules of jcm_seq_filter with this entry point's own map limit
+int smooth_check(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho) {
+  const std::string w("seq_smooth");
+  if (S < 1 || T < 1 || HH < 1 || WW < 1 || K < 1) return fail(JCM_ERR_ARG, w + ": bad sizes (S, T, HH, WW, K >= 1)");
+  if (K > kSeqMaxK) return fail(JCM_ERR_ARG, w + ": K = " + std::to_string(K) + " joints; K <= 16");
+  if (R < 0 || R > kSeqMaxR) return fail(JCM_ERR_ARG, w + ": R = " + std::to_string(R) + "; 0 <= R <= 16");
+  if (!(rho >= 0.0 && rho <= 1.0)) return fail(JCM_ERR_ARG, w + ": rho outside [0, 1]");
+  if ((int64_t)HH * WW > kSeqSmoothMaxHW)
+    return fail(JCM_ERR_ARG, w + ": a map of " + std::to_string(HH) + " x " + std::to_string(WW) +
+                                 " cells; HH * WW <= 6144 (three float64 planes in 160 KB of LDS), a larger map is not truncated");
+  if ((int64_t)S * T >= ((int64_t)1 << 31) / K) return fail(JCM_ERR_ARG, w + ": bad sizes (S * T * K < 2^31)");
+  if (!hm || !taps) return fail(JCM_ERR_ARG, w + ": null pointer (hm and taps are required)");
+  return JCM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jcm_seq_smooth(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho, float* smoothed,
+                   int32_t* coords, float* conf, double* norm, int32_t* reset, double* mass, int32_t* cut, double* trans) {
+  JCM_TRY(check(h, false));
+  JCM_TRY(smooth_check(hm, S, T, HH, WW, K, taps, R, rho));
+  if (!coords)
+    return fail(JCM_ERR_ARG, "seq_smooth: null pointer (coords is required; smoothed, conf, norm, reset, mass, cut and trans may be NULL)");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  // every a_t, float64 per (sequence, joint, frame, cell): the workspace grows to hold them, and a clip they cannot fit in is refused
+  const double need_d = (double)S * K * T * HH * WW * 8.0 + (double)S * K * T * 12.0 + 8192.0;
+  if (need_d > (double)c->arena_cap) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need_d > (double)free_b + (double)c->arena_cap)
+      return fail(JCM_ERR_STATE, "seq_smooth: the beliefs of " + std::to_string(S) + " x " + std::to_string(T) + " frames need " +
+                                     std::to_string((unsigned long long)need_d) + " bytes of workspace, " +
+                                     std::to_string((unsigned long long)(free_b + c->arena_cap)) + " bytes are available; split the clip");
+  }
+  const double om = 1.0 - rho, u = rho / (double)(HH * WW);
+  return with_arena(c, [&] {
+    double* dtaps = arena_alloc<double>(c, (size_t)K * (2 * R + 1));
+    double* belief = arena_alloc<double>(c, (size_t)S * K * T * HH * WW);
+    double* norm_w = norm ? norm : arena_alloc<double>(c, (size_t)S * T * K);
+    int32_t* reset_w = reset ? reset : arena_alloc<int32_t>(c, (size_t)S * T * K);
+    if (c->dry) return (int)JCM_OK;
+    hipEvent_t e0, e1;
+    JCM_TRY(prof_begin(c, &e0, &e1));
+    hipError_t launch = seq_put_taps(taps, K * (2 * R + 1), dtaps, c->stream);
+    if (launch == hipSuccess)
+      launch = seq_smooth(hm, S, T, HH, WW, K, dtaps, R, om, u, belief, smoothed, coords, conf, norm_w, reset_w, mass, cut, trans, c->stream);
+    prof_end(c, "seq_smooth", e0, e1, launch == hipSuccess);
+    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("seq_smooth: ") + hipGetErrorString(launch));
+    return (int)JCM_OK;
+  });
+}
+
+}  // extern "C"

@@ -260,3 +260,16 @@ def render_people(engine, poses, indices, seed, image_dtype='uint8', batch=64, *
         ys.append(y)
         cs.append(cells)
     return x, np.concatenate(ys), np.concatenate(cs)
+
+
+def render_clip(engine, rng, pose_a, pose_b, T, other_xy=None, H=480, W=720, cuts=(), image_dtype='uint8', **ranges):
+    """A clip of rendered people: the T frames synth.people_clip(rng, pose_a, pose_b, T, other_xy, H, W, cuts, **ranges) lists,
+    drawn by ONE Engine.synth_people call -> (x device [T,H,W,3], uint8 or float32 = byte / 255; records int32 [T,20]; prims int32 [NP,16]; xy
+    float64 [T,2,9], the annotated person's joints (x, y) of every frame).  No kernel of its own: a clip is a batch whose scenes share everything
+    but one person's joints -- the sensor noise too, whose seed is the record's."""
+    from . import synth
+    if image_dtype not in ('float32', 'uint8'):
+        raise ValueError("image_dtype must be 'float32' or 'uint8', got %r" % (image_dtype,))
+    records, prims, xy = synth.people_clip(rng, pose_a, pose_b, T, other_xy, H, W, cuts, **ranges)
+    x = engine.synth_people(records, prims, H, W, dtype=torch.uint8 if image_dtype == 'uint8' else torch.float32)
+    return x, records, prims, xy

@@ -395,6 +395,32 @@ class Engine:
                                              self._p(out['path']), self._p(out['maxes']), self._p(out['breaks'])), 'jcm_seq_viterbi')
         return {k: v[0] for k, v in out.items()} if single else out
 
+    def seq_smooth(self, hm, sigma, rho, radius=None, want_smoothed=True):
+        """The smoothed marginals P(x_t | all frames) of a clip's heat maps and the expected transition statistics of the backward pass (DESIGN.md
+        4.23, include/jcm.h: jcm_seq_smooth); hm, sigma, rho and radius as for seq_filter, offline (no state).  Returns {'smoothed' fp32 like hm
+        (left out with want_smoothed=False), 'coords' int32 [S,T,2,K] (row, col), 'conf' fp32 [S,T,K] (the marginal at that cell), 'norm' float64
+        [S,T,K] and 'reset' int32 [S,T,K] (the filter's), 'mass' float64 [S,T,K], 'cut' int32 [S,T,K], 'trans' float64 [S,T,K,3] (moved, jumped,
+        squared displacement; row 0 is zero)}, device tensors without the S axis for a 4-d hm; nothing is read back.  HH * WW <= 6144 here; the
+        float64 beliefs of all frames live in the engine's workspace, and a clip they do not fit in is a RuntimeError that names the bytes."""
+        hm5, single, taps, R = self._seq_args(hm, sigma, radius)
+        S, T, HH, WW, K = hm5.shape
+        out = {'coords': self._new(S, T, 2, K, dtype=torch.int32), 'conf': self._new(S, T, K), 'norm': self._new(S, T, K, dtype=torch.float64),
+               'reset': self._new(S, T, K, dtype=torch.int32), 'mass': self._new(S, T, K, dtype=torch.float64), 'cut': self._new(S, T, K, dtype=torch.int32),
+               'trans': self._new(S, T, K, 3, dtype=torch.float64)}
+        if want_smoothed:
+            out['smoothed'] = self._new(S, T, HH, WW, K)
+        self._on_stream(hm5, *out.values())
+        _lib.check(self._lib.jcm_seq_smooth(self._h, self._p(hm5), S, T, HH, WW, K, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R, float(rho),
+                                            self._p(out.get('smoothed')), self._p(out['coords']), self._p(out['conf']), self._p(out['norm']),
+                                            self._p(out['reset']), self._p(out['mass']), self._p(out['cut']), self._p(out['trans'])), 'jcm_seq_smooth')
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def seq_fit(self, hm, sigma=None, rho=None, iters=10, radius=16, fit_rho=True):
+        """predict.seq_fit on this engine: sigma per joint and rho re-estimated on the clip's own maps (EM, one seq_smooth per iteration)."""
+        from . import predict
+        return predict.seq_fit(self, hm, predict.SEQ_SIGMA if sigma is None else sigma, predict.SEQ_RHO if rho is None else rho, iters=iters, radius=radius,
+                               fit_rho=fit_rho)
+
     def seq_tracks(self, hm, people, sigma, rho, radius=None, exclude=SEQ_EXCLUDE, mode='viterbi', state=None, want_filtered=False):
         """Several consistent tracks through single-channel maps -- one torso per person of a clip (include/jcm.h:
         jcm_seq_tracks_viterbi / jcm_seq_tracks_filter).  hm [T,HH,WW] or [S,T,HH,WW], non-negative (spatial_softmax of the torso energy);

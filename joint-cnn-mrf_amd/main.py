@@ -119,14 +119,19 @@ def build_parser():
                         'joints with --use_sm (a zoomed person\'s from the second pass), the part detector\'s otherwise.  The JSON line gains render_ms.')
     parser.add_argument('--render_heat', default=None, choices=['pd', 'sm'], help='with --render: tint the images with the heat maps of the part detector (pd) or '
                         'of the spatial model (sm, needs --use_sm) under the skeleton, every joint in the colour the reference\'s overlays give it.')
-    parser.add_argument('--sequence', default=None, choices=['filter', 'viterbi'], help='with --predict: the expanded paths, in their sorted order, are the frames '
+    parser.add_argument('--sequence', default=None, choices=['filter', 'viterbi', 'marginal'], help='with --predict: the expanded paths, in their sorted order, are the frames '
                         'of ONE clip (all of one size); every image of the document gains "track", one position per joint that is consistent over the clip '
-                        '(predict.predict_sequence, DESIGN.md 4.19): filter = the causal forward filter, viterbi = the most probable track.  With --render the '
-                        'tracked skeleton is drawn.  What tracking buys with trained weights has not been measured.')
+                        '(predict.predict_sequence, DESIGN.md 4.19): filter = the causal forward filter, viterbi = the most probable track, marginal = the arg-max of every frame\'s '
+                        'smoothed posterior given all frames, with its confidence (DESIGN.md 4.23; not with --seq_people).  With --render the tracked '
+                        'skeleton is drawn.  What tracking buys has been measured on rendered clips only (DESIGN.md 4.23).')
     parser.add_argument('--seq_sigma', type=float, nargs='+', default=None, metavar='CELLS', help='with --sequence: the standard deviation of a joint\'s motion per '
-                        'frame in heat-map cells, one value or one per joint (default 1.5, an untuned placeholder).')
+                        'frame in heat-map cells, one value or one per joint (default 1.5, an untuned placeholder), for filter, viterbi and marginal alike; --seq_fit starts from it.')
     parser.add_argument('--seq_rho', type=float, default=None, metavar='RHO', help='with --sequence: the mass in [0,1] of the uniform "anywhere" term that absorbs '
-                        'misses and scene cuts (default 0.05, an untuned placeholder).')
+                        'misses and scene cuts (default 0.05, an untuned placeholder), for filter, viterbi and marginal alike; --seq_fit starts from it.')
+    parser.add_argument('--seq_fit', type=int, default=None, metavar='ITERS', help='with --sequence: first fit the motion model to the clip\'s own heat maps, without '
+                        'annotations -- ITERS (1..100) iterations of EM on the smoothed posteriors (predict.seq_fit, DESIGN.md 4.23), starting from --seq_sigma / '
+                        '--seq_rho or their defaults -- then run the chosen mode with the fitted sigma per joint and rho; the JSON line gains seq_fit.  Not with '
+                        '--seq_people.')
     parser.add_argument('--seq_people', type=int, default=None, metavar='M', help='with --sequence, --predict and --use_sm: a clip with up to M (1..4) people in it '
                         '(predict.predict_sequence_people, DESIGN.md 4.21): M consistent torso tracks are pulled out of the frames\' torso maps, the spatial model '
                         'runs once per frame and track, and every person\'s joints are tracked; every image of the document gains "tracks" ("track" is track 0) '
@@ -349,6 +354,9 @@ SEQUENCE_ONE_PERSON = '--sequence tracks one person: --people M > 1 would need a
 SEQ_OPTION_NEEDS_SEQUENCE = '--seq_sigma and --seq_rho set the motion model of --sequence: give --sequence filter or --sequence viterbi as well'
 SEQ_PEOPLE_NEEDS_SEQUENCE = '--seq_people tracks the people of the clip --sequence names: give --sequence filter or --sequence viterbi as well'
 SEQ_PEOPLE_NEEDS_USE_SM = '--seq_people needs --use_sm: the torso tracks come from the inferred torso map and every person is one run of the spatial model'
+SEQ_MARGINAL_NO_PEOPLE = '--sequence marginal cannot be combined with --seq_people: the torso tracks have the filter and Viterbi only'
+SEQ_FIT_NEEDS_SEQUENCE = '--seq_fit fits the motion model of --sequence to the clip: give --sequence filter, viterbi or marginal as well'
+SEQ_FIT_NO_PEOPLE = '--seq_fit cannot be combined with --seq_people: the fit is that of one person\'s joint maps'
 SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
@@ -384,6 +392,8 @@ def predict_main(args):
             seq = dict(mode=args.sequence, sigma=sigma[0] if isinstance(sigma, list) and len(sigma) == 1 else sigma,
                        rho=predict.SEQ_RHO if args.seq_rho is None else args.seq_rho, batch_size=args.batch_size, keep_maps=bool(args.render_heat),
                        peaks=args.peaks, decode=args.decode_pose, timing=timing)
+            if args.seq_fit is not None:
+                seq.update(fit_iters=args.seq_fit)
             if args.seq_people is not None:
                 results = predict.predict_sequence_people(eng, images, args.seq_people, exclude=predict.SEQ_EXCLUDE if args.seq_exclude is None else args.seq_exclude,
                                                           torso_sigma=predict.SEQ_TORSO_SIGMA if args.seq_torso_sigma is None else args.seq_torso_sigma, **seq)
@@ -404,6 +414,9 @@ def predict_main(args):
             'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}
     if args.sequence:
         line.update(sequence=args.sequence)
+    if args.seq_fit is not None:
+        fit = results[0]['seq_fit']
+        line.update(seq_fit={'sigma': fit['sigma'].tolist(), 'rho': fit['rho'], 'loglik': fit['loglik'].tolist(), 'clamped': fit['clamped'].tolist()})
     if args.seq_people is not None:
         line.update(seq_people=args.seq_people, seq_torso_ms=timing['seq_torso_ms'], seq_people_sm_ms=timing['seq_people_sm_ms'])
     if args.zoom:
@@ -701,13 +714,20 @@ SYNTH_PEOPLE_RULES = (
     (lambda a: a.synth_people and poses_problem(a.synth_people) is not None,      # (poses_problem remembers its answer per path)
      lambda a: '--synth_people %s: an [N,2,9] float64 array of at least five poses (data.py\'s xy) is expected; the file %s' % (a.synth_people, poses_problem(a.synth_people))),
 )
+# The rules of --sequence marginal and --seq_fit, walked behind SYNTH_PEOPLE_RULES (a table of their own for the same reason).
+SEQ_SMOOTH_RULES = (
+    (lambda a: a.seq_fit is not None and not a.sequence, SEQ_FIT_NEEDS_SEQUENCE),
+    (lambda a: a.seq_fit is not None and not 1 <= a.seq_fit <= 100, lambda a: '--seq_fit %d: 1 <= ITERS <= 100' % a.seq_fit),
+    (lambda a: a.seq_fit is not None and a.seq_people is not None, SEQ_FIT_NO_PEOPLE),
+    (lambda a: a.sequence == 'marginal' and a.seq_people is not None, SEQ_MARGINAL_NO_PEOPLE),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

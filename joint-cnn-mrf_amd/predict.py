@@ -15,13 +15,17 @@ under them -- onto the images at their own size through Engine.render_poses.
 
 Frame sequences: predict_sequence takes the frames of a clip, all of one size, and adds to every frame's result a 'track': one
 position per joint that is consistent over the clip, from Engine.seq_filter (causal) or Engine.seq_viterbi (the most probable track) on the
-stacked heat maps.  SequenceTracker is the online form of the filter.  SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what tracking buys
-with trained weights has not been measured.
+stacked heat maps.  SequenceTracker is the online form of the filter.  SEQ_SIGMA and SEQ_RHO are not fitted to anything; what tracking buys has
+been measured on rendered clips only, not on real video.
 
 Clips with several people: predict_sequence_people pulls up to four consistent torso tracks out of the frames' torso maps
 (Engine.seq_tracks: successive passes of the temporal model, each with the earlier tracks' neighbourhoods excluded), runs the spatial model
 once per (frame, track) with the blob at the track's cell and tracks every person's joints; PeopleTracker is its online form.  SEQ_EXCLUDE and
-SEQ_TORSO_SIGMA are untuned placeholders too."""
+SEQ_TORSO_SIGMA are untuned placeholders too.
+
+Smoothed marginals and the fit: predict_sequence(mode='marginal') takes every frame's position from the smoothed posterior
+P(x_t | all frames) of Engine.seq_smooth, with its confidence; seq_fit re-estimates sigma (per joint) and rho on a clip's own maps by EM, without
+annotations, and predict_sequence(fit_iters=) runs any mode with the fitted values."""
 import os
 
 import numpy as np
@@ -46,6 +50,8 @@ SEQ_SIGMA = 1.5
 SEQ_RHO = 0.05
 SEQ_TORSO_SIGMA = 1.5                     # a torso's motion per frame in cells (predict_sequence_people): an untuned placeholder
 SEQ_RADIUS_MAX = 16                       # include/jcm.h: R of jcm_seq_filter / jcm_seq_viterbi
+SEQ_SIGMA_MAX = 64.0                      # what seq_fit clamps a joint's sigma to when its moment reaches that of flat taps (at R = 16 such taps are flat within 3 %)
+SEQ_MODES = ('filter', 'viterbi', 'marginal')
 IMAGE_EXTENSIONS = ('.npy', '.png', '.jpg', '.jpeg', '.bmp', '.gif', '.tif', '.tiff', '.webp', '.ppm')
 
 
@@ -299,12 +305,18 @@ def _one_size(frames):
 
 
 def _track_entries(seq, geom, mode):
-    """The dict of Engine.seq_filter / seq_viterbi on [T,HH,WW,K] maps and the frames' fit -> one 'track' dict per frame."""
-    cells = seq['coords' if mode == 'filter' else 'path']
+    """The dict of Engine.seq_filter / seq_viterbi / seq_smooth on [T,HH,WW,K] maps and the frames' fit -> one 'track' dict per frame."""
+    cells = seq['path' if mode == 'viterbi' else 'coords']
     pts, inside = fit_to_source(_coords_to_points(cells), geom)
-    value, flag = ('norm', 'reset') if mode == 'filter' else ('maxes', 'breaks')
-    v, f = seq[value].cpu().numpy(), seq[flag].cpu().numpy()
-    return [{'mode': mode, 'points': pts[t], 'inside': inside[t], value: v[t], flag: f[t]} for t in range(pts.shape[0])]
+    keys = {'filter': ('norm', 'reset'), 'viterbi': ('maxes', 'breaks'), 'marginal': ('conf', 'norm', 'reset', 'cut')}[mode]
+    host = {k: seq[k].cpu().numpy() for k in keys}
+    return [dict({'mode': mode, 'points': pts[t], 'inside': inside[t]}, **{k: host[k][t] for k in keys}) for t in range(pts.shape[0])]
+
+
+def _seq_call(engine, mode, hm, sigma, rho, radius):
+    if mode == 'marginal':
+        return engine.seq_smooth(hm, sigma, rho, radius=radius, want_smoothed=False)
+    return (engine.seq_filter if mode == 'filter' else engine.seq_viterbi)(hm, sigma, rho, radius=radius)
 
 
 def _seq_maps(results, use_sm):
@@ -312,19 +324,25 @@ def _seq_maps(results, use_sm):
 
 
 def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
-                     keep_maps=False, **kw):
+                     keep_maps=False, fit_iters=0, **kw):
     """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
     geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
-    [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal) or Engine.seq_viterbi (mode 'viterbi', the most probable
-    track); evaluation.fit_to_source maps the cells back.  Returns predict_images' dicts, every key with the value it has there, plus
+    [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal), Engine.seq_viterbi (mode 'viterbi', the most probable
+    track) or Engine.seq_smooth (mode 'marginal', the arg-max of every frame's smoothed posterior P(x_t | all frames), DESIGN.md 4.23);
+    evaluation.fit_to_source maps the cells back.  Returns predict_images' dicts, every key with the value it has there, plus
       'track': {'mode', 'points' float64 [K,2] (row, col) in the frame's own pixels, 'inside' bool [K], 'norm' or 'maxes' float64 [K], 'reset' or
-                'breaks' int [K]}  (the library's Z / M and its flags, include/jcm.h).
+                'breaks' int [K]}  (the library's Z / M and its flags, include/jcm.h); mode 'marginal': 'conf' float32 [K] (the posterior at the
+                point), 'norm', 'reset' and 'cut' int [K].
+    fit_iters = ITERS > 0 first re-estimates sigma (per joint) and rho on the clip's own maps (seq_fit below, starting from sigma and rho) and runs
+    the mode with the fitted values; frame 0's dict then carries 'seq_fit', seq_fit's return value for the clip.
     'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
     the defaults SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what the track buys with trained weights has not been measured.
     One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
     frame, are out of scope."""
-    if mode not in ('filter', 'viterbi'):
-        raise ValueError("mode must be 'filter' or 'viterbi', got %r" % (mode,))
+    if mode not in SEQ_MODES:
+        raise ValueError("mode must be 'filter', 'viterbi' or 'marginal', got %r" % (mode,))
+    if not 0 <= int(fit_iters) <= 100:
+        raise ValueError('fit_iters must be 0 (off) or the EM iterations 1..100, got %r' % (fit_iters,))
     if people != 1:
         raise ValueError('predict_sequence tracks one person: people=%r would need an association of people across frames, which is out of scope' % (people,))
     if zoom:
@@ -333,13 +351,103 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
     results = predict_images(engine, frames, use_sm=use_sm, batch_size=batch_size, keep_maps=True, **kw)
     with torch.cuda.stream(engine._stream):
         hm = _seq_maps(results, use_sm)
-        seq = (engine.seq_filter if mode == 'filter' else engine.seq_viterbi)(hm, sigma, rho, radius=radius)
+        fit = seq_fit(engine, hm, sigma, rho, iters=int(fit_iters)) if int(fit_iters) else None
+        if fit is not None:
+            sigma, rho = fit['sigma'], fit['rho']
+        seq = _seq_call(engine, mode, hm, sigma, rho, radius)
         geom = np.array([r['geom'] for r in results], np.int64)
         for r, track in zip(results, _track_entries(seq, geom, mode)):
             r['track'] = track
             if not keep_maps:
                 del r['maps']
+        if fit is not None:
+            results[0]['seq_fit'] = fit
     return results
+
+
+def seq_moment(sigma, radius):
+    """sum over d of d^2 w_sigma[d] of the truncated taps seq_taps builds: the 1-D second moment of the motion kernel, float64.  Monotone in sigma,
+    from 0 towards the flat taps' R (R + 1) / 3."""
+    R = int(radius)
+    d = np.arange(-R, R + 1, dtype=np.float64)
+    return float(np.sum(d * d * seq_taps(sigma, R, 1)[0]))
+
+
+def seq_sigma_of_moment(target, radius, sigma_max=SEQ_SIGMA_MAX):
+    """The M-step of one joint: the sigma whose truncated taps have seq_moment == target, by bisection in float64 -> (sigma, clamped).  A target at or
+    above the flat taps' R (R + 1) / 3 (no sigma reaches it), or one only a sigma above sigma_max reaches, gives (sigma_max, True); a target so small
+    that no representable taps have it gives the lower end of the bracket, 2^-6 cells."""
+    R = int(radius)
+    target = float(target)
+    if R < 1:
+        raise ValueError('a motion kernel of radius 0 has no sigma to fit')
+    if not target < R * (R + 1) / 3.0 or seq_moment(sigma_max, R) <= target:
+        return float(sigma_max), True
+    lo, hi = 2.0 ** -6, float(sigma_max)
+    if seq_moment(lo, R) >= target:
+        return lo, False
+    for _ in range(200):      # moment(lo) < target <= moment(hi) throughout
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            break
+        if seq_moment(mid, R) < target:
+            lo = mid
+        else:
+            hi = mid
+    return (lo if abs(seq_moment(lo, R) - target) <= abs(seq_moment(hi, R) - target) else hi), False
+
+
+def seq_m_step(trans_sum, sigma, rho, radius, fit_rho=True, sigma_max=SEQ_SIGMA_MAX):
+    """trans_sum float64 [K,3] = (moved, jumped, squared displacement) summed over sequences and frames; sigma [K], rho: the current values ->
+    (sigma' [K], rho', clamped bool [K]).  rho' = sum jumped / (sum moved + sum jumped) over all joints (rho when that is 0 / 0, or with
+    fit_rho=False); sigma_k' solves seq_moment(sigma_k') = squared_k / (2 moved_k) -- the displacement has two axes with the same taps -- and a
+    joint with moved_k == 0 keeps its sigma."""
+    tr = np.asarray(trans_sum, np.float64)
+    sigma = np.array(sigma, np.float64)
+    move, jump, sq = tr[:, 0], tr[:, 1], tr[:, 2]
+    total = move.sum() + jump.sum()
+    new_rho = float(jump.sum() / total) if fit_rho and total > 0 else float(rho)
+    new_sigma, clamped = sigma.copy(), np.zeros(sigma.shape, bool)
+    for k in range(sigma.size):
+        if move[k] > 0:
+            new_sigma[k], clamped[k] = seq_sigma_of_moment(sq[k] / (2.0 * move[k]), radius, sigma_max)
+    return new_sigma, min(max(new_rho, 0.0), 1.0), clamped
+
+
+def seq_fit(engine, hm, sigma=SEQ_SIGMA, rho=SEQ_RHO, iters=10, radius=16, fit_rho=True):
+    """Fit the motion model to a clip without annotations (Baum-Welch).  hm [T,HH,WW,K] or [S,T,HH,WW,K] device maps as for
+    Engine.seq_smooth; sigma (a scalar or K values) and rho are the start.  Each of the `iters` iterations is one Engine.seq_smooth at the current
+    values (E-step), whose 'trans' is read back and summed over s and t on the host in float64 (np.sum over the two axes), and seq_m_step
+    (M-step).  Returns {'sigma' float64 [K], 'rho' float, 'loglik' float64 [iters + 1] -- the sum over sequences, frames and joints of log norm
+    (frames with norm 0, reset 2, left out) at the values BEFORE each iteration and, last, at the returned ones (one more seq_smooth) --,
+    'history' [(sigma [K], rho)] * (iters + 1), the values the entries of loglik belong to, 'clamped' bool [K]: the joints whose sigma the last
+    M-step held at SEQ_SIGMA_MAX}.
+    What is approximate: the motion kernel is not renormalised at the map's border (cells outside contribute nothing), so the transition rows of
+    cells within `radius` of the border sum to less than 1 and the M-step -- exact EM for mass away from the border -- slightly overstates rho and
+    understates sigma for tracks along it; and the taps are truncated at `radius`, so no sigma explains a mean squared step of R (R + 1) / 3 per
+    axis or more: such a joint is clamped and reported.  radius is fixed over the iterations (16, the largest, by default) so that a growing sigma
+    is not cut off by the radius its start implied."""
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError('iters must be >= 1, got %r' % (iters,))
+    K = int(hm.shape[-1])
+    sg = np.array(_seq_sigma(sigma, K), np.float64)
+    rho = float(rho)
+    R = int(radius)
+    loglik, history = [], []
+    clamped = np.zeros(K, bool)
+
+    def e_step():
+        r = engine.seq_smooth(hm, sg, rho, radius=R, want_smoothed=False)
+        norm = r['norm'].cpu().numpy().reshape(-1)
+        loglik.append(float(np.sum(np.log(norm[norm > 0]))))
+        history.append((sg.copy(), rho))
+        return r['trans'].cpu().numpy().reshape(-1, K, 3).sum(axis=0)
+
+    for _ in range(iters):
+        sg, rho, clamped = seq_m_step(e_step(), sg, rho, R, fit_rho=fit_rho)
+    e_step()
+    return {'sigma': sg, 'rho': rho, 'loglik': np.array(loglik, np.float64), 'history': history, 'clamped': clamped}
 
 
 class SequenceTracker:
@@ -464,7 +572,7 @@ def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SI
     consecutive-frame data and no trained weights are at hand -- and what this buys with trained weights has not been measured.  zoom=True
     raises ValueError."""
     if mode not in ('filter', 'viterbi'):
-        raise ValueError("mode must be 'filter' or 'viterbi', got %r" % (mode,))
+        raise ValueError("mode must be 'filter' or 'viterbi', got %r (the torso tracks have the filter and Viterbi only)" % (mode,))
     _check_people(people, zoom)
     _one_size(frames)
     results = predict_images(engine, frames, use_sm=True, people=1, batch_size=batch_size, keep_maps=True, torso_prob=True, timing=timing, **kw)

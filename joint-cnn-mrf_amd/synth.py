@@ -277,10 +277,23 @@ def people_scene(rng, pose_xy, other_xy=None, H=480, W=720, **ranges):
       the clutter: the count, then per capsule (centre x, y, angle, length, radius, skin?, colour, texture amplitude, texture seed);
       the background: seed, c0, c1, the four amplitudes, the sensor-noise amplitude.
     Listing order, back to front: the second person, the clutter, the annotated person.  Geometry is rounded to sixteenths of a pixel last."""
+    sc = _scene_draw(rng, pose_xy, other_xy, H, W, _ranges(ranges))
+    record, prims = _scene_place(sc, sc['person'])
+    return record, prims, sc['J']
+
+
+def _ranges(ranges):
     unknown = set(ranges) - set(PEOPLE_DEFAULTS)
     if unknown:
         raise TypeError('people_scene: unknown ranges %s' % sorted(unknown))
-    rg = dict(PEOPLE_DEFAULTS, **ranges)
+    return dict(PEOPLE_DEFAULTS, **ranges)
+
+
+def _scene_draw(rng, pose_xy, other_xy, H, W, rg):
+    """Every draw of people_scene, in its order -> the scene before it is listed: the annotated person's joints 'J' and primitives 'person', 'move'
+    (the map of the plane that took the pose to J: a pose [2,9] of the 480x720 frame -> the H x W frame), 'look' (the generator's state just
+    before the person's _figure: replaying _figure from it with other joints gives the same clothes, skin, seeds and listing order, since none of
+    its draws depends on the joints), 'other', 'clutter', 'record' (its count and first index still 0) and the geometry."""
     f = min(H / 480.0, W / 720.0)
     frame_c, src_c = np.array([[(W - 1) / 2.0], [(H - 1) / 2.0]]), np.array([[719 / 2.0], [479 / 2.0]])
 
@@ -288,17 +301,27 @@ def people_scene(rng, pose_xy, other_xy=None, H=480, W=720, **ranges):
         return frame_c + f * (np.asarray(p, np.float64).reshape(2, 9) - src_c)
 
     J0 = to_frame(pose_xy)
-    J = None
+    J = move = None
     for _ in range(int(rg['tries'])):
         s = rng.uniform(*rg['scale'])
         mirror = rng.random_sample() < 0.5
         dx, dy = rng.uniform(-rg['shift'], rg['shift']) * W, rng.uniform(-rg['shift'], rg['shift']) * H
-        cand = _similarity(_mirror(J0, W) if mirror else J0, s, dx, dy)
+        base = _mirror(J0, W) if mirror else J0
+        cand = _similarity(base, s, dx, dy)
         if _inside(cand, H, W):
             J = cand
+            c = base.mean(axis=1, keepdims=True)      # the same similarity about the SAME centre, for another pose
+
+            def move(p, s=s, dx=dx, dy=dy, mirror=mirror, c=c):
+                q = to_frame(p)
+                return c + s * ((_mirror(q, W) if mirror else q) - c) + np.array([[dx], [dy]])
             break
     if J is None:
         J = J0 if _inside(J0, H, W) else _fit_inside(J0, H, W)
+
+        def move(p, J=J):      # the pose as it is: another pose keeps its offsets from this one
+            return J + (to_frame(p) - J0)
+    look = rng.get_state()
     person = _figure(rng, J, H, rg)
 
     other = []
@@ -337,7 +360,13 @@ def people_scene(rng, pose_xy, other_xy=None, H=480, W=720, **ranges):
     record[7:11] = [rng.randint(lo, hi + 1) for lo, hi in rg['bg_amp']]
     record[11:15] = SYNTH_SHIFTS
     record[15] = rng.randint(rg['noise'][0], rg['noise'][1] + 1)
-    listed = other + clutter + person
+    return dict(J=J, move=move, look=look, person=person, other=other, clutter=clutter, record=record, H=H, rg=rg)
+
+
+def _scene_place(sc, person, first=0):
+    """The scene listed with `person` as the annotated person's primitives -> (record int32 [20], prims int32 [n,16])."""
+    record = sc['record'].copy()
+    listed = sc['other'] + sc['clutter'] + person
     if len(listed) > SYNTH_PRIM_MAX:
         raise ValueError('people_scene: %d primitives, the kernel takes %d an image' % (len(listed), SYNTH_PRIM_MAX))
     record[16] = len(listed)
@@ -346,7 +375,51 @@ def people_scene(rng, pose_xy, other_xy=None, H=480, W=720, **ranges):
     for i, (kind, geo, col, tamp, ts, tseed) in enumerate(listed):
         g = np.clip(np.rint(np.asarray(geo, np.float64) * 16.0), -lim, lim)      # sixteenths of a pixel, last
         prims[i, 0], prims[i, 1:9], prims[i, 9:12], prims[i, 12:15] = kind, g.astype(np.int64), col, (tamp, ts, tseed)
-    return record, prims, J
+    record[17] = first
+    return record, prims
+
+
+def people_clip(rng, pose_a, pose_b, T, other_xy=None, H=480, W=720, cuts=(), **ranges):
+    """T frames of ONE scene of rendered people in which the annotated person moves -> (records int32 [T,20], prims int32 [NP,16],
+    xy float64 [T,2,9]); records[t, 17] is frame t's first row of prims, so Engine.synth_people draws the clip as it is.  The scene -- similarity,
+    look, clutter, background, second person, draw order -- is people_scene(rng, pose_a, other_xy, ...)'s, and frame 0 IS that scene, bit for bit
+    (and the generator is left where people_scene leaves it).  In frame t the annotated person's joints are A + (t / (T - 1)) * (B - A): A the
+    joints of frame 0, B pose_b under the same similarity -- brought towards A along the straight line by the least amount that keeps all nine
+    joints inside the frame, so that every frame's joints are known and inside.  The clothes, skin, texture seeds and listing order do not change:
+    _figure is replayed from the generator state saved before it with the frame's joints.  A frame index in `cuts` (1 .. T-1) starts a new
+    scene, drawn from the generator as it stands, with the same pose pair and the same t / (T - 1).  Everything else stands still, the sensor
+    noise included: its seed is the record's, so the noise pattern repeats from frame to frame within a scene."""
+    T = int(T)
+    cuts = sorted({int(c) for c in cuts})
+    if T < 1 or any(c < 1 or c >= T for c in cuts):
+        raise ValueError('people_clip: T >= 1 and cuts in 1 .. T-1 are expected, got T = %d, cuts = %s' % (T, cuts))
+    rg = _ranges(ranges)
+    records, prims, xy, first, sc = [], [], [], 0, None
+    replay = np.random.RandomState(0)
+    for t in range(T):
+        if t == 0 or t in cuts:
+            sc = _scene_draw(rng, pose_a, other_xy, H, W, rg)
+            A, B = sc['J'], sc['move'](pose_b)
+            lam = 1.0
+            for lo_side, hi_side, ax in ((0.0, W - 1.0, 0), (0.0, H - 1.0, 1)):      # A is inside: the largest share of the way to B that still is
+                for k in range(9):
+                    if B[ax, k] < lo_side:
+                        lam = min(lam, (A[ax, k] - lo_side) / (A[ax, k] - B[ax, k]))
+                    elif B[ax, k] > hi_side:
+                        lam = min(lam, (hi_side - A[ax, k]) / (B[ax, k] - A[ax, k]))
+            step = (lam * (1 - 1e-9) if lam < 1.0 else 1.0) * (B - A)
+        J = sc['J'] + (t / float(max(T - 1, 1))) * step
+        if t == 0:
+            person = sc['person']
+        else:
+            replay.set_state(sc['look'])
+            person = _figure(replay, J, H, rg)
+        r, p = _scene_place(sc, person, first)
+        first += p.shape[0]
+        records.append(r)
+        prims.append(p)
+        xy.append(J)
+    return np.stack(records), np.concatenate(prims).reshape(-1, SYNTH_PRIM_INTS), np.stack(xy)
 
 
 def people_batch(rng, poses, indices, H=480, W=720, second=True, **ranges):
