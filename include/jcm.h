@@ -356,6 +356,36 @@ int jcm_seq_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, 
 int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
                     int32_t* path, double* maxes, int32_t* breaks);
 
+/* -- frame sequences whose lattice moves: a whole-cell shift of the belief plane per frame ------
+ * jcm_seq_filter / jcm_seq_viterbi for maps that live in a window which moves with the person (the zoom pass of a clip): every argument as
+ * there, plus shift: device int32 [S,T,2] = (sy, sx), where frame t's lattice lies on frame t-1's: cell (y, x) of frame t is cell
+ * (y + sy, x + sx) of frame t-1.  The previous belief seen from frame t is a'(y,x) = a_{t-1}(y + sy, x + sx), 0 where that cell lies outside
+ * the map; a' is defined on every integer cell, also outside frame t's map, and the taps reach it there.  Nothing is interpolated, the planes
+ * in LDS do not grow, and it is the same one copy of each recurrence (csrc/seq_scan.h), instantiated with the shift.
+ * Filter:
+ *   c(y,x) = sum over dy = -R .. R, ascending from 0.0, of w[dy+R] * a_{t-1}(y - dy + sy, x)      terms outside the map skipped; c is indexed
+ *                                                                                                  (row of frame t, column of frame t-1)
+ *   m(y,x) = sum over dx = -R .. R, ascending from 0.0, of w[dx+R] * c(y, x - dx + sx)             terms outside the map skipped
+ *   pred, b, Z in the kernel's fixed order, resets, state_in / state_out and every output: exactly jcm_seq_filter.  shift[s,0] applies to the
+ *   transition from state_in (state_in is in the lattice of the frame before frame 0) and is ignored when state_in is NULL; state_out is in
+ *   frame T-1's lattice, coords[s,t] in frame t's own.
+ * Viterbi:
+ *   c(y,x) = max over dy of w[dy+R] * d_{t-1}(y - dy + sy, x),  m(y,x) = max over dx of w[dx+R] * c(y, x - dx + sx): the same ascending scans
+ *   over the terms inside the map and the same tie rules (the lowest dy, then the lowest dx); a maximum over no term is 0.
+ *   source cell = (y - dy*(y, x - dx* + sx) + sy, x - dx* + sx), a cell of frame t-1's lattice.  A cell with m == 0 has no source inside the
+ *   map: its b is 0 unless the jump wins, and the jump's source is its source (no path passes through a cell whose b is 0).
+ *   The jump, b, M, breaks and the backtrace are unchanged.  path[s,t] is in frame t's own lattice.  shift[s,0] is ignored.
+ * Any int32 shift is legal.  With |sy| >= HH + R or |sx| >= WW + R no tap reaches the map: pred is u alone for the filter, and for Viterbi the
+ * jump or a break takes over.  (For HH <= |sy| < HH + R the two maps share no cell, but a tap still reaches across, as the sums above say.)
+ * The tap loops run over clipped bounds and never index outside the plane; no term is multiplied by zero instead of being skipped.  An all-zero
+ * shift gives the bits of jcm_seq_filter / jcm_seq_viterbi.
+ * JCM_ERR_ARG / JCM_ERR_STATE as for the entries above, and JCM_ERR_ARG for shift == NULL. */
+int jcm_seq_filter_moving(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                          const int32_t* shift, const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset,
+                          double* state_out);
+int jcm_seq_viterbi_moving(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                           const int32_t* shift, int32_t* path, double* maxes, int32_t* breaks);
+
 /* -- frame sequences, offline: smoothed marginals and expected transition statistics -----------
  * The third inference of the model above: gamma_t = P(x_t | all T frames) per (s, k), and from the same backward pass the posterior mass of
  * "moved" and of "jumped" and the expected squared displacement of every transition, from which sigma (per joint) and rho are re-estimated on

@@ -423,13 +423,15 @@ constexpr int kSeqMaxHW = 8192;
 constexpr int kSeqMaxK = 16;
 constexpr int kSeqMaxR = 16;
 hipError_t seq_put_taps(const double* taps_host, int n, double* taps_dev, hipStream_t st);
-// the forward filter (jcm.h: jcm_seq_filter); state_in, filtered, norm, reset and state_out may be null
-hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const double* state_in,
-                      float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st);
+// the forward filter (jcm.h: jcm_seq_filter); state_in, filtered, norm, reset and state_out may be null.  shift: null, or device int32 [S][T][2], the
+// lattice of every frame relative to the one before (jcm.h: jcm_seq_filter_moving): the moving instantiation of the same scan.
+hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* shift,
+                      const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st);
 // the most probable track (jcm.h: jcm_seq_viterbi); workspace the caller provides: bp int16 [S*K][T][HH*WW] (the source cell of every cell, -1 = none),
 // amax int32 [S*K][T] (the arg-max of every frame's d).  Two launches: the scan, then the backtrace (one lane per (sequence, joint)).
-hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, int16_t* bp, int32_t* amax,
-                       int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
+// shift as for seq_filter (jcm.h: jcm_seq_viterbi_moving).
+hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* shift,
+                       int16_t* bp, int32_t* amax, int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
 // ---- seq_smooth.hip : the smoothed marginals and the expected transition statistics --
 // Two launches, one work group per (sequence, joint) each: the filter's scan (seq_scan.h) that also writes every a_t to belief float64 [S*K][T][HH*WW],
 // then the backward scan with three float64 planes in LDS for all T frames, so HH * WW <= kSeqSmoothMaxHW (3 * 48 KB + the reduction scratch of 160 KB).

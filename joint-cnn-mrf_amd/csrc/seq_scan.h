@@ -15,6 +15,12 @@
 //
 // The policy `Tr` is what a caller does to the observation: tr.frame(t) gives the frame's functor ex, ex(cell, value) is the value staged for that
 // cell, and tr.emit(ex, frame, cell, p) is called by one thread with the filter's arg-max cell of the frame.  SqPlain stages the map as it is.
+//
+// The policy `Mv` is where a frame's lattice lies on the one before: cell (y, x) of frame t is cell (y + sy, x + sx) of frame t-1, so
+// the vertical pass reads A a whole number of rows away and the horizontal pass C a whole number of columns away, with the tap ranges clipped to the
+// plane as before -- nothing is interpolated and the planes do not grow.  C is indexed (row of frame t, column of frame t-1).  SqStill is no shift,
+// a compile-time zero: with it both scans are, instruction for instruction, what they were without the policy.  SqShift reads (sy, sx) of the frame
+// from the sequence's int32 [T][2] row and clamps it to +-(side + R), beyond which no tap reaches the map, so that no index sum can overflow.
 #pragma once
 
 #include "ctx.h"
@@ -36,6 +42,19 @@ struct SqPlain {
   };
   __device__ __forceinline__ Frame frame(int) const { return Frame(); }
   __device__ __forceinline__ void emit(const Frame&, size_t, int, const float*) const {}
+};
+
+struct SqStill {
+  static constexpr bool kMoving = false;
+  __device__ __forceinline__ int sy(int, int) const { return 0; }
+  __device__ __forceinline__ int sx(int, int) const { return 0; }
+};
+
+struct SqShift {
+  static constexpr bool kMoving = true;
+  const int32_t* __restrict__ sh;      // [T][2] of the group's sequence
+  __device__ __forceinline__ int sy(int t, int lim) const { return min(max(sh[2 * t], -lim), lim); }
+  __device__ __forceinline__ int sx(int t, int lim) const { return min(max(sh[2 * t + 1], -lim), lim); }
 };
 
 __device__ __forceinline__ bool sq_better(double v, int i, double w, int j) { return v > w || (v == w && i < j); }
@@ -105,11 +124,12 @@ __device__ __forceinline__ void sq_block_argmax(double& bv, int& bi, double* rd,
 // The filter of one group: it reads sequence s_in of hm, channel k, and writes as sequence s_out of the outputs (the two differ only for the tracks).
 // sq_planes: A [HW], C [HW] of dynamic LDS.  belief: the group's own float64 [T][HW], every a_t as it is divided (what the smoother's backward launch
 // reads, seq_smooth.hip), or null.
-template <class Tr>
+template <class Tr, class Mv = SqStill>
 __device__ __forceinline__ void sq_filter_scan(double* sq_planes, const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
                                                int R, double om, double u, const double* __restrict__ state_in, float* __restrict__ filtered,
                                                int32_t* coords, double* __restrict__ norm, int32_t* __restrict__ reset, double* __restrict__ state_out,
-                                               int vec, int s_in, int s_out, int k, const Tr& tr, double* __restrict__ belief = nullptr) {
+                                               int vec, int s_in, int s_out, int k, const Tr& tr, double* __restrict__ belief = nullptr,
+                                               const Mv& mv = Mv()) {
   __shared__ double w[kSqTaps];
   __shared__ double rd[kSqWaves];
   __shared__ int ri[kSqWaves];
@@ -131,11 +151,12 @@ __device__ __forceinline__ void sq_filter_scan(double* sq_planes, const float* _
     int rs = 0;
     double Z = 0.0;
     if (prev) {
+      const int sy = mv.sy(t, HH + R), sx = mv.sx(t, WW + R);      // 0 at compile time for SqStill
       for (int i = tid; i < HW; i += kSqThreads) {
-        const int y = i / WW;
+        const int y = i / WW + sy;                                 // the cell's row in frame t-1's lattice; an empty range leaves 0.0
         const int lo = max(-R, y - (HH - 1)), hi = min(R, y);
         double acc = 0.0;
-        for (int dy = lo; dy <= hi; ++dy) acc = acc + w[dy + R] * A[i - dy * WW];
+        for (int dy = lo; dy <= hi; ++dy) acc = acc + w[dy + R] * A[i + (sy - dy) * WW];
         C[i] = acc;
       }
       __syncthreads();
@@ -143,10 +164,10 @@ __device__ __forceinline__ void sq_filter_scan(double* sq_planes, const float* _
       __syncthreads();
       double zp = 0.0;
       for (int i = tid; i < HW; i += kSqThreads) {
-        const int y = i / WW, x = i - y * WW;
+        const int y = i / WW, x = i - y * WW + sx;
         const int lo = max(-R, x - (WW - 1)), hi = min(R, x);
         double m = 0.0;
-        for (int dx = lo; dx <= hi; ++dx) m = m + w[dx + R] * C[i - dx];
+        for (int dx = lo; dx <= hi; ++dx) m = m + w[dx + R] * C[i + (sx - dx)];
         const double pred = om * m + u;
         const double b = A[i] * pred;
         A[i] = b;
@@ -189,10 +210,11 @@ __device__ __forceinline__ void sq_filter_scan(double* sq_planes, const float* _
 }
 
 // Viterbi's scan of one group; g_ws: the group's slot of the workspace (bp [.][T][HW], amax [.][T]).  sq_planes: D [HW], C [HW], dy* [HW] bytes.
-template <class Tr>
+template <class Tr, class Mv = SqStill>
 __device__ __forceinline__ void sq_viterbi_scan(double* sq_planes, const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
                                                 int R, double om, double u, int16_t* __restrict__ bp, int32_t* __restrict__ amax, double* __restrict__ maxes,
-                                                int32_t* __restrict__ breaks, int vec, int s_in, int s_out, int k, int g_ws, const Tr& tr) {
+                                                int32_t* __restrict__ breaks, int vec, int s_in, int s_out, int k, int g_ws, const Tr& tr,
+                                                const Mv& mv = Mv()) {
   __shared__ double w[kSqTaps];
   __shared__ double rd[kSqWaves];
   __shared__ int ri[kSqWaves];
@@ -215,15 +237,17 @@ __device__ __forceinline__ void sq_viterbi_scan(double* sq_planes, const float* 
     int brk = 0;
     double M = 0.0;
     if (t > 0) {
+      const int sy = mv.sy(t, HH + R), sx = mv.sx(t, WW + R);      // 0 at compile time for SqStill
       for (int i = tid; i < HW; i += kSqThreads) {
-        const int y = i / WW;
+        const int y = i / WW + sy;
         const int lo = max(-R, y - (HH - 1)), hi = min(R, y);
         double best = -1.0;
         int bdy = lo;
         for (int dy = lo; dy <= hi; ++dy) {
-          const double v = w[dy + R] * D[i - dy * WW];
+          const double v = w[dy + R] * D[i + (sy - dy) * WW];
           if (v > best) { best = v; bdy = dy; }
         }
+        if (Mv::kMoving && lo > hi) { best = 0.0; bdy = 0; }       // no tap reaches the map: the maximum over nothing is 0
         C[i] = best;
         dyb[i] = (uint8_t)(bdy + R);
       }
@@ -233,16 +257,17 @@ __device__ __forceinline__ void sq_viterbi_scan(double* sq_planes, const float* 
       const double jump = u * Dmax;
       double mp = 0.0;
       for (int i = tid; i < HW; i += kSqThreads) {
-        const int y = i / WW, x = i - y * WW;
+        const int y = i / WW, x = i - y * WW + sx;
         const int lo = max(-R, x - (WW - 1)), hi = min(R, x);
         double best = -1.0;
         int bdx = lo;
         for (int dx = lo; dx <= hi; ++dx) {
-          const double v = w[dx + R] * C[i - dx];
+          const double v = w[dx + R] * C[i + (sx - dx)];
           if (v > best) { best = v; bdx = dx; }
         }
-        const int via = i - bdx;                                 // (y, x - dx*)
-        int from = via - ((int)dyb[via] - R) * WW;               // (y - dy*(y, x - dx*), x - dx*)
+        const int via = Mv::kMoving && lo > hi ? i : i + (sx - bdx);      // (y, x - dx* + sx); with no tap inside the map any cell of the plane
+        int from = via + (sy - ((int)dyb[via] - R)) * WW;        // (y - dy*(y, x - dx* + sx) + sy, x - dx* + sx), a cell of frame t-1's lattice
+        if (Mv::kMoving && !(best > 0.0)) { best = 0.0; from = Darg; }      // m = 0 has no source inside the map: b is 0 unless the jump wins
         double e = om * best;
         if (jump > e) { e = jump; from = Darg; }
         const double b = D[i] * e;

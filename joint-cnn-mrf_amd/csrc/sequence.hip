@@ -3,6 +3,7 @@
 // "anywhere" term.  All arithmetic is float64, one correctly rounded operation per step, in the order include/jcm.h states.
 // One work group per (sequence, joint) scans the T frames of a launch; the scan itself -- planes, staging, reductions, back-pointers -- is seq_scan.h,
 // which seq_tracks.hip shares.  Here: its kernels on the map as it is (SqPlain), the backtrace launch, the tap upload and the entry points.
+// The *_moving kernels are the same scans with SqShift: every frame's lattice lies a whole number of cells from the one before.
 #include <string>
 
 #include "seq_scan.h"
@@ -37,6 +38,27 @@ __global__ __launch_bounds__(kSqThreads) void seq_viterbi_kernel(const float* __
   sq_viterbi_scan(sq_planes, hm, T, HH, WW, K, taps, R, om, u, bp, amax, maxes, breaks, vec, s, s, k, (int)blockIdx.x, SqPlain());
 }
 
+__global__ __launch_bounds__(kSqThreads) void seq_filter_moving_kernel(const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
+                                                                       int R, double om, double u, const int32_t* __restrict__ shift,
+                                                                       const double* __restrict__ state_in, float* __restrict__ filtered,
+                                                                       int32_t* __restrict__ coords, double* __restrict__ norm, int32_t* __restrict__ reset,
+                                                                       double* __restrict__ state_out, int vec) {
+  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // A [HW], C [HW]
+  const int s = blockIdx.x / K, k = blockIdx.x - s * K;
+  sq_filter_scan(sq_planes, hm, T, HH, WW, K, taps, R, om, u, state_in, filtered, coords, norm, reset, state_out, vec, s, s, k, SqPlain(), nullptr,
+                 SqShift{shift + (size_t)s * T * 2});
+}
+
+__global__ __launch_bounds__(kSqThreads) void seq_viterbi_moving_kernel(const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
+                                                                        int R, double om, double u, const int32_t* __restrict__ shift, int16_t* __restrict__ bp,
+                                                                        int32_t* __restrict__ amax, double* __restrict__ maxes, int32_t* __restrict__ breaks,
+                                                                        int vec) {
+  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // D [HW], C [HW], dy* [HW] bytes
+  const int s = blockIdx.x / K, k = blockIdx.x - s * K;
+  sq_viterbi_scan(sq_planes, hm, T, HH, WW, K, taps, R, om, u, bp, amax, maxes, breaks, vec, s, s, k, (int)blockIdx.x, SqPlain(),
+                  SqShift{shift + (size_t)s * T * 2});
+}
+
 // one lane per (sequence, joint)
 __global__ __launch_bounds__(64) void seq_backtrace_kernel(const int16_t* __restrict__ bp, const int32_t* __restrict__ amax, int G, int T, int HW, int WW, int K,
                                                            int32_t* __restrict__ path) {
@@ -64,10 +86,17 @@ hipError_t seq_put_taps(const double* taps_host, int n, double* taps_dev, hipStr
   return hipGetLastError();
 }
 
-hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const double* state_in,
-                      float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st) {
+hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* shift,
+                      const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st) {
   if (!sq_sizes_ok(S, T, HH, WW, K, R)) return hipErrorInvalidValue;
   const int HW = HH * WW;
+  if (shift) {
+    static LdsAttr attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(seq_filter_moving_kernel), kSqLdsMax); e != hipSuccess) return e;
+    hipLaunchKernelGGL(seq_filter_moving_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8, st, hm, T, HH, WW, K, taps, R, om, u, shift, state_in, filtered,
+                       coords, norm, reset, state_out, sq_vec(hm, HW, K) ? 1 : 0);
+    return hipGetLastError();
+  }
   static LdsAttr attr;
   if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(seq_filter_kernel), kSqLdsMax); e != hipSuccess) return e;
   hipLaunchKernelGGL(seq_filter_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8, st, hm, T, HH, WW, K, taps, R, om, u, state_in, filtered, coords, norm,
@@ -75,14 +104,21 @@ hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, cons
   return hipGetLastError();
 }
 
-hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, int16_t* bp, int32_t* amax,
-                       int32_t* path, double* maxes, int32_t* breaks, hipStream_t st) {
+hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* shift,
+                       int16_t* bp, int32_t* amax, int32_t* path, double* maxes, int32_t* breaks, hipStream_t st) {
   if (!sq_sizes_ok(S, T, HH, WW, K, R)) return hipErrorInvalidValue;
   const int HW = HH * WW;
-  static LdsAttr attr;
-  if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(seq_viterbi_kernel), kSqLdsMax); e != hipSuccess) return e;
-  hipLaunchKernelGGL(seq_viterbi_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8 + ((HW + 7) & ~7), st, hm, T, HH, WW, K, taps, R, om, u, bp, amax, maxes,
-                     breaks, sq_vec(hm, HW, K) ? 1 : 0);
+  if (shift) {
+    static LdsAttr attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(seq_viterbi_moving_kernel), kSqLdsMax); e != hipSuccess) return e;
+    hipLaunchKernelGGL(seq_viterbi_moving_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8 + ((HW + 7) & ~7), st, hm, T, HH, WW, K, taps, R, om, u, shift, bp,
+                       amax, maxes, breaks, sq_vec(hm, HW, K) ? 1 : 0);
+  } else {
+    static LdsAttr attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(seq_viterbi_kernel), kSqLdsMax); e != hipSuccess) return e;
+    hipLaunchKernelGGL(seq_viterbi_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8 + ((HW + 7) & ~7), st, hm, T, HH, WW, K, taps, R, om, u, bp, amax, maxes,
+                       breaks, sq_vec(hm, HW, K) ? 1 : 0);
+  }
   const int G = S * K;
   hipLaunchKernelGGL(seq_backtrace_kernel, dim3((G + 63) / 64), dim3(64), 0, st, bp, amax, G, T, HW, WW, K, path);
   return hipGetLastError();
@@ -109,15 +145,14 @@ int seq_check(const char* what, const float* hm, int S, int T, int HH, int WW, i
   return JCM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int jcm_seq_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho, const double* state_in,
-                   float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out) {
+// The two filter entries and the two Viterbi entries are one body each: `moving` says whether a shift is required, `what` names the entry point.
+int seq_filter_entry(const char* what, bool moving, jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                     const int32_t* shift, const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out) {
   JCM_TRY(check(h, false));
-  JCM_TRY(seq_check("seq_filter", hm, S, T, HH, WW, K, taps, R, rho));
-  if (!coords) return fail(JCM_ERR_ARG, "seq_filter: null pointer (coords is required; state_in, filtered, norm, reset and state_out may be NULL)");
+  JCM_TRY(seq_check(what, hm, S, T, HH, WW, K, taps, R, rho));
+  if (!coords)
+    return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (coords is required; state_in, filtered, norm, reset and state_out may be NULL)");
+  if (moving && !shift) return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (shift is required)");
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
@@ -129,18 +164,19 @@ int jcm_seq_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, 
     JCM_TRY(prof_begin(c, &e0, &e1));
     hipError_t launch = seq_put_taps(taps, K * (2 * R + 1), dtaps, c->stream);
     if (launch == hipSuccess)
-      launch = seq_filter(hm, S, T, HH, WW, K, dtaps, R, om, u, state_in, filtered, coords, norm, reset, state_out, c->stream);
-    prof_end(c, "seq_filter", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("seq_filter: ") + hipGetErrorString(launch));
+      launch = seq_filter(hm, S, T, HH, WW, K, dtaps, R, om, u, moving ? shift : nullptr, state_in, filtered, coords, norm, reset, state_out, c->stream);
+    prof_end(c, what, e0, e1, launch == hipSuccess);
+    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(launch));
     return (int)JCM_OK;
   });
 }
 
-int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho, int32_t* path,
-                    double* maxes, int32_t* breaks) {
+int seq_viterbi_entry(const char* what, bool moving, jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R,
+                      double rho, const int32_t* shift, int32_t* path, double* maxes, int32_t* breaks) {
   JCM_TRY(check(h, false));
-  JCM_TRY(seq_check("seq_viterbi", hm, S, T, HH, WW, K, taps, R, rho));
-  if (!path) return fail(JCM_ERR_ARG, "seq_viterbi: null pointer (path is required; maxes and breaks may be NULL)");
+  JCM_TRY(seq_check(what, hm, S, T, HH, WW, K, taps, R, rho));
+  if (!path) return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (path is required; maxes and breaks may be NULL)");
+  if (moving && !shift) return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (shift is required)");
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
@@ -150,7 +186,7 @@ int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW,
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     if (need_d > (double)free_b + (double)c->arena_cap)
-      return fail(JCM_ERR_STATE, "seq_viterbi: the back-pointers of " + std::to_string(S) + " x " + std::to_string(T) + " frames need " +
+      return fail(JCM_ERR_STATE, std::string(what) + ": the back-pointers of " + std::to_string(S) + " x " + std::to_string(T) + " frames need " +
                                      std::to_string((unsigned long long)need_d) + " bytes of workspace, " +
                                      std::to_string((unsigned long long)(free_b + c->arena_cap)) + " bytes are available; split the clip");
   }
@@ -163,11 +199,36 @@ int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW,
     hipEvent_t e0, e1;
     JCM_TRY(prof_begin(c, &e0, &e1));
     hipError_t launch = seq_put_taps(taps, K * (2 * R + 1), dtaps, c->stream);
-    if (launch == hipSuccess) launch = seq_viterbi(hm, S, T, HH, WW, K, dtaps, R, om, u, bp, amax, path, maxes, breaks, c->stream);
-    prof_end(c, "seq_viterbi", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("seq_viterbi: ") + hipGetErrorString(launch));
+    if (launch == hipSuccess)
+      launch = seq_viterbi(hm, S, T, HH, WW, K, dtaps, R, om, u, moving ? shift : nullptr, bp, amax, path, maxes, breaks, c->stream);
+    prof_end(c, what, e0, e1, launch == hipSuccess);
+    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(launch));
     return (int)JCM_OK;
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int jcm_seq_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho, const double* state_in,
+                   float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out) {
+  return seq_filter_entry("seq_filter", false, h, hm, S, T, HH, WW, K, taps, R, rho, nullptr, state_in, filtered, coords, norm, reset, state_out);
+}
+
+int jcm_seq_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho, int32_t* path,
+                    double* maxes, int32_t* breaks) {
+  return seq_viterbi_entry("seq_viterbi", false, h, hm, S, T, HH, WW, K, taps, R, rho, nullptr, path, maxes, breaks);
+}
+
+int jcm_seq_filter_moving(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho, const int32_t* shift,
+                          const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out) {
+  return seq_filter_entry("seq_filter_moving", true, h, hm, S, T, HH, WW, K, taps, R, rho, shift, state_in, filtered, coords, norm, reset, state_out);
+}
+
+int jcm_seq_viterbi_moving(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                           const int32_t* shift, int32_t* path, double* maxes, int32_t* breaks) {
+  return seq_viterbi_entry("seq_viterbi_moving", true, h, hm, S, T, HH, WW, K, taps, R, rho, shift, path, maxes, breaks);
 }
 
 }  // extern "C"

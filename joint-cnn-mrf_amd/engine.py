@@ -360,39 +360,69 @@ class Engine:
             raise ValueError('radius must be in 0..16, got %r' % (radius,))
         return hm5, single, seq_taps(sigma, R, K), R
 
-    def seq_filter(self, hm, sigma, rho, radius=None, state=None):
+    def _seq_shift(self, shift, S, T, single):
+        """shift: int32 [T,2] (a 4-d hm) or [S,T,2] = (sy, sx), host or device -> a contiguous device int32 [S,T,2]."""
+        if not isinstance(shift, torch.Tensor):
+            a = np.asarray(shift)
+            if a.dtype.kind not in 'iu' or a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError('shift must hold int32 values, got %s' % (a.dtype,))
+            shift = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32)))
+        if shift.dtype != torch.int32:
+            raise ValueError('shift must be int32, got %s' % (shift.dtype,))
+        if single and shift.dim() == 2:
+            shift = shift.unsqueeze(0)
+        if tuple(shift.shape) != (S, T, 2):
+            raise ValueError('shift must be [S,T,2] = %s (or [T,2] with a 4-d hm), got %s' % ((S, T, 2), tuple(shift.shape)))
+        return shift.to(self.device).contiguous()
+
+    def seq_filter(self, hm, sigma, rho, radius=None, state=None, shift=None):
         """The causal forward filter of a clip's heat maps (include/jcm.h: jcm_seq_filter): hm [T,HH,WW,K] or [S,T,HH,WW,K],
         frame after frame of what forward returns as pd_prob / sm_prob; sigma: a scalar or K values, the motion per frame in heat-map cells
         (predict.seq_taps builds the taps); rho in [0,1]: the mass of the uniform "anywhere" term; radius: default min(16, ceil(3 max sigma));
         state: float64 [S,K,HH,WW] ([K,HH,WW] for a 4-d hm), the 'state' of the call that ended just before frame 0, or None at a clip's start.
         Returns {'filtered' fp32 like hm, 'coords' int32 [S,T,2,K] (row, col), 'norm' float64 [S,T,K], 'reset' int32 [S,T,K], 'state' float64
         [S,K,HH,WW]}, device tensors without the S axis for a 4-d hm; nothing is read back.  HH * WW <= 8192 and K <= 16 are checked by the
-        library."""
+        library.
+        shift: None, or int32 [T,2] / [S,T,2] = (sy, sx) on the host or the device, for maps whose lattice moves (include/jcm.h:
+        jcm_seq_filter_moving): cell (y, x) of frame t is cell (y + sy, x + sx) of frame t-1; shift[0] applies to the transition from `state`
+        and is ignored without one.  'coords' are in every frame's own lattice, 'state' in the last frame's."""
         hm5, single, taps, R = self._seq_args(hm, sigma, radius)
         S, T, HH, WW, K = hm5.shape
+        if shift is not None:
+            shift = self._seq_shift(shift, S, T, single)
         if state is not None:
             state = self._chk(state.unsqueeze(0) if single and isinstance(state, torch.Tensor) and state.dim() == 3 else state, 4, 'state', torch.float64)
             if tuple(state.shape) != (S, K, HH, WW):
                 raise ValueError('state must be [S,K,HH,WW] = %s, got %s' % ((S, K, HH, WW), tuple(state.shape)))
         out = {'filtered': self._new(S, T, HH, WW, K), 'coords': self._new(S, T, 2, K, dtype=torch.int32), 'norm': self._new(S, T, K, dtype=torch.float64),
                'reset': self._new(S, T, K, dtype=torch.int32), 'state': self._new(S, K, HH, WW, dtype=torch.float64)}
-        self._on_stream(hm5, *([state] if state is not None else []), *out.values())
-        _lib.check(self._lib.jcm_seq_filter(self._h, self._p(hm5), S, T, HH, WW, K, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R, float(rho),
-                                            self._p(state), self._p(out['filtered']), self._p(out['coords']), self._p(out['norm']), self._p(out['reset']),
-                                            self._p(out['state'])), 'jcm_seq_filter')
+        self._on_stream(hm5, *([state] if state is not None else []), *([shift] if shift is not None else []), *out.values())
+        tp = taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        tail = (self._p(state), self._p(out['filtered']), self._p(out['coords']), self._p(out['norm']), self._p(out['reset']), self._p(out['state']))
+        if shift is not None:
+            _lib.check(self._lib.jcm_seq_filter_moving(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), self._p(shift), *tail), 'jcm_seq_filter_moving')
+        else:
+            _lib.check(self._lib.jcm_seq_filter(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), *tail), 'jcm_seq_filter')
         return {k: v[0] for k, v in out.items()} if single else out
 
-    def seq_viterbi(self, hm, sigma, rho, radius=None):
+    def seq_viterbi(self, hm, sigma, rho, radius=None, shift=None):
         """The most probable track through a clip's heat maps (include/jcm.h: jcm_seq_viterbi); hm, sigma, rho and radius as for
         seq_filter.  Returns {'path' int32 [S,T,2,K] (row, col), 'maxes' float64 [S,T,K], 'breaks' int32 [S,T,K]}, device tensors without the S
         axis for a 4-d hm; nothing is read back.  The back-pointers (2 bytes per cell, frame, joint and sequence) live in the engine's
-        workspace; a clip they do not fit in is a RuntimeError that names the bytes."""
+        workspace; a clip they do not fit in is a RuntimeError that names the bytes.
+        shift: as for seq_filter (include/jcm.h: jcm_seq_viterbi_moving); 'path' is in every frame's own lattice, shift[0] is ignored."""
         hm5, single, taps, R = self._seq_args(hm, sigma, radius)
         S, T, HH, WW, K = hm5.shape
+        if shift is not None:
+            shift = self._seq_shift(shift, S, T, single)
         out = {'path': self._new(S, T, 2, K, dtype=torch.int32), 'maxes': self._new(S, T, K, dtype=torch.float64), 'breaks': self._new(S, T, K, dtype=torch.int32)}
-        self._on_stream(hm5, *out.values())
-        _lib.check(self._lib.jcm_seq_viterbi(self._h, self._p(hm5), S, T, HH, WW, K, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R, float(rho),
-                                             self._p(out['path']), self._p(out['maxes']), self._p(out['breaks'])), 'jcm_seq_viterbi')
+        self._on_stream(hm5, *([shift] if shift is not None else []), *out.values())
+        tp = taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        tail = (self._p(out['path']), self._p(out['maxes']), self._p(out['breaks']))
+        if shift is not None:
+            _lib.check(self._lib.jcm_seq_viterbi_moving(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), self._p(shift), *tail), 'jcm_seq_viterbi_moving')
+        else:
+            _lib.check(self._lib.jcm_seq_viterbi(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), *tail), 'jcm_seq_viterbi')
         return {k: v[0] for k, v in out.items()} if single else out
 
     def seq_smooth(self, hm, sigma, rho, radius=None, want_smoothed=True):

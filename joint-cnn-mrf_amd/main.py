@@ -136,6 +136,10 @@ def build_parser():
                         '(predict.predict_sequence_people, DESIGN.md 4.21): M consistent torso tracks are pulled out of the frames\' torso maps, the spatial model '
                         'runs once per frame and track, and every person\'s joints are tracked; every image of the document gains "tracks" ("track" is track 0) '
                         'and --render draws one skeleton per track present in the frame.  What this buys with trained weights has not been measured.')
+    parser.add_argument('--seq_zoom', action='store_true', help='with --sequence filter or viterbi, --predict and --use_sm: track the person a second time at the scale '
+                        'the tower was trained on (predict.predict_sequence_zoom, DESIGN.md 4.24): one zoom window per frame around the torso track, all on one '
+                        'cell lattice, and the temporal scan with a whole-cell shift per frame; the document gains "zoom" and "track_zoom" per file, the JSON '
+                        'line seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms.  Not with --sequence marginal, --seq_fit or --seq_people.')
     parser.add_argument('--seq_torso_sigma', type=float, default=None, metavar='CELLS', help='with --seq_people: the standard deviation of a torso\'s motion per '
                         'frame in heat-map cells (default 1.5, an untuned placeholder).')
     parser.add_argument('--seq_exclude', type=int, default=None, metavar='CELLS', help='with --seq_people: the half-width in 0..64 heat-map cells of the square '
@@ -357,6 +361,11 @@ SEQ_PEOPLE_NEEDS_USE_SM = '--seq_people needs --use_sm: the torso tracks come fr
 SEQ_MARGINAL_NO_PEOPLE = '--sequence marginal cannot be combined with --seq_people: the torso tracks have the filter and Viterbi only'
 SEQ_FIT_NEEDS_SEQUENCE = '--seq_fit fits the motion model of --sequence to the clip: give --sequence filter, viterbi or marginal as well'
 SEQ_FIT_NO_PEOPLE = '--seq_fit cannot be combined with --seq_people: the fit is that of one person\'s joint maps'
+SEQ_ZOOM_NEEDS_SEQUENCE = '--seq_zoom zooms into the clip --sequence names: give --sequence filter or --sequence viterbi as well'
+SEQ_ZOOM_NEEDS_USE_SM = '--seq_zoom needs --use_sm: the windows are placed on the torso track and sized by the spatial model\'s shoulders and hips'
+SEQ_ZOOM_NO_MARGINAL = '--seq_zoom cannot be combined with --sequence marginal: the smoother has no form for windows that move from frame to frame'
+SEQ_ZOOM_NO_FIT = '--seq_zoom cannot be combined with --seq_fit: the fit runs on the smoother, which has no form for windows that move from frame to frame'
+SEQ_ZOOM_NO_PEOPLE = '--seq_zoom cannot be combined with --seq_people: a zoom pass per track is out of scope'
 SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
@@ -377,7 +386,9 @@ def predict_main(args):
     --predictions, one JSON line with the image count and the device times of the fit and of the forwards to stdout.  With --render DIR the
     images come back with the result drawn on them (predict.render_images) and go to DIR as PNG files; the line gains render_ms.  With --sequence
     the images are the frames of one clip (predict.predict_sequence): the document gains "track" per file, the pictures show the tracked skeleton; with --seq_people M
-    (predict.predict_sequence_people) also "tracks", one skeleton per person, and the line gains seq_people, seq_torso_ms and seq_people_sm_ms."""
+    (predict.predict_sequence_people) also "tracks", one skeleton per person, and the line gains seq_people, seq_torso_ms and seq_people_sm_ms; with --seq_zoom
+    (predict.predict_sequence_zoom) "zoom" and "track_zoom", the pictures show the skeleton tracked through the windows where the clip was zoomed, and the line
+    gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -394,7 +405,9 @@ def predict_main(args):
                        peaks=args.peaks, decode=args.decode_pose, timing=timing)
             if args.seq_fit is not None:
                 seq.update(fit_iters=args.seq_fit)
-            if args.seq_people is not None:
+            if args.seq_zoom:
+                results = predict.predict_sequence_zoom(eng, images, **seq)
+            elif args.seq_people is not None:
                 results = predict.predict_sequence_people(eng, images, args.seq_people, exclude=predict.SEQ_EXCLUDE if args.seq_exclude is None else args.seq_exclude,
                                                           torso_sigma=predict.SEQ_TORSO_SIGMA if args.seq_torso_sigma is None else args.seq_torso_sigma, **seq)
             else:
@@ -403,7 +416,7 @@ def predict_main(args):
             results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
                                              batch_size=args.batch_size, timing=timing, zoom=args.zoom, keep_maps=bool(args.render_heat))
         if args.render:
-            pictures = predict.render_images(eng, images, results, heat=args.render_heat, which='track' if args.sequence else None,
+            pictures = predict.render_images(eng, images, results, heat=args.render_heat, which=('track_zoom' if args.seq_zoom and 'track_zoom' in results[0] else 'track') if args.sequence else None,
                                              batch_size=args.batch_size, timing=timing)
     finally:
         eng.close()
@@ -419,6 +432,8 @@ def predict_main(args):
         line.update(seq_fit={'sigma': fit['sigma'].tolist(), 'rho': fit['rho'], 'loglik': fit['loglik'].tolist(), 'clamped': fit['clamped'].tolist()})
     if args.seq_people is not None:
         line.update(seq_people=args.seq_people, seq_torso_ms=timing['seq_torso_ms'], seq_people_sm_ms=timing['seq_people_sm_ms'])
+    if args.seq_zoom:
+        line.update(seq_zoom=True, seq_zoom_pitch=timing['seq_zoom_pitch'], zoom_fit_ms=timing['zoom_fit_ms'], zoom_forward_ms=timing['zoom_forward_ms'])
     if args.zoom:
         line.update(zoom=True, zoom_fit_ms=timing['zoom_fit_ms'], zoom_forward_ms=timing['zoom_forward_ms'])
     if args.render:
@@ -721,13 +736,21 @@ SEQ_SMOOTH_RULES = (
     (lambda a: a.seq_fit is not None and a.seq_people is not None, SEQ_FIT_NO_PEOPLE),
     (lambda a: a.sequence == 'marginal' and a.seq_people is not None, SEQ_MARGINAL_NO_PEOPLE),
 )
+# The rules of --seq_zoom, walked behind SEQ_SMOOTH_RULES (a table of their own for the same reason).  --zoom with --sequence stays refused above.
+SEQ_ZOOM_RULES = (
+    (lambda a: a.seq_zoom and not a.sequence, SEQ_ZOOM_NEEDS_SEQUENCE),
+    (lambda a: a.seq_zoom and not a.use_sm, SEQ_ZOOM_NEEDS_USE_SM),
+    (lambda a: a.seq_zoom and a.sequence == 'marginal', SEQ_ZOOM_NO_MARGINAL),
+    (lambda a: a.seq_zoom and a.seq_fit is not None, SEQ_ZOOM_NO_FIT),
+    (lambda a: a.seq_zoom and a.seq_people is not None, SEQ_ZOOM_NO_PEOPLE),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

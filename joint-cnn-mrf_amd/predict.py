@@ -25,7 +25,11 @@ SEQ_TORSO_SIGMA are untuned placeholders too.
 
 Smoothed marginals and the fit: predict_sequence(mode='marginal') takes every frame's position from the smoothed posterior
 P(x_t | all frames) of Engine.seq_smooth, with its confidence; seq_fit re-estimates sigma (per joint) and rho on a clip's own maps by EM, without
-annotations, and predict_sequence(fit_iters=) runs any mode with the fitted values."""
+annotations, and predict_sequence(fit_iters=) runs any mode with the fitted values.
+
+Zoomed clips: predict_sequence_zoom runs the zoom pass on every frame of a clip in windows that follow the person and share
+one cell lattice (zoom_window_track), so that two frames' maps differ by a whole number of cells, and tracks the joints through them with
+Engine.seq_filter / seq_viterbi(shift=), the scans with a per-frame shift of the belief plane."""
 import os
 
 import numpy as np
@@ -365,6 +369,157 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
     return results
 
 
+# ------------------------------------------------------------------ zoomed clips
+ZOOM_MAP = (FRAME[0] // STRIDE, FRAME[1] // STRIDE)      # 60 x 90 cells: a window of 60 p x 90 p source pixels puts p x p of them into every cell
+SEQ_ZOOM_MODES = ('filter', 'viterbi')
+
+
+def zoom_window_track(points, inside, torso, geom, frame=FRAME):
+    """Where the second pass of a CLIP looks; host arithmetic only, float64 and integers.  One row per frame: points float
+    [T,K,2] and inside bool [T,K], the tracked pass-1 joints in the frame's pixels ('track' of predict_sequence); torso float [T,2], the torso
+    track in the frame's pixels; geom int [6] or [T,6], the clip's one pass-1 fit (y0, x0, ch, cw, h, w).  All windows of the clip share ONE
+    lattice of pitch p source pixels per heat-map cell, so that two windows differ by a whole number of cells:
+      valid frame: the four torso joints are inside and torso_length >= 2 * STRIDE * h / ch (the skip rules of zoom_windows);
+      tmed = the median of torso_length over the valid frames;  p = max(1, floor(tmed * STRIDE / ZOOM_TORSO_PIXELS + 0.5));
+      wh = 60 p, ww = 90 p for every frame: exactly 3:2, so fit_geometry gives the whole 480 x 720 frame and a cell is exactly p x p pixels;
+      wy0 = p * floor((cy - 30 p) / p + 0.5), wx0 = p * floor((cx - 45 p) / p + 0.5) with (cy, cx) the frame's torso point, clamped to the
+        nearest multiple of p at which the window still holds a pixel of the frame: -59 p <= wy0 <= p * ((h - 1) // p), -89 p <= wx0 <=
+        p * ((w - 1) // p) (Engine.fit_windows refuses a window that shares nothing with the image);
+      shift[t] = ((wy0[t] - wy0[t-1]) / p, (wx0[t] - wx0[t-1]) / p), exact integers, shift[0] = (0, 0): cell (y, x) of frame t's maps is cell
+        (y + sy, x + sx) of frame t-1's -- the convention of jcm_seq_filter_moving / jcm_seq_viterbi_moving;
+      cells = the torso point taken forward through the window, floor((c - w0 + 0.5) / p - 0.5) // STRIDE clamped to the map, as zoom_windows
+        computes it: where the torso blob of the second pass goes.
+    Returns (windows int64 [T,5] = (frame, wy0, wx0, wh, ww), cells int32 [T,2], shift int32 [T,2], p, valid bool [T]).  Every frame gets a
+    window, a valid one or not: the track needs the maps of all of them.  With no valid frame the clip is not zoomed: p = 0 and windows,
+    cells and shift are zero.  90 p > FIT_SIDE_MAX raises ValueError.
+    One pitch per clip is a stated limit: a person who walks towards the camera changes scale, and the clip's median decides the pitch."""
+    pts, inside, torso = np.asarray(points, np.float64), np.asarray(inside, bool), np.asarray(torso, np.float64)
+    T = pts.shape[0]
+    geom = np.asarray(geom, np.int64)
+    if geom.ndim == 1:
+        geom = np.broadcast_to(geom, (T, 6)) if geom.shape == (6,) else geom
+    if pts.ndim != 3 or T < 1 or pts.shape[2] != 2 or pts.shape[1] < 8 or inside.shape != pts.shape[:2] or torso.shape != (T, 2) or geom.shape != (T, 6):
+        raise ValueError('zoom_window_track expects points [T,K >= 8,2], inside [T,K], torso [T,2] and geom [6] or [T,6]; got %s, %s, %s, %s' %
+                         (pts.shape, inside.shape, torso.shape, geom.shape))
+    if (geom != geom[0]).any():
+        raise ValueError('zoom_window_track: the frames of a clip have one fit; got several')
+    OH, OW = int(frame[0]), int(frame[1])
+    MH, MW = OH // STRIDE, OW // STRIDE
+    ch, h, w = int(geom[0, 2]), int(geom[0, 4]), int(geom[0, 5])
+    t = torso_length(pts)
+    torso_joints = [j for pair in ZOOM_TORSO_JOINTS for j in pair]
+    valid = inside[:, torso_joints].all(axis=1) & ~(t < 2.0 * STRIDE * h / ch)
+    windows = np.zeros((T, 5), np.int64)
+    windows[:, 0] = np.arange(T)
+    if not valid.any():
+        return windows, np.zeros((T, 2), np.int32), np.zeros((T, 2), np.int32), 0, valid
+    p = max(1, int(np.floor(np.median(t[valid]) * STRIDE / ZOOM_TORSO_PIXELS + 0.5)))
+    wh, ww = MH * p, MW * p
+    if ww > FIT_SIDE_MAX or wh > FIT_SIDE_MAX:
+        raise ValueError('zoom_window_track: a torso of %.1f pixels gives windows of %d x %d pixels; the sides a fit takes end at %d' %
+                         (float(np.median(t[valid])), wh, ww, FIT_SIDE_MAX))
+    origin, cells = np.empty((T, 2), np.int64), np.empty((T, 2), np.int32)
+    for axis, (half, cells_n, size, content) in enumerate(((MH // 2, MH, h, OH), (MW // 2, MW, w, OW))):
+        o = p * np.floor((torso[:, axis] - half * p) / p + 0.5).astype(np.int64)
+        o = np.clip(o, -(cells_n - 1) * p, p * ((size - 1) // p))
+        origin[:, axis] = o
+        at = np.floor((torso[:, axis] - o + 0.5) * content / (cells_n * p) - 0.5).astype(np.int64) // STRIDE      # the fit's content origin is 0
+        cells[:, axis] = np.clip(at, 0, cells_n - 1)
+    windows[:, 1:3] = origin
+    windows[:, 3], windows[:, 4] = wh, ww
+    shift = np.zeros((T, 2), np.int64)
+    shift[1:] = (origin[1:] - origin[:-1]) // p
+    return windows, cells, shift.astype(np.int32), p, valid
+
+
+def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, radius=None, batch_size=16, people=1,
+                          keep_maps=False, fit_iters=0, pad=0, timing=None, **kw):
+    """The frames of ONE clip with one person in it, tracked a second time at the scale the tower was trained on; frames as
+    for predict_sequence.
+      1. predict_sequence(frames, mode, ..., torso_prob=True): the first pass and its 'track'; the torso track comes from the frames'
+         torso_prob maps with Engine.seq_tracks(people=1), as predict_sequence_people obtains its tracks;
+      2. zoom_window_track: one window per frame around the torso track, all on one lattice of pitch p, and the whole-cell shift of every
+         frame's lattice against the one before;
+      3. Engine.fit_windows of every frame, a forward with the blob at the window's torso cell and want_prob=True, batch_size at a time; the
+         'sm' maps stacked as [T,60,90,K]; Engine.seq_filter or Engine.seq_viterbi with shift=; evaluation.window_to_source maps every frame's
+         cells back through that frame's window.
+    Returns predict_sequence's dicts, every key with its value, plus
+      'zoom': one entry as predict_images(zoom=True) writes it, the per-frame arg-max of the second pass; 'window' is the frame's window here;
+      'track_zoom': {'mode', 'points' float64 [K,2] (row, col) in the frame's own pixels, 'inside' bool [K], 'window' (y0, x0, h, w), 'shift'
+                     (sy, sx), 'pitch', and 'norm' / 'reset' or 'maxes' / 'breaks' [K] as in 'track'}.
+    A clip with no valid frame (zoom_window_track) is not zoomed: every frame's 'zoom' entry has zoomed False and the pass-1 values, and there
+    is no 'track_zoom'.  timing also receives 'zoom_fit_ms', 'zoom_forward_ms' and 'seq_zoom_pitch'.
+    The modes are 'filter' and 'viterbi': mode='marginal' and fit_iters raise ValueError (jcm_seq_smooth has no moving form), people != 1 too.
+    One pitch per clip is a stated limit; torso_sigma, sigma and rho are untuned placeholders, and what this buys with trained weights has not
+    been measured."""
+    if mode not in SEQ_ZOOM_MODES:
+        raise ValueError("mode must be 'filter' or 'viterbi', got %r (the smoother has no moving form: mode 'marginal' is not offered with zoomed clips)" % (mode,))
+    if int(fit_iters) != 0:
+        raise ValueError('predict_sequence_zoom has no fit: fit_iters=%r needs the smoother, which has no moving form' % (fit_iters,))
+    if people != 1:
+        raise ValueError('predict_sequence_zoom tracks one person: people=%r is out of scope' % (people,))
+    B = int(batch_size)
+    results = predict_sequence(engine, frames, mode=mode, sigma=sigma, rho=rho, radius=radius, use_sm=True, batch_size=B, keep_maps=True, torso_prob=True,
+                               pad=pad, timing=timing, **kw)
+    T = len(results)
+    zoom_ms = [0.0, 0.0]
+    with torch.cuda.stream(engine._stream):
+        torso_maps = torch.stack([r['maps']['torso_prob'] for r in results]).contiguous()
+        torso = engine.seq_tracks(torso_maps, 1, torso_sigma, rho, mode=mode)
+        tc = torso['coords' if mode == 'filter' else 'path'].cpu().numpy().reshape(T, 2).astype(np.float64)
+        geom1 = np.array([r['geom'] for r in results], np.int64)
+        torso_px, _ = fit_to_source(tc * STRIDE, geom1)
+        points, inside = np.stack([r['track']['points'] for r in results]), np.stack([r['track']['inside'] for r in results])
+        wins, cells, shift, pitch, valid = zoom_window_track(points, inside, torso_px, geom1)
+        lengths = torso_length(points)
+        if pitch:
+            maps, coords = [], {'pd': [], 'sm': []}
+            geom2 = np.empty((T, 6), np.int64)
+            for lo in range(0, T, B):
+                hi = min(T, lo + B)
+                batch = [_upload(im, engine.device) for im in frames[lo:hi]]
+                local = wins[lo:hi].copy()
+                local[:, 0] -= lo
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ev[0].record(engine._stream)
+                x2, g2 = engine.fit_windows(batch, local, out_hw=FRAME, pad=pad)
+                ev[1].record(engine._stream)
+                blob = engine.torso_infer(None, cells=torch.from_numpy(np.ascontiguousarray(cells[lo:hi])).to(engine.device))['torso']
+                r2 = engine.forward(x2, torso=blob, use_sm=True, want_prob=True)
+                ev[2].record(engine._stream)
+                ev[2].synchronize()
+                zoom_ms[0] += ev[0].elapsed_time(ev[1])
+                zoom_ms[1] += ev[1].elapsed_time(ev[2])
+                geom2[lo:hi] = g2
+                maps.append(r2['sm_prob'])
+                for key in coords:
+                    coords[key].append(r2[key + '_coords'])
+            hm = torch.cat(maps).contiguous()
+            seq = (engine.seq_filter if mode == 'filter' else engine.seq_viterbi)(hm, sigma, rho, radius=radius, shift=shift)
+            sizes = np.array([r['size'] for r in results], np.int64)
+            second = {key: window_to_source(_coords_to_points(torch.cat(coords[key])), geom2, wins, sizes) for key in coords}
+            tpts, tin = window_to_source(_coords_to_points(seq['path' if mode == 'viterbi' else 'coords']), geom2, wins, sizes)
+            keys = ('norm', 'reset') if mode == 'filter' else ('maxes', 'breaks')
+            host = {k: seq[k].cpu().numpy() for k in keys}
+        for t, r in enumerate(results):
+            e = {'zoomed': bool(pitch), 'window': tuple(int(v) for v in wins[t, 1:]), 'torso_len': float(lengths[t])}
+            if pitch:
+                for key in ('pd', 'sm'):
+                    e[key], e[key + '_inside'] = second[key][0][t], second[key][1][t]
+                r['track_zoom'] = dict({'mode': mode, 'points': tpts[t], 'inside': tin[t], 'window': e['window'], 'shift': (int(shift[t, 0]), int(shift[t, 1])),
+                                        'pitch': int(pitch)}, **{k: host[k][t] for k in keys})
+                if keep_maps:
+                    r['maps']['sm_zoom'] = hm[t]
+            else:
+                e.update(pd=r['pd'], pd_inside=r['pd_inside'], sm=r['sm'], sm_inside=r['sm_inside'])
+            r['zoom'] = [e]
+            if not keep_maps:
+                del r['maps']
+    if timing is not None:
+        timing.update(zoom_fit_ms=zoom_ms[0], zoom_forward_ms=zoom_ms[1], seq_zoom_pitch=int(pitch))
+    return results
+
+
 def seq_moment(sigma, radius):
     """sum over d of d^2 w_sigma[d] of the truncated taps seq_taps builds: the 1-D second moment of the motion kernel, float64.  Monotone in sigma,
     from 0 towards the flat taps' R (R + 1) / 3."""
@@ -637,8 +792,8 @@ def _skeletons(r, which, zoom):
     if which == 'track' and 'tracks' in r:
         p = r['tracks']
         return [(p['points'][m], p['inside'][m]) for m in range(len(p['present'])) if p['present'][m]]
-    if which == 'track':
-        return [(r['track']['points'], r['track']['inside'])]
+    if which in ('track', 'track_zoom'):
+        return [(r[which]['points'], r[which]['inside'])]
     if zoom and 'zoom' in r:
         return [(e[which], e[which + '_inside']) for e in r['zoom']]
     if which == 'sm' and 'people' in r:
@@ -652,14 +807,14 @@ def skeleton_primitives(results, which='sm', zoom=True):
     int32 [NP,8] = (image, ay, ax, by, bx, r, rgb, alpha), coordinates and radii in sixteenths of a pixel (floor(16 v + 0.5)).  Per image
     rl = max(16, 2 * (h + w) // 75), 2 px at 480 x 720.  Per skeleton, first the limbs of SKELETON whose two ends are inside (radius rl, the
     colour of the second joint, alpha 192; the neck exists when both shoulders do), then a disc per inside joint (radius 2 rl, alpha 255).
-    which: 'sm' or 'pd', whose joints are drawn, or 'track', the tracked joints of predict_sequence (one skeleton per present track of predict_sequence_people); with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
+    which: 'sm' or 'pd', whose joints are drawn, 'track_zoom', the joints predict_sequence_zoom tracked through the windows, or 'track', the tracked joints of predict_sequence (one skeleton per present track of predict_sequence_people); with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
     in a result, one skeleton per entry of it, a zoomed person's from the second pass."""
-    if which not in ('sm', 'pd', 'track'):
-        raise ValueError("which must be 'sm', 'pd' or 'track', got %r" % (which,))
+    if which not in ('sm', 'pd', 'track', 'track_zoom'):
+        raise ValueError("which must be 'sm', 'pd', 'track' or 'track_zoom', got %r" % (which,))
     rows = []
     for i, r in enumerate(results):
         if which not in r:
-            raise ValueError("results[%d] has no %r joints (%s makes them)" % (i, which, 'predict_sequence' if which == 'track' else 'predict_images(use_sm=%s)' % (which == 'sm')))
+            raise ValueError("results[%d] has no %r joints (%s makes them)" % (i, which, {'track': 'predict_sequence', 'track_zoom': 'predict_sequence_zoom'}.get(which, 'predict_images(use_sm=%s)' % (which == 'sm'))))
         rl = max(16, 2 * (int(r['size'][0]) + int(r['size'][1])) // 75)
         for joints, inside in _skeletons(r, which, zoom):
             K = len(inside)
@@ -681,7 +836,8 @@ def skeleton_primitives(results, which='sm', zoom=True):
 
 def render_images(engine, images, results, heat=None, which=None, zoom=True, heat_gain=255, batch_size=16, timing=None):
     """`images` (what predict_images took) with `results` (what it returned) drawn on them by Engine.render_poses, batch_size at a time -> a list
-    of host uint8 [h,w,3] arrays.  which: 'sm', 'pd' or 'track' (default: 'sm' where the results have it); zoom as for skeleton_primitives.  heat:
+    of host uint8 [h,w,3] arrays.  which: 'sm', 'pd', 'track' or 'track_zoom' (default: 'track_zoom' where the results have it, else 'sm' where they have it); zoom as for
+    skeleton_primitives.  heat:
     None, or 'pd' / 'sm': the maps of that stage tinted under the skeleton (JOINT_RGB's colours; needs predict_images(keep_maps=True)).
     timing: a dict that receives 'render_ms', the device-event time of the render calls summed over the batches (uploads and the read-back
     are not part of it)."""
@@ -690,7 +846,7 @@ def render_images(engine, images, results, heat=None, which=None, zoom=True, hea
     if heat not in (None, 'pd', 'sm'):
         raise ValueError("heat must be None, 'pd' or 'sm', got %r" % (heat,))
     if which is None:
-        which = 'sm' if 'sm' in results[0] else 'pd'
+        which = 'track_zoom' if 'track_zoom' in results[0] else 'sm' if 'sm' in results[0] else 'pd'
     out, ms = [], 0.0
     with torch.cuda.stream(engine._stream):
         for lo in range(0, len(images), int(batch_size)):
