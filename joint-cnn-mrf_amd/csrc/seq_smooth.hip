@@ -11,6 +11,7 @@
 // thread i % 1024 in every pass that writes it, so a plane is only read across threads between barriers; every sum is sq_block_sum's.
 #include <string>
 
+#include "seq_entry.h"
 #include "seq_scan.h"
 
 namespace jcm {
@@ -170,61 +171,29 @@ hipError_t seq_smooth(const float* hm, int S, int T, int HH, int WW, int K, cons
 
 using namespace jcm;
 
-namespace {
-
-// the argument rules of jcm_seq_filter with this entry point's own map limit
-int smooth_check(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho) {
-  const std::string w("seq_smooth");
-  if (S < 1 || T < 1 || HH < 1 || WW < 1 || K < 1) return fail(JCM_ERR_ARG, w + ": bad sizes (S, T, HH, WW, K >= 1)");
-  if (K > kSeqMaxK) return fail(JCM_ERR_ARG, w + ": K = " + std::to_string(K) + " joints; K <= 16");
-  if (R < 0 || R > kSeqMaxR) return fail(JCM_ERR_ARG, w + ": R = " + std::to_string(R) + "; 0 <= R <= 16");
-  if (!(rho >= 0.0 && rho <= 1.0)) return fail(JCM_ERR_ARG, w + ": rho outside [0, 1]");
-  if ((int64_t)HH * WW > kSeqSmoothMaxHW)
-    return fail(JCM_ERR_ARG, w + ": a map of " + std::to_string(HH) + " x " + std::to_string(WW) +
-                                 " cells; HH * WW <= 6144 (three float64 planes in 160 KB of LDS), a larger map is not truncated");
-  if ((int64_t)S * T >= ((int64_t)1 << 31) / K) return fail(JCM_ERR_ARG, w + ": bad sizes (S * T * K < 2^31)");
-  if (!hm || !taps) return fail(JCM_ERR_ARG, w + ": null pointer (hm and taps are required)");
-  return JCM_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int jcm_seq_smooth(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho, float* smoothed,
                    int32_t* coords, float* conf, double* norm, int32_t* reset, double* mass, int32_t* cut, double* trans) {
+  const std::string w("seq_smooth");
   JCM_TRY(check(h, false));
-  JCM_TRY(smooth_check(hm, S, T, HH, WW, K, taps, R, rho));
-  if (!coords)
-    return fail(JCM_ERR_ARG, "seq_smooth: null pointer (coords is required; smoothed, conf, norm, reset, mass, cut and trans may be NULL)");
+  // the argument rules of jcm_seq_filter with this entry point's own map limit
+  JCM_TRY(seq_check_joints(w, hm, S, T, HH, WW, K, taps, R, rho, kSeqSmoothMaxHW, "three float64 planes"));
+  if (!coords) return fail(JCM_ERR_ARG, w + ": null pointer (coords is required; smoothed, conf, norm, reset, mass, cut and trans may be NULL)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
   // every a_t, float64 per (sequence, joint, frame, cell): the workspace grows to hold them, and a clip they cannot fit in is refused
-  const double need_d = (double)S * K * T * HH * WW * 8.0 + (double)S * K * T * 12.0 + 8192.0;
-  if (need_d > (double)c->arena_cap) {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (need_d > (double)free_b + (double)c->arena_cap)
-      return fail(JCM_ERR_STATE, "seq_smooth: the beliefs of " + std::to_string(S) + " x " + std::to_string(T) + " frames need " +
-                                     std::to_string((unsigned long long)need_d) + " bytes of workspace, " +
-                                     std::to_string((unsigned long long)(free_b + c->arena_cap)) + " bytes are available; split the clip");
-  }
+  JCM_TRY(workspace_or_refuse(h, w, (double)S * K * T * HH * WW * 8.0 + (double)S * K * T * 12.0 + 8192.0, "beliefs", S, T));
   const double om = 1.0 - rho, u = rho / (double)(HH * WW);
-  return with_arena(c, [&] {
-    double* dtaps = arena_alloc<double>(c, (size_t)K * (2 * R + 1));
-    double* belief = arena_alloc<double>(c, (size_t)S * K * T * HH * WW);
-    double* norm_w = norm ? norm : arena_alloc<double>(c, (size_t)S * T * K);
-    int32_t* reset_w = reset ? reset : arena_alloc<int32_t>(c, (size_t)S * T * K);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    hipError_t launch = seq_put_taps(taps, K * (2 * R + 1), dtaps, c->stream);
-    if (launch == hipSuccess)
-      launch = seq_smooth(hm, S, T, HH, WW, K, dtaps, R, om, u, belief, smoothed, coords, conf, norm_w, reset_w, mass, cut, trans, c->stream);
-    prof_end(c, "seq_smooth", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("seq_smooth: ") + hipGetErrorString(launch));
-    return (int)JCM_OK;
+  double* belief = nullptr;
+  double* norm_w = norm;
+  int32_t* reset_w = reset;
+  return seq_launch(h, w, taps, K * (2 * R + 1), [&] {
+    belief = arena_alloc<double>(h, (size_t)S * K * T * HH * WW);
+    if (!norm) norm_w = arena_alloc<double>(h, (size_t)S * T * K);
+    if (!reset) reset_w = arena_alloc<int32_t>(h, (size_t)S * T * K);
+  }, [&](const double* dtaps) {
+    return seq_smooth(hm, S, T, HH, WW, K, dtaps, R, om, u, belief, smoothed, coords, conf, norm_w, reset_w, mass, cut, trans, h->stream);
   });
 }
 

@@ -7,6 +7,7 @@
 // kernel boundary -- and Viterbi's back-pointer workspace [S][T][HW] is the same for every pass: its backtrace has run before the next scan starts.
 #include <string>
 
+#include "seq_entry.h"
 #include "seq_scan.h"
 
 namespace jcm {
@@ -132,20 +133,13 @@ using namespace jcm;
 
 namespace {
 
-// the argument rules the two entry points share: those of jcm_seq_* at K = 1, then M and D
-int tracks_check(const char* what, const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double rho, int D) {
-  const std::string w(what);
-  if (S < 1 || T < 1 || HH < 1 || WW < 1) return fail(JCM_ERR_ARG, w + ": bad sizes (S, T, HH, WW >= 1)");
-  if (M < 1 || M > kTrMaxM) return fail(JCM_ERR_ARG, w + ": M = " + std::to_string(M) + " tracks; 1 <= M <= 4");
-  if (D < 0 || D > kTrMaxD) return fail(JCM_ERR_ARG, w + ": D = " + std::to_string(D) + "; 0 <= D <= 64");
-  if (R < 0 || R > kSeqMaxR) return fail(JCM_ERR_ARG, w + ": R = " + std::to_string(R) + "; 0 <= R <= 16");
-  if (!(rho >= 0.0 && rho <= 1.0)) return fail(JCM_ERR_ARG, w + ": rho outside [0, 1]");
-  if ((int64_t)HH * WW > kSeqMaxHW)
-    return fail(JCM_ERR_ARG, w + ": a map of " + std::to_string(HH) + " x " + std::to_string(WW) +
-                                 " cells; HH * WW <= 8192 (two float64 planes and a byte plane in 160 KB of LDS), a larger map is not truncated");
-  if ((int64_t)S * T >= ((int64_t)1 << 31) / kTrMaxM) return fail(JCM_ERR_ARG, w + ": bad sizes (S * T * 4 < 2^31)");
-  if (!hm || !taps) return fail(JCM_ERR_ARG, w + ": null pointer (hm and taps are required)");
-  return JCM_OK;
+// the argument rules the two entry points share: those of jcm_seq_* on single-channel maps, with M and D in the place of K
+int tracks_check(const std::string& w, const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double rho, int D) {
+  return seq_check(w, hm, S, T, HH, WW, taps, R, rho, "S, T, HH, WW", true, [&] {
+    if (M < 1 || M > kTrMaxM) return fail(JCM_ERR_ARG, w + ": M = " + std::to_string(M) + " tracks; 1 <= M <= 4");
+    if (D < 0 || D > kTrMaxD) return fail(JCM_ERR_ARG, w + ": D = " + std::to_string(D) + "; 0 <= D <= 64");
+    return (int)JCM_OK;
+  }, kSeqMaxHW, kSeqScanPlanes, kTrMaxM, "4");
 }
 
 }  // namespace
@@ -154,59 +148,37 @@ extern "C" {
 
 int jcm_seq_tracks_filter(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double rho, int D,
                           const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, float* value) {
+  const std::string w("seq_tracks_filter");
   JCM_TRY(check(h, false));
-  JCM_TRY(tracks_check("seq_tracks_filter", hm, S, T, HH, WW, M, taps, R, rho, D));
+  JCM_TRY(tracks_check(w, hm, S, T, HH, WW, M, taps, R, rho, D));
   if (!coords || !value)
-    return fail(JCM_ERR_ARG, "seq_tracks_filter: null pointer (coords and value are required; state_in, filtered, norm, reset and state_out may be NULL)");
+    return fail(JCM_ERR_ARG, w + ": null pointer (coords and value are required; state_in, filtered, norm, reset and state_out may be NULL)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
   const double om = 1.0 - rho, u = rho / (double)(HH * WW);
-  return with_arena(c, [&] {
-    double* dtaps = arena_alloc<double>(c, (size_t)(2 * R + 1));
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    hipError_t launch = seq_put_taps(taps, 2 * R + 1, dtaps, c->stream);
-    if (launch == hipSuccess)
-      launch = seq_tracks_filter(hm, S, T, HH, WW, M, dtaps, R, om, u, D, state_in, filtered, coords, norm, reset, state_out, value, c->stream);
-    prof_end(c, "seq_tracks_filter", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("seq_tracks_filter: ") + hipGetErrorString(launch));
-    return (int)JCM_OK;
+  return seq_launch(h, w, taps, 2 * R + 1, [] {}, [&](const double* dtaps) {
+    return seq_tracks_filter(hm, S, T, HH, WW, M, dtaps, R, om, u, D, state_in, filtered, coords, norm, reset, state_out, value, h->stream);
   });
 }
 
 int jcm_seq_tracks_viterbi(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double rho, int D,
                            int32_t* path, double* maxes, int32_t* breaks, float* value) {
+  const std::string w("seq_tracks_viterbi");
   JCM_TRY(check(h, false));
-  JCM_TRY(tracks_check("seq_tracks_viterbi", hm, S, T, HH, WW, M, taps, R, rho, D));
-  if (!path || !value) return fail(JCM_ERR_ARG, "seq_tracks_viterbi: null pointer (path and value are required; maxes and breaks may be NULL)");
+  JCM_TRY(tracks_check(w, hm, S, T, HH, WW, M, taps, R, rho, D));
+  if (!path || !value) return fail(JCM_ERR_ARG, w + ": null pointer (path and value are required; maxes and breaks may be NULL)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
   // the back-pointers of ONE pass, int16 per (clip, frame, cell): every pass writes them anew after the backtrace of the pass before it
-  const double need_d = (double)S * T * HH * WW * 2.0 + (double)S * T * 4.0 + 8192.0;
-  if (need_d > (double)c->arena_cap) {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (need_d > (double)free_b + (double)c->arena_cap)
-      return fail(JCM_ERR_STATE, "seq_tracks_viterbi: the back-pointers of " + std::to_string(S) + " x " + std::to_string(T) + " frames need " +
-                                     std::to_string((unsigned long long)need_d) + " bytes of workspace, " +
-                                     std::to_string((unsigned long long)(free_b + c->arena_cap)) + " bytes are available; split the clip");
-  }
+  JCM_TRY(workspace_or_refuse(h, w, (double)S * T * HH * WW * 2.0 + (double)S * T * 4.0 + 8192.0, "back-pointers", S, T));
   const double om = 1.0 - rho, u = rho / (double)(HH * WW);
-  return with_arena(c, [&] {
-    double* dtaps = arena_alloc<double>(c, (size_t)(2 * R + 1));
-    int16_t* bp = arena_alloc<int16_t>(c, (size_t)S * T * HH * WW);
-    int32_t* amax = arena_alloc<int32_t>(c, (size_t)S * T);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    hipError_t launch = seq_put_taps(taps, 2 * R + 1, dtaps, c->stream);
-    if (launch == hipSuccess) launch = seq_tracks_viterbi(hm, S, T, HH, WW, M, dtaps, R, om, u, D, bp, amax, path, maxes, breaks, value, c->stream);
-    prof_end(c, "seq_tracks_viterbi", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("seq_tracks_viterbi: ") + hipGetErrorString(launch));
-    return (int)JCM_OK;
+  int16_t* bp = nullptr;
+  int32_t* amax = nullptr;
+  return seq_launch(h, w, taps, 2 * R + 1, [&] {
+    bp = arena_alloc<int16_t>(h, (size_t)S * T * HH * WW);
+    amax = arena_alloc<int32_t>(h, (size_t)S * T);
+  }, [&](const double* dtaps) {
+    return seq_tracks_viterbi(hm, S, T, HH, WW, M, dtaps, R, om, u, D, bp, amax, path, maxes, breaks, value, h->stream);
   });
 }
 

@@ -6,6 +6,7 @@
 // The *_moving kernels are the same scans with SqShift: every frame's lattice lies a whole number of cells from the one before.
 #include <string>
 
+#include "seq_entry.h"
 #include "seq_scan.h"
 
 namespace jcm {
@@ -130,80 +131,41 @@ using namespace jcm;
 
 namespace {
 
-// the argument rules the two entry points share; `what` names the entry point in the message
-int seq_check(const char* what, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho) {
-  const std::string w(what);
-  if (S < 1 || T < 1 || HH < 1 || WW < 1 || K < 1) return fail(JCM_ERR_ARG, w + ": bad sizes (S, T, HH, WW, K >= 1)");
-  if (K > kSeqMaxK) return fail(JCM_ERR_ARG, w + ": K = " + std::to_string(K) + " joints; K <= 16");
-  if (R < 0 || R > kSeqMaxR) return fail(JCM_ERR_ARG, w + ": R = " + std::to_string(R) + "; 0 <= R <= 16");
-  if (!(rho >= 0.0 && rho <= 1.0)) return fail(JCM_ERR_ARG, w + ": rho outside [0, 1]");
-  if ((int64_t)HH * WW > kSeqMaxHW)
-    return fail(JCM_ERR_ARG, w + ": a map of " + std::to_string(HH) + " x " + std::to_string(WW) +
-                                 " cells; HH * WW <= 8192 (two float64 planes and a byte plane in 160 KB of LDS), a larger map is not truncated");
-  if ((int64_t)S * T >= ((int64_t)1 << 31) / K) return fail(JCM_ERR_ARG, w + ": bad sizes (S * T * K < 2^31)");
-  if (!hm || !taps) return fail(JCM_ERR_ARG, w + ": null pointer (hm and taps are required)");
-  return JCM_OK;
-}
-
 // The two filter entries and the two Viterbi entries are one body each: `moving` says whether a shift is required, `what` names the entry point.
 int seq_filter_entry(const char* what, bool moving, jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
                      const int32_t* shift, const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out) {
+  const std::string w(what);
   JCM_TRY(check(h, false));
-  JCM_TRY(seq_check(what, hm, S, T, HH, WW, K, taps, R, rho));
-  if (!coords)
-    return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (coords is required; state_in, filtered, norm, reset and state_out may be NULL)");
-  if (moving && !shift) return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (shift is required)");
+  JCM_TRY(seq_check_joints(w, hm, S, T, HH, WW, K, taps, R, rho, kSeqMaxHW, kSeqScanPlanes));
+  if (!coords) return fail(JCM_ERR_ARG, w + ": null pointer (coords is required; state_in, filtered, norm, reset and state_out may be NULL)");
+  if (moving && !shift) return fail(JCM_ERR_ARG, w + ": null pointer (shift is required)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
   const double om = 1.0 - rho, u = rho / (double)(HH * WW);
-  return with_arena(c, [&] {
-    double* dtaps = arena_alloc<double>(c, (size_t)K * (2 * R + 1));
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    hipError_t launch = seq_put_taps(taps, K * (2 * R + 1), dtaps, c->stream);
-    if (launch == hipSuccess)
-      launch = seq_filter(hm, S, T, HH, WW, K, dtaps, R, om, u, moving ? shift : nullptr, state_in, filtered, coords, norm, reset, state_out, c->stream);
-    prof_end(c, what, e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(launch));
-    return (int)JCM_OK;
+  return seq_launch(h, w, taps, K * (2 * R + 1), [] {}, [&](const double* dtaps) {
+    return seq_filter(hm, S, T, HH, WW, K, dtaps, R, om, u, moving ? shift : nullptr, state_in, filtered, coords, norm, reset, state_out, h->stream);
   });
 }
 
 int seq_viterbi_entry(const char* what, bool moving, jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R,
                       double rho, const int32_t* shift, int32_t* path, double* maxes, int32_t* breaks) {
+  const std::string w(what);
   JCM_TRY(check(h, false));
-  JCM_TRY(seq_check(what, hm, S, T, HH, WW, K, taps, R, rho));
-  if (!path) return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (path is required; maxes and breaks may be NULL)");
-  if (moving && !shift) return fail(JCM_ERR_ARG, std::string(what) + ": null pointer (shift is required)");
+  JCM_TRY(seq_check_joints(w, hm, S, T, HH, WW, K, taps, R, rho, kSeqMaxHW, kSeqScanPlanes));
+  if (!path) return fail(JCM_ERR_ARG, w + ": null pointer (path is required; maxes and breaks may be NULL)");
+  if (moving && !shift) return fail(JCM_ERR_ARG, w + ": null pointer (shift is required)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
   // the back-pointers: one int16 per (sequence, joint, frame, cell); the workspace grows to hold them, and a clip they cannot fit in is refused
-  const double need_d = (double)S * K * T * HH * WW * 2.0 + (double)S * K * T * 4.0 + 8192.0;
-  if (need_d > (double)c->arena_cap) {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (need_d > (double)free_b + (double)c->arena_cap)
-      return fail(JCM_ERR_STATE, std::string(what) + ": the back-pointers of " + std::to_string(S) + " x " + std::to_string(T) + " frames need " +
-                                     std::to_string((unsigned long long)need_d) + " bytes of workspace, " +
-                                     std::to_string((unsigned long long)(free_b + c->arena_cap)) + " bytes are available; split the clip");
-  }
+  JCM_TRY(workspace_or_refuse(h, w, (double)S * K * T * HH * WW * 2.0 + (double)S * K * T * 4.0 + 8192.0, "back-pointers", S, T));
   const double om = 1.0 - rho, u = rho / (double)(HH * WW);
-  return with_arena(c, [&] {
-    double* dtaps = arena_alloc<double>(c, (size_t)K * (2 * R + 1));
-    int16_t* bp = arena_alloc<int16_t>(c, (size_t)S * K * T * HH * WW);
-    int32_t* amax = arena_alloc<int32_t>(c, (size_t)S * K * T);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    hipError_t launch = seq_put_taps(taps, K * (2 * R + 1), dtaps, c->stream);
-    if (launch == hipSuccess)
-      launch = seq_viterbi(hm, S, T, HH, WW, K, dtaps, R, om, u, moving ? shift : nullptr, bp, amax, path, maxes, breaks, c->stream);
-    prof_end(c, what, e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(launch));
-    return (int)JCM_OK;
+  int16_t* bp = nullptr;
+  int32_t* amax = nullptr;
+  return seq_launch(h, w, taps, K * (2 * R + 1), [&] {
+    bp = arena_alloc<int16_t>(h, (size_t)S * K * T * HH * WW);
+    amax = arena_alloc<int32_t>(h, (size_t)S * K * T);
+  }, [&](const double* dtaps) {
+    return seq_viterbi(hm, S, T, HH, WW, K, dtaps, R, om, u, moving ? shift : nullptr, bp, amax, path, maxes, breaks, h->stream);
   });
 }
 

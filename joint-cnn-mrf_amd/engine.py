@@ -6,10 +6,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
-
-# The exclusion half-width of seq_tracks in heat-map cells.  An untuned placeholder: no consecutive-frame data is at hand to derive it from.
-SEQ_EXCLUDE = 4
+from . import _lib, motion
+from .motion import SEQ_EXCLUDE      # noqa: F401  (the default of seq_tracks; engine.SEQ_EXCLUDE stays importable)
 
 
 def _hm_size(n):
@@ -349,16 +347,12 @@ class Engine:
 
     def _seq_args(self, hm, sigma, radius):
         """hm [T,HH,WW,K] or [S,T,HH,WW,K] -> (hm as [S,T,HH,WW,K], whether a sequence axis was added, host taps [K,2R+1], R)."""
-        from .predict import seq_radius, seq_taps
         if not isinstance(hm, torch.Tensor) or hm.dim() not in (4, 5):
             raise ValueError('hm must be a device tensor [T,HH,WW,K] or [S,T,HH,WW,K]')
         single = hm.dim() == 4
         hm5 = self._chk(hm.unsqueeze(0) if single else hm, 5, 'hm')
-        K = hm5.shape[4]
-        R = seq_radius(sigma) if radius is None else int(radius)
-        if not 0 <= R <= 16:      # before the taps are built; the library checks it again
-            raise ValueError('radius must be in 0..16, got %r' % (radius,))
-        return hm5, single, seq_taps(sigma, R, K), R
+        R, taps = motion.seq_kernel(sigma, radius, hm5.shape[4])
+        return hm5, single, taps, R
 
     def _seq_shift(self, shift, S, T, single):
         """shift: int32 [T,2] (a 4-d hm) or [S,T,2] = (sy, sx), host or device -> a contiguous device int32 [S,T,2]."""
@@ -378,7 +372,7 @@ class Engine:
     def seq_filter(self, hm, sigma, rho, radius=None, state=None, shift=None):
         """The causal forward filter of a clip's heat maps (include/jcm.h: jcm_seq_filter): hm [T,HH,WW,K] or [S,T,HH,WW,K],
         frame after frame of what forward returns as pd_prob / sm_prob; sigma: a scalar or K values, the motion per frame in heat-map cells
-        (predict.seq_taps builds the taps); rho in [0,1]: the mass of the uniform "anywhere" term; radius: default min(16, ceil(3 max sigma));
+        (motion.seq_taps builds the taps); rho in [0,1]: the mass of the uniform "anywhere" term; radius: default min(16, ceil(3 max sigma));
         state: float64 [S,K,HH,WW] ([K,HH,WW] for a 4-d hm), the 'state' of the call that ended just before frame 0, or None at a clip's start.
         Returns {'filtered' fp32 like hm, 'coords' int32 [S,T,2,K] (row, col), 'norm' float64 [S,T,K], 'reset' int32 [S,T,K], 'state' float64
         [S,K,HH,WW]}, device tensors without the S axis for a 4-d hm; nothing is read back.  HH * WW <= 8192 and K <= 16 are checked by the
@@ -446,22 +440,20 @@ class Engine:
         return {k: v[0] for k, v in out.items()} if single else out
 
     def seq_fit(self, hm, sigma=None, rho=None, iters=10, radius=16, fit_rho=True):
-        """predict.seq_fit on this engine: sigma per joint and rho re-estimated on the clip's own maps (EM, one seq_smooth per iteration)."""
-        from . import predict
-        return predict.seq_fit(self, hm, predict.SEQ_SIGMA if sigma is None else sigma, predict.SEQ_RHO if rho is None else rho, iters=iters, radius=radius,
-                               fit_rho=fit_rho)
+        """motion.seq_fit on this engine: sigma per joint and rho re-estimated on the clip's own maps (EM, one seq_smooth per iteration)."""
+        return motion.seq_fit(self, hm, motion.SEQ_SIGMA if sigma is None else sigma, motion.SEQ_RHO if rho is None else rho, iters=iters, radius=radius,
+                              fit_rho=fit_rho)
 
     def seq_tracks(self, hm, people, sigma, rho, radius=None, exclude=SEQ_EXCLUDE, mode='viterbi', state=None, want_filtered=False):
         """Several consistent tracks through single-channel maps -- one torso per person of a clip (include/jcm.h:
         jcm_seq_tracks_viterbi / jcm_seq_tracks_filter).  hm [T,HH,WW] or [S,T,HH,WW], non-negative (spatial_softmax of the torso energy);
-        people = M in 1..4; sigma (a scalar), rho and radius as for seq_filter (predict.seq_taps builds the one tap row); exclude = D in 0..64:
+        people = M in 1..4; sigma (a scalar), rho and radius as for seq_filter (motion.seq_taps builds the one tap row); exclude = D in 0..64:
         pass n sees the map with the cells within D (Chebyshev) of every earlier track's cell zeroed, frame by frame, where that track has a
         positive value -- SEQ_EXCLUDE is an untuned placeholder.  Track 0 is seq_viterbi / seq_filter on the map, bit for bit.
         mode 'viterbi' returns {'path' int32 [S,M,T,2] (row, col), 'maxes' float64 [S,M,T], 'breaks' int32 [S,M,T], 'value' fp32 [S,M,T]};
         mode 'filter' takes state (float64 [S,M,HH*WW] or None at a clip's start) and returns {'coords', 'norm', 'reset', 'value' in the same
         shapes, 'state' float64 [S,M,HH*WW]} and, with want_filtered, 'filtered' fp32 [S,M,T,HH,WW], the beliefs.  Device tensors, without the S axis for a 3-d hm; nothing is read back.  M, D and the map size
         (HH * WW <= 8192) are checked by the library."""
-        from .predict import seq_radius, seq_taps
         if mode not in ('filter', 'viterbi'):
             raise ValueError("mode must be 'filter' or 'viterbi', got %r" % (mode,))
         if state is not None and mode != 'filter':
@@ -472,13 +464,10 @@ class Engine:
         hm4 = self._chk(hm.unsqueeze(0) if single else hm, 4, 'hm')
         S, T, HH, WW = hm4.shape
         M, D = int(people), int(exclude)
-        R = seq_radius(sigma) if radius is None else int(radius)
-        if not 0 <= R <= 16:      # before the taps are built; the library checks it again
-            raise ValueError('radius must be in 0..16, got %r' % (radius,))
-        tap_row = seq_taps(sigma, R, 1)
+        R, tap_row = motion.seq_kernel(sigma, radius, 1)
         taps = tap_row.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         n = max(M, 0)
-        cells, v, f = ('coords', 'norm', 'reset') if mode == 'filter' else ('path', 'maxes', 'breaks')
+        cells, v, f = motion.SEQ_KEYS[mode]
         out = {cells: self._new(S, n, T, 2, dtype=torch.int32), v: self._new(S, n, T, dtype=torch.float64), f: self._new(S, n, T, dtype=torch.int32),
                'value': self._new(S, n, T)}
         if mode == 'filter':

@@ -1,0 +1,139 @@
+"""The motion model of the sequence stages: a joint moves by a truncated Gaussian step per frame, in heat-map cells, or -- with
+mass rho -- jumps anywhere.  Host arithmetic in float64, numpy only: the constants, the taps the library takes (seq_taps), the per-mode keys of what
+the scans return (SEQ_KEYS) and the EM fit of sigma and rho to a clip's own maps (seq_fit; the engine is an argument).  engine.py and the
+prediction modules both read this module; it imports neither."""
+import numpy as np
+
+# The standard deviation of a joint's motion per frame in heat-map cells, and the mass of the uniform "anywhere" term.  Untuned placeholders: no
+# consecutive-frame data is at hand to derive them from.
+SEQ_SIGMA = 1.5
+SEQ_RHO = 0.05
+SEQ_TORSO_SIGMA = 1.5                     # a torso's motion per frame in cells (predict_sequence_people): an untuned placeholder
+SEQ_RADIUS_MAX = 16                       # include/jcm.h: R of jcm_seq_filter / jcm_seq_viterbi
+SEQ_SIGMA_MAX = 64.0                      # what seq_fit clamps a joint's sigma to when its moment reaches that of flat taps (at R = 16 such taps are flat within 3 %)
+SEQ_MODES = ('filter', 'viterbi', 'marginal')
+SEQ_EXCLUDE = 4                           # the exclusion half-width of Engine.seq_tracks, cells: an untuned placeholder
+# Per mode, what the scans of the engine return per frame: the key of the cells, then those of a 'track' beside the points -- (cells, value, flag) but for 'marginal'.
+SEQ_KEYS = {'filter': ('coords', 'norm', 'reset'), 'viterbi': ('path', 'maxes', 'breaks'), 'marginal': ('coords', 'conf', 'norm', 'reset', 'cut')}
+
+
+def _seq_sigma(sigma, K=None):
+    sg = np.asarray(sigma, np.float64).reshape(-1)
+    if sg.size == 0 or not np.all(np.isfinite(sg)) or np.any(sg <= 0):
+        raise ValueError('sigma must be positive and finite, got %r' % (sigma,))
+    if K is not None:
+        if sg.size not in (1, K):
+            raise ValueError('sigma must be a scalar or %d values (one per joint), got %d' % (K, sg.size))
+        sg = np.broadcast_to(sg, (K,))
+    return sg
+
+
+def seq_radius(sigma):
+    """The default tap radius of the sequence stages: min(16, ceil(3 * max sigma))."""
+    return int(min(SEQ_RADIUS_MAX, np.ceil(3.0 * _seq_sigma(sigma).max())))
+
+
+def seq_taps(sigma, radius, K):
+    """The 1-D taps of the motion kernel jcm_seq_filter / jcm_seq_viterbi take: float64 [K, 2 * radius + 1], row k = exp(-d^2 / (2 sigma_k^2)) for
+    d = -radius .. radius, divided by its sum.  sigma: a scalar or K values, in heat-map cells per frame.  The one builder: Engine.seq_* and the
+    restatement of the tests share it."""
+    R = int(radius)
+    if R < 0:
+        raise ValueError('radius must be >= 0, got %r' % (radius,))
+    sg = _seq_sigma(sigma, int(K))
+    d = np.arange(-R, R + 1, dtype=np.float64)
+    w = np.exp(-(d[None, :] * d[None, :]) / (2.0 * sg[:, None] * sg[:, None]))
+    return np.ascontiguousarray(w / w.sum(axis=1, keepdims=True))
+
+
+def seq_kernel(sigma, radius, K):
+    """(R, host taps [K, 2R+1]) of an Engine.seq_* call; radius None is seq_radius(sigma).  R is checked before the taps are built, and again by the library."""
+    R = seq_radius(sigma) if radius is None else int(radius)
+    if not 0 <= R <= SEQ_RADIUS_MAX:
+        raise ValueError('radius must be in 0..16, got %r' % (radius,))
+    return R, seq_taps(sigma, R, K)
+
+
+def seq_moment(sigma, radius):
+    """sum over d of d^2 w_sigma[d] of the truncated taps seq_taps builds: the 1-D second moment of the motion kernel, float64.  Monotone in sigma,
+    from 0 towards the flat taps' R (R + 1) / 3."""
+    R = int(radius)
+    d = np.arange(-R, R + 1, dtype=np.float64)
+    return float(np.sum(d * d * seq_taps(sigma, R, 1)[0]))
+
+
+def seq_sigma_of_moment(target, radius, sigma_max=SEQ_SIGMA_MAX):
+    """The M-step of one joint: the sigma whose truncated taps have seq_moment == target, by bisection in float64 -> (sigma, clamped).  A target at or
+    above the flat taps' R (R + 1) / 3 (no sigma reaches it), or one only a sigma above sigma_max reaches, gives (sigma_max, True); a target so small
+    that no representable taps have it gives the lower end of the bracket, 2^-6 cells."""
+    R = int(radius)
+    target = float(target)
+    if R < 1:
+        raise ValueError('a motion kernel of radius 0 has no sigma to fit')
+    if not target < R * (R + 1) / 3.0 or seq_moment(sigma_max, R) <= target:
+        return float(sigma_max), True
+    lo, hi = 2.0 ** -6, float(sigma_max)
+    if seq_moment(lo, R) >= target:
+        return lo, False
+    for _ in range(200):      # moment(lo) < target <= moment(hi) throughout
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            break
+        if seq_moment(mid, R) < target:
+            lo = mid
+        else:
+            hi = mid
+    return (lo if abs(seq_moment(lo, R) - target) <= abs(seq_moment(hi, R) - target) else hi), False
+
+
+def seq_m_step(trans_sum, sigma, rho, radius, fit_rho=True, sigma_max=SEQ_SIGMA_MAX):
+    """trans_sum float64 [K,3] = (moved, jumped, squared displacement) summed over sequences and frames; sigma [K], rho: the current values ->
+    (sigma' [K], rho', clamped bool [K]).  rho' = sum jumped / (sum moved + sum jumped) over all joints (rho when that is 0 / 0, or with
+    fit_rho=False); sigma_k' solves seq_moment(sigma_k') = squared_k / (2 moved_k) -- the displacement has two axes with the same taps -- and a
+    joint with moved_k == 0 keeps its sigma."""
+    tr = np.asarray(trans_sum, np.float64)
+    sigma = np.array(sigma, np.float64)
+    move, jump, sq = tr[:, 0], tr[:, 1], tr[:, 2]
+    total = move.sum() + jump.sum()
+    new_rho = float(jump.sum() / total) if fit_rho and total > 0 else float(rho)
+    new_sigma, clamped = sigma.copy(), np.zeros(sigma.shape, bool)
+    for k in range(sigma.size):
+        if move[k] > 0:
+            new_sigma[k], clamped[k] = seq_sigma_of_moment(sq[k] / (2.0 * move[k]), radius, sigma_max)
+    return new_sigma, min(max(new_rho, 0.0), 1.0), clamped
+
+
+def seq_fit(engine, hm, sigma=SEQ_SIGMA, rho=SEQ_RHO, iters=10, radius=16, fit_rho=True):
+    """Fit the motion model to a clip without annotations (Baum-Welch).  hm [T,HH,WW,K] or [S,T,HH,WW,K] device maps as for
+    Engine.seq_smooth; sigma (a scalar or K values) and rho are the start.  Each of the `iters` iterations is one Engine.seq_smooth at the current
+    values (E-step), whose 'trans' is read back and summed over s and t on the host in float64 (np.sum over the two axes), and seq_m_step
+    (M-step).  Returns {'sigma' float64 [K], 'rho' float, 'loglik' float64 [iters + 1] -- the sum over sequences, frames and joints of log norm
+    (frames with norm 0, reset 2, left out) at the values BEFORE each iteration and, last, at the returned ones (one more seq_smooth) --,
+    'history' [(sigma [K], rho)] * (iters + 1), the values the entries of loglik belong to, 'clamped' bool [K]: the joints whose sigma the last
+    M-step held at SEQ_SIGMA_MAX}.
+    What is approximate: the motion kernel is not renormalised at the map's border (cells outside contribute nothing), so the transition rows of
+    cells within `radius` of the border sum to less than 1 and the M-step -- exact EM for mass away from the border -- slightly overstates rho and
+    understates sigma for tracks along it; and the taps are truncated at `radius`, so no sigma explains a mean squared step of R (R + 1) / 3 per
+    axis or more: such a joint is clamped and reported.  radius is fixed over the iterations (16, the largest, by default) so that a growing sigma
+    is not cut off by the radius its start implied."""
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError('iters must be >= 1, got %r' % (iters,))
+    K = int(hm.shape[-1])
+    sg = np.array(_seq_sigma(sigma, K), np.float64)
+    rho = float(rho)
+    R = int(radius)
+    loglik, history = [], []
+    clamped = np.zeros(K, bool)
+
+    def e_step():
+        r = engine.seq_smooth(hm, sg, rho, radius=R, want_smoothed=False)
+        norm = r['norm'].cpu().numpy().reshape(-1)
+        loglik.append(float(np.sum(np.log(norm[norm > 0]))))
+        history.append((sg.copy(), rho))
+        return r['trans'].cpu().numpy().reshape(-1, K, 3).sum(axis=0)
+
+    for _ in range(iters):
+        sg, rho, clamped = seq_m_step(e_step(), sg, rho, R, fit_rho=fit_rho)
+    e_step()
+    return {'sigma': sg, 'rho': rho, 'loglik': np.array(loglik, np.float64), 'history': history, 'clamped': clamped}

@@ -1,0 +1,364 @@
+"""Frame sequences: predict_sequence takes the frames of a clip, all of one size, and adds to every frame's result a 'track': one
+position per joint that is consistent over the clip, from Engine.seq_filter (causal) or Engine.seq_viterbi (the most probable track) on the
+stacked heat maps.  SequenceTracker is the online form of the filter.  SEQ_SIGMA and SEQ_RHO (motion.py) are not fitted to anything; what tracking
+buys has been measured on rendered clips only, not on real video.
+
+Clips with several people: predict_sequence_people pulls up to four consistent torso tracks out of the frames' torso maps
+(Engine.seq_tracks: successive passes of the temporal model, each with the earlier tracks' neighbourhoods excluded), runs the spatial model
+once per (frame, track) with the blob at the track's cell and tracks every person's joints; PeopleTracker is its online form.  SEQ_EXCLUDE and
+SEQ_TORSO_SIGMA are untuned placeholders too.
+
+Smoothed marginals and the fit: predict_sequence(mode='marginal') takes every frame's position from the smoothed posterior
+P(x_t | all frames) of Engine.seq_smooth, with its confidence; motion.seq_fit re-estimates sigma (per joint) and rho on a clip's own maps by EM,
+without annotations, and predict_sequence(fit_iters=) runs any mode with the fitted values.
+
+Zoomed clips: predict_sequence_zoom runs the zoom pass on every frame of a clip in windows that follow the person and share
+one cell lattice (zoom_window_track), so that two frames' maps differ by a whole number of cells, and tracks the joints through them with
+Engine.seq_filter / seq_viterbi(shift=), the scans with a per-frame shift of the belief plane."""
+import numpy as np
+import torch
+
+from ..evaluation import fit_to_source, window_to_source
+from ..motion import SEQ_EXCLUDE, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, seq_fit
+from .images import FIT_SIDE_MAX, FRAME, STRIDE, ZOOM_TORSO_JOINTS, ZOOM_TORSO_PIXELS, DeviceTimer, _coords_to_points, _upload, predict_images, second_pass, zoom_entry
+
+
+def torso_length(points):
+    """images.torso_length as the package's surface has it bound when the call is made: what replaces predict.torso_length replaces it for the clips too."""
+    from .. import predict
+    return predict.torso_length(points)
+
+
+def _first_pass(engine, frames, clip=None, **kw):
+    """Pass 1 of a clip: the frames, of one size -- that of the earlier pushes of `clip`, a tracker --, through predict_images(keep_maps=True, **kw)."""
+    if not isinstance(frames, (list, tuple)) or len(frames) == 0:
+        raise ValueError('frames must be a non-empty list of uint8 [h,w,3] images of one size')
+    shapes = {tuple(f.shape) for f in frames}
+    if len(shapes) != 1:
+        raise ValueError('the frames of a clip have one size (one letterbox geometry); got %s' % sorted(shapes))
+    if clip is not None:
+        clip.same_size(shapes.pop())
+    return predict_images(engine, frames, keep_maps=True, **kw)
+
+
+def _track_entries(seq, mode, to_source, extra=None):
+    """The dict of one scan (Engine.seq_filter / seq_viterbi / seq_smooth) over T frames -> one 'track' dict per frame, by the mode's keys in SEQ_KEYS.
+    to_source: cells as points [T,K,2] of the maps' frame -> (points, inside) in the frames' own pixels; extra: per frame, fields that follow 'inside'."""
+    cells, *keys = SEQ_KEYS[mode]
+    pts, inside = to_source(_coords_to_points(seq[cells]))
+    host = {k: seq[k].cpu().numpy() for k in keys}
+    return [dict({'mode': mode, 'points': pts[t], 'inside': inside[t]}, **(extra[t] if extra else {}), **{k: host[k][t] for k in keys}) for t in range(pts.shape[0])]
+
+
+def _geom(results):
+    return np.array([r['geom'] for r in results], np.int64)
+
+
+def _stacked(results, key):
+    return torch.stack([r['maps'][key] for r in results]).contiguous()
+
+
+def _finish(results, keep_maps):
+    for r in ([] if keep_maps else results):
+        del r['maps']
+    return results
+
+
+def _seq_call(engine, mode, hm, sigma, rho, radius, **kw):
+    if mode == 'marginal':
+        return engine.seq_smooth(hm, sigma, rho, radius=radius, want_smoothed=False)
+    return (engine.seq_filter if mode == 'filter' else engine.seq_viterbi)(hm, sigma, rho, radius=radius, **kw)
+
+
+def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
+                     keep_maps=False, fit_iters=0, **kw):
+    """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
+    geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
+    [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal), Engine.seq_viterbi (mode 'viterbi', the most probable
+    track) or Engine.seq_smooth (mode 'marginal', the arg-max of every frame's smoothed posterior P(x_t | all frames));
+    evaluation.fit_to_source maps the cells back.  Returns predict_images' dicts, every key with the value it has there, plus
+      'track': {'mode', 'points' float64 [K,2] (row, col) in the frame's own pixels, 'inside' bool [K], 'norm' or 'maxes' float64 [K], 'reset' or
+                'breaks' int [K]}  (the library's Z / M and its flags, include/jcm.h); mode 'marginal': 'conf' float32 [K] (the posterior at the
+                point), 'norm', 'reset' and 'cut' int [K].
+    fit_iters = ITERS > 0 first re-estimates sigma (per joint) and rho on the clip's own maps (seq_fit below, starting from sigma and rho) and runs
+    the mode with the fitted values; frame 0's dict then carries 'seq_fit', seq_fit's return value for the clip.
+    'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
+    the defaults SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what the track buys with trained weights has not been measured.
+    One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
+    frame, are out of scope."""
+    if mode not in SEQ_MODES:
+        raise ValueError("mode must be 'filter', 'viterbi' or 'marginal', got %r" % (mode,))
+    if not 0 <= int(fit_iters) <= 100:
+        raise ValueError('fit_iters must be 0 (off) or the EM iterations 1..100, got %r' % (fit_iters,))
+    if people != 1:
+        raise ValueError('predict_sequence tracks one person: people=%r would need an association of people across frames, which is out of scope' % (people,))
+    if zoom:
+        raise ValueError('predict_sequence has no zoom pass: its windows would move from frame to frame, which is out of scope')
+    results = _first_pass(engine, frames, use_sm=use_sm, batch_size=batch_size, **kw)
+    with torch.cuda.stream(engine._stream):
+        hm = _stacked(results, 'sm' if use_sm else 'pd')
+        fit = seq_fit(engine, hm, sigma, rho, iters=int(fit_iters)) if int(fit_iters) else None
+        if fit is not None:
+            sigma, rho = fit['sigma'], fit['rho']
+        seq = _seq_call(engine, mode, hm, sigma, rho, radius)
+        geom = _geom(results)
+        for r, track in zip(results, _track_entries(seq, mode, lambda pts: fit_to_source(pts, geom))):
+            r['track'] = track
+        if fit is not None:
+            results[0]['seq_fit'] = fit
+    return _finish(results, keep_maps)
+
+
+# ------------------------------------------------------------------ zoomed clips
+ZOOM_MAP = (FRAME[0] // STRIDE, FRAME[1] // STRIDE)      # 60 x 90 cells: a window of 60 p x 90 p source pixels puts p x p of them into every cell
+SEQ_ZOOM_MODES = ('filter', 'viterbi')
+
+
+def zoom_window_track(points, inside, torso, geom, frame=FRAME):
+    """Where the second pass of a CLIP looks; host arithmetic only, float64 and integers.  One row per frame: points float
+    [T,K,2] and inside bool [T,K], the tracked pass-1 joints in the frame's pixels ('track' of predict_sequence); torso float [T,2], the torso
+    track in the frame's pixels; geom int [6] or [T,6], the clip's one pass-1 fit (y0, x0, ch, cw, h, w).  All windows of the clip share ONE
+    lattice of pitch p source pixels per heat-map cell, so that two windows differ by a whole number of cells:
+      valid frame: the four torso joints are inside and torso_length >= 2 * STRIDE * h / ch (the skip rules of zoom_windows);
+      tmed = the median of torso_length over the valid frames;  p = max(1, floor(tmed * STRIDE / ZOOM_TORSO_PIXELS + 0.5));
+      wh = 60 p, ww = 90 p for every frame: exactly 3:2, so fit_geometry gives the whole 480 x 720 frame and a cell is exactly p x p pixels;
+      wy0 = p * floor((cy - 30 p) / p + 0.5), wx0 = p * floor((cx - 45 p) / p + 0.5) with (cy, cx) the frame's torso point, clamped to the
+        nearest multiple of p at which the window still holds a pixel of the frame: -59 p <= wy0 <= p * ((h - 1) // p), -89 p <= wx0 <=
+        p * ((w - 1) // p) (Engine.fit_windows refuses a window that shares nothing with the image);
+      shift[t] = ((wy0[t] - wy0[t-1]) / p, (wx0[t] - wx0[t-1]) / p), exact integers, shift[0] = (0, 0): cell (y, x) of frame t's maps is cell
+        (y + sy, x + sx) of frame t-1's -- the convention of jcm_seq_filter_moving / jcm_seq_viterbi_moving;
+      cells = the torso point taken forward through the window, floor((c - w0 + 0.5) / p - 0.5) // STRIDE clamped to the map, as zoom_windows
+        computes it: where the torso blob of the second pass goes.
+    Returns (windows int64 [T,5] = (frame, wy0, wx0, wh, ww), cells int32 [T,2], shift int32 [T,2], p, valid bool [T]).  Every frame gets a
+    window, a valid one or not: the track needs the maps of all of them.  With no valid frame the clip is not zoomed: p = 0 and windows,
+    cells and shift are zero.  90 p > FIT_SIDE_MAX raises ValueError.
+    One pitch per clip is a stated limit: a person who walks towards the camera changes scale, and the clip's median decides the pitch."""
+    pts, inside, torso = np.asarray(points, np.float64), np.asarray(inside, bool), np.asarray(torso, np.float64)
+    T = pts.shape[0]
+    geom = np.asarray(geom, np.int64)
+    if geom.ndim == 1:
+        geom = np.broadcast_to(geom, (T, 6)) if geom.shape == (6,) else geom
+    if pts.ndim != 3 or T < 1 or pts.shape[2] != 2 or pts.shape[1] < 8 or inside.shape != pts.shape[:2] or torso.shape != (T, 2) or geom.shape != (T, 6):
+        raise ValueError('zoom_window_track expects points [T,K >= 8,2], inside [T,K], torso [T,2] and geom [6] or [T,6]; got %s, %s, %s, %s' %
+                         (pts.shape, inside.shape, torso.shape, geom.shape))
+    if (geom != geom[0]).any():
+        raise ValueError('zoom_window_track: the frames of a clip have one fit; got several')
+    OH, OW = int(frame[0]), int(frame[1])
+    MH, MW = OH // STRIDE, OW // STRIDE
+    ch, h, w = int(geom[0, 2]), int(geom[0, 4]), int(geom[0, 5])
+    t = torso_length(pts)
+    torso_joints = [j for pair in ZOOM_TORSO_JOINTS for j in pair]
+    valid = inside[:, torso_joints].all(axis=1) & ~(t < 2.0 * STRIDE * h / ch)
+    windows = np.zeros((T, 5), np.int64)
+    windows[:, 0] = np.arange(T)
+    if not valid.any():
+        return windows, np.zeros((T, 2), np.int32), np.zeros((T, 2), np.int32), 0, valid
+    p = max(1, int(np.floor(np.median(t[valid]) * STRIDE / ZOOM_TORSO_PIXELS + 0.5)))
+    wh, ww = MH * p, MW * p
+    if ww > FIT_SIDE_MAX or wh > FIT_SIDE_MAX:
+        raise ValueError('zoom_window_track: a torso of %.1f pixels gives windows of %d x %d pixels; the sides a fit takes end at %d' %
+                         (float(np.median(t[valid])), wh, ww, FIT_SIDE_MAX))
+    origin, cells = np.empty((T, 2), np.int64), np.empty((T, 2), np.int32)
+    for axis, (half, cells_n, size, content) in enumerate(((MH // 2, MH, h, OH), (MW // 2, MW, w, OW))):
+        o = p * np.floor((torso[:, axis] - half * p) / p + 0.5).astype(np.int64)
+        o = np.clip(o, -(cells_n - 1) * p, p * ((size - 1) // p))
+        origin[:, axis] = o
+        at = np.floor((torso[:, axis] - o + 0.5) * content / (cells_n * p) - 0.5).astype(np.int64) // STRIDE      # the fit's content origin is 0
+        cells[:, axis] = np.clip(at, 0, cells_n - 1)
+    windows[:, 1:3] = origin
+    windows[:, 3], windows[:, 4] = wh, ww
+    shift = np.zeros((T, 2), np.int64)
+    shift[1:] = (origin[1:] - origin[:-1]) // p
+    return windows, cells, shift.astype(np.int32), p, valid
+
+
+def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, radius=None, batch_size=16, people=1,
+                          keep_maps=False, fit_iters=0, pad=0, timing=None, **kw):
+    """The frames of ONE clip with one person in it, tracked a second time at the scale the tower was trained on; frames as
+    for predict_sequence.
+      1. predict_sequence(frames, mode, ..., torso_prob=True): the first pass and its 'track'; the torso track comes from the frames'
+         torso_prob maps with Engine.seq_tracks(people=1), as predict_sequence_people obtains its tracks;
+      2. zoom_window_track: one window per frame around the torso track, all on one lattice of pitch p, and the whole-cell shift of every
+         frame's lattice against the one before;
+      3. Engine.fit_windows of every frame, a forward with the blob at the window's torso cell and want_prob=True, batch_size at a time; the
+         'sm' maps stacked as [T,60,90,K]; Engine.seq_filter or Engine.seq_viterbi with shift=; evaluation.window_to_source maps every frame's
+         cells back through that frame's window.
+    Returns predict_sequence's dicts, every key with its value, plus
+      'zoom': one entry as predict_images(zoom=True) writes it, the per-frame arg-max of the second pass; 'window' is the frame's window here;
+      'track_zoom': {'mode', 'points' float64 [K,2] (row, col) in the frame's own pixels, 'inside' bool [K], 'window' (y0, x0, h, w), 'shift'
+                     (sy, sx), 'pitch', and 'norm' / 'reset' or 'maxes' / 'breaks' [K] as in 'track'}.
+    A clip with no valid frame (zoom_window_track) is not zoomed: every frame's 'zoom' entry has zoomed False and the pass-1 values, and there
+    is no 'track_zoom'.  timing also receives 'zoom_fit_ms', 'zoom_forward_ms' and 'seq_zoom_pitch'.
+    The modes are 'filter' and 'viterbi': mode='marginal' and fit_iters raise ValueError (jcm_seq_smooth has no moving form), people != 1 too.
+    One pitch per clip is a stated limit; torso_sigma, sigma and rho are untuned placeholders, and what this buys with trained weights has not
+    been measured."""
+    if mode not in SEQ_ZOOM_MODES:
+        raise ValueError("mode must be 'filter' or 'viterbi', got %r (the smoother has no moving form: mode 'marginal' is not offered with zoomed clips)" % (mode,))
+    if int(fit_iters) != 0:
+        raise ValueError('predict_sequence_zoom has no fit: fit_iters=%r needs the smoother, which has no moving form' % (fit_iters,))
+    if people != 1:
+        raise ValueError('predict_sequence_zoom tracks one person: people=%r is out of scope' % (people,))
+    B = int(batch_size)
+    results = predict_sequence(engine, frames, mode=mode, sigma=sigma, rho=rho, radius=radius, use_sm=True, batch_size=B, keep_maps=True, torso_prob=True,
+                               pad=pad, timing=timing, **kw)
+    T, zoom_ms = len(results), [0.0, 0.0]
+    with torch.cuda.stream(engine._stream):
+        torso = engine.seq_tracks(_stacked(results, 'torso_prob'), 1, torso_sigma, rho, mode=mode)
+        tc = torso[SEQ_KEYS[mode][0]].cpu().numpy().reshape(T, 2).astype(np.float64)
+        geom1 = _geom(results)
+        torso_px, _ = fit_to_source(tc * STRIDE, geom1)
+        points, inside = np.stack([r['track']['points'] for r in results]), np.stack([r['track']['inside'] for r in results])
+        wins, cells, shift, pitch, valid = zoom_window_track(points, inside, torso_px, geom1)
+        lengths = torso_length(points)
+        second, parts = None, []
+        if pitch:
+            for lo in range(0, T, B):
+                local = wins[lo:lo + B].copy()
+                local[:, 0] -= lo
+                parts.append(second_pass(engine, [_upload(im, engine.device) for im in frames[lo:lo + B]], local, cells[lo:lo + B], B, pad, True, zoom_ms))
+            second = {key: tuple(np.concatenate([p[0][key][i] for p in parts]) for i in range(2)) for key in ('pd', 'sm')}
+            geom2, hm = np.concatenate([p[1] for p in parts]), torch.cat([p[2] for p in parts]).contiguous()
+            seq = _seq_call(engine, mode, hm, sigma, rho, radius, shift=shift)
+            sizes = np.array([r['size'] for r in results], np.int64)
+            extra = [{'window': tuple(int(v) for v in wins[t, 1:]), 'shift': (int(shift[t, 0]), int(shift[t, 1])), 'pitch': int(pitch)} for t in range(T)]
+            for r, track, maps in zip(results, _track_entries(seq, mode, lambda pts: window_to_source(pts, geom2, wins, sizes), extra), hm):
+                r['track_zoom'] = track
+                r['maps']['sm_zoom'] = maps
+        for t, r in enumerate(results):
+            r['zoom'] = [zoom_entry(wins[t], lengths[t], r, second, t)]
+    if timing is not None:
+        timing.update(zoom_fit_ms=zoom_ms[0], zoom_forward_ms=zoom_ms[1], seq_zoom_pitch=int(pitch))
+    return _finish(results, keep_maps)
+
+
+class _Clip:
+    """What the online trackers share: the size of the clip's frames, fixed by the first push, and push().  A tracker has its state, None at a clip's
+    start, and _track(results), which adds what it tracks to the dicts of pass 1 and moves the state on."""
+
+    def reset(self):
+        self.state, self.shape = None, None
+
+    def same_size(self, shape):
+        if self.shape is not None and shape != self.shape:
+            raise ValueError('the frames of a clip have one size: this clip began with %s, got %s' % (self.shape, shape))
+        self.shape = shape
+
+    def push(self, frames, keep_maps=False):
+        results = _first_pass(self.engine, frames, clip=self, **self.pass1)
+        self._track(results)
+        return _finish(results, keep_maps)
+
+
+class SequenceTracker(_Clip):
+    """The online form of predict_sequence(mode='filter'): push(frames) takes the next frames of the clip, a few or one at a time, and returns
+    their dicts with 'track'; the filter's float64 belief is carried from call to call, so any split of a clip gives the values of one
+    predict_sequence over all of it.  Every push must bring frames of the first push's size.  reset() starts a new clip."""
+
+    def __init__(self, engine, sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, **kw):
+        self.engine, self.sigma, self.rho, self.radius, self.use_sm = engine, sigma, rho, radius, use_sm
+        self.pass1 = dict(kw, use_sm=use_sm, batch_size=batch_size)
+        self.reset()
+
+    def _track(self, results):
+        with torch.cuda.stream(self.engine._stream):
+            seq = self.engine.seq_filter(_stacked(results, 'sm' if self.use_sm else 'pd'), self.sigma, self.rho, radius=self.radius, state=self.state)
+            self.state = seq['state']
+            geom = _geom(results)
+            for r, track in zip(results, _track_entries(seq, 'filter', lambda pts: fit_to_source(pts, geom))):
+                r['track'] = track
+
+
+# ------------------------------------------------------------------ clips with several people
+def _people_joint_maps(engine, pd, cells, batch_size):
+    """pd [T,60,90,9], the frames' part-detector probabilities, and cells int32 [M,T,2], every track's torso cell -> [M,T,60,90,9]: per (frame,
+    track) the spatial model on [pd of the frame, the torso blob at the track's cell], as probabilities; batch_size frames at a time."""
+    M, T = cells.shape[:2]
+    out = []
+    for lo in range(0, T, batch_size):
+        hi = min(T, lo + batch_size)
+        at = cells[:, lo:hi].permute(1, 0, 2).reshape(-1, 2).contiguous()                      # (frame, track) order
+        blob = engine.torso_infer(None, cells=at)['torso']
+        hm10 = torch.cat([pd[lo:hi].repeat_interleave(M, dim=0), blob], dim=3)
+        prob, _ = engine.softmax_argmax(engine.spatial_model(hm10), want_prob=True)
+        out.append(prob.view(hi - lo, M, *prob.shape[1:]))
+    return torch.cat(out).permute(1, 0, 2, 3, 4).contiguous()
+
+
+
+
+def _people_pass(engine, results, people, mode, sigma, torso_sigma, rho, radius, exclude, people_threshold, batch_size, states, timing):
+    """Steps 2 to 5 of predict_sequence_people on the dicts of pass 1, which gain 'tracks' and 'track'; states: the filter's (torso, joints).  Returns the new states."""
+    M, (cells_key, value, flag) = int(people), SEQ_KEYS[mode]
+    with torch.cuda.stream(engine._stream):
+        timer = DeviceTimer(engine)
+        torso = engine.seq_tracks(_stacked(results, 'torso_prob'), M, torso_sigma, rho, exclude=exclude, mode=mode, state=states[0])
+        timer.mark()
+        hm = _people_joint_maps(engine, _stacked(results, 'pd'), torso[cells_key], int(batch_size))
+        timer.mark()
+        seq = _seq_call(engine, mode, hm, sigma, rho, radius, **({'state': states[1]} if mode == 'filter' else {}))
+        geom = _geom(results)
+        tc, tv, tf = (torso[k].cpu().numpy() for k in (cells_key, 'value', flag))                 # [M,T,2], [M,T], [M,T]
+        tpts, _ = fit_to_source(np.where(tc < 0, -1.0, tc.astype(np.float64) * STRIDE).transpose(1, 0, 2), geom)      # [T,M,2]
+        present = (tv > people_threshold) & (tf != 2)
+        count = int(present.any(axis=1).sum())      # the tracks present in at least one frame of the call
+        person = [_track_entries({k: seq[k][m] for k in SEQ_KEYS[mode]}, mode, lambda pts: fit_to_source(pts, geom)) for m in range(M)]
+        for t, r in enumerate(results):
+            r['tracks'] = dict({'mode': mode, 'count': count, 'torso': tpts[t], 'torso_value': tv[:, t], 'present': present[:, t]},
+                               **{k: np.stack([p[t][k] for p in person]) for k in ('points', 'inside', value, flag)})
+            r['track'] = person[0][t]
+        if timing is not None:
+            timer.add(timing, 'seq_torso_ms', 'seq_people_sm_ms')
+    return torso.get('state'), seq.get('state')
+
+
+def _check_people(people, zoom):
+    if not isinstance(people, int) or not 1 <= people <= 4:
+        raise ValueError('people must be an integer in 1..4, got %r' % (people,))
+    if zoom:
+        raise ValueError('predict_sequence_people has no zoom pass: a zoom pass per track is out of scope')
+
+
+def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, exclude=SEQ_EXCLUDE,
+                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, **kw):
+    """The frames of ONE clip with up to people = M (1..4) persons in it; frames as for predict_sequence.  On the device:
+      1. predict_images(frames, use_sm=True, people=1, keep_maps=True, torso_prob=True, **kw): per frame the part-detector maps and the torso map
+         spatial_softmax(E);
+      2. Engine.seq_tracks on the stacked torso maps [T,60,90]: M torso tracks -- track 0 the most probable torso track (mode 'viterbi') or the
+         causal filter's (mode 'filter'), track n the same through what is left once the cells within `exclude` of the tracks before it are
+         taken out of every frame; identity is stable by construction, tracks are reported in pass order and never re-sorted;
+      3. per (frame, track) the spatial model on [the frame's pd maps, the blob at the track's cell], batch_size frames at a time;
+      4. the existing Engine.seq_filter / seq_viterbi on the [M,T,60,90,K] maps, the persons as its sequences;
+      5. evaluation.fit_to_source.
+    Returns predict_images' dicts, every key with its value, plus
+      'tracks': {'mode', 'count' (the tracks present in at least one frame of the call), 'torso' float64 [M,2] (row, col) in the frame's pixels,
+                 'torso_value' float32 [M] (the torso map at the track's cell, 0 where an earlier track excludes it), 'present' bool [M]
+                 (torso_value > people_threshold and the torso pass did not meet an all-zero map there, flag 2), 'points' float64 [M,K,2],
+                 'inside' bool [M,K], 'maxes' / 'breaks' or 'norm' / 'reset' [M,K]}
+      'track': track 0 in the layout of predict_sequence, so that what reads 'track' works unchanged.
+    timing also receives 'seq_torso_ms' and 'seq_people_sm_ms', the device times of steps 2 and 3.  'maps' is kept only with keep_maps.
+    exclude (SEQ_EXCLUDE = 4 cells), torso_sigma (SEQ_TORSO_SIGMA = 1.5), sigma, rho and people_threshold are untuned placeholders -- no
+    consecutive-frame data and no trained weights are at hand -- and what this buys with trained weights has not been measured.  zoom=True
+    raises ValueError."""
+    if mode not in ('filter', 'viterbi'):
+        raise ValueError("mode must be 'filter' or 'viterbi', got %r (the torso tracks have the filter and Viterbi only)" % (mode,))
+    _check_people(people, zoom)
+    results = _first_pass(engine, frames, use_sm=True, people=1, batch_size=batch_size, torso_prob=True, timing=timing, **kw)
+    _people_pass(engine, results, people, mode, sigma, torso_sigma, rho, radius, exclude, people_threshold, batch_size, (None, None), timing)
+    return _finish(results, keep_maps)
+
+
+class PeopleTracker(_Clip):
+    """The online form of predict_sequence_people(mode='filter'): push(frames) takes the next frames of the clip and returns their dicts with
+    'tracks' and 'track'; the float64 beliefs of the torso passes and of the persons' joints are both carried from call to call, so any split of
+    a clip gives the values of one predict_sequence_people over all of it -- except 'count', which counts over the frames of its own push.
+    Every push must bring frames of the first push's size.  reset() starts a new clip."""
+
+    def __init__(self, engine, people, sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, exclude=SEQ_EXCLUDE, people_threshold=0.0, radius=None,
+                 batch_size=16, **kw):
+        _check_people(people, False)
+        self.engine, self.people, self.pass1 = engine, people, dict(kw, use_sm=True, people=1, batch_size=batch_size, torso_prob=True)
+        self.args = (sigma, torso_sigma, rho, radius, exclude, people_threshold, batch_size)
+        self.reset()
+
+    def _track(self, results):
+        self.state = _people_pass(self.engine, results, self.people, 'filter', *self.args, self.state or (None, None), None)
