@@ -419,6 +419,29 @@ int jcm_seq_viterbi_moving(jcm_handle h, const float* hm, int S, int T, int HH, 
 int jcm_seq_smooth(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
                    float* smoothed, int32_t* coords, float* conf, double* norm, int32_t* reset, double* mass, int32_t* cut, double* trans);
 
+/* -- frame sequences, online: the fixed-lag smoother ------------------------------------------
+ * The smoothed marginal of frame s once frame s + L has been seen: P(x_s | frames 0 .. s+L), L >= 1 frames late.  With N frames pushed so far,
+ * h(s) = s + L, or min(s + L, N - 1) when the clip is flushed; frame s is emitted once h(s) <= N - 1, and its outputs are the outputs jcm_seq_smooth
+ * writes for frame s when given frames 0 .. h(s) of the clip, bit for bit: smoothed, coords, conf, mass, cut, norm, reset -- the step-by-step G
+ * test (cut) and the chain split at reset != 0 included.  There is no trans: the fit stays offline.
+ * The library keeps no state; the caller holds the WINDOW: the P frames still pending from earlier calls followed by W - P new ones.  hm: device
+ * fp32 [S,W,HH,WW,K], the maps of all W;  belief float64 [S*K][W][HH*WW], norm float64 [S,W,K] and reset int32 [S,W,K] hold in [.., :P] what the
+ * earlier call wrote for those frames and are filled for frames P .. W-1.  taps, R, rho as for jcm_seq_filter.
+ * Forward: the recurrence of jcm_seq_filter (the library's one copy of it) over frames P .. W-1, from belief[.., P-1]; with P == 0 as at a clip's
+ *   start.  P == W: nothing new, no forward launch.
+ * Emission: E = flush ? W : max(0, W - L) frames.  For e < E, beta = 1 at t = min(e + L, W - 1), then the backward step of jcm_seq_smooth (the
+ *   library's one copy of it) for t down to e; frame e's outputs alone are written.  One work group per (s, k, e); E == 0 launches nothing.
+ *   Afterwards the caller keeps window frames E .. W-1 as the next call's pending frames.  Any 0 <= P <= W is legal (P <= L is not required).
+ * Outputs (device), for the E emitted frames:  smoothed fp32 [S,E,HH,WW,K], may be NULL;  coords int32 [S,E,2,K], required when E > 0;  conf
+ *   fp32 [S,E,K], mass float64 [S,E,K], cut int32 [S,E,K], may be NULL.  norm and reset of an emitted frame are rows of the window's.
+ * Any split of a clip into calls gives the same bits.  HH * WW <= 6144 as for jcm_seq_smooth.
+ * JCM_ERR_ARG, nothing launched and no output touched: every refusal of jcm_seq_smooth (W in T's place, so W < 1);  P outside 0 .. W;  L < 1
+ * (lag 0 is the filter: jcm_seq_filter);  flush not 0 or 1;  belief, norm or reset NULL;  coords NULL when E > 0;  S * W * K >= 2^31.
+ * Enqueues on the handle's stream and does not synchronise (growing the workspace, which holds the taps and the scan's scratch, does). */
+int jcm_seq_smooth_lag(jcm_handle h, const float* hm, int S, int W, int P, int HH, int WW, int K, const double* taps, int R, double rho, int L,
+                       int flush, double* belief, double* norm, int32_t* reset, float* smoothed, int32_t* coords, float* conf, double* mass,
+                       int32_t* cut);
+
 /* -- several tracks through single-channel maps: one torso track per person of a clip ----------
  * hm: device fp32 [S,T,HH,WW], one non-negative channel (the torso probabilities of the frames); M in 1..4 tracks; taps HOST [2R+1], R and rho as for
  * jcm_seq_* with one tap row; D in 0..64, the exclusion half-width in cells.

@@ -63,6 +63,9 @@ SIGNATURES = {
     'jcm_seq_smooth': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                       ctypes.c_int, ctypes.c_double, _c_float_p, _c_i32_p, _c_float_p, ctypes.c_void_p, _c_i32_p, ctypes.c_void_p, _c_i32_p,
                                       ctypes.c_void_p]),
+    'jcm_seq_smooth_lag': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_void_p, _c_i32_p, _c_float_p, _c_i32_p, _c_float_p, ctypes.c_void_p, _c_i32_p]),
     'jcm_seq_tracks_viterbi': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_i32_p, ctypes.c_void_p, _c_i32_p,
                                               _c_float_p]),

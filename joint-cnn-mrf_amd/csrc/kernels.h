@@ -439,6 +439,12 @@ hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, con
 constexpr int kSeqSmoothMaxHW = 6144;
 hipError_t seq_smooth(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, double* belief, float* smoothed,
                       int32_t* coords, float* conf, double* norm, int32_t* reset, double* mass, int32_t* cut, double* trans, hipStream_t st);
+// The fixed-lag form (jcm.h: jcm_seq_smooth_lag) on a window of W frames the caller holds, P of them pending from earlier calls: the scan over
+// frames P .. W-1 from belief[.., P-1] (no launch with P == W), then one work group per (s, k, e < E) that walks frame min(e + L, W-1) down to e with the
+// backward step above and writes frame e's outputs [S,E,..] (no launch with E == 0).  scan_coords: scratch int32 [S, W-P, 2, K], required with P < W.
+hipError_t seq_smooth_lag(const float* hm, int S, int W, int P, int E, int L, int HH, int WW, int K, const double* taps, int R, double om, double u,
+                          int32_t* scan_coords, double* belief, double* norm, int32_t* reset, float* smoothed, int32_t* coords, float* conf, double* mass,
+                          int32_t* cut, hipStream_t st);
 // ---- seq_tracks.hip : several torso tracks through single-channel maps -------------
 // hm [S,T,HH,WW]; M in 1..4 passes of the scan above at K = 1 (seq_scan.h), pass n with the cells within D of the tracks m < n zeroed while the frame is
 // staged; one work group per clip and pass, the passes in stream order.  taps: DEVICE [2R+1].  Outputs [S,M,..] in the layouts of jcm.h.

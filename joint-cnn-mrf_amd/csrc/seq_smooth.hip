@@ -9,6 +9,8 @@
 // The passes use the ADJOINT index of the filter's (q(y + dy, x), c(y, x + dx)): beta_{t-1}(x') sums over where the position goes, not where it came
 // from.  Consecutive lanes read consecutive cells of a row dy away, as in the filter's vertical pass: conflict-free ds_read_b64.  A cell i belongs to
 // thread i % 1024 in every pass that writes it, so a plane is only read across threads between barriers; every sum is sq_block_sum's.
+// The fixed-lag form (jcm_seq_smooth_lag) is the same two steps on a window the caller holds: the scan over the window's new frames from the
+// last pending belief, then one work group per (sequence, joint, emitted frame) that runs the same backward step from L frames ahead down to its frame.
 #include <string>
 
 #include "seq_entry.h"
@@ -39,18 +41,20 @@ __global__ __launch_bounds__(kSqThreads) void seq_smooth_fwd_kernel(const float*
                  belief + (size_t)blockIdx.x * T * HH * WW);
 }
 
-__global__ __launch_bounds__(kSqThreads) void seq_smooth_bwd_kernel(const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
-                                                                    int R, double om, double u, const double* __restrict__ belief,
-                                                                    const double* __restrict__ norm, const int32_t* __restrict__ reset,
-                                                                    float* __restrict__ smoothed, int32_t* __restrict__ coords, float* __restrict__ conf,
-                                                                    double* __restrict__ mass, int32_t* __restrict__ cut, double* __restrict__ trans, int vec) {
-  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // B [HW], C [HW], C2 [HW]
+// The backward pass of one (sequence, joint), the ONE copy of its step (seq_smooth_bwd_kernel and seq_smooth_lag_bwd_kernel call it): beta = 1 at
+// frame t_start, then frames t_start down to t_end as include/jcm.h states them.  Frames above t_write only carry beta down (their G test and their
+// reset still apply); frames t_write .. t_end write their outputs.  ag: the group's beliefs [.][HW] from the sequence's frame 0;  fin: the index of that
+// frame in hm, norm and reset;  fout: the index frame 0 would have in the outputs.  The transition below t_end is not taken.  trans may be NULL.
+__device__ __forceinline__ void sq_smooth_back(double* sq_planes, const float* __restrict__ hm, int HH, int WW, int K, const double* __restrict__ taps, int R,
+                                               double om, double u, const double* __restrict__ ag, const double* __restrict__ norm,
+                                               const int32_t* __restrict__ reset, size_t fin, size_t fout, int k, int t_start, int t_end, int t_write,
+                                               float* __restrict__ smoothed, int32_t* __restrict__ coords, float* __restrict__ conf, double* __restrict__ mass,
+                                               int32_t* __restrict__ cut, double* __restrict__ trans, int vec) {
   __shared__ double w[kSqTaps];
   __shared__ double w2[kSqTaps];
   __shared__ double rd[kSqWaves];
   __shared__ int ri[kSqWaves];
   const int tid = threadIdx.x;
-  const int s = blockIdx.x / K, k = blockIdx.x - s * K;
   const int HW = HH * WW, n = HW * K;
   double* B = sq_planes;
   double* C = sq_planes + HW;
@@ -62,10 +66,10 @@ __global__ __launch_bounds__(kSqThreads) void seq_smooth_bwd_kernel(const float*
   }
   for (int i = tid; i < HW; i += kSqThreads) B[i] = 1.0;
   __syncthreads();
-  const double* ag = belief + (size_t)blockIdx.x * T * HW;
 
-  for (int t = T - 1; t >= 0; --t) {
-    const size_t ft = (size_t)s * T + t;
+  for (int t = t_start; t >= t_end; --t) {
+    const size_t ft = fin + t, fo = fout + t;
+    const bool wr = t <= t_write;      // thread-uniform
     const double* at = ag + (size_t)t * HW;
     double gp = 0.0;
     for (int i = tid; i < HW; i += kSqThreads) {
@@ -81,20 +85,20 @@ __global__ __launch_bounds__(kSqThreads) void seq_smooth_bwd_kernel(const float*
       const double gam = bad ? at[i] : C[i] / G;
       if (bad) B[i] = 1.0;
       if (gam > bv) { bv = gam; bi = i; }
-      if (smoothed) smoothed[(ft * HW + i) * K + k] = (float)gam;
+      if (smoothed && wr) smoothed[(fo * HW + i) * K + k] = (float)gam;
     }
     sq_block_argmax(bv, bi, rd, ri, tid);      // its barriers also order B against the staging below
-    if (tid == 0) {
+    if (tid == 0 && wr) {
       bi = min(max(bi, 0), HW - 1);
       const int r = bi / WW;
-      coords[(ft * 2 + 0) * K + k] = r;
-      coords[(ft * 2 + 1) * K + k] = bi - r * WW;
-      if (conf) conf[ft * K + k] = (float)bv;
-      if (mass) mass[ft * K + k] = G;
-      if (cut) cut[ft * K + k] = bad ? 1 : 0;
+      coords[(fo * 2 + 0) * K + k] = r;
+      coords[(fo * 2 + 1) * K + k] = bi - r * WW;
+      if (conf) conf[fo * K + k] = (float)bv;
+      if (mass) mass[fo * K + k] = G;
+      if (cut) cut[fo * K + k] = bad ? 1 : 0;
     }
     double tm = 0.0, tj = 0.0, ts = 0.0;
-    if (t >= 1) {
+    if (t > t_end) {
       if (reset[ft * K + k] != 0) {      // frame t never saw frame t-1 (thread-uniform)
         for (int i = tid; i < HW; i += kSqThreads) B[i] = 1.0;
       } else {
@@ -143,12 +147,55 @@ __global__ __launch_bounds__(kSqThreads) void seq_smooth_bwd_kernel(const float*
         ts = (om * M2) / Z;
       }
     }
-    if (trans && tid == 0) {
-      trans[(ft * K + k) * 3 + 0] = tm;
-      trans[(ft * K + k) * 3 + 1] = tj;
-      trans[(ft * K + k) * 3 + 2] = ts;
+    if (trans && wr && tid == 0) {
+      trans[(fo * K + k) * 3 + 0] = tm;
+      trans[(fo * K + k) * 3 + 1] = tj;
+      trans[(fo * K + k) * 3 + 2] = ts;
     }
   }
+}
+
+__global__ __launch_bounds__(kSqThreads) void seq_smooth_bwd_kernel(const float* __restrict__ hm, int T, int HH, int WW, int K, const double* __restrict__ taps,
+                                                                    int R, double om, double u, const double* __restrict__ belief,
+                                                                    const double* __restrict__ norm, const int32_t* __restrict__ reset,
+                                                                    float* __restrict__ smoothed, int32_t* __restrict__ coords, float* __restrict__ conf,
+                                                                    double* __restrict__ mass, int32_t* __restrict__ cut, double* __restrict__ trans, int vec) {
+  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // B [HW], C [HW], C2 [HW]
+  const int s = blockIdx.x / K, k = blockIdx.x - s * K;
+  const size_t f0 = (size_t)s * T;
+  sq_smooth_back(sq_planes, hm, HH, WW, K, taps, R, om, u, belief + (size_t)blockIdx.x * T * HH * WW, norm, reset, f0, f0, k, T - 1, 0, T - 1, smoothed, coords,
+                 conf, mass, cut, trans, vec);
+}
+
+// The fixed-lag smoother.  Forward: the filter's scan over the new frames P .. W-1 of the window, from the belief of frame P-1 that an
+// earlier call left in `belief`.  The scan indexes one sequence's frames from 0, so it is given sequence 0 of pointers that start at the group's frame
+// P; its state plane is read at (joint k) * HW of state_in, hence the k * HW taken off the address of frame P-1.  coords: scratch [S][W-P][2][K].
+__global__ __launch_bounds__(kSqThreads) void seq_smooth_lag_fwd_kernel(const float* __restrict__ hm, int W, int P, int HH, int WW, int K,
+                                                                        const double* __restrict__ taps, int R, double om, double u, int32_t* __restrict__ coords,
+                                                                        double* __restrict__ norm, int32_t* __restrict__ reset, double* belief, int vec) {
+  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // A [HW], C [HW]
+  const int s = blockIdx.x / K, k = blockIdx.x - s * K;
+  const size_t HW = (size_t)HH * WW;
+  const size_t f0 = (size_t)s * W + P;
+  double* bg = belief + ((size_t)blockIdx.x * W + P) * HW;
+  const double* prev = P > 0 ? bg - HW - (size_t)k * HW : nullptr;
+  sq_filter_scan(sq_planes, hm + f0 * HW * K, W - P, HH, WW, K, taps, R, om, u, prev, nullptr, coords + (size_t)s * (W - P) * 2 * K, norm + f0 * K,
+                 reset + f0 * K, nullptr, vec, 0, 0, k, SqPlain(), bg);
+}
+
+// Backward: one group per (s, k, e), e fastest (the groups of one (s, k) read the same frames).  Frame e's outputs given frames 0 .. min(e + L, W - 1).
+__global__ __launch_bounds__(kSqThreads) void seq_smooth_lag_bwd_kernel(const float* __restrict__ hm, int W, int E, int L, int HH, int WW, int K,
+                                                                        const double* __restrict__ taps, int R, double om, double u,
+                                                                        const double* __restrict__ belief, const double* __restrict__ norm,
+                                                                        const int32_t* __restrict__ reset, float* __restrict__ smoothed,
+                                                                        int32_t* __restrict__ coords, float* __restrict__ conf, double* __restrict__ mass,
+                                                                        int32_t* __restrict__ cut, int vec) {
+  extern __shared__ __attribute__((aligned(16))) double sq_planes[];      // B [HW], C [HW], C2 [HW]
+  const int g = blockIdx.x / E, e = blockIdx.x - g * E;
+  const int s = g / K, k = g - s * K;
+  const int top = L < W - 1 - e ? e + L : W - 1;
+  sq_smooth_back(sq_planes, hm, HH, WW, K, taps, R, om, u, belief + (size_t)g * W * HH * WW, norm, reset, (size_t)s * W, (size_t)s * E, k, top, e, e, smoothed,
+                 coords, conf, mass, cut, nullptr, vec);
 }
 
 }  // namespace
@@ -164,6 +211,26 @@ hipError_t seq_smooth(const float* hm, int S, int T, int HH, int WW, int K, cons
   hipLaunchKernelGGL(seq_smooth_fwd_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8, st, hm, T, HH, WW, K, taps, R, om, u, coords, norm, reset, belief, vec);
   hipLaunchKernelGGL(seq_smooth_bwd_kernel, dim3(S * K), dim3(kSqThreads), 3 * HW * 8, st, hm, T, HH, WW, K, taps, R, om, u, belief, norm, reset, smoothed,
                      coords, conf, mass, cut, trans, vec);
+  return hipGetLastError();
+}
+
+hipError_t seq_smooth_lag(const float* hm, int S, int W, int P, int E, int L, int HH, int WW, int K, const double* taps, int R, double om, double u,
+                          int32_t* scan_coords, double* belief, double* norm, int32_t* reset, float* smoothed, int32_t* coords, float* conf, double* mass,
+                          int32_t* cut, hipStream_t st) {
+  if (!sq_sizes_ok(S, W, HH, WW, K, R) || (int64_t)HH * WW > kSeqSmoothMaxHW || P < 0 || P > W || E < 0 || E > W || L < 1 || !belief || !norm || !reset ||
+      (E > 0 && !coords) || (P < W && !scan_coords) || (int64_t)S * K * W >= ((int64_t)1 << 31))
+    return hipErrorInvalidValue;
+  const int HW = HH * WW;
+  const int vec = sq_vec(hm, HW, K) ? 1 : 0;
+  static LdsAttr fwd_attr, bwd_attr;
+  if (hipError_t e = fwd_attr.ensure(reinterpret_cast<const void*>(seq_smooth_lag_fwd_kernel), kSqLdsMax); e != hipSuccess) return e;
+  if (hipError_t e = bwd_attr.ensure(reinterpret_cast<const void*>(seq_smooth_lag_bwd_kernel), kSmLdsMax); e != hipSuccess) return e;
+  if (P < W)
+    hipLaunchKernelGGL(seq_smooth_lag_fwd_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8, st, hm, W, P, HH, WW, K, taps, R, om, u, scan_coords, norm, reset,
+                       belief, vec);
+  if (E > 0)      // a zero-size grid is an error
+    hipLaunchKernelGGL(seq_smooth_lag_bwd_kernel, dim3(S * K * E), dim3(kSqThreads), 3 * HW * 8, st, hm, W, E, L, HH, WW, K, taps, R, om, u, belief, norm, reset,
+                       smoothed, coords, conf, mass, cut, vec);
   return hipGetLastError();
 }
 
@@ -194,6 +261,31 @@ int jcm_seq_smooth(jcm_handle h, const float* hm, int S, int T, int HH, int WW, 
     if (!reset) reset_w = arena_alloc<int32_t>(h, (size_t)S * T * K);
   }, [&](const double* dtaps) {
     return seq_smooth(hm, S, T, HH, WW, K, dtaps, R, om, u, belief, smoothed, coords, conf, norm_w, reset_w, mass, cut, trans, h->stream);
+  });
+}
+
+int jcm_seq_smooth_lag(jcm_handle h, const float* hm, int S, int W, int P, int HH, int WW, int K, const double* taps, int R, double rho, int L, int flush,
+                       double* belief, double* norm, int32_t* reset, float* smoothed, int32_t* coords, float* conf, double* mass, int32_t* cut) {
+  const std::string w("seq_smooth_lag");
+  JCM_TRY(check(h, false));
+  // the argument rules of jcm_seq_smooth on the window (W < 1 is its T < 1), then this entry point's own
+  JCM_TRY(seq_check_joints(w, hm, S, W, HH, WW, K, taps, R, rho, kSeqSmoothMaxHW, "three float64 planes"));
+  if (P < 0 || P > W) return fail(JCM_ERR_ARG, w + ": P = " + std::to_string(P) + " pending frames in a window of " + std::to_string(W) + "; 0 <= P <= W");
+  if (L < 1) return fail(JCM_ERR_ARG, w + ": L = " + std::to_string(L) + "; L >= 1 (lag 0 is the filter: jcm_seq_filter, Engine.seq_filter)");
+  if (flush != 0 && flush != 1) return fail(JCM_ERR_ARG, w + ": flush = " + std::to_string(flush) + "; 0 or 1");
+  const int E = flush ? W : (W > L ? W - L : 0);
+  if (!belief || !norm || !reset) return fail(JCM_ERR_ARG, w + ": null pointer (belief, norm and reset are the caller's window and are required)");
+  if (E > 0 && !coords) return fail(JCM_ERR_ARG, w + ": null pointer (coords is required when a frame is emitted; smoothed, conf, mass and cut may be NULL)");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  const size_t n_scan = (size_t)S * (W - P) * 2 * K;      // the scan's own arg-max of the new frames, scratch
+  JCM_TRY(workspace_or_refuse(h, w, (double)n_scan * 4.0 + 8192.0, "scan coordinates", S, W));
+  const double om = 1.0 - rho, u = rho / (double)(HH * WW);
+  int32_t* scan_coords = nullptr;
+  return seq_launch(h, w, taps, K * (2 * R + 1), [&] {
+    if (P < W) scan_coords = arena_alloc<int32_t>(h, n_scan);
+  }, [&](const double* dtaps) {
+    return seq_smooth_lag(hm, S, W, P, E, L, HH, WW, K, dtaps, R, om, u, scan_coords, belief, norm, reset, smoothed, coords, conf, mass, cut, h->stream);
   });
 }
 

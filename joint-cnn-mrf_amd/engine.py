@@ -439,6 +439,53 @@ class Engine:
                                             self._p(out['reset']), self._p(out['mass']), self._p(out['cut']), self._p(out['trans'])), 'jcm_seq_smooth')
         return {k: v[0] for k, v in out.items()} if single else out
 
+    def seq_smooth_lag(self, hm, sigma, rho, lag, radius=None, state=None, flush=False, want_smoothed=False):
+        """The fixed-lag smoother (include/jcm.h: jcm_seq_smooth_lag): frame s of a live clip as P(x_s | frames 0 .. s+lag),
+        lag >= 1 frames late -- what seq_smooth writes for frame s given frames 0 .. s+lag, bit for bit, for any split of the clip into calls.
+        hm [T,HH,WW,K] or [S,T,HH,WW,K]: the NEW frames only (T may be 0 with a state, to flush a clip); sigma, rho and radius as for seq_filter;
+        state: the 'state' of the call that ended just before frame 0, or None at a clip's start; flush=True ends the clip: every pending frame
+        is emitted with the future it has.  Returns the E emitted frames' {'coords' int32 [S,E,2,K], 'conf' fp32 [S,E,K], 'norm' float64
+        [S,E,K], 'reset' int32 [S,E,K], 'mass' float64 [S,E,K], 'cut' int32 [S,E,K], 'smoothed' fp32 [S,E,HH,WW,K] with want_smoothed}, without
+        the S axis for a 4-d hm, 'lag' int32 [E], the lag each emitted frame actually got (below `lag` only at a flushed clip's end), and
+        'state': a dict of device tensors -- the pending frames' maps, float64 beliefs, norm and reset -- with the shape, lag and taps the next
+        call checks; None after a flush.  E may be 0.  The window is assembled and cut with device copies; nothing is read back."""
+        hm5, single, taps, R = self._seq_args(hm, sigma, radius)
+        S, T, HH, WW, K = hm5.shape
+        L, flush = int(lag), bool(flush)
+        if L < 1:
+            raise ValueError('lag must be >= 1, got %r (lag 0 is the causal filter: seq_filter)' % (lag,))
+        sig = {'shape': (S, HH, WW, K), 'lag': L, 'taps': (R, float(rho), taps.tobytes())}
+        P = 0
+        if state is not None:
+            if not isinstance(state, dict) or any(state.get(k) != v for k, v in sig.items()):
+                raise ValueError("state is not the 'state' of a seq_smooth_lag call with these maps' shape %s, this lag and these taps" % (sig['shape'],))
+            P = int(state['hm'].shape[1])
+        W = P + T
+        if W < 1:
+            raise ValueError('seq_smooth_lag needs a frame: hm has none and there is no pending frame')
+        E = W if flush else max(0, W - L)
+        self._on_stream(hm5, *([state[k] for k in ('hm', 'belief', 'norm', 'reset')] if state is not None else []))
+        with torch.cuda.stream(self._stream):
+            win = {'hm': self._new(S, W, HH, WW, K), 'belief': self._new(S * K, W, HH * WW, dtype=torch.float64),
+                   'norm': self._new(S, W, K, dtype=torch.float64), 'reset': self._new(S, W, K, dtype=torch.int32)}
+            win['hm'][:, P:] = hm5
+            for k in (win if state is not None else ()):
+                win[k][:, :P] = state[k]
+            out = {'coords': self._new(S, E, 2, K, dtype=torch.int32), 'conf': self._new(S, E, K), 'mass': self._new(S, E, K, dtype=torch.float64),
+                   'cut': self._new(S, E, K, dtype=torch.int32)}
+            if want_smoothed:
+                out['smoothed'] = self._new(S, E, HH, WW, K)
+            _lib.check(self._lib.jcm_seq_smooth_lag(self._h, self._p(win['hm']), S, W, P, HH, WW, K, taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R,
+                                                    float(rho), L, int(flush), self._p(win['belief']), self._p(win['norm']), self._p(win['reset']),
+                                                    self._p(out.get('smoothed')), self._p(out['coords']), self._p(out['conf']), self._p(out['mass']),
+                                                    self._p(out['cut'])), 'jcm_seq_smooth_lag')
+            out['norm'], out['reset'] = win['norm'][:, :E].contiguous(), win['reset'][:, :E].contiguous()
+            if single:
+                out = {k: v[0] for k, v in out.items()}
+            out['lag'] = torch.clamp(torch.arange(W - 1, W - 1 - E, -1, dtype=torch.int32, device=self.device), max=L)
+            out['state'] = None if flush else dict(sig, **{k: v[:, E:].contiguous() for k, v in win.items()})
+        return out
+
     def seq_fit(self, hm, sigma=None, rho=None, iters=10, radius=16, fit_rho=True):
         """motion.seq_fit on this engine: sigma per joint and rho re-estimated on the clip's own maps (EM, one seq_smooth per iteration)."""
         return motion.seq_fit(self, hm, motion.SEQ_SIGMA if sigma is None else sigma, motion.SEQ_RHO if rho is None else rho, iters=iters, radius=radius,

@@ -119,10 +119,11 @@ def build_parser():
                         'joints with --use_sm (a zoomed person\'s from the second pass), the part detector\'s otherwise.  The JSON line gains render_ms.')
     parser.add_argument('--render_heat', default=None, choices=['pd', 'sm'], help='with --render: tint the images with the heat maps of the part detector (pd) or '
                         'of the spatial model (sm, needs --use_sm) under the skeleton, every joint in the colour the reference\'s overlays give it.')
-    parser.add_argument('--sequence', default=None, choices=['filter', 'viterbi', 'marginal'], help='with --predict: the expanded paths, in their sorted order, are the frames '
+    parser.add_argument('--sequence', default=None, choices=['filter', 'viterbi', 'marginal', 'lag'], help='with --predict: the expanded paths, in their sorted order, are the frames '
                         'of ONE clip (all of one size); every image of the document gains "track", one position per joint that is consistent over the clip '
                         '(predict.predict_sequence, DESIGN.md 4.19): filter = the causal forward filter, viterbi = the most probable track, marginal = the arg-max of every frame\'s '
-                        'smoothed posterior given all frames, with its confidence (DESIGN.md 4.23; not with --seq_people).  With --render the tracked '
+                        'smoothed posterior given all frames, with its confidence (DESIGN.md 4.23; not with --seq_people), lag = that posterior given the next --seq_lag L frames only, '
+                        'what an online caller can have L frames late (DESIGN.md 4.25; not with --seq_people or --seq_zoom).  With --render the tracked '
                         'skeleton is drawn.  What tracking buys has been measured on rendered clips only (DESIGN.md 4.23).')
     parser.add_argument('--seq_sigma', type=float, nargs='+', default=None, metavar='CELLS', help='with --sequence: the standard deviation of a joint\'s motion per '
                         'frame in heat-map cells, one value or one per joint (default 1.5, an untuned placeholder), for filter, viterbi and marginal alike; --seq_fit starts from it.')
@@ -132,6 +133,8 @@ def build_parser():
                         'annotations -- ITERS (1..100) iterations of EM on the smoothed posteriors (predict.seq_fit, DESIGN.md 4.23), starting from --seq_sigma / '
                         '--seq_rho or their defaults -- then run the chosen mode with the fitted sigma per joint and rho; the JSON line gains seq_fit.  Not with '
                         '--seq_people.')
+    parser.add_argument('--seq_lag', type=int, default=None, metavar='L', help='with --sequence lag: the frames of future every position is given, L >= 1 (there is no '
+                        'default: none has been tuned); the JSON line gains seq_lag.')
     parser.add_argument('--seq_people', type=int, default=None, metavar='M', help='with --sequence, --predict and --use_sm: a clip with up to M (1..4) people in it '
                         '(predict.predict_sequence_people, DESIGN.md 4.21): M consistent torso tracks are pulled out of the frames\' torso maps, the spatial model '
                         'runs once per frame and track, and every person\'s joints are tracked; every image of the document gains "tracks" ("track" is track 0) '
@@ -366,6 +369,10 @@ SEQ_ZOOM_NEEDS_USE_SM = '--seq_zoom needs --use_sm: the windows are placed on th
 SEQ_ZOOM_NO_MARGINAL = '--seq_zoom cannot be combined with --sequence marginal: the smoother has no form for windows that move from frame to frame'
 SEQ_ZOOM_NO_FIT = '--seq_zoom cannot be combined with --seq_fit: the fit runs on the smoother, which has no form for windows that move from frame to frame'
 SEQ_ZOOM_NO_PEOPLE = '--seq_zoom cannot be combined with --seq_people: a zoom pass per track is out of scope'
+SEQ_LAG_NEEDS_SEQUENCE_LAG = '--seq_lag sets the lag of --sequence lag: give --sequence lag as well'
+SEQ_LAG_NEEDS_SEQ_LAG = '--sequence lag needs its lag: give --seq_lag L as well (there is no default: none has been tuned)'
+SEQ_LAG_NO_PEOPLE = '--sequence lag cannot be combined with --seq_people: the torso tracks have the filter and Viterbi only'
+SEQ_LAG_NO_ZOOM = '--sequence lag cannot be combined with --seq_zoom: the smoother has no form for windows that move from frame to frame'
 SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
@@ -388,7 +395,7 @@ def predict_main(args):
     the images are the frames of one clip (predict.predict_sequence): the document gains "track" per file, the pictures show the tracked skeleton; with --seq_people M
     (predict.predict_sequence_people) also "tracks", one skeleton per person, and the line gains seq_people, seq_torso_ms and seq_people_sm_ms; with --seq_zoom
     (predict.predict_sequence_zoom) "zoom" and "track_zoom", the pictures show the skeleton tracked through the windows where the clip was zoomed, and the line
-    gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms."""
+    gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms; with --sequence lag --seq_lag L the line gains seq_lag."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -405,6 +412,8 @@ def predict_main(args):
                        peaks=args.peaks, decode=args.decode_pose, timing=timing)
             if args.seq_fit is not None:
                 seq.update(fit_iters=args.seq_fit)
+            if args.seq_lag is not None:
+                seq.update(lag=args.seq_lag)
             if args.seq_zoom:
                 results = predict.predict_sequence_zoom(eng, images, **seq)
             elif args.seq_people is not None:
@@ -427,6 +436,8 @@ def predict_main(args):
             'use_sm': bool(args.use_sm), 'debug': bool(args.debug)}
     if args.sequence:
         line.update(sequence=args.sequence)
+    if args.seq_lag is not None:
+        line.update(seq_lag=args.seq_lag)
     if args.seq_fit is not None:
         fit = results[0]['seq_fit']
         line.update(seq_fit={'sigma': fit['sigma'].tolist(), 'rho': fit['rho'], 'loglik': fit['loglik'].tolist(), 'clamped': fit['clamped'].tolist()})
@@ -744,13 +755,21 @@ SEQ_ZOOM_RULES = (
     (lambda a: a.seq_zoom and a.seq_fit is not None, SEQ_ZOOM_NO_FIT),
     (lambda a: a.seq_zoom and a.seq_people is not None, SEQ_ZOOM_NO_PEOPLE),
 )
+# The rules of --sequence lag and --seq_lag, walked behind SEQ_ZOOM_RULES (a table of their own for the same reason).
+SEQ_LAG_RULES = (
+    (lambda a: a.seq_lag is not None and a.sequence != 'lag', SEQ_LAG_NEEDS_SEQUENCE_LAG),
+    (lambda a: a.sequence == 'lag' and a.seq_lag is None, SEQ_LAG_NEEDS_SEQ_LAG),
+    (lambda a: a.seq_lag is not None and a.seq_lag < 1, lambda a: '--seq_lag %d: L >= 1 (lag 0 is --sequence filter)' % a.seq_lag),
+    (lambda a: a.sequence == 'lag' and a.seq_people is not None, SEQ_LAG_NO_PEOPLE),
+    (lambda a: a.sequence == 'lag' and a.seq_zoom, SEQ_LAG_NO_ZOOM),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

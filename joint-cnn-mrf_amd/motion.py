@@ -11,10 +11,12 @@ SEQ_RHO = 0.05
 SEQ_TORSO_SIGMA = 1.5                     # a torso's motion per frame in cells (predict_sequence_people): an untuned placeholder
 SEQ_RADIUS_MAX = 16                       # include/jcm.h: R of jcm_seq_filter / jcm_seq_viterbi
 SEQ_SIGMA_MAX = 64.0                      # what seq_fit clamps a joint's sigma to when its moment reaches that of flat taps (at R = 16 such taps are flat within 3 %)
-SEQ_MODES = ('filter', 'viterbi', 'marginal')
+SEQ_MODES = ('filter', 'viterbi', 'marginal', 'lag')
 SEQ_EXCLUDE = 4                           # the exclusion half-width of Engine.seq_tracks, cells: an untuned placeholder
-# Per mode, what the scans of the engine return per frame: the key of the cells, then those of a 'track' beside the points -- (cells, value, flag) but for 'marginal'.
-SEQ_KEYS = {'filter': ('coords', 'norm', 'reset'), 'viterbi': ('path', 'maxes', 'breaks'), 'marginal': ('coords', 'conf', 'norm', 'reset', 'cut')}
+# Per mode, what the scans of the engine return per frame: the key of the cells, then those of a 'track' beside the points -- (cells, value, flag) but for 'marginal'
+# and 'lag' (the fixed-lag smoother, DESIGN.md 4.25: the marginal's keys and the lag the frame got).
+SEQ_KEYS = {'filter': ('coords', 'norm', 'reset'), 'viterbi': ('path', 'maxes', 'breaks'), 'marginal': ('coords', 'conf', 'norm', 'reset', 'cut'),
+            'lag': ('coords', 'conf', 'norm', 'reset', 'cut', 'lag')}
 
 
 def _seq_sigma(sigma, K=None):

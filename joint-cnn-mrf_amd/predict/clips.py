@@ -14,7 +14,10 @@ without annotations, and predict_sequence(fit_iters=) runs any mode with the fit
 
 Zoomed clips: predict_sequence_zoom runs the zoom pass on every frame of a clip in windows that follow the person and share
 one cell lattice (zoom_window_track), so that two frames' maps differ by a whole number of cells, and tracks the joints through them with
-Engine.seq_filter / seq_viterbi(shift=), the scans with a per-frame shift of the belief plane."""
+Engine.seq_filter / seq_viterbi(shift=), the scans with a per-frame shift of the belief plane.
+
+The fixed-lag smoother: predict_sequence(mode='lag', lag=L) takes every frame's position from P(x_t | frames 0 .. t+L) of
+Engine.seq_smooth_lag, and LagTracker is its online form: a frame's dict becomes final L frames after it was pushed."""
 import numpy as np
 import torch
 
@@ -64,22 +67,27 @@ def _finish(results, keep_maps):
     return results
 
 
-def _seq_call(engine, mode, hm, sigma, rho, radius, **kw):
+def _seq_call(engine, mode, hm, sigma, rho, radius, lag=None, **kw):
+    if mode == 'lag':      # one flushed call over the clip: no state comes back
+        seq = engine.seq_smooth_lag(hm, sigma, rho, lag, radius=radius, flush=True)
+        return {k: seq[k] for k in SEQ_KEYS[mode]}
     if mode == 'marginal':
         return engine.seq_smooth(hm, sigma, rho, radius=radius, want_smoothed=False)
     return (engine.seq_filter if mode == 'filter' else engine.seq_viterbi)(hm, sigma, rho, radius=radius, **kw)
 
 
 def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
-                     keep_maps=False, fit_iters=0, **kw):
+                     keep_maps=False, fit_iters=0, lag=None, **kw):
     """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
     geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
     [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal), Engine.seq_viterbi (mode 'viterbi', the most probable
-    track) or Engine.seq_smooth (mode 'marginal', the arg-max of every frame's smoothed posterior P(x_t | all frames), DESIGN.md 4.23);
+    track), Engine.seq_smooth (mode 'marginal', the arg-max of every frame's smoothed posterior P(x_t | all frames)) or
+    Engine.seq_smooth_lag (mode 'lag' with lag = L >= 1, the marginal given frames 0 .. t+L only: what LagTracker reports online, DESIGN.md 4.25);
     evaluation.fit_to_source maps the cells back.  Returns predict_images' dicts, every key with the value it has there, plus
       'track': {'mode', 'points' float64 [K,2] (row, col) in the frame's own pixels, 'inside' bool [K], 'norm' or 'maxes' float64 [K], 'reset' or
                 'breaks' int [K]}  (the library's Z / M and its flags, include/jcm.h); mode 'marginal': 'conf' float32 [K] (the posterior at the
-                point), 'norm', 'reset' and 'cut' int [K].
+                point), 'norm', 'reset' and 'cut' int [K]; mode 'lag': those and 'lag', the lag the frame got (below L at the clip's end).
+    lag is required with mode 'lag' and refused with any other.
     fit_iters = ITERS > 0 first re-estimates sigma (per joint) and rho on the clip's own maps (seq_fit below, starting from sigma and rho) and runs
     the mode with the fitted values; frame 0's dict then carries 'seq_fit', seq_fit's return value for the clip.
     'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
@@ -87,7 +95,11 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
     One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
     frame, are out of scope."""
     if mode not in SEQ_MODES:
-        raise ValueError("mode must be 'filter', 'viterbi' or 'marginal', got %r" % (mode,))
+        raise ValueError("mode must be 'filter', 'viterbi', 'marginal' or 'lag', got %r" % (mode,))
+    if (mode == 'lag') != (lag is not None):
+        raise ValueError("lag=%r: mode 'lag' needs lag = L >= 1, and lag belongs to mode 'lag' alone (mode is %r)" % (lag, mode))
+    if lag is not None and int(lag) < 1:
+        raise ValueError('lag must be >= 1, got %r (lag 0 is the causal filter: mode=\'filter\')' % (lag,))
     if not 0 <= int(fit_iters) <= 100:
         raise ValueError('fit_iters must be 0 (off) or the EM iterations 1..100, got %r' % (fit_iters,))
     if people != 1:
@@ -100,7 +112,7 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
         fit = seq_fit(engine, hm, sigma, rho, iters=int(fit_iters)) if int(fit_iters) else None
         if fit is not None:
             sigma, rho = fit['sigma'], fit['rho']
-        seq = _seq_call(engine, mode, hm, sigma, rho, radius)
+        seq = _seq_call(engine, mode, hm, sigma, rho, radius, lag=lag)
         geom = _geom(results)
         for r, track in zip(results, _track_entries(seq, mode, lambda pts: fit_to_source(pts, geom))):
             r['track'] = track
@@ -266,6 +278,53 @@ class SequenceTracker(_Clip):
             geom = _geom(results)
             for r, track in zip(results, _track_entries(seq, 'filter', lambda pts: fit_to_source(pts, geom))):
                 r['track'] = track
+
+
+class LagTracker(_Clip):
+    """The online form of predict_sequence(mode='lag', lag=L): push(frames) takes the next frames of the clip, runs pass 1 on
+    them and returns the dicts that became FINAL with this push -- those of the frames now `lag` frames old, possibly an empty list --, each
+    with a 'track' of mode 'lag'; flush() returns the rest, with the future they have, and starts a new clip.  The pending frames' maps, float64
+    beliefs, norm and reset live in the state of Engine.seq_smooth_lag, so a held-back dict carries no 'maps'.  Any split of a clip into pushes
+    gives the values of one predict_sequence over all of it.  Every push must bring frames of the first push's size.  reset() drops the
+    pending frames and starts a new clip."""
+
+    def __init__(self, engine, lag, sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, **kw):
+        if int(lag) < 1:
+            raise ValueError('lag must be >= 1, got %r (lag 0 is the causal filter: SequenceTracker)' % (lag,))
+        self.engine, self.lag, self.sigma, self.rho, self.radius, self.use_sm = engine, int(lag), sigma, rho, radius, use_sm
+        self.pass1 = dict(kw, use_sm=use_sm, batch_size=batch_size)
+        self.reset()
+
+    def reset(self):
+        super().reset()
+        self.pending = []
+
+    def _emit(self, hm, flush):
+        """The new frames' maps (None: none) through the engine -> the pending dicts that became final, with their 'track'."""
+        with torch.cuda.stream(self.engine._stream):
+            if hm is None:
+                hm = self.state['hm'][0, :0]      # no new frame: [0,HH,WW,K]
+            seq = self.engine.seq_smooth_lag(hm, self.sigma, self.rho, self.lag, radius=self.radius, state=self.state, flush=flush)
+            self.state = seq['state']
+            E = int(seq['lag'].shape[0])
+            done, self.pending = self.pending[:E], self.pending[E:]
+            if E:
+                geom = _geom(done)
+                for r, track in zip(done, _track_entries(seq, 'lag', lambda pts: fit_to_source(pts, geom))):
+                    r['track'] = track
+        return done
+
+    def push(self, frames):
+        results = _first_pass(self.engine, frames, clip=self, **self.pass1)
+        with torch.cuda.stream(self.engine._stream):
+            hm = _stacked(results, 'sm' if self.use_sm else 'pd')
+        self.pending += _finish(results, False)      # the state holds the maps it needs
+        return self._emit(hm, False)
+
+    def flush(self):
+        done = self._emit(None, True) if self.pending else []
+        self.reset()
+        return done
 
 
 # ------------------------------------------------------------------ clips with several people (DESIGN.md 4.21)
