@@ -442,6 +442,32 @@ int jcm_seq_smooth_lag(jcm_handle h, const float* hm, int S, int W, int P, int H
                        int flush, double* belief, double* norm, int32_t* reset, float* smoothed, int32_t* coords, float* conf, double* mass,
                        int32_t* cut);
 
+/* -- camera pans: the global translation between consecutive fitted frames ---------------------
+ * What turns a clip's own frames into the `shift` of jcm_seq_filter_moving / jcm_seq_viterbi_moving.  Every step is integer arithmetic; the
+ * sums are order-free, so the result is a function of the bytes alone.
+ * x: device uint8 [T,H,W,3], the letterboxed frames;  (y0, x0, ch, cw): the content rectangle of the fit -- no byte outside it is read, the
+ * bars have no say;  D in 1..16: the coarse search radius;  prev: device uint8 [H,W,3], the frame before frame 0, or NULL.
+ * Per pair (t-1, t), prev acting as frame -1:
+ *   L(y,x) = R + 2 G + B                                               in 0 .. 1020
+ *   C(Y,X) = the sum of L over the 4 x 4 block at (y0 + 4Y, x0 + 4X)    Y < Hc = ch / 4, X < Wc = cw / 4 (floor; trailing pixels dropped)
+ *   coarse: for every (dy, dx) in [-D, D]^2   S_c = sum of |C_t(Y,X) - C_{t-1}(Y+dy, X+dx)| over Y in [D, Hc-D), X in [D, Wc-D) -- the same
+ *           number of terms for every candidate;  the winner (dy_c, dx_c) minimises the tuple (S_c, dy^2 + dx^2, dy, dx)
+ *   fine:   candidates (dy, dx) = (4 dy_c + ey, 4 dx_c + ex), ey, ex in [-3, 3];  S_f = sum of |L_t(y,x) - L_{t-1}(y+dy, x+dx)| over
+ *           y in [y0+M, y0+ch-M), x in [x0+M, x0+cw-M), M = 4D + 3;  the winner minimises (S_f, dy^2 + dx^2, dy, dx) of the full displacement
+ * Outputs (device): disp int32 [T,2] = the fine winner (dy, dx) in fitted-frame pixels;  sad int64 [T,2] = (S_f at the winner, S_f at (0,0)),
+ *   both over the same window, the second computed whether or not (0,0) is a fine candidate.  With prev == NULL, disp[0] = sad[0] = (0,0).
+ * Sign: the content at pixel (y,x) of frame t is at (y+dy, x+dx) of frame t-1 -- the convention of `shift` above.  Ties: two identical frames,
+ *   uniform ones included, give (0,0).
+ * JCM_ERR_ARG -- nothing is launched, disp and sad are untouched -- for a null x, disp or sad;  T < 1 or T > 65534;  D outside 1..16;  a
+ *   rectangle that is not inside the frame;  ch or cw below 8D + 7 (the smallest at which both windows hold a pixel);  H or W above 4096
+ *   (seven rows of the fine window are staged in LDS);  H * W * 1020 >= 2^32: a candidate's sum is at most H * W * 1020, and the partial
+ *   sums of threads and work groups are held in 32 bits (the slots they are added into in 64).
+ * Uses the workspace arena (2 bytes per frame and pixel of the rectangle, and a sixteenth of that again); JCM_ERR_STATE with the bytes in the
+ * message when they do not fit.  Enqueues on the handle's stream and does not synchronise (growing the workspace does); the fine search
+ * reads the coarse winner from device memory.  Timed as "frame_shift". */
+int jcm_frame_shift(jcm_handle h, const uint8_t* x, int T, int H, int W, int y0, int x0, int ch, int cw, int D, const uint8_t* prev,
+                    int32_t* disp, int64_t* sad);
+
 /* -- several tracks through single-channel maps: one torso track per person of a clip ----------
  * hm: device fp32 [S,T,HH,WW], one non-negative channel (the torso probabilities of the frames); M in 1..4 tracks; taps HOST [2R+1], R and rho as for
  * jcm_seq_* with one tap row; D in 0..64, the exclusion half-width in cells.

@@ -72,6 +72,8 @@ SIGNATURES = {
     'jcm_seq_tracks_filter': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, _c_float_p, _c_i32_p,
                                              ctypes.c_void_p, _c_i32_p, ctypes.c_void_p, _c_float_p]),
+    'jcm_frame_shift': (ctypes.c_int, [_handle, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_void_p, _c_i32_p, ctypes.c_void_p]),
     'jcm_torso_infer': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32_p, _c_float_p, _c_i32_p, _c_float_p]),
     'jcm_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    _c_float_p, _c_float_p, _c_i32_p, _c_i32_p]),

@@ -454,6 +454,16 @@ hipError_t seq_tracks_filter(const float* hm, int S, int T, int HH, int WW, int 
 // workspace of ONE pass, reused by the next: bp int16 [S][T][HH*WW], amax int32 [S][T]
 hipError_t seq_tracks_viterbi(const float* hm, int S, int T, int HH, int WW, int M, const double* taps, int R, double om, double u, int D, int16_t* bp,
                               int32_t* amax, int32_t* path, double* maxes, int32_t* breaks, float* value, hipStream_t st);
+// ---- frame_shift.hip : the global translation between consecutive fitted frames ----
+// x [T,H,W,3] bytes, prev [H,W,3] or null; the content rectangle (y0, x0, ch, cw) inside the frame, ch, cw >= 8 D + 7, 1 <= D <= kFrameShiftMaxD,
+// H, W <= kFrameShiftMaxSide, H * W * 1020 < 2^32, T <= kFrameShiftMaxT.  Workspace: L uint16 [T+1][ch][cw], C uint16 [T+1][ch/4][cw/4],
+// slots uint64 [frame_shift_slots(pairs, D)] (pairs = T, or T - 1 without prev), center int32 [T][2].  disp int32 [T,2], sad int64 [T,2] as in jcm.h.
+constexpr int kFrameShiftMaxD = 16;
+constexpr int kFrameShiftMaxSide = 4096;
+constexpr int kFrameShiftMaxT = 65534;
+size_t frame_shift_slots(int pairs, int D);
+hipError_t frame_shift(const uint8_t* x, int T, int H, int W, int y0, int x0, int ch, int cw, int D, const uint8_t* prev, uint16_t* L, uint16_t* C,
+                       unsigned long long* slots, int32_t* center, int32_t* disp, int64_t* sad, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

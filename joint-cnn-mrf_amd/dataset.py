@@ -273,3 +273,53 @@ def render_clip(engine, rng, pose_a, pose_b, T, other_xy=None, H=480, W=720, cut
     records, prims, xy = synth.people_clip(rng, pose_a, pose_b, T, other_xy, H, W, cuts, **ranges)
     x = engine.synth_people(records, prims, H, W, dtype=torch.uint8 if image_dtype == 'uint8' else torch.float32)
     return x, records, prims, xy
+
+
+def pan_origins(pan, margin, T, H=480, W=720):
+    """Where the crops of a panned clip lie on its canvas of (H + 2 my) x (W + 2 mx), margin = (my, mx): pan int [T,2] = (dy, dx) per frame ->
+    int64 [T,2], (oy_t, ox_t) = (my, mx) + pan_0 + .. + pan_t.  A crop that would leave the canvas raises ValueError.  Host integers only."""
+    pan = np.asarray(pan)
+    my, mx = int(margin[0]), int(margin[1])
+    if pan.dtype.kind not in 'iu' or pan.shape != (int(T), 2) or my < 0 or mx < 0:
+        raise ValueError('pan must be an integer array [T,2] = (%d, 2) and margin two non-negative ints, got %s %s and %r' % (int(T), pan.dtype, pan.shape, margin))
+    o = np.array([my, mx], np.int64)[None, :] + np.cumsum(pan.astype(np.int64), axis=0)
+    bad = (o < 0).any(axis=1) | (o[:, 0] > 2 * my) | (o[:, 1] > 2 * mx)
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError('crop %d at (%d, %d) leaves the canvas: origins lie in [0, %d] x [0, %d]' % (t, o[t, 0], o[t, 1], 2 * my, 2 * mx))
+    return o
+
+
+def crop_pan(canvas, xy, origins, H=480, W=720):
+    """canvas [T,Hc,Wc,3] (a tensor or an array), xy float [T,2,9] = (x, y) on the canvas, origins int [T,2] -> (the crops canvas_t[oy_t : oy_t + H,
+    ox_t : ox_t + W] stacked as [T,H,W,3], xy moved into each crop, inside bool [T,9]: is the joint within the crop?).  Plain slicing."""
+    o = np.asarray(origins, np.int64)
+    crops = [canvas[t, int(o[t, 0]):int(o[t, 0]) + H, int(o[t, 1]):int(o[t, 1]) + W] for t in range(o.shape[0])]
+    x = torch.stack(crops).contiguous() if isinstance(canvas, torch.Tensor) else np.ascontiguousarray(np.stack(crops))
+    moved = np.asarray(xy, np.float64) - o[:, ::-1, None].astype(np.float64)
+    inside = (moved[:, 0] >= 0) & (moved[:, 0] <= W - 1) & (moved[:, 1] >= 0) & (moved[:, 1] <= H - 1)
+    return x, moved, inside
+
+
+def render_clip_pan(engine, rng, pose_a, pose_b, T, pan, margin, other_xy=None, cuts=(), image_dtype='uint8', **ranges):
+    """A clip of rendered people seen by a camera that pans: synth.people_clip draws the T frames of one scene on a canvas of
+    (480 + 2 my) x (720 + 2 mx), margin = (my, mx), in ONE Engine.synth_people call, and frame t is the crop canvas_t[oy_t : oy_t + 480, ox_t :
+    ox_t + 720] with (oy_t, ox_t) = (my, mx) + pan_0 + .. + pan_t, pan int [T,2] (pan_origins; a crop that would leave the canvas raises
+    ValueError).  Returns (x device [T,480,720,3]; xy float64 [T,2,9], the annotated person's joints (x, y) in every crop; inside bool [T,9], is
+    the joint within its crop; disp int64 [T,2], the true displacement of frame t against frame t-1 with the sign of Engine.frame_shift -- the
+    content at (y, x) of frame t is at (y, x) + disp_t of frame t-1 --, which is pan_t, and (0, 0) for frame 0, which has no frame before it).
+    Cropping is tensor slicing: the renderer and its records are unchanged.  A property of these clips: the sensor noise belongs to the canvas
+    (its seed is the record's and its pattern is a function of the canvas pixel), so it pans with the crop like the scene does -- a real
+    sensor's noise stays with the sensor.  The estimate therefore sees frames that match exactly at the true displacement."""
+    from . import synth
+    if image_dtype not in ('float32', 'uint8'):
+        raise ValueError("image_dtype must be 'float32' or 'uint8', got %r" % (image_dtype,))
+    origins = pan_origins(pan, margin, T)
+    Hc, Wc = 480 + 2 * int(margin[0]), 720 + 2 * int(margin[1])
+    records, prims, xy = synth.people_clip(rng, pose_a, pose_b, T, other_xy, Hc, Wc, cuts, **ranges)
+    canvas = engine.synth_people(records, prims, Hc, Wc, dtype=torch.uint8 if image_dtype == 'uint8' else torch.float32)
+    with torch.cuda.stream(engine._stream):
+        x, moved, inside = crop_pan(canvas, xy, origins)
+    disp = np.asarray(pan, np.int64).copy()
+    disp[0] = 0
+    return x, moved, inside, disp

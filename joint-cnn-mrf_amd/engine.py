@@ -419,6 +419,29 @@ class Engine:
             _lib.check(self._lib.jcm_seq_viterbi(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), *tail), 'jcm_seq_viterbi')
         return {k: v[0] for k, v in out.items()} if single else out
 
+    def frame_shift(self, x, rect, search=motion.SEQ_CAMERA_SEARCH, prev=None):
+        """The camera's whole-pixel translation between consecutive fitted frames (include/jcm.h: jcm_frame_shift): x uint8
+        [T,H,W,3] on the device, the letterboxed frames of a clip; rect = (y0, x0, ch, cw), the content rectangle of their fit (the first four of
+        fit_images' geom) -- nothing outside it is read; search: the coarse radius D in 1..16, reaching +-(4 D + 3) pixels a frame; prev: uint8
+        [H,W,3], the frame before frame 0, or None at a clip's start.  Returns {'disp' int32 [T,2] = (dy, dx): the content at pixel (y, x) of
+        frame t is at (y + dy, x + dx) of frame t-1, 'sad' int64 [T,2] = (the sum of absolute luma differences at disp, the same at (0, 0))},
+        device tensors; row 0 is zero without prev.  Integer arithmetic throughout; nothing is read back.  motion.camera_shifts turns 'disp' into
+        the shift of seq_filter / seq_viterbi.  Sizes, the rectangle and search are checked by the library."""
+        self._chk(x, 4, 'x', torch.uint8)
+        T, H, W, C = x.shape
+        if C != 3:
+            raise ValueError('x must be [T,H,W,3], got shape %s' % (tuple(x.shape),))
+        if prev is not None:
+            self._chk(prev, 3, 'prev', torch.uint8)
+            if tuple(prev.shape) != (H, W, 3):
+                raise ValueError('prev must be [H,W,3] = %s, got %s' % ((H, W, 3), tuple(prev.shape)))
+        y0, x0, ch, cw = (int(v) for v in rect)
+        out = {'disp': self._new(T, 2, dtype=torch.int32), 'sad': self._new(T, 2, dtype=torch.int64)}
+        self._on_stream(x, *([prev] if prev is not None else []), *out.values())
+        _lib.check(self._lib.jcm_frame_shift(self._h, self._p(x), T, H, W, y0, x0, ch, cw, int(search), self._p(prev), self._p(out['disp']),
+                                             self._p(out['sad'])), 'jcm_frame_shift')
+        return out
+
     def seq_smooth(self, hm, sigma, rho, radius=None, want_smoothed=True):
         """The smoothed marginals P(x_t | all frames) of a clip's heat maps and the expected transition statistics of the backward pass (DESIGN.md
         4.23, include/jcm.h: jcm_seq_smooth); hm, sigma, rho and radius as for seq_filter, offline (no state).  Returns {'smoothed' fp32 like hm

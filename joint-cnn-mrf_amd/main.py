@@ -143,6 +143,12 @@ def build_parser():
                         'the tower was trained on (predict.predict_sequence_zoom, DESIGN.md 4.24): one zoom window per frame around the torso track, all on one '
                         'cell lattice, and the temporal scan with a whole-cell shift per frame; the document gains "zoom" and "track_zoom" per file, the JSON '
                         'line seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms.  Not with --sequence marginal, --seq_fit or --seq_people.')
+    parser.add_argument('--seq_camera', action='store_true', help='with --sequence filter or viterbi: a camera that pans (DESIGN.md 4.26): the translation between '
+                        'consecutive fitted frames is estimated on the device (Engine.frame_shift), turned into whole-cell shifts (motion.camera_shifts) and given to '
+                        'the temporal scan, so that its motion kernel follows the camera; the document gains "camera" per file (disp, shift, sad).  Global '
+                        'translation only, no cut detection.  Not with --seq_zoom, --seq_people, --seq_fit or --sequence marginal / lag.')
+    parser.add_argument('--seq_camera_search', type=int, default=None, metavar='D', help='with --seq_camera: the coarse search radius in 1..16, reaching 4 D + 3 fitted '
+                        'pixels a frame (default 8, an untuned placeholder).')
     parser.add_argument('--seq_torso_sigma', type=float, default=None, metavar='CELLS', help='with --seq_people: the standard deviation of a torso\'s motion per '
                         'frame in heat-map cells (default 1.5, an untuned placeholder).')
     parser.add_argument('--seq_exclude', type=int, default=None, metavar='CELLS', help='with --seq_people: the half-width in 0..64 heat-map cells of the square '
@@ -373,6 +379,12 @@ SEQ_LAG_NEEDS_SEQUENCE_LAG = '--seq_lag sets the lag of --sequence lag: give --s
 SEQ_LAG_NEEDS_SEQ_LAG = '--sequence lag needs its lag: give --seq_lag L as well (there is no default: none has been tuned)'
 SEQ_LAG_NO_PEOPLE = '--sequence lag cannot be combined with --seq_people: the torso tracks have the filter and Viterbi only'
 SEQ_LAG_NO_ZOOM = '--sequence lag cannot be combined with --seq_zoom: the smoother has no form for windows that move from frame to frame'
+SEQ_CAMERA_NEEDS_SEQUENCE = '--seq_camera follows the camera through the clip --sequence names: give --sequence filter or --sequence viterbi as well'
+SEQ_CAMERA_NO_SMOOTHER = '--seq_camera cannot be combined with --sequence marginal or lag: the smoother has no form for a lattice that moves from frame to frame'
+SEQ_CAMERA_NO_FIT = '--seq_camera cannot be combined with --seq_fit: the fit runs on the smoother, which has no form for a lattice that moves from frame to frame'
+SEQ_CAMERA_NO_ZOOM = '--seq_camera cannot be combined with --seq_zoom: the zoom windows already move with the person'
+SEQ_CAMERA_NO_PEOPLE = '--seq_camera cannot be combined with --seq_people: the torso passes have no form for a lattice that moves from frame to frame'
+SEQ_CAMERA_SEARCH_NEEDS_SEQ_CAMERA = '--seq_camera_search sets the search radius of --seq_camera: give --seq_camera as well'
 SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
@@ -395,7 +407,8 @@ def predict_main(args):
     the images are the frames of one clip (predict.predict_sequence): the document gains "track" per file, the pictures show the tracked skeleton; with --seq_people M
     (predict.predict_sequence_people) also "tracks", one skeleton per person, and the line gains seq_people, seq_torso_ms and seq_people_sm_ms; with --seq_zoom
     (predict.predict_sequence_zoom) "zoom" and "track_zoom", the pictures show the skeleton tracked through the windows where the clip was zoomed, and the line
-    gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms; with --sequence lag --seq_lag L the line gains seq_lag."""
+    gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms; with --sequence lag --seq_lag L the line gains seq_lag; with --seq_camera the document gains
+    "camera" per file and the line seq_camera, the search radius."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -420,6 +433,8 @@ def predict_main(args):
                 results = predict.predict_sequence_people(eng, images, args.seq_people, exclude=predict.SEQ_EXCLUDE if args.seq_exclude is None else args.seq_exclude,
                                                           torso_sigma=predict.SEQ_TORSO_SIGMA if args.seq_torso_sigma is None else args.seq_torso_sigma, **seq)
             else:
+                if args.seq_camera:
+                    seq.update(camera=True, camera_search=predict.SEQ_CAMERA_SEARCH if args.seq_camera_search is None else args.seq_camera_search)
                 results = predict.predict_sequence(eng, images, use_sm=args.use_sm, **seq)
         else:
             results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
@@ -441,6 +456,8 @@ def predict_main(args):
     if args.seq_fit is not None:
         fit = results[0]['seq_fit']
         line.update(seq_fit={'sigma': fit['sigma'].tolist(), 'rho': fit['rho'], 'loglik': fit['loglik'].tolist(), 'clamped': fit['clamped'].tolist()})
+    if args.seq_camera:
+        line.update(seq_camera=predict.SEQ_CAMERA_SEARCH if args.seq_camera_search is None else args.seq_camera_search)
     if args.seq_people is not None:
         line.update(seq_people=args.seq_people, seq_torso_ms=timing['seq_torso_ms'], seq_people_sm_ms=timing['seq_people_sm_ms'])
     if args.seq_zoom:
@@ -763,13 +780,23 @@ SEQ_LAG_RULES = (
     (lambda a: a.sequence == 'lag' and a.seq_people is not None, SEQ_LAG_NO_PEOPLE),
     (lambda a: a.sequence == 'lag' and a.seq_zoom, SEQ_LAG_NO_ZOOM),
 )
+# The rules of --seq_camera, walked behind SEQ_LAG_RULES (a table of their own for the same reason).
+SEQ_CAMERA_RULES = (
+    (lambda a: a.seq_camera_search is not None and not a.seq_camera, SEQ_CAMERA_SEARCH_NEEDS_SEQ_CAMERA),
+    (lambda a: a.seq_camera and not a.sequence, SEQ_CAMERA_NEEDS_SEQUENCE),
+    (lambda a: a.seq_camera and a.sequence in ('marginal', 'lag'), SEQ_CAMERA_NO_SMOOTHER),
+    (lambda a: a.seq_camera and a.seq_fit is not None, SEQ_CAMERA_NO_FIT),
+    (lambda a: a.seq_camera and a.seq_zoom, SEQ_CAMERA_NO_ZOOM),
+    (lambda a: a.seq_camera and a.seq_people is not None, SEQ_CAMERA_NO_PEOPLE),
+    (lambda a: a.seq_camera_search is not None and not 1 <= a.seq_camera_search <= 16, lambda a: '--seq_camera_search %d: 1 <= D <= 16' % a.seq_camera_search),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

@@ -19,6 +19,33 @@ SEQ_KEYS = {'filter': ('coords', 'norm', 'reset'), 'viterbi': ('path', 'maxes', 
             'lag': ('coords', 'conf', 'norm', 'reset', 'cut', 'lag')}
 
 
+SEQ_CAMERA_SEARCH = 8                     # the coarse search radius of Engine.frame_shift: reaches +-(4 * 8 + 3) = 35 fitted pixels a frame; an untuned placeholder
+
+
+def camera_shifts(disp, carry=(0, 0), stride=8):
+    """The camera's displacement per frame in fitted-frame pixels (Engine.frame_shift's 'disp', int [T,2] = (dy, dx)) -> (shift int32 [T,2], carry):
+    the whole-cell lattice shift per frame that Engine.seq_filter / seq_viterbi(shift=) take.  Exact integer arithmetic:
+      c_t = carry + disp_0 + .. + disp_t        the cumulative displacement in pixels
+      o_t = (c_t + stride // 2) // stride       floor division: the cumulative displacement in cells, rounded to the nearest
+      shift_t = o_t - o_{t-1}                   with o_{-1} = (carry + stride // 2) // stride
+    so the shifts of any run of frames add up to the rounded cumulative displacement and rounding never accumulates; what is left, at most half
+    a cell, is motion the taps (sigma) have to cover.  carry, a pair of ints, holds the part of the cumulative displacement of all frames so far
+    that has not become whole cells: c_{T-1} - stride * o_{T-1}, in [-(stride // 2), stride - stride // 2).  Pass the returned carry to the call
+    for the next frames of the clip ((0, 0) at a clip's start): any split of a clip gives the shifts of one call."""
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError('stride must be >= 1, got %r' % (stride,))
+    d = np.asarray(disp)
+    if d.dtype.kind not in 'iu' or d.ndim != 2 or d.shape[1] != 2:
+        raise ValueError('disp must be an integer array [T,2], got %s %s' % (d.dtype, d.shape))
+    c0 = np.array([int(carry[0]), int(carry[1])], np.int64)
+    c = c0[None, :] + np.cumsum(d.astype(np.int64), axis=0)
+    half = stride // 2
+    o = np.concatenate([((c0 + half) // stride)[None, :], (c + half) // stride])
+    last = c[-1] - stride * o[-1] if len(c) else c0 - stride * o[0]
+    return (o[1:] - o[:-1]).astype(np.int32), (int(last[0]), int(last[1]))
+
+
 def _seq_sigma(sigma, K=None):
     sg = np.asarray(sigma, np.float64).reshape(-1)
     if sg.size == 0 or not np.all(np.isfinite(sg)) or np.any(sg <= 0):

@@ -17,12 +17,16 @@ one cell lattice (zoom_window_track), so that two frames' maps differ by a whole
 Engine.seq_filter / seq_viterbi(shift=), the scans with a per-frame shift of the belief plane.
 
 The fixed-lag smoother: predict_sequence(mode='lag', lag=L) takes every frame's position from P(x_t | frames 0 .. t+L) of
-Engine.seq_smooth_lag, and LagTracker is its online form: a frame's dict becomes final L frames after it was pushed."""
+Engine.seq_smooth_lag, and LagTracker is its online form: a frame's dict becomes final L frames after it was pushed.
+
+Camera pans: predict_sequence(camera=True) and SequenceTracker(camera=True) estimate the camera's translation between consecutive
+fitted frames on the device (Engine.frame_shift), turn it into whole-cell lattice shifts (motion.camera_shifts) and run the filter or Viterbi with
+shift=, so that the motion kernel is centred on where the camera's motion takes a joint, not on where it was."""
 import numpy as np
 import torch
 
 from ..evaluation import fit_to_source, window_to_source
-from ..motion import SEQ_EXCLUDE, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, seq_fit
+from ..motion import SEQ_CAMERA_SEARCH, SEQ_EXCLUDE, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, camera_shifts, seq_fit
 from .images import FIT_SIDE_MAX, FRAME, STRIDE, ZOOM_TORSO_JOINTS, ZOOM_TORSO_PIXELS, DeviceTimer, _coords_to_points, _upload, predict_images, second_pass, zoom_entry
 
 
@@ -76,8 +80,30 @@ def _seq_call(engine, mode, hm, sigma, rho, radius, lag=None, **kw):
     return (engine.seq_filter if mode == 'filter' else engine.seq_viterbi)(hm, sigma, rho, radius=radius, **kw)
 
 
+SEQ_CAMERA_MODES = ('filter', 'viterbi')      # the scans that have a moving form
+
+
+def _camera(engine, results, search, prev=None, carry=(0, 0)):
+    """The camera's motion over the frames of `results` (dicts of pass 1 with the fitted frames kept): one Engine.frame_shift call on the stacked
+    frames with the clip's content rectangle, prev the last fitted frame of the push before (None at a clip's start), then motion.camera_shifts
+    from `carry`.  Every dict gains 'camera'.  Returns (shift int32 [T,2], the last fitted frame, the new carry)."""
+    x = _stacked(results, 'frame')
+    cam = engine.frame_shift(x, _geom(results)[0, :4], search=search, prev=prev)
+    disp, sad = cam['disp'].cpu().numpy(), cam['sad'].cpu().numpy()
+    shift, carry = camera_shifts(disp, carry, STRIDE)
+    for t, r in enumerate(results):
+        r['camera'] = {'disp': (int(disp[t, 0]), int(disp[t, 1])), 'shift': (int(shift[t, 0]), int(shift[t, 1])), 'sad': (int(sad[t, 0]), int(sad[t, 1]))}
+    return shift, x[-1].clone(), carry
+
+
+def _check_camera_search(camera, camera_search):
+    if not 1 <= int(camera_search) <= 16:
+        raise ValueError('camera_search must be in 1..16, got %r' % (camera_search,))
+    return bool(camera)
+
+
 def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
-                     keep_maps=False, fit_iters=0, lag=None, **kw):
+                     keep_maps=False, fit_iters=0, lag=None, camera=False, camera_search=SEQ_CAMERA_SEARCH, **kw):
     """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
     geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
     [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal), Engine.seq_viterbi (mode 'viterbi', the most probable
@@ -90,6 +116,12 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
     lag is required with mode 'lag' and refused with any other.
     fit_iters = ITERS > 0 first re-estimates sigma (per joint) and rho on the clip's own maps (seq_fit below, starting from sigma and rho) and runs
     the mode with the fitted values; frame 0's dict then carries 'seq_fit', seq_fit's return value for the clip.
+    camera=True (modes 'filter' and 'viterbi' only -- 'marginal', 'lag' and fit_iters raise ValueError, the smoother has no moving
+    form): the fitted frames are kept and stacked, ONE Engine.frame_shift call with the clip's content rectangle and search radius camera_search
+    (1..16) estimates the camera's translation per frame, motion.camera_shifts turns it into whole-cell shifts and the scan runs with shift=.
+    Every frame's dict gains 'camera': {'disp': (dy, dx) in fitted-frame pixels, 'shift': (sy, sx) in cells, 'sad': (best, zero), the sums of
+    absolute luma differences at disp and at no displacement -- there is no cut detection, a caller judges by the two}.  Global translation
+    only; camera_search = 8 is an untuned placeholder like sigma and rho.
     'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
     the defaults SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what the track buys with trained weights has not been measured.
     One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
@@ -106,13 +138,20 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
         raise ValueError('predict_sequence tracks one person: people=%r would need an association of people across frames, which is out of scope' % (people,))
     if zoom:
         raise ValueError('predict_sequence has no zoom pass: its windows would move from frame to frame, which is out of scope')
+    if _check_camera_search(camera, camera_search):
+        if mode not in SEQ_CAMERA_MODES:
+            raise ValueError("camera=True: mode must be 'filter' or 'viterbi', got %r (the smoother has no moving form)" % (mode,))
+        if int(fit_iters) != 0:
+            raise ValueError('camera=True has no fit: fit_iters=%r needs the smoother, which has no moving form' % (fit_iters,))
+        kw = dict(kw, keep_frames=True)
     results = _first_pass(engine, frames, use_sm=use_sm, batch_size=batch_size, **kw)
     with torch.cuda.stream(engine._stream):
         hm = _stacked(results, 'sm' if use_sm else 'pd')
         fit = seq_fit(engine, hm, sigma, rho, iters=int(fit_iters)) if int(fit_iters) else None
         if fit is not None:
             sigma, rho = fit['sigma'], fit['rho']
-        seq = _seq_call(engine, mode, hm, sigma, rho, radius, lag=lag)
+        moving = {'shift': _camera(engine, results, int(camera_search))[0]} if camera else {}
+        seq = _seq_call(engine, mode, hm, sigma, rho, radius, lag=lag, **moving)
         geom = _geom(results)
         for r, track in zip(results, _track_entries(seq, mode, lambda pts: fit_to_source(pts, geom))):
             r['track'] = track
@@ -185,7 +224,7 @@ def zoom_window_track(points, inside, torso, geom, frame=FRAME):
 
 
 def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, radius=None, batch_size=16, people=1,
-                          keep_maps=False, fit_iters=0, pad=0, timing=None, **kw):
+                          keep_maps=False, fit_iters=0, pad=0, timing=None, camera=False, **kw):
     """The frames of ONE clip with one person in it, tracked a second time at the scale the tower was trained on; frames as
     for predict_sequence.
       1. predict_sequence(frames, mode, ..., torso_prob=True): the first pass and its 'track'; the torso track comes from the frames'
@@ -203,7 +242,9 @@ def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso
     is no 'track_zoom'.  timing also receives 'zoom_fit_ms', 'zoom_forward_ms' and 'seq_zoom_pitch'.
     The modes are 'filter' and 'viterbi': mode='marginal' and fit_iters raise ValueError (jcm_seq_smooth has no moving form), people != 1 too.
     One pitch per clip is a stated limit; torso_sigma, sigma and rho are untuned placeholders, and what this buys with trained weights has not
-    been measured."""
+    been measured.  camera=True raises ValueError: the windows already move with the person, and a camera estimate under them is out of scope."""
+    if camera:
+        raise ValueError('predict_sequence_zoom has no camera estimate: its windows follow the person already (camera=True belongs to predict_sequence)')
     if mode not in SEQ_ZOOM_MODES:
         raise ValueError("mode must be 'filter' or 'viterbi', got %r (the smoother has no moving form: mode 'marginal' is not offered with zoomed clips)" % (mode,))
     if int(fit_iters) != 0:
@@ -264,16 +305,27 @@ class _Clip:
 class SequenceTracker(_Clip):
     """The online form of predict_sequence(mode='filter'): push(frames) takes the next frames of the clip, a few or one at a time, and returns
     their dicts with 'track'; the filter's float64 belief is carried from call to call, so any split of a clip gives the values of one
-    predict_sequence over all of it.  Every push must bring frames of the first push's size.  reset() starts a new clip."""
+    predict_sequence over all of it.  Every push must bring frames of the first push's size.  reset() starts a new clip.
+    camera=True is the online form of predict_sequence(mode='filter', camera=True): the last fitted frame and the carry of
+    motion.camera_shifts travel from push to push beside the belief (the shift of a push's first frame applies to the transition from the carried
+    belief), so any split gives the values of the one call; reset() clears both."""
 
-    def __init__(self, engine, sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, **kw):
+    def __init__(self, engine, sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, camera=False, camera_search=SEQ_CAMERA_SEARCH, **kw):
         self.engine, self.sigma, self.rho, self.radius, self.use_sm = engine, sigma, rho, radius, use_sm
-        self.pass1 = dict(kw, use_sm=use_sm, batch_size=batch_size)
+        self.camera, self.camera_search = _check_camera_search(camera, camera_search), int(camera_search)
+        self.pass1 = dict(kw, use_sm=use_sm, batch_size=batch_size, **({'keep_frames': True} if self.camera else {}))
         self.reset()
+
+    def reset(self):
+        super().reset()
+        self.last_frame, self.carry = None, (0, 0)
 
     def _track(self, results):
         with torch.cuda.stream(self.engine._stream):
-            seq = self.engine.seq_filter(_stacked(results, 'sm' if self.use_sm else 'pd'), self.sigma, self.rho, radius=self.radius, state=self.state)
+            moving = {}
+            if self.camera:
+                moving['shift'], self.last_frame, self.carry = _camera(self.engine, results, self.camera_search, self.last_frame, self.carry)
+            seq = self.engine.seq_filter(_stacked(results, 'sm' if self.use_sm else 'pd'), self.sigma, self.rho, radius=self.radius, state=self.state, **moving)
             self.state = seq['state']
             geom = _geom(results)
             for r, track in zip(results, _track_entries(seq, 'filter', lambda pts: fit_to_source(pts, geom))):
@@ -378,7 +430,7 @@ def _check_people(people, zoom):
 
 
 def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, exclude=SEQ_EXCLUDE,
-                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, **kw):
+                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, camera=False, **kw):
     """The frames of ONE clip with up to people = M (1..4) persons in it; frames as for predict_sequence.  On the device:
       1. predict_images(frames, use_sm=True, people=1, keep_maps=True, torso_prob=True, **kw): per frame the part-detector maps and the torso map
          spatial_softmax(E);
@@ -397,7 +449,9 @@ def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SI
     timing also receives 'seq_torso_ms' and 'seq_people_sm_ms', the device times of steps 2 and 3.  'maps' is kept only with keep_maps.
     exclude (SEQ_EXCLUDE = 4 cells), torso_sigma (SEQ_TORSO_SIGMA = 1.5), sigma, rho and people_threshold are untuned placeholders -- no
     consecutive-frame data and no trained weights are at hand -- and what this buys with trained weights has not been measured.  zoom=True
-    raises ValueError."""
+    and camera=True raise ValueError (the torso passes have no moving form)."""
+    if camera:
+        raise ValueError('predict_sequence_people has no camera estimate: the torso passes have no moving form (camera=True belongs to predict_sequence)')
     if mode not in ('filter', 'viterbi'):
         raise ValueError("mode must be 'filter' or 'viterbi', got %r (the torso tracks have the filter and Viterbi only)" % (mode,))
     _check_people(people, zoom)
