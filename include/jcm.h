@@ -214,6 +214,15 @@ int jcm_conv_layer_pre(jcm_handle h, const char* scope, int stride, const float*
  * and multiplies by RN(1/3) -- the last fp32 bit of a value that is then rounded to bf16 (two merged values in a million round the other way). */
 int jcm_conv_layer_merged(jcm_handle h, const char* scope, const float* x1, const float* x2, int H2, int W2, const float* x3, int H3, int W3,
                           int B, int H, int W, float* out);
+/* ((x1 + up(x2)) + up(x3)) / 3 alone (main.py:58,67,69-70), by the launcher the tower calls where the merge is not formed inside conv5's forward row
+ * pass: for testing the merge kernels on their own.  Device tensors of one element type, fp32 or (is_bf16 != 0) bf16; NHWC x1, out [B,H,W,C], x2
+ * [B,H2,W2,C], x3 [B,H3,W3,C], or (planar != 0) planar [B][C/8][H][W][8].  The kernel follows from the arguments alone, never from the handle's
+ * precision, and nothing is cast: fp32 -> upsample_merge3_kernel<float>; bf16 with C % 8 == 4 -> upsample_merge3_kernel<__bf16>; bf16 with C % 8 == 0 ->
+ * upsample_merge3_bf16x8_kernel; planar -> upsample_merge3_planar_kernel.  Arithmetic: fp32, lerp along x, then along y, ((x1 + u2) + u3), a correctly
+ * rounded third; a branch that already has H x W is read as it is.  JCM_ERR_ARG before any launch for a null pointer, a size < 1, C % 4 != 0, planar
+ * without is_bf16 or with C % 8 != 0, or a tensor of 2^32 or more of the kernel's units (4 channels; 8 for bf16 with C % 8 == 0 and for planar). */
+int jcm_upsample_merge3(jcm_handle h, const void* x1, const void* x2, int H2, int W2, const void* x3, int H3, int W3, int B, int H, int W, int C,
+                        int is_bf16, int planar, void* out);
 /* max_pool_layer(x, 2, 2) (main.py:172-174): 2x2/2 SAME. [B,H,W,C] -> [B,ceil(H/2),ceil(W/2),C] */
 int jcm_max_pool(jcm_handle h, const float* x, int B, int H, int W, int C, float* out);
 /* tf.image.resize_images(x, [OH,OW]) (main.py:51,58,60,67,89): TF-1.x legacy bilinear. */

@@ -493,6 +493,31 @@ int jcm_max_pool(jcm_handle h, const float* x, int B, int H, int W, int C, float
   return JCM_OK;
 }
 
+// ((x1 + up(x2)) + up(x3)) / 3 by the launcher the tower calls: upsample_merge3, or upsample_merge3_planar on planar tensors.  No casts, no dependence on
+// the handle's precision; everything is checked before the launch.
+int jcm_upsample_merge3(jcm_handle h, const void* x1, const void* x2, int H2, int W2, const void* x3, int H3, int W3, int B, int H, int W, int C, int is_bf16,
+                        int planar, void* out) {
+  JCM_TRY(check(h, false));
+  if (!x1 || !x2 || !x3 || !out || B < 1 || H < 1 || W < 1 || C < 1 || H2 < 1 || W2 < 1 || H3 < 1 || W3 < 1)
+    return fail(JCM_ERR_ARG, "bad upsample_merge3 arguments");
+  if (C % 4) return fail(JCM_ERR_ARG, "upsample_merge3: C must be a multiple of 4, got " + std::to_string(C));
+  if (planar && (!is_bf16 || C % 8)) return fail(JCM_ERR_ARG, "upsample_merge3: planar tensors are bf16 with C % 8 == 0");
+  const int cu = (planar || (is_bf16 && C % 8 == 0)) ? 8 : 4;      // channels per unit of the kernel that runs
+  const auto too_large = [&](int hh, int ww) {      // a product of four ints: each partial product is tested, so nothing wraps
+    uint64_t n = (uint64_t)B * (uint64_t)hh;
+    if (n >> 32) return true;
+    n *= (uint64_t)ww;
+    if (n >> 32) return true;
+    return (n * (uint64_t)(C / cu)) >> 32 != 0;
+  };
+  if (too_large(H, W) || too_large(H2, W2) || too_large(H3, W3)) return fail(JCM_ERR_ARG, "upsample_merge3: 2^32 units or more");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  if (planar) HIP_TRY(upsample_merge3_planar(x1, x2, H2, W2, x3, H3, W3, out, B, H, W, C, h->stream));
+  else HIP_TRY(upsample_merge3(x1, x2, H2, W2, x3, H3, W3, out, is_bf16 != 0, B, H, W, C, h->stream));
+  return JCM_OK;
+}
+
 int jcm_resize_bilinear(jcm_handle h, const float* x, int B, int H, int W, int C, int OH, int OW, float* out) {
   JCM_TRY(check(h, false));
   if (!x || !out || B < 1 || H < 1 || W < 1 || C < 1 || OH < 1 || OW < 1) return fail(JCM_ERR_ARG, "bad resize arguments");

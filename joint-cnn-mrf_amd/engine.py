@@ -171,6 +171,36 @@ class Engine:
                                                    B, H, W, self._p(out)), 'jcm_conv_layer_merged(%s)' % name)
         return out
 
+    def upsample_merge3(self, x1, x2, x3, planar=False):
+        """((x1 + up(x2)) + up(x3)) / 3 (main.py:58,67,69-70) by the merge kernel alone, as the tower launches it where conv5 does not form the merge
+        itself.  float32 or bfloat16 tensors, all three of one dtype (the engine's precision plays no part): NHWC x1 [B,H,W,C], x2 [B,H2,W2,C],
+        x3 [B,H3,W3,C] with C % 4 == 0, or with planar=True bfloat16 [B,C/8,H,W,8].  Returns x1's dtype, shape and layout."""
+        ts = (x1, x2, x3)
+        if not all(isinstance(t, torch.Tensor) for t in ts):
+            raise TypeError('x1, x2, x3 must be torch tensors')
+        if x1.dtype not in (torch.float32, torch.bfloat16) or x2.dtype != x1.dtype or x3.dtype != x1.dtype:
+            raise TypeError('x1, x2, x3 must share one dtype, torch.float32 or torch.bfloat16; got %s, %s, %s' % (x1.dtype, x2.dtype, x3.dtype))
+        if planar and x1.dtype != torch.bfloat16:
+            raise TypeError('planar tensors are torch.bfloat16, got %s' % x1.dtype)
+        for t, nm in zip(ts, ('x1', 'x2', 'x3')):
+            self._chk(t, 5 if planar else 4, nm, x1.dtype)
+        if planar:
+            (B, C8, H, W, e), C = x1.shape, x1.shape[1] * 8
+            same = e == 8 and all(t.shape[0] == B and t.shape[1] == C8 and t.shape[4] == 8 for t in ts)
+            sizes = [(t.shape[2], t.shape[3]) for t in (x2, x3)]
+        else:
+            B, H, W, C = x1.shape
+            same = C % 4 == 0 and all(t.shape[0] == B and t.shape[3] == C for t in ts)
+            sizes = [(t.shape[1], t.shape[2]) for t in (x2, x3)]
+        if not same or min(x1.shape) < 1 or min(min(s) for s in sizes) < 1:
+            raise ValueError('x1, x2, x3 must be non-empty and share batch and channel counts (%s); got %s, %s, %s'
+                             % ('[B,C/8,H,W,8]' if planar else '[B,H,W,C], C % 4 == 0', tuple(x1.shape), tuple(x2.shape), tuple(x3.shape)))
+        out = torch.empty_like(x1)
+        self._on_stream(x1, x2, x3, out)
+        _lib.check(self._lib.jcm_upsample_merge3(self._h, self._p(x1), self._p(x2), sizes[0][0], sizes[0][1], self._p(x3), sizes[1][0], sizes[1][1],
+                                                 B, H, W, C, int(x1.dtype == torch.bfloat16), int(bool(planar)), self._p(out)), 'jcm_upsample_merge3')
+        return out
+
     def max_pool(self, x):
         """main.py:172-174."""
         self._chk(x, 4, 'x')

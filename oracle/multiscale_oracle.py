@@ -98,7 +98,8 @@ def take_window(x, win):
     out = np.zeros((h, w, C), x.dtype)
     ys, xs = max(y0, 0), max(x0, 0)
     ye, xe = min(y0 + h, H), min(x0 + w, W)
-    out[ys - y0:ye - y0, xs - x0:xe - x0] = x[ys:ye, xs:xe]
+    if ye > ys and xe > xs:      # a window that lies wholly outside the image is all padding
+        out[ys - y0:ye - y0, xs - x0:xe - x0] = x[ys:ye, xs:xe]
     return out
 
 
