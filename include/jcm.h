@@ -760,6 +760,31 @@ int jcm_augment_affine_indexed(jcm_handle h, const float* x_all, const int32_t* 
 int jcm_augment_affine_indexed_u8(jcm_handle h, const uint8_t* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
                                   const double* geom, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out);
 
+/* -- the antialiased affine sample: jcm_augment_affine with a triangle filter as wide as the picture is shrunk ------------------
+ * The three entries above with one more HOST float64 array, width [B]: the filter half-width of image b in source pixels, max(1, sqrt(|a e - b d|)) of
+ * its inverse map (augmentation.affine_footprint: the square root is taken on the host, none on the device).  It is read before the call returns and
+ * travels in the kernel arguments beside geom.  Everything else -- the position (xs, ys), the colour-transformed value v of a source pixel and its
+ * contrast mean m_c, `pad`, the maps (the same kernel, not a copy), the _indexed / _u8 forms (float32(k) / float32(255) per tap), the checks and the error
+ * texts (under the _aa names) -- is that of the plain entries.
+ * Image, for w = width[b], float64, one rounded operation per step as written, sums from 0 in ascending order:
+ *   tx_i = 1 - |xs - i| / w   for the integers i of [ceil(xs - w), floor(xs + w)],   ty_j = 1 - |ys - j| / w   for j of [ceil(ys - w), floor(ys + w)];
+ *   a column with tx_i <= 0 and a row with ty_j <= 0 are skipped everywhere below;
+ *   Sx = sum_i tx_i,   Sy = sum_j ty_j;
+ *   u_ji = v(j, i) for 0 <= i < W and 0 <= j < H, else `pad`: a tap outside the source takes part in the sum;
+ *   acc = 0;  for ascending j:  row = 0;  for ascending i: row = row + tx_i * u_ji;   acc = acc + ty_j * row;
+ *   out = float32(acc / (Sx * Sy)).
+ *   A pixel none of whose columns, or none of whose rows, reaches the source (xs + w < 0, xs - w > W - 1, y alike) is written as `pad` without the
+ *   loops: the same float32, since the weighted mean of equal float32 values is that value to 1e-14.  A position that is not finite gives `pad`.
+ *   An image with width[b] == 1.0 exactly is sampled by the plain entry's four-tap arithmetic and has its bits (at w = 1 the triangle IS bilinear, to
+ *   rounding; the plain form keeps scales >= 1 at the plain entry's cost and bits).  At most 9 x 9 taps (w = 4, scale 0.25).
+ * JCM_ERR_ARG, with nothing launched or written, also for: width NULL, a width[b] that is not finite, below 1 or above 4 (its index in the message). */
+int jcm_augment_affine_aa(jcm_handle h, const float* x, const int32_t* cells, const float* colour, const double* geom, const double* width, int B, int H,
+                          int W, int hh, int hw, float pad, float* x_out, float* y_out);
+int jcm_augment_affine_aa_indexed(jcm_handle h, const float* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
+                                  const double* geom, const double* width, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out);
+int jcm_augment_affine_aa_indexed_u8(jcm_handle h, const uint8_t* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
+                                     const double* geom, const double* width, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out);
+
 /* -- TensorBoard summaries (tensorboard.py) -------------------------------------------------
  * jcm_tensor_stats: per segment (offset, count) of a flat device fp32 buffer -- or, with data == NULL, of the handle's stored
  *   trainable parameters in the layout of jcm_train_param_info (read in place; a segment must lie inside one tensor) -- the

@@ -119,6 +119,15 @@ SIGNATURES = {
     'jcm_augment_affine_indexed_u8': (ctypes.c_int, [_handle, ctypes.c_void_p, _c_i32_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
                                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                      ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_float_p, _c_float_p]),
+    'jcm_augment_affine_aa': (ctypes.c_int, [_handle, _c_float_p, _c_i32_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                             _c_float_p, _c_float_p]),
+    'jcm_augment_affine_aa_indexed': (ctypes.c_int, [_handle, _c_float_p, _c_i32_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float),
+                                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_float_p, _c_float_p]),
+    'jcm_augment_affine_aa_indexed_u8': (ctypes.c_int, [_handle, ctypes.c_void_p, _c_i32_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
+                                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_float_p, _c_float_p]),
     'jcm_tensor_stats': (ctypes.c_int, [_handle, _c_float_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_void_p, ctypes.c_void_p]),
     'jcm_hist_bucket_limits': (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int]),

@@ -137,12 +137,52 @@ def check_affine(colour, geom):
     return np.ascontiguousarray(col), np.ascontiguousarray(g)
 
 
+MAX_AFFINE_WIDTH = 4.0                       # the widest filter of the antialiased sample (csrc/augment_affine.hip: 9 x 9 taps, scale 0.25)
+
+
+def affine_footprint(geom):
+    """geom [B, 12] -> float64 [B]: the filter half-width of the antialiased sample in source pixels, max(1, sqrt(|a e - b d|)) of the
+    inverse map -- how many source pixels an output pixel spans along an axis of a similarity map; 1 where the picture is not shrunk.  The square root is
+    taken here, on the host.  The root is rounded to 12 decimals, so that the last-bit rounding of the cosines and sines in geom does not turn scale 1
+    into a width a hair above 1 (which would leave the plain four-tap form) or scale 0.25 into one a hair above 4 (which the kernel refuses)."""
+    g = np.asarray(geom, dtype=np.float64)
+    if g.ndim != 2 or g.shape[1] != 12:
+        raise ValueError('affine geometry must be [B, 12], got shape %s' % (g.shape,))
+    return np.maximum(1.0, np.round(np.sqrt(np.abs(g[:, 0] * g[:, 4] - g[:, 1] * g[:, 3])), 12))
+
+
+def check_width(width, B):
+    """Host-side check of the filter half-widths of the antialiased sample: [B], finite, in [1, 4].  Returns them as a contiguous float64 array; raises
+    ValueError."""
+    w = np.asarray(width, dtype=np.float64)
+    if w.shape != (int(B),):
+        raise ValueError('the filter widths must be [%d], got shape %s' % (B, w.shape))
+    if not ((w >= 1.0) & (w <= MAX_AFFINE_WIDTH)).all():      # (a NaN fails both comparisons)
+        raise ValueError('a filter width must be finite and in [1, %g] (scale 0.25 at the least); got %s' % (MAX_AFFINE_WIDTH, w[~((w >= 1.0) & (w <= MAX_AFFINE_WIDTH))][:4]))
+    return np.ascontiguousarray(w)
+
+
+def affine_joints_inside(cells, geom, H, W):
+    """cells [B, 10, 2] (row, col) heat-map cells, geom [B, 12] -> bool [B]: whether every one of the ten points the cells stand for, (8 col + 3.5,
+    8 row + 3.5), lands inside [0, W] x [0, H] under image b's forward map -- i.e. none of them is clamped when the targets are redrawn (the clamp of
+    jcm_augment_affine, in its float64 order).  A flip permutes the channels, not the set of points, so it does not enter."""
+    c, g = np.asarray(cells), np.asarray(geom, dtype=np.float64)
+    if c.ndim != 3 or c.shape[1:] != (10, 2) or g.shape != (c.shape[0], 12):
+        raise ValueError('affine_joints_inside expects cells [B,10,2] and geom [B,12]; got %s, %s' % (c.shape, g.shape))
+    px, py = 8.0 * c[:, :, 1].astype(np.float64) + 3.5, 8.0 * c[:, :, 0].astype(np.float64) + 3.5
+    qx = (g[:, 6:7] * px + g[:, 7:8] * py) + g[:, 8:9]
+    qy = (g[:, 9:10] * px + g[:, 10:11] * py) + g[:, 11:12]
+    return ((qx >= 0.0) & (qx <= float(W)) & (qy >= 0.0) & (qy <= float(H))).all(axis=1)
+
+
 class AffineDraw:
     """One batch's draw of the affine augmentation: colour [B, 3], geom [B, 12] (affine_geometry) and the pad value -- what Trainer.train_step(augment=)
-    takes besides the [B, 6] array of the reference's augmentation.  draw[lo:hi] is the draw of a tower's slice of the batch."""
+    takes besides the [B, 6] array of the reference's augmentation.  draw[lo:hi] is the draw of a tower's slice of the batch.  width: None (the plain
+    bilinear sample), or the [B] filter half-widths of the antialiased sample (affine_footprint(geom))."""
 
-    def __init__(self, colour, geom, pad=0.0):
+    def __init__(self, colour, geom, pad=0.0, width=None):
         self.colour, self.geom = check_affine(colour, geom)
+        self.width = None if width is None else check_width(width, self.colour.shape[0])
         self.pad = float(pad)
         if not np.isfinite(self.pad):
             raise ValueError('pad must be finite, got %r' % (pad,))
@@ -153,12 +193,26 @@ class AffineDraw:
     def __getitem__(self, s):
         if not isinstance(s, slice):
             raise TypeError('an AffineDraw is sliced by image ranges, got %r' % (s,))
-        return AffineDraw(self.colour[s], self.geom[s], self.pad)
+        return AffineDraw(self.colour[s], self.geom[s], self.pad, None if self.width is None else self.width[s])
 
 
-def draw_affine(rng, B, H, W, pad=0.0, **ranges):
-    """AffineDraw for B images of H x W: draw_affine_params(rng, B, **ranges) through affine_geometry."""
-    return AffineDraw(*affine_geometry(draw_affine_params(rng, B, **ranges), H, W), pad=pad)
+def draw_affine(rng, B, H, W, pad=0.0, antialias=False, **ranges):
+    """AffineDraw for B images of H x W: draw_affine_params(rng, B, **ranges) through affine_geometry.  antialias: with the filter widths of the
+    antialiased sample (the same draw from `rng`; a scale below 0.25 is refused)."""
+    colour, geom = affine_geometry(draw_affine_params(rng, B, **ranges), H, W)
+    return AffineDraw(colour, geom, pad=pad, width=affine_footprint(geom) if antialias else None)
+
+
+def fixed_affine(B, H, W, scale, angle=0.0, shift=(0, 0), flip=False, pad=0.0, antialias=True):
+    """AffineDraw of ONE geometry for all B images of H x W, the colour left as it is (delta 0, factor 1): scale and angle about the centre, shift =
+    (tx, ty) as fractions of the frame width / height (draw_affine_params), the mirrored picture with flip.  What evaluation.eval_curves_affine shows the
+    tower; antialias: with the filter widths of the antialiased sample."""
+    scale = float(scale)
+    if not (0 < scale < np.inf):
+        raise ValueError('scale must be positive and finite, got %r' % (scale,))
+    p = np.tile(np.array([[1.0 if flip else 0.0, 0.0, 1.0, float(angle), scale, float(shift[0]), float(shift[1])]], np.float64), (int(B), 1))
+    colour, geom = affine_geometry(p, H, W)
+    return AffineDraw(colour, geom, pad=pad, width=affine_footprint(geom) if antialias else None)
 
 
 def augment_test(x, y):

@@ -6,7 +6,8 @@
 // Three launches per group of kAffMax images, whose parameters (maps, colour, source index) travel by value in the kernel arguments -- no staging buffer,
 // no copy, nothing for the host to wait for:
 //   aff_mean_kernel   per-image channel sums of the brightened source (partials, fixed order, no atomics: the sums of aug_mean_kernel)
-//   aff_image_kernel  one thread per output pixel, three channels: four source taps, colour per tap, bilinear
+//   aff_image_kernel  one thread per output pixel, three channels: four source taps, colour per tap, bilinear; in the antialiased entries
+//                     (jcm_augment_affine_aa*) a triangle filter of the image's half-width, two tap loops, where that is not exactly 1
 //   aff_maps_kernel   the ten transformed cells once per work group into LDS, then one thread per output element (a test, no scatter)
 #include <cmath>
 #include <string>
@@ -23,6 +24,7 @@ constexpr int kAffMax = 16;             // images per launch: 16 * 112 bytes of 
 constexpr int kAffParts = 128;          // partial sums per image, reduction width and their fold: those of augment.hip, so that the mean is the same number
 constexpr int kAffRed = 192;
 constexpr int kAffThreads = 256;
+constexpr double kAffMaxWidth = 4.0;    // the widest triangle filter of the antialiased entries: scale 0.25, 9 x 9 taps
 static_assert(kHmFlipChannels == 10, "aff_maps_kernel permutes the 10 heat-map channels by kHmFlipPerm (hm_flip.h)");
 static_assert(kAffRed == 3 * (kAffParts / 2) && kAffThreads >= kAffRed, "aff_image_kernel folds two parts per reduction slot");
 
@@ -65,13 +67,8 @@ __global__ __launch_bounds__(kAffRed) void aff_mean_kernel(const PixT* __restric
   if (threadIdx.x < 3) partials[((size_t)b * kAffParts + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x];
 }
 
-template <class PixT>
-__global__ __launch_bounds__(kAffThreads) void aff_image_kernel(const PixT* __restrict__ x, AffArgs A, int H, int W, float pad,
-                                                                const double* __restrict__ partials, float* __restrict__ x_out) {
-  __shared__ double red[kAffRed];
-  __shared__ float s_mean[3];
-  const int b = blockIdx.y;
-  const int HW = H * W;
+// the contrast means of image b from its partial sums, by every thread of the work group: s_mean[c] = float32(sum_c / HW)
+__device__ __forceinline__ void aff_means(const double* __restrict__ partials, int b, int HW, double* red, float* s_mean) {
   const int t = threadIdx.x;
   if (t < kAffRed) {      // channel t % 3, parts t / 3 and t / 3 + 64
     const double* pb = partials + (size_t)b * kAffParts * 3;
@@ -80,10 +77,103 @@ __global__ __launch_bounds__(kAffThreads) void aff_image_kernel(const PixT* __re
   fold3(red);
   if (t < 3) s_mean[t] = (float)(red[t] / (double)HW);
   __syncthreads();
-  const int i = blockIdx.x * kAffThreads + t;
+}
+
+// One image's source as the samplers read it: a pixel after brightness, contrast and clip (float32, the order of DESIGN.md 4.7), `pad` itself outside.
+template <class PixT>
+struct AffSource {
+  const PixT* xb;
+  int H, W;
+  float m[3], delta, factor, pad;
+
+  __device__ __forceinline__ void inside(int j, int i, double* v) const {      // 0 <= j < H, 0 <= i < W
+    const PixT* s = xb + ((size_t)j * W + i) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float u = px_f32(s[k]) + delta;
+      u = (u - m[k]) * factor + m[k];
+      v[k] = (double)fminf(fmaxf(u, 0.f), 1.f);
+    }
+  }
+  __device__ __forceinline__ void tap(double yy, double xx, double* v) const {
+    if (yy >= 0.0 && yy <= (double)(H - 1) && xx >= 0.0 && xx <= (double)(W - 1)) {      // only then are they turned into integers
+      inside((int)yy, (int)xx, v);
+    } else {
+      v[0] = v[1] = v[2] = (double)pad;
+    }
+  }
+  // the four taps around a finite position (xs, ys)
+  __device__ __forceinline__ void bilinear(double xs, double ys, float* dst) const {
+    const double x0 = floor(xs), y0 = floor(ys);
+    const double fx = xs - x0, fy = ys - y0;
+    double v00[3], v01[3], v10[3], v11[3];
+    tap(y0, x0, v00);
+    tap(y0, x0 + 1.0, v01);
+    tap(y0 + 1.0, x0, v10);
+    tap(y0 + 1.0, x0 + 1.0, v11);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double top = (1.0 - fx) * v00[k] + fx * v01[k];
+      const double bot = (1.0 - fx) * v10[k] + fx * v11[k];
+      dst[k] = (float)((1.0 - fy) * top + fy * bot);
+    }
+  }
+  // The triangle filter of half-width w in (1, 4] around a finite position (include/jcm.h, jcm_augment_affine_aa): at most 9 x 9 taps, walked by two
+  // loops -- no array of weights, nothing in scratch.  The weight of a column is formed again in every row: a division more per tap, and no run-time indexed array.
+  __device__ __forceinline__ void triangle(double xs, double ys, double w, float* dst) const {
+    // every tap of a column (row) range that misses the source is `pad`, and the weighted mean of equal values rounds to that value in float32: such a
+    // pixel is `pad` without a loop, and a position far outside never becomes an integer
+    if (!(xs + w >= 0.0 && xs - w <= (double)(W - 1) && ys + w >= 0.0 && ys - w <= (double)(H - 1))) {
+      dst[0] = dst[1] = dst[2] = pad;
+      return;
+    }
+    const int i0 = (int)ceil(xs - w), i1 = (int)floor(xs + w);      // within [-4, W + 3]
+    const int j0 = (int)ceil(ys - w), j1 = (int)floor(ys + w);
+    const double padv = (double)pad;
+    double Sx = 0.0, Sy = 0.0;
+    for (int i = i0; i <= i1; ++i) {
+      const double tx = 1.0 - fabs(xs - (double)i) / w;
+      if (tx > 0.0) Sx += tx;
+    }
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int j = j0; j <= j1; ++j) {
+      const double ty = 1.0 - fabs(ys - (double)j) / w;
+      if (!(ty > 0.0)) continue;
+      Sy += ty;
+      const bool row_in = j >= 0 && j < H;
+      double row[3] = {0.0, 0.0, 0.0};
+      for (int i = i0; i <= i1; ++i) {
+        const double tx = 1.0 - fabs(xs - (double)i) / w;
+        if (!(tx > 0.0)) continue;
+        double v[3] = {padv, padv, padv};
+        if (row_in && i >= 0 && i < W) inside(j, i, v);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) row[k] += tx * v[k];
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[k] += ty * row[k];
+    }
+    const double S = Sx * Sy;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dst[k] = (float)(acc[k] / S);
+  }
+};
+
+// kAA: the antialiased entries -- image b is sampled with the triangle filter of half-width Wd.w[b], or, where that is exactly 1, as the plain entry does
+struct AffWidths {
+  double w[kAffMax];
+};
+
+template <class PixT, bool kAA>
+__global__ __launch_bounds__(kAffThreads) void aff_image_kernel(const PixT* __restrict__ x, AffArgs A, AffWidths Wd, int H, int W, float pad,
+                                                                const double* __restrict__ partials, float* __restrict__ x_out) {
+  __shared__ double red[kAffRed];
+  __shared__ float s_mean[3];
+  const int b = blockIdx.y;
+  const int HW = H * W;
+  aff_means(partials, b, HW, red, s_mean);
+  const int i = blockIdx.x * kAffThreads + (int)threadIdx.x;
   if (i >= HW) return;
-  const float m[3] = {s_mean[0], s_mean[1], s_mean[2]};
-  const float delta = A.im[b].delta, factor = A.im[b].factor;
   const int r = i / W, q = i - r * W;
   const double xs = (A.im[b].inv[0] * (double)q + A.im[b].inv[1] * (double)r) + A.im[b].inv[2];
   const double ys = (A.im[b].inv[3] * (double)q + A.im[b].inv[4] * (double)r) + A.im[b].inv[5];
@@ -92,35 +182,11 @@ __global__ __launch_bounds__(kAffThreads) void aff_image_kernel(const PixT* __re
     dst[0] = dst[1] = dst[2] = pad;
     return;
   }
-  const PixT* xb = x + (size_t)A.im[b].src * HW * 3;
-  const double wm = (double)(W - 1), hm = (double)(H - 1);
-  // a source pixel after brightness, contrast and clip (float32, the order of DESIGN.md 4.7); `pad` itself outside the image
-  auto tap = [&](double yy, double xx, double* v) {
-    if (yy >= 0.0 && yy <= hm && xx >= 0.0 && xx <= wm) {      // only then are they turned into integers
-      const PixT* s = xb + ((size_t)(int)yy * W + (int)xx) * 3;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        float u = px_f32(s[k]) + delta;
-        u = (u - m[k]) * factor + m[k];
-        v[k] = (double)fminf(fmaxf(u, 0.f), 1.f);
-      }
-    } else {
-      v[0] = v[1] = v[2] = (double)pad;
-    }
-  };
-  const double x0 = floor(xs), y0 = floor(ys);
-  const double fx = xs - x0, fy = ys - y0;
-  double v00[3], v01[3], v10[3], v11[3];
-  tap(y0, x0, v00);
-  tap(y0, x0 + 1.0, v01);
-  tap(y0 + 1.0, x0, v10);
-  tap(y0 + 1.0, x0 + 1.0, v11);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double top = (1.0 - fx) * v00[k] + fx * v01[k];
-    const double bot = (1.0 - fx) * v10[k] + fx * v11[k];
-    dst[k] = (float)((1.0 - fy) * top + fy * bot);
-  }
+  const AffSource<PixT> S{x + (size_t)A.im[b].src * HW * 3, H, W, {s_mean[0], s_mean[1], s_mean[2]}, A.im[b].delta, A.im[b].factor, pad};
+  if (kAA && Wd.w[b] != 1.0)
+    S.triangle(xs, ys, Wd.w[b], dst);
+  else
+    S.bilinear(xs, ys, dst);
 }
 
 // y_out[b, r, c, k] = the blob weight of cell (r, c) around the transformed cell of channel k (source channel kHmFlipPerm[k] of a flipped image)
@@ -153,12 +219,13 @@ __global__ __launch_bounds__(kAffThreads) void aff_maps_kernel(const int32_t* __
 }
 
 template <class PixT>
-hipError_t aff_launch(const PixT* x, const int32_t* cells, const int* idx, const float* colour, const double* geom, int B, int H, int W, int hh, int hw,
-                      float pad, double* scratch, float* x_out, float* y_out, hipStream_t st) {
+hipError_t aff_launch(const PixT* x, const int32_t* cells, const int* idx, const float* colour, const double* geom, const double* width, int B, int H, int W,
+                      int hh, int hw, float pad, double* scratch, float* x_out, float* y_out, hipStream_t st) {
   const int HW = H * W, ny = hh * hw * kHmFlipChannels;
   for (int b0 = 0; b0 < B; b0 += kAffMax) {      // image b0 + i of the batch is image i of its launches: every per-image array starts at b0
     const int nb = B - b0 < kAffMax ? B - b0 : kAffMax;
     AffArgs A{};
+    AffWidths Wd{};
     for (int i = 0; i < nb; ++i) {
       AffImage& P = A.im[i];
       const double* g = geom + (size_t)(b0 + i) * 12;
@@ -168,23 +235,27 @@ hipError_t aff_launch(const PixT* x, const int32_t* cells, const int* idx, const
       P.delta = c[1];
       P.factor = c[2];
       P.src = idx ? idx[b0 + i] : b0 + i;
+      Wd.w[i] = width ? width[b0 + i] : 1.0;
     }
     double* part = scratch + (size_t)b0 * kAffParts * 3;
     hipLaunchKernelGGL(aff_mean_kernel<PixT>, dim3(kAffParts, nb), dim3(kAffRed), 0, st, x, A, HW, part);
-    hipLaunchKernelGGL(aff_image_kernel<PixT>, dim3((HW + kAffThreads - 1) / kAffThreads, nb), dim3(kAffThreads), 0, st, x, A, H, W, pad, part,
-                       x_out + (size_t)b0 * HW * 3);
+    const dim3 grid((HW + kAffThreads - 1) / kAffThreads, nb);
+    if (width)
+      hipLaunchKernelGGL((aff_image_kernel<PixT, true>), grid, dim3(kAffThreads), 0, st, x, A, Wd, H, W, pad, part, x_out + (size_t)b0 * HW * 3);
+    else
+      hipLaunchKernelGGL((aff_image_kernel<PixT, false>), grid, dim3(kAffThreads), 0, st, x, A, Wd, H, W, pad, part, x_out + (size_t)b0 * HW * 3);
     hipLaunchKernelGGL(aff_maps_kernel, dim3((ny + kAffThreads - 1) / kAffThreads, nb), dim3(kAffThreads), 0, st, cells, A, hh, hw,
                        y_out + (size_t)b0 * ny);
   }
   return hipGetLastError();
 }
 
-// the entry points' shared body; idx == nullptr: image b of x / cells itself (N == B)
+// the entry points' shared body; idx == nullptr: image b of x / cells itself (N == B); aa: the antialiased entries, which take width[B]
 int aff_entry(jcm_handle h, const char* who, const void* x, bool x_u8, const int32_t* cells, int64_t N, const int32_t* idx, bool indexed, const float* colour,
-              const double* geom, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out) {
+              const double* geom, const double* width, bool aa, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out) {
   JCM_TRY(check(h, false));
   const std::string w(who);
-  if (!x || !cells || (indexed && !idx) || !colour || !geom || !x_out || !y_out) return fail(JCM_ERR_ARG, w + ": null pointer");
+  if (!x || !cells || (indexed && !idx) || !colour || !geom || (aa && !width) || !x_out || !y_out) return fail(JCM_ERR_ARG, w + ": null pointer");
   if (h->K != 9)
     return fail(JCM_ERR_ARG, w + ": the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
   if (N < 1 || N > INT32_MAX || B < 1 || B > 65535 || hh < 1 || hw < 1 || H < 1 || W < 1 || (int64_t)H * W * 3 >= (int64_t)1 << 30)
@@ -205,6 +276,10 @@ int aff_entry(jcm_handle h, const char* who, const void* x, bool x_u8, const int
       if (!std::isfinite(geom[(size_t)b * 12 + j]))
         return fail(JCM_ERR_ARG, w + ": geom[" + std::to_string(b) + "][" + std::to_string(j) + "] is not finite");
   }
+  if (aa)
+    for (int b = 0; b < B; ++b)
+      if (!(width[b] >= 1.0 && width[b] <= kAffMaxWidth))      // (a NaN fails both comparisons)
+        return fail(JCM_ERR_ARG, w + ": width[" + std::to_string(b) + "] = " + std::to_string(width[b]) + " is not a finite filter half-width in [1, 4]");
   const size_t ix = (size_t)H * W * 3, iy = (size_t)hh * hw * kHmFlipChannels;
   const size_t nxa = (size_t)N * ix * (x_u8 ? 1 : sizeof(float)), nca = (size_t)N * kHmFlipChannels * 2 * sizeof(int32_t);
   const size_t nx = (size_t)B * ix * sizeof(float), ny = (size_t)B * iy * sizeof(float);
@@ -221,8 +296,8 @@ int aff_entry(jcm_handle h, const char* who, const void* x, bool x_u8, const int
   return with_arena(c, [&] {
     double* scratch = arena_alloc<double>(c, (size_t)B * kAffParts * 3);
     if (c->dry) return (int)JCM_OK;
-    const hipError_t launch = x_u8 ? aff_launch(static_cast<const uint8_t*>(x), cells, idx, colour, geom, B, H, W, hh, hw, pad, scratch, x_out, y_out, c->stream)
-                                   : aff_launch(static_cast<const float*>(x), cells, idx, colour, geom, B, H, W, hh, hw, pad, scratch, x_out, y_out, c->stream);
+    const hipError_t launch = x_u8 ? aff_launch(static_cast<const uint8_t*>(x), cells, idx, colour, geom, aa ? width : nullptr, B, H, W, hh, hw, pad, scratch, x_out, y_out, c->stream)
+                                   : aff_launch(static_cast<const float*>(x), cells, idx, colour, geom, aa ? width : nullptr, B, H, W, hh, hw, pad, scratch, x_out, y_out, c->stream);
     if (launch != hipSuccess) return fail(JCM_ERR_HIP, w + ": " + hipGetErrorString(launch));
     return (int)JCM_OK;
   });
@@ -238,17 +313,32 @@ extern "C" {
 
 int jcm_augment_affine(jcm_handle h, const float* x, const int32_t* cells, const float* colour, const double* geom, int B, int H, int W, int hh, int hw,
                        float pad, float* x_out, float* y_out) {
-  return aff_entry(h, "augment_affine", x, false, cells, B, nullptr, false, colour, geom, B, H, W, hh, hw, pad, x_out, y_out);
+  return aff_entry(h, "augment_affine", x, false, cells, B, nullptr, false, colour, geom, nullptr, false, B, H, W, hh, hw, pad, x_out, y_out);
 }
 
 int jcm_augment_affine_indexed(jcm_handle h, const float* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
                                const double* geom, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out) {
-  return aff_entry(h, "augment_affine_indexed", x_all, false, cells_all, N, idx, true, colour, geom, B, H, W, hh, hw, pad, x_out, y_out);
+  return aff_entry(h, "augment_affine_indexed", x_all, false, cells_all, N, idx, true, colour, geom, nullptr, false, B, H, W, hh, hw, pad, x_out, y_out);
 }
 
 int jcm_augment_affine_indexed_u8(jcm_handle h, const uint8_t* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
                                   const double* geom, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out) {
-  return aff_entry(h, "augment_affine_indexed_u8", x_all, true, cells_all, N, idx, true, colour, geom, B, H, W, hh, hw, pad, x_out, y_out);
+  return aff_entry(h, "augment_affine_indexed_u8", x_all, true, cells_all, N, idx, true, colour, geom, nullptr, false, B, H, W, hh, hw, pad, x_out, y_out);
+}
+
+int jcm_augment_affine_aa(jcm_handle h, const float* x, const int32_t* cells, const float* colour, const double* geom, const double* width, int B, int H,
+                          int W, int hh, int hw, float pad, float* x_out, float* y_out) {
+  return aff_entry(h, "augment_affine_aa", x, false, cells, B, nullptr, false, colour, geom, width, true, B, H, W, hh, hw, pad, x_out, y_out);
+}
+
+int jcm_augment_affine_aa_indexed(jcm_handle h, const float* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
+                                  const double* geom, const double* width, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out) {
+  return aff_entry(h, "augment_affine_aa_indexed", x_all, false, cells_all, N, idx, true, colour, geom, width, true, B, H, W, hh, hw, pad, x_out, y_out);
+}
+
+int jcm_augment_affine_aa_indexed_u8(jcm_handle h, const uint8_t* x_all, const int32_t* cells_all, int64_t N, const int32_t* idx, const float* colour,
+                                     const double* geom, const double* width, int B, int H, int W, int hh, int hw, float pad, float* x_out, float* y_out) {
+  return aff_entry(h, "augment_affine_aa_indexed_u8", x_all, true, cells_all, N, idx, true, colour, geom, width, true, B, H, W, hh, hw, pad, x_out, y_out);
 }
 
 }  // extern "C"

@@ -1114,9 +1114,10 @@ class Engine:
         return x_out, y_out
 
     # ------------------------------------------------------------------ the affine augmentation (augmentation.py)
-    def _affine_call(self, who, x, cells, idx, colour, geom, pad, x_out, y_out):
-        """The checks and the call the two affine entries share; idx None: image b of x / cells itself."""
-        from .augmentation import check_affine
+    def _affine_call(self, who, x, cells, idx, colour, geom, pad, x_out, y_out, width=None):
+        """The checks and the call the two affine entries share; idx None: image b of x / cells itself; width None: the plain entries, else the
+        antialiased ones (jcm_augment_affine_aa*) with that [B] array of filter half-widths."""
+        from .augmentation import check_affine, check_width
         u8 = self._chk_img(x, 'x_all' if idx is not None else 'x')
         self._chk(cells, 3, 'cells', torch.int32)
         N, H, W, C = x.shape
@@ -1144,6 +1145,7 @@ class Engine:
         colour, geom = check_affine(colour, geom)
         if colour.shape[0] != B:
             raise ValueError('%s: %d parameter rows for a batch of %d' % (who, colour.shape[0], B))
+        aa, wp = ('_aa', (check_width(width, B).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),)) if width is not None else ('', ())
         hh, hw = H // 8, W // 8
         x_out = self._new(B, H, W, 3) if x_out is None else self._chk(x_out, 4, 'x_out')
         y_out = self._new(B, hh, hw, 10) if y_out is None else self._chk(y_out, 4, 'y_out')
@@ -1152,28 +1154,29 @@ class Engine:
         self._on_stream(x, cells, x_out, y_out)
         cp, gp = colour.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), geom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         if idx is None:
-            status, what = self._lib.jcm_augment_affine(self._h, self._p(x), self._p(cells), cp, gp, B, H, W, hh, hw, float(pad),
-                                                        self._p(x_out), self._p(y_out)), 'jcm_augment_affine'
+            what = 'jcm_augment_affine' + aa
+            status = getattr(self._lib, what)(self._h, self._p(x), self._p(cells), cp, gp, *wp, B, H, W, hh, hw, float(pad), self._p(x_out), self._p(y_out))
         else:
-            fn, what = ((self._lib.jcm_augment_affine_indexed_u8, 'jcm_augment_affine_indexed_u8') if u8
-                        else (self._lib.jcm_augment_affine_indexed, 'jcm_augment_affine_indexed'))
-            status = fn(self._h, self._p(x), self._p(cells), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, gp, B, H, W, hh, hw, float(pad),
-                        self._p(x_out), self._p(y_out))
+            what = 'jcm_augment_affine' + aa + ('_indexed_u8' if u8 else '_indexed')
+            status = getattr(self._lib, what)(self._h, self._p(x), self._p(cells), N, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cp, gp, *wp, B, H, W,
+                                              hh, hw, float(pad), self._p(x_out), self._p(y_out))
         _lib.check(status, what)
         return x_out, y_out
 
-    def augment_affine(self, x, cells, colour, geom, pad=0.0, x_out=None, y_out=None):
+    def augment_affine(self, x, cells, colour, geom, pad=0.0, x_out=None, y_out=None, width=None):
         """The affine augmentation: x [B,H,W,3] device fp32, cells [B,10,2] device int32 = the (row, col) heat-map cell of every channel's
         joint, colour [B,3] / geom [B,12] HOST arrays (augmentation.affine_geometry), pad the value outside the source -> (x_out [B,H,W,3], y_out
         [B,H/8,W/8,10]), new tensors unless given: one bilinear sample of the image through the inverse map, the targets redrawn as 3x3 blobs at the cells
-        the forward map sends the joints to.  Enqueued on the engine's stream; the host does not wait."""
-        return self._affine_call('augment_affine', x, cells, None, colour, geom, pad, x_out, y_out)
+        the forward map sends the joints to.  Enqueued on the engine's stream; the host does not wait.
+        width: None, or a HOST float64 [B] array of filter half-widths in [1, 4] (augmentation.affine_footprint(geom)): the antialiased sample
+         -- image b through a triangle filter of half-width width[b] source pixels, the plain sample's bits where that is exactly 1."""
+        return self._affine_call('augment_affine', x, cells, None, colour, geom, pad, x_out, y_out, width)
 
-    def augment_affine_indexed(self, x_all, cells_all, idx, colour, geom, pad=0.0, x_out=None, y_out=None):
+    def augment_affine_indexed(self, x_all, cells_all, idx, colour, geom, pad=0.0, x_out=None, y_out=None, width=None):
         """augment_affine of the images idx[b] of the data set (x_all [N,H,W,3], cells_all [N,10,2]) read through the index: the same bits as gather_batch
         followed by augment_affine, without the gathered copy.  x_all may be uint8 (a byte data set): the same bits as from the float data set
-        float32(x_all) / float32(255)."""
-        return self._affine_call('augment_affine_indexed', x_all, cells_all, idx, colour, geom, pad, x_out, y_out)
+        float32(x_all) / float32(255).  width: as in augment_affine."""
+        return self._affine_call('augment_affine_indexed', x_all, cells_all, idx, colour, geom, pad, x_out, y_out, width)
 
     def joint_cells(self, y):
         """y [B,h,w,K+1] target maps -> int32 [B,K+1,2], the (row, col) of every channel's arg-max cell (the first maximum, as jcm_argmax_coords picks it): the

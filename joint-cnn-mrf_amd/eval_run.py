@@ -327,6 +327,28 @@ def write_det_curve(args, eng, res, y_test):
     print('test_dr: {} {}'.format(c_pd.rate(2, 10), c_sm.rate(2, 10)))
 
 
+def write_scale_curve(args, eng, x_test, y_test, cells=None):
+    """--eval_scale S [S ...] --scale_curve PATH: the test set through evaluation.eval_curves_affine on `eng` -- every image, the last
+    batch partial, at each scale S about the centre with the antialiased sample -- as a JSON document: the curves per scale in the shape --det_curve
+    gives a curve, and how many images each scale counted (those none of whose joints left the frame).  cells: the joint cells of the set where the
+    run has them (--synth_people); else the arg-max cells of y_test, taken on the device batch by batch."""
+    from .evaluation import eval_curves_affine
+    B = args.batch_size
+    if cells is None:
+        cells = np.concatenate([eng.joint_cells(torch.as_tensor(np.ascontiguousarray(y_test[lo:lo + B], np.float32), device=eng.device)).cpu().numpy()
+                                for lo in range(0, len(y_test), B)])
+    scales = [float(s) for s in args.eval_scale]
+    curves = eval_curves_affine(x_test, cells, eng, B, scales, use_sm=args.use_sm, antialias=True)
+    names = [str(n) for n in JOINT_NAMES[:eng.n_joints]]
+    per = lambda c: {n: v for n, v in c.as_dict(names).items() if n in names} if c.n_images else None      # (no image counted: no rates)
+    doc = {'scales': scales, 'counted': [int(curves[s][0].n_images) for s in scales], 'pd': {str(s): per(curves[s][0]) for s in scales},
+           'sm': {str(s): per(curves[s][1]) for s in scales}, 'antialias': True, 'radii': [float(r) for r in curves[scales[0]][0].radii],
+           'joint_names': names, 'n_images': int(len(x_test)), 'use_sm': bool(args.use_sm)}
+    os.makedirs(os.path.dirname(args.scale_curve) or '.', exist_ok=True)
+    with open(args.scale_curve, 'w') as fh:
+        json.dump(doc, fh)
+
+
 def summary_line(args, res, dt, y_test):
     """The JSON line a run ends with."""
     n = int(res.pred_pd.shape[2])
@@ -336,6 +358,8 @@ def summary_line(args, res, dt, y_test):
         line.update(res.fed)
     if args.flip_test:
         line['flip_test'] = True
+    if getattr(args, 'eval_scale', None):
+        line['eval_scale'] = [float(s) for s in args.eval_scale]
     if res.torso_cells is not None:      # how far the inferred cell lies from the arg-max of the annotated torso channel (first occurrence), in cells
         index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus))
         ann = np.asarray(y_test)[index][:, :, :, N_JOINTS].reshape(len(index), -1).argmax(axis=1)
@@ -367,7 +391,8 @@ def run(args):
     """The evaluation run (main.py:668-675): predictions of the test set, single scale sharded over the towers of --gpus or --multiscale on the
     first of them."""
     from .dist import Towers
-    x_train, y_train, x_test, y_test, pairwise = load_data(args)
+    people = {}      # --synth_people: the joint cells of the rendered sets, which --eval_scale transforms
+    x_train, y_train, x_test, y_test, pairwise = load_data(args, people)
     if args.synthetic and args.u8_images and not args.multiscale:
         x_test = byte_grid(x_test)
     params, _ = run_params(args, pairwise)
@@ -394,5 +419,7 @@ def run(args):
     if res.pose is not None:
         index = evaluated_indices(len(y_test), args.batch_size, len(args.gpus))
         print('test_dr_pose: {}'.format(pose_det_rate(eng, res.pose['coords'].transpose(1, 2, 0), y_test, index)))
+    if args.eval_scale:      # after the clock has stopped and the run's own outputs are written: they are what they are without the flags
+        write_scale_curve(args, eng, x_test, y_test, people.get('cells_test'))
     summary_line(args, res, dt, y_test)
     towers.close()

@@ -221,6 +221,43 @@ def eval_curves(X, Y, engine, batch_size, use_sm=True, radii=range(1, 21), flip_
     return pd, sm
 
 
+def eval_curves_affine(X, cells, engine, batch_size, scales, angle=0.0, pad=0.0, use_sm=True, radii=range(1, 21), antialias=True):
+    """Detection-rate curves of a set shown to the tower at other scales: for every scale, every batch (the last may be partial) is
+    drawn through ONE fixed geometry -- augmentation.fixed_affine(scale, angle) about the centre, `pad` outside, the antialiased sample unless
+    antialias=False -- by Engine.augment_affine, which also redraws the targets at the moved cells; the transformed batch goes through
+    engine.forward with the redrawn tenth channel as the torso, and the coordinates are judged against the redrawn targets.
+    X [N,H,W,3] float or uint8 (bytes are widened to the floats they stand for), cells [N,10,2] int (data.joint_cells, Engine.joint_cells(Y)); numpy or
+    torch, host or device.  An image any of whose ten points leaves the frame under the forward map (augmentation.affine_joints_inside, decided on the
+    host in float64) has a clamped target and is left out of that scale's counts: DetCurve.n_images of a scale is the number counted.
+    Returns {scale: (DetCurve of the part detector, DetCurve of the spatial model)}; without use_sm the second counts the part detector's coordinates."""
+    from .augmentation import affine_joints_inside, fixed_affine
+    K = engine.n_joints
+    host_cells = cells.cpu().numpy() if isinstance(cells, torch.Tensor) else np.asarray(cells)
+    out = {}
+    for scale in scales:
+        pd, sm = DetCurve(engine, radii), DetCurve(engine, radii)
+        for lo in range(0, len(X), batch_size):
+            bx = torch.as_tensor(X[lo:lo + batch_size]).to(engine.device)
+            x = (bx.to(torch.float32) / 255.0 if bx.dtype == torch.uint8 else bx.to(torch.float32)).contiguous()      # float32(k) / float32(255)
+            c = torch.as_tensor(host_cells[lo:lo + batch_size].astype(np.int32), device=engine.device).contiguous()
+            n, H, W, _ = x.shape
+            draw = fixed_affine(n, H, W, scale, angle=angle, pad=pad, antialias=antialias)
+            xa, ya = engine.augment_affine(x, c, draw.colour, draw.geom, draw.pad, width=draw.width)
+            keep = affine_joints_inside(host_cells[lo:lo + batch_size], draw.geom, H, W)
+            r = engine.forward(xa, ya[..., K:].contiguous() if use_sm else None, use_sm=use_sm, want_prob=False)
+            if not keep.any():
+                continue
+            rows = torch.as_tensor(np.flatnonzero(keep), device=engine.device)
+            with torch.cuda.stream(engine._stream):      # the coordinates and the targets were written on the engine's stream
+                yk = ya.index_select(0, rows).contiguous()
+                pk = r['pd_coords'].index_select(0, rows).contiguous()
+                sk = r['sm_coords'].index_select(0, rows).contiguous() if use_sm else pk
+            pd.update(pk, yk)
+            sm.update(sk, yk)
+        out[scale] = (pd, sm)
+    return out
+
+
 def eval_error(X_np, Y_np, engine, batch_size, use_sm=True, joints=(2,), det_radius=10, curves=None):
     """main.py:275-283: run a data set through the tower in inference mode batch by batch and return the means over
     batches of (loss_pd, loss_sm, det_rate_pd, det_rate_sm).  X_np [N,480,720,3] (float, or uint8 byte images), Y_np [N,60,90,10] (numpy or torch,

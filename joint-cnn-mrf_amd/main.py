@@ -93,6 +93,11 @@ def build_parser():
     parser.add_argument('--det_curve', default=None, metavar='PATH', help='evaluation run: write the detection-rate curves of the predictions (every joint, radii '
                         '1..20 %% of the torso length, part detector and spatial model) to this JSON file and print the reference\'s test_dr line '
                         '(main.py:424; DESIGN.md 4.11).')
+    parser.add_argument('--eval_scale', type=float, nargs='+', default=None, metavar='S', help='single-scale evaluation run, with --scale_curve: after the run\'s own '
+                        'outputs, show the tower the whole test set at every person scale S in [0.25, 4] -- one antialiased affine sample about the centre, the '
+                        'targets redrawn at the moved joints (evaluation.eval_curves_affine, DESIGN.md 4.27) -- and write one detection-rate curve per scale; an '
+                        'image a joint of which leaves the frame is not counted at that scale.')
+    parser.add_argument('--scale_curve', default=None, metavar='PATH', help='with --eval_scale: the JSON file the curves per scale go to.')
     parser.add_argument('--peaks', type=int, default=0, metavar='P', help='evaluation run with --predictions: also write flic_peaks_pd / flic_peaks_sm, [N,K,P,3] = '
                         '(row, col, score) in image pixels of the P highest local maxima of every heat map, refined by a quarter cell towards the higher '
                         'neighbour (evaluation.peaks_to_pixels; DESIGN.md 4.12).  1..8; 0 = off.')
@@ -157,6 +162,9 @@ def build_parser():
                         'flip, brightness, contrast, a rotation of up to 20 degrees, scale and shift -- and targets redrawn as 3x3 blobs at the transformed joint '
                         'cells (Engine.augment_affine, DESIGN.md 4.20; drawn from --seed + 1).  Not the reference\'s --data_augm.  What it buys in detection rate '
                         'has not been measured.')
+    parser.add_argument('--augm_antialias', action='store_true', help='with --augm_affine: sample through a triangle filter as wide as the picture is shrunk '
+                        '(Engine.augment_affine(width=), DESIGN.md 4.27) instead of four bilinear taps, which alias below scale 1; scales >= 1 are sampled as '
+                        'without it.  The scale range must start at 0.25 or above')
     parser.add_argument('--augm_scale', type=float, nargs=2, default=None, metavar=('LO', 'HI'), help='with --augm_affine: the scale is uniform in [LO, HI], '
                         '0 < LO <= HI (default 0.5 1.5, the range of the reference\'s docstring: an untuned placeholder).')
     parser.add_argument('--augm_shift', type=float, default=None, metavar='F', help='with --augm_affine: the shift is uniform in +-F of the frame width and height, '
@@ -389,6 +397,13 @@ SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set th
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
 AUGM_AFFINE_NEEDS_TRAIN = '--augm_affine augments the batches of a training run: give --train as well'
+AUGM_ANTIALIAS_NEEDS_AUGM_AFFINE = '--augm_antialias chooses the sampler of --augm_affine: give --augm_affine as well'
+AUGM_ANTIALIAS_SCALE_FLOOR = '--augm_antialias: the widest filter is 9 x 9 taps, scale 0.25: give --augm_scale LO HI with LO >= 0.25'
+EVAL_SCALE_NEEDS_SCALE_CURVE = '--eval_scale sweeps the test set over person scales and writes the curves: give --scale_curve PATH as well'
+SCALE_CURVE_NEEDS_EVAL_SCALE = '--scale_curve is where the curves of --eval_scale go: give --eval_scale S [S ...] as well'
+EVAL_SCALE_IS_EVALUATION_ONLY = '--eval_scale belongs to the evaluation run (the run without --train and without --predict)'
+EVAL_SCALE_SINGLE_SCALE_ONLY = ('--eval_scale cannot be combined with --multiscale, --flip_test, --infer_torso or --u8_images: the sweep sends float batches '
+                                'through the single-scale forward with the redrawn torso map')
 AUGM_OPTION_NEEDS_AUGM_AFFINE = '--augm_scale, --augm_shift and --augm_pad set the ranges of --augm_affine: give --augm_affine as well'
 SYNTH_PEOPLE_NOT_WITH_SYNTHETIC = '--synth_people and --synthetic both replace the data set: give one of them'
 SYNTH_PEOPLE_NOT_WITH_PREDICT = '--synth_people replaces the data of --train and of the evaluation run; --predict reads the images it names: drop one of them'
@@ -492,7 +507,7 @@ class TowerTrainer:
         self.towers = towers
         self.augment_rng = augment_rng      # numpy RandomState: augment every step (main.py:494-497), parameters drawn for the global batch
         self.augment_kind = augment_kind    # 'reference': augmentation.draw_params; 'affine': augmentation.draw_affine
-        self.affine_kw = dict(affine_kw or {})      # pad, scale, max_angle, shift of augmentation.draw_affine
+        self.affine_kw = dict(affine_kw or {})      # pad, scale, max_angle, shift, antialias of augmentation.draw_affine
         self.trainers = [Trainer(e, **trainer_kw) for e in towers.engines]
         self.moving = {k: np.asarray(v, np.float32).reshape(-1).copy() for k, v in params.items()
                        if k.endswith('moving_mean') or k.endswith('moving_variance')}
@@ -619,7 +634,7 @@ def train_main(args):
     towers = Towers(params, args.gpus, precision=args.precision)
     augm = {}
     if args.augm_affine:      # drawn from a generator of its own: the batches are those of the run without it
-        kw = {'scale': args.augm_scale, 'shift': args.augm_shift, 'pad': args.augm_pad}
+        kw = {'scale': args.augm_scale, 'shift': args.augm_shift, 'pad': args.augm_pad, 'antialias': True if args.augm_antialias else None}
         augm = dict(augment_rng=np.random.RandomState(args.seed + 1), augment_kind='affine', affine_kw={k: v for k, v in kw.items() if v is not None})
     tt = TowerTrainer(towers, params, optimizer=args.optimizer, lr=args.lr, lmbd=args.lmbd, use_sm=args.use_sm, n_updates_total=n_updates_total, **augm)
     if state:
@@ -790,13 +805,24 @@ SEQ_CAMERA_RULES = (
     (lambda a: a.seq_camera and a.seq_people is not None, SEQ_CAMERA_NO_PEOPLE),
     (lambda a: a.seq_camera_search is not None and not 1 <= a.seq_camera_search <= 16, lambda a: '--seq_camera_search %d: 1 <= D <= 16' % a.seq_camera_search),
 )
+# The rules of --eval_scale / --scale_curve and of --augm_antialias, walked behind SEQ_CAMERA_RULES (a table of their own for the same reason).
+EVAL_SCALE_RULES = (
+    (lambda a: a.eval_scale is not None and not a.scale_curve, EVAL_SCALE_NEEDS_SCALE_CURVE),
+    (lambda a: a.scale_curve and a.eval_scale is None, SCALE_CURVE_NEEDS_EVAL_SCALE),
+    (lambda a: a.eval_scale is not None and (a.train or a.predict), EVAL_SCALE_IS_EVALUATION_ONLY),
+    (lambda a: a.eval_scale is not None and (a.multiscale or a.flip_test or a.infer_torso or a.u8_images), EVAL_SCALE_SINGLE_SCALE_ONLY),
+    (lambda a: a.eval_scale is not None and not all(0.25 <= s <= 4 for s in a.eval_scale),
+     lambda a: '--eval_scale %s: 0.25 <= S <= 4' % ' '.join('%g' % s for s in a.eval_scale)),
+    (lambda a: a.augm_antialias and not a.augm_affine, AUGM_ANTIALIAS_NEEDS_AUGM_AFFINE),
+    (lambda a: a.augm_antialias and a.augm_scale is not None and a.augm_scale[0] < 0.25, AUGM_ANTIALIAS_SCALE_FLOOR),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES + EVAL_SCALE_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

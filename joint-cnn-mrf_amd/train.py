@@ -94,7 +94,7 @@ class Trainer:
                              % (hh, ww, e.n_joints + 1, tuple(x.shape), tuple(y.shape)))
         if isinstance(augment, AffineDraw):
             xa, ya = self._aff_buffers(x.shape, y.shape, augment)
-            x, y = e.augment_affine(x, e.joint_cells(y), augment.colour, augment.geom, augment.pad, xa, ya)
+            x, y = e.augment_affine(x, e.joint_cells(y), augment.colour, augment.geom, augment.pad, xa, ya, width=augment.width)
         elif augment is not None:
             x, y = self._augmented(x, y, augment)
         return self._loss_and_grads(x, y)
@@ -159,7 +159,7 @@ class Trainer:
             if getattr(dataset, 'cells', None) is None:
                 raise ValueError('the affine augmentation reads the joint cells of the data set: it must have .cells [N,10,2] (dataset.DeviceDataset)')
             xa, ya = self._aff_buffers(shape_x, shape_y, augment)
-            x, y = e.augment_affine_indexed(dataset.x, dataset.cells, idx, augment.colour, augment.geom, augment.pad, xa, ya)
+            x, y = e.augment_affine_indexed(dataset.x, dataset.cells, idx, augment.colour, augment.geom, augment.pad, xa, ya, width=augment.width)
         elif augment is not None:
             xa, ya, pd = self._aug_buffers(shape_x, shape_y, augment)
             x, y = e.augment_train_indexed(dataset.x, dataset.y, idx, pd, xa, ya)

@@ -5,8 +5,9 @@ each a child process of this tool whose exit status is checked; the first failur
          have passed; then eval_error on the held-out set and the variables as an .npz.
   eval:  on the last 20 % of the poses, rendered from the test seed: the eval_curves detection rates at r = 1..20, every joint, part detector and
          spatial model; the same with flip_test=True; the same through multiscale.get_predictions; the mean torso_cell_dist of torso='infer'.
-The run 'augm' is the same with --augm_affine.  Writes <outdir>/synth_people_train.json, one entry per run (an existing file keeps its other runs).
-    python tools/synth_people_train.py <outdir> [--runs plain,augm] [--epochs 40] [--minutes 10] [--poses P.npy] [--limit N] [--debug] [--revision R]
+The run 'augm' is the same with --augm_affine, the run 'augm_aa' with --augm_affine --augm_antialias.  --keep_state leaves state_<run>.npz in
+<outdir> (tools/scale_sweep_measure.py reads it).  Writes <outdir>/synth_people_train.json, one entry per run (an existing file keeps its other runs).
+    python tools/synth_people_train.py <outdir> [--runs plain,augm,augm_aa] [--epochs 40] [--minutes 10] [--poses P.npy] [--limit N] [--debug] [--revision R]
 These are rates on rendered figures and say nothing about FLIC."""
 import argparse
 import json
@@ -26,7 +27,7 @@ def cli(a, train, augm):
     v = ['--use_sm', '--u8_images', '--synth_people', a.poses, '--batch_size', str(BATCH), '--gpus', '0', '--seed', '0'] + (['--debug'] if a.debug else [])
     if train:
         v += ['--train', '--device_data', '--synth_fresh', '--optimizer', 'adam', '--lr', '0.001', '--lmbd', '0.001', '--n_epochs', str(a.epochs)]
-        v += ['--augm_affine'] if augm else []
+        v += {'augm': ['--augm_affine'], 'augm_aa': ['--augm_affine', '--augm_antialias']}.get(augm, [])
     else:
         v += ['--restore', '--restore_path', os.path.join(a.outdir, 'state_%s.npz' % a.run)]
     return v
@@ -38,7 +39,7 @@ def stage_train(a):
     from joint_cnn_mrf_amd import main as M
     from joint_cnn_mrf_amd.dataset import DeviceDataset
     from joint_cnn_mrf_amd.dist import Towers
-    augm = a.run == 'augm'
+    augm = a.run if a.run in ('augm', 'augm_aa') else None
     args = M.build_parser().parse_args(cli(a, True, augm))
     t0 = time.time()
     people = {}
@@ -47,7 +48,7 @@ def stage_train(a):
     params, _ = M.run_params(args, pairwise)
     towers = Towers(params, args.gpus, precision=args.precision)
     eng = towers.engines[0]
-    kw = dict(augment_rng=np.random.RandomState(args.seed + 1), augment_kind='affine') if augm else {}
+    kw = dict(augment_rng=np.random.RandomState(args.seed + 1), augment_kind='affine', affine_kw={'antialias': True} if augm == 'augm_aa' else None) if augm else {}
     tt = M.TowerTrainer(towers, params, optimizer=args.optimizer, lr=args.lr, lmbd=args.lmbd, use_sm=True, n_updates_total=args.n_epochs * n_train // BATCH, **kw)
     ds = DeviceDataset(x_train, y_train, device=eng.device, reserve_bytes=(2 << 30) if a.debug else (64 << 30), image_dtype='uint8', cells=people['cells_train'])
     del x_train
@@ -87,7 +88,7 @@ def stage_eval(a):
     from joint_cnn_mrf_amd import main as M
     from joint_cnn_mrf_amd.engine import Engine
     from joint_cnn_mrf_amd.eval_run import det_curves_of_predictions
-    args = M.build_parser().parse_args(cli(a, False, False))
+    args = M.build_parser().parse_args(cli(a, False, None))
     _xt, _yt, x_test, y_test, _ = M.load_data(args)
     params, _ = M.run_params(args, None)
     eng = Engine(device=0, precision=args.precision, n_joints=9).load_params(params)
@@ -134,6 +135,7 @@ def main():
     ap.add_argument('--limit', type=int, default=0, help='use the first N poses only (a rehearsal)')
     ap.add_argument('--debug', action='store_true', help='the quarter-width tower (a rehearsal)')
     ap.add_argument('--revision', default=None)
+    ap.add_argument('--keep_state', action='store_true', help='leave state_<run>.npz, the trained variables, in <outdir>')
     ap.add_argument('--stage', default=None, choices=['train', 'eval'])
     ap.add_argument('--run', default=None)
     a = ap.parse_args()
@@ -160,7 +162,8 @@ def main():
         doc[run] = dict(json.load(open(os.path.join(a.outdir, 'train_%s.json' % run))), **json.load(open(os.path.join(a.outdir, 'eval_%s.json' % run))))
         with open(path, 'w') as fh:
             json.dump(doc, fh, indent=1)
-        os.remove(os.path.join(a.outdir, 'state_%s.npz' % run))
+        if not a.keep_state:
+            os.remove(os.path.join(a.outdir, 'state_%s.npz' % run))
     print('wrote %s' % path)
 
 
