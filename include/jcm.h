@@ -477,6 +477,48 @@ int jcm_seq_smooth_lag(jcm_handle h, const float* hm, int S, int W, int P, int H
 int jcm_frame_shift(jcm_handle h, const uint8_t* x, int T, int H, int W, int y0, int x0, int ch, int cw, int D, const uint8_t* prev,
                     int32_t* disp, int64_t* sad);
 
+/* -- local motion: one displacement per heat-map cell -------------------------------------------
+ * Exhaustive block matching on the integer luma of jcm_frame_shift, once per heat-map cell (8 x 8 fitted-frame pixels) and reference frame.  Every
+ * step is integer arithmetic and the sums are order-free, so the result is a function of the bytes alone.
+ * x: device uint8 [T,H,W,3], the letterboxed frames, H and W multiples of 8;  (y0, x0, ch, cw): the content rectangle of the fit -- no byte outside
+ * it is read;  D in 1..16: the search radius in pixels;  ref: DEVICE int32 [T,R], R in 1..8: slot r of frame t is matched against frame
+ * s = ref[t,r]; an entry that is negative or >= T means "no such frame" (the host cannot refuse it without reading it back, so the kernel
+ * treats it so).  With HH = H / 8, WW = W / 8, per (t, r) with a frame s and per cell (Y, X):
+ *   L(y,x)  = R + 2 G + B                                              in 0 .. 1020
+ *   block   = the 16 x 16 pixels [8Y - 4, 8Y + 12) x [8X - 4, 8X + 12)
+ *   P       = the block intersected with the content rectangle: a rectangle, possibly empty
+ *   (dy,dx) in [-D, D]^2 is valid when P displaced by it lies inside the content rectangle; (0,0) always is
+ *   S(dy,dx) = sum over p in P of |L_t(p) - L_s(p + (dy,dx))|          at most 256 * 1020, held in 32 bits
+ *   the winner minimises the tuple (S, dy^2 + dx^2, dy, dx) over the valid candidates -- the tie-break of jcm_frame_shift: a uniform block, or
+ *   two identical frames, give (0,0)
+ * Outputs (device): flow int32 [T,R,HH,WW,2] = the winner (dy, dx);  sad int32 [T,R,HH,WW,2] = (S at the winner, S at (0,0)).  A cell with an
+ *   empty P and every cell of a slot without a frame: flow = sad = 0.
+ * Sign: the content at pixel (y,x) of frame t is at (y+dy, x+dx) of frame s -- the convention of `shift` and of jcm_frame_shift's disp.
+ * JCM_ERR_ARG -- nothing is launched, flow and sad are untouched -- for a null x, ref, flow or sad;  T < 1 or T > 65534;  D outside 1..16;  R
+ *   outside 1..8;  H or W that is no multiple of 8, or above 4096;  a rectangle that is not inside the frame.
+ * Uses the workspace arena (2 bytes per frame and pixel of the rectangle); JCM_ERR_STATE with the bytes in the message when they do not fit.
+ * Enqueues on the handle's stream and does not synchronise (growing the workspace does).  Timed as "frame_flow". */
+int jcm_frame_flow(jcm_handle h, const uint8_t* x, int T, int H, int W, int y0, int x0, int ch, int cw, int D, const int32_t* ref, int R,
+                   int32_t* flow, int32_t* sad);
+
+/* -- local motion: the neighbours' heat maps warped onto the frame and pooled -------------------
+ * hm: device fp32 [T,HH,WW,K];  flow: device int32 [T,2N,HH,WW,2] as jcm_frame_flow writes it with slot 2(n-1) holding ref = t - n and slot
+ * 2(n-1) + 1 holding ref = t + n, n = 1 .. N, N in 1..4;  w: HOST float64 [N+1].  Per (t, y, x, k), float64, one correctly rounded operation per
+ * step, evaluated as written:
+ *   acc = w[0] * hm[t,y,x,k];   ws = w[0]
+ *   for n = 1 .. N, first s = t - n, then s = t + n; an s outside [0, T) is skipped (whatever its flow slot holds):
+ *     (dy, dx) = flow[t, slot, y, x];   py = y + dy / 8,  px = x + dx / 8  (exact), clamped to [0, HH-1] and [0, WW-1]
+ *     ya = floor(py), yb = min(ya + 1, HH-1), fy = py - ya;  xa, xb, fx likewise;  v_ab = (double)hm[s, y_a, x_b, k]
+ *     top = (1 - fx) * v_aa + fx * v_ab;   bot = (1 - fx) * v_ba + fx * v_bb;   v = (1 - fy) * top + fy * bot
+ *     acc = acc + w[n] * v;   ws = ws + w[n]
+ *   out[t,y,x,k] = (float)(acc / ws)
+ * The flow is a cell's own displacement in pixels, so the neighbour's map is read where the cell's content is in that frame.  With w[n] = 0 for
+ * all n >= 1 out has hm's bits.  Any int32 flow is legal: the sample point is clamped.
+ * JCM_ERR_ARG -- nothing is launched, out is untouched -- for sizes below 1;  K > 16;  HH * WW > 8192 (what jcm_seq_* take);  N outside 1..4;  a
+ *   null pointer;  w[0] <= 0, another w[n] < 0, a w[n] that is not finite;  out overlapping hm.
+ * Enqueues on the handle's stream and does not synchronise.  Timed as "hm_flow_pool". */
+int jcm_hm_flow_pool(jcm_handle h, const float* hm, int T, int HH, int WW, int K, const int32_t* flow, int N, const double* w, float* out);
+
 /* -- several tracks through single-channel maps: one torso track per person of a clip ----------
  * hm: device fp32 [S,T,HH,WW], one non-negative channel (the torso probabilities of the frames); M in 1..4 tracks; taps HOST [2R+1], R and rho as for
  * jcm_seq_* with one tap row; D in 0..64, the exclusion half-width in cells.

@@ -76,6 +76,10 @@ SIGNATURES = {
                                              ctypes.c_void_p, _c_i32_p, ctypes.c_void_p, _c_float_p]),
     'jcm_frame_shift': (ctypes.c_int, [_handle, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_void_p, _c_i32_p, ctypes.c_void_p]),
+    'jcm_frame_flow': (ctypes.c_int, [_handle, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, _c_i32_p, ctypes.c_int, _c_i32_p, _c_i32_p]),
+    'jcm_hm_flow_pool': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32_p, ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_double), _c_float_p]),
     'jcm_torso_infer': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32_p, _c_float_p, _c_i32_p, _c_float_p]),
     'jcm_forward': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    _c_float_p, _c_float_p, _c_i32_p, _c_i32_p]),

@@ -464,6 +464,19 @@ constexpr int kFrameShiftMaxT = 65534;
 size_t frame_shift_slots(int pairs, int D);
 hipError_t frame_shift(const uint8_t* x, int T, int H, int W, int y0, int x0, int ch, int cw, int D, const uint8_t* prev, uint16_t* L, uint16_t* C,
                        unsigned long long* slots, int32_t* center, int32_t* disp, int64_t* sad, hipStream_t st);
+// ---- frame_flow.hip : one displacement per heat-map cell, and the neighbours' maps pooled along it ----
+// x [T,H,W,3] bytes; H, W multiples of 8 and <= kFrameFlowMaxSide; the content rectangle inside the frame; 1 <= D <= kFrameFlowMaxD; ref DEVICE int32
+// [T][R], 1 <= R <= kFrameFlowMaxR, an entry outside [0, T) is "no such frame".  Workspace: L uint16 [T][ch][cw].  flow, sad int32 [T,R,H/8,W/8,2] as in
+// jcm.h.  Two launches.
+constexpr int kFrameFlowMaxD = 16;
+constexpr int kFrameFlowMaxR = 8;
+constexpr int kFrameFlowMaxSide = 4096;
+constexpr int kFrameFlowMaxT = 65534;
+hipError_t frame_flow(const uint8_t* x, int T, int H, int W, int y0, int x0, int ch, int cw, int D, const int32_t* ref, int R, uint16_t* L, int32_t* flow,
+                      int32_t* sad, hipStream_t st);
+// hm, out [T,HH,WW,K]; flow int32 [T,2N,HH,WW,2]; w HOST [N+1], checked by the caller and carried in the launch's arguments.  One launch.
+constexpr int kFlowPoolMaxN = 4;
+hipError_t hm_flow_pool(const float* hm, int T, int HH, int WW, int K, const int32_t* flow, int N, const double* w, float* out, hipStream_t st);
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale
 hipError_t bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* scale, float* shift,
                    int n, hipStream_t st);

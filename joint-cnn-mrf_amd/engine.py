@@ -472,6 +472,56 @@ class Engine:
                                              self._p(out['sad'])), 'jcm_frame_shift')
         return out
 
+    def frame_flow(self, x, rect, ref, search=motion.SEQ_FLOW_SEARCH):
+        """One whole-pixel displacement per heat-map cell between every frame and its reference frames (include/jcm.h:
+        jcm_frame_flow): x uint8 [T,H,W,3] on the device, the letterboxed frames of a clip, H and W multiples of 8; rect = (y0, x0, ch, cw), the
+        content rectangle of their fit -- nothing outside it is read; ref: int [T,R] on the host or the device, R in 1..8: slot r of frame t is
+        matched against frame ref[t,r], a negative entry (or one >= T) is "no such frame" (motion.flow_refs builds the layout hm_flow_pool
+        takes); search: the radius D in 1..16 pixels.  Returns {'flow' int32 [T,R,H/8,W/8,2] = (dy, dx): the content at pixel (y, x) of frame t is
+        at (y + dy, x + dx) of the reference frame, 'sad' int32 [T,R,H/8,W/8,2] = (the sum of absolute luma differences over the cell's block
+        at flow, the same at (0, 0))}, device tensors, zero where there is no frame or no pixel.  Integer arithmetic throughout; nothing is
+        read back.  Sizes, the rectangle and search are checked by the library."""
+        self._chk(x, 4, 'x', torch.uint8)
+        T, H, W, C = x.shape
+        if C != 3:
+            raise ValueError('x must be [T,H,W,3], got shape %s' % (tuple(x.shape),))
+        if not isinstance(ref, torch.Tensor):
+            a = np.asarray(ref)
+            if a.dtype.kind not in 'iu' or a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError('ref must hold int32 values, got %s' % (a.dtype,))
+            ref = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32)))
+        if ref.dtype != torch.int32:
+            raise ValueError('ref must be int32, got %s' % (ref.dtype,))
+        if ref.dim() != 2 or ref.shape[0] != T:
+            raise ValueError('ref must be [T,R] = [%d,R], got %s' % (T, tuple(ref.shape)))
+        ref = ref.to(self.device).contiguous()
+        R = int(ref.shape[1])
+        y0, x0, ch, cw = (int(v) for v in rect)
+        out = {'flow': self._new(T, R, H // 8, W // 8, 2, dtype=torch.int32), 'sad': self._new(T, R, H // 8, W // 8, 2, dtype=torch.int32)}
+        self._on_stream(x, ref, *out.values())
+        _lib.check(self._lib.jcm_frame_flow(self._h, self._p(x), T, H, W, y0, x0, ch, cw, int(search), self._p(ref), R, self._p(out['flow']),
+                                            self._p(out['sad'])), 'jcm_frame_flow')
+        return out
+
+    def hm_flow_pool(self, hm, flow, weights):
+        """The neighbouring frames' heat maps warped onto every frame by its cells' own displacement and pooled with the frame's map (DESIGN.md
+        4.28, include/jcm.h: jcm_hm_flow_pool): hm fp32 [T,HH,WW,K]; flow int32 [T,2N,HH,WW,2], what frame_flow returns for motion.flow_refs(T, N);
+        weights: N + 1 host values, w[0] > 0 for the frame itself and w[n] >= 0 for the frames n before and after (motion.flow_weights).  Returns
+        fp32 like hm: the weighted mean, in float64 and one fixed order, of the frame's value and the bilinear samples of the neighbours that
+        exist.  A device tensor; nothing is read back.  N in 1..4, K <= 16 and HH * WW <= 8192 are checked by the library."""
+        self._chk(hm, 4, 'hm')
+        self._chk(flow, 5, 'flow', torch.int32)
+        T, HH, WW, K = hm.shape
+        w = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
+        N = int(w.size) - 1
+        if tuple(flow.shape) != (T, 2 * N, HH, WW, 2):
+            raise ValueError('flow must be [T,2N,HH,WW,2] = %s for %d weights, got %s' % ((T, 2 * N, HH, WW, 2), w.size, tuple(flow.shape)))
+        out = self._new(T, HH, WW, K)
+        self._on_stream(hm, flow, out)
+        _lib.check(self._lib.jcm_hm_flow_pool(self._h, self._p(hm), T, HH, WW, K, self._p(flow), N, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                              self._p(out)), 'jcm_hm_flow_pool')
+        return out
+
     def seq_smooth(self, hm, sigma, rho, radius=None, want_smoothed=True):
         """The smoothed marginals P(x_t | all frames) of a clip's heat maps and the expected transition statistics of the backward pass (DESIGN.md
         4.23, include/jcm.h: jcm_seq_smooth); hm, sigma, rho and radius as for seq_filter, offline (no state).  Returns {'smoothed' fp32 like hm

@@ -154,6 +154,13 @@ def build_parser():
                         'translation only, no cut detection.  Not with --seq_zoom, --seq_people, --seq_fit or --sequence marginal / lag.')
     parser.add_argument('--seq_camera_search', type=int, default=None, metavar='D', help='with --seq_camera: the coarse search radius in 1..16, reaching 4 D + 3 fitted '
                         'pixels a frame (default 8, an untuned placeholder).')
+    parser.add_argument('--seq_flow', type=int, default=None, metavar='N', help='with --sequence filter, viterbi or marginal: pool every frame\'s heat maps with those of '
+                        'the N (1..4, no default: none has been tuned) frames before and after it, each warped onto the frame by one displacement per heat-map cell '
+                        '(Engine.frame_flow, Engine.hm_flow_pool, DESIGN.md 4.28), and run the mode on the pooled maps; the document gains "flow" per file, the JSON '
+                        'line seq_flow and seq_flow_search.  Block matching on luma, whole pixels, no occlusion reasoning.  Not with --sequence lag, --seq_zoom or '
+                        '--seq_people.')
+    parser.add_argument('--seq_flow_search', type=int, default=None, metavar='D', help='with --seq_flow: the search radius in 1..16 fitted pixels a frame (default 8, an '
+                        'untuned placeholder).')
     parser.add_argument('--seq_torso_sigma', type=float, default=None, metavar='CELLS', help='with --seq_people: the standard deviation of a torso\'s motion per '
                         'frame in heat-map cells (default 1.5, an untuned placeholder).')
     parser.add_argument('--seq_exclude', type=int, default=None, metavar='CELLS', help='with --seq_people: the half-width in 0..64 heat-map cells of the square '
@@ -393,6 +400,11 @@ SEQ_CAMERA_NO_FIT = '--seq_camera cannot be combined with --seq_fit: the fit run
 SEQ_CAMERA_NO_ZOOM = '--seq_camera cannot be combined with --seq_zoom: the zoom windows already move with the person'
 SEQ_CAMERA_NO_PEOPLE = '--seq_camera cannot be combined with --seq_people: the torso passes have no form for a lattice that moves from frame to frame'
 SEQ_CAMERA_SEARCH_NEEDS_SEQ_CAMERA = '--seq_camera_search sets the search radius of --seq_camera: give --seq_camera as well'
+SEQ_FLOW_NEEDS_SEQUENCE = '--seq_flow pools the heat maps of the clip --sequence names: give --sequence filter, viterbi or marginal as well'
+SEQ_FLOW_NO_LAG = '--seq_flow cannot be combined with --sequence lag: two-sided pooling reads frames that the lag has not yet seen'
+SEQ_FLOW_NO_ZOOM = '--seq_flow cannot be combined with --seq_zoom: the zoom windows move the lattice from frame to frame'
+SEQ_FLOW_NO_PEOPLE = '--seq_flow cannot be combined with --seq_people: every track has maps of its own, and pooling per track is out of scope'
+SEQ_FLOW_SEARCH_NEEDS_SEQ_FLOW = '--seq_flow_search sets the search radius of --seq_flow: give --seq_flow N as well'
 SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
@@ -423,7 +435,8 @@ def predict_main(args):
     (predict.predict_sequence_people) also "tracks", one skeleton per person, and the line gains seq_people, seq_torso_ms and seq_people_sm_ms; with --seq_zoom
     (predict.predict_sequence_zoom) "zoom" and "track_zoom", the pictures show the skeleton tracked through the windows where the clip was zoomed, and the line
     gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms; with --sequence lag --seq_lag L the line gains seq_lag; with --seq_camera the document gains
-    "camera" per file and the line seq_camera, the search radius."""
+    "camera" per file and the line seq_camera, the search radius; with --seq_flow N the document gains "flow" per file and the line seq_flow
+    and seq_flow_search."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -450,6 +463,8 @@ def predict_main(args):
             else:
                 if args.seq_camera:
                     seq.update(camera=True, camera_search=predict.SEQ_CAMERA_SEARCH if args.seq_camera_search is None else args.seq_camera_search)
+                if args.seq_flow is not None:
+                    seq.update(flow=args.seq_flow, flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
                 results = predict.predict_sequence(eng, images, use_sm=args.use_sm, **seq)
         else:
             results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
@@ -473,6 +488,8 @@ def predict_main(args):
         line.update(seq_fit={'sigma': fit['sigma'].tolist(), 'rho': fit['rho'], 'loglik': fit['loglik'].tolist(), 'clamped': fit['clamped'].tolist()})
     if args.seq_camera:
         line.update(seq_camera=predict.SEQ_CAMERA_SEARCH if args.seq_camera_search is None else args.seq_camera_search)
+    if args.seq_flow is not None:
+        line.update(seq_flow=args.seq_flow, seq_flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
     if args.seq_people is not None:
         line.update(seq_people=args.seq_people, seq_torso_ms=timing['seq_torso_ms'], seq_people_sm_ms=timing['seq_people_sm_ms'])
     if args.seq_zoom:
@@ -816,13 +833,23 @@ EVAL_SCALE_RULES = (
     (lambda a: a.augm_antialias and not a.augm_affine, AUGM_ANTIALIAS_NEEDS_AUGM_AFFINE),
     (lambda a: a.augm_antialias and a.augm_scale is not None and a.augm_scale[0] < 0.25, AUGM_ANTIALIAS_SCALE_FLOOR),
 )
+# The rules of --seq_flow, walked behind EVAL_SCALE_RULES (a table of their own for the same reason).
+SEQ_FLOW_RULES = (
+    (lambda a: a.seq_flow_search is not None and a.seq_flow is None, SEQ_FLOW_SEARCH_NEEDS_SEQ_FLOW),
+    (lambda a: a.seq_flow is not None and not a.sequence, SEQ_FLOW_NEEDS_SEQUENCE),
+    (lambda a: a.seq_flow is not None and a.sequence == 'lag', SEQ_FLOW_NO_LAG),
+    (lambda a: a.seq_flow is not None and a.seq_zoom, SEQ_FLOW_NO_ZOOM),
+    (lambda a: a.seq_flow is not None and a.seq_people is not None, SEQ_FLOW_NO_PEOPLE),
+    (lambda a: a.seq_flow is not None and not 1 <= a.seq_flow <= 4, lambda a: '--seq_flow %d: 1 <= N <= 4' % a.seq_flow),
+    (lambda a: a.seq_flow_search is not None and not 1 <= a.seq_flow_search <= 16, lambda a: '--seq_flow_search %d: 1 <= D <= 16' % a.seq_flow_search),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES + EVAL_SCALE_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES + EVAL_SCALE_RULES + SEQ_FLOW_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

@@ -46,6 +46,32 @@ def camera_shifts(disp, carry=(0, 0), stride=8):
     return (o[1:] - o[:-1]).astype(np.int32), (int(last[0]), int(last[1]))
 
 
+SEQ_FLOW_SEARCH = 8                       # the search radius of Engine.frame_flow in fitted pixels, one heat-map cell a frame: an untuned placeholder
+SEQ_FLOW_MAX = 4                          # include/jcm.h: N of jcm_hm_flow_pool
+
+
+def _flow_n(N):
+    if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 1 <= int(N) <= SEQ_FLOW_MAX:
+        raise ValueError('flow must be the neighbours on either side, an integer in 1..4, got %r' % (N,))
+    return int(N)
+
+
+def flow_refs(T, N):
+    """The reference frames of Engine.frame_flow in the layout Engine.hm_flow_pool reads: int32 [T,2N], slot 2(n-1) = t - n and
+    slot 2(n-1) + 1 = t + n for n = 1 .. N, -1 where that frame is outside the clip."""
+    T, N = int(T), _flow_n(N)
+    if T < 1:
+        raise ValueError('T must be >= 1, got %r' % (T,))
+    t, n = np.arange(T, dtype=np.int64)[:, None], np.arange(1, N + 1, dtype=np.int64)[None, :]
+    ref = np.stack([t - n, t + n], axis=2).reshape(T, 2 * N)
+    return np.where((ref < 0) | (ref >= T), -1, ref).astype(np.int32)
+
+
+def flow_weights(N):
+    """The pooling weights of Engine.hm_flow_pool, float64 [N+1]: uniform -- the frame and every neighbour count alike.  An untuned placeholder."""
+    return np.ones(_flow_n(N) + 1, np.float64)
+
+
 def _seq_sigma(sigma, K=None):
     sg = np.asarray(sigma, np.float64).reshape(-1)
     if sg.size == 0 or not np.all(np.isfinite(sg)) or np.any(sg <= 0):

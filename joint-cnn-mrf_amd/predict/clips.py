@@ -21,12 +21,17 @@ Engine.seq_smooth_lag, and LagTracker is its online form: a frame's dict becomes
 
 Camera pans: predict_sequence(camera=True) and SequenceTracker(camera=True) estimate the camera's translation between consecutive
 fitted frames on the device (Engine.frame_shift), turn it into whole-cell lattice shifts (motion.camera_shifts) and run the filter or Viterbi with
-shift=, so that the motion kernel is centred on where the camera's motion takes a joint, not on where it was."""
+shift=, so that the motion kernel is centred on where the camera's motion takes a joint, not on where it was.
+
+Local motion: predict_sequence(flow=N) estimates one displacement per heat-map cell between every frame and the N frames before
+and after it (Engine.frame_flow), warps those frames' maps onto the frame and pools them with its own (Engine.hm_flow_pool); the chosen mode then
+runs on the pooled maps, which are maps like any other."""
 import numpy as np
 import torch
 
 from ..evaluation import fit_to_source, window_to_source
-from ..motion import SEQ_CAMERA_SEARCH, SEQ_EXCLUDE, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, camera_shifts, seq_fit
+from ..motion import (SEQ_CAMERA_SEARCH, SEQ_EXCLUDE, SEQ_FLOW_MAX, SEQ_FLOW_SEARCH, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, camera_shifts, flow_refs,
+                      flow_weights, seq_fit)
 from .images import FIT_SIDE_MAX, FRAME, STRIDE, ZOOM_TORSO_JOINTS, ZOOM_TORSO_PIXELS, DeviceTimer, _coords_to_points, _upload, predict_images, second_pass, zoom_entry
 
 
@@ -83,11 +88,12 @@ def _seq_call(engine, mode, hm, sigma, rho, radius, lag=None, **kw):
 SEQ_CAMERA_MODES = ('filter', 'viterbi')      # the scans that have a moving form
 
 
-def _camera(engine, results, search, prev=None, carry=(0, 0)):
+def _camera(engine, results, search, prev=None, carry=(0, 0), x=None):
     """The camera's motion over the frames of `results` (dicts of pass 1 with the fitted frames kept): one Engine.frame_shift call on the stacked
-    frames with the clip's content rectangle, prev the last fitted frame of the push before (None at a clip's start), then motion.camera_shifts
-    from `carry`.  Every dict gains 'camera'.  Returns (shift int32 [T,2], the last fitted frame, the new carry)."""
-    x = _stacked(results, 'frame')
+    frames (x, when the caller has stacked them already) with the clip's content rectangle, prev the last fitted frame of the push before (None at
+    a clip's start), then motion.camera_shifts from `carry`.  Every dict gains 'camera'.  Returns (shift int32 [T,2], the last fitted frame, the
+    new carry)."""
+    x = _stacked(results, 'frame') if x is None else x
     cam = engine.frame_shift(x, _geom(results)[0, :4], search=search, prev=prev)
     disp, sad = cam['disp'].cpu().numpy(), cam['sad'].cpu().numpy()
     shift, carry = camera_shifts(disp, carry, STRIDE)
@@ -102,8 +108,43 @@ def _check_camera_search(camera, camera_search):
     return bool(camera)
 
 
+SEQ_FLOW_MODES = ('filter', 'viterbi', 'marginal')      # every offline mode: the pooling reads the frames after a frame as well as those before
+
+
+def _check_flow(flow, flow_search, flow_weights_):
+    """flow = 0 (off) or the neighbours on either side, 1..4 -> (N, D, the N + 1 pooling weights or None)."""
+    if isinstance(flow, bool) or not isinstance(flow, (int, np.integer)) or not 0 <= int(flow) <= SEQ_FLOW_MAX:
+        raise ValueError('flow must be 0 (off) or the neighbouring frames on either side, 1..4, got %r' % (flow,))
+    N = int(flow)
+    if not N:      # off: flow_search is the radius of flow = N >= 1 and is not looked at; weights given for no pooling are a mistake
+        if flow_weights_ is not None:
+            raise ValueError('flow_weights belongs to flow = N >= 1 (flow is %r)' % (flow,))
+        return 0, None, None
+    if not 1 <= int(flow_search) <= 16:
+        raise ValueError('flow_search must be in 1..16, got %r' % (flow_search,))
+    w = flow_weights(N) if flow_weights_ is None else np.asarray(flow_weights_, np.float64).reshape(-1)
+    if w.size != N + 1 or not np.isfinite(w).all() or not w[0] > 0 or (w < 0).any():
+        raise ValueError('flow_weights must be %d finite values, the first > 0 and the others >= 0 (flow=%d), got %r' % (N + 1, N, flow_weights_))
+    return N, int(flow_search), w
+
+
+def _flow_pool(engine, results, hm, x, N, search, weights):
+    """The maps of a clip pooled along its local motion: one Engine.frame_flow call on the stacked fitted frames x with
+    motion.flow_refs and the clip's content rectangle, one Engine.hm_flow_pool on the stacked maps hm.  Every dict gains 'flow' -- the per-frame
+    arg-max of the pooled maps through fit_to_source -- and its 'maps' 'pooled'.  Returns the pooled maps."""
+    T = hm.shape[0]
+    flow = engine.frame_flow(x, _geom(results)[0, :4], flow_refs(T, N), search=search)['flow']
+    pooled = engine.hm_flow_pool(hm, flow, weights)
+    pts, inside = fit_to_source(_coords_to_points(engine.argmax_coords(pooled)), _geom(results))
+    for t, r in enumerate(results):
+        r['flow'] = {'n': N, 'search': search, 'points': pts[t], 'inside': inside[t]}
+        r['maps']['pooled'] = pooled[t]
+    return pooled
+
+
 def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
-                     keep_maps=False, fit_iters=0, lag=None, camera=False, camera_search=SEQ_CAMERA_SEARCH, **kw):
+                     keep_maps=False, fit_iters=0, lag=None, camera=False, camera_search=SEQ_CAMERA_SEARCH, flow=0, flow_search=SEQ_FLOW_SEARCH,
+                     flow_weights=None, **kw):
     """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
     geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
     [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal), Engine.seq_viterbi (mode 'viterbi', the most probable
@@ -122,6 +163,14 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
     Every frame's dict gains 'camera': {'disp': (dy, dx) in fitted-frame pixels, 'shift': (sy, sx) in cells, 'sad': (best, zero), the sums of
     absolute luma differences at disp and at no displacement -- there is no cut detection, a caller judges by the two}.  Global translation
     only; camera_search = 8 is an untuned placeholder like sigma and rho.
+    flow = N in 1..4 (modes 'filter', 'viterbi' and 'marginal', with fit_iters and with camera=True too -- the two are independent,
+    and the frames are stacked once for both; mode 'lag' raises ValueError: two-sided pooling reads frames the lag has not yet seen): the fitted
+    frames are kept and stacked, ONE Engine.frame_flow call with motion.flow_refs(T, N), the clip's content rectangle and search radius flow_search
+    (1..16 pixels) gives one displacement per heat-map cell against the N frames before and after every frame, ONE Engine.hm_flow_pool warps those
+    frames' maps onto the frame and pools them with its own under flow_weights (N + 1 values, default motion.flow_weights(N): uniform), and the
+    fit and the mode run on the pooled maps.  Every frame's dict gains 'flow': {'n', 'search', 'points' float64 [K,2], 'inside' bool [K]: the
+    frame's own arg-max of the pooled maps}, and 'maps' gains 'pooled'.  Block matching on luma, whole pixels, no occlusion reasoning, no gating
+    of a neighbour by its match; flow_search = 8 and the uniform weights are untuned placeholders.  flow = 0 changes nothing.
     'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
     the defaults SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what the track buys with trained weights has not been measured.
     One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
@@ -144,13 +193,21 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
         if int(fit_iters) != 0:
             raise ValueError('camera=True has no fit: fit_iters=%r needs the smoother, which has no moving form' % (fit_iters,))
         kw = dict(kw, keep_frames=True)
+    n_flow, flow_search, flow_w = _check_flow(flow, flow_search, flow_weights)
+    if n_flow:
+        if mode not in SEQ_FLOW_MODES:
+            raise ValueError("flow=%d: mode must be 'filter', 'viterbi' or 'marginal', got %r (two-sided pooling reads frames the lag has not yet seen)" % (n_flow, mode))
+        kw = dict(kw, keep_frames=True)
     results = _first_pass(engine, frames, use_sm=use_sm, batch_size=batch_size, **kw)
     with torch.cuda.stream(engine._stream):
         hm = _stacked(results, 'sm' if use_sm else 'pd')
+        x = _stacked(results, 'frame') if camera or n_flow else None      # stacked once for both
+        if n_flow:
+            hm = _flow_pool(engine, results, hm, x, n_flow, flow_search, flow_w)
         fit = seq_fit(engine, hm, sigma, rho, iters=int(fit_iters)) if int(fit_iters) else None
         if fit is not None:
             sigma, rho = fit['sigma'], fit['rho']
-        moving = {'shift': _camera(engine, results, int(camera_search))[0]} if camera else {}
+        moving = {'shift': _camera(engine, results, int(camera_search), x=x)[0]} if camera else {}
         seq = _seq_call(engine, mode, hm, sigma, rho, radius, lag=lag, **moving)
         geom = _geom(results)
         for r, track in zip(results, _track_entries(seq, mode, lambda pts: fit_to_source(pts, geom))):
@@ -224,7 +281,7 @@ def zoom_window_track(points, inside, torso, geom, frame=FRAME):
 
 
 def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, radius=None, batch_size=16, people=1,
-                          keep_maps=False, fit_iters=0, pad=0, timing=None, camera=False, **kw):
+                          keep_maps=False, fit_iters=0, pad=0, timing=None, camera=False, flow=0, **kw):
     """The frames of ONE clip with one person in it, tracked a second time at the scale the tower was trained on; frames as
     for predict_sequence.
       1. predict_sequence(frames, mode, ..., torso_prob=True): the first pass and its 'track'; the torso track comes from the frames'
@@ -242,9 +299,12 @@ def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso
     is no 'track_zoom'.  timing also receives 'zoom_fit_ms', 'zoom_forward_ms' and 'seq_zoom_pitch'.
     The modes are 'filter' and 'viterbi': mode='marginal' and fit_iters raise ValueError (jcm_seq_smooth has no moving form), people != 1 too.
     One pitch per clip is a stated limit; torso_sigma, sigma and rho are untuned placeholders, and what this buys with trained weights has not
-    been measured.  camera=True raises ValueError: the windows already move with the person, and a camera estimate under them is out of scope."""
+    been measured.  camera=True raises ValueError: the windows already move with the person, and a camera estimate under them is out of scope;
+    flow != 0 raises ValueError too: the windows move the lattice from frame to frame, and flow under moving windows is out of scope."""
     if camera:
         raise ValueError('predict_sequence_zoom has no camera estimate: its windows follow the person already (camera=True belongs to predict_sequence)')
+    if flow:
+        raise ValueError('predict_sequence_zoom has no flow pooling: its windows move the lattice from frame to frame (flow=%r belongs to predict_sequence)' % (flow,))
     if mode not in SEQ_ZOOM_MODES:
         raise ValueError("mode must be 'filter' or 'viterbi', got %r (the smoother has no moving form: mode 'marginal' is not offered with zoomed clips)" % (mode,))
     if int(fit_iters) != 0:
@@ -430,7 +490,7 @@ def _check_people(people, zoom):
 
 
 def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, exclude=SEQ_EXCLUDE,
-                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, camera=False, **kw):
+                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, camera=False, flow=0, **kw):
     """The frames of ONE clip with up to people = M (1..4) persons in it; frames as for predict_sequence.  On the device:
       1. predict_images(frames, use_sm=True, people=1, keep_maps=True, torso_prob=True, **kw): per frame the part-detector maps and the torso map
          spatial_softmax(E);
@@ -449,9 +509,11 @@ def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SI
     timing also receives 'seq_torso_ms' and 'seq_people_sm_ms', the device times of steps 2 and 3.  'maps' is kept only with keep_maps.
     exclude (SEQ_EXCLUDE = 4 cells), torso_sigma (SEQ_TORSO_SIGMA = 1.5), sigma, rho and people_threshold are untuned placeholders -- no
     consecutive-frame data and no trained weights are at hand -- and what this buys with trained weights has not been measured.  zoom=True
-    and camera=True raise ValueError (the torso passes have no moving form)."""
+    and camera=True raise ValueError (the torso passes have no moving form), flow != 0 too (pooling per track is out of scope)."""
     if camera:
         raise ValueError('predict_sequence_people has no camera estimate: the torso passes have no moving form (camera=True belongs to predict_sequence)')
+    if flow:
+        raise ValueError('predict_sequence_people has no flow pooling: every track has maps of its own (flow=%r belongs to predict_sequence)' % (flow,))
     if mode not in ('filter', 'viterbi'):
         raise ValueError("mode must be 'filter' or 'viterbi', got %r (the torso tracks have the filter and Viterbi only)" % (mode,))
     _check_people(people, zoom)
