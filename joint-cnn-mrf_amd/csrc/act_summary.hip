@@ -6,7 +6,7 @@
 // repeated call returns the same bytes.  A work group owns kActChunk consecutive elements of one slice: the grid follows the tensor.
 #include <cstdint>
 
-#include "ctx.h"
+#include "entry.h"
 #include "summary_stats.h"
 
 namespace jcm {
@@ -127,16 +127,13 @@ int jcm_act_summary(jcm_handle h, const char* scope, const float* z, int B, int 
     if (c->dry) return (int)JCM_OK;
     auto* cnt = reinterpret_cast<unsigned long long*>(counts);
     HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_groups * (3 + JCM_HIST_BUCKETS) * sizeof(int64_t), c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const dim3 grid((unsigned)nck, (unsigned)n_groups);
-    if (vec) hipLaunchKernelGGL(act_summary_kernel<true>, grid, dim3(kStatsThreads), 0, c->stream, a, c->hist_limits, parts, cnt);
-    else hipLaunchKernelGGL(act_summary_kernel<false>, grid, dim3(kStatsThreads), 0, c->stream, a, c->hist_limits, parts, cnt);
-    hipLaunchKernelGGL(stats_fold_kernel, dim3(n_groups), dim3(kStatsThreads), 0, c->stream, parts, static_cast<const int*>(nullptr), (int)nck, stats, cnt);
-    const hipError_t e = hipGetLastError();
-    prof_end(c, std::string(scope) + "/act_summary", e0, e1, e == hipSuccess);
-    HIP_TRY(e);
-    return (int)JCM_OK;
+    return timed_launch(c, std::string(scope) + "/act_summary", [&] {
+      const dim3 grid((unsigned)nck, (unsigned)n_groups);
+      if (vec) hipLaunchKernelGGL(act_summary_kernel<true>, grid, dim3(kStatsThreads), 0, c->stream, a, c->hist_limits, parts, cnt);
+      else hipLaunchKernelGGL(act_summary_kernel<false>, grid, dim3(kStatsThreads), 0, c->stream, a, c->hist_limits, parts, cnt);
+      hipLaunchKernelGGL(stats_fold_kernel, dim3(n_groups), dim3(kStatsThreads), 0, c->stream, parts, static_cast<const int*>(nullptr), (int)nck, stats, cnt);
+      return hipGetLastError();
+    });
   });
 }
 

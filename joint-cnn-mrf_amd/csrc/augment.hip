@@ -4,8 +4,8 @@
 // The semantics are DESIGN.md 4.7 (a restatement of the TF-1.x ops, float32 in the order written; tests/augment_ref.py).
 // Three launches: the per-image channel sums of the brightened image (partials, no atomics), the image gather (crop taps ->
 // rotated samples -> source taps, the colour steps applied per source tap) and one work group per (image, heat-map channel).
+#include "entry.h"
 #include "hm_flip.h"
-#include "kernels.h"
 #include "u8.h"
 
 namespace jcm {
@@ -228,8 +228,7 @@ __global__ __launch_bounds__(kAugHmThreads) void aug_hm_kernel(const float* __re
   for (int i = t; i < hw; i += kAugHmThreads) ob[(size_t)i * 10] = ob[(size_t)i * 10] / tot;     // this thread's own stores
 }
 
-}  // namespace
-
+// the scratch of a batch: the per-image channel sums of the brightened image
 size_t augment_scratch_doubles(int B) { return (size_t)B * kAugParts * 3; }
 
 template <class Src, class PixT>
@@ -242,13 +241,14 @@ void augment_launch(const PixT* x, const float* y, const float* params, int B, i
   hipLaunchKernelGGL(aug_hm_kernel<Src>, dim3(10, B), dim3(kAugHmThreads), 0, st, y, params, hh, hw, y_out, src);
 }
 
+// x [B,H,W,3], y [B,hh,hw,10], params [B,6] = (flip, delta, factor, angle, rh, rw), all device fp32; three launches on `st`
 hipError_t augment_train(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch,
                          float* x_out, float* y_out, hipStream_t st) {
   augment_launch(x, y, params, B, H, W, hh, hw, scratch, x_out, y_out, SrcDirect{}, st);
   return hipGetLastError();
 }
 
-namespace {
+// augment_train with image idx[b] of (x_all, y_all) as the source of output image b (kGatherMax images a launch); same kernels, same arithmetic
 template <class PixT>
 hipError_t augment_indexed(const PixT* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
                            double* scratch, float* x_out, float* y_out, hipStream_t st) {
@@ -261,8 +261,7 @@ hipError_t augment_indexed(const PixT* x_all, const float* y_all, const int* idx
   }
   return hipGetLastError();
 }
-}  // namespace
-
+// ... from a float and from a byte image array (every tap converted by u8_to_f32; sums in the same order: the same bits), under the names an error carries
 hipError_t augment_train_indexed(const float* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
                                  double* scratch, float* x_out, float* y_out, hipStream_t st) {
   return augment_indexed(x_all, y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, st);
@@ -272,4 +271,62 @@ hipError_t augment_train_indexed_u8(const uint8_t* x_all, const float* y_all, co
   return augment_indexed(x_all, y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, st);
 }
 
+}  // namespace
+
 }  // namespace jcm
+
+using namespace jcm;
+
+extern "C" {
+
+int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
+                      int hh, int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  if (!x || !y || !params || !x_out || !y_out) return fail(JCM_ERR_ARG, "augment_train: null pointer");
+  if (B < 1 || B > 65535 || H < 2 || W < 2 || hh < 2 || hw < 2 || (int64_t)H * W * 3 >= (int64_t)1 << 30 || (int64_t)hh * hw * 10 >= (int64_t)1 << 30)
+    return fail(JCM_ERR_ARG, "augment_train: bad sizes (B in [1, 65535], H, W, h, w >= 2)");
+  if (h->K != 9) return fail(JCM_ERR_ARG, "augment_train: the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
+  const size_t nx = (size_t)B * H * W * 3 * sizeof(float), ny = (size_t)B * hh * hw * 10 * sizeof(float), np = (size_t)B * 6 * sizeof(float);
+  if (ranges_overlap(x_out, nx, x, nx) || ranges_overlap(x_out, nx, y, ny) || ranges_overlap(x_out, nx, params, np) || ranges_overlap(y_out, ny, x, nx) ||
+      ranges_overlap(y_out, ny, y, ny) || ranges_overlap(y_out, ny, params, np) || ranges_overlap(x_out, nx, y_out, ny))
+    return fail(JCM_ERR_ARG, "augment_train: x_out / y_out alias an input or each other");
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  return with_arena(c, [&] {
+    double* scratch = arena_alloc<double>(c, augment_scratch_doubles(B));
+    if (c->dry) return (int)JCM_OK;
+    HIP_TRY(augment_train(x, y, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
+    return (int)JCM_OK;
+  });
+}
+
+static int augment_indexed_entry(jcm_handle h, const char* who, const void* x_all, bool x_u8, const float* y_all, int64_t N, const int32_t* idx,
+                                 const float* params, int B, int H, int W, int hh, int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  const std::string w(who);
+  if (!params) return fail(JCM_ERR_ARG, w + ": null pointer");
+  if (h->K != 9)
+    return fail(JCM_ERR_ARG, w + ": the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
+  JCM_TRY(check_indexed(who, x_all, x_u8 ? 1 : sizeof(float), y_all, N, idx, params, B, H, W, hh, hw, 10, 2, x_out, y_out));
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  return with_arena(c, [&] {
+    double* scratch = arena_alloc<double>(c, augment_scratch_doubles(B));
+    if (c->dry) return (int)JCM_OK;
+    if (x_u8) HIP_TRY(augment_train_indexed_u8(static_cast<const uint8_t*>(x_all), y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
+    else HIP_TRY(augment_train_indexed(static_cast<const float*>(x_all), y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
+    return (int)JCM_OK;
+  });
+}
+int jcm_augment_train_indexed(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
+                              int H, int W, int hh, int hw, float* x_out, float* y_out) {
+  return augment_indexed_entry(h, "augment_train_indexed", x_all, false, y_all, N, idx, params, B, H, W, hh, hw, x_out, y_out);
+}
+int jcm_augment_train_indexed_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
+                                 int H, int W, int hh, int hw, float* x_out, float* y_out) {
+  return augment_indexed_entry(h, "augment_train_indexed_u8", x_all, true, y_all, N, idx, params, B, H, W, hh, hw, x_out, y_out);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Internal context of libjcm shared by the translation units behind include/jcm.h
-// (jcm_api.hip: entry points, parameter store, call order, arena; conv_route.hip: how one conv layer runs; derived.hip: weight packings; pd_tower.hip: inference graph;
+// (jcm_api.hip: handle, parameter store, options, layer and tower entry points, call order, arena; entry.h: the launch scaffold of the entry points beside their kernels; conv_route.hip: how one conv layer runs; derived.hip: weight packings; pd_tower.hip: inference graph;
 // jcm_train.hip: training step; train_state.hip: training state, optimizer and its entry points, both on train.h).  Not part of the ABI.
 #pragma once
 #include "../../include/jcm.h"

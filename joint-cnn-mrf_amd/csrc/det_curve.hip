@@ -8,7 +8,7 @@
 // images does not matter.  Nothing is read back and nothing but the radii (kernel arguments) comes from the host.
 #include <string>
 
-#include "ctx.h"
+#include "entry.h"
 
 namespace jcm {
 
@@ -145,13 +145,7 @@ int jcm_det_curve(jcm_handle h, const int32_t* pred_coords, const float* y, int 
   if (!pred_coords || !y || !radii) return fail(JCM_ERR_ARG, "det_curve: null pointer (pred_coords, y and radii are required)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
-  hipEvent_t e0, e1;
-  JCM_TRY(prof_begin(c, &e0, &e1));
-  const hipError_t launch = det_curve(pred_coords, y, B, HH * WW, WW, K, C, radii, R, true_coords, norm_dist, hits, c->stream);
-  prof_end(c, "det_curve", e0, e1, launch == hipSuccess);
-  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("det_curve: ") + hipGetErrorString(launch));
-  return JCM_OK;
+  return timed_launch(h, "det_curve", [&] { return det_curve(pred_coords, y, B, HH * WW, WW, K, C, radii, R, true_coords, norm_dist, hits, h->stream); });
 }
 
 }  // extern "C"

@@ -18,9 +18,10 @@
 // has one and `pad` elsewhere.  A staged row outside the image is filled with `pad` before any offset is formed from it; the in-image part of a
 // staged row is [vb_lo, vb_hi) of its segment bytes and offsets are formed from its first in-image column only.  The strips, the ring and the
 // groups of rows are the window's, so the work is the window's whatever the image's size.  The FitBatch instantiation is the code it was.
+#include <string>
 #include <type_traits>
 
-#include "kernels.h"
+#include "entry.h"
 #include "u8.h"
 
 namespace jcm {
@@ -309,7 +310,9 @@ int fit_lds_bytes(int R, int C, int TX) {
   return (R * kFitTW * C + kFitTW * TX + kFitWyCap + raw) * (int)sizeof(double) + kFitStage + (2 * kFitTW + 4 * kFitGMax + 8 * kFitTW) * (int)sizeof(int);
 }
 
-// one launch per Batch-ful of desc rows: (offset, h, w) of an image, or (offset, h, w, wy0, wx0, wh, ww) of a window
+// one launch per Batch-ful of desc rows: (offset, h, w) of an image, or (offset, h, w, wy0, wx0, wh, ww) of a window.  desc is a HOST array, read
+// before the call returns, every entry checked by the entry point: 1 <= C <= 4, sizes, bounds, a reduction of at most 32 per axis (of the window,
+// whose image sides are <= 2^24 and which shares a pixel with its image) -> out [B,OH,OW,C] uint8 or (out_f32) float32 = u8_to_f32(byte).
 template <class Batch>
 hipError_t fit_launch(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
                       hipStream_t st) {
@@ -358,16 +361,93 @@ hipError_t fit_launch(const uint8_t* src, int64_t src_bytes, const int64_t* desc
   return hipGetLastError();
 }
 
+// what jcm_fit_images and jcm_fit_windows check alike (`who` names the entry point in the message): pointers, the frame, the size of out
+int fit_check_frame(const std::string& who, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad,
+                    const void* out) {
+  if (!src || !desc || !out) return fail(JCM_ERR_ARG, who + ": null pointer (src, desc and out are required, geom may be NULL)");
+  if (B < 1 || C < 1 || C > 4 || OH < 1 || OH > 4096 || OW < 1 || OW > 4096 || pad < 0 || pad > 255 || src_bytes < 1)
+    return fail(JCM_ERR_ARG, who + ": bad sizes (B >= 1, C in 1..4, OH and OW in 1..4096, pad in 0..255)");
+  if ((int64_t)B * OH * OW * C >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, who + ": B * OH * OW * C >= 2^31");
+  return JCM_OK;
+}
+// fh x fw, the size the filter sees (an image, or a window), against the size and reduction limits
+int fit_check_size(const std::string& who, int64_t fh, int64_t fw, int OH, int OW) {
+  if (fh < 1 || fh > 16384 || fw < 1 || fw > 16384)
+    return fail(JCM_ERR_ARG, who + " is " + std::to_string(fh) + " x " + std::to_string(fw) + "; both sides lie in 1..16384");
+  const FitGeom g = fit_geometry((int)fh, (int)fw, OH, OW);
+  if (fh > 32 * (int64_t)g.ch || fw > 32 * (int64_t)g.cw)
+    return fail(JCM_ERR_ARG, who + ", " + std::to_string(fh) + " x " + std::to_string(fw) + " into " + std::to_string(g.ch) + " x " + std::to_string(g.cw) +
+                                 ": a reduction above 32 (at most 66 taps per axis)");
+  return JCM_OK;
+}
+int fit_check_overlap(const std::string& who, const uint8_t* src, int64_t src_bytes, const void* out, size_t no) {
+  if (ranges_overlap(src, (size_t)src_bytes, out, no)) return fail(JCM_ERR_ARG, who + ": out overlaps src");
+  return JCM_OK;
+}
+// geom[i] = the content rectangle of desc row i (`stride` entries a row, the filter's size at entries at, at + 1)
+void fit_write_geom(const int64_t* desc, int B, int stride, int at, int OH, int OW, int32_t* geom) {
+  for (int b = 0; b < B; ++b) {
+    const FitGeom g = fit_geometry((int)desc[b * (int64_t)stride + at], (int)desc[b * (int64_t)stride + at + 1], OH, OW);
+    geom[b * (int64_t)4] = g.y0;
+    geom[b * (int64_t)4 + 1] = g.x0;
+    geom[b * (int64_t)4 + 2] = g.ch;
+    geom[b * (int64_t)4 + 3] = g.cw;
+  }
+}
+
 }  // namespace
 
-hipError_t fit_images(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
-                      hipStream_t st) {
-  return fit_launch<FitBatch>(src, src_bytes, desc, B, C, OH, OW, pad, out_f32, out, st);
-}
-
-hipError_t fit_windows(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, bool out_f32, void* out,
-                       hipStream_t st) {
-  return fit_launch<FitWinBatch>(src, src_bytes, desc, NW, C, OH, OW, pad, out_f32, out, st);
-}
-
 }  // namespace jcm
+
+using namespace jcm;
+
+extern "C" {
+
+int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, int out_f32,
+                   void* out, int32_t* geom) {
+  JCM_TRY(check(h, false));
+  JCM_TRY(fit_check_frame("fit_images", src, src_bytes, desc, B, C, OH, OW, pad, out));
+  for (int b = 0; b < B; ++b) {
+    const int64_t off = desc[b * (int64_t)3], hb = desc[b * (int64_t)3 + 1], wb = desc[b * (int64_t)3 + 2];
+    const std::string who = "fit_images: image " + std::to_string(b);
+    if (hb < 1 || hb > 16384 || wb < 1 || wb > 16384)
+      return fail(JCM_ERR_ARG, who + " is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..16384");
+    if (off < 0 || off > src_bytes || hb * wb * C > src_bytes - off)
+      return fail(JCM_ERR_ARG, who + " (" + std::to_string(hb * wb * C) + " bytes at offset " + std::to_string(off) + ") does not lie inside the " +
+                                   std::to_string(src_bytes) + " bytes of src");
+    JCM_TRY(fit_check_size(who, hb, wb, OH, OW));
+  }
+  JCM_TRY(fit_check_overlap("fit_images", src, src_bytes, out, (size_t)B * OH * OW * C * (out_f32 ? sizeof(float) : 1)));
+  if (geom) fit_write_geom(desc, B, 3, 1, OH, OW, geom);
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  return timed_launch(h, "fit_images", [&] { return fit_launch<FitBatch>(src, src_bytes, desc, B, C, OH, OW, pad, out_f32 != 0, out, h->stream); });
+}
+
+int jcm_fit_windows(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, int out_f32,
+                    void* out, int32_t* geom) {
+  JCM_TRY(check(h, false));
+  JCM_TRY(fit_check_frame("fit_windows", src, src_bytes, desc, NW, C, OH, OW, pad, out));
+  constexpr int64_t kSide = (int64_t)1 << 24;      // image sides: rows, columns and their sums with a window's stay far inside int
+  for (int i = 0; i < NW; ++i) {
+    const int64_t* d = desc + i * (int64_t)7;
+    const int64_t off = d[0], hb = d[1], wb = d[2], wy0 = d[3], wx0 = d[4], wh = d[5], ww = d[6];
+    const std::string who = "fit_windows: window " + std::to_string(i);
+    if (hb < 1 || hb > kSide || wb < 1 || wb > kSide)
+      return fail(JCM_ERR_ARG, who + ": its image is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..2^24");
+    if (off < 0 || off > src_bytes || hb * wb * C > src_bytes - off)
+      return fail(JCM_ERR_ARG, who + ": its image (" + std::to_string(hb * wb * C) + " bytes at offset " + std::to_string(off) +
+                                   ") does not lie inside the " + std::to_string(src_bytes) + " bytes of src");
+    JCM_TRY(fit_check_size(who, wh, ww, OH, OW));
+    if (wy0 >= hb || wy0 + wh <= 0 || wx0 >= wb || wx0 + ww <= 0)      // wh, ww <= 16384: the sums cannot overflow unless the window is disjoint anyway
+      return fail(JCM_ERR_ARG, who + ", rows " + std::to_string(wy0) + ".. and columns " + std::to_string(wx0) + ".., " + std::to_string(wh) + " x " +
+                                   std::to_string(ww) + ", shares no pixel with its " + std::to_string(hb) + " x " + std::to_string(wb) + " image");
+  }
+  JCM_TRY(fit_check_overlap("fit_windows", src, src_bytes, out, (size_t)NW * OH * OW * C * (out_f32 ? sizeof(float) : 1)));
+  if (geom) fit_write_geom(desc, NW, 7, 5, OH, OW, geom);
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  return timed_launch(h, "fit_windows", [&] { return fit_launch<FitWinBatch>(src, src_bytes, desc, NW, C, OH, OW, pad, out_f32 != 0, out, h->stream); });
+}
+
+}  // extern "C"

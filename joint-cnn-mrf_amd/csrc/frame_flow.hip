@@ -13,7 +13,7 @@
 #include <cmath>
 #include <string>
 
-#include "seq_entry.h"
+#include "entry.h"
 
 namespace jcm {
 
@@ -244,24 +244,14 @@ int jcm_frame_flow(jcm_handle h, const uint8_t* x, int T, int H, int W, int y0, 
   if (R < 1 || R > kFrameFlowMaxR) return fail(JCM_ERR_ARG, w + ": R = " + std::to_string(R) + " reference frames per frame; 1 <= R <= 8");
   if (H % 8 || W % 8 || H > kFrameFlowMaxSide || W > kFrameFlowMaxSide)
     return fail(JCM_ERR_ARG, w + ": a frame of " + std::to_string(H) + " x " + std::to_string(W) + "; H and W are multiples of 8 (whole heat-map cells) and <= 4096");
-  if (y0 < 0 || x0 < 0 || ch < 1 || cw < 1 || y0 > H - ch || x0 > W - cw)
-    return fail(JCM_ERR_ARG, w + ": the rectangle (" + std::to_string(y0) + ", " + std::to_string(x0) + ", " + std::to_string(ch) + ", " + std::to_string(cw) +
-                                 ") is not inside the frame of " + std::to_string(H) + " x " + std::to_string(W));
+  JCM_TRY(check_rectangle(w, H, W, y0, x0, ch, cw));
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
   const size_t nL = (size_t)T * ch * cw;
   JCM_TRY(workspace_or_refuse(c, w, (double)nL * 2.0 + 8192.0, "luma planes", 1, T));
-  return with_arena(c, [&] {
-    uint16_t* L = arena_alloc<uint16_t>(c, nL);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const hipError_t e = frame_flow(x, T, H, W, y0, x0, ch, cw, D, ref, R, L, flow, sad, c->stream);
-    prof_end(c, w, e0, e1, e == hipSuccess);
-    if (e != hipSuccess) return fail(JCM_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return (int)JCM_OK;
-  });
+  uint16_t* L = nullptr;
+  return arena_launch(c, w, [&] { L = arena_alloc<uint16_t>(c, nL); }, [&] { return frame_flow(x, T, H, W, y0, x0, ch, cw, D, ref, R, L, flow, sad, c->stream); });
 }
 
 int jcm_hm_flow_pool(jcm_handle h, const float* hm, int T, int HH, int WW, int K, const int32_t* flow, int N, const double* wts, float* out) {
@@ -278,16 +268,10 @@ int jcm_hm_flow_pool(jcm_handle h, const float* hm, int T, int HH, int WW, int K
     if (!std::isfinite(wts[i]) || wts[i] < 0.0 || (i == 0 && !(wts[0] > 0.0)))
       return fail(JCM_ERR_ARG, w + ": w[" + std::to_string(i) + "] = " + std::to_string(wts[i]) + "; w[0] > 0, the others >= 0, all finite");
   const size_t n = (size_t)T * HH * WW * K;
-  if (out < hm + n && hm < out + n) return fail(JCM_ERR_ARG, w + ": out overlaps hm (a frame's value reads its neighbours' maps)");
+  if (ranges_overlap(hm, n * sizeof(float), out, n * sizeof(float))) return fail(JCM_ERR_ARG, w + ": out overlaps hm (a frame's value reads its neighbours' maps)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
-  hipEvent_t e0, e1;
-  JCM_TRY(prof_begin(c, &e0, &e1));
-  const hipError_t e = hm_flow_pool(hm, T, HH, WW, K, flow, N, wts, out, c->stream);
-  prof_end(c, w, e0, e1, e == hipSuccess);
-  if (e != hipSuccess) return fail(JCM_ERR_HIP, w + ": " + hipGetErrorString(e));
-  return JCM_OK;
+  return timed_launch(h, w, [&] { return hm_flow_pool(hm, T, HH, WW, K, flow, N, wts, out, h->stream); });
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 // entry point).  The slots the groups add into are uint64.
 #include <string>
 
-#include "seq_entry.h"
+#include "entry.h"
 
 namespace jcm {
 
@@ -303,9 +303,7 @@ int jcm_frame_shift(jcm_handle h, const uint8_t* x, int T, int H, int W, int y0,
     return fail(JCM_ERR_ARG, w + ": a frame of " + std::to_string(H) + " x " + std::to_string(W) + "; H, W <= 4096 (seven rows of the window are staged in LDS)");
   if ((int64_t)H * W * 1020 >= ((int64_t)1 << 32))
     return fail(JCM_ERR_ARG, w + ": a frame of " + std::to_string(H) + " x " + std::to_string(W) + "; H * W * 1020 < 2^32 (a candidate's sum is held in 32 bits)");
-  if (y0 < 0 || x0 < 0 || ch < 1 || cw < 1 || y0 > H - ch || x0 > W - cw)
-    return fail(JCM_ERR_ARG, w + ": the rectangle (" + std::to_string(y0) + ", " + std::to_string(x0) + ", " + std::to_string(ch) + ", " + std::to_string(cw) +
-                                 ") is not inside the frame of " + std::to_string(H) + " x " + std::to_string(W));
+  JCM_TRY(check_rectangle(w, H, W, y0, x0, ch, cw));
   if (ch < 8 * D + 7 || cw < 8 * D + 7)
     return fail(JCM_ERR_ARG, w + ": a rectangle of " + std::to_string(ch) + " x " + std::to_string(cw) + " at D = " + std::to_string(D) + "; ch, cw >= 8 D + 7 = " +
                                  std::to_string(8 * D + 7) + " (the smallest at which both search windows hold a pixel)");
@@ -316,19 +314,15 @@ int jcm_frame_shift(jcm_handle h, const uint8_t* x, int T, int H, int W, int y0,
   const size_t nL = pairs > 0 ? (size_t)(T + 1) * ch * cw : 0, nC = pairs > 0 ? (size_t)(T + 1) * (ch / 4) * (cw / 4) : 0;
   const size_t ns = frame_shift_slots(pairs > 0 ? pairs : 0, D);
   JCM_TRY(workspace_or_refuse(c, w, (double)(nL + nC) * 2.0 + (double)ns * 8.0 + (double)T * 8.0 + 8192.0, "luma planes", 1, T));
-  return with_arena(c, [&] {
-    uint16_t* L = arena_alloc<uint16_t>(c, nL);
-    uint16_t* C = arena_alloc<uint16_t>(c, nC);
-    unsigned long long* slots = arena_alloc<unsigned long long>(c, ns + 1);
-    int32_t* center = arena_alloc<int32_t>(c, (size_t)2 * T);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const hipError_t e = frame_shift(x, T, H, W, y0, x0, ch, cw, D, prev, L, C, slots, center, disp, sad, c->stream);
-    prof_end(c, w, e0, e1, e == hipSuccess);
-    if (e != hipSuccess) return fail(JCM_ERR_HIP, w + ": " + hipGetErrorString(e));
-    return (int)JCM_OK;
-  });
+  uint16_t *L = nullptr, *C = nullptr;
+  unsigned long long* slots = nullptr;
+  int32_t* center = nullptr;
+  return arena_launch(c, w, [&] {
+    L = arena_alloc<uint16_t>(c, nL);
+    C = arena_alloc<uint16_t>(c, nC);
+    slots = arena_alloc<unsigned long long>(c, ns + 1);
+    center = arena_alloc<int32_t>(c, (size_t)2 * T);
+  }, [&] { return frame_shift(x, T, H, W, y0, x0, ch, cw, D, prev, L, C, slots, center, disp, sad, c->stream); });
 }
 
 }  // extern "C"

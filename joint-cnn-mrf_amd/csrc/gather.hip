@@ -7,7 +7,9 @@
 // Byte data sets: the image columns convert instead of copying, x_out = u8_to_f32(x_all[idx]) -- a lane takes one aligned dword
 // of four image bytes and writes one float4, so a wave reads 256 contiguous bytes and writes 1 KB of whole lines per instruction (wide path:
 // image byte count and source base multiples of 4, destination base a multiple of 16); byte loads and dword stores otherwise.
-#include "kernels.h"
+#include <string>
+
+#include "entry.h"
 #include "u8.h"
 
 namespace jcm {
@@ -111,8 +113,9 @@ bool wide_u8(const void* src, const void* dst, size_t bytes_per_image) {
 
 }  // namespace
 
-hipError_t gather_batch_u8(const uint8_t* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
-                           hipStream_t st) {
+// the same from a byte image array: x_out[b][i] = u8_to_f32(x_all[idx[b]][i]) (u8.h), nx values per image; the heat maps are copied as below
+static hipError_t gather_batch_u8(const uint8_t* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
+                                  hipStream_t st) {
   const bool wx = wide_u8(x_all, x_out, nx), wy = wide(y_all, y_out, ny);
   for (int b0 = 0; b0 < B; b0 += kGatherMax) {
     const int nb = B - b0 < kGatherMax ? B - b0 : kGatherMax;
@@ -135,8 +138,9 @@ hipError_t u8_to_f32_array(const uint8_t* x, float* x_out, size_t n, hipStream_t
   return hipGetLastError();
 }
 
-hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
-                        hipStream_t st) {
+// x_out[b] = x_all[idx[b]] (nx floats per image), y_out[b] = y_all[idx[b]] (ny floats); idx: HOST, B entries, every one checked by the entry point
+static hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
+                               hipStream_t st) {
   const bool wx = wide(x_all, x_out, nx), wy = wide(y_all, y_out, ny);
   for (int b0 = 0; b0 < B; b0 += kGatherMax) {
     const int nb = B - b0 < kGatherMax ? B - b0 : kGatherMax;
@@ -151,4 +155,52 @@ hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, 
   return hipGetLastError();
 }
 
+// (declared in entry.h: augment.hip's indexed entries take the same rules)
+int check_indexed(const char* who, const void* x_all, size_t xes, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B, int H, int W,
+                  int hh, int hw, int Ky, int min_side, const float* x_out, const float* y_out) {
+  const std::string w(who);
+  if (!x_all || !y_all || !idx || !x_out || !y_out) return fail(JCM_ERR_ARG, w + ": null pointer");
+  if (N < 1 || N > INT32_MAX || B < 1 || B > 65535 || H < min_side || W < min_side || hh < min_side || hw < min_side ||
+      (int64_t)H * W * 3 >= (int64_t)1 << 30 || (int64_t)hh * hw * Ky >= (int64_t)1 << 30)
+    return fail(JCM_ERR_ARG, w + ": bad sizes (N in [1, 2^31), B in [1, 65535], H, W, h, w >= " + std::to_string(min_side) + ")");
+  for (int b = 0; b < B; ++b)
+    if (idx[b] < 0 || (int64_t)idx[b] >= N)
+      return fail(JCM_ERR_ARG, w + ": idx[" + std::to_string(b) + "] = " + std::to_string(idx[b]) + " is outside [0, " + std::to_string(N) + ")");
+  const size_t ix = (size_t)H * W * 3 * sizeof(float), iy = (size_t)hh * hw * Ky * sizeof(float);
+  const size_t nxa = (size_t)N * H * W * 3 * xes, nya = (size_t)N * iy, nx = (size_t)B * ix, ny = (size_t)B * iy, np = (size_t)B * 6 * sizeof(float);
+  const auto overlap = [](const void* a, size_t na, const void* b, size_t nb) { return b != nullptr && ranges_overlap(a, na, b, nb); };
+  if (overlap(x_out, nx, x_all, nxa) || overlap(x_out, nx, y_all, nya) || overlap(x_out, nx, params, np) || overlap(y_out, ny, x_all, nxa) ||
+      overlap(y_out, ny, y_all, nya) || overlap(y_out, ny, params, np) || overlap(x_out, nx, y_out, ny))
+    return fail(JCM_ERR_ARG, w + ": x_out / y_out overlap the data set, params or each other");
+  return JCM_OK;
+}
+
 }  // namespace jcm
+
+using namespace jcm;
+
+extern "C" {
+
+int jcm_gather_batch(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W, int hh,
+                     int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  const int Ky = h->K + 1;
+  JCM_TRY(check_indexed("gather_batch", x_all, sizeof(float), y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  HIP_TRY(gather_batch(x_all, y_all, idx, B, (size_t)H * W * 3, (size_t)hh * hw * Ky, x_out, y_out, h->stream));
+  return JCM_OK;
+}
+
+int jcm_gather_batch_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W, int hh,
+                        int hw, float* x_out, float* y_out) {
+  JCM_TRY(check(h, false));
+  const int Ky = h->K + 1;
+  JCM_TRY(check_indexed("gather_batch_u8", x_all, 1, y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  HIP_TRY(gather_batch_u8(x_all, y_all, idx, B, (size_t)H * W * 3, (size_t)hh * hw * Ky, x_out, y_out, h->stream));
+  return JCM_OK;
+}
+
+}  // extern "C"

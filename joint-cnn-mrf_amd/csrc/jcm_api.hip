@@ -1,6 +1,7 @@
-// libjcm C ABI (include/jcm.h): context, parameter store, weight packing, workspace arena and
-// the forward graph of main.py:29-74,94-125,522-531 as a sequence of kernel launches on one
-// HIP stream.  No tensor library types cross this boundary -- plain pointers and sizes.
+// libjcm C ABI (include/jcm.h), the part that belongs to no kernel file: the handle's lifetime, the parameter store, the options, the entry points
+// of single layers and of the towers (main.py:29-74,94-125,522-531 as a sequence of kernel launches on one HIP stream) and the profile reader,
+// with the helpers every translation unit draws on (fail, CallOrder, the arena, find / check / conv_of, prof_*).  Every other entry point sits
+// beside its kernels, on the scaffold of entry.h.  No tensor library types cross this boundary -- plain pointers and sizes.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -770,322 +771,6 @@ int jcm_group_mean(jcm_handle h, const float* in, int n, int G, int64_t M, float
   CallOrder order(h);
   HIP_TRY(group_mean(in, out, n, G, (size_t)M, h->stream));
   return JCM_OK;
-}
-
-namespace {
-
-// what jcm_fit_images and jcm_fit_windows check alike (`who` names the entry point in the message): pointers, the frame, the size of out
-int fit_check_frame(const std::string& who, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad,
-                    const void* out) {
-  if (!src || !desc || !out) return fail(JCM_ERR_ARG, who + ": null pointer (src, desc and out are required, geom may be NULL)");
-  if (B < 1 || C < 1 || C > 4 || OH < 1 || OH > 4096 || OW < 1 || OW > 4096 || pad < 0 || pad > 255 || src_bytes < 1)
-    return fail(JCM_ERR_ARG, who + ": bad sizes (B >= 1, C in 1..4, OH and OW in 1..4096, pad in 0..255)");
-  if ((int64_t)B * OH * OW * C >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, who + ": B * OH * OW * C >= 2^31");
-  return JCM_OK;
-}
-// fh x fw, the size the filter sees (an image, or a window), against the size and reduction limits
-int fit_check_size(const std::string& who, int64_t fh, int64_t fw, int OH, int OW) {
-  if (fh < 1 || fh > 16384 || fw < 1 || fw > 16384)
-    return fail(JCM_ERR_ARG, who + " is " + std::to_string(fh) + " x " + std::to_string(fw) + "; both sides lie in 1..16384");
-  const FitGeom g = fit_geometry((int)fh, (int)fw, OH, OW);
-  if (fh > 32 * (int64_t)g.ch || fw > 32 * (int64_t)g.cw)
-    return fail(JCM_ERR_ARG, who + ", " + std::to_string(fh) + " x " + std::to_string(fw) + " into " + std::to_string(g.ch) + " x " + std::to_string(g.cw) +
-                                 ": a reduction above 32 (at most 66 taps per axis)");
-  return JCM_OK;
-}
-int fit_check_overlap(const std::string& who, const uint8_t* src, int64_t src_bytes, const void* out, size_t no) {
-  const char *pa = reinterpret_cast<const char*>(src), *pb = static_cast<const char*>(out);
-  if (pa < pb + no && pb < pa + src_bytes) return fail(JCM_ERR_ARG, who + ": out overlaps src");
-  return JCM_OK;
-}
-// geom[i] = the content rectangle of desc row i (`stride` entries a row, the filter's size at entries at, at + 1)
-void fit_write_geom(const int64_t* desc, int B, int stride, int at, int OH, int OW, int32_t* geom) {
-  for (int b = 0; b < B; ++b) {
-    const FitGeom g = fit_geometry((int)desc[b * (int64_t)stride + at], (int)desc[b * (int64_t)stride + at + 1], OH, OW);
-    geom[b * (int64_t)4] = g.y0;
-    geom[b * (int64_t)4 + 1] = g.x0;
-    geom[b * (int64_t)4 + 2] = g.ch;
-    geom[b * (int64_t)4 + 3] = g.cw;
-  }
-}
-
-}  // namespace
-
-int jcm_fit_images(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, int out_f32,
-                   void* out, int32_t* geom) {
-  JCM_TRY(check(h, false));
-  JCM_TRY(fit_check_frame("fit_images", src, src_bytes, desc, B, C, OH, OW, pad, out));
-  for (int b = 0; b < B; ++b) {
-    const int64_t off = desc[b * (int64_t)3], hb = desc[b * (int64_t)3 + 1], wb = desc[b * (int64_t)3 + 2];
-    const std::string who = "fit_images: image " + std::to_string(b);
-    if (hb < 1 || hb > 16384 || wb < 1 || wb > 16384)
-      return fail(JCM_ERR_ARG, who + " is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..16384");
-    if (off < 0 || off > src_bytes || hb * wb * C > src_bytes - off)
-      return fail(JCM_ERR_ARG, who + " (" + std::to_string(hb * wb * C) + " bytes at offset " + std::to_string(off) + ") does not lie inside the " +
-                                   std::to_string(src_bytes) + " bytes of src");
-    JCM_TRY(fit_check_size(who, hb, wb, OH, OW));
-  }
-  JCM_TRY(fit_check_overlap("fit_images", src, src_bytes, out, (size_t)B * OH * OW * C * (out_f32 ? sizeof(float) : 1)));
-  if (geom) fit_write_geom(desc, B, 3, 1, OH, OW, geom);
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  jcm_ctx* c = h;
-  hipEvent_t e0, e1;
-  JCM_TRY(prof_begin(c, &e0, &e1));
-  const hipError_t launch = fit_images(src, src_bytes, desc, B, C, OH, OW, pad, out_f32 != 0, out, c->stream);
-  prof_end(c, "fit_images", e0, e1, launch == hipSuccess);
-  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("fit_images: ") + hipGetErrorString(launch));
-  return JCM_OK;
-}
-
-int jcm_fit_windows(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, int out_f32,
-                    void* out, int32_t* geom) {
-  JCM_TRY(check(h, false));
-  JCM_TRY(fit_check_frame("fit_windows", src, src_bytes, desc, NW, C, OH, OW, pad, out));
-  constexpr int64_t kSide = (int64_t)1 << 24;      // image sides: rows, columns and their sums with a window's stay far inside int
-  for (int i = 0; i < NW; ++i) {
-    const int64_t* d = desc + i * (int64_t)7;
-    const int64_t off = d[0], hb = d[1], wb = d[2], wy0 = d[3], wx0 = d[4], wh = d[5], ww = d[6];
-    const std::string who = "fit_windows: window " + std::to_string(i);
-    if (hb < 1 || hb > kSide || wb < 1 || wb > kSide)
-      return fail(JCM_ERR_ARG, who + ": its image is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..2^24");
-    if (off < 0 || off > src_bytes || hb * wb * C > src_bytes - off)
-      return fail(JCM_ERR_ARG, who + ": its image (" + std::to_string(hb * wb * C) + " bytes at offset " + std::to_string(off) +
-                                   ") does not lie inside the " + std::to_string(src_bytes) + " bytes of src");
-    JCM_TRY(fit_check_size(who, wh, ww, OH, OW));
-    if (wy0 >= hb || wy0 + wh <= 0 || wx0 >= wb || wx0 + ww <= 0)      // wh, ww <= 16384: the sums cannot overflow unless the window is disjoint anyway
-      return fail(JCM_ERR_ARG, who + ", rows " + std::to_string(wy0) + ".. and columns " + std::to_string(wx0) + ".., " + std::to_string(wh) + " x " +
-                                   std::to_string(ww) + ", shares no pixel with its " + std::to_string(hb) + " x " + std::to_string(wb) + " image");
-  }
-  JCM_TRY(fit_check_overlap("fit_windows", src, src_bytes, out, (size_t)NW * OH * OW * C * (out_f32 ? sizeof(float) : 1)));
-  if (geom) fit_write_geom(desc, NW, 7, 5, OH, OW, geom);
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  jcm_ctx* c = h;
-  hipEvent_t e0, e1;
-  JCM_TRY(prof_begin(c, &e0, &e1));
-  const hipError_t launch = fit_windows(src, src_bytes, desc, NW, C, OH, OW, pad, out_f32 != 0, out, c->stream);
-  prof_end(c, "fit_windows", e0, e1, launch == hipSuccess);
-  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("fit_windows: ") + hipGetErrorString(launch));
-  return JCM_OK;
-}
-
-int jcm_render_poses(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP,
-                     const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain) {
-  JCM_TRY(check(h, false));
-  const std::string who = "render_poses";
-  if (!src || !desc || !out) return fail(JCM_ERR_ARG, who + ": null pointer (src, desc and out are required)");
-  if (B < 1 || src_bytes < 1) return fail(JCM_ERR_ARG, who + ": B >= 1 images in src_bytes >= 1 bytes are expected");
-  for (int b = 0; b < B; ++b) {
-    const int64_t off = desc[b * (int64_t)3], hb = desc[b * (int64_t)3 + 1], wb = desc[b * (int64_t)3 + 2];
-    const std::string img = who + ": image " + std::to_string(b);
-    if (hb < 1 || hb > 16384 || wb < 1 || wb > 16384)
-      return fail(JCM_ERR_ARG, img + " is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..16384");
-    if (off < 0 || off > src_bytes || hb * wb * 3 > src_bytes - off)
-      return fail(JCM_ERR_ARG, img + " (" + std::to_string(hb * wb * 3) + " bytes at offset " + std::to_string(off) + ") does not lie inside the " +
-                                   std::to_string(src_bytes) + " bytes of src");
-  }
-  if (out != src) {
-    const char *pa = reinterpret_cast<const char*>(src), *pb = reinterpret_cast<const char*>(out);
-    if (pa < pb + src_bytes && pb < pa + src_bytes) return fail(JCM_ERR_ARG, who + ": out overlaps src in part (out == src, in place, is allowed)");
-  }
-  if (NP < 0 || (NP > 0 && !prims)) return fail(JCM_ERR_ARG, who + ": NP >= 0 primitives are expected, and prims with NP > 0");
-  constexpr int32_t kCoord = 1 << 20;
-  for (int i = 0, run = 0; i < NP; ++i) {
-    const int32_t* p = prims + i * (int64_t)8;
-    const std::string prim = who + ": primitive " + std::to_string(i);
-    if (p[0] < 0 || p[0] >= B || (i > 0 && p[0] < p[-8]))
-      return fail(JCM_ERR_ARG, prim + " names image " + std::to_string(p[0]) + "; the images are 0.." + std::to_string(B - 1) + " and the list is sorted by image");
-    run = i > 0 && p[0] == p[-8] ? run + 1 : 1;
-    if (run > kRenderPrimMax) return fail(JCM_ERR_ARG, who + ": image " + std::to_string(p[0]) + " has more than " + std::to_string(kRenderPrimMax) + " primitives");
-    for (int k = 1; k <= 4; ++k)
-      if (p[k] < -kCoord || p[k] > kCoord) return fail(JCM_ERR_ARG, prim + ": coordinate " + std::to_string(p[k]) + " outside +-2^20 sixteenths of a pixel");
-    if (p[5] < 0 || p[5] > (1 << 16)) return fail(JCM_ERR_ARG, prim + ": r = " + std::to_string(p[5]) + " outside 0..2^16");
-    if (p[6] < 0 || p[6] > 0xFFFFFF) return fail(JCM_ERR_ARG, prim + ": rgb outside 0..0xFFFFFF");
-    if (p[7] < 0 || p[7] > 255) return fail(JCM_ERR_ARG, prim + ": alpha = " + std::to_string(p[7]) + " outside 0..255");
-  }
-  if (hm) {
-    if (!geom || !heat_mask) return fail(JCM_ERR_ARG, who + ": hm needs geom and heat_mask");
-    if (K < 1 || K > 16 || hh < 1 || hw < 1 || stride < 1 || heat_gain < 0 || heat_gain > 255)
-      return fail(JCM_ERR_ARG, who + ": hm needs K in 1..16, hh, hw and stride >= 1 and heat_gain in 0..255");
-    if ((int64_t)B * hh * hw * K >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, who + ": B * hh * hw * K >= 2^31");
-    for (int b = 0; b < B; ++b)
-      if (geom[b * (int64_t)4 + 2] < 1 || geom[b * (int64_t)4 + 3] < 1)
-        return fail(JCM_ERR_ARG, who + ": geom row " + std::to_string(b) + " has a content rectangle without a pixel");
-  }
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  jcm_ctx* c = h;
-  return with_arena(c, [&] {
-    int32_t* prims_dev = arena_alloc<int32_t>(c, render_prim_ints(NP));
-    float* maxima = hm ? arena_alloc<float>(c, (size_t)B * K) : nullptr;
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const hipError_t launch = render_poses(src, desc, B, out, prims, NP, prims_dev, hm, hh, hw, K, stride, geom, heat_mask, heat_gain, maxima, c->stream);
-    prof_end(c, "render_poses", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("render_poses: ") + hipGetErrorString(launch));
-    return (int)JCM_OK;
-  });
-}
-
-int jcm_synth_people(jcm_handle h, const int32_t* records, int B, const int32_t* prims, int NP, int H, int W, int out_f32, void* out) {
-  JCM_TRY(check(h, false));
-  const std::string who = "synth_people";
-  if (!records || !out) return fail(JCM_ERR_ARG, who + ": null pointer (records and out are required)");
-  if (B < 1 || B > 65535) return fail(JCM_ERR_ARG, who + ": B = " + std::to_string(B) + " outside 1..65535");
-  if (H < 1 || W < 1) return fail(JCM_ERR_ARG, who + ": H and W >= 1 are expected, got " + std::to_string(H) + " x " + std::to_string(W));
-  if ((int64_t)H * W > (int64_t)INT32_MAX) return fail(JCM_ERR_ARG, who + ": H * W = " + std::to_string((int64_t)H * W) + " is over the int32 range");
-  if (NP < 0 || (NP > 0 && !prims)) return fail(JCM_ERR_ARG, who + ": NP >= 0 primitives are expected, and prims with NP > 0");
-  if (out_f32 && (reinterpret_cast<uintptr_t>(out) & 3u)) return fail(JCM_ERR_ARG, who + ": a float32 out is 4-byte aligned");
-  auto byte = [](int32_t v) { return v >= 0 && v <= 255; };
-  for (int b = 0; b < B; ++b) {
-    const int32_t* r = records + b * (int64_t)kSynthRecInts;
-    const std::string img = who + ": image " + std::to_string(b);
-    for (int k = 1; k <= 6; ++k)
-      if (!byte(r[k])) return fail(JCM_ERR_ARG, img + ": background colour " + std::to_string(r[k]) + " outside 0..255");
-    for (int o = 0; o < 4; ++o) {
-      if (!byte(r[7 + o])) return fail(JCM_ERR_ARG, img + ": octave amplitude " + std::to_string(r[7 + o]) + " outside 0..255");
-      if (r[11 + o] < 0 || r[11 + o] > 8) return fail(JCM_ERR_ARG, img + ": octave shift " + std::to_string(r[11 + o]) + " outside 0..8");
-    }
-    if (!byte(r[15])) return fail(JCM_ERR_ARG, img + ": sensor-noise amplitude " + std::to_string(r[15]) + " outside 0..255");
-    if (r[16] < 0 || r[16] > kSynthPrimMax)
-      return fail(JCM_ERR_ARG, img + ": n = " + std::to_string(r[16]) + " primitives outside 0.." + std::to_string(kSynthPrimMax));
-    if (r[17] < 0 || (int64_t)r[17] + r[16] > NP)
-      return fail(JCM_ERR_ARG, img + ": primitives " + std::to_string(r[17]) + ".." + std::to_string((int64_t)r[17] + r[16]) + " do not lie inside the " +
-                                   std::to_string(NP) + " of prims");
-  }
-  constexpr int32_t kCoord = 1 << 20;
-  for (int i = 0; i < NP; ++i) {
-    const int32_t* p = prims + i * (int64_t)kSynthPrimInts;
-    const std::string prim = who + ": primitive " + std::to_string(i);
-    if (p[0] != 0 && p[0] != 1) return fail(JCM_ERR_ARG, prim + ": kind " + std::to_string(p[0]) + " is neither 0 (capsule) nor 1 (quadrilateral)");
-    for (int k = 1; k <= (p[0] == 0 ? 4 : 8); ++k)
-      if (p[k] < -kCoord || p[k] > kCoord) return fail(JCM_ERR_ARG, prim + ": coordinate " + std::to_string(p[k]) + " outside +-2^20 sixteenths of a pixel");
-    if (p[0] == 0 && (p[5] < 0 || p[5] > (1 << 16))) return fail(JCM_ERR_ARG, prim + ": r = " + std::to_string(p[5]) + " outside 0..2^16");
-    for (int k = 9; k <= 11; ++k)
-      if (!byte(p[k])) return fail(JCM_ERR_ARG, prim + ": colour " + std::to_string(p[k]) + " outside 0..255");
-    if (!byte(p[12])) return fail(JCM_ERR_ARG, prim + ": texture amplitude " + std::to_string(p[12]) + " outside 0..255");
-    if (p[13] < 0 || p[13] > 8) return fail(JCM_ERR_ARG, prim + ": texture shift " + std::to_string(p[13]) + " outside 0..8");
-  }
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  jcm_ctx* c = h;
-  return with_arena(c, [&] {
-    int32_t* records_dev = arena_alloc<int32_t>(c, (size_t)B * kSynthRecInts);
-    int32_t* prims_dev = arena_alloc<int32_t>(c, (size_t)(NP > 0 ? NP : 1) * kSynthPrimInts);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const hipError_t launch = synth_people(records, B, prims, NP, H, W, out_f32 != 0, out, records_dev, prims_dev, c->stream);
-    prof_end(c, "synth_people", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("synth_people: ") + hipGetErrorString(launch));
-    return (int)JCM_OK;
-  });
-}
-
-int jcm_augment_train(jcm_handle h, const float* x, const float* y, const float* params, int B, int H, int W,
-                      int hh, int hw, float* x_out, float* y_out) {
-  JCM_TRY(check(h, false));
-  if (!x || !y || !params || !x_out || !y_out) return fail(JCM_ERR_ARG, "augment_train: null pointer");
-  if (B < 1 || B > 65535 || H < 2 || W < 2 || hh < 2 || hw < 2 || (int64_t)H * W * 3 >= (int64_t)1 << 30 || (int64_t)hh * hw * 10 >= (int64_t)1 << 30)
-    return fail(JCM_ERR_ARG, "augment_train: bad sizes (B in [1, 65535], H, W, h, w >= 2)");
-  if (h->K != 9) return fail(JCM_ERR_ARG, "augment_train: the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
-  const size_t nx = (size_t)B * H * W * 3 * sizeof(float), ny = (size_t)B * hh * hw * 10 * sizeof(float), np = (size_t)B * 6 * sizeof(float);
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-    return pa < pb + nb && pb < pa + na;
-  };
-  if (overlap(x_out, nx, x, nx) || overlap(x_out, nx, y, ny) || overlap(x_out, nx, params, np) || overlap(y_out, ny, x, nx) ||
-      overlap(y_out, ny, y, ny) || overlap(y_out, ny, params, np) || overlap(x_out, nx, y_out, ny))
-    return fail(JCM_ERR_ARG, "augment_train: x_out / y_out alias an input or each other");
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  jcm_ctx* c = h;
-  return with_arena(c, [&] {
-    double* scratch = arena_alloc<double>(c, augment_scratch_doubles(B));
-    if (c->dry) return (int)JCM_OK;
-    HIP_TRY(augment_train(x, y, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
-    return (int)JCM_OK;
-  });
-}
-
-namespace {
-
-// the argument checks jcm_gather_batch and jcm_augment_train_indexed share; Ky = heat-map channels; params may be null (gather)
-// xes: bytes per image value of the data set (4, or 1 for a byte data set; the outputs are fp32 either way)
-int check_indexed(const char* who, const void* x_all, size_t xes, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B, int H, int W,
-                  int hh, int hw, int Ky, int min_side, const float* x_out, const float* y_out) {
-  const std::string w(who);
-  if (!x_all || !y_all || !idx || !x_out || !y_out) return fail(JCM_ERR_ARG, w + ": null pointer");
-  if (N < 1 || N > INT32_MAX || B < 1 || B > 65535 || H < min_side || W < min_side || hh < min_side || hw < min_side ||
-      (int64_t)H * W * 3 >= (int64_t)1 << 30 || (int64_t)hh * hw * Ky >= (int64_t)1 << 30)
-    return fail(JCM_ERR_ARG, w + ": bad sizes (N in [1, 2^31), B in [1, 65535], H, W, h, w >= " + std::to_string(min_side) + ")");
-  for (int b = 0; b < B; ++b)
-    if (idx[b] < 0 || (int64_t)idx[b] >= N)
-      return fail(JCM_ERR_ARG, w + ": idx[" + std::to_string(b) + "] = " + std::to_string(idx[b]) + " is outside [0, " + std::to_string(N) + ")");
-  const size_t ix = (size_t)H * W * 3 * sizeof(float), iy = (size_t)hh * hw * Ky * sizeof(float);
-  const size_t nxa = (size_t)N * H * W * 3 * xes, nya = (size_t)N * iy, nx = (size_t)B * ix, ny = (size_t)B * iy, np = (size_t)B * 6 * sizeof(float);
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-    return b != nullptr && pa < pb + nb && pb < pa + na;
-  };
-  if (overlap(x_out, nx, x_all, nxa) || overlap(x_out, nx, y_all, nya) || overlap(x_out, nx, params, np) || overlap(y_out, ny, x_all, nxa) ||
-      overlap(y_out, ny, y_all, nya) || overlap(y_out, ny, params, np) || overlap(x_out, nx, y_out, ny))
-    return fail(JCM_ERR_ARG, w + ": x_out / y_out overlap the data set, params or each other");
-  return JCM_OK;
-}
-
-}  // namespace
-
-int jcm_gather_batch(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W, int hh,
-                     int hw, float* x_out, float* y_out) {
-  JCM_TRY(check(h, false));
-  const int Ky = h->K + 1;
-  JCM_TRY(check_indexed("gather_batch", x_all, sizeof(float), y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  HIP_TRY(gather_batch(x_all, y_all, idx, B, (size_t)H * W * 3, (size_t)hh * hw * Ky, x_out, y_out, h->stream));
-  return JCM_OK;
-}
-
-int jcm_gather_batch_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, int B, int H, int W, int hh,
-                        int hw, float* x_out, float* y_out) {
-  JCM_TRY(check(h, false));
-  const int Ky = h->K + 1;
-  JCM_TRY(check_indexed("gather_batch_u8", x_all, 1, y_all, N, idx, nullptr, B, H, W, hh, hw, Ky, 1, x_out, y_out));
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  HIP_TRY(gather_batch_u8(x_all, y_all, idx, B, (size_t)H * W * 3, (size_t)hh * hw * Ky, x_out, y_out, h->stream));
-  return JCM_OK;
-}
-
-static int augment_indexed_entry(jcm_handle h, const char* who, const void* x_all, bool x_u8, const float* y_all, int64_t N, const int32_t* idx,
-                                 const float* params, int B, int H, int W, int hh, int hw, float* x_out, float* y_out) {
-  JCM_TRY(check(h, false));
-  const std::string w(who);
-  if (!params) return fail(JCM_ERR_ARG, w + ": null pointer");
-  if (h->K != 9)
-    return fail(JCM_ERR_ARG, w + ": the heat maps have 10 channels (n_joints == 9), this handle has n_joints = " + std::to_string(h->K));
-  JCM_TRY(check_indexed(who, x_all, x_u8 ? 1 : sizeof(float), y_all, N, idx, params, B, H, W, hh, hw, 10, 2, x_out, y_out));
-  DeviceGuard g(h->device);
-  CallOrder order(h);
-  jcm_ctx* c = h;
-  return with_arena(c, [&] {
-    double* scratch = arena_alloc<double>(c, augment_scratch_doubles(B));
-    if (c->dry) return (int)JCM_OK;
-    if (x_u8) HIP_TRY(augment_train_indexed_u8(static_cast<const uint8_t*>(x_all), y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
-    else HIP_TRY(augment_train_indexed(static_cast<const float*>(x_all), y_all, idx, params, B, H, W, hh, hw, scratch, x_out, y_out, c->stream));
-    return (int)JCM_OK;
-  });
-}
-int jcm_augment_train_indexed(jcm_handle h, const float* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
-                              int H, int W, int hh, int hw, float* x_out, float* y_out) {
-  return augment_indexed_entry(h, "augment_train_indexed", x_all, false, y_all, N, idx, params, B, H, W, hh, hw, x_out, y_out);
-}
-int jcm_augment_train_indexed_u8(jcm_handle h, const uint8_t* x_all, const float* y_all, int64_t N, const int32_t* idx, const float* params, int B,
-                                 int H, int W, int hh, int hw, float* x_out, float* y_out) {
-  return augment_indexed_entry(h, "augment_train_indexed_u8", x_all, true, y_all, N, idx, params, B, H, W, hh, hw, x_out, y_out);
 }
 
 int jcm_profile_read(jcm_handle h, const char* scope, double* total_ms, int* launches) {

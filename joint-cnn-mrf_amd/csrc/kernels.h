@@ -361,11 +361,6 @@ __host__ __device__ inline FitGeom fit_geometry(int h, int w, int OH, int OW) {
   g.x0 = (OW - g.cw) / 2;
   return g;
 }
-// src: B byte images [h_b, w_b, C] at desc[b] = (byte offset, h_b, w_b) (HOST int64 [B][3], read before the call returns; every entry checked by the
-// caller: 1 <= C <= 4, sizes, bounds, a reduction of at most 32 per axis) -> out [B,OH,OW,C] uint8 or (out_f32) float32 = u8_to_f32(byte); the
-// separable triangle filter of jcm.h in float64, `pad` outside the content rectangle.  One launch per kFitMax images.
-hipError_t fit_images(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, int C, int OH, int OW, int pad, bool out_f32, void* out,
-                      hipStream_t st);
 // The windows of a launch (jcm.h: jcm_fit_windows): window i is rows [wy0, wy0 + wh) x columns [wx0, wx0 + ww) of the h x w image
 // at off, `pad` where the image has no sample.  36 bytes a window: 64 of them are 2308 bytes of kernel arguments (FitBatch: 1284; the limit is 4096).
 constexpr int kFitWinMax = 64;
@@ -375,11 +370,6 @@ struct FitWinBatch {
   int wy0[kFitWinMax], wx0[kFitWinMax], wh[kFitWinMax], ww[kFitWinMax];
   int first[kFitWinMax + 1];    // work groups [first[i], first[i + 1]) are the strips of window i
 };
-// desc: HOST int64 [NW][7] = (byte offset, h, w, wy0, wx0, wh, ww), every entry checked by the caller (as for fit_images, the size and reduction
-// limits on wh x ww; image sides <= 2^24; every window shares a pixel with its image) -> out [NW,OH,OW,C]: fit_images of the padded window, bit
-// for bit.  One launch per kFitWinMax windows; the source rows and columns a work group stages are those of its window's support only.
-hipError_t fit_windows(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int NW, int C, int OH, int OW, int pad, bool out_f32, void* out,
-                       hipStream_t st);
 // ---- render.hip : poses drawn onto the ragged byte batch --------------------------
 // The images of a launch travel by value in its kernel arguments, as FitBatch does; a batch of more than kRenderMax images takes several launches.
 constexpr int kRenderMax = 64;
@@ -398,24 +388,11 @@ struct RenderHeat {
   int hh, hw, K, stride, gain;
   uint8_t mask[16];
 };
-// workspace the caller provides: prims_dev = render_prim_ints(NP) ints (256-byte aligned), maxima = B * K floats (hm only)
-size_t render_prim_ints(int NP);
-// src / out: the packed buffers; desc HOST int64 [B][3]; prims HOST int32 [NP][8] sorted by image; geom HOST int32 [B][4], heat_mask HOST [K] (hm only).
-// Every entry has been checked by the caller (jcm.h: jcm_render_poses).  The host arrays are read before the call returns; ceil(NP / 120) upload
-// launches, one launch for the maxima (hm), one launch per kRenderMax images.  out == src is allowed.
-hipError_t render_poses(const uint8_t* src, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP, int32_t* prims_dev,
-                        const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain,
-                        float* maxima, hipStream_t st);
 // ---- synth_people.hip : rendered people, a data set drawn on the device ------------
 constexpr int kSynthRecInts = 20;        // a scene record (jcm.h: JCM_SYNTH_REC_INTS)
 constexpr int kSynthPrimInts = 16;       // a primitive record (jcm.h: JCM_SYNTH_PRIM_INTS)
 constexpr int kSynthPrimMax = 64;        // primitives per image: one lane of a wave culls one
 constexpr int kSynthTile = 8192;         // consecutive pixels (row-major) per work group: 24 KB of LDS
-// records HOST int32 [B][20], prims HOST int32 [NP][16], every entry checked by the caller (jcm.h: jcm_synth_people); both are read before the call
-// returns: they go into records_dev (B * 20 ints) and prims_dev (max(NP, 1) * 16 ints), workspace the caller provides (256-byte aligned), by
-// ceil(n / 960) small launches that carry them in their arguments.  out: uint8 [B,H,W,3], or float32 (out_f32) = byte / 255.  One more launch.
-hipError_t synth_people(const int32_t* records, int B, const int32_t* prims, int NP, int H, int W, bool out_f32, void* out, int32_t* records_dev,
-                        int32_t* prims_dev, hipStream_t st);
 // ---- sequence.hip : the temporal edge, a scan over the T frames of a clip ----------
 // hm [S,T,HH,WW,K]; one work group per (sequence, joint), whose belief plane stays in LDS for all T frames of the launch.  HH * WW <= kSeqMaxHW,
 // K <= kSeqMaxK, 0 <= R <= kSeqMaxR; taps: DEVICE [K][2R+1] (seq_put_taps uploads a host table through kernel arguments, ceil(n / 480) launches).
@@ -535,33 +512,14 @@ hipError_t window_resize(const float* src, int H, int W, int C, const int* windo
                          int OH, int OW, float* out, hipStream_t st);
 hipError_t group_mean(const float* in, float* out, int n, int G, size_t M, hipStream_t st);
 
-// ---- augment.hip : training-time augmentation (augmentation.py:58-78) ---------------
-// x [B,H,W,3], y [B,hh,hw,10], params [B,6] = (flip, delta, factor, angle, rh, rw), all device fp32; three launches on `st`.
-// scratch: augment_scratch_doubles(B) doubles (the per-image channel sums of the brightened image)
-size_t augment_scratch_doubles(int B);
-hipError_t augment_train(const float* x, const float* y, const float* params, int B, int H, int W, int hh, int hw, double* scratch,
-                         float* x_out, float* y_out, hipStream_t st);
-
-// ---- gather.hip : batches by index from a device-resident data set -----------------
+// ---- gather.hip : batches by index from a device-resident data set (augment.hip's indexed entries draw on it) ----
 // The indices of a launch travel by value in its kernel arguments; a batch of more than kGatherMax images takes several launches.
 constexpr int kGatherMax = 256;
 struct GatherIdx {
   int v[kGatherMax];
 };
-// x_out[b] = x_all[idx[b]] (nx floats per image), y_out[b] = y_all[idx[b]] (ny floats); idx: HOST, B entries, every one checked by the caller
-hipError_t gather_batch(const float* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
-                        hipStream_t st);
-// the same from a byte image array: x_out[b][i] = u8_to_f32(x_all[idx[b]][i]) (u8.h), nx values per image; the heat maps are copied as above
-hipError_t gather_batch_u8(const uint8_t* x_all, const float* y_all, const int* idx, int B, size_t nx, size_t ny, float* x_out, float* y_out,
-                           hipStream_t st);
 // x_out[i] = u8_to_f32(x[i]), n values (a byte batch whose branch inputs need a real resize: jcm_pd_forward_u8 at sizes not divisible by 4)
 hipError_t u8_to_f32_array(const uint8_t* x, float* x_out, size_t n, hipStream_t st);
-// augment_train with image idx[b] of (x_all, y_all) as the source of output image b; same kernels, same arithmetic (augment.hip)
-hipError_t augment_train_indexed(const float* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
-                                 double* scratch, float* x_out, float* y_out, hipStream_t st);
-// the same with a byte image array as the source (every tap converted by u8_to_f32; sums in the same order: the same bits)
-hipError_t augment_train_indexed_u8(const uint8_t* x_all, const float* y_all, const int* idx, const float* params, int B, int H, int W, int hh, int hw,
-                                    double* scratch, float* x_out, float* y_out, hipStream_t st);
 
 // ---- train_kernels.hip : training-step kernels other than convolutions (fp32 NHWC) ------------------
 size_t train_reduce_scratch_doubles(int C);      // scratch the per-channel reductions below need

@@ -10,7 +10,7 @@
 // from the mirrored pixels -- the lanes of a wave still cover the same contiguous KiB of the copy, in another order, so every fetched line is used.
 #include <string>
 
-#include "ctx.h"
+#include "entry.h"
 #include "hm_flip.h"
 
 namespace jcm {
@@ -159,11 +159,6 @@ int gcd_int(int a, int b) {
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 hipError_t mirror_pairs(const void* x, bool x_u8, int B, int H, int W, int C, void* out, hipStream_t st) {
@@ -222,16 +217,10 @@ int jcm_mirror_pairs(jcm_handle h, const void* x, int x_u8, int B, int H, int W,
     return fail(JCM_ERR_ARG, "mirror_pairs: a row of " + std::to_string((int64_t)W * C * es) + " bytes; W * C * sizeof(value) <= 65536 (a row is staged in LDS)");
   if ((int64_t)H * W * C >= ((int64_t)1 << 31) || (int64_t)B * 2 >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, "mirror_pairs: bad sizes (H * W * C < 2^31, B < 2^30)");
   const size_t nx = (size_t)B * H * W * C * es;
-  if (overlap(x, nx, out, 2 * nx)) return fail(JCM_ERR_ARG, "mirror_pairs: out overlaps x");
+  if (ranges_overlap(x, nx, out, 2 * nx)) return fail(JCM_ERR_ARG, "mirror_pairs: out overlaps x");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
-  hipEvent_t e0, e1;
-  JCM_TRY(prof_begin(c, &e0, &e1));
-  const hipError_t launch = mirror_pairs(x, x_u8 != 0, B, H, W, C, out, c->stream);
-  prof_end(c, "mirror_pairs", e0, e1, launch == hipSuccess);
-  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("mirror_pairs: ") + hipGetErrorString(launch));
-  return JCM_OK;
+  return timed_launch(h, "mirror_pairs", [&] { return mirror_pairs(x, x_u8 != 0, B, H, W, C, out, h->stream); });
 }
 
 int jcm_mirror_merge(jcm_handle h, const float* hm, int n, int G, int HH, int WW, int K, const int32_t* perm, float* out) {
@@ -252,16 +241,10 @@ int jcm_mirror_merge(jcm_handle h, const float* hm, int n, int G, int HH, int WW
     table[k] = v;
   }
   const size_t no = (size_t)n * HH * WW * K * sizeof(float);
-  if (overlap(hm, no * G, out, no)) return fail(JCM_ERR_ARG, "mirror_merge: out overlaps hm");
+  if (ranges_overlap(hm, no * G, out, no)) return fail(JCM_ERR_ARG, "mirror_merge: out overlaps hm");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
-  hipEvent_t e0, e1;
-  JCM_TRY(prof_begin(c, &e0, &e1));
-  const hipError_t launch = mirror_merge(hm, n, G, HH, WW, K, table, out, c->stream);
-  prof_end(c, "mirror_merge", e0, e1, launch == hipSuccess);
-  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("mirror_merge: ") + hipGetErrorString(launch));
-  return JCM_OK;
+  return timed_launch(h, "mirror_merge", [&] { return mirror_merge(hm, n, G, HH, WW, K, table, out, h->stream); });
 }
 
 }  // extern "C"

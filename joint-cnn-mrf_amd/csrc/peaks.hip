@@ -12,7 +12,7 @@
 // the waves, double-buffered: one barrier per round), each round retiring its winner from the list of the thread that owns it.
 #include <string>
 
-#include "ctx.h"
+#include "entry.h"
 
 namespace jcm {
 
@@ -217,13 +217,7 @@ int jcm_hm_peaks(jcm_handle h, const float* hm, int B, int HH, int WW, int K, in
   if (!hm || !cells || !scores || !count) return fail(JCM_ERR_ARG, "hm_peaks: null pointer (hm, cells, scores and count are required; offsets may be NULL)");
   DeviceGuard g(h->device);
   CallOrder order(h);
-  jcm_ctx* c = h;
-  hipEvent_t e0, e1;
-  JCM_TRY(prof_begin(c, &e0, &e1));
-  const hipError_t launch = hm_peaks(hm, B, HH, WW, K, P, threshold, cells, offsets, scores, count, c->stream);
-  prof_end(c, "hm_peaks", e0, e1, launch == hipSuccess);
-  if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("hm_peaks: ") + hipGetErrorString(launch));
-  return JCM_OK;
+  return timed_launch(h, "hm_peaks", [&] { return hm_peaks(hm, B, HH, WW, K, P, threshold, cells, offsets, scores, count, h->stream); });
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 // the rest broadcasts); the reads of the depth-first walk are wave-uniform.  No atomics; every store is a vector store of plain C++.
 #include <string>
 
-#include "ctx.h"
+#include "entry.h"
 #include "sm_lds_fft.h"
 
 namespace jcm {
@@ -276,19 +276,16 @@ int jcm_pose_decode(jcm_handle h, const float* hm10, int B, const int32_t* cells
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
-  return with_arena(c, [&] {
-    float* v = V ? V : arena_alloc<float>(c, (size_t)B * kPdK * P);
-    float* m = M ? M : arena_alloc<float>(c, (size_t)B * kPdPairs * P * P);
-    float* pscore = arena_alloc<float>(c, (size_t)B * kPdGroups);
-    int32_t* ppose = arena_alloc<int32_t>(c, (size_t)B * kPdGroups);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const hipError_t launch = pose_decode(hm10, B, cells, count, P, c->sp_energy, c->sp_bias, c->bn_sm_scale, c->bn_sm_shift, v, m, pscore, ppose, index, coords,
-                                          score, score0, c->stream);
-    prof_end(c, "pose_decode", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("pose_decode: ") + hipGetErrorString(launch));
-    return (int)JCM_OK;
+  float *v = V, *m = M, *pscore = nullptr;
+  int32_t* ppose = nullptr;
+  return arena_launch(c, "pose_decode", [&] {
+    if (!V) v = arena_alloc<float>(c, (size_t)B * kPdK * P);
+    if (!M) m = arena_alloc<float>(c, (size_t)B * kPdPairs * P * P);
+    pscore = arena_alloc<float>(c, (size_t)B * kPdGroups);
+    ppose = arena_alloc<int32_t>(c, (size_t)B * kPdGroups);
+  }, [&] {
+    return pose_decode(hm10, B, cells, count, P, c->sp_energy, c->sp_bias, c->bn_sm_scale, c->bn_sm_shift, v, m, pscore, ppose, index, coords, score, score0,
+                       c->stream);
   });
 }
 

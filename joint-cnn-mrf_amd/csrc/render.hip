@@ -16,8 +16,10 @@
 //     bytes an image) and are put into workspace by small launches that carry kRenderPut of them each in THEIR arguments: nothing is copied
 //     from caller-owned host memory asynchronously, so nothing has to be waited for.
 //   * the per-map maxima the tint normalises by come from a launch of their own (one work group per map) into workspace.
+#include <string>
+
 #include "coverage.h"      // render_coverage: the capsule test, shared with synth_people.hip
-#include "kernels.h"
+#include "entry.h"
 
 namespace jcm {
 
@@ -239,10 +241,12 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const uint8_t* s
   }
 }
 
-}  // namespace
-
+// workspace of render_poses: prims_dev = render_prim_ints(NP) ints, maxima = B * K floats (hm only)
 size_t render_prim_ints(int NP) { return (size_t)(NP > 0 ? NP : 1) * 8; }
 
+// src / out: the packed buffers; desc HOST int64 [B][3]; prims HOST int32 [NP][8] sorted by image; geom HOST int32 [B][4], heat_mask HOST [K] (hm only).
+// Every entry has been checked by the entry point.  The host arrays are read before the call returns; ceil(NP / 120) upload launches, one launch
+// for the maxima (hm), one launch per kRenderMax images.  out == src is allowed.
 hipError_t render_poses(const uint8_t* src, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP, int32_t* prims_dev,
                         const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain,
                         float* maxima, hipStream_t st) {
@@ -296,4 +300,64 @@ hipError_t render_poses(const uint8_t* src, const int64_t* desc, int B, uint8_t*
   return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace jcm
+
+using namespace jcm;
+
+extern "C" {
+
+int jcm_render_poses(jcm_handle h, const uint8_t* src, int64_t src_bytes, const int64_t* desc, int B, uint8_t* out, const int32_t* prims, int NP,
+                     const float* hm, int hh, int hw, int K, int stride, const int32_t* geom, const uint8_t* heat_mask, int heat_gain) {
+  JCM_TRY(check(h, false));
+  const std::string who = "render_poses";
+  if (!src || !desc || !out) return fail(JCM_ERR_ARG, who + ": null pointer (src, desc and out are required)");
+  if (B < 1 || src_bytes < 1) return fail(JCM_ERR_ARG, who + ": B >= 1 images in src_bytes >= 1 bytes are expected");
+  for (int b = 0; b < B; ++b) {
+    const int64_t off = desc[b * (int64_t)3], hb = desc[b * (int64_t)3 + 1], wb = desc[b * (int64_t)3 + 2];
+    const std::string img = who + ": image " + std::to_string(b);
+    if (hb < 1 || hb > 16384 || wb < 1 || wb > 16384)
+      return fail(JCM_ERR_ARG, img + " is " + std::to_string(hb) + " x " + std::to_string(wb) + "; both sides lie in 1..16384");
+    if (off < 0 || off > src_bytes || hb * wb * 3 > src_bytes - off)
+      return fail(JCM_ERR_ARG, img + " (" + std::to_string(hb * wb * 3) + " bytes at offset " + std::to_string(off) + ") does not lie inside the " +
+                                   std::to_string(src_bytes) + " bytes of src");
+  }
+  if (out != src && ranges_overlap(src, (size_t)src_bytes, out, (size_t)src_bytes))
+    return fail(JCM_ERR_ARG, who + ": out overlaps src in part (out == src, in place, is allowed)");
+  if (NP < 0 || (NP > 0 && !prims)) return fail(JCM_ERR_ARG, who + ": NP >= 0 primitives are expected, and prims with NP > 0");
+  constexpr int32_t kCoord = 1 << 20;
+  for (int i = 0, run = 0; i < NP; ++i) {
+    const int32_t* p = prims + i * (int64_t)8;
+    const std::string prim = who + ": primitive " + std::to_string(i);
+    if (p[0] < 0 || p[0] >= B || (i > 0 && p[0] < p[-8]))
+      return fail(JCM_ERR_ARG, prim + " names image " + std::to_string(p[0]) + "; the images are 0.." + std::to_string(B - 1) + " and the list is sorted by image");
+    run = i > 0 && p[0] == p[-8] ? run + 1 : 1;
+    if (run > kRenderPrimMax) return fail(JCM_ERR_ARG, who + ": image " + std::to_string(p[0]) + " has more than " + std::to_string(kRenderPrimMax) + " primitives");
+    for (int k = 1; k <= 4; ++k)
+      if (p[k] < -kCoord || p[k] > kCoord) return fail(JCM_ERR_ARG, prim + ": coordinate " + std::to_string(p[k]) + " outside +-2^20 sixteenths of a pixel");
+    if (p[5] < 0 || p[5] > (1 << 16)) return fail(JCM_ERR_ARG, prim + ": r = " + std::to_string(p[5]) + " outside 0..2^16");
+    if (p[6] < 0 || p[6] > 0xFFFFFF) return fail(JCM_ERR_ARG, prim + ": rgb outside 0..0xFFFFFF");
+    if (p[7] < 0 || p[7] > 255) return fail(JCM_ERR_ARG, prim + ": alpha = " + std::to_string(p[7]) + " outside 0..255");
+  }
+  if (hm) {
+    if (!geom || !heat_mask) return fail(JCM_ERR_ARG, who + ": hm needs geom and heat_mask");
+    if (K < 1 || K > 16 || hh < 1 || hw < 1 || stride < 1 || heat_gain < 0 || heat_gain > 255)
+      return fail(JCM_ERR_ARG, who + ": hm needs K in 1..16, hh, hw and stride >= 1 and heat_gain in 0..255");
+    if ((int64_t)B * hh * hw * K >= ((int64_t)1 << 31)) return fail(JCM_ERR_ARG, who + ": B * hh * hw * K >= 2^31");
+    for (int b = 0; b < B; ++b)
+      if (geom[b * (int64_t)4 + 2] < 1 || geom[b * (int64_t)4 + 3] < 1)
+        return fail(JCM_ERR_ARG, who + ": geom row " + std::to_string(b) + " has a content rectangle without a pixel");
+  }
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  int32_t* prims_dev = nullptr;
+  float* maxima = nullptr;
+  return arena_launch(c, who, [&] {
+    prims_dev = arena_alloc<int32_t>(c, render_prim_ints(NP));
+    if (hm) maxima = arena_alloc<float>(c, (size_t)B * K);
+  }, [&] { return render_poses(src, desc, B, out, prims, NP, prims_dev, hm, hh, hw, K, stride, geom, heat_mask, heat_gain, maxima, c->stream); });
+}
+
+}  // extern "C"

@@ -1,10 +1,11 @@
-// The host side the entry points of the sequence library share (sequence.hip, seq_tracks.hip, seq_smooth.hip): ONE copy of the argument rules, of the
-// workspace refusal and of the launch scaffold, as seq_scan.h is the one copy of the scans.  Host code only; every message is part of the interface.
+// The host side the entry points of the sequence library share (sequence.hip, seq_tracks.hip, seq_smooth.hip): ONE copy of the argument rules and
+// of the taps upload in front of the launch (on entry.h's scaffold), as seq_scan.h is the one copy of the scans.  Host code only; every message is
+// part of the interface.
 #pragma once
 
 #include <string>
 
-#include "ctx.h"
+#include "entry.h"
 
 namespace jcm {
 
@@ -37,33 +38,17 @@ inline int seq_check_joints(const std::string& w, const float* hm, int S, int T,
   }, max_hw, planes, K, "K");
 }
 
-// The workspace grows to hold need_bytes; a clip whose `noun` ("back-pointers", "beliefs") cannot fit in what the device has left is refused.
-inline int workspace_or_refuse(jcm_ctx* c, const std::string& what, double need_bytes, const char* noun, int S, int T) {
-  if (need_bytes <= (double)c->arena_cap) return JCM_OK;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  if (need_bytes > (double)free_b + (double)c->arena_cap)
-    return fail(JCM_ERR_STATE, what + ": the " + noun + " of " + std::to_string(S) + " x " + std::to_string(T) + " frames need " +
-                                   std::to_string((unsigned long long)need_bytes) + " bytes of workspace, " +
-                                   std::to_string((unsigned long long)(free_b + c->arena_cap)) + " bytes are available; split the clip");
-  return JCM_OK;
-}
-
-// Both passes of with_arena: the n_taps device taps come first in the arena, then whatever alloc() takes from it (the sizing pass sees the same
-// calls in the same order); the real pass uploads the taps and runs launch(device taps) between one pair of profile events named `what`.
+// Both passes of with_arena: the n_taps device taps come first in the arena, then whatever alloc() takes from it; the real pass uploads the taps and
+// runs launch(device taps) between one pair of profile events named `what` (entry.h: arena_launch).
 template <class Alloc, class Launch>
 int seq_launch(jcm_ctx* c, const std::string& what, const double* taps, int n_taps, Alloc&& alloc, Launch&& launch) {
-  return with_arena(c, [&] {
-    double* dtaps = arena_alloc<double>(c, (size_t)n_taps);
+  double* dtaps = nullptr;
+  return arena_launch(c, what, [&] {
+    dtaps = arena_alloc<double>(c, (size_t)n_taps);
     alloc();
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    hipError_t e = seq_put_taps(taps, n_taps, dtaps, c->stream);
-    if (e == hipSuccess) e = launch(dtaps);
-    prof_end(c, what, e0, e1, e == hipSuccess);
-    if (e != hipSuccess) return fail(JCM_ERR_HIP, what + ": " + hipGetErrorString(e));
-    return (int)JCM_OK;
+  }, [&] {
+    const hipError_t e = seq_put_taps(taps, n_taps, dtaps, c->stream);
+    return e == hipSuccess ? launch(dtaps) : e;
   });
 }
 

@@ -13,8 +13,10 @@
 //     over the pixels of the primitive's box inside the tile: the 16 sub-sample test and the texture hash run for those pixels only.
 //   * records and primitives travel in the arguments of small launches into workspace (SynthPut, as render.hip's RenderPut): nothing is copied
 //     from caller-owned host memory asynchronously.
+#include <string>
+
 #include "coverage.h"
-#include "kernels.h"
+#include "entry.h"
 #include "u8.h"
 
 namespace jcm {
@@ -289,8 +291,9 @@ void synth_put(const int32_t* host, size_t n, int32_t* dev, hipStream_t st) {
   }
 }
 
-}  // namespace
-
+// records HOST int32 [B][20], prims HOST int32 [NP][16], every entry checked by the entry point; both are read before the call returns: they go
+// into records_dev (B * 20 ints) and prims_dev (max(NP, 1) * 16 ints) of the workspace by ceil(n / 960) small launches that carry them in their
+// arguments.  out: uint8 [B,H,W,3], or float32 (out_f32) = byte / 255.  One more launch.
 hipError_t synth_people(const int32_t* records, int B, const int32_t* prims, int NP, int H, int W, bool out_f32, void* out, int32_t* records_dev,
                         int32_t* prims_dev, hipStream_t st) {
   synth_put(records, (size_t)B * kSynthRecInts, records_dev, st);
@@ -302,4 +305,61 @@ hipError_t synth_people(const int32_t* records, int B, const int32_t* prims, int
   return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace jcm
+
+using namespace jcm;
+
+extern "C" {
+
+int jcm_synth_people(jcm_handle h, const int32_t* records, int B, const int32_t* prims, int NP, int H, int W, int out_f32, void* out) {
+  JCM_TRY(check(h, false));
+  const std::string who = "synth_people";
+  if (!records || !out) return fail(JCM_ERR_ARG, who + ": null pointer (records and out are required)");
+  if (B < 1 || B > 65535) return fail(JCM_ERR_ARG, who + ": B = " + std::to_string(B) + " outside 1..65535");
+  if (H < 1 || W < 1) return fail(JCM_ERR_ARG, who + ": H and W >= 1 are expected, got " + std::to_string(H) + " x " + std::to_string(W));
+  if ((int64_t)H * W > (int64_t)INT32_MAX) return fail(JCM_ERR_ARG, who + ": H * W = " + std::to_string((int64_t)H * W) + " is over the int32 range");
+  if (NP < 0 || (NP > 0 && !prims)) return fail(JCM_ERR_ARG, who + ": NP >= 0 primitives are expected, and prims with NP > 0");
+  if (out_f32 && (reinterpret_cast<uintptr_t>(out) & 3u)) return fail(JCM_ERR_ARG, who + ": a float32 out is 4-byte aligned");
+  auto byte = [](int32_t v) { return v >= 0 && v <= 255; };
+  for (int b = 0; b < B; ++b) {
+    const int32_t* r = records + b * (int64_t)kSynthRecInts;
+    const std::string img = who + ": image " + std::to_string(b);
+    for (int k = 1; k <= 6; ++k)
+      if (!byte(r[k])) return fail(JCM_ERR_ARG, img + ": background colour " + std::to_string(r[k]) + " outside 0..255");
+    for (int o = 0; o < 4; ++o) {
+      if (!byte(r[7 + o])) return fail(JCM_ERR_ARG, img + ": octave amplitude " + std::to_string(r[7 + o]) + " outside 0..255");
+      if (r[11 + o] < 0 || r[11 + o] > 8) return fail(JCM_ERR_ARG, img + ": octave shift " + std::to_string(r[11 + o]) + " outside 0..8");
+    }
+    if (!byte(r[15])) return fail(JCM_ERR_ARG, img + ": sensor-noise amplitude " + std::to_string(r[15]) + " outside 0..255");
+    if (r[16] < 0 || r[16] > kSynthPrimMax)
+      return fail(JCM_ERR_ARG, img + ": n = " + std::to_string(r[16]) + " primitives outside 0.." + std::to_string(kSynthPrimMax));
+    if (r[17] < 0 || (int64_t)r[17] + r[16] > NP)
+      return fail(JCM_ERR_ARG, img + ": primitives " + std::to_string(r[17]) + ".." + std::to_string((int64_t)r[17] + r[16]) + " do not lie inside the " +
+                                   std::to_string(NP) + " of prims");
+  }
+  constexpr int32_t kCoord = 1 << 20;
+  for (int i = 0; i < NP; ++i) {
+    const int32_t* p = prims + i * (int64_t)kSynthPrimInts;
+    const std::string prim = who + ": primitive " + std::to_string(i);
+    if (p[0] != 0 && p[0] != 1) return fail(JCM_ERR_ARG, prim + ": kind " + std::to_string(p[0]) + " is neither 0 (capsule) nor 1 (quadrilateral)");
+    for (int k = 1; k <= (p[0] == 0 ? 4 : 8); ++k)
+      if (p[k] < -kCoord || p[k] > kCoord) return fail(JCM_ERR_ARG, prim + ": coordinate " + std::to_string(p[k]) + " outside +-2^20 sixteenths of a pixel");
+    if (p[0] == 0 && (p[5] < 0 || p[5] > (1 << 16))) return fail(JCM_ERR_ARG, prim + ": r = " + std::to_string(p[5]) + " outside 0..2^16");
+    for (int k = 9; k <= 11; ++k)
+      if (!byte(p[k])) return fail(JCM_ERR_ARG, prim + ": colour " + std::to_string(p[k]) + " outside 0..255");
+    if (!byte(p[12])) return fail(JCM_ERR_ARG, prim + ": texture amplitude " + std::to_string(p[12]) + " outside 0..255");
+    if (p[13] < 0 || p[13] > 8) return fail(JCM_ERR_ARG, prim + ": texture shift " + std::to_string(p[13]) + " outside 0..8");
+  }
+  DeviceGuard g(h->device);
+  CallOrder order(h);
+  jcm_ctx* c = h;
+  int32_t *records_dev = nullptr, *prims_dev = nullptr;
+  return arena_launch(c, who, [&] {
+    records_dev = arena_alloc<int32_t>(c, (size_t)B * kSynthRecInts);
+    prims_dev = arena_alloc<int32_t>(c, (size_t)(NP > 0 ? NP : 1) * kSynthPrimInts);
+  }, [&] { return synth_people(records, B, prims, NP, H, W, out_f32 != 0, out, records_dev, prims_dev, c->stream); });
+}
+
+}  // extern "C"

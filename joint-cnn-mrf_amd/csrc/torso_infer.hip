@@ -17,7 +17,7 @@
 // No atomics; every store is a vector store of plain C++.
 #include <string>
 
-#include "ctx.h"
+#include "entry.h"
 #include "sm_lds_fft.h"
 
 namespace jcm {
@@ -193,25 +193,12 @@ int jcm_torso_infer(jcm_handle h, const float* prob, int B, int HH, int WW, int 
   DeviceGuard g(h->device);
   CallOrder order(h);
   jcm_ctx* c = h;
-  if (cells_in) {
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const hipError_t launch = torso_blobs(cells_in, B, torso, c->stream);
-    prof_end(c, "torso_infer", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("torso_infer: ") + hipGetErrorString(launch));
-    return JCM_OK;
-  }
-  return with_arena(c, [&] {
-    float* lik = arena_alloc<float>(c, (size_t)B * kTiK * kHmH * kTiLP);
-    float* corr = arena_alloc<float>(c, (size_t)B * kTiK * kHmHW);
-    if (c->dry) return (int)JCM_OK;
-    hipEvent_t e0, e1;
-    JCM_TRY(prof_begin(c, &e0, &e1));
-    const hipError_t launch = torso_infer_direct(prob, B, c->sp_energy, c->bn_sm_scale, c->bn_sm_shift, lik, corr, energy, cell, torso, c->stream);
-    prof_end(c, "torso_infer", e0, e1, launch == hipSuccess);
-    if (launch != hipSuccess) return fail(JCM_ERR_HIP, std::string("torso_infer: ") + hipGetErrorString(launch));
-    return (int)JCM_OK;
-  });
+  if (cells_in) return timed_launch(c, "torso_infer", [&] { return torso_blobs(cells_in, B, torso, c->stream); });
+  float *lik = nullptr, *corr = nullptr;
+  return arena_launch(c, "torso_infer", [&] {
+    lik = arena_alloc<float>(c, (size_t)B * kTiK * kHmH * kTiLP);
+    corr = arena_alloc<float>(c, (size_t)B * kTiK * kHmHW);
+  }, [&] { return torso_infer_direct(prob, B, c->sp_energy, c->bn_sm_scale, c->bn_sm_shift, lik, corr, energy, cell, torso, c->stream); });
 }
 
 }  // extern "C"
