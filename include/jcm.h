@@ -395,6 +395,36 @@ int jcm_seq_filter_moving(jcm_handle h, const float* hm, int S, int T, int HH, i
 int jcm_seq_viterbi_moving(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
                            const int32_t* shift, int32_t* path, double* maxes, int32_t* breaks);
 
+/* -- frame sequences centred on a per-cell motion estimate: a lattice shift per cell, not per frame --
+ * jcm_seq_filter_moving / jcm_seq_viterbi_moving with the shift read per DESTINATION cell: every argument as there, except centre: device int32
+ * [S,T,HH,WW,2] = (sy, sx), aligned to 8 bytes: cell (y, x) of frame t was cell (y + sy, x + sx) of frame t-1 -- the sign convention of shift, of
+ * jcm_frame_shift's disp and of jcm_frame_flow's flow.  One table serves all K joints.  The definition is the text above, word for word, with
+ * (sy, sx) = centre[s,t,y,x] where it says shift[s,t]; each component is clamped to +-(HH + R) / +-(WW + R), beyond which no tap reaches the map.
+ * Filter, per cell (y, x):
+ *   for dx = -R .. R ascending, x' = x - dx + sx inside [0, WW):
+ *     c = sum over dy = -R .. R, ascending from 0.0, of w[dy+R] * a_{t-1}(y - dy + sy, x')      rows outside the map skipped; no row inside: c = 0.0
+ *     m = m + w[dx+R] * c                                                                       from 0.0; the term is added also when c = 0.0
+ *   pred = om * m + u;  b = p_t * pred;  Z in the kernel's fixed order, resets, the division, the arg-max, state_in / state_out and every output:
+ *   exactly jcm_seq_filter.  centre[s,0] applies to the transition from state_in and is ignored when state_in is NULL.
+ * Viterbi, per cell: c(x') = max over dy of w[dy+R] * d_{t-1}(y - dy + sy, x'), m = max over dx of w[dx+R] * c(x - dx + sx): ascending scans over the
+ *   terms inside the map, a strictly greater value replaces, a maximum over no term is 0.  source cell = (y - dy* + sy, x - dx* + sx) with dy* that of
+ *   the winning column; where m is not above 0 the source is the jump's; the jump wins only when strictly greater.  b, M, breaks and the backtrace
+ *   are unchanged.  centre[s,0] is never read.
+ * Two consequences are part of the contract: a table with the same (sy, sx) in every cell of every frame gives the bits of the *_moving entries
+ * with that shift, on every output; an all-zero table gives the bits of jcm_seq_filter / jcm_seq_viterbi.
+ * The transition is GATHERED per destination cell: where the table is not uniform, the mass that leaves a cell of frame t-1 does not sum to that
+ * of the kernel -- two cells may be centred on the same source, a source may be nobody's centre -- so it is no stochastic matrix (as the clipped taps
+ * of the entries above are none at the border).  The filter normalises every frame anyway; norm is the Z of this transition.
+ * Any int32 pair is legal.  No tap outside the plane is indexed; none is multiplied by zero instead of being skipped.  Two float64 planes live in
+ * LDS (Viterbi stores each source cell as it is found and keeps no byte plane); the limits are those of jcm_seq_filter all the same.
+ * JCM_ERR_ARG / JCM_ERR_STATE as for jcm_seq_filter / jcm_seq_viterbi, and JCM_ERR_ARG -- nothing is launched, no output is touched -- for
+ * centre == NULL or a centre that is not aligned to 8 bytes (a cell's pair is one load). */
+int jcm_seq_filter_centred(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                           const int32_t* centre, const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset,
+                           double* state_out);
+int jcm_seq_viterbi_centred(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
+                            const int32_t* centre, int32_t* path, double* maxes, int32_t* breaks);
+
 /* -- frame sequences, offline: smoothed marginals and expected transition statistics -----------
  * The third inference of the model above: gamma_t = P(x_t | all T frames) per (s, k), and from the same backward pass the posterior mass of
  * "moved" and of "jumped" and the expected squared displacement of every transition, from which sigma (per joint) and rho are re-estimated on

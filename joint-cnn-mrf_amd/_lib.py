@@ -62,6 +62,11 @@ SIGNATURES = {
                                              ctypes.c_void_p, _c_i32_p, ctypes.c_void_p]),
     'jcm_seq_viterbi_moving': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, _c_i32_p, _c_i32_p, ctypes.c_void_p, _c_i32_p]),
+    'jcm_seq_filter_centred': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, _c_i32_p, ctypes.c_void_p, _c_float_p, _c_i32_p,
+                                              ctypes.c_void_p, _c_i32_p, ctypes.c_void_p]),
+    'jcm_seq_viterbi_centred': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, _c_i32_p, _c_i32_p, ctypes.c_void_p, _c_i32_p]),
     'jcm_seq_smooth': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                       ctypes.c_int, ctypes.c_double, _c_float_p, _c_i32_p, _c_float_p, ctypes.c_void_p, _c_i32_p, ctypes.c_void_p, _c_i32_p,
                                       ctypes.c_void_p]),

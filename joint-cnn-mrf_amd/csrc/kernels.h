@@ -409,6 +409,15 @@ hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, cons
 // shift as for seq_filter (jcm.h: jcm_seq_viterbi_moving).
 hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* shift,
                        int16_t* bp, int32_t* amax, int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
+// Viterbi's second launch, one lane per (sequence, joint): bp and amax as the scan's launch left them -> path int32 [S][T][2][K] (seq_centred.hip shares it)
+hipError_t seq_backtrace(const int16_t* bp, const int32_t* amax, int S, int T, int HW, int WW, int K, int32_t* path, hipStream_t st);
+// ---- seq_centred.hip : the same filter and track with the shift read per destination cell --
+// centre: device int32 [S][T][HH][WW][2] = (sy, sx), aligned to 8 bytes, required (jcm.h: jcm_seq_filter_centred / jcm_seq_viterbi_centred); every other
+// argument as for seq_filter / seq_viterbi.  Two float64 planes in LDS and one pass of (2R+1)^2 reads per cell; the same limits.
+hipError_t seq_filter_centred(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* centre,
+                              const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st);
+hipError_t seq_viterbi_centred(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* centre,
+                               int16_t* bp, int32_t* amax, int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
 // ---- seq_smooth.hip : the smoothed marginals and the expected transition statistics --
 // Two launches, one work group per (sequence, joint) each: the filter's scan (seq_scan.h) that also writes every a_t to belief float64 [S*K][T][HH*WW],
 // then the backward scan with three float64 planes in LDS for all T frames, so HH * WW <= kSeqSmoothMaxHW (3 * 48 KB + the reduction scratch of 160 KB).

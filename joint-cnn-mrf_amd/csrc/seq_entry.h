@@ -1,4 +1,4 @@
-// The host side the entry points of the sequence library share (sequence.hip, seq_tracks.hip, seq_smooth.hip): ONE copy of the argument rules and
+// The host side the entry points of the sequence library share (sequence.hip, seq_centred.hip, seq_tracks.hip, seq_smooth.hip): ONE copy of the argument rules and
 // of the taps upload in front of the launch (on entry.h's scaffold), as seq_scan.h is the one copy of the scans.  Host code only; every message is
 // part of the interface.
 #pragma once

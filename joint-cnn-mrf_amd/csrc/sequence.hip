@@ -4,6 +4,7 @@
 // One work group per (sequence, joint) scans the T frames of a launch; the scan itself -- planes, staging, reductions, back-pointers -- is seq_scan.h,
 // which seq_tracks.hip shares.  Here: its kernels on the map as it is (SqPlain), the backtrace launch, the tap upload and the entry points.
 // The *_moving kernels are the same scans with SqShift: every frame's lattice lies a whole number of cells from the one before.
+// seq_centred.hip (a shift per cell) has a pass of its own and shares the backtrace launch, seq_backtrace.
 #include <string>
 
 #include "seq_entry.h"
@@ -87,6 +88,12 @@ hipError_t seq_put_taps(const double* taps_host, int n, double* taps_dev, hipStr
   return hipGetLastError();
 }
 
+hipError_t seq_backtrace(const int16_t* bp, const int32_t* amax, int S, int T, int HW, int WW, int K, int32_t* path, hipStream_t st) {
+  const int G = S * K;
+  hipLaunchKernelGGL(seq_backtrace_kernel, dim3((G + 63) / 64), dim3(64), 0, st, bp, amax, G, T, HW, WW, K, path);
+  return hipGetLastError();
+}
+
 hipError_t seq_filter(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* shift,
                       const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st) {
   if (!sq_sizes_ok(S, T, HH, WW, K, R)) return hipErrorInvalidValue;
@@ -120,9 +127,7 @@ hipError_t seq_viterbi(const float* hm, int S, int T, int HH, int WW, int K, con
     hipLaunchKernelGGL(seq_viterbi_kernel, dim3(S * K), dim3(kSqThreads), 2 * HW * 8 + ((HW + 7) & ~7), st, hm, T, HH, WW, K, taps, R, om, u, bp, amax, maxes,
                        breaks, sq_vec(hm, HW, K) ? 1 : 0);
   }
-  const int G = S * K;
-  hipLaunchKernelGGL(seq_backtrace_kernel, dim3((G + 63) / 64), dim3(64), 0, st, bp, amax, G, T, HW, WW, K, path);
-  return hipGetLastError();
+  return seq_backtrace(bp, amax, S, T, HW, WW, K, path, st);
 }
 
 }  // namespace jcm

@@ -399,7 +399,24 @@ class Engine:
             raise ValueError('shift must be [S,T,2] = %s (or [T,2] with a 4-d hm), got %s' % ((S, T, 2), tuple(shift.shape)))
         return shift.to(self.device).contiguous()
 
-    def seq_filter(self, hm, sigma, rho, radius=None, state=None, shift=None):
+    def _seq_centre(self, centre, shift, S, T, HH, WW, single):
+        """centre: int32 [T,HH,WW,2] (a 4-d hm) or [S,T,HH,WW,2] = (sy, sx) per cell, host or device -> a contiguous device int32 [S,T,HH,WW,2]."""
+        if shift is not None:
+            raise ValueError('centre and shift are two forms of one thing: a shift per cell or one per frame; give one of them')
+        if not isinstance(centre, torch.Tensor):
+            a = np.asarray(centre)
+            if a.dtype.kind not in 'iu' or a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError('centre must hold int32 values, got %s' % (a.dtype,))
+            centre = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32)))
+        if centre.dtype != torch.int32:
+            raise ValueError('centre must be int32, got %s' % (centre.dtype,))
+        if single and centre.dim() == 4:
+            centre = centre.unsqueeze(0)
+        if tuple(centre.shape) != (S, T, HH, WW, 2):
+            raise ValueError('centre must be [S,T,HH,WW,2] = %s (or [T,HH,WW,2] with a 4-d hm), got %s' % ((S, T, HH, WW, 2), tuple(centre.shape)))
+        return centre.to(self.device).contiguous()
+
+    def seq_filter(self, hm, sigma, rho, radius=None, state=None, shift=None, centre=None):
         """The causal forward filter of a clip's heat maps (include/jcm.h: jcm_seq_filter): hm [T,HH,WW,K] or [S,T,HH,WW,K],
         frame after frame of what forward returns as pd_prob / sm_prob; sigma: a scalar or K values, the motion per frame in heat-map cells
         (motion.seq_taps builds the taps); rho in [0,1]: the mass of the uniform "anywhere" term; radius: default min(16, ceil(3 max sigma));
@@ -409,10 +426,16 @@ class Engine:
         library.
         shift: None, or int32 [T,2] / [S,T,2] = (sy, sx) on the host or the device, for maps whose lattice moves (include/jcm.h:
         jcm_seq_filter_moving): cell (y, x) of frame t is cell (y + sy, x + sx) of frame t-1; shift[0] applies to the transition from `state`
-        and is ignored without one.  'coords' are in every frame's own lattice, 'state' in the last frame's."""
+        and is ignored without one.  'coords' are in every frame's own lattice, 'state' in the last frame's.
+        centre: None, or int32 [T,HH,WW,2] / [S,T,HH,WW,2] = (sy, sx) on the host or the device: the same shift per DESTINATION cell (DESIGN.md 4.29,
+        include/jcm.h: jcm_seq_filter_centred) -- cell (y, x) of frame t was cell (y + sy, x + sx) of frame t-1, one table for all joints
+        (motion.flow_cell_shifts makes one of Engine.frame_flow's output); centre[0] applies to the transition from `state` and is ignored without
+        one.  A table that is uniform over every frame gives the bits of shift=, an all-zero table those of a call without either.  centre with shift is a ValueError."""
         hm5, single, taps, R = self._seq_args(hm, sigma, radius)
         S, T, HH, WW, K = hm5.shape
-        if shift is not None:
+        if centre is not None:
+            centre = self._seq_centre(centre, shift, S, T, HH, WW, single)
+        elif shift is not None:
             shift = self._seq_shift(shift, S, T, single)
         if state is not None:
             state = self._chk(state.unsqueeze(0) if single and isinstance(state, torch.Tensor) and state.dim() == 3 else state, 4, 'state', torch.float64)
@@ -420,30 +443,37 @@ class Engine:
                 raise ValueError('state must be [S,K,HH,WW] = %s, got %s' % ((S, K, HH, WW), tuple(state.shape)))
         out = {'filtered': self._new(S, T, HH, WW, K), 'coords': self._new(S, T, 2, K, dtype=torch.int32), 'norm': self._new(S, T, K, dtype=torch.float64),
                'reset': self._new(S, T, K, dtype=torch.int32), 'state': self._new(S, K, HH, WW, dtype=torch.float64)}
-        self._on_stream(hm5, *([state] if state is not None else []), *([shift] if shift is not None else []), *out.values())
+        self._on_stream(hm5, *(t for t in (state, shift, centre) if t is not None), *out.values())
         tp = taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         tail = (self._p(state), self._p(out['filtered']), self._p(out['coords']), self._p(out['norm']), self._p(out['reset']), self._p(out['state']))
-        if shift is not None:
+        if centre is not None:
+            _lib.check(self._lib.jcm_seq_filter_centred(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), self._p(centre), *tail), 'jcm_seq_filter_centred')
+        elif shift is not None:
             _lib.check(self._lib.jcm_seq_filter_moving(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), self._p(shift), *tail), 'jcm_seq_filter_moving')
         else:
             _lib.check(self._lib.jcm_seq_filter(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), *tail), 'jcm_seq_filter')
         return {k: v[0] for k, v in out.items()} if single else out
 
-    def seq_viterbi(self, hm, sigma, rho, radius=None, shift=None):
+    def seq_viterbi(self, hm, sigma, rho, radius=None, shift=None, centre=None):
         """The most probable track through a clip's heat maps (include/jcm.h: jcm_seq_viterbi); hm, sigma, rho and radius as for
         seq_filter.  Returns {'path' int32 [S,T,2,K] (row, col), 'maxes' float64 [S,T,K], 'breaks' int32 [S,T,K]}, device tensors without the S
         axis for a 4-d hm; nothing is read back.  The back-pointers (2 bytes per cell, frame, joint and sequence) live in the engine's
         workspace; a clip they do not fit in is a RuntimeError that names the bytes.
-        shift: as for seq_filter (include/jcm.h: jcm_seq_viterbi_moving); 'path' is in every frame's own lattice, shift[0] is ignored."""
+        shift: as for seq_filter (include/jcm.h: jcm_seq_viterbi_moving); 'path' is in every frame's own lattice, shift[0] is ignored.
+        centre: as for seq_filter (include/jcm.h: jcm_seq_viterbi_centred); centre[0] is never read.  centre with shift is a ValueError."""
         hm5, single, taps, R = self._seq_args(hm, sigma, radius)
         S, T, HH, WW, K = hm5.shape
-        if shift is not None:
+        if centre is not None:
+            centre = self._seq_centre(centre, shift, S, T, HH, WW, single)
+        elif shift is not None:
             shift = self._seq_shift(shift, S, T, single)
         out = {'path': self._new(S, T, 2, K, dtype=torch.int32), 'maxes': self._new(S, T, K, dtype=torch.float64), 'breaks': self._new(S, T, K, dtype=torch.int32)}
-        self._on_stream(hm5, *([shift] if shift is not None else []), *out.values())
+        self._on_stream(hm5, *(t for t in (shift, centre) if t is not None), *out.values())
         tp = taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         tail = (self._p(out['path']), self._p(out['maxes']), self._p(out['breaks']))
-        if shift is not None:
+        if centre is not None:
+            _lib.check(self._lib.jcm_seq_viterbi_centred(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), self._p(centre), *tail), 'jcm_seq_viterbi_centred')
+        elif shift is not None:
             _lib.check(self._lib.jcm_seq_viterbi_moving(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), self._p(shift), *tail), 'jcm_seq_viterbi_moving')
         else:
             _lib.check(self._lib.jcm_seq_viterbi(self._h, self._p(hm5), S, T, HH, WW, K, tp, R, float(rho), *tail), 'jcm_seq_viterbi')

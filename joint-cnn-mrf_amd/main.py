@@ -159,8 +159,13 @@ def build_parser():
                         '(Engine.frame_flow, Engine.hm_flow_pool, DESIGN.md 4.28), and run the mode on the pooled maps; the document gains "flow" per file, the JSON '
                         'line seq_flow and seq_flow_search.  Block matching on luma, whole pixels, no occlusion reasoning.  Not with --sequence lag, --seq_zoom or '
                         '--seq_people.')
-    parser.add_argument('--seq_flow_search', type=int, default=None, metavar='D', help='with --seq_flow: the search radius in 1..16 fitted pixels a frame (default 8, an '
-                        'untuned placeholder).')
+    parser.add_argument('--seq_flow_search', type=int, default=None, metavar='D', help='with --seq_flow or --seq_flow_centre: the search radius in 1..16 fitted pixels a '
+                        'frame (default 8, an untuned placeholder).')
+    parser.add_argument('--seq_flow_centre', action='store_true', help='with --sequence filter or viterbi: centre every cell\'s motion kernel on where the cell\'s own '
+                        'content was in the frame before (DESIGN.md 4.29): one displacement per heat-map cell against the frame before (Engine.frame_flow), rounded '
+                        'to whole cells, fed to the scans as centre= (Engine.seq_filter / seq_viterbi).  With --seq_flow N as well the pooling\'s own matching is '
+                        'reused and the scan runs on the pooled maps.  The document gains "flow_centre" per file, the JSON line seq_flow_centre, the search radius; '
+                        'with --render the drawn track is the centred one.  Not with --seq_camera, --seq_zoom, --seq_people, --seq_fit or --sequence marginal / lag.')
     parser.add_argument('--seq_torso_sigma', type=float, default=None, metavar='CELLS', help='with --seq_people: the standard deviation of a torso\'s motion per '
                         'frame in heat-map cells (default 1.5, an untuned placeholder).')
     parser.add_argument('--seq_exclude', type=int, default=None, metavar='CELLS', help='with --seq_people: the half-width in 0..64 heat-map cells of the square '
@@ -405,6 +410,12 @@ SEQ_FLOW_NO_LAG = '--seq_flow cannot be combined with --sequence lag: two-sided 
 SEQ_FLOW_NO_ZOOM = '--seq_flow cannot be combined with --seq_zoom: the zoom windows move the lattice from frame to frame'
 SEQ_FLOW_NO_PEOPLE = '--seq_flow cannot be combined with --seq_people: every track has maps of its own, and pooling per track is out of scope'
 SEQ_FLOW_SEARCH_NEEDS_SEQ_FLOW = '--seq_flow_search sets the search radius of --seq_flow: give --seq_flow N as well'
+SEQ_FLOW_CENTRE_NEEDS_SEQUENCE = '--seq_flow_centre centres the scan of the clip --sequence names: give --sequence filter or --sequence viterbi as well'
+SEQ_FLOW_CENTRE_NO_SMOOTHER = '--seq_flow_centre cannot be combined with --sequence marginal or lag: the smoother has no form for a shift per cell'
+SEQ_FLOW_CENTRE_NO_FIT = '--seq_flow_centre cannot be combined with --seq_fit: the fit runs on the smoother, which has no form for a shift per cell'
+SEQ_FLOW_CENTRE_NO_CAMERA = '--seq_flow_centre cannot be combined with --seq_camera: the flow of a cell already contains the pan'
+SEQ_FLOW_CENTRE_NO_ZOOM = '--seq_flow_centre cannot be combined with --seq_zoom: the zoom windows move the lattice from frame to frame'
+SEQ_FLOW_CENTRE_NO_PEOPLE = '--seq_flow_centre cannot be combined with --seq_people: the torso passes have no form for a shift per cell'
 SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
@@ -436,7 +447,8 @@ def predict_main(args):
     (predict.predict_sequence_zoom) "zoom" and "track_zoom", the pictures show the skeleton tracked through the windows where the clip was zoomed, and the line
     gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms; with --sequence lag --seq_lag L the line gains seq_lag; with --seq_camera the document gains
     "camera" per file and the line seq_camera, the search radius; with --seq_flow N the document gains "flow" per file and the line seq_flow
-    and seq_flow_search."""
+    and seq_flow_search; with --seq_flow_centre the document gains "flow_centre" per file and the line seq_flow_centre, the search radius --
+    'track', which --render draws, is the centred one."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -465,6 +477,8 @@ def predict_main(args):
                     seq.update(camera=True, camera_search=predict.SEQ_CAMERA_SEARCH if args.seq_camera_search is None else args.seq_camera_search)
                 if args.seq_flow is not None:
                     seq.update(flow=args.seq_flow, flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
+                if args.seq_flow_centre:
+                    seq.update(flow_centre=True, flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
                 results = predict.predict_sequence(eng, images, use_sm=args.use_sm, **seq)
         else:
             results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
@@ -490,6 +504,8 @@ def predict_main(args):
         line.update(seq_camera=predict.SEQ_CAMERA_SEARCH if args.seq_camera_search is None else args.seq_camera_search)
     if args.seq_flow is not None:
         line.update(seq_flow=args.seq_flow, seq_flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
+    if args.seq_flow_centre:
+        line.update(seq_flow_centre=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
     if args.seq_people is not None:
         line.update(seq_people=args.seq_people, seq_torso_ms=timing['seq_torso_ms'], seq_people_sm_ms=timing['seq_people_sm_ms'])
     if args.seq_zoom:
@@ -835,7 +851,7 @@ EVAL_SCALE_RULES = (
 )
 # The rules of --seq_flow, walked behind EVAL_SCALE_RULES (a table of their own for the same reason).
 SEQ_FLOW_RULES = (
-    (lambda a: a.seq_flow_search is not None and a.seq_flow is None, SEQ_FLOW_SEARCH_NEEDS_SEQ_FLOW),
+    (lambda a: a.seq_flow_search is not None and a.seq_flow is None and not a.seq_flow_centre, SEQ_FLOW_SEARCH_NEEDS_SEQ_FLOW),
     (lambda a: a.seq_flow is not None and not a.sequence, SEQ_FLOW_NEEDS_SEQUENCE),
     (lambda a: a.seq_flow is not None and a.sequence == 'lag', SEQ_FLOW_NO_LAG),
     (lambda a: a.seq_flow is not None and a.seq_zoom, SEQ_FLOW_NO_ZOOM),
@@ -843,13 +859,22 @@ SEQ_FLOW_RULES = (
     (lambda a: a.seq_flow is not None and not 1 <= a.seq_flow <= 4, lambda a: '--seq_flow %d: 1 <= N <= 4' % a.seq_flow),
     (lambda a: a.seq_flow_search is not None and not 1 <= a.seq_flow_search <= 16, lambda a: '--seq_flow_search %d: 1 <= D <= 16' % a.seq_flow_search),
 )
+# The rules of --seq_flow_centre, walked behind SEQ_FLOW_RULES (a table of their own for the same reason).
+SEQ_FLOW_CENTRE_RULES = (
+    (lambda a: a.seq_flow_centre and not a.sequence, SEQ_FLOW_CENTRE_NEEDS_SEQUENCE),
+    (lambda a: a.seq_flow_centre and a.sequence in ('marginal', 'lag'), SEQ_FLOW_CENTRE_NO_SMOOTHER),
+    (lambda a: a.seq_flow_centre and a.seq_fit is not None, SEQ_FLOW_CENTRE_NO_FIT),
+    (lambda a: a.seq_flow_centre and a.seq_camera, SEQ_FLOW_CENTRE_NO_CAMERA),
+    (lambda a: a.seq_flow_centre and a.seq_zoom, SEQ_FLOW_CENTRE_NO_ZOOM),
+    (lambda a: a.seq_flow_centre and a.seq_people is not None, SEQ_FLOW_CENTRE_NO_PEOPLE),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES + EVAL_SCALE_RULES + SEQ_FLOW_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES + EVAL_SCALE_RULES + SEQ_FLOW_RULES + SEQ_FLOW_CENTRE_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

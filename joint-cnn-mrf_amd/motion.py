@@ -72,6 +72,26 @@ def flow_weights(N):
     return np.ones(_flow_n(N) + 1, np.float64)
 
 
+def flow_cell_shifts(flow, stride=8):
+    """One slot of Engine.frame_flow's 'flow', int [T,HH,WW,2] = (dy, dx) in fitted-frame pixels -> int32 of the same shape = (sy, sx) in heat-map
+    cells: the `centre` of Engine.seq_filter / seq_viterbi.  The rule, per component d:
+      s = floor((d + stride // 2) / stride)      floor division in integer arithmetic: the nearest cell, a half rounds up
+    so with stride 8: 3 -> 0, 4 -> 1, -4 -> 0, -5 -> -1.  The signs agree as they are: the content at pixel (y, x) of frame t is at (y + dy, x + dx) of
+    the reference frame, and cell (y, x) of frame t was cell (y + sy, x + sx) of frame t-1 when the slot's reference is t-1.  flow: a torch tensor
+    (the arithmetic runs on its own device, nothing is read back) or a numpy array.  A whole-pixel flow becomes whole cells: what is left, at most
+    half a cell, is motion the taps (sigma) have to cover."""
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError('stride must be >= 1, got %r' % (stride,))
+    if isinstance(flow, np.ndarray):
+        if flow.dtype.kind not in 'iu':
+            raise ValueError('flow must be an integer array, got %s' % (flow.dtype,))
+        return ((flow.astype(np.int64) + stride // 2) // stride).astype(np.int32)
+    if flow.dtype.is_floating_point or flow.dtype.is_complex:      # a torch tensor: this module does not import torch
+        raise ValueError('flow must be an integer tensor, got %s' % (flow.dtype,))
+    return ((flow.long() + stride // 2) // stride).int()
+
+
 def _seq_sigma(sigma, K=None):
     sg = np.asarray(sigma, np.float64).reshape(-1)
     if sg.size == 0 or not np.all(np.isfinite(sg)) or np.any(sg <= 0):

@@ -25,13 +25,17 @@ shift=, so that the motion kernel is centred on where the camera's motion takes 
 
 Local motion: predict_sequence(flow=N) estimates one displacement per heat-map cell between every frame and the N frames before
 and after it (Engine.frame_flow), warps those frames' maps onto the frame and pools them with its own (Engine.hm_flow_pool); the chosen mode then
-runs on the pooled maps, which are maps like any other."""
+runs on the pooled maps, which are maps like any other.
+
+Flow-centred scans: predict_sequence(flow_centre=True) and SequenceTracker(flow_centre=True) match every frame against the one before
+it (Engine.frame_flow, the causal slot), round the displacement of every cell to whole cells (motion.flow_cell_shifts) and run the filter or Viterbi
+with centre=, so that the motion kernel of a cell is centred on where that cell's own content was, not on the cell itself."""
 import numpy as np
 import torch
 
 from ..evaluation import fit_to_source, window_to_source
-from ..motion import (SEQ_CAMERA_SEARCH, SEQ_EXCLUDE, SEQ_FLOW_MAX, SEQ_FLOW_SEARCH, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, camera_shifts, flow_refs,
-                      flow_weights, seq_fit)
+from ..motion import (SEQ_CAMERA_SEARCH, SEQ_EXCLUDE, SEQ_FLOW_MAX, SEQ_FLOW_SEARCH, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, camera_shifts,
+                      flow_cell_shifts, flow_refs, flow_weights, seq_fit)
 from .images import FIT_SIDE_MAX, FRAME, STRIDE, ZOOM_TORSO_JOINTS, ZOOM_TORSO_PIXELS, DeviceTimer, _coords_to_points, _upload, predict_images, second_pass, zoom_entry
 
 
@@ -128,12 +132,15 @@ def _check_flow(flow, flow_search, flow_weights_):
     return N, int(flow_search), w
 
 
-def _flow_pool(engine, results, hm, x, N, search, weights):
+def _flow_pool(engine, results, hm, x, N, search, weights, keep=None):
     """The maps of a clip pooled along its local motion: one Engine.frame_flow call on the stacked fitted frames x with
     motion.flow_refs and the clip's content rectangle, one Engine.hm_flow_pool on the stacked maps hm.  Every dict gains 'flow' -- the per-frame
-    arg-max of the pooled maps through fit_to_source -- and its 'maps' 'pooled'.  Returns the pooled maps."""
+    arg-max of the pooled maps through fit_to_source -- and its 'maps' 'pooled'.  Returns the pooled maps; keep, a list, receives the flow
+    [T,2N,HH,WW,2] for a caller who has a second use for it."""
     T = hm.shape[0]
     flow = engine.frame_flow(x, _geom(results)[0, :4], flow_refs(T, N), search=search)['flow']
+    if keep is not None:
+        keep.append(flow)
     pooled = engine.hm_flow_pool(hm, flow, weights)
     pts, inside = fit_to_source(_coords_to_points(engine.argmax_coords(pooled)), _geom(results))
     for t, r in enumerate(results):
@@ -142,9 +149,48 @@ def _flow_pool(engine, results, hm, x, N, search, weights):
     return pooled
 
 
+SEQ_FLOW_CENTRE_MODES = ('filter', 'viterbi')      # the scans that have a centred form
+
+
+def _check_flow_centre(flow_centre, flow_search, mode=None, camera=False, fit_iters=0):
+    """flow_centre and what it cannot go with -> bool; flow_search is looked at only when it is on (flow = N checks its own use of it)."""
+    if not flow_centre:
+        return False
+    if not 1 <= int(flow_search) <= 16:
+        raise ValueError('flow_search must be in 1..16, got %r' % (flow_search,))
+    if mode is not None and mode not in SEQ_FLOW_CENTRE_MODES:
+        raise ValueError("flow_centre=True: mode must be 'filter' or 'viterbi', got %r (the smoother has no centred form)" % (mode,))
+    if camera:
+        raise ValueError('flow_centre=True cannot be combined with camera=True: the flow of a cell already contains the pan')
+    if int(fit_iters) != 0:
+        raise ValueError('flow_centre=True has no fit: fit_iters=%r needs the smoother, which has no centred form' % (fit_iters,))
+    return True
+
+
+def _flow_centre(engine, results, search, x=None, prev=None, flow=None):
+    """The centre table of the frames of `results` (dicts of pass 1 with the fitted frames kept): every frame matched against the one
+    before it -- slot `flow` [T,HH,WW,2] of a frame_flow call the caller has made already, or ONE Engine.frame_flow call here on the stacked frames x
+    with a one-slot ref table and the clip's content rectangle; prev [H,W,3], the last fitted frame of the push before, is stacked in front and its
+    row dropped again --, then motion.flow_cell_shifts.  Every dict gains 'flow_centre'.  Returns (centre int32 [T,HH,WW,2], the stacked frames or
+    None when none were needed); row 0 is zero without prev."""
+    if flow is None:
+        x = _stacked(results, 'frame') if x is None else x
+        lead = 0 if prev is None else 1
+        if lead:
+            x = torch.cat([prev.unsqueeze(0), x])
+        n = int(x.shape[0])
+        ref = np.arange(-1, n - 1, dtype=np.int32).reshape(n, 1)      # frame t against t-1; the first has none
+        flow = engine.frame_flow(x, _geom(results)[0, :4], ref, search=search)['flow'][lead:, 0]
+    centre = flow_cell_shifts(flow).contiguous()
+    moved = (centre != 0).any(dim=3).sum(dim=(1, 2)).cpu().numpy()
+    for t, r in enumerate(results):
+        r['flow_centre'] = {'search': int(search), 'moved': int(moved[t])}
+    return centre, x
+
+
 def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
                      keep_maps=False, fit_iters=0, lag=None, camera=False, camera_search=SEQ_CAMERA_SEARCH, flow=0, flow_search=SEQ_FLOW_SEARCH,
-                     flow_weights=None, **kw):
+                     flow_weights=None, flow_centre=False, **kw):
     """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
     geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
     [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal), Engine.seq_viterbi (mode 'viterbi', the most probable
@@ -171,6 +217,14 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
     fit and the mode run on the pooled maps.  Every frame's dict gains 'flow': {'n', 'search', 'points' float64 [K,2], 'inside' bool [K]: the
     frame's own arg-max of the pooled maps}, and 'maps' gains 'pooled'.  Block matching on luma, whole pixels, no occlusion reasoning, no gating
     of a neighbour by its match; flow_search = 8 and the uniform weights are untuned placeholders.  flow = 0 changes nothing.
+    flow_centre=True (modes 'filter' and 'viterbi' only -- 'marginal', 'lag' and fit_iters raise ValueError, the smoother has no centred
+    form; camera=True raises ValueError too, the flow of a cell already contains the pan): the fitted frames are kept and stacked, ONE
+    Engine.frame_flow call matches every frame against the one before it with search radius flow_search, motion.flow_cell_shifts rounds every
+    cell's displacement to whole cells and the scan runs with centre=: a cell's motion kernel is centred on where the cell's own content was.
+    With flow = N as well there is no second matching call -- slot 0 of the pooling's own call IS the frame before -- and the scan runs with
+    centre= on the pooled maps.  Every frame's dict gains 'flow_centre': {'search', 'moved': the cells of the frame with a non-zero shift}.
+    Whole cells of a whole-pixel flow, no gating of a cell by its match; what it buys in detection rate has not been measured.  flow_centre=False
+    changes nothing.
     'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
     the defaults SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what the track buys with trained weights has not been measured.
     One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
@@ -193,21 +247,27 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
         if int(fit_iters) != 0:
             raise ValueError('camera=True has no fit: fit_iters=%r needs the smoother, which has no moving form' % (fit_iters,))
         kw = dict(kw, keep_frames=True)
+    centred = _check_flow_centre(flow_centre, flow_search, mode, camera, fit_iters)
+    centre_search = int(flow_search) if centred else None
     n_flow, flow_search, flow_w = _check_flow(flow, flow_search, flow_weights)
     if n_flow:
         if mode not in SEQ_FLOW_MODES:
             raise ValueError("flow=%d: mode must be 'filter', 'viterbi' or 'marginal', got %r (two-sided pooling reads frames the lag has not yet seen)" % (n_flow, mode))
+    if n_flow or centred:
         kw = dict(kw, keep_frames=True)
     results = _first_pass(engine, frames, use_sm=use_sm, batch_size=batch_size, **kw)
     with torch.cuda.stream(engine._stream):
         hm = _stacked(results, 'sm' if use_sm else 'pd')
-        x = _stacked(results, 'frame') if camera or n_flow else None      # stacked once for both
+        x = _stacked(results, 'frame') if camera or n_flow or centred else None      # stacked once for all
+        flows = []
         if n_flow:
-            hm = _flow_pool(engine, results, hm, x, n_flow, flow_search, flow_w)
+            hm = _flow_pool(engine, results, hm, x, n_flow, flow_search, flow_w, keep=flows if centred else None)
         fit = seq_fit(engine, hm, sigma, rho, iters=int(fit_iters)) if int(fit_iters) else None
         if fit is not None:
             sigma, rho = fit['sigma'], fit['rho']
         moving = {'shift': _camera(engine, results, int(camera_search), x=x)[0]} if camera else {}
+        if centred:      # with flow = N slot 0 of the pooling's call is the frame before: no second matching call
+            moving = {'centre': _flow_centre(engine, results, centre_search, x=x, flow=flows[0][:, 0] if flows else None)[0]}
         seq = _seq_call(engine, mode, hm, sigma, rho, radius, lag=lag, **moving)
         geom = _geom(results)
         for r, track in zip(results, _track_entries(seq, mode, lambda pts: fit_to_source(pts, geom))):
@@ -281,7 +341,7 @@ def zoom_window_track(points, inside, torso, geom, frame=FRAME):
 
 
 def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, radius=None, batch_size=16, people=1,
-                          keep_maps=False, fit_iters=0, pad=0, timing=None, camera=False, flow=0, **kw):
+                          keep_maps=False, fit_iters=0, pad=0, timing=None, camera=False, flow=0, flow_centre=False, **kw):
     """The frames of ONE clip with one person in it, tracked a second time at the scale the tower was trained on; frames as
     for predict_sequence.
       1. predict_sequence(frames, mode, ..., torso_prob=True): the first pass and its 'track'; the torso track comes from the frames'
@@ -300,7 +360,10 @@ def predict_sequence_zoom(engine, frames, mode='viterbi', sigma=SEQ_SIGMA, torso
     The modes are 'filter' and 'viterbi': mode='marginal' and fit_iters raise ValueError (jcm_seq_smooth has no moving form), people != 1 too.
     One pitch per clip is a stated limit; torso_sigma, sigma and rho are untuned placeholders, and what this buys with trained weights has not
     been measured.  camera=True raises ValueError: the windows already move with the person, and a camera estimate under them is out of scope;
-    flow != 0 raises ValueError too: the windows move the lattice from frame to frame, and flow under moving windows is out of scope."""
+    flow != 0 raises ValueError too: the windows move the lattice from frame to frame, and flow under moving windows is out of scope;
+    flow_centre=True likewise (there is no centred form with a frame shift on top)."""
+    if flow_centre:
+        raise ValueError('predict_sequence_zoom has no flow-centred scan: its windows move the lattice from frame to frame (flow_centre=True belongs to predict_sequence)')
     if camera:
         raise ValueError('predict_sequence_zoom has no camera estimate: its windows follow the person already (camera=True belongs to predict_sequence)')
     if flow:
@@ -368,12 +431,19 @@ class SequenceTracker(_Clip):
     predict_sequence over all of it.  Every push must bring frames of the first push's size.  reset() starts a new clip.
     camera=True is the online form of predict_sequence(mode='filter', camera=True): the last fitted frame and the carry of
     motion.camera_shifts travel from push to push beside the belief (the shift of a push's first frame applies to the transition from the carried
-    belief), so any split gives the values of the one call; reset() clears both."""
+    belief), so any split gives the values of the one call; reset() clears both.
+    flow_centre=True is the online form of predict_sequence(mode='filter', flow_centre=True), the first online use of local motion:
+    the last fitted frame travels from push to push; a push stacks it in front of its own frames, matches every frame against its predecessor
+    (one Engine.frame_flow call with a one-slot ref table, search radius flow_search) and drops the carried frame's row again -- the first row of
+    a clip's first push has no predecessor and is zero --, so any split gives the bits of the one call; reset() forgets the frame.  Not with
+    camera=True (ValueError)."""
 
-    def __init__(self, engine, sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, camera=False, camera_search=SEQ_CAMERA_SEARCH, **kw):
+    def __init__(self, engine, sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, camera=False, camera_search=SEQ_CAMERA_SEARCH,
+                 flow_centre=False, flow_search=SEQ_FLOW_SEARCH, **kw):
         self.engine, self.sigma, self.rho, self.radius, self.use_sm = engine, sigma, rho, radius, use_sm
         self.camera, self.camera_search = _check_camera_search(camera, camera_search), int(camera_search)
-        self.pass1 = dict(kw, use_sm=use_sm, batch_size=batch_size, **({'keep_frames': True} if self.camera else {}))
+        self.flow_centre, self.flow_search = _check_flow_centre(flow_centre, flow_search, camera=self.camera), int(flow_search)
+        self.pass1 = dict(kw, use_sm=use_sm, batch_size=batch_size, **({'keep_frames': True} if self.camera or self.flow_centre else {}))
         self.reset()
 
     def reset(self):
@@ -385,6 +455,9 @@ class SequenceTracker(_Clip):
             moving = {}
             if self.camera:
                 moving['shift'], self.last_frame, self.carry = _camera(self.engine, results, self.camera_search, self.last_frame, self.carry)
+            if self.flow_centre:
+                moving['centre'], x = _flow_centre(self.engine, results, self.flow_search, prev=self.last_frame)
+                self.last_frame = x[-1].clone()
             seq = self.engine.seq_filter(_stacked(results, 'sm' if self.use_sm else 'pd'), self.sigma, self.rho, radius=self.radius, state=self.state, **moving)
             self.state = seq['state']
             geom = _geom(results)
@@ -490,7 +563,7 @@ def _check_people(people, zoom):
 
 
 def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SIGMA, torso_sigma=SEQ_TORSO_SIGMA, rho=SEQ_RHO, exclude=SEQ_EXCLUDE,
-                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, camera=False, flow=0, **kw):
+                            people_threshold=0.0, radius=None, batch_size=16, keep_maps=False, zoom=False, timing=None, camera=False, flow=0, flow_centre=False, **kw):
     """The frames of ONE clip with up to people = M (1..4) persons in it; frames as for predict_sequence.  On the device:
       1. predict_images(frames, use_sm=True, people=1, keep_maps=True, torso_prob=True, **kw): per frame the part-detector maps and the torso map
          spatial_softmax(E);
@@ -509,7 +582,10 @@ def predict_sequence_people(engine, frames, people, mode='viterbi', sigma=SEQ_SI
     timing also receives 'seq_torso_ms' and 'seq_people_sm_ms', the device times of steps 2 and 3.  'maps' is kept only with keep_maps.
     exclude (SEQ_EXCLUDE = 4 cells), torso_sigma (SEQ_TORSO_SIGMA = 1.5), sigma, rho and people_threshold are untuned placeholders -- no
     consecutive-frame data and no trained weights are at hand -- and what this buys with trained weights has not been measured.  zoom=True
-    and camera=True raise ValueError (the torso passes have no moving form), flow != 0 too (pooling per track is out of scope)."""
+    and camera=True raise ValueError (the torso passes have no moving form), flow != 0 too (pooling per track is out of scope), and
+    flow_centre=True (the torso passes have no centred form)."""
+    if flow_centre:
+        raise ValueError('predict_sequence_people has no flow-centred scan: the torso passes have no centred form (flow_centre=True belongs to predict_sequence)')
     if camera:
         raise ValueError('predict_sequence_people has no camera estimate: the torso passes have no moving form (camera=True belongs to predict_sequence)')
     if flow:
