@@ -425,6 +425,36 @@ int jcm_seq_filter_centred(jcm_handle h, const float* hm, int S, int T, int HH, 
 int jcm_seq_viterbi_centred(jcm_handle h, const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double rho,
                             const int32_t* centre, int32_t* path, double* maxes, int32_t* breaks);
 
+/* -- clip pose decoding: one skeleton per frame by MRF energy and motion ------------------------
+ * The exact MAP over the product of the two models above: a chain of the fully connected 9-joint pose models of jcm_pose_decode, one per frame,
+ * linked in time by one P x P transition table per joint.  Geometry of jcm_pose_decode: 9 joints, 1 <= P <= 4; S clips of T frames.
+ * Inputs (device): V fp32 [S,T,9,P], M fp32 [S,T,36,P,P], count int32 [S,T,9] (read clamped to 0..P), cells int32 [S,T,9,P,2] -- what
+ * jcm_pose_decode and jcm_hm_peaks write with B = S * T -- and tau float64 [S,T,9,P,P]: tau[s,t,j,a,b] is the log-score of joint j moving from
+ * candidate a of frame t-1 to candidate b of frame t.  tau[s,0] is never read; an entry may be -inf; NaN is outside the contract.  Slots at or
+ * beyond count are never read from V, M or tau.  The entry evaluates no transcendental: tau arrives ready-made.
+ * State: s = (p_0 .. p_8), flat index sum p_j P^(8-j) (p_0 most significant), valid in frame t when every p_j < count[t,j].  E_t(s) is the
+ * fixed-order fp32 sum S_8 of jcm_pose_decode (the same device expression, csrc/pose_score.h); -inf for a state that is not valid.
+ * Recurrence, float64, one rounded operation per step, evaluated as written:
+ *   frame 0, and the frame after a frame without a pose:  D_t(s) = (double)E_t(s)
+ *   t >= 1: G = D_{t-1}; for j = 0, 1, .. 8 in that order
+ *     G'(.., b_j, ..) = max over a_j = 0 .. count[t-1,j]-1, ascending, of G(.., a_j, ..) + tau[t,j,a_j,b_j]
+ *     a strictly greater value replaces (the lowest a_j wins a tie); the winner is the back-pointer of (t, pass j, that state); b_j >= count[t,j]:
+ *     -inf.  After pass j digits 0 .. j belong to frame t and digits j+1 .. 8 to frame t-1.
+ *   D_t(s) = (double)E_t(s) + G_9(s);  m_t = max D_t;  valid states become D_t - m_t, the others stay -inf;  maxes[s,t] = m_t.
+ *   break 1: frame t has a valid state but m_t = -inf (no connection to frame t-1): D_t = (double)E_t, m_t the max of that, breaks = 1.
+ *   break 2: some count[t,j] = 0, frame t has no pose: breaks = 2, maxes = 0, index and coords -1, frame_score -inf; the chain restarts at the
+ *   next frame, which like frame 0 carries no flag of its own.
+ * Backtrace: the end state is the first-occurrence flat arg-max of D_{T-1}; per frame t, descending, a_8 is pass 8's pointer at (b_0 .. b_8), a_7
+ * pass 7's at (b_0 .. b_7, a_8), and so on down to a_0.  Across a break the earlier segment ends at the first-occurrence arg-max of its own last D.
+ * Outputs (device; each may be NULL except index): index int32 [S,T,9], the chosen candidate per joint; coords int32 [S,T,2,9], its cell in the
+ * layout of jcm_argmax_coords; frame_score fp32 [S,T], E_t of the chosen pose; maxes float64 [S,T]; breaks int32 [S,T].
+ * JCM_ERR_ARG -- nothing is launched, no output is touched -- for P outside 1..4, S or T < 1, S * T >= 2^31 or a required pointer that is NULL;
+ * JCM_ERR_STATE with the bytes in the message when the plane (8 P^9 bytes per clip) and the back-pointers (3 P^9 bytes per frame) do not fit the
+ * workspace, as jcm_seq_viterbi refuses.  One launch on the handle's stream, one work group per clip, no synchronisation; follows call_order;
+ * profiling scope seq_pose_viterbi.  There is no online form: no state is carried from call to call. */
+int jcm_seq_pose_viterbi(jcm_handle h, const float* V, const float* M, const int32_t* count, const int32_t* cells, const double* tau, int S, int T,
+                         int P, int32_t* index, int32_t* coords, float* frame_score, double* maxes, int32_t* breaks);
+
 /* -- frame sequences, offline: smoothed marginals and expected transition statistics -----------
  * The third inference of the model above: gamma_t = P(x_t | all T frames) per (s, k), and from the same backward pass the posterior mass of
  * "moved" and of "jumped" and the expected squared displacement of every transition, from which sigma (per joint) and rho are re-estimated on

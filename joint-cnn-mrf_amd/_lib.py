@@ -67,6 +67,8 @@ SIGNATURES = {
                                               ctypes.c_void_p, _c_i32_p, ctypes.c_void_p]),
     'jcm_seq_viterbi_centred': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double, _c_i32_p, _c_i32_p, ctypes.c_void_p, _c_i32_p]),
+    'jcm_seq_pose_viterbi': (ctypes.c_int, [_handle, _c_float_p, _c_float_p, _c_i32_p, _c_i32_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            _c_i32_p, _c_i32_p, _c_float_p, ctypes.c_void_p, _c_i32_p]),
     'jcm_seq_smooth': (ctypes.c_int, [_handle, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                       ctypes.c_int, ctypes.c_double, _c_float_p, _c_i32_p, _c_float_p, ctypes.c_void_p, _c_i32_p, ctypes.c_void_p, _c_i32_p,
                                       ctypes.c_void_p]),

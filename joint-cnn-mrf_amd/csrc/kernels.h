@@ -418,6 +418,14 @@ hipError_t seq_filter_centred(const float* hm, int S, int T, int HH, int WW, int
                               const double* state_in, float* filtered, int32_t* coords, double* norm, int32_t* reset, double* state_out, hipStream_t st);
 hipError_t seq_viterbi_centred(const float* hm, int S, int T, int HH, int WW, int K, const double* taps, int R, double om, double u, const int32_t* centre,
                                int16_t* bp, int32_t* amax, int32_t* path, double* maxes, int32_t* breaks, hipStream_t st);
+// ---- seq_pose.hip : the clip decode, Viterbi over the P^9 poses of every frame --
+// V [S*T][9][P], M [S*T][36][P][P], count [S*T][9], cells [S*T][9][P][2] as pose_decode leaves them, tau float64 [S*T][9][P][P] (jcm.h:
+// jcm_seq_pose_viterbi).  Workspace: plane float64 [S][P^9], bpa uint8 and bpb uint16 [S*T][P^9] (2 bits per pass: passes 0 .. 3 / 4 .. 8), amax and start
+// int32 [S*T].  One launch, one work group per clip; index is required, the other outputs may be null.
+size_t seq_pose_states(int P);
+hipError_t seq_pose_viterbi(const float* V, const float* M, const int32_t* count, const int32_t* cells, const double* tau, int S, int T, int P, double* plane,
+                            uint8_t* bpa, uint16_t* bpb, int32_t* amax, int32_t* start, int32_t* index, int32_t* coords, float* frame_score, double* maxes,
+                            int32_t* breaks, hipStream_t st);
 // ---- seq_smooth.hip : the smoothed marginals and the expected transition statistics --
 // Two launches, one work group per (sequence, joint) each: the filter's scan (seq_scan.h) that also writes every a_t to belief float64 [S*K][T][HH*WW],
 // then the backward scan with three float64 planes in LDS for all T frames, so HH * WW <= kSeqSmoothMaxHW (3 * 48 KB + the reduction scratch of 160 KB).

@@ -15,25 +15,22 @@
 #include <string>
 
 #include "entry.h"
+#include "pose_score.h"
 #include "sm_lds_fft.h"
 
 namespace jcm {
 
 namespace {
 
-constexpr int kPdK = 9;                        // joints
+// kPdK, kPdPairs, kPdMaxP, pd_pair, pd_count and the score itself: pose_score.h, shared with seq_pose.hip
 constexpr int kPdPJ = kC - 1;                  // pairs per joint in sp_energy / sp_bias: <j>_<c>, c in name order without j
-constexpr int kPdPairs = kPdK * (kPdK - 1) / 2;      // 36 unordered joint pairs (a < b), lexicographic
-constexpr int kPdMaxP = 4;
 constexpr int kPdThreads = 256;
 constexpr int kPdGroups = kPdMaxP * kPdMaxP;   // work groups per image of the search: (p_0, p_1)
 constexpr float kPdDelta = 1e-6f;              // main.py:110
 constexpr int kPdNone = 0x7fffffff;
 
-__host__ __device__ constexpr int pd_pair(int a, int b) { return a * (17 - a) / 2 + (b - a - 1); }      // a < b
 __device__ __forceinline__ int pd_row(int j, int c) { return j * kPdPJ + (c < j ? c : c - 1); }          // the row of pair <j>_<c> in sp_energy / sp_bias
 __device__ __forceinline__ bool pd_better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-__device__ __forceinline__ int pd_count(const int32_t* __restrict__ count, int b, int j, int P) { return min(max(count[b * kPdK + j], 0), P); }
 
 __global__ __launch_bounds__(kPdThreads) void pose_tables_kernel(const float* __restrict__ hm10, const int32_t* __restrict__ cells, const int32_t* __restrict__ count,
                                                                  int P, const float* __restrict__ spe, const float* __restrict__ spb,
@@ -133,16 +130,7 @@ __global__ __launch_bounds__(kPdThreads) void pose_search_kernel(const float* __
   __shared__ float rv[kPdThreads / 64];
   __shared__ int ri[kPdThreads / 64];
   const int b = blockIdx.x / kPdGroups, g = blockIdx.x - b * kPdGroups, tid = threadIdx.x;
-  const int PP = P * P;
-  for (int i = tid; i < kPdPairs * kPdMaxP * kPdMaxP; i += kPdThreads) {
-    const int pb = i & 3, pa = (i >> 2) & 3, pr = i >> 4;
-    Ms[pr][pa][pb] = (pa < P && pb < P) ? M[((size_t)b * kPdPairs + pr) * PP + pa * P + pb] : 0.f;
-  }
-  if (tid < kPdK * kPdMaxP) {
-    const int j = tid >> 2, p = tid & 3;
-    Vs[j][p] = p < P ? V[((size_t)b * kPdK + j) * P + p] : 0.f;
-    if (p == 0) cnt[j] = pd_count(count, b, j, P);
-  }
+  pose_tables_stage(V, M, count, b, P, Vs, Ms, cnt, tid, kPdThreads);
   __syncthreads();
 
   const int p[6] = {g >> 2, g & 3, tid >> 6, (tid >> 4) & 3, (tid >> 2) & 3, tid & 3};
@@ -152,43 +140,11 @@ __global__ __launch_bounds__(kPdThreads) void pose_search_kernel(const float* __
   float bv = -INFINITY;
   int bi = kPdNone;
   if (live) {
-    float S = Vs[0][p[0]];      // S_0
-#pragma unroll
-    for (int k = 1; k < 6; ++k) {
-      float inc = Vs[k][p[k]];
-#pragma unroll
-      for (int a = 0; a < k; ++a) inc = inc + Ms[pd_pair(a, k)][p[a]][p[k]];
-      S = S + inc;              // S_k
-    }
-    float base[3][kPdMaxP];      // the first terms of inc_6, inc_7, inc_8: V and the pairs with the fixed joints 0 .. 5
-#pragma unroll
-    for (int k = 6; k < kPdK; ++k)
-#pragma unroll
-      for (int q = 0; q < kPdMaxP; ++q) {
-        float inc = Vs[k][q];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) inc = inc + Ms[pd_pair(a, k)][p[a]][q];
-        base[k - 6][q] = inc;
-      }
     const int n5 = (g << 14) | (tid << 6);      // pose number: 2 bits per joint, p_0 on top
-    const int c6 = cnt[6], c7 = cnt[7], c8 = cnt[8];
-#pragma unroll
-    for (int p6 = 0; p6 < kPdMaxP; ++p6) {
-      if (p6 >= c6) break;
-      const float S6 = S + base[0][p6];
-#pragma unroll
-      for (int p7 = 0; p7 < kPdMaxP; ++p7) {
-        if (p7 >= c7) break;
-        const float S7 = S6 + (base[1][p7] + Ms[pd_pair(6, 7)][p6][p7]);
-#pragma unroll
-        for (int p8 = 0; p8 < kPdMaxP; ++p8) {
-          if (p8 >= c8) break;
-          const float S8 = S7 + ((base[2][p8] + Ms[pd_pair(6, 8)][p6][p8]) + Ms[pd_pair(7, 8)][p7][p8]);
-          const int n = n5 | (p6 << 4) | (p7 << 2) | p8;
-          if (pd_better(S8, n, bv, bi)) { bv = S8; bi = n; }
-        }
-      }
-    }
+    pose_walk(Vs, Ms, cnt, p, [&](int p6, int p7, int p8, float S8) {
+      const int n = n5 | (p6 << 4) | (p7 << 2) | p8;
+      if (pd_better(S8, n, bv, bi)) { bv = S8; bi = n; }
+    });
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -234,15 +190,8 @@ __global__ __launch_bounds__(64) void pose_finish_kernel(const float* __restrict
   if (lane == kPdK + 1 && score0) {      // the all-peak-0 pose, the same sum
     float S = -INFINITY;
     if (!none) {
-      const int PP = P * P;
-      const float* v = V + (size_t)b * kPdK * P;
-      const float* m = M + (size_t)b * kPdPairs * PP;
-      S = v[0];
-      for (int k = 1; k < kPdK; ++k) {
-        float inc = v[k * P];
-        for (int a = 0; a < k; ++a) inc = inc + m[pd_pair(a, k) * PP];
-        S = S + inc;
-      }
+      const int zero[kPdK] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      S = pose_score_of(V + (size_t)b * kPdK * P, M + (size_t)b * kPdPairs * P * P, P, zero);
     }
     score0[b] = S;
   }

@@ -375,6 +375,40 @@ class Engine:
                                              self._p(out['score']), self._p(out['score0']), self._p(out.get('V')), self._p(out.get('M'))), 'jcm_pose_decode')
         return out
 
+    def seq_pose_viterbi(self, V, M, count, cells, tau):
+        """The clip decode (include/jcm.h: jcm_seq_pose_viterbi): the most probable sequence of POSES through a clip -- per frame the
+        P^9 poses of pose_decode with their scores, linked in time by tau, one P x P table of log-scores per joint and frame.  V fp32 [T,9,P] or
+        [S,T,9,P] and M fp32 [.,36,P,P] as pose_decode(want_tables=True) returns them for the clip's frames, count int32 [.,9] and cells int32
+        [.,9,P,2] as hm_peaks does, tau float64 [.,9,P,P] (motion.seq_pose_tau; host or device): tau[t,j,a,b] scores joint j going from
+        candidate a of frame t-1 to candidate b of frame t.  Returns {'index' int32 [S,T,9], 'coords' int32 [S,T,2,9], 'frame_score' fp32 [S,T],
+        'maxes' float64 [S,T], 'breaks' int32 [S,T]}, device tensors without the S axis for tables without one; nothing is read back.  Shapes
+        and dtypes that do not fit raise ValueError before any launch; the plane and the back-pointers (3 P^9 bytes per frame) live in the
+        engine's workspace, and a clip they do not fit in is a RuntimeError that names the bytes.  There is no online form."""
+        if not isinstance(V, torch.Tensor) or V.dim() not in (3, 4):
+            raise ValueError('V must be a device tensor [T,9,P] or [S,T,9,P]')
+        single = V.dim() == 3
+        if not isinstance(tau, torch.Tensor):
+            tau = torch.from_numpy(np.ascontiguousarray(np.asarray(tau, np.float64))).to(self.device)
+        lift = lambda t: t.unsqueeze(0) if single and isinstance(t, torch.Tensor) else t
+        try:
+            V, M, count, cells, tau = (self._chk(lift(t), n, name, dt) for t, n, name, dt in (
+                (V, 4, 'V', torch.float32), (M, 5, 'M', torch.float32), (count, 3, 'count', torch.int32), (cells, 5, 'cells', torch.int32),
+                (tau, 5, 'tau', torch.float64)))
+        except TypeError as e:
+            raise ValueError(str(e))
+        S, T, K, P = V.shape
+        if (K != 9 or not 1 <= P <= 4 or S < 1 or T < 1 or tuple(M.shape) != (S, T, 36, P, P) or tuple(count.shape) != (S, T, 9)
+                or tuple(cells.shape) != (S, T, 9, P, 2) or tuple(tau.shape) != (S, T, 9, P, P)):
+            raise ValueError('seq_pose_viterbi expects V [S,T,9,P] with 1 <= P <= 4, M [S,T,36,P,P], count [S,T,9], cells [S,T,9,P,2] and tau [S,T,9,P,P]; '
+                             'got %s, %s, %s, %s, %s' % tuple(tuple(t.shape) for t in (V, M, count, cells, tau)))
+        out = {'index': self._new(S, T, 9, dtype=torch.int32), 'coords': self._new(S, T, 2, 9, dtype=torch.int32), 'frame_score': self._new(S, T),
+               'maxes': self._new(S, T, dtype=torch.float64), 'breaks': self._new(S, T, dtype=torch.int32)}
+        self._on_stream(V, M, count, cells, tau, *out.values())
+        _lib.check(self._lib.jcm_seq_pose_viterbi(self._h, self._p(V), self._p(M), self._p(count), self._p(cells), self._p(tau), S, T, P, self._p(out['index']),
+                                                  self._p(out['coords']), self._p(out['frame_score']), self._p(out['maxes']), self._p(out['breaks'])),
+                   'jcm_seq_pose_viterbi')
+        return {k: v[0] for k, v in out.items()} if single else out
+
     def _seq_args(self, hm, sigma, radius):
         """hm [T,HH,WW,K] or [S,T,HH,WW,K] -> (hm as [S,T,HH,WW,K], whether a sequence axis was added, host taps [K,2R+1], R)."""
         if not isinstance(hm, torch.Tensor) or hm.dim() not in (4, 5):

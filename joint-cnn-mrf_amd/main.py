@@ -166,6 +166,13 @@ def build_parser():
                         'to whole cells, fed to the scans as centre= (Engine.seq_filter / seq_viterbi).  With --seq_flow N as well the pooling\'s own matching is '
                         'reused and the scan runs on the pooled maps.  The document gains "flow_centre" per file, the JSON line seq_flow_centre, the search radius; '
                         'with --render the drawn track is the centred one.  Not with --seq_camera, --seq_zoom, --seq_people, --seq_fit or --sequence marginal / lag.')
+    parser.add_argument('--seq_pose', type=int, default=None, metavar='P', help='with --sequence viterbi and --use_sm: also decode ONE skeleton per frame over the '
+                        'whole clip (DESIGN.md 4.30): the P in 1..4 heat-map peaks per joint of every frame, the spatial model\'s energy of each of the P^9 poses '
+                        '(Engine.pose_decode) and the motion model between the candidates of consecutive frames (Engine.seq_pose_viterbi), the exact MAP over the '
+                        'sequence of poses.  The document gains "track_pose" per file, the JSON line seq_pose and seq_pose_weight; with --render the skeleton of '
+                        'track_pose is drawn in place of the track.  Not with --seq_people, --seq_zoom, --seq_camera, --seq_flow, --seq_flow_centre or --seq_fit.')
+    parser.add_argument('--seq_pose_weight', type=float, default=None, metavar='W', help='with --seq_pose: the weight of the motion term against the pose energy, '
+                        'finite and >= 0 (default 1.0, an untuned placeholder: the two log-scores are of different origin).')
     parser.add_argument('--seq_torso_sigma', type=float, default=None, metavar='CELLS', help='with --seq_people: the standard deviation of a torso\'s motion per '
                         'frame in heat-map cells (default 1.5, an untuned placeholder).')
     parser.add_argument('--seq_exclude', type=int, default=None, metavar='CELLS', help='with --seq_people: the half-width in 0..64 heat-map cells of the square '
@@ -416,6 +423,16 @@ SEQ_FLOW_CENTRE_NO_FIT = '--seq_flow_centre cannot be combined with --seq_fit: t
 SEQ_FLOW_CENTRE_NO_CAMERA = '--seq_flow_centre cannot be combined with --seq_camera: the flow of a cell already contains the pan'
 SEQ_FLOW_CENTRE_NO_ZOOM = '--seq_flow_centre cannot be combined with --seq_zoom: the zoom windows move the lattice from frame to frame'
 SEQ_FLOW_CENTRE_NO_PEOPLE = '--seq_flow_centre cannot be combined with --seq_people: the torso passes have no form for a shift per cell'
+SEQ_POSE_NEEDS_PREDICT = '--seq_pose decodes the poses of the clip --predict names: give --predict as well'
+SEQ_POSE_NEEDS_USE_SM = '--seq_pose needs --use_sm: the pose energy is the spatial model\'s'
+SEQ_POSE_NEEDS_VITERBI = '--seq_pose is an offline MAP over the clip: give --sequence viterbi as well'
+SEQ_POSE_WEIGHT_NEEDS_SEQ_POSE = '--seq_pose_weight weighs the motion term of --seq_pose: give --seq_pose P as well'
+SEQ_POSE_NO_PEOPLE = '--seq_pose cannot be combined with --seq_people: the clip decode picks one skeleton per frame'
+SEQ_POSE_NO_ZOOM = '--seq_pose cannot be combined with --seq_zoom: the zoom windows move the lattice from frame to frame'
+SEQ_POSE_NO_CAMERA = '--seq_pose cannot be combined with --seq_camera: the transition between candidates has no moving form'
+SEQ_POSE_NO_FLOW = '--seq_pose cannot be combined with --seq_flow: the candidates are the peaks of the frames\' own maps, not of pooled ones'
+SEQ_POSE_NO_FLOW_CENTRE = '--seq_pose cannot be combined with --seq_flow_centre: the transition between candidates has no centred form'
+SEQ_POSE_NO_FIT = '--seq_pose cannot be combined with --seq_fit: the fitted sigma and rho belong to the per-joint scans'
 SEQ_PEOPLE_OPTION_NEEDS_SEQ_PEOPLE = '--seq_torso_sigma and --seq_exclude set the torso passes of --seq_people: give --seq_people M as well'
 U8_TRAIN_NEEDS_DEVICE_DATA = ('--train --u8_images needs --device_data: byte images are held on the device and widened by the gather / the augmentation; '
                               'host-fed training steps take float batches')
@@ -448,7 +465,8 @@ def predict_main(args):
     gains seq_zoom, seq_zoom_pitch, zoom_fit_ms and zoom_forward_ms; with --sequence lag --seq_lag L the line gains seq_lag; with --seq_camera the document gains
     "camera" per file and the line seq_camera, the search radius; with --seq_flow N the document gains "flow" per file and the line seq_flow
     and seq_flow_search; with --seq_flow_centre the document gains "flow_centre" per file and the line seq_flow_centre, the search radius --
-    'track', which --render draws, is the centred one."""
+    'track', which --render draws, is the centred one; with --seq_pose P the document gains "track_pose" per file and the line seq_pose
+    and seq_pose_weight -- --render draws the skeleton of track_pose."""
     from . import predict
     files = predict.expand_paths(args.predict)
     images = [predict.load_image(f) for f in files]
@@ -479,12 +497,14 @@ def predict_main(args):
                     seq.update(flow=args.seq_flow, flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
                 if args.seq_flow_centre:
                     seq.update(flow_centre=True, flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
+                if args.seq_pose is not None:
+                    seq.update(pose=args.seq_pose, pose_weight=1.0 if args.seq_pose_weight is None else args.seq_pose_weight)
                 results = predict.predict_sequence(eng, images, use_sm=args.use_sm, **seq)
         else:
             results = predict.predict_images(eng, images, use_sm=args.use_sm, peaks=args.peaks, decode=args.decode_pose, people=args.people,
                                              batch_size=args.batch_size, timing=timing, zoom=args.zoom, keep_maps=bool(args.render_heat))
         if args.render:
-            pictures = predict.render_images(eng, images, results, heat=args.render_heat, which=('track_zoom' if args.seq_zoom and 'track_zoom' in results[0] else 'track') if args.sequence else None,
+            pictures = predict.render_images(eng, images, results, heat=args.render_heat, which=('track_zoom' if args.seq_zoom and 'track_zoom' in results[0] else 'track_pose' if args.seq_pose is not None else 'track') if args.sequence else None,
                                              batch_size=args.batch_size, timing=timing)
     finally:
         eng.close()
@@ -506,6 +526,8 @@ def predict_main(args):
         line.update(seq_flow=args.seq_flow, seq_flow_search=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
     if args.seq_flow_centre:
         line.update(seq_flow_centre=predict.SEQ_FLOW_SEARCH if args.seq_flow_search is None else args.seq_flow_search)
+    if args.seq_pose is not None:
+        line.update(seq_pose=args.seq_pose, seq_pose_weight=1.0 if args.seq_pose_weight is None else args.seq_pose_weight)
     if args.seq_people is not None:
         line.update(seq_people=args.seq_people, seq_torso_ms=timing['seq_torso_ms'], seq_people_sm_ms=timing['seq_people_sm_ms'])
     if args.seq_zoom:
@@ -868,13 +890,29 @@ SEQ_FLOW_CENTRE_RULES = (
     (lambda a: a.seq_flow_centre and a.seq_zoom, SEQ_FLOW_CENTRE_NO_ZOOM),
     (lambda a: a.seq_flow_centre and a.seq_people is not None, SEQ_FLOW_CENTRE_NO_PEOPLE),
 )
+# The rules of --seq_pose, walked behind SEQ_FLOW_CENTRE_RULES (a table of their own for the same reason).
+SEQ_POSE_RULES = (
+    (lambda a: a.seq_pose_weight is not None and a.seq_pose is None, SEQ_POSE_WEIGHT_NEEDS_SEQ_POSE),
+    (lambda a: a.seq_pose is not None and not a.predict, SEQ_POSE_NEEDS_PREDICT),
+    (lambda a: a.seq_pose is not None and not a.use_sm, SEQ_POSE_NEEDS_USE_SM),
+    (lambda a: a.seq_pose is not None and a.sequence != 'viterbi', SEQ_POSE_NEEDS_VITERBI),
+    (lambda a: a.seq_pose is not None and not 1 <= a.seq_pose <= 4, lambda a: '--seq_pose %d: 1 <= P <= 4' % a.seq_pose),
+    (lambda a: a.seq_pose_weight is not None and not (np.isfinite(a.seq_pose_weight) and a.seq_pose_weight >= 0),
+     lambda a: '--seq_pose_weight %r: W is finite and >= 0' % a.seq_pose_weight),
+    (lambda a: a.seq_pose is not None and a.seq_people is not None, SEQ_POSE_NO_PEOPLE),
+    (lambda a: a.seq_pose is not None and a.seq_zoom, SEQ_POSE_NO_ZOOM),
+    (lambda a: a.seq_pose is not None and a.seq_camera, SEQ_POSE_NO_CAMERA),
+    (lambda a: a.seq_pose is not None and a.seq_flow is not None, SEQ_POSE_NO_FLOW),
+    (lambda a: a.seq_pose is not None and a.seq_flow_centre, SEQ_POSE_NO_FLOW_CENTRE),
+    (lambda a: a.seq_pose is not None and a.seq_fit is not None, SEQ_POSE_NO_FIT),
+)
 
 
 def main(argv=None):
     global hps
     args = build_parser().parse_args(argv)
     hps = args
-    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES + EVAL_SCALE_RULES + SEQ_FLOW_RULES + SEQ_FLOW_CENTRE_RULES:
+    for holds, message in FLAG_RULES + SEQUENCE_RULES + AUGM_RULES + SEQ_PEOPLE_RULES + SYNTH_PEOPLE_RULES + SEQ_SMOOTH_RULES + SEQ_ZOOM_RULES + SEQ_LAG_RULES + SEQ_CAMERA_RULES + EVAL_SCALE_RULES + SEQ_FLOW_RULES + SEQ_FLOW_CENTRE_RULES + SEQ_POSE_RULES:
         if holds(args):
             raise SystemExit(message(args) if callable(message) else message)
     for g in args.gpus:      # after the rules: a refused combination is reported as such on a machine without the device too

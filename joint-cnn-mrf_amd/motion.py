@@ -129,6 +129,37 @@ def seq_kernel(sigma, radius, K):
     return R, seq_taps(sigma, R, K)
 
 
+def seq_pose_tau(cells, count, sigma, rho, radius=None, weight=1.0, hw=5400):
+    """The transition tables of the clip decode (Engine.seq_pose_viterbi) from the candidates of a clip: cells int [T,K,P,2] (row, col),
+    count int [T,K] as hm_peaks leaves them, host arrays -> float64 [T,K,P,P],
+        tau[t,j,a,b] = weight * log(om * w_j[dy + R] * w_j[dx + R] + u),   (dy, dx) = cell_b(t) - cell_a(t-1),
+    with (R, w) = seq_kernel(sigma, radius, K), om = 1 - rho and u = rho / hw: the taps and the two constants of Engine.seq_viterbi, so a candidate
+    pair scores what that scan's transition gives its two cells.  Outside the radius the product is 0: with rho = 0 the entry is -inf.  tau[0] and
+    every slot at or beyond count are 0 and are never read.  weight mixes two log-scores of different origin; 1.0 is an untuned placeholder."""
+    cells, count = np.asarray(cells, np.int64), np.asarray(count, np.int64)
+    if cells.ndim != 4 or cells.shape[3] != 2 or count.shape != cells.shape[:2]:
+        raise ValueError('seq_pose_tau expects cells [T,K,P,2] and count [T,K]; got %s, %s' % (cells.shape, count.shape))
+    if not 0.0 <= float(rho) <= 1.0 or not np.isfinite(float(weight)) or float(weight) < 0.0:
+        raise ValueError('seq_pose_tau expects rho in [0,1] and a finite weight >= 0; got %r, %r' % (rho, weight))
+    T, K, P = cells.shape[:3]
+    R, w = seq_kernel(sigma, radius, K)
+    om, u = 1.0 - float(rho), float(rho) / float(hw)
+    tau = np.zeros((T, K, P, P), np.float64)
+    if T < 2:
+        return tau
+    d = cells[1:, :, None, :, :] - cells[:-1, :, :, None, :]                     # [T-1,K,a,b,2]
+    near = (np.abs(d) <= R).all(axis=4)
+    tap = lambda k: np.where(near, np.take_along_axis(w[None, :, None, :], np.clip(d[..., k] + R, 0, 2 * R).reshape(T - 1, K, 1, P * P), axis=3).reshape(T - 1, K, P, P), 0.0)
+    n = np.clip(count, 0, P)
+    live = (np.arange(P)[None, None, :, None] < n[:-1, :, None, None]) & (np.arange(P)[None, None, None, :] < n[1:, :, None, None])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        val = float(weight) * np.log(om * tap(0) * tap(1) + u)
+    if float(weight) == 0.0:
+        val = np.where(np.isnan(val), 0.0, val)      # 0 * -inf: a weight of 0 switches the motion term off, also where it forbids
+    tau[1:] = np.where(live, val, 0.0)
+    return tau
+
+
 def seq_moment(sigma, radius):
     """sum over d of d^2 w_sigma[d] of the truncated taps seq_taps builds: the 1-D second moment of the motion kernel, float64.  Monotone in sigma,
     from 0 towards the flat taps' R (R + 1) / 3."""

@@ -29,13 +29,17 @@ runs on the pooled maps, which are maps like any other.
 
 Flow-centred scans: predict_sequence(flow_centre=True) and SequenceTracker(flow_centre=True) match every frame against the one before
 it (Engine.frame_flow, the causal slot), round the displacement of every cell to whole cells (motion.flow_cell_shifts) and run the filter or Viterbi
-with centre=, so that the motion kernel of a cell is centred on where that cell's own content was, not on the cell itself."""
+with centre=, so that the motion kernel of a cell is centred on where that cell's own content was, not on the cell itself.
+
+Clip pose decoding: predict_sequence(mode='viterbi', pose=P) also decodes ONE skeleton per frame over the whole clip -- the P^9 poses
+of every frame's pose_decode, linked in time by the motion model between the candidates (motion.seq_pose_tau, Engine.seq_pose_viterbi) -- as
+'track_pose'; there is no online form."""
 import numpy as np
 import torch
 
 from ..evaluation import fit_to_source, window_to_source
 from ..motion import (SEQ_CAMERA_SEARCH, SEQ_EXCLUDE, SEQ_FLOW_MAX, SEQ_FLOW_SEARCH, SEQ_KEYS, SEQ_MODES, SEQ_RHO, SEQ_SIGMA, SEQ_TORSO_SIGMA, camera_shifts,
-                      flow_cell_shifts, flow_refs, flow_weights, seq_fit)
+                      flow_cell_shifts, flow_refs, flow_weights, seq_fit, seq_pose_tau)
 from .images import FIT_SIDE_MAX, FRAME, STRIDE, ZOOM_TORSO_JOINTS, ZOOM_TORSO_PIXELS, DeviceTimer, _coords_to_points, _upload, predict_images, second_pass, zoom_entry
 
 
@@ -190,7 +194,7 @@ def _flow_centre(engine, results, search, x=None, prev=None, flow=None):
 
 def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO, radius=None, use_sm=True, batch_size=16, people=1, zoom=False,
                      keep_maps=False, fit_iters=0, lag=None, camera=False, camera_search=SEQ_CAMERA_SEARCH, flow=0, flow_search=SEQ_FLOW_SEARCH,
-                     flow_weights=None, flow_centre=False, **kw):
+                     flow_weights=None, flow_centre=False, pose=0, pose_weight=1.0, **kw):
     """The frames of ONE clip, in order: a list of uint8 [h,w,3] images of one size (any other size raises ValueError: a clip has one letterbox
     geometry).  predict_images(frames, keep_maps=True, **kw) runs over them; the 'sm' maps ('pd' without use_sm) are stacked on the device as
     [T,60,90,K] and go through ONE call of Engine.seq_filter (mode 'filter', causal), Engine.seq_viterbi (mode 'viterbi', the most probable
@@ -225,6 +229,15 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
     centre= on the pooled maps.  Every frame's dict gains 'flow_centre': {'search', 'moved': the cells of the frame with a non-zero shift}.
     Whole cells of a whole-pixel flow, no gating of a cell by its match; what it buys in detection rate has not been measured.  flow_centre=False
     changes nothing.
+    pose = P in 1..4 (mode 'viterbi' with use_sm only; camera, flow, flow_centre, fit_iters and any other P raise ValueError): pass 1
+    runs with peaks=P, decode=True and keeps its candidates on the device; ONE Engine.pose_decode(want_tables=True) call covers the clip, then
+    motion.seq_pose_tau(cells, count, sigma, rho, radius, pose_weight) on the host and ONE Engine.seq_pose_viterbi call: the exact MAP over the
+    sequence of poses, where 'track' follows every joint on its own.  'track' is what it is without pose; every frame's dict gains the keys of
+    peaks=P, decode=True and 'track_pose': {'peaks': P, 'index' int [K] (the candidate per joint, -1 without a pose), 'points' float64 [K,2] and
+    'inside' bool [K] (the candidate's cell with its sub-cell offset, through fit_to_source), 'score' (E_t of the pose), 'maxes', 'breaks' (the
+    library's m_t and flag), 'changed': the joints whose candidate is not the one of the frame's own decode}.  pose_weight = 1.0 mixes two
+    log-scores of different origin -- the spatial model's energy and the motion kernel -- and is an untuned placeholder; with 0 the clip decode is
+    every frame's own.  What this buys in detection rate has not been measured.  pose = 0 changes nothing.
     'maps' is kept only with keep_maps.  sigma (a scalar or K values, heat-map cells per frame), rho and radius are those of Engine.seq_filter;
     the defaults SEQ_SIGMA and SEQ_RHO are untuned placeholders, and what the track buys with trained weights has not been measured.
     One person, one pass: people != 1 and zoom=True raise ValueError -- associating people across frames, and windows that move from frame to
@@ -255,6 +268,9 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
             raise ValueError("flow=%d: mode must be 'filter', 'viterbi' or 'marginal', got %r (two-sided pooling reads frames the lag has not yet seen)" % (n_flow, mode))
     if n_flow or centred:
         kw = dict(kw, keep_frames=True)
+    n_pose = _check_pose(pose, pose_weight, mode, use_sm, camera, n_flow, centred, fit_iters)
+    if n_pose:
+        kw = dict(kw, peaks=n_pose, decode=True, keep_peaks=True)
     results = _first_pass(engine, frames, use_sm=use_sm, batch_size=batch_size, **kw)
     with torch.cuda.stream(engine._stream):
         hm = _stacked(results, 'sm' if use_sm else 'pd')
@@ -274,7 +290,53 @@ def predict_sequence(engine, frames, mode='filter', sigma=SEQ_SIGMA, rho=SEQ_RHO
             r['track'] = track
         if fit is not None:
             results[0]['seq_fit'] = fit
+        if n_pose:
+            _pose_track(engine, results, n_pose, sigma, rho, radius, float(pose_weight))
     return _finish(results, keep_maps)
+
+
+def _check_pose(pose, pose_weight, mode, use_sm, camera, n_flow, centred, fit_iters):
+    """pose = 0 (off) or the candidates per joint of the clip decode, 1..4, and what it cannot go with -> P."""
+    if isinstance(pose, bool) or not isinstance(pose, (int, np.integer)) or not 0 <= int(pose) <= 4:
+        raise ValueError('pose must be 0 (off) or the candidates per joint, 1..4, got %r' % (pose,))
+    if not int(pose):
+        return 0
+    if not np.isfinite(float(pose_weight)) or float(pose_weight) < 0:
+        raise ValueError('pose_weight must be finite and >= 0, got %r' % (pose_weight,))
+    if mode != 'viterbi' or not use_sm:
+        raise ValueError("pose=%d: the clip decode goes with mode='viterbi' and use_sm=True (mode is %r, use_sm %r)" % (pose, mode, bool(use_sm)))
+    if camera or n_flow or centred or int(fit_iters):
+        raise ValueError('pose=%d cannot be combined with camera, flow, flow_centre or fit_iters: the transition between candidates is the plain motion '
+                         'kernel with the given sigma and rho' % (pose,))
+    return int(pose)
+
+
+def _pose_track(engine, results, P, sigma, rho, radius, weight):
+    """The clip decode over the frames of `results` (dicts of pass 1 with keep_peaks): ONE Engine.pose_decode(want_tables=True) on the stacked
+    part-detector maps and torso maps, motion.seq_pose_tau on the host, ONE Engine.seq_pose_viterbi.  Every dict gains 'track_pose'."""
+    maps = [r['maps'] for r in results]
+    hm10 = torch.cat([torch.stack([m['pd'] for m in maps]), torch.stack([m['torso'] for m in maps])], dim=3).contiguous()
+    peaks = {f: torch.stack([m['pd_peaks'][f] for m in maps]).contiguous() for f in ('cells', 'count')}
+    dec = engine.pose_decode(hm10, peaks, want_tables=True)
+    cells, count = peaks['cells'].cpu().numpy(), peaks['count'].cpu().numpy()
+    tau = seq_pose_tau(cells, count, sigma, rho, radius=radius, weight=weight, hw=hm10.shape[1] * hm10.shape[2])
+    seq = {k: v.cpu().numpy() for k, v in engine.seq_pose_viterbi(dec['V'], dec['M'], peaks['count'], peaks['cells'], tau).items()}
+    own = torch.stack([m['pose_index'] for m in maps]).cpu().numpy()
+    index = seq['index']
+    # the chosen candidates in fitted-frame pixels as pose_to_pixels gives them: cell plus sub-cell offset; pass 1 kept the offsets in 'pd_peaks'
+    pk = np.stack([np.asarray(r['pd_peaks'], np.float64) for r in results])      # [T,K,P,3], already in source pixels
+    pin = np.stack([np.asarray(r['pd_peaks_inside']) for r in results])
+    pick = np.maximum(index, 0).astype(np.int64)[:, :, None]
+    pts = np.take_along_axis(pk[..., :2], pick[..., None], axis=2)[:, :, 0, :]
+    inside = np.take_along_axis(pin, pick, axis=2)[:, :, 0]
+    none = index < 0
+    pts[none] = -1.0
+    inside = inside & ~none
+    for t, r in enumerate(results):
+        r['track_pose'] = {'peaks': P, 'index': index[t], 'points': pts[t], 'inside': inside[t], 'score': float(seq['frame_score'][t]),
+                           'maxes': float(seq['maxes'][t]), 'breaks': int(seq['breaks'][t]), 'changed': int((index[t] != own[t]).sum())}
+        for key in ('torso', 'pd_peaks', 'pose_index'):
+            del r['maps'][key]
 
 
 # ------------------------------------------------------------------ zoomed clips (DESIGN.md 4.24)

@@ -51,7 +51,7 @@ def _coords_to_points(coords):
 
 
 def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1, batch_size=16, pad=0, timing=None, zoom=False, keep_maps=False,
-                   torso_prob=False, keep_frames=False):
+                   torso_prob=False, keep_frames=False, keep_peaks=False):
     """images: a list of uint8 [h,w,3] arrays or tensors of mixed sizes (what Engine.fit_images takes).  They are fitted and run through
     engine.forward(x_u8, torso='infer' if use_sm else None, use_sm=use_sm, peaks=peaks, decode=decode, people=people) batch_size at a time.
     Returns one dict per image, everything in the image's own pixels (row, col), host numpy:
@@ -72,6 +72,9 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
         spatial_softmax of the torso energy E -- the map predict_sequence_people tracks torsos through.
       with keep_frames (needs keep_maps; every key above keeps its value): 'maps' also holds 'frame', device uint8 [480,720,3], the fitted byte
         frame the tower read, a view of the batch -- what Engine.frame_shift estimates the camera's motion from.
+      with keep_peaks (needs keep_maps, use_sm, decode and people == 1; every key above keeps its value): 'maps' also holds 'torso', device float32
+        [60,90,1], the inferred torso map, 'pd_peaks' = {'cells' int32 [K,P,2], 'count' int32 [K]} and 'pose_index' int32 [K], views of the batch's
+        device results -- what the clip decode builds its tables from.
     timing: a dict that receives 'fit_ms' and 'forward_ms', device-event times summed over the batches (the upload of host images is part of
     neither), and with zoom 'zoom_fit_ms' and 'zoom_forward_ms', those of the second pass."""
     if not isinstance(images, (list, tuple)) or len(images) == 0:
@@ -84,6 +87,8 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
         raise ValueError('torso_prob=True needs keep_maps=True and use_sm=True: the map is kept in \'maps\' and comes from the inferred torso')
     if keep_frames and not keep_maps:
         raise ValueError('keep_frames=True needs keep_maps=True: the fitted frame is kept in \'maps\'')
+    if keep_peaks and not (keep_maps and use_sm and decode and people == 1):
+        raise ValueError('keep_peaks=True needs keep_maps=True, use_sm=True, decode=True and people=1: the candidates and the torso map are kept in \'maps\'')
     names = list(JOINT_NAMES[:engine.n_joints])
     out = []
     ms, zoom_ms = {'fit_ms': 0.0, 'forward_ms': 0.0}, [0.0, 0.0]
@@ -106,6 +111,8 @@ def predict_images(engine, images, use_sm=True, peaks=0, decode=False, people=1,
                         e['maps']['torso_prob'] = r['torso_prob'][b]
                     if keep_frames:
                         e['maps']['frame'] = x[b]
+                    if keep_peaks:
+                        e['maps'].update(torso=r['torso'][b], pd_peaks={f: r['pd_peaks'][f][b] for f in ('cells', 'count')}, pose_index=r['pose']['index'][b])
             if zoom:
                 _zoom_pass(engine, batch, res, people, int(batch_size), pad, zoom_ms)
             out.extend(res)

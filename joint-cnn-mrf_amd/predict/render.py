@@ -26,7 +26,7 @@ def _skeletons(r, which, zoom):
     if which == 'track' and 'tracks' in r:
         p = r['tracks']
         return [(p['points'][m], p['inside'][m]) for m in range(len(p['present'])) if p['present'][m]]
-    if which in ('track', 'track_zoom'):
+    if which in ('track', 'track_zoom', 'track_pose'):
         return [(r[which]['points'], r[which]['inside'])]
     if zoom and 'zoom' in r:
         return [(e[which], e[which + '_inside']) for e in r['zoom']]
@@ -43,12 +43,12 @@ def skeleton_primitives(results, which='sm', zoom=True):
     colour of the second joint, alpha 192; the neck exists when both shoulders do), then a disc per inside joint (radius 2 rl, alpha 255).
     which: 'sm' or 'pd', whose joints are drawn, 'track_zoom', the joints predict_sequence_zoom tracked through the windows, or 'track', the tracked joints of predict_sequence (one skeleton per present track of predict_sequence_people); with 'people' in a result one skeleton per counted slot ('sm' only); with zoom=True and 'zoom'
     in a result, one skeleton per entry of it, a zoomed person's from the second pass."""
-    if which not in ('sm', 'pd', 'track', 'track_zoom'):
-        raise ValueError("which must be 'sm', 'pd', 'track' or 'track_zoom', got %r" % (which,))
+    if which not in ('sm', 'pd', 'track', 'track_zoom', 'track_pose'):      # 'track_pose': the clip decode of predict_sequence(pose=P), DESIGN.md 4.30
+        raise ValueError("which must be 'sm', 'pd', 'track', 'track_zoom' or 'track_pose', got %r" % (which,))
     rows = []
     for i, r in enumerate(results):
         if which not in r:
-            raise ValueError("results[%d] has no %r joints (%s makes them)" % (i, which, {'track': 'predict_sequence', 'track_zoom': 'predict_sequence_zoom'}.get(which, 'predict_images(use_sm=%s)' % (which == 'sm'))))
+            raise ValueError("results[%d] has no %r joints (%s makes them)" % (i, which, {'track': 'predict_sequence', 'track_zoom': 'predict_sequence_zoom', 'track_pose': 'predict_sequence(pose=P)'}.get(which, 'predict_images(use_sm=%s)' % (which == 'sm'))))
         rl = max(16, 2 * (int(r['size'][0]) + int(r['size'][1])) // 75)
         for joints, inside in _skeletons(r, which, zoom):
             K = len(inside)
