@@ -1,6 +1,6 @@
 """The motion model of the sequence stages: a joint moves by a truncated Gaussian step per frame, in heat-map cells, or -- with
 mass rho -- jumps anywhere.  Host arithmetic in float64, numpy only: the constants, the taps the library takes (seq_taps), the per-mode keys of what
-the scans return (SEQ_KEYS) and the EM fit of sigma and rho to a clip's own maps (seq_fit; the engine is an argument).  engine.py and the
+the scans return (SEQ_KEYS) and the EM fit of sigma and rho to a clip's own maps (seq_fit; the engine is an argument).  engine/sequence.py and the
 prediction modules both read this module; it imports neither."""
 import numpy as np
 
